@@ -16,14 +16,21 @@ Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL).  On the
 is weak (every rank steps --bodies bodies).  The `contacts` sub-results are the north-star workload (body-body
 contacts: the EXTENSION, parity unpinned).
 
-ONE JSON line on rank 0:
+ONE JSON line on rank 0.  A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, pre-rolls, warms up, times the
+K frames and prints the headline (metric, value, unit, ms_per_step, ...) with
   roofline      the dominant kernel (k_step) at the algorithmic 412 B per body per launch against the
-                8 TB/s HBM peak, plus `peak_measured` = a device-to-device copy by the library's own streaming kernel
-                in this run, and `frac_of_measured`
+                8 TB/s HBM peak, from the timed frames themselves
+--full adds everything that takes runs of its own:
+  roofline      + `peak_measured` = a device-to-device copy by the library's own streaming kernel in this run, and
+                `frac_of_measured`; roofline_unfused, roofline_hbm_resident, pcie_inclusive, render_readback
   cpu_baseline  the CPU oracle (C restatement of the reference, single thread like the reference) on a bounded sample
                 of the SAME pre-rolled state, median of 3 repeats
   contacts      {name: {...}} box stacks with SAT contacts (262 144 x 20) and 65 536 mixed polyhedra on the GJK/EPA
                 path, each with its own value, roofline (whole-substep byte model) and cpu_baseline (op_contacts_step)
+  north_star    the headline and the contacts sub-results once more, short
+
+--dump-outputs DIR writes what the timed path computed in its last frame -- the bodies' dynamic state and the ground
+contacts of the last substep, what a caller downloads -- as DIR/<name>.npy (float64), see dump_outputs().
 """
 import argparse
 import json
@@ -86,6 +93,38 @@ def timed_frames(step, stream, steps):
     barrier()
     wall = reduce_max_seconds(time.perf_counter() - t0)
     return wall, ev0.elapsed_time(ev1)
+
+
+# What one frame writes per body (the 13 doubles of SURVEY 8d; the other 25 of the 38 are inputs the step never changes)
+DUMP_FIELDS = ("position", "rotation", "velocity", "angular_velocity")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(np, out_dir, bodies, contacts=None, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the outputs of the timed path's last frame as out_dir/<name>.npy, float64.
+    bodies: (n, 38) rigid records as downloaded; each field of DUMP_FIELDS becomes <field>.npy (n, k).
+    contacts: (m, 2) (body, vertex) ground contacts of the last substep -> contacts.npy (exact in float64).
+    Above `limit` bytes in all, a fixed, seeded sample of the bodies is written instead (body_index.npy names the rows)
+    with the contacts of those bodies, the contacts cut to what still fits."""
+    from constraint_solver_amd import capi
+    n = bodies.shape[0]
+    fields = {f: bodies[:, capi.RIGID_FIELDS[f][0]: capi.RIGID_FIELDS[f][0] + capi.RIGID_FIELDS[f][1]] for f in DUMP_FIELDS}
+    out = dict(fields)
+    if contacts is not None:
+        out["contacts"] = np.asarray(contacts, dtype=np.float64).reshape(-1, 2)
+    total = sum(a.size * 8 for a in out.values())
+    if total > limit:
+        rows = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * 0.9 * limit / total)), replace=False))
+        out = {f: a[rows] for f, a in fields.items()}
+        out["body_index"] = rows.astype(np.float64)
+        if contacts is not None:
+            c = np.asarray(contacts, dtype=np.float64).reshape(-1, 2)
+            c = c[np.isin(c[:, 0], out["body_index"])]
+            room = (limit - sum(a.size * 8 for a in out.values())) // 16
+            out["contacts"] = c[: max(room, 0)]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def median_rate(run, units, repeats=3):
@@ -247,16 +286,17 @@ def sample_of(np, total, layers, sample):
 
 
 def run_contacts(capi, np, torch, args, scene, bodies, narrowphase, joints_n, pitch, rank, local_rank, world_size, steps, warmup,
-                 with_cpu, layers=0, name=None, depenetration=0.0, preroll=None):
+                 with_cpu, layers=0, name=None, depenetration=0.0, preroll=None, dump=None):
     """One contact-pipeline measurement on a world of its own: pre-roll, warm-up, K timed frames.  Returns the result
-    object (rank 0) -- value, roofline of a whole substep, cpu_baseline -- or None."""
+    object (rank 0) -- value, roofline of a whole substep, cpu_baseline -- or None.  dump: directory for dump_outputs()."""
     kind = getattr(capi, SCENE_KIND[scene])
     total = bodies * world_size
     pad = 0.02
     preroll = preroll or (PREROLL_PILE if layers else PREROLL[scene])
     if world_size > 1 or args.local_shards:
         return run_contacts_sharded(capi, np, torch, args, scene, kind, bodies, narrowphase, joints_n, pitch, layers, preroll, rank,
-                                    local_rank, world_size, steps, warmup, local_shards=args.local_shards, depenetration=depenetration)
+                                    local_rank, world_size, steps, warmup, local_shards=args.local_shards, depenetration=depenetration,
+                                    dump=dump)
     count = total
     state, shape_id = contacts_scene(capi, args, kind, total, pitch, layers)
     world = capi.World(device=local_rank, mode=capi.MODE_CONTACTS)
@@ -327,6 +367,8 @@ def run_contacts(capi, np, torch, args, scene, bodies, narrowphase, joints_n, pi
                                  "bound, the per-body kernel bandwidth bound; per-kernel times in profiles/)"},
             "cpu_baseline": None,
         }
+        if dump:
+            dump_outputs(np, dump, end_state, world.contacts())
         if with_cpu:
             pick, what = sample_of(np, total, layers, 4096)
             result["cpu_baseline"] = cpu_baseline_contacts(start_state, shape_id, POLY_NAMES["mixed" in scene], args.substeps, pad,
@@ -336,7 +378,7 @@ def run_contacts(capi, np, torch, args, scene, bodies, narrowphase, joints_n, pi
 
 
 def run_contacts_sharded(capi, np, torch, args, scene, kind, bodies, narrowphase, joints_n, pitch, layers, preroll, rank, local_rank,
-                         world_size, steps, warmup, local_shards=0, depenetration=0.0):
+                         world_size, steps, warmup, local_shards=0, depenetration=0.0, dump=None):
     """EXTENSION, N > 1: body-body contacts through the NATIVE multi-GPU world (xpbd_multi_world_*, csrc/xpbd_multi.cpp):
     every rank hands over its index slice of the scene (generating ONLY those bodies); the library cuts the shards -- slabs
     of space across the world's longest axis, near-equal body counts, re-balanced at every re-plan -- moves each body to
@@ -428,6 +470,10 @@ def run_contacts_sharded(capi, np, torch, args, scene, kind, bodies, narrowphase
                               "kernel": "one substep of one rank: integrate + ground, narrowphase, pair solve, halo export / "
                                         "all-gather / import", "launch_us": substep_s * 1e6, "bytes_per_launch": substep_bytes,
                               "note": "per-GPU figure from wall time (the exchange is inside it); byte model of DESIGN.md 8"}
+    if dump:
+        state = world.download()                                   # collective with more than one process: every rank
+        if rank == 0:                                              # (rank 0's slice of the world)
+            dump_outputs(np, dump, state)
     world.close()
     return result
 
@@ -476,6 +522,12 @@ def main():
                     help="contacts = EXTENSION (body-body contacts; not in the reference, parity unpinned)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--block-size", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, in runs of their own: CPU baselines, the measured HBM "
+                         "roof, the per-substep and HBM-resident rooflines, PCIe-inclusive and read-back rates, the contacts "
+                         "sub-results and north_star (a plain run: set-up, warm-up, the timed frames, the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the timed path computed in its last frame to DIR/<name>.npy (float64; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the informational extra measurements (unfused roofline, HBM-resident size, PCIe-inclusive)")
@@ -509,6 +561,8 @@ def main():
     ap.add_argument("--contacts-child", action="store_true", help=argparse.SUPPRESS)   # N > 1: see contacts_in_child_processes
     ap.add_argument("--force-contacts", action="store_true", help=argparse.SUPPRESS)   # rehearsal of the child's failure path
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -545,7 +599,7 @@ def main():
     stream = torch.cuda.Stream()
     torch.cuda.set_stream(stream)
     assert stream.cuda_stream != 0
-    with_cpu = world_size == 1 and not args.no_cpu_baseline and not args.only
+    with_cpu = world_size == 1 and args.full and not args.no_cpu_baseline and not args.only
 
     # the contacts sub-results of the default line: the north-star workloads (BASELINE.json configs[3] size with SAT
     # box stacks; configs[2]: 65 536 mixed convex polyhedra on the GJK/EPA path)
@@ -581,7 +635,7 @@ def main():
         if args.only not in sub_runs:
             raise SystemExit("--only: one of pinned, %s" % ", ".join(sub_runs))
         r = run_contacts(capi, np, torch, args, rank=rank, local_rank=local_rank, world_size=world_size, steps=args.steps,
-                         warmup=args.warmup, with_cpu=False, name=args.only, **sub_runs[args.only])
+                         warmup=args.warmup, with_cpu=False, name=args.only, dump=args.dump_outputs, **sub_runs[args.only])
         if rank == 0:
             print(json.dumps({"metric": METRIC, "n_gpus": world_size, **r}), flush=True)
         barrier()
@@ -591,7 +645,8 @@ def main():
 
     if args.mode == "contacts":
         r = run_contacts(capi, np, torch, args, args.scene, args.bodies, args.narrowphase, args.joints, args.pitch, rank, local_rank,
-                         world_size, args.steps, args.warmup, with_cpu, layers=args.layers, depenetration=args.max_depenetration_speed)
+                         world_size, args.steps, args.warmup, with_cpu, layers=args.layers, depenetration=args.max_depenetration_speed,
+                         dump=args.dump_outputs)
         result = None
         if rank == 0:
             result = {"metric": METRIC, "value": r["value"], "unit": UNIT, "n_gpus": world_size, "steps": args.steps,
@@ -632,6 +687,8 @@ def main():
     for _ in range(args.warmup):
         world.step(FRAME_TIME, args.substeps)
     wall, device_ms = timed_frames(lambda: world.step(FRAME_TIME, args.substeps), stream, args.steps)
+    if args.dump_outputs and rank == 0:                  # (rank 0's shard), before anything else steps this world
+        dump_outputs(np, args.dump_outputs, world.download(), world.contacts())
 
     result = None
     if rank == 0:
@@ -684,7 +741,7 @@ def main():
                                                   "insts_per_wave_substep": d.get("valu_insts_per_wave_substep"),
                                                   "source": os.path.relpath(f, ROOT)}
                     break
-        extras = world_size == 1 and not args.no_extras and not args.only
+        extras = world_size == 1 and args.full and not args.no_extras and not args.only
         if extras:
             # The HBM roof as measured in THIS run: device-to-device copy of 2 GiB (8x the 256 MiB Infinity Cache) by the
             # library's own streaming kernel ("HBM_peak both nominal and measured").
@@ -771,7 +828,7 @@ def main():
     world.close()
 
     # ---------------------------------------------------------------- the north-star workloads (extension)
-    if not args.no_contacts and not args.only and mode == capi.MODE_FUSED:
+    if args.full and not args.no_contacts and not args.only and mode == capi.MODE_FUSED:
         if world_size > 1:
             subs = contacts_in_child_processes(args, rank)
         else:
@@ -784,7 +841,7 @@ def main():
                     subs[name] = {"error": str(e)}
         if rank == 0:
             result["contacts"] = subs
-    if rank == 0:
+    if rank == 0 and args.full:
         # The north-star numbers once more, short and LAST on the line (a long line is kept from its tail): body.substeps/s of
         # the workloads BASELINE.json names -- box stacks with SAT contacts, mixed convex polyhedra on GJK/EPA, bodies + joints --
         # with the fraction of the 8 TB/s HBM roof at SURVEY.md 8(d)'s algorithmic bytes, next to the pinned headline.
@@ -809,6 +866,7 @@ def main():
             "mixed_sat": brief("mixed_pile_65536_sat"), "joints": brief("boxes_262144_joints_65536"),
             "cpu_1_thread": (result.get("cpu_baseline") or {}).get("value"),
         }
+    if rank == 0:
         print(json.dumps(result), flush=True)
     barrier()
     if world_size > 1:

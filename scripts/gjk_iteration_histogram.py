@@ -1,5 +1,6 @@
-import sys, numpy as np
-sys.path[:0]=['/root/repo','/root/repo/tests']
+import os, sys, numpy as np
+ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0]=[ROOT,os.path.join(ROOT,'tests')]
 from constraint_solver_amd import capi
 for name,kind,pitch in (("mixed pile",capi.SCENE_MIXED_DROP,1.4),("boxes pile",capi.SCENE_BOXES_DROP,1.8)):
     n=65536

@@ -34,7 +34,7 @@ pmc_cmd() { # name, counter, command...   (a counter pass over another program: 
 }
 
 if has bench; then
-  timeout -k 10 600 $B > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 600 $B --full > "$OUT/bench.json" 2> "$OUT/bench.err"   # the whole line: summary.json reads its sub-results
 fi
 if has trace; then
   trace pinned --only pinned
