@@ -26,19 +26,17 @@ struct HaloLists {
 struct xpbd_world;
 
 namespace xpbd {
-// frame:   halo_frame_begin; substeps x { halo_substep_boundary; <all-gather send -> recv, overlapping:> halo_substep_interior;
-//          <wait for the gather> halo_substep_ghosts }
-// begin:    the broadphase of the frame and the integrate + ground stage of substep 0 for every local body
+// frame:   halo_frame_begin_enqueue; halo_frame_begin_collect; substeps x { halo_substep_boundary; <all-gather send -> recv,
+//          overlapping:> halo_substep_interior; <wait for the gather> halo_substep_ghosts }
+// begin:    the broadphase of the frame and the integrate + ground stage of substep 0 for every local body, in two halves
+//           (enqueue = bounding spheres, buckets, neighbour counts, the totals on their way to pinned host memory, no wait;
+//           collect = wait for the totals, size the pair buffers, fill the lists, integrate + ground stage of substep 0)
 // boundary: the narrowphase of substep k, then the pair solve (+ the integrate + ground stage of substep k + 1 unless `last`)
 //           of the BOUNDARY bodies, whose end-of-substep state goes straight into `send`
 // interior: the same for the owned bodies nobody mirrors
 // ghosts:   the ghosts take their owners' end-of-substep state from `recv` (and run their own integrate + ground stage of
 //           substep k + 1 unless `last`)
 // Same arithmetic per body as xpbd_world_step, so the same bits.
-int halo_frame_begin(xpbd_world *w, double dt, double h);
-// ... in two halves, so that a host driving several shards enqueues the broadphase of ALL of them before it waits for any:
-// enqueue = bounding spheres, buckets, neighbour counts, the totals on their way to pinned host memory (no wait);
-// collect = wait for the totals, size the pair buffers, fill the lists, integrate + ground stage of substep 0.
 int halo_frame_begin_enqueue(xpbd_world *w, double dt);
 int halo_frame_begin_collect(xpbd_world *w, double h);
 // The state a frame starts from (13 dynamic fields per body + last contact masks) kept aside on the device / put back:

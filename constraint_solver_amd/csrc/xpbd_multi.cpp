@@ -18,8 +18,9 @@
 // body before the next plan, in ascending GLOBAL id (the caller's numbering) -- so every neighbour list and every
 // floating-point sum has the order of the single-device run and the result is that run's, bit for bit.  Per substep:
 //     narrowphase -> boundary bodies (their end-of-substep state straight into the send buffer) -> ONE all-gather (RCCL over
-//     xGMI: ncclAllGather, all local shards in one group call) on a communication stream, overlapping the interior bodies ->
-//     the ghosts take their owners' state from the gathered buffer.
+//     xGMI: ncclAllGather) on a communication stream, overlapping the interior bodies -> the ghosts take their owners' state
+//     from the gathered buffer.
+// One function enqueues a shard's frame (shard_frame), from one host thread per local shard.
 // The plan (who owns, who mirrors whom) is built HERE, in C++, from the shards' own bodies plus a handful of small
 // all-gathers (cell keys or rims, boundary lists, the records of migrating and boundary bodies); no rank holds the global scene.
 // Every plan-time all-gather carries a status word per rank and so does the frame's last one, so a rank that fails locally
@@ -627,6 +628,11 @@ struct Shard {
     DevBuf boundary_slots, ghost_slots, ghost_rows, owned_slots, skip_flags, disp_scale, send, recv, snapshot, disp, disp_all, stage_send, stage_recv;
     double *disp_host = nullptr;   // pinned, n_ranks x {largest squared fraction of an allowance used, status}
     double *status_host = nullptr; // pinned, this process's status of the frame
+    xpbd::HaloLists lists() const
+    {
+        return xpbd::HaloLists{boundary_slots.as<uint32_t>(), (uint32_t)boundary.size(), ghost_slots.as<uint32_t>(), ghost_rows.as<uint32_t>(),
+                               (uint32_t)ghosts.size(), skip_flags.as<uint8_t>(), send.as<double>(), recv.as<double>()};
+    }
 };
 
 // One host thread per local shard (a process that owns several GPUs): a frame is ~20 runtime calls per shard and substep, and
@@ -652,11 +658,26 @@ struct Barrier {
     }
 };
 
-struct ShardJob {
-    int rc = XPBD_OK;           // first local error of the shard's frame (LocalStatus)
+// The first local error of a collective operation (a plan, a frame).  The operation goes on taking part in its collectives
+// -- with whatever payload -- so that the ranks stay in step, and every collective carries each rank's status: all ranks
+// leave the operation with an error at the same point.
+struct LocalStatus {
+    int rc = XPBD_OK;
     std::string message;
-    int fatal = XPBD_OK;        // a collective could not be enqueued
-    std::string fatal_message;
+    void keep(int r)
+    {
+        if (rc == XPBD_OK && r != XPBD_OK) {
+            rc = r;
+            message = xpbd_last_error();
+        }
+    }
+    bool ok() const { return rc == XPBD_OK; }
+    int report() const { return set_error(rc, "%s", message.c_str()); }
+};
+
+struct ShardJob {
+    LocalStatus st;    // first local error of the shard's frame
+    LocalStatus fatal; // first collective that could not be enqueued
     uint64_t ns_wait_broadphase = 0;
 };
 
@@ -738,31 +759,62 @@ int transport_broken(xpbd_multi_world *mw, int rc)
     return set_error(rc, "%s -- the communicator is unusable now: destroy this xpbd_multi_world on every rank", msg.c_str());
 }
 
-// One all-gather over all ranks: every local shard contributes `bytes` from its `send` and receives n_ranks x bytes into its
-// `recv` (device pointers, picked per shard by the callbacks), ordered on the shards' streams.
-// `on_comm_stream`: enqueue on the shards' communication streams (the caller orders them against the world streams with
-// events) instead of the world streams.
-template <class Send, class Recv>
-int all_gather_device_raw(xpbd_multi_world *mw, size_t bytes, Send send_of, Recv recv_of, bool on_comm_stream)
+// ---- one all-gather over all ranks: every shard contributes `bytes` of its buffer `send` and receives n_ranks x bytes, row
+// r from rank r, into its buffer `recv`.  Written per shard: all_gather_device_raw drives every local shard from one thread,
+// shard_frame drives one shard from that shard's thread.
+
+// RCCL: shard s's part of the collective, on `stream`.
+int rccl_all_gather(xpbd_multi_world *mw, Shard &s, const void *send, void *recv, size_t bytes, hipStream_t stream)
 {
-    auto stream_of = [on_comm_stream](Shard &s) { return on_comm_stream ? s.comm_stream : s.stream; };
+    // RCCL reads the thread's last HIP error after its own calls: a stale, harmless one left by somebody else in the
+    // process (hipErrorNotReady from an event query, say) would be reported as "unhandled cuda error"
+    (void)hipGetLastError();
+    const ncclResult_t r = mw->rccl->AllGather(send, recv, bytes, ncclChar, s.comm, stream);
+    return r == ncclSuccess ? XPBD_OK : nccl_fail(mw, r, "ncclAllGather");
+}
+
+// XPBD_TRANSPORT_LOCAL (every rank lives in this process): peer copies ordered by events, in three phases.  Every shard's
+// phase must have been enqueued before any shard enters the next one: a stream can only wait for an event already RECORDED.
+// 1. my send buffer is ready
+int local_send(Shard &s, hipStream_t stream)
+{
+    MW_HIP_TRY(hipEventRecord(s.ev_send, stream));
+    return XPBD_OK;
+}
+
+// 2. wait for the peers' send events, copy every rank's row into my `recv`, record my receive event
+int local_copy(xpbd_multi_world *mw, Shard &s, DevBuf Shard::*send, void *recv, size_t bytes, hipStream_t stream)
+{
+    for (Shard &p : mw->shards) {
+        if (&p != &s)
+            MW_HIP_TRY(hipStreamWaitEvent(stream, p.ev_send, 0));
+        MW_HIP_TRY(hipMemcpyAsync(static_cast<char *>(recv) + (size_t)p.rank * bytes, (p.*send).ptr, bytes, hipMemcpyDefault, stream));
+    }
+    MW_HIP_TRY(hipEventRecord(s.ev_recv, stream));
+    return XPBD_OK;
+}
+
+// 3. wait for the peers' receive events: nobody overwrites its send buffer before every peer has read it
+int local_release(xpbd_multi_world *mw, Shard &s, hipStream_t stream)
+{
+    for (Shard &p : mw->shards)
+        if (&p != &s)
+            MW_HIP_TRY(hipStreamWaitEvent(stream, p.ev_recv, 0));
+    return XPBD_OK;
+}
+
+// The all-gather of every local shard from this thread, on the shards' world streams (RCCL: in one group call).
+int all_gather_device_raw(xpbd_multi_world *mw, size_t bytes, DevBuf Shard::*send, DevBuf Shard::*recv)
+{
     if (mw->transport == XPBD_TRANSPORT_RCCL) {
-        // RCCL reads the thread's last HIP error after its own calls: a stale, harmless one left by somebody else in the
-        // process (hipErrorNotReady from an event query, say) would be reported as "unhandled cuda error"
-        (void)hipGetLastError();
+        (void)hipGetLastError(); // see rccl_all_gather
         ncclResult_t r = mw->rccl->GroupStart();
         if (r != ncclSuccess)
             return nccl_fail(mw, r, "ncclGroupStart");
         int rc = XPBD_OK;
-        for (Shard &s : mw->shards) {
-            if ((rc = bind(s)) != XPBD_OK)
+        for (Shard &s : mw->shards)
+            if ((rc = bind(s)) != XPBD_OK || (rc = rccl_all_gather(mw, s, (s.*send).ptr, (s.*recv).ptr, bytes, s.stream)) != XPBD_OK)
                 break;
-            r = mw->rccl->AllGather(send_of(s), recv_of(s), bytes, ncclChar, s.comm, stream_of(s));
-            if (r != ncclSuccess) {
-                rc = nccl_fail(mw, r, "ncclAllGather");
-                break;
-            }
-        }
         r = mw->rccl->GroupEnd(); // the group is closed whatever happened inside it
         if (rc != XPBD_OK)
             return rc;
@@ -770,53 +822,27 @@ int all_gather_device_raw(xpbd_multi_world *mw, size_t bytes, Send send_of, Recv
             return nccl_fail(mw, r, "ncclGroupEnd");
         return XPBD_OK;
     }
-    // XPBD_TRANSPORT_LOCAL: every rank lives in this process; peer copies ordered by events
-    for (Shard &p : mw->shards) {
-        MW_TRY(bind(p));
-        MW_HIP_TRY(hipEventRecord(p.ev_send, stream_of(p)));
+    for (Shard &s : mw->shards) {
+        MW_TRY(bind(s));
+        MW_TRY(local_send(s, s.stream));
     }
-    for (Shard &r : mw->shards) {
-        MW_TRY(bind(r));
-        for (Shard &p : mw->shards) {
-            if (&p != &r)
-                MW_HIP_TRY(hipStreamWaitEvent(stream_of(r), p.ev_send, 0));
-            MW_HIP_TRY(hipMemcpyAsync(static_cast<char *>(recv_of(r)) + (size_t)p.rank * bytes, send_of(p), bytes, hipMemcpyDefault, stream_of(r)));
-        }
-        MW_HIP_TRY(hipEventRecord(r.ev_recv, stream_of(r)));
+    for (Shard &s : mw->shards) {
+        MW_TRY(bind(s));
+        MW_TRY(local_copy(mw, s, send, (s.*recv).ptr, bytes, s.stream));
     }
-    for (Shard &p : mw->shards) { // nobody overwrites its send buffer before every peer has read it
-        MW_TRY(bind(p));
-        for (Shard &r : mw->shards)
-            if (&p != &r)
-                MW_HIP_TRY(hipStreamWaitEvent(stream_of(p), r.ev_recv, 0));
+    for (Shard &s : mw->shards) {
+        MW_TRY(bind(s));
+        MW_TRY(local_release(mw, s, s.stream));
     }
     return XPBD_OK;
 }
 
-template <class Send, class Recv>
-int all_gather_device(xpbd_multi_world *mw, size_t bytes, Send send_of, Recv recv_of, bool on_comm_stream = false)
+int all_gather_device(xpbd_multi_world *mw, size_t bytes, DevBuf Shard::*send, DevBuf Shard::*recv)
 {
-    if (int rc = all_gather_device_raw(mw, bytes, send_of, recv_of, on_comm_stream))
+    if (int rc = all_gather_device_raw(mw, bytes, send, recv))
         return transport_broken(mw, rc);
     return XPBD_OK;
 }
-
-// The first local error of a collective operation (a plan, a frame).  The operation goes on taking part in its collectives
-// -- with whatever payload -- so that the ranks stay in step, and every collective carries each rank's status: all ranks
-// leave the operation with an error at the same point.
-struct LocalStatus {
-    int rc = XPBD_OK;
-    std::string message;
-    void keep(int r)
-    {
-        if (rc == XPBD_OK && r != XPBD_OK) {
-            rc = r;
-            message = xpbd_last_error();
-        }
-    }
-    bool ok() const { return rc == XPBD_OK; }
-    int report() const { return set_error(rc, "%s", message.c_str()); }
-};
 
 // Plan-time all-gather of host data: send[k] = `bytes` of local shard k; out = the n_ranks x bytes everybody ends up with.
 // Every row is preceded by the sender's status; if any rank reports an error, every rank returns one.
@@ -852,7 +878,7 @@ int all_gather_host(xpbd_multi_world *mw, const std::vector<const void *> &send,
         };
         if ((rc = stage()) != XPBD_OK) // the staging buffers are the transport's: without them this rank cannot take part
             return transport_broken(mw, rc);
-        MW_TRY(all_gather_device(mw, row, [](Shard &s) { return s.stage_send.ptr; }, [](Shard &s) { return s.stage_recv.ptr; }));
+        MW_TRY(all_gather_device(mw, row, &Shard::stage_send, &Shard::stage_recv));
         auto collect = [&]() -> int {
             for (Shard &s : mw->shards) { // every shard takes part in the collective; the content is the same everywhere
                 MW_TRY(bind(s));
@@ -1646,152 +1672,39 @@ int replan(xpbd_multi_world *mw)
     return make_plan(mw, st);
 }
 
-// Enqueues one whole frame on every local shard and, behind it, the end-of-frame exchange: per rank the largest fraction of
-// its travel allowance any owned body has used since the plan (squared) and the rank's status.  Local errors are kept in
-// `st` (the remaining local launches are skipped, the collectives still run); only a failing collective returns at once.
-int enqueue_frame(xpbd_multi_world *mw, double dt, uint32_t substeps, LocalStatus &st)
-{
-    const bool multi = mw->n_ranks > 1;
-    const double h = dt / (double)substeps; // src/solver.rs:4
-    const uint64_t t0 = now_ns();
-    if (multi)
-        for (Shard &s : mw->shards)
-            if (st.ok())
-                st.keep(xpbd::frame_snapshot_save(s.world));
-    // the broadphase of ALL shards is on its way before the host waits for any of them
-    for (Shard &s : mw->shards)
-        if (st.ok())
-            st.keep(xpbd::halo_frame_begin_enqueue(s.world, dt));
-    const uint64_t t1 = now_ns();
-    for (Shard &s : mw->shards)
-        if (st.ok())
-            st.keep(xpbd::halo_frame_begin_collect(s.world, h));
-    const uint64_t t2 = now_ns();
-    mw->ns_wait_broadphase += t2 - t1;
-    const size_t bytes = (size_t)mw->rows_per_rank() * kDyn * 8;
-    auto lists_of = [](Shard &s) {
-        return xpbd::HaloLists{s.boundary_slots.as<uint32_t>(), (uint32_t)s.boundary.size(), s.ghost_slots.as<uint32_t>(), s.ghost_rows.as<uint32_t>(),
-                               (uint32_t)s.ghosts.size(), s.skip_flags.as<uint8_t>(), s.send.as<double>(), s.recv.as<double>()};
-    };
-    auto hip_keep = [&st](hipError_t e, const char *what) {
-        if (e != hipSuccess)
-            st.keep(set_error(XPBD_E_HIP, "%s failed: %s", what, hipGetErrorString(e)));
-    };
-    for (uint32_t k = 0; k < substeps; ++k) {
-        const bool last = k + 1 == substeps;
-        // 1. the narrowphase, then the boundary bodies: their end-of-substep state lands in the send buffer
-        for (Shard &s : mw->shards) {
-            if (st.ok())
-                st.keep(xpbd::halo_substep_boundary(s.world, h, k, last, lists_of(s)));
-            if (multi) {
-                st.keep(bind(s));
-                hip_keep(hipEventRecord(s.ev_ready, s.stream), "hipEventRecord");
-                hip_keep(hipStreamWaitEvent(s.comm_stream, s.ev_ready, 0), "hipStreamWaitEvent");
-            }
-        }
-        // 2. ONE all-gather per substep on the communication streams ...
-        if (multi) {
-            MW_TRY(all_gather_device(mw, bytes, [](Shard &s) { return s.send.ptr; }, [](Shard &s) { return s.recv.ptr; }, true));
-            for (Shard &s : mw->shards) {
-                st.keep(bind(s));
-                hip_keep(hipEventRecord(s.ev_gathered, s.comm_stream), "hipEventRecord");
-            }
-        }
-        // 3. ... while the interior bodies (nobody mirrors them) run on the world streams
-        for (Shard &s : mw->shards)
-            if (st.ok())
-                st.keep(xpbd::halo_substep_interior(s.world, h, k, last, lists_of(s)));
-        // 4. the ghosts take their owners' state from the gathered buffer
-        if (multi)
-            for (Shard &s : mw->shards) {
-                st.keep(bind(s));
-                hip_keep(hipStreamWaitEvent(s.stream, s.ev_gathered, 0), "hipStreamWaitEvent");
-                if (st.ok())
-                    st.keep(xpbd::halo_substep_ghosts(s.world, h, k, last, lists_of(s)));
-                // the next substep's boundary launch rewrites the send buffer: not before this exchange has read it
-                // (the communication stream is in order, so waiting for ev_gathered above covers the own copy; the peers'
-                // reads of OUR buffer are ordered by the transport: RCCL completes the collective, the in-process
-                // transport makes the communication streams wait for every peer's ev_recv)
-            }
-    }
-    if (multi) {
-        // halo validity of THIS frame and the ranks' status, agreed on by all ranks
-        for (Shard &s : mw->shards) {
-            st.keep(bind(s));
-            hip_keep(hipMemsetAsync(s.disp.ptr, 0, 16, s.stream), "hipMemsetAsync");
-            if (st.ok())
-                st.keep(xpbd_world_max_displacement2(s.world, s.owned_slots.as<uint32_t>(), (uint32_t)s.held_ids.size(), s.snapshot.as<double>(),
-                                                     s.disp_scale.as<double>(), s.disp.as<double>()));
-        }
-        for (Shard &s : mw->shards) { // (after the last local launch that could still fail)
-            (void)hipSetDevice(s.device);
-            *s.status_host = (double)st.rc;
-            hip_keep(hipMemcpyAsync(s.disp.as<double>() + 1, s.status_host, 8, hipMemcpyHostToDevice, s.stream), "hipMemcpyAsync");
-        }
-        MW_TRY(all_gather_device(mw, 16, [](Shard &s) { return s.disp.ptr; }, [](Shard &s) { return s.disp_all.ptr; }));
-        for (Shard &s : mw->shards) {
-            (void)hipSetDevice(s.device);
-            hip_keep(hipMemcpyAsync(s.disp_host, s.disp_all.ptr, (size_t)mw->n_ranks * 16, hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync");
-        }
-    }
-    mw->ns_enqueue += (now_ns() - t0) - (t2 - t1);
-    return XPBD_OK;
-}
-
-// ---- the same frame with one enqueueing thread per local shard -----------------------------------------------------------------
-// What thread k does for shard k is what enqueue_frame does for it, in the same order on the same streams; the collectives:
-//   RCCL   each thread calls ncclAllGather on its own communicator (one thread per device, no group call);
-//   local  record my send event | BARRIER | wait for the peers' send events, copy their rows, record my receive event |
-//          BARRIER | wait for the peers' receive events (nobody overwrites a send buffer that is still being read).
-// Every thread passes every barrier whatever went wrong (errors only skip the runtime calls), so nobody is left waiting.
+// One frame of local shard k and, behind it, the end-of-frame exchange: per rank the largest fraction of its travel allowance
+// any owned body has used since the plan (squared) and the rank's status.  Enqueued by one thread per shard: the caller's
+// with one local shard, worker k's with several (enqueue_frame).  The collectives, per thread:
+//   RCCL   ncclAllGather on the shard's own communicator (one thread per device, no group call);
+//   local  local_send | BARRIER | local_copy | BARRIER | local_release.
+// A local error (job.st) skips the shard's remaining launches, the collectives still run; a collective that could not be
+// enqueued (job.fatal) skips the shard's remaining collectives.  Every thread passes every barrier whatever went wrong, so
+// nobody is left waiting.
 void shard_frame(xpbd_multi_world *mw, size_t k, double dt, uint32_t substeps, ShardJob &job, Barrier &bar)
 {
     Shard &s = mw->shards[k];
     const bool multi = mw->n_ranks > 1;
     const double h = dt / (double)substeps; // src/solver.rs:4
-    LocalStatus st;
+    LocalStatus &st = job.st;
     auto hip_keep = [&st](hipError_t e, const char *what) {
         if (e != hipSuccess)
             st.keep(set_error(XPBD_E_HIP, "%s failed: %s", what, hipGetErrorString(e)));
     };
-    auto fatal = [&job](int rc) {
-        if (job.fatal == XPBD_OK && rc != XPBD_OK) {
-            job.fatal = rc;
-            job.fatal_message = xpbd_last_error();
-        }
-    };
-    auto fatal_hip = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess)
-            fatal(set_error(XPBD_E_HIP, "%s failed: %s", what, hipGetErrorString(e)));
-    };
-    // one all-gather: `bytes` from send_of(me) into my recv at row rank, for every rank
-    auto gather = [&](size_t bytes, void *(*send_of)(Shard &), void *recv, hipStream_t stream, hipStream_t (*stream_of)(Shard &)) {
-        (void)stream_of;
+    // one all-gather: `bytes` of every rank's buffer `send` into row rank of my buffer `recv`
+    auto gather = [&](size_t bytes, DevBuf Shard::*send, DevBuf Shard::*recv, hipStream_t stream) {
         if (mw->transport == XPBD_TRANSPORT_RCCL) {
-            if (job.fatal == XPBD_OK) {
-                (void)hipGetLastError(); // see all_gather_device_raw
-                const ncclResult_t r = mw->rccl->AllGather(send_of(s), recv, bytes, ncclChar, s.comm, stream);
-                if (r != ncclSuccess)
-                    fatal(nccl_fail(mw, r, "ncclAllGather"));
-            }
+            if (job.fatal.ok())
+                job.fatal.keep(rccl_all_gather(mw, s, (s.*send).ptr, (s.*recv).ptr, bytes, stream));
             return;
         }
-        if (job.fatal == XPBD_OK)
-            fatal_hip(hipEventRecord(s.ev_send, stream), "hipEventRecord");
+        if (job.fatal.ok())
+            job.fatal.keep(local_send(s, stream));
         bar.arrive_and_wait(); // every shard's send event has been recorded
-        if (job.fatal == XPBD_OK) {
-            for (Shard &p : mw->shards) {
-                if (&p != &s)
-                    fatal_hip(hipStreamWaitEvent(stream, p.ev_send, 0), "hipStreamWaitEvent");
-                fatal_hip(hipMemcpyAsync(static_cast<char *>(recv) + (size_t)p.rank * bytes, send_of(p), bytes, hipMemcpyDefault, stream), "hipMemcpyAsync");
-            }
-            fatal_hip(hipEventRecord(s.ev_recv, stream), "hipEventRecord");
-        }
+        if (job.fatal.ok())
+            job.fatal.keep(local_copy(mw, s, send, (s.*recv).ptr, bytes, stream));
         bar.arrive_and_wait(); // every shard's receive event has been recorded
-        if (job.fatal == XPBD_OK)
-            for (Shard &r : mw->shards)
-                if (&r != &s)
-                    fatal_hip(hipStreamWaitEvent(stream, r.ev_recv, 0), "hipStreamWaitEvent");
+        if (job.fatal.ok())
+            job.fatal.keep(local_release(mw, s, stream));
     };
     st.keep(bind(s));
     if (multi && st.ok())
@@ -1802,21 +1715,27 @@ void shard_frame(xpbd_multi_world *mw, size_t k, double dt, uint32_t substeps, S
     if (st.ok())
         st.keep(xpbd::halo_frame_begin_collect(s.world, h));
     job.ns_wait_broadphase = now_ns() - t0;
-    const xpbd::HaloLists lists{s.boundary_slots.as<uint32_t>(), (uint32_t)s.boundary.size(), s.ghost_slots.as<uint32_t>(), s.ghost_rows.as<uint32_t>(),
-                                (uint32_t)s.ghosts.size(), s.skip_flags.as<uint8_t>(), s.send.as<double>(), s.recv.as<double>()};
+    const xpbd::HaloLists lists = s.lists();
     const size_t bytes = (size_t)mw->rows_per_rank() * kDyn * 8;
     for (uint32_t q = 0; q < substeps; ++q) {
         const bool last = q + 1 == substeps;
+        // 1. the narrowphase, then the boundary bodies: their end-of-substep state lands in the send buffer
         if (st.ok())
             st.keep(xpbd::halo_substep_boundary(s.world, h, q, last, lists));
+        // 2. ONE all-gather per substep on the communication stream ...
         if (multi) {
             hip_keep(hipEventRecord(s.ev_ready, s.stream), "hipEventRecord");
             hip_keep(hipStreamWaitEvent(s.comm_stream, s.ev_ready, 0), "hipStreamWaitEvent");
-            gather(bytes, [](Shard &x) -> void * { return x.send.ptr; }, s.recv.ptr, s.comm_stream, nullptr);
+            gather(bytes, &Shard::send, &Shard::recv, s.comm_stream);
             hip_keep(hipEventRecord(s.ev_gathered, s.comm_stream), "hipEventRecord");
         }
+        // 3. ... while the interior bodies (nobody mirrors them) run on the world stream
         if (st.ok())
             st.keep(xpbd::halo_substep_interior(s.world, h, q, last, lists));
+        // 4. the ghosts take their owners' state from the gathered buffer.  The next substep's boundary launch rewrites the
+        // send buffer only after this exchange has read it: the communication stream is in order, so waiting for
+        // ev_gathered covers the own copy; the peers' reads of OUR buffer are ordered by the transport (RCCL completes the
+        // collective, local_release makes the communication stream wait for every peer's receive event).
         if (multi) {
             hip_keep(hipStreamWaitEvent(s.stream, s.ev_gathered, 0), "hipStreamWaitEvent");
             if (st.ok())
@@ -1824,17 +1743,16 @@ void shard_frame(xpbd_multi_world *mw, size_t k, double dt, uint32_t substeps, S
         }
     }
     if (multi) {
+        // halo validity of THIS frame and the ranks' status, agreed on by all ranks
         hip_keep(hipMemsetAsync(s.disp.ptr, 0, 16, s.stream), "hipMemsetAsync");
         if (st.ok())
             st.keep(xpbd_world_max_displacement2(s.world, s.owned_slots.as<uint32_t>(), (uint32_t)s.held_ids.size(), s.snapshot.as<double>(),
                                                  s.disp_scale.as<double>(), s.disp.as<double>()));
-        *s.status_host = (double)st.rc;
+        *s.status_host = (double)st.rc; // (after the last local launch that could still fail)
         hip_keep(hipMemcpyAsync(s.disp.as<double>() + 1, s.status_host, 8, hipMemcpyHostToDevice, s.stream), "hipMemcpyAsync");
-        gather(16, [](Shard &x) -> void * { return x.disp.ptr; }, s.disp_all.ptr, s.stream, nullptr);
+        gather(16, &Shard::disp, &Shard::disp_all, s.stream);
         hip_keep(hipMemcpyAsync(s.disp_host, s.disp_all.ptr, (size_t)mw->n_ranks * 16, hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync");
     }
-    job.rc = st.rc;
-    job.message = st.message;
 }
 
 void worker_main(xpbd_multi_world *mw, size_t k)
@@ -1862,9 +1780,9 @@ void worker_main(xpbd_multi_world *mw, size_t k)
     }
 }
 
-int enqueue_frame_threaded(xpbd_multi_world *mw, double dt, uint32_t substeps, LocalStatus &st)
+// Runs shard_frame on every worker (started by the first call) and waits until all of them have enqueued their frames.
+int run_workers(xpbd_multi_world *mw, double dt, uint32_t substeps)
 {
-    const uint64_t t0 = now_ns();
     if (!mw->workers) {
         mw->workers = new (std::nothrow) Workers;
         if (!mw->workers)
@@ -1876,26 +1794,39 @@ int enqueue_frame_threaded(xpbd_multi_world *mw, double dt, uint32_t substeps, L
             w.threads.emplace_back(worker_main, mw, k);
     }
     Workers &w = *mw->workers;
-    {
-        std::unique_lock<std::mutex> lock(w.m);
-        w.dt = dt, w.substeps = substeps, w.done = 0;
-        ++w.job;
-        w.cv_job.notify_all();
-        w.cv_done.wait(lock, [&] { return w.done == (uint32_t)w.threads.size(); });
+    std::unique_lock<std::mutex> lock(w.m);
+    w.dt = dt, w.substeps = substeps, w.done = 0;
+    ++w.job;
+    w.cv_job.notify_all();
+    w.cv_done.wait(lock, [&] { return w.done == (uint32_t)w.threads.size(); });
+    return XPBD_OK;
+}
+
+// Enqueues one whole frame on every local shard (shard_frame): on this thread with one local shard, on the workers with
+// several.  Local errors are kept in `st` (the first in shard order); a collective that could not be enqueued breaks the
+// transport.
+int enqueue_frame(xpbd_multi_world *mw, double dt, uint32_t substeps, LocalStatus &st)
+{
+    const uint64_t t0 = now_ns();
+    ShardJob alone;
+    const ShardJob *jobs = &alone;
+    if (mw->shards.size() == 1) {
+        Barrier bar; // one party: arrive_and_wait passes straight through
+        shard_frame(mw, 0, dt, substeps, alone, bar);
+    } else {
+        MW_TRY(run_workers(mw, dt, substeps));
+        jobs = mw->workers->result.data();
     }
     uint64_t wait = 0;
-    for (const ShardJob &j : w.result)
-        wait = std::max(wait, j.ns_wait_broadphase);
+    for (size_t k = 0; k < mw->shards.size(); ++k)
+        wait = std::max(wait, jobs[k].ns_wait_broadphase);
     mw->ns_wait_broadphase += wait;
     mw->ns_enqueue += (now_ns() - t0) - wait;
-    for (const ShardJob &j : w.result)
-        if (j.fatal != XPBD_OK)
-            return transport_broken(mw, set_error(j.fatal, "%s", j.fatal_message.c_str()));
-    for (const ShardJob &j : w.result)
-        if (j.rc != XPBD_OK && st.ok()) {
-            st.rc = j.rc;
-            st.message = j.message;
-        }
+    for (size_t k = 0; k < mw->shards.size(); ++k)
+        if (!jobs[k].fatal.ok())
+            return transport_broken(mw, jobs[k].fatal.report());
+    for (size_t k = 0; k < mw->shards.size() && st.ok(); ++k)
+        st = jobs[k].st;
     return XPBD_OK;
 }
 
@@ -2013,7 +1944,7 @@ int xpbd_comm_unique_id(uint8_t id[XPBD_COMM_ID_BYTES])
     if (!api)
         return set_error(XPBD_E_NO_DEVICE, "xpbd_comm_unique_id: RCCL is not available (%s)", why);
     ncclUniqueId u;
-    (void)hipGetLastError(); // see all_gather_device
+    (void)hipGetLastError(); // see rccl_all_gather
     const ncclResult_t r = api->GetUniqueId(&u);
     if (r != ncclSuccess)
         return set_error(XPBD_E_HIP, "ncclGetUniqueId failed: %s", api->GetErrorString(r));
@@ -2061,7 +1992,7 @@ int xpbd_multi_world_create(xpbd_multi_world **out, const xpbd_multi_config *cfg
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_create: XPBD_TRANSPORT_RCCL needs comm_id (xpbd_comm_unique_id on one rank, handed to all)");
     if (!(cfg->contact_pad >= 0.0) || !(cfg->halo_margin > 0.0) || cfg->contact_pad > 1.0e6 || cfg->halo_margin > 1.0e6)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_create: contact_pad %g / halo_margin %g", cfg->contact_pad, cfg->halo_margin);
-    if (cfg->flags & ~(XPBD_MULTI_AUTO_REPLAN | XPBD_MULTI_PLAN_THROUGH_DEVICE | XPBD_MULTI_SERIAL_ENQUEUE | XPBD_MULTI_FULL_PLANS))
+    if (cfg->flags & ~(XPBD_MULTI_AUTO_REPLAN | XPBD_MULTI_PLAN_THROUGH_DEVICE | XPBD_MULTI_FULL_PLANS))
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_create: unknown flags 0x%x", cfg->flags);
     if (cfg->narrowphase != XPBD_NARROWPHASE_SAT && cfg->narrowphase != XPBD_NARROWPHASE_GJK_EPA)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_create: unknown narrowphase %u", cfg->narrowphase);
@@ -2111,7 +2042,7 @@ int xpbd_multi_world_create(xpbd_multi_world **out, const xpbd_multi_config *cfg
     if (mw->transport == XPBD_TRANSPORT_RCCL) {
         ncclUniqueId id;
         std::memcpy(&id, cfg->comm_id, sizeof id);
-        (void)hipGetLastError(); // see all_gather_device
+        (void)hipGetLastError(); // see rccl_all_gather
         ncclResult_t r = mw->rccl->GroupStart();
         bool device_failed = false;
         int failed_device = 0;
@@ -2279,10 +2210,7 @@ int xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps)
     ++mw->steps;
     for (int attempt = 0;; ++attempt) {
         LocalStatus st;
-        if (mw->shards.size() > 1 && !(mw->flags & XPBD_MULTI_SERIAL_ENQUEUE))
-            MW_TRY(enqueue_frame_threaded(mw, dt, substeps, st));
-        else
-            MW_TRY(enqueue_frame(mw, dt, substeps, st));
+        MW_TRY(enqueue_frame(mw, dt, substeps, st));
         if (mw->n_ranks == 1)
             return st.ok() ? XPBD_OK : st.report(); // no ghosts, nothing to validate: asynchronous after the broadphase
         double moved = 0.0;

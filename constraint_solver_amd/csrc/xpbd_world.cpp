@@ -502,13 +502,6 @@ int halo_frame_begin_collect(xpbd_world *w, double h)
     return XPBD_OK;
 }
 
-int halo_frame_begin(xpbd_world *w, double dt, double h)
-{
-    if (int rc = halo_frame_begin_enqueue(w, dt))
-        return rc;
-    return halo_frame_begin_collect(w, h);
-}
-
 // The state a frame starts from -- the 13 dynamic fields of every body and the contact masks of the last substep -- kept
 // aside (device to device, on the world's stream) so that a frame whose halos turn out to have been too thin can be undone.
 int frame_snapshot_save(xpbd_world *w)

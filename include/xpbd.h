@@ -363,8 +363,6 @@ int  xpbd_world_max_displacement2(xpbd_world *w, const uint32_t *dev_indices, ui
 #define XPBD_TRANSPORT_RCCL  0u
 #define XPBD_TRANSPORT_LOCAL 1u         /* needs n_local == n_ranks */
 #define XPBD_MULTI_AUTO_REPLAN 1u
-#define XPBD_MULTI_SERIAL_ENQUEUE 4u      /* diagnostics: one host thread enqueues all local shards' frames (default with several
-                                           * local shards: one enqueueing thread per shard, see Threading above) */
 #define XPBD_MULTI_PLAN_THROUGH_DEVICE 2u /* diagnostics: the plan-time all-gathers go through the device transport even when
                                            * every rank lives in this process (the path a one-process-per-GPU run takes) */
 #define XPBD_MULTI_FULL_PLANS 8u          /* diagnostics: every re-plan re-cuts the shards from the cell keys of the WHOLE world

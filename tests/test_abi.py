@@ -61,6 +61,14 @@ def test_bad_config_is_rejected_before_touching_the_device():
     assert L.xpbd_world_create(C.byref(h), C.byref(cfg)) == capi.E_INVALID
     assert L.xpbd_world_create(None, None) == capi.E_INVALID
     assert h.value is None
+    mcfg = capi.MultiConfig()
+    L.xpbd_multi_config_default(C.byref(mcfg))
+    devices = (C.c_int32 * 1)(0)
+    mcfg.devices, mcfg.transport = devices, capi.TRANSPORT_LOCAL
+    mcfg.flags = 4   # no such flag: 1, 2 and 8 are the only ones
+    assert L.xpbd_multi_world_create(C.byref(h), C.byref(mcfg)) == capi.E_INVALID
+    assert b"unknown flags" in L.xpbd_last_error()
+    assert h.value is None
 
 
 def test_null_arguments_are_errors_not_crashes():
