@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "xpbd_world_contact_stats", "xpbd_world_build_neighbours",
     "xpbd_world_download_neighbours", "xpbd_world_contacts_begin", "xpbd_world_contacts_substep",
     "xpbd_world_export_dynamic", "xpbd_world_import_dynamic", "xpbd_world_import_dynamic_rows", "xpbd_world_set_joints",
+    "xpbd_world_set_joint_limits", "xpbd_multi_world_set_joint_limits",
     "xpbd_world_narrowphase_gjk", "xpbd_world_set_narrowphase",
     "xpbd_world_set_sat_schedule",
     "xpbd_world_edge_axes_separation",
@@ -93,6 +94,10 @@ class PolytopeDesc(C.Structure):
 JOINT_DTYPE = np.dtype([("body_a", "<u4"), ("body_b", "<u4"), ("anchor_a", "<f8", (3,)), ("anchor_b", "<f8", (3,)),
                         ("distance", "<f8"), ("axis_a", "<f8", (3,)), ("axis_b", "<f8", (3,)), ("kind", "<u4"), ("reserved", "<u4")])
 JOINT_DISTANCE, JOINT_HINGE = 0, 1
+# xpbd_joint_limit as a numpy record (72 bytes)
+JOINT_LIMIT_DTYPE = np.dtype([("joint", "<u4"), ("kind", "<u4"), ("ref_a", "<f8", (3,)), ("ref_b", "<f8", (3,)),
+                              ("lower", "<f8"), ("upper", "<f8")])
+LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST = 0, 1, 2
 # xpbd_gjk_result as a numpy record (96 bytes)
 GJK_DTYPE = np.dtype([("status", "<i4"), ("gjk_iterations", "<u4"), ("epa_iterations", "<u4"), ("reserved", "<u4"),
                       ("depth", "<f8"), ("normal", "<f8", (3,)), ("point_a", "<f8", (3,)), ("point_b", "<f8", (3,))])
@@ -192,6 +197,8 @@ def hip_lib():
         L.xpbd_world_build_neighbours.argtypes = [C.c_void_p, C.c_double, _u32p]
         L.xpbd_world_download_neighbours.argtypes = [C.c_void_p, _u32p, _u32p, C.c_uint32]
         L.xpbd_world_set_joints.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.xpbd_world_set_joint_limits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.xpbd_multi_world_set_joint_limits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.xpbd_world_contacts_begin.argtypes = [C.c_void_p, C.c_double]
         L.xpbd_world_contacts_substep.argtypes = [C.c_void_p, C.c_double]
         L.xpbd_world_export_dynamic.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -370,6 +377,11 @@ class World:
         j = np.ascontiguousarray(joints, dtype=JOINT_DTYPE)
         _check(hip_lib().xpbd_world_set_joints(self._h, j.ctypes.data if j.size else None, j.size))
 
+    def set_joint_limits(self, limits):
+        """limits: JOINT_LIMIT_DTYPE records naming joints of the last set_joints (extension; empty clears them)."""
+        lim = np.ascontiguousarray(limits, dtype=JOINT_LIMIT_DTYPE)
+        _check(hip_lib().xpbd_world_set_joint_limits(self._h, lim.ctypes.data if lim.size else None, lim.size))
+
     def contacts_begin(self, dt):
         _check(hip_lib().xpbd_world_contacts_begin(self._h, dt))
 
@@ -491,6 +503,11 @@ class MultiWorld:
 
     def set_max_depenetration_speed(self, speed):
         _check(hip_lib().xpbd_multi_world_set_max_depenetration_speed(self._h, speed))
+
+    def set_joint_limits(self, limits):
+        """limits: JOINT_LIMIT_DTYPE records naming joints of the last upload by their global index (empty clears them)."""
+        lim = np.ascontiguousarray(limits, dtype=JOINT_LIMIT_DTYPE)
+        _check(hip_lib().xpbd_multi_world_set_joint_limits(self._h, lim.ctypes.data if lim.size else None, lim.size))
 
     def upload(self, bodies, shape_id, first_global, n_global, joints=None):
         """bodies / shape_id: the slice of the caller's bodies this process hands over, global indices [first_global,

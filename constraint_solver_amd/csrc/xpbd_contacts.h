@@ -15,6 +15,13 @@ struct Joint {
     uint32_t kind, reserved;
 };
 
+// xpbd_joint_limit, device copy.
+struct JointLimit {
+    uint32_t joint, kind;
+    double ref_a[3], ref_b[3]; // XPBD_LIMIT_HINGE / _TWIST
+    double lower, upper;
+};
+
 // The uniform grid of one broadphase (device, written by k_grid).
 struct GridInfo {
     double edge;        // cell edge = 2 * largest bounding radius
@@ -60,6 +67,9 @@ struct ContactBuffers {
     const Joint *joints;
     const uint32_t *joint_off;   // [n + 1]
     const uint32_t *joint_list;  // [2 * n_joints]
+    // joint limits: CSR joint -> its limits (the caller's order); limit_off is NULL when there are none
+    const JointLimit *limits;
+    const uint32_t *limit_off;   // [n_joints + 1]
     double max_depenetration_speed; // 0 = off: xpbd_world_set_max_depenetration_speed
 };
 

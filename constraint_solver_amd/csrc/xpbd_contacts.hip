@@ -715,6 +715,62 @@ __device__ __forceinline__ double generalized_inverse_mass(const PairBody &p, Ve
     return p.inv_mass + dot(p.inv_inertia * angular_impulse, angular_impulse);
 }
 
+// The angular limits of joint `joint` for body `self` (xpbd.h, XPBD_LIMIT_*): every limit that binds is a Jacobi entry of its
+// own, in the caller's order.  Evaluated per body like the hinge's angular term, 3-vectors selected by role (a / b), so both
+// ends of the joint compute the same phi, n and lambda.  A limit that does not bind adds nothing, not even to `count`.
+#ifndef XPBD_JOINT_LIMIT_INLINE
+#define XPBD_JOINT_LIMIT_INLINE __forceinline__
+#endif
+__device__ XPBD_JOINT_LIMIT_INLINE void joint_limit_terms(const ContactBuffers &c, uint32_t joint, const Joint &jt, bool self_is_a,
+                                                          const PairBody &self, const PairBody &other, double compliance, Quat &drot,
+                                                          uint32_t &count)
+{
+    const uint32_t l_end = c.limit_off[joint + 1];
+    for (uint32_t l = c.limit_off[joint]; l < l_end; ++l) {
+        const JointLimit &lim = c.limits[l];
+        const Quat q_a = self_is_a ? self.rot : other.rot, q_b = self_is_a ? other.rot : self.rot;
+        const Vec3 a_w = q_a * Vec3{jt.axis_a[0], jt.axis_a[1], jt.axis_a[2]};
+        double phi;
+        Vec3 n;
+        if (lim.kind == XPBD_LIMIT_SWING) {
+            const Vec3 b_w = q_b * Vec3{jt.axis_b[0], jt.axis_b[1], jt.axis_b[2]};
+            const Vec3 cr = cross(a_w, b_w);
+            const double s = length(cr);
+            if (s == 0.0)
+                continue;
+            phi = atan2(s, dot(a_w, b_w));
+            n = cr * (1.0 / s);
+        } else {
+            Vec3 p_a = q_a * Vec3{lim.ref_a[0], lim.ref_a[1], lim.ref_a[2]};
+            Vec3 p_b = q_b * Vec3{lim.ref_b[0], lim.ref_b[1], lim.ref_b[2]};
+            if (lim.kind == XPBD_LIMIT_HINGE) {
+                n = a_w;
+            } else { // XPBD_LIMIT_TWIST: about the bisector of the two axes, on the references' projections
+                const Vec3 bisector = a_w + q_b * Vec3{jt.axis_b[0], jt.axis_b[1], jt.axis_b[2]};
+                const double len = length(bisector);
+                if (len == 0.0)
+                    continue;
+                n = bisector * (1.0 / len);
+                p_a = p_a - n * dot(p_a, n);
+                p_b = p_b - n * dot(p_b, n);
+            }
+            phi = atan2(dot(cross(p_a, p_b), n), dot(p_a, p_b));
+        }
+        const double clamped = phi < lim.lower ? lim.lower : (phi > lim.upper ? lim.upper : phi);
+        const double err = phi - clamped;
+        if (err == 0.0)
+            continue;
+        const Vec3 n_self = conjugate(self.rot) * n, n_other = conjugate(other.rot) * n;
+        const double w_s = dot(self.inv_inertia * n_self, n_self), w_o = dot(other.inv_inertia * n_other, n_other);
+        const double w = self_is_a ? w_s + w_o : w_o + w_s; // w_a + w_b
+        const double lambda = err / (w + compliance);
+        const Vec3 turn = self_is_a ? lambda * n : (-lambda) * n;
+        const Quat spin = quat_sv(0.0, self.inv_inertia * turn);
+        drot = drot + (0.5 * spin) * self.rot;
+        ++count;
+    }
+}
+
 // Jacobi pair solve + joints + derive of body i: its state at the end of the substep.
 // (touching, points: += the manifolds with contact points among this body's pairs (i, j > i) and their points -- every
 // pair is counted by its smaller body, which gives the pipeline's statistics without a pass of their own)
@@ -925,6 +981,8 @@ __device__ __forceinline__ BodyDynamic pair_solve_derive_body(const ContactBuffe
                     ++count;
                 }
             }
+            if (c.limit_off)
+                joint_limit_terms(c, c.joint_list[k], jt, self_is_a, self, other, compliance, drot, count);
         }
     }
 

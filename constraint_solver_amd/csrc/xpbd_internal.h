@@ -24,6 +24,8 @@ struct HaloLists {
 } // namespace xpbd
 
 struct xpbd_world;
+struct xpbd_joint;
+struct xpbd_joint_limit;
 
 namespace xpbd {
 // frame:   halo_frame_begin_enqueue; halo_frame_begin_collect; substeps x { halo_substep_boundary; <all-gather send -> recv,
@@ -55,4 +57,6 @@ int download_records(xpbd_world *w, const uint32_t *host_slots, uint32_t n, doub
 // The world's bodies become: body s = the present body host_src[s] (>= 0) or incoming record -host_src[s] - 1 (39 doubles
 // each).  Only the incoming records cross the bus; otherwise as xpbd_world_upload_bodies (joints and neighbour lists dropped).
 int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const double *incoming39, uint32_t n_incoming);
+// The argument checks of xpbd_world_set_joint_limits against a joint list (XPBD_E_INVALID with a message naming `who`).
+int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits);
 } // namespace xpbd

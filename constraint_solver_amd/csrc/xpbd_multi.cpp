@@ -625,6 +625,7 @@ struct Shard {
     std::vector<uint32_t> local_ids, ghosts, boundary; // global ids (ascending): owned + ghost bodies; ghosts; mirrored owned bodies
     std::vector<uint32_t> owned_slots_h;               // local slot of held_ids[i]
     std::vector<uint8_t> far; // per owned body: more than two cells away from every foreign body (larger travel allowance)
+    std::vector<uint32_t> joint_ids; // global ids (ascending) of the joints the shard's world has: local joint q = joint_ids[q]
     DevBuf boundary_slots, ghost_slots, ghost_rows, owned_slots, skip_flags, disp_scale, send, recv, snapshot, disp, disp_all, stage_send, stage_recv;
     double *disp_host = nullptr;   // pinned, n_ranks x {largest squared fraction of an allowance used, status}
     double *status_host = nullptr; // pinned, this process's status of the frame
@@ -705,6 +706,7 @@ struct xpbd_multi_world {
     std::vector<double> shape_radius, shape_centroid; // per shape: max |vertex - centroid|, centroid xyz
     uint32_t n_global = 0, first_global = 0, n_bodies = 0, capacity = 1;
     std::vector<xpbd_joint> joints;
+    std::vector<xpbd_joint_limit> limits; // xpbd_multi_world_set_joint_limits: GLOBAL joint indices
     std::vector<uint8_t> owner;        // [n_global] as of the last plan
     std::vector<uint32_t> owned_count; // [n_ranks]
     uint64_t plans = 0, rollbacks = 0, migrated = 0, steps = 0, ns_enqueue = 0, ns_wait_broadphase = 0, ns_wait_frame = 0, ns_plan = 0;
@@ -1007,6 +1009,21 @@ int gather_world_keys(xpbd_multi_world *mw, LocalStatus &st, const std::vector<s
     return XPBD_OK;
 }
 
+// The world's joint limits on the joints of shard s, re-indexed to the shard's joint numbering (the caller's order kept).
+int push_joint_limits(const xpbd_multi_world *mw, const Shard &s)
+{
+    std::vector<xpbd_joint_limit> local;
+    for (const xpbd_joint_limit &l : mw->limits) {
+        const auto at = std::lower_bound(s.joint_ids.begin(), s.joint_ids.end(), l.joint);
+        if (at != s.joint_ids.end() && *at == l.joint) {
+            xpbd_joint_limit m = l;
+            m.joint = (uint32_t)(at - s.joint_ids.begin());
+            local.push_back(m);
+        }
+    }
+    return xpbd_world_set_joint_limits(s.world, local.data(), (uint32_t)local.size());
+}
+
 // The second half of every plan: the boundary lists of all ranks fix the rows of the per-substep all-gather, the records of
 // the bodies that change hands or are mirrored travel, and every shard's local world is re-packed on its device.  Collective.
 int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &plans, double edge, PlanTrace &trace)
@@ -1168,6 +1185,9 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
         for (uint32_t q = 0; q < n_loc; ++q)
             mw->slot_of[local_ids[q]] = -1;
         if (int rc = xpbd_world_set_joints(s.world, local_joints.data(), (uint32_t)local_joints.size()))
+            return rc;
+        s.joint_ids = std::move(joint_ids);
+        if (int rc = push_joint_limits(mw, s))
             return rc;
         MW_HIP_TRY(hipStreamSynchronize(s.stream));
         trace.lap("  joints");
@@ -2109,6 +2129,23 @@ int xpbd_multi_world_set_max_depenetration_speed(xpbd_multi_world *mw, double sp
     return XPBD_OK;
 }
 
+int xpbd_multi_world_set_joint_limits(xpbd_multi_world *mw, const xpbd_joint_limit *limits, uint32_t n_limits)
+{
+    MW_TRY(check_usable(mw, "xpbd_multi_world_set_joint_limits"));
+    if (int rc = xpbd::check_joint_limits("xpbd_multi_world_set_joint_limits", mw->joints.data(), (uint32_t)mw->joints.size(), limits, n_limits))
+        return rc;
+    mw->limits.assign(limits, limits + n_limits);
+    if (!mw->planned)
+        return XPBD_OK; // the plan hands them to the shards
+    for (Shard &s : mw->shards)
+        if (int rc = push_joint_limits(mw, s)) { // (checked above: only a device failure gets here, and the shards disagree now)
+            const std::string msg = xpbd_last_error();
+            mw->broken = true;
+            return set_error(rc, "%s -- the shards' joint limits disagree now: destroy this xpbd_multi_world", msg.c_str());
+        }
+    return XPBD_OK;
+}
+
 int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, const uint32_t *shape_id, uint32_t first_global, uint32_t n_bodies,
                             uint32_t n_global, const xpbd_joint *joints, uint32_t n_joints)
 {
@@ -2132,6 +2169,7 @@ int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, cons
             return set_error(XPBD_E_INVALID, "xpbd_multi_world_upload: joint %u links bodies %u and %u of %u", j, joints[j].body_a, joints[j].body_b, n_global);
     mw->n_global = n_global, mw->first_global = first_global, mw->n_bodies = n_bodies;
     mw->joints.assign(joints, joints + n_joints);
+    mw->limits.clear(); // limits name joints by index: a new upload invalidates them
     mw->planned = false;
     mw->cuts_valid = false; // the first plan is a full one
     mw->check_plans = std::getenv("XPBD_MULTI_CHECK_PLANS") != nullptr;

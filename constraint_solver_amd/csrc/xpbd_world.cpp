@@ -175,6 +175,9 @@ struct xpbd_world {
     bool frame_snapshot_valid = false, frame_snapshot_stepped = false;
     DeviceBuffer jt_joints, jt_off, jt_list;
     uint32_t n_joints = 0;
+    std::vector<xpbd_joint> joints_host; // the joints of the last set_joints: what xpbd_world_set_joint_limits checks against
+    DeviceBuffer jt_limits, jt_limit_off;
+    uint32_t n_limits = 0;
     // state history (xpbd_world_history_*): `history_length` slots of history_slot_bytes() in one growing block
     DeviceBuffer history;
     uint32_t history_length = 0;
@@ -222,6 +225,8 @@ struct xpbd_world {
         c.joints = n_joints ? jt_joints.as<xpbd::Joint>() : nullptr;
         c.joint_off = n_joints ? jt_off.as<uint32_t>() : nullptr;
         c.joint_list = n_joints ? jt_list.as<uint32_t>() : nullptr;
+        c.limits = n_limits ? jt_limits.as<xpbd::JointLimit>() : nullptr;
+        c.limit_off = n_limits ? jt_limit_off.as<uint32_t>() : nullptr;
         c.max_depenetration_speed = max_depenetration_speed;
         return c;
     }
@@ -715,6 +720,8 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     XPBD_HIP_TRY(w->aos_staging.reserve((size_t)(n_new ? n_new : 1) * sizeof(xpbd_rigid)));
     w->have_neighbours = false;
     w->n_joints = 0;
+    w->joints_host.clear();
+    w->n_limits = 0;
     w->history_length = 0;
     w->history_stepped.clear();
     w->n = n_new;
@@ -743,6 +750,53 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     XPBD_HIP_TRY(hipMemsetAsync(w->last_mask.ptr, 0, (size_t)stride * 4, w->stream));
     XPBD_HIP_TRY(launch_aos_to_soa(w->repack_aos.as<double>(), w->arrays(), w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the caller's buffers are only borrowed
+    return XPBD_OK;
+}
+
+int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits)
+{
+    static_assert(sizeof(xpbd_joint_limit) == 72 && sizeof(xpbd_joint_limit) == sizeof(JointLimit), "xpbd_joint_limit must mirror xpbd::JointLimit");
+    if (n_limits && !limits)
+        return set_error(XPBD_E_INVALID, "%s: NULL argument", who);
+    auto unit = [](const double *v) {
+        const double len2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+        return len2 > 0.999 && len2 < 1.001; // the hinge's tolerance (xpbd_world_set_joints)
+    };
+    auto perpendicular = [](const double *v, const double *axis) {
+        const double d = v[0] * axis[0] + v[1] * axis[1] + v[2] * axis[2];
+        return d > -1e-3 && d < 1e-3;
+    };
+    std::vector<uint8_t> kinds_seen(n_joints, 0);
+    for (uint32_t k = 0; k < n_limits; ++k) {
+        const xpbd_joint_limit &l = limits[k];
+        if (l.joint >= n_joints)
+            return set_error(XPBD_E_INVALID, "%s: limit %u names joint %u of %u", who, k, l.joint, n_joints);
+        const xpbd_joint &j = joints[l.joint];
+        if (l.kind == XPBD_LIMIT_HINGE) {
+            if (j.kind != XPBD_JOINT_HINGE)
+                return set_error(XPBD_E_INVALID, "%s: limit %u is a HINGE limit on joint %u of kind %u", who, k, l.joint, j.kind);
+        } else if (l.kind == XPBD_LIMIT_SWING || l.kind == XPBD_LIMIT_TWIST) {
+            if (j.kind != XPBD_JOINT_DISTANCE)
+                return set_error(XPBD_E_INVALID, "%s: limit %u (kind %u) needs a DISTANCE joint, joint %u is of kind %u", who, k, l.kind, l.joint, j.kind);
+            if (!unit(j.axis_a) || !unit(j.axis_b))
+                return set_error(XPBD_E_INVALID, "%s: limit %u needs unit axes on joint %u", who, k, l.joint);
+        } else {
+            return set_error(XPBD_E_INVALID, "%s: limit %u has unknown kind %u", who, k, l.kind);
+        }
+        if (kinds_seen[l.joint] & (1u << l.kind))
+            return set_error(XPBD_E_INVALID, "%s: joint %u has two limits of kind %u", who, l.joint, l.kind);
+        kinds_seen[l.joint] |= (uint8_t)(1u << l.kind);
+        if (l.kind != XPBD_LIMIT_SWING) {
+            if (!unit(l.ref_a) || !unit(l.ref_b))
+                return set_error(XPBD_E_INVALID, "%s: limit %u needs unit references", who, k);
+            if (!perpendicular(l.ref_a, j.axis_a) || !perpendicular(l.ref_b, j.axis_b))
+                return set_error(XPBD_E_INVALID, "%s: limit %u: a reference is not perpendicular to its axis", who, k);
+        }
+        if (!(l.lower >= -M_PI && l.lower <= l.upper && l.upper <= M_PI)) // (NaN fails every comparison)
+            return set_error(XPBD_E_INVALID, "%s: limit %u has bounds [%g, %g] (need -pi <= lower <= upper <= pi)", who, k, l.lower, l.upper);
+        if (l.kind == XPBD_LIMIT_SWING && l.lower != 0.0)
+            return set_error(XPBD_E_INVALID, "%s: swing limit %u needs lower = 0 (got %g)", who, k, l.lower);
+    }
     return XPBD_OK;
 }
 
@@ -838,7 +892,7 @@ void xpbd_world_destroy(xpbd_world *w)
                             &w->cb_key, &w->cb_maxr, &w->cb_bucket_start, &w->cb_bucket_cursor, &w->cb_items,
                             &w->cb_nbr_off, &w->cb_pair_first, &w->cb_upper_start, &w->cb_nbr, &w->cb_nbr_pair,
                             &w->cb_pairs, &w->cb_rec, &w->cb_stat_rec, &w->cb_manifolds,
-                            &w->cb_stats, &w->cb_scan, &w->jt_joints, &w->jt_off, &w->jt_list, &w->gjk_counters,
+                            &w->cb_stats, &w->cb_scan, &w->jt_joints, &w->jt_off, &w->jt_list, &w->jt_limits, &w->jt_limit_off, &w->gjk_counters,
                             &w->gjk_pairs_scratch, &w->cb_slot_sphere, &w->cb_slot_cell, &w->history,
                             &w->sat_counters, &w->sat_survivors, &w->sat_axis_cache, &w->gjk_axis_cache, &w->cb_stat_shape, &w->cb_pair_codes, &w->cb_rec_b,
                             &w->cb_grid_partials, &w->cb_items_unsorted})
@@ -1095,7 +1149,9 @@ int xpbd_world_upload_bodies(xpbd_world *w, const xpbd_rigid *aos, const uint32_
     const uint32_t stride = round_up(n ? n : 1, 256);
     XPBD_HIP_TRY(w->dyn.reserve((size_t)xpbd::kDynFields * stride * 8));
     w->have_neighbours = false;
-    w->n_joints = 0; // joints name bodies by index: a new upload invalidates them
+    w->n_joints = 0; // joints name bodies by index: a new upload invalidates them (and their limits)
+    w->joints_host.clear();
+    w->n_limits = 0;
     w->history_length = 0;
     w->history_stepped.clear();
     XPBD_HIP_TRY(w->stat.reserve((size_t)xpbd::kStatFields * stride * 8));
@@ -1382,6 +1438,8 @@ int xpbd_world_set_joints(xpbd_world *w, const xpbd_joint *joints, uint32_t n_jo
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     w->n_joints = 0;
+    w->joints_host.clear();
+    w->n_limits = 0; // limits name joints by index: new joints invalidate them
     if (n_joints == 0)
         return XPBD_OK;
     XPBD_HIP_TRY(w->jt_joints.reserve((size_t)n_joints * sizeof(xpbd::Joint)));
@@ -1391,6 +1449,43 @@ int xpbd_world_set_joints(xpbd_world *w, const xpbd_joint *joints, uint32_t n_jo
     XPBD_HIP_TRY(hipMemcpy(w->jt_off.ptr, off.data(), (size_t)(w->n + 1) * 4, hipMemcpyHostToDevice));
     XPBD_HIP_TRY(hipMemcpy(w->jt_list.ptr, list.data(), (size_t)2 * n_joints * 4, hipMemcpyHostToDevice));
     w->n_joints = n_joints;
+    w->joints_host.assign(joints, joints + n_joints);
+    return XPBD_OK;
+}
+
+int xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, uint32_t n_limits)
+{
+    if (!w)
+        return fail(XPBD_E_INVALID, "xpbd_world_set_joint_limits: NULL world");
+    if (n_limits && w->mode != XPBD_MODE_CONTACTS)
+        return fail(XPBD_E_INVALID, "xpbd_world_set_joint_limits: limits need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
+    if (int rc = xpbd::check_joint_limits("xpbd_world_set_joint_limits", w->joints_host.data(), w->n_joints, limits, n_limits))
+        return rc;
+    // CSR joint -> limits, the caller's order inside a joint
+    std::vector<uint32_t> off((size_t)w->n_joints + 1, 0);
+    for (uint32_t k = 0; k < n_limits; ++k)
+        ++off[limits[k].joint + 1];
+    for (uint32_t j = 0; j < w->n_joints; ++j)
+        off[j + 1] += off[j];
+    std::vector<xpbd_joint_limit> sorted(n_limits);
+    {
+        std::vector<uint32_t> cursor(off.begin(), off.end() - 1);
+        for (uint32_t k = 0; k < n_limits; ++k)
+            sorted[cursor[limits[k].joint]++] = limits[k];
+    }
+    if (int rc = bind_device(w))
+        return rc;
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    if (n_limits == 0) {
+        w->n_limits = 0;
+        return XPBD_OK;
+    }
+    XPBD_HIP_TRY(w->jt_limits.reserve((size_t)n_limits * sizeof(xpbd::JointLimit)));
+    XPBD_HIP_TRY(w->jt_limit_off.reserve(off.size() * 4));
+    w->n_limits = 0; // (a failed copy below leaves none rather than a torn table)
+    XPBD_HIP_TRY(hipMemcpy(w->jt_limits.ptr, sorted.data(), (size_t)n_limits * sizeof(xpbd::JointLimit), hipMemcpyHostToDevice));
+    XPBD_HIP_TRY(hipMemcpy(w->jt_limit_off.ptr, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    w->n_limits = n_limits;
     return XPBD_OK;
 }
 

@@ -96,6 +96,18 @@ pub struct XpbdJoint {
     pub reserved: u32,
 }
 
+/// EXTENSION: angular limit of a joint (XPBD_LIMIT_HINGE = 0, XPBD_LIMIT_SWING = 1, XPBD_LIMIT_TWIST = 2; see xpbd.h).
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct XpbdJointLimit {
+    pub joint: u32,       // index into the joints of the last xpbd_world_set_joints
+    pub kind: u32,
+    pub ref_a: [f64; 3],  // HINGE, TWIST: unit vectors perpendicular to axis_a / axis_b, object space of a / b
+    pub ref_b: [f64; 3],
+    pub lower: f64,       // radians, -pi <= lower <= upper <= pi (SWING: lower = 0)
+    pub upper: f64,
+}
+
 /// EXTENSION: result of the GJK + EPA narrowphase for one pair.
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -189,6 +201,7 @@ extern "C" {
     pub fn xpbd_world_build_neighbours(w: *mut XpbdWorld, dt: f64, n_entries_out: *mut u32) -> c_int;
     pub fn xpbd_world_download_neighbours(w: *mut XpbdWorld, offsets: *mut u32, neighbours: *mut u32, cap: u32) -> c_int;
     pub fn xpbd_world_set_joints(w: *mut XpbdWorld, joints: *const XpbdJoint, n_joints: u32) -> c_int;
+    pub fn xpbd_world_set_joint_limits(w: *mut XpbdWorld, limits: *const XpbdJointLimit, n_limits: u32) -> c_int;
     pub fn xpbd_world_set_max_depenetration_speed(w: *mut XpbdWorld, speed: f64) -> c_int;
     pub fn xpbd_multi_world_set_max_depenetration_speed(mw: *mut XpbdMultiWorld, speed: f64) -> c_int;
     pub fn xpbd_world_snapshot_positions(w: *mut XpbdWorld, dev_indices: *const u32, n: u32, dev_snapshot: *mut f64) -> c_int;
@@ -202,6 +215,7 @@ extern "C" {
     pub fn xpbd_multi_world_set_polytopes(mw: *mut XpbdMultiWorld, shapes: *const XpbdPolytope, n_shapes: u32) -> c_int;
     pub fn xpbd_multi_world_upload(mw: *mut XpbdMultiWorld, bodies: *const XpbdRigid, shape_id: *const u32, first_global: u32, n_bodies: u32,
                                    n_global: u32, joints: *const XpbdJoint, n_joints: u32) -> c_int;
+    pub fn xpbd_multi_world_set_joint_limits(mw: *mut XpbdMultiWorld, limits: *const XpbdJointLimit, n_limits: u32) -> c_int;
     pub fn xpbd_multi_world_step(mw: *mut XpbdMultiWorld, dt: f64, substeps: u32) -> c_int;
     pub fn xpbd_multi_world_replan(mw: *mut XpbdMultiWorld) -> c_int;
     pub fn xpbd_multi_world_synchronize(mw: *mut XpbdMultiWorld) -> c_int;

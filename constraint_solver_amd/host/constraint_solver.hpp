@@ -568,6 +568,11 @@ class ShardedWorld {
         check(xpbd_multi_world_upload(w_, bodies.empty() ? nullptr : bodies[0].c(), shape_id.empty() ? nullptr : shape_id.data(), 0, n_, n_,
                                       joints.empty() ? nullptr : joints.data(), (uint32_t)joints.size()));
     }
+    // angular limits on the joints of the last upload (global joint indices; empty: none); upload clears them
+    void set_joint_limits(const std::vector<xpbd_joint_limit> &limits)
+    {
+        check(xpbd_multi_world_set_joint_limits(w_, limits.empty() ? nullptr : limits.data(), (uint32_t)limits.size()));
+    }
     void integrate(double dt, uint32_t substeps) { check(xpbd_multi_world_step(w_, dt, substeps)); }
     void replan() { check(xpbd_multi_world_replan(w_)); }
     void synchronize() { check(xpbd_multi_world_synchronize(w_)); }

@@ -295,6 +295,38 @@ typedef struct xpbd_joint {
 } xpbd_joint;
 int  xpbd_world_set_joints(xpbd_world *w, const xpbd_joint *joints, uint32_t n_joints);
 
+/* Angular joint LIMITS (EXTENSION; Mueller et al. 2020, "Detailed Rigid Body Simulation with Extended Position Based
+ * Dynamics", 3.3): a stop on the rotation a joint leaves free.  With q_a, q_b the body rotations, a_w = q_a * axis_a,
+ * b_w = q_b * axis_b, r_a = q_a * ref_a, r_b = q_b * ref_b, every limit measures an angle phi about an axis n:
+ *   XPBD_LIMIT_HINGE  n = a_w;  phi = atan2((r_a x r_b) . n, r_a . r_b)
+ *   XPBD_LIMIT_SWING  c = a_w x b_w;  phi = atan2(|c|, a_w . b_w);  n = c / |c|  (|c| = 0: no entry)
+ *   XPBD_LIMIT_TWIST  n = (a_w + b_w) / |a_w + b_w|  (length 0: no entry);  p_a, p_b = r_a, r_b without their components
+ *                     along n;  phi = atan2((p_a x p_b) . n, p_a . p_b)
+ * err = phi - clamp(phi, lower, upper).  err == 0: the limit adds nothing (no Jacobi entry, the count is unchanged), so a
+ * world whose limits never bind steps bit for bit as the same world without them.  Otherwise
+ * w = sum over both bodies of (I^-1 (q^-1 n)) . (q^-1 n), lambda = err / (w + compliance), and a turns by +lambda n, b by
+ * -lambda n, applied as the hinge's angular term applies its turn.  Every active limit is one Jacobi entry, after its
+ * joint's positional and hinge terms, in the order the caller listed the joint's limits.
+ * phi is computed with the device's f64 atan2, which is not correctly rounded: results are bit-identical from run to run
+ * and between a sharded and a single world, not against a CPU model (which agrees to rounding).
+ * Limits name joints of the last xpbd_world_set_joints; setting joints or uploading bodies clears them; n_limits = 0 clears
+ * them.  XPBD_E_INVALID (the previous limits stay in place): a world not in XPBD_MODE_CONTACTS, a joint index out of range,
+ * a kind that does not fit the joint (HINGE needs XPBD_JOINT_HINGE, SWING and TWIST need XPBD_JOINT_DISTANCE with unit
+ * axis_a / axis_b), two limits of one kind on one joint, a non-unit ref_a / ref_b or one not perpendicular to its axis
+ * (HINGE, TWIST; |ref|^2 and ref . axis within 1e-3 as the hinge's axes), NaN bounds, bounds outside
+ * -pi <= lower <= upper <= pi, SWING with lower != 0. */
+#define XPBD_LIMIT_HINGE 0u  /* joint kind HINGE: signed angle about a_w from r_a to r_b in [lower, upper] */
+#define XPBD_LIMIT_SWING 1u  /* joint kind DISTANCE: angle between a_w and b_w <= upper (lower must be 0) */
+#define XPBD_LIMIT_TWIST 2u  /* joint kind DISTANCE: signed twist about the bisector of a_w, b_w in [lower, upper] */
+typedef struct xpbd_joint_limit {
+    uint32_t joint;          /* index into the list of the last xpbd_world_set_joints */
+    uint32_t kind;           /* XPBD_LIMIT_* */
+    double   ref_a[3];       /* HINGE, TWIST: unit vector perpendicular to axis_a, object space of body_a */
+    double   ref_b[3];       /* HINGE, TWIST: unit vector perpendicular to axis_b, object space of body_b */
+    double   lower, upper;   /* radians */
+} xpbd_joint_limit;          /* 72 bytes */
+int  xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, uint32_t n_limits);
+
 /* Split form of xpbd_world_step(w, dt, n) in XPBD_MODE_CONTACTS, for hosts that exchange halo
  * bodies between substeps (multi-GPU):  begin(dt); n x { substep(dt / n); <exchange> }.
  * begin runs the broadphase for the coming frame; substep is one substep of the pipeline. */
@@ -403,6 +435,10 @@ int  xpbd_multi_world_set_max_depenetration_speed(xpbd_multi_world *mw, double s
  * grid).  Collective: cuts the shards, moves every body to its owner and builds the halo plan. */
 int  xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, const uint32_t *shape_id, uint32_t first_global,
                              uint32_t n_bodies, uint32_t n_global, const xpbd_joint *joints, uint32_t n_joints);
+/* xpbd_world_set_joint_limits for the joints of the last upload (GLOBAL joint indices, the same list on every rank); upload
+ * clears them.  Checked against those joints before any device work; not collective.  A device failure while the limits are
+ * handed to the local shards leaves the shards disagreeing: the world is unusable then (destroy it). */
+int  xpbd_multi_world_set_joint_limits(xpbd_multi_world *mw, const xpbd_joint_limit *limits, uint32_t n_limits);
 /* xpbd_world_step(dt, substeps) of the whole sharded world; collective.  XPBD_E_HALO: see above (the frame was undone). */
 int  xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps);
 /* Re-cuts the shards from the bodies' current positions (re-balancing them), migrates bodies whose owner changed and
