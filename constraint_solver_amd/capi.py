@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "xpbd_halo_cell_key", "xpbd_halo_plan", "xpbd_halo_plan_far", "xpbd_halo_partition", "xpbd_halo_plan_owned", "xpbd_halo_plan_light",
     "xpbd_multi_world_download_owned", "xpbd_multi_world_plan_stats", "xpbd_multi_world_owners",
     "xpbd_world_history_push", "xpbd_world_history_restore", "xpbd_world_history_truncate", "xpbd_world_history_length",
+    "xpbd_world_raycast", "xpbd_world_raycast_device", "xpbd_multi_world_raycast",
 ]
 
 
@@ -108,6 +109,26 @@ NARROWPHASE_SAT, NARROWPHASE_GJK_EPA = 0, 1
 MAX_MANIFOLD_POINTS = 8
 FEATURE_FACE_A, FEATURE_FACE_B, FEATURE_EDGES = 0, 1, 2
 # xpbd_manifold as a numpy record (408 bytes)
+# xpbd_ray / xpbd_ray_hit as numpy records (64 bytes each); scene queries (EXTENSION)
+RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("direction", "<f8", (3,)), ("max_distance", "<f8"), ("ignore_body", "<u4"),
+                      ("reserved", "<u4")])
+RAY_HIT_DTYPE = np.dtype([("body", "<u4"), ("face", "<u4"), ("distance", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,))])
+NO_HIT = RAY_INSIDE = 0xFFFFFFFF
+RAYCAST_BRUTE_FORCE = 1
+RAYCAST_BRUTE_FORCE_RAYS = 8      # calls with at most this many rays take the brute-force path anyway
+
+
+def rays(origins, directions, max_distance=np.inf, ignore=None):
+    """RAY_DTYPE records from (n, 3) origins and directions (broadcast), a max_distance per ray or for all, and the body each
+    ray ignores (None: none)."""
+    o, d = np.atleast_2d(np.asarray(origins, dtype=np.float64)), np.atleast_2d(np.asarray(directions, dtype=np.float64))
+    n = max(o.shape[0], d.shape[0])
+    out = np.zeros(n, dtype=RAY_DTYPE)
+    out["origin"], out["direction"], out["max_distance"] = o, d, max_distance
+    out["ignore_body"] = NO_HIT if ignore is None else ignore
+    return out
+
+
 MANIFOLD_DTYPE = np.dtype([("n_points", "<u4"), ("feature", "<u4"), ("index_a", "<u4"), ("index_b", "<u4"),
                            ("separation", "<f8"), ("p_ref", "<f8", (8, 3)), ("p_inc", "<f8", (8, 3))])
 
@@ -210,6 +231,9 @@ def hip_lib():
         L.xpbd_world_history_truncate.argtypes = [C.c_void_p, C.c_uint32]
         L.xpbd_world_history_length.argtypes = [C.c_void_p]
         L.xpbd_world_history_length.restype = C.c_uint32
+        L.xpbd_world_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.xpbd_world_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.xpbd_multi_world_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         _hip = L
     return _hip
 
@@ -419,6 +443,18 @@ class World:
     def history_length(self):
         return hip_lib().xpbd_world_history_length(self._h)
 
+    def raycast(self, rays, flags=0):
+        """RAY_HIT_DTYPE records of the closest body along every ray (RAY_DTYPE records, see rays()) at the current poses."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        out = np.zeros(r.size, dtype=RAY_HIT_DTYPE)
+        _check(hip_lib().xpbd_world_raycast(self._h, r.ctypes.data if r.size else None, r.size, flags,
+                                            out.ctypes.data if r.size else None))
+        return out
+
+    def raycast_device(self, rays_ptr, n, hits_ptr, flags=0):
+        """Device arrays of n xpbd_ray / xpbd_ray_hit, stream-ordered on the world's stream."""
+        _check(hip_lib().xpbd_world_raycast_device(self._h, C.c_void_p(rays_ptr), n, flags, C.c_void_p(hits_ptr)))
+
     def set_stream(self, stream_ptr):
         _check(hip_lib().xpbd_world_set_stream(self._h, C.c_void_p(stream_ptr)))
 
@@ -524,6 +560,14 @@ class MultiWorld:
 
     def replan(self):
         _check(hip_lib().xpbd_multi_world_replan(self._h))
+
+    def raycast(self, rays, flags=0):
+        """World.raycast over the whole sharded world (collective); bodies and ignore_body are global indices."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        out = np.zeros(r.size, dtype=RAY_HIT_DTYPE)
+        _check(hip_lib().xpbd_multi_world_raycast(self._h, r.ctypes.data if r.size else None, r.size, flags,
+                                                  out.ctypes.data if r.size else None))
+        return out
 
     def synchronize(self):
         _check(hip_lib().xpbd_multi_world_synchronize(self._h))

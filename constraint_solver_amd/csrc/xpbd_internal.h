@@ -26,6 +26,8 @@ struct HaloLists {
 struct xpbd_world;
 struct xpbd_joint;
 struct xpbd_joint_limit;
+struct xpbd_ray;
+struct xpbd_ray_hit;
 
 namespace xpbd {
 // frame:   halo_frame_begin_enqueue; halo_frame_begin_collect; substeps x { halo_substep_boundary; <all-gather send -> recv,
@@ -58,5 +60,12 @@ int download_records(xpbd_world *w, const uint32_t *host_slots, uint32_t n, doub
 // each).  Only the incoming records cross the bus; otherwise as xpbd_world_upload_bodies (joints and neighbour lists dropped).
 int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const double *incoming39, uint32_t n_incoming);
 // The argument checks of xpbd_world_set_joint_limits against a joint list (XPBD_E_INVALID with a message naming `who`).
+// The argument checks of xpbd_world_raycast(_device) against one world (topology present) / of the rays' reserved fields.
+int check_raycast(const char *who, const xpbd_world *w, const void *rays, uint32_t n_rays, uint32_t flags, const void *hits);
+int check_rays_reserved(const char *who, const xpbd_ray *rays, uint32_t n_rays);
+// Ray casts of the world's bodies, stream-ordered (device arrays) / from and to host arrays (waits).  dev_global_id: device
+// array of w's body count, the index each body is known by (XPBD_NO_HIT: the body does not answer); NULL: its slot.
+int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits, const uint32_t *dev_global_id);
+int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id);
 int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits);
 } // namespace xpbd

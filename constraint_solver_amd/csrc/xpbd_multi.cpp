@@ -627,6 +627,7 @@ struct Shard {
     std::vector<uint8_t> far; // per owned body: more than two cells away from every foreign body (larger travel allowance)
     std::vector<uint32_t> joint_ids; // global ids (ascending) of the joints the shard's world has: local joint q = joint_ids[q]
     DevBuf boundary_slots, ghost_slots, ghost_rows, owned_slots, skip_flags, disp_scale, send, recv, snapshot, disp, disp_all, stage_send, stage_recv;
+    DevBuf query_ids; // xpbd_multi_world_raycast: global id of every local slot, XPBD_NO_HIT for the ghosts
     double *disp_host = nullptr;   // pinned, n_ranks x {largest squared fraction of an allowance used, status}
     double *status_host = nullptr; // pinned, this process's status of the frame
     xpbd::HaloLists lists() const
@@ -1941,6 +1942,23 @@ void destroy(xpbd_multi_world *mw)
     delete mw;
 }
 
+// One shard's part of a ray cast: its OWNED bodies answer, under their global ids (ghosts are listed as XPBD_NO_HIT).
+int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
+{
+    MW_TRY(bind(s));
+    std::vector<uint32_t> ids(s.local_ids);
+    size_t g = 0;
+    for (uint32_t &id : ids) { // local_ids and ghosts are both ascending
+        while (g < s.ghosts.size() && s.ghosts[g] < id)
+            ++g;
+        if (g < s.ghosts.size() && s.ghosts[g] == id)
+            id = XPBD_NO_HIT;
+    }
+    MW_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
+    MW_TRY(upload_vector(s.query_ids, ids, s.stream));
+    return xpbd::raycast_host(s.world, rays, n_rays, flags, hits, s.query_ids.as<uint32_t>());
+}
+
 int check_usable(const xpbd_multi_world *mw, const char *who)
 {
     if (!mw)
@@ -2281,6 +2299,47 @@ int xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps)
         }
         MW_TRY(replan(mw)); // from the restored state; then the same frame again
     }
+}
+
+int xpbd_multi_world_raycast(xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
+{
+    MW_TRY(check_usable(mw, "xpbd_multi_world_raycast"));
+    if (n_rays && (!rays || !hits))
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_raycast: NULL rays or hits");
+    if (flags & ~XPBD_RAYCAST_BRUTE_FORCE)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_raycast: unknown flags 0x%x", flags);
+    if (!mw->have_shapes)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_raycast: call xpbd_multi_world_set_polytopes first");
+    MW_TRY(xpbd::check_rays_reserved("xpbd_multi_world_raycast", rays, n_rays));
+    if (!mw->planned)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_raycast: no bodies uploaded");
+    if (n_rays == 0)
+        return XPBD_OK;
+    // every local shard casts against its owned bodies; one all-gather of the hit records (with every rank's status) over
+    // all ranks, then every rank merges the n_ranks rows by the (t, global index) rule of a single world
+    LocalStatus st;
+    const size_t bytes = (size_t)n_rays * sizeof(xpbd_ray_hit);
+    std::vector<std::vector<xpbd_ray_hit>> mine(mw->shards.size(), std::vector<xpbd_ray_hit>(n_rays));
+    std::vector<const void *> send;
+    for (size_t k = 0; k < mw->shards.size(); ++k) {
+        if (st.ok())
+            st.keep(shard_raycast(mw->shards[k], rays, n_rays, flags, mine[k].data()));
+        send.push_back(mine[k].data());
+    }
+    std::vector<uint8_t> all;
+    MW_TRY(all_gather_host(mw, send, bytes, all, st));
+    for (uint32_t r = 0; r < n_rays; ++r) {
+        xpbd_ray_hit best;
+        std::memcpy(&best, all.data() + (size_t)r * sizeof(xpbd_ray_hit), sizeof best);
+        for (uint32_t k = 1; k < mw->n_ranks; ++k) {
+            xpbd_ray_hit h;
+            std::memcpy(&h, all.data() + (size_t)k * bytes + (size_t)r * sizeof(xpbd_ray_hit), sizeof h);
+            if (h.distance < best.distance || (h.distance == best.distance && h.body < best.body))
+                best = h;
+        }
+        hits[r] = best;
+    }
+    return XPBD_OK;
 }
 
 int xpbd_multi_world_synchronize(xpbd_multi_world *mw)

@@ -1,0 +1,562 @@
+// xpbd_query.hip -- scene queries (EXTENSION) for gfx950: batched ray casts against the world's bodies.
+//
+// Semantics: include/xpbd.h, "Scene queries"; layout of the work: xpbd_query.h.  Determinism: the winner of a ray is the
+// minimum of its candidates under one total order -- (t, index) -- and a candidate's t is a function of the ray and the body
+// alone, so neither the order in which the atomics of the grid build leave a cell's bodies nor a body being tested in
+// several cells changes any bit.  Atomics count integers only.
+#include <cfloat>
+#include <cmath>
+
+#include "xpbd_query.h"
+#include "xpbd_contacts.h"
+#include "xpbd_device.hpp"
+
+namespace xpbd {
+namespace {
+
+constexpr uint32_t kBlock = 256;
+constexpr uint32_t kBruteRays = 8;      // rays per workgroup of the brute-force path (their winners stay in registers)
+constexpr uint32_t kBruteBlocks = 2048; // the brute-force path splits the bodies until about this many workgroups run
+// Cell edge = 2 * largest radius * kEdgeScale and every sphere's box is padded by largest radius * kPadScale before it is
+// binned: a padded box is still narrower than a cell (at most 2 x 2 x 2 cells per body), and a body whose surface touches a
+// cell face -- a hit point on the face, a ray running inside the face -- is listed in the cells on BOTH sides of it.  The DDA
+// below locates points by rounded divisions; the pad (5e-8 of a cell) is far above their error as long as cell coordinates
+// stay below kMaxCell (2^24 * 2^-52 = 2^-28 of a cell), and worlds whose box does not fit fall back to brute force per ray.
+constexpr double kEdgeScale = 1.0 + 1e-6;
+constexpr double kPadScale = 1e-7;
+constexpr double kMaxCell = 16777216.0;   // |cell coordinate| <= 2^24
+constexpr double kMaxDim = 1048576.0;     // cells per axis <= 2^20
+// The sphere pre-test rejects a body only when the ray's line passes farther than its sphere by a relative 1e-6 (a few
+// thousand times the rounding of the test): it never decides a hit, only saves the face loop of bodies the ray cannot reach.
+constexpr double kSphereSlack = 1.0 + 1e-6;
+
+uint32_t blocks_of(uint32_t n) { return (n + kBlock - 1) / kBlock; }
+
+uint32_t brute_chunks(uint32_t n, uint32_t n_rays)
+{
+    const uint32_t tiles = (n_rays + kBruteRays - 1) / kBruteRays;
+    uint32_t chunks = (kBruteBlocks + tiles - 1) / (tiles ? tiles : 1);
+    const uint32_t most = blocks_of(n) ? blocks_of(n) : 1; // at least one body block (kBlock bodies) per workgroup
+    return chunks < 1 ? 1 : (chunks > most ? most : chunks);
+}
+
+uint32_t next_pow2(uint32_t v)
+{
+    uint32_t p = 1;
+    while (p < v)
+        p <<= 1;
+    return p;
+}
+
+struct QueryGrid {
+    double edge, pad;
+    int32_t lo[3];    // cell coordinates of the box of all padded spheres
+    uint32_t dims[3];
+    uint32_t mode;    // kEmpty, kGrid or kEveryBody
+    uint32_t dense;   // key = linear cell index (else hashed)
+    uint32_t mask;    // table_size - 1
+};
+constexpr uint32_t kEmpty = 0, kGrid = 1, kEveryBody = 2;
+
+// A candidate of the winner: t, the index it is known by, the face, and the slot of its record.
+struct Best {
+    double t;
+    uint32_t id, face, slot, pad;
+};
+static_assert(sizeof(Best) == 24, "brute-force partials are 24 bytes");
+
+__device__ __forceinline__ bool better(double t, uint32_t id, const Best &b) { return t < b.t || (t == b.t && id < b.id); }
+
+__device__ __forceinline__ Best no_hit() { return Best{INFINITY, XPBD_NO_HIT, XPBD_NO_HIT, XPBD_NO_HIT, 0}; }
+
+struct Ray {
+    Vec3 o, d;
+    double tmax;
+    uint32_t ignore;
+    bool valid;
+};
+
+__device__ __forceinline__ Ray load_ray(const xpbd_ray *__restrict__ rays, uint32_t r)
+{
+    const xpbd_ray &x = rays[r];
+    Ray ray;
+    ray.o = Vec3{x.origin[0], x.origin[1], x.origin[2]};
+    ray.d = Vec3{x.direction[0], x.direction[1], x.direction[2]};
+    ray.tmax = x.max_distance;
+    ray.ignore = x.ignore_body;
+    const bool finite = isfinite(ray.o.x) && isfinite(ray.o.y) && isfinite(ray.o.z) && isfinite(ray.d.x) && isfinite(ray.d.y) &&
+                        isfinite(ray.d.z);
+    const bool moving = ray.d.x != 0.0 || ray.d.y != 0.0 || ray.d.z != 0.0;
+    ray.valid = finite && moving && ray.tmax >= 0.0; // (a NaN max_distance fails the comparison; +inf passes)
+    return ray;
+}
+
+struct BodyQ {
+    Vec3 inv_pos;
+    Quat inv_rot;
+    Vec3 centre;
+    double radius; // < 0: never hit
+};
+
+__device__ __forceinline__ BodyQ load_body(const double *__restrict__ rec, uint32_t i)
+{
+    const double2 *r = reinterpret_cast<const double2 *>(rec + (size_t)i * kQueryRecDoubles);
+    const double2 a = r[0], b = r[1], c = r[2], d = r[3], e = r[4], f = r[5];
+    return BodyQ{Vec3{a.x, a.y, b.x}, Quat{b.y, c.x, c.y, d.x}, Vec3{d.y, e.x, e.y}, f.x};
+}
+
+// The routine of one (ray, body) pair (include/xpbd.h): true on a hit, with its t and entering face.
+__device__ __forceinline__ bool ray_body(const Ray &ray, const BodyQ &q, const PolytopeTables &t, uint32_t sid, double &t_hit,
+                                         uint32_t &face)
+{
+    const Vec3 o_l = q.inv_rot * ray.o + q.inv_pos; // inv * origin (src/frame.rs:47-53)
+    const Vec3 d_l = q.inv_rot * ray.d;
+    const ShapeDesc desc = t.desc[sid];
+    double t_lo = 0.0, t_hi = ray.tmax;
+    uint32_t f = XPBD_RAY_INSIDE;
+    for (uint32_t k = 0; k < desc.n_faces; ++k) {
+        const double *p = t.planes + 4 * (size_t)(desc.face0 + k);
+        const Plane pl{Vec3{p[0], p[1], p[2]}, p[3]};
+        const double s = distance(pl, o_l), v = dot(pl.normal, d_l);
+        if (s != s || v != v)
+            return false;
+        if (v < 0.0) {
+            const double tk = (-s) / v;
+            if (tk > t_lo) {
+                t_lo = tk;
+                f = k;
+            }
+        } else if (v > 0.0) {
+            const double tk = (-s) / v;
+            t_hi = tk < t_hi ? tk : t_hi;
+        } else if (s > 0.0) {
+            return false;
+        }
+        if (t_lo > t_hi) // t_lo only grows and t_hi only shrinks: a miss for good
+            return false;
+    }
+    t_hit = t_lo;
+    face = f;
+    return true;
+}
+
+// Conservative sphere test: false only if the ray certainly misses the body's bounding sphere.
+__device__ __forceinline__ bool may_reach(const Ray &ray, const BodyQ &q)
+{
+    const Vec3 w = q.centre - ray.o;
+    const double w2 = dot(w, w), wd = dot(w, ray.d), dd = dot(ray.d, ray.d);
+    const double r2 = q.radius * q.radius * kSphereSlack;
+    if (w2 <= r2)
+        return true; // the origin is inside (or close to) the sphere
+    if (wd < 0.0)
+        return false; // outside the sphere and moving away from its centre
+    const double line2 = w2 - wd * (wd / dd);
+    return line2 <= r2 + 1e-12 * w2;
+}
+
+__device__ __forceinline__ void test_body(const Ray &ray, const double *__restrict__ rec, const uint32_t *__restrict__ shape_id,
+                                          const uint32_t *__restrict__ gid, const PolytopeTables &t, uint32_t i, Best &best)
+{
+    const BodyQ q = load_body(rec, i);
+    if (!(q.radius >= 0.0))
+        return;
+    const uint32_t id = gid ? gid[i] : i;
+    if (id == ray.ignore || !may_reach(ray, q))
+        return;
+    double th;
+    uint32_t face;
+    if (ray_body(ray, q, t, shape_id[i], th, face) && better(th, id, best))
+        best = Best{th, id, face, i, 0};
+}
+
+__device__ __forceinline__ void write_hit(const Ray &ray, const Best &best, const double *__restrict__ rec, const uint32_t *__restrict__ shape_id,
+                                          const PolytopeTables &t, xpbd_ray_hit *__restrict__ hit)
+{
+    xpbd_ray_hit h;
+    h.body = best.id;
+    h.face = best.face;
+    h.distance = best.t;
+    h.point[0] = h.point[1] = h.point[2] = 0.0;
+    h.normal[0] = h.normal[1] = h.normal[2] = 0.0;
+    if (best.id != XPBD_NO_HIT) {
+        const Vec3 p = ray.o + ray.d * best.t;
+        h.point[0] = p.x, h.point[1] = p.y, h.point[2] = p.z;
+        if (best.face != XPBD_RAY_INSIDE) {
+            const BodyQ q = load_body(rec, best.slot);
+            const double *pl = t.planes + 4 * (size_t)(t.desc[shape_id[best.slot]].face0 + best.face);
+            const Vec3 n = conjugate(q.inv_rot) * Vec3{pl[0], pl[1], pl[2]}; // f.rotation = conjugate(inv.rotation), exactly
+            h.normal[0] = n.x, h.normal[1] = n.y, h.normal[2] = n.z;
+        }
+    } else {
+        h.face = XPBD_NO_HIT;
+        h.distance = INFINITY;
+    }
+    *hit = h;
+}
+
+// ---- grid build -------------------------------------------------------------------------------------------------------
+// Inverse frame and bounding sphere of every body, and per workgroup the largest radius and the box of the spheres.
+__global__ void __launch_bounds__(kBlock) k_query_bodies(BodyArrays b, PolytopeTables t, const uint32_t *__restrict__ gid,
+                                                         double *__restrict__ rec, double *__restrict__ partials)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    double v[7] = {0.0, DBL_MAX, DBL_MAX, DBL_MAX, -DBL_MAX, -DBL_MAX, -DBL_MAX}; // rmax, min xyz, max xyz
+    if (i < b.n) {
+        const Frame f = body_frame(b, i);
+        const Frame inv = inverse(f);
+        const uint32_t sid = b.shape_id[i];
+        const double *cc = t.centroids + 3 * (size_t)sid;
+        const Vec3 c = f * Vec3{cc[0], cc[1], cc[2]};
+        const double r = t.radii[sid];
+        const bool finite = isfinite(f.position.x) && isfinite(f.position.y) && isfinite(f.position.z) && isfinite(f.rotation.s) &&
+                            isfinite(f.rotation.x) && isfinite(f.rotation.y) && isfinite(f.rotation.z) && isfinite(c.x) &&
+                            isfinite(c.y) && isfinite(c.z);
+        const bool able = finite && (!gid || gid[i] != XPBD_NO_HIT);
+        double2 *o = reinterpret_cast<double2 *>(rec + (size_t)i * kQueryRecDoubles);
+        o[0] = double2{inv.position.x, inv.position.y};
+        o[1] = double2{inv.position.z, inv.rotation.s};
+        o[2] = double2{inv.rotation.x, inv.rotation.y};
+        o[3] = double2{inv.rotation.z, c.x};
+        o[4] = double2{c.y, c.z};
+        o[5] = double2{able ? r : -1.0, 0.0};
+        if (able) {
+            v[0] = r;
+            v[1] = c.x - r, v[2] = c.y - r, v[3] = c.z - r;
+            v[4] = c.x + r, v[5] = c.y + r, v[6] = c.z + r;
+        }
+    }
+    __shared__ double part[kBlock / 64][7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        double x = v[q];
+        for (uint32_t off = 32; off; off >>= 1) {
+            const double o = __shfl_xor(x, off, 64);
+            x = (q >= 1 && q <= 3) ? (o < x ? o : x) : (o > x ? o : x);
+        }
+        if ((threadIdx.x & 63u) == 0)
+            part[threadIdx.x >> 6][q] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < 7) {
+        const uint32_t q = threadIdx.x;
+        double x = part[0][q];
+        for (uint32_t w = 1; w < kBlock / 64; ++w) {
+            const double o = part[w][q];
+            x = (q >= 1 && q <= 3) ? (o < x ? o : x) : (o > x ? o : x);
+        }
+        partials[(size_t)blockIdx.x * 7 + q] = x;
+    }
+}
+
+// One workgroup: the grid of this call from the partials.
+__global__ void __launch_bounds__(kBlock) k_query_grid(const double *__restrict__ partials, uint32_t n_partials, uint32_t table_size,
+                                                       QueryGrid *__restrict__ grid)
+{
+    __shared__ double part[kBlock / 64][7];
+    double v[7] = {0.0, DBL_MAX, DBL_MAX, DBL_MAX, -DBL_MAX, -DBL_MAX, -DBL_MAX};
+    for (uint32_t k = threadIdx.x; k < n_partials; k += kBlock)
+#pragma unroll
+        for (int q = 0; q < 7; ++q) {
+            const double o = partials[(size_t)k * 7 + q];
+            v[q] = (q >= 1 && q <= 3) ? (o < v[q] ? o : v[q]) : (o > v[q] ? o : v[q]);
+        }
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        double x = v[q];
+        for (uint32_t off = 32; off; off >>= 1) {
+            const double o = __shfl_xor(x, off, 64);
+            x = (q >= 1 && q <= 3) ? (o < x ? o : x) : (o > x ? o : x);
+        }
+        if ((threadIdx.x & 63u) == 0)
+            part[threadIdx.x >> 6][q] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0)
+        return;
+    double m[7];
+    for (int q = 0; q < 7; ++q) {
+        m[q] = part[0][q];
+        for (uint32_t w = 1; w < kBlock / 64; ++w) {
+            const double o = part[w][q];
+            m[q] = (q >= 1 && q <= 3) ? (o < m[q] ? o : m[q]) : (o > m[q] ? o : m[q]);
+        }
+    }
+    QueryGrid g{};
+    g.mask = table_size - 1;
+    const bool any = m[1] <= m[4]; // some body can be hit
+    g.edge = 2.0 * m[0] * kEdgeScale;
+    g.pad = m[0] * kPadScale;
+    bool fits = any && m[0] > 0.0 && isfinite(g.edge);
+    double cells = 1.0;
+    for (int a = 0; a < 3 && fits; ++a) {
+        const double lo = floor((m[1 + a] - g.pad) / g.edge), hi = floor((m[4 + a] + g.pad) / g.edge);
+        if (!(lo >= -kMaxCell && hi <= kMaxCell && hi - lo < kMaxDim)) {
+            fits = false;
+            break;
+        }
+        g.lo[a] = (int32_t)lo;
+        g.dims[a] = (uint32_t)(hi - lo) + 1u;
+        cells *= (double)g.dims[a];
+    }
+    g.mode = !any ? kEmpty : (fits ? kGrid : kEveryBody);
+    g.dense = cells <= (double)table_size ? 1u : 0u;
+    *grid = g;
+}
+
+__device__ __forceinline__ uint32_t query_key(const QueryGrid &g, int32_t x, int32_t y, int32_t z)
+{
+    if (g.dense)
+        return (uint32_t)(x - g.lo[0]) + g.dims[0] * ((uint32_t)(y - g.lo[1]) + g.dims[1] * (uint32_t)(z - g.lo[2]));
+    return (((uint32_t)x * 73856093u) ^ ((uint32_t)y * 19349663u) ^ ((uint32_t)z * 83492791u)) & g.mask;
+}
+
+__device__ __forceinline__ int32_t clamp_axis(const QueryGrid &g, int a, double q)
+{
+    const double lo = (double)g.lo[a], hi = (double)g.lo[a] + (double)(g.dims[a] - 1u);
+    q = q < lo ? lo : q; // (q is finite: the sphere is, and the grid's box holds it)
+    return (int32_t)(q > hi ? hi : q);
+}
+
+// Every body into every cell its padded sphere box overlaps: FILL = false counts the cells' populations, true lists the bodies.
+template <bool FILL>
+__global__ void __launch_bounds__(kBlock) k_query_bin(uint32_t n, const double *__restrict__ rec, const QueryGrid *__restrict__ grid,
+                                                      uint32_t *__restrict__ cell_start, uint32_t *__restrict__ cell_fill,
+                                                      uint32_t *__restrict__ items)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const QueryGrid g = *grid;
+    if (g.mode != kGrid)
+        return;
+    const BodyQ q = load_body(rec, i);
+    if (!(q.radius >= 0.0))
+        return;
+    const double c[3] = {q.centre.x, q.centre.y, q.centre.z};
+    int32_t lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = clamp_axis(g, a, floor((c[a] - q.radius - g.pad) / g.edge));
+        hi[a] = clamp_axis(g, a, floor((c[a] + q.radius + g.pad) / g.edge));
+        hi[a] = hi[a] > lo[a] + 1 ? lo[a] + 1 : hi[a]; // (never binding, see kEdgeScale; `items` holds 8 entries per body)
+    }
+    for (int32_t z = lo[2]; z <= hi[2]; ++z)
+        for (int32_t y = lo[1]; y <= hi[1]; ++y)
+            for (int32_t x = lo[0]; x <= hi[0]; ++x) {
+                const uint32_t key = query_key(g, x, y, z);
+                if (FILL)
+                    items[cell_start[key] + atomicAdd(&cell_fill[key], 1u)] = i;
+                else
+                    atomicAdd(&cell_start[key], 1u);
+            }
+}
+
+// ---- traversal: one lane per ray ----------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) k_query_walk(const xpbd_ray *__restrict__ rays, uint32_t n_rays, uint32_t n,
+                                                       const double *__restrict__ rec, const uint32_t *__restrict__ shape_id,
+                                                       const uint32_t *__restrict__ gid, PolytopeTables t,
+                                                       const QueryGrid *__restrict__ grid, const uint32_t *__restrict__ cell_start,
+                                                       const uint32_t *__restrict__ items, xpbd_ray_hit *__restrict__ hits)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rays)
+        return;
+    const Ray ray = load_ray(rays, r);
+    const QueryGrid g = *grid;
+    Best best = no_hit();
+    if (ray.valid && g.mode == kEveryBody) {
+        for (uint32_t i = 0; i < n; ++i)
+            test_body(ray, rec, shape_id, gid, t, i, best);
+    } else if (ray.valid && g.mode == kGrid) {
+        const double o[3] = {ray.o.x, ray.o.y, ray.o.z}, d[3] = {ray.d.x, ray.d.y, ray.d.z};
+        // clip to the grid's box: [t_near, t_far]
+        double t_near = 0.0, t_far = ray.tmax;
+        bool inside = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double lo = (double)g.lo[a] * g.edge, hi = ((double)g.lo[a] + (double)g.dims[a]) * g.edge;
+            if (d[a] == 0.0) {
+                inside = inside && o[a] >= lo && o[a] <= hi;
+            } else {
+                const double t1 = (lo - o[a]) / d[a], t2 = (hi - o[a]) / d[a];
+                const double tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1;
+                t_near = tn > t_near ? tn : t_near;
+                t_far = tf < t_far ? tf : t_far;
+            }
+        }
+        if (inside && t_near <= t_far) {
+            int32_t cell[3], step[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                // A zero component is its own case: the ray stays in the slab of cells of its origin, and when the origin
+                // lies ON a cell face (o = k * edge exactly) that is cell k -- every body touching the face is listed
+                // there too, because binned boxes are padded.
+                const double p = d[a] == 0.0 ? o[a] : o[a] + t_near * d[a];
+                cell[a] = clamp_axis(g, a, floor(p / g.edge));
+                step[a] = d[a] > 0.0 ? 1 : (d[a] < 0.0 ? -1 : 0);
+            }
+            double t_enter = t_near;
+            for (;;) {
+                if (t_enter > best.t) // strict: a tie in the next cell can still win on the smaller index
+                    break;
+                const uint32_t key = query_key(g, cell[0], cell[1], cell[2]);
+                const uint32_t s1 = cell_start[key + 1];
+                for (uint32_t s = cell_start[key]; s < s1; ++s)
+                    test_body(ray, rec, shape_id, gid, t, items[s], best);
+                // the next cell: the nearest face ahead, each face's t from its own coordinate (no accumulated error); a
+                // ray through an edge or a corner steps one axis at a time (first axis first), with equal t
+                double t_next = INFINITY;
+                int axis = -1;
+#pragma unroll
+                for (int a = 0; a < 3; ++a)
+                    if (step[a] != 0) {
+                        const double face = (double)(cell[a] + (step[a] > 0 ? 1 : 0)) * g.edge;
+                        const double ta = (face - o[a]) / d[a];
+                        if (ta < t_next) {
+                            t_next = ta;
+                            axis = a;
+                        }
+                    }
+                if (axis < 0 || t_next > t_far)
+                    break;
+                cell[axis] += step[axis];
+                if (cell[axis] < g.lo[axis] || cell[axis] >= g.lo[axis] + (int32_t)g.dims[axis])
+                    break;
+                t_enter = t_next;
+            }
+        }
+    }
+    write_hit(ray, best, rec, shape_id, t, hits + r);
+}
+
+// ---- brute force: workgroup (tile of kBruteRays rays, chunk of bodies) --------------------------------------------------
+__device__ __forceinline__ void wave_min(Best &b)
+{
+    for (uint32_t off = 32; off; off >>= 1) {
+        Best o;
+        o.t = __shfl_xor(b.t, off, 64);
+        o.id = __shfl_xor(b.id, off, 64);
+        o.face = __shfl_xor(b.face, off, 64);
+        o.slot = __shfl_xor(b.slot, off, 64);
+        o.pad = 0;
+        if (better(o.t, o.id, b))
+            b = o;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_query_brute(const xpbd_ray *__restrict__ rays, uint32_t n_rays, uint32_t n, uint32_t chunk_len,
+                                                        const double *__restrict__ rec, const uint32_t *__restrict__ shape_id,
+                                                        const uint32_t *__restrict__ gid, PolytopeTables t, Best *__restrict__ partial)
+{
+    const uint32_t r0 = blockIdx.x * kBruteRays, chunk = blockIdx.y, chunks = gridDim.y;
+    __shared__ Best wave_best[kBlock / 64][kBruteRays];
+    Ray ray[kBruteRays];
+    Best best[kBruteRays];
+#pragma unroll
+    for (uint32_t q = 0; q < kBruteRays; ++q) {
+        ray[q] = r0 + q < n_rays ? load_ray(rays, r0 + q) : Ray{};
+        if (r0 + q >= n_rays)
+            ray[q].valid = false;
+        best[q] = no_hit();
+    }
+    const uint32_t begin = chunk * chunk_len, end = begin + chunk_len < n ? begin + chunk_len : n;
+    for (uint32_t i = begin + threadIdx.x; i < end; i += kBlock) {
+#pragma unroll
+        for (uint32_t q = 0; q < kBruteRays; ++q)
+            if (ray[q].valid)
+                test_body(ray[q], rec, shape_id, gid, t, i, best[q]);
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < kBruteRays; ++q) {
+        wave_min(best[q]);
+        if ((threadIdx.x & 63u) == 0)
+            wave_best[threadIdx.x >> 6][q] = best[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < kBruteRays && r0 + threadIdx.x < n_rays) {
+        const uint32_t q = threadIdx.x;
+        Best b = wave_best[0][q];
+        for (uint32_t w = 1; w < kBlock / 64; ++w)
+            if (better(wave_best[w][q].t, wave_best[w][q].id, b))
+                b = wave_best[w][q];
+        partial[(size_t)(r0 + q) * chunks + chunk] = b;
+    }
+}
+
+// One wave per ray: the partials of its workgroups (up to kBruteBlocks of them for a single ray) reduced across the lanes.
+__global__ void __launch_bounds__(64) k_query_brute_finish(const xpbd_ray *__restrict__ rays, uint32_t chunks, const Best *__restrict__ partial,
+                                                           const double *__restrict__ rec, const uint32_t *__restrict__ shape_id,
+                                                           PolytopeTables t, xpbd_ray_hit *__restrict__ hits)
+{
+    const uint32_t r = blockIdx.x;
+    Best best = no_hit();
+    for (uint32_t c = threadIdx.x; c < chunks; c += 64) {
+        const Best b = partial[(size_t)r * chunks + c];
+        if (better(b.t, b.id, best))
+            best = b;
+    }
+    wave_min(best);
+    if (threadIdx.x == 0)
+        write_hit(load_ray(rays, r), best, rec, shape_id, t, hits + r);
+}
+
+} // namespace
+
+QuerySizes query_scratch_bytes(uint32_t n, uint32_t n_rays, bool brute)
+{
+    QuerySizes q{};
+    q.rec = (size_t)(n ? n : 1) * kQueryRecDoubles * 8;
+    q.partials = (size_t)(blocks_of(n) + 1) * 7 * 8;
+    q.grid = sizeof(QueryGrid);
+    q.table_size = next_pow2(4 * (n > 256 ? n : 256));
+    if (brute) {
+        q.cell_start = q.cell_fill = q.items = q.scan_scratch = 8;
+        const uint32_t tiles = (n_rays + kBruteRays - 1) / kBruteRays;
+        q.brute = (size_t)(tiles ? tiles : 1) * kBruteRays * brute_chunks(n, n_rays) * sizeof(Best);
+    } else {
+        q.cell_start = (size_t)(q.table_size + 1) * 4;
+        q.cell_fill = (size_t)q.table_size * 4;
+        q.items = (size_t)8 * (n ? n : 1) * 4;
+        q.scan_scratch = ((size_t)q.table_size / 1024 + 8) * 4;
+        q.brute = 8;
+    }
+    return q;
+}
+
+hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const void *rays_v, uint32_t n_rays,
+                          bool brute, const QueryScratch &s, void *hits_v, hipStream_t stream)
+{
+    if (n_rays == 0)
+        return hipSuccess;
+    const xpbd_ray *rays = static_cast<const xpbd_ray *>(rays_v);
+    xpbd_ray_hit *hits = static_cast<xpbd_ray_hit *>(hits_v);
+    QueryGrid *grid = static_cast<QueryGrid *>(s.grid);
+    if (b.n)
+        hipLaunchKernelGGL(k_query_bodies, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b, t, global_id, s.rec, s.partials);
+    if (brute || b.n == 0) {
+        const uint32_t tiles = (n_rays + kBruteRays - 1) / kBruteRays, chunks = brute_chunks(b.n, n_rays);
+        const uint32_t chunk_len = (b.n + chunks - 1) / chunks;
+        Best *partial = static_cast<Best *>(s.brute);
+        hipLaunchKernelGGL(k_query_brute, dim3(tiles, chunks), dim3(kBlock), 0, stream, rays, n_rays, b.n, chunk_len, s.rec, b.shape_id,
+                           global_id, t, partial);
+        hipLaunchKernelGGL(k_query_brute_finish, dim3(n_rays), dim3(64), 0, stream, rays, chunks, partial, s.rec, b.shape_id, t, hits);
+        return hipGetLastError();
+    }
+    hipError_t e = hipMemsetAsync(s.cell_start, 0, (size_t)(s.table_size + 1) * 4, stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(s.cell_fill, 0, (size_t)s.table_size * 4, stream);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_query_grid, dim3(1), dim3(kBlock), 0, stream, s.partials, blocks_of(b.n), s.table_size, grid);
+    hipLaunchKernelGGL(k_query_bin<false>, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b.n, s.rec, grid, s.cell_start, s.cell_fill,
+                       s.items);
+    if ((e = launch_exclusive_scan(s.cell_start, s.table_size, s.scan_scratch, stream)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_query_bin<true>, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b.n, s.rec, grid, s.cell_start, s.cell_fill,
+                       s.items);
+    hipLaunchKernelGGL(k_query_walk, dim3(blocks_of(n_rays)), dim3(kBlock), 0, stream, rays, n_rays, b.n, s.rec, b.shape_id, global_id, t,
+                       grid, s.cell_start, s.items, hits);
+    return hipGetLastError();
+}
+
+} // namespace xpbd

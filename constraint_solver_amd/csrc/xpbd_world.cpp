@@ -21,6 +21,7 @@
 #include "xpbd_contacts.h"
 #include "xpbd_gjk.h"
 #include "xpbd_pairs.h"
+#include "xpbd_query.h"
 
 namespace {
 
@@ -178,6 +179,8 @@ struct xpbd_world {
     std::vector<xpbd_joint> joints_host; // the joints of the last set_joints: what xpbd_world_set_joint_limits checks against
     DeviceBuffer jt_limits, jt_limit_off;
     uint32_t n_limits = 0;
+    // scene queries (xpbd_world_raycast*): scratch of one call, and the staging of the host variant's rays and hits
+    DeviceBuffer q_rec, q_partials, q_grid, q_cell_start, q_cell_fill, q_items, q_scan, q_brute, q_rays, q_hits;
     // state history (xpbd_world_history_*): `history_length` slots of history_slot_bytes() in one growing block
     DeviceBuffer history;
     uint32_t history_length = 0;
@@ -800,6 +803,75 @@ int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joi
     return XPBD_OK;
 }
 
+int check_raycast(const char *who, const xpbd_world *w, const void *rays, uint32_t n_rays, uint32_t flags, const void *hits)
+{
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n_rays && (!rays || !hits))
+        return set_error(XPBD_E_INVALID, "%s: NULL rays or hits", who);
+    if (flags & ~XPBD_RAYCAST_BRUTE_FORCE)
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (!w->has_topology)
+        return set_error(XPBD_E_INVALID, "%s: call xpbd_world_set_polytopes first (set_shapes gives vertices only)", who);
+    return XPBD_OK;
+}
+
+int check_rays_reserved(const char *who, const xpbd_ray *rays, uint32_t n_rays)
+{
+    for (uint32_t r = 0; r < n_rays; ++r)
+        if (rays[r].reserved)
+            return set_error(XPBD_E_INVALID, "%s: ray %u has reserved = %u (must be 0)", who, r, rays[r].reserved);
+    return XPBD_OK;
+}
+
+int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits,
+                    const uint32_t *dev_global_id)
+{
+    static_assert(sizeof(xpbd_ray) == 64 && sizeof(xpbd_ray_hit) == 64, "xpbd_ray and xpbd_ray_hit are 64 bytes");
+    if (n_rays == 0)
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    // (a world without bodies takes the brute-force path too: every ray misses, no grid to build)
+    const bool brute = (flags & XPBD_RAYCAST_BRUTE_FORCE) || n_rays <= XPBD_RAYCAST_BRUTE_FORCE_RAYS || w->n == 0;
+    const QuerySizes q = query_scratch_bytes(w->n, n_rays, brute);
+    const std::pair<DeviceBuffer *, size_t> need[] = {{&w->q_rec, q.rec}, {&w->q_partials, q.partials}, {&w->q_grid, q.grid},
+                                                      {&w->q_cell_start, q.cell_start}, {&w->q_cell_fill, q.cell_fill},
+                                                      {&w->q_items, q.items}, {&w->q_scan, q.scan_scratch}, {&w->q_brute, q.brute}};
+    bool grow = false;
+    for (const auto &b : need)
+        grow = grow || b.first->bytes < b.second;
+    if (grow) { // reserve() frees the block it replaces, which queued work may still use
+        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+        for (const auto &b : need)
+            XPBD_HIP_TRY(b.first->reserve(b.second));
+    }
+    const QueryScratch s{w->q_rec.as<double>(), w->q_partials.as<double>(), w->q_grid.ptr, w->q_cell_start.as<uint32_t>(),
+                         w->q_cell_fill.as<uint32_t>(), w->q_items.as<uint32_t>(), w->q_scan.as<uint32_t>(), w->q_brute.ptr, q.table_size};
+    XPBD_HIP_TRY(launch_raycast(w->arrays(), w->tables(), dev_global_id, dev_rays, n_rays, brute, s, dev_hits, w->stream));
+    return XPBD_OK;
+}
+
+int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id)
+{
+    if (n_rays == 0)
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    const size_t bytes = (size_t)n_rays * sizeof(xpbd_ray);
+    if (w->q_rays.bytes < bytes || w->q_hits.bytes < bytes) {
+        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+        XPBD_HIP_TRY(w->q_rays.reserve(bytes));
+        XPBD_HIP_TRY(w->q_hits.reserve(bytes));
+    }
+    XPBD_HIP_TRY(hipMemcpyAsync(w->q_rays.ptr, rays, bytes, hipMemcpyHostToDevice, w->stream));
+    if (int rc = raycast_enqueue(w, w->q_rays.as<xpbd_ray>(), n_rays, flags, w->q_hits.as<xpbd_ray_hit>(), dev_global_id))
+        return rc;
+    XPBD_HIP_TRY(hipMemcpyAsync(hits, w->q_hits.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    return XPBD_OK;
+}
+
 } // namespace xpbd
 
 extern "C" {
@@ -895,7 +967,8 @@ void xpbd_world_destroy(xpbd_world *w)
                             &w->cb_stats, &w->cb_scan, &w->jt_joints, &w->jt_off, &w->jt_list, &w->jt_limits, &w->jt_limit_off, &w->gjk_counters,
                             &w->gjk_pairs_scratch, &w->cb_slot_sphere, &w->cb_slot_cell, &w->history,
                             &w->sat_counters, &w->sat_survivors, &w->sat_axis_cache, &w->gjk_axis_cache, &w->cb_stat_shape, &w->cb_pair_codes, &w->cb_rec_b,
-                            &w->cb_grid_partials, &w->cb_items_unsorted})
+                            &w->cb_grid_partials, &w->cb_items_unsorted, &w->q_rec, &w->q_partials, &w->q_grid, &w->q_cell_start,
+                            &w->q_cell_fill, &w->q_items, &w->q_scan, &w->q_brute, &w->q_rays, &w->q_hits})
         b->release();
     for (DeviceBuffer *b : {&w->frame_snapshot, &w->repack_aos, &w->repack_shape, &w->repack_src, &w->repack_incoming, &w->halo_keys, &w->halo_records})
         b->release();
@@ -1722,6 +1795,22 @@ int xpbd_world_history_truncate(xpbd_world *w, uint32_t length)
 }
 
 uint32_t xpbd_world_history_length(const xpbd_world *w) { return w ? w->history_length : 0; }
+
+int xpbd_world_raycast(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
+{
+    if (int rc = xpbd::check_raycast("xpbd_world_raycast", w, rays, n_rays, flags, hits))
+        return rc;
+    if (int rc = xpbd::check_rays_reserved("xpbd_world_raycast", rays, n_rays))
+        return rc;
+    return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr);
+}
+
+int xpbd_world_raycast_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits)
+{
+    if (int rc = xpbd::check_raycast("xpbd_world_raycast_device", w, dev_rays, n_rays, flags, dev_hits))
+        return rc;
+    return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr);
+}
 
 int xpbd_selftest_div_sqrt(int32_t device, const double *a, const double *b, double *quotient, double *root,
                            uint32_t n)

@@ -130,6 +130,32 @@ pub struct XpbdEdgeQuery {
     pub edge_b: u32,
 }
 
+pub const XPBD_NO_HIT: u32 = 0xFFFF_FFFF;
+pub const XPBD_RAY_INSIDE: u32 = 0xFFFF_FFFF;
+pub const XPBD_RAYCAST_BRUTE_FORCE: u32 = 1;
+
+/// xpbd_ray (64 bytes): distances are in units of |direction|; ignore_body = XPBD_NO_HIT for none; reserved = 0
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdRay {
+    pub origin: [f64; 3],
+    pub direction: [f64; 3],
+    pub max_distance: f64,
+    pub ignore_body: u32,
+    pub reserved: u32,
+}
+
+/// xpbd_ray_hit (64 bytes): body = XPBD_NO_HIT on a miss; face = XPBD_RAY_INSIDE when the ray starts inside the body
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdRayHit {
+    pub body: u32,
+    pub face: u32,
+    pub distance: f64,
+    pub point: [f64; 3],
+    pub normal: [f64; 3],
+}
+
 #[repr(C)]
 pub struct XpbdWorld {
     _private: [u8; 0],
@@ -246,6 +272,11 @@ extern "C" {
     pub fn xpbd_world_history_restore(w: *mut XpbdWorld, index: u32) -> c_int;
     pub fn xpbd_world_history_truncate(w: *mut XpbdWorld, length: u32) -> c_int;
     pub fn xpbd_world_history_length(w: *const XpbdWorld) -> u32;
+    pub fn xpbd_world_raycast(w: *mut XpbdWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, hits: *mut XpbdRayHit) -> c_int;
+    pub fn xpbd_world_raycast_device(w: *mut XpbdWorld, dev_rays: *const XpbdRay, n_rays: u32, flags: u32, dev_hits: *mut XpbdRayHit)
+        -> c_int;
+    pub fn xpbd_multi_world_raycast(mw: *mut XpbdMultiWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, hits: *mut XpbdRayHit)
+        -> c_int;
 }
 
 fn v3(v: Vector3<f64>) -> [f64; 3] {

@@ -500,6 +500,13 @@ class BatchWorld {
     void history_restore(uint32_t index) { check(xpbd_world_history_restore(w_, index)); }
     void history_truncate(uint32_t length) { check(xpbd_world_history_truncate(w_, length)); }
     uint32_t history_length() const { return xpbd_world_history_length(w_); }
+    // closest body along every ray at the current poses (include/xpbd.h, "Scene queries")
+    std::vector<xpbd_ray_hit> raycast(const std::vector<xpbd_ray> &rays, uint32_t flags = 0)
+    {
+        std::vector<xpbd_ray_hit> hits(rays.size());
+        check(xpbd_world_raycast(w_, rays.empty() ? nullptr : rays.data(), (uint32_t)rays.size(), flags, hits.empty() ? nullptr : hits.data()));
+        return hits;
+    }
 
     std::vector<xpbd_contact> contacts()
     {
@@ -575,6 +582,13 @@ class ShardedWorld {
     }
     void integrate(double dt, uint32_t substeps) { check(xpbd_multi_world_step(w_, dt, substeps)); }
     void replan() { check(xpbd_multi_world_replan(w_)); }
+    // closest body along every ray, bodies by global index (collective: every rank passes the same rays)
+    std::vector<xpbd_ray_hit> raycast(const std::vector<xpbd_ray> &rays, uint32_t flags = 0)
+    {
+        std::vector<xpbd_ray_hit> hits(rays.size());
+        check(xpbd_multi_world_raycast(w_, rays.empty() ? nullptr : rays.data(), (uint32_t)rays.size(), flags, hits.empty() ? nullptr : hits.data()));
+        return hits;
+    }
     void synchronize() { check(xpbd_multi_world_synchronize(w_)); }
     void download(std::vector<rigid::Rigid> &bodies)
     {

@@ -506,6 +506,68 @@ int  xpbd_world_history_restore(xpbd_world *w, uint32_t index);
 int  xpbd_world_history_truncate(xpbd_world *w, uint32_t length);
 uint32_t xpbd_world_history_length(const xpbd_world *w);
 
+/* ---------------------------------------------------------------------------
+ * Scene queries (EXTENSION): the closest body along each of a batch of rays, at the bodies' current poses.  NOT in the
+ * reference; its app would use it for picking under the cursor (src/app.rs, src/camera.rs).
+ *
+ * Poses and bodies.  A ray sees every body at the pose xpbd_world_download_bodies would return after the work already
+ * enqueued, in every mode (in XPBD_MODE_CONTACTS the current state, never the other half of its double buffer).  A body is
+ * the convex polytope of its shape as set by xpbd_world_set_polytopes (without polytopes: XPBD_E_INVALID; set_shapes gives
+ * vertices only).  The ground plane is not a body: rays never hit it.  A body whose pose is not finite is never hit.
+ *
+ * One ray against one body, with f = Rigid::frame() of the body (src/rigid.rs:75-80) and inv = inverse(f) (src/frame.rs:30-37):
+ *   o_l = inv * origin, d_l = inv.rotation * direction; t_lo = 0, face = XPBD_RAY_INSIDE, t_hi = max_distance;
+ *   for every face k in index order, with the outward local plane P_k (Polytope::plane, src/geometry.rs:262-271):
+ *     s = distance(P_k, o_l) (src/geometry.rs:39-41), v = dot(P_k.normal, d_l); if s or v is NaN the ray misses;
+ *     v < 0: t_k = (-s) / v, and if t_k > t_lo then t_lo = t_k, face = k   (strict: the first maximum wins)
+ *     v > 0: t_hi = min(t_hi, (-s) / v)
+ *     v = 0: the ray misses if s > 0 (parallel, outside the slab)
+ *   hit iff t_lo <= t_hi; point = origin + t_lo * direction (per component, no fused multiply-add), normal =
+ *   f.rotation * P_face.normal.  Quotients are correctly rounded f64 divisions.
+ * Per ray the smallest t wins and equal t go to the smaller body index (in xpbd_multi_world_raycast: the caller's global
+ * index).  ignore_body is never hit.  A ray with a NaN or infinite component, a zero direction, or a max_distance that is
+ * negative or NaN hits nothing (the call still succeeds).  A miss is {XPBD_NO_HIT, XPBD_NO_HIT, +inf, 0, 0}.
+ *
+ * Errors: XPBD_E_INVALID for a NULL world, NULL rays / hits with n_rays > 0, unknown flags, a nonzero `reserved` (host
+ * variants: the device variant cannot see the rays).  n_rays == 0 is XPBD_OK.  A ray cast changes no body, contact list,
+ * mask, history entry or plan: stepping after it gives the same bits as stepping without it.
+ *
+ * Method: a uniform grid of the bodies' bounding spheres built for every call (counting passes and scans), walked by every
+ * ray cell by cell (3D-DDA).  Up to XPBD_RAYCAST_BRUTE_FORCE_RAYS rays take the brute-force path instead, which needs no
+ * grid (picking latency).  Same bits either way.
+ * ------------------------------------------------------------------------- */
+#define XPBD_NO_HIT      0xFFFFFFFFu  /* xpbd_ray_hit.body when nothing was hit */
+#define XPBD_RAY_INSIDE  0xFFFFFFFFu  /* xpbd_ray_hit.face when the ray starts inside (or on) the hit body */
+#define XPBD_RAYCAST_BRUTE_FORCE 1u   /* diagnostics: test every ray against every body, no grid */
+#define XPBD_RAYCAST_BRUTE_FORCE_RAYS 8u /* calls with at most this many rays take the brute-force path anyway */
+
+typedef struct xpbd_ray {            /* 64 bytes */
+    double   origin[3];
+    double   direction[3];           /* need not be unit; distances are in units of |direction| */
+    double   max_distance;           /* may be +inf */
+    uint32_t ignore_body;            /* a body this ray never hits (XPBD_NO_HIT: none) */
+    uint32_t reserved;               /* must be 0 */
+} xpbd_ray;
+
+typedef struct xpbd_ray_hit {        /* 64 bytes */
+    uint32_t body;                   /* XPBD_NO_HIT: missed */
+    uint32_t face;                   /* shape-local face index the ray enters through, or XPBD_RAY_INSIDE */
+    double   distance;               /* t: point = origin + t * direction */
+    double   point[3];
+    double   normal[3];              /* world-space outward normal of `face`; (0,0,0) for XPBD_RAY_INSIDE */
+} xpbd_ray_hit;
+
+/* Host arrays; waits for the result. */
+int  xpbd_world_raycast(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits);
+/* Device arrays; stream-ordered on the world's stream, returns before completion (it waits only when its scratch has to
+ * grow).  `reserved` is not checked. */
+int  xpbd_world_raycast_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags,
+                               xpbd_ray_hit *dev_hits);
+/* Collective: every rank passes the same rays and gets all hits.  Every shard casts against the bodies it OWNS; bodies
+ * and ignore_body are global indices. */
+int  xpbd_multi_world_raycast(xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags,
+                              xpbd_ray_hit *hits);
+
 /* Diagnostics: quotient[i] = a[i] / b[i], root[i] = sqrt(a[i]) computed on the
  * device with the stepper's own code generation.  Bit-exact contact lists need
  * both to be correctly rounded; the parity tests check this against the host. */
