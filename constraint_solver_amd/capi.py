@@ -52,6 +52,8 @@ ABI_SYMBOLS = [
     "xpbd_multi_world_download_owned", "xpbd_multi_world_plan_stats", "xpbd_multi_world_owners",
     "xpbd_world_history_push", "xpbd_world_history_restore", "xpbd_world_history_truncate", "xpbd_world_history_length",
     "xpbd_world_raycast", "xpbd_world_raycast_device", "xpbd_multi_world_raycast",
+    "xpbd_world_set_collision_filters", "xpbd_multi_world_set_collision_filters", "xpbd_world_raycast_masked",
+    "xpbd_world_raycast_masked_device", "xpbd_multi_world_raycast_masked",
 ]
 
 
@@ -99,6 +101,9 @@ JOINT_DISTANCE, JOINT_HINGE = 0, 1
 JOINT_LIMIT_DTYPE = np.dtype([("joint", "<u4"), ("kind", "<u4"), ("ref_a", "<f8", (3,)), ("ref_b", "<f8", (3,)),
                               ("lower", "<f8"), ("upper", "<f8")])
 LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST = 0, 1, 2
+# xpbd_collision_filter as a numpy record (8 bytes): bodies i, j may touch iff group_i & mask_j and group_j & mask_i
+COLLISION_FILTER_DTYPE = np.dtype([("group", "<u4"), ("mask", "<u4")])
+FILTER_JOINTED = 1                # bodies joined by a joint never collide
 # xpbd_gjk_result as a numpy record (96 bytes)
 GJK_DTYPE = np.dtype([("status", "<i4"), ("gjk_iterations", "<u4"), ("epa_iterations", "<u4"), ("reserved", "<u4"),
                       ("depth", "<f8"), ("normal", "<f8", (3,)), ("point_a", "<f8", (3,)), ("point_b", "<f8", (3,))])
@@ -234,6 +239,14 @@ def hip_lib():
         L.xpbd_world_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.xpbd_world_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.xpbd_multi_world_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        try:
+            L.xpbd_world_set_collision_filters.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+            L.xpbd_multi_world_set_collision_filters.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+            L.xpbd_world_raycast_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.xpbd_world_raycast_masked_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.xpbd_multi_world_raycast_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
         _hip = L
     return _hip
 
@@ -406,6 +419,12 @@ class World:
         lim = np.ascontiguousarray(limits, dtype=JOINT_LIMIT_DTYPE)
         _check(hip_lib().xpbd_world_set_joint_limits(self._h, lim.ctypes.data if lim.size else None, lim.size))
 
+    def set_collision_filters(self, filters=None, flags=0):
+        """filters: COLLISION_FILTER_DTYPE records, one per body of the last upload, or None for the default {~0, ~0}
+        (extension); flags: FILTER_JOINTED or 0."""
+        f = _filters(filters)
+        _check(hip_lib().xpbd_world_set_collision_filters(self._h, None if f is None else f.ctypes.data, 0 if f is None else f.size, flags))
+
     def contacts_begin(self, dt):
         _check(hip_lib().xpbd_world_contacts_begin(self._h, dt))
 
@@ -443,23 +462,40 @@ class World:
     def history_length(self):
         return hip_lib().xpbd_world_history_length(self._h)
 
-    def raycast(self, rays, flags=0):
-        """RAY_HIT_DTYPE records of the closest body along every ray (RAY_DTYPE records, see rays()) at the current poses."""
+    def raycast(self, rays, flags=0, mask=None):
+        """RAY_HIT_DTYPE records of the closest body along every ray (RAY_DTYPE records, see rays()) at the current poses.
+        mask: only bodies whose collision-filter group meets it can be hit (None: every body)."""
         r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
         out = np.zeros(r.size, dtype=RAY_HIT_DTYPE)
-        _check(hip_lib().xpbd_world_raycast(self._h, r.ctypes.data if r.size else None, r.size, flags,
-                                            out.ctypes.data if r.size else None))
+        rp, hp = r.ctypes.data if r.size else None, out.ctypes.data if r.size else None
+        if mask is None:
+            _check(hip_lib().xpbd_world_raycast(self._h, rp, r.size, flags, hp))
+        else:
+            _check(hip_lib().xpbd_world_raycast_masked(self._h, rp, r.size, flags, mask, hp))
         return out
 
-    def raycast_device(self, rays_ptr, n, hits_ptr, flags=0):
+    def raycast_device(self, rays_ptr, n, hits_ptr, flags=0, mask=None):
         """Device arrays of n xpbd_ray / xpbd_ray_hit, stream-ordered on the world's stream."""
-        _check(hip_lib().xpbd_world_raycast_device(self._h, C.c_void_p(rays_ptr), n, flags, C.c_void_p(hits_ptr)))
+        if mask is None:
+            _check(hip_lib().xpbd_world_raycast_device(self._h, C.c_void_p(rays_ptr), n, flags, C.c_void_p(hits_ptr)))
+        else:
+            _check(hip_lib().xpbd_world_raycast_masked_device(self._h, C.c_void_p(rays_ptr), n, flags, mask, C.c_void_p(hits_ptr)))
 
     def set_stream(self, stream_ptr):
         _check(hip_lib().xpbd_world_set_stream(self._h, C.c_void_p(stream_ptr)))
 
     def set_mode(self, mode):
         _check(hip_lib().xpbd_world_set_mode(self._h, mode))
+
+
+def _filters(filters):
+    """COLLISION_FILTER_DTYPE records from records or an (n, 2) array of (group, mask); None stays None."""
+    if filters is None:
+        return None
+    f = np.asarray(filters)
+    if f.dtype != COLLISION_FILTER_DTYPE:
+        f = np.ascontiguousarray(f, dtype=np.uint32).reshape(-1, 2).view(COLLISION_FILTER_DTYPE).reshape(-1)
+    return np.ascontiguousarray(f)
 
 
 def polytope_descs(polytopes):
@@ -545,6 +581,12 @@ class MultiWorld:
         lim = np.ascontiguousarray(limits, dtype=JOINT_LIMIT_DTYPE)
         _check(hip_lib().xpbd_multi_world_set_joint_limits(self._h, lim.ctypes.data if lim.size else None, lim.size))
 
+    def set_collision_filters(self, filters=None, flags=0):
+        """World.set_collision_filters over the whole sharded world: n_global records in global body order (not collective)."""
+        f = _filters(filters)
+        _check(hip_lib().xpbd_multi_world_set_collision_filters(self._h, None if f is None else f.ctypes.data, 0 if f is None else f.size,
+                                                                flags))
+
     def upload(self, bodies, shape_id, first_global, n_global, joints=None):
         """bodies / shape_id: the slice of the caller's bodies this process hands over, global indices [first_global,
         first_global + len), in any order: the library decides who owns what."""
@@ -561,12 +603,15 @@ class MultiWorld:
     def replan(self):
         _check(hip_lib().xpbd_multi_world_replan(self._h))
 
-    def raycast(self, rays, flags=0):
+    def raycast(self, rays, flags=0, mask=None):
         """World.raycast over the whole sharded world (collective); bodies and ignore_body are global indices."""
         r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
         out = np.zeros(r.size, dtype=RAY_HIT_DTYPE)
-        _check(hip_lib().xpbd_multi_world_raycast(self._h, r.ctypes.data if r.size else None, r.size, flags,
-                                                  out.ctypes.data if r.size else None))
+        rp, hp = r.ctypes.data if r.size else None, out.ctypes.data if r.size else None
+        if mask is None:
+            _check(hip_lib().xpbd_multi_world_raycast(self._h, rp, r.size, flags, hp))
+        else:
+            _check(hip_lib().xpbd_multi_world_raycast_masked(self._h, rp, r.size, flags, mask, hp))
         return out
 
     def synchronize(self):

@@ -71,6 +71,11 @@ struct ContactBuffers {
     const JointLimit *limits;
     const uint32_t *limit_off;   // [n_joints + 1]
     double max_depenetration_speed; // 0 = off: xpbd_world_set_max_depenetration_speed
+    // collision filters (xpbd_world_set_collision_filters): NULL = none, every pair may touch.  (Last: the kernel arguments
+    // before them keep their offsets, so the kernels of a world without filters load exactly what they loaded before.)
+    const uint2 *filter;    // [n] group, mask of every body
+    uint32_t *slot_filter;  // [2][stride] group, mask of items[s] (bucket order; written only when `filter` is set)
+    uint32_t filter_jointed; // XPBD_FILTER_JOINTED: bodies joined by a joint of `joints` are never neighbours
 };
 
 // Which bodies a per-body kernel of the pipeline works on.  Default: all of them.  The multi-GPU world (xpbd_multi.cpp) runs

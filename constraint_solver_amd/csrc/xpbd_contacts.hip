@@ -297,6 +297,11 @@ __global__ void k_gather_slots(BodyArrays b, ContactBuffers c)
         c.slot_cell[a * st + s] = c.cell[a * st + j];
     }
     c.slot_sphere[3 * st + s] = c.radius[j];
+    if (c.filter) { // (a kernel argument: uniform)
+        const uint2 f = c.filter[j];
+        c.slot_filter[s] = f.x;
+        c.slot_filter[st + s] = f.y;
+    }
 }
 
 constexpr uint32_t kCellLanes = 8;    // lanes per body in the neighbour kernels
@@ -309,13 +314,27 @@ struct CellRanges {
     uint32_t len[kBodiesPerBlock][27];
 };
 
+// A joint of the world links i and j.  joint_list holds every joint at both of its ends, so joined(i, j) == joined(j, i).
+__device__ __forceinline__ bool joined(const ContactBuffers &c, uint32_t i, uint32_t j)
+{
+    for (uint32_t k = c.joint_off[i]; k < c.joint_off[i + 1]; ++k) {
+        const Joint &jt = c.joints[c.joint_list[k]];
+        if ((jt.body_a == i ? jt.body_b : jt.body_a) == j)
+            return true;
+    }
+    return false;
+}
+
 // Neighbour search of body i by its group of kCellLanes lanes (`cl` = lane inside the group, `g` = the group's row in
 // the LDS tables).  First the 27 bucket ranges are fetched side by side; then the lanes stride over the CONCATENATION
 // of the 27 ranges, so every lane has independent loads in flight whatever the occupancy of the single cells.
 // Several cells can share a bucket, so a candidate counts only when it sits in the cell being visited: every
 // overlapping j != i is visited exactly once, by exactly one lane.  Must be called by all lanes of the block
 // (`live` = false for the groups past the last body): it contains a barrier.
-template <class Visit>
+// FILTER: a pair whose collision filters exclude each other is no neighbour (the candidate's filter is read in slot order,
+// next to its sphere); JOINTED: nor is a pair joined by a joint.  Both tests are symmetric in i and j -- count, fill and
+// the pair index of both ends rely on every pair being seen from both of them or from neither.
+template <bool FILTER, bool JOINTED, class Visit>
 __device__ __forceinline__ void for_each_neighbour(const BodyArrays &b, const ContactBuffers &c, CellRanges &r, uint32_t i, bool live,
                                                    uint32_t g, uint32_t cl, Visit visit)
 {
@@ -337,6 +356,9 @@ __device__ __forceinline__ void for_each_neighbour(const BodyArrays &b, const Co
         return;
     const Vec3 ci = load3(c.centers, 0, b.stride, i);
     const double ri = c.radius[i];
+    uint2 fi = {0u, 0u};
+    if (FILTER)
+        fi = c.filter[i];
     uint32_t k = 0, base = 0; // cell being walked and the position of its first candidate in the concatenation
     for (uint32_t q = cl;; q += kCellLanes) {
         while (k < 27 && q >= base + r.len[g][k])
@@ -352,8 +374,13 @@ __device__ __forceinline__ void for_each_neighbour(const BodyArrays &b, const Co
             continue;
         const Vec3 d = ci - load3(c.slot_sphere, 0, b.stride, s);
         const double reach = ri + c.slot_sphere[3 * st + s];
-        if (dot(d, d) < reach * reach)
-            visit(j);
+        if (!(dot(d, d) < reach * reach))
+            continue;
+        if (FILTER && !((fi.x & c.slot_filter[st + s]) && (c.slot_filter[s] & fi.y)))
+            continue;
+        if (JOINTED && joined(c, i, j))
+            continue;
+        visit(j);
     }
 }
 
@@ -365,6 +392,7 @@ __device__ __forceinline__ uint32_t cell_group_sum(uint32_t v)
 }
 
 // Counts of all neighbours of every body and of those with a larger id.
+template <bool FILTER, bool JOINTED>
 __global__ void __launch_bounds__(kBlock) k_neighbour_count(BodyArrays b, ContactBuffers c)
 {
     __shared__ CellRanges ranges;
@@ -375,7 +403,7 @@ __global__ void __launch_bounds__(kBlock) k_neighbour_count(BodyArrays b, Contac
     const bool live = slot < b.n;
     const uint32_t i = (live && c.grid->dense) ? c.items[slot] : slot;
     uint32_t all = 0, upper = 0;
-    for_each_neighbour(b, c, ranges, i, live, g, cl, [&](uint32_t j) {
+    for_each_neighbour<FILTER, JOINTED>(b, c, ranges, i, live, g, cl, [&](uint32_t j) {
         ++all;
         upper += j > i;
     });
@@ -392,6 +420,7 @@ __global__ void __launch_bounds__(kBlock) k_neighbour_count(BodyArrays b, Contac
 // Neighbour list of every body, ASCENDING, the pair list i < j in (i, j) order, and upper_start.  The lanes append
 // their finds to an LDS list in arrival order; a rank sort (ids are distinct) then gives every entry its final
 // place, so the result does not depend on that order.  Lists longer than kNbrStage take a one-lane path.
+template <bool FILTER, bool JOINTED>
 __global__ void __launch_bounds__(kBlock) k_neighbour_fill(BodyArrays b, ContactBuffers c)
 {
     __shared__ CellRanges ranges;
@@ -409,7 +438,7 @@ __global__ void __launch_bounds__(kBlock) k_neighbour_fill(BodyArrays b, Contact
     const bool staged = total <= kNbrStage;
     if (cl == 0)
         cursor[g] = 0; // for_each_neighbour's barrier comes before the first visit
-    for_each_neighbour(b, c, ranges, i, live, g, cl, [&](uint32_t j) {
+    for_each_neighbour<FILTER, JOINTED>(b, c, ranges, i, live, g, cl, [&](uint32_t j) {
         const uint32_t pos = atomicAdd(&cursor[g], 1u);
         if (staged)
             stage[g][pos] = j;
@@ -1300,10 +1329,24 @@ hipError_t launch_build_buckets(const BodyArrays &b, const ContactBuffers &c, hi
     return hipGetLastError();
 }
 
+// Which form of the neighbour kernels a broadphase runs: bit 0 = group / mask test, bit 1 = jointed-pair test (only when
+// there are joints).  A world without filters runs the plain form, the loads of which are those of a world before filters.
+static uint32_t filter_variant(const ContactBuffers &c)
+{
+    return (c.filter ? 1u : 0u) | (c.filter_jointed && c.joint_off ? 2u : 0u);
+}
+
 hipError_t launch_neighbour_count(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream)
 {
-    if (b.n)
-        hipLaunchKernelGGL(k_neighbour_count, dim3((b.n + kBodiesPerBlock - 1) / kBodiesPerBlock), dim3(kBlock), 0, stream, b, c);
+    if (b.n) {
+        const dim3 grid((b.n + kBodiesPerBlock - 1) / kBodiesPerBlock);
+        switch (filter_variant(c)) {
+        case 0: hipLaunchKernelGGL((k_neighbour_count<false, false>), grid, dim3(kBlock), 0, stream, b, c); break;
+        case 1: hipLaunchKernelGGL((k_neighbour_count<true, false>), grid, dim3(kBlock), 0, stream, b, c); break;
+        case 2: hipLaunchKernelGGL((k_neighbour_count<false, true>), grid, dim3(kBlock), 0, stream, b, c); break;
+        default: hipLaunchKernelGGL((k_neighbour_count<true, true>), grid, dim3(kBlock), 0, stream, b, c); break;
+        }
+    }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = launch_exclusive_scan(c.nbr_off, b.n, c.scan_scratch, stream);
@@ -1316,7 +1359,13 @@ hipError_t launch_neighbour_fill(const BodyArrays &b, const ContactBuffers &c, h
 {
     if (b.n == 0)
         return hipSuccess;
-    hipLaunchKernelGGL(k_neighbour_fill, dim3((b.n + kBodiesPerBlock - 1) / kBodiesPerBlock), dim3(kBlock), 0, stream, b, c);
+    const dim3 grid((b.n + kBodiesPerBlock - 1) / kBodiesPerBlock);
+    switch (filter_variant(c)) {
+    case 0: hipLaunchKernelGGL((k_neighbour_fill<false, false>), grid, dim3(kBlock), 0, stream, b, c); break;
+    case 1: hipLaunchKernelGGL((k_neighbour_fill<true, false>), grid, dim3(kBlock), 0, stream, b, c); break;
+    case 2: hipLaunchKernelGGL((k_neighbour_fill<false, true>), grid, dim3(kBlock), 0, stream, b, c); break;
+    default: hipLaunchKernelGGL((k_neighbour_fill<true, true>), grid, dim3(kBlock), 0, stream, b, c); break;
+    }
     hipLaunchKernelGGL(k_neighbour_pair_index, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
     return hipGetLastError();
 }

@@ -65,7 +65,10 @@ int check_raycast(const char *who, const xpbd_world *w, const void *rays, uint32
 int check_rays_reserved(const char *who, const xpbd_ray *rays, uint32_t n_rays);
 // Ray casts of the world's bodies, stream-ordered (device arrays) / from and to host arrays (waits).  dev_global_id: device
 // array of w's body count, the index each body is known by (XPBD_NO_HIT: the body does not answer); NULL: its slot.
-int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits, const uint32_t *dev_global_id);
-int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id);
+// masked: only bodies whose collision-filter group meets `mask` answer (xpbd_world_raycast_masked); else every body does.
+int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits, const uint32_t *dev_global_id,
+                    bool masked, uint32_t mask);
+int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id,
+                 bool masked, uint32_t mask);
 int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits);
 } // namespace xpbd

@@ -708,6 +708,8 @@ struct xpbd_multi_world {
     uint32_t n_global = 0, first_global = 0, n_bodies = 0, capacity = 1;
     std::vector<xpbd_joint> joints;
     std::vector<xpbd_joint_limit> limits; // xpbd_multi_world_set_joint_limits: GLOBAL joint indices
+    std::vector<xpbd_collision_filter> filters; // xpbd_multi_world_set_collision_filters: [n_global] or empty (none)
+    uint32_t filter_flags = 0;
     std::vector<uint8_t> owner;        // [n_global] as of the last plan
     std::vector<uint32_t> owned_count; // [n_ranks]
     uint64_t plans = 0, rollbacks = 0, migrated = 0, steps = 0, ns_enqueue = 0, ns_wait_broadphase = 0, ns_wait_frame = 0, ns_plan = 0;
@@ -1025,6 +1027,18 @@ int push_joint_limits(const xpbd_multi_world *mw, const Shard &s)
     return xpbd_world_set_joint_limits(s.world, local.data(), (uint32_t)local.size());
 }
 
+// The world's collision filters on the bodies of shard s (local_ids: global id of every local slot, owned bodies and ghosts
+// alike -- an owned-ghost pair is decided on this shard).
+int push_collision_filters(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &local_ids)
+{
+    if (mw->filters.empty())
+        return xpbd_world_set_collision_filters(s.world, nullptr, 0, mw->filter_flags);
+    std::vector<xpbd_collision_filter> local(local_ids.size());
+    for (size_t q = 0; q < local_ids.size(); ++q)
+        local[q] = mw->filters[local_ids[q]];
+    return xpbd_world_set_collision_filters(s.world, local.data(), (uint32_t)local.size(), mw->filter_flags);
+}
+
 // The second half of every plan: the boundary lists of all ranks fix the rows of the per-substep all-gather, the records of
 // the bodies that change hands or are mirrored travel, and every shard's local world is re-packed on its device.  Collective.
 int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &plans, double edge, PlanTrace &trace)
@@ -1189,6 +1203,8 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
             return rc;
         s.joint_ids = std::move(joint_ids);
         if (int rc = push_joint_limits(mw, s))
+            return rc;
+        if (int rc = push_collision_filters(mw, s, local_ids))
             return rc;
         MW_HIP_TRY(hipStreamSynchronize(s.stream));
         trace.lap("  joints");
@@ -1943,7 +1959,7 @@ void destroy(xpbd_multi_world *mw)
 }
 
 // One shard's part of a ray cast: its OWNED bodies answer, under their global ids (ghosts are listed as XPBD_NO_HIT).
-int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
+int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, bool masked, uint32_t mask, xpbd_ray_hit *hits)
 {
     MW_TRY(bind(s));
     std::vector<uint32_t> ids(s.local_ids);
@@ -1956,7 +1972,7 @@ int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flag
     }
     MW_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
     MW_TRY(upload_vector(s.query_ids, ids, s.stream));
-    return xpbd::raycast_host(s.world, rays, n_rays, flags, hits, s.query_ids.as<uint32_t>());
+    return xpbd::raycast_host(s.world, rays, n_rays, flags, hits, s.query_ids.as<uint32_t>(), masked, mask);
 }
 
 int check_usable(const xpbd_multi_world *mw, const char *who)
@@ -1965,6 +1981,49 @@ int check_usable(const xpbd_multi_world *mw, const char *who)
         return set_error(XPBD_E_INVALID, "%s: NULL world", who);
     if (mw->broken)
         return set_error(XPBD_E_HIP, "%s: a collective of this world failed earlier; destroy it on every rank", who);
+    return XPBD_OK;
+}
+
+// xpbd_multi_world_raycast(_masked), named `who` in its errors.
+int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, bool masked, uint32_t mask,
+                  xpbd_ray_hit *hits)
+{
+    MW_TRY(check_usable(mw, who));
+    if (n_rays && (!rays || !hits))
+        return set_error(XPBD_E_INVALID, "%s: NULL rays or hits", who);
+    if (flags & ~XPBD_RAYCAST_BRUTE_FORCE)
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (!mw->have_shapes)
+        return set_error(XPBD_E_INVALID, "%s: call xpbd_multi_world_set_polytopes first", who);
+    MW_TRY(xpbd::check_rays_reserved(who, rays, n_rays));
+    if (!mw->planned)
+        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    if (n_rays == 0)
+        return XPBD_OK;
+    // every local shard casts against its owned bodies; one all-gather of the hit records (with every rank's status) over
+    // all ranks, then every rank merges the n_ranks rows by the (t, global index) rule of a single world
+    LocalStatus st;
+    const size_t bytes = (size_t)n_rays * sizeof(xpbd_ray_hit);
+    std::vector<std::vector<xpbd_ray_hit>> mine(mw->shards.size(), std::vector<xpbd_ray_hit>(n_rays));
+    std::vector<const void *> send;
+    for (size_t k = 0; k < mw->shards.size(); ++k) {
+        if (st.ok())
+            st.keep(shard_raycast(mw->shards[k], rays, n_rays, flags, masked, mask, mine[k].data()));
+        send.push_back(mine[k].data());
+    }
+    std::vector<uint8_t> all;
+    MW_TRY(all_gather_host(mw, send, bytes, all, st));
+    for (uint32_t r = 0; r < n_rays; ++r) {
+        xpbd_ray_hit best;
+        std::memcpy(&best, all.data() + (size_t)r * sizeof(xpbd_ray_hit), sizeof best);
+        for (uint32_t k = 1; k < mw->n_ranks; ++k) {
+            xpbd_ray_hit h;
+            std::memcpy(&h, all.data() + (size_t)k * bytes + (size_t)r * sizeof(xpbd_ray_hit), sizeof h);
+            if (h.distance < best.distance || (h.distance == best.distance && h.body < best.body))
+                best = h;
+        }
+        hits[r] = best;
+    }
     return XPBD_OK;
 }
 
@@ -2164,6 +2223,36 @@ int xpbd_multi_world_set_joint_limits(xpbd_multi_world *mw, const xpbd_joint_lim
     return XPBD_OK;
 }
 
+int xpbd_multi_world_set_collision_filters(xpbd_multi_world *mw, const xpbd_collision_filter *filters, uint32_t n_global, uint32_t flags)
+{
+    MW_TRY(check_usable(mw, "xpbd_multi_world_set_collision_filters"));
+    if (!filters && n_global)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_collision_filters: NULL filters with n_global = %u", n_global);
+    if (filters && n_global != mw->n_global)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_collision_filters: n_global = %u but the world holds %u bodies", n_global,
+                         mw->n_global);
+    if (flags & ~XPBD_FILTER_JOINTED)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_collision_filters: unknown flags 0x%x", flags);
+    if (filters && n_global)
+        mw->filters.assign(filters, filters + n_global);
+    else
+        mw->filters.clear();
+    mw->filter_flags = flags;
+    if (!mw->planned)
+        return XPBD_OK; // the plan hands them to the shards
+    for (Shard &s : mw->shards) {
+        int rc = bind(s);
+        if (rc == XPBD_OK)
+            rc = push_collision_filters(mw, s, s.local_ids);
+        if (rc != XPBD_OK) { // (checked above: only a device failure gets here, and the shards disagree now)
+            const std::string msg = xpbd_last_error();
+            mw->broken = true;
+            return set_error(rc, "%s -- the shards' collision filters disagree now: destroy this xpbd_multi_world", msg.c_str());
+        }
+    }
+    return XPBD_OK;
+}
+
 int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, const uint32_t *shape_id, uint32_t first_global, uint32_t n_bodies,
                             uint32_t n_global, const xpbd_joint *joints, uint32_t n_joints)
 {
@@ -2188,6 +2277,8 @@ int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, cons
     mw->n_global = n_global, mw->first_global = first_global, mw->n_bodies = n_bodies;
     mw->joints.assign(joints, joints + n_joints);
     mw->limits.clear(); // limits name joints by index: a new upload invalidates them
+    mw->filters.clear(); // filters name bodies by index
+    mw->filter_flags = 0;
     mw->planned = false;
     mw->cuts_valid = false; // the first plan is a full one
     mw->check_plans = std::getenv("XPBD_MULTI_CHECK_PLANS") != nullptr;
@@ -2303,43 +2394,13 @@ int xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps)
 
 int xpbd_multi_world_raycast(xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
 {
-    MW_TRY(check_usable(mw, "xpbd_multi_world_raycast"));
-    if (n_rays && (!rays || !hits))
-        return set_error(XPBD_E_INVALID, "xpbd_multi_world_raycast: NULL rays or hits");
-    if (flags & ~XPBD_RAYCAST_BRUTE_FORCE)
-        return set_error(XPBD_E_INVALID, "xpbd_multi_world_raycast: unknown flags 0x%x", flags);
-    if (!mw->have_shapes)
-        return set_error(XPBD_E_INVALID, "xpbd_multi_world_raycast: call xpbd_multi_world_set_polytopes first");
-    MW_TRY(xpbd::check_rays_reserved("xpbd_multi_world_raycast", rays, n_rays));
-    if (!mw->planned)
-        return set_error(XPBD_E_INVALID, "xpbd_multi_world_raycast: no bodies uploaded");
-    if (n_rays == 0)
-        return XPBD_OK;
-    // every local shard casts against its owned bodies; one all-gather of the hit records (with every rank's status) over
-    // all ranks, then every rank merges the n_ranks rows by the (t, global index) rule of a single world
-    LocalStatus st;
-    const size_t bytes = (size_t)n_rays * sizeof(xpbd_ray_hit);
-    std::vector<std::vector<xpbd_ray_hit>> mine(mw->shards.size(), std::vector<xpbd_ray_hit>(n_rays));
-    std::vector<const void *> send;
-    for (size_t k = 0; k < mw->shards.size(); ++k) {
-        if (st.ok())
-            st.keep(shard_raycast(mw->shards[k], rays, n_rays, flags, mine[k].data()));
-        send.push_back(mine[k].data());
-    }
-    std::vector<uint8_t> all;
-    MW_TRY(all_gather_host(mw, send, bytes, all, st));
-    for (uint32_t r = 0; r < n_rays; ++r) {
-        xpbd_ray_hit best;
-        std::memcpy(&best, all.data() + (size_t)r * sizeof(xpbd_ray_hit), sizeof best);
-        for (uint32_t k = 1; k < mw->n_ranks; ++k) {
-            xpbd_ray_hit h;
-            std::memcpy(&h, all.data() + (size_t)k * bytes + (size_t)r * sizeof(xpbd_ray_hit), sizeof h);
-            if (h.distance < best.distance || (h.distance == best.distance && h.body < best.body))
-                best = h;
-        }
-        hits[r] = best;
-    }
-    return XPBD_OK;
+    return multi_raycast("xpbd_multi_world_raycast", mw, rays, n_rays, flags, false, 0u, hits);
+}
+
+int xpbd_multi_world_raycast_masked(xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, uint32_t mask,
+                                    xpbd_ray_hit *hits)
+{
+    return multi_raycast("xpbd_multi_world_raycast_masked", mw, rays, n_rays, flags, true, mask, hits);
 }
 
 int xpbd_multi_world_synchronize(xpbd_multi_world *mw)

@@ -42,10 +42,18 @@ struct QuerySizes {
 // What a call over n bodies and n_rays rays needs (brute: whether it takes the brute-force path).
 QuerySizes query_scratch_bytes(uint32_t n, uint32_t n_rays, bool brute);
 
+// The collision-filter test of a masked ray cast: with `masked`, body i answers only if (group_i & mask) != 0, group_i =
+// filter[i].x (filter == NULL: every body is in group ~0u).  Without it no group is tested.
+struct RayFilter {
+    const uint2 *filter;
+    uint32_t mask;
+    uint32_t masked;
+};
+
 // Casts n_rays rays (device xpbd_ray) against the bodies of `b` and writes n_rays xpbd_ray_hit.  global_id (device, n entries,
 // or null): the index a body is known by -- the tie-break and what ignore_body and hit.body mean -- and XPBD_NO_HIT for a
-// body that must not answer; null: the body's slot.
-hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const void *rays,
+// body that must not answer; null: the body's slot.  A body the filter drops answers no ray, as a ghost does.
+hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const RayFilter &filter, const void *rays,
                           uint32_t n_rays, bool brute, const QueryScratch &s, void *hits, hipStream_t stream);
 
 } // namespace xpbd

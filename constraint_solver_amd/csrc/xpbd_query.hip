@@ -197,7 +197,7 @@ __device__ __forceinline__ void write_hit(const Ray &ray, const Best &best, cons
 // ---- grid build -------------------------------------------------------------------------------------------------------
 // Inverse frame and bounding sphere of every body, and per workgroup the largest radius and the box of the spheres.
 __global__ void __launch_bounds__(kBlock) k_query_bodies(BodyArrays b, PolytopeTables t, const uint32_t *__restrict__ gid,
-                                                         double *__restrict__ rec, double *__restrict__ partials)
+                                                         RayFilter filter, double *__restrict__ rec, double *__restrict__ partials)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     double v[7] = {0.0, DBL_MAX, DBL_MAX, DBL_MAX, -DBL_MAX, -DBL_MAX, -DBL_MAX}; // rmax, min xyz, max xyz
@@ -211,7 +211,8 @@ __global__ void __launch_bounds__(kBlock) k_query_bodies(BodyArrays b, PolytopeT
         const bool finite = isfinite(f.position.x) && isfinite(f.position.y) && isfinite(f.position.z) && isfinite(f.rotation.s) &&
                             isfinite(f.rotation.x) && isfinite(f.rotation.y) && isfinite(f.rotation.z) && isfinite(c.x) &&
                             isfinite(c.y) && isfinite(c.z);
-        const bool able = finite && (!gid || gid[i] != XPBD_NO_HIT);
+        const uint32_t group = filter.filter ? filter.filter[i].x : ~0u;
+        const bool able = finite && (!gid || gid[i] != XPBD_NO_HIT) && (!filter.masked || (group & filter.mask) != 0);
         double2 *o = reinterpret_cast<double2 *>(rec + (size_t)i * kQueryRecDoubles);
         o[0] = double2{inv.position.x, inv.position.y};
         o[1] = double2{inv.position.z, inv.rotation.s};
@@ -523,7 +524,7 @@ QuerySizes query_scratch_bytes(uint32_t n, uint32_t n_rays, bool brute)
     return q;
 }
 
-hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const void *rays_v, uint32_t n_rays,
+hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const RayFilter &filter, const void *rays_v, uint32_t n_rays,
                           bool brute, const QueryScratch &s, void *hits_v, hipStream_t stream)
 {
     if (n_rays == 0)
@@ -532,7 +533,7 @@ hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const ui
     xpbd_ray_hit *hits = static_cast<xpbd_ray_hit *>(hits_v);
     QueryGrid *grid = static_cast<QueryGrid *>(s.grid);
     if (b.n)
-        hipLaunchKernelGGL(k_query_bodies, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b, t, global_id, s.rec, s.partials);
+        hipLaunchKernelGGL(k_query_bodies, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b, t, global_id, filter, s.rec, s.partials);
     if (brute || b.n == 0) {
         const uint32_t tiles = (n_rays + kBruteRays - 1) / kBruteRays, chunks = brute_chunks(b.n, n_rays);
         const uint32_t chunk_len = (b.n + chunks - 1) / chunks;

@@ -179,6 +179,10 @@ struct xpbd_world {
     std::vector<xpbd_joint> joints_host; // the joints of the last set_joints: what xpbd_world_set_joint_limits checks against
     DeviceBuffer jt_limits, jt_limit_off;
     uint32_t n_limits = 0;
+    // collision filters (xpbd_world_set_collision_filters): group, mask per body (has_filters), XPBD_FILTER_* flags
+    DeviceBuffer ft_filters, cb_slot_filter;
+    bool has_filters = false;
+    uint32_t filter_flags = 0;
     // scene queries (xpbd_world_raycast*): scratch of one call, and the staging of the host variant's rays and hits
     DeviceBuffer q_rec, q_partials, q_grid, q_cell_start, q_cell_fill, q_items, q_scan, q_brute, q_rays, q_hits;
     // state history (xpbd_world_history_*): `history_length` slots of history_slot_bytes() in one growing block
@@ -230,6 +234,9 @@ struct xpbd_world {
         c.joint_list = n_joints ? jt_list.as<uint32_t>() : nullptr;
         c.limits = n_limits ? jt_limits.as<xpbd::JointLimit>() : nullptr;
         c.limit_off = n_limits ? jt_limit_off.as<uint32_t>() : nullptr;
+        c.filter = has_filters ? ft_filters.as<uint2>() : nullptr;
+        c.slot_filter = has_filters ? cb_slot_filter.as<uint32_t>() : nullptr;
+        c.filter_jointed = (filter_flags & XPBD_FILTER_JOINTED) ? 1u : 0u;
         c.max_depenetration_speed = max_depenetration_speed;
         return c;
     }
@@ -299,6 +306,8 @@ int build_neighbours_enqueue(xpbd_world *w, double dt)
     XPBD_HIP_TRY(w->cb_items_unsorted.reserve((size_t)st * 4));
     XPBD_HIP_TRY(w->cb_slot_sphere.reserve((size_t)4 * st * 8));
     XPBD_HIP_TRY(w->cb_slot_cell.reserve((size_t)3 * st * 4));
+    if (w->has_filters)
+        XPBD_HIP_TRY(w->cb_slot_filter.reserve((size_t)2 * st * 4));
     XPBD_HIP_TRY(w->cb_nbr_off.reserve((size_t)(st + 1) * 4));
     XPBD_HIP_TRY(w->cb_pair_first.reserve((size_t)(st + 1) * 4));
     XPBD_HIP_TRY(w->cb_upper_start.reserve((size_t)st * 4));
@@ -725,6 +734,8 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     w->n_joints = 0;
     w->joints_host.clear();
     w->n_limits = 0;
+    w->has_filters = false;
+    w->filter_flags = 0;
     w->history_length = 0;
     w->history_stepped.clear();
     w->n = n_new;
@@ -825,7 +836,7 @@ int check_rays_reserved(const char *who, const xpbd_ray *rays, uint32_t n_rays)
 }
 
 int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits,
-                    const uint32_t *dev_global_id)
+                    const uint32_t *dev_global_id, bool masked, uint32_t mask)
 {
     static_assert(sizeof(xpbd_ray) == 64 && sizeof(xpbd_ray_hit) == 64, "xpbd_ray and xpbd_ray_hit are 64 bytes");
     if (n_rays == 0)
@@ -848,11 +859,13 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
     }
     const QueryScratch s{w->q_rec.as<double>(), w->q_partials.as<double>(), w->q_grid.ptr, w->q_cell_start.as<uint32_t>(),
                          w->q_cell_fill.as<uint32_t>(), w->q_items.as<uint32_t>(), w->q_scan.as<uint32_t>(), w->q_brute.ptr, q.table_size};
-    XPBD_HIP_TRY(launch_raycast(w->arrays(), w->tables(), dev_global_id, dev_rays, n_rays, brute, s, dev_hits, w->stream));
+    const RayFilter filter{masked && w->has_filters ? w->ft_filters.as<uint2>() : nullptr, mask, masked ? 1u : 0u};
+    XPBD_HIP_TRY(launch_raycast(w->arrays(), w->tables(), dev_global_id, filter, dev_rays, n_rays, brute, s, dev_hits, w->stream));
     return XPBD_OK;
 }
 
-int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id)
+int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id,
+                 bool masked, uint32_t mask)
 {
     if (n_rays == 0)
         return XPBD_OK;
@@ -865,7 +878,7 @@ int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t 
         XPBD_HIP_TRY(w->q_hits.reserve(bytes));
     }
     XPBD_HIP_TRY(hipMemcpyAsync(w->q_rays.ptr, rays, bytes, hipMemcpyHostToDevice, w->stream));
-    if (int rc = raycast_enqueue(w, w->q_rays.as<xpbd_ray>(), n_rays, flags, w->q_hits.as<xpbd_ray_hit>(), dev_global_id))
+    if (int rc = raycast_enqueue(w, w->q_rays.as<xpbd_ray>(), n_rays, flags, w->q_hits.as<xpbd_ray_hit>(), dev_global_id, masked, mask))
         return rc;
     XPBD_HIP_TRY(hipMemcpyAsync(hits, w->q_hits.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
@@ -968,7 +981,8 @@ void xpbd_world_destroy(xpbd_world *w)
                             &w->gjk_pairs_scratch, &w->cb_slot_sphere, &w->cb_slot_cell, &w->history,
                             &w->sat_counters, &w->sat_survivors, &w->sat_axis_cache, &w->gjk_axis_cache, &w->cb_stat_shape, &w->cb_pair_codes, &w->cb_rec_b,
                             &w->cb_grid_partials, &w->cb_items_unsorted, &w->q_rec, &w->q_partials, &w->q_grid, &w->q_cell_start,
-                            &w->q_cell_fill, &w->q_items, &w->q_scan, &w->q_brute, &w->q_rays, &w->q_hits})
+                            &w->q_cell_fill, &w->q_items, &w->q_scan, &w->q_brute, &w->q_rays, &w->q_hits, &w->ft_filters,
+                            &w->cb_slot_filter})
         b->release();
     for (DeviceBuffer *b : {&w->frame_snapshot, &w->repack_aos, &w->repack_shape, &w->repack_src, &w->repack_incoming, &w->halo_keys, &w->halo_records})
         b->release();
@@ -1222,9 +1236,11 @@ int xpbd_world_upload_bodies(xpbd_world *w, const xpbd_rigid *aos, const uint32_
     const uint32_t stride = round_up(n ? n : 1, 256);
     XPBD_HIP_TRY(w->dyn.reserve((size_t)xpbd::kDynFields * stride * 8));
     w->have_neighbours = false;
-    w->n_joints = 0; // joints name bodies by index: a new upload invalidates them (and their limits)
+    w->n_joints = 0; // joints name bodies by index: a new upload invalidates them (and their limits), and so do filters
     w->joints_host.clear();
     w->n_limits = 0;
+    w->has_filters = false;
+    w->filter_flags = 0;
     w->history_length = 0;
     w->history_stepped.clear();
     XPBD_HIP_TRY(w->stat.reserve((size_t)xpbd::kStatFields * stride * 8));
@@ -1562,6 +1578,32 @@ int xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, u
     return XPBD_OK;
 }
 
+int xpbd_world_set_collision_filters(xpbd_world *w, const xpbd_collision_filter *filters, uint32_t n, uint32_t flags)
+{
+    static_assert(sizeof(xpbd_collision_filter) == sizeof(uint2), "xpbd_collision_filter must mirror uint2 {group, mask}");
+    if (!w)
+        return fail(XPBD_E_INVALID, "xpbd_world_set_collision_filters: NULL world");
+    if (!filters && n)
+        return fail(XPBD_E_INVALID, "xpbd_world_set_collision_filters: NULL filters with n = %u", n);
+    if (filters && n != w->n)
+        return fail(XPBD_E_INVALID, "xpbd_world_set_collision_filters: n = %u but the world holds %u bodies", n, w->n);
+    if (flags & ~XPBD_FILTER_JOINTED)
+        return fail(XPBD_E_INVALID, "xpbd_world_set_collision_filters: unknown flags 0x%x", flags);
+    if (int rc = bind_device(w))
+        return rc;
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued broadphases may still read the present filters
+    w->filter_flags = flags;
+    if (!filters || n == 0) {
+        w->has_filters = false;
+        return XPBD_OK;
+    }
+    XPBD_HIP_TRY(w->ft_filters.reserve((size_t)n * sizeof(uint2)));
+    w->has_filters = false; // (a failed copy below leaves none rather than a torn table)
+    XPBD_HIP_TRY(hipMemcpy(w->ft_filters.ptr, filters, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice));
+    w->has_filters = true;
+    return XPBD_OK;
+}
+
 int xpbd_world_contacts_begin(xpbd_world *w, double dt)
 {
     if (!w)
@@ -1802,14 +1844,31 @@ int xpbd_world_raycast(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uin
         return rc;
     if (int rc = xpbd::check_rays_reserved("xpbd_world_raycast", rays, n_rays))
         return rc;
-    return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr);
+    return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr, false, 0u);
+}
+
+int xpbd_world_raycast_masked(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, uint32_t mask, xpbd_ray_hit *hits)
+{
+    if (int rc = xpbd::check_raycast("xpbd_world_raycast_masked", w, rays, n_rays, flags, hits))
+        return rc;
+    if (int rc = xpbd::check_rays_reserved("xpbd_world_raycast_masked", rays, n_rays))
+        return rc;
+    return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr, true, mask);
 }
 
 int xpbd_world_raycast_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits)
 {
     if (int rc = xpbd::check_raycast("xpbd_world_raycast_device", w, dev_rays, n_rays, flags, dev_hits))
         return rc;
-    return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr);
+    return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr, false, 0u);
+}
+
+int xpbd_world_raycast_masked_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, uint32_t mask,
+                                     xpbd_ray_hit *dev_hits)
+{
+    if (int rc = xpbd::check_raycast("xpbd_world_raycast_masked_device", w, dev_rays, n_rays, flags, dev_hits))
+        return rc;
+    return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr, true, mask);
 }
 
 int xpbd_selftest_div_sqrt(int32_t device, const double *a, const double *b, double *quotient, double *root,

@@ -108,6 +108,22 @@ pub struct XpbdJointLimit {
     pub upper: f64,
 }
 
+/// EXTENSION: collision filter of one body: bodies i, j may touch iff group_i & mask_j != 0 && group_j & mask_i != 0.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct XpbdCollisionFilter {
+    pub group: u32, // the layers this body is in
+    pub mask: u32,  // the layers it collides with
+}
+
+impl Default for XpbdCollisionFilter {
+    fn default() -> Self {
+        XpbdCollisionFilter { group: !0u32, mask: !0u32 }
+    }
+}
+
+pub const XPBD_FILTER_JOINTED: u32 = 1;
+
 /// EXTENSION: result of the GJK + EPA narrowphase for one pair.
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -277,6 +293,15 @@ extern "C" {
         -> c_int;
     pub fn xpbd_multi_world_raycast(mw: *mut XpbdMultiWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, hits: *mut XpbdRayHit)
         -> c_int;
+    pub fn xpbd_world_set_collision_filters(w: *mut XpbdWorld, filters: *const XpbdCollisionFilter, n: u32, flags: u32) -> c_int;
+    pub fn xpbd_multi_world_set_collision_filters(mw: *mut XpbdMultiWorld, filters: *const XpbdCollisionFilter, n_global: u32, flags: u32)
+        -> c_int;
+    pub fn xpbd_world_raycast_masked(w: *mut XpbdWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32, hits: *mut XpbdRayHit)
+        -> c_int;
+    pub fn xpbd_world_raycast_masked_device(w: *mut XpbdWorld, dev_rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32,
+                                            dev_hits: *mut XpbdRayHit) -> c_int;
+    pub fn xpbd_multi_world_raycast_masked(mw: *mut XpbdMultiWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32,
+                                           hits: *mut XpbdRayHit) -> c_int;
 }
 
 fn v3(v: Vector3<f64>) -> [f64; 3] {

@@ -507,6 +507,19 @@ class BatchWorld {
         check(xpbd_world_raycast(w_, rays.empty() ? nullptr : rays.data(), (uint32_t)rays.size(), flags, hits.empty() ? nullptr : hits.data()));
         return hits;
     }
+    // ... against the bodies whose collision-filter group meets `mask` only
+    std::vector<xpbd_ray_hit> raycast_masked(const std::vector<xpbd_ray> &rays, uint32_t mask, uint32_t flags = 0)
+    {
+        std::vector<xpbd_ray_hit> hits(rays.size());
+        check(xpbd_world_raycast_masked(w_, rays.empty() ? nullptr : rays.data(), (uint32_t)rays.size(), flags, mask,
+                                        hits.empty() ? nullptr : hits.data()));
+        return hits;
+    }
+    // collision filters, one per body (empty: every body {~0u, ~0u}); flags: XPBD_FILTER_JOINTED or 0.  Upload clears them.
+    void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)
+    {
+        check(xpbd_world_set_collision_filters(w_, filters.empty() ? nullptr : filters.data(), (uint32_t)filters.size(), flags));
+    }
 
     std::vector<xpbd_contact> contacts()
     {
@@ -588,6 +601,18 @@ class ShardedWorld {
         std::vector<xpbd_ray_hit> hits(rays.size());
         check(xpbd_multi_world_raycast(w_, rays.empty() ? nullptr : rays.data(), (uint32_t)rays.size(), flags, hits.empty() ? nullptr : hits.data()));
         return hits;
+    }
+    std::vector<xpbd_ray_hit> raycast_masked(const std::vector<xpbd_ray> &rays, uint32_t mask, uint32_t flags = 0)
+    {
+        std::vector<xpbd_ray_hit> hits(rays.size());
+        check(xpbd_multi_world_raycast_masked(w_, rays.empty() ? nullptr : rays.data(), (uint32_t)rays.size(), flags, mask,
+                                              hits.empty() ? nullptr : hits.data()));
+        return hits;
+    }
+    // collision filters of the whole world, global body order (not collective); upload clears them
+    void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)
+    {
+        check(xpbd_multi_world_set_collision_filters(w_, filters.empty() ? nullptr : filters.data(), (uint32_t)filters.size(), flags));
     }
     void synchronize() { check(xpbd_multi_world_synchronize(w_)); }
     void download(std::vector<rigid::Rigid> &bodies)

@@ -327,6 +327,32 @@ typedef struct xpbd_joint_limit {
 } xpbd_joint_limit;          /* 72 bytes */
 int  xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, uint32_t n_limits);
 
+/* Collision FILTERS (EXTENSION): which body-body pairs may touch.
+ * Pair rule: bodies i and j may touch iff (group_i & mask_j) != 0 && (group_j & mask_i) != 0; with XPBD_FILTER_JOINTED
+ * they also may not touch when any joint of the world's current joint list connects them.  The rule is symmetric.
+ * Defaults: without filters every body is {~0u, ~0u}.  filters == NULL with n == 0 sets that default (flags may still turn
+ * on XPBD_FILTER_JOINTED); otherwise n must equal xpbd_world_body_count (the multi world: n_global), the caller's order.
+ * What is filtered: body-body contacts only, in the broadphase.  A filtered pair is absent from the neighbour lists
+ * (xpbd_world_download_neighbours), from the pair list and from xpbd_world_contact_stats' pair count.  Ground contacts (the
+ * reference path), joints (they still act between filtered bodies) and the plain ray casts (they keep hitting every body)
+ * are not affected.  Accepted in every mode; XPBD_MODE_FUSED / _PER_SUBSTEP have no body-body contacts, so there the filters
+ * matter only to the masked ray casts.
+ * Masked ray casts: a ray can hit body b only if (group_b & mask) != 0; everything else as the ray casts below (nearest hit,
+ * ties to the smaller index, ignore_body, same bits on the grid and brute-force paths).
+ * Lifetime: xpbd_world_upload_bodies / xpbd_multi_world_upload clear the filters and the flags (as they clear joints);
+ * xpbd_world_set_joints leaves them alone (XPBD_FILTER_JOINTED applies to the joints present when the next broadphase runs);
+ * history push / restore do not touch them.
+ * XPBD_E_INVALID (the previous filters stay in place): a NULL world, filters == NULL with n > 0, filters != NULL with n not
+ * equal to the body count, unknown flag bits.  The multi-world call is not collective: every rank passes the same list (as
+ * xpbd_multi_world_set_joint_limits); a device failure while the filters are handed to the shards leaves that world unusable.
+ * A world without filters, or with all {~0u, ~0u} and flags = 0, steps bit for bit as before. */
+#define XPBD_FILTER_JOINTED 1u   /* two bodies joined by a joint of the world never collide */
+typedef struct xpbd_collision_filter {   /* 8 bytes */
+    uint32_t group;                      /* the layers this body is in */
+    uint32_t mask;                       /* the layers it collides with */
+} xpbd_collision_filter;
+int  xpbd_world_set_collision_filters(xpbd_world *w, const xpbd_collision_filter *filters, uint32_t n, uint32_t flags);
+
 /* Split form of xpbd_world_step(w, dt, n) in XPBD_MODE_CONTACTS, for hosts that exchange halo
  * bodies between substeps (multi-GPU):  begin(dt); n x { substep(dt / n); <exchange> }.
  * begin runs the broadphase for the coming frame; substep is one substep of the pipeline. */
@@ -439,6 +465,10 @@ int  xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, con
  * clears them.  Checked against those joints before any device work; not collective.  A device failure while the limits are
  * handed to the local shards leaves the shards disagreeing: the world is unusable then (destroy it). */
 int  xpbd_multi_world_set_joint_limits(xpbd_multi_world *mw, const xpbd_joint_limit *limits, uint32_t n_limits);
+/* xpbd_world_set_collision_filters for the whole world: n_global filters in GLOBAL body order, the same list on every rank;
+ * upload clears them.  Every shard gets the filters of the bodies it owns and mirrors.  Not collective. */
+int  xpbd_multi_world_set_collision_filters(xpbd_multi_world *mw, const xpbd_collision_filter *filters, uint32_t n_global,
+                                            uint32_t flags);
 /* xpbd_world_step(dt, substeps) of the whole sharded world; collective.  XPBD_E_HALO: see above (the frame was undone). */
 int  xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps);
 /* Re-cuts the shards from the bodies' current positions (re-balancing them), migrates bodies whose owner changed and
@@ -567,6 +597,14 @@ int  xpbd_world_raycast_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t
  * and ignore_body are global indices. */
 int  xpbd_multi_world_raycast(xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags,
                               xpbd_ray_hit *hits);
+/* The same three, against the bodies whose collision-filter group meets `mask` only ((group & mask) != 0; bodies without
+ * filters are in group ~0u).  The plain calls test no group at all, so they still hit bodies of group 0. */
+int  xpbd_world_raycast_masked(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, uint32_t mask,
+                               xpbd_ray_hit *hits);
+int  xpbd_world_raycast_masked_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags,
+                                      uint32_t mask, xpbd_ray_hit *dev_hits);
+int  xpbd_multi_world_raycast_masked(xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags,
+                                     uint32_t mask, xpbd_ray_hit *hits);
 
 /* Diagnostics: quotient[i] = a[i] / b[i], root[i] = sqrt(a[i]) computed on the
  * device with the stepper's own code generation.  Bit-exact contact lists need
