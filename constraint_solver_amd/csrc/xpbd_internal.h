@@ -1,12 +1,83 @@
 // xpbd_internal.h -- shared by the translation units behind the C ABI (not installed).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
+#include <utility>
+
+#include <hip/hip_runtime_api.h>
 
 namespace xpbd {
 
-// Records the thread's last error message (xpbd_last_error) and returns `code`.
-int set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// ---- host error and resource layer -----------------------------------------------------------------------------------------
+// Records the thread's last error message (xpbd_last_error: a thread-local buffer of kErrorBytes, nothing is allocated) and
+// returns `code`.  An argument may be the current message itself: set_error(rc, "%s -- more", xpbd_last_error()).
+constexpr size_t kErrorBytes = 512;
+int set_error(int code, const char *fmt, ...) noexcept __attribute__((format(printf, 2, 3)));
+// Inside a catch block: XPBD_E_OOM, with a message naming `who` and the exception.
+int abi_exception(const char *who) noexcept;
+
+#define XPBD_TRY(expr)        \
+    do {                      \
+        if (int rc_ = (expr)) \
+            return rc_;       \
+    } while (0)
+#define XPBD_HIP_TRY(expr)                                                                                          \
+    do {                                                                                                            \
+        hipError_t e_ = (expr);                                                                                     \
+        if (e_ != hipSuccess)                                                                                       \
+            return ::xpbd::set_error(e_ == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "%s failed: %s", #expr,   \
+                                     hipGetErrorString(e_));                                                        \
+    } while (0)
+// Closes the function-try-block of every int entry point of the C ABI: no exception unwinds into the caller.
+#define XPBD_ABI_CATCH \
+    catch (...) { return ::xpbd::abi_exception(__func__); }
+
+// A device allocation that only ever grows, freed with its owner.  The first request is served exactly (most buffers are
+// sized by the body count and never change); a buffer that has to GROW takes a quarter more than asked: the pair, neighbour
+// and manifold buffers follow the pair count of the frame, which creeps up frame after frame while a pile settles, the ghost
+// lists of the multi-GPU world grow with the re-plans, and every hipFree + hipMalloc of a block of ~100 MB stalls the stream
+// for several hundred microseconds.  Growing frees the old block: queued work must not use it any more.
+struct DeviceBuffer {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer &&o) noexcept : ptr(std::exchange(o.ptr, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept
+    {
+        std::swap(ptr, o.ptr);
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
+    ~DeviceBuffer() { release(); }
+
+    hipError_t reserve(size_t want) noexcept
+    {
+        if (want <= bytes)
+            return hipSuccess;
+        if (ptr) {
+            want += want / 4;
+            hipError_t e = hipFree(ptr);
+            ptr = nullptr;
+            bytes = 0;
+            if (e != hipSuccess)
+                return e;
+        }
+        hipError_t e = hipMalloc(&ptr, want);
+        if (e == hipSuccess)
+            bytes = want;
+        return e;
+    }
+    void release() noexcept
+    {
+        if (ptr)
+            (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+    template <class T> T *as() const { return static_cast<T *>(ptr); }
+};
 
 // ---- one frame of a shard of the multi-GPU world (xpbd_multi.cpp), split at the halo exchange ---------------------------
 // All device pointers; slots are local body indices of the shard's world.
@@ -41,15 +112,15 @@ namespace xpbd {
 // ghosts:   the ghosts take their owners' end-of-substep state from `recv` (and run their own integrate + ground stage of
 //           substep k + 1 unless `last`)
 // Same arithmetic per body as xpbd_world_step, so the same bits.
-int halo_frame_begin_enqueue(xpbd_world *w, double dt);
-int halo_frame_begin_collect(xpbd_world *w, double h);
+int halo_frame_begin_enqueue(xpbd_world *w, double dt) noexcept;
+int halo_frame_begin_collect(xpbd_world *w, double h) noexcept;
 // The state a frame starts from (13 dynamic fields per body + last contact masks) kept aside on the device / put back:
 // a frame whose halos turn out to have been too thin is undone, re-planned and run again (xpbd_multi.cpp).
-int frame_snapshot_save(xpbd_world *w);
-int frame_snapshot_restore(xpbd_world *w);
-int halo_substep_boundary(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l);
-int halo_substep_interior(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l);
-int halo_substep_ghosts(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l);
+int frame_snapshot_save(xpbd_world *w) noexcept;
+int frame_snapshot_restore(xpbd_world *w) noexcept;
+int halo_substep_boundary(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l) noexcept;
+int halo_substep_interior(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l) noexcept;
+int halo_substep_ghosts(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l) noexcept;
 // ---- a plan of the multi-GPU world with the bodies staying on the device -----------------------------------------------------
 // host_keys[k] = grid cell (xpbd_halo_cell_key: same bits) of the bounding-sphere centre of body dev_slots[k] (a device array;
 // NULL: body k); *bad_index = first k whose centre is not finite (UINT32_MAX: none).  Synchronous.
@@ -59,7 +130,6 @@ int download_records(xpbd_world *w, const uint32_t *host_slots, uint32_t n, doub
 // The world's bodies become: body s = the present body host_src[s] (>= 0) or incoming record -host_src[s] - 1 (39 doubles
 // each).  Only the incoming records cross the bus; otherwise as xpbd_world_upload_bodies (joints and neighbour lists dropped).
 int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const double *incoming39, uint32_t n_incoming);
-// The argument checks of xpbd_world_set_joint_limits against a joint list (XPBD_E_INVALID with a message naming `who`).
 // The argument checks of xpbd_world_raycast(_device) against one world (topology present) / of the rays' reserved fields.
 int check_raycast(const char *who, const xpbd_world *w, const void *rays, uint32_t n_rays, uint32_t flags, const void *hits);
 int check_rays_reserved(const char *who, const xpbd_ray *rays, uint32_t n_rays);
@@ -70,5 +140,8 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
                     bool masked, uint32_t mask);
 int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id,
                  bool masked, uint32_t mask);
+// The argument checks of xpbd_world_set_joints against a world of n_bodies bodies / of xpbd_world_set_joint_limits against a
+// joint list (XPBD_E_INVALID with a message naming `who`).
+int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies);
 int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits);
 } // namespace xpbd

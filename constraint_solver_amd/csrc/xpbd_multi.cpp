@@ -42,8 +42,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
-#include <string>
+#include <exception>
+#include <memory>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -56,20 +56,8 @@
 
 namespace {
 
+using xpbd::DeviceBuffer;
 using xpbd::set_error;
-
-#define MW_HIP_TRY(expr)                                                                                      \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return set_error(e_ == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "%s failed: %s", #expr,     \
-                             hipGetErrorString(e_));                                                          \
-    } while (0)
-#define MW_TRY(expr)            \
-    do {                        \
-        if (int rc_ = (expr))   \
-            return rc_;         \
-    } while (0)
 
 constexpr uint32_t kDyn = 13;    // dynamic doubles per body: position, rotation, velocity, angular velocity
 constexpr uint32_t kRigid = 38;  // sizeof(xpbd_rigid) / 8
@@ -107,31 +95,6 @@ void cell_of_key(int64_t key, int64_t c[3])
     c[2] = (key & ((1 << 21) - 1)) - kCellBias;
 }
 
-struct DevBuf {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    hipError_t reserve(size_t want)
-    {
-        if (want <= bytes)
-            return hipSuccess;
-        if (ptr)
-            want += want / 4; // a buffer that grows once (ghost lists after a re-plan) will grow again: see DeviceBuffer
-        release();
-        hipError_t e = hipMalloc(&ptr, want);
-        if (e == hipSuccess)
-            bytes = want;
-        return e;
-    }
-    void release()
-    {
-        if (ptr)
-            (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
-    template <class T> T *as() const { return static_cast<T *>(ptr); }
-};
-
 // ---- ownership: the x-major sequence of grid cells cut into n_ranks runs of near-equal body count ----------------------------
 // A cut is a (cell key, body id) pair; rank r owns the bodies whose (key, id) lies in [cut[r], cut[r + 1]).  Cuts fall on
 // cell boundaries (whole cells stay together) unless that would leave a rank more than a quarter of its share off balance
@@ -156,6 +119,8 @@ unsigned plan_threads(size_t n)
     return n < ((size_t)1 << 16) ? 1u : hw;
 }
 
+// An exception in any chunk, or a thread that cannot be started, is rethrown on the calling thread (the first in thread order)
+// once every thread that did start has been joined.
 template <class F>
 void parallel_chunks(size_t n, F fn)
 {
@@ -164,13 +129,28 @@ void parallel_chunks(size_t n, F fn)
         fn(0u, (size_t)0, n);
         return;
     }
+    std::exception_ptr error[kPlanThreads];
+    auto chunk = [&](unsigned t) {
+        try {
+            fn(t, n * t / t_count, n * (t + 1) / t_count);
+        } catch (...) {
+            error[t] = std::current_exception();
+        }
+    };
     std::vector<std::thread> threads;
     threads.reserve(t_count - 1);
-    for (unsigned t = 1; t < t_count; ++t)
-        threads.emplace_back([&fn, t, t_count, n] { fn(t, n * t / t_count, n * (t + 1) / t_count); });
-    fn(0u, (size_t)0, n / t_count);
+    try {
+        for (unsigned t = 1; t < t_count; ++t)
+            threads.emplace_back(chunk, t);
+        chunk(0);
+    } catch (...) {
+        error[0] = std::current_exception();
+    }
     for (std::thread &th : threads)
         th.join();
+    for (const std::exception_ptr &e : error)
+        if (e)
+            std::rethrow_exception(e);
 }
 
 // The slabs are cut ACROSS THE LONGEST AXIS of the world's box of cells (a world 64 cells by 256 gets four slabs of 64 x 64,
@@ -626,14 +606,34 @@ struct Shard {
     std::vector<uint32_t> owned_slots_h;               // local slot of held_ids[i]
     std::vector<uint8_t> far; // per owned body: more than two cells away from every foreign body (larger travel allowance)
     std::vector<uint32_t> joint_ids; // global ids (ascending) of the joints the shard's world has: local joint q = joint_ids[q]
-    DevBuf boundary_slots, ghost_slots, ghost_rows, owned_slots, skip_flags, disp_scale, send, recv, snapshot, disp, disp_all, stage_send, stage_recv;
-    DevBuf query_ids; // xpbd_multi_world_raycast: global id of every local slot, XPBD_NO_HIT for the ghosts
+    DeviceBuffer boundary_slots, ghost_slots, ghost_rows, owned_slots, skip_flags, disp_scale, send, recv, snapshot, disp, disp_all, stage_send, stage_recv;
+    DeviceBuffer query_ids; // xpbd_multi_world_raycast: global id of every local slot, XPBD_NO_HIT for the ghosts
     double *disp_host = nullptr;   // pinned, n_ranks x {largest squared fraction of an allowance used, status}
     double *status_host = nullptr; // pinned, this process's status of the frame
+    const xpbd::RcclApi *rccl = nullptr; // destroys `comm`
     xpbd::HaloLists lists() const
     {
         return xpbd::HaloLists{boundary_slots.as<uint32_t>(), (uint32_t)boundary.size(), ghost_slots.as<uint32_t>(), ghost_rows.as<uint32_t>(),
                                (uint32_t)ghosts.size(), skip_flags.as<uint8_t>(), send.as<double>(), recv.as<double>()};
+    }
+
+    ~Shard() // (then the device buffers free themselves)
+    {
+        (void)hipSetDevice(device);
+        if (stream)
+            (void)hipStreamSynchronize(stream);
+        if (comm && rccl)
+            (void)rccl->CommDestroy(comm);
+        if (disp_host)
+            (void)hipHostFree(disp_host);
+        if (status_host)
+            (void)hipHostFree(status_host);
+        if (comm_stream)
+            (void)hipStreamDestroy(comm_stream);
+        for (hipEvent_t e : {ev_send, ev_ready, ev_gathered, ev_recv})
+            if (e)
+                (void)hipEventDestroy(e);
+        xpbd_world_destroy(world);
     }
 };
 
@@ -646,7 +646,7 @@ struct Barrier {
     std::condition_variable cv;
     uint32_t n = 1, waiting = 0;
     uint64_t generation = 0;
-    void arrive_and_wait()
+    void arrive_and_wait() noexcept
     {
         std::unique_lock<std::mutex> lock(m);
         const uint64_t g = generation;
@@ -665,16 +665,16 @@ struct Barrier {
 // leave the operation with an error at the same point.
 struct LocalStatus {
     int rc = XPBD_OK;
-    std::string message;
-    void keep(int r)
+    char message[xpbd::kErrorBytes] = {};
+    void keep(int r) noexcept
     {
         if (rc == XPBD_OK && r != XPBD_OK) {
             rc = r;
-            message = xpbd_last_error();
+            std::memcpy(message, xpbd_last_error(), sizeof message);
         }
     }
     bool ok() const { return rc == XPBD_OK; }
-    int report() const { return set_error(rc, "%s", message.c_str()); }
+    int report() const noexcept { return set_error(rc, "%s", message); }
 };
 
 struct ShardJob {
@@ -724,6 +724,7 @@ struct xpbd_multi_world {
     uint64_t full_plans = 0, light_plans = 0;
     double last_displacement = 0.0; // the largest fraction of its travel allowance any body had used at the last check, times halo_margin
     Workers *workers = nullptr;     // one enqueueing thread per local shard (n_local > 1), started by the first step
+    ~xpbd_multi_world(); // stops the workers (then the shards go)
     bool all_local() const { return shards.size() == n_ranks; }
     bool shortcut() const { return all_local() && !(flags & XPBD_MULTI_PLAN_THROUGH_DEVICE); } // plan-time gathers are memcpys
     uint32_t rows_per_rank() const { return capacity; }
@@ -739,7 +740,7 @@ uint64_t now_ns()
 
 int bind(const Shard &s)
 {
-    MW_HIP_TRY(hipSetDevice(s.device));
+    XPBD_HIP_TRY(hipSetDevice(s.device));
     return XPBD_OK;
 }
 
@@ -750,9 +751,8 @@ int nccl_fail(const xpbd_multi_world *mw, ncclResult_t r, const char *what)
 
 // A collective that could not be enqueued leaves the ranks out of step for good: the communicators are aborted (peers
 // blocked in the collective return with an error instead of hanging) and every later call on this world fails.
-int transport_broken(xpbd_multi_world *mw, int rc)
+int transport_broken(xpbd_multi_world *mw, int rc) noexcept
 {
-    const std::string msg = xpbd_last_error();
     mw->broken = true;
     if (mw->rccl && mw->rccl->CommAbort)
         for (Shard &s : mw->shards)
@@ -761,8 +761,13 @@ int transport_broken(xpbd_multi_world *mw, int rc)
                 (void)mw->rccl->CommAbort(s.comm);
                 s.comm = nullptr;
             }
-    return set_error(rc, "%s -- the communicator is unusable now: destroy this xpbd_multi_world on every rank", msg.c_str());
+    return set_error(rc, "%s -- the communicator is unusable now: destroy this xpbd_multi_world on every rank", xpbd_last_error());
 }
+
+// Closes the function-try-block of every xpbd_multi_world_* call (but create): an exception leaves the shards in an unknown
+// state and maybe the peers inside a collective, so it breaks the transport (see XPBD_ABI_CATCH).
+#define XPBD_MULTI_ABI_CATCH \
+    catch (...) { return transport_broken(mw, xpbd::abi_exception(__func__)); }
 
 // ---- one all-gather over all ranks: every shard contributes `bytes` of its buffer `send` and receives n_ranks x bytes, row
 // r from rank r, into its buffer `recv`.  Written per shard: all_gather_device_raw drives every local shard from one thread,
@@ -783,19 +788,19 @@ int rccl_all_gather(xpbd_multi_world *mw, Shard &s, const void *send, void *recv
 // 1. my send buffer is ready
 int local_send(Shard &s, hipStream_t stream)
 {
-    MW_HIP_TRY(hipEventRecord(s.ev_send, stream));
+    XPBD_HIP_TRY(hipEventRecord(s.ev_send, stream));
     return XPBD_OK;
 }
 
 // 2. wait for the peers' send events, copy every rank's row into my `recv`, record my receive event
-int local_copy(xpbd_multi_world *mw, Shard &s, DevBuf Shard::*send, void *recv, size_t bytes, hipStream_t stream)
+int local_copy(xpbd_multi_world *mw, Shard &s, DeviceBuffer Shard::*send, void *recv, size_t bytes, hipStream_t stream)
 {
     for (Shard &p : mw->shards) {
         if (&p != &s)
-            MW_HIP_TRY(hipStreamWaitEvent(stream, p.ev_send, 0));
-        MW_HIP_TRY(hipMemcpyAsync(static_cast<char *>(recv) + (size_t)p.rank * bytes, (p.*send).ptr, bytes, hipMemcpyDefault, stream));
+            XPBD_HIP_TRY(hipStreamWaitEvent(stream, p.ev_send, 0));
+        XPBD_HIP_TRY(hipMemcpyAsync(static_cast<char *>(recv) + (size_t)p.rank * bytes, (p.*send).ptr, bytes, hipMemcpyDefault, stream));
     }
-    MW_HIP_TRY(hipEventRecord(s.ev_recv, stream));
+    XPBD_HIP_TRY(hipEventRecord(s.ev_recv, stream));
     return XPBD_OK;
 }
 
@@ -804,12 +809,12 @@ int local_release(xpbd_multi_world *mw, Shard &s, hipStream_t stream)
 {
     for (Shard &p : mw->shards)
         if (&p != &s)
-            MW_HIP_TRY(hipStreamWaitEvent(stream, p.ev_recv, 0));
+            XPBD_HIP_TRY(hipStreamWaitEvent(stream, p.ev_recv, 0));
     return XPBD_OK;
 }
 
 // The all-gather of every local shard from this thread, on the shards' world streams (RCCL: in one group call).
-int all_gather_device_raw(xpbd_multi_world *mw, size_t bytes, DevBuf Shard::*send, DevBuf Shard::*recv)
+int all_gather_device_raw(xpbd_multi_world *mw, size_t bytes, DeviceBuffer Shard::*send, DeviceBuffer Shard::*recv)
 {
     if (mw->transport == XPBD_TRANSPORT_RCCL) {
         (void)hipGetLastError(); // see rccl_all_gather
@@ -828,21 +833,21 @@ int all_gather_device_raw(xpbd_multi_world *mw, size_t bytes, DevBuf Shard::*sen
         return XPBD_OK;
     }
     for (Shard &s : mw->shards) {
-        MW_TRY(bind(s));
-        MW_TRY(local_send(s, s.stream));
+        XPBD_TRY(bind(s));
+        XPBD_TRY(local_send(s, s.stream));
     }
     for (Shard &s : mw->shards) {
-        MW_TRY(bind(s));
-        MW_TRY(local_copy(mw, s, send, (s.*recv).ptr, bytes, s.stream));
+        XPBD_TRY(bind(s));
+        XPBD_TRY(local_copy(mw, s, send, (s.*recv).ptr, bytes, s.stream));
     }
     for (Shard &s : mw->shards) {
-        MW_TRY(bind(s));
-        MW_TRY(local_release(mw, s, s.stream));
+        XPBD_TRY(bind(s));
+        XPBD_TRY(local_release(mw, s, s.stream));
     }
     return XPBD_OK;
 }
 
-int all_gather_device(xpbd_multi_world *mw, size_t bytes, DevBuf Shard::*send, DevBuf Shard::*recv)
+int all_gather_device(xpbd_multi_world *mw, size_t bytes, DeviceBuffer Shard::*send, DeviceBuffer Shard::*recv)
 {
     if (int rc = all_gather_device_raw(mw, bytes, send, recv))
         return transport_broken(mw, rc);
@@ -873,23 +878,23 @@ int all_gather_host(xpbd_multi_world *mw, const std::vector<const void *> &send,
                 std::memcpy(staged[k].data(), &mine, 8);
                 if (bytes && status.ok())
                     std::memcpy(staged[k].data() + 8, send[k], bytes);
-                MW_TRY(bind(s));
-                MW_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free a block that is still in use
-                MW_HIP_TRY(s.stage_send.reserve(row));
-                MW_HIP_TRY(s.stage_recv.reserve((size_t)mw->n_ranks * row));
-                MW_HIP_TRY(hipMemcpyAsync(s.stage_send.ptr, staged[k].data(), row, hipMemcpyHostToDevice, s.stream));
+                XPBD_TRY(bind(s));
+                XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free a block that is still in use
+                XPBD_HIP_TRY(s.stage_send.reserve(row));
+                XPBD_HIP_TRY(s.stage_recv.reserve((size_t)mw->n_ranks * row));
+                XPBD_HIP_TRY(hipMemcpyAsync(s.stage_send.ptr, staged[k].data(), row, hipMemcpyHostToDevice, s.stream));
             }
             return XPBD_OK;
         };
         if ((rc = stage()) != XPBD_OK) // the staging buffers are the transport's: without them this rank cannot take part
             return transport_broken(mw, rc);
-        MW_TRY(all_gather_device(mw, row, &Shard::stage_send, &Shard::stage_recv));
+        XPBD_TRY(all_gather_device(mw, row, &Shard::stage_send, &Shard::stage_recv));
         auto collect = [&]() -> int {
             for (Shard &s : mw->shards) { // every shard takes part in the collective; the content is the same everywhere
-                MW_TRY(bind(s));
+                XPBD_TRY(bind(s));
                 if (&s == &mw->shards[0])
-                    MW_HIP_TRY(hipMemcpyAsync(all.data(), s.stage_recv.ptr, all.size(), hipMemcpyDeviceToHost, s.stream));
-                MW_HIP_TRY(hipStreamSynchronize(s.stream));
+                    XPBD_HIP_TRY(hipMemcpyAsync(all.data(), s.stage_recv.ptr, all.size(), hipMemcpyDeviceToHost, s.stream));
+                XPBD_HIP_TRY(hipStreamSynchronize(s.stream));
             }
             return XPBD_OK;
         };
@@ -918,11 +923,11 @@ int all_gather_host(xpbd_multi_world *mw, const std::vector<const void *> &send,
 }
 
 template <class T>
-int upload_vector(DevBuf &buf, const std::vector<T> &v, hipStream_t stream)
+int upload_vector(DeviceBuffer &buf, const std::vector<T> &v, hipStream_t stream)
 {
-    MW_HIP_TRY(buf.reserve(std::max<size_t>(v.size() * sizeof(T), 8)));
+    XPBD_HIP_TRY(buf.reserve(std::max<size_t>(v.size() * sizeof(T), 8)));
     if (!v.empty())
-        MW_HIP_TRY(hipMemcpyAsync(buf.ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        XPBD_HIP_TRY(hipMemcpyAsync(buf.ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
     return XPBD_OK;
 }
 
@@ -993,7 +998,7 @@ int gather_world_keys(xpbd_multi_world *mw, LocalStatus &st, const std::vector<s
             key_rows[k][i] = KeyRow{held_keys[k][i], s.held_ids[i], 0};
         send[k] = key_rows[k].data();
     }
-    MW_TRY(all_gather_host(mw, send, (size_t)max_held * sizeof(KeyRow), gathered, st));
+    XPBD_TRY(all_gather_host(mw, send, (size_t)max_held * sizeof(KeyRow), gathered, st));
     keys.assign(n, 0);
     holder.assign(n, 0xFF);
     for (uint32_t r = 0; r < w && st.ok(); ++r) {
@@ -1057,7 +1062,7 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
         mine[k] = Counts{(uint32_t)plans[k].boundary.size(), (uint32_t)plans[k].exports.size()};
         send[k] = &mine[k];
     }
-    MW_TRY(all_gather_host(mw, send, sizeof(Counts), gathered, st));
+    XPBD_TRY(all_gather_host(mw, send, sizeof(Counts), gathered, st));
     std::memcpy(counts.data(), gathered.data(), (size_t)w * sizeof(Counts));
     uint32_t cap = 1, cap_exp = 0;
     for (uint32_t r = 0; r < w; ++r) {
@@ -1073,7 +1078,7 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
                 std::copy(plans[k].boundary.begin(), plans[k].boundary.end(), pad_list[k].begin());
             send[k] = pad_list[k].data();
         }
-        MW_TRY(all_gather_host(mw, send, (size_t)cap * 4, gathered, st));
+        XPBD_TRY(all_gather_host(mw, send, (size_t)cap * 4, gathered, st));
         std::memcpy(lists.data(), gathered.data(), lists.size() * 4);
     }
     // the records of the exported bodies: gathered on the device that holds them, 39 doubles each
@@ -1088,7 +1093,7 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
                 std::copy(plans[k].exports.begin(), plans[k].exports.end(), pad_list[k].begin());
             send[k] = pad_list[k].data();
         }
-        MW_TRY(all_gather_host(mw, send, (size_t)cap_exp * 4, gathered, st));
+        XPBD_TRY(all_gather_host(mw, send, (size_t)cap_exp * 4, gathered, st));
         exp_lists.resize((size_t)w * cap_exp);
         std::memcpy(exp_lists.data(), gathered.data(), exp_lists.size() * 4);
         std::vector<uint32_t> slots;
@@ -1103,7 +1108,7 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
                 st.keep(xpbd::download_records(s.world, slots.data(), (uint32_t)slots.size(), pad_rec[k].data()));
             send[k] = pad_rec[k].data();
         }
-        MW_TRY(all_gather_host(mw, send, (size_t)cap_exp * kRecord * 8, gathered, st));
+        XPBD_TRY(all_gather_host(mw, send, (size_t)cap_exp * kRecord * 8, gathered, st));
         exp_records.resize((size_t)w * cap_exp * kRecord);
         std::memcpy(exp_records.data(), gathered.data(), exp_records.size() * 8);
     }
@@ -1126,7 +1131,7 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
     auto build_shard = [&](size_t k) -> int {
         Shard &s = mw->shards[k];
         ShardPlan &pl = plans[k];
-        MW_TRY(bind(s));
+        XPBD_TRY(bind(s));
         const uint32_t n_own = (uint32_t)pl.own.size(), n_ghost = (uint32_t)pl.ghosts.size(), n_loc = n_own + n_ghost;
         std::vector<int32_t> src(n_loc);
         std::vector<double> incoming;
@@ -1206,34 +1211,34 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
             return rc;
         if (int rc = push_collision_filters(mw, s, local_ids))
             return rc;
-        MW_HIP_TRY(hipStreamSynchronize(s.stream));
+        XPBD_HIP_TRY(hipStreamSynchronize(s.stream));
         trace.lap("  joints");
-        MW_TRY(upload_vector(s.boundary_slots, boundary_slots, s.stream));
-        MW_TRY(upload_vector(s.ghost_slots, ghost_slots, s.stream));
-        MW_TRY(upload_vector(s.ghost_rows, ghost_rows, s.stream));
-        MW_TRY(upload_vector(s.owned_slots, owned_slots, s.stream));
+        XPBD_TRY(upload_vector(s.boundary_slots, boundary_slots, s.stream));
+        XPBD_TRY(upload_vector(s.ghost_slots, ghost_slots, s.stream));
+        XPBD_TRY(upload_vector(s.ghost_rows, ghost_rows, s.stream));
+        XPBD_TRY(upload_vector(s.owned_slots, owned_slots, s.stream));
         std::vector<uint8_t> skip(n_loc, 0); // what the interior launch leaves out: boundary bodies (done first) and ghosts (done last)
         for (uint32_t q : boundary_slots)
             skip[q] = 1;
         for (uint32_t q : ghost_slots)
             skip[q] = 1;
-        MW_TRY(upload_vector(s.skip_flags, skip, s.stream));
+        XPBD_TRY(upload_vector(s.skip_flags, skip, s.stream));
         // 1 / allowance^2 per owned body: the displacement check then yields the largest FRACTION of its allowance any body has used
         std::vector<double> scale(n_own);
         const double near_allow = mw->margin, far_allow = mw->margin + 0.5 * edge;
         const double near_scale = 1.0 / (near_allow * near_allow), far_scale = 1.0 / (far_allow * far_allow);
         for (uint32_t i = 0; i < n_own; ++i)
             scale[i] = pl.far[i] ? far_scale : near_scale;
-        MW_TRY(upload_vector(s.disp_scale, scale, s.stream));
-        MW_HIP_TRY(s.send.reserve((size_t)rows * kDyn * 8));
-        MW_HIP_TRY(s.recv.reserve((size_t)w * rows * kDyn * 8));
-        MW_HIP_TRY(hipMemsetAsync(s.send.ptr, 0, (size_t)rows * kDyn * 8, s.stream));
-        MW_HIP_TRY(s.snapshot.reserve(std::max<size_t>((size_t)3 * n_own * 8, 8)));
-        MW_HIP_TRY(s.disp.reserve(16));
-        MW_HIP_TRY(s.disp_all.reserve((size_t)w * 16));
+        XPBD_TRY(upload_vector(s.disp_scale, scale, s.stream));
+        XPBD_HIP_TRY(s.send.reserve((size_t)rows * kDyn * 8));
+        XPBD_HIP_TRY(s.recv.reserve((size_t)w * rows * kDyn * 8));
+        XPBD_HIP_TRY(hipMemsetAsync(s.send.ptr, 0, (size_t)rows * kDyn * 8, s.stream));
+        XPBD_HIP_TRY(s.snapshot.reserve(std::max<size_t>((size_t)3 * n_own * 8, 8)));
+        XPBD_HIP_TRY(s.disp.reserve(16));
+        XPBD_HIP_TRY(s.disp_all.reserve((size_t)w * 16));
         if (int rc = xpbd_world_snapshot_positions(s.world, s.owned_slots.as<uint32_t>(), n_own, s.snapshot.as<double>()))
             return rc;
-        MW_HIP_TRY(hipStreamSynchronize(s.stream)); // the host vectors above go out of scope
+        XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // the host vectors above go out of scope
         s.owned_slots_h.swap(owned_slots);
         s.local_ids.swap(local_ids);
         s.held_ids.swap(pl.own); // from now on the shard holds what it owns
@@ -1296,7 +1301,7 @@ int gather_heads(xpbd_multi_world *mw, LocalStatus &st, double &rmax, uint64_t &
         head[k] = Head{mw->rmax_local, mw->shards[k].held_ids.size()};
         send[k] = &head[k];
     }
-    MW_TRY(all_gather_host(mw, send, sizeof(Head), gathered, st));
+    XPBD_TRY(all_gather_host(mw, send, sizeof(Head), gathered, st));
     rmax = 0.0, max_held = 0;
     uint64_t total_held = 0;
     for (uint32_t r = 0; r < mw->n_ranks; ++r) {
@@ -1328,15 +1333,15 @@ int make_plan_full(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace)
     //    a property of the bodies, known since the upload) and how many bodies every rank owns
     double rmax = 0.0;
     uint64_t max_held = 0;
-    MW_TRY(gather_heads(mw, st, rmax, max_held));
+    XPBD_TRY(gather_heads(mw, st, rmax, max_held));
     const double edge = plan_cell_edge(mw, rmax);
     // 2. grid cell of every body of the world (centre = position + center_of_mass)
     std::vector<std::vector<int64_t>> held_keys;
-    MW_TRY(held_cell_keys(mw, st, edge, held_keys));
+    XPBD_TRY(held_cell_keys(mw, st, edge, held_keys));
     trace.lap("cell keys (device)");
     std::vector<int64_t> keys;
     std::vector<uint8_t> holder;
-    MW_TRY(gather_world_keys(mw, st, held_keys, max_held, keys, holder));
+    XPBD_TRY(gather_world_keys(mw, st, held_keys, max_held, keys, holder));
     trace.lap("keys of the world");
 
     // 3. ownership: the cell sequence (longest axis first) cut into runs of near-equal body count; then who mirrors whom
@@ -1372,7 +1377,7 @@ int make_plan_full(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace)
         }
     }
     trace.lap("halo plans");
-    MW_TRY(finish_plan(mw, st, plans, edge, trace));
+    XPBD_TRY(finish_plan(mw, st, plans, edge, trace));
     mw->owner.swap(owner);
     mw->owned_count.swap(owned_count);
     mw->migrated = migrated;
@@ -1528,10 +1533,10 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
     std::vector<const void *> send(n_local);
     double rmax = 0.0;
     uint64_t max_held = 0;
-    MW_TRY(gather_heads(mw, st, rmax, max_held));
+    XPBD_TRY(gather_heads(mw, st, rmax, max_held));
     const double edge = plan_cell_edge(mw, rmax);
     std::vector<std::vector<int64_t>> held_keys;
-    MW_TRY(held_cell_keys(mw, st, edge, held_keys));
+    XPBD_TRY(held_cell_keys(mw, st, edge, held_keys));
     trace.lap("cell keys (device)");
     // the new owner of every held body from the sticky cuts; how many bodies every rank sends to every rank
     std::vector<std::vector<uint8_t>> held_owner(n_local);
@@ -1548,7 +1553,7 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
         }
         send[k] = tally[k].data();
     }
-    MW_TRY(all_gather_host(mw, send, (size_t)w * 4, gathered, st));
+    XPBD_TRY(all_gather_host(mw, send, (size_t)w * 4, gathered, st));
     std::vector<uint32_t> owned_count(w, 0);
     uint64_t migrated = 0;
     for (uint32_t h = 0; h < w; ++h)
@@ -1585,7 +1590,7 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
         rim_count[k] = (uint32_t)rim[k].size();
         send[k] = &rim_count[k];
     }
-    MW_TRY(all_gather_host(mw, send, 4, gathered, st));
+    XPBD_TRY(all_gather_host(mw, send, 4, gathered, st));
     std::memcpy(rim_counts.data(), gathered.data(), (size_t)w * 4);
     uint32_t cap_rim = 1;
     for (uint32_t c : rim_counts)
@@ -1594,7 +1599,7 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
         rim[k].resize(cap_rim, RimRow{0, UINT32_MAX, 0xFF, {0, 0, 0}});
         send[k] = rim[k].data();
     }
-    MW_TRY(all_gather_host(mw, send, (size_t)cap_rim * sizeof(RimRow), gathered, st));
+    XPBD_TRY(all_gather_host(mw, send, (size_t)cap_rim * sizeof(RimRow), gathered, st));
     if (trace.on)
         std::fprintf(stderr, "[xpbd plan %llu] rim rows per rank: up to %u\n", (unsigned long long)mw->plans, cap_rim);
     trace.lap("rims of the world");
@@ -1633,7 +1638,7 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
     if (mw->check_plans) { // XPBD_MULTI_CHECK_PLANS=1: the same lists from the keys of the whole world (the full planner, same cuts)
         std::vector<int64_t> keys;
         std::vector<uint8_t> holder;
-        MW_TRY(gather_world_keys(mw, st, held_keys, max_held, keys, holder));
+        XPBD_TRY(gather_world_keys(mw, st, held_keys, max_held, keys, holder));
         if (st.ok()) {
             std::vector<uint8_t> owner(n);
             for (uint32_t g = 0; g < n; ++g)
@@ -1653,7 +1658,7 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
         }
         trace.lap("checked against the full planner");
     }
-    MW_TRY(finish_plan(mw, st, plans, edge, trace));
+    XPBD_TRY(finish_plan(mw, st, plans, edge, trace));
     mw->owner.clear(); // (rebuilt on demand: xpbd_multi_world_owners)
     mw->owned_count.swap(owned_count);
     mw->migrated = migrated;
@@ -1678,9 +1683,8 @@ int make_plan(xpbd_multi_world *mw, LocalStatus &st)
     if (rc != XPBD_OK && mw->plan_torn && !mw->broken) {
         // A plan that fails BEFORE any shard is re-packed leaves the old plan and the state as they were (every rank returns
         // the error); one that fails in the middle of the re-packing does not: the world cannot be used any more.
-        const std::string msg = xpbd_last_error();
         mw->broken = true;
-        return set_error(rc, "%s -- the shards were being re-packed: destroy this xpbd_multi_world on every rank", msg.c_str());
+        return set_error(rc, "%s -- the shards were being re-packed: destroy this xpbd_multi_world on every rank", xpbd_last_error());
     }
     return rc;
 }
@@ -1691,7 +1695,7 @@ int fetch_owned(xpbd_multi_world *mw, std::vector<std::vector<double>> &held)
     held.assign(mw->shards.size(), std::vector<double>());
     for (size_t k = 0; k < mw->shards.size(); ++k) {
         Shard &s = mw->shards[k];
-        MW_TRY(bind(s));
+        XPBD_TRY(bind(s));
         const uint32_t n_loc = (uint32_t)s.local_ids.size();
         std::vector<double> aos((size_t)n_loc * kRigid);
         if (int rc = xpbd_world_download_bodies(s.world, reinterpret_cast<xpbd_rigid *>(aos.data()), n_loc))
@@ -1717,7 +1721,7 @@ int replan(xpbd_multi_world *mw)
 // A local error (job.st) skips the shard's remaining launches, the collectives still run; a collective that could not be
 // enqueued (job.fatal) skips the shard's remaining collectives.  Every thread passes every barrier whatever went wrong, so
 // nobody is left waiting.
-void shard_frame(xpbd_multi_world *mw, size_t k, double dt, uint32_t substeps, ShardJob &job, Barrier &bar)
+void shard_frame(xpbd_multi_world *mw, size_t k, double dt, uint32_t substeps, ShardJob &job, Barrier &bar) noexcept
 {
     Shard &s = mw->shards[k];
     const bool multi = mw->n_ranks > 1;
@@ -1728,7 +1732,7 @@ void shard_frame(xpbd_multi_world *mw, size_t k, double dt, uint32_t substeps, S
             st.keep(set_error(XPBD_E_HIP, "%s failed: %s", what, hipGetErrorString(e)));
     };
     // one all-gather: `bytes` of every rank's buffer `send` into row rank of my buffer `recv`
-    auto gather = [&](size_t bytes, DevBuf Shard::*send, DevBuf Shard::*recv, hipStream_t stream) {
+    auto gather = [&](size_t bytes, DeviceBuffer Shard::*send, DeviceBuffer Shard::*recv, hipStream_t stream) {
         if (mw->transport == XPBD_TRANSPORT_RCCL) {
             if (job.fatal.ok())
                 job.fatal.keep(rccl_all_gather(mw, s, (s.*send).ptr, (s.*recv).ptr, bytes, stream));
@@ -1817,18 +1821,25 @@ void worker_main(xpbd_multi_world *mw, size_t k)
     }
 }
 
+void stop_workers(xpbd_multi_world *mw) noexcept;
+
 // Runs shard_frame on every worker (started by the first call) and waits until all of them have enqueued their frames.
+// Workers that cannot all be started are stopped again (mw->workers stays NULL) and the exception goes on to the caller's
+// handler, which breaks the world like any host failure of a step: remote ranks may already wait in this frame's collectives.
 int run_workers(xpbd_multi_world *mw, double dt, uint32_t substeps)
 {
     if (!mw->workers) {
-        mw->workers = new (std::nothrow) Workers;
-        if (!mw->workers)
-            return set_error(XPBD_E_OOM, "xpbd_multi_world_step: host allocation failed");
-        Workers &w = *mw->workers;
-        w.result.resize(mw->shards.size());
-        w.barrier.n = (uint32_t)mw->shards.size();
-        for (size_t k = 0; k < mw->shards.size(); ++k)
-            w.threads.emplace_back(worker_main, mw, k);
+        mw->workers = new Workers;
+        try {
+            Workers &w = *mw->workers;
+            w.result.resize(mw->shards.size());
+            w.barrier.n = (uint32_t)mw->shards.size();
+            for (size_t k = 0; k < mw->shards.size(); ++k)
+                w.threads.emplace_back(worker_main, mw, k);
+        } catch (...) {
+            stop_workers(mw);
+            throw;
+        }
     }
     Workers &w = *mw->workers;
     std::unique_lock<std::mutex> lock(w.m);
@@ -1851,7 +1862,7 @@ int enqueue_frame(xpbd_multi_world *mw, double dt, uint32_t substeps, LocalStatu
         Barrier bar; // one party: arrive_and_wait passes straight through
         shard_frame(mw, 0, dt, substeps, alone, bar);
     } else {
-        MW_TRY(run_workers(mw, dt, substeps));
+        XPBD_TRY(run_workers(mw, dt, substeps));
         jobs = mw->workers->result.data();
     }
     uint64_t wait = 0;
@@ -1867,7 +1878,7 @@ int enqueue_frame(xpbd_multi_world *mw, double dt, uint32_t substeps, LocalStatu
     return XPBD_OK;
 }
 
-void stop_workers(xpbd_multi_world *mw)
+void stop_workers(xpbd_multi_world *mw) noexcept
 {
     if (!mw->workers)
         return;
@@ -1919,49 +1930,23 @@ int finish_frame(xpbd_multi_world *mw, LocalStatus &st, double *moved)
     return XPBD_OK;
 }
 
+} // namespace
+
+xpbd_multi_world::~xpbd_multi_world() { stop_workers(this); }
+
+namespace {
+
 int restore_frame(xpbd_multi_world *mw)
 {
     for (Shard &s : mw->shards)
-        MW_TRY(xpbd::frame_snapshot_restore(s.world));
+        XPBD_TRY(xpbd::frame_snapshot_restore(s.world));
     return XPBD_OK;
-}
-
-void destroy(xpbd_multi_world *mw)
-{
-    if (!mw)
-        return;
-    stop_workers(mw);
-    for (Shard &s : mw->shards) {
-        (void)hipSetDevice(s.device);
-        if (s.stream)
-            (void)hipStreamSynchronize(s.stream);
-        if (s.comm && mw->rccl)
-            (void)mw->rccl->CommDestroy(s.comm);
-        for (DevBuf *b : {&s.boundary_slots, &s.ghost_slots, &s.ghost_rows, &s.owned_slots, &s.skip_flags, &s.disp_scale, &s.send, &s.recv, &s.snapshot, &s.disp, &s.disp_all, &s.stage_send, &s.stage_recv})
-            b->release();
-        if (s.disp_host)
-            (void)hipHostFree(s.disp_host);
-        if (s.status_host)
-            (void)hipHostFree(s.status_host);
-        if (s.comm_stream)
-            (void)hipStreamDestroy(s.comm_stream);
-        if (s.ev_send)
-            (void)hipEventDestroy(s.ev_send);
-        if (s.ev_ready)
-            (void)hipEventDestroy(s.ev_ready);
-        if (s.ev_gathered)
-            (void)hipEventDestroy(s.ev_gathered);
-        if (s.ev_recv)
-            (void)hipEventDestroy(s.ev_recv);
-        xpbd_world_destroy(s.world);
-    }
-    delete mw;
 }
 
 // One shard's part of a ray cast: its OWNED bodies answer, under their global ids (ghosts are listed as XPBD_NO_HIT).
 int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, bool masked, uint32_t mask, xpbd_ray_hit *hits)
 {
-    MW_TRY(bind(s));
+    XPBD_TRY(bind(s));
     std::vector<uint32_t> ids(s.local_ids);
     size_t g = 0;
     for (uint32_t &id : ids) { // local_ids and ghosts are both ascending
@@ -1970,8 +1955,8 @@ int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flag
         if (g < s.ghosts.size() && s.ghosts[g] == id)
             id = XPBD_NO_HIT;
     }
-    MW_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
-    MW_TRY(upload_vector(s.query_ids, ids, s.stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
+    XPBD_TRY(upload_vector(s.query_ids, ids, s.stream));
     return xpbd::raycast_host(s.world, rays, n_rays, flags, hits, s.query_ids.as<uint32_t>(), masked, mask);
 }
 
@@ -1988,14 +1973,14 @@ int check_usable(const xpbd_multi_world *mw, const char *who)
 int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, bool masked, uint32_t mask,
                   xpbd_ray_hit *hits)
 {
-    MW_TRY(check_usable(mw, who));
+    XPBD_TRY(check_usable(mw, who));
     if (n_rays && (!rays || !hits))
         return set_error(XPBD_E_INVALID, "%s: NULL rays or hits", who);
     if (flags & ~XPBD_RAYCAST_BRUTE_FORCE)
         return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
     if (!mw->have_shapes)
         return set_error(XPBD_E_INVALID, "%s: call xpbd_multi_world_set_polytopes first", who);
-    MW_TRY(xpbd::check_rays_reserved(who, rays, n_rays));
+    XPBD_TRY(xpbd::check_rays_reserved(who, rays, n_rays));
     if (!mw->planned)
         return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
     if (n_rays == 0)
@@ -2012,7 +1997,7 @@ int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, u
         send.push_back(mine[k].data());
     }
     std::vector<uint8_t> all;
-    MW_TRY(all_gather_host(mw, send, bytes, all, st));
+    XPBD_TRY(all_gather_host(mw, send, bytes, all, st));
     for (uint32_t r = 0; r < n_rays; ++r) {
         xpbd_ray_hit best;
         std::memcpy(&best, all.data() + (size_t)r * sizeof(xpbd_ray_hit), sizeof best);
@@ -2032,7 +2017,7 @@ int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, u
 extern "C" {
 
 int xpbd_comm_unique_id(uint8_t id[XPBD_COMM_ID_BYTES])
-{
+try {
     static_assert(sizeof(ncclUniqueId) == XPBD_COMM_ID_BYTES, "XPBD_COMM_ID_BYTES must be sizeof(ncclUniqueId)");
     if (!id)
         return set_error(XPBD_E_INVALID, "xpbd_comm_unique_id: NULL argument");
@@ -2047,15 +2032,17 @@ int xpbd_comm_unique_id(uint8_t id[XPBD_COMM_ID_BYTES])
         return set_error(XPBD_E_HIP, "ncclGetUniqueId failed: %s", api->GetErrorString(r));
     std::memcpy(id, &u, XPBD_COMM_ID_BYTES);
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
-const char *xpbd_comm_library(void)
-{
+const char *xpbd_comm_library(void) noexcept
+try {
     const xpbd::RcclApi *api = xpbd::rccl_api(nullptr);
     return api ? api->path : nullptr;
+} catch (...) {
+    return nullptr; // (the search for RCCL ran out of host memory)
 }
 
-void xpbd_multi_config_default(xpbd_multi_config *cfg)
+void xpbd_multi_config_default(xpbd_multi_config *cfg) noexcept
 {
     if (!cfg)
         return;
@@ -2070,7 +2057,7 @@ void xpbd_multi_config_default(xpbd_multi_config *cfg)
 }
 
 int xpbd_multi_world_create(xpbd_multi_world **out, const xpbd_multi_config *cfg)
-{
+try {
     if (!out || !cfg)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_create: NULL argument");
     *out = nullptr;
@@ -2094,36 +2081,31 @@ int xpbd_multi_world_create(xpbd_multi_world **out, const xpbd_multi_config *cfg
     if (cfg->narrowphase != XPBD_NARROWPHASE_SAT && cfg->narrowphase != XPBD_NARROWPHASE_GJK_EPA)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_create: unknown narrowphase %u", cfg->narrowphase);
 
-    xpbd_multi_world *mw = new (std::nothrow) xpbd_multi_world;
-    if (!mw)
-        return set_error(XPBD_E_OOM, "xpbd_multi_world_create: host allocation failed");
+    std::unique_ptr<xpbd_multi_world> mw(new xpbd_multi_world); // (deleted on every way out but the last)
     mw->n_ranks = cfg->n_ranks, mw->first_rank = cfg->first_rank, mw->transport = cfg->transport, mw->flags = cfg->flags;
     mw->pad = cfg->contact_pad, mw->margin = cfg->halo_margin, mw->narrowphase = cfg->narrowphase;
-    mw->shards.resize(cfg->n_local);
-    auto bail = [&](int rc) {
-        destroy(mw);
-        return rc;
-    };
+    mw->shards = std::vector<Shard>(cfg->n_local);
     if (mw->transport == XPBD_TRANSPORT_RCCL) {
         const char *why = nullptr;
         mw->rccl = xpbd::rccl_api(&why);
         if (!mw->rccl)
-            return bail(set_error(XPBD_E_NO_DEVICE, "xpbd_multi_world_create: RCCL is not available (%s)", why));
+            return set_error(XPBD_E_NO_DEVICE, "xpbd_multi_world_create: RCCL is not available (%s)", why);
     }
     for (uint32_t k = 0; k < cfg->n_local; ++k) {
         Shard &s = mw->shards[k];
         s.device = cfg->devices[k];
         s.rank = cfg->first_rank + k;
+        s.rccl = mw->rccl;
         xpbd_config wc;
         xpbd_config_default(&wc);
         wc.device = s.device;
         wc.mode = XPBD_MODE_CONTACTS;
         if (int rc = xpbd_world_create(&s.world, &wc))
-            return bail(rc);
+            return rc;
         if (int rc = xpbd_world_set_contact_pad(s.world, mw->pad))
-            return bail(rc);
+            return rc;
         if (int rc = xpbd_world_set_narrowphase(s.world, mw->narrowphase))
-            return bail(rc);
+            return rc;
         s.stream = static_cast<hipStream_t>(xpbd_world_get_stream(s.world));
         hipError_t e = hipSetDevice(s.device);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_send, hipEventDisableTiming);
@@ -2134,7 +2116,7 @@ int xpbd_multi_world_create(xpbd_multi_world **out, const xpbd_multi_config *cfg
         if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&s.disp_host), (size_t)cfg->n_ranks * 16, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&s.status_host), 8, hipHostMallocDefault);
         if (e != hipSuccess)
-            return bail(set_error(XPBD_E_HIP, "xpbd_multi_world_create: %s", hipGetErrorString(e)));
+            return set_error(XPBD_E_HIP, "xpbd_multi_world_create: %s", hipGetErrorString(e));
     }
     if (mw->transport == XPBD_TRANSPORT_RCCL) {
         ncclUniqueId id;
@@ -2155,20 +2137,20 @@ int xpbd_multi_world_create(xpbd_multi_world **out, const xpbd_multi_config *cfg
         }
         const ncclResult_t r_end = mw->rccl->GroupEnd();
         if (device_failed)
-            return bail(set_error(XPBD_E_HIP, "xpbd_multi_world_create: hipSetDevice(%d) failed", failed_device));
+            return set_error(XPBD_E_HIP, "xpbd_multi_world_create: hipSetDevice(%d) failed", failed_device);
         if (r == ncclSuccess)
             r = r_end;
         if (r != ncclSuccess)
-            return bail(nccl_fail(mw, r, "ncclCommInitRank"));
+            return nccl_fail(mw.get(), r, "ncclCommInitRank");
     }
-    *out = mw;
+    *out = mw.release();
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
-void xpbd_multi_world_destroy(xpbd_multi_world *mw) { destroy(mw); }
+void xpbd_multi_world_destroy(xpbd_multi_world *mw) noexcept { delete mw; }
 
 int xpbd_multi_world_set_polytopes(xpbd_multi_world *mw, const xpbd_polytope *shapes, uint32_t n_shapes)
-{
+try {
     if (!mw || !shapes || n_shapes == 0)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_polytopes: NULL argument or no shapes");
     // validated by the first shard before any shard changes; a later failure leaves the world without shapes (and says so)
@@ -2194,21 +2176,21 @@ int xpbd_multi_world_set_polytopes(xpbd_multi_world *mw, const xpbd_polytope *sh
     }
     mw->have_shapes = true;
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_set_max_depenetration_speed(xpbd_multi_world *mw, double speed)
-{
+try {
     if (!mw)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_max_depenetration_speed: NULL world");
     for (Shard &s : mw->shards)
         if (int rc = xpbd_world_set_max_depenetration_speed(s.world, speed))
             return rc;
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_set_joint_limits(xpbd_multi_world *mw, const xpbd_joint_limit *limits, uint32_t n_limits)
-{
-    MW_TRY(check_usable(mw, "xpbd_multi_world_set_joint_limits"));
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_set_joint_limits"));
     if (int rc = xpbd::check_joint_limits("xpbd_multi_world_set_joint_limits", mw->joints.data(), (uint32_t)mw->joints.size(), limits, n_limits))
         return rc;
     mw->limits.assign(limits, limits + n_limits);
@@ -2216,16 +2198,15 @@ int xpbd_multi_world_set_joint_limits(xpbd_multi_world *mw, const xpbd_joint_lim
         return XPBD_OK; // the plan hands them to the shards
     for (Shard &s : mw->shards)
         if (int rc = push_joint_limits(mw, s)) { // (checked above: only a device failure gets here, and the shards disagree now)
-            const std::string msg = xpbd_last_error();
             mw->broken = true;
-            return set_error(rc, "%s -- the shards' joint limits disagree now: destroy this xpbd_multi_world", msg.c_str());
+            return set_error(rc, "%s -- the shards' joint limits disagree now: destroy this xpbd_multi_world", xpbd_last_error());
         }
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_set_collision_filters(xpbd_multi_world *mw, const xpbd_collision_filter *filters, uint32_t n_global, uint32_t flags)
-{
-    MW_TRY(check_usable(mw, "xpbd_multi_world_set_collision_filters"));
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_set_collision_filters"));
     if (!filters && n_global)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_collision_filters: NULL filters with n_global = %u", n_global);
     if (filters && n_global != mw->n_global)
@@ -2245,18 +2226,17 @@ int xpbd_multi_world_set_collision_filters(xpbd_multi_world *mw, const xpbd_coll
         if (rc == XPBD_OK)
             rc = push_collision_filters(mw, s, s.local_ids);
         if (rc != XPBD_OK) { // (checked above: only a device failure gets here, and the shards disagree now)
-            const std::string msg = xpbd_last_error();
             mw->broken = true;
-            return set_error(rc, "%s -- the shards' collision filters disagree now: destroy this xpbd_multi_world", msg.c_str());
+            return set_error(rc, "%s -- the shards' collision filters disagree now: destroy this xpbd_multi_world", xpbd_last_error());
         }
     }
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, const uint32_t *shape_id, uint32_t first_global, uint32_t n_bodies,
                             uint32_t n_global, const xpbd_joint *joints, uint32_t n_joints)
-{
-    MW_TRY(check_usable(mw, "xpbd_multi_world_upload"));
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_upload"));
     // Argument errors are found by every rank alike (or are the caller's to agree on): they return before any collective.
     if ((n_bodies && !bodies) || (n_joints && !joints))
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_upload: NULL argument");
@@ -2271,9 +2251,7 @@ int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, cons
     for (uint32_t i = 0; shape_id && i < n_bodies; ++i)
         if (shape_id[i] >= n_shapes)
             return set_error(XPBD_E_INVALID, "xpbd_multi_world_upload: shape_id[%u] = %u >= n_shapes %zu", i, shape_id[i], n_shapes);
-    for (uint32_t j = 0; j < n_joints; ++j)
-        if (joints[j].body_a >= n_global || joints[j].body_b >= n_global || joints[j].body_a == joints[j].body_b)
-            return set_error(XPBD_E_INVALID, "xpbd_multi_world_upload: joint %u links bodies %u and %u of %u", j, joints[j].body_a, joints[j].body_b, n_global);
+    XPBD_TRY(xpbd::check_joints("xpbd_multi_world_upload", joints, n_joints, n_global));
     mw->n_global = n_global, mw->first_global = first_global, mw->n_bodies = n_bodies;
     mw->joints.assign(joints, joints + n_joints);
     mw->limits.clear(); // limits name joints by index: a new upload invalidates them
@@ -2318,12 +2296,12 @@ int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, cons
         s.local_ids = s.held_ids;
         s.ghosts.clear(), s.boundary.clear();
         auto upload = [&]() -> int {
-            MW_TRY(bind(s));
+            XPBD_TRY(bind(s));
             if (int rc = xpbd_world_upload_bodies(s.world, bodies + (slice.first - first_global), shape_id ? shape_id + (slice.first - first_global) : nullptr,
                                                   slice.count))
                 return rc;
-            MW_TRY(upload_vector(s.owned_slots, s.owned_slots_h, s.stream));
-            MW_HIP_TRY(hipStreamSynchronize(s.stream));
+            XPBD_TRY(upload_vector(s.owned_slots, s.owned_slots_h, s.stream));
+            XPBD_HIP_TRY(hipStreamSynchronize(s.stream));
             return XPBD_OK;
         };
         if (st.ok())
@@ -2333,19 +2311,19 @@ int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, cons
     mw->rollbacks = 0;
     mw->full_plans = mw->light_plans = 0;
     return make_plan(mw, st);
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_replan(xpbd_multi_world *mw)
-{
-    MW_TRY(check_usable(mw, "xpbd_multi_world_replan"));
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_replan"));
     if (!mw->planned)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_replan: no bodies uploaded");
     return replan(mw);
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps)
-{
-    MW_TRY(check_usable(mw, "xpbd_multi_world_step"));
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_step"));
     if (substeps == 0)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_step: substeps must be > 0");
     if (!mw->planned)
@@ -2357,16 +2335,17 @@ int xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps)
     ++mw->steps;
     for (int attempt = 0;; ++attempt) {
         LocalStatus st;
-        MW_TRY(enqueue_frame(mw, dt, substeps, st));
+        XPBD_TRY(enqueue_frame(mw, dt, substeps, st));
         if (mw->n_ranks == 1)
             return st.ok() ? XPBD_OK : st.report(); // no ghosts, nothing to validate: asynchronous after the broadphase
         double moved = 0.0;
         if (int rc = finish_frame(mw, st, &moved)) {
             if (mw->broken)
                 return rc;
-            const std::string msg = xpbd_last_error();
+            LocalStatus failed;
+            failed.keep(rc);
             (void)restore_frame(mw); // best effort: the state of the frame's start, on every rank
-            return set_error(rc, "%s", msg.c_str());
+            return failed.report();
         }
         const double gain = std::max(0.0, moved - mw->last_displacement); // what this frame used up of the allowance
         mw->last_displacement = moved;
@@ -2374,11 +2353,11 @@ int xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps)
             // pre-emptive: another frame like this one (and half as much again) would outrun the allowance, so re-plan (and
             // re-balance) from the state just reached.  A wrong guess costs a frame: it is undone and run again below.
             if ((mw->flags & XPBD_MULTI_AUTO_REPLAN) && moved + 1.5 * gain > mw->margin)
-                MW_TRY(replan(mw));
+                XPBD_TRY(replan(mw));
             return XPBD_OK;
         }
         // A body outran its allowance during THIS frame: a remote contact may have been missed in it.  Undo the frame.
-        MW_TRY(restore_frame(mw));
+        XPBD_TRY(restore_frame(mw));
         ++mw->rollbacks;
         if (!(mw->flags & XPBD_MULTI_AUTO_REPLAN) || attempt == 1) {
             mw->violated = true;
@@ -2388,34 +2367,34 @@ int xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps)
                              moved, mw->margin, attempt ? ", even right after a re-plan" : "",
                              attempt ? " with a larger halo_margin or a shorter frame" : "");
         }
-        MW_TRY(replan(mw)); // from the restored state; then the same frame again
+        XPBD_TRY(replan(mw)); // from the restored state; then the same frame again
     }
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_raycast(xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
-{
+try {
     return multi_raycast("xpbd_multi_world_raycast", mw, rays, n_rays, flags, false, 0u, hits);
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_raycast_masked(xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, uint32_t mask,
                                     xpbd_ray_hit *hits)
-{
+try {
     return multi_raycast("xpbd_multi_world_raycast_masked", mw, rays, n_rays, flags, true, mask, hits);
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_synchronize(xpbd_multi_world *mw)
-{
+try {
     if (!mw)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_synchronize: NULL world");
     for (Shard &s : mw->shards)
         if (int rc = xpbd_world_synchronize(s.world))
             return rc;
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_download_owned(xpbd_multi_world *mw, uint32_t *ids, xpbd_rigid *out, uint32_t cap, uint32_t *n_out)
-{
-    MW_TRY(check_usable(mw, "xpbd_multi_world_download_owned"));
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_download_owned"));
     if (!n_out || (cap && (!ids || !out)))
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_download_owned: NULL argument");
     if (!mw->planned)
@@ -2427,7 +2406,7 @@ int xpbd_multi_world_download_owned(xpbd_multi_world *mw, uint32_t *ids, xpbd_ri
     if (total > cap)
         return set_error(XPBD_E_CAPACITY, "xpbd_multi_world_download_owned: %zu owned bodies, capacity %u", total, cap);
     std::vector<std::vector<double>> held;
-    MW_TRY(fetch_owned(mw, held));
+    XPBD_TRY(fetch_owned(mw, held));
     size_t at = 0;
     for (size_t k = 0; k < mw->shards.size(); ++k) {
         const Shard &s = mw->shards[k];
@@ -2438,11 +2417,11 @@ int xpbd_multi_world_download_owned(xpbd_multi_world *mw, uint32_t *ids, xpbd_ri
         at += s.held_ids.size();
     }
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_download(xpbd_multi_world *mw, xpbd_rigid *out, uint32_t n)
-{
-    MW_TRY(check_usable(mw, "xpbd_multi_world_download"));
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_download"));
     if (n && !out)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_download: NULL argument");
     if (!mw->planned || n != mw->n_bodies)
@@ -2478,7 +2457,7 @@ int xpbd_multi_world_download(xpbd_multi_world *mw, xpbd_rigid *out, uint32_t n)
         send[k] = payload[k].data();
     }
     std::vector<uint8_t> gathered;
-    MW_TRY(all_gather_host(mw, send, (size_t)cap * row, gathered, st));
+    XPBD_TRY(all_gather_host(mw, send, (size_t)cap * row, gathered, st));
     uint32_t found = 0;
     for (uint32_t r = 0; r < mw->n_ranks; ++r)
         for (uint32_t i = 0; i < mw->owned_count[r]; ++i) {
@@ -2493,10 +2472,10 @@ int xpbd_multi_world_download(xpbd_multi_world *mw, xpbd_rigid *out, uint32_t n)
     if (found != mw->n_bodies)
         return set_error(XPBD_E_HIP, "xpbd_multi_world_download: %u of the %u bodies of this process came back", found, mw->n_bodies);
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_halo_stats(xpbd_multi_world *mw, uint64_t out[6], double *max_displacement)
-{
+try {
     if (!mw || !out)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_halo_stats: NULL argument");
     uint64_t owned = 0, ghosts = 0, boundary = 0;
@@ -2509,10 +2488,10 @@ int xpbd_multi_world_halo_stats(xpbd_multi_world *mw, uint64_t out[6], double *m
     if (max_displacement)
         *max_displacement = mw->last_displacement;
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_plan_stats(xpbd_multi_world *mw, uint64_t out[12])
-{
+try {
     if (!mw || !out)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_plan_stats: NULL argument");
     uint32_t lo = UINT32_MAX, hi = 0;
@@ -2524,10 +2503,10 @@ int xpbd_multi_world_plan_stats(xpbd_multi_world *mw, uint64_t out[12])
     out[5] = mw->steps, out[6] = mw->ns_enqueue, out[7] = mw->ns_wait_broadphase, out[8] = mw->ns_wait_frame, out[9] = mw->ns_plan;
     out[10] = mw->full_plans, out[11] = mw->light_plans;
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_owners(xpbd_multi_world *mw, uint8_t *owner, uint32_t n_global)
-{
+try {
     if (!mw || !owner)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_owners: NULL argument");
     if (!mw->planned || n_global != mw->n_global)
@@ -2547,7 +2526,7 @@ int xpbd_multi_world_owners(xpbd_multi_world *mw, uint8_t *owner, uint32_t n_glo
             send[k] = ids[k].data();
         }
         std::vector<uint8_t> gathered;
-        MW_TRY(all_gather_host(mw, send, (size_t)cap * 4, gathered, st));
+        XPBD_TRY(all_gather_host(mw, send, (size_t)cap * 4, gathered, st));
         std::vector<uint8_t> all(n_global, 0xFF);
         for (uint32_t r = 0; r < mw->n_ranks; ++r)
             for (uint32_t i = 0; i < mw->owned_count[r]; ++i) {
@@ -2560,10 +2539,10 @@ int xpbd_multi_world_owners(xpbd_multi_world *mw, uint8_t *owner, uint32_t n_glo
     }
     std::memcpy(owner, mw->owner.data(), n_global);
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_contact_stats(xpbd_multi_world *mw, uint64_t out[3])
-{
+try {
     if (!mw || !out)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_contact_stats: NULL argument");
     out[0] = out[1] = out[2] = 0;
@@ -2575,23 +2554,23 @@ int xpbd_multi_world_contact_stats(xpbd_multi_world *mw, uint64_t out[3])
             out[k] += one[k];
     }
     return XPBD_OK;
-}
+} XPBD_MULTI_ABI_CATCH
 
 // Diagnostics (host only, no device): ownership and halo plans from the global cell keys, as make_plan computes them.
 int xpbd_halo_partition(const int64_t *cell_keys, uint32_t n_global, uint32_t n_ranks, uint8_t *owner)
-{
+try {
     if ((n_global && (!cell_keys || !owner)) || n_ranks == 0 || n_ranks > 64)
         return set_error(XPBD_E_INVALID, "xpbd_halo_partition: bad argument");
     std::vector<Cut> cuts;
     int axes[3];
     compute_owners(cell_keys, n_global, n_ranks, owner, cuts, axes);
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_halo_plan_light(const int64_t *keys_at_cut, const int64_t *cell_keys, uint32_t n_global, uint32_t n_ranks, uint32_t rank,
                          const xpbd_joint *joints, uint32_t n_joints, uint8_t *owner_now, uint32_t *own, uint32_t *n_own, uint32_t *ghosts,
                          uint32_t *n_ghosts, uint32_t *boundary, uint32_t *n_boundary, uint8_t *far, uint32_t cap)
-{
+try {
     if (!keys_at_cut || !cell_keys || !owner_now || !n_own || !n_ghosts || !n_boundary || n_ranks == 0 || n_ranks > 64 || rank >= n_ranks ||
         (n_joints && !joints) || (cap && (!own || !ghosts || !boundary)))
         return set_error(XPBD_E_INVALID, "xpbd_halo_plan_light: bad argument");
@@ -2652,11 +2631,11 @@ int xpbd_halo_plan_light(const int64_t *keys_at_cut, const int64_t *cell_keys, u
     if (far)
         std::copy(pl.far.begin(), pl.far.end(), far);
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_halo_plan_owned(const int64_t *cell_keys, const uint8_t *owner, uint32_t n_global, uint32_t n_ranks, uint32_t rank, const xpbd_joint *joints,
                          uint32_t n_joints, uint32_t *ghosts, uint32_t *n_ghosts, uint32_t *boundary, uint32_t *n_boundary, uint8_t *far, uint32_t cap)
-{
+try {
     if (!cell_keys || !owner || !n_ghosts || !n_boundary || n_ranks == 0 || n_ranks > 64 || rank >= n_ranks || (n_joints && !joints) ||
         (cap && (!ghosts || !boundary)))
         return set_error(XPBD_E_INVALID, "xpbd_halo_plan_owned: bad argument");
@@ -2679,7 +2658,7 @@ int xpbd_halo_plan_owned(const int64_t *cell_keys, const uint8_t *owner, uint32_
     if (far)
         std::copy(f.begin(), f.end(), far); // one flag per owned body, in ascending id
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 namespace {
 void range_owners(uint32_t n_global, uint32_t n_ranks, std::vector<uint8_t> &owner)
@@ -2695,16 +2674,16 @@ void range_owners(uint32_t n_global, uint32_t n_ranks, std::vector<uint8_t> &own
 // ... with ownership by contiguous index ranges (what a caller that orders its bodies itself would get)
 int xpbd_halo_plan(const int64_t *cell_keys, uint32_t n_global, uint32_t n_ranks, uint32_t rank, const xpbd_joint *joints, uint32_t n_joints,
                    uint32_t *ghosts, uint32_t *n_ghosts, uint32_t *boundary, uint32_t *n_boundary, uint32_t cap)
-{
+try {
     if (n_ranks == 0 || n_ranks > 64)
         return set_error(XPBD_E_INVALID, "xpbd_halo_plan: bad argument");
     std::vector<uint8_t> owner;
     range_owners(n_global, n_ranks, owner);
     return xpbd_halo_plan_owned(cell_keys, owner.data(), n_global, n_ranks, rank, joints, n_joints, ghosts, n_ghosts, boundary, n_boundary, nullptr, cap);
-}
+} XPBD_ABI_CATCH
 
 int xpbd_halo_plan_far(const int64_t *cell_keys, uint32_t n_global, uint32_t n_ranks, uint32_t rank, uint8_t *far, uint32_t cap, uint32_t *n_owned)
-{
+try {
     if (!cell_keys || !n_owned || n_ranks == 0 || n_ranks > 64 || rank >= n_ranks || (cap && !far))
         return set_error(XPBD_E_INVALID, "xpbd_halo_plan_far: bad argument");
     std::vector<uint8_t> owner;
@@ -2719,9 +2698,9 @@ int xpbd_halo_plan_far(const int64_t *cell_keys, uint32_t n_global, uint32_t n_r
         return set_error(XPBD_E_CAPACITY, "xpbd_halo_plan_far: %zu owned bodies, capacity %u", f.size(), cap);
     std::copy(f.begin(), f.end(), far);
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
-int64_t xpbd_halo_cell_key(const double centre[3], double cell_edge)
+int64_t xpbd_halo_cell_key(const double centre[3], double cell_edge) noexcept
 {
     if (!centre || !(cell_edge > 0.0))
         return 0;

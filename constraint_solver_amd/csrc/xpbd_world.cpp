@@ -8,8 +8,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
-#include <string>
+#include <exception>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -25,82 +25,38 @@
 
 namespace {
 
-thread_local std::string g_last_error;
-
-int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#define XPBD_HIP_TRY(expr)                                                                         \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(e_ == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "%s failed: %s",      \
-                        #expr, hipGetErrorString(e_));                                             \
-    } while (0)
+thread_local char g_last_error[xpbd::kErrorBytes];
 
 uint32_t round_up(uint32_t v, uint32_t to) { return (v + to - 1) / to * to; }
 
 } // namespace
 
 namespace xpbd {
-int set_error(int code, const char *fmt, ...)
+int set_error(int code, const char *fmt, ...) noexcept
 {
-    char buf[512];
+    char buf[kErrorBytes]; // (an argument may be g_last_error itself)
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
-    g_last_error = buf;
+    std::memcpy(g_last_error, buf, sizeof buf);
     return code;
+}
+
+int abi_exception(const char *who) noexcept
+{
+    try {
+        throw;
+    } catch (const std::exception &e) {
+        return set_error(XPBD_E_OOM, "%s: %s", who, e.what());
+    } catch (...) {
+        return set_error(XPBD_E_OOM, "%s: unknown exception", who);
+    }
 }
 } // namespace xpbd
 
-namespace {
-
-// A device allocation that only ever grows.  The first request is served exactly (most buffers are sized by the body
-// count and never change); a buffer that has to GROW takes a quarter more than asked: the pair, neighbour and manifold
-// buffers follow the pair count of the frame, which creeps up frame after frame while a pile settles, and every
-// hipFree + hipMalloc of a block of ~100 MB stalls the stream for several hundred microseconds.
-struct DeviceBuffer {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-
-    hipError_t reserve(size_t want)
-    {
-        if (want <= bytes)
-            return hipSuccess;
-        if (ptr) {
-            want += want / 4;
-            hipError_t e = hipFree(ptr);
-            ptr = nullptr;
-            bytes = 0;
-            if (e != hipSuccess)
-                return e;
-        }
-        hipError_t e = hipMalloc(&ptr, want);
-        if (e == hipSuccess)
-            bytes = want;
-        return e;
-    }
-    void release()
-    {
-        if (ptr)
-            (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
-    template <class T> T *as() const { return static_cast<T *>(ptr); }
-};
-
-} // namespace
+using xpbd::DeviceBuffer;
+using xpbd::set_error;
 
 struct xpbd_world {
     int device = 0;
@@ -249,6 +205,19 @@ struct xpbd_world {
     {
         return xpbd::ShapeTable{shape_verts.as<double>(), shape_offsets.as<uint32_t>(), n_shapes, total_verts};
     }
+
+    ~xpbd_world() // (then the device buffers free themselves)
+    {
+        (void)hipSetDevice(device);
+        if (stream)
+            (void)hipStreamSynchronize(stream);
+        if (bp_totals)
+            (void)hipHostFree(bp_totals);
+        if (bp_event)
+            (void)hipEventDestroy(bp_event);
+        if (own_stream)
+            (void)hipStreamDestroy(own_stream);
+    }
 };
 
 namespace {
@@ -357,7 +326,7 @@ int build_neighbours_enqueue(xpbd_world *w, double dt)
 int build_neighbours_collect(xpbd_world *w)
 {
     if (!w->bp_pending)
-        return fail(XPBD_E_INVALID, "build_neighbours_collect without build_neighbours_enqueue");
+        return set_error(XPBD_E_INVALID, "build_neighbours_collect without build_neighbours_enqueue");
     XPBD_HIP_TRY(hipEventSynchronize(w->bp_event));
     w->bp_pending = false;
     const xpbd::BodyArrays b = w->arrays();
@@ -465,7 +434,7 @@ int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_ro
 int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_t *trace)
 {
     if (!w->has_topology)
-        return fail(XPBD_E_INVALID, "XPBD_MODE_CONTACTS needs xpbd_world_set_polytopes");
+        return set_error(XPBD_E_INVALID, "XPBD_MODE_CONTACTS needs xpbd_world_set_polytopes");
     if (int rc = build_neighbours(w, dt))
         return rc;
     if (substeps == 0)
@@ -493,10 +462,10 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
 // ---- the frame of a multi-GPU shard, split at the halo exchange (xpbd_internal.h) -------------------------------------------
 namespace xpbd {
 
-int halo_frame_begin_enqueue(xpbd_world *w, double dt)
+int halo_frame_begin_enqueue(xpbd_world *w, double dt) noexcept
 {
     if (!w || w->mode != XPBD_MODE_CONTACTS || !w->has_topology)
-        return fail(XPBD_E_INVALID, "halo_frame_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
+        return set_error(XPBD_E_INVALID, "halo_frame_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
     if (w->n == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -504,10 +473,10 @@ int halo_frame_begin_enqueue(xpbd_world *w, double dt)
     return build_neighbours_enqueue(w, dt);
 }
 
-int halo_frame_begin_collect(xpbd_world *w, double h)
+int halo_frame_begin_collect(xpbd_world *w, double h) noexcept
 {
     if (!w || w->mode != XPBD_MODE_CONTACTS || !w->has_topology)
-        return fail(XPBD_E_INVALID, "halo_frame_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
+        return set_error(XPBD_E_INVALID, "halo_frame_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
     if (w->n == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -521,10 +490,10 @@ int halo_frame_begin_collect(xpbd_world *w, double h)
 
 // The state a frame starts from -- the 13 dynamic fields of every body and the contact masks of the last substep -- kept
 // aside (device to device, on the world's stream) so that a frame whose halos turn out to have been too thin can be undone.
-int frame_snapshot_save(xpbd_world *w)
+int frame_snapshot_save(xpbd_world *w) noexcept
 {
     if (!w)
-        return fail(XPBD_E_INVALID, "frame_snapshot_save: NULL world");
+        return set_error(XPBD_E_INVALID, "frame_snapshot_save: NULL world");
     if (w->n == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -542,14 +511,14 @@ int frame_snapshot_save(xpbd_world *w)
     return XPBD_OK;
 }
 
-int frame_snapshot_restore(xpbd_world *w)
+int frame_snapshot_restore(xpbd_world *w) noexcept
 {
     if (!w)
-        return fail(XPBD_E_INVALID, "frame_snapshot_restore: NULL world");
+        return set_error(XPBD_E_INVALID, "frame_snapshot_restore: NULL world");
     if (w->n == 0)
         return XPBD_OK;
     if (!w->frame_snapshot_valid)
-        return fail(XPBD_E_INVALID, "frame_snapshot_restore: no snapshot");
+        return set_error(XPBD_E_INVALID, "frame_snapshot_restore: no snapshot");
     if (int rc = bind_device(w))
         return rc;
     const size_t dyn_bytes = (size_t)kDynFields * w->stride * 8, mask_bytes = (size_t)w->stride * 4;
@@ -578,7 +547,7 @@ int halo_pair_solve(xpbd_world *w, double h, uint32_t k, bool last, const BodySu
 }
 } // namespace
 
-int halo_substep_boundary(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l)
+int halo_substep_boundary(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l) noexcept
 {
     if (w->n == 0)
         return XPBD_OK;
@@ -593,7 +562,7 @@ int halo_substep_boundary(xpbd_world *w, double h, uint32_t k, bool last, const 
     return halo_pair_solve(w, h, k, last, subset);
 }
 
-int halo_substep_interior(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l)
+int halo_substep_interior(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l) noexcept
 {
     if (w->n == 0)
         return XPBD_OK;
@@ -604,7 +573,7 @@ int halo_substep_interior(xpbd_world *w, double h, uint32_t k, bool last, const 
     return halo_pair_solve(w, h, k, last, subset);
 }
 
-int halo_substep_ghosts(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l)
+int halo_substep_ghosts(xpbd_world *w, double h, uint32_t k, bool last, const HaloLists &l) noexcept
 {
     if (w->n == 0 || l.n_ghosts == 0)
         return XPBD_OK;
@@ -672,7 +641,7 @@ int download_records(xpbd_world *w, const uint32_t *host_slots, uint32_t n, doub
         return XPBD_OK;
     for (uint32_t k = 0; k < n; ++k)
         if (host_slots[k] >= w->n)
-            return fail(XPBD_E_INVALID, "xpbd::download_records: slot %u of a world of %u bodies", host_slots[k], w->n);
+            return set_error(XPBD_E_INVALID, "xpbd::download_records: slot %u of a world of %u bodies", host_slots[k], w->n);
     if (int rc = bind_device(w))
         return rc;
     constexpr size_t rec = (size_t)(kRigidDoubles + 1) * 8;
@@ -692,18 +661,18 @@ int download_records(xpbd_world *w, const uint32_t *host_slots, uint32_t n, doub
 int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const double *incoming39, uint32_t n_incoming)
 {
     if (!w || (n_new && !host_src) || (n_incoming && !incoming39))
-        return fail(XPBD_E_INVALID, "xpbd::repack_bodies: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd::repack_bodies: NULL argument");
     constexpr uint32_t rec = kRigidDoubles + 1;
     uint32_t max_shape_id = w->max_shape_id;
     for (uint32_t s = 0; s < n_new; ++s) {
         const int32_t from = host_src[s];
         if (from >= 0 ? (uint32_t)from >= w->n : (uint32_t)(-(from + 1)) >= n_incoming)
-            return fail(XPBD_E_INVALID, "xpbd::repack_bodies: body %u comes from %d (%u bodies present, %u incoming)", s, from, w->n, n_incoming);
+            return set_error(XPBD_E_INVALID, "xpbd::repack_bodies: body %u comes from %d (%u bodies present, %u incoming)", s, from, w->n, n_incoming);
     }
     for (uint32_t k = 0; k < n_incoming; ++k) {
         const double sid = incoming39[(size_t)k * rec + kRigidDoubles];
         if (!(sid >= 0.0) || sid >= (double)w->n_shapes)
-            return fail(XPBD_E_INVALID, "xpbd::repack_bodies: incoming record %u has shape id %g of %u", k, sid, w->n_shapes);
+            return set_error(XPBD_E_INVALID, "xpbd::repack_bodies: incoming record %u has shape id %g of %u", k, sid, w->n_shapes);
         max_shape_id = std::max(max_shape_id, (uint32_t)sid);
     }
     if (int rc = bind_device(w))
@@ -764,6 +733,28 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     XPBD_HIP_TRY(hipMemsetAsync(w->last_mask.ptr, 0, (size_t)stride * 4, w->stream));
     XPBD_HIP_TRY(launch_aos_to_soa(w->repack_aos.as<double>(), w->arrays(), w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the caller's buffers are only borrowed
+    return XPBD_OK;
+}
+
+int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies)
+{
+    for (uint32_t k = 0; k < n_joints; ++k) {
+        const xpbd_joint &j = joints[k];
+        if (j.body_a >= n_bodies || j.body_b >= n_bodies || j.body_a == j.body_b)
+            return set_error(XPBD_E_INVALID, "%s: joint %u links bodies %u and %u of %u", who, k, j.body_a, j.body_b, n_bodies);
+        if (!(j.distance >= 0.0) || !(j.distance <= 1.0e300))
+            return set_error(XPBD_E_INVALID, "%s: joint %u has distance %g", who, k, j.distance);
+        if (j.kind != XPBD_JOINT_DISTANCE && j.kind != XPBD_JOINT_HINGE)
+            return set_error(XPBD_E_INVALID, "%s: joint %u has unknown kind %u", who, k, j.kind);
+        if (j.reserved != 0)
+            return set_error(XPBD_E_INVALID, "%s: joint %u: reserved must be 0", who, k);
+        if (j.kind == XPBD_JOINT_HINGE)
+            for (const double *axis : {j.axis_a, j.axis_b}) {
+                const double len2 = axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2];
+                if (!(len2 > 0.999 && len2 < 1.001))
+                    return set_error(XPBD_E_INVALID, "%s: hinge %u needs unit axes (|axis|^2 = %g)", who, k, len2);
+            }
+    }
     return XPBD_OK;
 }
 
@@ -889,11 +880,11 @@ int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t 
 
 extern "C" {
 
-uint32_t xpbd_abi_version(void) { return XPBD_ABI_VERSION; }
+uint32_t xpbd_abi_version(void) noexcept { return XPBD_ABI_VERSION; }
 
-const char *xpbd_last_error(void) { return g_last_error.c_str(); }
+const char *xpbd_last_error(void) noexcept { return g_last_error; }
 
-void xpbd_config_default(xpbd_config *cfg)
+void xpbd_config_default(xpbd_config *cfg) noexcept
 {
     if (!cfg)
         return;
@@ -904,49 +895,47 @@ void xpbd_config_default(xpbd_config *cfg)
 }
 
 int xpbd_device_count(void)
-{
+try {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess)
-        return fail(XPBD_E_NO_DEVICE, "hipGetDeviceCount failed: %s", hipGetErrorString(e));
+        return set_error(XPBD_E_NO_DEVICE, "hipGetDeviceCount failed: %s", hipGetErrorString(e));
     return n;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_create(xpbd_world **out, const xpbd_config *cfg)
-{
+try {
     if (!out)
-        return fail(XPBD_E_INVALID, "xpbd_world_create: out is NULL");
+        return set_error(XPBD_E_INVALID, "xpbd_world_create: out is NULL");
     *out = nullptr;
     xpbd_config c;
     xpbd_config_default(&c);
     if (cfg) {
         if (cfg->struct_size != sizeof(xpbd_config))
-            return fail(XPBD_E_INVALID, "xpbd_world_create: struct_size %u != %zu", cfg->struct_size,
-                        sizeof(xpbd_config));
+            return set_error(XPBD_E_INVALID, "xpbd_world_create: struct_size %u != %zu", cfg->struct_size,
+                             sizeof(xpbd_config));
         c = *cfg;
     }
     if (c.mode != XPBD_MODE_FUSED && c.mode != XPBD_MODE_PER_SUBSTEP && c.mode != XPBD_MODE_CONTACTS)
-        return fail(XPBD_E_INVALID, "xpbd_world_create: unknown mode %u", c.mode);
+        return set_error(XPBD_E_INVALID, "xpbd_world_create: unknown mode %u", c.mode);
     if (c.flags & ~XPBD_FLAG_TRACE_CONTACTS)
-        return fail(XPBD_E_INVALID, "xpbd_world_create: unknown flags 0x%x", c.flags);
+        return set_error(XPBD_E_INVALID, "xpbd_world_create: unknown flags 0x%x", c.flags);
     // k_step is compiled with __launch_bounds__(xpbd::kMaxStepBlock): a larger workgroup is a launch failure
     if (c.block_size != 0 && (c.block_size % 64 != 0 || c.block_size > xpbd::kMaxStepBlock))
-        return fail(XPBD_E_INVALID, "xpbd_world_create: block_size %u must be a multiple of 64, <= %u",
-                    c.block_size, xpbd::kMaxStepBlock);
+        return set_error(XPBD_E_INVALID, "xpbd_world_create: block_size %u must be a multiple of 64, <= %u",
+                         c.block_size, xpbd::kMaxStepBlock);
     if (c.reserved[0] || c.reserved[1] || c.reserved[2])
-        return fail(XPBD_E_INVALID, "xpbd_world_create: reserved fields must be 0");
+        return set_error(XPBD_E_INVALID, "xpbd_world_create: reserved fields must be 0");
 
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0)
-        return fail(XPBD_E_NO_DEVICE, "no HIP device available (%s)",
-                    e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
+        return set_error(XPBD_E_NO_DEVICE, "no HIP device available (%s)",
+                         e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
     if (c.device < 0 || c.device >= count)
-        return fail(XPBD_E_INVALID, "xpbd_world_create: device %d out of range [0,%d)", c.device, count);
+        return set_error(XPBD_E_INVALID, "xpbd_world_create: device %d out of range [0,%d)", c.device, count);
 
-    xpbd_world *w = new (std::nothrow) xpbd_world;
-    if (!w)
-        return fail(XPBD_E_OOM, "xpbd_world_create: host allocation failed");
+    std::unique_ptr<xpbd_world> w(new xpbd_world);
     w->device = c.device;
     w->mode = c.mode;
     w->flags = c.flags;
@@ -954,69 +943,37 @@ int xpbd_world_create(xpbd_world **out, const xpbd_config *cfg)
     e = hipSetDevice(w->device);
     if (e == hipSuccess)
         e = hipStreamCreateWithFlags(&w->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete w;
-        return fail(XPBD_E_HIP, "xpbd_world_create: stream creation failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess)
+        return set_error(XPBD_E_HIP, "xpbd_world_create: stream creation failed: %s", hipGetErrorString(e));
     w->stream = w->own_stream;
-    *out = w;
+    *out = w.release();
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
-void xpbd_world_destroy(xpbd_world *w)
-{
-    if (!w)
-        return;
-    (void)hipSetDevice(w->device);
-    if (w->stream)
-        (void)hipStreamSynchronize(w->stream);
-    for (DeviceBuffer *b : {&w->dyn, &w->stat, &w->shape_id, &w->aos_staging, &w->last_mask, &w->trace,
-                            &w->block_counts, &w->contacts, &w->shape_verts, &w->shape_offsets, &w->planes,
-                            &w->centroids, &w->shape_desc, &w->face_start, &w->face_verts, &w->edges, &w->pair_buf,
-                            &w->manifold_buf, &w->shape_radii, &w->edge_dirs, &w->edge_dir_id, &w->shape_class, &w->dyn_alt, &w->cb_centers, &w->cb_radius, &w->cb_cell,
-                            &w->cb_key, &w->cb_maxr, &w->cb_bucket_start, &w->cb_bucket_cursor, &w->cb_items,
-                            &w->cb_nbr_off, &w->cb_pair_first, &w->cb_upper_start, &w->cb_nbr, &w->cb_nbr_pair,
-                            &w->cb_pairs, &w->cb_rec, &w->cb_stat_rec, &w->cb_manifolds,
-                            &w->cb_stats, &w->cb_scan, &w->jt_joints, &w->jt_off, &w->jt_list, &w->jt_limits, &w->jt_limit_off, &w->gjk_counters,
-                            &w->gjk_pairs_scratch, &w->cb_slot_sphere, &w->cb_slot_cell, &w->history,
-                            &w->sat_counters, &w->sat_survivors, &w->sat_axis_cache, &w->gjk_axis_cache, &w->cb_stat_shape, &w->cb_pair_codes, &w->cb_rec_b,
-                            &w->cb_grid_partials, &w->cb_items_unsorted, &w->q_rec, &w->q_partials, &w->q_grid, &w->q_cell_start,
-                            &w->q_cell_fill, &w->q_items, &w->q_scan, &w->q_brute, &w->q_rays, &w->q_hits, &w->ft_filters,
-                            &w->cb_slot_filter})
-        b->release();
-    for (DeviceBuffer *b : {&w->frame_snapshot, &w->repack_aos, &w->repack_shape, &w->repack_src, &w->repack_incoming, &w->halo_keys, &w->halo_records})
-        b->release();
-    if (w->bp_totals)
-        (void)hipHostFree(w->bp_totals);
-    if (w->bp_event)
-        (void)hipEventDestroy(w->bp_event);
-    if (w->own_stream)
-        (void)hipStreamDestroy(w->own_stream);
-    delete w;
-}
+void xpbd_world_destroy(xpbd_world *w) noexcept { delete w; }
 
 int xpbd_world_set_shapes(xpbd_world *w, const double *verts_xyz, const uint32_t *vert_offsets,
                           uint32_t n_shapes)
-{
+try {
     if (!w || !verts_xyz || !vert_offsets || n_shapes == 0)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_shapes: NULL argument or no shapes");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: NULL argument or no shapes");
     if (vert_offsets[0] != 0)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_shapes: vert_offsets[0] must be 0");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: vert_offsets[0] must be 0");
     for (uint32_t s = 0; s < n_shapes; ++s) {
         if (vert_offsets[s + 1] < vert_offsets[s])
-            return fail(XPBD_E_INVALID, "xpbd_world_set_shapes: vert_offsets not monotone at %u", s);
+            return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: vert_offsets not monotone at %u", s);
         if (vert_offsets[s + 1] - vert_offsets[s] > XPBD_MAX_SHAPE_VERTS)
-            return fail(XPBD_E_INVALID, "xpbd_world_set_shapes: shape %u has %u vertices (max %u)", s,
-                        vert_offsets[s + 1] - vert_offsets[s], XPBD_MAX_SHAPE_VERTS);
+            return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: shape %u has %u vertices (max %u)", s,
+                             vert_offsets[s + 1] - vert_offsets[s], XPBD_MAX_SHAPE_VERTS);
     }
     const uint32_t total = vert_offsets[n_shapes];
     // The tables are staged into LDS by every block; keep them far below the 160 KiB/CU.
     if ((size_t)total * 24 + (size_t)(n_shapes + 1) * 4 > 48 * 1024)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_shapes: shape tables exceed 48 KiB");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: shape tables exceed 48 KiB");
     // the resident bodies keep their shape ids: the kernels index the staged table with them unchecked
     if (w->n && n_shapes <= w->max_shape_id)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_shapes: %u shapes, but the uploaded bodies use shape id %u (upload bodies "
-                                    "again after shrinking the table)", n_shapes, w->max_shape_id);
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: %u shapes, but the uploaded bodies use shape id %u (upload bodies "
+                                         "again after shrinking the table)", n_shapes, w->max_shape_id);
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
@@ -1029,12 +986,12 @@ int xpbd_world_set_shapes(xpbd_world *w, const double *verts_xyz, const uint32_t
     w->total_verts = total;
     w->has_topology = false;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_set_polytopes(xpbd_world *w, const xpbd_polytope *shapes, uint32_t n_shapes)
-{
+try {
     if (!w || !shapes || n_shapes == 0)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_polytopes: NULL argument or no shapes");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: NULL argument or no shapes");
     std::vector<double> verts, planes, centroids, radii, dirs;
     std::vector<uint32_t> vert_offsets{0}, face_start{0}, face_verts, edges, dir_id;
     std::vector<xpbd::ShapeDesc> desc;
@@ -1042,10 +999,10 @@ int xpbd_world_set_polytopes(xpbd_world *w, const xpbd_polytope *shapes, uint32_
         const xpbd_polytope &p = shapes[s];
         if ((p.n_vertices && !p.vertices_xyz) || (p.n_edges && !p.edges) ||
             (p.n_faces && (!p.face_offsets || !p.face_indices)))
-            return fail(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u has a NULL table", s);
+            return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u has a NULL table", s);
         if (p.n_vertices > XPBD_MAX_SHAPE_VERTS || p.n_faces > 64 || p.n_edges > 4096)
-            return fail(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u too large (%u vertices, %u faces, %u edges)",
-                        s, p.n_vertices, p.n_faces, p.n_edges);
+            return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u too large (%u vertices, %u faces, %u edges)",
+                             s, p.n_vertices, p.n_faces, p.n_edges);
         xpbd::ShapeDesc d{};
         d.vert0 = (uint32_t)(verts.size() / 3);
         d.n_verts = p.n_vertices;
@@ -1060,7 +1017,7 @@ int xpbd_world_set_polytopes(xpbd_world *w, const xpbd_polytope *shapes, uint32_
         };
         for (uint32_t e = 0; e < 2 * p.n_edges; ++e) {
             if (p.edges[e] >= p.n_vertices)
-                return fail(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u edge vertex out of range", s);
+                return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u edge vertex out of range", s);
             edges.push_back(p.edges[e]);
         }
         // unique edge directions (up to sign), first edge with a direction represents it
@@ -1087,11 +1044,11 @@ int xpbd_world_set_polytopes(xpbd_world *w, const xpbd_polytope *shapes, uint32_
         for (uint32_t f = 0; f < p.n_faces; ++f) {
             const uint32_t f0 = p.face_offsets[f], f1 = p.face_offsets[f + 1];
             if (f1 < f0 || f1 - f0 < 3 || f1 - f0 > xpbd::kMaxFaceVerts)
-                return fail(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u face %u needs 3..%u vertices", s, f,
-                            xpbd::kMaxFaceVerts);
+                return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u face %u needs 3..%u vertices", s, f,
+                                 xpbd::kMaxFaceVerts);
             for (uint32_t q = f0; q < f1; ++q) {
                 if (p.face_indices[q] >= p.n_vertices)
-                    return fail(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u face vertex out of range", s);
+                    return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u face vertex out of range", s);
                 face_verts.push_back(p.face_indices[q]);
             }
             face_start.push_back((uint32_t)face_verts.size());
@@ -1158,18 +1115,18 @@ int xpbd_world_set_polytopes(xpbd_world *w, const xpbd_polytope *shapes, uint32_
     w->max_faces = max_faces;
     w->max_face_verts = max_face_verts;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_narrowphase(xpbd_world *w, const uint32_t *pairs, uint32_t n_pairs, xpbd_manifold *out)
-{
+try {
     static_assert(sizeof(xpbd_manifold) == sizeof(xpbd::Manifold), "xpbd_manifold must mirror xpbd::Manifold");
     if (!w || (n_pairs && (!pairs || !out)))
-        return fail(XPBD_E_INVALID, "xpbd_world_narrowphase: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase: NULL argument");
     if (!w->has_topology)
-        return fail(XPBD_E_INVALID, "xpbd_world_narrowphase: call xpbd_world_set_polytopes first");
+        return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase: call xpbd_world_set_polytopes first");
     for (uint32_t k = 0; k < 2 * n_pairs; ++k)
         if (pairs[k] >= w->n)
-            return fail(XPBD_E_INVALID, "xpbd_world_narrowphase: pair %u names body %u of %u", k / 2, pairs[k], w->n);
+            return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase: pair %u names body %u of %u", k / 2, pairs[k], w->n);
     if (n_pairs == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -1187,18 +1144,18 @@ int xpbd_world_narrowphase(xpbd_world *w, const uint32_t *pairs, uint32_t n_pair
                                 hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_edge_axes_separation(xpbd_world *w, const uint32_t *pairs, uint32_t n_pairs, xpbd_edge_query *out)
-{
+try {
     static_assert(sizeof(xpbd_edge_query) == sizeof(xpbd::EdgeQuery), "xpbd_edge_query must mirror xpbd::EdgeQuery");
     if (!w || (n_pairs && (!pairs || !out)))
-        return fail(XPBD_E_INVALID, "xpbd_world_edge_axes_separation: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_edge_axes_separation: NULL argument");
     if (!w->has_topology)
-        return fail(XPBD_E_INVALID, "xpbd_world_edge_axes_separation: call xpbd_world_set_polytopes first");
+        return set_error(XPBD_E_INVALID, "xpbd_world_edge_axes_separation: call xpbd_world_set_polytopes first");
     for (uint32_t k = 0; k < 2 * n_pairs; ++k)
         if (pairs[k] >= w->n)
-            return fail(XPBD_E_INVALID, "xpbd_world_edge_axes_separation: pair %u names body %u of %u", k / 2, pairs[k], w->n);
+            return set_error(XPBD_E_INVALID, "xpbd_world_edge_axes_separation: pair %u names body %u of %u", k / 2, pairs[k], w->n);
     if (n_pairs == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -1214,20 +1171,20 @@ int xpbd_world_edge_axes_separation(xpbd_world *w, const uint32_t *pairs, uint32
     XPBD_HIP_TRY(hipMemcpyAsync(out, w->manifold_buf.ptr, (size_t)n_pairs * sizeof(xpbd::EdgeQuery), hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_upload_bodies(xpbd_world *w, const xpbd_rigid *aos, const uint32_t *shape_id, uint32_t n)
-{
+try {
     if (!w || (!aos && n))
-        return fail(XPBD_E_INVALID, "xpbd_world_upload_bodies: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_upload_bodies: NULL argument");
     if (w->n_shapes == 0)
-        return fail(XPBD_E_INVALID, "xpbd_world_upload_bodies: call xpbd_world_set_shapes first");
+        return set_error(XPBD_E_INVALID, "xpbd_world_upload_bodies: call xpbd_world_set_shapes first");
     uint32_t max_shape_id = 0;
     if (shape_id)
         for (uint32_t i = 0; i < n; ++i) {
             if (shape_id[i] >= w->n_shapes)
-                return fail(XPBD_E_INVALID, "xpbd_world_upload_bodies: shape_id[%u] = %u >= n_shapes %u", i,
-                            shape_id[i], w->n_shapes);
+                return set_error(XPBD_E_INVALID, "xpbd_world_upload_bodies: shape_id[%u] = %u >= n_shapes %u", i,
+                                 shape_id[i], w->n_shapes);
             max_shape_id = shape_id[i] > max_shape_id ? shape_id[i] : max_shape_id;
         }
     if (int rc = bind_device(w))
@@ -1273,14 +1230,14 @@ int xpbd_world_upload_bodies(xpbd_world *w, const xpbd_rigid *aos, const uint32_
     // The caller's buffers are only borrowed for the duration of the call.
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_download_bodies(xpbd_world *w, xpbd_rigid *aos, uint32_t n)
-{
+try {
     if (!w || (!aos && n))
-        return fail(XPBD_E_INVALID, "xpbd_world_download_bodies: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_bodies: NULL argument");
     if (n != w->n)
-        return fail(XPBD_E_INVALID, "xpbd_world_download_bodies: n = %u but the world holds %u bodies", n, w->n);
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_bodies: n = %u but the world holds %u bodies", n, w->n);
     if (n == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -1290,16 +1247,16 @@ int xpbd_world_download_bodies(xpbd_world *w, xpbd_rigid *aos, uint32_t n)
                                 w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
-uint32_t xpbd_world_body_count(const xpbd_world *w) { return w ? w->n : 0; }
+uint32_t xpbd_world_body_count(const xpbd_world *w) noexcept { return w ? w->n : 0; }
 
 int xpbd_world_download_frames(xpbd_world *w, double *frames, uint32_t n)
-{
+try {
     if (!w || (!frames && n))
-        return fail(XPBD_E_INVALID, "xpbd_world_download_frames: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_frames: NULL argument");
     if (n != w->n)
-        return fail(XPBD_E_INVALID, "xpbd_world_download_frames: n = %u but the world holds %u bodies", n, w->n);
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_frames: n = %u but the world holds %u bodies", n, w->n);
     if (n == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -1309,16 +1266,16 @@ int xpbd_world_download_frames(xpbd_world *w, double *frames, uint32_t n)
     XPBD_HIP_TRY(hipMemcpyAsync(frames, w->aos_staging.ptr, (size_t)n * 7 * 8, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_step(xpbd_world *w, double dt, uint32_t substeps)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_step: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_step: NULL world");
     if (substeps == 0) // the reference divides by zero and runs no substep; treat as an argument error
-        return fail(XPBD_E_INVALID, "xpbd_world_step: substeps must be > 0");
+        return set_error(XPBD_E_INVALID, "xpbd_world_step: substeps must be > 0");
     if (w->n_shapes == 0)
-        return fail(XPBD_E_INVALID, "xpbd_world_step: no shapes set");
+        return set_error(XPBD_E_INVALID, "xpbd_world_step: no shapes set");
     if (w->n == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -1344,22 +1301,22 @@ int xpbd_world_step(xpbd_world *w, double dt, uint32_t substeps)
     }
     w->stepped = true;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_synchronize(xpbd_world *w)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_synchronize: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_synchronize: NULL world");
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_download_contacts(xpbd_world *w, xpbd_contact *out, uint32_t cap, uint32_t *n_out)
-{
+try {
     if (!w || !n_out || (!out && cap))
-        return fail(XPBD_E_INVALID, "xpbd_world_download_contacts: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_contacts: NULL argument");
     *n_out = 0;
     if (w->n == 0 || !w->stepped)
         return XPBD_OK;
@@ -1384,20 +1341,20 @@ int xpbd_world_download_contacts(xpbd_world *w, xpbd_contact *out, uint32_t cap,
         XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     }
     if (total > cap)
-        return fail(XPBD_E_CAPACITY, "xpbd_world_download_contacts: %u contacts, capacity %u", total, cap);
+        return set_error(XPBD_E_CAPACITY, "xpbd_world_download_contacts: %u contacts, capacity %u", total, cap);
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_download_contact_masks(xpbd_world *w, uint32_t *masks, uint32_t substeps, uint32_t n)
-{
+try {
     if (!w || !masks)
-        return fail(XPBD_E_INVALID, "xpbd_world_download_contact_masks: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_contact_masks: NULL argument");
     if (!(w->flags & XPBD_FLAG_TRACE_CONTACTS))
-        return fail(XPBD_E_INVALID, "xpbd_world_download_contact_masks: world created without "
-                                    "XPBD_FLAG_TRACE_CONTACTS");
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_contact_masks: world created without "
+                                         "XPBD_FLAG_TRACE_CONTACTS");
     if (n != w->n || substeps != w->trace_rows)
-        return fail(XPBD_E_INVALID, "xpbd_world_download_contact_masks: asked for %u x %u, last step recorded %u x %u",
-                    substeps, n, w->trace_rows, w->n);
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_contact_masks: asked for %u x %u, last step recorded %u x %u",
+                         substeps, n, w->trace_rows, w->n);
     if (n == 0 || substeps == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -1406,33 +1363,33 @@ int xpbd_world_download_contact_masks(xpbd_world *w, uint32_t *masks, uint32_t s
                                   hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_set_stream(xpbd_world *w, void *hip_stream)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_stream: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_stream: NULL world");
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     w->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : w->own_stream;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
-void *xpbd_world_get_stream(const xpbd_world *w) { return w ? static_cast<void *>(w->stream) : nullptr; }
+void *xpbd_world_get_stream(const xpbd_world *w) noexcept { return w ? static_cast<void *>(w->stream) : nullptr; }
 
 int xpbd_world_set_mode(xpbd_world *w, uint32_t mode)
-{
+try {
     if (!w || (mode != XPBD_MODE_FUSED && mode != XPBD_MODE_PER_SUBSTEP && mode != XPBD_MODE_CONTACTS))
-        return fail(XPBD_E_INVALID, "xpbd_world_set_mode: bad argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_mode: bad argument");
     w->mode = mode;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_step_one(xpbd_rigid *rigid, const double *verts_xyz, uint32_t nverts, double dt, uint32_t substeps)
-{
+try {
     if (!rigid || !verts_xyz)
-        return fail(XPBD_E_INVALID, "xpbd_step_one: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_step_one: NULL argument");
     // One cached single-body world per host thread (the reference's step is re-entrant and
     // stateless; so is this apart from the cache).
     struct Cache {
@@ -1454,18 +1411,18 @@ int xpbd_step_one(xpbd_rigid *rigid, const double *verts_xyz, uint32_t nverts, d
     if (int rc = xpbd_world_step(cache.w, dt, substeps))
         return rc;
     return xpbd_world_download_bodies(cache.w, rigid, 1);
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_narrowphase_gjk(xpbd_world *w, const uint32_t *pairs, uint32_t n_pairs, xpbd_gjk_result *out)
-{
+try {
     static_assert(sizeof(xpbd_gjk_result) == sizeof(xpbd::GjkResult), "xpbd_gjk_result must mirror xpbd::GjkResult");
     if (!w || (n_pairs && (!pairs || !out)))
-        return fail(XPBD_E_INVALID, "xpbd_world_narrowphase_gjk: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase_gjk: NULL argument");
     if (!w->has_topology)
-        return fail(XPBD_E_INVALID, "xpbd_world_narrowphase_gjk: call xpbd_world_set_polytopes first");
+        return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase_gjk: call xpbd_world_set_polytopes first");
     for (uint32_t k = 0; k < 2 * n_pairs; ++k)
         if (pairs[k] >= w->n)
-            return fail(XPBD_E_INVALID, "xpbd_world_narrowphase_gjk: pair %u names body %u of %u", k / 2, pairs[k], w->n);
+            return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase_gjk: pair %u names body %u of %u", k / 2, pairs[k], w->n);
     if (n_pairs == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -1486,35 +1443,20 @@ int xpbd_world_narrowphase_gjk(xpbd_world *w, const uint32_t *pairs, uint32_t n_
                                 w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_set_joints(xpbd_world *w, const xpbd_joint *joints, uint32_t n_joints)
-{
+try {
     static_assert(sizeof(xpbd_joint) == sizeof(xpbd::Joint), "xpbd_joint must mirror xpbd::Joint");
     if (!w || (n_joints && !joints))
-        return fail(XPBD_E_INVALID, "xpbd_world_set_joints: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_joints: NULL argument");
     if (n_joints && w->mode != XPBD_MODE_CONTACTS) // only the contact pipeline projects joints: do not accept and ignore them
-        return fail(XPBD_E_INVALID, "xpbd_world_set_joints: joints need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_joints: joints need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
+    XPBD_TRY(xpbd::check_joints("xpbd_world_set_joints", joints, n_joints, w->n));
     std::vector<uint32_t> off((size_t)w->n + 2, 0), list((size_t)2 * n_joints);
     for (uint32_t k = 0; k < n_joints; ++k) {
-        const xpbd_joint &j = joints[k];
-        if (j.body_a >= w->n || j.body_b >= w->n || j.body_a == j.body_b)
-            return fail(XPBD_E_INVALID, "xpbd_world_set_joints: joint %u links bodies %u and %u of %u", k, j.body_a,
-                        j.body_b, w->n);
-        if (!(j.distance >= 0.0) || !(j.distance <= 1.0e300))
-            return fail(XPBD_E_INVALID, "xpbd_world_set_joints: joint %u has distance %g", k, j.distance);
-        if (j.kind != XPBD_JOINT_DISTANCE && j.kind != XPBD_JOINT_HINGE)
-            return fail(XPBD_E_INVALID, "xpbd_world_set_joints: joint %u has unknown kind %u", k, j.kind);
-        if (j.reserved != 0)
-            return fail(XPBD_E_INVALID, "xpbd_world_set_joints: joint %u: reserved must be 0", k);
-        if (j.kind == XPBD_JOINT_HINGE)
-            for (const double *axis : {j.axis_a, j.axis_b}) {
-                const double len2 = axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2];
-                if (!(len2 > 0.999 && len2 < 1.001))
-                    return fail(XPBD_E_INVALID, "xpbd_world_set_joints: hinge %u needs unit axes (|axis|^2 = %g)", k, len2);
-            }
-        ++off[j.body_a + 1];
-        ++off[j.body_b + 1];
+        ++off[joints[k].body_a + 1];
+        ++off[joints[k].body_b + 1];
     }
     for (uint32_t i = 0; i < w->n; ++i)
         off[i + 1] += off[i];
@@ -1540,14 +1482,14 @@ int xpbd_world_set_joints(xpbd_world *w, const xpbd_joint *joints, uint32_t n_jo
     w->n_joints = n_joints;
     w->joints_host.assign(joints, joints + n_joints);
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, uint32_t n_limits)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_joint_limits: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_limits: NULL world");
     if (n_limits && w->mode != XPBD_MODE_CONTACTS)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_joint_limits: limits need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_limits: limits need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
     if (int rc = xpbd::check_joint_limits("xpbd_world_set_joint_limits", w->joints_host.data(), w->n_joints, limits, n_limits))
         return rc;
     // CSR joint -> limits, the caller's order inside a joint
@@ -1576,19 +1518,19 @@ int xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, u
     XPBD_HIP_TRY(hipMemcpy(w->jt_limit_off.ptr, off.data(), off.size() * 4, hipMemcpyHostToDevice));
     w->n_limits = n_limits;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_set_collision_filters(xpbd_world *w, const xpbd_collision_filter *filters, uint32_t n, uint32_t flags)
-{
+try {
     static_assert(sizeof(xpbd_collision_filter) == sizeof(uint2), "xpbd_collision_filter must mirror uint2 {group, mask}");
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_collision_filters: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_collision_filters: NULL world");
     if (!filters && n)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_collision_filters: NULL filters with n = %u", n);
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_collision_filters: NULL filters with n = %u", n);
     if (filters && n != w->n)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_collision_filters: n = %u but the world holds %u bodies", n, w->n);
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_collision_filters: n = %u but the world holds %u bodies", n, w->n);
     if (flags & ~XPBD_FILTER_JOINTED)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_collision_filters: unknown flags 0x%x", flags);
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_collision_filters: unknown flags 0x%x", flags);
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued broadphases may still read the present filters
@@ -1602,123 +1544,123 @@ int xpbd_world_set_collision_filters(xpbd_world *w, const xpbd_collision_filter 
     XPBD_HIP_TRY(hipMemcpy(w->ft_filters.ptr, filters, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice));
     w->has_filters = true;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_contacts_begin(xpbd_world *w, double dt)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_contacts_begin: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: NULL world");
     if (w->mode != XPBD_MODE_CONTACTS || !w->has_topology)
-        return fail(XPBD_E_INVALID, "xpbd_world_contacts_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
+        return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
     if (int rc = bind_device(w))
         return rc;
     w->stepped = true;
     return w->n ? build_neighbours(w, dt) : XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_contacts_substep(xpbd_world *w, double h)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_contacts_substep: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_contacts_substep: NULL world");
     if (w->mode != XPBD_MODE_CONTACTS || (w->n && !w->have_neighbours))
-        return fail(XPBD_E_INVALID, "xpbd_world_contacts_substep: call xpbd_world_contacts_begin first");
+        return set_error(XPBD_E_INVALID, "xpbd_world_contacts_substep: call xpbd_world_contacts_begin first");
     if (w->n == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
         return rc;
     return substep_contacts(w, h, nullptr, 0);
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_export_dynamic(xpbd_world *w, const uint32_t *dev_indices, uint32_t n, double *dev_buf)
-{
+try {
     if (!w || (n && (!dev_indices || !dev_buf)))
-        return fail(XPBD_E_INVALID, "xpbd_world_export_dynamic: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_export_dynamic: NULL argument");
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(xpbd::launch_export_dynamic(w->arrays(), dev_indices, n, dev_buf, w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_import_dynamic(xpbd_world *w, const uint32_t *dev_indices, uint32_t n, const double *dev_buf)
-{
+try {
     if (!w || (n && (!dev_indices || !dev_buf)))
-        return fail(XPBD_E_INVALID, "xpbd_world_import_dynamic: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_import_dynamic: NULL argument");
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(xpbd::launch_import_dynamic(w->arrays(), dev_indices, nullptr, n, dev_buf, w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_import_dynamic_rows(xpbd_world *w, const uint32_t *dev_indices, const uint32_t *dev_rows, uint32_t n,
                                    const double *dev_buf)
-{
+try {
     if (!w || (n && (!dev_indices || !dev_rows || !dev_buf)))
-        return fail(XPBD_E_INVALID, "xpbd_world_import_dynamic_rows: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_import_dynamic_rows: NULL argument");
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(xpbd::launch_import_dynamic(w->arrays(), dev_indices, dev_rows, n, dev_buf, w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_snapshot_positions(xpbd_world *w, const uint32_t *dev_indices, uint32_t n, double *dev_snapshot)
-{
+try {
     if (!w || (n && (!dev_indices || !dev_snapshot)))
-        return fail(XPBD_E_INVALID, "xpbd_world_snapshot_positions: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_snapshot_positions: NULL argument");
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(xpbd::launch_snapshot_positions(w->arrays(), dev_indices, n, dev_snapshot, w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_max_displacement2(xpbd_world *w, const uint32_t *dev_indices, uint32_t n, const double *dev_snapshot, const double *dev_scale,
                                  double *dev_max)
-{
+try {
     if (!w || !dev_max || (n && (!dev_indices || !dev_snapshot)))
-        return fail(XPBD_E_INVALID, "xpbd_world_max_displacement2: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_max_displacement2: NULL argument");
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(xpbd::launch_max_displacement2(w->arrays(), dev_indices, n, dev_snapshot, dev_scale, dev_max, w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_set_sat_schedule(xpbd_world *w, uint32_t schedule)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_sat_schedule: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_sat_schedule: NULL world");
     if (schedule > XPBD_SAT_SCHEDULE_TWO_PASS)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_sat_schedule: unknown schedule %u", schedule);
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_sat_schedule: unknown schedule %u", schedule);
     w->sat_schedule = schedule;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_set_narrowphase(xpbd_world *w, uint32_t narrowphase)
-{
+try {
     if (!w || (narrowphase != XPBD_NARROWPHASE_SAT && narrowphase != XPBD_NARROWPHASE_GJK_EPA))
-        return fail(XPBD_E_INVALID, "xpbd_world_set_narrowphase: bad argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_narrowphase: bad argument");
     w->narrowphase = narrowphase;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_set_contact_pad(xpbd_world *w, double pad)
-{
+try {
     if (!w || !(pad >= 0.0) || pad > 1.0e6)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_contact_pad: bad argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_contact_pad: bad argument");
     w->contact_pad = pad;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_set_max_depenetration_speed(xpbd_world *w, double speed)
-{
+try {
     if (!w || !(speed >= 0.0) || speed > 1.0e300)
-        return fail(XPBD_E_INVALID, "xpbd_world_set_max_depenetration_speed: bad argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_max_depenetration_speed: bad argument");
     w->max_depenetration_speed = speed;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_contact_stats(xpbd_world *w, uint64_t out[3])
-{
+try {
     if (!w || !out)
-        return fail(XPBD_E_INVALID, "xpbd_world_contact_stats: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_contact_stats: NULL argument");
     out[0] = w->n_pairs;
     out[1] = out[2] = 0;
     if (!w->cb_stats.ptr)
@@ -1734,30 +1676,30 @@ int xpbd_world_contact_stats(xpbd_world *w, uint64_t out[3])
     out[1] = host[0];
     out[2] = host[1];
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_build_neighbours(xpbd_world *w, double dt, uint32_t *n_entries_out)
-{
+try {
     if (!w || !n_entries_out)
-        return fail(XPBD_E_INVALID, "xpbd_world_build_neighbours: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_build_neighbours: NULL argument");
     if (!w->has_topology)
-        return fail(XPBD_E_INVALID, "xpbd_world_build_neighbours: call xpbd_world_set_polytopes first");
+        return set_error(XPBD_E_INVALID, "xpbd_world_build_neighbours: call xpbd_world_set_polytopes first");
     if (int rc = bind_device(w))
         return rc;
     if (int rc = build_neighbours(w, dt))
         return rc;
     *n_entries_out = w->n_entries;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_download_neighbours(xpbd_world *w, uint32_t *offsets, uint32_t *neighbours, uint32_t cap)
-{
+try {
     if (!w || !offsets || (!neighbours && cap))
-        return fail(XPBD_E_INVALID, "xpbd_world_download_neighbours: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_neighbours: NULL argument");
     if (!w->have_neighbours)
-        return fail(XPBD_E_INVALID, "xpbd_world_download_neighbours: no neighbour lists built yet");
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_neighbours: no neighbour lists built yet");
     if (cap < w->n_entries)
-        return fail(XPBD_E_CAPACITY, "xpbd_world_download_neighbours: %u entries, capacity %u", w->n_entries, cap);
+        return set_error(XPBD_E_CAPACITY, "xpbd_world_download_neighbours: %u entries, capacity %u", w->n_entries, cap);
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipMemcpyAsync(offsets, w->cb_nbr_off.ptr, (size_t)(w->n + 1) * 4, hipMemcpyDeviceToHost, w->stream));
@@ -1765,14 +1707,14 @@ int xpbd_world_download_neighbours(xpbd_world *w, uint32_t *offsets, uint32_t *n
         XPBD_HIP_TRY(hipMemcpyAsync(neighbours, w->cb_nbr.ptr, (size_t)w->n_entries * 4, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_history_push(xpbd_world *w, uint32_t *index_out)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_history_push: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_history_push: NULL world");
     if (w->n == 0)
-        return fail(XPBD_E_INVALID, "xpbd_world_history_push: no bodies uploaded");
+        return set_error(XPBD_E_INVALID, "xpbd_world_history_push: no bodies uploaded");
     if (int rc = bind_device(w))
         return rc;
     const size_t slot = w->history_slot_bytes();
@@ -1783,17 +1725,14 @@ int xpbd_world_history_push(xpbd_world *w, uint32_t *index_out)
         DeviceBuffer bigger;
         hipError_t e = bigger.reserve((size_t)capacity * slot);
         if (e != hipSuccess)
-            return fail(e == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "xpbd_world_history_push: %u states of %zu bytes: %s",
-                        capacity, slot, hipGetErrorString(e));
+            return set_error(e == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "xpbd_world_history_push: %u states of %zu bytes: %s",
+                             capacity, slot, hipGetErrorString(e));
         e = hipStreamSynchronize(w->stream);
         if (e == hipSuccess && w->history_length)
             e = hipMemcpy(bigger.ptr, w->history.ptr, (size_t)w->history_length * slot, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            bigger.release();
-            return fail(XPBD_E_HIP, "xpbd_world_history_push: carrying %u states over failed: %s", w->history_length, hipGetErrorString(e));
-        }
-        w->history.release();
-        w->history = bigger;
+        if (e != hipSuccess)
+            return set_error(XPBD_E_HIP, "xpbd_world_history_push: carrying %u states over failed: %s", w->history_length, hipGetErrorString(e));
+        w->history = std::move(bigger); // (the old block goes with `bigger`)
     }
     char *dst = static_cast<char *>(w->history.ptr) + (size_t)w->history_length * slot;
     const size_t dyn_bytes = (size_t)xpbd::kDynFields * w->stride * 8;
@@ -1804,14 +1743,14 @@ int xpbd_world_history_push(xpbd_world *w, uint32_t *index_out)
         *index_out = w->history_length;
     ++w->history_length;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_history_restore(xpbd_world *w, uint32_t index)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_history_restore: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_history_restore: NULL world");
     if (index >= w->history_length)
-        return fail(XPBD_E_INVALID, "xpbd_world_history_restore: state %u of %u", index, w->history_length);
+        return set_error(XPBD_E_INVALID, "xpbd_world_history_restore: state %u of %u", index, w->history_length);
     if (int rc = bind_device(w))
         return rc;
     const size_t slot = w->history_slot_bytes();
@@ -1823,59 +1762,59 @@ int xpbd_world_history_restore(xpbd_world *w, uint32_t index)
     w->have_neighbours = false;
     w->trace_rows = 0; // the per-substep trace belongs to the step call that was overwritten
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_history_truncate(xpbd_world *w, uint32_t length)
-{
+try {
     if (!w)
-        return fail(XPBD_E_INVALID, "xpbd_world_history_truncate: NULL world");
+        return set_error(XPBD_E_INVALID, "xpbd_world_history_truncate: NULL world");
     if (length > w->history_length)
-        return fail(XPBD_E_INVALID, "xpbd_world_history_truncate: length %u > %u", length, w->history_length);
+        return set_error(XPBD_E_INVALID, "xpbd_world_history_truncate: length %u > %u", length, w->history_length);
     w->history_length = length;
     w->history_stepped.resize(length);
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
-uint32_t xpbd_world_history_length(const xpbd_world *w) { return w ? w->history_length : 0; }
+uint32_t xpbd_world_history_length(const xpbd_world *w) noexcept { return w ? w->history_length : 0; }
 
 int xpbd_world_raycast(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
-{
+try {
     if (int rc = xpbd::check_raycast("xpbd_world_raycast", w, rays, n_rays, flags, hits))
         return rc;
     if (int rc = xpbd::check_rays_reserved("xpbd_world_raycast", rays, n_rays))
         return rc;
     return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr, false, 0u);
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_raycast_masked(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, uint32_t mask, xpbd_ray_hit *hits)
-{
+try {
     if (int rc = xpbd::check_raycast("xpbd_world_raycast_masked", w, rays, n_rays, flags, hits))
         return rc;
     if (int rc = xpbd::check_rays_reserved("xpbd_world_raycast_masked", rays, n_rays))
         return rc;
     return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr, true, mask);
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_raycast_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits)
-{
+try {
     if (int rc = xpbd::check_raycast("xpbd_world_raycast_device", w, dev_rays, n_rays, flags, dev_hits))
         return rc;
     return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr, false, 0u);
-}
+} XPBD_ABI_CATCH
 
 int xpbd_world_raycast_masked_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, uint32_t mask,
                                      xpbd_ray_hit *dev_hits)
-{
+try {
     if (int rc = xpbd::check_raycast("xpbd_world_raycast_masked_device", w, dev_rays, n_rays, flags, dev_hits))
         return rc;
     return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr, true, mask);
-}
+} XPBD_ABI_CATCH
 
 int xpbd_selftest_div_sqrt(int32_t device, const double *a, const double *b, double *quotient, double *root,
                            uint32_t n)
-{
+try {
     if (n && (!a || !b || !quotient || !root))
-        return fail(XPBD_E_INVALID, "xpbd_selftest_div_sqrt: NULL argument");
+        return set_error(XPBD_E_INVALID, "xpbd_selftest_div_sqrt: NULL argument");
     if (n == 0)
         return XPBD_OK;
     XPBD_HIP_TRY(hipSetDevice(device));
@@ -1883,23 +1822,22 @@ int xpbd_selftest_div_sqrt(int32_t device, const double *a, const double *b, dou
     const size_t bytes = (size_t)n * 8;
     hipError_t e = buf.reserve(4 * bytes);
     if (e != hipSuccess)
-        return fail(XPBD_E_OOM, "xpbd_selftest_div_sqrt: %s", hipGetErrorString(e));
+        return set_error(XPBD_E_OOM, "xpbd_selftest_div_sqrt: %s", hipGetErrorString(e));
     double *d = buf.as<double>();
     e = hipMemcpy(d, a, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d + n, b, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = xpbd::launch_selftest_div_sqrt(d, d + n, d + 2 * (size_t)n, d + 3 * (size_t)n, n, nullptr);
     if (e == hipSuccess) e = hipMemcpy(quotient, d + 2 * (size_t)n, bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(root, d + 3 * (size_t)n, bytes, hipMemcpyDeviceToHost);
-    buf.release();
     if (e != hipSuccess)
-        return fail(XPBD_E_HIP, "xpbd_selftest_div_sqrt: %s", hipGetErrorString(e));
+        return set_error(XPBD_E_HIP, "xpbd_selftest_div_sqrt: %s", hipGetErrorString(e));
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_selftest_hbm_copy(int32_t device, uint64_t bytes, uint32_t repeats, double *gbytes_per_s)
-{
+try {
     if (!gbytes_per_s || bytes < 16 || bytes >= (1ull << 40) || repeats == 0)
-        return fail(XPBD_E_INVALID, "xpbd_selftest_hbm_copy: bad argument");
+        return set_error(XPBD_E_INVALID, "xpbd_selftest_hbm_copy: bad argument");
     *gbytes_per_s = 0.0;
     XPBD_HIP_TRY(hipSetDevice(device));
     bytes &= ~(uint64_t)15;
@@ -1927,18 +1865,16 @@ int xpbd_selftest_hbm_copy(int32_t device, uint64_t bytes, uint32_t repeats, dou
     const float ms = best_ms;
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    src.release();
-    dst.release();
     if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "xpbd_selftest_hbm_copy: %s", hipGetErrorString(e));
+        return set_error(e == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "xpbd_selftest_hbm_copy: %s", hipGetErrorString(e));
     *gbytes_per_s = 2.0 * (double)bytes * repeats / ((double)ms * 1e-3) / 1e9; // bytes read + bytes written
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_selftest_gather(int32_t device, uint32_t records, uint32_t record_bytes, uint32_t read_bytes, uint32_t repeats, double *gbytes_per_s)
-{
+try {
     if (!gbytes_per_s || records < 256 || (records & (records - 1)) != 0 || repeats == 0 || read_bytes > record_bytes)
-        return fail(XPBD_E_INVALID, "xpbd_selftest_gather: records must be a power of two >= 256, read_bytes <= record_bytes");
+        return set_error(XPBD_E_INVALID, "xpbd_selftest_gather: records must be a power of two >= 256, read_bytes <= record_bytes");
     *gbytes_per_s = 0.0;
     XPBD_HIP_TRY(hipSetDevice(device));
     const size_t in_bytes = (size_t)records * record_bytes, out_bytes = (size_t)records * 8;
@@ -1962,20 +1898,18 @@ int xpbd_selftest_gather(int32_t device, uint32_t records, uint32_t record_bytes
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    in.release();
-    out.release();
     if (e == hipErrorInvalidValue)
-        return fail(XPBD_E_INVALID, "xpbd_selftest_gather: no kernel for %u bytes read of %u-byte records", read_bytes, record_bytes);
+        return set_error(XPBD_E_INVALID, "xpbd_selftest_gather: no kernel for %u bytes read of %u-byte records", read_bytes, record_bytes);
     if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "xpbd_selftest_gather: %s", hipGetErrorString(e));
+        return set_error(e == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "xpbd_selftest_gather: %s", hipGetErrorString(e));
     *gbytes_per_s = ((double)records * read_bytes + (double)out_bytes) / ((double)best_ms * 1e-3) / 1e9;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 int xpbd_selftest_field_streams(int32_t device, uint64_t bodies, uint32_t tile_major, uint32_t repeats, double *gbytes_per_s)
-{
+try {
     if (!gbytes_per_s || bodies < 64 || bodies > (1ull << 28) || repeats == 0)
-        return fail(XPBD_E_INVALID, "xpbd_selftest_field_streams: bad argument");
+        return set_error(XPBD_E_INVALID, "xpbd_selftest_field_streams: bad argument");
     *gbytes_per_s = 0.0;
     XPBD_HIP_TRY(hipSetDevice(device));
     bodies = (bodies + 63) / 64 * 64;
@@ -2000,12 +1934,10 @@ int xpbd_selftest_field_streams(int32_t device, uint64_t bodies, uint32_t tile_m
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    in.release();
-    out.release();
     if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "xpbd_selftest_field_streams: %s", hipGetErrorString(e));
+        return set_error(e == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "xpbd_selftest_field_streams: %s", hipGetErrorString(e));
     *gbytes_per_s = (double)(in_bytes + out_bytes) / ((double)best_ms * 1e-3) / 1e9;
     return XPBD_OK;
-}
+} XPBD_ABI_CATCH
 
 } // extern "C"

@@ -35,6 +35,9 @@
 
 #ifdef __cplusplus
 extern "C" {
+#define XPBD_NOEXCEPT noexcept /* the calls that cannot fail; every other call reports an exception as XPBD_E_OOM */
+#else
+#define XPBD_NOEXCEPT
 #endif
 
 /* 2: xpbd_multi_world_* (library-owned sharding), XPBD_E_HALO, edge_axes_separation, state history */
@@ -44,7 +47,7 @@ extern "C" {
 #define XPBD_OK                   0
 #define XPBD_E_INVALID          (-1)  /* bad argument / state */
 #define XPBD_E_HIP              (-2)  /* a HIP runtime call failed */
-#define XPBD_E_OOM              (-3)  /* host or device allocation failed */
+#define XPBD_E_OOM              (-3)  /* host or device allocation failed, or a host thread could not be started */
 #define XPBD_E_SINGULAR_INERTIA (-4)  /* mirrors the panic at src/rigid.rs:59 */
 #define XPBD_E_NO_DEVICE        (-5)  /* no usable gfx950 device */
 #define XPBD_E_CAPACITY         (-6)  /* caller buffer too small */
@@ -99,17 +102,17 @@ typedef struct xpbd_config {
 typedef struct xpbd_world xpbd_world;
 
 /* Library / error ---------------------------------------------------------- */
-uint32_t    xpbd_abi_version(void);
+uint32_t    xpbd_abi_version(void) XPBD_NOEXCEPT;
 /* Message for the last failing call on this thread; valid until the next call. */
-const char *xpbd_last_error(void);
+const char *xpbd_last_error(void) XPBD_NOEXCEPT;
 /* Fills cfg with defaults (device 0, fused mode, no flags). */
-void        xpbd_config_default(xpbd_config *cfg);
+void        xpbd_config_default(xpbd_config *cfg) XPBD_NOEXCEPT;
 /* Number of visible HIP devices, or a negative error code. */
 int         xpbd_device_count(void);
 
 /* World lifetime ----------------------------------------------------------- */
 int  xpbd_world_create(xpbd_world **out, const xpbd_config *cfg);
-void xpbd_world_destroy(xpbd_world *w);
+void xpbd_world_destroy(xpbd_world *w) XPBD_NOEXCEPT;
 
 /* Shapes: all shapes' vertices back to back (xyz triples) and a CSR offset
  * array of n_shapes+1 entries (in vertices).  Copied; caller keeps ownership.
@@ -121,7 +124,7 @@ int  xpbd_world_set_shapes(xpbd_world *w, const double *verts_xyz,
 int  xpbd_world_upload_bodies(xpbd_world *w, const xpbd_rigid *aos,
                               const uint32_t *shape_id, uint32_t n);
 int  xpbd_world_download_bodies(xpbd_world *w, xpbd_rigid *aos, uint32_t n);
-uint32_t xpbd_world_body_count(const xpbd_world *w);
+uint32_t xpbd_world_body_count(const xpbd_world *w) XPBD_NOEXCEPT;
 /* Rigid::frame() of every body (src/rigid.rs:75-80), the only thing the reference's renderer reads per
  * frame (src/app.rs:227-230): frames[7*i .. 7*i+6] = origin x y z, rotation s x y z.  56 B/body instead of 304. */
 int  xpbd_world_download_frames(xpbd_world *w, double *frames, uint32_t n);
@@ -143,7 +146,7 @@ int  xpbd_world_download_contact_masks(xpbd_world *w, uint32_t *masks,
 /* Stream interop: run on a caller-owned hipStream_t (NULL restores the
  * world's own stream).  The caller keeps the stream alive. */
 int  xpbd_world_set_stream(xpbd_world *w, void *hip_stream);
-void *xpbd_world_get_stream(const xpbd_world *w);
+void *xpbd_world_get_stream(const xpbd_world *w) XPBD_NOEXCEPT;
 int  xpbd_world_set_mode(xpbd_world *w, uint32_t mode);
 
 /* Literal single-body drop-in for solver::step (src/solver.rs:3): uploads,
@@ -406,7 +409,7 @@ int  xpbd_world_max_displacement2(xpbd_world *w, const uint32_t *dev_indices, ui
  * (upload, replan, the re-plans of a step) that fails before any shard has been re-packed leaves the previous plan and the
  * state in place; one that fails while the shards are being re-packed leaves nothing to go back to: every later call on that
  * world fails then, destroy it.  If a collective itself cannot be enqueued the communicator is aborted (ncclCommAbort: blocked peers return with an error) and
- * every later call on that world fails: destroy it.  Argument errors are returned before any collective: the ranks' hosts
+ * every later call on that world fails: destroy it.  So does a host allocation failure inside any xpbd_multi_world_* call.  Argument errors are returned before any collective: the ranks' hosts
  * pass consistent arguments.  A rank that never reaches xpbd_multi_world_create leaves its peers waiting inside RCCL's
  * bootstrap; only the host's launcher can detect that.
  * Threading: xpbd_multi_world_step waits once for the broadphase's pair counts (all shards' broadphases are enqueued before
@@ -448,10 +451,10 @@ typedef struct xpbd_multi_world xpbd_multi_world;
 int  xpbd_comm_unique_id(uint8_t id[XPBD_COMM_ID_BYTES]);
 /* The RCCL library the collectives are bound to at run time (a copy already loaded into the process is preferred over
  * loading a second one), or NULL if none could be loaded. */
-const char *xpbd_comm_library(void);
-void xpbd_multi_config_default(xpbd_multi_config *cfg);
+const char *xpbd_comm_library(void) XPBD_NOEXCEPT;
+void xpbd_multi_config_default(xpbd_multi_config *cfg) XPBD_NOEXCEPT;
 int  xpbd_multi_world_create(xpbd_multi_world **out, const xpbd_multi_config *cfg);   /* collective over all ranks (RCCL) */
-void xpbd_multi_world_destroy(xpbd_multi_world *mw);
+void xpbd_multi_world_destroy(xpbd_multi_world *mw) XPBD_NOEXCEPT;
 int  xpbd_multi_world_set_polytopes(xpbd_multi_world *mw, const xpbd_polytope *shapes, uint32_t n_shapes);
 int  xpbd_multi_world_set_max_depenetration_speed(xpbd_multi_world *mw, double speed);   /* as xpbd_world_set_max_depenetration_speed */
 /* bodies: the slice of the caller's bodies this process HANDS OVER = global indices [first_global, first_global + n_bodies) of
@@ -500,7 +503,7 @@ int  xpbd_multi_world_contact_stats(xpbd_multi_world *mw, uint64_t out[3]);     
  * ghost ids: the remote bodies it mirrors; ascending boundary ids: its own bodies that others mirror; far (optional): per
  * owned body in ascending index, 1 if no foreign body lies within two cells, so that it may travel halo_margin + half a cell
  * edge before the halos must be re-planned, the others halo_margin). */
-int64_t xpbd_halo_cell_key(const double centre[3], double cell_edge);
+int64_t xpbd_halo_cell_key(const double centre[3], double cell_edge) XPBD_NOEXCEPT;
 int  xpbd_halo_partition(const int64_t *cell_keys, uint32_t n_global, uint32_t n_ranks, uint8_t *owner);
 int  xpbd_halo_plan_owned(const int64_t *cell_keys, const uint8_t *owner, uint32_t n_global, uint32_t n_ranks, uint32_t rank,
                           const xpbd_joint *joints, uint32_t n_joints, uint32_t *ghosts, uint32_t *n_ghosts, uint32_t *boundary,
@@ -534,7 +537,7 @@ int  xpbd_halo_plan(const int64_t *cell_keys, uint32_t n_global, uint32_t n_rank
 int  xpbd_world_history_push(xpbd_world *w, uint32_t *index_out);
 int  xpbd_world_history_restore(xpbd_world *w, uint32_t index);
 int  xpbd_world_history_truncate(xpbd_world *w, uint32_t length);
-uint32_t xpbd_world_history_length(const xpbd_world *w);
+uint32_t xpbd_world_history_length(const xpbd_world *w) XPBD_NOEXCEPT;
 
 /* ---------------------------------------------------------------------------
  * Scene queries (EXTENSION): the closest body along each of a batch of rays, at the bodies' current poses.  NOT in the

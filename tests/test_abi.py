@@ -1,8 +1,11 @@
 """The C-ABI library loads without a GPU, exports every symbol include/xpbd.h declares,
 and fails loudly (never silently falls back) when there is no device."""
 import ctypes as C
+import glob
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -34,6 +37,60 @@ def test_rust_binding_text_declares_every_symbol():
     text = open(os.path.join(ROOT, "constraint_solver_amd", "ffi", "xpbd_ffi.rs")).read()
     declared = set(re.findall(r"pub fn (xpbd_[a-z_0-9]+)\(", text))
     assert declared == set(header_functions())
+
+
+def test_no_entry_point_lets_an_exception_out():
+    """Every function include/xpbd.h declares is defined noexcept, or as a function-try-block closed by the ABI's handler
+    (csrc/xpbd_internal.h: XPBD_ABI_CATCH; csrc/xpbd_multi.cpp: XPBD_MULTI_ABI_CATCH)."""
+    src = "".join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "constraint_solver_amd", "csrc", "*.cpp"))))
+    for name in header_functions():
+        m = re.search(r"^[A-Za-z_][\w *]*\b%s\(([^;{}]*?)\)( noexcept)?\s*(try )?\{" % name, src, re.M)
+        assert m, "no definition of %s" % name
+        if m.group(2):
+            continue
+        assert m.group(3), "%s is neither noexcept nor a function-try-block" % name
+        end = src.index("\n}", m.end())
+        assert re.match(r"\n\} XPBD_(MULTI_)?ABI_CATCH\n", src[end:]), "%s does not end in the ABI's handler" % name
+
+
+# A child process that runs out of HOST memory inside the host-only planner: the library must report XPBD_E_OOM instead of
+# letting std::bad_alloc (or std::system_error from a thread that cannot start) terminate the process.  Nothing touches HIP.
+# The child loads the library this suite tests (capi.hip_lib's choice, XPBD_HIP_LIB included) with the environment as it is.
+_HOST_OOM_CHILD = r"""
+import ctypes as C, resource, sys
+import numpy as np
+lib = C.CDLL(sys.argv[1])
+lib.xpbd_last_error.restype = C.c_char_p
+n, bias = 1 << 23, 1 << 20
+g = np.arange(n, dtype=np.int64)
+keys = np.ascontiguousarray(((g // 32768 + bias) << 42) | ((g // 128 % 256 + bias) << 21) | (g % 128 + bias))
+owner = np.ascontiguousarray((g >= n // 2).astype(np.uint8))
+counts = (C.c_uint32 * 2)()
+vm = int(open("/proc/self/statm").read().split()[0]) * resource.getpagesize()
+resource.setrlimit(resource.RLIMIT_AS, (vm + (64 << 20), resource.getrlimit(resource.RLIMIT_AS)[1]))
+rc = lib.xpbd_halo_partition(C.c_void_p(keys.ctypes.data), n, 2, C.c_void_p(owner.ctypes.data))
+print("partition", rc, lib.xpbd_last_error().decode())
+rc = lib.xpbd_halo_plan_owned(C.c_void_p(keys.ctypes.data), C.c_void_p(owner.ctypes.data), n, 2, 0, None, 0, None, C.byref(counts, 0),
+                              None, C.byref(counts, 4), None, 0)
+print("plan_owned", rc, lib.xpbd_last_error().decode())
+"""
+
+
+def _sanitizer_runtime_loaded():
+    process = C.CDLL(None)
+    return any(hasattr(process, init) for init in ("__asan_init", "__hwasan_init", "__tsan_init"))
+
+
+@pytest.mark.skipif(_sanitizer_runtime_loaded(), reason="a sanitizer's allocator aborts under RLIMIT_AS instead of failing the allocation")
+def test_host_out_of_memory_is_an_error_not_an_abort():
+    lib = os.environ.get("XPBD_HIP_LIB") or os.path.join(capi.LIB_DIR, "libxpbd_hip.so")
+    p = subprocess.run([sys.executable, "-c", _HOST_OOM_CHILD, lib], env=dict(os.environ, XPBD_PLAN_THREADS="8"),
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout
+    lines = dict(line.split(" ", 1) for line in p.stdout.splitlines())
+    for call, name in (("partition", "xpbd_halo_partition"), ("plan_owned", "xpbd_halo_plan_owned")):
+        rc, message = lines[call].split(" ", 1)
+        assert int(rc) == capi.E_OOM and message.startswith(name + ": "), p.stdout
 
 
 def test_struct_layouts_match_header():

@@ -112,6 +112,30 @@ def test_sharded_pile_with_joints_across_shards_and_gjk():
         assert bits_equal(got, one)
 
 
+def test_a_bad_joint_is_refused_before_any_collective_and_the_world_stays_usable():
+    """xpbd_multi_world_upload checks the joints as xpbd_world_set_joints does, before any device work: a hinge whose axis is
+    not a unit vector is XPBD_E_INVALID, and the next (valid) upload runs as on a fresh world."""
+    kind, n, substeps, frames = capi.SCENE_BOXES_DROP, 64, 4, 3
+    bodies, sid = line_scene(capi, kind, n, 5, 1.3)
+    joints = chain_joints(capi, n, limit=n // 2)
+    centre = bodies[:, 31:34] + bodies[:, 28:31]                        # at rest at t = 0 (anchors are the centres of mass)
+    joints["distance"] = np.linalg.norm(centre[joints["body_b"]] - centre[joints["body_a"]], axis=1)
+    bad = joints.copy()
+    bad["kind"][0], bad["distance"][0] = capi.JOINT_HINGE, 0.0
+    bad["axis_a"][0], bad["axis_b"][0] = [0.0, 2.0, 0.0], [0.0, 1.0, 0.0]
+    with capi.MultiWorld(2, devices=[0, 0], transport=capi.TRANSPORT_LOCAL, halo_margin=0.75, auto_replan=True) as mw:
+        mw.set_polytopes(capi.scene_polytopes(kind))
+        with pytest.raises(capi.XpbdError) as e:
+            mw.upload(bodies, sid, 0, n, bad)
+        assert e.value.code == capi.E_INVALID and "xpbd_multi_world_upload: hinge 0 needs unit axes" in str(e.value)
+        mw.upload(bodies, sid, 0, n, joints)
+        for _ in range(frames):
+            mw.step(DT, substeps)
+        got = mw.download()
+    one, _ = single(bodies, sid, kind, frames, substeps, joints=joints)
+    assert not np.isnan(one).any() and bits_equal(got, one)
+
+
 def boundary_body(kind, bodies, sid, n_ranks, margin):
     """Index of a body the plan puts next to a shard boundary (travel allowance = halo_margin, not the larger one of a
     body deep inside its slab)."""
