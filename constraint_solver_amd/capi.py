@@ -54,6 +54,9 @@ ABI_SYMBOLS = [
     "xpbd_world_raycast", "xpbd_world_raycast_device", "xpbd_multi_world_raycast",
     "xpbd_world_set_collision_filters", "xpbd_multi_world_set_collision_filters", "xpbd_world_raycast_masked",
     "xpbd_world_raycast_masked_device", "xpbd_multi_world_raycast_masked",
+    "xpbd_world_set_contact_report", "xpbd_world_contact_report_counts", "xpbd_world_download_pair_contacts",
+    "xpbd_world_download_contact_events", "xpbd_multi_world_set_contact_report", "xpbd_multi_world_contact_report_counts",
+    "xpbd_multi_world_download_pair_contacts", "xpbd_multi_world_download_contact_events",
 ]
 
 
@@ -132,6 +135,14 @@ def rays(origins, directions, max_distance=np.inf, ignore=None):
     out["origin"], out["direction"], out["max_distance"] = o, d, max_distance
     out["ignore_body"] = NO_HIT if ignore is None else ignore
     return out
+
+
+# Contact reports (EXTENSION): xpbd_pair_contact (64 bytes), xpbd_contact_point (48), xpbd_contact_event (12)
+PAIR_CONTACT_DTYPE = np.dtype([("body_a", "<u4"), ("body_b", "<u4"), ("substeps", "<u4"), ("n_points", "<u4"), ("feature", "<u4"),
+                               ("first_point", "<u4"), ("reserved", "<u4", (2,)), ("normal", "<f8", (3,)), ("depth", "<f8")])
+CONTACT_POINT_DTYPE = np.dtype([("p_ref", "<f8", (3,)), ("p_inc", "<f8", (3,))])
+CONTACT_EVENT_DTYPE = np.dtype([("body_a", "<u4"), ("body_b", "<u4"), ("kind", "<u4")])
+CONTACT_BEGIN, CONTACT_END = 0, 1
 
 
 MANIFOLD_DTYPE = np.dtype([("n_points", "<u4"), ("feature", "<u4"), ("index_a", "<u4"), ("index_b", "<u4"),
@@ -245,6 +256,17 @@ def hip_lib():
             L.xpbd_world_raycast_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
             L.xpbd_world_raycast_masked_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
             L.xpbd_multi_world_raycast_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            L.xpbd_world_set_contact_report.argtypes = [C.c_void_p, C.c_uint32]
+            L.xpbd_world_contact_report_counts.argtypes = [C.c_void_p, _u32p]
+            L.xpbd_world_download_pair_contacts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _u32p, _u32p]
+            L.xpbd_world_download_contact_events.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, _u32p]
+            L.xpbd_multi_world_set_contact_report.argtypes = [C.c_void_p, C.c_uint32]
+            L.xpbd_multi_world_contact_report_counts.argtypes = [C.c_void_p, _u32p]
+            L.xpbd_multi_world_download_pair_contacts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _u32p, _u32p]
+            L.xpbd_multi_world_download_contact_events.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, _u32p]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -487,6 +509,47 @@ class World:
     def set_mode(self, mode):
         _check(hip_lib().xpbd_world_set_mode(self._h, mode))
 
+    # contact reports (include/xpbd.h, "Contact REPORTS"): the touching pairs of the current frame, their last manifolds and the
+    # begin / end events against the previous frame
+    def set_contact_report(self, enable):
+        _check(hip_lib().xpbd_world_set_contact_report(self._h, 1 if enable else 0))
+
+    def contact_report_counts(self):
+        """(pairs, points, begins, ends) of the current frame's report."""
+        return _report_counts(hip_lib().xpbd_world_contact_report_counts, self._h)
+
+    def pair_contacts(self, points=True):
+        """(PAIR_CONTACT_DTYPE records, CONTACT_POINT_DTYPE records or None) of the current frame."""
+        return _pair_contacts(hip_lib().xpbd_world_contact_report_counts, hip_lib().xpbd_world_download_pair_contacts, self._h, points)
+
+    def contact_events(self):
+        """CONTACT_EVENT_DTYPE records: BEGINs then ENDs, each in (body_a, body_b) order."""
+        return _contact_events(hip_lib().xpbd_world_contact_report_counts, hip_lib().xpbd_world_download_contact_events, self._h)
+
+
+def _report_counts(counts_fn, h):
+    out = (C.c_uint32 * 4)()
+    _check(counts_fn(h, out))
+    return tuple(int(v) for v in out)
+
+
+def _pair_contacts(counts_fn, download_fn, h, points):
+    n_pairs, n_points, _, _ = _report_counts(counts_fn, h)
+    pairs = np.zeros(n_pairs, dtype=PAIR_CONTACT_DTYPE)
+    pts = np.zeros(n_points, dtype=CONTACT_POINT_DTYPE) if points else None
+    got_pairs, got_points = C.c_uint32(0), C.c_uint32(0)
+    _check(download_fn(h, pairs.ctypes.data if n_pairs else None, n_pairs, pts.ctypes.data if points and n_points else None,
+                       n_points if points else 0, C.byref(got_pairs), C.byref(got_points)))
+    return pairs, pts
+
+
+def _contact_events(counts_fn, download_fn, h):
+    _, _, begins, ends = _report_counts(counts_fn, h)
+    out = np.zeros(begins + ends, dtype=CONTACT_EVENT_DTYPE)
+    n = C.c_uint32(0)
+    _check(download_fn(h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+    return out
+
 
 def _filters(filters):
     """COLLISION_FILTER_DTYPE records from records or an (n, 2) array of (group, mask); None stays None."""
@@ -657,6 +720,21 @@ class MultiWorld:
         out = (C.c_uint64 * 3)()
         _check(hip_lib().xpbd_multi_world_contact_stats(self._h, out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    # contact reports of the whole sharded world, global body indices (include/xpbd.h, "Contact REPORTS"); gathered by step()
+    def set_contact_report(self, enable):
+        _check(hip_lib().xpbd_multi_world_set_contact_report(self._h, 1 if enable else 0))
+
+    def contact_report_counts(self):
+        return _report_counts(hip_lib().xpbd_multi_world_contact_report_counts, self._h)
+
+    def pair_contacts(self, points=True):
+        L = hip_lib()
+        return _pair_contacts(L.xpbd_multi_world_contact_report_counts, L.xpbd_multi_world_download_pair_contacts, self._h, points)
+
+    def contact_events(self):
+        L = hip_lib()
+        return _contact_events(L.xpbd_multi_world_contact_report_counts, L.xpbd_multi_world_download_contact_events, self._h)
 
 
 def halo_cell_key(centre, edge):

@@ -4,6 +4,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <utility>
+#include <vector>
 
 #include <hip/hip_runtime_api.h>
 
@@ -99,6 +100,8 @@ struct xpbd_joint;
 struct xpbd_joint_limit;
 struct xpbd_ray;
 struct xpbd_ray_hit;
+struct xpbd_pair_contact;
+struct xpbd_contact_point;
 
 namespace xpbd {
 // frame:   halo_frame_begin_enqueue; halo_frame_begin_collect; substeps x { halo_substep_boundary; <all-gather send -> recv,
@@ -140,6 +143,11 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
                     bool masked, uint32_t mask);
 int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id,
                  bool masked, uint32_t mask);
+// The current frame's contact report of a shard of the multi-GPU world (include/xpbd.h, "Contact REPORTS"): only the pairs whose
+// lower body has dev_owned[slot] != 0, bodies named by dev_global_id[slot] (device arrays of the world's body count; global ids
+// ascending with the slot).  Waits.  A world without bodies reports nothing.
+int report_shard(xpbd_world *w, const uint8_t *dev_owned, const uint32_t *dev_global_id, std::vector<xpbd_pair_contact> &pairs,
+                 std::vector<xpbd_contact_point> &points) noexcept;
 // The argument checks of xpbd_world_set_joints against a world of n_bodies bodies / of xpbd_world_set_joint_limits against a
 // joint list (XPBD_E_INVALID with a message naming `who`).
 int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies);

@@ -608,6 +608,7 @@ struct Shard {
     std::vector<uint32_t> joint_ids; // global ids (ascending) of the joints the shard's world has: local joint q = joint_ids[q]
     DeviceBuffer boundary_slots, ghost_slots, ghost_rows, owned_slots, skip_flags, disp_scale, send, recv, snapshot, disp, disp_all, stage_send, stage_recv;
     DeviceBuffer query_ids; // xpbd_multi_world_raycast: global id of every local slot, XPBD_NO_HIT for the ghosts
+    DeviceBuffer report_ids, report_owned; // contact reports: global id of every local slot; 1 for the owned slots, 0 for the ghosts
     double *disp_host = nullptr;   // pinned, n_ranks x {largest squared fraction of an allowance used, status}
     double *status_host = nullptr; // pinned, this process's status of the frame
     const xpbd::RcclApi *rccl = nullptr; // destroys `comm`
@@ -724,6 +725,14 @@ struct xpbd_multi_world {
     uint64_t full_plans = 0, light_plans = 0;
     double last_displacement = 0.0; // the largest fraction of its travel allowance any body had used at the last check, times halo_margin
     Workers *workers = nullptr;     // one enqueueing thread per local shard (n_local > 1), started by the first step
+    // contact reports (xpbd_multi_world_set_contact_report): the whole world's report of the last frame, gathered on every rank
+    // when the frame has been accepted (before a re-plan repacks the shards), and the touching pairs of the frame before it
+    bool report_on = false, report_valid = false;
+    std::vector<xpbd_pair_contact> report_pairs;
+    std::vector<xpbd_contact_point> report_points;
+    std::vector<xpbd_contact_event> report_events;
+    std::vector<uint64_t> report_prev; // keys (a << 32 | b) of the previous frame's touching pairs; empty: S_prev is empty
+    uint32_t report_begins = 0;
     ~xpbd_multi_world(); // stops the workers (then the shards go)
     bool all_local() const { return shards.size() == n_ranks; }
     bool shortcut() const { return all_local() && !(flags & XPBD_MULTI_PLAN_THROUGH_DEVICE); } // plan-time gathers are memcpys
@@ -2012,6 +2021,145 @@ int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, u
     return XPBD_OK;
 }
 
+// ---- contact reports ----------------------------------------------------------------------------------------------------
+void report_clear(xpbd_multi_world *mw)
+{
+    mw->report_valid = false;
+    mw->report_pairs.clear();
+    mw->report_points.clear();
+    mw->report_events.clear();
+    mw->report_prev.clear();
+    mw->report_begins = 0;
+}
+
+// One shard's part of the frame's report: the pairs whose lower body it owns (the owner holds the other body as well, owned
+// or as a ghost), under global ids.  local_ids are ascending, so the shard's list is sorted by global key.
+int shard_report(Shard &s, std::vector<xpbd_pair_contact> &pairs, std::vector<xpbd_contact_point> &points)
+{
+    XPBD_TRY(bind(s));
+    if (xpbd_world_body_count(s.world) != s.local_ids.size())
+        return set_error(XPBD_E_INVALID, "contact report: shard %u holds %u bodies, its plan %zu", s.rank, xpbd_world_body_count(s.world),
+                         s.local_ids.size());
+    std::vector<uint8_t> owned(s.local_ids.size(), 1);
+    size_t g = 0;
+    for (size_t q = 0; q < s.local_ids.size(); ++q) { // local_ids and ghosts are both ascending
+        while (g < s.ghosts.size() && s.ghosts[g] < s.local_ids[q])
+            ++g;
+        if (g < s.ghosts.size() && s.ghosts[g] == s.local_ids[q])
+            owned[q] = 0;
+    }
+    XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
+    XPBD_TRY(upload_vector(s.report_ids, s.local_ids, s.stream));
+    XPBD_TRY(upload_vector(s.report_owned, owned, s.stream));
+    return xpbd::report_shard(s.world, s.report_owned.as<uint8_t>(), s.report_ids.as<uint32_t>(), pairs, points);
+}
+
+// Collective, at the end of an accepted frame: every rank gathers every shard's list, merges them by key (the lists are
+// disjoint: a pair belongs to the owner of its lower body) and derives the events from the merged lists, so that owners
+// changing at a re-plan do not matter.  Same records as one world over the same bodies.
+int capture_report(xpbd_multi_world *mw)
+{
+    const size_t nl = mw->shards.size();
+    LocalStatus st;
+    std::vector<std::vector<xpbd_pair_contact>> pairs(nl);
+    std::vector<std::vector<xpbd_contact_point>> points(nl);
+    for (size_t k = 0; k < nl; ++k)
+        if (st.ok())
+            st.keep(shard_report(mw->shards[k], pairs[k], points[k]));
+    struct Counts {
+        uint32_t pairs, points;
+    };
+    std::vector<Counts> mine(nl);
+    std::vector<const void *> send(nl);
+    for (size_t k = 0; k < nl; ++k) {
+        mine[k] = Counts{(uint32_t)pairs[k].size(), (uint32_t)points[k].size()};
+        send[k] = &mine[k];
+    }
+    std::vector<uint8_t> gathered;
+    XPBD_TRY(all_gather_host(mw, send, sizeof(Counts), gathered, st));
+    const uint32_t w = mw->n_ranks;
+    std::vector<Counts> counts(w);
+    std::memcpy(counts.data(), gathered.data(), (size_t)w * sizeof(Counts));
+    uint32_t cap = 1, cap_points = 1;
+    for (const Counts &c : counts) {
+        cap = std::max(cap, c.pairs);
+        cap_points = std::max(cap_points, c.points);
+    }
+    for (size_t k = 0; k < nl; ++k) {
+        pairs[k].resize(cap);
+        points[k].resize(cap_points);
+        send[k] = pairs[k].data();
+    }
+    std::vector<uint8_t> all_pairs, all_points;
+    XPBD_TRY(all_gather_host(mw, send, (size_t)cap * sizeof(xpbd_pair_contact), all_pairs, st));
+    for (size_t k = 0; k < nl; ++k)
+        send[k] = points[k].data();
+    XPBD_TRY(all_gather_host(mw, send, (size_t)cap_points * sizeof(xpbd_contact_point), all_points, st));
+    // merge: (key, rank, row) in key order
+    struct Item {
+        uint64_t key;
+        uint32_t rank, row;
+    };
+    std::vector<Item> items;
+    for (uint32_t r = 0; r < w; ++r)
+        for (uint32_t i = 0; i < counts[r].pairs; ++i) {
+            xpbd_pair_contact c;
+            std::memcpy(&c, all_pairs.data() + ((size_t)r * cap + i) * sizeof c, sizeof c);
+            items.push_back(Item{(uint64_t)c.body_a << 32 | c.body_b, r, i});
+        }
+    std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.key < b.key; });
+    std::vector<xpbd_pair_contact> merged(items.size());
+    std::vector<xpbd_contact_point> merged_points;
+    std::vector<uint64_t> keys(items.size());
+    for (size_t i = 0; i < items.size(); ++i) {
+        xpbd_pair_contact c;
+        std::memcpy(&c, all_pairs.data() + ((size_t)items[i].rank * cap + items[i].row) * sizeof c, sizeof c);
+        const uint32_t from = c.first_point;
+        c.first_point = (uint32_t)merged_points.size();
+        for (uint32_t q = 0; q < c.n_points; ++q) {
+            xpbd_contact_point p;
+            std::memcpy(&p, all_points.data() + ((size_t)items[i].rank * cap_points + from + q) * sizeof p, sizeof p);
+            merged_points.push_back(p);
+        }
+        merged[i] = c;
+        keys[i] = items[i].key;
+    }
+    // events: BEGINs (keys - prev), then ENDs (prev - keys), each in key order
+    std::vector<xpbd_contact_event> events, ends;
+    size_t a = 0, b = 0;
+    const std::vector<uint64_t> &prev = mw->report_prev;
+    while (a < keys.size() || b < prev.size()) {
+        if (b == prev.size() || (a < keys.size() && keys[a] < prev[b])) {
+            events.push_back(xpbd_contact_event{(uint32_t)(keys[a] >> 32), (uint32_t)keys[a], XPBD_CONTACT_BEGIN});
+            ++a;
+        } else if (a == keys.size() || prev[b] < keys[a]) {
+            ends.push_back(xpbd_contact_event{(uint32_t)(prev[b] >> 32), (uint32_t)prev[b], XPBD_CONTACT_END});
+            ++b;
+        } else {
+            ++a, ++b;
+        }
+    }
+    mw->report_begins = (uint32_t)events.size();
+    events.insert(events.end(), ends.begin(), ends.end());
+    mw->report_pairs.swap(merged);
+    mw->report_points.swap(merged_points);
+    mw->report_events.swap(events);
+    mw->report_prev.swap(keys);
+    mw->report_valid = true;
+    return XPBD_OK;
+}
+
+int check_report(const xpbd_multi_world *mw, const char *who)
+{
+    XPBD_TRY(check_usable(mw, who));
+    if (!mw->report_on)
+        return set_error(XPBD_E_INVALID, "%s: contact reports are off (xpbd_multi_world_set_contact_report)", who);
+    if (!mw->report_valid)
+        return set_error(XPBD_E_INVALID, "%s: no report: no frame has been stepped since the reports were enabled, the bodies uploaded "
+                                         "or a step failed", who);
+    return XPBD_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -2258,6 +2406,7 @@ try {
     mw->filters.clear(); // filters name bodies by index
     mw->filter_flags = 0;
     mw->planned = false;
+    report_clear(mw);
     mw->cuts_valid = false; // the first plan is a full one
     mw->check_plans = std::getenv("XPBD_MULTI_CHECK_PLANS") != nullptr;
     // the joints at every body (ascending joint index per body): the plans walk the joints of a rank's own bodies only
@@ -2324,6 +2473,16 @@ try {
 int xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps)
 try {
     XPBD_TRY(check_usable(mw, "xpbd_multi_world_step"));
+    // a step that does not finish with a gathered report leaves none, and an empty S_prev for the next one
+    struct ReportGuard {
+        xpbd_multi_world *mw;
+        ~ReportGuard()
+        {
+            if (!mw->report_valid)
+                report_clear(mw);
+        }
+    } report_guard{mw};
+    mw->report_valid = false;
     if (substeps == 0)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_step: substeps must be > 0");
     if (!mw->planned)
@@ -2336,8 +2495,11 @@ try {
     for (int attempt = 0;; ++attempt) {
         LocalStatus st;
         XPBD_TRY(enqueue_frame(mw, dt, substeps, st));
-        if (mw->n_ranks == 1)
-            return st.ok() ? XPBD_OK : st.report(); // no ghosts, nothing to validate: asynchronous after the broadphase
+        if (mw->n_ranks == 1) { // no ghosts, nothing to validate: asynchronous after the broadphase (unless reports are gathered)
+            if (!st.ok())
+                return st.report();
+            return mw->report_on ? capture_report(mw) : XPBD_OK;
+        }
         double moved = 0.0;
         if (int rc = finish_frame(mw, st, &moved)) {
             if (mw->broken)
@@ -2350,6 +2512,8 @@ try {
         const double gain = std::max(0.0, moved - mw->last_displacement); // what this frame used up of the allowance
         mw->last_displacement = moved;
         if (moved <= mw->margin) {
+            if (mw->report_on) // before a re-plan repacks the shards
+                XPBD_TRY(capture_report(mw));
             // pre-emptive: another frame like this one (and half as much again) would outrun the allowance, so re-plan (and
             // re-balance) from the state just reached.  A wrong guess costs a frame: it is undone and run again below.
             if ((mw->flags & XPBD_MULTI_AUTO_REPLAN) && moved + 1.5 * gain > mw->margin)
@@ -2380,6 +2544,64 @@ int xpbd_multi_world_raycast_masked(xpbd_multi_world *mw, const xpbd_ray *rays, 
                                     xpbd_ray_hit *hits)
 try {
     return multi_raycast("xpbd_multi_world_raycast_masked", mw, rays, n_rays, flags, true, mask, hits);
+} XPBD_MULTI_ABI_CATCH
+
+int xpbd_multi_world_set_contact_report(xpbd_multi_world *mw, uint32_t enable)
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_set_contact_report"));
+    if (enable > 1u)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_contact_report: enable must be 0 or 1, not %u", enable);
+    report_clear(mw);
+    mw->report_on = false;
+    for (Shard &s : mw->shards) // the shards count their touching substeps; their lists are gathered by the step
+        XPBD_TRY(xpbd_world_set_contact_report(s.world, enable));
+    mw->report_on = enable != 0;
+    return XPBD_OK;
+} XPBD_MULTI_ABI_CATCH
+
+int xpbd_multi_world_contact_report_counts(xpbd_multi_world *mw, uint32_t out[4])
+try {
+    if (mw && !out)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_contact_report_counts: NULL argument");
+    XPBD_TRY(check_report(mw, "xpbd_multi_world_contact_report_counts"));
+    out[0] = (uint32_t)mw->report_pairs.size();
+    out[1] = (uint32_t)mw->report_points.size();
+    out[2] = mw->report_begins;
+    out[3] = (uint32_t)mw->report_events.size() - mw->report_begins;
+    return XPBD_OK;
+} XPBD_MULTI_ABI_CATCH
+
+int xpbd_multi_world_download_pair_contacts(xpbd_multi_world *mw, xpbd_pair_contact *pairs, uint32_t pair_cap, xpbd_contact_point *points,
+                                            uint32_t point_cap, uint32_t *n_pairs, uint32_t *n_points)
+try {
+    if (mw && (!n_pairs || !n_points || (!pairs && pair_cap) || (!points && point_cap)))
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_download_pair_contacts: NULL argument");
+    XPBD_TRY(check_report(mw, "xpbd_multi_world_download_pair_contacts"));
+    const uint32_t k = (uint32_t)mw->report_pairs.size(), total_points = (uint32_t)mw->report_points.size();
+    *n_pairs = k;
+    *n_points = total_points;
+    if (pair_cap)
+        std::memcpy(pairs, mw->report_pairs.data(), (size_t)std::min(k, pair_cap) * sizeof(xpbd_pair_contact));
+    if (points && point_cap)
+        std::memcpy(points, mw->report_points.data(), (size_t)std::min(total_points, point_cap) * sizeof(xpbd_contact_point));
+    if (k > pair_cap || (points && total_points > point_cap))
+        return set_error(XPBD_E_CAPACITY, "xpbd_multi_world_download_pair_contacts: %u pairs, capacity %u; %u points, capacity %u", k, pair_cap,
+                         total_points, point_cap);
+    return XPBD_OK;
+} XPBD_MULTI_ABI_CATCH
+
+int xpbd_multi_world_download_contact_events(xpbd_multi_world *mw, xpbd_contact_event *out, uint32_t cap, uint32_t *n_out)
+try {
+    if (mw && (!n_out || (!out && cap)))
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_download_contact_events: NULL argument");
+    XPBD_TRY(check_report(mw, "xpbd_multi_world_download_contact_events"));
+    const uint32_t total = (uint32_t)mw->report_events.size();
+    *n_out = total;
+    if (cap)
+        std::memcpy(out, mw->report_events.data(), (size_t)std::min(total, cap) * sizeof(xpbd_contact_event));
+    if (total > cap)
+        return set_error(XPBD_E_CAPACITY, "xpbd_multi_world_download_contact_events: %u events, capacity %u", total, cap);
+    return XPBD_OK;
 } XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_synchronize(xpbd_multi_world *mw)

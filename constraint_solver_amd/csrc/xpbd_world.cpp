@@ -22,6 +22,7 @@
 #include "xpbd_gjk.h"
 #include "xpbd_pairs.h"
 #include "xpbd_query.h"
+#include "xpbd_report.h"
 
 namespace {
 
@@ -155,6 +156,20 @@ struct xpbd_world {
     unsigned long long stats_touching_seen = 0, stats_pair_substeps = 0, stats_pair_substeps_seen = 0;
     DeviceBuffer gjk_counters, gjk_pairs_scratch;   // hit list of the two-kernel GJK/EPA narrowphase (xpbd_gjk.h)
     xpbd::GjkScratch gjk_scratch{nullptr, nullptr, 0, nullptr, nullptr};
+    // contact reports (xpbd_world_set_contact_report; xpbd_report.h).  rep_keys[report_cur] holds this frame's touching
+    // pairs once compacted, rep_keys[report_cur ^ 1] those of the previous frame (S_prev, when report_prev_valid).
+    bool report_on = false;
+    bool report_frame = false;      // the current pair list counts its touching substeps in rep_touch (zeroed by its broadphase)
+    bool report_keys_ready = false; // rep_keys[report_cur] is up to date with the substeps run (its count on its way to rep_host)
+    bool report_ready = false;      // report_counts and the scans behind them are up to date
+    bool report_prev_valid = false;
+    uint32_t report_substeps = 0, report_cur = 0;
+    uint32_t report_counts[4] = {0, 0, 0, 0}; // pairs, points, begins, ends
+    uint32_t *rep_host = nullptr;   // hipHostMalloc: [0..1] key counts of rep_keys[0..1], [2..4] point / BEGIN / event totals
+    DeviceBuffer rep_touch, rep_flag, rep_sel, rep_npts, rep_keys[2], rep_scan, rep_ev_flag, rep_pairs, rep_points, rep_events;
+    // a shard of the multi-GPU world, for the duration of xpbd::report_shard only: owned slots and global ids (ReportFrame)
+    const uint8_t *rep_map_owned = nullptr;
+    const uint32_t *rep_map_ids = nullptr;
     // frame_set: which of the two frame sets the substep reads (always 0 outside step_contacts)
     xpbd::ContactBuffers contact_buffers(uint32_t frame_set = 0) const
     {
@@ -215,6 +230,8 @@ struct xpbd_world {
             (void)hipHostFree(bp_totals);
         if (bp_event)
             (void)hipEventDestroy(bp_event);
+        if (rep_host)
+            (void)hipHostFree(rep_host);
         if (own_stream)
             (void)hipStreamDestroy(own_stream);
     }
@@ -252,11 +269,111 @@ int ensure_gjk_scratch(xpbd_world *w, uint32_t n_pairs)
     return XPBD_OK;
 }
 
+// ---- contact reports (xpbd_world_set_contact_report; semantics in include/xpbd.h) ---------------------------------------------
+// Nothing starts a frame, no touch count, no scan runs while reporting is off.
+void report_reset(xpbd_world *w)
+{
+    w->report_frame = w->report_keys_ready = w->report_ready = w->report_prev_valid = false;
+    w->report_substeps = 0;
+}
+
+xpbd::ReportFrame report_frame_of(const xpbd_world *w)
+{
+    return xpbd::ReportFrame{w->cb_pairs.as<uint32_t>(), w->cb_pair_codes.as<uint8_t>(), w->cb_manifolds.as<xpbd::ContactManifold>(),
+                             w->rep_touch.as<uint32_t>(), w->n_pairs, w->rep_map_owned, w->rep_map_ids};
+}
+
+// This frame's touching pairs -> rep_keys[report_cur]; their count travels to rep_host[report_cur].  Enqueued only.
+int report_compact_keys(xpbd_world *w)
+{
+    const uint32_t cur = w->report_cur;
+    XPBD_HIP_TRY(xpbd::launch_report_keys(report_frame_of(w), w->rep_flag.as<uint32_t>(), w->rep_scan.as<uint32_t>(),
+                                          w->rep_keys[cur].as<unsigned long long>(), w->rep_sel.as<uint32_t>(), w->rep_npts.as<uint32_t>(),
+                                          w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(&w->rep_host[cur], w->rep_flag.as<uint32_t>() + w->n_pairs, 4, hipMemcpyDeviceToHost, w->stream));
+    w->report_keys_ready = true;
+    return XPBD_OK;
+}
+
+// Before a broadphase replaces the pair list: the frame's touching set becomes the next frame's S_prev (a frame without a
+// substep touched nothing).  The keys must be compacted now -- the pairs, codes and counters they come from are rebuilt.
+int report_frame_end(xpbd_world *w)
+{
+    if (!w->report_on)
+        return XPBD_OK;
+    if (w->report_frame && w->report_substeps) {
+        if (!w->report_keys_ready)
+            XPBD_TRY(report_compact_keys(w));
+        w->report_prev_valid = true;
+        w->report_cur ^= 1u;
+    } else {
+        w->report_prev_valid = false; // a frame without a substep touched nothing; and after an enable, upload, restore or failure S_prev is empty
+    }
+    w->report_frame = w->report_keys_ready = w->report_ready = false;
+    w->report_substeps = 0;
+    return XPBD_OK;
+}
+
+// After the broadphase has sized the pair list: the counters of the new frame start at zero.
+int report_frame_begin(xpbd_world *w)
+{
+    if (!w->report_on)
+        return XPBD_OK;
+    const size_t np = w->n_pairs ? w->n_pairs : 1;
+    XPBD_HIP_TRY(w->rep_touch.reserve(np * 4));
+    XPBD_HIP_TRY(w->rep_flag.reserve((np + 1) * 4));
+    XPBD_HIP_TRY(w->rep_sel.reserve(np * 4));
+    XPBD_HIP_TRY(w->rep_npts.reserve((np + 1) * 4));
+    XPBD_HIP_TRY(w->rep_keys[w->report_cur].reserve(np * 8)); // (the other one holds S_prev)
+    XPBD_HIP_TRY(w->rep_scan.reserve((np / 1024 + 8) * 4));
+    XPBD_HIP_TRY(hipMemsetAsync(w->rep_touch.ptr, 0, np * 4, w->stream));
+    w->report_frame = true;
+    w->report_keys_ready = w->report_ready = false;
+    w->report_substeps = 0;
+    return XPBD_OK;
+}
+
+// Everything a count or download needs of the current frame: keys, point offsets, event flags and their totals.  Waits.
+int report_prepare(xpbd_world *w, const char *who)
+{
+    if (!w->report_on)
+        return set_error(XPBD_E_INVALID, "%s: contact reports are off (xpbd_world_set_contact_report)", who);
+    if (!w->report_frame || !w->report_substeps)
+        return set_error(XPBD_E_INVALID, "%s: no report: no substep of XPBD_MODE_CONTACTS has run since the last broadphase, upload, "
+                                         "history restore, enable, failed step or step in another mode", who);
+    if (w->report_ready)
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    if (!w->report_keys_ready)
+        XPBD_TRY(report_compact_keys(w));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // (also: reserve() frees a block only when no queued work uses it)
+    const uint32_t cur = w->report_cur, k = w->rep_host[cur], n_prev = w->report_prev_valid ? w->rep_host[cur ^ 1u] : 0u;
+    const size_t n_ev = (size_t)k + n_prev;
+    XPBD_HIP_TRY(w->rep_ev_flag.reserve((n_ev + 1) * 4));
+    XPBD_HIP_TRY(w->rep_scan.reserve((n_ev / 1024 + 8) * 4)); // both scans below: k <= n_ev
+    XPBD_HIP_TRY(xpbd::launch_exclusive_scan(w->rep_npts.as<uint32_t>(), k, w->rep_scan.as<uint32_t>(), w->stream));
+    XPBD_HIP_TRY(xpbd::launch_report_event_flags(w->rep_keys[cur].as<unsigned long long>(), k, w->rep_keys[cur ^ 1u].as<unsigned long long>(),
+                                                 n_prev, w->rep_ev_flag.as<uint32_t>(), w->rep_scan.as<uint32_t>(), w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(&w->rep_host[2], w->rep_npts.as<uint32_t>() + k, 4, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(&w->rep_host[3], w->rep_ev_flag.as<uint32_t>() + k, 4, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(&w->rep_host[4], w->rep_ev_flag.as<uint32_t>() + n_ev, 4, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    w->report_counts[0] = k;
+    w->report_counts[1] = w->rep_host[2];
+    w->report_counts[2] = w->rep_host[3];
+    w->report_counts[3] = w->rep_host[4] - w->rep_host[3];
+    w->report_ready = true;
+    return XPBD_OK;
+}
+
 // Sphere broadphase of the contact pipeline: neighbour lists + pair list for the coming frame, in two halves.
 // First half: bounding spheres, buckets and the neighbour COUNT of every body are enqueued, the totals travel to pinned host
 // memory behind them, an event marks their arrival.  Nothing here waits for the device.
 int build_neighbours_enqueue(xpbd_world *w, double dt)
 {
+    if (int rc = report_frame_end(w))
+        return rc;
     if (!w->bp_totals) {
         XPBD_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->bp_totals), sizeof *w->bp_totals, hipHostMallocDefault));
         XPBD_HIP_TRY(hipEventCreateWithFlags(&w->bp_event, hipEventDisableTiming));
@@ -383,7 +500,7 @@ int build_neighbours_collect(xpbd_world *w)
     c = w->contact_buffers();
     XPBD_HIP_TRY(xpbd::launch_neighbour_fill(b, c, w->stream));
     w->have_neighbours = true;
-    return XPBD_OK;
+    return report_frame_begin(w);
 }
 
 int build_neighbours(xpbd_world *w, double dt)
@@ -410,6 +527,11 @@ int narrowphase_contacts(xpbd_world *w, const xpbd::BodyArrays &b, const xpbd::C
                                                     w->stream, w->sat_scratch.cache_edge_axes /* = a dense scene, see below */));
     }
     w->stats_pair_substeps += w->n_pairs;
+    if (w->report_frame) {
+        XPBD_HIP_TRY(xpbd::launch_report_touch(c.pair_codes, w->rep_touch.as<uint32_t>(), w->n_pairs, w->stream));
+        ++w->report_substeps;
+        w->report_keys_ready = w->report_ready = false;
+    }
     return XPBD_OK;
 }
 
@@ -715,6 +837,7 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     w->trace_rows = 0;
     w->frame_snapshot_valid = false;
     w->bp_pending = false;
+    report_reset(w);
     // mass properties shared per shape: the bodies that stay kept the property, the incoming ones are checked
     if (w->stat_shape_seen.size() != w->n_shapes) {
         w->stat_shape_host.assign((size_t)w->n_shapes * kStatRecDoubles, 0.0);
@@ -1217,6 +1340,7 @@ try {
     w->trace_rows = 0;
     w->frame_snapshot_valid = false;
     w->bp_pending = false;
+    report_reset(w);
     if (n == 0)
         return XPBD_OK;
     XPBD_HIP_TRY(hipMemcpyAsync(w->aos_staging.ptr, aos, (size_t)n * sizeof(xpbd_rigid), hipMemcpyHostToDevice,
@@ -1289,12 +1413,16 @@ try {
         w->trace_rows = substeps;
     }
     if (w->mode == XPBD_MODE_CONTACTS) {
-        if (int rc = step_contacts(w, dt, h, substeps, trace))
+        if (int rc = step_contacts(w, dt, h, substeps, trace)) {
+            report_reset(w);
             return rc;
+        }
     } else if (w->mode == XPBD_MODE_FUSED) {
+        report_reset(w);
         XPBD_HIP_TRY(xpbd::launch_step(w->arrays(), w->shapes(), h, substeps, w->last_mask.as<uint32_t>(), trace, 0,
                                        w->block_size, w->stream));
     } else {
+        report_reset(w);
         for (uint32_t k = 0; k < substeps; ++k)
             XPBD_HIP_TRY(xpbd::launch_step(w->arrays(), w->shapes(), h, 1, w->last_mask.as<uint32_t>(), trace, k,
                                            w->block_size, w->stream));
@@ -1555,7 +1683,12 @@ try {
     if (int rc = bind_device(w))
         return rc;
     w->stepped = true;
-    return w->n ? build_neighbours(w, dt) : XPBD_OK;
+    if (w->n == 0)
+        return XPBD_OK;
+    const int rc = build_neighbours(w, dt);
+    if (rc)
+        report_reset(w);
+    return rc;
 } XPBD_ABI_CATCH
 
 int xpbd_world_contacts_substep(xpbd_world *w, double h)
@@ -1568,7 +1701,10 @@ try {
         return XPBD_OK;
     if (int rc = bind_device(w))
         return rc;
-    return substep_contacts(w, h, nullptr, 0);
+    const int rc = substep_contacts(w, h, nullptr, 0);
+    if (rc)
+        report_reset(w);
+    return rc;
 } XPBD_ABI_CATCH
 
 int xpbd_world_export_dynamic(xpbd_world *w, const uint32_t *dev_indices, uint32_t n, double *dev_buf)
@@ -1678,6 +1814,89 @@ try {
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
+int xpbd_world_set_contact_report(xpbd_world *w, uint32_t enable)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_contact_report: NULL world");
+    if (enable > 1u)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_contact_report: enable must be 0 or 1, not %u", enable);
+    if (int rc = bind_device(w))
+        return rc;
+    if (enable && !w->rep_host)
+        XPBD_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->rep_host), 8 * sizeof(uint32_t), hipHostMallocDefault));
+    if (!enable && w->report_on) { // (queued work may still read the buffers)
+        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+        for (DeviceBuffer *b : {&w->rep_touch, &w->rep_flag, &w->rep_sel, &w->rep_npts, &w->rep_keys[0], &w->rep_keys[1], &w->rep_scan,
+                                &w->rep_ev_flag, &w->rep_pairs, &w->rep_points, &w->rep_events})
+            b->release();
+    }
+    report_reset(w);
+    w->report_on = enable != 0;
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_contact_report_counts(xpbd_world *w, uint32_t out[4])
+try {
+    if (!w || !out)
+        return set_error(XPBD_E_INVALID, "xpbd_world_contact_report_counts: NULL argument");
+    XPBD_TRY(report_prepare(w, "xpbd_world_contact_report_counts"));
+    for (int k = 0; k < 4; ++k)
+        out[k] = w->report_counts[k];
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_download_pair_contacts(xpbd_world *w, xpbd_pair_contact *pairs, uint32_t pair_cap, xpbd_contact_point *points,
+                                      uint32_t point_cap, uint32_t *n_pairs, uint32_t *n_points)
+try {
+    if (!w || !n_pairs || !n_points || (!pairs && pair_cap) || (!points && point_cap))
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_pair_contacts: NULL argument");
+    XPBD_TRY(report_prepare(w, "xpbd_world_download_pair_contacts"));
+    const uint32_t k = w->report_counts[0], total_points = w->report_counts[1];
+    *n_pairs = k;
+    *n_points = total_points;
+    const uint32_t take = k < pair_cap ? k : pair_cap, take_points = points ? (total_points < point_cap ? total_points : point_cap) : 0u;
+    if (take || take_points) {
+        XPBD_HIP_TRY(w->rep_pairs.reserve((size_t)k * sizeof(xpbd_pair_contact)));
+        if (points)
+            XPBD_HIP_TRY(w->rep_points.reserve((size_t)(total_points ? total_points : 1) * sizeof(xpbd_contact_point)));
+        const uint32_t cur = w->report_cur;
+        XPBD_HIP_TRY(xpbd::launch_report_records(report_frame_of(w), w->rep_keys[cur].as<unsigned long long>(), w->rep_sel.as<uint32_t>(),
+                                                 w->rep_npts.as<uint32_t>(), k, w->rep_pairs.as<xpbd_pair_contact>(),
+                                                 points ? w->rep_points.as<xpbd_contact_point>() : nullptr, w->stream));
+        if (take)
+            XPBD_HIP_TRY(hipMemcpyAsync(pairs, w->rep_pairs.ptr, (size_t)take * sizeof(xpbd_pair_contact), hipMemcpyDeviceToHost, w->stream));
+        if (take_points)
+            XPBD_HIP_TRY(hipMemcpyAsync(points, w->rep_points.ptr, (size_t)take_points * sizeof(xpbd_contact_point), hipMemcpyDeviceToHost,
+                                        w->stream));
+        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    }
+    if (k > pair_cap || (points && total_points > point_cap))
+        return set_error(XPBD_E_CAPACITY, "xpbd_world_download_pair_contacts: %u pairs, capacity %u; %u points, capacity %u", k, pair_cap,
+                         total_points, point_cap);
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_download_contact_events(xpbd_world *w, xpbd_contact_event *out, uint32_t cap, uint32_t *n_out)
+try {
+    if (!w || !n_out || (!out && cap))
+        return set_error(XPBD_E_INVALID, "xpbd_world_download_contact_events: NULL argument");
+    XPBD_TRY(report_prepare(w, "xpbd_world_download_contact_events"));
+    const uint32_t total = w->report_counts[2] + w->report_counts[3];
+    *n_out = total;
+    const uint32_t take = total < cap ? total : cap;
+    if (take) {
+        const uint32_t cur = w->report_cur, k = w->report_counts[0], n_prev = w->report_prev_valid ? w->rep_host[cur ^ 1u] : 0u;
+        XPBD_HIP_TRY(w->rep_events.reserve((size_t)total * sizeof(xpbd_contact_event)));
+        XPBD_HIP_TRY(xpbd::launch_report_event_write(w->rep_keys[cur].as<unsigned long long>(), k, w->rep_keys[cur ^ 1u].as<unsigned long long>(),
+                                                     n_prev, w->rep_ev_flag.as<uint32_t>(), w->rep_events.as<xpbd_contact_event>(), w->stream));
+        XPBD_HIP_TRY(hipMemcpyAsync(out, w->rep_events.ptr, (size_t)take * sizeof(xpbd_contact_event), hipMemcpyDeviceToHost, w->stream));
+        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    }
+    if (total > cap)
+        return set_error(XPBD_E_CAPACITY, "xpbd_world_download_contact_events: %u events, capacity %u", total, cap);
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
 int xpbd_world_build_neighbours(xpbd_world *w, double dt, uint32_t *n_entries_out)
 try {
     if (!w || !n_entries_out)
@@ -1760,6 +1979,7 @@ try {
     XPBD_HIP_TRY(hipMemcpyAsync(w->last_mask.ptr, src + dyn_bytes, (size_t)w->stride * 4, hipMemcpyDeviceToDevice, w->stream));
     w->stepped = w->history_stepped[index] != 0;
     w->have_neighbours = false;
+    report_reset(w);
     w->trace_rows = 0; // the per-substep trace belongs to the step call that was overwritten
     return XPBD_OK;
 } XPBD_ABI_CATCH
@@ -1941,3 +2161,37 @@ try {
 } XPBD_ABI_CATCH
 
 } // extern "C"
+
+namespace xpbd {
+int report_shard(xpbd_world *w, const uint8_t *dev_owned, const uint32_t *dev_global_id, std::vector<xpbd_pair_contact> &pairs,
+                 std::vector<xpbd_contact_point> &points) noexcept
+try {
+    pairs.clear();
+    points.clear();
+    if (!w)
+        return set_error(XPBD_E_INVALID, "report_shard: NULL world");
+    if (w->n == 0)
+        return XPBD_OK;
+    // the keys are compacted again with the shard's mapping, and once more without it should the shard world itself be asked
+    w->rep_map_owned = dev_owned;
+    w->rep_map_ids = dev_global_id;
+    w->report_keys_ready = w->report_ready = false;
+    uint32_t counts[4] = {0, 0, 0, 0}, n_pairs = 0, n_points = 0;
+    int rc = xpbd_world_contact_report_counts(w, counts);
+    if (rc == XPBD_OK) {
+        pairs.resize(counts[0]);
+        points.resize(counts[1]);
+        rc = xpbd_world_download_pair_contacts(w, pairs.empty() ? nullptr : pairs.data(), counts[0], points.empty() ? nullptr : points.data(),
+                                               counts[1], &n_pairs, &n_points);
+    }
+    w->rep_map_owned = nullptr;
+    w->rep_map_ids = nullptr;
+    w->report_keys_ready = w->report_ready = false;
+    return rc;
+} catch (...) {
+    w->rep_map_owned = nullptr;
+    w->rep_map_ids = nullptr;
+    w->report_keys_ready = w->report_ready = false;
+    return abi_exception("report_shard");
+}
+} // namespace xpbd

@@ -172,6 +172,41 @@ pub struct XpbdRayHit {
     pub normal: [f64; 3],
 }
 
+pub const XPBD_CONTACT_BEGIN: u32 = 0;
+pub const XPBD_CONTACT_END: u32 = 1;
+
+/// xpbd_pair_contact (64 bytes): a pair that touched in the frame; manifold of its last substep (include/xpbd.h, "Contact REPORTS")
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdPairContact {
+    pub body_a: u32,
+    pub body_b: u32,
+    pub substeps: u32,
+    pub n_points: u32,
+    pub feature: u32,
+    pub first_point: u32,
+    pub reserved: [u32; 2],
+    pub normal: [f64; 3],
+    pub depth: f64,
+}
+
+/// xpbd_contact_point (48 bytes, world space)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdContactPoint {
+    pub p_ref: [f64; 3],
+    pub p_inc: [f64; 3],
+}
+
+/// xpbd_contact_event (12 bytes): kind = XPBD_CONTACT_BEGIN / XPBD_CONTACT_END
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdContactEvent {
+    pub body_a: u32,
+    pub body_b: u32,
+    pub kind: u32,
+}
+
 #[repr(C)]
 pub struct XpbdWorld {
     _private: [u8; 0],
@@ -302,6 +337,17 @@ extern "C" {
                                             dev_hits: *mut XpbdRayHit) -> c_int;
     pub fn xpbd_multi_world_raycast_masked(mw: *mut XpbdMultiWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32,
                                            hits: *mut XpbdRayHit) -> c_int;
+    pub fn xpbd_world_set_contact_report(w: *mut XpbdWorld, enable: u32) -> c_int;
+    pub fn xpbd_world_contact_report_counts(w: *mut XpbdWorld, out: *mut u32) -> c_int;
+    pub fn xpbd_world_download_pair_contacts(w: *mut XpbdWorld, pairs: *mut XpbdPairContact, pair_cap: u32, points: *mut XpbdContactPoint,
+                                             point_cap: u32, n_pairs: *mut u32, n_points: *mut u32) -> c_int;
+    pub fn xpbd_world_download_contact_events(w: *mut XpbdWorld, out: *mut XpbdContactEvent, cap: u32, n_out: *mut u32) -> c_int;
+    pub fn xpbd_multi_world_set_contact_report(mw: *mut XpbdMultiWorld, enable: u32) -> c_int;
+    pub fn xpbd_multi_world_contact_report_counts(mw: *mut XpbdMultiWorld, out: *mut u32) -> c_int;
+    pub fn xpbd_multi_world_download_pair_contacts(mw: *mut XpbdMultiWorld, pairs: *mut XpbdPairContact, pair_cap: u32,
+                                                   points: *mut XpbdContactPoint, point_cap: u32, n_pairs: *mut u32, n_points: *mut u32)
+        -> c_int;
+    pub fn xpbd_multi_world_download_contact_events(mw: *mut XpbdMultiWorld, out: *mut XpbdContactEvent, cap: u32, n_out: *mut u32) -> c_int;
 }
 
 fn v3(v: Vector3<f64>) -> [f64; 3] {

@@ -521,6 +521,32 @@ class BatchWorld {
         check(xpbd_world_set_collision_filters(w_, filters.empty() ? nullptr : filters.data(), (uint32_t)filters.size(), flags));
     }
 
+    // contact reports (include/xpbd.h, "Contact REPORTS"): the touching pairs of the current frame and the begin / end events
+    void set_contact_report(bool enable) { check(xpbd_world_set_contact_report(w_, enable ? 1u : 0u)); }
+    std::array<uint32_t, 4> contact_report_counts() // pairs, points, begins, ends
+    {
+        std::array<uint32_t, 4> out{};
+        check(xpbd_world_contact_report_counts(w_, out.data()));
+        return out;
+    }
+    void pair_contacts(std::vector<xpbd_pair_contact> &pairs, std::vector<xpbd_contact_point> &points)
+    {
+        const std::array<uint32_t, 4> n = contact_report_counts();
+        pairs.resize(n[0]);
+        points.resize(n[1]);
+        uint32_t n_pairs = 0, n_points = 0;
+        check(xpbd_world_download_pair_contacts(w_, pairs.empty() ? nullptr : pairs.data(), n[0], points.empty() ? nullptr : points.data(), n[1],
+                                                &n_pairs, &n_points));
+    }
+    std::vector<xpbd_contact_event> contact_events()
+    {
+        const std::array<uint32_t, 4> n = contact_report_counts();
+        std::vector<xpbd_contact_event> out(n[2] + n[3]);
+        uint32_t n_out = 0;
+        check(xpbd_world_download_contact_events(w_, out.empty() ? nullptr : out.data(), (uint32_t)out.size(), &n_out));
+        return out;
+    }
+
     std::vector<xpbd_contact> contacts()
     {
         uint32_t n = 0;
@@ -613,6 +639,31 @@ class ShardedWorld {
     void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)
     {
         check(xpbd_multi_world_set_collision_filters(w_, filters.empty() ? nullptr : filters.data(), (uint32_t)filters.size(), flags));
+    }
+    // contact reports of the whole world, global body indices; step() gathers them, these calls read every rank's copy
+    void set_contact_report(bool enable) { check(xpbd_multi_world_set_contact_report(w_, enable ? 1u : 0u)); }
+    std::array<uint32_t, 4> contact_report_counts() // pairs, points, begins, ends
+    {
+        std::array<uint32_t, 4> out{};
+        check(xpbd_multi_world_contact_report_counts(w_, out.data()));
+        return out;
+    }
+    void pair_contacts(std::vector<xpbd_pair_contact> &pairs, std::vector<xpbd_contact_point> &points)
+    {
+        const std::array<uint32_t, 4> n = contact_report_counts();
+        pairs.resize(n[0]);
+        points.resize(n[1]);
+        uint32_t n_pairs = 0, n_points = 0;
+        check(xpbd_multi_world_download_pair_contacts(w_, pairs.empty() ? nullptr : pairs.data(), n[0], points.empty() ? nullptr : points.data(),
+                                                      n[1], &n_pairs, &n_points));
+    }
+    std::vector<xpbd_contact_event> contact_events()
+    {
+        const std::array<uint32_t, 4> n = contact_report_counts();
+        std::vector<xpbd_contact_event> out(n[2] + n[3]);
+        uint32_t n_out = 0;
+        check(xpbd_multi_world_download_contact_events(w_, out.empty() ? nullptr : out.data(), (uint32_t)out.size(), &n_out));
+        return out;
     }
     void synchronize() { check(xpbd_multi_world_synchronize(w_)); }
     void download(std::vector<rigid::Rigid> &bodies)

@@ -609,6 +609,92 @@ int  xpbd_world_raycast_masked_device(xpbd_world *w, const xpbd_ray *dev_rays, u
 int  xpbd_multi_world_raycast_masked(xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags,
                                      uint32_t mask, xpbd_ray_hit *hits);
 
+/* ---------------------------------------------------------------------------
+ * Contact REPORTS (EXTENSION): which body pairs the contact pipeline of XPBD_MODE_CONTACTS found touching, with the
+ * manifolds it solved, and which pairs began or ended touching.  NOT in the reference; its app draws the reference and
+ * incident planes of `sat` into DebugLines (src/collision.rs:69, 87) and, commented out, the contact points (:97-108).
+ *
+ * Frame.  A frame runs from one broadphase (xpbd_world_step, xpbd_world_contacts_begin, xpbd_world_build_neighbours) to
+ * the next one.  The report describes the current frame once at least one of its substeps has run; with the split API a
+ * download mid-frame covers the substeps run so far.
+ *
+ * Touching.  A pair touches in a substep when its manifold of that substep has n_points > 0.  Pairs the sphere pre-test
+ * answers, GJK's degenerate queries and separated pairs do not touch.  Filtered pairs (xpbd_world_set_collision_filters)
+ * are never reported: they are not in the pair list.
+ *
+ * Pair records: every pair that touched in at least one substep of the frame, sorted by (body_a, body_b), body_a <
+ * body_b, the caller's body indices.  `substeps` = the substeps of the frame in which it touched; the rest describes the
+ * LAST substep, as the pair solve used it -- the points at the post-integrate poses P1 (oracle/xpbd_pairs_oracle.h,
+ * step 2):
+ *   n_points  0 when the pair touched only in earlier substeps (then feature = 0, normal = (0,0,0), depth = 0);
+ *   feature   XPBD_FEATURE_*;
+ *   points    p_ref[k] on the reference body, p_inc[k] the incident body's penetrating point.  A face contact's p_ref[k] is
+ *             p_inc[k] projected onto the reference plane with the clipper's own expression,
+ *             p_inc - (dot(n, p_inc) - d) * n  (Plane::project, src/geometry.rs:45-47), so it equals the oracle's bits;
+ *   normal    from body_a towards body_b: a face contact's reference-plane normal, negated for XPBD_FEATURE_FACE_B; the
+ *             one-point contact (XPBD_FEATURE_EDGES: edges, or GJK + EPA without a face normal): u * (1 / |u|) with
+ *             u = p_ref[0] - p_inc[0], (0,0,0) when u is zero;
+ *   depth     max over k of |p_ref[k] - p_inc[k]|.
+ * `first_point` indexes the point list, in which every pair's points follow each other in pair order.
+ *
+ * Events.  With S the touching set of this frame and S_prev the one of the world's previous frame: XPBD_CONTACT_BEGIN for
+ * every pair of S not in S_prev, XPBD_CONTACT_END for every pair of S_prev not in S; all BEGINs in key order, then all
+ * ENDs in key order.  S_prev is EMPTY after enabling reports, after xpbd_world_upload_bodies,
+ * after xpbd_world_history_restore, after a step in another mode and after a failed step.  After a failed step or a step
+ * in another mode, and until the next broadphase of XPBD_MODE_CONTACTS has run a substep, the counts and downloads are
+ * XPBD_E_INVALID.  Joints, limits, filters, the narrowphase and the SAT schedule may change between frames.
+ *
+ * The report only reads: bodies, contact lists, masks, statistics and history are the same bits with reporting on or off,
+ * and with reporting off (the default) no part of it runs.
+ *
+ * Calls.  xpbd_world_set_contact_report: enable 0 or 1, in any mode (only steps in XPBD_MODE_CONTACTS produce a report).
+ * The counts and downloads wait for the device.  Capacities as xpbd_world_download_contacts: the totals always go to
+ * *n_pairs / *n_points / *n_out, a short buffer gets XPBD_E_CAPACITY with its first `cap` entries filled.  points == NULL
+ * (with point_cap 0) downloads no points and is no capacity error.  XPBD_E_INVALID: a NULL world, reporting off, no report
+ * available (above), NULL counts, or a NULL buffer with a nonzero capacity.
+ *
+ * Multi world (xpbd_multi_world_*): the same report with global body indices, the same bits as one xpbd_world over the same
+ * bodies, events included.  Every shard reports the pairs whose lower body it owns; xpbd_multi_world_step (collective) gathers
+ * the lists of all ranks at the end of every accepted frame and merges them, so every rank holds the whole world's report and
+ * derives the events from the merged lists (owners changing at a re-plan do not matter; a frame that is undone and re-run under
+ * XPBD_MULTI_AUTO_REPLAN leaves no trace).  The counts and downloads then read that copy: they communicate nothing and may be
+ * called on any rank.  S_prev is empty after enabling, after xpbd_multi_world_upload and after a failed step.
+ * ------------------------------------------------------------------------- */
+#define XPBD_CONTACT_BEGIN 0u
+#define XPBD_CONTACT_END   1u
+
+typedef struct xpbd_pair_contact {   /* 64 bytes */
+    uint32_t body_a, body_b;         /* body_a < body_b */
+    uint32_t substeps;               /* substeps of the frame in which the pair touched (>= 1) */
+    uint32_t n_points;               /* in the last substep (0: touched only earlier in the frame) */
+    uint32_t feature;                /* XPBD_FEATURE_* of the last substep (valid when n_points > 0) */
+    uint32_t first_point;            /* index of its first point in the point list */
+    uint32_t reserved[2];
+    double   normal[3];
+    double   depth;
+} xpbd_pair_contact;
+
+typedef struct xpbd_contact_point {  /* 48 bytes, world space, last substep */
+    double p_ref[3];                 /* on the reference body's surface */
+    double p_inc[3];                 /* the penetrating point of the incident body */
+} xpbd_contact_point;
+
+typedef struct xpbd_contact_event {  /* 12 bytes */
+    uint32_t body_a, body_b, kind;   /* XPBD_CONTACT_* */
+} xpbd_contact_event;
+
+int  xpbd_world_set_contact_report(xpbd_world *w, uint32_t enable);
+/* out = {pairs, points, begins, ends} */
+int  xpbd_world_contact_report_counts(xpbd_world *w, uint32_t out[4]);
+int  xpbd_world_download_pair_contacts(xpbd_world *w, xpbd_pair_contact *pairs, uint32_t pair_cap,
+                                       xpbd_contact_point *points, uint32_t point_cap, uint32_t *n_pairs, uint32_t *n_points);
+int  xpbd_world_download_contact_events(xpbd_world *w, xpbd_contact_event *out, uint32_t cap, uint32_t *n_out);
+int  xpbd_multi_world_set_contact_report(xpbd_multi_world *mw, uint32_t enable);
+int  xpbd_multi_world_contact_report_counts(xpbd_multi_world *mw, uint32_t out[4]);
+int  xpbd_multi_world_download_pair_contacts(xpbd_multi_world *mw, xpbd_pair_contact *pairs, uint32_t pair_cap,
+                                             xpbd_contact_point *points, uint32_t point_cap, uint32_t *n_pairs, uint32_t *n_points);
+int  xpbd_multi_world_download_contact_events(xpbd_multi_world *mw, xpbd_contact_event *out, uint32_t cap, uint32_t *n_out);
+
 /* Diagnostics: quotient[i] = a[i] / b[i], root[i] = sqrt(a[i]) computed on the
  * device with the stepper's own code generation.  Bit-exact contact lists need
  * both to be correctly rounded; the parity tests check this against the host. */
