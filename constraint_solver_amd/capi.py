@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "xpbd_world_set_contact_report", "xpbd_world_contact_report_counts", "xpbd_world_download_pair_contacts",
     "xpbd_world_download_contact_events", "xpbd_multi_world_set_contact_report", "xpbd_multi_world_contact_report_counts",
     "xpbd_multi_world_download_pair_contacts", "xpbd_multi_world_download_contact_events",
+    "xpbd_world_set_materials", "xpbd_multi_world_set_materials",
 ]
 
 
@@ -107,6 +108,8 @@ LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST = 0, 1, 2
 # xpbd_collision_filter as a numpy record (8 bytes): bodies i, j may touch iff group_i & mask_j and group_j & mask_i
 COLLISION_FILTER_DTYPE = np.dtype([("group", "<u4"), ("mask", "<u4")])
 FILTER_JOINTED = 1                # bodies joined by a joint never collide
+# xpbd_material as a numpy record (16 bytes): Coulomb friction coefficient >= 0 (+inf: the reference's contact), reserved = 0
+MATERIAL_DTYPE = np.dtype([("friction", "<f8"), ("reserved", "<f8")])
 # xpbd_gjk_result as a numpy record (96 bytes)
 GJK_DTYPE = np.dtype([("status", "<i4"), ("gjk_iterations", "<u4"), ("epa_iterations", "<u4"), ("reserved", "<u4"),
                       ("depth", "<f8"), ("normal", "<f8", (3,)), ("point_a", "<f8", (3,)), ("point_b", "<f8", (3,))])
@@ -267,6 +270,11 @@ def hip_lib():
             L.xpbd_multi_world_contact_report_counts.argtypes = [C.c_void_p, _u32p]
             L.xpbd_multi_world_download_pair_contacts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, _u32p, _u32p]
             L.xpbd_multi_world_download_contact_events.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, _u32p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            L.xpbd_world_set_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double]
+            L.xpbd_multi_world_set_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -447,6 +455,12 @@ class World:
         f = _filters(filters)
         _check(hip_lib().xpbd_world_set_collision_filters(self._h, None if f is None else f.ctypes.data, 0 if f is None else f.size, flags))
 
+    def set_materials(self, materials=None, ground_friction=np.inf):
+        """materials: MATERIAL_DTYPE records or plain friction coefficients, one per body of the last upload, or None for
+        the default +inf (extension; XPBD_MODE_CONTACTS); ground_friction: the coefficient of the plane z = 0."""
+        m = _materials(materials)
+        _check(hip_lib().xpbd_world_set_materials(self._h, None if m is None else m.ctypes.data, 0 if m is None else m.size, ground_friction))
+
     def contacts_begin(self, dt):
         _check(hip_lib().xpbd_world_contacts_begin(self._h, dt))
 
@@ -561,6 +575,18 @@ def _filters(filters):
     return np.ascontiguousarray(f)
 
 
+def _materials(materials):
+    """MATERIAL_DTYPE records from records or an array of friction coefficients; None stays None."""
+    if materials is None:
+        return None
+    m = np.asarray(materials)
+    if m.dtype != MATERIAL_DTYPE:
+        rec = np.zeros(m.size, dtype=MATERIAL_DTYPE)
+        rec["friction"] = np.asarray(m, dtype=np.float64).reshape(-1)
+        m = rec
+    return np.ascontiguousarray(m)
+
+
 def polytope_descs(polytopes):
     """(xpbd_polytope array, the numpy arrays it points into) from a list of polytope dicts."""
     keep, descs = [], (PolytopeDesc * len(polytopes))()
@@ -649,6 +675,12 @@ class MultiWorld:
         f = _filters(filters)
         _check(hip_lib().xpbd_multi_world_set_collision_filters(self._h, None if f is None else f.ctypes.data, 0 if f is None else f.size,
                                                                 flags))
+
+    def set_materials(self, materials=None, ground_friction=np.inf):
+        """World.set_materials over the whole sharded world: n_global records in global body order (not collective)."""
+        m = _materials(materials)
+        _check(hip_lib().xpbd_multi_world_set_materials(self._h, None if m is None else m.ctypes.data, 0 if m is None else m.size,
+                                                        ground_friction))
 
     def upload(self, bodies, shape_id, first_global, n_global, joints=None):
         """bodies / shape_id: the slice of the caller's bodies this process hands over, global indices [first_global,

@@ -76,6 +76,10 @@ struct ContactBuffers {
     const uint2 *filter;    // [n] group, mask of every body
     uint32_t *slot_filter;  // [2][stride] group, mask of items[s] (bucket order; written only when `filter` is set)
     uint32_t filter_jointed; // XPBD_FILTER_JOINTED: bodies joined by a joint of `joints` are never neighbours
+    // contact materials (xpbd_world_set_materials): NULL = off, every contact is the reference's (the kernels' plain forms,
+    // which never read these two).  (After the filters, for the same reason.)
+    const double *friction;  // [n] Coulomb coefficient of every body, >= 0, may be +inf
+    double ground_friction;  // ... and of the plane z = 0
 };
 
 // Which bodies a per-body kernel of the pipeline works on.  Default: all of them.  The multi-GPU world (xpbd_multi.cpp) runs

@@ -514,6 +514,11 @@ __global__ void k_neighbour_pair_index(BodyArrays b, ContactBuffers c)
     }
 }
 
+// Contact materials (include/xpbd.h, "Contact MATERIALS"): the coefficient of a contact is the smaller of its two sides'.
+// (The coefficients are validated on the host: never NaN, so the comparison is an exact minimum.)
+__device__ __forceinline__ double min_mu(double a, double b) { return b < a ? b : a; }
+__device__ __forceinline__ double ground_mu(const ContactBuffers &c, uint32_t i) { return min_mu(c.friction[i], c.ground_friction); }
+
 // Body of work item `slot` under a BodySubset (false: nothing to do).
 __device__ __forceinline__ bool subset_body(const BodySubset &ss, uint32_t n, uint32_t slot, uint32_t &i)
 {
@@ -546,7 +551,8 @@ __device__ __forceinline__ BodyDynamic load_row(const double *__restrict__ rows,
 // ---------------------------------------------------------------------------------------------------
 // Per substep, per body: integrate, remember the frames, ground contacts (reference path).
 // ---------------------------------------------------------------------------------------------------
-template <bool TRACE>
+// MATERIALS: the form of a world with contact materials (c.friction set); the plain form never reads them.
+template <bool TRACE, bool MATERIALS>
 __global__ void __launch_bounds__(kBlock) k_integrate_ground(BodyArrays b, ShapeTable shapes, double h, ContactBuffers c, BodySubset subset,
                                                              uint32_t *__restrict__ last_mask,
                                                              uint32_t *__restrict__ trace_masks, uint32_t trace_row)
@@ -572,8 +578,9 @@ __global__ void __launch_bounds__(kBlock) k_integrate_ground(BodyArrays b, Shape
     const double compliance = 1e-6 / (h * h);
 
     const SubstepFrames f = integrate_body(d, s, h);
-    const uint32_t mask = solve_ground(d, s, f, compliance, lds + 3 * v0, lds_off[sid + 1] - v0,
-                                       c.max_depenetration_speed > 0.0 ? c.max_depenetration_speed * h : 0.0);
+    const uint32_t mask = solve_ground<MATERIALS>(d, s, f, compliance, lds + 3 * v0, lds_off[sid + 1] - v0,
+                                                  c.max_depenetration_speed > 0.0 ? c.max_depenetration_speed * h : 0.0,
+                                                  MATERIALS ? ground_mu(c, i) : 0.0);
 
     // the pose after the ground contacts lives in the record only: the pair solve (the one reader) takes it from there and
     // rewrites the whole SoA state (velocities come from derive)
@@ -811,7 +818,9 @@ __device__ XPBD_JOINT_LIMIT_INLINE void joint_limit_terms(const ContactBuffers &
 #define XPBD_PAIR_SOLVE_ROUND_POINTS 2 // points of a manifold per round, see pass 2 below; A/B (boxes pile / mixed pile SAT / GJK+EPA,
                                        // 1e8 body-substeps/s): 1 point 5.24 / 2.56 / 2.76, 2 points 5.35 / 2.57 / 2.80, 3 points 5.30 / 2.54 / 2.75
 #endif
-template <uint32_t G>
+// MATERIALS: contact materials are set (c.friction; uniform over the launch, chosen by the launcher).  The plain form is the
+// reference's contact: it loads no coefficient and keeps the literal 1.0.
+template <uint32_t G, bool MATERIALS>
 __device__ __forceinline__ BodyDynamic pair_solve_derive_body(const ContactBuffers &c, uint32_t i, double h,
                                                               const PairBody &self, Vec3 self_past_pos, uint32_t sub, uint32_t &touching,
                                                               uint32_t &points, const RecordStage &stage = RecordStage())
@@ -819,6 +828,7 @@ __device__ __forceinline__ BodyDynamic pair_solve_derive_body(const ContactBuffe
     static_assert(G == 1 || G == kMaxManifoldPoints, "one lane per body or one lane per manifold point");
     const double compliance = 1e-6 / (h * h);
     const double limit = c.max_depenetration_speed > 0.0 ? c.max_depenetration_speed * h : 0.0;
+    const double mu_self = MATERIALS ? c.friction[i] : 0.0;
 
     Vec3 dpos{0.0, 0.0, 0.0};
     Quat drot{0.0, 0.0, 0.0, 0.0};
@@ -830,6 +840,7 @@ __device__ __forceinline__ BodyDynamic pair_solve_derive_body(const ContactBuffe
             points += n_points;
         }
         const PairBody other = load_pair_body(c, j, nullptr, stage);
+        const double mu = MATERIALS ? min_mu(mu_self, c.friction[j]) : 0.0; // (only touching neighbours get here)
         // pair (A, B) = (min, max); the reference body is A unless the reference face is on B.  The formulas are
         // written in terms of the incident and the reference body; here every term is evaluated for `self` and
         // `other` with their own point and only 3-vectors are selected by role -- selecting whole bodies by a
@@ -858,7 +869,14 @@ __device__ __forceinline__ BodyDynamic pair_solve_derive_body(const ContactBuffe
             const Vec3 delta_rel = self_is_inc ? moved_self - moved_other : moved_other - moved_self; // incident - reference
             const Vec3 delta_tangential = delta_rel - project_on(delta_rel, correction);
             const Vec3 c0 = p_inc;
-            const Vec3 c1 = p_ref - 1.0 * delta_tangential;
+            double k = 1.0;
+            if (MATERIALS) { // Coulomb's cone on positions: at most mu * |correction| of the tangential slip is taken back
+                const double bound = mu * length(correction);
+                const double len_t = length(delta_tangential);
+                if (bound < len_t) // (false for mu = +inf, a NaN bound, len_t = 0: the reference's contact)
+                    k = bound / len_t;
+            }
+            const Vec3 c1 = p_ref - k * delta_tangential;
             const Vec3 difference = c1 - c0;
             const double dist = length(difference);
             const Vec3 dir = difference * (1.0 / dist);
@@ -1054,7 +1072,7 @@ __device__ __forceinline__ void block_add_stats(uint32_t touching, uint32_t poin
     }
 }
 
-template <uint32_t G>
+template <uint32_t G, bool MATERIALS>
 __global__ void __launch_bounds__(kBlock, XPBD_PAIR_SOLVE_MIN_WAVES) k_pair_solve_derive(BodyArrays b, double *__restrict__ dyn_out, double h,
                                                                                         ContactBuffers c, BodySubset subset)
 {
@@ -1069,7 +1087,7 @@ __global__ void __launch_bounds__(kBlock, XPBD_PAIR_SOLVE_MIN_WAVES) k_pair_solv
     if (subset_body(subset, b.n, slot, i)) {
         Vec3 past_pos;
         const PairBody self = load_pair_body(c, i, &past_pos, stage);
-        const BodyDynamic d = pair_solve_derive_body<G>(c, i, h, self, past_pos, sub, touching, points, stage);
+        const BodyDynamic d = pair_solve_derive_body<G, MATERIALS>(c, i, h, self, past_pos, sub, touching, points, stage);
         if (sub == 0) {
             store_dynamic(dyn_out, b.stride, i, d);
             if (subset.export_rows)
@@ -1087,7 +1105,7 @@ __global__ void __launch_bounds__(kBlock, XPBD_PAIR_SOLVE_MIN_WAVES) k_pair_solv
 // that run all their substeps on one device: a halo exchange sits exactly at this seam.
 // (G lanes per body as in pair_solve_derive_body; with G = 8 the integrate + ground part runs redundantly on the eight
 // lanes and lane 0 stores.)
-template <bool TRACE, uint32_t G>
+template <bool TRACE, uint32_t G, bool MATERIALS>
 __global__ void __launch_bounds__(kBlock, XPBD_PAIR_SOLVE_MIN_WAVES) k_pair_solve_integrate_ground(
     BodyArrays b, ShapeTable shapes, double h, ContactBuffers c, BodySubset subset, double *__restrict__ next_rec,
     uint32_t *__restrict__ last_mask, uint32_t *__restrict__ trace_masks, uint32_t trace_row)
@@ -1114,7 +1132,7 @@ __global__ void __launch_bounds__(kBlock, XPBD_PAIR_SOLVE_MIN_WAVES) k_pair_solv
         {
             Vec3 past_pos;
             const PairBody self = load_pair_body(c, i, &past_pos, stage);
-            d = pair_solve_derive_body<G>(c, i, h, self, past_pos, sub, touching, points, stage);
+            d = pair_solve_derive_body<G, MATERIALS>(c, i, h, self, past_pos, sub, touching, points, stage);
             s = static_of(b, i, self.inv_mass, self.inv_inertia, self.com);
         }
         if (subset.export_rows && sub == 0)
@@ -1123,8 +1141,9 @@ __global__ void __launch_bounds__(kBlock, XPBD_PAIR_SOLVE_MIN_WAVES) k_pair_solv
         const uint32_t v0 = lds_off[sid];
         const double compliance = 1e-6 / (h * h);
         const SubstepFrames f = integrate_body(d, s, h);
-        const uint32_t mask = solve_ground(d, s, f, compliance, lds + 3 * v0, lds_off[sid + 1] - v0,
-                                       c.max_depenetration_speed > 0.0 ? c.max_depenetration_speed * h : 0.0);
+        const uint32_t mask = solve_ground<MATERIALS>(d, s, f, compliance, lds + 3 * v0, lds_off[sid + 1] - v0,
+                                                      c.max_depenetration_speed > 0.0 ? c.max_depenetration_speed * h : 0.0,
+                                                      MATERIALS ? ground_mu(c, i) : 0.0);
         if (sub == 0) {
             // everything the next kernel needs of this body is its record: no SoA state is written between the substeps of
             // a step call (the last substep's k_pair_solve_derive writes all 13 dynamic fields)
@@ -1378,12 +1397,18 @@ hipError_t launch_integrate_ground(const BodyArrays &b, const ShapeTable &s, dou
     if (items == 0)
         return hipSuccess;
     const size_t lds_bytes = (size_t)s.total_verts * 3 * sizeof(double) + (size_t)(s.n_shapes + 1) * sizeof(uint32_t);
-    if (trace_masks)
-        hipLaunchKernelGGL(k_integrate_ground<true>, dim3(blocks_for(items)), dim3(kBlock), lds_bytes, stream, b, s, h, c, subset,
-                           last_mask, trace_masks, trace_row);
+    auto launch = [&](auto trace, auto materials) {
+        hipLaunchKernelGGL((k_integrate_ground<decltype(trace)::value, decltype(materials)::value>), dim3(blocks_for(items)), dim3(kBlock),
+                           lds_bytes, stream, b, s, h, c, subset, last_mask, trace_masks, trace_row);
+    };
+    if (trace_masks && c.friction)
+        launch(std::true_type{}, std::true_type{});
+    else if (trace_masks)
+        launch(std::true_type{}, std::false_type{});
+    else if (c.friction)
+        launch(std::false_type{}, std::true_type{});
     else
-        hipLaunchKernelGGL(k_integrate_ground<false>, dim3(blocks_for(items)), dim3(kBlock), lds_bytes, stream, b, s, h, c, subset,
-                           last_mask, trace_masks, trace_row);
+        launch(std::false_type{}, std::false_type{});
     return hipGetLastError();
 }
 
@@ -1399,11 +1424,22 @@ hipError_t launch_pair_solve_derive(const BodyArrays &b, double *dyn_out, double
     const uint32_t items = subset.list ? subset.count : b.n;
     if (items == 0)
         return hipSuccess;
-    if (b.n <= kSmallWorld)
-        hipLaunchKernelGGL(k_pair_solve_derive<kMaxManifoldPoints>, dim3(blocks_for(items * kMaxManifoldPoints)), dim3(kBlock), 0, stream, b,
+    auto launch = [&](auto lanes, auto materials) {
+        constexpr uint32_t G = decltype(lanes)::value;
+        hipLaunchKernelGGL((k_pair_solve_derive<G, decltype(materials)::value>), dim3(blocks_for(items * G)), dim3(kBlock), 0, stream, b,
                            dyn_out, h, c, subset);
+    };
+    using Wide = std::integral_constant<uint32_t, kMaxManifoldPoints>;
+    using One = std::integral_constant<uint32_t, 1>;
+    const bool small = b.n <= kSmallWorld;
+    if (small && c.friction)
+        launch(Wide{}, std::true_type{});
+    else if (small)
+        launch(Wide{}, std::false_type{});
+    else if (c.friction)
+        launch(One{}, std::true_type{});
     else
-        hipLaunchKernelGGL(k_pair_solve_derive<1>, dim3(blocks_for(items)), dim3(kBlock), 0, stream, b, dyn_out, h, c, subset);
+        launch(One{}, std::false_type{});
     return hipGetLastError();
 }
 
@@ -1415,10 +1451,16 @@ hipError_t launch_pair_solve_integrate_ground(const BodyArrays &b, const ShapeTa
     if (items == 0)
         return hipSuccess;
     const size_t lds_bytes = (size_t)s.total_verts * 3 * sizeof(double) + (size_t)(s.n_shapes + 1) * sizeof(uint32_t);
-    auto launch = [&](auto trace, auto lanes) {
+    auto launch_form = [&](auto trace, auto lanes, auto materials) {
         constexpr uint32_t G = decltype(lanes)::value;
-        hipLaunchKernelGGL((k_pair_solve_integrate_ground<decltype(trace)::value, G>), dim3(blocks_for(items * G)), dim3(kBlock), lds_bytes,
-                           stream, b, s, h, c, subset, next_rec, last_mask, trace_masks, trace_row);
+        hipLaunchKernelGGL((k_pair_solve_integrate_ground<decltype(trace)::value, G, decltype(materials)::value>), dim3(blocks_for(items * G)),
+                           dim3(kBlock), lds_bytes, stream, b, s, h, c, subset, next_rec, last_mask, trace_masks, trace_row);
+    };
+    auto launch = [&](auto trace, auto lanes) { // contact materials: uniform over the launch, see pair_solve_derive_body
+        if (c.friction)
+            launch_form(trace, lanes, std::true_type{});
+        else
+            launch_form(trace, lanes, std::false_type{});
     };
     using Wide = std::integral_constant<uint32_t, kMaxManifoldPoints>;
     using One = std::integral_constant<uint32_t, 1>;

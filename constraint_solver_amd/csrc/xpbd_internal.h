@@ -98,6 +98,7 @@ struct HaloLists {
 struct xpbd_world;
 struct xpbd_joint;
 struct xpbd_joint_limit;
+struct xpbd_material;
 struct xpbd_ray;
 struct xpbd_ray_hit;
 struct xpbd_pair_contact;
@@ -152,4 +153,6 @@ int report_shard(xpbd_world *w, const uint8_t *dev_owned, const uint32_t *dev_gl
 // joint list (XPBD_E_INVALID with a message naming `who`).
 int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies);
 int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits);
+// ... and of the records of xpbd_world_set_materials: friction >= 0 (+inf allowed, NaN not), reserved == 0.
+int check_materials(const char *who, const xpbd_material *materials, uint32_t n);
 } // namespace xpbd

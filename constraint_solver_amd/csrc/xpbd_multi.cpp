@@ -43,6 +43,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <limits>
 #include <memory>
 #include <unordered_map>
 #include <unordered_set>
@@ -711,6 +712,8 @@ struct xpbd_multi_world {
     std::vector<xpbd_joint_limit> limits; // xpbd_multi_world_set_joint_limits: GLOBAL joint indices
     std::vector<xpbd_collision_filter> filters; // xpbd_multi_world_set_collision_filters: [n_global] or empty (none)
     uint32_t filter_flags = 0;
+    std::vector<xpbd_material> materials; // xpbd_multi_world_set_materials: [n_global] or empty (every body +inf)
+    double ground_friction = std::numeric_limits<double>::infinity();
     std::vector<uint8_t> owner;        // [n_global] as of the last plan
     std::vector<uint32_t> owned_count; // [n_ranks]
     uint64_t plans = 0, rollbacks = 0, migrated = 0, steps = 0, ns_enqueue = 0, ns_wait_broadphase = 0, ns_wait_frame = 0, ns_plan = 0;
@@ -1053,6 +1056,18 @@ int push_collision_filters(const xpbd_multi_world *mw, const Shard &s, const std
     return xpbd_world_set_collision_filters(s.world, local.data(), (uint32_t)local.size(), mw->filter_flags);
 }
 
+// ... and its contact materials: a ghost's coefficient enters the min of an owned-ghost contact, so every local slot gets its
+// body's.  Called after every plan (a body takes its coefficient along when it changes owner) and by the setter.
+int push_materials(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &local_ids)
+{
+    if (mw->materials.empty())
+        return xpbd_world_set_materials(s.world, nullptr, 0, mw->ground_friction);
+    std::vector<xpbd_material> local(local_ids.size());
+    for (size_t q = 0; q < local_ids.size(); ++q)
+        local[q] = mw->materials[local_ids[q]];
+    return xpbd_world_set_materials(s.world, local.data(), (uint32_t)local.size(), mw->ground_friction);
+}
+
 // The second half of every plan: the boundary lists of all ranks fix the rows of the per-substep all-gather, the records of
 // the bodies that change hands or are mirrored travel, and every shard's local world is re-packed on its device.  Collective.
 int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &plans, double edge, PlanTrace &trace)
@@ -1219,6 +1234,8 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
         if (int rc = push_joint_limits(mw, s))
             return rc;
         if (int rc = push_collision_filters(mw, s, local_ids))
+            return rc;
+        if (int rc = push_materials(mw, s, local_ids))
             return rc;
         XPBD_HIP_TRY(hipStreamSynchronize(s.stream));
         trace.lap("  joints");
@@ -2381,6 +2398,36 @@ try {
     return XPBD_OK;
 } XPBD_MULTI_ABI_CATCH
 
+int xpbd_multi_world_set_materials(xpbd_multi_world *mw, const xpbd_material *materials, uint32_t n_global, double ground_friction)
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_set_materials"));
+    if (!materials && n_global)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_materials: NULL materials with n_global = %u", n_global);
+    if (materials && n_global != mw->n_global)
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_materials: n_global = %u but the world holds %u bodies", n_global, mw->n_global);
+    if (!(ground_friction >= 0.0))
+        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_materials: ground_friction = %g (must be >= 0, +inf allowed)", ground_friction);
+    if (int rc = xpbd::check_materials("xpbd_multi_world_set_materials", materials, n_global))
+        return rc;
+    if (materials && n_global)
+        mw->materials.assign(materials, materials + n_global);
+    else
+        mw->materials.clear();
+    mw->ground_friction = ground_friction;
+    if (!mw->planned)
+        return XPBD_OK; // the plan hands them to the shards
+    for (Shard &s : mw->shards) {
+        int rc = bind(s);
+        if (rc == XPBD_OK)
+            rc = push_materials(mw, s, s.local_ids);
+        if (rc != XPBD_OK) { // (checked above: only a device failure gets here, and the shards disagree now)
+            mw->broken = true;
+            return set_error(rc, "%s -- the shards' materials disagree now: destroy this xpbd_multi_world", xpbd_last_error());
+        }
+    }
+    return XPBD_OK;
+} XPBD_MULTI_ABI_CATCH
+
 int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, const uint32_t *shape_id, uint32_t first_global, uint32_t n_bodies,
                             uint32_t n_global, const xpbd_joint *joints, uint32_t n_joints)
 try {
@@ -2405,6 +2452,8 @@ try {
     mw->limits.clear(); // limits name joints by index: a new upload invalidates them
     mw->filters.clear(); // filters name bodies by index
     mw->filter_flags = 0;
+    mw->materials.clear(); // and so do materials
+    mw->ground_friction = std::numeric_limits<double>::infinity();
     mw->planned = false;
     report_clear(mw);
     mw->cuts_valid = false; // the first plan is a full one

@@ -122,9 +122,13 @@ __device__ __forceinline__ uint32_t ground_mask(const Frame &cur, const double *
 // `limit` (> 0 only in XPBD_MODE_CONTACTS with xpbd_world_set_max_depenetration_speed; the pinned path passes the literal 0
 // and compiles to the reference's arithmetic alone): the length of a ground constraint's correction is limited to
 // max(0, limit - what the vertex has already moved towards its target in this substep), limit = speed * h.
+// MATERIALS (XPBD_MODE_CONTACTS with xpbd_world_set_materials only; the pinned path compiles the plain form, where `mu` is
+// never read and the reference's literal 1.0 stays a literal): Coulomb friction, mu = min(body, ground) -- the constraint
+// takes back at most mu * |correction| of the tangential slip (include/xpbd.h, "Contact MATERIALS").
+template <bool MATERIALS = false>
 __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_mass, const Mat3 &inv_inertia, const Vec3 &com,
                                              const Frame &cur, const Frame &past, double compliance, const double *verts,
-                                             uint32_t mask, double limit = 0.0)
+                                             uint32_t mask, double limit = 0.0, double mu = 0.0)
 {
     const Frame cur_inv = inverse(cur); // src/frame.rs:30-37, shared by every penetrating vertex
     for (uint32_t todo = mask; todo != 0; todo &= todo - 1) {
@@ -139,7 +143,14 @@ __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_ma
         const Vec3 delta = x - past * local; // src/frame.rs:42-43
         const Vec3 delta_tangential = delta - project_on(delta, correction);
         const Vec3 c0 = x;
-        const Vec3 c1 = target - 1.0 * delta_tangential;
+        double k = 1.0;
+        if (MATERIALS) {
+            const double bound = mu * length(correction);
+            const double len_t = length(delta_tangential);
+            if (bound < len_t) // (false for mu = +inf, a NaN bound, len_t = 0: the reference's contact)
+                k = bound / len_t;
+        }
+        const Vec3 c1 = target - k * delta_tangential;
 
         // solver::solve body, src/solver.rs:23-25 (distance == 0.0, src/collision.rs:30)
         const Vec3 difference = c1 - c0;                              // src/constraint.rs:13-15
@@ -170,11 +181,13 @@ __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_ma
 }
 
 // Both passes for the lane's own body.  Returns the contact mask.
+template <bool MATERIALS = false>
 __device__ __forceinline__ uint32_t solve_ground(BodyDynamic &d, const BodyStatic &s, const SubstepFrames &f,
-                                                 double compliance, const double *verts, uint32_t n_verts, double limit = 0.0)
+                                                 double compliance, const double *verts, uint32_t n_verts, double limit = 0.0,
+                                                 double mu = 0.0)
 {
     const uint32_t mask = ground_mask(f.cur, verts, n_verts);
-    solve_masked(d.pos, d.rot, s.inv_mass, s.inv_inertia, s.com, f.cur, f.past, compliance, verts, mask, limit);
+    solve_masked<MATERIALS>(d.pos, d.rot, s.inv_mass, s.inv_inertia, s.com, f.cur, f.past, compliance, verts, mask, limit, mu);
     return mask;
 }
 

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <limits>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -140,6 +141,11 @@ struct xpbd_world {
     DeviceBuffer ft_filters, cb_slot_filter;
     bool has_filters = false;
     uint32_t filter_flags = 0;
+    // contact materials (xpbd_world_set_materials): the friction coefficient of every body (has_materials: one of them, or the
+    // ground's, has been set -- the contact kernels then run their MATERIALS forms) and of the ground plane
+    DeviceBuffer mt_friction;
+    bool has_materials = false;
+    double ground_friction = std::numeric_limits<double>::infinity();
     // scene queries (xpbd_world_raycast*): scratch of one call, and the staging of the host variant's rays and hits
     DeviceBuffer q_rec, q_partials, q_grid, q_cell_start, q_cell_fill, q_items, q_scan, q_brute, q_rays, q_hits;
     // state history (xpbd_world_history_*): `history_length` slots of history_slot_bytes() in one growing block
@@ -209,6 +215,8 @@ struct xpbd_world {
         c.slot_filter = has_filters ? cb_slot_filter.as<uint32_t>() : nullptr;
         c.filter_jointed = (filter_flags & XPBD_FILTER_JOINTED) ? 1u : 0u;
         c.max_depenetration_speed = max_depenetration_speed;
+        c.friction = has_materials ? mt_friction.as<double>() : nullptr;
+        c.ground_friction = ground_friction;
         return c;
     }
 
@@ -827,6 +835,8 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     w->n_limits = 0;
     w->has_filters = false;
     w->filter_flags = 0;
+    w->has_materials = false;
+    w->ground_friction = std::numeric_limits<double>::infinity();
     w->history_length = 0;
     w->history_stepped.clear();
     w->n = n_new;
@@ -877,6 +887,17 @@ int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, u
                 if (!(len2 > 0.999 && len2 < 1.001))
                     return set_error(XPBD_E_INVALID, "%s: hinge %u needs unit axes (|axis|^2 = %g)", who, k, len2);
             }
+    }
+    return XPBD_OK;
+}
+
+int check_materials(const char *who, const xpbd_material *materials, uint32_t n)
+{
+    for (uint32_t i = 0; materials && i < n; ++i) {
+        if (!(materials[i].friction >= 0.0))
+            return set_error(XPBD_E_INVALID, "%s: materials[%u].friction = %g (must be >= 0, +inf allowed)", who, i, materials[i].friction);
+        if (!(materials[i].reserved == 0.0))
+            return set_error(XPBD_E_INVALID, "%s: materials[%u].reserved = %g (must be 0)", who, i, materials[i].reserved);
     }
     return XPBD_OK;
 }
@@ -1321,6 +1342,8 @@ try {
     w->n_limits = 0;
     w->has_filters = false;
     w->filter_flags = 0;
+    w->has_materials = false;
+    w->ground_friction = std::numeric_limits<double>::infinity();
     w->history_length = 0;
     w->history_stepped.clear();
     XPBD_HIP_TRY(w->stat.reserve((size_t)xpbd::kStatFields * stride * 8));
@@ -1671,6 +1694,42 @@ try {
     w->has_filters = false; // (a failed copy below leaves none rather than a torn table)
     XPBD_HIP_TRY(hipMemcpy(w->ft_filters.ptr, filters, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice));
     w->has_filters = true;
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_set_materials(xpbd_world *w, const xpbd_material *materials, uint32_t n, double ground_friction)
+try {
+    static_assert(sizeof(xpbd_material) == 16, "xpbd_material is {friction, reserved}");
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_materials: NULL world");
+    if (!materials && n)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_materials: NULL materials with n = %u", n);
+    if (materials && n != w->n)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_materials: n = %u but the world holds %u bodies", n, w->n);
+    if (!(ground_friction >= 0.0))
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_materials: ground_friction = %g (must be >= 0, +inf allowed)", ground_friction);
+    if (int rc = xpbd::check_materials("xpbd_world_set_materials", materials, n))
+        return rc;
+    if (int rc = bind_device(w))
+        return rc;
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present coefficients
+    const double inf = std::numeric_limits<double>::infinity();
+    if ((!materials || n == 0) && ground_friction == inf) { // the default: the contact kernels' plain forms
+        w->has_materials = false;
+        w->ground_friction = inf;
+        return XPBD_OK;
+    }
+    // (a finite ground coefficient alone: every body +inf, so that the kernels have one switch, the array)
+    std::vector<double> friction(std::max(w->n, 1u), inf);
+    for (uint32_t i = 0; materials && i < n; ++i)
+        friction[i] = materials[i].friction;
+    // staged in a buffer of its own and swapped in: a failed allocation or copy leaves the previous materials in place
+    DeviceBuffer fresh;
+    XPBD_HIP_TRY(fresh.reserve(friction.size() * sizeof(double)));
+    XPBD_HIP_TRY(hipMemcpy(fresh.ptr, friction.data(), friction.size() * sizeof(double), hipMemcpyHostToDevice));
+    w->mt_friction = std::move(fresh);
+    w->has_materials = true;
+    w->ground_friction = ground_friction;
     return XPBD_OK;
 } XPBD_ABI_CATCH
 

@@ -124,6 +124,21 @@ impl Default for XpbdCollisionFilter {
 
 pub const XPBD_FILTER_JOINTED: u32 = 1;
 
+/// EXTENSION: contact material of one body: Coulomb friction at the position level (a contact uses the smaller coefficient
+/// of its two sides; +inf, the default, is the reference's contact).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct XpbdMaterial {
+    pub friction: f64, // >= 0, may be +inf
+    pub reserved: f64, // must be 0 (room for restitution)
+}
+
+impl Default for XpbdMaterial {
+    fn default() -> Self {
+        XpbdMaterial { friction: f64::INFINITY, reserved: 0.0 }
+    }
+}
+
 /// EXTENSION: result of the GJK + EPA narrowphase for one pair.
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -330,6 +345,9 @@ extern "C" {
         -> c_int;
     pub fn xpbd_world_set_collision_filters(w: *mut XpbdWorld, filters: *const XpbdCollisionFilter, n: u32, flags: u32) -> c_int;
     pub fn xpbd_multi_world_set_collision_filters(mw: *mut XpbdMultiWorld, filters: *const XpbdCollisionFilter, n_global: u32, flags: u32)
+        -> c_int;
+    pub fn xpbd_world_set_materials(w: *mut XpbdWorld, materials: *const XpbdMaterial, n: u32, ground_friction: f64) -> c_int;
+    pub fn xpbd_multi_world_set_materials(mw: *mut XpbdMultiWorld, materials: *const XpbdMaterial, n_global: u32, ground_friction: f64)
         -> c_int;
     pub fn xpbd_world_raycast_masked(w: *mut XpbdWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32, hits: *mut XpbdRayHit)
         -> c_int;

@@ -22,6 +22,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -520,6 +521,12 @@ class BatchWorld {
     {
         check(xpbd_world_set_collision_filters(w_, filters.empty() ? nullptr : filters.data(), (uint32_t)filters.size(), flags));
     }
+    // contact materials, one per body (empty: every body +inf, the reference's contact), and the ground's friction coefficient
+    // (include/xpbd.h, "Contact MATERIALS").  Upload resets them.
+    void set_materials(const std::vector<xpbd_material> &materials, double ground_friction = std::numeric_limits<double>::infinity())
+    {
+        check(xpbd_world_set_materials(w_, materials.empty() ? nullptr : materials.data(), (uint32_t)materials.size(), ground_friction));
+    }
 
     // contact reports (include/xpbd.h, "Contact REPORTS"): the touching pairs of the current frame and the begin / end events
     void set_contact_report(bool enable) { check(xpbd_world_set_contact_report(w_, enable ? 1u : 0u)); }
@@ -639,6 +646,11 @@ class ShardedWorld {
     void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)
     {
         check(xpbd_multi_world_set_collision_filters(w_, filters.empty() ? nullptr : filters.data(), (uint32_t)filters.size(), flags));
+    }
+    // contact materials of the whole world, global body order (not collective); upload resets them
+    void set_materials(const std::vector<xpbd_material> &materials, double ground_friction = std::numeric_limits<double>::infinity())
+    {
+        check(xpbd_multi_world_set_materials(w_, materials.empty() ? nullptr : materials.data(), (uint32_t)materials.size(), ground_friction));
     }
     // contact reports of the whole world, global body indices; step() gathers them, these calls read every rank's copy
     void set_contact_report(bool enable) { check(xpbd_multi_world_set_contact_report(w_, enable ? 1u : 0u)); }

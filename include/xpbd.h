@@ -356,6 +356,40 @@ typedef struct xpbd_collision_filter {   /* 8 bytes */
 } xpbd_collision_filter;
 int  xpbd_world_set_collision_filters(xpbd_world *w, const xpbd_collision_filter *filters, uint32_t n, uint32_t flags);
 
+/* Contact MATERIALS (EXTENSION): Coulomb friction at the position level, per body and for the ground plane.
+ * Every body has a friction coefficient friction_b and the ground plane has one, ground_friction: doubles >= 0, +inf allowed
+ * and the default.  The coefficient of a contact is the smaller of its two sides' (exact, symmetric, no inf * 0):
+ *   mu = min(friction_inc, friction_ref)      for a body-body contact point,
+ *   mu = min(friction_b, ground_friction)     for a ground contact.
+ * Both contact kinds form `correction` (ground: target - x; pair: p_ref - p_inc) and `delta_tangential`, the tangential part
+ * of the contact point's (relative) motion during the substep.  The reference subtracts all of it from the contact's target
+ * (collision::ground: `target_position - 1.0 * delta_tangential_position`); with materials the literal 1.0 becomes k:
+ *   len_c = length(correction), len_t = length(delta_tangential)       (sqrt(dot(..)), as everywhere else)
+ *   bound = mu * len_c
+ *   k     = (bound < len_t) ? bound / len_t : 1.0
+ *   c1    = (target | p_ref) - k * delta_tangential
+ * and everything after c1 (difference, distance, direction, w, the depenetration limit -- whose `closing` uses delta and
+ * correction, not c1 --, lambda, the impulses, the Jacobi average) is unchanged.  This is Coulomb's cone on positions: len_c,
+ * the penetration the contact removes in this substep, stands for the normal impulse, and the contact may take back at most
+ * mu * len_c of the tangential slip; a contact that slips less sticks exactly as without materials (k = 1.0).  The comparison
+ * is false for mu = +inf, for len_c = 0 with mu = +inf (bound is NaN), for len_t = 0 and for any NaN: all keep k = 1.0.
+ * Hence a world without materials, or with every coefficient +inf, steps bit for bit as before.
+ * Where: XPBD_MODE_CONTACTS only, its ground contacts and its pair contacts under both narrowphases.  XPBD_MODE_FUSED /
+ * _PER_SUBSTEP (the pinned reference path) accept the call and ignore the values, as they ignore the depenetration limit.
+ * Joints, joint limits, filters, ray casts, contact reports (still the manifolds at the post-integrate poses) and history
+ * are not affected.
+ * Defaults: materials == NULL with n == 0 makes every body +inf (ground_friction still applies); otherwise n must equal
+ * xpbd_world_body_count (the multi world: n_global), the caller's order.
+ * Lifetime: xpbd_world_upload_bodies / xpbd_multi_world_upload reset every coefficient to +inf; xpbd_world_set_joints,
+ * history push / restore and mode changes leave the materials alone.
+ * XPBD_E_INVALID (the previous materials stay in place): a NULL world, materials == NULL with n > 0, materials != NULL with n
+ * not equal to the body count, a negative or NaN coefficient (ground_friction included), a nonzero `reserved`. */
+typedef struct xpbd_material {   /* 16 bytes */
+    double friction;             /* >= 0, may be +inf (the default: the reference's contact) */
+    double reserved;             /* must be 0 (room for restitution) */
+} xpbd_material;
+int  xpbd_world_set_materials(xpbd_world *w, const xpbd_material *materials, uint32_t n, double ground_friction);
+
 /* Split form of xpbd_world_step(w, dt, n) in XPBD_MODE_CONTACTS, for hosts that exchange halo
  * bodies between substeps (multi-GPU):  begin(dt); n x { substep(dt / n); <exchange> }.
  * begin runs the broadphase for the coming frame; substep is one substep of the pipeline. */
@@ -472,6 +506,10 @@ int  xpbd_multi_world_set_joint_limits(xpbd_multi_world *mw, const xpbd_joint_li
  * upload clears them.  Every shard gets the filters of the bodies it owns and mirrors.  Not collective. */
 int  xpbd_multi_world_set_collision_filters(xpbd_multi_world *mw, const xpbd_collision_filter *filters, uint32_t n_global,
                                             uint32_t flags);
+/* xpbd_world_set_materials for the whole world: n_global materials in GLOBAL body order, the same list on every rank; upload
+ * resets them.  Every shard gets the coefficients of the bodies it owns and mirrors (a ghost's coefficient enters the min),
+ * and they follow the bodies through re-plans and migration.  Not collective. */
+int  xpbd_multi_world_set_materials(xpbd_multi_world *mw, const xpbd_material *materials, uint32_t n_global, double ground_friction);
 /* xpbd_world_step(dt, substeps) of the whole sharded world; collective.  XPBD_E_HALO: see above (the frame was undone). */
 int  xpbd_multi_world_step(xpbd_multi_world *mw, double dt, uint32_t substeps);
 /* Re-cuts the shards from the bodies' current positions (re-balancing them), migrates bodies whose owner changed and
