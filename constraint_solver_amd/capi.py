@@ -57,7 +57,7 @@ ABI_SYMBOLS = [
     "xpbd_world_set_contact_report", "xpbd_world_contact_report_counts", "xpbd_world_download_pair_contacts",
     "xpbd_world_download_contact_events", "xpbd_multi_world_set_contact_report", "xpbd_multi_world_contact_report_counts",
     "xpbd_multi_world_download_pair_contacts", "xpbd_multi_world_download_contact_events",
-    "xpbd_world_set_materials", "xpbd_multi_world_set_materials",
+    "xpbd_world_set_materials", "xpbd_multi_world_set_materials", "xpbd_world_set_restitution",
 ]
 
 
@@ -277,6 +277,10 @@ def hip_lib():
             L.xpbd_multi_world_set_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
+        try:
+            L.xpbd_world_set_restitution.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
         _hip = L
     return _hip
 
@@ -460,6 +464,14 @@ class World:
         the default +inf (extension; XPBD_MODE_CONTACTS); ground_friction: the coefficient of the plane z = 0."""
         m = _materials(materials)
         _check(hip_lib().xpbd_world_set_materials(self._h, None if m is None else m.ctypes.data, 0 if m is None else m.size, ground_friction))
+
+    def set_restitution(self, restitution=None, ground_restitution=0.0, bounce_threshold=0.0):
+        """restitution: coefficients in [0, 1], one per body of the last upload, or None for the default 0 (extension;
+        XPBD_MODE_CONTACTS); ground_restitution: the coefficient of the plane z = 0; bounce_threshold: closing speed (m/s) below
+        which a contact does not bounce."""
+        e = None if restitution is None else np.ascontiguousarray(restitution, dtype=np.float64).reshape(-1)
+        _check(hip_lib().xpbd_world_set_restitution(self._h, None if e is None else e.ctypes.data, 0 if e is None else e.size,
+                                                    ground_restitution, bounce_threshold))
 
     def contacts_begin(self, dt):
         _check(hip_lib().xpbd_world_contacts_begin(self._h, dt))

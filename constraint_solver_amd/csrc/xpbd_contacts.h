@@ -80,6 +80,10 @@ struct ContactBuffers {
     // which never read these two).  (After the filters, for the same reason.)
     const double *friction;  // [n] Coulomb coefficient of every body, >= 0, may be +inf
     double ground_friction;  // ... and of the plane z = 0
+    // restitution (xpbd_world_set_restitution): NULL = off, no velocity pass is launched.  (Last again.)
+    const double *restitution; // [n] coefficient of every body, in [0, 1]
+    double ground_restitution; // ... and of the plane z = 0
+    double bounce_threshold;   // a contact bounces only when it closed faster than this at the start of the substep
 };
 
 // Which bodies a per-body kernel of the pipeline works on.  Default: all of them.  The multi-GPU world (xpbd_multi.cpp) runs
@@ -124,6 +128,13 @@ hipError_t launch_pair_solve_derive(const BodyArrays &b, double *dyn_out, double
 hipError_t launch_pair_solve_integrate_ground(const BodyArrays &b, const ShapeTable &s, double h, const ContactBuffers &c,
                                               double *next_rec, uint32_t *last_mask, uint32_t *trace_masks, uint32_t trace_row,
                                               hipStream_t stream, const BodySubset &subset = BodySubset());
+
+// Restitution, the velocity pass after derive (only when c.restitution is set): `post` holds the 13 dynamic fields after derive
+// (the dyn_out of launch_pair_solve_derive; NOT b.dyn), `start` velocity and angular velocity at the start of the substep
+// ([6][stride]: fields D_VEL.. of b.dyn before launch_integrate_ground), ground_masks the masks of launch_integrate_ground.
+// Every body's end-of-substep state (pose copied, velocities updated) goes to b.dyn, which no lane of the launch reads.
+hipError_t launch_restitution(const BodyArrays &b, const double *post, const double *start, const ShapeTable &s, const ContactBuffers &c,
+                              const uint32_t *ground_masks, hipStream_t stream);
 
 // Rigid::frame() of all bodies from the SoA state into the post-integrate frame of their records (all the diagnostic
 // narrowphase entry points need); and the StatRecords from the SoA static fields (after an upload).

@@ -146,6 +146,12 @@ struct xpbd_world {
     DeviceBuffer mt_friction;
     bool has_materials = false;
     double ground_friction = std::numeric_limits<double>::infinity();
+    // restitution (xpbd_world_set_restitution): the coefficient of every body and of the ground (has_restitution: one of them is
+    // > 0 -- the step then runs the unfused schedule with the velocity pass after derive; all zero runs what ran before), the
+    // start-of-substep velocities the pass reads ([6][stride]); dyn_alt holds the state after derive meanwhile
+    DeviceBuffer rs_restitution, rs_start;
+    bool has_restitution = false;
+    double ground_restitution = 0.0, bounce_threshold = 0.0;
     // scene queries (xpbd_world_raycast*): scratch of one call, and the staging of the host variant's rays and hits
     DeviceBuffer q_rec, q_partials, q_grid, q_cell_start, q_cell_fill, q_items, q_scan, q_brute, q_rays, q_hits;
     // state history (xpbd_world_history_*): `history_length` slots of history_slot_bytes() in one growing block
@@ -217,6 +223,9 @@ struct xpbd_world {
         c.max_depenetration_speed = max_depenetration_speed;
         c.friction = has_materials ? mt_friction.as<double>() : nullptr;
         c.ground_friction = ground_friction;
+        c.restitution = has_restitution ? rs_restitution.as<double>() : nullptr;
+        c.ground_restitution = ground_restitution;
+        c.bounce_threshold = bounce_threshold;
         return c;
     }
 
@@ -549,10 +558,23 @@ int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_ro
 {
     const xpbd::BodyArrays b = w->arrays();
     const xpbd::ContactBuffers c = w->contact_buffers();
+    if (c.restitution) {
+        // The velocity pass reads, of every body, the velocities the substep started from and the state after derive while it
+        // writes its own body's result: the former are copied aside first (fields D_VEL.. of the SoA state are one block), the
+        // latter goes to dyn_alt, and the pass writes the SoA state, which nobody reads by then.
+        XPBD_HIP_TRY(hipMemcpyAsync(w->rs_start.ptr, b.dyn + (size_t)xpbd::D_VEL * b.stride, (size_t)6 * b.stride * 8, hipMemcpyDeviceToDevice,
+                                    w->stream));
+    }
     XPBD_HIP_TRY(xpbd::launch_integrate_ground(b, w->shapes(), h, c, w->last_mask.as<uint32_t>(), trace, trace_row, w->stream));
     if (int rc = narrowphase_contacts(w, b, c))
         return rc;
-    XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream));
+    if (!c.restitution) {
+        XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream));
+        return XPBD_OK;
+    }
+    XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, w->dyn_alt.as<double>(), h, c, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_restitution(b, w->dyn_alt.as<double>(), w->rs_start.as<double>(), w->shapes(), c, w->last_mask.as<uint32_t>(),
+                                          w->stream));
     return XPBD_OK;
 }
 
@@ -569,6 +591,12 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         return rc;
     if (substeps == 0)
         return XPBD_OK;
+    if (w->has_restitution) { // the velocity pass sits where the fused kernel below has the next substep's integrate
+        for (uint32_t k = 0; k < substeps; ++k)
+            if (int rc = substep_contacts(w, h, trace, k))
+                return rc;
+        return XPBD_OK;
+    }
     XPBD_HIP_TRY(xpbd::launch_integrate_ground(w->arrays(), w->shapes(), h, w->contact_buffers(0), w->last_mask.as<uint32_t>(), trace, 0,
                                                w->stream));
     for (uint32_t k = 0; k < substeps; ++k) {
@@ -837,6 +865,8 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     w->filter_flags = 0;
     w->has_materials = false;
     w->ground_friction = std::numeric_limits<double>::infinity();
+    w->has_restitution = false;
+    w->ground_restitution = w->bounce_threshold = 0.0;
     w->history_length = 0;
     w->history_stepped.clear();
     w->n = n_new;
@@ -1344,6 +1374,8 @@ try {
     w->filter_flags = 0;
     w->has_materials = false;
     w->ground_friction = std::numeric_limits<double>::infinity();
+    w->has_restitution = false;
+    w->ground_restitution = w->bounce_threshold = 0.0;
     w->history_length = 0;
     w->history_stepped.clear();
     XPBD_HIP_TRY(w->stat.reserve((size_t)xpbd::kStatFields * stride * 8));
@@ -1730,6 +1762,50 @@ try {
     w->mt_friction = std::move(fresh);
     w->has_materials = true;
     w->ground_friction = ground_friction;
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_set_restitution(xpbd_world *w, const double *restitution, uint32_t n, double ground_restitution, double bounce_threshold)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: NULL world");
+    if (!restitution && n)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: NULL restitution with n = %u", n);
+    if (restitution && n != w->n)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: n = %u but the world holds %u bodies", n, w->n);
+    if (!(ground_restitution >= 0.0 && ground_restitution <= 1.0))
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: ground_restitution = %g (must be in [0, 1])", ground_restitution);
+    if (!(bounce_threshold >= 0.0 && bounce_threshold <= std::numeric_limits<double>::max()))
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: bounce_threshold = %g (must be >= 0 and finite)", bounce_threshold);
+    bool any = ground_restitution > 0.0;
+    for (uint32_t i = 0; restitution && i < n; ++i) {
+        if (!(restitution[i] >= 0.0 && restitution[i] <= 1.0))
+            return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: restitution[%u] = %g (must be in [0, 1])", i, restitution[i]);
+        any = any || restitution[i] > 0.0;
+    }
+    if (int rc = bind_device(w))
+        return rc;
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present coefficients
+    if (!any) { // nothing can bounce: the step runs what it ran before the call
+        w->has_restitution = false;
+        w->ground_restitution = 0.0;
+        w->bounce_threshold = bounce_threshold;
+        return XPBD_OK;
+    }
+    std::vector<double> values(std::max(w->n, 1u), 0.0);
+    for (uint32_t i = 0; restitution && i < n; ++i)
+        values[i] = restitution[i];
+    // staged in a buffer of its own and swapped in: a failed allocation or copy leaves the previous values in place
+    DeviceBuffer fresh;
+    XPBD_HIP_TRY(fresh.reserve(values.size() * sizeof(double)));
+    XPBD_HIP_TRY(hipMemcpy(fresh.ptr, values.data(), values.size() * sizeof(double), hipMemcpyHostToDevice));
+    const uint32_t stride = w->stride ? w->stride : 256u;
+    XPBD_HIP_TRY(w->dyn_alt.reserve((size_t)xpbd::kDynFields * stride * 8));
+    XPBD_HIP_TRY(w->rs_start.reserve((size_t)6 * stride * 8));
+    w->rs_restitution = std::move(fresh);
+    w->has_restitution = true;
+    w->ground_restitution = ground_restitution;
+    w->bounce_threshold = bounce_threshold;
     return XPBD_OK;
 } XPBD_ABI_CATCH
 

@@ -349,6 +349,8 @@ extern "C" {
     pub fn xpbd_world_set_materials(w: *mut XpbdWorld, materials: *const XpbdMaterial, n: u32, ground_friction: f64) -> c_int;
     pub fn xpbd_multi_world_set_materials(mw: *mut XpbdMultiWorld, materials: *const XpbdMaterial, n_global: u32, ground_friction: f64)
         -> c_int;
+    pub fn xpbd_world_set_restitution(w: *mut XpbdWorld, restitution: *const f64, n: u32, ground_restitution: f64, bounce_threshold: f64)
+        -> c_int;
     pub fn xpbd_world_raycast_masked(w: *mut XpbdWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32, hits: *mut XpbdRayHit)
         -> c_int;
     pub fn xpbd_world_raycast_masked_device(w: *mut XpbdWorld, dev_rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32,

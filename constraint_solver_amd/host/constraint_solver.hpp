@@ -527,6 +527,13 @@ class BatchWorld {
     {
         check(xpbd_world_set_materials(w_, materials.empty() ? nullptr : materials.data(), (uint32_t)materials.size(), ground_friction));
     }
+    // restitution, one coefficient in [0, 1] per body (empty: every body 0), the ground's, and the closing speed below which a
+    // contact does not bounce (include/xpbd.h, "RESTITUTION").  Upload resets them.
+    void set_restitution(const std::vector<double> &restitution, double ground_restitution = 0.0, double bounce_threshold = 0.0)
+    {
+        check(xpbd_world_set_restitution(w_, restitution.empty() ? nullptr : restitution.data(), (uint32_t)restitution.size(), ground_restitution,
+                                         bounce_threshold));
+    }
 
     // contact reports (include/xpbd.h, "Contact REPORTS"): the touching pairs of the current frame and the begin / end events
     void set_contact_report(bool enable) { check(xpbd_world_set_contact_report(w_, enable ? 1u : 0u)); }

@@ -4,7 +4,9 @@
 //
 //   xpbd_headless --bodies 262144 --substeps 20 --frames 10 [--scene boxes|mixed|boxes-drop|mixed-drop|stacks]
 //                 [--seed 1] [--mode fused|substep|contacts] [--device 0] [--dump poses.bin]
-//                 [--history] [--rewind K] [--shards N]
+//                 [--history] [--rewind K] [--shards N] [--friction MU] [--restitution E]
+// --friction MU, --restitution E (with --mode contacts, not with --shards): one Coulomb friction coefficient (>= 0) / one
+// restitution coefficient (in [0, 1]) for every body and the ground.
 // --shards N (with --mode contacts): the world sharded over N GPUs driven by this one process (world::ShardedWorld over
 // xpbd_multi_world_*: devices --device .. --device + N - 1 over RCCL; with fewer visible devices all shards share --device and
 // exchange by peer copies -- the one-GPU rehearsal).  The dump then equals the unsharded run's, byte for byte.
@@ -24,12 +26,18 @@ int main(int argc, char **argv)
 {
     uint32_t bodies = 4096, substeps = 20, frames = 10, warmup = 2, shards = 0;
     bool history = false;
+    double friction = -1.0, restitution = -1.0; // < 0: not given
     long rewind = -1;
     uint64_t seed = 1;
     int device = 0;
     scene::Kind kind = scene::BOXES;
     uint32_t mode = XPBD_MODE_FUSED;
     std::string dump;
+    auto number = [](const char *text, double &out) { // the whole of `text` is one number
+        char *end = nullptr;
+        out = std::strtod(text, &end);
+        return end != text && *end == '\0';
+    };
     for (int i = 1; i < argc; ++i) {
         auto val = [&](const char *flag) -> const char * {
             if (std::strcmp(argv[i], flag) != 0)
@@ -51,11 +59,26 @@ int main(int argc, char **argv)
         else if (const char *v = val("--dump")) dump = v;
         else if (const char *v = val("--rewind")) rewind = std::strtol(v, nullptr, 10);
         else if (const char *v = val("--shards")) shards = (uint32_t)std::strtoul(v, nullptr, 10);
+        else if (const char *v = val("--friction")) {
+            if (!number(v, friction) || !(friction >= 0.0)) {
+                std::fprintf(stderr, "--friction %s: must be a number >= 0\n", v);
+                return 2;
+            }
+        } else if (const char *v = val("--restitution")) {
+            if (!number(v, restitution) || !(restitution >= 0.0 && restitution <= 1.0)) {
+                std::fprintf(stderr, "--restitution %s: must be a number in [0, 1]\n", v);
+                return 2;
+            }
+        }
         else if (std::strcmp(argv[i], "--history") == 0) history = true;
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
             return 2;
         }
+    }
+    if ((friction >= 0.0 || restitution >= 0.0) && (mode != XPBD_MODE_CONTACTS || shards)) {
+        std::fprintf(stderr, "--friction and --restitution need --mode contacts and no --shards\n");
+        return 2;
     }
     try {
         std::vector<rigid::Rigid> state;
@@ -108,6 +131,10 @@ int main(int argc, char **argv)
         else
             w.set_shapes(scene::shapes_of(kind));
         w.upload(state, shape_id);
+        if (friction >= 0.0)
+            w.set_materials(std::vector<xpbd_material>(state.size(), xpbd_material{friction, 0.0}), friction);
+        if (restitution >= 0.0)
+            w.set_restitution(std::vector<double>(state.size(), restitution), restitution);
 
         if (history)
             warmup = 0; // state 0 of the timeline is the initial world

@@ -390,6 +390,70 @@ typedef struct xpbd_material {   /* 16 bytes */
 } xpbd_material;
 int  xpbd_world_set_materials(xpbd_world *w, const xpbd_material *materials, uint32_t n, double ground_friction);
 
+/* RESTITUTION (EXTENSION): bouncing contacts, a velocity pass after derive.
+ * Every body has a restitution coefficient restitution_b and the ground plane has one, ground_restitution: doubles in [0, 1],
+ * 0 the default; bounce_threshold >= 0 (m/s, finite, default 0) is the closing speed below which a contact does not bounce.
+ * The coefficient of a contact is the larger of its two sides', written as a compare-and-select:
+ *   e = (e_inc < e_ref) ? e_ref : e_inc             for a body-body contact point,
+ *   e = (e_b < ground_restitution) ? ground_restitution : e_b      for a ground contact.
+ * Where: XPBD_MODE_CONTACTS only, as stage 6 of every substep, after Rigid::derive (stage 5 of oracle/xpbd_pairs_oracle.h),
+ * under both narrowphases, on the manifolds and the ground contact mask of THIS substep (both formed at the post-integrate
+ * poses).  xpbd_world_step and xpbd_world_contacts_substep run it alike.
+ * Notation.  v0, w0: a body's velocity and angular velocity at the start of the substep (before integrate); x, q, v, w: its
+ * position, rotation and velocities after derive; c = x + center_of_mass.  For a world point p of a body, with arm = p - c:
+ *   u(p)  = v  + cross(w,  arm)            u0(p) = v0 + cross(w0, arm)
+ *   W(p, n) = inverse_mass + dot(inverse_inertia * a, a),  a = conjugate(q) * cross(arm, n)      (inverse_resistance at x, q)
+ * and an impulse P at p changes the body as the position pass applies a correction:
+ *   v += P * inverse_mass            w += cross(inverse_inertia * arm, P)
+ * dot(a, b) is (a.x * b.x + a.y * b.y) + a.z * b.z and length is sqrt(dot(..)), as everywhere else.
+ * Pair contact point, with p_inc and p_ref exactly as the position pass forms them (a face contact: the stored point on the
+ * incident body and its projection onto the reference plane; the one-point contact: its two points):
+ *   n      = the reference plane's normal (face contact), or d * (1.0 / length(d)) with d = p_ref - p_inc (one-point contact;
+ *            no entry when length(d) == 0).  Both point out of the reference body.
+ * One MANIFOLD is solved by sequential impulses on copies (v_inc, w_inc, v_ref, w_ref) of its two bodies' post-derive
+ * velocities; every point k keeps total_k, the impulse it has applied so far, which starts at 0 and is never negative.
+ * XPBD_RESTITUTION_SWEEPS passes over the points in point order; a visit of point k computes, with u taken from the copies as
+ * they are at that moment and u0 from v0, w0:
+ *   vn     = dot(n, u_inc(p_inc) - u_ref(p_ref))          vn0 = dot(n, u0_inc(p_inc) - u0_ref(p_ref))
+ *   Wsum   = W_inc(p_inc, n) + W_ref(p_ref, n)
+ *   the visit does nothing unless  e > 0 && vn0 < -bounce_threshold && Wsum > 0  (two immovable bodies: never);
+ *   wanted = total_k + ((-e) * vn0 - vn) / Wsum           (no compliance);   if (!(wanted > 0)) wanted = 0
+ *   lambda = wanted - total_k;   nothing more when lambda == 0;   total_k = wanted
+ *   P = lambda * n on the incident copy at p_inc, (-lambda) * n on the reference copy at p_ref, applied at once.
+ * So a point pushes (lambda > 0) while it closes faster than (-e) * vn0 allows and gives back (lambda < 0) at most what it has
+ * pushed: the manifold converges to the impulses that make every pushing point leave at exactly e times its closing speed.
+ * (An average over the points, as the position pass forms it, delivers a quarter of a four-point face contact per substep and
+ * never reaches e; a plain sum overshoots when the points are close together.)
+ * The manifold's entry for a body is (dv, dw) = (v_copy - v, w_copy - w) of that body's copy after the last pass; a manifold
+ * in which no visit applied an impulse makes no entry.
+ * Jacobi over the manifolds, as the position pass over its points: every body reads the post-derive state of all bodies, adds
+ * the entries of its touching neighbours in neighbour index order, each sum starting from 0, and then v += dv / count,
+ * w += dw / count (count = number of entries as a double; nothing happens when it is 0).  Both bodies of a pair compute the
+ * same sequence on the same values, so they apply opposite impulses of the same size.
+ * Ground, after the body's pair entries have been applied, sequentially per body as collision::ground: for every set bit of
+ * the substep's ground contact mask in ascending vertex order, p = frame * vertex with frame the body's Rigid::frame() at
+ * (x, q), n = (0, 0, 1), vn = dot(n, u(p)), vn0 = dot(n, u0(p)) with the body's CURRENT v, w (v0, w0 never change),
+ * Wsum = W(p, n); the vertex makes an entry iff  e > 0 && vn0 < -bounce_threshold && Wsum > 0 && vn < (-e) * vn0, with
+ * lambda = ((-e) * vn0 - vn) / Wsum and P = lambda * n applied at once, so that the next vertex sees the updated velocities
+ * (one pass, no give-back).
+ * The impulse of a contact point is never attractive.  A contact with e == 0 makes no entry and does not count, so a world without
+ * restitution, or with every coefficient 0, steps bit for bit as before (it runs the same kernels in the same order), and so
+ * does every joint, limit, filter, report, ray cast and history call.  Positions and rotations are not touched by the pass.
+ * Defaults: restitution == NULL with n == 0 sets every body to 0 (ground_restitution and bounce_threshold still apply);
+ * otherwise n must equal xpbd_world_body_count, the caller's order.
+ * Lifetime: xpbd_world_upload_bodies resets every coefficient and the threshold to 0; xpbd_world_set_joints,
+ * xpbd_world_set_materials, history push / restore and mode changes leave them alone.  XPBD_MODE_FUSED / _PER_SUBSTEP accept
+ * the call and ignore the values.
+ * XPBD_E_INVALID (the previous values stay in place): a NULL world, restitution == NULL with n > 0, restitution != NULL with
+ * n not equal to the body count, a coefficient outside [0, 1] or NaN (ground_restitution included), a negative, infinite or
+ * NaN bounce_threshold.
+ * Not here: xpbd_multi_world_* has no such call (a shard steps its ghosts without the ghosts' own neighbours, so a ghost's
+ * post-derive velocity is not its owner's: the pass needs a second exchange per substep); joints and joint limits do not
+ * bounce; xpbd_material is unchanged. */
+#define XPBD_RESTITUTION_SWEEPS 4u   /* passes over the points of one manifold */
+int  xpbd_world_set_restitution(xpbd_world *w, const double *restitution, uint32_t n, double ground_restitution,
+                                double bounce_threshold);
+
 /* Split form of xpbd_world_step(w, dt, n) in XPBD_MODE_CONTACTS, for hosts that exchange halo
  * bodies between substeps (multi-GPU):  begin(dt); n x { substep(dt / n); <exchange> }.
  * begin runs the broadphase for the coming frame; substep is one substep of the pipeline. */
