@@ -153,6 +153,9 @@ int report_shard(xpbd_world *w, const uint8_t *dev_owned, const uint32_t *dev_gl
 // joint list (XPBD_E_INVALID with a message naming `who`).
 int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies);
 int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits);
+// ... of a per-body array (`what`) handed to a world of n_bodies bodies: NULL only with n == 0 (the default), else n == n_bodies.
+// `count`: what the caller's interface calls n.
+int check_per_body(const char *who, const char *what, const void *values, uint32_t n, uint32_t n_bodies, const char *count = "n");
 // ... and of the records of xpbd_world_set_materials: friction >= 0 (+inf allowed, NaN not), reserved == 0.
 int check_materials(const char *who, const xpbd_material *materials, uint32_t n);
 } // namespace xpbd

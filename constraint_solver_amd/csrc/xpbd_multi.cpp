@@ -1029,8 +1029,23 @@ int gather_world_keys(xpbd_multi_world *mw, LocalStatus &st, const std::vector<s
     return XPBD_OK;
 }
 
-// The world's joint limits on the joints of shard s, re-indexed to the shard's joint numbering (the caller's order kept).
-int push_joint_limits(const xpbd_multi_world *mw, const Shard &s)
+// ---- body-indexed settings: the world's copy (global indices) handed to a shard (local slots) -------------------------------
+// Called for every shard after every plan (a body takes its settings along when it changes owner) and by the setters.
+// local_ids: global id of every local slot, owned bodies and ghosts alike -- an owned-ghost pair is decided on this shard, and a
+// ghost's coefficient enters the min of an owned-ghost contact.
+using PushSetting = int (*)(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &local_ids);
+
+// The rows of a per-body table of the world at the local slots; an empty table (the default) stays empty.
+template <class T> std::vector<T> local_rows(const std::vector<T> &global, const std::vector<uint32_t> &local_ids)
+{
+    std::vector<T> local(global.empty() ? 0 : local_ids.size());
+    for (size_t q = 0; q < local.size(); ++q)
+        local[q] = global[local_ids[q]];
+    return local;
+}
+
+// The joint limits on the joints of shard s, re-indexed to the shard's joint numbering (the caller's order kept).
+int push_joint_limits(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &)
 {
     std::vector<xpbd_joint_limit> local;
     for (const xpbd_joint_limit &l : mw->limits) {
@@ -1044,28 +1059,42 @@ int push_joint_limits(const xpbd_multi_world *mw, const Shard &s)
     return xpbd_world_set_joint_limits(s.world, local.data(), (uint32_t)local.size());
 }
 
-// The world's collision filters on the bodies of shard s (local_ids: global id of every local slot, owned bodies and ghosts
-// alike -- an owned-ghost pair is decided on this shard).
 int push_collision_filters(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &local_ids)
 {
-    if (mw->filters.empty())
-        return xpbd_world_set_collision_filters(s.world, nullptr, 0, mw->filter_flags);
-    std::vector<xpbd_collision_filter> local(local_ids.size());
-    for (size_t q = 0; q < local_ids.size(); ++q)
-        local[q] = mw->filters[local_ids[q]];
-    return xpbd_world_set_collision_filters(s.world, local.data(), (uint32_t)local.size(), mw->filter_flags);
+    const std::vector<xpbd_collision_filter> local = local_rows(mw->filters, local_ids);
+    return xpbd_world_set_collision_filters(s.world, local.empty() ? nullptr : local.data(), (uint32_t)local.size(), mw->filter_flags);
 }
 
-// ... and its contact materials: a ghost's coefficient enters the min of an owned-ghost contact, so every local slot gets its
-// body's.  Called after every plan (a body takes its coefficient along when it changes owner) and by the setter.
 int push_materials(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &local_ids)
 {
-    if (mw->materials.empty())
-        return xpbd_world_set_materials(s.world, nullptr, 0, mw->ground_friction);
-    std::vector<xpbd_material> local(local_ids.size());
-    for (size_t q = 0; q < local_ids.size(); ++q)
-        local[q] = mw->materials[local_ids[q]];
-    return xpbd_world_set_materials(s.world, local.data(), (uint32_t)local.size(), mw->ground_friction);
+    const std::vector<xpbd_material> local = local_rows(mw->materials, local_ids);
+    return xpbd_world_set_materials(s.world, local.empty() ? nullptr : local.data(), (uint32_t)local.size(), mw->ground_friction);
+}
+
+// Every body-indexed setting of the world on shard s (its joints are set: the limits name them).  A new setting is added here.
+int push_body_settings(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &local_ids)
+{
+    for (PushSetting push : {push_joint_limits, push_collision_filters, push_materials})
+        XPBD_TRY(push(mw, s, local_ids));
+    return XPBD_OK;
+}
+
+// The tail of a setter: the checked and recorded setting goes to every shard of a planned world (the plan hands it over
+// otherwise).  Only a device failure fails here, and the shards disagree then.
+int push_to_shards(xpbd_multi_world *mw, PushSetting push, const char *what)
+{
+    if (!mw->planned)
+        return XPBD_OK;
+    for (Shard &s : mw->shards) {
+        int rc = bind(s);
+        if (rc == XPBD_OK)
+            rc = push(mw, s, s.local_ids);
+        if (rc != XPBD_OK) {
+            mw->broken = true;
+            return set_error(rc, "%s -- the shards' %s disagree now: destroy this xpbd_multi_world", xpbd_last_error(), what);
+        }
+    }
+    return XPBD_OK;
 }
 
 // The second half of every plan: the boundary lists of all ranks fix the rows of the per-substep all-gather, the records of
@@ -1231,12 +1260,7 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
         if (int rc = xpbd_world_set_joints(s.world, local_joints.data(), (uint32_t)local_joints.size()))
             return rc;
         s.joint_ids = std::move(joint_ids);
-        if (int rc = push_joint_limits(mw, s))
-            return rc;
-        if (int rc = push_collision_filters(mw, s, local_ids))
-            return rc;
-        if (int rc = push_materials(mw, s, local_ids))
-            return rc;
+        XPBD_TRY(push_body_settings(mw, s, local_ids));
         XPBD_HIP_TRY(hipStreamSynchronize(s.stream));
         trace.lap("  joints");
         XPBD_TRY(upload_vector(s.boundary_slots, boundary_slots, s.stream));
@@ -2359,24 +2383,13 @@ try {
     if (int rc = xpbd::check_joint_limits("xpbd_multi_world_set_joint_limits", mw->joints.data(), (uint32_t)mw->joints.size(), limits, n_limits))
         return rc;
     mw->limits.assign(limits, limits + n_limits);
-    if (!mw->planned)
-        return XPBD_OK; // the plan hands them to the shards
-    for (Shard &s : mw->shards)
-        if (int rc = push_joint_limits(mw, s)) { // (checked above: only a device failure gets here, and the shards disagree now)
-            mw->broken = true;
-            return set_error(rc, "%s -- the shards' joint limits disagree now: destroy this xpbd_multi_world", xpbd_last_error());
-        }
-    return XPBD_OK;
+    return push_to_shards(mw, push_joint_limits, "joint limits");
 } XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_set_collision_filters(xpbd_multi_world *mw, const xpbd_collision_filter *filters, uint32_t n_global, uint32_t flags)
 try {
     XPBD_TRY(check_usable(mw, "xpbd_multi_world_set_collision_filters"));
-    if (!filters && n_global)
-        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_collision_filters: NULL filters with n_global = %u", n_global);
-    if (filters && n_global != mw->n_global)
-        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_collision_filters: n_global = %u but the world holds %u bodies", n_global,
-                         mw->n_global);
+    XPBD_TRY(xpbd::check_per_body("xpbd_multi_world_set_collision_filters", "filters", filters, n_global, mw->n_global, "n_global"));
     if (flags & ~XPBD_FILTER_JOINTED)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_collision_filters: unknown flags 0x%x", flags);
     if (filters && n_global)
@@ -2384,27 +2397,13 @@ try {
     else
         mw->filters.clear();
     mw->filter_flags = flags;
-    if (!mw->planned)
-        return XPBD_OK; // the plan hands them to the shards
-    for (Shard &s : mw->shards) {
-        int rc = bind(s);
-        if (rc == XPBD_OK)
-            rc = push_collision_filters(mw, s, s.local_ids);
-        if (rc != XPBD_OK) { // (checked above: only a device failure gets here, and the shards disagree now)
-            mw->broken = true;
-            return set_error(rc, "%s -- the shards' collision filters disagree now: destroy this xpbd_multi_world", xpbd_last_error());
-        }
-    }
-    return XPBD_OK;
+    return push_to_shards(mw, push_collision_filters, "collision filters");
 } XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_set_materials(xpbd_multi_world *mw, const xpbd_material *materials, uint32_t n_global, double ground_friction)
 try {
     XPBD_TRY(check_usable(mw, "xpbd_multi_world_set_materials"));
-    if (!materials && n_global)
-        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_materials: NULL materials with n_global = %u", n_global);
-    if (materials && n_global != mw->n_global)
-        return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_materials: n_global = %u but the world holds %u bodies", n_global, mw->n_global);
+    XPBD_TRY(xpbd::check_per_body("xpbd_multi_world_set_materials", "materials", materials, n_global, mw->n_global, "n_global"));
     if (!(ground_friction >= 0.0))
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_materials: ground_friction = %g (must be >= 0, +inf allowed)", ground_friction);
     if (int rc = xpbd::check_materials("xpbd_multi_world_set_materials", materials, n_global))
@@ -2414,18 +2413,7 @@ try {
     else
         mw->materials.clear();
     mw->ground_friction = ground_friction;
-    if (!mw->planned)
-        return XPBD_OK; // the plan hands them to the shards
-    for (Shard &s : mw->shards) {
-        int rc = bind(s);
-        if (rc == XPBD_OK)
-            rc = push_materials(mw, s, s.local_ids);
-        if (rc != XPBD_OK) { // (checked above: only a device failure gets here, and the shards disagree now)
-            mw->broken = true;
-            return set_error(rc, "%s -- the shards' materials disagree now: destroy this xpbd_multi_world", xpbd_last_error());
-        }
-    }
-    return XPBD_OK;
+    return push_to_shards(mw, push_materials, "materials");
 } XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, const uint32_t *shape_id, uint32_t first_global, uint32_t n_bodies,

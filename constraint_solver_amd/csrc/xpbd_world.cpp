@@ -132,26 +132,37 @@ struct xpbd_world {
     // state at the start of a frame (xpbd::frame_snapshot_save / _restore): the 13 dynamic fields and the contact masks
     DeviceBuffer frame_snapshot;
     bool frame_snapshot_valid = false, frame_snapshot_stepped = false;
-    DeviceBuffer jt_joints, jt_off, jt_list;
-    uint32_t n_joints = 0;
-    std::vector<xpbd_joint> joints_host; // the joints of the last set_joints: what xpbd_world_set_joint_limits checks against
-    DeviceBuffer jt_limits, jt_limit_off;
-    uint32_t n_limits = 0;
-    // collision filters (xpbd_world_set_collision_filters): group, mask per body (has_filters), XPBD_FILTER_* flags
+    // Body-indexed settings: each names bodies (or the joints between them) by index, so a new set of bodies clears all four
+    // (adopt_body_count).  Plain values whose clear() restores the defaults; their device tables stay allocated beside them.
+    struct Joints { // xpbd_world_set_joints, xpbd_world_set_joint_limits (limits name joints by index: new joints drop them)
+        uint32_t n = 0, n_limits = 0;
+        std::vector<xpbd_joint> host; // the joints of the last set_joints: what xpbd_world_set_joint_limits checks against
+        void clear() { *this = Joints{}; }
+    } joints;
+    DeviceBuffer jt_joints, jt_off, jt_list, jt_limits, jt_limit_off;
+    struct Filters { // xpbd_world_set_collision_filters: group, mask per body (on), XPBD_FILTER_* flags
+        bool on = false;
+        uint32_t flags = 0;
+        void clear() { *this = Filters{}; }
+    } filters;
     DeviceBuffer ft_filters, cb_slot_filter;
-    bool has_filters = false;
-    uint32_t filter_flags = 0;
-    // contact materials (xpbd_world_set_materials): the friction coefficient of every body (has_materials: one of them, or the
-    // ground's, has been set -- the contact kernels then run their MATERIALS forms) and of the ground plane
+    // xpbd_world_set_materials: the friction coefficient of every body (on: one of them, or the ground's, has been set -- the
+    // contact kernels then run their MATERIALS forms) and of the ground plane
+    struct Materials {
+        bool on = false;
+        double ground_friction = std::numeric_limits<double>::infinity();
+        void clear() { *this = Materials{}; }
+    } materials;
     DeviceBuffer mt_friction;
-    bool has_materials = false;
-    double ground_friction = std::numeric_limits<double>::infinity();
-    // restitution (xpbd_world_set_restitution): the coefficient of every body and of the ground (has_restitution: one of them is
-    // > 0 -- the step then runs the unfused schedule with the velocity pass after derive; all zero runs what ran before), the
-    // start-of-substep velocities the pass reads ([6][stride]); dyn_alt holds the state after derive meanwhile
+    // xpbd_world_set_restitution: the coefficient of every body and of the ground (on: one of them is > 0 -- the step then runs
+    // the unfused schedule with the velocity pass after derive; all zero runs what ran before), the start-of-substep velocities
+    // the pass reads ([6][stride]); dyn_alt holds the state after derive meanwhile
+    struct Restitution {
+        bool on = false;
+        double ground = 0.0, bounce_threshold = 0.0;
+        void clear() { *this = Restitution{}; }
+    } restitution;
     DeviceBuffer rs_restitution, rs_start;
-    bool has_restitution = false;
-    double ground_restitution = 0.0, bounce_threshold = 0.0;
     // scene queries (xpbd_world_raycast*): scratch of one call, and the staging of the host variant's rays and hits
     DeviceBuffer q_rec, q_partials, q_grid, q_cell_start, q_cell_fill, q_items, q_scan, q_brute, q_rays, q_hits;
     // state history (xpbd_world_history_*): `history_length` slots of history_slot_bytes() in one growing block
@@ -212,20 +223,20 @@ struct xpbd_world {
         c.pair_codes = cb_pair_codes.as<uint8_t>();
         c.stats = cb_stats.as<unsigned long long>();
         c.scan_scratch = cb_scan.as<uint32_t>();
-        c.joints = n_joints ? jt_joints.as<xpbd::Joint>() : nullptr;
-        c.joint_off = n_joints ? jt_off.as<uint32_t>() : nullptr;
-        c.joint_list = n_joints ? jt_list.as<uint32_t>() : nullptr;
-        c.limits = n_limits ? jt_limits.as<xpbd::JointLimit>() : nullptr;
-        c.limit_off = n_limits ? jt_limit_off.as<uint32_t>() : nullptr;
-        c.filter = has_filters ? ft_filters.as<uint2>() : nullptr;
-        c.slot_filter = has_filters ? cb_slot_filter.as<uint32_t>() : nullptr;
-        c.filter_jointed = (filter_flags & XPBD_FILTER_JOINTED) ? 1u : 0u;
+        c.joints = joints.n ? jt_joints.as<xpbd::Joint>() : nullptr;
+        c.joint_off = joints.n ? jt_off.as<uint32_t>() : nullptr;
+        c.joint_list = joints.n ? jt_list.as<uint32_t>() : nullptr;
+        c.limits = joints.n_limits ? jt_limits.as<xpbd::JointLimit>() : nullptr;
+        c.limit_off = joints.n_limits ? jt_limit_off.as<uint32_t>() : nullptr;
+        c.filter = filters.on ? ft_filters.as<uint2>() : nullptr;
+        c.slot_filter = filters.on ? cb_slot_filter.as<uint32_t>() : nullptr;
+        c.filter_jointed = (filters.flags & XPBD_FILTER_JOINTED) ? 1u : 0u;
         c.max_depenetration_speed = max_depenetration_speed;
-        c.friction = has_materials ? mt_friction.as<double>() : nullptr;
-        c.ground_friction = ground_friction;
-        c.restitution = has_restitution ? rs_restitution.as<double>() : nullptr;
-        c.ground_restitution = ground_restitution;
-        c.bounce_threshold = bounce_threshold;
+        c.friction = materials.on ? mt_friction.as<double>() : nullptr;
+        c.ground_friction = materials.ground_friction;
+        c.restitution = restitution.on ? rs_restitution.as<double>() : nullptr;
+        c.ground_restitution = restitution.ground;
+        c.bounce_threshold = restitution.bounce_threshold;
         return c;
     }
 
@@ -409,7 +420,7 @@ int build_neighbours_enqueue(xpbd_world *w, double dt)
     XPBD_HIP_TRY(w->cb_items_unsorted.reserve((size_t)st * 4));
     XPBD_HIP_TRY(w->cb_slot_sphere.reserve((size_t)4 * st * 8));
     XPBD_HIP_TRY(w->cb_slot_cell.reserve((size_t)3 * st * 4));
-    if (w->has_filters)
+    if (w->filters.on)
         XPBD_HIP_TRY(w->cb_slot_filter.reserve((size_t)2 * st * 4));
     XPBD_HIP_TRY(w->cb_nbr_off.reserve((size_t)(st + 1) * 4));
     XPBD_HIP_TRY(w->cb_pair_first.reserve((size_t)(st + 1) * 4));
@@ -591,7 +602,7 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         return rc;
     if (substeps == 0)
         return XPBD_OK;
-    if (w->has_restitution) { // the velocity pass sits where the fused kernel below has the next substep's integrate
+    if (w->restitution.on) { // the velocity pass sits where the fused kernel below has the next substep's integrate
         for (uint32_t k = 0; k < substeps; ++k)
             if (int rc = substep_contacts(w, h, trace, k))
                 return rc;
@@ -770,6 +781,48 @@ void absorb_stat_record(xpbd_world *w, const xpbd_rigid &body, uint32_t sid)
         w->stat_shared = false;
     }
 }
+
+// The world takes a new set of n_new bodies (xpbd_world_upload_bodies, xpbd::repack_bodies; device bound, stream idle): room for
+// them, and everything that named the old bodies by index or was derived from them is dropped -- the body-indexed settings,
+// neighbour lists, history, trace, frame snapshot and contact report.  The callers fill the arrays and see to the per-shape mass
+// properties (stat_shape_*), which one resets and the other keeps.
+int adopt_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id)
+{
+    const uint32_t stride = round_up(n_new ? n_new : 1, 256);
+    XPBD_HIP_TRY(w->dyn.reserve((size_t)xpbd::kDynFields * stride * 8));
+    w->have_neighbours = false;
+    w->joints.clear();
+    w->filters.clear();
+    w->materials.clear();
+    w->restitution.clear();
+    w->history_length = 0;
+    w->history_stepped.clear();
+    XPBD_HIP_TRY(w->stat.reserve((size_t)xpbd::kStatFields * stride * 8));
+    XPBD_HIP_TRY(w->shape_id.reserve((size_t)stride * 4));
+    XPBD_HIP_TRY(w->last_mask.reserve((size_t)stride * 4));
+    XPBD_HIP_TRY(w->aos_staging.reserve((size_t)(n_new ? n_new : 1) * sizeof(xpbd_rigid)));
+    w->n = n_new;
+    w->stride = stride;
+    w->stat_rec_valid = false;
+    w->max_shape_id = max_shape_id;
+    w->stepped = false;
+    w->trace_rows = 0;
+    w->frame_snapshot_valid = false;
+    w->bp_pending = false;
+    report_reset(w);
+    return XPBD_OK;
+}
+
+// A per-body table of a setter: staged in a buffer of its own and moved over `table`, so that a failed allocation or copy
+// leaves the previous table in force.  The stream is idle (queued work may still read the present table).
+int upload_table(DeviceBuffer &table, const void *values, size_t bytes)
+{
+    DeviceBuffer fresh;
+    XPBD_HIP_TRY(fresh.reserve(bytes));
+    XPBD_HIP_TRY(hipMemcpy(fresh.ptr, values, bytes, hipMemcpyHostToDevice));
+    table = std::move(fresh);
+    return XPBD_OK;
+}
 } // namespace
 
 // ---- re-planning a shard of the multi-GPU world on the device (xpbd_multi.cpp) ---------------------------------------------
@@ -850,34 +903,8 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     XPBD_HIP_TRY(launch_repack_bodies(w->aos_staging.as<double>(), w->shape_id.as<uint32_t>(), w->repack_src.as<int32_t>(), n_new,
                                       w->repack_incoming.as<double>(), w->repack_aos.as<double>(), w->repack_shape.as<uint32_t>(), w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the arrays below may move
-    // 2. the world takes the new size (as xpbd_world_upload_bodies)
-    const uint32_t stride = round_up(n_new ? n_new : 1, 256);
-    XPBD_HIP_TRY(w->dyn.reserve((size_t)kDynFields * stride * 8));
-    XPBD_HIP_TRY(w->stat.reserve((size_t)kStatFields * stride * 8));
-    XPBD_HIP_TRY(w->shape_id.reserve((size_t)stride * 4));
-    XPBD_HIP_TRY(w->last_mask.reserve((size_t)stride * 4));
-    XPBD_HIP_TRY(w->aos_staging.reserve((size_t)(n_new ? n_new : 1) * sizeof(xpbd_rigid)));
-    w->have_neighbours = false;
-    w->n_joints = 0;
-    w->joints_host.clear();
-    w->n_limits = 0;
-    w->has_filters = false;
-    w->filter_flags = 0;
-    w->has_materials = false;
-    w->ground_friction = std::numeric_limits<double>::infinity();
-    w->has_restitution = false;
-    w->ground_restitution = w->bounce_threshold = 0.0;
-    w->history_length = 0;
-    w->history_stepped.clear();
-    w->n = n_new;
-    w->stride = stride;
-    w->stat_rec_valid = false;
-    w->max_shape_id = max_shape_id;
-    w->stepped = false;
-    w->trace_rows = 0;
-    w->frame_snapshot_valid = false;
-    w->bp_pending = false;
-    report_reset(w);
+    // 2. the world takes the new size
+    XPBD_TRY(adopt_body_count(w, n_new, max_shape_id));
     // mass properties shared per shape: the bodies that stay kept the property, the incoming ones are checked
     if (w->stat_shape_seen.size() != w->n_shapes) {
         w->stat_shape_host.assign((size_t)w->n_shapes * kStatRecDoubles, 0.0);
@@ -891,9 +918,9 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     }
     if (n_new == 0)
         return XPBD_OK;
-    XPBD_HIP_TRY(hipMemsetAsync(w->shape_id.ptr, 0, (size_t)stride * 4, w->stream));
+    XPBD_HIP_TRY(hipMemsetAsync(w->shape_id.ptr, 0, (size_t)w->stride * 4, w->stream));
     XPBD_HIP_TRY(hipMemcpyAsync(w->shape_id.ptr, w->repack_shape.ptr, (size_t)n_new * 4, hipMemcpyDeviceToDevice, w->stream));
-    XPBD_HIP_TRY(hipMemsetAsync(w->last_mask.ptr, 0, (size_t)stride * 4, w->stream));
+    XPBD_HIP_TRY(hipMemsetAsync(w->last_mask.ptr, 0, (size_t)w->stride * 4, w->stream));
     XPBD_HIP_TRY(launch_aos_to_soa(w->repack_aos.as<double>(), w->arrays(), w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the caller's buffers are only borrowed
     return XPBD_OK;
@@ -918,6 +945,15 @@ int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, u
                     return set_error(XPBD_E_INVALID, "%s: hinge %u needs unit axes (|axis|^2 = %g)", who, k, len2);
             }
     }
+    return XPBD_OK;
+}
+
+int check_per_body(const char *who, const char *what, const void *values, uint32_t n, uint32_t n_bodies, const char *count)
+{
+    if (!values && n)
+        return set_error(XPBD_E_INVALID, "%s: NULL %s with %s = %u", who, what, count, n);
+    if (values && n != n_bodies)
+        return set_error(XPBD_E_INVALID, "%s: %s = %u but the world holds %u bodies", who, count, n, n_bodies);
     return XPBD_OK;
 }
 
@@ -1024,7 +1060,7 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
     }
     const QueryScratch s{w->q_rec.as<double>(), w->q_partials.as<double>(), w->q_grid.ptr, w->q_cell_start.as<uint32_t>(),
                          w->q_cell_fill.as<uint32_t>(), w->q_items.as<uint32_t>(), w->q_scan.as<uint32_t>(), w->q_brute.ptr, q.table_size};
-    const RayFilter filter{masked && w->has_filters ? w->ft_filters.as<uint2>() : nullptr, mask, masked ? 1u : 0u};
+    const RayFilter filter{masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr, mask, masked ? 1u : 0u};
     XPBD_HIP_TRY(launch_raycast(w->arrays(), w->tables(), dev_global_id, filter, dev_rays, n_rays, brute, s, dev_hits, w->stream));
     return XPBD_OK;
 }
@@ -1364,38 +1400,12 @@ try {
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    const uint32_t stride = round_up(n ? n : 1, 256);
-    XPBD_HIP_TRY(w->dyn.reserve((size_t)xpbd::kDynFields * stride * 8));
-    w->have_neighbours = false;
-    w->n_joints = 0; // joints name bodies by index: a new upload invalidates them (and their limits), and so do filters
-    w->joints_host.clear();
-    w->n_limits = 0;
-    w->has_filters = false;
-    w->filter_flags = 0;
-    w->has_materials = false;
-    w->ground_friction = std::numeric_limits<double>::infinity();
-    w->has_restitution = false;
-    w->ground_restitution = w->bounce_threshold = 0.0;
-    w->history_length = 0;
-    w->history_stepped.clear();
-    XPBD_HIP_TRY(w->stat.reserve((size_t)xpbd::kStatFields * stride * 8));
-    XPBD_HIP_TRY(w->shape_id.reserve((size_t)stride * 4));
-    XPBD_HIP_TRY(w->last_mask.reserve((size_t)stride * 4));
-    XPBD_HIP_TRY(w->aos_staging.reserve((size_t)(n ? n : 1) * sizeof(xpbd_rigid)));
-    w->n = n;
-    w->stride = stride;
-    w->stat_rec_valid = false;
-    w->max_shape_id = max_shape_id;
+    XPBD_TRY(adopt_body_count(w, n, max_shape_id));
     w->stat_shape_host.assign((size_t)w->n_shapes * xpbd::kStatRecDoubles, 0.0);
     w->stat_shape_seen.assign(w->n_shapes, 0);
     w->stat_shared = n != 0;
     for (uint32_t i = 0; i < n && w->stat_shared; ++i)
         absorb_stat_record(w, aos[i], shape_id ? shape_id[i] : 0u);
-    w->stepped = false;
-    w->trace_rows = 0;
-    w->frame_snapshot_valid = false;
-    w->bp_pending = false;
-    report_reset(w);
     if (n == 0)
         return XPBD_OK;
     XPBD_HIP_TRY(hipMemcpyAsync(w->aos_staging.ptr, aos, (size_t)n * sizeof(xpbd_rigid), hipMemcpyHostToDevice,
@@ -1403,8 +1413,8 @@ try {
     if (shape_id)
         XPBD_HIP_TRY(hipMemcpyAsync(w->shape_id.ptr, shape_id, (size_t)n * 4, hipMemcpyHostToDevice, w->stream));
     else
-        XPBD_HIP_TRY(hipMemsetAsync(w->shape_id.ptr, 0, (size_t)stride * 4, w->stream));
-    XPBD_HIP_TRY(hipMemsetAsync(w->last_mask.ptr, 0, (size_t)stride * 4, w->stream));
+        XPBD_HIP_TRY(hipMemsetAsync(w->shape_id.ptr, 0, (size_t)w->stride * 4, w->stream));
+    XPBD_HIP_TRY(hipMemsetAsync(w->last_mask.ptr, 0, (size_t)w->stride * 4, w->stream));
     XPBD_HIP_TRY(xpbd::launch_aos_to_soa(w->aos_staging.as<double>(), w->arrays(), w->stream));
     // The caller's buffers are only borrowed for the duration of the call.
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
@@ -1651,9 +1661,7 @@ try {
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    w->n_joints = 0;
-    w->joints_host.clear();
-    w->n_limits = 0; // limits name joints by index: new joints invalidate them
+    w->joints.clear(); // (limits name joints by index: new joints invalidate them)
     if (n_joints == 0)
         return XPBD_OK;
     XPBD_HIP_TRY(w->jt_joints.reserve((size_t)n_joints * sizeof(xpbd::Joint)));
@@ -1662,8 +1670,8 @@ try {
     XPBD_HIP_TRY(hipMemcpy(w->jt_joints.ptr, joints, (size_t)n_joints * sizeof(xpbd::Joint), hipMemcpyHostToDevice));
     XPBD_HIP_TRY(hipMemcpy(w->jt_off.ptr, off.data(), (size_t)(w->n + 1) * 4, hipMemcpyHostToDevice));
     XPBD_HIP_TRY(hipMemcpy(w->jt_list.ptr, list.data(), (size_t)2 * n_joints * 4, hipMemcpyHostToDevice));
-    w->n_joints = n_joints;
-    w->joints_host.assign(joints, joints + n_joints);
+    w->joints.n = n_joints;
+    w->joints.host.assign(joints, joints + n_joints);
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -1673,13 +1681,13 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_limits: NULL world");
     if (n_limits && w->mode != XPBD_MODE_CONTACTS)
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_limits: limits need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
-    if (int rc = xpbd::check_joint_limits("xpbd_world_set_joint_limits", w->joints_host.data(), w->n_joints, limits, n_limits))
+    if (int rc = xpbd::check_joint_limits("xpbd_world_set_joint_limits", w->joints.host.data(), w->joints.n, limits, n_limits))
         return rc;
     // CSR joint -> limits, the caller's order inside a joint
-    std::vector<uint32_t> off((size_t)w->n_joints + 1, 0);
+    std::vector<uint32_t> off((size_t)w->joints.n + 1, 0);
     for (uint32_t k = 0; k < n_limits; ++k)
         ++off[limits[k].joint + 1];
-    for (uint32_t j = 0; j < w->n_joints; ++j)
+    for (uint32_t j = 0; j < w->joints.n; ++j)
         off[j + 1] += off[j];
     std::vector<xpbd_joint_limit> sorted(n_limits);
     {
@@ -1691,15 +1699,15 @@ try {
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     if (n_limits == 0) {
-        w->n_limits = 0;
+        w->joints.n_limits = 0;
         return XPBD_OK;
     }
     XPBD_HIP_TRY(w->jt_limits.reserve((size_t)n_limits * sizeof(xpbd::JointLimit)));
     XPBD_HIP_TRY(w->jt_limit_off.reserve(off.size() * 4));
-    w->n_limits = 0; // (a failed copy below leaves none rather than a torn table)
+    w->joints.n_limits = 0; // (a failed copy below leaves none rather than a torn table)
     XPBD_HIP_TRY(hipMemcpy(w->jt_limits.ptr, sorted.data(), (size_t)n_limits * sizeof(xpbd::JointLimit), hipMemcpyHostToDevice));
     XPBD_HIP_TRY(hipMemcpy(w->jt_limit_off.ptr, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    w->n_limits = n_limits;
+    w->joints.n_limits = n_limits;
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -1708,24 +1716,20 @@ try {
     static_assert(sizeof(xpbd_collision_filter) == sizeof(uint2), "xpbd_collision_filter must mirror uint2 {group, mask}");
     if (!w)
         return set_error(XPBD_E_INVALID, "xpbd_world_set_collision_filters: NULL world");
-    if (!filters && n)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_collision_filters: NULL filters with n = %u", n);
-    if (filters && n != w->n)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_collision_filters: n = %u but the world holds %u bodies", n, w->n);
+    XPBD_TRY(xpbd::check_per_body("xpbd_world_set_collision_filters", "filters", filters, n, w->n));
     if (flags & ~XPBD_FILTER_JOINTED)
         return set_error(XPBD_E_INVALID, "xpbd_world_set_collision_filters: unknown flags 0x%x", flags);
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued broadphases may still read the present filters
-    w->filter_flags = flags;
     if (!filters || n == 0) {
-        w->has_filters = false;
+        w->filters.clear();
+        w->filters.flags = flags;
         return XPBD_OK;
     }
-    XPBD_HIP_TRY(w->ft_filters.reserve((size_t)n * sizeof(uint2)));
-    w->has_filters = false; // (a failed copy below leaves none rather than a torn table)
-    XPBD_HIP_TRY(hipMemcpy(w->ft_filters.ptr, filters, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice));
-    w->has_filters = true;
+    XPBD_TRY(upload_table(w->ft_filters, filters, (size_t)n * sizeof(uint2)));
+    w->filters.on = true;
+    w->filters.flags = flags;
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -1734,10 +1738,7 @@ try {
     static_assert(sizeof(xpbd_material) == 16, "xpbd_material is {friction, reserved}");
     if (!w)
         return set_error(XPBD_E_INVALID, "xpbd_world_set_materials: NULL world");
-    if (!materials && n)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_materials: NULL materials with n = %u", n);
-    if (materials && n != w->n)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_materials: n = %u but the world holds %u bodies", n, w->n);
+    XPBD_TRY(xpbd::check_per_body("xpbd_world_set_materials", "materials", materials, n, w->n));
     if (!(ground_friction >= 0.0))
         return set_error(XPBD_E_INVALID, "xpbd_world_set_materials: ground_friction = %g (must be >= 0, +inf allowed)", ground_friction);
     if (int rc = xpbd::check_materials("xpbd_world_set_materials", materials, n))
@@ -1747,21 +1748,16 @@ try {
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present coefficients
     const double inf = std::numeric_limits<double>::infinity();
     if ((!materials || n == 0) && ground_friction == inf) { // the default: the contact kernels' plain forms
-        w->has_materials = false;
-        w->ground_friction = inf;
+        w->materials.clear();
         return XPBD_OK;
     }
     // (a finite ground coefficient alone: every body +inf, so that the kernels have one switch, the array)
     std::vector<double> friction(std::max(w->n, 1u), inf);
     for (uint32_t i = 0; materials && i < n; ++i)
         friction[i] = materials[i].friction;
-    // staged in a buffer of its own and swapped in: a failed allocation or copy leaves the previous materials in place
-    DeviceBuffer fresh;
-    XPBD_HIP_TRY(fresh.reserve(friction.size() * sizeof(double)));
-    XPBD_HIP_TRY(hipMemcpy(fresh.ptr, friction.data(), friction.size() * sizeof(double), hipMemcpyHostToDevice));
-    w->mt_friction = std::move(fresh);
-    w->has_materials = true;
-    w->ground_friction = ground_friction;
+    XPBD_TRY(upload_table(w->mt_friction, friction.data(), friction.size() * sizeof(double)));
+    w->materials.on = true;
+    w->materials.ground_friction = ground_friction;
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -1769,10 +1765,7 @@ int xpbd_world_set_restitution(xpbd_world *w, const double *restitution, uint32_
 try {
     if (!w)
         return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: NULL world");
-    if (!restitution && n)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: NULL restitution with n = %u", n);
-    if (restitution && n != w->n)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: n = %u but the world holds %u bodies", n, w->n);
+    XPBD_TRY(xpbd::check_per_body("xpbd_world_set_restitution", "restitution", restitution, n, w->n));
     if (!(ground_restitution >= 0.0 && ground_restitution <= 1.0))
         return set_error(XPBD_E_INVALID, "xpbd_world_set_restitution: ground_restitution = %g (must be in [0, 1])", ground_restitution);
     if (!(bounce_threshold >= 0.0 && bounce_threshold <= std::numeric_limits<double>::max()))
@@ -1787,25 +1780,20 @@ try {
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present coefficients
     if (!any) { // nothing can bounce: the step runs what it ran before the call
-        w->has_restitution = false;
-        w->ground_restitution = 0.0;
-        w->bounce_threshold = bounce_threshold;
+        w->restitution.clear();
+        w->restitution.bounce_threshold = bounce_threshold;
         return XPBD_OK;
     }
     std::vector<double> values(std::max(w->n, 1u), 0.0);
     for (uint32_t i = 0; restitution && i < n; ++i)
         values[i] = restitution[i];
-    // staged in a buffer of its own and swapped in: a failed allocation or copy leaves the previous values in place
-    DeviceBuffer fresh;
-    XPBD_HIP_TRY(fresh.reserve(values.size() * sizeof(double)));
-    XPBD_HIP_TRY(hipMemcpy(fresh.ptr, values.data(), values.size() * sizeof(double), hipMemcpyHostToDevice));
     const uint32_t stride = w->stride ? w->stride : 256u;
     XPBD_HIP_TRY(w->dyn_alt.reserve((size_t)xpbd::kDynFields * stride * 8));
     XPBD_HIP_TRY(w->rs_start.reserve((size_t)6 * stride * 8));
-    w->rs_restitution = std::move(fresh);
-    w->has_restitution = true;
-    w->ground_restitution = ground_restitution;
-    w->bounce_threshold = bounce_threshold;
+    XPBD_TRY(upload_table(w->rs_restitution, values.data(), values.size() * sizeof(double)));
+    w->restitution.on = true;
+    w->restitution.ground = ground_restitution;
+    w->restitution.bounce_threshold = bounce_threshold;
     return XPBD_OK;
 } XPBD_ABI_CATCH
 

@@ -2,7 +2,9 @@
 GPU: the filtered broadphase equals the oracle's lists minus what the model (tests/collision_filter_model.py) filters out;
 filters that filter nothing change no bit; filtering everything gives the reference path; two piles in disjoint groups step
 as if each were alone; jointed pairs drop out; a sharded world equals the single one; masked ray casts equal plain casts
-on the admitted bodies; bad arguments leave the previous filters in place."""
+on the admitted bodies; bad arguments leave the previous filters in place.  Last, for every body-indexed setting (joints with
+limits, filters, materials, restitution): an upload of the same bodies drops it, and a planned sharded world keeps it through
+re-plans that move bodies between owners."""
 import numpy as np
 import pytest
 
@@ -412,3 +414,79 @@ def test_multi_world_rejects_bad_filters_and_upload_clears_them():
         for _ in range(8):
             mw.step(DT, 6)
         assert bits_equal(mw.download(), plain)
+
+
+# ---- 9. every body-indexed setting goes with the bodies it indexed --------------------------------------------------------
+def body_settings(n):
+    """name -> what sets it on a World or a MultiWorld (the multi world has the first two only)."""
+    rng = np.random.default_rng(5)
+    joints, lims = limited_chain(n)
+    filters = random_filters(rng, n, layers=2)
+    mu = rng.choice([0.0, 0.2, 0.5, 1.0, np.inf], n)
+    e = rng.choice([0.0, 0.3, 0.8, 1.0], n)
+    return {"filters": lambda w: w.set_collision_filters(filters, capi.FILTER_JOINTED),
+            "materials": lambda w: w.set_materials(mu, 0.3),
+            "joints with limits": lambda w: (w.set_joints(joints), w.set_joint_limits(lims)),
+            "restitution": lambda w: w.set_restitution(e, 0.5, 0.02)}
+
+
+def stepped(w, frames, substeps):
+    for _ in range(frames):
+        w.step(DT, substeps)
+    return w.download()
+
+
+@pytest.mark.parametrize("setting", ["joints with limits", "filters", "materials", "restitution"])
+def test_upload_of_the_same_bodies_drops_every_body_indexed_setting(setting):
+    kind, n, frames, substeps = capi.SCENE_BOXES_DROP, 200, 12, 6
+    bodies, sid = pile(capi, kind, n, 7, 4.0, 3.0)
+    with world(kind, bodies, sid) as w:
+        plain = stepped(w, frames, substeps)                          # a world that never had the setting
+    with world(kind, bodies, sid) as w:
+        body_settings(n)[setting](w)
+        with_setting = stepped(w, frames, substeps)
+        w.upload(bodies, sid)
+        again = stepped(w, frames, substeps)
+    assert not np.isnan(plain).any() and not np.isnan(with_setting).any()
+    assert not bits_equal(with_setting, plain)                        # the setting matters in this scene
+    assert bits_equal(again, plain)
+
+
+@pytest.mark.parametrize("setting", ["filters", "materials"])
+def test_setting_given_to_a_planned_multi_world_survives_forced_replans_with_migration(setting):
+    """The migrating line of test_sharded_world_with_filters_equals_single; the setting arrives after the first plan, so the
+    setter hands it to the shards itself, and every later plan hands it over again to the bodies' new owners."""
+    kind, n, substeps, before, frames = capi.SCENE_BOXES_DROP, 96, 6, 6, 24
+    rng = np.random.default_rng(3)
+    bodies, sid = line_scene(capi, kind, n, 11, 1.3)
+    bodies[:, 34:38] = [1.0, 0.0, 0.0, 0.0]
+    bodies[:, 25:28] = rng.normal(scale=6.0, size=(n, 3))
+    bodies[:, 22] += 1.5
+    joints = chain_joints(capi, n, every=1, distance=0.0, limit=n // 2)
+    joints["anchor_a"], joints["anchor_b"] = [1.15, 0.5, 0.5], [-0.15, 0.5, 0.5]
+    apply = body_settings(n)[setting]
+    with world(kind, bodies, sid) as w:
+        w.set_joints(joints)
+        plain = stepped(w, before + frames, substeps)
+    with world(kind, bodies, sid) as w:
+        w.set_joints(joints)
+        stepped(w, before, substeps)
+        apply(w)
+        one = stepped(w, frames, substeps)
+    assert not np.isnan(one).any() and not bits_equal(one, plain)
+    with capi.MultiWorld(4, devices=[0] * 4, transport=capi.TRANSPORT_LOCAL, halo_margin=0.75, auto_replan=True) as mw:
+        mw.set_polytopes(capi.scene_polytopes(kind))
+        mw.upload(bodies, sid, 0, n, joints)
+        for _ in range(before):
+            mw.step(DT, substeps)
+        assert mw.plan_stats()["plans"] >= 1
+        apply(mw)
+        migrated = 0
+        for f in range(frames):
+            mw.step(DT, substeps)
+            if f % 6 == 5:
+                mw.replan()
+                migrated += mw.plan_stats()["migrated"]
+        got = mw.download()
+    assert migrated > 0
+    assert bits_equal(got, one)
