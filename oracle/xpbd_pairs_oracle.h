@@ -40,7 +40,7 @@ typedef struct {
     int32_t  feature;      /* OP_FEATURE_* */
     uint32_t index_a;      /* FACE_A: reference face on A | FACE_B: incident face on A | EDGES: edge of A */
     uint32_t index_b;      /* FACE_A: incident face on B  | FACE_B: reference face on B | EDGES: edge of B */
-    double   separation;   /* max(a, b, e) < 0 when touching */
+    double   separation;   /* the chosen feature's query, < 0: max(a, b) for a face, e for EDGES (e > max(a, b) + OP_EDGE_BIAS) */
     double   query[3];     /* the three query values a, b, e (e is -DBL_MAX if no edge pair qualified) */
     uint32_t n_points;     /* <= OP_MAX_POINTS */
     o_vec3   p_ref[OP_MAX_POINTS]; /* point on the REFERENCE body's surface (world) */

@@ -139,6 +139,113 @@ def shape_table(verts, offsets, shape_id):
     return slots, counts
 
 
+def integrate(s, pos, rot, vel, ang, h, sqrt):
+    """Rigid::integrate, rigid.rs:82-99, for every body of the unpacked state `s`."""
+    im, M = s["inverse_mass"], s["inverse_inertia"]
+    force = s["external_force"] + qrot(rot, s["internal_force"])
+    vel = vel + force * h * im
+    pos = pos + vel * h
+    torque = s["external_torque"] + qrot(rot, s["internal_torque"])
+    ang = ang + matvec(M, torque) * h
+    rot = normalize_q(rot + qmul(pure(ang) * (h / 2), rot), sqrt)
+    return pos, rot, vel, ang
+
+
+def friction_factor(num, mu, correction, tangential, cc):
+    """include/xpbd.h, "Contact MATERIALS": the contact takes back at most mu |correction| of the tangential slip.  Returns
+    (k, |bound - slip| in metres; inf where mu is +inf).  mu: f64 array over the contacts."""
+    sqrt = num.sqrt
+    finite = np.isfinite(mu)
+    len_c, len_t = sqrt(cc), sqrt(dot(tangential, tangential))
+    bound = num.conv(np.where(finite, mu, 0.0)) * len_c
+    slides = finite & (bound < len_t).astype(bool)
+    k = np.where(slides, bound / np.where(slides, len_t, len_t * 0 + 1), len_t * 0 + 1)
+    return k, np.where(finite, np.abs(num.to_f64(bound - len_t)), np.inf)
+
+
+def limited(num, dist, limit, delta, correction, cc):
+    """oracle/xpbd_pairs_oracle.h, op_contacts_set_max_depenetration_speed: the constraint's length is limited to
+    max(0, speed h - closing), closing = delta . correction / |correction|.  limit = speed h, None = off.  Returns (the
+    length to remove, |dist - allowed| in metres; inf when off)."""
+    if limit is None:
+        return dist, np.full(dist.shape, np.inf)
+    allowed = limit - dot(delta, correction) / num.sqrt(cc)
+    allowed = np.where((allowed > 0).astype(bool), allowed, allowed * 0)
+    return np.where((dist > allowed).astype(bool), allowed, dist), np.abs(num.to_f64(dist - allowed))
+
+
+def ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain, mu=None, limit=None):
+    """collision::ground and solver::solve for every body, from the post-integrate pose (pos, rot).  mu (f64 per body) and
+    limit (speed h) are the extension's friction and depenetration limit; None is the reference.  Returns the pose after
+    the solve and the masks, margins and conditioning of step()."""
+    sqrt = num.sqrt
+    im, M, com = s["inverse_mass"], s["inverse_inertia"], s["center_of_mass"]
+    n, vmax = pos.shape[1], len(vert)
+    # collision::ground, collision.rs:13-35: every constraint is built from this post-integrate frame
+    cur_p, cur_q = pos + com + qrot(rot, -com), rot
+    mask = np.zeros(n, dtype=np.uint32)
+    margin = np.full(n, np.inf)
+    branch = np.full(n, np.inf)
+    xs = []
+    for v in range(vmax):
+        x = frame_apply(cur_p, cur_q, vert[v])                              # collision.rs:17
+        live = v < counts
+        z = num.to_f64(x[2])
+        below = live & (x[2] < 0).astype(bool)                              # collision.rs:18, skip when z >= 0
+        margin = np.where(live, np.minimum(margin, np.abs(z)), margin)
+        mask |= below.astype(np.uint32) << np.uint32(v)
+        xs.append(x)
+
+    # solver::solve, solver.rs:19-27: the constraints in push order, each against the live pose
+    cond = np.full(n, np.inf)
+    pos, rot = pos.copy(), rot.copy()               # the live pose; cur_p and cur_q stay frozen
+    for v in range(vmax):
+        idx = np.nonzero((mask >> np.uint32(v)) & 1)[0]
+        if not len(idx):
+            continue
+        x = xs[v][:, idx]
+        p_, q_, M_, c_, im_ = pos[:, idx], rot[:, idx], M[:, :, idx], com[:, idx], im[idx]
+        target = np.stack([x[0], x[1], x[2] * 0])                          # collision.rs:22
+        correction = target - x                                             # collision.rs:23
+        cc = dot(correction, correction)
+        domain[idx] &= num.to_f64(cc) >= F64_MIN_NORMAL
+        cc = np.where(num.to_f64(cc) > 0, cc, cc + 1)                       # only out-of-domain bodies reach 0
+        delta = frame_delta(cur_p[:, idx], cur_q[:, idx], past_p[:, idx], past_rot[:, idx], x)   # collision.rs:24
+        tangential = delta - correction * (dot(delta, correction) / cc)    # collision.rs:25, project_on
+        if mu is not None:
+            k, gap = friction_factor(num, mu[idx], correction, tangential, cc)
+            branch[idx] = np.minimum(branch[idx], gap)
+            tangential = tangential * k
+        c0, c1 = x, target - tangential                                     # collision.rs:27-31, distance 0
+        diff = c1 - c0                                                      # constraint.rs:13-15
+        dist = sqrt(dot(diff, diff))                                        # constraint.rs:21-23
+        cond[idx] = np.minimum(cond[idx], num.to_f64(dist))
+        dist = np.where(num.to_f64(dist) > 0, dist, dist + 1)
+        direction = diff / dist                                             # constraint.rs:17-19
+        # inverse_resitance, constraint.rs:25-32: the arm is taken into rest space
+        ai = qrot(conj(q_), cross(c0 - (p_ + c_), direction))
+        w = im_ + dot(matvec(M_, ai), ai)
+        error, gap = limited(num, dist, limit, delta, correction, cc)
+        branch[idx] = np.minimum(branch[idx], gap)
+        lam = error / (w + compliance)                                      # solver.rs:23-24 (distance == 0)
+        impulse = direction * lam                                           # constraint.rs:34-37
+        # Rigid::apply_impulse, rigid.rs:113-123: the world-space arm is NOT rotated into rest space
+        p_ = p_ + impulse * im_
+        spin = cross(matvec(M_, c0 - (p_ + c_)), impulse)
+        q_ = normalize_q(q_ + qmul(pure(spin) * 0.5, q_), sqrt)
+        pos[:, idx], rot[:, idx] = p_, q_
+    return pos, rot, {"mask": mask, "margin": margin, "cond": cond, "branch": branch}
+
+
+def derive(num, pos, rot, past_pos, past_rot, h):
+    """Rigid::derive, rigid.rs:101-109.  Returns velocity, angular velocity, the flip taken and |delta.s|."""
+    vel = (pos - past_pos) / h
+    dq = qmul(rot, conj(past_rot))
+    flip = (dq[0] < 0).astype(bool)
+    dq = np.where(flip, -dq, dq)
+    return vel, dq[1:] * 2 / h, flip, np.abs(num.to_f64(dq[0]))
+
+
 def step(bodies, verts, offsets, shape_id, dt, substeps, num=None):
     """solver::step (solver.rs:3-17) for every body, in the model's precision.  `bodies`: (n, 38) f64, converted
     exactly, or the `state` of an earlier call, carried on in the model's scalars.
@@ -165,8 +272,7 @@ def step(bodies, verts, offsets, shape_id, dt, substeps, num=None):
     vmax = int(counts.max()) if n else 0
     vert = [num.conv(slots[:, v].T) for v in range(vmax)]
 
-    im, M, com = s["inverse_mass"], s["inverse_inertia"], s["center_of_mass"]
-    ef, fi, et, ti = s["external_force"], s["internal_force"], s["external_torque"], s["internal_torque"]
+    com = s["center_of_mass"]
     pos, rot, vel, ang = s["position"], s["rotation"], s["velocity"], s["angular_velocity"]
     h = num.const(float(dt)) / substeps                  # solver.rs:4, dt / substep_count taken exactly
     compliance = num.const("1e-6") / (h * h)             # solver.rs:20
@@ -175,73 +281,14 @@ def step(bodies, verts, offsets, shape_id, dt, substeps, num=None):
     for _ in range(substeps):
         past_pos, past_rot = pos, rot                                           # solver.rs:7-8
         past_p = pos + com + qrot(rot, -com)                                    # solver.rs:9, Rigid::frame rigid.rs:75-80
-
-        # Rigid::integrate, rigid.rs:82-99
-        force = ef + qrot(rot, fi)
-        vel = vel + force * h * im
-        pos = pos + vel * h
-        torque = et + qrot(rot, ti)
-        ang = ang + matvec(M, torque) * h
-        rot = normalize_q(rot + qmul(pure(ang) * (h / 2), rot), sqrt)
-
-        # collision::ground, collision.rs:13-35: every constraint is built from this post-integrate frame
-        cur_p, cur_q = pos + com + qrot(rot, -com), rot
-        mask = np.zeros(n, dtype=np.uint32)
-        margin = np.full(n, np.inf)
-        xs = []
-        for v in range(vmax):
-            x = frame_apply(cur_p, cur_q, vert[v])                              # collision.rs:17
-            live = v < counts
-            z = num.to_f64(x[2])
-            below = live & (x[2] < 0).astype(bool)                              # collision.rs:18, skip when z >= 0
-            margin = np.where(live, np.minimum(margin, np.abs(z)), margin)
-            mask |= below.astype(np.uint32) << np.uint32(v)
-            xs.append(x)
-
-        # solver::solve, solver.rs:19-27: the constraints in push order, each against the live pose
-        cond = np.full(n, np.inf)
-        pos, rot = pos.copy(), rot.copy()               # the live pose; cur_p and cur_q stay frozen
-        for v in range(vmax):
-            idx = np.nonzero((mask >> np.uint32(v)) & 1)[0]
-            if not len(idx):
-                continue
-            x = xs[v][:, idx]
-            p_, q_, M_, c_, im_ = pos[:, idx], rot[:, idx], M[:, :, idx], com[:, idx], im[idx]
-            target = np.stack([x[0], x[1], x[2] * 0])                          # collision.rs:22
-            correction = target - x                                             # collision.rs:23
-            cc = dot(correction, correction)
-            domain[idx] &= num.to_f64(cc) >= F64_MIN_NORMAL
-            cc = np.where(num.to_f64(cc) > 0, cc, cc + 1)                       # only out-of-domain bodies reach 0
-            delta = frame_delta(cur_p[:, idx], cur_q[:, idx], past_p[:, idx], past_rot[:, idx], x)   # collision.rs:24
-            tangential = delta - correction * (dot(delta, correction) / cc)    # collision.rs:25, project_on
-            c0, c1 = x, target - tangential                                     # collision.rs:27-31, distance 0
-            diff = c1 - c0                                                      # constraint.rs:13-15
-            dist = sqrt(dot(diff, diff))                                        # constraint.rs:21-23
-            cond[idx] = np.minimum(cond[idx], num.to_f64(dist))
-            dist = np.where(num.to_f64(dist) > 0, dist, dist + 1)
-            direction = diff / dist                                             # constraint.rs:17-19
-            # inverse_resitance, constraint.rs:25-32: the arm is taken into rest space
-            ai = qrot(conj(q_), cross(c0 - (p_ + c_), direction))
-            w = im_ + dot(matvec(M_, ai), ai)
-            lam = dist / (w + compliance)                                       # solver.rs:23-24 (distance == 0)
-            impulse = direction * lam                                           # constraint.rs:34-37
-            # Rigid::apply_impulse, rigid.rs:113-123: the world-space arm is NOT rotated into rest space
-            p_ = p_ + impulse * im_
-            spin = cross(matvec(M_, c0 - (p_ + c_)), impulse)
-            q_ = normalize_q(q_ + qmul(pure(spin) * 0.5, q_), sqrt)
-            pos[:, idx], rot[:, idx] = p_, q_
-
-        # Rigid::derive, rigid.rs:101-109
-        vel = (pos - past_pos) / h
-        dq = qmul(rot, conj(past_rot))
-        flip = (dq[0] < 0).astype(bool)
-        dq = np.where(flip, -dq, dq)
-        ang = dq[1:] * 2 / h
-        out["masks"].append(mask)
-        out["margin"].append(margin)
-        out["cond"].append(cond)
+        pos, rot, vel, ang = integrate(s, pos, rot, vel, ang, h, sqrt)
+        pos, rot, g = ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain)
+        vel, ang, flip, flip_margin = derive(num, pos, rot, past_pos, past_rot, h)
+        out["masks"].append(g["mask"])
+        out["margin"].append(g["margin"])
+        out["cond"].append(g["cond"])
         out["flip"].append(flip)
-        out["flip_margin"].append(np.abs(num.to_f64(dq[0])))
+        out["flip_margin"].append(flip_margin)
 
     s.update(position=pos, rotation=rot, velocity=vel, angular_velocity=ang)
     res = {k: np.array(v) for k, v in out.items()}

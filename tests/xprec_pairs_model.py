@@ -1,0 +1,362 @@
+"""Extended-precision model of the body-body contact extension: the manifold of a pair (stage N) and one contacts
+substep of n bodies (stage S).
+
+A second reading of oracle/xpbd_pairs_oracle.h's prose (steps 1-5, the manifold conventions) and of the reference lines
+that header cites; it does not follow xpbd_pairs_oracle.c, the kernels or tests/material_model.py.  Stage N is plain
+geometry: every query is a maximum over ALL faces or edge pairs of a minimum over ALL vertices, evaluated in world space
+(a rigid motion keeps distances), where the oracle works in A's space, over unique edge directions and with supports.
+Stage S uses tests/xprec_model.py's scalar abstraction, cgmath helpers, integrate, ground and derive.
+
+Vectors are arrays (3, k) of model scalars as in xprec_model.py.  Reference lines are jim-ec/constraint_solver src/*.rs.
+"""
+import numpy as np
+
+import xprec_model as xm
+from xprec_model import conj, cross, dot, frame_apply, frame_delta, matvec, normalize_q, pure, qmul, qrot
+
+EDGE_BIAS = 1e-6          # OP_EDGE_BIAS
+MAX_POINTS = 8            # OP_MAX_POINTS
+FACE_A, FACE_B, EDGES = 0, 1, 2
+# two edges whose directions enclose less than this sine span no axis (the reference's normalize of their cross product
+# is NaN only at exactly 0; next to it the axis is noise, and a face axis describes the same contact)
+PARALLEL_SIN = 1e-9
+MUTATIONS = ("reference_sign", "arm_without_com", "transposed_inertia", "average_by_pairs", "friction_against_distance",
+             "tangential_dropped")
+
+
+def shape(poly):
+    """An oracle_binding.Polytope as the model's shape: f64 vertices (V, 3), edges (E, 2), a list of face index arrays,
+    the centroid."""
+    nv, ne, nf = int(poly.n_vertices), int(poly.n_edges), int(poly.n_faces)
+    off = [int(poly.face_offsets[i]) for i in range(nf + 1)]
+    idx = [int(poly.face_indices[i]) for i in range(off[-1])]
+    return {"verts": poly.verts(), "edges": np.array([[poly.edges[i][0], poly.edges[i][1]] for i in range(ne)], dtype=np.int64),
+            "faces": [np.array(idx[off[i]:off[i + 1]]) for i in range(nf)], "centroid": poly.centroid.np(),
+            "radius": float(np.linalg.norm(poly.verts() - poly.centroid.np(), axis=1).max())}
+
+
+def _unit(num, v):
+    return v / num.sqrt(dot(v, v))
+
+
+def _world(num, frame, sh):
+    """World vertices (3, V), face normals (3, F) and displacements (F,) (Plane::from_points, geometry.rs:16-25, of the
+    face's first three vertices, pointing away from the centroid) and the centroid of a shape under a frame (position (3,), rotation (4,))."""
+    p, q = frame
+    w = frame_apply(p[:, None], q[:, None], num.conv(sh["verts"].T))
+    first = np.array([f[:3] for f in sh["faces"]])
+    p0, p1, p2 = w[:, first[:, 0]], w[:, first[:, 1]], w[:, first[:, 2]]
+    normal = _unit(num, cross(p1 - p0, p2 - p0))
+    centroid = frame_apply(p[:, None], q[:, None], num.conv(sh["centroid"][:, None]))
+    inward = (dot(normal, centroid - p0) > 0).astype(bool)             # Polytope::plane, geometry.rs:262-271: away from it
+    normal = np.where(inward, -normal, normal)
+    return w, normal, dot(normal, p0), centroid
+
+
+def _runner_up(num, values, best):
+    rest = np.delete(num.to_f64(values - values[best]), best)
+    return float(-rest.max()) if len(rest) else np.inf
+
+
+def _face_query(num, normal, disp, other):
+    """face_axes_separation (collision.rs:123-149): max over the faces of the min over the other body's vertices of the
+    plane distance; first maximum.  Returns (value, face, gap to the runner-up face)."""
+    dist = (normal[0][:, None] * other[0][None] + normal[1][:, None] * other[1][None] + normal[2][:, None] * other[2][None]
+            - disp[:, None])
+    depth = dist.min(axis=1)
+    best = int(np.argmax(depth))
+    return depth[best], best, _runner_up(num, depth, best), depth
+
+
+def _edge_query(num, wa, wb, ea, eb, centroid_a):
+    """edge_axes_separation (collision.rs:151-197) over all E_A x E_B pairs: the normalised cross product, oriented away
+    from A's centroid (collision.rs:176-179), separates by min_B - max_A of the projections.  Returns (value or None,
+    axis, (edge of A, edge of B), (every pair's value, every pair's axis) in f64)."""
+    da, db = wa[:, ea[:, 1]] - wa[:, ea[:, 0]], wb[:, eb[:, 1]] - wb[:, eb[:, 0]]
+    foot = wa[:, ea[:, 0]] - centroid_a[:, None]
+    best, best_axis, best_pair = None, None, None
+    seps, axes = [], []
+    for i in range(ea.shape[0]):
+        axis = cross(da[:, i:i + 1], db)                                                 # (3, E_B)
+        sin2 = dot(axis, axis) / (dot(da[:, i], da[:, i]) * dot(db, db))
+        ok = np.nonzero(num.to_f64(sin2) > PARALLEL_SIN ** 2)[0]
+        if not len(ok):
+            continue
+        axis = _unit(num, axis[:, ok])
+        flip = (dot(axis, foot[:, i:i + 1]) < 0).astype(bool)
+        axis = np.where(flip, -axis, axis)
+        proj_a = axis[0][:, None] * wa[0][None] + axis[1][:, None] * wa[1][None] + axis[2][:, None] * wa[2][None]
+        proj_b = axis[0][:, None] * wb[0][None] + axis[1][:, None] * wb[1][None] + axis[2][:, None] * wb[2][None]
+        sep = proj_b.min(axis=1) - proj_a.max(axis=1)
+        seps.append(num.to_f64(sep))
+        axes.append(num.to_f64(axis))
+        k = int(np.argmax(sep))
+        if best is None or sep[k] > best:
+            best, best_axis, best_pair = sep[k], axis[:, k], (i, int(ok[k]))
+    every = (np.concatenate(seps), np.concatenate(axes, axis=1)) if seps else (np.zeros(0), np.zeros((3, 0)))
+    return best, best_axis, best_pair, every
+
+
+def _supporting_edge(num, w, edges, direction, axis, sign):
+    """Among the edges parallel to `direction`, the one furthest along sign * axis (by its midpoint)."""
+    d = w[:, edges[:, 1]] - w[:, edges[:, 0]]
+    c = cross(d, direction[:, None])
+    parallel = num.to_f64(dot(c, c) / (dot(d, d) * dot(direction, direction))) <= PARALLEL_SIN ** 2
+    mid = dot(w[:, edges[:, 0]] + w[:, edges[:, 1]], axis[:, None]) * sign
+    mid = np.where(parallel, num.to_f64(mid), -np.inf)
+    return int(np.argmax(mid))
+
+
+def _closest_on_segments(num, a0, a1, b0, b1):
+    """Closest points of two segments whose lines are not parallel: the lines' closest points, clamped to the segments."""
+    u, v, r = a1 - a0, b1 - b0, a0 - b0
+    uu, uv, vv, ur, vr = dot(u, u), dot(u, v), dot(v, v), dot(u, r), dot(v, r)
+    den = uu * vv - uv * uv
+    one, zero = uu * 0 + 1, uu * 0
+    s = min(max((uv * vr - vv * ur) / den, zero), one)
+    t = min(max((uv * s + vr) / vv, zero), one)
+    s = min(max((uv * t - ur) / uu, zero), one)
+    return a0 + u * s, b0 + v * t
+
+
+def _clip(num, poly, ref_poly, ref_normal):
+    """Sutherland-Hodgman: the polygon (list of (3,) points) against the side planes of the reference face, the planes
+    through its edges along its normal; a point on a plane is inside.  Returns (polygon, smallest non-zero |distance| of a
+    tested vertex from a side plane)."""
+    margin = np.inf
+    centre = sum(ref_poly[1:], ref_poly[0]) / len(ref_poly)
+    for k in range(len(ref_poly)):
+        if not poly:
+            break
+        e0, e1 = ref_poly[k], ref_poly[(k + 1) % len(ref_poly)]
+        side = _unit(num, cross(e1 - e0, ref_normal))
+        if dot(side, centre - e0) > 0:                                  # outward, whichever way the face is wound
+            side = -side
+        d = [dot(side, p - e0) for p in poly]
+        margin = min([margin] + [abs(float(x)) for x in d if x != 0])
+        out = []
+        for m in range(len(poly)):
+            p, q, dp, dq = poly[m], poly[(m + 1) % len(poly)], d[m], d[(m + 1) % len(poly)]
+            if dp <= 0:
+                out.append(p)
+            if (dp < 0 and dq > 0) or (dp > 0 and dq < 0):
+                out.append(p + (q - p) * (dp / (dp - dq)))
+        poly = out
+    return poly, margin
+
+
+def manifold(frame_a, frame_b, sh_a, sh_b, num=None):
+    """Stage N.  frames: (position (3,), rotation (4,)) in model scalars or f64.  Returns a dict: separated, feature,
+    index_a, index_b (faces as in op_manifold; for EDGES the undirected vertex pairs edge_a, edge_b instead), separation
+    (the chosen feature's query),
+    query (a, b, e or None), p_ref and p_inc (lists of (3,) points) and `margins`: touch (|separation|), ab (|a - b|),
+    edge (|e - max(a, b) - bias|), ref_face and inc_face (gap to the runner-up: metres, cosine), clip (smallest non-zero
+    distance of a clip vertex from a side plane or of a clipped point from the reference plane), axis (how far the best
+    query leads the best other axis).  `axis` is the largest query's axis from A towards B, `depth` minus that query."""
+    num = num or xm.native()
+    fa = (np.asarray(frame_a[0]), np.asarray(frame_a[1]))
+    fb = (np.asarray(frame_b[0]), np.asarray(frame_b[1]))
+    if fa[0].dtype == np.float64:
+        fa, fb = (num.conv(fa[0]), num.conv(fa[1])), (num.conv(fb[0]), num.conv(fb[1]))
+    wa, na, da, ca = _world(num, fa, sh_a)
+    wb, nb, db, _ = _world(num, fb, sh_b)
+    a, face_a, gap_a, all_a = _face_query(num, na, da, wb)
+    b, face_b, gap_b, all_b = _face_query(num, nb, db, wa)
+    e, axis, pair, (edge_seps, edge_axes) = _edge_query(num, wa, wb, sh_a["edges"], sh_b["edges"], ca[:, 0])
+    faces = max(a, b)
+    sep = faces if e is None else max(faces, e)
+    margins = {"touch": abs(float(sep)), "ab": abs(float(a - b)), "edge": np.inf if e is None else abs(float(e - faces) - EDGE_BIAS),
+               "ref_face": np.inf, "inc_face": np.inf, "clip": np.inf}
+    # the axis of the largest query, from A towards B, and how far the next other axis is behind it (metres)
+    if e is not None and e > faces:
+        best_axis = axis
+    else:
+        best_axis = na[:, face_a] if a >= b else -nb[:, face_b]
+    values = np.concatenate([num.to_f64(all_a), num.to_f64(all_b), edge_seps])
+    axes = np.concatenate([num.to_f64(na), -num.to_f64(nb), edge_axes], axis=1)
+    other = np.abs(num.to_f64(best_axis) @ axes) < 1 - 1e-9
+    unique = float(sep) - values[other].max() if other.any() else np.inf
+    margins["axis"] = unique
+    out = {"separated": bool(sep >= 0), "separation": faces, "axis": best_axis, "depth": -sep, "query": (a, b, e),
+           "margins": margins, "p_ref": [], "p_inc": [], "face_axes": (num.to_f64(na), -num.to_f64(nb)),
+           "feature": None, "index_a": None, "index_b": None}
+    if out["separated"]:
+        return out
+    if e is not None and e - faces > EDGE_BIAS:                          # the edge pair must beat both faces by the bias
+        i = _supporting_edge(num, wa, sh_a["edges"], wa[:, sh_a["edges"][pair[0], 1]] - wa[:, sh_a["edges"][pair[0], 0]], axis, 1)
+        j = _supporting_edge(num, wb, sh_b["edges"], wb[:, sh_b["edges"][pair[1], 1]] - wb[:, sh_b["edges"][pair[1], 0]], axis, -1)
+        ea, eb = sh_a["edges"][i], sh_b["edges"][j]
+        pa, pb = _closest_on_segments(num, wa[:, ea[0]], wa[:, ea[1]], wb[:, eb[0]], wb[:, eb[1]])
+        out.update(separation=e, feature=EDGES, edge_a=frozenset(int(x) for x in ea), edge_b=frozenset(int(x) for x in eb), p_ref=[pa], p_inc=[pb])
+        return out
+    if a >= b:                                                           # the reference face goes to A on a tie
+        feature, rf, gap, w_ref, n_ref, d_ref, sh_ref, w_inc, n_inc, sh_inc = FACE_A, face_a, gap_a, wa, na, da, sh_a, wb, nb, sh_b
+    else:
+        feature, rf, gap, w_ref, n_ref, d_ref, sh_ref, w_inc, n_inc, sh_inc = FACE_B, face_b, gap_b, wb, nb, db, sh_b, wa, na, sh_a
+    normal, disp = n_ref[:, rf], d_ref[rf]
+    cosines = dot(n_inc, normal[:, None])                                # collision.rs:76-85, first minimum
+    inc = int(np.argmin(cosines))
+    margins["ref_face"], margins["inc_face"] = gap, _runner_up(num, -cosines, inc)
+    poly, clip = _clip(num, [w_inc[:, v] for v in sh_inc["faces"][inc]], [w_ref[:, v] for v in sh_ref["faces"][rf]], normal)
+    for p in poly:
+        depth = dot(normal, p) - disp
+        if depth != 0:
+            clip = min(clip, abs(float(depth)))
+        if depth < 0:                                                    # strictly below the reference plane
+            out["p_inc"].append(p)
+            out["p_ref"].append(p - normal * depth)                      # Plane::project, geometry.rs:45-47
+    margins["clip"] = clip
+    out.update(feature=feature, index_a=rf if feature == FACE_A else inc, index_b=inc if feature == FACE_A else rf)
+    return out
+
+
+def decided(m, tau):
+    """No discrete decision of the manifold has a margin in (0, tau]: an exact tie is decided by the stated rule."""
+    g = m["margins"]
+    keys = ("touch",) if m["separated"] else (("touch", "edge") if m["feature"] == EDGES else
+                                              ("touch", "ab", "edge", "ref_face", "inc_face", "clip"))
+    return not any(0 < g[k] <= tau for k in keys)
+
+
+def manifold_points(manifolds):
+    """Flat contact list of stage S from {(i, j): stage N result}: (inc, ref, pair, p_inc (3, P), p_ref (3, P))."""
+    inc, ref, pair, p_inc, p_ref = [], [], [], [], []
+    for k, ((i, j), m) in enumerate(sorted(manifolds.items())):
+        if m["separated"]:
+            continue
+        r, c = (j, i) if m["feature"] == FACE_B else (i, j)             # reference body: A for FACE_A and EDGES
+        for pr, pi in zip(m["p_ref"], m["p_inc"]):
+            inc.append(c), ref.append(r), pair.append(k), p_inc.append(pi), p_ref.append(pr)
+    return inc, ref, pair, p_inc, p_ref
+
+
+def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.inf, max_depenetration_speed=0.0, num=None,
+            mutation=None, tau=0.0):
+    """Stage S: one contacts substep (steps 1, 3, 4, 5 of xpbd_pairs_oracle.h) of n bodies ((n, 38) f64).  shapes: list of
+    shape() dicts.  manifolds: {(i, j), i < j: {"feature", "p_ref": [(3,)], "p_inc": [(3,)]}} of the touching pairs at the
+    post-integrate frames, or None: stage N on every pair (stage S o N, the fully independent substep).  mu: per-body
+    friction coefficients (None: the reference's contact), ground_mu the plane's.  mutation: one of MUTATIONS, a
+    deliberately wrong reading for the mutation check.
+
+    Returns a dict: state (n, 38) model scalars; frames: the post-integrate frames [(position, rotation)]; manifolds: the
+    ones used; per body: mask, margin, cond, flip_margin, domain (as xprec_model.step), branch (smallest distance in
+    metres of a friction or depenetration-limit comparison from its threshold) and pair_cond (smallest |c1 - c0| of a
+    pair point); undecided: the pairs whose stage N manifold has a margin in (0, tau]."""
+    assert mutation is None or mutation in MUTATIONS
+    num = num or xm.native()
+    sqrt = num.sqrt
+    b64 = np.ascontiguousarray(bodies, dtype=np.float64).reshape(-1, 38)
+    n = b64.shape[0]
+    sid = np.asarray(shape_id, dtype=np.int64)
+    s = xm._unpack(b64, num)
+    im, M, com = s["inverse_mass"], s["inverse_inertia"], s["center_of_mass"]
+    pos, rot, vel, ang = s["position"], s["rotation"], s["velocity"], s["angular_velocity"]
+    hx = num.const(float(h))
+    compliance = num.const("1e-6") / (hx * hx)                           # solver.rs:20
+    limit = hx * num.const(float(max_depenetration_speed)) if max_depenetration_speed > 0 else None
+    domain = np.ones(n, dtype=bool)
+    vmax = max(len(shapes[k]["verts"]) for k in set(sid.tolist()))
+    counts = np.array([len(shapes[k]["verts"]) for k in sid])
+    slots = np.zeros((n, vmax, 3))
+    for b in range(n):
+        slots[b, :counts[b]] = shapes[sid[b]]["verts"]
+    vert = [num.conv(slots[:, v].T) for v in range(vmax)]
+
+    # 1. past = pose; integrate; P1 = Rigid::frame()                        solver.rs:7-10
+    past_pos, past_rot = pos, rot
+    past_p = pos + com + qrot(rot, -com)
+    pos, rot, vel, ang = xm.integrate(s, pos, rot, vel, ang, hx, sqrt)
+    p1_p, p1_q = pos + com + qrot(rot, -com), rot
+    frames = [(p1_p[:, b], p1_q[:, b]) for b in range(n)]
+
+    # 2. manifolds of all pairs by brute force (stage N), unless given
+    undecided = []
+    if manifolds is None:
+        manifolds = {}
+        centre = np.array([num.to_f64(frame_apply(p1_p[:, b], p1_q[:, b], num.conv(shapes[sid[b]]["centroid"]))) for b in range(n)])
+        for i in range(n):
+            for j in range(i + 1, n):
+                reach = shapes[sid[i]]["radius"] + shapes[sid[j]]["radius"]
+                if np.linalg.norm(centre[i] - centre[j]) > reach + 1e-3:   # the bounding spheres are a millimetre apart
+                    continue
+                m = manifold(frames[i], frames[j], shapes[sid[i]], shapes[sid[j]], num)
+                if not decided(m, tau):
+                    undecided.append((i, j))
+                if not m["separated"]:
+                    manifolds[(i, j)] = m
+
+    # 3. ground contacts from P1, sequentially per body                     solver.rs:12-13
+    body_mu = None
+    if mu is not None or np.isfinite(ground_mu):
+        body_mu = np.minimum(np.full(n, np.inf) if mu is None else np.asarray(mu, dtype=np.float64), ground_mu)
+    pos, rot, g = xm.ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain, body_mu, limit)
+
+    # 4. pair contacts, Jacobi: every point from the poses after step 3, a body applies the average of its points
+    inc, ref, pair, p_inc, p_ref = manifold_points(manifolds)
+    branch, pair_cond = g["branch"].copy(), np.full(n, np.inf)
+    if inc:
+        inc, ref, pair = np.array(inc), np.array(ref), np.array(pair)
+        c0, surface = np.stack(p_inc, axis=1), np.stack(p_ref, axis=1)
+        if c0.dtype == np.float64:
+            c0, surface = num.conv(c0), num.conv(surface)
+        correction = surface - c0
+        cc = dot(correction, correction)
+        delta = (frame_delta(p1_p[:, inc], p1_q[:, inc], past_p[:, inc], past_rot[:, inc], c0)
+                 - frame_delta(p1_p[:, ref], p1_q[:, ref], past_p[:, ref], past_rot[:, ref], surface))
+        tangential = delta - correction * (dot(delta, correction) / cc)                 # collision.rs:24-29, two bodies
+        k, gap = np.ones(len(inc)), np.full(len(inc), np.inf)
+        if mu is not None:
+            point_mu = np.minimum(np.asarray(mu, dtype=np.float64)[inc], np.asarray(mu, dtype=np.float64)[ref])
+            against = cc
+            if mutation == "friction_against_distance":
+                full = correction - tangential
+                against = dot(full, full)
+            k, gap = xm.friction_factor(num, point_mu, correction, tangential, against)
+        if mutation == "tangential_dropped":
+            k = k * 0
+        c1 = surface - tangential * k
+        diff = c1 - c0                                                                   # constraint.rs:13-23
+        dist = sqrt(dot(diff, diff))
+        direction = diff / dist
+        Mi, Mr = M[:, :, inc], M[:, :, ref]
+        if mutation == "transposed_inertia":
+            Mi, Mr = Mi.transpose(1, 0, 2), Mr.transpose(1, 0, 2)
+        origin_i, origin_r = pos[:, inc] + com[:, inc], pos[:, ref] + com[:, ref]       # rigid.rs:113-123, position + com
+        if mutation == "arm_without_com":
+            origin_i, origin_r = pos[:, inc], pos[:, ref]
+        arm_i, arm_r = c0 - origin_i, surface - origin_r
+        ai = qrot(conj(rot[:, inc]), cross(arm_i, direction))                           # constraint.rs:25-32
+        ar = qrot(conj(rot[:, ref]), cross(arm_r, direction))
+        w = im[inc] + dot(matvec(Mi, ai), ai) + im[ref] + dot(matvec(Mr, ar), ar)
+        error, clamp = xm.limited(num, dist, limit, delta, correction, cc)
+        lam = error / (w + compliance)
+        impulse_i = direction * lam                                                      # +lambda dir on the incident body at c0
+        impulse_r = direction * (lam if mutation == "reference_sign" else -lam)          # -lambda dir on the reference body
+        dpos_i, dpos_r = impulse_i * im[inc], impulse_r * im[ref]
+        drot_i = qmul(pure(cross(matvec(Mi, arm_i), impulse_i)) * 0.5, rot[:, inc])     # rigid.rs:118-122
+        drot_r = qmul(pure(cross(matvec(Mr, arm_r), impulse_r)) * 0.5, rot[:, ref])
+        sum_p, sum_q, count = pos * 0, rot * 0, np.zeros(n, dtype=np.int64)
+        seen = set()
+        d64 = num.to_f64(dist)
+        both = np.minimum(gap, clamp)
+        for t in range(len(inc)):
+            for body, dp, dq in ((inc[t], dpos_i[:, t], drot_i[:, t]), (ref[t], dpos_r[:, t], drot_r[:, t])):
+                sum_p[:, body] = sum_p[:, body] + dp
+                sum_q[:, body] = sum_q[:, body] + dq
+                if mutation != "average_by_pairs" or (body, pair[t]) not in seen:
+                    count[body] += 1
+                seen.add((body, pair[t]))
+                pair_cond[body] = min(pair_cond[body], d64[t])
+                branch[body] = min(branch[body], both[t])
+        hit = np.nonzero(count)[0]
+        cnt = num.conv(count[hit].astype(np.float64))
+        pos, rot = pos.copy(), rot.copy()
+        pos[:, hit] = pos[:, hit] + sum_p[:, hit] / cnt
+        rot[:, hit] = normalize_q(rot[:, hit] + sum_q[:, hit] / cnt, sqrt)
+
+    # 5. Rigid::derive(past, h)                                             solver.rs:15
+    vel, ang, _, flip_margin = xm.derive(num, pos, rot, past_pos, past_rot, hx)
+    s.update(position=pos, rotation=rot, velocity=vel, angular_velocity=ang)
+    return {"state": xm._pack(s), "frames": frames, "manifolds": manifolds, "undecided": undecided, "mask": g["mask"],
+            "margin": g["margin"], "cond": g["cond"], "flip_margin": flip_margin, "domain": domain, "branch": branch,
+            "pair_cond": pair_cond}
