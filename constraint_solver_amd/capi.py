@@ -58,6 +58,9 @@ ABI_SYMBOLS = [
     "xpbd_world_download_contact_events", "xpbd_multi_world_set_contact_report", "xpbd_multi_world_contact_report_counts",
     "xpbd_multi_world_download_pair_contacts", "xpbd_multi_world_download_contact_events",
     "xpbd_world_set_materials", "xpbd_multi_world_set_materials", "xpbd_world_set_restitution",
+    "xpbd_world_set_external_wrench", "xpbd_world_set_external_wrench_device", "xpbd_world_apply_impulses",
+    "xpbd_world_apply_impulses_device", "xpbd_world_set_dynamics", "xpbd_world_get_dynamics",
+    "xpbd_multi_world_set_external_wrench", "xpbd_multi_world_apply_impulses",
 ]
 
 
@@ -110,6 +113,19 @@ COLLISION_FILTER_DTYPE = np.dtype([("group", "<u4"), ("mask", "<u4")])
 FILTER_JOINTED = 1                # bodies joined by a joint never collide
 # xpbd_material as a numpy record (16 bytes): Coulomb friction coefficient >= 0 (+inf: the reference's contact), reserved = 0
 MATERIAL_DTYPE = np.dtype([("friction", "<f8"), ("reserved", "<f8")])
+# body edits (EXTENSION): xpbd_impulse as a ctypes struct and as a numpy record (80 bytes)
+IMPULSE_AT_POINT, IMPULSE_AT_CENTRE = 0, 1
+DYNAMIC_DOUBLES = 13              # a row of set_dynamics / get_dynamics: position, rotation {s,x,y,z}, velocity, angular_velocity
+
+
+class Impulse(C.Structure):
+    """xpbd_impulse"""
+    _fields_ = [("body", C.c_uint32), ("flags", C.c_uint32), ("impulse", C.c_double * 3), ("point", C.c_double * 3),
+                ("angular_impulse", C.c_double * 3)]
+
+
+IMPULSE_DTYPE = np.dtype([("body", "<u4"), ("flags", "<u4"), ("impulse", "<f8", (3,)), ("point", "<f8", (3,)),
+                          ("angular_impulse", "<f8", (3,))])
 # xpbd_gjk_result as a numpy record (96 bytes)
 GJK_DTYPE = np.dtype([("status", "<i4"), ("gjk_iterations", "<u4"), ("epa_iterations", "<u4"), ("reserved", "<u4"),
                       ("depth", "<f8"), ("normal", "<f8", (3,)), ("point_a", "<f8", (3,)), ("point_b", "<f8", (3,))])
@@ -279,6 +295,17 @@ def hip_lib():
             pass
         try:
             L.xpbd_world_set_restitution.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            L.xpbd_world_set_external_wrench.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.xpbd_world_set_external_wrench_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.xpbd_world_apply_impulses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_apply_impulses_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_set_dynamics.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.xpbd_world_get_dynamics.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.xpbd_multi_world_set_external_wrench.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.xpbd_multi_world_apply_impulses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -529,6 +556,43 @@ class World:
         else:
             _check(hip_lib().xpbd_world_raycast_masked_device(self._h, C.c_void_p(rays_ptr), n, flags, mask, C.c_void_p(hits_ptr)))
 
+    # body edits (include/xpbd.h, "Body EDITS"): forces, impulses and state of resident bodies
+    def set_external_wrench(self, indices=None, force=None, torque=None):
+        """external_force / external_torque of the listed bodies (None: all bodies, in order) = rows of force / torque
+        ((n, 3); None leaves that field alone).  Waits."""
+        _check(_set_wrench(hip_lib().xpbd_world_set_external_wrench, self._h, indices, force, torque))
+
+    def set_external_wrench_device(self, dev_indices_ptr, n, dev_force_ptr, dev_torque_ptr):
+        """Device pointers (0 / None: no index list, a field left alone), stream-ordered on the world's stream."""
+        _check(hip_lib().xpbd_world_set_external_wrench_device(self._h, C.c_void_p(dev_indices_ptr or None), n,
+                                                               C.c_void_p(dev_force_ptr or None), C.c_void_p(dev_torque_ptr or None)))
+
+    def apply_impulses(self, impulses):
+        """impulses: IMPULSE_DTYPE records (see impulses()), applied per body in list order.  Waits."""
+        imp = np.ascontiguousarray(impulses, dtype=IMPULSE_DTYPE).reshape(-1)
+        _check(hip_lib().xpbd_world_apply_impulses(self._h, imp.ctypes.data if imp.size else None, imp.size))
+
+    def apply_impulses_device(self, dev_list_ptr, n):
+        """Device array of n xpbd_impulse, the entries of one body adjacent; stream-ordered on the world's stream."""
+        _check(hip_lib().xpbd_world_apply_impulses_device(self._h, C.c_void_p(dev_list_ptr), n))
+
+    def set_dynamics(self, indices, rows):
+        """rows: (n, 13) position, rotation {s,x,y,z}, velocity, angular_velocity of the listed bodies (None: all).  Waits."""
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        r = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, DYNAMIC_DOUBLES)
+        _check(hip_lib().xpbd_world_set_dynamics(self._h, None if idx is None else idx.ctypes.data, r.shape[0], r.ctypes.data if r.size else None))
+
+    def get_dynamics(self, indices=None):
+        """(n, 13) rows of the listed bodies (None: all bodies, in order)."""
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        n = self.n if idx is None else idx.size
+        out = np.empty((n, DYNAMIC_DOUBLES), dtype=np.float64)
+        _check(hip_lib().xpbd_world_get_dynamics(self._h, None if idx is None else idx.ctypes.data, n, out.ctypes.data if n else None))
+        return out
+
+    def get_stream(self):
+        return hip_lib().xpbd_world_get_stream(self._h)
+
     def set_stream(self, stream_ptr):
         _check(hip_lib().xpbd_world_set_stream(self._h, C.c_void_p(stream_ptr)))
 
@@ -575,6 +639,32 @@ def _contact_events(counts_fn, download_fn, h):
     n = C.c_uint32(0)
     _check(download_fn(h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
     return out
+
+
+def impulses(body, impulse, point=None, angular_impulse=None):
+    """IMPULSE_DTYPE records from bodies, (n, 3) impulses (broadcast), world points (None: at the centre of mass) and angular
+    impulses (None: zero)."""
+    b = np.atleast_1d(np.asarray(body, dtype=np.uint32))
+    out = np.zeros(b.size, dtype=IMPULSE_DTYPE)
+    out["body"], out["impulse"] = b, impulse
+    if point is None:
+        out["flags"] = IMPULSE_AT_CENTRE
+    else:
+        out["point"] = point
+    if angular_impulse is not None:
+        out["angular_impulse"] = angular_impulse
+    return out
+
+
+def _set_wrench(fn, h, indices, force, torque):
+    idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    f = None if force is None else np.ascontiguousarray(force, dtype=np.float64).reshape(-1, 3)
+    t = None if torque is None else np.ascontiguousarray(torque, dtype=np.float64).reshape(-1, 3)
+    n = idx.size if idx is not None else (f if f is not None else t).shape[0] if (f is not None or t is not None) else 0
+    for a in (f, t):
+        if a is not None and a.shape[0] != n:
+            raise ValueError("force / torque need one row per listed body")
+    return fn(h, None if idx is None else idx.ctypes.data, n, None if f is None else f.ctypes.data, None if t is None else t.ctypes.data)
 
 
 def _filters(filters):
@@ -693,6 +783,15 @@ class MultiWorld:
         m = _materials(materials)
         _check(hip_lib().xpbd_multi_world_set_materials(self._h, None if m is None else m.ctypes.data, 0 if m is None else m.size,
                                                         ground_friction))
+
+    def set_external_wrench(self, indices=None, force=None, torque=None):
+        """World.set_external_wrench with GLOBAL body indices (not collective: every rank passes the same list)."""
+        _check(_set_wrench(hip_lib().xpbd_multi_world_set_external_wrench, self._h, indices, force, torque))
+
+    def apply_impulses(self, impulses):
+        """World.apply_impulses with GLOBAL bodies (not collective: every rank passes the same list)."""
+        imp = np.ascontiguousarray(impulses, dtype=IMPULSE_DTYPE).reshape(-1)
+        _check(hip_lib().xpbd_multi_world_apply_impulses(self._h, imp.ctypes.data if imp.size else None, imp.size))
 
     def upload(self, bodies, shape_id, first_global, n_global, joints=None):
         """bodies / shape_id: the slice of the caller's bodies this process hands over, global indices [first_global,

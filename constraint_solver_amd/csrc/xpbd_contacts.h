@@ -148,6 +148,15 @@ hipError_t launch_export_dynamic(const BodyArrays &b, const uint32_t *indices, u
 hipError_t launch_import_dynamic(const BodyArrays &b, const uint32_t *indices, const uint32_t *rows, uint32_t n, const double *buf,
                                  hipStream_t stream); // rows: NULL = row k of buf for entry k
 
+// Body edits (include/xpbd.h, "Body EDITS"), device arrays, stream-ordered.  external_force / external_torque of body
+// indices[k] (NULL: body k) = force / torque[3k..3k+2] (NULL: that field is left alone);  the impulses of `list` (16-byte
+// aligned; the entries of one body adjacent) on the velocities of their bodies, in list order.  An index outside the world is
+// skipped.  More than kMaxEditEntries entries, or a misaligned list, is hipErrorInvalidValue.
+constexpr uint32_t kMaxEditEntries = 1u << 29;
+hipError_t launch_set_wrench(const BodyArrays &b, const uint32_t *indices, uint32_t n, const double *force, const double *torque,
+                             hipStream_t stream);
+hipError_t launch_apply_impulses(const BodyArrays &b, const xpbd_impulse *list, uint32_t n, hipStream_t stream);
+
 // Halo validity: snapshot[3k..3k+2] = position of body indices[k]; *out = max(*out, max_k scale[k] * |position - snapshot|^2)
 // (scale == NULL: 1).
 hipError_t launch_snapshot_positions(const BodyArrays &b, const uint32_t *indices, uint32_t n, double *snapshot, hipStream_t stream);

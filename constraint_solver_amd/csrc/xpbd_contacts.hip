@@ -1356,6 +1356,92 @@ __global__ void k_import_dynamic(BodyArrays b, const uint32_t *__restrict__ indi
     b.dyn[(size_t)f * b.stride + indices[k]] = buf[(size_t)(rows ? rows[k] : k) * kDynFields + f];
 }
 
+// ---- body edits (include/xpbd.h, "Body EDITS") ----------------------------------------------------------------------------
+// external_force / external_torque of the listed bodies: one lane per (entry, component), three force components and then
+// three torque components; force / torque may be NULL (that field is left alone), indices NULL means body k.  An index
+// outside the world is skipped.
+__global__ void k_set_wrench(BodyArrays b, const uint32_t *__restrict__ indices, uint32_t n, const double *__restrict__ force,
+                             const double *__restrict__ torque)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * 6u)
+        return;
+    const uint32_t k = t / 6u, f = t - k * 6u;
+    const uint32_t i = indices ? indices[k] : k;
+    if (i >= b.n)
+        return;
+    if (f < 3u) {
+        if (force)
+            b.stat[(size_t)(S_EXT_FORCE + f) * b.stride + i] = force[3 * (size_t)k + f];
+    } else if (torque) {
+        b.stat[(size_t)(S_EXT_TORQUE + (f - 3u)) * b.stride + i] = torque[3 * (size_t)k + (f - 3u)];
+    }
+}
+
+// One xpbd_impulse (80 bytes = five 16-byte loads): {body | flags << 32, P.x} {P.y, P.z} {point.x, point.y}
+// {point.z, L.x} {L.y, L.z}.
+struct ImpulseEntry {
+    uint32_t body, flags;
+    Vec3 impulse, point, angular;
+};
+
+__device__ __forceinline__ ImpulseEntry load_impulse(const ulonglong2 *__restrict__ list, uint32_t k)
+{
+    const ulonglong2 *e = list + (size_t)k * 5;
+    const ulonglong2 q0 = e[0], q1 = e[1], q2 = e[2], q3 = e[3], q4 = e[4];
+    ImpulseEntry r;
+    r.body = (uint32_t)q0.x;
+    r.flags = (uint32_t)(q0.x >> 32);
+    r.impulse = Vec3{__longlong_as_double((long long)q0.y), __longlong_as_double((long long)q1.x), __longlong_as_double((long long)q1.y)};
+    r.point = Vec3{__longlong_as_double((long long)q2.x), __longlong_as_double((long long)q2.y), __longlong_as_double((long long)q3.x)};
+    r.angular = Vec3{__longlong_as_double((long long)q3.y), __longlong_as_double((long long)q4.x), __longlong_as_double((long long)q4.y)};
+    return r;
+}
+
+__device__ __forceinline__ uint32_t impulse_body(const ulonglong2 *__restrict__ list, uint32_t k)
+{
+    return reinterpret_cast<const uint32_t *>(list + (size_t)k * 5)[0];
+}
+
+// Impulses on the listed bodies, the entries of one body adjacent (a run) and applied in list order.  One lane per entry; the
+// lane of a run's first entry does the whole run -- the body's mass properties, centre and velocities are loaded once, every
+// entry is applied to the result of the one before with the restitution pass's impulse arithmetic, the velocities are stored
+// once -- and the other lanes leave at once.  No two lanes write one body, so there are no atomics and the result does not
+// depend on the launch shape.  A long run is serial in its lane by design (the order is the semantics); the lanes of a wave
+// that have shorter runs wait for it.  A body outside the world is skipped.
+__global__ void __launch_bounds__(kBlock) k_apply_impulses(BodyArrays b, const ulonglong2 *__restrict__ list, uint32_t n)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n)
+        return;
+    const uint32_t i = impulse_body(list, k);
+    if (k != 0 && impulse_body(list, k - 1) == i)
+        return;
+    if (i >= b.n)
+        return;
+    const uint32_t st = b.stride;
+    const double inv_mass = b.stat[(size_t)S_INV_MASS * st + i];
+    Mat3 inv_inertia;
+    inv_inertia.cx = load3(b.stat, S_INV_INERTIA + 0, st, i);
+    inv_inertia.cy = load3(b.stat, S_INV_INERTIA + 3, st, i);
+    inv_inertia.cz = load3(b.stat, S_INV_INERTIA + 6, st, i);
+    const Vec3 centre = load3(b.dyn, D_POS, st, i) + load3(b.stat, S_COM, st, i);
+    Vec3 vel = load3(b.dyn, D_VEL, st, i), ang = load3(b.dyn, D_ANG, st, i);
+    for (uint32_t j = k; j < n; ++j) {
+        const ImpulseEntry e = load_impulse(list, j);
+        if (e.body != i)
+            break;
+        vel = vel + e.impulse * inv_mass;
+        if (!(e.flags & XPBD_IMPULSE_AT_CENTRE)) {
+            const Vec3 arm = e.point - centre;
+            ang = ang + cross(inv_inertia * arm, e.impulse);
+        }
+        ang = ang + inv_inertia * e.angular;
+    }
+    store3(b.dyn, D_VEL, st, i, vel);
+    store3(b.dyn, D_ANG, st, i, ang);
+}
+
 // Halo validity (multi-GPU): positions of the listed bodies when the halos were chosen ...
 __global__ void k_snapshot_positions(BodyArrays b, const uint32_t *__restrict__ indices, uint32_t n, double *__restrict__ snapshot)
 {
@@ -1685,6 +1771,26 @@ hipError_t launch_import_dynamic(const BodyArrays &b, const uint32_t *indices, c
 {
     if (n)
         hipLaunchKernelGGL(k_import_dynamic, dim3(blocks_for(n * kDynFields)), dim3(kBlock), 0, stream, b, indices, rows, n, buf);
+    return hipGetLastError();
+}
+
+hipError_t launch_set_wrench(const BodyArrays &b, const uint32_t *indices, uint32_t n, const double *force, const double *torque,
+                             hipStream_t stream)
+{
+    if (n > kMaxEditEntries)
+        return hipErrorInvalidValue;
+    if (n && (force || torque))
+        hipLaunchKernelGGL(k_set_wrench, dim3(blocks_for(n * 6u)), dim3(kBlock), 0, stream, b, indices, n, force, torque);
+    return hipGetLastError();
+}
+
+hipError_t launch_apply_impulses(const BodyArrays &b, const xpbd_impulse *list, uint32_t n, hipStream_t stream)
+{
+    static_assert(sizeof(xpbd_impulse) == 80 && sizeof(ulonglong2) == 16, "an xpbd_impulse is five 16-byte loads");
+    if (n > kMaxEditEntries || (reinterpret_cast<uintptr_t>(list) & 15u))
+        return hipErrorInvalidValue;
+    if (n)
+        hipLaunchKernelGGL(k_apply_impulses, dim3(blocks_for(n)), dim3(kBlock), 0, stream, b, reinterpret_cast<const ulonglong2 *>(list), n);
     return hipGetLastError();
 }
 

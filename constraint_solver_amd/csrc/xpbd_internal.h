@@ -100,6 +100,7 @@ struct xpbd_joint;
 struct xpbd_joint_limit;
 struct xpbd_material;
 struct xpbd_ray;
+struct xpbd_impulse;
 struct xpbd_ray_hit;
 struct xpbd_pair_contact;
 struct xpbd_contact_point;
@@ -158,4 +159,11 @@ int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joi
 int check_per_body(const char *who, const char *what, const void *values, uint32_t n, uint32_t n_bodies, const char *count = "n");
 // ... and of the records of xpbd_world_set_materials: friction >= 0 (+inf allowed, NaN not), reserved == 0.
 int check_materials(const char *who, const xpbd_material *materials, uint32_t n);
+// ... of the host variants of the body edits (include/xpbd.h, "Body EDITS") against a world of n_bodies bodies, after the
+// caller has dealt with a NULL world and n == 0: a world without bodies, an index list (NULL: bodies 0..n-1, then n ==
+// n_bodies; an index >= n_bodies; with `unique`, an index twice), `count` doubles that must all be finite (`what` names them;
+// NULL values pass), and an impulse list (NULL, a body >= n_bodies, unknown flags, non-finite components).
+int check_edit_indices(const char *who, const uint32_t *indices, uint32_t n, uint32_t n_bodies, bool unique);
+int check_edit_finite(const char *who, const char *what, const double *values, size_t count);
+int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32_t n_bodies);
 } // namespace xpbd

@@ -1097,6 +1097,21 @@ int push_to_shards(xpbd_multi_world *mw, PushSetting push, const char *what)
     return XPBD_OK;
 }
 
+// Body edits (include/xpbd.h, "Body EDITS") reach every local shard that HOLDS the body, as owner or as ghost: the slot of
+// global body g in shard s (local_ids is ascending), or -1.
+int32_t slot_in_shard(const Shard &s, uint32_t g)
+{
+    const auto at = std::lower_bound(s.local_ids.begin(), s.local_ids.end(), g);
+    return at != s.local_ids.end() && *at == g ? (int32_t)(at - s.local_ids.begin()) : -1;
+}
+
+// The tail of an edit: a shard that fails here has not done what the others did.
+int edit_failed(xpbd_multi_world *mw, int rc, const char *what)
+{
+    mw->broken = true;
+    return set_error(rc, "%s -- the shards' %s disagree now: destroy this xpbd_multi_world", xpbd_last_error(), what);
+}
+
 // The second half of every plan: the boundary lists of all ranks fix the rows of the per-substep all-gather, the records of
 // the bodies that change hands or are mirrored travel, and every shard's local world is re-packed on its device.  Collective.
 int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &plans, double edge, PlanTrace &trace)
@@ -2414,6 +2429,70 @@ try {
         mw->materials.clear();
     mw->ground_friction = ground_friction;
     return push_to_shards(mw, push_materials, "materials");
+} XPBD_MULTI_ABI_CATCH
+
+int xpbd_multi_world_set_external_wrench(xpbd_multi_world *mw, const uint32_t *indices, uint32_t n, const double *force_xyz,
+                                         const double *torque_xyz)
+try {
+    const char *who = "xpbd_multi_world_set_external_wrench";
+    XPBD_TRY(check_usable(mw, who));
+    if (n == 0)
+        return XPBD_OK;
+    if (!force_xyz && !torque_xyz)
+        return set_error(XPBD_E_INVALID, "%s: force_xyz and torque_xyz are both NULL", who);
+    if (!mw->planned)
+        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    XPBD_TRY(xpbd::check_edit_indices(who, indices, n, mw->n_global, true));
+    XPBD_TRY(xpbd::check_edit_finite(who, "force_xyz", force_xyz, (size_t)n * 3));
+    XPBD_TRY(xpbd::check_edit_finite(who, "torque_xyz", torque_xyz, (size_t)n * 3));
+    std::vector<uint32_t> slots;
+    std::vector<double> force, torque;
+    for (Shard &s : mw->shards) {
+        slots.clear(), force.clear(), torque.clear();
+        for (uint32_t k = 0; k < n; ++k) {
+            const int32_t slot = slot_in_shard(s, indices ? indices[k] : k);
+            if (slot < 0)
+                continue;
+            slots.push_back((uint32_t)slot);
+            if (force_xyz)
+                force.insert(force.end(), force_xyz + 3 * (size_t)k, force_xyz + 3 * (size_t)k + 3);
+            if (torque_xyz)
+                torque.insert(torque.end(), torque_xyz + 3 * (size_t)k, torque_xyz + 3 * (size_t)k + 3);
+        }
+        if (slots.empty())
+            continue;
+        if (int rc = xpbd_world_set_external_wrench(s.world, slots.data(), (uint32_t)slots.size(), force_xyz ? force.data() : nullptr,
+                                                    torque_xyz ? torque.data() : nullptr))
+            return edit_failed(mw, rc, "external forces");
+    }
+    return XPBD_OK;
+} XPBD_MULTI_ABI_CATCH
+
+int xpbd_multi_world_apply_impulses(xpbd_multi_world *mw, const xpbd_impulse *list, uint32_t n)
+try {
+    const char *who = "xpbd_multi_world_apply_impulses";
+    XPBD_TRY(check_usable(mw, who));
+    if (n == 0)
+        return XPBD_OK;
+    if (!mw->planned)
+        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    XPBD_TRY(xpbd::check_impulses(who, list, n, mw->n_global));
+    std::vector<xpbd_impulse> local;
+    for (Shard &s : mw->shards) {
+        local.clear();
+        for (uint32_t k = 0; k < n; ++k) { // list order kept: the shard's world sorts by slot (stable), which ascends with the global id
+            const int32_t slot = slot_in_shard(s, list[k].body);
+            if (slot < 0)
+                continue;
+            local.push_back(list[k]);
+            local.back().body = (uint32_t)slot;
+        }
+        if (local.empty())
+            continue;
+        if (int rc = xpbd_world_apply_impulses(s.world, local.data(), (uint32_t)local.size()))
+            return edit_failed(mw, rc, "velocities");
+    }
+    return XPBD_OK;
 } XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, const uint32_t *shape_id, uint32_t first_global, uint32_t n_bodies,

@@ -4,6 +4,8 @@
 // one world, and turns each ABI call into kernel launches from xpbd_kernels.hip.
 // There is no CPU fallback: without a usable HIP device every compute entry
 // point fails with XPBD_E_NO_DEVICE / XPBD_E_HIP.
+#include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -165,6 +167,9 @@ struct xpbd_world {
     DeviceBuffer rs_restitution, rs_start;
     // scene queries (xpbd_world_raycast*): scratch of one call, and the staging of the host variant's rays and hits
     DeviceBuffer q_rec, q_partials, q_grid, q_cell_start, q_cell_fill, q_items, q_scan, q_brute, q_rays, q_hits;
+    // body edits (xpbd_world_set_external_wrench, _apply_impulses, _set_dynamics, _get_dynamics): the staging of the host
+    // variants' indices, values (force + torque, or rows of 13 doubles) and impulse lists
+    DeviceBuffer ed_indices, ed_values, ed_list;
     // state history (xpbd_world_history_*): `history_length` slots of history_slot_bytes() in one growing block
     DeviceBuffer history;
     uint32_t history_length = 0;
@@ -1011,6 +1016,55 @@ int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joi
             return set_error(XPBD_E_INVALID, "%s: limit %u has bounds [%g, %g] (need -pi <= lower <= upper <= pi)", who, k, l.lower, l.upper);
         if (l.kind == XPBD_LIMIT_SWING && l.lower != 0.0)
             return set_error(XPBD_E_INVALID, "%s: swing limit %u needs lower = 0 (got %g)", who, k, l.lower);
+    }
+    return XPBD_OK;
+}
+
+int check_edit_indices(const char *who, const uint32_t *indices, uint32_t n, uint32_t n_bodies, bool unique)
+{
+    if (n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    if (!indices) {
+        if (n != n_bodies)
+            return set_error(XPBD_E_INVALID, "%s: indices == NULL names the bodies 0..n-1, but n = %u and the world holds %u bodies", who, n, n_bodies);
+        return XPBD_OK;
+    }
+    std::vector<uint8_t> seen(unique ? n_bodies : 0u, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        if (indices[k] >= n_bodies)
+            return set_error(XPBD_E_INVALID, "%s: indices[%u] = %u but the world holds %u bodies", who, k, indices[k], n_bodies);
+        if (unique && seen[indices[k]]++)
+            return set_error(XPBD_E_INVALID, "%s: indices[%u] = %u is listed twice", who, k, indices[k]);
+    }
+    return XPBD_OK;
+}
+
+int check_edit_finite(const char *who, const char *what, const double *values, size_t count)
+{
+    for (size_t k = 0; values && k < count; ++k)
+        if (!std::isfinite(values[k]))
+            return set_error(XPBD_E_INVALID, "%s: %s[%zu] = %g (must be finite)", who, what, k, values[k]);
+    return XPBD_OK;
+}
+
+int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32_t n_bodies)
+{
+    if (!list)
+        return set_error(XPBD_E_INVALID, "%s: NULL list", who);
+    if (n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    for (uint32_t k = 0; k < n; ++k) {
+        const xpbd_impulse &e = list[k];
+        if (e.body >= n_bodies)
+            return set_error(XPBD_E_INVALID, "%s: list[%u].body = %u but the world holds %u bodies", who, k, e.body, n_bodies);
+        if (e.flags & ~XPBD_IMPULSE_AT_CENTRE)
+            return set_error(XPBD_E_INVALID, "%s: list[%u] has unknown flags 0x%x", who, k, e.flags);
+        bool finite = true;
+        for (int a = 0; a < 3; ++a)
+            finite = finite && std::isfinite(e.impulse[a]) && std::isfinite(e.angular_impulse[a]) &&
+                     ((e.flags & XPBD_IMPULSE_AT_CENTRE) || std::isfinite(e.point[a]));
+        if (!finite)
+            return set_error(XPBD_E_INVALID, "%s: list[%u] has a component that is not finite", who, k);
     }
     return XPBD_OK;
 }
@@ -2119,6 +2173,166 @@ try {
 } XPBD_ABI_CATCH
 
 uint32_t xpbd_world_history_length(const xpbd_world *w) noexcept { return w ? w->history_length : 0; }
+
+// ---- body edits (include/xpbd.h, "Body EDITS") ---------------------------------------------------------------------------------
+namespace {
+// Room in the staging buffers of the host variants (growing one frees the old block, which queued work may still use).
+int reserve_edit_staging(xpbd_world *w, size_t index_bytes, size_t value_bytes, size_t list_bytes)
+{
+    if (w->ed_indices.bytes >= index_bytes && w->ed_values.bytes >= value_bytes && w->ed_list.bytes >= list_bytes)
+        return XPBD_OK;
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    XPBD_HIP_TRY(w->ed_indices.reserve(index_bytes));
+    XPBD_HIP_TRY(w->ed_values.reserve(value_bytes));
+    XPBD_HIP_TRY(w->ed_list.reserve(list_bytes));
+    return XPBD_OK;
+}
+
+// The host variants' index list on the device (NULL: 0..n-1 written out, for the kernels that have no such form).
+int stage_edit_indices(xpbd_world *w, const uint32_t *indices, uint32_t n, std::vector<uint32_t> &iota)
+{
+    if (!indices) {
+        iota.resize(n);
+        for (uint32_t k = 0; k < n; ++k)
+            iota[k] = k;
+        indices = iota.data();
+    }
+    XPBD_HIP_TRY(hipMemcpyAsync(w->ed_indices.ptr, indices, (size_t)n * 4, hipMemcpyHostToDevice, w->stream));
+    return XPBD_OK;
+}
+} // namespace
+
+int xpbd_world_set_external_wrench(xpbd_world *w, const uint32_t *indices, uint32_t n, const double *force_xyz, const double *torque_xyz)
+try {
+    const char *who = "xpbd_world_set_external_wrench";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0)
+        return XPBD_OK;
+    if (!force_xyz && !torque_xyz)
+        return set_error(XPBD_E_INVALID, "%s: force_xyz and torque_xyz are both NULL", who);
+    XPBD_TRY(xpbd::check_edit_indices(who, indices, n, w->n, true));
+    XPBD_TRY(xpbd::check_edit_finite(who, "force_xyz", force_xyz, (size_t)n * 3));
+    XPBD_TRY(xpbd::check_edit_finite(who, "torque_xyz", torque_xyz, (size_t)n * 3));
+    XPBD_TRY(bind_device(w));
+    const size_t half = (size_t)n * 3 * 8;
+    XPBD_TRY(reserve_edit_staging(w, (size_t)n * 4, 2 * half, 0));
+    double *dev_force = w->ed_values.as<double>(), *dev_torque = dev_force + (size_t)n * 3;
+    if (indices)
+        XPBD_HIP_TRY(hipMemcpyAsync(w->ed_indices.ptr, indices, (size_t)n * 4, hipMemcpyHostToDevice, w->stream));
+    if (force_xyz)
+        XPBD_HIP_TRY(hipMemcpyAsync(dev_force, force_xyz, half, hipMemcpyHostToDevice, w->stream));
+    if (torque_xyz)
+        XPBD_HIP_TRY(hipMemcpyAsync(dev_torque, torque_xyz, half, hipMemcpyHostToDevice, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_set_wrench(w->arrays(), indices ? w->ed_indices.as<uint32_t>() : nullptr, n, force_xyz ? dev_force : nullptr,
+                                         torque_xyz ? dev_torque : nullptr, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the caller's arrays are only borrowed
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_set_external_wrench_device(xpbd_world *w, const uint32_t *dev_indices, uint32_t n, const double *dev_force_xyz,
+                                          const double *dev_torque_xyz)
+try {
+    const char *who = "xpbd_world_set_external_wrench_device";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0)
+        return XPBD_OK;
+    if (!dev_force_xyz && !dev_torque_xyz)
+        return set_error(XPBD_E_INVALID, "%s: dev_force_xyz and dev_torque_xyz are both NULL", who);
+    if (w->n == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    if (!dev_indices && n != w->n)
+        return set_error(XPBD_E_INVALID, "%s: dev_indices == NULL names the bodies 0..n-1, but n = %u and the world holds %u bodies", who, n, w->n);
+    if (n > xpbd::kMaxEditEntries)
+        return set_error(XPBD_E_INVALID, "%s: n = %u (at most %u entries per call)", who, n, xpbd::kMaxEditEntries);
+    XPBD_TRY(bind_device(w));
+    XPBD_HIP_TRY(xpbd::launch_set_wrench(w->arrays(), dev_indices, n, dev_force_xyz, dev_torque_xyz, w->stream));
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_apply_impulses(xpbd_world *w, const xpbd_impulse *list, uint32_t n)
+try {
+    const char *who = "xpbd_world_apply_impulses";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0)
+        return XPBD_OK;
+    XPBD_TRY(xpbd::check_impulses(who, list, n, w->n));
+    // the device path wants the entries of a body adjacent; a stable sort keeps their order
+    std::vector<xpbd_impulse> sorted(list, list + n);
+    std::stable_sort(sorted.begin(), sorted.end(), [](const xpbd_impulse &a, const xpbd_impulse &b) { return a.body < b.body; });
+    XPBD_TRY(bind_device(w));
+    const size_t bytes = (size_t)n * sizeof(xpbd_impulse);
+    XPBD_TRY(reserve_edit_staging(w, 0, 0, bytes));
+    XPBD_HIP_TRY(hipMemcpyAsync(w->ed_list.ptr, sorted.data(), bytes, hipMemcpyHostToDevice, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_apply_impulses(w->arrays(), w->ed_list.as<xpbd_impulse>(), n, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // `sorted` is read by the copy
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_apply_impulses_device(xpbd_world *w, const xpbd_impulse *dev_list, uint32_t n)
+try {
+    const char *who = "xpbd_world_apply_impulses_device";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0)
+        return XPBD_OK;
+    if (!dev_list)
+        return set_error(XPBD_E_INVALID, "%s: NULL list", who);
+    if (w->n == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    if (reinterpret_cast<uintptr_t>(dev_list) & 15u)
+        return set_error(XPBD_E_INVALID, "%s: dev_list must be 16-byte aligned", who);
+    if (n > xpbd::kMaxEditEntries)
+        return set_error(XPBD_E_INVALID, "%s: n = %u (at most %u entries per call)", who, n, xpbd::kMaxEditEntries);
+    XPBD_TRY(bind_device(w));
+    XPBD_HIP_TRY(xpbd::launch_apply_impulses(w->arrays(), dev_list, n, w->stream));
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_set_dynamics(xpbd_world *w, const uint32_t *indices, uint32_t n, const double *rows)
+try {
+    const char *who = "xpbd_world_set_dynamics";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0)
+        return XPBD_OK;
+    if (!rows)
+        return set_error(XPBD_E_INVALID, "%s: NULL rows", who);
+    XPBD_TRY(xpbd::check_edit_indices(who, indices, n, w->n, true));
+    XPBD_TRY(xpbd::check_edit_finite(who, "rows", rows, (size_t)n * xpbd::kDynFields));
+    XPBD_TRY(bind_device(w));
+    const size_t bytes = (size_t)n * xpbd::kDynFields * 8;
+    XPBD_TRY(reserve_edit_staging(w, (size_t)n * 4, bytes, 0));
+    std::vector<uint32_t> iota;
+    XPBD_TRY(stage_edit_indices(w, indices, n, iota));
+    XPBD_HIP_TRY(hipMemcpyAsync(w->ed_values.ptr, rows, bytes, hipMemcpyHostToDevice, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_import_dynamic(w->arrays(), w->ed_indices.as<uint32_t>(), nullptr, n, w->ed_values.as<double>(), w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_get_dynamics(xpbd_world *w, const uint32_t *indices, uint32_t n, double *rows)
+try {
+    const char *who = "xpbd_world_get_dynamics";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0)
+        return XPBD_OK;
+    if (!rows)
+        return set_error(XPBD_E_INVALID, "%s: NULL rows", who);
+    XPBD_TRY(xpbd::check_edit_indices(who, indices, n, w->n, false));
+    XPBD_TRY(bind_device(w));
+    const size_t bytes = (size_t)n * xpbd::kDynFields * 8;
+    XPBD_TRY(reserve_edit_staging(w, (size_t)n * 4, bytes, 0));
+    std::vector<uint32_t> iota;
+    XPBD_TRY(stage_edit_indices(w, indices, n, iota));
+    XPBD_HIP_TRY(xpbd::launch_export_dynamic(w->arrays(), w->ed_indices.as<uint32_t>(), n, w->ed_values.as<double>(), w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(rows, w->ed_values.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    return XPBD_OK;
+} XPBD_ABI_CATCH
 
 int xpbd_world_raycast(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
 try {

@@ -139,6 +139,19 @@ impl Default for XpbdMaterial {
     }
 }
 
+/// EXTENSION: body edits -- one impulse on a resident body (xpbd_world_apply_impulses); 80 bytes.
+pub const XPBD_IMPULSE_AT_POINT: u32 = 0; // the impulse acts at `point` (world space)
+pub const XPBD_IMPULSE_AT_CENTRE: u32 = 1; // ... at position + center_of_mass; `point` is ignored
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct XpbdImpulse {
+    pub body: u32,
+    pub flags: u32,                // XPBD_IMPULSE_*
+    pub impulse: [f64; 3],         // N s, world space
+    pub point: [f64; 3],           // world space
+    pub angular_impulse: [f64; 3], // N m s, world space
+}
+
 /// EXTENSION: result of the GJK + EPA narrowphase for one pair.
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -351,6 +364,18 @@ extern "C" {
         -> c_int;
     pub fn xpbd_world_set_restitution(w: *mut XpbdWorld, restitution: *const f64, n: u32, ground_restitution: f64, bounce_threshold: f64)
         -> c_int;
+    // body edits: forces, impulses and state of resident bodies (host arrays wait; `_device`: device arrays, stream-ordered)
+    pub fn xpbd_world_set_external_wrench(w: *mut XpbdWorld, indices: *const u32, n: u32, force_xyz: *const f64, torque_xyz: *const f64)
+        -> c_int;
+    pub fn xpbd_world_set_external_wrench_device(w: *mut XpbdWorld, dev_indices: *const u32, n: u32, dev_force_xyz: *const f64,
+                                                 dev_torque_xyz: *const f64) -> c_int;
+    pub fn xpbd_world_apply_impulses(w: *mut XpbdWorld, list: *const XpbdImpulse, n: u32) -> c_int;
+    pub fn xpbd_world_apply_impulses_device(w: *mut XpbdWorld, dev_list: *const XpbdImpulse, n: u32) -> c_int;
+    pub fn xpbd_world_set_dynamics(w: *mut XpbdWorld, indices: *const u32, n: u32, rows: *const f64) -> c_int;
+    pub fn xpbd_world_get_dynamics(w: *mut XpbdWorld, indices: *const u32, n: u32, rows: *mut f64) -> c_int;
+    pub fn xpbd_multi_world_set_external_wrench(mw: *mut XpbdMultiWorld, indices: *const u32, n: u32, force_xyz: *const f64,
+                                                torque_xyz: *const f64) -> c_int;
+    pub fn xpbd_multi_world_apply_impulses(mw: *mut XpbdMultiWorld, list: *const XpbdImpulse, n: u32) -> c_int;
     pub fn xpbd_world_raycast_masked(w: *mut XpbdWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32, hits: *mut XpbdRayHit)
         -> c_int;
     pub fn xpbd_world_raycast_masked_device(w: *mut XpbdWorld, dev_rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32,

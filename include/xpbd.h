@@ -642,6 +642,91 @@ int  xpbd_world_history_truncate(xpbd_world *w, uint32_t length);
 uint32_t xpbd_world_history_length(const xpbd_world *w) XPBD_NOEXCEPT;
 
 /* ---------------------------------------------------------------------------
+ * Body EDITS (EXTENSION): forces, impulses and state of RESIDENT bodies, without uploading them again.  NOT in the reference,
+ * whose app owns its two `Rigid`s and writes their fields directly (src/world.rs, src/app.rs); behind this ABI the bodies live
+ * on the device, and xpbd_world_upload_bodies drops every body-indexed setting with them.
+ *
+ * What an edit acts on.  The state xpbd_world_download_bodies would return after the work already enqueued, in every mode (in
+ * XPBD_MODE_CONTACTS the current state, as the ray casts see it).  An edit is ordered on the world's stream: the next
+ * xpbd_world_step (or xpbd_world_contacts_begin / _substep) sees it.  An edit changes NOTHING else: joints, limits, filters,
+ * materials, restitution, the contact report and its S_prev, the history entries, contact masks and neighbour lists all stay
+ * (the next xpbd_world_step builds its broadphase from the edited state anyway; a host on the split API that teleports bodies
+ * mid-frame calls xpbd_world_contacts_begin again).  The property everything else rests on: a world after an edit steps bit for
+ * bit like a fresh world into which the edited xpbd_rigid array was uploaded (with the same settings set again).
+ *
+ * Index lists.  indices[k] names the body of entry k.  indices == NULL means the bodies 0..n-1, and then n must equal
+ * xpbd_world_body_count.  n == 0 is XPBD_OK and does nothing.
+ *
+ * xpbd_world_set_external_wrench: external_force of body indices[k] = force_xyz[3k..3k+2] and external_torque =
+ *   torque_xyz[3k..3k+2].  force_xyz or torque_xyz may be NULL: that field of the listed bodies is left alone (both NULL with
+ *   n > 0 is XPBD_E_INVALID: nothing to set).  The values REPLACE the old ones and stay until they are replaced again: they are
+ *   two of the static fields of xpbd_rigid, so xpbd_world_history_restore does NOT bring old forces back (a history entry is
+ *   the 13 dynamic doubles), and every substep integrates them as it integrates uploaded ones (Rigid::integrate, src/rigid.rs:82-99).
+ *
+ * xpbd_world_apply_impulses: entry k changes velocity and angular_velocity of body list[k].body, exactly as the restitution
+ *   pass applies an impulse (above: v += P * inverse_mass; w += cross(inverse_inertia * arm, P)).  With c = position +
+ *   center_of_mass at the body's current pose, in this order:
+ *     1. velocity += impulse * inverse_mass
+ *     2. unless XPBD_IMPULSE_AT_CENTRE:  arm = point - c;  angular_velocity += cross(inverse_inertia * arm, impulse)
+ *     3. angular_velocity += inverse_inertia * angular_impulse      (always executed, also for a zero angular_impulse; as the
+ *        hinge's angular term uses inverse_inertia * turn)
+ *   per component, no fused multiply-add, dot / cross / matrix product as everywhere else.  A body may appear several times:
+ *   its entries are applied one after another in list order, each on the result of the one before.  Entries of different bodies
+ *   are independent.  Positions and rotations are not touched.  A body with inverse_mass == 0 and a zero inverse_inertia keeps
+ *   its velocities (+ 0.0).  The host variant sorts the entries by body (stable) and runs the device path.
+ *
+ * xpbd_world_set_dynamics / _get_dynamics: row k = the 13 dynamic doubles of body indices[k] in the order of
+ *   xpbd_world_export_dynamic: position[3], rotation {s, x, y, z}, velocity[3], angular_velocity[3].  set writes all 13 (a
+ *   teleport, a stop, a throw); the rotation is taken as given (the caller keeps it a unit quaternion).  get only reads.
+ *
+ * Host variants (no _device suffix) take host arrays, check EVERYTHING before any device work and wait for completion, as
+ * xpbd_world_raycast does.  XPBD_E_INVALID, the state exactly as it was: a NULL world; a NULL list with n > 0 (indices == NULL
+ * as above excepted); a world without resident bodies; an index >= xpbd_world_body_count; the same index twice in
+ * set_external_wrench / set_dynamics; unknown `flags` bits; any NaN or infinite force, torque, impulse, point (unless
+ * XPBD_IMPULSE_AT_CENTRE: then `point` is ignored altogether), angular impulse or row value.
+ *
+ * Device variants take DEVICE arrays (e.g. a torch tensor's data_ptr()), are ordered on the world's stream
+ * (xpbd_world_get_stream / _set_stream: the caller's producer runs on that stream or is ordered before it) and return before
+ * completion; the arrays must stay valid until the stream has passed the call.  They cannot see the values: only NULL
+ * arguments, a world without bodies, the indices == NULL form with n != body count, n > 2^29 and a dev_list that is not 16-byte
+ * aligned are XPBD_E_INVALID.  An index >= body count is SKIPPED by the kernel (that entry does nothing).  Unknown flag bits are
+ * ignored.  UNSPECIFIED results: the same index twice in xpbd_world_set_external_wrench_device (one of the values wins); entries
+ * of one body that are not ADJACENT in xpbd_world_apply_impulses_device -- the entries of a body must form one run; every run is
+ * applied by one lane, which loads the body once, walks the run in order and stores the velocities once.
+ *
+ * Multi world.  xpbd_multi_world_set_external_wrench / _apply_impulses take GLOBAL body indices and are checked against n_global
+ * as the host variants above.  Not collective: every rank passes the same list (as xpbd_multi_world_set_materials).  Every local
+ * shard applies the entries of every body it HOLDS, owned or ghost: a shard integrates its ghosts itself in the first substep
+ * of a frame, so a ghost carries the force and the velocity of its owner -- the same arithmetic on the same values, the same
+ * bits on every holder.  The forces are part of the body records, which travel with the bodies through re-plans and migration.
+ * Before the first xpbd_multi_world_upload: XPBD_E_INVALID.  A device failure inside leaves the shards disagreeing: the world is
+ * unusable then (destroy it).
+ * Not here: xpbd_multi_world_set_dynamics (a teleported body interacts with the halo plan's travel allowance and needs a
+ * design of its own: upload again, or move the body with impulses), device variants of the multi-world calls, kinematic
+ * bodies, changing the mass properties of resident bodies.
+ * ------------------------------------------------------------------------- */
+#define XPBD_IMPULSE_AT_POINT  0u   /* impulse acts at `point` (world space) */
+#define XPBD_IMPULSE_AT_CENTRE 1u   /* impulse acts at position + center_of_mass; `point` is ignored */
+typedef struct xpbd_impulse {       /* 80 bytes */
+    uint32_t body, flags;           /* XPBD_IMPULSE_* */
+    double   impulse[3];            /* N s, world space */
+    double   point[3];              /* world space */
+    double   angular_impulse[3];    /* N m s, world space */
+} xpbd_impulse;
+
+int  xpbd_world_set_external_wrench(xpbd_world *w, const uint32_t *indices, uint32_t n,
+                                    const double *force_xyz, const double *torque_xyz);
+int  xpbd_world_set_external_wrench_device(xpbd_world *w, const uint32_t *dev_indices, uint32_t n,
+                                           const double *dev_force_xyz, const double *dev_torque_xyz);
+int  xpbd_world_apply_impulses(xpbd_world *w, const xpbd_impulse *list, uint32_t n);
+int  xpbd_world_apply_impulses_device(xpbd_world *w, const xpbd_impulse *dev_list, uint32_t n);
+int  xpbd_world_set_dynamics(xpbd_world *w, const uint32_t *indices, uint32_t n, const double *rows);
+int  xpbd_world_get_dynamics(xpbd_world *w, const uint32_t *indices, uint32_t n, double *rows);
+int  xpbd_multi_world_set_external_wrench(xpbd_multi_world *mw, const uint32_t *indices, uint32_t n,
+                                          const double *force_xyz, const double *torque_xyz);   /* GLOBAL indices */
+int  xpbd_multi_world_apply_impulses(xpbd_multi_world *mw, const xpbd_impulse *list, uint32_t n); /* GLOBAL bodies */
+
+/* ---------------------------------------------------------------------------
  * Scene queries (EXTENSION): the closest body along each of a batch of rays, at the bodies' current poses.  NOT in the
  * reference; its app would use it for picking under the cursor (src/app.rs, src/camera.rs).
  *
