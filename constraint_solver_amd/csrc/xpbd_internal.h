@@ -8,31 +8,18 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "xpbd_error.h"
+
 namespace xpbd {
 
-// ---- host error and resource layer -----------------------------------------------------------------------------------------
-// Records the thread's last error message (xpbd_last_error: a thread-local buffer of kErrorBytes, nothing is allocated) and
-// returns `code`.  An argument may be the current message itself: set_error(rc, "%s -- more", xpbd_last_error()).
-constexpr size_t kErrorBytes = 512;
-int set_error(int code, const char *fmt, ...) noexcept __attribute__((format(printf, 2, 3)));
-// Inside a catch block: XPBD_E_OOM, with a message naming `who` and the exception.
-int abi_exception(const char *who) noexcept;
-
-#define XPBD_TRY(expr)        \
-    do {                      \
-        if (int rc_ = (expr)) \
-            return rc_;       \
-    } while (0)
-#define XPBD_HIP_TRY(expr)                                                                                          \
+// ---- host resource layer (the error layer: xpbd_error.h) ---------------------------------------------------------------------
+#define XPBD_HIP_TRY(expr)                                                                                       \
     do {                                                                                                            \
         hipError_t e_ = (expr);                                                                                     \
         if (e_ != hipSuccess)                                                                                       \
             return ::xpbd::set_error(e_ == hipErrorOutOfMemory ? XPBD_E_OOM : XPBD_E_HIP, "%s failed: %s", #expr,   \
                                      hipGetErrorString(e_));                                                        \
     } while (0)
-// Closes the function-try-block of every int entry point of the C ABI: no exception unwinds into the caller.
-#define XPBD_ABI_CATCH \
-    catch (...) { return ::xpbd::abi_exception(__func__); }
 
 // A device allocation that only ever grows, freed with its owner.  The first request is served exactly (most buffers are
 // sized by the body count and never change); a buffer that has to GROW takes a quarter more than asked: the pair, neighbour

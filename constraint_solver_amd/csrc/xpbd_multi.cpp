@@ -7,22 +7,20 @@
 // One xpbd_multi_world drives the LOCAL shards of a world of n_ranks shards -- all of them (a single process that owns
 // every GPU of the node: what a Rust host would do) or one each (one process per GPU, the ranks of a launcher).
 //
-// Ownership is the LIBRARY's: the bodies are binned into the cells of a uniform grid (edge = 2 * (largest bounding radius +
-// pad + halo_margin)), the cells are ordered by their spatial-hash cell key taken along the LONGEST axis of the world first,
-// and that sequence is cut into n_ranks runs of near-equal body count -- every rank owns a slab of space across the world's
-// longest axis, whatever order the caller numbered its bodies in.  The first plan cuts the slabs (a FULL plan: every rank
-// sees 16 bytes per body of the world); the re-plans keep the cuts, move the bodies that crossed one to their new owner and
-// exchange only the RIMS of the shards (LIGHT plans: make_plan_light), until a shard is a tenth of a share out of balance --
-// then the slabs are cut anew.  The bodies themselves stay on the devices through every plan.  A shard is an ordinary
-// xpbd_world in XPBD_MODE_CONTACTS holding its OWNED bodies plus GHOST copies of the remote bodies that can reach an owned
-// body before the next plan, in ascending GLOBAL id (the caller's numbering) -- so every neighbour list and every
-// floating-point sum has the order of the single-device run and the result is that run's, bit for bit.  Per substep:
+// Ownership is the LIBRARY's (xpbd_plan.hpp: slabs of space across the world's longest axis).  The first plan cuts the slabs
+// (a FULL plan: every rank sees 16 bytes per body of the world); the re-plans keep the cuts, move the bodies that crossed one
+// to their new owner and exchange only the RIMS of the shards (LIGHT plans: make_plan_light), until a shard is a tenth of a
+// share out of balance -- then the slabs are cut anew.  The bodies themselves stay on the devices through every plan.  A
+// shard is an ordinary xpbd_world in XPBD_MODE_CONTACTS holding its OWNED bodies plus GHOST copies of the remote bodies that
+// can reach an owned body before the next plan, in ascending GLOBAL id (the caller's numbering) -- so every neighbour list
+// and every floating-point sum has the order of the single-device run and the result is that run's, bit for bit.  Per substep:
 //     narrowphase -> boundary bodies (their end-of-substep state straight into the send buffer) -> ONE all-gather (RCCL over
 //     xGMI: ncclAllGather) on a communication stream, overlapping the interior bodies -> the ghosts take their owners' state
 //     from the gathered buffer.
 // One function enqueues a shard's frame (shard_frame), from one host thread per local shard.
-// The plan (who owns, who mirrors whom) is built HERE, in C++, from the shards' own bodies plus a handful of small
-// all-gathers (cell keys or rims, boundary lists, the records of migrating and boundary bodies); no rank holds the global scene.
+// This file holds what needs a device or a communicator: the shards, the transport, the plan-time collectives around the
+// planner (a handful of small all-gathers: cell keys or rims, boundary lists, the records of migrating and boundary bodies;
+// no rank holds the global scene), settings, edits, the frame, reports and the xpbd_multi_world_* ABI.
 // Every plan-time all-gather carries a status word per rank and so does the frame's last one, so a rank that fails locally
 // (out of memory, say) still takes part in the collectives and EVERY rank returns an error instead of the others hanging.
 //
@@ -46,549 +44,24 @@
 #include <limits>
 #include <memory>
 #include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/xpbd.h"
 #include "xpbd_internal.h"
+#include "xpbd_plan.hpp"
 #include "xpbd_rccl.h"
 
 namespace {
 
 using xpbd::DeviceBuffer;
 using xpbd::set_error;
+using namespace xpbd::plan;
 
 constexpr uint32_t kDyn = 13;    // dynamic doubles per body: position, rotation, velocity, angular velocity
 constexpr uint32_t kRigid = 38;  // sizeof(xpbd_rigid) / 8
 constexpr uint32_t kRecord = 39; // a body's plan-time record: its xpbd_rigid + the shape id
-constexpr int64_t kCellBias = 1 << 20;
-constexpr int64_t kCellLimit = kCellBias - 4; // |cell| <= this: the +-2 dilations of the planner stay inside the 21-bit fields
-
-struct Range {
-    uint32_t first, count;
-};
-
-// The index slice of the caller's bodies a rank HANDS OVER at upload: contiguous ranges, the first n % w ranks one body
-// longer (constraint_solver_amd/sharding.py).  It says nothing about ownership.
-Range shard_range(uint32_t n, uint32_t rank, uint32_t w)
-{
-    const uint32_t base = n / w, extra = n % w;
-    return Range{rank * base + std::min(rank, extra), base + (rank < extra ? 1u : 0u)};
-}
-
-int64_t clamp_cell(double q)
-{
-    const double lim = (double)kCellLimit;
-    if (!(q >= -lim)) // NaN or far negative
-        return -kCellLimit;
-    return q > lim ? kCellLimit : (int64_t)q;
-}
-
-// x-major: ascending keys are slabs along x, inside a slab rows along y, inside a row columns along z
-int64_t cell_key(int64_t x, int64_t y, int64_t z) { return ((x + kCellBias) << 42) | ((y + kCellBias) << 21) | (z + kCellBias); }
-
-void cell_of_key(int64_t key, int64_t c[3])
-{
-    c[0] = (key >> 42) - kCellBias;
-    c[1] = ((key >> 21) & ((1 << 21) - 1)) - kCellBias;
-    c[2] = (key & ((1 << 21) - 1)) - kCellBias;
-}
-
-// ---- ownership: the x-major sequence of grid cells cut into n_ranks runs of near-equal body count ----------------------------
-// A cut is a (cell key, body id) pair; rank r owns the bodies whose (key, id) lies in [cut[r], cut[r + 1]).  Cuts fall on
-// cell boundaries (whole cells stay together) unless that would leave a rank more than a quarter of its share off balance
-// (many bodies in one cell: a tiny world), in which case the cell is split by body id.
-struct Cut {
-    int64_t key;
-    uint32_t id;
-    bool operator<=(const Cut &o) const { return key < o.key || (key == o.key && id <= o.id); }
-};
-
-// The planner's passes over ALL bodies of the world (every rank makes them at every re-plan) in a few host threads.
-// fn(thread, begin, end) for contiguous chunks in thread order; small inputs stay on the calling thread.
-constexpr unsigned kPlanThreads = 8;
-
-unsigned plan_threads(size_t n)
-{
-    static const unsigned hw = [] { // XPBD_PLAN_THREADS=<1..8> overrides (1: everything on the calling thread)
-        const char *e = std::getenv("XPBD_PLAN_THREADS");
-        const unsigned want = e ? (unsigned)std::atoi(e) : std::thread::hardware_concurrency();
-        return std::max(1u, std::min(kPlanThreads, want));
-    }();
-    return n < ((size_t)1 << 16) ? 1u : hw;
-}
-
-// An exception in any chunk, or a thread that cannot be started, is rethrown on the calling thread (the first in thread order)
-// once every thread that did start has been joined.
-template <class F>
-void parallel_chunks(size_t n, F fn)
-{
-    const unsigned t_count = plan_threads(n);
-    if (t_count == 1) {
-        fn(0u, (size_t)0, n);
-        return;
-    }
-    std::exception_ptr error[kPlanThreads];
-    auto chunk = [&](unsigned t) {
-        try {
-            fn(t, n * t / t_count, n * (t + 1) / t_count);
-        } catch (...) {
-            error[t] = std::current_exception();
-        }
-    };
-    std::vector<std::thread> threads;
-    threads.reserve(t_count - 1);
-    try {
-        for (unsigned t = 1; t < t_count; ++t)
-            threads.emplace_back(chunk, t);
-        chunk(0);
-    } catch (...) {
-        error[0] = std::current_exception();
-    }
-    for (std::thread &th : threads)
-        th.join();
-    for (const std::exception_ptr &e : error)
-        if (e)
-            std::rethrow_exception(e);
-}
-
-// The slabs are cut ACROSS THE LONGEST AXIS of the world's box of cells (a world 64 cells by 256 gets four slabs of 64 x 64,
-// not of 16 x 256: a quarter of the boundary): `order` = the axes by falling extent (ties: x, y, z), and the bodies are
-// sequenced by their cell key re-packed with the axes in that order.  lo / hi: the box.
-void slab_axes(const int64_t *keys, uint32_t n, int order[3], int64_t lo[3], int64_t hi[3])
-{
-    int64_t tlo[kPlanThreads][3], thi[kPlanThreads][3];
-    for (unsigned t = 0; t < kPlanThreads; ++t)
-        for (int a = 0; a < 3; ++a)
-            tlo[t][a] = INT64_MAX, thi[t][a] = INT64_MIN;
-    parallel_chunks(n, [&](unsigned t, size_t begin, size_t end) {
-        int64_t l[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, h[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
-        for (size_t g = begin; g < end; ++g) {
-            int64_t c[3];
-            cell_of_key(keys[g], c);
-            for (int a = 0; a < 3; ++a) {
-                l[a] = std::min(l[a], c[a]);
-                h[a] = std::max(h[a], c[a]);
-            }
-        }
-        for (int a = 0; a < 3; ++a)
-            tlo[t][a] = l[a], thi[t][a] = h[a];
-    });
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = INT64_MAX, hi[a] = INT64_MIN;
-        for (unsigned t = 0; t < kPlanThreads; ++t) {
-            lo[a] = std::min(lo[a], tlo[t][a]);
-            hi[a] = std::max(hi[a], thi[t][a]);
-        }
-    }
-    order[0] = 0, order[1] = 1, order[2] = 2;
-    if (n == 0)
-        return;
-    std::stable_sort(order, order + 3, [&](int a, int b) { return hi[a] - lo[a] > hi[b] - lo[b]; });
-}
-
-int64_t slab_key(int64_t key, const int order[3])
-{
-    int64_t c[3];
-    cell_of_key(key, c);
-    return cell_key(c[order[0]], c[order[1]], c[order[2]]);
-}
-
-// Ownership of all bodies from their cell keys: owner[g], and the cuts (cuts[r] for r = 1 .. w - 1 over the SLAB keys,
-// cuts[0] = the smallest possible pair); a deterministic function of the keys alone.
-//   The body sequence (slab key, id) is cut at positions t_r = the start of rank r's equal share.  K_r = the slab key at
-// position t_r of the sorted sequence is found without sorting it: a histogram of the bodies per LAYER (the slab key's
-// leading coordinate, the one the slabs are cut across) locates the layer position t_r falls in, and only that layer's
-// bodies are gathered and sorted (a 1024-layer world: a thousandth of the bodies per cut).
-void compute_owners(const int64_t *keys, uint32_t n, uint32_t w, uint8_t *owner, std::vector<Cut> &cuts, int axes[3])
-{
-    cuts.assign(w, Cut{INT64_MIN, 0});
-    axes[0] = 0, axes[1] = 1, axes[2] = 2;
-    if (n == 0)
-        return;
-    int64_t lo[3], hi[3];
-    slab_axes(keys, n, axes, lo, hi);
-    std::vector<int64_t> slab(n);
-    const int64_t layer_lo = lo[axes[0]];
-    const size_t n_layers = (size_t)(hi[axes[0]] - layer_lo + 1);
-    auto layer_of = [layer_lo](int64_t slab_key_) { return (size_t)(((slab_key_ >> 42) - kCellBias) - layer_lo); };
-    const unsigned t_count = plan_threads(n);
-    std::vector<std::vector<uint32_t>> hist(t_count, std::vector<uint32_t>(n_layers, 0));
-    parallel_chunks(n, [&](unsigned t, size_t begin, size_t end) {
-        uint32_t *h = hist[t].data();
-        for (size_t g = begin; g < end; ++g) {
-            slab[g] = slab_key(keys[g], axes);
-            ++h[layer_of(slab[g])];
-        }
-    });
-    if (w >= 2) {
-        std::vector<uint64_t> first(n_layers + 1, 0); // bodies in the layers before layer x
-        for (size_t x = 0; x < n_layers; ++x) {
-            uint64_t c = 0;
-            for (unsigned t = 0; t < t_count; ++t)
-                c += hist[t][x];
-            first[x + 1] = first[x] + c;
-        }
-        // the layer every cut position falls in; the bodies of those layers
-        std::vector<size_t> cut_layer(w, SIZE_MAX);
-        std::vector<int32_t> slot_of_layer(n_layers, -1);
-        std::vector<std::vector<Cut>> members;
-        for (uint32_t r = 1; r < w; ++r) {
-            const size_t t = shard_range(n, r, w).first;
-            if (t >= n)
-                continue;
-            const size_t x = (size_t)(std::upper_bound(first.begin(), first.end(), (uint64_t)t) - first.begin()) - 1;
-            cut_layer[r] = x;
-            if (slot_of_layer[x] < 0) {
-                slot_of_layer[x] = (int32_t)members.size();
-                members.emplace_back();
-            }
-        }
-        std::vector<std::vector<std::vector<Cut>>> found(t_count, std::vector<std::vector<Cut>>(members.size()));
-        parallel_chunks(n, [&](unsigned t, size_t begin, size_t end) {
-            for (size_t g = begin; g < end; ++g) {
-                const int32_t m = slot_of_layer[layer_of(slab[g])];
-                if (m >= 0)
-                    found[t][(size_t)m].push_back(Cut{slab[g], (uint32_t)g});
-            }
-        });
-        for (size_t m = 0; m < members.size(); ++m) {
-            for (unsigned t = 0; t < t_count; ++t)
-                members[m].insert(members[m].end(), found[t][m].begin(), found[t][m].end());
-            std::sort(members[m].begin(), members[m].end(), [](const Cut &a, const Cut &b) { return a.key < b.key || (a.key == b.key && a.id < b.id); });
-        }
-        const uint32_t share = std::max(1u, n / w);
-        for (uint32_t r = 1; r < w; ++r) {
-            const size_t t = shard_range(n, r, w).first; // bodies the ranks before r should own
-            if (t >= n) {
-                cuts[r] = Cut{INT64_MAX, UINT32_MAX};
-                continue;
-            }
-            const std::vector<Cut> &layer = members[(size_t)slot_of_layer[cut_layer[r]]];
-            const size_t base = (size_t)first[cut_layer[r]];
-            const int64_t K = layer[t - base].key;
-            const auto key_less = [](const Cut &c, int64_t k) { return c.key < k; };
-            const size_t i_less = (size_t)(std::lower_bound(layer.begin(), layer.end(), K, key_less) - layer.begin());
-            const size_t i_leq = (size_t)(std::lower_bound(layer.begin(), layer.end(), K + 1, key_less) - layer.begin());
-            const size_t less = base + i_less, leq = base + i_leq;
-            const size_t before = t - less, after = leq - t; // bodies of cell K on the wrong side if the cut goes before / after it
-            if (std::min(before, after) * 4 <= share)
-                cuts[r] = before <= after ? Cut{K, 0} : Cut{K + 1, 0};
-            else // split cell K: its `before` lowest ids stay with the ranks before r
-                cuts[r] = Cut{K, layer[i_less + before].id};
-        }
-        for (uint32_t r = 1; r < w; ++r) // monotone whatever the snapping did
-            if (!(cuts[r - 1] <= cuts[r]))
-                cuts[r] = cuts[r - 1];
-    }
-    const std::vector<Cut> &cuts_ref = cuts;
-    parallel_chunks(n, [&](unsigned, size_t begin, size_t end) {
-        for (size_t g = begin; g < end; ++g) {
-            // number of cuts <= (key, id), minus one; cuts[0] is the smallest pair
-            uint32_t l = 0, h = (uint32_t)cuts_ref.size(); // cuts[l] <= pair < cuts[h]
-            const Cut me{slab[g], (uint32_t)g};
-            while (h - l > 1) {
-                const uint32_t mid = (l + h) / 2;
-                if (cuts_ref[mid] <= me)
-                    l = mid;
-                else
-                    h = mid;
-            }
-            owner[g] = (uint8_t)l;
-        }
-    });
-}
-
-uint32_t owner_of(const std::vector<Cut> &cuts, int64_t slab, uint32_t id)
-{
-    // number of cuts <= (key, id), minus one; cuts[0] is the smallest pair
-    uint32_t lo = 0, hi = (uint32_t)cuts.size(); // cuts[lo] <= pair < cuts[hi]
-    const Cut me{slab, id};
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) / 2;
-        if (cuts[mid] <= me)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
-// Which remote bodies a rank mirrors and which of its own bodies the others mirror; a pure function of the cell keys, the
-// owners and the joints, so every rank computes consistent plans.
-//   ghosts:   remote bodies in a cell within one cell of a cell this rank owns a body in (ascending);
-//   boundary: this rank's bodies in a cell within one cell of a cell another rank owns a body in (ascending).
-//   A joint between an owned and a remote body puts the remote one among the ghosts and the owned one on the boundary.
-//   far (optional, one flag per owned body): no cell within two cells of the body's holds a foreign body.  Such a body
-//   may travel halo_margin + edge / 2 before it can meet a body this rank does not mirror (any foreign body starts more
-//   than two cell edges away, and 2 * (margin + edge / 2) = edge + 2 * margin is less than the 2 * edge - 2 r - pad the
-//   two would have to close), the others halo_margin.
-struct HaloPlanner {
-    struct Foreign {
-        uint32_t id;
-        int64_t key;
-    };
-    struct CrossJoint { // a joint between one of the rank's bodies and a remote one
-        uint32_t own_id, remote_id;
-    };
-
-    // The plan from LISTS: the rank's bodies (ascending ids) with their cell keys, the foreign bodies that may matter (any
-    // superset of those within two cells of the box of the rank's cells), the joints that leave the rank.  Everything hashed
-    // lies in the RIM of the rank's box: a per-axis occupancy of foreign cells picks the axis along which the fewest of the
-    // rank's layers have a foreign cell within two layers (the axis the slabs are cut across), and own bodies outside those
-    // layers -- nearly all of a slab -- are classified without a hash lookup.
-    static void plan_lists(const std::vector<uint32_t> &own, const std::vector<int64_t> &own_keys, const std::vector<Foreign> &foreign,
-                           const std::vector<CrossJoint> &cross, std::vector<uint32_t> &ghosts, std::vector<uint32_t> &boundary,
-                           std::vector<uint8_t> *far)
-    {
-        const uint32_t n_own = (uint32_t)own.size();
-        int64_t lo[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, hi[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
-        const unsigned t_count = plan_threads(n_own);
-        {
-            std::vector<int64_t> box((size_t)t_count * 6);
-            parallel_chunks(n_own, [&](unsigned t, size_t begin, size_t end) {
-                int64_t l[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, h[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
-                for (size_t k = begin; k < end; ++k) {
-                    int64_t c[3];
-                    cell_of_key(own_keys[k], c);
-                    for (int a = 0; a < 3; ++a) {
-                        l[a] = std::min(l[a], c[a]);
-                        h[a] = std::max(h[a], c[a]);
-                    }
-                }
-                for (int a = 0; a < 3; ++a)
-                    box[(size_t)t * 6 + a] = l[a], box[(size_t)t * 6 + 3 + a] = h[a];
-            });
-            for (unsigned t = 0; t < t_count; ++t)
-                for (int a = 0; a < 3; ++a) {
-                    lo[a] = std::min(lo[a], box[(size_t)t * 6 + a]);
-                    hi[a] = std::max(hi[a], box[(size_t)t * 6 + 3 + a]);
-                }
-        }
-        // `layers[a]`: per coordinate of the box along axis a, is there a foreign cell?
-        std::vector<uint8_t> layers[3];
-        int64_t layer0[3] = {0, 0, 0};
-        for (int a = 0; a < 3 && n_own; ++a) {
-            layer0[a] = lo[a] - 4;
-            layers[a].assign((size_t)(hi[a] - lo[a] + 9), 0);
-        }
-        std::unordered_set<int64_t> foreign_cells;
-        std::vector<Foreign> candidates; // foreign bodies inside the box grown by one cell: the possible ghosts
-        for (const Foreign &f : foreign) {
-            if (!n_own)
-                break;
-            int64_t c[3];
-            cell_of_key(f.key, c);
-            bool in2 = true, in1 = true;
-            for (int a = 0; a < 3; ++a) {
-                in2 = in2 && c[a] >= lo[a] - 2 && c[a] <= hi[a] + 2;
-                in1 = in1 && c[a] >= lo[a] - 1 && c[a] <= hi[a] + 1;
-            }
-            if (!in2)
-                continue;
-            foreign_cells.insert(f.key);
-            for (int a = 0; a < 3; ++a)
-                layers[a][(size_t)(c[a] - layer0[a])] = 1;
-            if (in1)
-                candidates.push_back(f);
-        }
-        // near1 / near2 [x]: a foreign cell within one / two layers of layer x, along the axis that leaves the smallest share
-        // of the box near foreign layers
-        int major = 0;
-        std::vector<uint8_t> near1, near2;
-        double best = 2.0;
-        for (int a = 0; a < 3 && n_own; ++a) {
-            std::vector<uint8_t> n1(layers[a].size(), 0), n2(layers[a].size(), 0);
-            size_t marked = 0;
-            for (size_t x = 0; x < layers[a].size(); ++x) {
-                for (int d = -2; d <= 2; ++d) {
-                    const size_t y = x + (size_t)(d + 2);
-                    if (y < 2 || y - 2 >= layers[a].size() || !layers[a][y - 2])
-                        continue;
-                    n2[x] = 1;
-                    if (d >= -1 && d <= 1)
-                        n1[x] = 1;
-                }
-                marked += n2[x] && x >= 4 && x < layers[a].size() - 4;
-            }
-            const double share = (double)marked / (double)(hi[a] - lo[a] + 1);
-            if (share < best) {
-                best = share;
-                major = a;
-                near1.swap(n1);
-                near2.swap(n2);
-            }
-        }
-        const int64_t layer_base = layer0[major];
-        // this rank's cells next to foreign layers (the rim): per cell, is a foreign body within one cell?  (then all its
-        // bodies are boundary bodies)
-        std::unordered_map<int64_t, uint8_t> rim_cells;
-        std::vector<uint8_t> is_boundary(n_own, 0);
-        // (which own bodies lie in layers near foreign ones: a pass over all of them, in a few threads; the hashing below is
-        // for those only)
-        std::vector<std::vector<uint32_t>> rim_part(t_count), near2_part(t_count);
-        parallel_chunks(n_own, [&](unsigned t, size_t begin, size_t end) {
-            for (size_t k = begin; k < end; ++k) {
-                int64_t c[3];
-                cell_of_key(own_keys[k], c);
-                const size_t x = (size_t)(c[major] - layer_base);
-                if (near1[x])
-                    rim_part[t].push_back((uint32_t)k);
-                if (near2[x])
-                    near2_part[t].push_back((uint32_t)k);
-            }
-        });
-        std::vector<uint32_t> rim_list, near2_list;
-        for (unsigned t = 0; t < t_count; ++t) {
-            rim_list.insert(rim_list.end(), rim_part[t].begin(), rim_part[t].end());
-            near2_list.insert(near2_list.end(), near2_part[t].begin(), near2_part[t].end());
-        }
-        for (uint32_t k : rim_list) {
-            int64_t c[3];
-            cell_of_key(own_keys[k], c);
-            auto it = rim_cells.find(own_keys[k]);
-            if (it == rim_cells.end()) {
-                bool seen = false;
-                for (int dx = -1; dx <= 1 && !seen; ++dx)
-                    for (int dy = -1; dy <= 1 && !seen; ++dy)
-                        for (int dz = -1; dz <= 1 && !seen; ++dz)
-                            seen = foreign_cells.count(cell_key(c[0] + dx, c[1] + dy, c[2] + dz)) != 0;
-                it = rim_cells.emplace(own_keys[k], seen).first;
-            }
-            is_boundary[k] = it->second;
-        }
-        // a candidate is a ghost iff an own cell lies within one cell of its cell (such an own cell is a rim cell)
-        std::unordered_map<int64_t, uint8_t> reached; // foreign cell -> within one cell of an own cell (memoised)
-        std::vector<uint32_t> ghost_list;
-        for (const Foreign &f : candidates) {
-            auto it = reached.find(f.key);
-            if (it == reached.end()) {
-                int64_t c[3];
-                cell_of_key(f.key, c);
-                bool near = false;
-                for (int dx = -1; dx <= 1 && !near; ++dx)
-                    for (int dy = -1; dy <= 1 && !near; ++dy)
-                        for (int dz = -1; dz <= 1 && !near; ++dz)
-                            near = rim_cells.count(cell_key(c[0] + dx, c[1] + dy, c[2] + dz)) != 0;
-                it = reached.emplace(f.key, near).first;
-            }
-            if (it->second)
-                ghost_list.push_back(f.id);
-        }
-        for (const CrossJoint &j : cross) {
-            ghost_list.push_back(j.remote_id);
-            is_boundary[std::lower_bound(own.begin(), own.end(), j.own_id) - own.begin()] = 1;
-        }
-        std::sort(ghost_list.begin(), ghost_list.end());
-        ghost_list.erase(std::unique(ghost_list.begin(), ghost_list.end()), ghost_list.end());
-        ghosts.swap(ghost_list);
-        boundary.clear();
-        for (uint32_t k = 0; k < n_own; ++k)
-            if (is_boundary[k])
-                boundary.push_back(own[k]);
-        if (far) {
-            // an own body with a foreign cell within two cells of its own (or a boundary body) is not far
-            far->assign(n_own, 0);
-            const size_t limit = 20000; // beyond that many foreign cells around the slab the test is not worth it: nobody is far
-            if (n_own && foreign_cells.size() <= limit) {
-                std::unordered_map<int64_t, uint8_t> near_cells; // own cell in a layer near foreign ones -> a foreign cell within two cells
-                for (uint32_t k = 0; k < n_own; ++k) // (outside those layers: far unless a joint made it a boundary body)
-                    (*far)[k] = !is_boundary[k];
-                for (uint32_t k : near2_list) {
-                    int64_t c[3];
-                    cell_of_key(own_keys[k], c);
-                    auto it = near_cells.find(own_keys[k]);
-                    if (it == near_cells.end()) {
-                        bool seen = false;
-                        for (int dx = -2; dx <= 2 && !seen; ++dx)
-                            for (int dy = -2; dy <= 2 && !seen; ++dy)
-                                for (int dz = -2; dz <= 2 && !seen; ++dz)
-                                    seen = foreign_cells.count(cell_key(c[0] + dx, c[1] + dy, c[2] + dz)) != 0;
-                        it = near_cells.emplace(own_keys[k], seen).first;
-                    }
-                    (*far)[k] = !it->second && !is_boundary[k];
-                }
-            }
-        }
-    }
-
-    // ... and from the cell keys and owners of ALL bodies (a full plan, the host-only diagnostics): two passes over the world
-    // (in a few threads, see parallel_chunks) collect the rank's bodies and the foreign bodies within two cells of their box.
-    uint32_t n = 0, w = 0;
-    const int64_t *keys = nullptr;
-    const uint8_t *owner = nullptr; // [n] rank owning body g
-
-    void plan_rank(uint32_t rank, const xpbd_joint *joints, uint32_t n_joints, std::vector<uint32_t> &own, std::vector<uint32_t> &ghosts,
-                   std::vector<uint32_t> &boundary, std::vector<uint8_t> *far = nullptr) const
-    {
-        own.clear();
-        std::vector<int64_t> own_keys;
-        int64_t lo[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, hi[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
-        const unsigned t_count = plan_threads(n);
-        {
-            std::vector<std::vector<uint32_t>> part(t_count);
-            std::vector<int64_t> box((size_t)t_count * 6);
-            parallel_chunks(n, [&](unsigned t, size_t begin, size_t end) {
-                int64_t l[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, h[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
-                std::vector<uint32_t> &mine = part[t];
-                for (size_t g = begin; g < end; ++g)
-                    if (owner[g] == rank) {
-                        mine.push_back((uint32_t)g);
-                        int64_t c[3];
-                        cell_of_key(keys[g], c);
-                        for (int a = 0; a < 3; ++a) {
-                            l[a] = std::min(l[a], c[a]);
-                            h[a] = std::max(h[a], c[a]);
-                        }
-                    }
-                for (int a = 0; a < 3; ++a)
-                    box[(size_t)t * 6 + a] = l[a], box[(size_t)t * 6 + 3 + a] = h[a];
-            });
-            for (unsigned t = 0; t < t_count; ++t) {
-                own.insert(own.end(), part[t].begin(), part[t].end());
-                for (int a = 0; a < 3; ++a) {
-                    lo[a] = std::min(lo[a], box[(size_t)t * 6 + a]);
-                    hi[a] = std::max(hi[a], box[(size_t)t * 6 + 3 + a]);
-                }
-            }
-        }
-        own_keys.resize(own.size());
-        for (size_t k = 0; k < own.size(); ++k)
-            own_keys[k] = keys[own[k]];
-        std::vector<Foreign> foreign;
-        if (!own.empty()) {
-            std::vector<std::vector<Foreign>> part(t_count);
-            parallel_chunks(n, [&](unsigned t, size_t begin, size_t end) {
-                for (size_t g = begin; g < end; ++g) {
-                    if (owner[g] == rank)
-                        continue;
-                    int64_t c[3];
-                    cell_of_key(keys[g], c);
-                    bool in2 = true;
-                    for (int a = 0; a < 3; ++a)
-                        in2 = in2 && c[a] >= lo[a] - 2 && c[a] <= hi[a] + 2;
-                    if (in2)
-                        part[t].push_back(Foreign{(uint32_t)g, keys[g]});
-                }
-            });
-            for (unsigned t = 0; t < t_count; ++t)
-                foreign.insert(foreign.end(), part[t].begin(), part[t].end());
-        }
-        std::vector<CrossJoint> cross;
-        for (uint32_t j = 0; j < n_joints; ++j) {
-            const uint32_t a = joints[j].body_a, b = joints[j].body_b;
-            const bool own_a = owner[a] == rank, own_b = owner[b] == rank;
-            if (own_a && !own_b)
-                cross.push_back(CrossJoint{a, b});
-            else if (own_b && !own_a)
-                cross.push_back(CrossJoint{b, a});
-        }
-        plan_lists(own, own_keys, foreign, cross, ghosts, boundary, far);
-    }
-};
-
 struct Shard {
     int device = 0;
     uint32_t rank = 0;
@@ -720,7 +193,7 @@ struct xpbd_multi_world {
     double cell_edge = 0.0;
     double rmax_local = 0.0;          // largest bounding radius (r_shape + |centroid - com|) among the bodies this process handed over
     std::vector<int32_t> slot_of;     // [n_global] scratch of a plan: local slot of a body, -1 outside the shard being built
-    std::vector<uint32_t> joint_off, joint_adj; // [n_global + 1], [2 * joints]: the joints at every body (indices into `joints`, ascending)
+    JointLists joint_lists;           // the joints at every body (indices into `joints`, ascending)
     std::vector<Cut> cuts;            // the cuts of the last full plan, kept by the light plans between (cuts_valid)
     int cut_axes[3] = {0, 1, 2};      // ... over slab keys packed in this order of the axes
     bool cuts_valid = false, check_plans = false, plan_torn = false;
@@ -965,15 +438,6 @@ struct PlanTrace {
             t_last = t;
         }
     }
-};
-
-// The new plan of one local shard, besides Shard::ghosts / boundary / far: what it will own (ascending ids) and who holds
-// those bodies now, who owns and who holds its ghosts, what it hands out (bodies that change owner, bodies others mirror).
-struct ShardPlan {
-    std::vector<uint32_t> own, exports;
-    std::vector<uint8_t> own_holder, ghost_owner, ghost_holder;
-    std::vector<uint32_t> ghosts, boundary; // (they replace Shard::ghosts / boundary / far only when the shard has been re-packed:
-    std::vector<uint8_t> far;               //  a plan that fails before that leaves the old plan as it was)
 };
 
 // The cell keys of the bodies every local shard holds, computed where the bodies are (8 bytes per body come back).
@@ -1254,11 +718,11 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
         std::vector<uint32_t> joint_ids;
         for (uint32_t q = 0; q < n_loc; ++q) {
             const uint32_t g = local_ids[q];
-            for (uint32_t e = mw->joint_off[g]; e < mw->joint_off[g + 1]; ++e) {
-                const xpbd_joint &j = mw->joints[mw->joint_adj[e]];
+            for (uint32_t e = mw->joint_lists.off[g]; e < mw->joint_lists.off[g + 1]; ++e) {
+                const xpbd_joint &j = mw->joints[mw->joint_lists.adj[e]];
                 const uint32_t other = j.body_a == g ? j.body_b : j.body_a;
                 if (mw->slot_of[other] >= 0 && (g < other || (g == other && j.body_a == g)))
-                    joint_ids.push_back(mw->joint_adj[e]);
+                    joint_ids.push_back(mw->joint_lists.adj[e]);
             }
         }
         std::sort(joint_ids.begin(), joint_ids.end());
@@ -1334,21 +798,6 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
     return XPBD_OK;
 }
 
-// What a shard holds and somebody else needs: bodies that change owner, and its (remaining) bodies that others mirror.
-// held_owner[i] = new owner of held body i; boundary = the shard's NEW boundary list (ascending).
-void exports_of(const Shard &s, const std::vector<uint8_t> &held_owner, const std::vector<uint32_t> &boundary, std::vector<uint32_t> &exports)
-{
-    exports.clear();
-    size_t b = 0;
-    for (size_t i = 0; i < s.held_ids.size(); ++i) {
-        const uint32_t g = s.held_ids[i];
-        while (b < boundary.size() && boundary[b] < g)
-            ++b;
-        if (held_owner[i] != s.rank || (b < boundary.size() && boundary[b] == g))
-            exports.push_back(g);
-    }
-}
-
 double plan_cell_edge(const xpbd_multi_world *mw, double rmax) { return 2.0 * (rmax + mw->pad + mw->margin); }
 
 // (rmax of the world, bodies held per rank): the first collective of every plan
@@ -1421,13 +870,11 @@ int make_plan_full(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace)
             migrated += owner[g] != holder[g];
         }
         trace.lap("cuts, owners");
-        HaloPlanner planner;
-        planner.n = n, planner.w = w, planner.keys = keys.data(), planner.owner = owner.data();
         std::vector<uint8_t> held_owner;
         for (size_t k = 0; k < n_local; ++k) {
             Shard &s = mw->shards[k];
             ShardPlan &pl = plans[k];
-            planner.plan_rank(s.rank, mw->joints.data(), (uint32_t)mw->joints.size(), pl.own, pl.ghosts, pl.boundary, &pl.far);
+            HaloPlanner::plan_rank(keys.data(), owner.data(), n, s.rank, mw->joints.data(), (uint32_t)mw->joints.size(), pl.own, pl.ghosts, pl.boundary, &pl.far);
             pl.own_holder.resize(pl.own.size());
             for (size_t i = 0; i < pl.own.size(); ++i)
                 pl.own_holder[i] = holder[pl.own[i]];
@@ -1438,7 +885,7 @@ int make_plan_full(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace)
             held_owner.resize(s.held_ids.size());
             for (size_t i = 0; i < s.held_ids.size(); ++i)
                 held_owner[i] = owner[s.held_ids[i]];
-            exports_of(s, held_owner, pl.boundary, pl.exports);
+            exports_of(s.rank, s.held_ids, held_owner, pl.boundary, pl.exports);
         }
     }
     trace.lap("halo plans");
@@ -1453,134 +900,6 @@ int make_plan_full(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace)
         mw->balance_least = std::min(mw->balance_least, c);
     }
     ++mw->full_plans;
-    return XPBD_OK;
-}
-
-// ---- the pieces of a light plan that are pure host logic (also behind the diagnostic xpbd_halo_plan_light) -----------------
-struct RimRow { // what a holder publishes of a body: its cell key, its id, its new owner
-    int64_t key;
-    uint32_t id;
-    uint8_t owner, pad[3];
-};
-struct Known { // ... and what everybody then knows of it
-    int64_t key;
-    uint8_t owner, holder;
-};
-using KnownMap = std::unordered_map<uint32_t, Known>;
-struct JointIndex { // the joints of the world and, per body, the joints it is an end of (ascending joint index)
-    const xpbd_joint *joints;
-    const uint32_t *off, *adj;
-    bool any;
-};
-
-std::vector<int64_t> cut_layers_of(const std::vector<Cut> &cuts)
-{
-    std::vector<int64_t> layers;
-    for (size_t r = 1; r < cuts.size(); ++r)
-        if (cuts[r].key != INT64_MAX)
-            layers.push_back((cuts[r].key >> 42) - kCellBias);
-    std::sort(layers.begin(), layers.end());
-    layers.erase(std::unique(layers.begin(), layers.end()), layers.end());
-    return layers;
-}
-
-// The RIM a holder publishes: its bodies within two layers of a cut (no body further from every cut can lie within two cells
-// of a foreign cell: a rank's bodies and a foreign body near them sit on opposite sides of a cut layer), the bodies that
-// change owner, and the ends of joints that leave the shard (the other end is held elsewhere, or the two ends get different
-// owners).  slot_of: [n_global] scratch, -1 everywhere on entry and on return.
-void rim_rows_of(uint32_t rank, const std::vector<uint32_t> &held_ids, const std::vector<int64_t> &held_keys, const std::vector<uint8_t> &held_owner,
-                 const std::vector<int64_t> &held_slab, const std::vector<int64_t> &cut_layers, const JointIndex &ji, std::vector<int32_t> &slot_of,
-                 std::vector<RimRow> &rows)
-{
-    auto near_a_cut = [&](int64_t slab) {
-        const int64_t layer = (slab >> 42) - kCellBias;
-        const auto at = std::lower_bound(cut_layers.begin(), cut_layers.end(), layer - 2);
-        return at != cut_layers.end() && *at <= layer + 2;
-    };
-    if (ji.any) // (scratch: where in the held lists a body of this shard sits)
-        for (size_t i = 0; i < held_ids.size(); ++i)
-            slot_of[held_ids[i]] = (int32_t)i;
-    for (size_t i = 0; i < held_ids.size(); ++i) {
-        const uint32_t g = held_ids[i];
-        bool publish = held_owner[i] != rank || near_a_cut(held_slab[i]);
-        for (uint32_t e = ji.any ? ji.off[g] : 0u; ji.any && e < ji.off[g + 1] && !publish; ++e) {
-            const xpbd_joint &j = ji.joints[ji.adj[e]];
-            const int32_t at = slot_of[j.body_a == g ? j.body_b : j.body_a];
-            // the other end lives elsewhere now, or will: this end's owner (or mirror) must learn about both
-            publish = at < 0 || held_owner[(size_t)at] != held_owner[i];
-        }
-        if (publish)
-            rows.push_back(RimRow{held_keys[i], g, held_owner[i], {0, 0, 0}});
-    }
-    if (ji.any)
-        for (size_t i = 0; i < held_ids.size(); ++i)
-            slot_of[held_ids[i]] = -1;
-}
-
-// One rank's new plan from the bodies it holds and everybody's rims: what it will own (the held bodies that stay and the
-// published bodies that come to it), its ghosts / boundary / far lists, who owns and holds the ghosts.
-int light_rank_plan(uint32_t rank, const std::vector<uint32_t> &held_ids, const std::vector<int64_t> &held_keys, const std::vector<uint8_t> &held_owner,
-                    KnownMap &known, const JointIndex &ji, std::vector<int32_t> &slot_of, ShardPlan &pl)
-{
-    std::vector<std::pair<uint32_t, int64_t>> arriving;
-    std::vector<HaloPlanner::Foreign> foreign;
-    for (const auto &kv : known) {
-        if (kv.second.owner == rank) {
-            if (kv.second.holder != rank)
-                arriving.emplace_back(kv.first, kv.second.key);
-        } else {
-            foreign.push_back(HaloPlanner::Foreign{kv.first, kv.second.key});
-        }
-    }
-    std::sort(arriving.begin(), arriving.end());
-    std::vector<int64_t> own_keys;
-    pl.own.reserve(held_ids.size() + arriving.size());
-    own_keys.reserve(held_ids.size() + arriving.size());
-    size_t ai = 0;
-    for (size_t i = 0; i <= held_ids.size(); ++i) {
-        const uint32_t g = i < held_ids.size() ? held_ids[i] : UINT32_MAX;
-        for (; ai < arriving.size() && arriving[ai].first < g; ++ai) {
-            pl.own.push_back(arriving[ai].first);
-            own_keys.push_back(arriving[ai].second);
-            pl.own_holder.push_back(known[arriving[ai].first].holder);
-        }
-        if (i < held_ids.size() && held_owner[i] == rank) {
-            pl.own.push_back(g);
-            own_keys.push_back(held_keys[i]);
-            pl.own_holder.push_back((uint8_t)rank);
-        }
-    }
-    // joints that leave the rank: the other end was published by its holder (or is held here and goes elsewhere)
-    std::vector<HaloPlanner::CrossJoint> cross;
-    int rc = XPBD_OK;
-    if (ji.any) {
-        for (uint32_t g : pl.own)
-            slot_of[g] = 0; // (scratch: the bodies the shard will own)
-        for (uint32_t g : pl.own) {
-            for (uint32_t e = ji.off[g]; e < ji.off[g + 1] && rc == XPBD_OK; ++e) {
-                const xpbd_joint &j = ji.joints[ji.adj[e]];
-                const uint32_t other = j.body_a == g ? j.body_b : j.body_a;
-                if (slot_of[other] >= 0)
-                    continue;
-                if (!known.count(other)) {
-                    rc = set_error(XPBD_E_HIP, "xpbd_multi_world: body %u (joint %u) is in nobody's rim (inconsistent plans)", other, ji.adj[e]);
-                    break;
-                }
-                cross.push_back(HaloPlanner::CrossJoint{g, other});
-            }
-        }
-        for (uint32_t g : pl.own)
-            slot_of[g] = -1;
-    }
-    if (rc != XPBD_OK)
-        return rc;
-    HaloPlanner::plan_lists(pl.own, own_keys, foreign, cross, pl.ghosts, pl.boundary, &pl.far);
-    pl.ghost_owner.resize(pl.ghosts.size());
-    pl.ghost_holder.resize(pl.ghosts.size());
-    for (size_t i = 0; i < pl.ghosts.size(); ++i) {
-        const Known &kn = known[pl.ghosts[i]];
-        pl.ghost_owner[i] = kn.owner, pl.ghost_holder[i] = kn.holder;
-    }
     return XPBD_OK;
 }
 
@@ -1644,7 +963,7 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
     trace.lap("owners from the cuts");
     // the rims: (key, id, new owner) of the held bodies near a cut, changing owner, or at the end of a joint that leaves the shard
     const std::vector<int64_t> cut_layers = cut_layers_of(mw->cuts);
-    const JointIndex ji{mw->joints.data(), mw->joint_off.data(), mw->joint_adj.data(), !mw->joints.empty()};
+    const JointIndex ji = mw->joint_lists.view(mw->joints.data());
     std::vector<std::vector<RimRow>> rim(n_local);
     if (mw->slot_of.size() != n)
         mw->slot_of.assign(n, -1);
@@ -1697,7 +1016,7 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
                               pl.own.size()));
             break;
         }
-        exports_of(s, held_owner[k], pl.boundary, pl.exports);
+        exports_of(s.rank, s.held_ids, held_owner[k], pl.boundary, pl.exports);
     }
     trace.lap("halo plans (light)");
     if (mw->check_plans) { // XPBD_MULTI_CHECK_PLANS=1: the same lists from the keys of the whole world (the full planner, same cuts)
@@ -1708,12 +1027,10 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
             std::vector<uint8_t> owner(n);
             for (uint32_t g = 0; g < n; ++g)
                 owner[g] = (uint8_t)owner_of(mw->cuts, slab_key(keys[g], mw->cut_axes), g);
-            HaloPlanner planner;
-            planner.n = n, planner.w = w, planner.keys = keys.data(), planner.owner = owner.data();
             for (size_t k = 0; k < n_local && st.ok(); ++k) {
                 std::vector<uint32_t> own, ghosts, boundary;
                 std::vector<uint8_t> far;
-                planner.plan_rank(mw->shards[k].rank, mw->joints.data(), (uint32_t)mw->joints.size(), own, ghosts, boundary, &far);
+                HaloPlanner::plan_rank(keys.data(), owner.data(), n, mw->shards[k].rank, mw->joints.data(), (uint32_t)mw->joints.size(), own, ghosts, boundary, &far);
                 const ShardPlan &pl = plans[k];
                 if (own != pl.own || ghosts != pl.ghosts || boundary != pl.boundary || far != pl.far)
                     st.keep(set_error(XPBD_E_HIP, "xpbd_multi_world: the light plan of rank %u differs from the full planner's (own %zu / %zu, ghosts %zu / %zu, "
@@ -2526,19 +1843,7 @@ try {
     mw->cuts_valid = false; // the first plan is a full one
     mw->check_plans = std::getenv("XPBD_MULTI_CHECK_PLANS") != nullptr;
     // the joints at every body (ascending joint index per body): the plans walk the joints of a rank's own bodies only
-    mw->joint_off.assign((size_t)n_global + 1, 0);
-    for (uint32_t j = 0; j < n_joints; ++j)
-        ++mw->joint_off[joints[j].body_a + 1], ++mw->joint_off[joints[j].body_b + 1];
-    for (uint32_t g = 0; g < n_global; ++g)
-        mw->joint_off[g + 1] += mw->joint_off[g];
-    mw->joint_adj.assign((size_t)2 * n_joints, 0);
-    {
-        std::vector<uint32_t> cursor(mw->joint_off.begin(), mw->joint_off.end() - 1);
-        for (uint32_t j = 0; j < n_joints; ++j) {
-            mw->joint_adj[cursor[joints[j].body_a]++] = j;
-            mw->joint_adj[cursor[joints[j].body_b]++] = j;
-        }
-    }
+    mw->joint_lists.build(joints, n_joints, n_global);
     // the largest bounding radius among the bodies handed over here (r_shape + |centroid - com|: a property of the bodies)
     mw->rmax_local = 0.0;
     for (uint32_t i = 0; i < n_bodies; ++i) {
@@ -2893,156 +2198,5 @@ try {
     }
     return XPBD_OK;
 } XPBD_MULTI_ABI_CATCH
-
-// Diagnostics (host only, no device): ownership and halo plans from the global cell keys, as make_plan computes them.
-int xpbd_halo_partition(const int64_t *cell_keys, uint32_t n_global, uint32_t n_ranks, uint8_t *owner)
-try {
-    if ((n_global && (!cell_keys || !owner)) || n_ranks == 0 || n_ranks > 64)
-        return set_error(XPBD_E_INVALID, "xpbd_halo_partition: bad argument");
-    std::vector<Cut> cuts;
-    int axes[3];
-    compute_owners(cell_keys, n_global, n_ranks, owner, cuts, axes);
-    return XPBD_OK;
-} XPBD_ABI_CATCH
-
-int xpbd_halo_plan_light(const int64_t *keys_at_cut, const int64_t *cell_keys, uint32_t n_global, uint32_t n_ranks, uint32_t rank,
-                         const xpbd_joint *joints, uint32_t n_joints, uint8_t *owner_now, uint32_t *own, uint32_t *n_own, uint32_t *ghosts,
-                         uint32_t *n_ghosts, uint32_t *boundary, uint32_t *n_boundary, uint8_t *far, uint32_t cap)
-try {
-    if (!keys_at_cut || !cell_keys || !owner_now || !n_own || !n_ghosts || !n_boundary || n_ranks == 0 || n_ranks > 64 || rank >= n_ranks ||
-        (n_joints && !joints) || (cap && (!own || !ghosts || !boundary)))
-        return set_error(XPBD_E_INVALID, "xpbd_halo_plan_light: bad argument");
-    for (uint32_t j = 0; j < n_joints; ++j)
-        if (joints[j].body_a >= n_global || joints[j].body_b >= n_global)
-            return set_error(XPBD_E_INVALID, "xpbd_halo_plan_light: joint %u names a body out of range", j);
-    // the cuts of the last full plan; who holds what since
-    std::vector<Cut> cuts;
-    int axes[3];
-    std::vector<uint8_t> holder(n_global);
-    compute_owners(keys_at_cut, n_global, n_ranks, holder.data(), cuts, axes);
-    // the joints at every body
-    std::vector<uint32_t> joint_off((size_t)n_global + 1, 0), joint_adj((size_t)2 * n_joints, 0);
-    for (uint32_t j = 0; j < n_joints; ++j)
-        ++joint_off[joints[j].body_a + 1], ++joint_off[joints[j].body_b + 1];
-    for (uint32_t g = 0; g < n_global; ++g)
-        joint_off[g + 1] += joint_off[g];
-    {
-        std::vector<uint32_t> cursor(joint_off.begin(), joint_off.end() - 1);
-        for (uint32_t j = 0; j < n_joints; ++j) {
-            joint_adj[cursor[joints[j].body_a]++] = j;
-            joint_adj[cursor[joints[j].body_b]++] = j;
-        }
-    }
-    const JointIndex ji{joints, joint_off.data(), joint_adj.data(), n_joints != 0};
-    // every rank: the bodies it holds, their owners from the kept cuts, its rim
-    const std::vector<int64_t> cut_layers = cut_layers_of(cuts);
-    std::vector<int32_t> slot_of(n_global, -1);
-    std::vector<std::vector<uint32_t>> held_ids(n_ranks);
-    std::vector<std::vector<int64_t>> held_keys(n_ranks), held_slab(n_ranks);
-    std::vector<std::vector<uint8_t>> held_owner(n_ranks);
-    for (uint32_t g = 0; g < n_global; ++g) {
-        const uint32_t h = holder[g];
-        const int64_t slab = slab_key(cell_keys[g], axes);
-        owner_now[g] = (uint8_t)owner_of(cuts, slab, g);
-        held_ids[h].push_back(g);
-        held_keys[h].push_back(cell_keys[g]);
-        held_slab[h].push_back(slab);
-        held_owner[h].push_back(owner_now[g]);
-    }
-    KnownMap known;
-    for (uint32_t h = 0; h < n_ranks; ++h) {
-        std::vector<RimRow> rows;
-        rim_rows_of(h, held_ids[h], held_keys[h], held_owner[h], held_slab[h], cut_layers, ji, slot_of, rows);
-        for (const RimRow &r : rows)
-            known.emplace(r.id, Known{r.key, r.owner, (uint8_t)h});
-    }
-    ShardPlan pl;
-    if (int rc = light_rank_plan(rank, held_ids[rank], held_keys[rank], held_owner[rank], known, ji, slot_of, pl))
-        return rc;
-    *n_own = (uint32_t)pl.own.size(), *n_ghosts = (uint32_t)pl.ghosts.size(), *n_boundary = (uint32_t)pl.boundary.size();
-    if (pl.own.size() > cap || pl.ghosts.size() > cap || pl.boundary.size() > cap)
-        return set_error(XPBD_E_CAPACITY, "xpbd_halo_plan_light: %zu owned, %zu ghosts, %zu boundary bodies, capacity %u", pl.own.size(), pl.ghosts.size(),
-                         pl.boundary.size(), cap);
-    std::copy(pl.own.begin(), pl.own.end(), own);
-    std::copy(pl.ghosts.begin(), pl.ghosts.end(), ghosts);
-    std::copy(pl.boundary.begin(), pl.boundary.end(), boundary);
-    if (far)
-        std::copy(pl.far.begin(), pl.far.end(), far);
-    return XPBD_OK;
-} XPBD_ABI_CATCH
-
-int xpbd_halo_plan_owned(const int64_t *cell_keys, const uint8_t *owner, uint32_t n_global, uint32_t n_ranks, uint32_t rank, const xpbd_joint *joints,
-                         uint32_t n_joints, uint32_t *ghosts, uint32_t *n_ghosts, uint32_t *boundary, uint32_t *n_boundary, uint8_t *far, uint32_t cap)
-try {
-    if (!cell_keys || !owner || !n_ghosts || !n_boundary || n_ranks == 0 || n_ranks > 64 || rank >= n_ranks || (n_joints && !joints) ||
-        (cap && (!ghosts || !boundary)))
-        return set_error(XPBD_E_INVALID, "xpbd_halo_plan_owned: bad argument");
-    for (uint32_t g = 0; g < n_global; ++g)
-        if (owner[g] >= n_ranks)
-            return set_error(XPBD_E_INVALID, "xpbd_halo_plan_owned: owner[%u] = %u of %u ranks", g, owner[g], n_ranks);
-    for (uint32_t j = 0; j < n_joints; ++j)
-        if (joints[j].body_a >= n_global || joints[j].body_b >= n_global)
-            return set_error(XPBD_E_INVALID, "xpbd_halo_plan_owned: joint %u names a body out of range", j);
-    HaloPlanner planner;
-    planner.n = n_global, planner.w = n_ranks, planner.keys = cell_keys, planner.owner = owner;
-    std::vector<uint32_t> own, g, b;
-    std::vector<uint8_t> f;
-    planner.plan_rank(rank, joints, n_joints, own, g, b, far ? &f : nullptr);
-    *n_ghosts = (uint32_t)g.size(), *n_boundary = (uint32_t)b.size();
-    if (g.size() > cap || b.size() > cap || (far && f.size() > cap))
-        return set_error(XPBD_E_CAPACITY, "xpbd_halo_plan_owned: %zu ghosts, %zu boundary bodies, %zu owned, capacity %u", g.size(), b.size(), own.size(), cap);
-    std::copy(g.begin(), g.end(), ghosts);
-    std::copy(b.begin(), b.end(), boundary);
-    if (far)
-        std::copy(f.begin(), f.end(), far); // one flag per owned body, in ascending id
-    return XPBD_OK;
-} XPBD_ABI_CATCH
-
-namespace {
-void range_owners(uint32_t n_global, uint32_t n_ranks, std::vector<uint8_t> &owner)
-{
-    owner.resize(n_global);
-    for (uint32_t r = 0; r < n_ranks; ++r) {
-        const Range rr = shard_range(n_global, r, n_ranks);
-        std::fill(owner.begin() + rr.first, owner.begin() + rr.first + rr.count, (uint8_t)r);
-    }
-}
-} // namespace
-
-// ... with ownership by contiguous index ranges (what a caller that orders its bodies itself would get)
-int xpbd_halo_plan(const int64_t *cell_keys, uint32_t n_global, uint32_t n_ranks, uint32_t rank, const xpbd_joint *joints, uint32_t n_joints,
-                   uint32_t *ghosts, uint32_t *n_ghosts, uint32_t *boundary, uint32_t *n_boundary, uint32_t cap)
-try {
-    if (n_ranks == 0 || n_ranks > 64)
-        return set_error(XPBD_E_INVALID, "xpbd_halo_plan: bad argument");
-    std::vector<uint8_t> owner;
-    range_owners(n_global, n_ranks, owner);
-    return xpbd_halo_plan_owned(cell_keys, owner.data(), n_global, n_ranks, rank, joints, n_joints, ghosts, n_ghosts, boundary, n_boundary, nullptr, cap);
-} XPBD_ABI_CATCH
-
-int xpbd_halo_plan_far(const int64_t *cell_keys, uint32_t n_global, uint32_t n_ranks, uint32_t rank, uint8_t *far, uint32_t cap, uint32_t *n_owned)
-try {
-    if (!cell_keys || !n_owned || n_ranks == 0 || n_ranks > 64 || rank >= n_ranks || (cap && !far))
-        return set_error(XPBD_E_INVALID, "xpbd_halo_plan_far: bad argument");
-    std::vector<uint8_t> owner;
-    range_owners(n_global, n_ranks, owner);
-    HaloPlanner planner;
-    planner.n = n_global, planner.w = n_ranks, planner.keys = cell_keys, planner.owner = owner.data();
-    std::vector<uint32_t> own, g, b;
-    std::vector<uint8_t> f;
-    planner.plan_rank(rank, nullptr, 0, own, g, b, &f);
-    *n_owned = (uint32_t)f.size();
-    if (f.size() > cap)
-        return set_error(XPBD_E_CAPACITY, "xpbd_halo_plan_far: %zu owned bodies, capacity %u", f.size(), cap);
-    std::copy(f.begin(), f.end(), far);
-    return XPBD_OK;
-} XPBD_ABI_CATCH
-
-int64_t xpbd_halo_cell_key(const double centre[3], double cell_edge) noexcept
-{
-    if (!centre || !(cell_edge > 0.0))
-        return 0;
-    return cell_key(clamp_cell(std::floor(centre[0] / cell_edge)), clamp_cell(std::floor(centre[1] / cell_edge)), clamp_cell(std::floor(centre[2] / cell_edge)));
-}
 
 } // extern "C"

@@ -6,7 +6,6 @@
 // point fails with XPBD_E_NO_DEVICE / XPBD_E_HIP.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,35 +28,9 @@
 
 namespace {
 
-thread_local char g_last_error[xpbd::kErrorBytes];
-
 uint32_t round_up(uint32_t v, uint32_t to) { return (v + to - 1) / to * to; }
 
 } // namespace
-
-namespace xpbd {
-int set_error(int code, const char *fmt, ...) noexcept
-{
-    char buf[kErrorBytes]; // (an argument may be g_last_error itself)
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    std::memcpy(g_last_error, buf, sizeof buf);
-    return code;
-}
-
-int abi_exception(const char *who) noexcept
-{
-    try {
-        throw;
-    } catch (const std::exception &e) {
-        return set_error(XPBD_E_OOM, "%s: %s", who, e.what());
-    } catch (...) {
-        return set_error(XPBD_E_OOM, "%s: unknown exception", who);
-    }
-}
-} // namespace xpbd
 
 using xpbd::DeviceBuffer;
 using xpbd::set_error;
@@ -1145,8 +1118,6 @@ int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t 
 extern "C" {
 
 uint32_t xpbd_abi_version(void) noexcept { return XPBD_ABI_VERSION; }
-
-const char *xpbd_last_error(void) noexcept { return g_last_error; }
 
 void xpbd_config_default(xpbd_config *cfg) noexcept
 {

@@ -7,7 +7,7 @@ with tests/halo_common.OracleBackend standing in for the device) and tests/test_
 
 Scheme
 ------
-* Ownership: order="library" (what the native world does, csrc/xpbd_multi.cpp): the x-major sequence of
+* Ownership: order="library" (what the native world does, csrc/xpbd_plan.cpp): the x-major sequence of
   spatial-hash cells is cut into world_size runs of near-equal body count (partition_owner), so every rank
   owns a slab of space (across the world's longest axis) whatever the caller's numbering, and a re-plan re-balances the slabs; bodies keep
   the caller's numbering and results equal a single-device run over the caller's bodies, bit for bit.
@@ -69,7 +69,7 @@ def cell_keys(centre, edge):
 
 
 def partition_owner(key, world_size):
-    """owner[g] from the cell keys of ALL bodies, as xpbd_halo_partition (csrc/xpbd_multi.cpp partition_cuts): the bodies
+    """owner[g] from the cell keys of ALL bodies, as xpbd_halo_partition (csrc/xpbd_plan.cpp compute_owners): the bodies
     sorted by (key, index) are cut into world_size runs at the positions of sharding.shard_range, each cut moved to the
     nearer boundary of the cell it falls into -- unless that leaves more than a quarter of a share on the wrong side, in
     which case the cell is split by body index."""

@@ -1,4 +1,4 @@
-"""The native halo planner (csrc/xpbd_multi.cpp, host-only part behind xpbd_halo_plan) against the Python planner of
+"""The native halo planner (csrc/xpbd_plan.cpp, the host-only unit behind xpbd_halo_plan) against the Python planner of
 constraint_solver_amd/distributed.py, which the gloo tests pin to "sharded == single device": same ghosts, same boundary
 bodies, for random clouds, piles, and joints that cross shard boundaries.  No GPU needed."""
 import numpy as np
