@@ -1,0 +1,270 @@
+"""Jointed bodies in contact: the f64 oracle (oracle/xpbd_pairs_oracle.c: distance, ball and hinge joints) and the f64
+evaluation of the model against the extended-precision model (xprec_pairs_model.substep with joints= and limits=), substep
+by substep; tests/joint_limit_model.py's contact-free scenes within the same bound; the 40-digit model on the substeps that
+hold the maxima; a mutation table; and invariants of the model itself.  Scenes, bound, exclusions and the measured figures:
+xprec_joints_cases.py."""
+import math
+
+import numpy as np
+import pytest
+
+import joint_limit_model as jm
+import xprec_joints_cases as jc
+import xprec_model as xm
+import xprec_pairs_cases as pc
+import xprec_pairs_model as pm
+from constraint_solver_amd import capi
+
+SCENE_NAMES = list(jc.SCENES)
+
+
+@pytest.mark.parametrize("name", SCENE_NAMES)
+def test_f64_readings_against_the_model_substep_by_substep(name):
+    """Every checked body-substep of the f64 evaluation of the model, and of the oracle on the scenes it can run (no limits,
+    no friction), is within K_JOINTS of the longdouble model; the exclusion caps hold over all body-substeps and over those
+    that carry both a joint entry and a pair point; in scene (c) at least a quarter of the body-substeps that carry a joint
+    have a binding limit and a pair-contact point."""
+    t = jc.trajectory(name)
+    errs, excl, mixed = jc.check_states(name, [fr[3] for fr in t["frames"]])
+    line = "%s: f64 evaluation %.1f" % (name, np.where(excl, 0, errs).max())
+    if name in jc.ORACLE_SCENES:
+        errs_o, _, _ = jc.check_states(name, [fr[1] for fr in t["frames"]])
+        line += ", oracle %.1f" % np.where(excl, 0, errs_o).max()
+    print("%s; excluded %d of %d body-substeps, %d of %d with joint entry and pair point" % (
+        line, excl.sum(), excl.size, (excl & mixed).sum(), mixed.sum()))
+    jc.assert_caps(name, excl, mixed)
+    kinds = set(t["joints"]["kind"].tolist())
+    entries = sum(int(fr[2]["n_joint"].sum()) for fr in t["frames"])
+    assert entries >= 2 * len(t["joints"])                               # the joints act
+    if name.startswith("doors"):
+        assert kinds == {capi.JOINT_DISTANCE, capi.JOINT_HINGE}
+        exact = list(t["exact"])
+        for _, _, res, _ in t["frames"]:                                  # the skips are taken: a positional entry on the
+            assert res["n_joint"][exact].tolist() == [1, 1, 0, 0]        # aligned hinge's bodies, none on the satisfied ball's
+            assert (res["n_points"][exact] > 0).all()
+    if name.startswith("limits"):
+        jointed = np.zeros(len(t["sid"]), dtype=bool)
+        jointed[t["joints"]["body_a"]] = jointed[t["joints"]["body_b"]] = True
+        share = sum(int(((fr[2]["n_binding"] > 0) & (fr[2]["n_points"] > 0) & jointed).sum()) for fr in t["frames"])
+        total = int(jointed.sum()) * len(t["frames"])
+        seen = {(kind, err != 0) for fr in t["frames"] for (_, kind, _, err) in fr[2]["limits"]}
+        print("%s: %d of %d jointed body-substeps have a binding limit and a pair point" % (name, share, total))
+        assert share >= 0.25 * total
+        assert seen == {(k, b) for k in (pm.LIMIT_HINGE, pm.LIMIT_SWING, pm.LIMIT_TWIST) for b in (False, True)}
+        first = [entry for entry in t["frames"][0][2]["limits"] if entry[0] == 6]
+        assert first == [(6, pm.LIMIT_HINGE, 0.0, 0.0)]                  # phi exactly on its bound: no entry
+    if name.startswith("ends"):
+        both = np.zeros(len(t["sid"]), dtype=bool)
+        for fr in t["frames"]:
+            both |= jc.both(fr[2]) & ~jc.excluded(fr[2])
+        for cat in pc.EDGE_CATEGORIES + ("slab",):
+            assert both[t["labels"] == cat].any(), cat                   # every category is checked with joint and contact
+
+
+def test_the_bound_is_eight_times_the_measured_maximum():
+    """K_JOINTS is K_PAIRS when 8x the largest measured error of both comparisons over all scenes fits under it."""
+    worst = 0.0
+    for name in SCENE_NAMES:
+        t = jc.trajectory(name)
+        for start, want, res, plain in t["frames"]:
+            x = jc.excluded(res)
+            worst = max(worst, np.where(x, 0, jc.errors(name, plain, res, start)).max())
+            if name in jc.ORACLE_SCENES:
+                worst = max(worst, np.where(x, 0, jc.errors(name, want, res, start)).max())
+    print("largest normalised error of all scenes: %.1f; 8x = %.0f; K_JOINTS = %g" % (worst, 8 * worst, jc.K_JOINTS))
+    assert 8 * worst <= jc.K_JOINTS
+
+
+def contact_free_scene(seed, n_bodies=6):
+    """The recipe of test_gpu_joint_limits.random_limited_scene on this file's bodies: free cubes in a row 2 m apart 3 m up
+    (nothing touches), tilted and spinning, no gravity; hinges and ball joints with tight limits that bind."""
+    rng = np.random.default_rng(1000 + seed)
+    bodies, rows, lims = [], [], []
+    for i in range(n_bodies):
+        bodies.append(pc.new_body(pc.CUBE, (2.0 * i, 0.0, 3.0), jc.tilt(rng, 0.3), velocity=rng.normal(scale=0.3, size=3),
+                                  spin=rng.normal(scale=4.0, size=3), gravity=False, static=seed % 2 == 1 and i == 0))
+    for k in range(n_bodies - 1):
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        ref = np.cross(axis, rng.normal(size=3))
+        ref /= np.linalg.norm(ref)
+        row = dict(body_a=k, body_b=k + 1, anchor_a=(1.5, 0.5, 0.5), anchor_b=(-0.5, 0.5, 0.5), axis_a=axis, axis_b=axis)
+        if rng.uniform() < 0.5:
+            row["kind"] = capi.JOINT_HINGE
+            lo = rng.uniform(-0.2, 0.0)
+            lims.append((k, capi.LIMIT_HINGE, lo, lo + rng.uniform(0.0, 0.2), ref, ref))
+        else:
+            choice = rng.integers(3)
+            if choice != 1:
+                lims.append((k, capi.LIMIT_SWING, 0.0, rng.uniform(0.0, 0.2)))
+            if choice != 0:
+                lo = rng.uniform(-0.2, 0.0)
+                lims.append((k, capi.LIMIT_TWIST, lo, lo + rng.uniform(0.0, 0.2), ref, ref))
+        rows.append(row)
+    order = rng.permutation(len(lims))
+    return np.array(bodies), jc.joints_of(rows), jc.limits_of([lims[i] for i in order])
+
+
+def test_the_contact_free_limit_model_lies_within_the_bound():
+    """tests/joint_limit_model.py (f64, bodies that touch nothing) on 12 random scenes of 20 substeps, each substep against
+    this model from the same state: within K_JOINTS, and the limits bind."""
+    shapes, h = pc.table()[1], 1.0 / 1200.0
+    worst, binding, left_out, total = 0.0, 0, 0, 0
+    for seed in range(12):
+        state, joints, lims = contact_free_scene(seed)
+        sid = np.zeros(len(state), dtype=np.uint32)
+        ext = np.maximum(pc.extents(sid, state), math.sqrt(2.75))
+        pairs = [(int(j["body_a"]), int(j["body_b"])) for j in joints]
+        for _ in range(20):
+            got = jm.substep(state, joints, lims, h)
+            res = pm.substep(state, shapes, sid, h, {}, joints=joints, limits=lims)
+            assert not res["mask"].any() and not res["n_points"].any()
+            e = pc.normalized_errors(got, res["state"], state, ext, h, pairs)
+            x = jc.excluded(res)
+            left_out, total = left_out + int(x.sum()), total + x.size
+            worst = max(worst, np.where(x, 0, e).max())
+            binding += int(res["n_binding"].sum())
+            state = got
+    print("joint_limit_model against the model: %.1f, %d binding limit entries" % (worst, binding))
+    assert worst <= jc.K_JOINTS and binding > 500 and left_out <= 0.10 * total
+
+
+def lifted(ref, a):
+    """A longdouble array in another scalar type, exactly: two doubles."""
+    hi = np.asarray(a).astype(np.float64)
+    lo = (a - hi.astype(a.dtype)).astype(np.float64)
+    return ref.conv(hi) + ref.conv(lo)
+
+
+@pytest.mark.parametrize("name", SCENE_NAMES)
+def test_longdouble_model_equals_mpmath_model(name):
+    """The substep that holds the scene's largest error, stage S on the longdouble model's manifolds, in longdouble and in
+    40-digit mpmath (atan2 included): the states agree 2^11 times inside K_JOINTS and within a tenth of that maximum, and
+    every limit takes the same side of its bounds: longdouble's rounding does not set the bound."""
+    fast, ref = xm.native(), xm.mp(40)
+    t = jc.trajectory(name)
+    errs, excl, _ = jc.check_states(name, [fr[3] for fr in t["frames"]])
+    if name in jc.ORACLE_SCENES:
+        errs = np.maximum(errs, jc.check_states(name, [fr[1] for fr in t["frames"]])[0])
+    worst = int(np.where(excl, 0, errs).max(axis=1).argmax())
+    start, _, res, _ = t["frames"][worst]
+    given = {key: m for key, m in res["manifolds"].items() if m["p_ref"]}
+    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [lifted(ref, p) for p in m["p_ref"]],
+                   "p_inc": [lifted(ref, p) for p in m["p_inc"]]} for key, m in given.items()}
+    a = jc.model(name, start, num=fast, manifolds=given)
+    b = jc.model(name, start, num=ref, manifolds=exact)
+    assert [(k, kind, err == 0) for k, kind, _, err in a["limits"]] == [(k, kind, err == 0) for k, kind, _, err in b["limits"]]
+    assert np.array_equal(a["n_joint"], b["n_joint"]) and np.array_equal(a["mask"], b["mask"])
+    d = np.abs(ref.to_f64(lifted(ref, a["state"]) - b["state"]))
+    scale = pc.scales(start, fast.to_f64(a["state"]), t["ext"], jc.links(name, res))
+    turn = scale / t["ext"]
+    h = t["h"]
+    e = np.max(np.stack([d[:, 31:34].max(axis=1) / (pc.EPS * scale), d[:, 34:38].max(axis=1) / (pc.EPS * turn),
+                         d[:, 22:25].max(axis=1) * h / (pc.EPS * scale), d[:, 25:28].max(axis=1) * h / (pc.EPS * turn)]), axis=0)
+    top = np.where(excl, 0, errs).max()
+    print("%s substep %d: longdouble against mpmath %.4f = %.2g of the bound; the scene's maximum %.1f" % (
+        name, worst, e.max(), e.max() / jc.K_JOINTS, top))
+    assert e.max() <= jc.K_JOINTS / 2 ** 11 and e.max() <= 0.1 * top
+
+
+# The scene on which each wrong reading of the MODEL leaves the bound, and the measured factor (worst error / K_JOINTS).
+# joint_transposed_inertia transposes I^-1 wherever a joint entry uses it: in w alone, x . (M x), the transpose is the same
+# number (measured: 0.02 of the bound on ends-h1200, rounding only), so a transposed w cannot be seen by anything.
+CAUGHT_BY = {"joint_sign_a": ("chain-h1200", 2.4e12), "anchor_without_com": ("chain-h1200", 2.2e12),
+             "joints_from_integrated": ("chain-h1200", 9.4e11), "joints_uncounted": ("chain-h1200", 1.2e12),
+             "nonbinding_counted": ("limits-h1200", 4.4e9), "binding_twice": ("limits-h1200", 2.1e10),
+             "hinge_without_compliance": ("doors-h1200", 8.0e9), "twist_unprojected": ("limits-h1200", 6.7e6),
+             "limit_same_sign": ("limits-h1200", 3.8e10), "joint_depenetration_limited": ("chain-h240-limit3", 3.4e11),
+             "joint_transposed_inertia": ("ends-h1200", 1.6e12)}
+
+
+@pytest.mark.parametrize("mutation", pm.JOINT_MUTATIONS)
+def test_the_bound_sees_each_misreading(mutation):
+    """Each wrong variant of the model pushes the f64 definition beyond K_JOINTS on the named scene, on a body-substep that
+    the true model checks."""
+    name, factor = CAUGHT_BY[mutation]
+    t = jc.trajectory(name)
+    worst = 0.0
+    for start, want, res, _ in t["frames"]:
+        wrong = jc.model(name, start, mutation=mutation, manifolds=res["manifolds"])
+        worst = max(worst, np.where(jc.excluded(res), 0.0, jc.errors(name, want, wrong, start)).max())
+    print("%s on %s: %.3g x the bound (recorded: %.2g)" % (mutation, name, worst / jc.K_JOINTS, factor))
+    assert worst > jc.K_JOINTS
+
+
+# ---- invariants of the model itself -----------------------------------------------------------------------------------
+def free_pair(seed, kind):
+    """Two cubes 3 m apart, far from the ground, tilted, no forces: a rod, a ball joint, a hinge, or a ball joint with binding
+    SWING and TWIST limits."""
+    rng = np.random.default_rng(seed)
+    bodies = np.array([pc.new_body(pc.CUBE, (0.0, 0.0, 8.0), jc.tilt(rng, 0.4), gravity=False),
+                       pc.new_body(pc.CUBE, (3.0, 0.5, 8.2), jc.tilt(rng, 0.4), gravity=False)])
+    world = np.array([2.0, 0.7, 8.6])
+    lims = []
+    if kind == "rod":
+        rows = [jc.rod(bodies, 0, 1, (0.9, 0.2, 0.7), (0.1, 0.6, 0.3), 0.05)]
+    elif kind == "ball":
+        rows = [jc.ball(bodies, 0, 1, world, (0.02, -0.01, 0.015))]
+    elif kind == "hinge":
+        rows = [jc.ball(bodies, 0, 1, world, (0.02, -0.01, 0.015), kind=capi.JOINT_HINGE, axis_a=jc.Z, axis_b=jc.Z)]
+    else:
+        rows = [jc.ball(bodies, 0, 1, world, (0.02, -0.01, 0.015))]
+        lims = [(0, capi.LIMIT_SWING, 0.0, 0.05), (0, capi.LIMIT_TWIST, -0.02, 0.01)]
+    return bodies, jc.joints_of(rows), jc.limits_of(lims)
+
+
+def momenta(num, before, after, state0):
+    """Sum of m dx and of m x cross dx + I dtheta over the bodies, from the pose change of the Jacobi pass alone; dtheta is
+    twice the vector part of dq q^-1."""
+    lin, ang = 0, 0
+    for k in range(len(state0)):
+        m = 1.0 / state0[k, 0]
+        inv = state0[k, 1:10].reshape(3, 3).T
+        x0 = before[k, 31:34] + before[k, 28:31]
+        dx = after[k, 31:34] - before[k, 31:34]
+        dq = xm.qmul(after[k, 34:38][:, None], xm.conj(before[k, 34:38][:, None]))[:, 0]
+        lin = lin + dx * m
+        ang = ang + np.cross(x0, dx) * m + np.linalg.solve(inv, num.to_f64(dq[1:] * 2))
+    return num.to_f64(lin), num.to_f64(ang)
+
+
+@pytest.mark.parametrize("kind", ["rod", "ball", "hinge", "limits"])
+def test_model_conserves_momentum_on_a_free_jointed_pair(kind):
+    """No gravity, no contact, bodies at rest: a joint's entries are +-lambda dir at two points of one line and +-lambda n
+    about one axis, so sum m dx vanishes to rounding and sum m x cross dx + I dtheta to first order in the turn (the cube's
+    inverse inertia is isotropic: rigid.rs:118-122 turns by (M arm) x impulse, the conserved form only for M = k 1).  What
+    is left is second order (the Jacobi average of several spins, dtheta read back from a normalised quaternion): turns of
+    1e-2 rad leave 1e-2 of the moved momentum at most; the joint_sign_a reading leaves all of it."""
+    num = xm.native()
+    bodies, joints, lims = free_pair(3, kind)
+    res = pm.substep(bodies, pc.table()[1], np.zeros(2, dtype=np.uint32), pc.HS[1], {}, joints=joints, limits=lims)
+    assert res["n_joint"].min() >= (3 if kind == "limits" else 2 if kind == "hinge" else 1) and not res["n_points"].any()
+    before = num.conv(bodies)
+    lin, ang = momenta(num, before, res["state"], bodies)
+    moved = np.abs(num.to_f64(res["state"][:, 31:38] - before[:, 31:38])).max() / bodies[:, 0].min()
+    assert moved > 1e-4
+    assert np.abs(lin).max() <= 1e-15 * moved, (lin, moved)
+    assert np.abs(ang).max() <= 2e-2 * moved, (ang, moved)
+
+
+@pytest.mark.parametrize("kind", ["rod", "ball", "hinge", "limits"])
+def test_model_mirrors_when_a_and_b_are_swapped(kind):
+    """The joint written from b's side -- bodies, anchors and axes swapped; SWING keeps its bound (its axis turns with the
+    roles), TWIST's signed angle changes sign and so do its bounds -- moves both bodies as before."""
+    num = xm.native()
+    bodies, joints, lims = free_pair(5, kind)
+    bodies[:, 25:28] = [[0.5, -1.0, 2.0], [-1.5, 0.3, 0.8]]
+    swapped, mirrored = joints.copy(), lims.copy()
+    for x, y in (("body_a", "body_b"), ("anchor_a", "anchor_b"), ("axis_a", "axis_b")):
+        swapped[x], swapped[y] = joints[y], joints[x]
+    mirrored["ref_a"], mirrored["ref_b"] = lims["ref_b"], lims["ref_a"]
+    twist = lims["kind"] == capi.LIMIT_TWIST
+    mirrored["lower"][twist], mirrored["upper"][twist] = -lims["upper"][twist], -lims["lower"][twist]
+    sid = np.zeros(2, dtype=np.uint32)
+    one = pm.substep(bodies, pc.table()[1], sid, pc.HS[1], {}, joints=joints, limits=lims)
+    two = pm.substep(bodies, pc.table()[1], sid, pc.HS[1], {}, joints=swapped, limits=mirrored)
+    assert np.array_equal(one["n_joint"], two["n_joint"]) and one["n_joint"].min() >= 1
+    if kind == "limits":
+        assert one["n_binding"].tolist() == [2, 2]
+    d = np.abs(num.to_f64(one["state"] - two["state"]))
+    assert d[:, 31:38].max() <= 1e-15 and d[:, 22:28].max() <= 1e-15 / pc.HS[1], d.max()

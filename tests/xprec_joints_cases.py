@@ -1,0 +1,390 @@
+"""Jointed bodies in contact, shared by test_xprec_joints_oracle.py (oracle and f64 evaluation vs the longdouble model, CPU)
+and test_gpu_xprec_joints.py (HIP vs oracle and model): the scenes, each as a sequence of SINGLE-SUBSTEP frames (dt = h,
+substeps = 1), the model (xprec_pairs_model.substep with joints= and limits=) re-seeded before every one, the bound and the
+exclusions.  Helpers, normalisation and constants are those of xprec_pairs_cases.py.
+
+Seeding.  A frame starts from the previous frame's result of the f64 definition: the oracle (oracle/xpbd_pairs_oracle.c has
+distance, ball and hinge joints) where it can run the scene, i.e. without limits and without friction; otherwise from the
+f64 evaluation of the model itself (xprec_model.f64()), the only f64 comparand of a limit that is not the code under test.
+
+Scenes, 40 bodies or fewer each, at h = 1/1200 and 1/240:
+  (a) chain   the 40-body pile of xprec_pairs_cases.scene_pile with ball and distance joints between touching neighbours and
+              between bodies that do not touch, one pair joined twice, one joint with body_a > body_b; plain, with the
+              depenetration limit at 3 m/s, and with mixed friction (MUS, GROUND_MU) at limit 0 and 3 m/s
+  (b) doors   hinges between a box on a static slab and a door resting on another box, axes misaligned by 1e-3 to 0.5 rad;
+              one hinge exactly aligned and one exactly satisfied ball joint on binary-exact poses (re-made every frame)
+  (c) limits  seven boxes lying on each other and on a static slab, chained by ball joints and hinges with SWING, TWIST and
+              HINGE limits (lower == upper among them), and a hinged pair whose phi starts binary-exactly on its bound
+  (d) ends    the categories of edge_rigids as joint ends in touching pairs, an anchor 10 m outside its body, a hub box with
+              12 joints on a slab
+  (e)         scene (c) behind a far field of 16 400 boxes: the device's one-lane-per-body path (test_gpu_xprec_joints.py)
+
+Measured (test_xprec_joints_oracle.py prints them), largest normalised error of a checked body-substep per scene, f64
+evaluation against the longdouble model [oracle against the longdouble model]:
+  chain-h1200 19.0 [24.4]   chain-h240-limit3 10.1 [11.4]   chain-h1200-mu 6.9   chain-h240-mu-limit3 9.3
+  doors-h1200  2.4 [ 2.4]   doors-h240        23.3 [23.3]   limits-h1200   2.9   limits-h240          2.8
+  ends-h1200  16.3 [14.8]   ends-h240         55.0 [29.6]   (a static_linear body of scene (d) holds the maximum)
+The bound is 8x the largest of all of them (the margin K_PAIRS and K_MANIFOLD took: the device differs from these readings
+only in f64 operation order).  8 x 55.0 = 440 fits under K_PAIRS = 656, so K_JOINTS is K_PAIRS
+(test_the_bound_is_eight_times_the_measured_maximum keeps that true).  tests/joint_limit_model.py's contact-free scenes lie
+within 1.1 of the model; the 40-digit mpmath model moves the substep that holds a scene's maximum by 0.021 at most (3e-5 of
+the bound).  Excluded: 12 of 3 152 body-substeps, all in scene (d) (4 and 8; 3 and 2 of those with joint entry and pair point)."""
+import functools
+
+import numpy as np
+
+import oracle_binding as ob
+import xprec_cases as xc
+import xprec_model as xm
+import xprec_pairs_cases as pc
+import xprec_pairs_model as pm
+from constraint_solver_amd import capi
+from xprec_cases import COND_MIN, TAU
+from xprec_pairs_cases import CUBE, GROUND_MU, HS, K_PAIRS, SLAB
+
+K_JOINTS = K_PAIRS
+X, Y, Z = np.eye(3)
+NO_LIMITS = np.zeros(0, dtype=capi.JOINT_LIMIT_DTYPE)
+SUBSTEPS, CHAIN_SUBSTEPS = 12, 8            # frames of a scene; of the 40-body chain scenes
+
+
+# ---- placement helpers (f64; nothing is asserted from them) ---------------------------------------------------------------
+def _rot(q, v):
+    return xm.qrot(np.asarray(q, dtype=np.float64), np.asarray(v, dtype=np.float64))
+
+
+def to_world(body, anchor):
+    """Frame * anchor of a body row."""
+    com = body[28:31]
+    return _rot(body[34:38], anchor) + body[31:34] + com - _rot(body[34:38], com)
+
+
+def to_object(body, world):
+    com = body[28:31]
+    origin = body[31:34] + com - _rot(body[34:38], com)
+    return _rot(xm.conj(body[34:38]), np.asarray(world) - origin)
+
+
+def axis_to_object(body, direction):
+    d = np.asarray(direction, dtype=np.float64)
+    return _rot(xm.conj(body[34:38]), d / np.linalg.norm(d))
+
+
+def yaw(angle):
+    return np.array([np.cos(angle / 2), 0.0, 0.0, np.sin(angle / 2)])
+
+
+def tilt(rng, size):
+    axis = rng.normal(size=3)
+    angle = rng.uniform(-size, size)
+    return np.concatenate([[np.cos(angle / 2)], axis / np.linalg.norm(axis) * np.sin(angle / 2)])
+
+
+def joints_of(rows):
+    """rows of dicts with the fields of xpbd_joint (kind, axes default to a ball joint with axes x)."""
+    out = np.zeros(len(rows), dtype=capi.JOINT_DTYPE)
+    for k, r in enumerate(rows):
+        out[k]["axis_a"], out[k]["axis_b"] = X, X
+        for key, value in r.items():
+            out[k][key] = value
+    return out
+
+
+def limits_of(rows):
+    """rows of (joint, kind, lower, upper[, ref_a, ref_b]); the references default to y (axes x)."""
+    out = np.zeros(len(rows), dtype=capi.JOINT_LIMIT_DTYPE)
+    for k, r in enumerate(rows):
+        out[k]["joint"], out[k]["kind"], out[k]["lower"], out[k]["upper"] = r[:4]
+        out[k]["ref_a"], out[k]["ref_b"] = (r[4], r[5]) if len(r) > 4 else (Y, Y)
+    return out
+
+
+def ball(bodies, a, b, world, error=(0.0, 0.0, 0.0), **more):
+    """A ball joint of bodies a, b at the world point `world`, b's anchor `error` away from it."""
+    return dict(body_a=a, body_b=b, anchor_a=to_object(bodies[a], world), anchor_b=to_object(bodies[b], np.asarray(world) + error), **more)
+
+
+def rod(bodies, a, b, anchor_a, anchor_b, slack):
+    """A distance joint between two object-space anchors, `slack` shorter than they are apart now."""
+    d = np.linalg.norm(to_world(bodies[b], anchor_b) - to_world(bodies[a], anchor_a))
+    return dict(body_a=a, body_b=b, anchor_a=anchor_a, anchor_b=anchor_b, distance=d - slack)
+
+
+# ---- (a) chain through a pile -----------------------------------------------------------------------------------------
+def scene_chain(h):
+    bodies, sid, labels, mu = pc.scene_pile()
+    _, manifolds, _ = pc.oracle_manifolds(bodies, sid, h)
+    touching = [key for key, m in sorted(manifolds.items()) if not m.separated and m.n_points]
+    near = set(manifolds)
+    rows = []
+    for k, (i, j) in enumerate(touching[::3][:8]):                        # touching neighbours: ball joints 1 cm off
+        ref, _ = manifolds[(i, j)].points()
+        a, b = (j, i) if k == 1 else (i, j)                               # one joint with body_a > body_b
+        rows.append(ball(bodies, a, b, ref[0], (0.006, -0.005, 0.004)))
+    i, j = touching[0]                                                    # one pair joined twice: a ball joint and a rod
+    rows.append(rod(bodies, i, j, (0.2, 0.1, 0.3), (0.1, 0.3, 0.2), 0.03))
+    apart = [(i, (i + 17) % 40) for i in range(0, 40, 5) if (min(i, (i + 17) % 40), max(i, (i + 17) % 40)) not in near]
+    assert len(apart) >= 5
+    for i, j in apart:                                                    # bodies that do not touch: rods 5 cm too short
+        rows.append(rod(bodies, i, j, (0.3, 0.2, 0.1), (0.1, 0.2, 0.3), 0.05))
+    joints = joints_of(rows)
+    assert (joints["body_a"] > joints["body_b"]).any()
+    return {"bodies": bodies, "sid": sid, "labels": labels, "joints": joints, "limits": NO_LIMITS, "mu": mu, "exact": ()}
+
+
+# ---- (b) doors --------------------------------------------------------------------------------------------------------
+DOOR_ANGLES = (1e-3, 1e-2, 0.05, 0.1, 0.3, 0.5)
+EXACT_DEPTH = 2.0 ** -7
+
+
+def exact_units():
+    """Binary-exact poses, identity rotations, at rest, no forces: a box on a box twice.  Unit 1 carries a hinge with
+    exactly aligned axes (|delta| = 0: no hinge entry) whose anchors are 2^-7 m apart; unit 2 a ball joint whose anchors
+    coincide exactly (no entry at all).  Both pairs touch, so a skipped entry that counted would change the average."""
+    kw = {"gravity": False}
+    bodies = [pc.new_body(CUBE, (100.0, 0.0, 3.0), **kw), pc.new_body(CUBE, (100.25, 0.0, 4.0 - EXACT_DEPTH), **kw),
+              pc.new_body(CUBE, (110.0, 0.0, 3.0), **kw), pc.new_body(CUBE, (110.5, 0.25, 4.0 - EXACT_DEPTH), **kw)]
+    rows = [dict(body_a=0, body_b=1, anchor_a=(0.5, 0.5, 1.0), anchor_b=(0.25, 0.5, 2 * EXACT_DEPTH), kind=capi.JOINT_HINGE,
+                 axis_a=Z, axis_b=Z),
+            dict(body_a=2, body_b=3, anchor_a=(0.75, 0.5, 1.0), anchor_b=(0.25, 0.25, EXACT_DEPTH))]
+    return bodies, rows
+
+
+def scene_doors(h, seed=31):
+    rng = np.random.default_rng(seed)
+    bodies, sid, labels, rows = [], [], [], []
+    for u, angle in enumerate(DOOR_ANGLES):
+        x0, y0, top = 8.0 * u, 20.0, 0.5
+        slab = pc.new_body(SLAB, (x0, y0, -3.5), static=True)
+        post = pc.new_body(CUBE, (x0 + 0.4, y0 + 1.0, top - rng.uniform(0.002, 0.01)), yaw(rng.uniform(-0.2, 0.2)))
+        under = pc.new_body(CUBE, (x0 + 2.0, y0 + 1.0, top - rng.uniform(0.002, 0.01)), yaw(rng.uniform(-0.2, 0.2)))
+        door = pc.new_body(CUBE, (x0 + 2.1, y0 + 1.05, top + 1.0 - rng.uniform(0.012, 0.02)), yaw(rng.uniform(-0.2, 0.2)),
+                           velocity=rng.uniform(-0.2, 0.2, 3), spin=rng.uniform(-1, 1, 3))
+        base = len(bodies)
+        bodies += [slab, post, under, door]
+        sid += [SLAB, CUBE, CUBE, CUBE]
+        labels += ["slab", "post", "under", "door"]
+        world = np.array([x0 + 1.7, y0 + 1.5, top + 1.0])
+        lean = np.array([0.0, -np.sin(angle), np.cos(angle)])              # the door's axis, `angle` away from the post's
+        rows.append(ball(bodies, base + 1, base + 3, world, rng.uniform(-0.005, 0.005, 3), kind=capi.JOINT_HINGE,
+                         axis_a=axis_to_object(post, Z), axis_b=axis_to_object(door, lean)))
+    exact, exact_rows = exact_units()
+    base = len(bodies)
+    for r in exact_rows:
+        r["body_a"], r["body_b"] = r["body_a"] + base, r["body_b"] + base
+    bodies += exact
+    sid += [CUBE] * 4
+    labels += ["exact-hinge"] * 2 + ["exact-ball"] * 2
+    return {"bodies": np.array(bodies), "sid": np.array(sid, dtype=np.uint32), "labels": np.array(labels),
+            "joints": joints_of(rows + exact_rows), "limits": NO_LIMITS, "mu": None, "exact": tuple(range(base, base + 4)),
+            "refresh_every_frame": True}
+
+
+# ---- (c) limits that bind in contact --------------------------------------------------------------------------------------
+def scene_limits(h, seed=41):
+    """A static slab, four boxes in a row on it and three boxes lying on those, every box tilted by up to 0.06 rad and
+    spinning; the chain zigzags bottom, top, bottom, ...: every joint links two boxes that lie on each other.  Joints 0, 2, 4
+    are ball joints (axes x) with SWING and TWIST limits, joints 1, 3, 5 hinges (axes y) with a HINGE limit.  Two more boxes
+    (binary-exact poses, at rest) lie on each other away from the slab, hinged, with a HINGE limit [0, 0.3] whose phi is
+    exactly 0 in the first frame."""
+    rng = np.random.default_rng(seed)
+    top = 0.5
+    bodies = [pc.new_body(SLAB, (0.0, 0.0, -3.5), static=True)]
+    chain = []
+    for k in range(4):
+        bodies.append(pc.new_body(CUBE, (0.02 + 0.995 * k, 1.5, top - rng.uniform(0.002, 0.008)), tilt(rng, 0.06),
+                                  velocity=rng.uniform(-0.1, 0.1, 3), spin=rng.uniform(-1.5, 1.5, 3)))
+    for k in range(3):
+        bodies.append(pc.new_body(CUBE, (0.5 + 0.995 * k, 1.5 + 0.1 * k, top + 1.0 - rng.uniform(0.01, 0.02)), tilt(rng, 0.06),
+                                  velocity=rng.uniform(-0.1, 0.1, 3), spin=rng.uniform(-1.5, 1.5, 3)))
+    for k in range(3):
+        chain += [1 + k, 5 + k]
+    chain.append(4)
+    rows, lims = [], []
+    for k in range(6):
+        a, b = chain[k], chain[k + 1]
+        lo, hi = (a, b) if bodies[a][33] < bodies[b][33] else (b, a)
+        world = 0.5 * (to_world(bodies[lo], (0.5, 0.5, 1.0)) + to_world(bodies[hi], (0.5, 0.5, 0.0)))
+        error = rng.uniform(-0.004, 0.004, 3)
+        if k % 2 == 0:
+            rows.append(ball(bodies, a, b, world, error))
+        else:
+            rows.append(ball(bodies, a, b, world, error, kind=capi.JOINT_HINGE, axis_a=Y, axis_b=Y))
+    lims += [(0, capi.LIMIT_SWING, 0.0, 0.02), (0, capi.LIMIT_TWIST, -0.01, 0.01),
+             (1, capi.LIMIT_HINGE, 0.05, 0.05, X, X),                                        # lower == upper
+             (2, capi.LIMIT_TWIST, 0.02, 0.02), (2, capi.LIMIT_SWING, 0.0, 0.5),            # lower == upper; never binds
+             (3, capi.LIMIT_HINGE, -0.5, 0.5, X, X),                                         # never binds
+             (4, capi.LIMIT_SWING, 0.0, 0.01),
+             (5, capi.LIMIT_HINGE, -0.01, 0.01, Z, Z)]
+    base = len(bodies)
+    bodies += [pc.new_body(CUBE, (20.0, 0.0, 3.0), gravity=False), pc.new_body(CUBE, (20.25, 0.25, 4.0 - EXACT_DEPTH), gravity=False)]
+    rows.append(dict(body_a=base, body_b=base + 1, anchor_a=(0.5, 0.5, 1.0), anchor_b=(0.25, 0.25, 2 * EXACT_DEPTH),
+                     kind=capi.JOINT_HINGE, axis_a=Z, axis_b=Z))
+    lims.append((6, capi.LIMIT_HINGE, 0.0, 0.3, X, X))
+    order = rng.permutation(len(lims))                                     # the caller's order need not be the joints'
+    labels = ["slab"] + ["chain"] * 7 + ["exact-bound"] * 2
+    return {"bodies": np.array(bodies), "sid": np.array([SLAB] + [CUBE] * 9, dtype=np.uint32), "labels": np.array(labels),
+            "joints": joints_of(rows), "limits": limits_of([lims[i] for i in order]), "mu": None,
+            "exact": (base, base + 1), "refresh_every_frame": False}
+
+
+# ---- (d) edge bodies at joint ends ------------------------------------------------------------------------------------
+def scene_ends(h, seed=51):
+    """xprec_pairs_cases.scene_edge: 18 touching pairs (an edge body and a box) and two boxes on static slabs.  Every pair is
+    joined -- ball joints, rods and hinges in turn, a static_linear body being the static anchor of its joint --; a rod
+    whose anchor lies 10 m outside its box links the boxes of pairs 0 and 1; the box on slab 0 is a hub with 12 joints, six
+    ball joints to its slab and six rods to the box on slab 1."""
+    rng = np.random.default_rng(seed)
+    bodies, sid, labels = pc.scene_edge(h)
+    rows = []
+    for k in range(18):
+        a, b = 2 * k, 2 * k + 1
+        world = 0.5 * (to_world(bodies[a], pc.table()[1][int(sid[a])]["centroid"]) + to_world(bodies[b], (0.5, 0.5, 0.5)))
+        if k % 3 == 0:
+            rows.append(ball(bodies, a, b, world, rng.uniform(-0.005, 0.005, 3)))
+        elif k % 3 == 1:
+            i, j = (b, a) if k == 4 else (a, b)                           # one joint with body_a > body_b
+            rows.append(rod(bodies, i, j, (0.2, 0.3, 0.1), (0.3, 0.1, 0.2), 0.02))
+        else:
+            d = rng.normal(size=3)
+            lean = d + rng.normal(size=3) * 0.1
+            rows.append(ball(bodies, a, b, world, rng.uniform(-0.005, 0.005, 3), kind=capi.JOINT_HINGE,
+                             axis_a=axis_to_object(bodies[a], d), axis_b=axis_to_object(bodies[b], lean)))
+    rows.append(rod(bodies, 1, 3, (10.5, 0.5, 0.5), (0.5, 0.5, 0.5), 0.03))
+    hub, slab, other = 37, 36, 39
+    for k in range(6):
+        corner = to_world(bodies[hub], (k % 2, k // 2 % 2, 0.0)) + np.array([0.0, 0.0, -0.1 * (k // 4)])
+        rows.append(ball(bodies, slab, hub, corner, rng.uniform(-0.004, 0.004, 3)))
+        rows.append(rod(bodies, hub, other, (k % 2, k // 2 % 2, 1.0), (0.5, 0.5, 0.5), 0.01 * (k + 1)))
+    joints = joints_of(rows)
+    assert ((joints["body_a"] == hub) | (joints["body_b"] == hub)).sum() == 12
+    return {"bodies": bodies, "sid": sid, "labels": labels, "joints": joints, "limits": NO_LIMITS, "mu": None, "exact": ()}
+
+
+# name -> (builder, h, friction?, depenetration speed)
+def _scenes():
+    out = {"chain-h1200": (scene_chain, HS[0], False, 0.0), "chain-h240-limit3": (scene_chain, HS[1], False, 3.0),
+           "chain-h1200-mu": (scene_chain, HS[0], True, 0.0), "chain-h240-mu-limit3": (scene_chain, HS[1], True, 3.0)}
+    for h in HS:
+        tag = "h%d" % round(1.0 / h)
+        out["doors-" + tag] = (scene_doors, h, False, 0.0)
+        out["limits-" + tag] = (scene_limits, h, False, 0.0)
+        out["ends-" + tag] = (scene_ends, h, False, 0.0)
+    return out
+
+
+SCENES = _scenes()
+# the scenes the oracle can run: no limits, no friction
+ORACLE_SCENES = [n for n in SCENES if not n.startswith("limits") and not SCENES[n][2]]
+LIMIT_SCENES = [n for n in SCENES if n.startswith("limits")]
+
+
+@functools.lru_cache(maxsize=None)
+def build(name):
+    builder, h, friction, speed = SCENES[name]
+    s = dict(builder(h))
+    s.update(h=h, speed=speed, mu=s["mu"] if friction else None, ground_mu=GROUND_MU if friction else np.inf)
+    s["ext"] = np.maximum(pc.extents(s["sid"], s["bodies"]), arms(s))
+    return s
+
+
+def arms(s):
+    """Per body, the largest distance of one of its anchors from its position: a joint's lever, the extent of its body."""
+    out = np.zeros(len(s["sid"]))
+    for j in s["joints"]:
+        for body, anchor in ((int(j["body_a"]), j["anchor_a"]), (int(j["body_b"]), j["anchor_b"])):
+            out[body] = max(out[body], np.linalg.norm(anchor))
+    return out
+
+
+def model(name, state, num=None, mutation=None, tau=0.0, manifolds=None):
+    s = build(name)
+    return pm.substep(state, pc.table()[1], s["sid"], s["h"], manifolds, s["mu"], s["ground_mu"], s["speed"], num=num,
+                      mutation=mutation, tau=tau, joints=s["joints"], limits=s["limits"])
+
+
+def oracle(name, state):
+    s = build(name)
+    assert name in ORACLE_SCENES
+    return ob.contacts_step_joints(state, s["sid"], pc.table()[0], s["joints"], s["h"], 1, pc.PAD, max_depenetration_speed=s["speed"])
+
+
+def links(name, res):
+    """The body pairs that act on each other in the substep: touching pairs and joints."""
+    s = build(name)
+    return list(res["manifolds"]) + [(int(j["body_a"]), int(j["body_b"])) for j in s["joints"]]
+
+
+def errors(name, got, res, start):
+    s = build(name)
+    return pc.normalized_errors(got, res["state"], start, s["ext"], s["h"], links(name, res))
+
+
+def excluded(res):
+    """xprec_pairs_cases.excluded, and the joints' own: a limit whose phi is within (0, TAU] of a bound (on the bound the
+    stated rule decides: no entry) or within TAU of the wrap at +-pi, or a direction normalised by less than COND_MIN (s,
+    |bisector|, |delta|, anchor distance; exactly 0 is the stated skip)."""
+    x = pc.excluded(res)
+    margin = res["limit_margin"]
+    return x | ((margin > 0) & (margin <= TAU)) | (res["wrap_margin"] <= TAU) | (res["joint_cond"] < COND_MIN)
+
+
+def nudged(state, seed, exact):
+    out = xc.nudged(state, seed)
+    out[list(exact)] = state[list(exact)]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def trajectory(name):
+    """Returns dict of the scene (build) and frames: [(start, want, res, f64 state)]: `want` the f64 definition's state after
+    the substep (the oracle's where it can run the scene, else the f64 evaluation's), res the longdouble model's result from
+    `start` with its one-ulp sensitivity, the f64 evaluation's state."""
+    s = build(name)
+    exact = list(s["exact"])
+    state, out = s["bodies"], []
+    for f in range(CHAIN_SUBSTEPS if name.startswith("chain") else SUBSTEPS):
+        exact_now = bool(exact) and (f == 0 or s.get("refresh_every_frame", False))
+        if exact and f and exact_now:
+            state = state.copy()
+            state[exact] = s["bodies"][exact]
+        res = model(name, state, tau=TAU)
+        plain = xm.f64().to_f64(model(name, state, num=xm.f64())["state"])
+        want = oracle(name, state) if name in ORACLE_SCENES else plain
+        moved = model(name, nudged(state, f, exact if exact_now else ()))
+        res["sensitivity"] = errors(name, xm.native().to_f64(moved["state"]), res, state)
+        if exact_now:                   # on an exact tie the stated rule decides; one ulp beside it the decision is another one
+            res["sensitivity"][exact] = 0.0
+        out.append((state, want, res, plain))
+        state = want
+    return dict(s, frames=out)
+
+
+def both(res):
+    """The body-substeps that carry a joint entry and a pair-contact point."""
+    return (res["n_joint"] > 0) & (res["n_points"] > 0)
+
+
+def check_states(name, got_states, k=None, model_results=None):
+    """got_states[f]: the state after substep f of an implementation under test.  Asserts the bound on every body-substep
+    that is not excluded; returns (normalised errors, excluded, carries joint entry and pair point), each (frames, n)."""
+    t = trajectory(name)
+    k = K_JOINTS if k is None else k
+    errs, excl, mixed = [], [], []
+    for f, (start, _, res, _) in enumerate(t["frames"]):
+        m = res if model_results is None else model_results[f]
+        e = pc.normalized_errors(got_states[f], m["state"], start, t["ext"], t["h"], links(name, res))
+        x = excluded(res)
+        bad = np.nonzero(~x & ~(e <= k))[0]
+        assert not len(bad), "%s substep %d: bodies %s (%s) beyond K = %g: %s" % (name, f, bad[:8], t["labels"][bad[:8]], k, e[bad[:8]])
+        errs.append(e)
+        excl.append(x)
+        mixed.append(both(res))
+    return np.array(errs), np.array(excl), np.array(mixed)
+
+
+def assert_caps(name, excl, mixed):
+    """At most 10 % of all body-substeps, and of those that carry both a joint entry and a pair point, are excluded."""
+    assert mixed.sum() >= 20, (name, mixed.sum())
+    assert excl.mean() <= 0.10, (name, excl.mean())
+    assert (excl & mixed).sum() <= 0.10 * mixed.sum(), (name, (excl & mixed).sum(), mixed.sum())

@@ -20,15 +20,22 @@ F64_MIN_NORMAL = 2.0 ** -1022
 
 
 class Num:
-    """The scalar type: `conv` turns an f64 array into model scalars exactly, `sqrt` is the type's square root."""
+    """The scalar type: `conv` turns an f64 array into model scalars exactly, `sqrt` is the type's square root, `atan2` its
+    two-argument arc tangent (the angular joint limits)."""
 
-    def __init__(self, name, conv, sqrt, to_f64, const):
-        self.name, self.conv, self.sqrt, self.to_f64, self.const = name, conv, sqrt, to_f64, const
+    def __init__(self, name, conv, sqrt, to_f64, const, atan2=np.arctan2):
+        self.name, self.conv, self.sqrt, self.to_f64, self.const, self.atan2 = name, conv, sqrt, to_f64, const, atan2
 
 
 def longdouble():
     return Num("longdouble", lambda a: np.asarray(a, dtype=np.float64).astype(np.longdouble), np.sqrt,
                lambda a: np.asarray(a, dtype=np.longdouble).astype(np.float64), np.longdouble)
+
+
+def f64():
+    """Plain f64 (np.float64, np.sqrt, np.arctan2): the model's text evaluated as one more f64 implementation, with the
+    model's operation order and numpy's libm.  Not a reference: a comparand."""
+    return Num("f64", lambda a: np.array(a, dtype=np.float64), np.sqrt, lambda a: np.asarray(a, dtype=np.float64), np.float64)
 
 
 def mp(digits=40):
@@ -39,7 +46,8 @@ def mp(digits=40):
     conv = np.frompyfunc(lambda x: mpf(float(x)), 1, 1)
     back = np.frompyfunc(float, 1, 1)
     return Num("mpmath%d" % digits, lambda a: conv(np.asarray(a, dtype=np.float64)).astype(object),
-               np.frompyfunc(ctx.sqrt, 1, 1), lambda a: back(np.asarray(a, dtype=object)).astype(np.float64), mpf)
+               np.frompyfunc(ctx.sqrt, 1, 1), lambda a: back(np.asarray(a, dtype=object)).astype(np.float64), mpf,
+               np.frompyfunc(ctx.atan2, 2, 1))
 
 
 def native():

@@ -5,7 +5,9 @@ A second reading of oracle/xpbd_pairs_oracle.h's prose (steps 1-5, the manifold 
 that header cites; it does not follow xpbd_pairs_oracle.c, the kernels or tests/material_model.py.  Stage N is plain
 geometry: every query is a maximum over ALL faces or edge pairs of a minimum over ALL vertices, evaluated in world space
 (a rigid motion keeps distances), where the oracle works in A's space, over unique edge directions and with supports.
-Stage S uses tests/xprec_model.py's scalar abstraction, cgmath helpers, integrate, ground and derive.
+Stage S uses tests/xprec_model.py's scalar abstraction, cgmath helpers, integrate, ground and derive.  Its joint and limit
+entries (joint_terms) are read from include/xpbd.h (XPBD_JOINT_*, XPBD_LIMIT_*), the joint prose of xpbd_pairs_oracle.h and
+constraint.rs:6-37, rigid.rs:113-123; they follow neither tests/joint_limit_model.py, the oracle's C nor the kernel.
 
 Vectors are arrays (3, k) of model scalars as in xprec_model.py.  Reference lines are jim-ec/constraint_solver src/*.rs.
 """
@@ -22,6 +24,12 @@ FACE_A, FACE_B, EDGES = 0, 1, 2
 PARALLEL_SIN = 1e-9
 MUTATIONS = ("reference_sign", "arm_without_com", "transposed_inertia", "average_by_pairs", "friction_against_distance",
              "tangential_dropped")
+# wrong readings of the joint and limit entries of stage S (joint_terms)
+JOINT_MUTATIONS = ("joint_sign_a", "anchor_without_com", "joints_from_integrated", "joints_uncounted", "nonbinding_counted",
+                   "binding_twice", "hinge_without_compliance", "twist_unprojected", "limit_same_sign",
+                   "joint_depenetration_limited", "joint_transposed_inertia")
+JOINT_DISTANCE, JOINT_HINGE = 0, 1                                       # XPBD_JOINT_*
+LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST = 0, 1, 2                          # XPBD_LIMIT_*
 
 
 def shape(poly):
@@ -230,19 +238,163 @@ def manifold_points(manifolds):
     return inc, ref, pair, p_inc, p_ref
 
 
+def joint_terms(num, s, pos, rot, joints, limits, compliance, depenetration=None, mutation=None):
+    """The joint entries of stage S's Jacobi pass, all evaluated on the pose (pos, rot) (3, n), (4, n): the pose after
+    step 3.  joints / limits: records with the fields of xpbd_joint / xpbd_joint_limit (a limit belongs to `joint`; a joint's
+    limits act in the caller's order).  Per joint, each a Jacobi entry of its own on both bodies:
+      positional  p = Frame * anchor (frame.rs:47-53, Rigid::frame rigid.rs:75-80: the centre-of-mass offset included);
+                  lambda = (|p_b - p_a| - distance) / (w_a + w_b + compliance), w = Constraint::inverse_resitance
+                  (constraint.rs:25-32); +lambda dir on a at p_a, -lambda dir on b at p_b as Rigid::apply_impulse
+                  (rigid.rs:113-123); no entry when the points coincide exactly.  Never limited by the depenetration speed.
+      hinge       (XPBD_JOINT_HINGE) delta = a_w x b_w, n = delta / |delta|, no entry at |delta| = 0; w = the angular half
+                  of inverse_resitance; lambda = |delta| / (w + compliance); a turns by +lambda n, b by -lambda n:
+                  rotation += 0.5 Quat(0, I^-1 (lambda n)) * rotation.
+      limits      SWING, HINGE, TWIST as xpbd.h states them; err = phi - clamp(phi, lower, upper); err == 0 adds nothing,
+                  not even to the count; otherwise lambda = err / (w + compliance), turned like the hinge term.
+    Returns (sum of position terms (3, n), sum of rotation terms (4, n), count (n,), info): info holds per body n_joint (its
+    entries), n_binding (its binding limits), limit_margin (smallest |phi - nearer bound| of its limits, radians),
+    wrap_margin (smallest pi - |phi|) and joint_cond (smallest non-zero s, |bisector|, |delta| or anchor distance: what a
+    direction is normalised by), and per limit the list `limits` of (joint, kind, phi, err) in f64."""
+    assert mutation is None or mutation in JOINT_MUTATIONS
+    sqrt = num.sqrt
+    im, M, com = s["inverse_mass"], s["inverse_inertia"], s["center_of_mass"]
+    n = pos.shape[1]
+    sum_p, sum_q, count = pos * 0, rot * 0, np.zeros(n, dtype=np.int64)
+    info = {"n_joint": np.zeros(n, dtype=np.int64), "n_binding": np.zeros(n, dtype=np.int64), "limit_margin": np.full(n, np.inf),
+            "wrap_margin": np.full(n, np.inf), "joint_cond": np.full(n, np.inf), "limits": []}
+    by_joint = [[] for _ in range(len(joints))]
+    for lim in limits:
+        by_joint[int(lim["joint"])].append(lim)
+
+    def vec(x):
+        return num.conv(np.asarray(x, dtype=np.float64))
+
+    def as_float(x):
+        return float(num.to_f64(np.array([x]))[0])
+
+    def inertia(body):
+        """I^-1 of the body, [column, row].  (The mutation transposes it wherever a joint entry uses it: in w alone, a
+        quadratic form, the transpose is the same number.)"""
+        return M[:, :, body].T if mutation == "joint_transposed_inertia" else M[:, :, body]
+
+    def entry(body, dp, turn, counts=1):
+        """One entry of `body`: a displacement and an angular displacement I^-1-weighted already (rigid.rs:118-122)."""
+        if dp is not None:
+            sum_p[:, body] = sum_p[:, body] + dp
+        sum_q[:, body] = sum_q[:, body] + qmul(pure(turn) * 0.5, rot[:, body])
+        count[body] += 0 if mutation == "joints_uncounted" else counts
+        info["n_joint"][body] += 1
+
+    def conditioned(bodies, value):
+        v = as_float(value)
+        if v != 0:
+            for body in bodies:
+                info["joint_cond"][body] = min(info["joint_cond"][body], v)
+
+    def angular(a, b, n_axis, error, with_compliance=True, counts=1, same_sign=False):
+        """An angular entry about the unit axis n: a turns by +lambda n, b by -lambda n."""
+        w = 0
+        for body in (a, b):
+            local = qrot(conj(rot[:, body]), n_axis)                       # q^-1 n
+            w = w + dot(matvec(inertia(body), local), local)
+        lam = error / (w + compliance if with_compliance else w)
+        entry(a, None, matvec(inertia(a), n_axis * lam), counts)
+        entry(b, None, matvec(inertia(b), n_axis * (lam if same_sign else -lam)), counts)
+
+    for k, jt in enumerate(joints):
+        a, b = int(jt["body_a"]), int(jt["body_b"])
+        p, origin = [], []
+        for body, anchor in ((a, jt["anchor_a"]), (b, jt["anchor_b"])):
+            o = pos[:, body] + com[:, body]                                 # the body's origin in the world: position + com
+            frame_p = o + qrot(rot[:, body], -com[:, body])                 # Rigid::frame, rigid.rs:75-80
+            if mutation == "anchor_without_com":
+                frame_p = pos[:, body]
+            p.append(frame_apply(frame_p, rot[:, body], vec(anchor)))
+            origin.append(o)
+        diff = p[1] - p[0]                                                  # constraint.rs:13-15, contacts = (p_a, p_b)
+        dist = sqrt(dot(diff, diff))
+        conditioned((a, b), dist)
+        if dist != 0:
+            direction = diff / dist
+            w = 0
+            for body, point, o in ((a, p[0], origin[0]), (b, p[1], origin[1])):
+                local = qrot(conj(rot[:, body]), cross(point - o, direction))
+                w = w + im[body] + dot(matvec(inertia(body), local), local)
+            error = dist - vec([jt["distance"]])[0]
+            if mutation == "joint_depenetration_limited" and depenetration is not None:
+                error = min(max(error, -depenetration), depenetration)
+            lam = error / (w + compliance)
+            for body, point, o, impulse in ((a, p[0], origin[0], direction * (-lam if mutation == "joint_sign_a" else lam)),
+                                            (b, p[1], origin[1], direction * -lam)):
+                entry(body, impulse * im[body], cross(matvec(inertia(body), point - o), impulse))
+        a_w, b_w = qrot(rot[:, a], vec(jt["axis_a"])), qrot(rot[:, b], vec(jt["axis_b"]))
+        if int(jt["kind"]) == JOINT_HINGE:
+            delta = cross(a_w, b_w)
+            mag = sqrt(dot(delta, delta))
+            conditioned((a, b), mag)
+            if mag != 0:
+                angular(a, b, delta / mag, mag, with_compliance=mutation != "hinge_without_compliance")
+        for lim in by_joint[k]:
+            kind = int(lim["kind"])
+            if kind == LIMIT_SWING:
+                c = cross(a_w, b_w)
+                sine = sqrt(dot(c, c))
+                conditioned((a, b), sine)
+                if sine == 0:
+                    continue
+                phi, n_axis = num.atan2(sine, dot(a_w, b_w)), c / sine
+            else:
+                r_a, r_b = qrot(rot[:, a], vec(lim["ref_a"])), qrot(rot[:, b], vec(lim["ref_b"]))
+                if kind == LIMIT_HINGE:
+                    n_axis = a_w
+                else:
+                    assert kind == LIMIT_TWIST
+                    bisector = a_w + b_w
+                    length = sqrt(dot(bisector, bisector))
+                    conditioned((a, b), length)
+                    if length == 0:
+                        continue
+                    n_axis = bisector / length
+                    if mutation != "twist_unprojected":
+                        r_a, r_b = r_a - n_axis * dot(r_a, n_axis), r_b - n_axis * dot(r_b, n_axis)
+                phi = num.atan2(dot(cross(r_a, r_b), n_axis), dot(r_a, r_b))
+            lower, upper = vec([lim["lower"], lim["upper"]])
+            error = phi - min(max(phi, lower), upper)
+            phi64 = as_float(phi)
+            info["limits"].append((k, kind, phi64, as_float(error)))
+            for body in (a, b):
+                info["limit_margin"][body] = min(info["limit_margin"][body], abs(as_float(phi - lower)),
+                                                 abs(as_float(phi - upper)))
+                info["wrap_margin"][body] = min(info["wrap_margin"][body], np.pi - abs(phi64))
+            if error == 0:
+                if mutation == "nonbinding_counted":
+                    count[a] += 1
+                    count[b] += 1
+                continue
+            info["n_binding"][[a, b]] += 1
+            angular(a, b, n_axis, error, counts=2 if mutation == "binding_twice" else 1, same_sign=mutation == "limit_same_sign")
+    return sum_p, sum_q, count, info
+
+
 def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.inf, max_depenetration_speed=0.0, num=None,
-            mutation=None, tau=0.0):
+            mutation=None, tau=0.0, joints=(), limits=()):
     """Stage S: one contacts substep (steps 1, 3, 4, 5 of xpbd_pairs_oracle.h) of n bodies ((n, 38) f64).  shapes: list of
     shape() dicts.  manifolds: {(i, j), i < j: {"feature", "p_ref": [(3,)], "p_inc": [(3,)]}} of the touching pairs at the
     post-integrate frames, or None: stage N on every pair (stage S o N, the fully independent substep).  mu: per-body
     friction coefficients (None: the reference's contact), ground_mu the plane's.  mutation: one of MUTATIONS, a
-    deliberately wrong reading for the mutation check.
+    deliberately wrong reading for the mutation check (MUTATIONS, or JOINT_MUTATIONS for the joint entries).  joints, limits:
+    records with the fields of xpbd_joint / xpbd_joint_limit: all their entries are evaluated on the poses after step 3, in
+    the same Jacobi pass as the pair points, and a body applies the average of ALL its entries -- pair points, positional
+    joint entries, hinge entries and binding limits each count 1 (joint_terms).  Friction and the depenetration limit never
+    touch a joint entry.
 
     Returns a dict: state (n, 38) model scalars; frames: the post-integrate frames [(position, rotation)]; manifolds: the
     ones used; per body: mask, margin, cond, flip_margin, domain (as xprec_model.step), branch (smallest distance in
     metres of a friction or depenetration-limit comparison from its threshold) and pair_cond (smallest |c1 - c0| of a
-    pair point); undecided: the pairs whose stage N manifold has a margin in (0, tau]."""
-    assert mutation is None or mutation in MUTATIONS
+    pair point); undecided: the pairs whose stage N manifold has a margin in (0, tau]; n_points (pair-contact points of the
+    body) and, from joint_terms, n_joint, n_binding, limit_margin, wrap_margin, joint_cond and `limits`."""
+    assert mutation is None or mutation in MUTATIONS + JOINT_MUTATIONS
+    joint_mutation = mutation if mutation in JOINT_MUTATIONS else None
     num = num or xm.native()
     sqrt = num.sqrt
     b64 = np.ascontiguousarray(bodies, dtype=np.float64).reshape(-1, 38)
@@ -289,11 +441,13 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     body_mu = None
     if mu is not None or np.isfinite(ground_mu):
         body_mu = np.minimum(np.full(n, np.inf) if mu is None else np.asarray(mu, dtype=np.float64), ground_mu)
+    integrated_pos, integrated_rot = pos, rot
     pos, rot, g = xm.ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain, body_mu, limit)
 
     # 4. pair contacts, Jacobi: every point from the poses after step 3, a body applies the average of its points
     inc, ref, pair, p_inc, p_ref = manifold_points(manifolds)
     branch, pair_cond = g["branch"].copy(), np.full(n, np.inf)
+    sum_p, sum_q, count = pos * 0, rot * 0, np.zeros(n, dtype=np.int64)
     if inc:
         inc, ref, pair = np.array(inc), np.array(ref), np.array(pair)
         c0, surface = np.stack(p_inc, axis=1), np.stack(p_ref, axis=1)
@@ -335,7 +489,6 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
         dpos_i, dpos_r = impulse_i * im[inc], impulse_r * im[ref]
         drot_i = qmul(pure(cross(matvec(Mi, arm_i), impulse_i)) * 0.5, rot[:, inc])     # rigid.rs:118-122
         drot_r = qmul(pure(cross(matvec(Mr, arm_r), impulse_r)) * 0.5, rot[:, ref])
-        sum_p, sum_q, count = pos * 0, rot * 0, np.zeros(n, dtype=np.int64)
         seen = set()
         d64 = num.to_f64(dist)
         both = np.minimum(gap, clamp)
@@ -348,7 +501,14 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
                 seen.add((body, pair[t]))
                 pair_cond[body] = min(pair_cond[body], d64[t])
                 branch[body] = min(branch[body], both[t])
-        hit = np.nonzero(count)[0]
+    n_points = count.copy()
+    # ... and the joints' entries, from the same poses, in the same average
+    at = (integrated_pos, integrated_rot) if joint_mutation == "joints_from_integrated" else (pos, rot)
+    joint_p, joint_q, joint_count, joint_info = joint_terms(num, s, at[0], at[1], joints, limits, compliance, limit, joint_mutation)
+    if len(joints):
+        sum_p, sum_q, count = sum_p + joint_p, sum_q + joint_q, count + joint_count
+    hit = np.nonzero(count)[0]
+    if len(hit):
         cnt = num.conv(count[hit].astype(np.float64))
         pos, rot = pos.copy(), rot.copy()
         pos[:, hit] = pos[:, hit] + sum_p[:, hit] / cnt
@@ -359,4 +519,4 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     s.update(position=pos, rotation=rot, velocity=vel, angular_velocity=ang)
     return {"state": xm._pack(s), "frames": frames, "manifolds": manifolds, "undecided": undecided, "mask": g["mask"],
             "margin": g["margin"], "cond": g["cond"], "flip_margin": flip_margin, "domain": domain, "branch": branch,
-            "pair_cond": pair_cond}
+            "pair_cond": pair_cond, "n_points": n_points, **joint_info}
