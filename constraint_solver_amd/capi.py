@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "xpbd_world_set_external_wrench", "xpbd_world_set_external_wrench_device", "xpbd_world_apply_impulses",
     "xpbd_world_apply_impulses_device", "xpbd_world_set_dynamics", "xpbd_world_get_dynamics",
     "xpbd_multi_world_set_external_wrench", "xpbd_multi_world_apply_impulses",
+    "xpbd_world_overlap", "xpbd_world_overlap_device", "xpbd_multi_world_overlap",
 ]
 
 
@@ -154,6 +155,43 @@ def rays(origins, directions, max_distance=np.inf, ignore=None):
     out["origin"], out["direction"], out["max_distance"] = o, d, max_distance
     out["ignore_body"] = NO_HIT if ignore is None else ignore
     return out
+
+
+# xpbd_overlap_query (72 bytes) / xpbd_overlap_hit (16 bytes) as numpy records; overlap queries (EXTENSION)
+OVERLAP_QUERY_DTYPE = np.dtype([("position", "<f8", (3,)), ("rotation", "<f8", (4,)), ("shape", "<u4"), ("ignore_body", "<u4"),
+                                ("mask", "<u4"), ("reserved", "<u4")])
+OVERLAP_HIT_DTYPE = np.dtype([("body", "<u4"), ("feature", "<u4"), ("separation", "<f8")])
+OVERLAP_BRUTE_FORCE, OVERLAP_MASKED = 1, 2
+OVERLAP_SORT_STAGE = 1024         # hits of one query the sort stages in LDS (kOverlapSortStage, csrc/xpbd_query.h)
+
+
+def overlap_queries(position, rotation, shape, ignore=None, mask=None):
+    """OVERLAP_QUERY_DTYPE records from (n, 3) positions, (n, 4) rotations {s, x, y, z} and shape indices (all broadcast), the
+    body each query ignores (None: none) and its group mask (None: ~0; read with OVERLAP_MASKED only)."""
+    p, r = np.atleast_2d(np.asarray(position, dtype=np.float64)), np.atleast_2d(np.asarray(rotation, dtype=np.float64))
+    sh = np.atleast_1d(np.asarray(shape, dtype=np.uint32))
+    extra = [np.atleast_1d(np.asarray(x)) for x in (ignore, mask) if x is not None]
+    n = max([p.shape[0], r.shape[0], sh.shape[0]] + [x.shape[0] for x in extra])
+    out = np.zeros(n, dtype=OVERLAP_QUERY_DTYPE)
+    out["position"], out["rotation"], out["shape"] = p, r, sh
+    out["ignore_body"] = NO_HIT if ignore is None else ignore
+    out["mask"] = 0xFFFFFFFF if mask is None else mask
+    return out
+
+
+def _overlap(fn, h, queries, flags):
+    """(offsets, hits) of an overlap call with host arrays: once to count, once to fill."""
+    q = np.ascontiguousarray(queries, dtype=OVERLAP_QUERY_DTYPE).reshape(-1)
+    offsets = np.zeros(q.size + 1, dtype=np.uint32)
+    total = C.c_uint32(0)
+    qp = q.ctypes.data if q.size else None
+    rc = fn(h, qp, q.size, flags, offsets.ctypes.data, None, 0, C.byref(total))
+    if rc != E_CAPACITY:            # (a count of more than nothing comes back as "no room")
+        _check(rc)
+    hits = np.zeros(total.value, dtype=OVERLAP_HIT_DTYPE)
+    if total.value:
+        _check(fn(h, qp, q.size, flags, offsets.ctypes.data, hits.ctypes.data, hits.size, C.byref(total)))
+    return offsets, hits
 
 
 # Contact reports (EXTENSION): xpbd_pair_contact (64 bytes), xpbd_contact_point (48), xpbd_contact_event (12)
@@ -306,6 +344,13 @@ def hip_lib():
             L.xpbd_world_get_dynamics.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
             L.xpbd_multi_world_set_external_wrench.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
             L.xpbd_multi_world_apply_impulses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            ovl = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_overlap.argtypes = ovl + [_u32p]
+            L.xpbd_world_overlap_device.argtypes = ovl
+            L.xpbd_multi_world_overlap.argtypes = ovl + [_u32p]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -555,6 +600,17 @@ class World:
             _check(hip_lib().xpbd_world_raycast_device(self._h, C.c_void_p(rays_ptr), n, flags, C.c_void_p(hits_ptr)))
         else:
             _check(hip_lib().xpbd_world_raycast_masked_device(self._h, C.c_void_p(rays_ptr), n, flags, mask, C.c_void_p(hits_ptr)))
+
+    def overlap(self, queries, flags=0):
+        """(offsets, hits) of the bodies every convex volume touches (OVERLAP_QUERY_DTYPE records, see overlap_queries()) at the
+        current poses: the hits of query q are hits[offsets[q]:offsets[q + 1]] (OVERLAP_HIT_DTYPE), in ascending body index."""
+        return _overlap(hip_lib().xpbd_world_overlap, self._h, queries, flags)
+
+    def overlap_device(self, queries_ptr, n, offsets_ptr, hits_ptr, cap, flags=0):
+        """Device arrays of n xpbd_overlap_query, n + 1 uint32 offsets and cap xpbd_overlap_hit, stream-ordered on the world's
+        stream; the total is offsets[n], hits beyond cap are not written."""
+        _check(hip_lib().xpbd_world_overlap_device(self._h, C.c_void_p(queries_ptr), n, flags, C.c_void_p(offsets_ptr),
+                                                   C.c_void_p(hits_ptr) if hits_ptr else None, cap))
 
     # body edits (include/xpbd.h, "Body EDITS"): forces, impulses and state of resident bodies
     def set_external_wrench(self, indices=None, force=None, torque=None):
@@ -819,6 +875,10 @@ class MultiWorld:
         else:
             _check(hip_lib().xpbd_multi_world_raycast_masked(self._h, rp, r.size, flags, mask, hp))
         return out
+
+    def overlap(self, queries, flags=0):
+        """World.overlap over the whole sharded world (collective); bodies and ignore_body are global indices."""
+        return _overlap(hip_lib().xpbd_multi_world_overlap, self._h, queries, flags)
 
     def synchronize(self):
         _check(hip_lib().xpbd_multi_world_synchronize(self._h))

@@ -89,6 +89,8 @@ struct xpbd_material;
 struct xpbd_ray;
 struct xpbd_impulse;
 struct xpbd_ray_hit;
+struct xpbd_overlap_query;
+struct xpbd_overlap_hit;
 struct xpbd_pair_contact;
 struct xpbd_contact_point;
 
@@ -132,6 +134,19 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
                     bool masked, uint32_t mask);
 int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id,
                  bool masked, uint32_t mask);
+// The argument checks of xpbd_world_overlap(_device) against one world (polytopes set, bodies resident) / of the queries'
+// reserved and shape fields against a table of n_shapes shapes.
+int check_overlap(const char *who, const xpbd_world *w, const void *queries, uint32_t n_queries, uint32_t flags, const void *offsets,
+                  const void *hits, uint32_t cap);
+int check_overlap_queries(const char *who, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t n_shapes);
+uint32_t shape_count(const xpbd_world *w);
+// Overlap queries against the world's bodies (include/xpbd.h, "Overlap queries"), stream-ordered (device arrays; the total is
+// dev_offsets[n_queries]) / from and to host arrays (waits; *n_out = the total, XPBD_E_CAPACITY when it exceeds cap; a world
+// without bodies reports nothing).  dev_global_id as for the ray casts: what hit.body and ignore_body mean, ascending with the slot.
+int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32_t n_queries, uint32_t flags, uint32_t *dev_offsets,
+                    xpbd_overlap_hit *dev_hits, uint32_t cap, const uint32_t *dev_global_id);
+int overlap_host(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets, xpbd_overlap_hit *hits,
+                 uint32_t cap, uint32_t *n_out, const uint32_t *dev_global_id);
 // The current frame's contact report of a shard of the multi-GPU world (include/xpbd.h, "Contact REPORTS"): only the pairs whose
 // lower body has dev_owned[slot] != 0, bodies named by dev_global_id[slot] (device arrays of the world's body count; global ids
 // ascending with the slot).  Waits.  A world without bodies reports nothing.

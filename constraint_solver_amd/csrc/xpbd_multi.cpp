@@ -1325,8 +1325,9 @@ int restore_frame(xpbd_multi_world *mw)
     return XPBD_OK;
 }
 
-// One shard's part of a ray cast: its OWNED bodies answer, under their global ids (ghosts are listed as XPBD_NO_HIT).
-int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, bool masked, uint32_t mask, xpbd_ray_hit *hits)
+// The global id of every local slot of a shard for its scene queries: its OWNED bodies answer, under their global ids (ghosts
+// are listed as XPBD_NO_HIT).
+int upload_query_ids(Shard &s)
 {
     XPBD_TRY(bind(s));
     std::vector<uint32_t> ids(s.local_ids);
@@ -1338,8 +1339,30 @@ int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flag
             id = XPBD_NO_HIT;
     }
     XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
-    XPBD_TRY(upload_vector(s.query_ids, ids, s.stream));
+    return upload_vector(s.query_ids, ids, s.stream);
+}
+
+int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, bool masked, uint32_t mask, xpbd_ray_hit *hits)
+{
+    XPBD_TRY(upload_query_ids(s));
     return xpbd::raycast_host(s.world, rays, n_rays, flags, hits, s.query_ids.as<uint32_t>(), masked, mask);
+}
+
+// One shard's part of an overlap query: its OWNED bodies answer, under their global ids.  Counts first, then lists into a
+// buffer of exactly that size; local_ids ascend, so every query's list is ascending in global index.
+int shard_overlap(Shard &s, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, std::vector<uint32_t> &offsets,
+                  std::vector<xpbd_overlap_hit> &hits)
+{
+    XPBD_TRY(upload_query_ids(s));
+    offsets.assign((size_t)n_queries + 1, 0);
+    uint32_t total = 0;
+    const int rc = xpbd::overlap_host(s.world, queries, n_queries, flags, offsets.data(), nullptr, 0, &total, s.query_ids.as<uint32_t>());
+    if (rc != XPBD_OK && rc != XPBD_E_CAPACITY) // (a count of more than nothing comes back as "no room")
+        return rc;
+    hits.resize(total);
+    if (total == 0)
+        return XPBD_OK;
+    return xpbd::overlap_host(s.world, queries, n_queries, flags, offsets.data(), hits.data(), total, &total, s.query_ids.as<uint32_t>());
 }
 
 int check_usable(const xpbd_multi_world *mw, const char *who)
@@ -1391,6 +1414,100 @@ int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, u
         }
         hits[r] = best;
     }
+    return XPBD_OK;
+}
+
+// xpbd_multi_world_overlap: every local shard answers for its owned bodies; the counts, the offsets and the hits of every
+// rank are gathered (as capture_report gathers its lists, every rank's status in each collective) and merged per query --
+// the ranks' lists are disjoint and each is ascending.
+int multi_overlap(xpbd_multi_world *mw, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets,
+                  xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out)
+{
+    const char *who = "xpbd_multi_world_overlap";
+    XPBD_TRY(check_usable(mw, who));
+    if (n_queries && (!queries || !offsets || !n_out))
+        return set_error(XPBD_E_INVALID, "%s: NULL queries, offsets or n_out", who);
+    if (cap && !hits)
+        return set_error(XPBD_E_INVALID, "%s: NULL hits with cap = %u", who, cap);
+    if (flags & ~(XPBD_OVERLAP_BRUTE_FORCE | XPBD_OVERLAP_MASKED))
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (!mw->have_shapes)
+        return set_error(XPBD_E_INVALID, "%s: call xpbd_multi_world_set_polytopes first", who);
+    XPBD_TRY(xpbd::check_overlap_queries(who, queries, n_queries, (uint32_t)mw->shape_radius.size()));
+    if (!mw->planned || mw->n_global == 0)
+        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    if (n_queries == 0) {
+        if (n_out)
+            *n_out = 0;
+        return XPBD_OK;
+    }
+    const size_t nl = mw->shards.size();
+    const uint32_t w = mw->n_ranks;
+    LocalStatus st;
+    std::vector<std::vector<uint32_t>> my_offsets(nl, std::vector<uint32_t>((size_t)n_queries + 1, 0));
+    std::vector<std::vector<xpbd_overlap_hit>> my_hits(nl);
+    for (size_t k = 0; k < nl; ++k)
+        if (st.ok())
+            st.keep(shard_overlap(mw->shards[k], queries, n_queries, flags, my_offsets[k], my_hits[k]));
+    std::vector<uint32_t> my_total(nl);
+    std::vector<const void *> send(nl);
+    for (size_t k = 0; k < nl; ++k) {
+        my_total[k] = (uint32_t)my_hits[k].size();
+        send[k] = &my_total[k];
+    }
+    std::vector<uint8_t> gathered, all_offsets, all_hits;
+    XPBD_TRY(all_gather_host(mw, send, sizeof(uint32_t), gathered, st));
+    std::vector<uint32_t> totals(w);
+    std::memcpy(totals.data(), gathered.data(), (size_t)w * sizeof(uint32_t));
+    uint32_t widest = 1;
+    uint64_t total = 0;
+    for (uint32_t t : totals) {
+        widest = std::max(widest, t);
+        total += t;
+    }
+    const size_t row = ((size_t)n_queries + 1) * sizeof(uint32_t);
+    for (size_t k = 0; k < nl; ++k)
+        send[k] = my_offsets[k].data();
+    XPBD_TRY(all_gather_host(mw, send, row, all_offsets, st));
+    for (size_t k = 0; k < nl; ++k) {
+        my_hits[k].resize(widest);
+        send[k] = my_hits[k].data();
+    }
+    XPBD_TRY(all_gather_host(mw, send, (size_t)widest * sizeof(xpbd_overlap_hit), all_hits, st));
+    if (total > 0xFFFFFFFFull)
+        return set_error(XPBD_E_INVALID, "%s: %llu hits do not fit the 32-bit offsets", who, (unsigned long long)total);
+    auto offset_of = [&](uint32_t r, uint32_t q) {
+        uint32_t v;
+        std::memcpy(&v, all_offsets.data() + (size_t)r * row + (size_t)q * sizeof v, sizeof v);
+        return v;
+    };
+    std::vector<xpbd_overlap_hit> segment;
+    uint32_t at = 0;
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        offsets[q] = at;
+        segment.clear();
+        uint32_t parts = 0;
+        for (uint32_t r = 0; r < w; ++r) {
+            const uint32_t b0 = offset_of(r, q), b1 = offset_of(r, q + 1);
+            if (b1 == b0)
+                continue;
+            ++parts;
+            const size_t old = segment.size();
+            segment.resize(old + (b1 - b0));
+            std::memcpy(segment.data() + old, all_hits.data() + ((size_t)r * widest + b0) * sizeof(xpbd_overlap_hit), (size_t)(b1 - b0) * sizeof(xpbd_overlap_hit));
+        }
+        if (parts > 1)
+            std::sort(segment.begin(), segment.end(), [](const xpbd_overlap_hit &a, const xpbd_overlap_hit &b) { return a.body < b.body; });
+        for (const xpbd_overlap_hit &h : segment) {
+            if (at < cap)
+                hits[at] = h;
+            ++at;
+        }
+    }
+    offsets[n_queries] = at;
+    *n_out = at;
+    if (at > cap)
+        return set_error(XPBD_E_CAPACITY, "%s: %u hits but room for %u", who, at, cap);
     return XPBD_OK;
 }
 
@@ -1965,6 +2082,12 @@ int xpbd_multi_world_raycast_masked(xpbd_multi_world *mw, const xpbd_ray *rays, 
                                     xpbd_ray_hit *hits)
 try {
     return multi_raycast("xpbd_multi_world_raycast_masked", mw, rays, n_rays, flags, true, mask, hits);
+} XPBD_MULTI_ABI_CATCH
+
+int xpbd_multi_world_overlap(xpbd_multi_world *mw, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets,
+                             xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out)
+try {
+    return multi_overlap(mw, queries, n_queries, flags, offsets, hits, cap, n_out);
 } XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_set_contact_report(xpbd_multi_world *mw, uint32_t enable)

@@ -1,4 +1,4 @@
-// xpbd_query.h -- scene queries (EXTENSION): launchers for the batched ray casts in xpbd_query.hip.
+// xpbd_query.h -- scene queries (EXTENSION): launchers for the batched ray casts and overlap queries in xpbd_query.hip.
 //
 // Semantics: include/xpbd.h, "Scene queries".  Two paths give the same bits in every field of every hit:
 //  * grid: the bodies' bounding spheres (frame * centroid, PolytopeTables::radii) go into a uniform grid built for this call
@@ -55,5 +55,29 @@ struct RayFilter {
 // body that must not answer; null: the body's slot.  A body the filter drops answers no ray, as a ghost does.
 hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const RayFilter &filter, const void *rays,
                           uint32_t n_rays, bool brute, const QueryScratch &s, void *hits, hipStream_t stream);
+
+// ---- overlap queries: which bodies does each convex volume touch? (include/xpbd.h, "Overlap queries") ---------------------
+// Passes: the bounding spheres of the bodies (k_query_bodies) and of the queries (k_overlap_queries); on the grid path the grid
+// of a ray cast (k_query_grid, k_query_bin); a COUNT pass -- one group of 16 / 32 / 64 lanes per query tests its candidates
+// (ignore_body and mask, tight spheres, the decision part of the SAT) and leaves one number per query; an exclusive scan of
+// the numbers, which is the caller's `offsets`; a FILL pass that repeats the tests and writes the hits; a sort of every
+// query's segment into ascending body index.  Testing twice avoids any list whose length only the host could learn, so the
+// whole call is stream-ordered.  The brute-force path visits the bodies of every query in ascending index instead of walking
+// cells (no grid, no sort); a segment that the caller's `cap` cuts short is listed that way on the grid path too.
+constexpr uint32_t kOverlapSortStage = 1024; // hits of one query sorted in LDS; longer segments are sorted in global memory
+
+struct OverlapSizes {
+    QuerySizes q;  // the scratch shared with the ray casts (scan_scratch also covers the scan of the offsets)
+    size_t qrec;   // per query: sphere centre, radius
+};
+OverlapSizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute);
+
+// n_queries device xpbd_overlap_query against the bodies of `b`: offsets[n_queries + 1] (device) receives the CSR offsets of
+// the full answer, hits[0 .. min(total, cap)) (device xpbd_overlap_hit; may be null with cap == 0) its first entries.
+// global_id as for launch_raycast; filter: the bodies' collision filters (null: every body in group ~0u), tested against the
+// queries' masks when `masked`.
+hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *queries,
+                          uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, double *qrec, uint32_t *offsets, void *hits,
+                          uint32_t cap, hipStream_t stream);
 
 } // namespace xpbd

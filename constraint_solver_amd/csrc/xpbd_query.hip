@@ -1,4 +1,4 @@
-// xpbd_query.hip -- scene queries (EXTENSION) for gfx950: batched ray casts against the world's bodies.
+// xpbd_query.hip -- scene queries (EXTENSION) for gfx950: batched ray casts and overlap queries against the world's bodies.
 //
 // Semantics: include/xpbd.h, "Scene queries"; layout of the work: xpbd_query.h.  Determinism: the winner of a ray is the
 // minimum of its candidates under one total order -- (t, index) -- and a candidate's t is a function of the ray and the body
@@ -7,6 +7,9 @@
 #include <cfloat>
 #include <cmath>
 
+#include <type_traits>
+
+#include "xpbd_clip.hpp"
 #include "xpbd_query.h"
 #include "xpbd_contacts.h"
 #include "xpbd_device.hpp"
@@ -501,6 +504,385 @@ __global__ void __launch_bounds__(64) k_query_brute_finish(const xpbd_ray *__res
         write_hit(load_ray(rays, r), best, rec, shape_id, t, hits + r);
 }
 
+// ---- overlap queries: convex volumes against the bodies ------------------------------------------------------------------
+// Semantics: include/xpbd.h, "Overlap queries".  One (query, body) pair is decided by three steps -- ignore_body and the group
+// mask, the tight bounding spheres, the decision part of the SAT -- and both paths run the same routines for them, so the set
+// of hits of a query does not depend on the path.  Neither does its order: the brute-force path visits the bodies in
+// ascending index and reports them as it goes; the grid path reports them in cell order and k_overlap_sort brings every
+// segment into ascending index (indices are distinct).  Every pass is run twice: once to count, once to fill, with an
+// exclusive scan in between -- no list whose length the host would have to learn.
+constexpr uint32_t kOverlapRecDoubles = 4; // per query: sphere centre xyz, radius (< 0: the query reports nothing)
+constexpr uint32_t kNoBody = 0xFFFFFFFFu;
+static_assert(sizeof(xpbd_overlap_query) == 72 && sizeof(xpbd_overlap_hit) == 16, "xpbd_overlap_query is 72 bytes, xpbd_overlap_hit 16");
+
+// One lane per query: its bounding sphere, and whether it can report anything (finite frame, shape of the table).
+__global__ void __launch_bounds__(kBlock) k_overlap_queries(const xpbd_overlap_query *__restrict__ queries, uint32_t n_queries, PolytopeTables t,
+                                                            double *__restrict__ qrec)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_queries)
+        return;
+    const xpbd_overlap_query &x = queries[q];
+    const Frame f{Vec3{x.position[0], x.position[1], x.position[2]}, Quat{x.rotation[0], x.rotation[1], x.rotation[2], x.rotation[3]}};
+    Vec3 c{0.0, 0.0, 0.0};
+    double r = -1.0;
+    if (x.shape < t.n_shapes) {
+        const double *cc = t.centroids + 3 * (size_t)x.shape;
+        c = f * Vec3{cc[0], cc[1], cc[2]};
+        const bool finite = isfinite(f.position.x) && isfinite(f.position.y) && isfinite(f.position.z) && isfinite(f.rotation.s) &&
+                            isfinite(f.rotation.x) && isfinite(f.rotation.y) && isfinite(f.rotation.z) && isfinite(c.x) && isfinite(c.y) &&
+                            isfinite(c.z);
+        const double rs = t.radii[x.shape];
+        if (finite && rs >= 0.0)
+            r = rs;
+    }
+    double2 *o = reinterpret_cast<double2 *>(qrec + (size_t)q * kOverlapRecDoubles);
+    o[0] = double2{c.x, c.y};
+    o[1] = double2{c.z, r};
+}
+
+// Working set of one group: the world-space vertices of the volume (0, staged once per query) and of the candidate body (1),
+// and each set in the other's local space; the world-space edge directions take the place of `local` for the edge axes.
+template <uint32_t V>
+struct OverlapLds {
+    static constexpr uint32_t kVerts = V;
+    double world[2][V][3];
+    double local[2][V][3];
+};
+
+// The decision part of the SAT for volume A (frame fa, shape sa, its world-space vertices already in s.world[0]) against body
+// B, by a group of L lanes: op_sat of the oracle up to its feature choice, with the arithmetic of the contact pipeline's
+// sat_pair (xpbd_pairs.hip) -- vertices through their own frame into world space and through the inverse of the other frame
+// into its local space, supports as LAST maxima under the total order, faces and edge-direction pairs as FIRST maxima.  True:
+// not separated, with the feature and its separation.  Every lane of the group returns the same values.
+template <uint32_t L, class Lds>
+__device__ __forceinline__ bool overlap_decide(Lds &s, const PolytopeTables &t, const Frame &fa, const Frame &fa_inv, uint32_t sa, const Frame &fb,
+                                               uint32_t sb, uint32_t lane, uint32_t &feature, double &separation)
+{
+    constexpr uint32_t H = L / 2;
+    const ShapeDesc da = t.desc[sa], db = t.desc[sb];
+    if (da.n_verts == 0 || db.n_verts == 0 || da.n_faces == 0 || db.n_faces == 0)
+        return false;
+    const Frame fb_inv = inverse(fb);
+    const uint32_t half = lane / H, k = lane % H; // first half of the group works for A, second for B
+    __syncthreads(); // (one wave per workgroup: a fence; the previous candidate's reads are done)
+    if (half == 0) {
+        for (uint32_t vtx = k; vtx < da.n_verts; vtx += H)
+            st3(s.local[0], vtx, fb_inv * ld3(s.world[0], vtx));
+    } else {
+        for (uint32_t vtx = k; vtx < db.n_verts; vtx += H) {
+            const double *v = t.verts + 3 * (size_t)(db.vert0 + vtx);
+            const Vec3 w = fb * Vec3{v[0], v[1], v[2]};
+            st3(s.world[1], vtx, w);
+            st3(s.local[1], vtx, fa_inv * w);
+        }
+    }
+    __syncthreads();
+
+    // ---- face queries: A's faces on the first half, B's on the second --------------------------------------------------
+    double fdist = -DBL_MAX;
+    uint32_t fidx = kNoBody;
+    {
+        const ShapeDesc dm = half ? db : da;
+        const uint32_t n_other = half ? da.n_verts : db.n_verts;
+        for (uint32_t f = k; f < dm.n_faces; f += H) {
+            const double *pl = t.planes + 4 * (size_t)(dm.face0 + f);
+            const Vec3 n{pl[0], pl[1], pl[2]}, dir = -n;
+            Vec3 sup = ld3(s.local[half ^ 1u], 0);
+            long long sup_key = total_key(dot(sup, dir));
+            for (uint32_t v = 1; v < n_other; ++v) {
+                const Vec3 x = ld3(s.local[half ^ 1u], v);
+                const long long key = total_key(dot(x, dir));
+                if (sup_key <= key) {
+                    sup_key = key;
+                    sup = x;
+                }
+            }
+            const double dist = dot(n, sup) - pl[3];
+            if (dist > fdist) { // ascending f on this lane: first maximum; a NaN never wins
+                fdist = dist;
+                fidx = f;
+            }
+        }
+    }
+    reduce_max_first(fdist, fidx, H);
+    const double fdist_other = partner(fdist, H);
+    const uint32_t fidx_other = partner(fidx, H);
+    const double qa = half ? fdist_other : fdist, qb = half ? fdist : fdist_other;
+    const uint32_t face_a = half ? fidx_other : fidx, face_b = half ? fidx : fidx_other;
+    if (qa >= 0.0 || qb >= 0.0 || face_a == kNoBody || face_b == kNoBody)
+        return false;
+
+    // ---- edge axes: (unique edge direction of A) x (unique edge direction of B) -----------------------------------------
+    double ebest = -DBL_MAX;
+    uint32_t eq = kNoBody;
+    const double *cca = t.centroids + 3 * (size_t)sa, *ccb = t.centroids + 3 * (size_t)sb;
+    const Vec3 a_to_b = fb * Vec3{ccb[0], ccb[1], ccb[2]} - fa * Vec3{cca[0], cca[1], cca[2]};
+    const bool dirs_staged = da.n_dirs <= Lds::kVerts && db.n_dirs <= Lds::kVerts;
+    __syncthreads();
+    if (dirs_staged) {
+        for (uint32_t d = lane; d < da.n_dirs + db.n_dirs; d += L) {
+            const bool of_b = d >= da.n_dirs;
+            const uint32_t kd = of_b ? d - da.n_dirs : d;
+            const double *dd = t.edge_dirs + 3 * (size_t)((of_b ? db.dir0 : da.dir0) + kd);
+            st3(s.local[of_b ? 1 : 0], kd, (of_b ? fb : fa).rotation * Vec3{dd[0], dd[1], dd[2]});
+        }
+        __syncthreads();
+    }
+    const uint32_t total = da.n_dirs * db.n_dirs;
+    for (uint32_t q = lane; q < total; q += L) {
+        const uint32_t i = q / db.n_dirs, j = q - i * db.n_dirs;
+        Vec3 n;
+        if (dirs_staged) {
+            n = normalized(cross(ld3(s.local[0], i), ld3(s.local[1], j)));
+        } else {
+            const double *da_ = t.edge_dirs + 3 * (size_t)(da.dir0 + i), *db_ = t.edge_dirs + 3 * (size_t)(db.dir0 + j);
+            n = normalized(cross(fa.rotation * Vec3{da_[0], da_[1], da_[2]}, fb.rotation * Vec3{db_[0], db_[1], db_[2]}));
+        }
+        if (!(fabs(n.x) <= DBL_MAX && fabs(n.y) <= DBL_MAX && fabs(n.z) <= DBL_MAX))
+            continue; // parallel directions: a NaN axis contributes nothing
+        if (dot(n, a_to_b) < 0.0)
+            n = -n;
+        double reach_a = dot(ld3(s.world[0], 0), n), reach_b = dot(ld3(s.world[1], 0), n);
+        for (uint32_t v = 1; v < da.n_verts; ++v) {
+            const double rr = dot(ld3(s.world[0], v), n);
+            if (rr > reach_a)
+                reach_a = rr;
+        }
+        for (uint32_t v = 1; v < db.n_verts; ++v) {
+            const double rr = dot(ld3(s.world[1], v), n);
+            if (rr < reach_b)
+                reach_b = rr;
+        }
+        const double dist = reach_b - reach_a;
+        if (dist > ebest) { // ascending q on this lane: first maximum
+            ebest = dist;
+            eq = q;
+        }
+    }
+    reduce_max_first(ebest, eq, L);
+    if (ebest >= 0.0)
+        return false;
+    const double face_best = qa > qb ? qa : qb;
+    const bool use_edges = eq != kNoBody && ebest > face_best + kEdgeBias;
+    feature = use_edges ? XPBD_FEATURE_EDGES : (qa == face_best ? XPBD_FEATURE_FACE_A : XPBD_FEATURE_FACE_B);
+    separation = use_edges ? ebest : face_best;
+    return true;
+}
+
+struct OverlapArgs {
+    const xpbd_overlap_query *queries;
+    const double *qrec;         // k_overlap_queries
+    const double *rec;          // k_query_bodies
+    const uint32_t *gid;        // the index a body is known by (null: its slot); XPBD_NO_HIT bodies have radius < 0 in rec
+    const uint2 *filter;        // collision filters (null: every body in group ~0u)
+    const QueryGrid *grid;      // grid path only
+    const uint32_t *cell_start;
+    const uint32_t *items;
+    uint32_t *offsets;          // count pass: offsets[q] = hits of q; fill pass: the scanned array
+    xpbd_overlap_hit *hits;
+    uint32_t n_queries, cap, masked, brute;
+};
+
+// Count (FILL = false) or list (true) the hits of every query: one group of L lanes per query, 64 / L queries per wave.  The
+// lanes of a group run steps 1 and 2 for one candidate each -- on the grid path each lane walks cells of its own out of the
+// box of cells the query's sphere covers -- and the group then decides the survivors one after the other (step 3).
+template <uint32_t L, uint32_t V, bool FILL>
+__global__ void __launch_bounds__(64) k_overlap_pass(BodyArrays b, PolytopeTables t, OverlapArgs a)
+{
+    constexpr uint32_t PW = 64 / L;
+    __shared__ OverlapLds<V> s_all[PW];
+    const uint32_t group = threadIdx.x / L, lane = threadIdx.x % L;
+    const uint32_t q = blockIdx.x * PW + group;
+    if (q >= a.n_queries)
+        return;
+    OverlapLds<V> &s = s_all[group];
+    const double2 *qr = reinterpret_cast<const double2 *>(a.qrec + (size_t)q * kOverlapRecDoubles);
+    const double2 q0 = qr[0], q1 = qr[1];
+    const Vec3 cq{q0.x, q0.y, q1.x};
+    const double rq = q1.y;
+    // A segment the caller's buffer cuts short is listed in ascending order straight away (its first entries are what the
+    // caller gets, and the sort needs whole segments); segments past the buffer are not listed at all.
+    bool ordered = a.brute != 0;
+    uint32_t base = 0, room = 0xFFFFFFFFu;
+    if (FILL) {
+        base = a.offsets[q];
+        const uint32_t end = a.offsets[q + 1];
+        if (end == base || base >= a.cap)
+            return;
+        ordered = ordered || end > a.cap;
+        room = a.cap - base;
+    }
+    uint32_t count = 0;
+    if (rq >= 0.0) {
+        const xpbd_overlap_query &x = a.queries[q];
+        const Frame fq{Vec3{x.position[0], x.position[1], x.position[2]}, Quat{x.rotation[0], x.rotation[1], x.rotation[2], x.rotation[3]}};
+        const Frame fq_inv = inverse(fq);
+        const uint32_t sq = x.shape, ignore = x.ignore_body, mask = x.mask;
+        {
+            const ShapeDesc dq = t.desc[sq];
+            for (uint32_t vtx = lane; vtx < dq.n_verts; vtx += L) {
+                const double *v = t.verts + 3 * (size_t)(dq.vert0 + vtx);
+                st3(s.world[0], vtx, fq * Vec3{v[0], v[1], v[2]});
+            }
+        }
+        // steps 1 and 2 of body i (one lane)
+        auto admit = [&](uint32_t i, Vec3 &centre, double &radius) -> bool {
+            const double2 *r = reinterpret_cast<const double2 *>(a.rec + (size_t)i * kQueryRecDoubles);
+            const double2 d = r[3], e = r[4], f = r[5];
+            centre = Vec3{d.y, e.x, e.y};
+            radius = f.x;
+            if (!(radius >= 0.0))
+                return false;
+            if ((a.gid ? a.gid[i] : i) == ignore)
+                return false;
+            if (a.masked && ((a.filter ? a.filter[i].x : ~0u) & mask) == 0)
+                return false;
+            const Vec3 between = centre - cq;
+            const double reach = rq + radius;
+            return dot(between, between) < reach * reach;
+        };
+        // step 3 of the bodies the lanes of the group hold in `mine` (kNoBody: none), in lane order
+        auto decide = [&](uint32_t mine) {
+            uint64_t todo = group_bits<L>(__ballot(mine != kNoBody));
+            while (todo) {
+                const uint32_t src = (uint32_t)__ffsll((long long)todo) - 1u;
+                todo &= todo - 1;
+                const uint32_t i = (uint32_t)__shfl((int)mine, (int)src, L);
+                uint32_t feature = 0;
+                double separation = 0.0;
+                if (overlap_decide<L>(s, t, fq, fq_inv, sq, body_frame(b, i), b.shape_id[i], lane, feature, separation)) {
+                    if (FILL && lane == 0 && count < room) {
+                        xpbd_overlap_hit h;
+                        h.body = a.gid ? a.gid[i] : i;
+                        h.feature = feature;
+                        h.separation = separation;
+                        a.hits[base + count] = h;
+                    }
+                    ++count;
+                }
+            }
+        };
+        // the cells of the query on the grid, and whether walking them beats looking at every body
+        QueryGrid g{};
+        int32_t qlo[3] = {0, 0, 0};
+        uint32_t qdim[3] = {1, 1, 1};
+        bool walk = false;
+        if (!ordered) {
+            g = *a.grid;
+            if (g.mode == kGrid) {
+                const double c[3] = {cq.x, cq.y, cq.z};
+                double cells = 1.0;
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    qlo[ax] = clamp_axis(g, ax, floor((c[ax] - rq - g.pad) / g.edge));
+                    const int32_t hi = clamp_axis(g, ax, floor((c[ax] + rq + g.pad) / g.edge));
+                    qdim[ax] = (uint32_t)(hi - qlo[ax]) + 1u;
+                    cells *= (double)qdim[ax];
+                }
+                walk = cells <= (double)g.mask + 1.0; // at most the cells a dense grid can have; beyond that, every body in turn
+            }
+        }
+        if (walk) {
+            const uint32_t cells = qdim[0] * qdim[1] * qdim[2];
+            uint32_t next = lane, at = 0, end = 0, first = 0;
+            int32_t cell[3] = {0, 0, 0};
+            for (;;) {
+                uint32_t mine = kNoBody;
+                while (mine == kNoBody) {
+                    if (at == end) { // this lane's next cell
+                        if (next >= cells)
+                            break;
+                        const uint32_t zy = next / qdim[0];
+                        cell[0] = qlo[0] + (int32_t)(next - zy * qdim[0]);
+                        cell[1] = qlo[1] + (int32_t)(zy % qdim[1]);
+                        cell[2] = qlo[2] + (int32_t)(zy / qdim[1]);
+                        next += L;
+                        const uint32_t key = query_key(g, cell[0], cell[1], cell[2]);
+                        first = at = a.cell_start[key];
+                        end = a.cell_start[key + 1];
+                        continue;
+                    }
+                    const uint32_t slot = at++, i = a.items[slot];
+                    Vec3 cb;
+                    double rb;
+                    if (!admit(i, cb, rb))
+                        continue;
+                    // A body is listed in up to 8 cells and the query covers a box of them: the pair counts in ONE cell, the
+                    // component-wise maximum of the lower corners of the two cell ranges (k_query_bin's expressions).  A
+                    // hashed key is shared by several cells: the body must really be listed in this one, and once.
+                    const double c[3] = {cb.x, cb.y, cb.z};
+                    bool here = true;
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        const int32_t lo = clamp_axis(g, ax, floor((c[ax] - rb - g.pad) / g.edge));
+                        int32_t hi = clamp_axis(g, ax, floor((c[ax] + rb + g.pad) / g.edge));
+                        hi = hi > lo + 1 ? lo + 1 : hi;
+                        here = here && cell[ax] == (lo > qlo[ax] ? lo : qlo[ax]) && cell[ax] <= hi;
+                    }
+                    if (here && !g.dense)
+                        for (uint32_t e = first; e < slot; ++e)
+                            here = here && a.items[e] != i;
+                    if (here)
+                        mine = i;
+                }
+                if (!group_bits<L>(__ballot(mine != kNoBody)))
+                    break; // every lane has run out of cells
+                decide(mine);
+            }
+        } else if (ordered || g.mode != kEmpty) {
+            for (uint32_t i0 = 0; i0 < b.n && count < room; i0 += L) {
+                const uint32_t i = i0 + lane;
+                Vec3 cb;
+                double rb;
+                decide(i < b.n && admit(i, cb, rb) ? i : kNoBody);
+            }
+        }
+    }
+    if (!FILL && lane == 0)
+        a.offsets[q] = count;
+}
+
+// Every query's segment into ascending body order, one workgroup per query.  Indices are distinct: up to kOverlapSortStage
+// entries are staged in LDS and each goes to the place its rank names; longer segments are sorted where they are, in global
+// memory, by a bitonic network whose comparators all point upwards (entries past the end count as +inf and never move).
+__global__ void __launch_bounds__(kBlock) k_overlap_sort(const uint32_t *__restrict__ offsets, xpbd_overlap_hit *__restrict__ hits, uint32_t cap)
+{
+    __shared__ xpbd_overlap_hit stage[kOverlapSortStage];
+    const uint32_t b0 = offsets[blockIdx.x], b1 = offsets[blockIdx.x + 1];
+    if (b1 > cap || b1 - b0 < 2)
+        return; // (a segment the buffer cuts short was listed in order)
+    const uint32_t len = b1 - b0;
+    xpbd_overlap_hit *seg = hits + b0;
+    if (len <= kOverlapSortStage) {
+        for (uint32_t e = threadIdx.x; e < len; e += kBlock)
+            stage[e] = seg[e];
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < len; e += kBlock) {
+            const uint32_t id = stage[e].body;
+            uint32_t rank = 0;
+            for (uint32_t o = 0; o < len; ++o)
+                rank += stage[o].body < id ? 1u : 0u;
+            seg[rank] = stage[e];
+        }
+        return;
+    }
+    for (uint32_t k = 2; (k >> 1) < len; k <<= 1)
+        for (uint32_t j = k >> 1; j; j >>= 1) {
+            for (uint32_t i = threadIdx.x; i < len; i += kBlock) {
+                const uint32_t p = j == (k >> 1) ? i ^ (k - 1u) : i ^ j; // merge of two sorted runs: mirrored; then half-cleaners
+                if (p > i && p < len) {
+                    const xpbd_overlap_hit lo = seg[i], hi = seg[p];
+                    if (lo.body > hi.body) {
+                        seg[i] = hi;
+                        seg[p] = lo;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+}
+
 } // namespace
 
 QuerySizes query_scratch_bytes(uint32_t n, uint32_t n_rays, bool brute)
@@ -557,6 +939,68 @@ hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const ui
                        s.items);
     hipLaunchKernelGGL(k_query_walk, dim3(blocks_of(n_rays)), dim3(kBlock), 0, stream, rays, n_rays, b.n, s.rec, b.shape_id, global_id, t,
                        grid, s.cell_start, s.items, hits);
+    return hipGetLastError();
+}
+
+OverlapSizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute)
+{
+    OverlapSizes o{};
+    o.q = query_scratch_bytes(n, 0, brute || n == 0);
+    o.q.brute = 8;
+    const size_t scan = ((size_t)n_queries / 1024 + 8) * 4;
+    o.q.scan_scratch = o.q.scan_scratch > scan ? o.q.scan_scratch : scan;
+    o.qrec = (size_t)(n_queries ? n_queries : 1) * kOverlapRecDoubles * 8;
+    return o;
+}
+
+hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *queries_v,
+                          uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, double *qrec, uint32_t *offsets, void *hits_v,
+                          uint32_t cap, hipStream_t stream)
+{
+    if (n_queries == 0)
+        return hipMemsetAsync(offsets, 0, sizeof(uint32_t), stream);
+    brute = brute || b.n == 0;
+    QueryGrid *grid = static_cast<QueryGrid *>(s.grid);
+    hipError_t e = hipSuccess;
+    if (b.n)
+        hipLaunchKernelGGL(k_query_bodies, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b, t, global_id, RayFilter{nullptr, 0u, 0u}, s.rec,
+                           s.partials);
+    hipLaunchKernelGGL(k_overlap_queries, dim3(blocks_of(n_queries)), dim3(kBlock), 0, stream, static_cast<const xpbd_overlap_query *>(queries_v),
+                       n_queries, t, qrec);
+    if (!brute) { // the grid of a ray cast, by the same passes
+        e = hipMemsetAsync(s.cell_start, 0, (size_t)(s.table_size + 1) * 4, stream);
+        if (e == hipSuccess)
+            e = hipMemsetAsync(s.cell_fill, 0, (size_t)s.table_size * 4, stream);
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(k_query_grid, dim3(1), dim3(kBlock), 0, stream, s.partials, blocks_of(b.n), s.table_size, grid);
+        hipLaunchKernelGGL(k_query_bin<false>, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b.n, s.rec, grid, s.cell_start, s.cell_fill,
+                           s.items);
+        if ((e = launch_exclusive_scan(s.cell_start, s.table_size, s.scan_scratch, stream)) != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(k_query_bin<true>, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b.n, s.rec, grid, s.cell_start, s.cell_fill,
+                           s.items);
+    }
+    const OverlapArgs a{static_cast<const xpbd_overlap_query *>(queries_v), qrec, s.rec, global_id, filter, grid, s.cell_start, s.items, offsets,
+                        static_cast<xpbd_overlap_hit *>(hits_v), n_queries, cap, masked ? 1u : 0u, brute ? 1u : 0u};
+    // lanes per query and vertex capacity by the largest shape, as the SAT launchers of the contact pipeline choose theirs
+    auto pass = [&](auto fill) {
+        constexpr bool FILL = decltype(fill)::value;
+        if (t.max_verts <= 8 && t.max_faces <= 8)
+            hipLaunchKernelGGL((k_overlap_pass<16, 8, FILL>), dim3((n_queries + 3) / 4), dim3(64), 0, stream, b, t, a);
+        else if (t.max_verts <= 16)
+            hipLaunchKernelGGL((k_overlap_pass<32, 16, FILL>), dim3((n_queries + 1) / 2), dim3(64), 0, stream, b, t, a);
+        else
+            hipLaunchKernelGGL((k_overlap_pass<64, XPBD_MAX_SHAPE_VERTS, FILL>), dim3(n_queries), dim3(64), 0, stream, b, t, a);
+    };
+    pass(std::false_type{});
+    if ((e = launch_exclusive_scan(offsets, n_queries, s.scan_scratch, stream)) != hipSuccess)
+        return e;
+    if (cap) {
+        pass(std::true_type{});
+        if (!brute)
+            hipLaunchKernelGGL(k_overlap_sort, dim3(n_queries), dim3(kBlock), 0, stream, offsets, static_cast<xpbd_overlap_hit *>(hits_v), cap);
+    }
     return hipGetLastError();
 }
 

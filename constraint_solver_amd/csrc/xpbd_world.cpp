@@ -140,6 +140,8 @@ struct xpbd_world {
     DeviceBuffer rs_restitution, rs_start;
     // scene queries (xpbd_world_raycast*): scratch of one call, and the staging of the host variant's rays and hits
     DeviceBuffer q_rec, q_partials, q_grid, q_cell_start, q_cell_fill, q_items, q_scan, q_brute, q_rays, q_hits;
+    // ... (xpbd_world_overlap*): the queries' spheres, and the staging of the host variant's queries, offsets and hits
+    DeviceBuffer q_ovl_rec, q_ovl_queries, q_ovl_offsets, q_ovl_hits;
     // body edits (xpbd_world_set_external_wrench, _apply_impulses, _set_dynamics, _get_dynamics): the staging of the host
     // variants' indices, values (force + torque, or rows of 13 doubles) and impulse lists
     DeviceBuffer ed_indices, ed_values, ed_list;
@@ -1110,6 +1112,102 @@ int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t 
         return rc;
     XPBD_HIP_TRY(hipMemcpyAsync(hits, w->q_hits.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    return XPBD_OK;
+}
+
+int check_overlap(const char *who, const xpbd_world *w, const void *queries, uint32_t n_queries, uint32_t flags, const void *offsets,
+                  const void *hits, uint32_t cap)
+{
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n_queries && (!queries || !offsets))
+        return set_error(XPBD_E_INVALID, "%s: NULL queries or offsets", who);
+    if (cap && !hits)
+        return set_error(XPBD_E_INVALID, "%s: NULL hits with cap = %u", who, cap);
+    if (flags & ~(XPBD_OVERLAP_BRUTE_FORCE | XPBD_OVERLAP_MASKED))
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (!w->has_topology)
+        return set_error(XPBD_E_INVALID, "%s: call xpbd_world_set_polytopes first (set_shapes gives vertices only)", who);
+    if (w->n == 0)
+        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    return XPBD_OK;
+}
+
+int check_overlap_queries(const char *who, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t n_shapes)
+{
+    for (uint32_t q = 0; q < n_queries; ++q) {
+        if (queries[q].reserved)
+            return set_error(XPBD_E_INVALID, "%s: query %u has reserved = %u (must be 0)", who, q, queries[q].reserved);
+        if (queries[q].shape >= n_shapes)
+            return set_error(XPBD_E_INVALID, "%s: query %u has shape = %u but the table holds %u shapes", who, q, queries[q].shape, n_shapes);
+    }
+    return XPBD_OK;
+}
+
+uint32_t shape_count(const xpbd_world *w) { return w->n_shapes; }
+
+int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32_t n_queries, uint32_t flags, uint32_t *dev_offsets,
+                    xpbd_overlap_hit *dev_hits, uint32_t cap, const uint32_t *dev_global_id)
+{
+    static_assert(sizeof(xpbd_overlap_query) == 72 && sizeof(xpbd_overlap_hit) == 16, "xpbd_overlap_query is 72 bytes, xpbd_overlap_hit 16");
+    if (int rc = bind_device(w))
+        return rc;
+    if (n_queries == 0) {
+        if (dev_offsets)
+            XPBD_HIP_TRY(hipMemsetAsync(dev_offsets, 0, sizeof(uint32_t), w->stream));
+        return XPBD_OK;
+    }
+    const bool brute = (flags & XPBD_OVERLAP_BRUTE_FORCE) || w->n == 0;
+    const OverlapSizes o = overlap_scratch_bytes(w->n, n_queries, brute);
+    const std::pair<DeviceBuffer *, size_t> need[] = {{&w->q_rec, o.q.rec}, {&w->q_partials, o.q.partials}, {&w->q_grid, o.q.grid},
+                                                      {&w->q_cell_start, o.q.cell_start}, {&w->q_cell_fill, o.q.cell_fill},
+                                                      {&w->q_items, o.q.items}, {&w->q_scan, o.q.scan_scratch}, {&w->q_ovl_rec, o.qrec}};
+    bool grow = false;
+    for (const auto &b : need)
+        grow = grow || b.first->bytes < b.second;
+    if (grow) { // reserve() frees the block it replaces, which queued work may still use
+        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+        for (const auto &b : need)
+            XPBD_HIP_TRY(b.first->reserve(b.second));
+    }
+    const QueryScratch s{w->q_rec.as<double>(), w->q_partials.as<double>(), w->q_grid.ptr, w->q_cell_start.as<uint32_t>(),
+                         w->q_cell_fill.as<uint32_t>(), w->q_items.as<uint32_t>(), w->q_scan.as<uint32_t>(), nullptr, o.q.table_size};
+    const bool masked = (flags & XPBD_OVERLAP_MASKED) != 0;
+    XPBD_HIP_TRY(launch_overlap(w->arrays(), w->tables(), dev_global_id, masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr, dev_queries,
+                                n_queries, masked, brute, s, w->q_ovl_rec.as<double>(), dev_offsets, dev_hits, cap, w->stream));
+    return XPBD_OK;
+}
+
+int overlap_host(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets, xpbd_overlap_hit *hits,
+                 uint32_t cap, uint32_t *n_out, const uint32_t *dev_global_id)
+{
+    *n_out = 0;
+    if (n_queries == 0)
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    const size_t q_bytes = (size_t)n_queries * sizeof(xpbd_overlap_query), o_bytes = ((size_t)n_queries + 1) * sizeof(uint32_t);
+    const size_t h_bytes = (size_t)(cap ? cap : 1) * sizeof(xpbd_overlap_hit);
+    if (w->q_ovl_queries.bytes < q_bytes || w->q_ovl_offsets.bytes < o_bytes || w->q_ovl_hits.bytes < h_bytes) {
+        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+        XPBD_HIP_TRY(w->q_ovl_queries.reserve(q_bytes));
+        XPBD_HIP_TRY(w->q_ovl_offsets.reserve(o_bytes));
+        XPBD_HIP_TRY(w->q_ovl_hits.reserve(h_bytes));
+    }
+    XPBD_HIP_TRY(hipMemcpyAsync(w->q_ovl_queries.ptr, queries, q_bytes, hipMemcpyHostToDevice, w->stream));
+    if (int rc = overlap_enqueue(w, w->q_ovl_queries.as<xpbd_overlap_query>(), n_queries, flags, w->q_ovl_offsets.as<uint32_t>(),
+                                 cap ? w->q_ovl_hits.as<xpbd_overlap_hit>() : nullptr, cap, dev_global_id))
+        return rc;
+    XPBD_HIP_TRY(hipMemcpyAsync(offsets, w->q_ovl_offsets.ptr, o_bytes, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    const uint32_t total = offsets[n_queries], held = total < cap ? total : cap;
+    if (held) {
+        XPBD_HIP_TRY(hipMemcpyAsync(hits, w->q_ovl_hits.ptr, (size_t)held * sizeof(xpbd_overlap_hit), hipMemcpyDeviceToHost, w->stream));
+        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    }
+    *n_out = total;
+    if (total > cap)
+        return set_error(XPBD_E_CAPACITY, "overlap query: %u hits but room for %u", total, cap);
     return XPBD_OK;
 }
 
@@ -2336,6 +2434,30 @@ try {
     if (int rc = xpbd::check_raycast("xpbd_world_raycast_masked_device", w, dev_rays, n_rays, flags, dev_hits))
         return rc;
     return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr, true, mask);
+} XPBD_ABI_CATCH
+
+int xpbd_world_overlap(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets,
+                       xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out)
+try {
+    if (int rc = xpbd::check_overlap("xpbd_world_overlap", w, queries, n_queries, flags, offsets, hits, cap))
+        return rc;
+    if (n_queries && !n_out)
+        return set_error(XPBD_E_INVALID, "xpbd_world_overlap: NULL n_out");
+    if (int rc = xpbd::check_overlap_queries("xpbd_world_overlap", queries, n_queries, w->n_shapes))
+        return rc;
+    uint32_t total = 0;
+    const int rc = xpbd::overlap_host(w, queries, n_queries, flags, offsets, hits, cap, &total, nullptr);
+    if (n_out && (rc == XPBD_OK || rc == XPBD_E_CAPACITY))
+        *n_out = total;
+    return rc;
+} XPBD_ABI_CATCH
+
+int xpbd_world_overlap_device(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32_t n_queries, uint32_t flags, uint32_t *dev_offsets,
+                              xpbd_overlap_hit *dev_hits, uint32_t cap)
+try {
+    if (int rc = xpbd::check_overlap("xpbd_world_overlap_device", w, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap))
+        return rc;
+    return xpbd::overlap_enqueue(w, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap, nullptr);
 } XPBD_ABI_CATCH
 
 int xpbd_selftest_div_sqrt(int32_t device, const double *a, const double *b, double *quotient, double *root,

@@ -200,6 +200,31 @@ pub struct XpbdRayHit {
     pub normal: [f64; 3],
 }
 
+pub const XPBD_OVERLAP_BRUTE_FORCE: u32 = 1;
+pub const XPBD_OVERLAP_MASKED: u32 = 2;
+
+/// xpbd_overlap_query (72 bytes): a convex volume, shape `shape` of the polytope table at the frame {position, rotation {s, x, y, z}};
+/// ignore_body = XPBD_NO_HIT for none; mask is read with XPBD_OVERLAP_MASKED only; reserved = 0
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdOverlapQuery {
+    pub position: [f64; 3],
+    pub rotation: [f64; 4],
+    pub shape: u32,
+    pub ignore_body: u32,
+    pub mask: u32,
+    pub reserved: u32,
+}
+
+/// xpbd_overlap_hit (16 bytes): a body the volume touches; feature = XPBD_FEATURE_* (A = the volume, B = the body), separation < 0
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdOverlapHit {
+    pub body: u32,
+    pub feature: u32,
+    pub separation: f64,
+}
+
 pub const XPBD_CONTACT_BEGIN: u32 = 0;
 pub const XPBD_CONTACT_END: u32 = 1;
 
@@ -382,6 +407,12 @@ extern "C" {
                                             dev_hits: *mut XpbdRayHit) -> c_int;
     pub fn xpbd_multi_world_raycast_masked(mw: *mut XpbdMultiWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32,
                                            hits: *mut XpbdRayHit) -> c_int;
+    pub fn xpbd_world_overlap(w: *mut XpbdWorld, queries: *const XpbdOverlapQuery, n_queries: u32, flags: u32, offsets: *mut u32,
+                              hits: *mut XpbdOverlapHit, cap: u32, n_out: *mut u32) -> c_int;
+    pub fn xpbd_world_overlap_device(w: *mut XpbdWorld, dev_queries: *const XpbdOverlapQuery, n_queries: u32, flags: u32, dev_offsets: *mut u32,
+                                     dev_hits: *mut XpbdOverlapHit, cap: u32) -> c_int;
+    pub fn xpbd_multi_world_overlap(mw: *mut XpbdMultiWorld, queries: *const XpbdOverlapQuery, n_queries: u32, flags: u32, offsets: *mut u32,
+                                    hits: *mut XpbdOverlapHit, cap: u32, n_out: *mut u32) -> c_int;
     pub fn xpbd_world_set_contact_report(w: *mut XpbdWorld, enable: u32) -> c_int;
     pub fn xpbd_world_contact_report_counts(w: *mut XpbdWorld, out: *mut u32) -> c_int;
     pub fn xpbd_world_download_pair_contacts(w: *mut XpbdWorld, pairs: *mut XpbdPairContact, pair_cap: u32, points: *mut XpbdContactPoint,

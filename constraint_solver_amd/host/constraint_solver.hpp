@@ -25,6 +25,7 @@
 #include <limits>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/xpbd.h"
@@ -516,6 +517,21 @@ class BatchWorld {
                                         hits.empty() ? nullptr : hits.data()));
         return hits;
     }
+    // the bodies every convex volume touches at the current poses (include/xpbd.h, "Overlap queries"): the hits of query q are
+    // result.second[result.first[q] .. result.first[q + 1]), in ascending body index; counts first, then fills
+    std::pair<std::vector<uint32_t>, std::vector<xpbd_overlap_hit>> overlap(const std::vector<xpbd_overlap_query> &queries, uint32_t flags = 0)
+    {
+        std::vector<uint32_t> offsets(queries.size() + 1, 0);
+        const xpbd_overlap_query *q = queries.empty() ? nullptr : queries.data();
+        uint32_t total = 0;
+        const int rc = xpbd_world_overlap(w_, q, (uint32_t)queries.size(), flags, offsets.data(), nullptr, 0, &total);
+        if (rc != XPBD_OK && rc != XPBD_E_CAPACITY)
+            check(rc);
+        std::vector<xpbd_overlap_hit> hits(total);
+        if (total)
+            check(xpbd_world_overlap(w_, q, (uint32_t)queries.size(), flags, offsets.data(), hits.data(), total, &total));
+        return {std::move(offsets), std::move(hits)};
+    }
     // collision filters, one per body (empty: every body {~0u, ~0u}); flags: XPBD_FILTER_JOINTED or 0.  Upload clears them.
     void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)
     {
@@ -648,6 +664,21 @@ class ShardedWorld {
         check(xpbd_multi_world_raycast_masked(w_, rays.empty() ? nullptr : rays.data(), (uint32_t)rays.size(), flags, mask,
                                               hits.empty() ? nullptr : hits.data()));
         return hits;
+    }
+    // the bodies every convex volume touches, bodies by global index; collective (include/xpbd.h, "Overlap queries"): the hits of query q are
+    // result.second[result.first[q] .. result.first[q + 1]), in ascending body index; counts first, then fills
+    std::pair<std::vector<uint32_t>, std::vector<xpbd_overlap_hit>> overlap(const std::vector<xpbd_overlap_query> &queries, uint32_t flags = 0)
+    {
+        std::vector<uint32_t> offsets(queries.size() + 1, 0);
+        const xpbd_overlap_query *q = queries.empty() ? nullptr : queries.data();
+        uint32_t total = 0;
+        const int rc = xpbd_multi_world_overlap(w_, q, (uint32_t)queries.size(), flags, offsets.data(), nullptr, 0, &total);
+        if (rc != XPBD_OK && rc != XPBD_E_CAPACITY)
+            check(rc);
+        std::vector<xpbd_overlap_hit> hits(total);
+        if (total)
+            check(xpbd_multi_world_overlap(w_, q, (uint32_t)queries.size(), flags, offsets.data(), hits.data(), total, &total));
+        return {std::move(offsets), std::move(hits)};
     }
     // collision filters of the whole world, global body order (not collective); upload clears them
     void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)

@@ -797,6 +797,75 @@ int  xpbd_multi_world_raycast_masked(xpbd_multi_world *mw, const xpbd_ray *rays,
                                      uint32_t mask, xpbd_ray_hit *hits);
 
 /* ---------------------------------------------------------------------------
+ * Overlap queries (EXTENSION): which bodies does each of a batch of convex volumes touch, at the bodies' current poses.  NOT
+ * in the reference.  A host asks before it spawns or teleports a body (is the place free?), for trigger and sensor volumes,
+ * for area selection.
+ *
+ * Poses and frames.  The volume of query q is the convex polytope `shape` (xpbd_world_set_polytopes) at the frame {position,
+ * rotation}: x_world = position + rotation * x_shape.  It takes the place of body A's Rigid::frame() in the SAT.  Body b is
+ * its shape's polytope at its own Rigid::frame(), at the pose xpbd_world_download_bodies would return after the work already
+ * enqueued (the state the ray casts see).  The ground plane is not a body.
+ *
+ * Body b is reported for query q iff, in this order:
+ *   1. b is not ignore_body; with XPBD_OVERLAP_MASKED also (group_b & mask) != 0 (bodies without filters are in group ~0u;
+ *      without the flag no group is tested);
+ *   2. the tight bounding spheres overlap: between = frame_b * centroid_b - frame_q * centroid_q, reach = radius_q + radius_b,
+ *      dot(between, between) < reach * reach (any NaN makes the comparison false: a body pose or query frame that is not
+ *      finite reports nothing).  This is part of the definition, as in the contact pipeline: a pair whose spheres just miss
+ *      by rounding is not reported whatever the SAT would say;
+ *   3. the decision part of the SAT says "not separated": qa = face_axes_separation(volume, body), stop if qa >= 0 or NaN;
+ *      qb = the same with the roles swapped, stop if qb >= 0 or NaN; qe = the best separation over the pairs of unique edge
+ *      directions, stop if qe >= 0; m = max(qa, qb); the edge feature is used iff an edge pair qualified and qe > m + 1e-6,
+ *      then m = qe.  feature = XPBD_FEATURE_EDGES, else XPBD_FEATURE_FACE_A if qa == m, else XPBD_FEATURE_FACE_B (A = the
+ *      volume, B = the body); separation = m (< 0; penetration depth = -separation).  No contact points are computed.
+ *
+ * Result.  offsets[n_queries + 1] is a CSR array: the hits of query q are hits[offsets[q] .. offsets[q + 1]), in ascending
+ * body index.  offsets is always complete and *n_out always receives the total number of hits (which must fit 32 bits).  If
+ * the total exceeds cap the call returns XPBD_E_CAPACITY and hits holds the first cap entries of the full list.  hits == NULL
+ * with cap == 0 is a pure count, and no error when the total is 0.
+ *
+ * Errors (host variants, before any device work; the outputs are untouched): XPBD_E_INVALID for a NULL world, NULL queries /
+ * offsets / n_out with n_queries > 0, NULL hits with cap > 0, unknown flags, a nonzero `reserved`, a `shape` outside the
+ * table, no polytopes set, no bodies resident.  n_queries == 0 is XPBD_OK with *n_out = 0.  An overlap query changes no body,
+ * list, mask, report, history entry or plan: stepping after it gives the same bits as stepping without it.  Every mode
+ * accepts it.
+ *
+ * Method: the per-call grid of the ray casts; per query a group of lanes walks the cells its sphere covers, counts its hits,
+ * and after a scan of the counts lists them (every pair is tested twice instead of keeping a candidate list whose length
+ * the host would have to learn); each query's segment is then sorted.  Same bits with XPBD_OVERLAP_BRUTE_FORCE.
+ * ------------------------------------------------------------------------- */
+#define XPBD_OVERLAP_BRUTE_FORCE 1u   /* diagnostics: every query against every body, no grid */
+#define XPBD_OVERLAP_MASKED      2u   /* test xpbd_overlap_query.mask against the bodies' filter groups */
+
+typedef struct xpbd_overlap_query {   /* 72 bytes */
+    double   position[3];             /* frame of the volume: x_world = position + rotation * x_shape */
+    double   rotation[4];             /* {s, x, y, z}, taken as given (the caller keeps it a unit quaternion) */
+    uint32_t shape;                   /* index into the table of xpbd_world_set_polytopes */
+    uint32_t ignore_body;             /* never reported (XPBD_NO_HIT: none) */
+    uint32_t mask;                    /* with XPBD_OVERLAP_MASKED: body b answers only if (group_b & mask) != 0 */
+    uint32_t reserved;                /* must be 0 */
+} xpbd_overlap_query;
+
+typedef struct xpbd_overlap_hit {     /* 16 bytes */
+    uint32_t body;
+    uint32_t feature;                 /* XPBD_FEATURE_*: A = the query volume, B = the body */
+    double   separation;              /* < 0: the SAT's value for that feature (penetration depth = -separation) */
+} xpbd_overlap_hit;
+
+/* Host arrays; checks everything before any device work and waits for the result. */
+int  xpbd_world_overlap(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
+                        uint32_t *offsets, xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out);
+/* Device arrays; stream-ordered on the world's stream, returns before completion (it waits only when its scratch has to
+ * grow).  The total is dev_offsets[n_queries]; hits beyond cap are not written.  It cannot see the queries: a query with
+ * `shape` outside the table reports nothing and `reserved` is not checked. */
+int  xpbd_world_overlap_device(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32_t n_queries, uint32_t flags,
+                               uint32_t *dev_offsets, xpbd_overlap_hit *dev_hits, uint32_t cap);
+/* Collective: every rank passes the same queries and gets the whole answer.  Every shard answers for the bodies it OWNS;
+ * body and ignore_body are global indices.  Same bits as one xpbd_world over the same bodies. */
+int  xpbd_multi_world_overlap(xpbd_multi_world *mw, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
+                              uint32_t *offsets, xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out);
+
+/* ---------------------------------------------------------------------------
  * Contact REPORTS (EXTENSION): which body pairs the contact pipeline of XPBD_MODE_CONTACTS found touching, with the
  * manifolds it solved, and which pairs began or ended touching.  NOT in the reference; its app draws the reference and
  * incident planes of `sat` into DebugLines (src/collision.rs:69, 87) and, commented out, the contact points (:97-108).
