@@ -3,6 +3,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <utility>
 #include <vector>
 
@@ -67,6 +68,26 @@ struct DeviceBuffer {
     template <class T> T *as() const { return static_cast<T *>(ptr); }
 };
 
+// Room in buffers that work queued on `stream` may still use: growing one frees its block, so the stream is waited for first --
+// only when one of them has to grow.
+struct Reservation {
+    DeviceBuffer &buffer;
+    size_t bytes;
+};
+inline hipError_t reserve_after_sync(hipStream_t stream, std::initializer_list<Reservation> need) noexcept
+{
+    bool grow = false;
+    for (const Reservation &r : need)
+        grow = grow || r.buffer.bytes < r.bytes;
+    if (!grow)
+        return hipSuccess;
+    hipError_t e = hipStreamSynchronize(stream);
+    for (const Reservation &r : need)
+        if (e == hipSuccess)
+            e = r.buffer.reserve(r.bytes);
+    return e;
+}
+
 // ---- one frame of a shard of the multi-GPU world (xpbd_multi.cpp), split at the halo exchange ---------------------------
 // All device pointers; slots are local body indices of the shard's world.
 struct HaloLists {
@@ -124,9 +145,19 @@ int download_records(xpbd_world *w, const uint32_t *host_slots, uint32_t n, doub
 // The world's bodies become: body s = the present body host_src[s] (>= 0) or incoming record -host_src[s] - 1 (39 doubles
 // each).  Only the incoming records cross the bus; otherwise as xpbd_world_upload_bodies (joints and neighbour lists dropped).
 int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const double *incoming39, uint32_t n_incoming);
-// The argument checks of xpbd_world_raycast(_device) against one world (topology present) / of the rays' reserved fields.
-int check_raycast(const char *who, const xpbd_world *w, const void *rays, uint32_t n_rays, uint32_t flags, const void *hits);
-int check_rays_reserved(const char *who, const xpbd_ray *rays, uint32_t n_rays);
+// The argument checks of the scene queries, shared by the single and the multi-GPU world (XPBD_E_INVALID with a message naming
+// `who`; the caller has dealt with a NULL world).  In order: NULL arrays, unknown flags, no polytopes (`setter`: the call that
+// sets them), with `host` the records' own fields (reserved, shape: the arrays are host memory) and, for an overlap, a target
+// without bodies.  A ray cast does not mind one: every ray misses.
+struct QueryTarget {
+    bool has_topology;
+    uint32_t n_bodies, n_shapes;
+    const char *setter;
+};
+int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host);
+// n_out: what a host variant reports its total through (NULL passes for a device variant, which has none).
+int check_overlap(const char *who, const QueryTarget &t, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
+                  const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host);
 // Ray casts of the world's bodies, stream-ordered (device arrays) / from and to host arrays (waits).  dev_global_id: device
 // array of w's body count, the index each body is known by (XPBD_NO_HIT: the body does not answer); NULL: its slot.
 // masked: only bodies whose collision-filter group meets `mask` answer (xpbd_world_raycast_masked); else every body does.
@@ -134,12 +165,6 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
                     bool masked, uint32_t mask);
 int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id,
                  bool masked, uint32_t mask);
-// The argument checks of xpbd_world_overlap(_device) against one world (polytopes set, bodies resident) / of the queries'
-// reserved and shape fields against a table of n_shapes shapes.
-int check_overlap(const char *who, const xpbd_world *w, const void *queries, uint32_t n_queries, uint32_t flags, const void *offsets,
-                  const void *hits, uint32_t cap);
-int check_overlap_queries(const char *who, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t n_shapes);
-uint32_t shape_count(const xpbd_world *w);
 // Overlap queries against the world's bodies (include/xpbd.h, "Overlap queries"), stream-ordered (device arrays; the total is
 // dev_offsets[n_queries]) / from and to host arrays (waits; *n_out = the total, XPBD_E_CAPACITY when it exceeds cap; a world
 // without bodies reports nothing).  dev_global_id as for the ray casts: what hit.body and ignore_body mean, ascending with the slot.

@@ -29,6 +29,7 @@
 // on the device), and either re-run after a re-plan (XPBD_MULTI_AUTO_REPLAN) or reported as XPBD_E_HALO with the state of
 // the frame's start in place.  A state with possibly missed contacts never reaches the caller.
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -50,6 +51,7 @@
 
 #include "../../include/xpbd.h"
 #include "xpbd_internal.h"
+#include "xpbd_merge.hpp"
 #include "xpbd_plan.hpp"
 #include "xpbd_rccl.h"
 
@@ -405,6 +407,58 @@ int all_gather_host(xpbd_multi_world *mw, const std::vector<const void *> &send,
         return set_error((int)peer_rc, "xpbd_multi_world: rank %u failed with error %d in this collective call (see its xpbd_last_error); "
                                        "every rank leaves the call with that error", peer, (int)peer_rc);
     return XPBD_OK;
+}
+
+// Variable-length lists of T from every rank: `local` holds every local shard's list; gather_counts (one collective for the
+// lengths of all the lists it is given) yields `counts` and `widest`, gather_rows (one collective) pads every local list to
+// `widest` and yields `rows`.  Both carry `st` as all_gather_host does: a failed shard takes part with whatever it holds.
+template <class T> struct RankLists {
+    std::vector<std::vector<T>> local;
+    std::vector<uint32_t> counts; // per rank
+    uint32_t widest = 1;          // the longest list, at least 1
+    std::vector<uint8_t> rows;    // n_ranks x widest x T
+    explicit RankLists(size_t n_local) : local(n_local) {}
+    T at(uint32_t rank, uint32_t i) const
+    {
+        T v;
+        std::memcpy(&v, rows.data() + ((size_t)rank * widest + i) * sizeof v, sizeof v);
+        return v;
+    }
+};
+
+template <class... T> int gather_counts(xpbd_multi_world *mw, LocalStatus &st, RankLists<T> &...lists)
+{
+    constexpr size_t N = sizeof...(T);
+    const size_t nl = mw->shards.size();
+    std::vector<std::array<uint32_t, N>> mine(nl);
+    std::vector<const void *> send(nl);
+    for (size_t k = 0; k < nl; ++k) {
+        mine[k] = {(uint32_t)lists.local[k].size()...};
+        send[k] = mine[k].data();
+    }
+    std::vector<uint8_t> gathered;
+    XPBD_TRY(all_gather_host(mw, send, N * sizeof(uint32_t), gathered, st));
+    size_t column = 0;
+    auto take = [&](std::vector<uint32_t> &counts, uint32_t &widest) {
+        counts.resize(mw->n_ranks);
+        for (uint32_t r = 0; r < mw->n_ranks; ++r) {
+            std::memcpy(&counts[r], gathered.data() + ((size_t)r * N + column) * sizeof(uint32_t), sizeof(uint32_t));
+            widest = std::max(widest, counts[r]);
+        }
+        ++column;
+    };
+    (take(lists.counts, lists.widest), ...);
+    return XPBD_OK;
+}
+
+template <class T> int gather_rows(xpbd_multi_world *mw, LocalStatus &st, RankLists<T> &list)
+{
+    std::vector<const void *> send;
+    for (std::vector<T> &l : list.local) {
+        l.resize(list.widest);
+        send.push_back(l.data());
+    }
+    return all_gather_host(mw, send, (size_t)list.widest * sizeof(T), list.rows, st);
 }
 
 template <class T>
@@ -1325,19 +1379,30 @@ int restore_frame(xpbd_multi_world *mw)
     return XPBD_OK;
 }
 
+// 1 for the slots of a shard's owned bodies, 0 for its ghosts.
+std::vector<uint8_t> owned_mask(const Shard &s)
+{
+    std::vector<uint8_t> owned(s.local_ids.size(), 1);
+    size_t g = 0;
+    for (size_t q = 0; q < s.local_ids.size(); ++q) { // local_ids and ghosts are both ascending
+        while (g < s.ghosts.size() && s.ghosts[g] < s.local_ids[q])
+            ++g;
+        if (g < s.ghosts.size() && s.ghosts[g] == s.local_ids[q])
+            owned[q] = 0;
+    }
+    return owned;
+}
+
 // The global id of every local slot of a shard for its scene queries: its OWNED bodies answer, under their global ids (ghosts
 // are listed as XPBD_NO_HIT).
 int upload_query_ids(Shard &s)
 {
     XPBD_TRY(bind(s));
+    const std::vector<uint8_t> owned = owned_mask(s);
     std::vector<uint32_t> ids(s.local_ids);
-    size_t g = 0;
-    for (uint32_t &id : ids) { // local_ids and ghosts are both ascending
-        while (g < s.ghosts.size() && s.ghosts[g] < id)
-            ++g;
-        if (g < s.ghosts.size() && s.ghosts[g] == id)
-            id = XPBD_NO_HIT;
-    }
+    for (size_t q = 0; q < ids.size(); ++q)
+        if (!owned[q])
+            ids[q] = XPBD_NO_HIT;
     XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
     return upload_vector(s.query_ids, ids, s.stream);
 }
@@ -1374,26 +1439,25 @@ int check_usable(const xpbd_multi_world *mw, const char *who)
     return XPBD_OK;
 }
 
+// What the scene queries' argument checks (xpbd::check_raycast, xpbd::check_overlap) need to know of the world.
+xpbd::QueryTarget query_target(const xpbd_multi_world *mw)
+{
+    return {mw->have_shapes, mw->planned ? mw->n_global : 0u, (uint32_t)mw->shape_radius.size(), "xpbd_multi_world_set_polytopes"};
+}
+
 // xpbd_multi_world_raycast(_masked), named `who` in its errors.
 int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, bool masked, uint32_t mask,
                   xpbd_ray_hit *hits)
 {
     XPBD_TRY(check_usable(mw, who));
-    if (n_rays && (!rays || !hits))
-        return set_error(XPBD_E_INVALID, "%s: NULL rays or hits", who);
-    if (flags & ~XPBD_RAYCAST_BRUTE_FORCE)
-        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
-    if (!mw->have_shapes)
-        return set_error(XPBD_E_INVALID, "%s: call xpbd_multi_world_set_polytopes first", who);
-    XPBD_TRY(xpbd::check_rays_reserved(who, rays, n_rays));
-    if (!mw->planned)
+    XPBD_TRY(xpbd::check_raycast(who, query_target(mw), rays, n_rays, flags, hits, true));
+    if (!mw->planned) // (a plan over no bodies will do: every ray misses)
         return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
     if (n_rays == 0)
         return XPBD_OK;
     // every local shard casts against its owned bodies; one all-gather of the hit records (with every rank's status) over
     // all ranks, then every rank merges the n_ranks rows by the (t, global index) rule of a single world
     LocalStatus st;
-    const size_t bytes = (size_t)n_rays * sizeof(xpbd_ray_hit);
     std::vector<std::vector<xpbd_ray_hit>> mine(mw->shards.size(), std::vector<xpbd_ray_hit>(n_rays));
     std::vector<const void *> send;
     for (size_t k = 0; k < mw->shards.size(); ++k) {
@@ -1402,112 +1466,46 @@ int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, u
         send.push_back(mine[k].data());
     }
     std::vector<uint8_t> all;
-    XPBD_TRY(all_gather_host(mw, send, bytes, all, st));
-    for (uint32_t r = 0; r < n_rays; ++r) {
-        xpbd_ray_hit best;
-        std::memcpy(&best, all.data() + (size_t)r * sizeof(xpbd_ray_hit), sizeof best);
-        for (uint32_t k = 1; k < mw->n_ranks; ++k) {
-            xpbd_ray_hit h;
-            std::memcpy(&h, all.data() + (size_t)k * bytes + (size_t)r * sizeof(xpbd_ray_hit), sizeof h);
-            if (h.distance < best.distance || (h.distance == best.distance && h.body < best.body))
-                best = h;
-        }
-        hits[r] = best;
-    }
+    XPBD_TRY(all_gather_host(mw, send, (size_t)n_rays * sizeof(xpbd_ray_hit), all, st));
+    xpbd::merge_ray_hits(all.data(), mw->n_ranks, n_rays, hits);
     return XPBD_OK;
 }
 
 // xpbd_multi_world_overlap: every local shard answers for its owned bodies; the counts, the offsets and the hits of every
-// rank are gathered (as capture_report gathers its lists, every rank's status in each collective) and merged per query --
-// the ranks' lists are disjoint and each is ascending.
+// rank are gathered and merged per query (xpbd::merge_overlap_lists).
 int multi_overlap(xpbd_multi_world *mw, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets,
                   xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out)
 {
     const char *who = "xpbd_multi_world_overlap";
     XPBD_TRY(check_usable(mw, who));
-    if (n_queries && (!queries || !offsets || !n_out))
-        return set_error(XPBD_E_INVALID, "%s: NULL queries, offsets or n_out", who);
-    if (cap && !hits)
-        return set_error(XPBD_E_INVALID, "%s: NULL hits with cap = %u", who, cap);
-    if (flags & ~(XPBD_OVERLAP_BRUTE_FORCE | XPBD_OVERLAP_MASKED))
-        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
-    if (!mw->have_shapes)
-        return set_error(XPBD_E_INVALID, "%s: call xpbd_multi_world_set_polytopes first", who);
-    XPBD_TRY(xpbd::check_overlap_queries(who, queries, n_queries, (uint32_t)mw->shape_radius.size()));
-    if (!mw->planned || mw->n_global == 0)
-        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    XPBD_TRY(xpbd::check_overlap(who, query_target(mw), queries, n_queries, flags, offsets, hits, cap, n_out, true));
     if (n_queries == 0) {
         if (n_out)
             *n_out = 0;
         return XPBD_OK;
     }
     const size_t nl = mw->shards.size();
-    const uint32_t w = mw->n_ranks;
     LocalStatus st;
     std::vector<std::vector<uint32_t>> my_offsets(nl, std::vector<uint32_t>((size_t)n_queries + 1, 0));
-    std::vector<std::vector<xpbd_overlap_hit>> my_hits(nl);
+    RankLists<xpbd_overlap_hit> lists(nl);
     for (size_t k = 0; k < nl; ++k)
         if (st.ok())
-            st.keep(shard_overlap(mw->shards[k], queries, n_queries, flags, my_offsets[k], my_hits[k]));
-    std::vector<uint32_t> my_total(nl);
+            st.keep(shard_overlap(mw->shards[k], queries, n_queries, flags, my_offsets[k], lists.local[k]));
+    XPBD_TRY(gather_counts(mw, st, lists));
     std::vector<const void *> send(nl);
-    for (size_t k = 0; k < nl; ++k) {
-        my_total[k] = (uint32_t)my_hits[k].size();
-        send[k] = &my_total[k];
-    }
-    std::vector<uint8_t> gathered, all_offsets, all_hits;
-    XPBD_TRY(all_gather_host(mw, send, sizeof(uint32_t), gathered, st));
-    std::vector<uint32_t> totals(w);
-    std::memcpy(totals.data(), gathered.data(), (size_t)w * sizeof(uint32_t));
-    uint32_t widest = 1;
-    uint64_t total = 0;
-    for (uint32_t t : totals) {
-        widest = std::max(widest, t);
-        total += t;
-    }
-    const size_t row = ((size_t)n_queries + 1) * sizeof(uint32_t);
     for (size_t k = 0; k < nl; ++k)
         send[k] = my_offsets[k].data();
-    XPBD_TRY(all_gather_host(mw, send, row, all_offsets, st));
-    for (size_t k = 0; k < nl; ++k) {
-        my_hits[k].resize(widest);
-        send[k] = my_hits[k].data();
-    }
-    XPBD_TRY(all_gather_host(mw, send, (size_t)widest * sizeof(xpbd_overlap_hit), all_hits, st));
+    std::vector<uint8_t> all_offsets;
+    XPBD_TRY(all_gather_host(mw, send, ((size_t)n_queries + 1) * sizeof(uint32_t), all_offsets, st));
+    XPBD_TRY(gather_rows(mw, st, lists));
+    uint64_t total = 0;
+    for (uint32_t t : lists.counts)
+        total += t;
     if (total > 0xFFFFFFFFull)
         return set_error(XPBD_E_INVALID, "%s: %llu hits do not fit the 32-bit offsets", who, (unsigned long long)total);
-    auto offset_of = [&](uint32_t r, uint32_t q) {
-        uint32_t v;
-        std::memcpy(&v, all_offsets.data() + (size_t)r * row + (size_t)q * sizeof v, sizeof v);
-        return v;
-    };
-    std::vector<xpbd_overlap_hit> segment;
-    uint32_t at = 0;
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        offsets[q] = at;
-        segment.clear();
-        uint32_t parts = 0;
-        for (uint32_t r = 0; r < w; ++r) {
-            const uint32_t b0 = offset_of(r, q), b1 = offset_of(r, q + 1);
-            if (b1 == b0)
-                continue;
-            ++parts;
-            const size_t old = segment.size();
-            segment.resize(old + (b1 - b0));
-            std::memcpy(segment.data() + old, all_hits.data() + ((size_t)r * widest + b0) * sizeof(xpbd_overlap_hit), (size_t)(b1 - b0) * sizeof(xpbd_overlap_hit));
-        }
-        if (parts > 1)
-            std::sort(segment.begin(), segment.end(), [](const xpbd_overlap_hit &a, const xpbd_overlap_hit &b) { return a.body < b.body; });
-        for (const xpbd_overlap_hit &h : segment) {
-            if (at < cap)
-                hits[at] = h;
-            ++at;
-        }
-    }
-    offsets[n_queries] = at;
-    *n_out = at;
-    if (at > cap)
-        return set_error(XPBD_E_CAPACITY, "%s: %u hits but room for %u", who, at, cap);
+    *n_out = xpbd::merge_overlap_lists(all_offsets.data(), lists.rows.data(), lists.widest, mw->n_ranks, n_queries, offsets, hits, cap);
+    if (*n_out > cap)
+        return set_error(XPBD_E_CAPACITY, "%s: %u hits but room for %u", who, *n_out, cap);
     return XPBD_OK;
 }
 
@@ -1530,14 +1528,7 @@ int shard_report(Shard &s, std::vector<xpbd_pair_contact> &pairs, std::vector<xp
     if (xpbd_world_body_count(s.world) != s.local_ids.size())
         return set_error(XPBD_E_INVALID, "contact report: shard %u holds %u bodies, its plan %zu", s.rank, xpbd_world_body_count(s.world),
                          s.local_ids.size());
-    std::vector<uint8_t> owned(s.local_ids.size(), 1);
-    size_t g = 0;
-    for (size_t q = 0; q < s.local_ids.size(); ++q) { // local_ids and ghosts are both ascending
-        while (g < s.ghosts.size() && s.ghosts[g] < s.local_ids[q])
-            ++g;
-        if (g < s.ghosts.size() && s.ghosts[g] == s.local_ids[q])
-            owned[q] = 0;
-    }
+    const std::vector<uint8_t> owned = owned_mask(s);
     XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
     XPBD_TRY(upload_vector(s.report_ids, s.local_ids, s.stream));
     XPBD_TRY(upload_vector(s.report_owned, owned, s.stream));
@@ -1551,50 +1542,23 @@ int capture_report(xpbd_multi_world *mw)
 {
     const size_t nl = mw->shards.size();
     LocalStatus st;
-    std::vector<std::vector<xpbd_pair_contact>> pairs(nl);
-    std::vector<std::vector<xpbd_contact_point>> points(nl);
+    RankLists<xpbd_pair_contact> pairs(nl);
+    RankLists<xpbd_contact_point> points(nl);
     for (size_t k = 0; k < nl; ++k)
         if (st.ok())
-            st.keep(shard_report(mw->shards[k], pairs[k], points[k]));
-    struct Counts {
-        uint32_t pairs, points;
-    };
-    std::vector<Counts> mine(nl);
-    std::vector<const void *> send(nl);
-    for (size_t k = 0; k < nl; ++k) {
-        mine[k] = Counts{(uint32_t)pairs[k].size(), (uint32_t)points[k].size()};
-        send[k] = &mine[k];
-    }
-    std::vector<uint8_t> gathered;
-    XPBD_TRY(all_gather_host(mw, send, sizeof(Counts), gathered, st));
-    const uint32_t w = mw->n_ranks;
-    std::vector<Counts> counts(w);
-    std::memcpy(counts.data(), gathered.data(), (size_t)w * sizeof(Counts));
-    uint32_t cap = 1, cap_points = 1;
-    for (const Counts &c : counts) {
-        cap = std::max(cap, c.pairs);
-        cap_points = std::max(cap_points, c.points);
-    }
-    for (size_t k = 0; k < nl; ++k) {
-        pairs[k].resize(cap);
-        points[k].resize(cap_points);
-        send[k] = pairs[k].data();
-    }
-    std::vector<uint8_t> all_pairs, all_points;
-    XPBD_TRY(all_gather_host(mw, send, (size_t)cap * sizeof(xpbd_pair_contact), all_pairs, st));
-    for (size_t k = 0; k < nl; ++k)
-        send[k] = points[k].data();
-    XPBD_TRY(all_gather_host(mw, send, (size_t)cap_points * sizeof(xpbd_contact_point), all_points, st));
+            st.keep(shard_report(mw->shards[k], pairs.local[k], points.local[k]));
+    XPBD_TRY(gather_counts(mw, st, pairs, points));
+    XPBD_TRY(gather_rows(mw, st, pairs));
+    XPBD_TRY(gather_rows(mw, st, points));
     // merge: (key, rank, row) in key order
     struct Item {
         uint64_t key;
         uint32_t rank, row;
     };
     std::vector<Item> items;
-    for (uint32_t r = 0; r < w; ++r)
-        for (uint32_t i = 0; i < counts[r].pairs; ++i) {
-            xpbd_pair_contact c;
-            std::memcpy(&c, all_pairs.data() + ((size_t)r * cap + i) * sizeof c, sizeof c);
+    for (uint32_t r = 0; r < mw->n_ranks; ++r)
+        for (uint32_t i = 0; i < pairs.counts[r]; ++i) {
+            const xpbd_pair_contact c = pairs.at(r, i);
             items.push_back(Item{(uint64_t)c.body_a << 32 | c.body_b, r, i});
         }
     std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.key < b.key; });
@@ -1602,15 +1566,11 @@ int capture_report(xpbd_multi_world *mw)
     std::vector<xpbd_contact_point> merged_points;
     std::vector<uint64_t> keys(items.size());
     for (size_t i = 0; i < items.size(); ++i) {
-        xpbd_pair_contact c;
-        std::memcpy(&c, all_pairs.data() + ((size_t)items[i].rank * cap + items[i].row) * sizeof c, sizeof c);
+        xpbd_pair_contact c = pairs.at(items[i].rank, items[i].row);
         const uint32_t from = c.first_point;
         c.first_point = (uint32_t)merged_points.size();
-        for (uint32_t q = 0; q < c.n_points; ++q) {
-            xpbd_contact_point p;
-            std::memcpy(&p, all_points.data() + ((size_t)items[i].rank * cap_points + from + q) * sizeof p, sizeof p);
-            merged_points.push_back(p);
-        }
+        for (uint32_t q = 0; q < c.n_points; ++q)
+            merged_points.push_back(points.at(items[i].rank, from + q));
         merged[i] = c;
         keys[i] = items[i].key;
     }

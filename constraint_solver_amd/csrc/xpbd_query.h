@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <hip/hip_runtime_api.h>
 
+#include "xpbd_internal.h"
 #include "xpbd_kernels.h"
 #include "xpbd_pairs.h"
 
@@ -22,7 +23,7 @@ namespace xpbd {
 // radius (radius < 0: the body is never hit -- its pose is not finite, or it is a ghost of a multi-GPU shard).
 constexpr uint32_t kQueryRecDoubles = 12;
 
-// Device scratch of one call (the owner sizes it with query_scratch_bytes and keeps it).
+// Device scratch of one call (a view of SceneQueryScratch, which owns it).
 struct QueryScratch {
     double *rec;          // [n][kQueryRecDoubles]
     double *partials;     // [blocks_for(n)][7]
@@ -31,16 +32,29 @@ struct QueryScratch {
     uint32_t *cell_fill;  // [table_size]
     uint32_t *items;      // [8 n]: body slots, grouped by cell
     uint32_t *scan_scratch;
-    void *brute;          // per (ray, workgroup of bodies) partial winners of the brute-force path
+    void *brute;          // per (ray, workgroup of bodies) partial winners of the brute-force ray cast
+    double *qrec;         // per overlap query: sphere centre, radius
     uint32_t table_size;  // power of two
 };
 
 struct QuerySizes {
-    size_t rec, partials, grid, cell_start, cell_fill, items, scan_scratch, brute;
+    size_t rec, partials, grid, cell_start, cell_fill, items, scan_scratch, brute, qrec;
     uint32_t table_size;
 };
-// What a call over n bodies and n_rays rays needs (brute: whether it takes the brute-force path).
+// What a ray cast over n bodies and n_rays rays needs (brute: whether it takes the brute-force path).
 QuerySizes query_scratch_bytes(uint32_t n, uint32_t n_rays, bool brute);
+
+// The scene queries' device memory of one world: the scratch of a call, shared by the ray casts and the overlap queries, and
+// the staging of the host variants' arrays (rays or queries in, hits out, an overlap's offsets).  One call uses it at a time:
+// the calls of a world are ordered on its stream, and every host variant ends with a wait.
+struct SceneQueryScratch {
+    DeviceBuffer rec, partials, grid, cell_start, cell_fill, items, scan, brute, qrec;
+    DeviceBuffer in, out, offsets;
+
+    // Room for a call's scratch and staging (sizes of 0: not needed); waits for `stream` only if something has to grow.
+    hipError_t reserve(const QuerySizes &q, size_t in_bytes, size_t out_bytes, size_t offsets_bytes, hipStream_t stream) noexcept;
+    QueryScratch view(uint32_t table_size) const;
+};
 
 // The collision-filter test of a masked ray cast: with `masked`, body i answers only if (group_i & mask) != 0, group_i =
 // filter[i].x (filter == NULL: every body is in group ~0u).  Without it no group is tested.
@@ -66,18 +80,15 @@ hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const ui
 // cells (no grid, no sort); a segment that the caller's `cap` cuts short is listed that way on the grid path too.
 constexpr uint32_t kOverlapSortStage = 1024; // hits of one query sorted in LDS; longer segments are sorted in global memory
 
-struct OverlapSizes {
-    QuerySizes q;  // the scratch shared with the ray casts (scan_scratch also covers the scan of the offsets)
-    size_t qrec;   // per query: sphere centre, radius
-};
-OverlapSizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute);
+// The scratch shared with the ray casts (scan_scratch also covers the scan of the offsets; no brute-force partials) and qrec.
+QuerySizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute);
 
 // n_queries device xpbd_overlap_query against the bodies of `b`: offsets[n_queries + 1] (device) receives the CSR offsets of
 // the full answer, hits[0 .. min(total, cap)) (device xpbd_overlap_hit; may be null with cap == 0) its first entries.
 // global_id as for launch_raycast; filter: the bodies' collision filters (null: every body in group ~0u), tested against the
 // queries' masks when `masked`.
 hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *queries,
-                          uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, double *qrec, uint32_t *offsets, void *hits,
-                          uint32_t cap, hipStream_t stream);
+                          uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, uint32_t *offsets, void *hits, uint32_t cap,
+                          hipStream_t stream);
 
 } // namespace xpbd

@@ -906,25 +906,32 @@ QuerySizes query_scratch_bytes(uint32_t n, uint32_t n_rays, bool brute)
     return q;
 }
 
-hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const RayFilter &filter, const void *rays_v, uint32_t n_rays,
-                          bool brute, const QueryScratch &s, void *hits_v, hipStream_t stream)
+hipError_t SceneQueryScratch::reserve(const QuerySizes &q, size_t in_bytes, size_t out_bytes, size_t offsets_bytes, hipStream_t stream) noexcept
 {
-    if (n_rays == 0)
-        return hipSuccess;
-    const xpbd_ray *rays = static_cast<const xpbd_ray *>(rays_v);
-    xpbd_ray_hit *hits = static_cast<xpbd_ray_hit *>(hits_v);
-    QueryGrid *grid = static_cast<QueryGrid *>(s.grid);
+    return reserve_after_sync(stream, {{rec, q.rec}, {partials, q.partials}, {grid, q.grid}, {cell_start, q.cell_start}, {cell_fill, q.cell_fill},
+                                       {items, q.items}, {scan, q.scan_scratch}, {brute, q.brute}, {qrec, q.qrec}, {in, in_bytes},
+                                       {out, out_bytes}, {offsets, offsets_bytes}});
+}
+
+QueryScratch SceneQueryScratch::view(uint32_t table_size) const
+{
+    return QueryScratch{rec.as<double>(),    partials.as<double>(), grid.ptr,  cell_start.as<uint32_t>(), cell_fill.as<uint32_t>(),
+                        items.as<uint32_t>(), scan.as<uint32_t>(),   brute.ptr, qrec.as<double>(),         table_size};
+}
+
+namespace {
+// The first pass of every call: the bodies' records and the partial bounds of their spheres.
+void launch_query_bodies(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const RayFilter &filter, const QueryScratch &s,
+                         hipStream_t stream)
+{
     if (b.n)
         hipLaunchKernelGGL(k_query_bodies, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b, t, global_id, filter, s.rec, s.partials);
-    if (brute || b.n == 0) {
-        const uint32_t tiles = (n_rays + kBruteRays - 1) / kBruteRays, chunks = brute_chunks(b.n, n_rays);
-        const uint32_t chunk_len = (b.n + chunks - 1) / chunks;
-        Best *partial = static_cast<Best *>(s.brute);
-        hipLaunchKernelGGL(k_query_brute, dim3(tiles, chunks), dim3(kBlock), 0, stream, rays, n_rays, b.n, chunk_len, s.rec, b.shape_id,
-                           global_id, t, partial);
-        hipLaunchKernelGGL(k_query_brute_finish, dim3(n_rays), dim3(64), 0, stream, rays, chunks, partial, s.rec, b.shape_id, t, hits);
-        return hipGetLastError();
-    }
+}
+
+// The grid over the bodies' spheres: its dimensions, the cells' populations, their scan, the bodies grouped by cell.
+hipError_t launch_query_grid(const BodyArrays &b, const QueryScratch &s, hipStream_t stream)
+{
+    QueryGrid *grid = static_cast<QueryGrid *>(s.grid);
     hipError_t e = hipMemsetAsync(s.cell_start, 0, (size_t)(s.table_size + 1) * 4, stream);
     if (e == hipSuccess)
         e = hipMemsetAsync(s.cell_fill, 0, (size_t)s.table_size * 4, stream);
@@ -937,52 +944,59 @@ hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const ui
         return e;
     hipLaunchKernelGGL(k_query_bin<true>, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b.n, s.rec, grid, s.cell_start, s.cell_fill,
                        s.items);
+    return hipSuccess;
+}
+} // namespace
+
+hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const RayFilter &filter, const void *rays_v, uint32_t n_rays,
+                          bool brute, const QueryScratch &s, void *hits_v, hipStream_t stream)
+{
+    if (n_rays == 0)
+        return hipSuccess;
+    const xpbd_ray *rays = static_cast<const xpbd_ray *>(rays_v);
+    xpbd_ray_hit *hits = static_cast<xpbd_ray_hit *>(hits_v);
+    launch_query_bodies(b, t, global_id, filter, s, stream);
+    if (brute || b.n == 0) {
+        const uint32_t tiles = (n_rays + kBruteRays - 1) / kBruteRays, chunks = brute_chunks(b.n, n_rays);
+        const uint32_t chunk_len = (b.n + chunks - 1) / chunks;
+        Best *partial = static_cast<Best *>(s.brute);
+        hipLaunchKernelGGL(k_query_brute, dim3(tiles, chunks), dim3(kBlock), 0, stream, rays, n_rays, b.n, chunk_len, s.rec, b.shape_id,
+                           global_id, t, partial);
+        hipLaunchKernelGGL(k_query_brute_finish, dim3(n_rays), dim3(64), 0, stream, rays, chunks, partial, s.rec, b.shape_id, t, hits);
+        return hipGetLastError();
+    }
+    if (hipError_t e = launch_query_grid(b, s, stream))
+        return e;
     hipLaunchKernelGGL(k_query_walk, dim3(blocks_of(n_rays)), dim3(kBlock), 0, stream, rays, n_rays, b.n, s.rec, b.shape_id, global_id, t,
-                       grid, s.cell_start, s.items, hits);
+                       static_cast<QueryGrid *>(s.grid), s.cell_start, s.items, hits);
     return hipGetLastError();
 }
 
-OverlapSizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute)
+QuerySizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute)
 {
-    OverlapSizes o{};
-    o.q = query_scratch_bytes(n, 0, brute || n == 0);
-    o.q.brute = 8;
+    QuerySizes q = query_scratch_bytes(n, 0, brute || n == 0);
+    q.brute = 0;
     const size_t scan = ((size_t)n_queries / 1024 + 8) * 4;
-    o.q.scan_scratch = o.q.scan_scratch > scan ? o.q.scan_scratch : scan;
-    o.qrec = (size_t)(n_queries ? n_queries : 1) * kOverlapRecDoubles * 8;
-    return o;
+    q.scan_scratch = q.scan_scratch > scan ? q.scan_scratch : scan;
+    q.qrec = (size_t)(n_queries ? n_queries : 1) * kOverlapRecDoubles * 8;
+    return q;
 }
 
 hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *queries_v,
-                          uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, double *qrec, uint32_t *offsets, void *hits_v,
-                          uint32_t cap, hipStream_t stream)
+                          uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, uint32_t *offsets, void *hits_v, uint32_t cap,
+                          hipStream_t stream)
 {
     if (n_queries == 0)
         return hipMemsetAsync(offsets, 0, sizeof(uint32_t), stream);
     brute = brute || b.n == 0;
-    QueryGrid *grid = static_cast<QueryGrid *>(s.grid);
     hipError_t e = hipSuccess;
-    if (b.n)
-        hipLaunchKernelGGL(k_query_bodies, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b, t, global_id, RayFilter{nullptr, 0u, 0u}, s.rec,
-                           s.partials);
+    launch_query_bodies(b, t, global_id, RayFilter{nullptr, 0u, 0u}, s, stream);
     hipLaunchKernelGGL(k_overlap_queries, dim3(blocks_of(n_queries)), dim3(kBlock), 0, stream, static_cast<const xpbd_overlap_query *>(queries_v),
-                       n_queries, t, qrec);
-    if (!brute) { // the grid of a ray cast, by the same passes
-        e = hipMemsetAsync(s.cell_start, 0, (size_t)(s.table_size + 1) * 4, stream);
-        if (e == hipSuccess)
-            e = hipMemsetAsync(s.cell_fill, 0, (size_t)s.table_size * 4, stream);
-        if (e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(k_query_grid, dim3(1), dim3(kBlock), 0, stream, s.partials, blocks_of(b.n), s.table_size, grid);
-        hipLaunchKernelGGL(k_query_bin<false>, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b.n, s.rec, grid, s.cell_start, s.cell_fill,
-                           s.items);
-        if ((e = launch_exclusive_scan(s.cell_start, s.table_size, s.scan_scratch, stream)) != hipSuccess)
-            return e;
-        hipLaunchKernelGGL(k_query_bin<true>, dim3(blocks_of(b.n)), dim3(kBlock), 0, stream, b.n, s.rec, grid, s.cell_start, s.cell_fill,
-                           s.items);
-    }
-    const OverlapArgs a{static_cast<const xpbd_overlap_query *>(queries_v), qrec, s.rec, global_id, filter, grid, s.cell_start, s.items, offsets,
-                        static_cast<xpbd_overlap_hit *>(hits_v), n_queries, cap, masked ? 1u : 0u, brute ? 1u : 0u};
+                       n_queries, t, s.qrec);
+    if (!brute && (e = launch_query_grid(b, s, stream)) != hipSuccess) // the grid of a ray cast, by the same passes
+        return e;
+    const OverlapArgs a{static_cast<const xpbd_overlap_query *>(queries_v), s.qrec, s.rec, global_id, filter, static_cast<QueryGrid *>(s.grid),
+                        s.cell_start, s.items, offsets, static_cast<xpbd_overlap_hit *>(hits_v), n_queries, cap, masked ? 1u : 0u, brute ? 1u : 0u};
     // lanes per query and vertex capacity by the largest shape, as the SAT launchers of the contact pipeline choose theirs
     auto pass = [&](auto fill) {
         constexpr bool FILL = decltype(fill)::value;

@@ -138,10 +138,8 @@ struct xpbd_world {
         void clear() { *this = Restitution{}; }
     } restitution;
     DeviceBuffer rs_restitution, rs_start;
-    // scene queries (xpbd_world_raycast*): scratch of one call, and the staging of the host variant's rays and hits
-    DeviceBuffer q_rec, q_partials, q_grid, q_cell_start, q_cell_fill, q_items, q_scan, q_brute, q_rays, q_hits;
-    // ... (xpbd_world_overlap*): the queries' spheres, and the staging of the host variant's queries, offsets and hits
-    DeviceBuffer q_ovl_rec, q_ovl_queries, q_ovl_offsets, q_ovl_hits;
+    // scene queries (xpbd_world_raycast*, xpbd_world_overlap*): scratch of one call, staging of the host variants' arrays
+    xpbd::SceneQueryScratch query;
     // body edits (xpbd_world_set_external_wrench, _apply_impulses, _set_dynamics, _get_dynamics): the staging of the host
     // variants' indices, values (force + torque, or rows of 13 doubles) and impulse lists
     DeviceBuffer ed_indices, ed_values, ed_list;
@@ -1044,22 +1042,15 @@ int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32
     return XPBD_OK;
 }
 
-int check_raycast(const char *who, const xpbd_world *w, const void *rays, uint32_t n_rays, uint32_t flags, const void *hits)
+int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host)
 {
-    if (!w)
-        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
     if (n_rays && (!rays || !hits))
         return set_error(XPBD_E_INVALID, "%s: NULL rays or hits", who);
     if (flags & ~XPBD_RAYCAST_BRUTE_FORCE)
         return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
-    if (!w->has_topology)
-        return set_error(XPBD_E_INVALID, "%s: call xpbd_world_set_polytopes first (set_shapes gives vertices only)", who);
-    return XPBD_OK;
-}
-
-int check_rays_reserved(const char *who, const xpbd_ray *rays, uint32_t n_rays)
-{
-    for (uint32_t r = 0; r < n_rays; ++r)
+    if (!t.has_topology)
+        return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
+    for (uint32_t r = 0; host && r < n_rays; ++r)
         if (rays[r].reserved)
             return set_error(XPBD_E_INVALID, "%s: ray %u has reserved = %u (must be 0)", who, r, rays[r].reserved);
     return XPBD_OK;
@@ -1076,21 +1067,10 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
     // (a world without bodies takes the brute-force path too: every ray misses, no grid to build)
     const bool brute = (flags & XPBD_RAYCAST_BRUTE_FORCE) || n_rays <= XPBD_RAYCAST_BRUTE_FORCE_RAYS || w->n == 0;
     const QuerySizes q = query_scratch_bytes(w->n, n_rays, brute);
-    const std::pair<DeviceBuffer *, size_t> need[] = {{&w->q_rec, q.rec}, {&w->q_partials, q.partials}, {&w->q_grid, q.grid},
-                                                      {&w->q_cell_start, q.cell_start}, {&w->q_cell_fill, q.cell_fill},
-                                                      {&w->q_items, q.items}, {&w->q_scan, q.scan_scratch}, {&w->q_brute, q.brute}};
-    bool grow = false;
-    for (const auto &b : need)
-        grow = grow || b.first->bytes < b.second;
-    if (grow) { // reserve() frees the block it replaces, which queued work may still use
-        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-        for (const auto &b : need)
-            XPBD_HIP_TRY(b.first->reserve(b.second));
-    }
-    const QueryScratch s{w->q_rec.as<double>(), w->q_partials.as<double>(), w->q_grid.ptr, w->q_cell_start.as<uint32_t>(),
-                         w->q_cell_fill.as<uint32_t>(), w->q_items.as<uint32_t>(), w->q_scan.as<uint32_t>(), w->q_brute.ptr, q.table_size};
+    XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
     const RayFilter filter{masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr, mask, masked ? 1u : 0u};
-    XPBD_HIP_TRY(launch_raycast(w->arrays(), w->tables(), dev_global_id, filter, dev_rays, n_rays, brute, s, dev_hits, w->stream));
+    XPBD_HIP_TRY(launch_raycast(w->arrays(), w->tables(), dev_global_id, filter, dev_rays, n_rays, brute, w->query.view(q.table_size), dev_hits,
+                                w->stream));
     return XPBD_OK;
 }
 
@@ -1101,50 +1081,38 @@ int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t 
         return XPBD_OK;
     if (int rc = bind_device(w))
         return rc;
+    SceneQueryScratch &s = w->query;
     const size_t bytes = (size_t)n_rays * sizeof(xpbd_ray);
-    if (w->q_rays.bytes < bytes || w->q_hits.bytes < bytes) {
-        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-        XPBD_HIP_TRY(w->q_rays.reserve(bytes));
-        XPBD_HIP_TRY(w->q_hits.reserve(bytes));
-    }
-    XPBD_HIP_TRY(hipMemcpyAsync(w->q_rays.ptr, rays, bytes, hipMemcpyHostToDevice, w->stream));
-    if (int rc = raycast_enqueue(w, w->q_rays.as<xpbd_ray>(), n_rays, flags, w->q_hits.as<xpbd_ray_hit>(), dev_global_id, masked, mask))
+    XPBD_HIP_TRY(s.reserve(QuerySizes{}, bytes, bytes, 0, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(s.in.ptr, rays, bytes, hipMemcpyHostToDevice, w->stream));
+    if (int rc = raycast_enqueue(w, s.in.as<xpbd_ray>(), n_rays, flags, s.out.as<xpbd_ray_hit>(), dev_global_id, masked, mask))
         return rc;
-    XPBD_HIP_TRY(hipMemcpyAsync(hits, w->q_hits.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(hits, s.out.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
 }
 
-int check_overlap(const char *who, const xpbd_world *w, const void *queries, uint32_t n_queries, uint32_t flags, const void *offsets,
-                  const void *hits, uint32_t cap)
+int check_overlap(const char *who, const QueryTarget &t, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
+                  const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host)
 {
-    if (!w)
-        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
-    if (n_queries && (!queries || !offsets))
-        return set_error(XPBD_E_INVALID, "%s: NULL queries or offsets", who);
+    if (n_queries && (!queries || !offsets || (host && !n_out)))
+        return set_error(XPBD_E_INVALID, "%s: NULL queries, offsets or n_out", who);
     if (cap && !hits)
         return set_error(XPBD_E_INVALID, "%s: NULL hits with cap = %u", who, cap);
     if (flags & ~(XPBD_OVERLAP_BRUTE_FORCE | XPBD_OVERLAP_MASKED))
         return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
-    if (!w->has_topology)
-        return set_error(XPBD_E_INVALID, "%s: call xpbd_world_set_polytopes first (set_shapes gives vertices only)", who);
-    if (w->n == 0)
+    if (!t.has_topology)
+        return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
+    for (uint32_t q = 0; host && q < n_queries; ++q) {
+        if (queries[q].reserved)
+            return set_error(XPBD_E_INVALID, "%s: query %u has reserved = %u (must be 0)", who, q, queries[q].reserved);
+        if (queries[q].shape >= t.n_shapes)
+            return set_error(XPBD_E_INVALID, "%s: query %u has shape = %u but the table holds %u shapes", who, q, queries[q].shape, t.n_shapes);
+    }
+    if (t.n_bodies == 0)
         return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
     return XPBD_OK;
 }
-
-int check_overlap_queries(const char *who, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t n_shapes)
-{
-    for (uint32_t q = 0; q < n_queries; ++q) {
-        if (queries[q].reserved)
-            return set_error(XPBD_E_INVALID, "%s: query %u has reserved = %u (must be 0)", who, q, queries[q].reserved);
-        if (queries[q].shape >= n_shapes)
-            return set_error(XPBD_E_INVALID, "%s: query %u has shape = %u but the table holds %u shapes", who, q, queries[q].shape, n_shapes);
-    }
-    return XPBD_OK;
-}
-
-uint32_t shape_count(const xpbd_world *w) { return w->n_shapes; }
 
 int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32_t n_queries, uint32_t flags, uint32_t *dev_offsets,
                     xpbd_overlap_hit *dev_hits, uint32_t cap, const uint32_t *dev_global_id)
@@ -1158,23 +1126,11 @@ int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32
         return XPBD_OK;
     }
     const bool brute = (flags & XPBD_OVERLAP_BRUTE_FORCE) || w->n == 0;
-    const OverlapSizes o = overlap_scratch_bytes(w->n, n_queries, brute);
-    const std::pair<DeviceBuffer *, size_t> need[] = {{&w->q_rec, o.q.rec}, {&w->q_partials, o.q.partials}, {&w->q_grid, o.q.grid},
-                                                      {&w->q_cell_start, o.q.cell_start}, {&w->q_cell_fill, o.q.cell_fill},
-                                                      {&w->q_items, o.q.items}, {&w->q_scan, o.q.scan_scratch}, {&w->q_ovl_rec, o.qrec}};
-    bool grow = false;
-    for (const auto &b : need)
-        grow = grow || b.first->bytes < b.second;
-    if (grow) { // reserve() frees the block it replaces, which queued work may still use
-        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-        for (const auto &b : need)
-            XPBD_HIP_TRY(b.first->reserve(b.second));
-    }
-    const QueryScratch s{w->q_rec.as<double>(), w->q_partials.as<double>(), w->q_grid.ptr, w->q_cell_start.as<uint32_t>(),
-                         w->q_cell_fill.as<uint32_t>(), w->q_items.as<uint32_t>(), w->q_scan.as<uint32_t>(), nullptr, o.q.table_size};
+    const QuerySizes q = overlap_scratch_bytes(w->n, n_queries, brute);
+    XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
     const bool masked = (flags & XPBD_OVERLAP_MASKED) != 0;
     XPBD_HIP_TRY(launch_overlap(w->arrays(), w->tables(), dev_global_id, masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr, dev_queries,
-                                n_queries, masked, brute, s, w->q_ovl_rec.as<double>(), dev_offsets, dev_hits, cap, w->stream));
+                                n_queries, masked, brute, w->query.view(q.table_size), dev_offsets, dev_hits, cap, w->stream));
     return XPBD_OK;
 }
 
@@ -1186,23 +1142,18 @@ int overlap_host(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_qu
         return XPBD_OK;
     if (int rc = bind_device(w))
         return rc;
+    SceneQueryScratch &s = w->query;
     const size_t q_bytes = (size_t)n_queries * sizeof(xpbd_overlap_query), o_bytes = ((size_t)n_queries + 1) * sizeof(uint32_t);
-    const size_t h_bytes = (size_t)(cap ? cap : 1) * sizeof(xpbd_overlap_hit);
-    if (w->q_ovl_queries.bytes < q_bytes || w->q_ovl_offsets.bytes < o_bytes || w->q_ovl_hits.bytes < h_bytes) {
-        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-        XPBD_HIP_TRY(w->q_ovl_queries.reserve(q_bytes));
-        XPBD_HIP_TRY(w->q_ovl_offsets.reserve(o_bytes));
-        XPBD_HIP_TRY(w->q_ovl_hits.reserve(h_bytes));
-    }
-    XPBD_HIP_TRY(hipMemcpyAsync(w->q_ovl_queries.ptr, queries, q_bytes, hipMemcpyHostToDevice, w->stream));
-    if (int rc = overlap_enqueue(w, w->q_ovl_queries.as<xpbd_overlap_query>(), n_queries, flags, w->q_ovl_offsets.as<uint32_t>(),
-                                 cap ? w->q_ovl_hits.as<xpbd_overlap_hit>() : nullptr, cap, dev_global_id))
+    XPBD_HIP_TRY(s.reserve(QuerySizes{}, q_bytes, (size_t)(cap ? cap : 1) * sizeof(xpbd_overlap_hit), o_bytes, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(s.in.ptr, queries, q_bytes, hipMemcpyHostToDevice, w->stream));
+    if (int rc = overlap_enqueue(w, s.in.as<xpbd_overlap_query>(), n_queries, flags, s.offsets.as<uint32_t>(),
+                                 cap ? s.out.as<xpbd_overlap_hit>() : nullptr, cap, dev_global_id))
         return rc;
-    XPBD_HIP_TRY(hipMemcpyAsync(offsets, w->q_ovl_offsets.ptr, o_bytes, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(offsets, s.offsets.ptr, o_bytes, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     const uint32_t total = offsets[n_queries], held = total < cap ? total : cap;
     if (held) {
-        XPBD_HIP_TRY(hipMemcpyAsync(hits, w->q_ovl_hits.ptr, (size_t)held * sizeof(xpbd_overlap_hit), hipMemcpyDeviceToHost, w->stream));
+        XPBD_HIP_TRY(hipMemcpyAsync(hits, s.out.ptr, (size_t)held * sizeof(xpbd_overlap_hit), hipMemcpyDeviceToHost, w->stream));
         XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     }
     *n_out = total;
@@ -2248,12 +2199,7 @@ namespace {
 // Room in the staging buffers of the host variants (growing one frees the old block, which queued work may still use).
 int reserve_edit_staging(xpbd_world *w, size_t index_bytes, size_t value_bytes, size_t list_bytes)
 {
-    if (w->ed_indices.bytes >= index_bytes && w->ed_values.bytes >= value_bytes && w->ed_list.bytes >= list_bytes)
-        return XPBD_OK;
-    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    XPBD_HIP_TRY(w->ed_indices.reserve(index_bytes));
-    XPBD_HIP_TRY(w->ed_values.reserve(value_bytes));
-    XPBD_HIP_TRY(w->ed_list.reserve(list_bytes));
+    XPBD_HIP_TRY(xpbd::reserve_after_sync(w->stream, {{w->ed_indices, index_bytes}, {w->ed_values, value_bytes}, {w->ed_list, list_bytes}}));
     return XPBD_OK;
 }
 
@@ -2403,27 +2349,46 @@ try {
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
+namespace {
+// The scene queries' argument checks (xpbd::check_raycast, xpbd::check_overlap) against one world.
+xpbd::QueryTarget query_target(const xpbd_world *w)
+{
+    return {w->has_topology, w->n, w->n_shapes, "xpbd_world_set_polytopes (set_shapes gives vertices only)"};
+}
+
+int check_world_raycast(const char *who, const xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host)
+{
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    return xpbd::check_raycast(who, query_target(w), rays, n_rays, flags, hits, host);
+}
+
+int check_world_overlap(const char *who, const xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
+                        const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host)
+{
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    return xpbd::check_overlap(who, query_target(w), queries, n_queries, flags, offsets, hits, cap, n_out, host);
+}
+} // namespace
+
 int xpbd_world_raycast(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
 try {
-    if (int rc = xpbd::check_raycast("xpbd_world_raycast", w, rays, n_rays, flags, hits))
-        return rc;
-    if (int rc = xpbd::check_rays_reserved("xpbd_world_raycast", rays, n_rays))
+    if (int rc = check_world_raycast("xpbd_world_raycast", w, rays, n_rays, flags, hits, true))
         return rc;
     return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr, false, 0u);
 } XPBD_ABI_CATCH
 
 int xpbd_world_raycast_masked(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, uint32_t mask, xpbd_ray_hit *hits)
 try {
-    if (int rc = xpbd::check_raycast("xpbd_world_raycast_masked", w, rays, n_rays, flags, hits))
-        return rc;
-    if (int rc = xpbd::check_rays_reserved("xpbd_world_raycast_masked", rays, n_rays))
+    if (int rc = check_world_raycast("xpbd_world_raycast_masked", w, rays, n_rays, flags, hits, true))
         return rc;
     return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr, true, mask);
 } XPBD_ABI_CATCH
 
 int xpbd_world_raycast_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits)
 try {
-    if (int rc = xpbd::check_raycast("xpbd_world_raycast_device", w, dev_rays, n_rays, flags, dev_hits))
+    if (int rc = check_world_raycast("xpbd_world_raycast_device", w, dev_rays, n_rays, flags, dev_hits, false))
         return rc;
     return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr, false, 0u);
 } XPBD_ABI_CATCH
@@ -2431,7 +2396,7 @@ try {
 int xpbd_world_raycast_masked_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, uint32_t mask,
                                      xpbd_ray_hit *dev_hits)
 try {
-    if (int rc = xpbd::check_raycast("xpbd_world_raycast_masked_device", w, dev_rays, n_rays, flags, dev_hits))
+    if (int rc = check_world_raycast("xpbd_world_raycast_masked_device", w, dev_rays, n_rays, flags, dev_hits, false))
         return rc;
     return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr, true, mask);
 } XPBD_ABI_CATCH
@@ -2439,11 +2404,7 @@ try {
 int xpbd_world_overlap(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets,
                        xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out)
 try {
-    if (int rc = xpbd::check_overlap("xpbd_world_overlap", w, queries, n_queries, flags, offsets, hits, cap))
-        return rc;
-    if (n_queries && !n_out)
-        return set_error(XPBD_E_INVALID, "xpbd_world_overlap: NULL n_out");
-    if (int rc = xpbd::check_overlap_queries("xpbd_world_overlap", queries, n_queries, w->n_shapes))
+    if (int rc = check_world_overlap("xpbd_world_overlap", w, queries, n_queries, flags, offsets, hits, cap, n_out, true))
         return rc;
     uint32_t total = 0;
     const int rc = xpbd::overlap_host(w, queries, n_queries, flags, offsets, hits, cap, &total, nullptr);
@@ -2455,7 +2416,7 @@ try {
 int xpbd_world_overlap_device(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32_t n_queries, uint32_t flags, uint32_t *dev_offsets,
                               xpbd_overlap_hit *dev_hits, uint32_t cap)
 try {
-    if (int rc = xpbd::check_overlap("xpbd_world_overlap_device", w, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap))
+    if (int rc = check_world_overlap("xpbd_world_overlap_device", w, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap, nullptr, false))
         return rc;
     return xpbd::overlap_enqueue(w, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap, nullptr);
 } XPBD_ABI_CATCH

@@ -306,6 +306,47 @@ def test_an_overlap_query_has_no_side_effects():
     assert results[0][4][0] > 0
 
 
+def test_ray_casts_and_overlaps_share_scratch_that_grows_under_use():
+    """One world answers a stream of calls of both kinds and both paths, small batches before large ones: every call after the
+    first finds scratch and staging that the other kind sized, and grows or reuses it.  Each answer equals, bit for bit, that of
+    the same call on a fresh world with the same bodies.  300 bodies: above the 256 floor of the table size, two blocks."""
+    n = 300
+    bodies, sid = pile(n)
+    polys = capi.scene_polytopes(KIND)
+    rng = np.random.default_rng(83)
+    centre = bodies[:, 31:34] + bodies[:, 28:31]
+    # rays: straight down onto bodies from above the pile, then random ones inside its box
+    d = rng.normal(size=(300, 3))
+    lo, hi = centre.min(axis=0) - 0.5, centre.max(axis=0) + 0.5
+    r = np.concatenate([capi.rays(centre[rng.integers(0, n, 300)] + [0.0, 0.0, 50.0], [[0.0, 0.0, -1.0]]),
+                        capi.rays(rng.uniform(lo, hi, (300, 3)), d / np.linalg.norm(d, axis=1, keepdims=True))])
+    q = query_families(rng, bodies, sid, polys, 200)
+    at = 200 // 6 + 1                                               # the second family: poses of resident bodies, nobody ignored
+    calls = [("raycast", r[:8], capi.RAYCAST_BRUTE_FORCE), ("overlap", q[at:at + 8:2], 0), ("raycast", r, 0), ("overlap", q, BRUTE)]
+    calls += calls[:2]
+    assert len(r) == 600 and len(calls[1][1]) == 4
+
+    def world():
+        w = capi.World(mode=capi.MODE_CONTACTS)
+        w.set_polytopes(polys)
+        w.upload(bodies, sid)
+        return w
+
+    def ask(w, kind, batch, flags):
+        if kind == "raycast":
+            hits = w.raycast(batch, flags)
+            return np.zeros(0, dtype=np.uint32), hits, int(np.sum(hits["body"] != capi.NO_HIT))
+        offsets, hits = w.overlap(batch, flags)
+        return offsets, hits, len(hits)
+
+    with world() as w:
+        got = [ask(w, *call) for call in calls]
+    for call, (offsets, hits, found) in zip(calls, got):
+        with world() as fresh:
+            want = ask(fresh, *call)
+        assert found >= 4 and same_answer((offsets, hits), want[:2]), call[0]
+
+
 @pytest.mark.parametrize("n_ranks", [2, 4])
 def test_the_sharded_world_equals_the_single_world(n_ranks):
     n, frames, substeps = 4096, 6, 10
