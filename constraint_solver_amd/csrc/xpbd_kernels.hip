@@ -28,6 +28,39 @@ namespace {
 #define XPBD_STEP_MIN_WAVES_PER_SIMD 1
 #endif
 
+// The substep loop of one lane.  `pass1(cur)` returns the lane's contact mask (the three table paths of k_step differ
+// in it alone); pass 2 reads the lane's penetrating vertices from the LDS table `verts`.
+template <bool TRACE, class Pass1>
+__device__ __forceinline__ uint32_t run_substeps(BodyDynamic &d, const BodyStatic &s, double h, uint32_t substeps, const double *verts,
+                                                 Pass1 pass1, uint32_t *__restrict__ trace_lane, uint32_t trace_stride)
+{
+    const double compliance = 1e-6 / (h * h); // src/solver.rs:20
+    uint32_t mask = 0;
+    for (uint32_t k = 0; k < substeps; ++k) {
+        const SubstepFrames f = integrate_body(d, s, h);
+        mask = pass1(f.cur);
+        solve_masked(d.pos, d.rot, s.inv_mass, s.inv_inertia, s.com, f.cur, f.past, compliance, verts, mask);
+        derive_body(d, f.past_pos, f.past_rot, h);
+        if (TRACE)
+            trace_lane[(size_t)k * trace_stride] = mask;
+    }
+    return mask;
+}
+
+// A wave of one shape with exactly NV vertices: the table is read once, through a wave-uniform address.
+template <bool TRACE, uint32_t NV>
+__device__ __forceinline__ uint32_t run_substeps_table(BodyDynamic &d, const BodyStatic &s, double h, uint32_t substeps,
+                                                       const double *verts, const double *__restrict__ uniform_verts,
+                                                       uint32_t *__restrict__ trace_lane, uint32_t trace_stride)
+{
+    double table[3 * NV];
+#pragma unroll
+    for (uint32_t k = 0; k < 3 * NV; ++k)
+        table[k] = uniform_verts[k];
+    return run_substeps<TRACE>(d, s, h, substeps, verts, [&](const Frame &cur) { return ground_mask_table<NV>(cur, table); },
+                               trace_lane, trace_stride);
+}
+
 template <bool TRACE>
 __global__ void __launch_bounds__(kMaxStepBlock, XPBD_STEP_MIN_WAVES_PER_SIMD) k_step(BodyArrays b, ShapeTable shapes, double h, uint32_t substeps,
                        uint32_t *__restrict__ last_mask, uint32_t *__restrict__ trace_masks,
@@ -48,19 +81,32 @@ __global__ void __launch_bounds__(kMaxStepBlock, XPBD_STEP_MIN_WAVES_PER_SIMD) k
 
     const BodyStatic s = load_static(b, i);
     BodyDynamic d = load_dynamic(b.dyn, st, i);
+    uint32_t *trace_lane = TRACE ? trace_masks + (size_t)trace_row0 * st + i : nullptr;
 
+    // Bodies are usually stored shape by shape, so most waves hold one shape.  The lanes past b.n have left: the ballot
+    // counts live lanes only.
     const uint32_t sid = b.shape_id[i];
-    const uint32_t v0 = lds_off[sid];
-    const uint32_t nv = lds_off[sid + 1] - v0;
-    const double *verts = lds + 3 * v0;
-
-    const double compliance = 1e-6 / (h * h); // src/solver.rs:20
-
-    uint32_t mask = 0;
-    for (uint32_t k = 0; k < substeps; ++k) {
-        mask = substep(d, s, h, compliance, verts, nv);
-        if (TRACE)
-            trace_masks[(size_t)(trace_row0 + k) * st + i] = mask;
+    const uint32_t wave_sid = __builtin_amdgcn_readfirstlane(sid);
+    uint32_t mask;
+    if (__ballot(sid != wave_sid) == 0) {
+        // Uniform wave: offsets, vertex count and table address are scalars.
+        const uint32_t v0 = __builtin_amdgcn_readfirstlane(lds_off[wave_sid]);
+        const uint32_t nv = __builtin_amdgcn_readfirstlane(lds_off[wave_sid + 1]) - v0;
+        const double *verts = lds + 3 * v0;
+        if (nv == 8)
+            mask = run_substeps_table<TRACE, 8>(d, s, h, substeps, verts, shapes.verts + 3 * (size_t)v0, trace_lane, st);
+        else if (nv == 4)
+            mask = run_substeps_table<TRACE, 4>(d, s, h, substeps, verts, shapes.verts + 3 * (size_t)v0, trace_lane, st);
+        else // other counts: the table stays in LDS, walked by a scalar-counted loop
+            mask = run_substeps<TRACE>(d, s, h, substeps, verts, [&](const Frame &cur) { return ground_mask(cur, verts, nv); },
+                                       trace_lane, st);
+    } else {
+        // Mixed wave: every lane walks its own shape.
+        const uint32_t v0 = lds_off[sid];
+        const uint32_t nv = lds_off[sid + 1] - v0;
+        const double *verts = lds + 3 * v0;
+        mask = run_substeps<TRACE>(d, s, h, substeps, verts, [&](const Frame &cur) { return ground_mask(cur, verts, nv); },
+                                   trace_lane, st);
     }
 
     store_dynamic(b.dyn, st, i, d);

@@ -115,6 +115,24 @@ __device__ __forceinline__ uint32_t ground_mask(const Frame &cur, const double *
     return mask;
 }
 
+// Pass 1 for a wave whose lanes all have the same shape of exactly NV vertices: `table` holds that shape's vertices in
+// wave-uniform values (k_step loads them once per kernel through a uniform address, so they live in scalar registers
+// and feed the f64 instructions as scalar operands).  Fully unrolled: no LDS read and no per-lane loop in the substep.
+// The expression per vertex is ground_mask's.
+template <uint32_t NV>
+__device__ __forceinline__ uint32_t ground_mask_table(const Frame &cur, const double (&table)[3 * NV])
+{
+    uint32_t mask = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < NV; ++v) {
+        const Vec3 vertex{table[3 * v + 0], table[3 * v + 1], table[3 * v + 2]};
+        const Vec3 x = cur * vertex;
+        if (!(x.z >= 0.0))
+            mask |= 1u << v;
+    }
+    return mask;
+}
+
 // Pass 2 -- the lane walks the penetrating vertices of `mask` in ascending index order (the reference's push
 // order).  Lane-compacting the contact work this way makes a wave run the expensive body max-over-lanes(contact
 // count) times instead of once per shape vertex with most lanes masked off.  Recomputing x for the chosen vertex
@@ -199,16 +217,6 @@ __device__ __forceinline__ void derive_body(BodyDynamic &d, Vec3 past_pos, Quat 
     if (dr.s < 0.0)
         dr = -dr;
     d.ang = (2.0 * vec_of(dr)) / h;
-}
-
-// One whole substep of solver::step for one body (src/solver.rs:7-15).
-__device__ __forceinline__ uint32_t substep(BodyDynamic &d, const BodyStatic &s, double h, double compliance,
-                                            const double *verts, uint32_t n_verts)
-{
-    const SubstepFrames f = integrate_body(d, s, h);
-    const uint32_t mask = solve_ground(d, s, f, compliance, verts, n_verts);
-    derive_body(d, f.past_pos, f.past_rot, h);
-    return mask;
 }
 
 } // namespace xpbd

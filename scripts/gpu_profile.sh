@@ -3,7 +3,8 @@
 # same command restricted to one part at a time (--only: no extras / CPU leg, so the kernel rows are the timed regime),
 # and the PMC passes, each counter group in its own run (never mixed with other trace domains).
 # Usage: scripts/gpu_profile.sh <tag> [parts...]   -> everything lands under gpurun_out/<tag>/
-#   parts: bench trace trace_big pmc pmc_big contacts_pmc calib  (default: bench trace pmc)
+#   parts: bench trace trace_pinned trace_big pmc pmc_lds pmc_big contacts_pmc calib  (default: bench trace pmc)
+# XPBD_HIP_LIB=<another libxpbd_hip.so> profiles that build instead (the parent's, for a before / after pair).
 set -eo pipefail
 TAG=${1:-prof}; shift || true
 PARTS=${*:-bench trace pmc}
@@ -46,6 +47,9 @@ if has trace; then
   trace joints --only boxes_262144_joints_65536
   trace boxes_pile --only boxes_pile_262144_sat
 fi
+if has trace_pinned; then   # the fused stepper alone (the other parts of `trace` left out)
+  trace pinned --only pinned
+fi
 if has trace_big; then   # k_step at 2 097 152 bodies, one launch per substep: the HBM-resident roofline line, reproducible from rocprof
   trace pinned_substep_big --only pinned --mode substep --bodies 2097152 --steps 5 --warmup 2
 fi
@@ -62,6 +66,9 @@ if has pmc; then
   pmc write_fused "--only pinned" WRITE_SIZE
   pmc fetch_substep "--only pinned --mode substep" FETCH_SIZE
   pmc write_substep "--only pinned --mode substep" WRITE_SIZE
+fi
+if has pmc_lds; then   # where k_step's waves wait: parked on s_waitcnt (SQ_WAIT_ANY) against stalled at issue (SQ_WAIT_INST_ANY, its LDS share)
+  pmc lds "--only pinned" SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES
 fi
 if has pmc_big; then   # 2 097 152 bodies: 864 MB per launch, far beyond the 256 MiB Infinity Cache
   pmc fetch_substep_big "--only pinned --mode substep --bodies 2097152 --steps 5 --warmup 2" FETCH_SIZE

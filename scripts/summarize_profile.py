@@ -105,6 +105,14 @@ def main(out):
             except ValueError:
                 pass
     valu, wave = pmc(out, "valu", 20).get("k_step<false>", {}), pmc(out, "wave", 20).get("k_step<false>", {})
+    lds = pmc(out, "lds", 20).get("k_step<false>", {})
+    if lds:                                                # a wave's cycles: parked on s_waitcnt / stalled at issue / issuing
+        s["pmc_k_step_fused_waits_per_launch"] = lds
+        s["derived_k_step_fused_waits"] = {"parked_on_waitcnt_share": lds["SQ_WAIT_ANY"] / lds["SQ_WAVE_CYCLES"],
+                                           "issue_stall_share": lds["SQ_WAIT_INST_ANY"] / lds["SQ_WAVE_CYCLES"],
+                                           "lds_issue_stall_share": lds.get("SQ_WAIT_INST_LDS", 0.0) / lds["SQ_WAVE_CYCLES"]}
+        if valu.get("SQ_WAVES"):                           # the wave count comes from the `valu` pass of the same set (pmc)
+            s["derived_k_step_fused_waits"]["lds_insts_per_wave_substep"] = lds.get("SQ_INSTS_LDS", 0.0) / valu["SQ_WAVES"] / 20.0
     if valu:
         s["pmc_k_step_fused_per_launch"] = {**valu, **wave}
         d = {"valu_insts_per_wave_substep": valu["SQ_INSTS_VALU"] / valu["SQ_WAVES"] / 20.0,
