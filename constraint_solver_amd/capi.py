@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "xpbd_world_apply_impulses_device", "xpbd_world_set_dynamics", "xpbd_world_get_dynamics",
     "xpbd_multi_world_set_external_wrench", "xpbd_multi_world_apply_impulses",
     "xpbd_world_overlap", "xpbd_world_overlap_device", "xpbd_multi_world_overlap",
+    "xpbd_world_sweep", "xpbd_world_sweep_device", "xpbd_multi_world_sweep",
 ]
 
 
@@ -192,6 +193,38 @@ def _overlap(fn, h, queries, flags):
     if total.value:
         _check(fn(h, qp, q.size, flags, offsets.ctypes.data, hits.ctypes.data, hits.size, C.byref(total)))
     return offsets, hits
+
+
+# xpbd_sweep (104 bytes) / xpbd_sweep_hit (72 bytes) as numpy records; sweep queries (EXTENSION)
+SWEEP_DTYPE = np.dtype([("position", "<f8", (3,)), ("rotation", "<f8", (4,)), ("direction", "<f8", (3,)), ("max_distance", "<f8"),
+                        ("shape", "<u4"), ("ignore_body", "<u4"), ("mask", "<u4"), ("reserved", "<u4")])
+SWEEP_HIT_DTYPE = np.dtype([("body", "<u4"), ("feature", "<u4"), ("face", "<u4"), ("reserved", "<u4"), ("distance", "<f8"),
+                            ("position", "<f8", (3,)), ("normal", "<f8", (3,))])
+SWEEP_INITIAL = 3                 # xpbd_sweep_hit.feature: the volume overlaps the body at t = 0
+SWEEP_BRUTE_FORCE, SWEEP_MASKED = 1, 2
+SWEEP_BRUTE_FORCE_SWEEPS = 8      # calls with at most this many sweeps take the brute-force path anyway
+
+
+def sweeps(position, rotation, direction, shape, max_distance=np.inf, ignore=None, mask=None):
+    """SWEEP_DTYPE records from (n, 3) positions, (n, 4) rotations {s, x, y, z}, (n, 3) directions and shape indices (all
+    broadcast), a max_distance per sweep or for all, the body each sweep ignores (None: none) and its group mask (None: ~0; read
+    with SWEEP_MASKED only)."""
+    p, r = np.atleast_2d(np.asarray(position, dtype=np.float64)), np.atleast_2d(np.asarray(rotation, dtype=np.float64))
+    d, sh = np.atleast_2d(np.asarray(direction, dtype=np.float64)), np.atleast_1d(np.asarray(shape, dtype=np.uint32))
+    extra = [np.atleast_1d(np.asarray(x)) for x in (max_distance, ignore, mask) if x is not None]
+    n = max([p.shape[0], r.shape[0], d.shape[0], sh.shape[0]] + [x.shape[0] for x in extra])
+    out = np.zeros(n, dtype=SWEEP_DTYPE)
+    out["position"], out["rotation"], out["direction"], out["shape"], out["max_distance"] = p, r, d, sh, max_distance
+    out["ignore_body"] = NO_HIT if ignore is None else ignore
+    out["mask"] = 0xFFFFFFFF if mask is None else mask
+    return out
+
+
+def _sweep(fn, h, sweeps, flags):
+    s = np.ascontiguousarray(sweeps, dtype=SWEEP_DTYPE).reshape(-1)
+    out = np.zeros(s.size, dtype=SWEEP_HIT_DTYPE)
+    _check(fn(h, s.ctypes.data if s.size else None, s.size, flags, out.ctypes.data if s.size else None))
+    return out
 
 
 # Contact reports (EXTENSION): xpbd_pair_contact (64 bytes), xpbd_contact_point (48), xpbd_contact_event (12)
@@ -351,6 +384,12 @@ def hip_lib():
             L.xpbd_world_overlap.argtypes = ovl + [_u32p]
             L.xpbd_world_overlap_device.argtypes = ovl
             L.xpbd_multi_world_overlap.argtypes = ovl + [_u32p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            L.xpbd_world_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.xpbd_world_sweep_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.xpbd_multi_world_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -611,6 +650,15 @@ class World:
         stream; the total is offsets[n], hits beyond cap are not written."""
         _check(hip_lib().xpbd_world_overlap_device(self._h, C.c_void_p(queries_ptr), n, flags, C.c_void_p(offsets_ptr),
                                                    C.c_void_p(hits_ptr) if hits_ptr else None, cap))
+
+    def sweep(self, sweeps, flags=0):
+        """SWEEP_HIT_DTYPE records of the first body every convex volume hits when moved along its segment (SWEEP_DTYPE records,
+        see sweeps()) at the current poses."""
+        return _sweep(hip_lib().xpbd_world_sweep, self._h, sweeps, flags)
+
+    def sweep_device(self, sweeps_ptr, n, hits_ptr, flags=0):
+        """Device arrays of n xpbd_sweep and n xpbd_sweep_hit, stream-ordered on the world's stream."""
+        _check(hip_lib().xpbd_world_sweep_device(self._h, C.c_void_p(sweeps_ptr), n, flags, C.c_void_p(hits_ptr)))
 
     # body edits (include/xpbd.h, "Body EDITS"): forces, impulses and state of resident bodies
     def set_external_wrench(self, indices=None, force=None, torque=None):
@@ -879,6 +927,10 @@ class MultiWorld:
     def overlap(self, queries, flags=0):
         """World.overlap over the whole sharded world (collective); bodies and ignore_body are global indices."""
         return _overlap(hip_lib().xpbd_multi_world_overlap, self._h, queries, flags)
+
+    def sweep(self, sweeps, flags=0):
+        """World.sweep over the whole sharded world (collective); bodies and ignore_body are global indices."""
+        return _sweep(hip_lib().xpbd_multi_world_sweep, self._h, sweeps, flags)
 
     def synchronize(self):
         _check(hip_lib().xpbd_multi_world_synchronize(self._h))

@@ -112,6 +112,8 @@ struct xpbd_impulse;
 struct xpbd_ray_hit;
 struct xpbd_overlap_query;
 struct xpbd_overlap_hit;
+struct xpbd_sweep;
+struct xpbd_sweep_hit;
 struct xpbd_pair_contact;
 struct xpbd_contact_point;
 
@@ -172,6 +174,12 @@ int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32
                     xpbd_overlap_hit *dev_hits, uint32_t cap, const uint32_t *dev_global_id);
 int overlap_host(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets, xpbd_overlap_hit *hits,
                  uint32_t cap, uint32_t *n_out, const uint32_t *dev_global_id);
+// Sweep queries against the world's bodies (include/xpbd.h, "Sweep queries"): the check (as check_overlap; a sweep's shape is
+// not an error, it hits nothing), then stream-ordered / from and to host arrays, on the scratch and staging of the other queries.
+int check_sweep(const char *who, const QueryTarget &t, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, const void *hits, bool host);
+int sweep_enqueue(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *dev_hits,
+                  const uint32_t *dev_global_id);
+int sweep_host(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits, const uint32_t *dev_global_id);
 // The current frame's contact report of a shard of the multi-GPU world (include/xpbd.h, "Contact REPORTS"): only the pairs whose
 // lower body has dev_owned[slot] != 0, bodies named by dev_global_id[slot] (device arrays of the world's body count; global ids
 // ascending with the slot).  Waits.  A world without bodies reports nothing.

@@ -1430,6 +1430,12 @@ int shard_overlap(Shard &s, const xpbd_overlap_query *queries, uint32_t n_querie
     return xpbd::overlap_host(s.world, queries, n_queries, flags, offsets.data(), hits.data(), total, &total, s.query_ids.as<uint32_t>());
 }
 
+int shard_sweep(Shard &s, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits)
+{
+    XPBD_TRY(upload_query_ids(s));
+    return xpbd::sweep_host(s.world, sweeps, n_sweeps, flags, hits, s.query_ids.as<uint32_t>());
+}
+
 int check_usable(const xpbd_multi_world *mw, const char *who)
 {
     if (!mw)
@@ -1439,7 +1445,7 @@ int check_usable(const xpbd_multi_world *mw, const char *who)
     return XPBD_OK;
 }
 
-// What the scene queries' argument checks (xpbd::check_raycast, xpbd::check_overlap) need to know of the world.
+// What the scene queries' argument checks (xpbd::check_raycast, xpbd::check_overlap, xpbd::check_sweep) need to know of the world.
 xpbd::QueryTarget query_target(const xpbd_multi_world *mw)
 {
     return {mw->have_shapes, mw->planned ? mw->n_global : 0u, (uint32_t)mw->shape_radius.size(), "xpbd_multi_world_set_polytopes"};
@@ -1506,6 +1512,29 @@ int multi_overlap(xpbd_multi_world *mw, const xpbd_overlap_query *queries, uint3
     *n_out = xpbd::merge_overlap_lists(all_offsets.data(), lists.rows.data(), lists.widest, mw->n_ranks, n_queries, offsets, hits, cap);
     if (*n_out > cap)
         return set_error(XPBD_E_CAPACITY, "%s: %u hits but room for %u", who, *n_out, cap);
+    return XPBD_OK;
+}
+
+// xpbd_multi_world_sweep: every local shard sweeps against its owned bodies; one all-gather of the hit records, merged by the
+// (t, global index) rule of a single world (xpbd::merge_sweep_hits).
+int multi_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits)
+{
+    const char *who = "xpbd_multi_world_sweep";
+    XPBD_TRY(check_usable(mw, who));
+    XPBD_TRY(xpbd::check_sweep(who, query_target(mw), sweeps, n_sweeps, flags, hits, true));
+    if (n_sweeps == 0)
+        return XPBD_OK;
+    LocalStatus st;
+    std::vector<std::vector<xpbd_sweep_hit>> mine(mw->shards.size(), std::vector<xpbd_sweep_hit>(n_sweeps));
+    std::vector<const void *> send;
+    for (size_t k = 0; k < mw->shards.size(); ++k) {
+        if (st.ok())
+            st.keep(shard_sweep(mw->shards[k], sweeps, n_sweeps, flags, mine[k].data()));
+        send.push_back(mine[k].data());
+    }
+    std::vector<uint8_t> all;
+    XPBD_TRY(all_gather_host(mw, send, (size_t)n_sweeps * sizeof(xpbd_sweep_hit), all, st));
+    xpbd::merge_sweep_hits(all.data(), mw->n_ranks, n_sweeps, hits);
     return XPBD_OK;
 }
 
@@ -2048,6 +2077,11 @@ int xpbd_multi_world_overlap(xpbd_multi_world *mw, const xpbd_overlap_query *que
                              xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out)
 try {
     return multi_overlap(mw, queries, n_queries, flags, offsets, hits, cap, n_out);
+} XPBD_MULTI_ABI_CATCH
+
+int xpbd_multi_world_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits)
+try {
+    return multi_sweep(mw, sweeps, n_sweeps, flags, hits);
 } XPBD_MULTI_ABI_CATCH
 
 int xpbd_multi_world_set_contact_report(xpbd_multi_world *mw, uint32_t enable)

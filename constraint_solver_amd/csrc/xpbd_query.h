@@ -1,4 +1,4 @@
-// xpbd_query.h -- scene queries (EXTENSION): launchers for the batched ray casts and overlap queries in xpbd_query.hip.
+// xpbd_query.h -- scene queries (EXTENSION): launchers for the batched ray casts, overlap queries and sweep queries in xpbd_query.hip.
 //
 // Semantics: include/xpbd.h, "Scene queries".  Two paths give the same bits in every field of every hit:
 //  * grid: the bodies' bounding spheres (frame * centroid, PolytopeTables::radii) go into a uniform grid built for this call
@@ -44,7 +44,7 @@ struct QuerySizes {
 // What a ray cast over n bodies and n_rays rays needs (brute: whether it takes the brute-force path).
 QuerySizes query_scratch_bytes(uint32_t n, uint32_t n_rays, bool brute);
 
-// The scene queries' device memory of one world: the scratch of a call, shared by the ray casts and the overlap queries, and
+// The scene queries' device memory of one world: the scratch of a call, shared by the ray casts, the overlap and the sweep queries, and
 // the staging of the host variants' arrays (rays or queries in, hits out, an overlap's offsets).  One call uses it at a time:
 // the calls of a world are ordered on its stream, and every host variant ends with a wait.
 struct SceneQueryScratch {
@@ -90,5 +90,14 @@ QuerySizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute);
 hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *queries,
                           uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, uint32_t *offsets, void *hits, uint32_t cap,
                           hipStream_t stream);
+
+// ---- sweep queries: the first body a translating convex volume hits (include/xpbd.h, "Sweep queries") ----------------------
+// Passes: the bounding spheres of the bodies (k_query_bodies) and of the volumes at t = 0 (k_sweep_queries, the records of an
+// overlap query); on the grid path the grid of a ray cast; then one group of 16 / 32 / 64 lanes per sweep walks the cells of
+// its centre line as a ray does, looks for every stretch of it at the bodies in the cells the volume's sphere covers, and keeps
+// the minimum under (t, index).  The brute-force path visits every body instead.  A sweep's scratch is an overlap's
+// (overlap_scratch_bytes with the number of sweeps).
+hipError_t launch_sweep(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *sweeps,
+                        uint32_t n_sweeps, bool masked, bool brute, const QueryScratch &s, void *hits, hipStream_t stream);
 
 } // namespace xpbd

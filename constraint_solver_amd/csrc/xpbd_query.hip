@@ -1,4 +1,4 @@
-// xpbd_query.hip -- scene queries (EXTENSION) for gfx950: batched ray casts and overlap queries against the world's bodies.
+// xpbd_query.hip -- scene queries (EXTENSION) for gfx950: batched ray casts, overlap queries and sweep queries against the world's bodies.
 //
 // Semantics: include/xpbd.h, "Scene queries"; layout of the work: xpbd_query.h.  Determinism: the winner of a ray is the
 // minimum of its candidates under one total order -- (t, index) -- and a candidate's t is a function of the ray and the body
@@ -6,6 +6,7 @@
 // several cells changes any bit.  Atomics count integers only.
 #include <cfloat>
 #include <cmath>
+#include <cstdint>
 
 #include <type_traits>
 
@@ -550,6 +551,63 @@ struct OverlapLds {
     double local[2][V][3];
 };
 
+// Staging shared by the overlap and the sweep queries, for volume A (its world-space vertices already in s.world[0]) against body B
+// by a group of 2 H lanes, `half` of which works for A (0) or B (1): A's vertices into B's local space, B's into world space and
+// into A's local space -- vertices through their own frame into world space and through the inverse of the other frame.
+template <class Lds>
+__device__ __forceinline__ void stage_pair(Lds &s, const PolytopeTables &t, const ShapeDesc &da, const ShapeDesc &db, const Frame &fa_inv, const Frame &fb,
+                                           const Frame &fb_inv, uint32_t half, uint32_t k, uint32_t H)
+{
+    __syncthreads(); // (one wave per workgroup: a fence; the previous candidate's reads are done)
+    if (half == 0) {
+        for (uint32_t vtx = k; vtx < da.n_verts; vtx += H)
+            st3(s.local[0], vtx, fb_inv * ld3(s.world[0], vtx));
+    } else {
+        for (uint32_t vtx = k; vtx < db.n_verts; vtx += H) {
+            const double *v = t.verts + 3 * (size_t)(db.vert0 + vtx);
+            const Vec3 w = fb * Vec3{v[0], v[1], v[2]};
+            st3(s.world[1], vtx, w);
+            st3(s.local[1], vtx, fa_inv * w);
+        }
+    }
+    __syncthreads();
+}
+
+// The world-space unique edge directions of both shapes into s.local (whose vertices the face queries are done with), when
+// both tables fit it; false: edge_axis reads the tables.
+template <uint32_t L, class Lds>
+__device__ __forceinline__ bool stage_edge_dirs(Lds &s, const PolytopeTables &t, const ShapeDesc &da, const ShapeDesc &db, const Frame &fa, const Frame &fb,
+                                                uint32_t lane)
+{
+    const bool dirs_staged = da.n_dirs <= Lds::kVerts && db.n_dirs <= Lds::kVerts;
+    __syncthreads();
+    if (dirs_staged) {
+        for (uint32_t d = lane; d < da.n_dirs + db.n_dirs; d += L) {
+            const bool of_b = d >= da.n_dirs;
+            const uint32_t kd = of_b ? d - da.n_dirs : d;
+            const double *dd = t.edge_dirs + 3 * (size_t)((of_b ? db.dir0 : da.dir0) + kd);
+            st3(s.local[of_b ? 1 : 0], kd, (of_b ? fb : fa).rotation * Vec3{dd[0], dd[1], dd[2]});
+        }
+        __syncthreads();
+    }
+    return dirs_staged;
+}
+
+// The axis of edge directions i of A and j of B; a component that is not finite means parallel directions: no axis.
+__device__ __forceinline__ Vec3 edge_axis_of_table(const PolytopeTables &t, const ShapeDesc &da, const ShapeDesc &db, const Frame &fa, const Frame &fb,
+                                                   uint32_t i, uint32_t j)
+{
+    const double *da_ = t.edge_dirs + 3 * (size_t)(da.dir0 + i), *db_ = t.edge_dirs + 3 * (size_t)(db.dir0 + j);
+    return normalized(cross(fa.rotation * Vec3{da_[0], da_[1], da_[2]}, fb.rotation * Vec3{db_[0], db_[1], db_[2]}));
+}
+
+template <class Lds>
+__device__ __forceinline__ Vec3 edge_axis(const Lds &s, bool dirs_staged, const PolytopeTables &t, const ShapeDesc &da, const ShapeDesc &db, const Frame &fa,
+                                          const Frame &fb, uint32_t i, uint32_t j)
+{
+    return dirs_staged ? normalized(cross(ld3(s.local[0], i), ld3(s.local[1], j))) : edge_axis_of_table(t, da, db, fa, fb, i, j);
+}
+
 // The decision part of the SAT for volume A (frame fa, shape sa, its world-space vertices already in s.world[0]) against body
 // B, by a group of L lanes: op_sat of the oracle up to its feature choice, with the arithmetic of the contact pipeline's
 // sat_pair (xpbd_pairs.hip) -- vertices through their own frame into world space and through the inverse of the other frame
@@ -565,19 +623,7 @@ __device__ __forceinline__ bool overlap_decide(Lds &s, const PolytopeTables &t, 
         return false;
     const Frame fb_inv = inverse(fb);
     const uint32_t half = lane / H, k = lane % H; // first half of the group works for A, second for B
-    __syncthreads(); // (one wave per workgroup: a fence; the previous candidate's reads are done)
-    if (half == 0) {
-        for (uint32_t vtx = k; vtx < da.n_verts; vtx += H)
-            st3(s.local[0], vtx, fb_inv * ld3(s.world[0], vtx));
-    } else {
-        for (uint32_t vtx = k; vtx < db.n_verts; vtx += H) {
-            const double *v = t.verts + 3 * (size_t)(db.vert0 + vtx);
-            const Vec3 w = fb * Vec3{v[0], v[1], v[2]};
-            st3(s.world[1], vtx, w);
-            st3(s.local[1], vtx, fa_inv * w);
-        }
-    }
-    __syncthreads();
+    stage_pair(s, t, da, db, fa_inv, fb, fb_inv, half, k, H);
 
     // ---- face queries: A's faces on the first half, B's on the second --------------------------------------------------
     double fdist = -DBL_MAX;
@@ -618,27 +664,11 @@ __device__ __forceinline__ bool overlap_decide(Lds &s, const PolytopeTables &t, 
     uint32_t eq = kNoBody;
     const double *cca = t.centroids + 3 * (size_t)sa, *ccb = t.centroids + 3 * (size_t)sb;
     const Vec3 a_to_b = fb * Vec3{ccb[0], ccb[1], ccb[2]} - fa * Vec3{cca[0], cca[1], cca[2]};
-    const bool dirs_staged = da.n_dirs <= Lds::kVerts && db.n_dirs <= Lds::kVerts;
-    __syncthreads();
-    if (dirs_staged) {
-        for (uint32_t d = lane; d < da.n_dirs + db.n_dirs; d += L) {
-            const bool of_b = d >= da.n_dirs;
-            const uint32_t kd = of_b ? d - da.n_dirs : d;
-            const double *dd = t.edge_dirs + 3 * (size_t)((of_b ? db.dir0 : da.dir0) + kd);
-            st3(s.local[of_b ? 1 : 0], kd, (of_b ? fb : fa).rotation * Vec3{dd[0], dd[1], dd[2]});
-        }
-        __syncthreads();
-    }
+    const bool dirs_staged = stage_edge_dirs<L>(s, t, da, db, fa, fb, lane);
     const uint32_t total = da.n_dirs * db.n_dirs;
     for (uint32_t q = lane; q < total; q += L) {
         const uint32_t i = q / db.n_dirs, j = q - i * db.n_dirs;
-        Vec3 n;
-        if (dirs_staged) {
-            n = normalized(cross(ld3(s.local[0], i), ld3(s.local[1], j)));
-        } else {
-            const double *da_ = t.edge_dirs + 3 * (size_t)(da.dir0 + i), *db_ = t.edge_dirs + 3 * (size_t)(db.dir0 + j);
-            n = normalized(cross(fa.rotation * Vec3{da_[0], da_[1], da_[2]}, fb.rotation * Vec3{db_[0], db_[1], db_[2]}));
-        }
+        Vec3 n = edge_axis(s, dirs_staged, t, da, db, fa, fb, i, j);
         if (!(fabs(n.x) <= DBL_MAX && fabs(n.y) <= DBL_MAX && fabs(n.z) <= DBL_MAX))
             continue; // parallel directions: a NaN axis contributes nothing
         if (dot(n, a_to_b) < 0.0)
@@ -883,6 +913,429 @@ __global__ void __launch_bounds__(kBlock) k_overlap_sort(const uint32_t *__restr
         }
 }
 
+// ---- sweep queries: a convex volume translated along a segment -------------------------------------------------------------
+// Semantics: include/xpbd.h, "Sweep queries".  The volume A at fa + t * d against the resting body B is, over every axis the SAT
+// walks, one linear constraint "separation = s + t * v": the ray's slab test (ray_body) over the faces of A, the faces of B and
+// both signs of every edge-direction pair.  The winner of a sweep is the minimum of its candidates under (t, index), and a
+// candidate's t is a function of the sweep and the body alone, so neither the path nor how often a body is tested changes a bit.
+static_assert(sizeof(xpbd_sweep) == 104 && sizeof(xpbd_sweep_hit) == 72, "xpbd_sweep is 104 bytes, xpbd_sweep_hit 72");
+constexpr double kSweepReach = 4.0;   // volumes wider than this many cell edges look at every body instead of walking cells
+constexpr double kSweepMargin = 0.01; // the centre line is clipped to the grid's box grown by the radius and this part of a cell
+
+struct Sweep {
+    Frame f;
+    Vec3 d;
+    double tmax;
+    uint32_t shape, ignore, mask;
+};
+
+__device__ __forceinline__ Sweep load_sweep(const xpbd_sweep *__restrict__ sweeps, uint32_t q)
+{
+    const xpbd_sweep &x = sweeps[q];
+    return Sweep{Frame{Vec3{x.position[0], x.position[1], x.position[2]}, Quat{x.rotation[0], x.rotation[1], x.rotation[2], x.rotation[3]}},
+                 Vec3{x.direction[0], x.direction[1], x.direction[2]}, x.max_distance, x.shape, x.ignore_body, x.mask};
+}
+
+// One lane per sweep: the bounding sphere of the volume at t = 0 (the layout of k_overlap_queries) and whether the sweep can hit
+// anything -- a shape of the table, a finite frame and direction, a direction that moves, a max_distance >= 0 -- as radius >= 0.
+__global__ void __launch_bounds__(kBlock) k_sweep_queries(const xpbd_sweep *__restrict__ sweeps, uint32_t n_sweeps, PolytopeTables t,
+                                                          double *__restrict__ qrec)
+{
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_sweeps)
+        return;
+    const Sweep sw = load_sweep(sweeps, q);
+    Vec3 c{0.0, 0.0, 0.0};
+    double r = -1.0;
+    if (sw.shape < t.n_shapes) {
+        const double *cc = t.centroids + 3 * (size_t)sw.shape;
+        c = sw.f * Vec3{cc[0], cc[1], cc[2]};
+        const bool finite = isfinite(sw.f.position.x) && isfinite(sw.f.position.y) && isfinite(sw.f.position.z) && isfinite(sw.f.rotation.s) &&
+                            isfinite(sw.f.rotation.x) && isfinite(sw.f.rotation.y) && isfinite(sw.f.rotation.z) && isfinite(c.x) &&
+                            isfinite(c.y) && isfinite(c.z) && isfinite(sw.d.x) && isfinite(sw.d.y) && isfinite(sw.d.z);
+        const bool moving = sw.d.x != 0.0 || sw.d.y != 0.0 || sw.d.z != 0.0;
+        const double rs = t.radii[sw.shape];
+        if (finite && moving && sw.tmax >= 0.0 && rs >= 0.0) // (a NaN max_distance fails the comparison; +inf passes)
+            r = rs;
+    }
+    double2 *o = reinterpret_cast<double2 *>(qrec + (size_t)q * kOverlapRecDoubles);
+    o[0] = double2{c.x, c.y};
+    o[1] = double2{c.z, r};
+}
+
+// Conservative swept-sphere test: false only if the volume's bounding sphere, its centre moving from c along d over [0, t_end],
+// certainly stays clear of the body's.  Never part of the definition: the slack (a relative 1e-6 on the reach, 1e-12 on the
+// distance) is far above the rounding of the test and of the spheres, so no pair the routine below would hit is dropped.
+__device__ __forceinline__ bool sweep_may_reach(Vec3 c, double rq, Vec3 d, double t_end, Vec3 cb, double rb)
+{
+    const Vec3 w = cb - c;
+    const double reach = rq + rb;
+    const double w2 = dot(w, w), wd = dot(w, d), dd = dot(d, d);
+    const double bound = reach * reach * kSphereSlack + 1e-12 * w2;
+    if (!(w2 > bound))
+        return true; // in reach at the start
+    if (wd < 0.0)
+        return false; // out of reach and moving away
+    const double ts = wd / dd;
+    if (ts > t_end) { // the closest point of the segment is its end
+        const Vec3 e = w - d * t_end;
+        return !(dot(e, e) > bound);
+    }
+    return !(w2 - wd * ts > bound);
+}
+
+// The routine of one (sweep, body) pair by a group of L lanes.  A's world-space vertices are in s.world[0] already; t_cap is the
+// sweep's max_distance or the best t so far, whichever is smaller (a pair that enters later cannot win, and an equal t still
+// passes).  True on a hit, with its t and the position of the entering constraint in the order of the definition (kNoBody: the
+// volume overlaps the body at the start).  Every lane of the group returns the same values.
+template <uint32_t L, class Lds>
+__device__ __forceinline__ bool sweep_decide(Lds &s, const PolytopeTables &t, const Frame &fa, const Frame &fa_inv, uint32_t sa, Vec3 d, Vec3 d_a,
+                                             const Frame &fb, uint32_t sb, uint32_t lane, double t_cap, double &t_hit, uint32_t &entering)
+{
+    constexpr uint32_t H = L / 2;
+    const ShapeDesc da = t.desc[sa], db = t.desc[sb];
+    if (da.n_verts == 0 || db.n_verts == 0 || da.n_faces == 0 || db.n_faces == 0)
+        return false;
+    const Frame fb_inv = inverse(fb);
+    const Vec3 d_b = fb_inv.rotation * d;
+    const uint32_t half = lane / H, k = lane % H; // first half of the group works for A, second for B
+    stage_pair(s, t, da, db, fa_inv, fb, fb_inv, half, k, H);
+
+    double t_lo = -INFINITY, t_hi = t_cap;
+    uint32_t enter = kNoBody;
+    bool miss = false;
+    // one constraint, position `at` in the order of the definition (ascending on every lane: the first maximum stays)
+    auto constrain = [&](double sep, double vel, uint32_t at) {
+        if (sep != sep || vel != vel) {
+            miss = true;
+        } else if (vel < 0.0) {
+            const double tk = (-sep) / vel;
+            if (tk > t_lo) {
+                t_lo = tk;
+                enter = at;
+            }
+        } else if (vel > 0.0) {
+            const double tk = (-sep) / vel;
+            t_hi = tk < t_hi ? tk : t_hi;
+        } else if (sep >= 0.0) {
+            miss = true;
+        }
+    };
+    // the group's t_lo (first maximum), t_hi and verdict so far; true: a miss for good
+    auto settle = [&]() -> bool {
+        reduce_max_first(t_lo, enter, L);
+        for (uint32_t off = L >> 1; off; off >>= 1) {
+            const double o = partner(t_hi, off);
+            t_hi = o < t_hi ? o : t_hi;
+        }
+        return group_bits<L>(__ballot(miss)) != 0 || t_lo > t_hi;
+    };
+
+    // ---- faces: A's on the first half (against B's vertices in A's space), B's on the second ------------------------------
+    {
+        const ShapeDesc dm = half ? db : da;
+        const uint32_t n_other = half ? da.n_verts : db.n_verts;
+        const Vec3 d_m = half ? d_b : d_a;
+        for (uint32_t f = k; f < dm.n_faces; f += H) {
+            const double *pl = t.planes + 4 * (size_t)(dm.face0 + f);
+            const Vec3 n{pl[0], pl[1], pl[2]};
+            double low = dot(n, ld3(s.local[half ^ 1u], 0));
+            for (uint32_t v = 1; v < n_other; ++v) {
+                const double x = dot(n, ld3(s.local[half ^ 1u], v));
+                low = x < low ? x : low;
+            }
+            const double w = dot(n, d_m);
+            constrain(low - pl[3], half ? w : -w, half ? da.n_faces + f : f);
+        }
+    }
+    if (settle())
+        return false;
+
+    // ---- edge axes: (unique edge direction of A) x (unique edge direction of B), both signs -------------------------------
+    const bool dirs_staged = stage_edge_dirs<L>(s, t, da, db, fa, fb, lane);
+    const uint32_t total = da.n_dirs * db.n_dirs, edge0 = da.n_faces + db.n_faces;
+    for (uint32_t q = lane; q < total; q += L) {
+        const uint32_t i = q / db.n_dirs, j = q - i * db.n_dirs;
+        const Vec3 n = edge_axis(s, dirs_staged, t, da, db, fa, fb, i, j);
+        if (!(fabs(n.x) <= DBL_MAX && fabs(n.y) <= DBL_MAX && fabs(n.z) <= DBL_MAX))
+            continue; // parallel directions: no axis
+        double hi_a = dot(ld3(s.world[0], 0), n), lo_a = hi_a, hi_b = dot(ld3(s.world[1], 0), n), lo_b = hi_b;
+        for (uint32_t v = 1; v < da.n_verts; ++v) {
+            const double x = dot(ld3(s.world[0], v), n);
+            hi_a = x > hi_a ? x : hi_a;
+            lo_a = x < lo_a ? x : lo_a;
+        }
+        for (uint32_t v = 1; v < db.n_verts; ++v) {
+            const double x = dot(ld3(s.world[1], v), n);
+            hi_b = x > hi_b ? x : hi_b;
+            lo_b = x < lo_b ? x : lo_b;
+        }
+        const double w = dot(n, d);
+        constrain(lo_b - hi_a, -w, edge0 + 2u * q);
+        constrain(lo_a - hi_b, w, edge0 + 2u * q + 1u);
+    }
+    if (settle())
+        return false;
+    const bool initial = t_lo < 0.0;
+    t_hit = initial ? 0.0 : t_lo;
+    entering = initial ? kNoBody : enter;
+    return t_hit <= t_hi;
+}
+
+struct SweepArgs {
+    const xpbd_sweep *sweeps;
+    const double *qrec;         // k_sweep_queries
+    const double *rec;          // k_query_bodies
+    const uint32_t *gid;        // the index a body is known by (null: its slot); XPBD_NO_HIT bodies have radius < 0 in rec
+    const uint2 *filter;        // collision filters (null: every body in group ~0u)
+    const QueryGrid *grid;      // grid path only
+    const uint32_t *cell_start;
+    const uint32_t *items;
+    xpbd_sweep_hit *hits;
+    uint32_t n_sweeps, masked, brute;
+};
+
+// The closest body of every sweep: one group of L lanes per sweep, 64 / L sweeps per wave.  The lanes of a group admit one
+// candidate each (ignore_body, the mask, the swept spheres) and the group then decides the survivors one after the other.  On
+// the grid path the centre line is walked cell by cell as k_query_walk walks a ray, and for the time the centre spends in one
+// cell the lanes share out the box of cells the volume's sphere covers meanwhile.
+template <uint32_t L, uint32_t V>
+__global__ void __launch_bounds__(64) k_sweep_pass(BodyArrays b, PolytopeTables t, SweepArgs a)
+{
+    constexpr uint32_t PW = 64 / L;
+    __shared__ OverlapLds<V> s_all[PW];
+    const uint32_t group = threadIdx.x / L, lane = threadIdx.x % L;
+    const uint32_t q = blockIdx.x * PW + group;
+    if (q >= a.n_sweeps)
+        return;
+    OverlapLds<V> &s = s_all[group];
+    const double2 *qr = reinterpret_cast<const double2 *>(a.qrec + (size_t)q * kOverlapRecDoubles);
+    const double2 q0 = qr[0], q1 = qr[1];
+    const Vec3 cq{q0.x, q0.y, q1.x};
+    const double rq = q1.y;
+    const Sweep sw = load_sweep(a.sweeps, q);
+    Best best = no_hit(); // (face: the position of the entering constraint)
+    Frame fq_inv{};
+    Vec3 d_q{0.0, 0.0, 0.0};
+    if (rq >= 0.0) {
+        fq_inv = inverse(sw.f);
+        d_q = fq_inv.rotation * sw.d;
+        {
+            const ShapeDesc dq = t.desc[sw.shape];
+            for (uint32_t vtx = lane; vtx < dq.n_verts; vtx += L) {
+                const double *v = t.verts + 3 * (size_t)(dq.vert0 + vtx);
+                st3(s.world[0], vtx, sw.f * Vec3{v[0], v[1], v[2]});
+            }
+        }
+        // may body i win? (one lane)
+        auto admit = [&](uint32_t i, Vec3 &centre, double &radius) -> bool {
+            const double2 *r = reinterpret_cast<const double2 *>(a.rec + (size_t)i * kQueryRecDoubles);
+            const double2 d = r[3], e = r[4], f = r[5];
+            centre = Vec3{d.y, e.x, e.y};
+            radius = f.x;
+            if (!(radius >= 0.0))
+                return false;
+            if ((a.gid ? a.gid[i] : i) == sw.ignore)
+                return false;
+            if (a.masked && ((a.filter ? a.filter[i].x : ~0u) & sw.mask) == 0)
+                return false;
+            return sweep_may_reach(cq, rq, sw.d, best.t < sw.tmax ? best.t : sw.tmax, centre, radius);
+        };
+        // the bodies the lanes of the group hold in `mine` (kNoBody: none), in lane order
+        auto decide = [&](uint32_t mine) {
+            uint64_t todo = group_bits<L>(__ballot(mine != kNoBody));
+            while (todo) {
+                const uint32_t src = (uint32_t)__ffsll((long long)todo) - 1u;
+                todo &= todo - 1;
+                const uint32_t i = (uint32_t)__shfl((int)mine, (int)src, L);
+                double th = 0.0;
+                uint32_t entering = kNoBody;
+                if (sweep_decide<L>(s, t, sw.f, fq_inv, sw.shape, sw.d, d_q, body_frame(b, i), b.shape_id[i], lane,
+                                    best.t < sw.tmax ? best.t : sw.tmax, th, entering)) {
+                    const uint32_t id = a.gid ? a.gid[i] : i;
+                    if (better(th, id, best))
+                        best = Best{th, id, entering, i, 0};
+                }
+            }
+        };
+        QueryGrid g{};
+        if (!a.brute)
+            g = *a.grid;
+        if (a.brute || g.mode == kEveryBody || (g.mode == kGrid && !(rq <= kSweepReach * g.edge))) {
+            for (uint32_t i0 = 0; i0 < b.n; i0 += L) {
+                const uint32_t i = i0 + lane;
+                Vec3 cb;
+                double rb;
+                decide(i < b.n && admit(i, cb, rb) ? i : kNoBody);
+            }
+        } else if (g.mode == kGrid) {
+            const double o[3] = {cq.x, cq.y, cq.z}, d[3] = {sw.d.x, sw.d.y, sw.d.z};
+            // clip the centre line to the grid's box grown by the volume's radius: [t_near, t_far].  Outside it the volume
+            // reaches no body's sphere; the cells of the walk may lie outside the grid, the boxes below are clamped to it.
+            const double grow = rq + kSweepMargin * g.edge;
+            double t_near = 0.0, t_far = sw.tmax;
+            bool inside = true;
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                const double lo = (double)g.lo[ax] * g.edge - grow, hi = ((double)g.lo[ax] + (double)g.dims[ax]) * g.edge + grow;
+                if (d[ax] == 0.0) {
+                    inside = inside && o[ax] >= lo && o[ax] <= hi;
+                } else {
+                    const double t1 = (lo - o[ax]) / d[ax], t2 = (hi - o[ax]) / d[ax];
+                    const double tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1;
+                    t_near = tn > t_near ? tn : t_near;
+                    t_far = tf < t_far ? tf : t_far;
+                }
+            }
+            if (inside && t_near <= t_far) {
+                int32_t cell[3], step[3];
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    const double p = d[ax] == 0.0 ? o[ax] : o[ax] + t_near * d[ax];
+                    // (within kSweepReach + 1 cells of the grid, by the clip; the bound keeps the conversion defined regardless)
+                    double c = floor(p / g.edge);
+                    const double c_lo = (double)g.lo[ax] - (kSweepReach + 2.0), c_hi = (double)g.lo[ax] + (double)g.dims[ax] + (kSweepReach + 2.0);
+                    c = c < c_lo ? c_lo : (c > c_hi ? c_hi : c);
+                    cell[ax] = (int32_t)c;
+                    step[ax] = d[ax] > 0.0 ? 1 : (d[ax] < 0.0 ? -1 : 0);
+                }
+                double t_enter = t_near;
+                // the previous stretch's box; none yet: empty whatever the sign of the grid's cell coordinates
+                int32_t plo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, phi[3] = {INT32_MIN, INT32_MIN, INT32_MIN};
+                for (;;) {
+                    if (t_enter > best.t) // strict: a tie later on can still win on the smaller index
+                        break;
+                    // when the centre leaves this cell: the nearest face ahead, each face's t from its own coordinate
+                    double t_next = INFINITY;
+                    int axis = -1;
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax)
+                        if (step[ax] != 0) {
+                            const double face = (double)(cell[ax] + (step[ax] > 0 ? 1 : 0)) * g.edge;
+                            const double ta = (face - o[ax]) / d[ax];
+                            if (ta < t_next) {
+                                t_next = ta;
+                                axis = ax;
+                            }
+                        }
+                    const double t_leave = t_next < t_far ? t_next : t_far;
+                    // the box of cells the sphere covers while its centre runs over [t_enter, t_leave]
+                    int32_t qlo[3];
+                    uint32_t qdim[3];
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        const double p0 = d[ax] == 0.0 ? o[ax] : o[ax] + t_enter * d[ax], p1 = d[ax] == 0.0 ? o[ax] : o[ax] + t_leave * d[ax];
+                        const double c_min = p0 < p1 ? p0 : p1, c_max = p0 < p1 ? p1 : p0;
+                        qlo[ax] = clamp_axis(g, ax, floor((c_min - rq - g.pad) / g.edge));
+                        const int32_t hi = clamp_axis(g, ax, floor((c_max + rq + g.pad) / g.edge));
+                        qdim[ax] = (uint32_t)(hi - qlo[ax]) + 1u;
+                    }
+                    const uint32_t cells = qdim[0] * qdim[1] * qdim[2];
+                    uint32_t next = lane, at = 0, end = 0, first = 0;
+                    int32_t cc[3] = {0, 0, 0};
+                    for (;;) {
+                        uint32_t mine = kNoBody;
+                        while (mine == kNoBody) {
+                            if (at == end) { // this lane's next cell
+                                if (next >= cells)
+                                    break;
+                                const uint32_t zy = next / qdim[0];
+                                cc[0] = qlo[0] + (int32_t)(next - zy * qdim[0]);
+                                cc[1] = qlo[1] + (int32_t)(zy % qdim[1]);
+                                cc[2] = qlo[2] + (int32_t)(zy / qdim[1]);
+                                next += L;
+                                const uint32_t key = query_key(g, cc[0], cc[1], cc[2]);
+                                first = at = a.cell_start[key];
+                                end = a.cell_start[key + 1];
+                                continue;
+                            }
+                            const uint32_t slot = at++, i = a.items[slot];
+                            Vec3 cb;
+                            double rb;
+                            if (!admit(i, cb, rb))
+                                continue;
+                            // A body is listed in up to 8 cells: within this box the pair counts in ONE of them, as in the
+                            // overlap pass, and not at all if the previous segment's box held one of its cells -- the boxes
+                            // that meet a body's cells are consecutive segments (the centre moves one way on every axis), so
+                            // it was looked at then, with a t_cap no smaller than now.  A test too many would change nothing.
+                            const double c[3] = {cb.x, cb.y, cb.z};
+                            bool here = true, before = true;
+#pragma unroll
+                            for (int ax = 0; ax < 3; ++ax) {
+                                const int32_t lo = clamp_axis(g, ax, floor((c[ax] - rb - g.pad) / g.edge));
+                                int32_t hi = clamp_axis(g, ax, floor((c[ax] + rb + g.pad) / g.edge));
+                                hi = hi > lo + 1 ? lo + 1 : hi;
+                                here = here && cc[ax] == (lo > qlo[ax] ? lo : qlo[ax]) && cc[ax] <= hi;
+                                before = before && lo <= phi[ax] && hi >= plo[ax];
+                            }
+                            here = here && !before;
+                            if (here && !g.dense)
+                                for (uint32_t e = first; e < slot; ++e)
+                                    here = here && a.items[e] != i;
+                            if (here)
+                                mine = i;
+                        }
+                        if (!group_bits<L>(__ballot(mine != kNoBody)))
+                            break; // every lane has run out of cells
+                        decide(mine);
+                    }
+                    if (axis < 0 || t_next > t_far)
+                        break;
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        plo[ax] = qlo[ax];
+                        phi[ax] = qlo[ax] + (int32_t)qdim[ax] - 1;
+                    }
+                    cell[axis] += step[axis];
+                    t_enter = t_next;
+                }
+            }
+        }
+    }
+    if (lane != 0)
+        return;
+    xpbd_sweep_hit h;
+    h.body = best.id;
+    h.feature = 0;
+    h.face = XPBD_NO_HIT;
+    h.reserved = 0;
+    h.distance = INFINITY;
+    h.position[0] = h.position[1] = h.position[2] = 0.0;
+    h.normal[0] = h.normal[1] = h.normal[2] = 0.0;
+    if (best.id != XPBD_NO_HIT) {
+        h.distance = best.t;
+        const Vec3 p = sw.f.position + sw.d * best.t;
+        h.position[0] = p.x, h.position[1] = p.y, h.position[2] = p.z;
+        const uint32_t sb = b.shape_id[best.slot];
+        const ShapeDesc da = t.desc[sw.shape], db = t.desc[sb];
+        const uint32_t at = best.face;
+        if (at == kNoBody) {
+            h.feature = XPBD_SWEEP_INITIAL;
+        } else {
+            const Frame fb = body_frame(b, best.slot);
+            Vec3 n;
+            if (at < da.n_faces) {
+                const double *pl = t.planes + 4 * (size_t)(da.face0 + at);
+                h.feature = XPBD_FEATURE_FACE_A;
+                h.face = at;
+                n = -(sw.f.rotation * Vec3{pl[0], pl[1], pl[2]});
+            } else if (at < da.n_faces + db.n_faces) {
+                const double *pl = t.planes + 4 * (size_t)(db.face0 + (at - da.n_faces));
+                h.feature = XPBD_FEATURE_FACE_B;
+                h.face = at - da.n_faces;
+                n = fb.rotation * Vec3{pl[0], pl[1], pl[2]};
+            } else {
+                const uint32_t e = at - da.n_faces - db.n_faces, pair = e >> 1, i = pair / db.n_dirs, j = pair - i * db.n_dirs;
+                n = edge_axis_of_table(t, da, db, sw.f, fb, i, j);
+                h.feature = XPBD_FEATURE_EDGES;
+                n = (e & 1u) ? n : -n;
+            }
+            h.normal[0] = n.x, h.normal[1] = n.y, h.normal[2] = n.z;
+        }
+    }
+    a.hits[q] = h;
+}
+
 } // namespace
 
 QuerySizes query_scratch_bytes(uint32_t n, uint32_t n_rays, bool brute)
@@ -1015,6 +1468,30 @@ hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const ui
         if (!brute)
             hipLaunchKernelGGL(k_overlap_sort, dim3(n_queries), dim3(kBlock), 0, stream, offsets, static_cast<xpbd_overlap_hit *>(hits_v), cap);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_sweep(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *sweeps_v,
+                        uint32_t n_sweeps, bool masked, bool brute, const QueryScratch &s, void *hits_v, hipStream_t stream)
+{
+    if (n_sweeps == 0)
+        return hipSuccess;
+    brute = brute || b.n == 0;
+    const xpbd_sweep *sweeps = static_cast<const xpbd_sweep *>(sweeps_v);
+    launch_query_bodies(b, t, global_id, RayFilter{nullptr, 0u, 0u}, s, stream);
+    hipLaunchKernelGGL(k_sweep_queries, dim3(blocks_of(n_sweeps)), dim3(kBlock), 0, stream, sweeps, n_sweeps, t, s.qrec);
+    if (!brute)
+        if (hipError_t e = launch_query_grid(b, s, stream)) // the grid of a ray cast, by the same passes
+            return e;
+    const SweepArgs a{sweeps, s.qrec, s.rec, global_id, filter, static_cast<QueryGrid *>(s.grid), s.cell_start, s.items,
+                      static_cast<xpbd_sweep_hit *>(hits_v), n_sweeps, masked ? 1u : 0u, brute ? 1u : 0u};
+    // lanes per sweep and vertex capacity by the largest shape, as the overlap pass chooses them
+    if (t.max_verts <= 8 && t.max_faces <= 8)
+        hipLaunchKernelGGL((k_sweep_pass<16, 8>), dim3((n_sweeps + 3) / 4), dim3(64), 0, stream, b, t, a);
+    else if (t.max_verts <= 16)
+        hipLaunchKernelGGL((k_sweep_pass<32, 16>), dim3((n_sweeps + 1) / 2), dim3(64), 0, stream, b, t, a);
+    else
+        hipLaunchKernelGGL((k_sweep_pass<64, XPBD_MAX_SHAPE_VERTS>), dim3(n_sweeps), dim3(64), 0, stream, b, t, a);
     return hipGetLastError();
 }
 

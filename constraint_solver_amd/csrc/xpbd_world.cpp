@@ -1162,6 +1162,57 @@ int overlap_host(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_qu
     return XPBD_OK;
 }
 
+int check_sweep(const char *who, const QueryTarget &t, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, const void *hits, bool host)
+{
+    if (n_sweeps && (!sweeps || !hits))
+        return set_error(XPBD_E_INVALID, "%s: NULL sweeps or hits", who);
+    if (flags & ~(XPBD_SWEEP_BRUTE_FORCE | XPBD_SWEEP_MASKED))
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (!t.has_topology)
+        return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
+    for (uint32_t q = 0; host && q < n_sweeps; ++q)
+        if (sweeps[q].reserved)
+            return set_error(XPBD_E_INVALID, "%s: sweep %u has reserved = %u (must be 0)", who, q, sweeps[q].reserved);
+    if (t.n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    return XPBD_OK;
+}
+
+int sweep_enqueue(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *dev_hits,
+                  const uint32_t *dev_global_id)
+{
+    static_assert(sizeof(xpbd_sweep) == 104 && sizeof(xpbd_sweep_hit) == 72, "xpbd_sweep is 104 bytes, xpbd_sweep_hit 72");
+    if (n_sweeps == 0)
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    // (a shard without bodies takes the brute-force path too: every sweep misses, no grid to build)
+    const bool brute = (flags & XPBD_SWEEP_BRUTE_FORCE) || n_sweeps <= XPBD_SWEEP_BRUTE_FORCE_SWEEPS || w->n == 0;
+    const QuerySizes q = overlap_scratch_bytes(w->n, n_sweeps, brute); // a sweep's records are an overlap query's
+    XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
+    const bool masked = (flags & XPBD_SWEEP_MASKED) != 0;
+    XPBD_HIP_TRY(launch_sweep(w->arrays(), w->tables(), dev_global_id, masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr, dev_sweeps,
+                              n_sweeps, masked, brute, w->query.view(q.table_size), dev_hits, w->stream));
+    return XPBD_OK;
+}
+
+int sweep_host(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits, const uint32_t *dev_global_id)
+{
+    if (n_sweeps == 0)
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    SceneQueryScratch &s = w->query;
+    const size_t in_bytes = (size_t)n_sweeps * sizeof(xpbd_sweep), out_bytes = (size_t)n_sweeps * sizeof(xpbd_sweep_hit);
+    XPBD_HIP_TRY(s.reserve(QuerySizes{}, in_bytes, out_bytes, 0, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(s.in.ptr, sweeps, in_bytes, hipMemcpyHostToDevice, w->stream));
+    if (int rc = sweep_enqueue(w, s.in.as<xpbd_sweep>(), n_sweeps, flags, s.out.as<xpbd_sweep_hit>(), dev_global_id))
+        return rc;
+    XPBD_HIP_TRY(hipMemcpyAsync(hits, s.out.ptr, out_bytes, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    return XPBD_OK;
+}
+
 } // namespace xpbd
 
 extern "C" {
@@ -2350,7 +2401,7 @@ try {
 } XPBD_ABI_CATCH
 
 namespace {
-// The scene queries' argument checks (xpbd::check_raycast, xpbd::check_overlap) against one world.
+// The scene queries' argument checks (xpbd::check_raycast, xpbd::check_overlap, xpbd::check_sweep) against one world.
 xpbd::QueryTarget query_target(const xpbd_world *w)
 {
     return {w->has_topology, w->n, w->n_shapes, "xpbd_world_set_polytopes (set_shapes gives vertices only)"};
@@ -2419,6 +2470,24 @@ try {
     if (int rc = check_world_overlap("xpbd_world_overlap_device", w, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap, nullptr, false))
         return rc;
     return xpbd::overlap_enqueue(w, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap, nullptr);
+} XPBD_ABI_CATCH
+
+int xpbd_world_sweep(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_sweep: NULL world");
+    if (int rc = xpbd::check_sweep("xpbd_world_sweep", query_target(w), sweeps, n_sweeps, flags, hits, true))
+        return rc;
+    return xpbd::sweep_host(w, sweeps, n_sweeps, flags, hits, nullptr);
+} XPBD_ABI_CATCH
+
+int xpbd_world_sweep_device(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *dev_hits)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_sweep_device: NULL world");
+    if (int rc = xpbd::check_sweep("xpbd_world_sweep_device", query_target(w), dev_sweeps, n_sweeps, flags, dev_hits, false))
+        return rc;
+    return xpbd::sweep_enqueue(w, dev_sweeps, n_sweeps, flags, dev_hits, nullptr);
 } XPBD_ABI_CATCH
 
 int xpbd_selftest_div_sqrt(int32_t device, const double *a, const double *b, double *quotient, double *root,

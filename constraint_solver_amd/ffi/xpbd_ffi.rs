@@ -203,6 +203,40 @@ pub struct XpbdRayHit {
 pub const XPBD_OVERLAP_BRUTE_FORCE: u32 = 1;
 pub const XPBD_OVERLAP_MASKED: u32 = 2;
 
+pub const XPBD_SWEEP_INITIAL: u32 = 3;
+pub const XPBD_SWEEP_BRUTE_FORCE: u32 = 1;
+pub const XPBD_SWEEP_MASKED: u32 = 2;
+pub const XPBD_SWEEP_BRUTE_FORCE_SWEEPS: u32 = 8;
+
+/// xpbd_sweep (104 bytes): the convex volume `shape` at the frame {position, rotation {s, x, y, z}}, moved by t * direction for t in
+/// [0, max_distance]; ignore_body = XPBD_NO_HIT for none; mask is read with XPBD_SWEEP_MASKED only; reserved = 0
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdSweep {
+    pub position: [f64; 3],
+    pub rotation: [f64; 4],
+    pub direction: [f64; 3],
+    pub max_distance: f64,
+    pub shape: u32,
+    pub ignore_body: u32,
+    pub mask: u32,
+    pub reserved: u32,
+}
+
+/// xpbd_sweep_hit (72 bytes): the first body the volume hits (XPBD_NO_HIT: none) at t = distance; feature = XPBD_FEATURE_* (A = the
+/// volume, B = the body) or XPBD_SWEEP_INITIAL; position = the volume's frame position at the impact; normal out of the body
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdSweepHit {
+    pub body: u32,
+    pub feature: u32,
+    pub face: u32,
+    pub reserved: u32,
+    pub distance: f64,
+    pub position: [f64; 3],
+    pub normal: [f64; 3],
+}
+
 /// xpbd_overlap_query (72 bytes): a convex volume, shape `shape` of the polytope table at the frame {position, rotation {s, x, y, z}};
 /// ignore_body = XPBD_NO_HIT for none; mask is read with XPBD_OVERLAP_MASKED only; reserved = 0
 #[repr(C)]
@@ -413,6 +447,11 @@ extern "C" {
                                      dev_hits: *mut XpbdOverlapHit, cap: u32) -> c_int;
     pub fn xpbd_multi_world_overlap(mw: *mut XpbdMultiWorld, queries: *const XpbdOverlapQuery, n_queries: u32, flags: u32, offsets: *mut u32,
                                     hits: *mut XpbdOverlapHit, cap: u32, n_out: *mut u32) -> c_int;
+    pub fn xpbd_world_sweep(w: *mut XpbdWorld, sweeps: *const XpbdSweep, n_sweeps: u32, flags: u32, hits: *mut XpbdSweepHit) -> c_int;
+    pub fn xpbd_world_sweep_device(w: *mut XpbdWorld, dev_sweeps: *const XpbdSweep, n_sweeps: u32, flags: u32,
+                                   dev_hits: *mut XpbdSweepHit) -> c_int;
+    pub fn xpbd_multi_world_sweep(mw: *mut XpbdMultiWorld, sweeps: *const XpbdSweep, n_sweeps: u32, flags: u32,
+                                  hits: *mut XpbdSweepHit) -> c_int;
     pub fn xpbd_world_set_contact_report(w: *mut XpbdWorld, enable: u32) -> c_int;
     pub fn xpbd_world_contact_report_counts(w: *mut XpbdWorld, out: *mut u32) -> c_int;
     pub fn xpbd_world_download_pair_contacts(w: *mut XpbdWorld, pairs: *mut XpbdPairContact, pair_cap: u32, points: *mut XpbdContactPoint,

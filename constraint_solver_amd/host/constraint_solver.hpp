@@ -532,6 +532,13 @@ class BatchWorld {
             check(xpbd_world_overlap(w_, q, (uint32_t)queries.size(), flags, offsets.data(), hits.data(), total, &total));
         return {std::move(offsets), std::move(hits)};
     }
+    // the first body every convex volume hits when moved along its segment, at the current poses (include/xpbd.h, "Sweep queries")
+    std::vector<xpbd_sweep_hit> sweep(const std::vector<xpbd_sweep> &sweeps, uint32_t flags = 0)
+    {
+        std::vector<xpbd_sweep_hit> hits(sweeps.size());
+        check(xpbd_world_sweep(w_, sweeps.empty() ? nullptr : sweeps.data(), (uint32_t)sweeps.size(), flags, hits.empty() ? nullptr : hits.data()));
+        return hits;
+    }
     // collision filters, one per body (empty: every body {~0u, ~0u}); flags: XPBD_FILTER_JOINTED or 0.  Upload clears them.
     void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)
     {
@@ -679,6 +686,13 @@ class ShardedWorld {
         if (total)
             check(xpbd_multi_world_overlap(w_, q, (uint32_t)queries.size(), flags, offsets.data(), hits.data(), total, &total));
         return {std::move(offsets), std::move(hits)};
+    }
+    // the first body every convex volume hits when moved along its segment, bodies by global index; collective (include/xpbd.h, "Sweep queries")
+    std::vector<xpbd_sweep_hit> sweep(const std::vector<xpbd_sweep> &sweeps, uint32_t flags = 0)
+    {
+        std::vector<xpbd_sweep_hit> hits(sweeps.size());
+        check(xpbd_multi_world_sweep(w_, sweeps.empty() ? nullptr : sweeps.data(), (uint32_t)sweeps.size(), flags, hits.empty() ? nullptr : hits.data()));
+        return hits;
     }
     // collision filters of the whole world, global body order (not collective); upload clears them
     void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)

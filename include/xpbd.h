@@ -866,6 +866,100 @@ int  xpbd_multi_world_overlap(xpbd_multi_world *mw, const xpbd_overlap_query *qu
                               uint32_t *offsets, xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out);
 
 /* ---------------------------------------------------------------------------
+ * Sweep queries (EXTENSION): the first body each of a batch of convex volumes hits when it is moved along a segment, and
+ * when, at the bodies' current poses.  NOT in the reference.  A host asks to set a body down against a pile before it spawns
+ * it, for character and tool motion, for projectiles a ray is too thin for, for camera booms.
+ *
+ * Poses and frames.  The volume of sweep q is the convex polytope `shape` at the frame fa = {position, rotation}, translated
+ * by t * direction for t in [0, max_distance]; it does not rotate.  Distances are in units of |direction|, as for rays.
+ * Bodies stand still at the pose the other queries see.  The ground plane is not a body.
+ *
+ * One sweep against one body, with fb = Rigid::frame() of the body and d = direction.  World vertices aw = fa * a_v, bw =
+ * fb * b_v; in the other's local space a_in_b = inverse(fb) * aw, b_in_a = inverse(fa) * bw; d_a = inverse(fa).rotation * d,
+ * d_b = inverse(fb).rotation * d.  A list of linear constraints (s, v) -- "the separation along this axis at time t is
+ * s + t * v" -- is visited in this order:
+ *   1. every face k of the volume, local outward plane (n, disp), in face order:
+ *        s = min_v dot(n, b_in_a_v) - disp, v = -dot(n, d_a)
+ *   2. every face k of the body, in face order:
+ *        s = min_v dot(n, a_in_b_v) - disp, v = dot(n, d_b)
+ *   3. every pair q = i * n_dirs_b + j of unique edge directions (the first edge's v[e.1] - v[e.0] of every direction up to
+ *      sign, in edge order), ascending: n = normalized(cross(fa.rotation * dir_a_i, fb.rotation * dir_b_j)), skipped unless
+ *      all three components are finite; hiA, loA = max, min of dot(aw_v, n), hiB, loB the same over bw, w = dot(n, d); two
+ *      constraints: first (loB - hiA, -w), then (loA - hiB, w).
+ * (min and max: the first vertex's value, replaced by a later one that is smaller / larger.)  With t_lo = -inf, entering =
+ * none, t_hi = max_distance, every constraint follows the ray's rule:
+ *     s or v is NaN: the pair misses;
+ *     v < 0: t_k = (-s) / v, and if t_k > t_lo then t_lo = t_k, entering = this constraint (strict: the first maximum wins)
+ *     v > 0: t_k = (-s) / v, and if t_k < t_hi then t_hi = t_k
+ *     v = 0: the pair misses if s >= 0 (a volume sliding along a body in exact touch does not hit it: the overlap query's
+ *            ">= 0 is separated")
+ * t = (t_lo < 0) ? 0 : t_lo, and the pair hits iff t <= t_hi.  If t_lo < 0 the volume overlaps the body at the start:
+ * feature = XPBD_SWEEP_INITIAL, face = XPBD_NO_HIT, normal = (0,0,0).  Otherwise feature and normal come from `entering`; the
+ * normal is in world space and points out of the body towards the volume:
+ *     XPBD_FEATURE_FACE_A: face k of the volume, normal = -(fa.rotation * n_k);
+ *     XPBD_FEATURE_FACE_B: face k of the body, normal = fb.rotation * n_k;
+ *     XPBD_FEATURE_EDGES:  face = XPBD_NO_HIT, normal = -n if the first constraint of the pair entered, +n if the second.
+ * position = sweep.position + t * direction (per component): the frame position of the volume at the impact.  Quotients are
+ * correctly rounded f64 divisions, there is no fused multiply-add, dot, cross and normalized (v * (1 / sqrt(dot(v, v)))) are
+ * as everywhere else.  The half-spaces are those of the Minkowski difference of the two polytopes -- the body's faces, the
+ * volume's faces reversed, both signs of every edge-direction cross product; axes that are no face of it are supporting
+ * planes all the same and change nothing -- so the answer is exact up to rounding, without iteration.
+ *
+ * Per sweep the smallest t wins and equal t go to the smaller body index (in xpbd_multi_world_sweep: the caller's global
+ * index).  ignore_body is never hit; with XPBD_SWEEP_MASKED body b answers only if (group_b & mask) != 0 (bodies without
+ * filters are in group ~0u; without the flag no group is tested).  A body whose pose is not finite is never hit.  A sweep
+ * whose `shape` is outside the table, whose frame or direction has a NaN or infinite component, whose direction is zero or
+ * whose max_distance is negative or NaN hits nothing (the call still succeeds).  A miss is {XPBD_NO_HIT, 0, XPBD_NO_HIT, 0,
+ * +inf, zeros}.
+ *
+ * Errors (host variants, before any device work; the outputs are untouched): XPBD_E_INVALID for a NULL world, NULL sweeps /
+ * hits with n_sweeps > 0, unknown flags, a nonzero `reserved`, no polytopes set, no bodies resident.  n_sweeps == 0 is
+ * XPBD_OK.  A sweep changes no body, list, mask, report, history entry or plan: stepping after it gives the same bits as
+ * stepping without it.  Every mode accepts it.
+ *
+ * Method: the per-call grid of the ray casts; a group of lanes per sweep walks the cells of the volume's centre line as a ray
+ * does and, for the stretch of it inside one cell, tests the bodies listed in the cells the volume's bounding sphere covers
+ * meanwhile, until the next stretch starts beyond the best hit.  With XPBD_SWEEP_BRUTE_FORCE, or for at most
+ * XPBD_SWEEP_BRUTE_FORCE_SWEEPS sweeps, every body is looked at instead and no grid is built.  Same bits either way.
+ * ------------------------------------------------------------------------- */
+#define XPBD_SWEEP_INITIAL 3u             /* xpbd_sweep_hit.feature when the volume overlaps the body at t = 0 */
+#define XPBD_SWEEP_BRUTE_FORCE 1u         /* diagnostics: every sweep against every body, no grid */
+#define XPBD_SWEEP_MASKED 2u              /* test xpbd_sweep.mask against the bodies' filter groups */
+#define XPBD_SWEEP_BRUTE_FORCE_SWEEPS 8u  /* calls with at most this many sweeps take the brute-force path anyway */
+
+typedef struct xpbd_sweep {           /* 104 bytes */
+    double   position[3];             /* frame of the volume at t = 0: x_world = position + rotation * x_shape */
+    double   rotation[4];             /* {s, x, y, z}, taken as given (the caller keeps it a unit quaternion) */
+    double   direction[3];            /* need not be unit; distances are in units of |direction| */
+    double   max_distance;            /* may be +inf */
+    uint32_t shape;                   /* index into the table of xpbd_world_set_polytopes */
+    uint32_t ignore_body;             /* never hit (XPBD_NO_HIT: none) */
+    uint32_t mask;                    /* with XPBD_SWEEP_MASKED: body b answers only if (group_b & mask) != 0 */
+    uint32_t reserved;                /* must be 0 */
+} xpbd_sweep;
+
+typedef struct xpbd_sweep_hit {       /* 72 bytes */
+    uint32_t body;                    /* XPBD_NO_HIT: missed */
+    uint32_t feature;                 /* XPBD_FEATURE_* (A = the volume, B = the body) or XPBD_SWEEP_INITIAL */
+    uint32_t face;                    /* shape-local face of the volume (FACE_A) or the body (FACE_B); else XPBD_NO_HIT */
+    uint32_t reserved;                /* 0 */
+    double   distance;                /* t */
+    double   position[3];             /* sweep.position + t * direction: the volume's frame position at the impact */
+    double   normal[3];               /* world space, out of the body towards the volume; (0,0,0) for XPBD_SWEEP_INITIAL */
+} xpbd_sweep_hit;
+
+/* Host arrays; checks everything before any device work and waits for the result. */
+int  xpbd_world_sweep(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits);
+/* Device arrays; stream-ordered on the world's stream, returns before completion (it waits only when its scratch has to
+ * grow).  `reserved` is not checked. */
+int  xpbd_world_sweep_device(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps, uint32_t flags,
+                             xpbd_sweep_hit *dev_hits);
+/* Collective: every rank passes the same sweeps and gets all hits.  Every shard answers for the bodies it OWNS; body and
+ * ignore_body are global indices.  Same bits as one xpbd_world over the same bodies. */
+int  xpbd_multi_world_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags,
+                            xpbd_sweep_hit *hits);
+
+/* ---------------------------------------------------------------------------
  * Contact REPORTS (EXTENSION): which body pairs the contact pipeline of XPBD_MODE_CONTACTS found touching, with the
  * manifolds it solved, and which pairs began or ended touching.  NOT in the reference; its app draws the reference and
  * incident planes of `sat` into DebugLines (src/collision.rs:69, 87) and, commented out, the contact points (:97-108).
