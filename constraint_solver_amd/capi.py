@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "xpbd_world_download_neighbours", "xpbd_world_contacts_begin", "xpbd_world_contacts_substep",
     "xpbd_world_export_dynamic", "xpbd_world_import_dynamic", "xpbd_world_import_dynamic_rows", "xpbd_world_set_joints",
     "xpbd_world_set_joint_limits", "xpbd_multi_world_set_joint_limits",
+    "xpbd_world_set_joint_drives", "xpbd_multi_world_set_joint_drives",
     "xpbd_world_narrowphase_gjk", "xpbd_world_set_narrowphase",
     "xpbd_world_set_sat_schedule",
     "xpbd_world_edge_axes_separation",
@@ -105,11 +106,15 @@ class PolytopeDesc(C.Structure):
 # xpbd_joint as a numpy record (120 bytes)
 JOINT_DTYPE = np.dtype([("body_a", "<u4"), ("body_b", "<u4"), ("anchor_a", "<f8", (3,)), ("anchor_b", "<f8", (3,)),
                         ("distance", "<f8"), ("axis_a", "<f8", (3,)), ("axis_b", "<f8", (3,)), ("kind", "<u4"), ("reserved", "<u4")])
-JOINT_DISTANCE, JOINT_HINGE = 0, 1
+JOINT_DISTANCE, JOINT_HINGE, JOINT_SLIDER = 0, 1, 2
 # xpbd_joint_limit as a numpy record (72 bytes)
 JOINT_LIMIT_DTYPE = np.dtype([("joint", "<u4"), ("kind", "<u4"), ("ref_a", "<f8", (3,)), ("ref_b", "<f8", (3,)),
                               ("lower", "<f8"), ("upper", "<f8")])
-LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST = 0, 1, 2
+LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST, LIMIT_SLIDE = 0, 1, 2, 3
+# xpbd_joint_drive as a numpy record (80 bytes)
+JOINT_DRIVE_DTYPE = np.dtype([("joint", "<u4"), ("kind", "<u4"), ("ref_a", "<f8", (3,)), ("ref_b", "<f8", (3,)),
+                              ("target", "<f8"), ("compliance", "<f8"), ("max_force", "<f8")])
+DRIVE_ANGLE, DRIVE_ANGULAR_VELOCITY, DRIVE_POSITION, DRIVE_VELOCITY = 0, 1, 2, 3
 # xpbd_collision_filter as a numpy record (8 bytes): bodies i, j may touch iff group_i & mask_j and group_j & mask_i
 COLLISION_FILTER_DTYPE = np.dtype([("group", "<u4"), ("mask", "<u4")])
 FILTER_JOINTED = 1                # bodies joined by a joint never collide
@@ -326,6 +331,8 @@ def hip_lib():
         L.xpbd_world_set_joints.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.xpbd_world_set_joint_limits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.xpbd_multi_world_set_joint_limits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.xpbd_world_set_joint_drives.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.xpbd_multi_world_set_joint_drives.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.xpbd_world_contacts_begin.argtypes = [C.c_void_p, C.c_double]
         L.xpbd_world_contacts_substep.argtypes = [C.c_void_p, C.c_double]
         L.xpbd_world_export_dynamic.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -563,6 +570,11 @@ class World:
         """limits: JOINT_LIMIT_DTYPE records naming joints of the last set_joints (extension; empty clears them)."""
         lim = np.ascontiguousarray(limits, dtype=JOINT_LIMIT_DTYPE)
         _check(hip_lib().xpbd_world_set_joint_limits(self._h, lim.ctypes.data if lim.size else None, lim.size))
+
+    def set_joint_drives(self, drives):
+        """drives: JOINT_DRIVE_DTYPE records naming joints of the last set_joints (extension; empty clears them)."""
+        drv = np.ascontiguousarray(drives, dtype=JOINT_DRIVE_DTYPE)
+        _check(hip_lib().xpbd_world_set_joint_drives(self._h, drv.ctypes.data if drv.size else None, drv.size))
 
     def set_collision_filters(self, filters=None, flags=0):
         """filters: COLLISION_FILTER_DTYPE records, one per body of the last upload, or None for the default {~0, ~0}
@@ -875,6 +887,11 @@ class MultiWorld:
         """limits: JOINT_LIMIT_DTYPE records naming joints of the last upload by their global index (empty clears them)."""
         lim = np.ascontiguousarray(limits, dtype=JOINT_LIMIT_DTYPE)
         _check(hip_lib().xpbd_multi_world_set_joint_limits(self._h, lim.ctypes.data if lim.size else None, lim.size))
+
+    def set_joint_drives(self, drives):
+        """drives: JOINT_DRIVE_DTYPE records naming joints of the last upload by their global index (empty clears them)."""
+        drv = np.ascontiguousarray(drives, dtype=JOINT_DRIVE_DTYPE)
+        _check(hip_lib().xpbd_multi_world_set_joint_drives(self._h, drv.ctypes.data if drv.size else None, drv.size))
 
     def set_collision_filters(self, filters=None, flags=0):
         """World.set_collision_filters over the whole sharded world: n_global records in global body order (not collective)."""

@@ -22,6 +22,16 @@ struct JointLimit {
     double lower, upper;
 };
 
+// One extra term of a joint (k_joint_extras): an xpbd_joint_drive as it is (kind = XPBD_DRIVE_*), or the joint's
+// XPBD_LIMIT_SLIDE (kind = kExtraSlideLimit: target = lower, compliance = upper; refs and max_force unused).
+struct JointExtraItem {
+    uint32_t joint, kind;
+    double ref_a[3], ref_b[3];
+    double target, compliance, max_force;
+};
+constexpr uint32_t kExtraSlideLimit = 0x100u;
+constexpr uint32_t kJointExtraDoubles = 8; // a joint end's summed extra entries: dpos[3], drot[4] (s, x, y, z), count
+
 // The uniform grid of one broadphase (device, written by k_grid).
 struct GridInfo {
     double edge;        // cell edge = 2 * largest bounding radius
@@ -84,6 +94,17 @@ struct ContactBuffers {
     const double *restitution; // [n] coefficient of every body, in [0, 1]
     double ground_restitution; // ... and of the plane z = 0
     double bounce_threshold;   // a contact bounces only when it closed faster than this at the start of the substep
+    // sliders and joint drives (xpbd.h, XPBD_JOINT_SLIDER / XPBD_LIMIT_SLIDE / xpbd_joint_drive): NULL = none, no kernel of
+    // their own is launched and the pair solve loads nothing.  (Last again.)  k_joint_extras evaluates the extra entries of
+    // the joints extra_joints[0..n_extra_joints) once per substep and leaves their sums for the pair solve to add.
+    double *joint_extra;               // [2 * n_joints][kJointExtraDoubles] one record per entry of joint_list: the sum for that body
+                                       //   and joint; zero for a joint without extras.  (Indexed by the slot a body's loop is at
+                                       //   anyway: indexed by 2 * joint + end the 8-lane pair solve took two more VGPRs)
+    const uint32_t *extra_joints;      // [n_extra_joints] the joints with extras, ascending
+    const uint32_t *extra_slots;       // [2 * n_extra_joints] where in joint_list end a / end b of extra_joints[t] sits
+    const uint32_t *extra_off;         // [n_extra_joints + 1] CSR into extra_items: the SLIDE limit first, then the drives in the caller's order
+    const JointExtraItem *extra_items;
+    uint32_t n_extra_joints;
 };
 
 // Which bodies a per-body kernel of the pipeline works on.  Default: all of them.  The multi-GPU world (xpbd_multi.cpp) runs
@@ -128,6 +149,10 @@ hipError_t launch_pair_solve_derive(const BodyArrays &b, double *dyn_out, double
 hipError_t launch_pair_solve_integrate_ground(const BodyArrays &b, const ShapeTable &s, double h, const ContactBuffers &c,
                                               double *next_rec, uint32_t *last_mask, uint32_t *trace_masks, uint32_t trace_row,
                                               hipStream_t stream, const BodySubset &subset = BodySubset());
+
+// Sliders and joint drives (only when c.joint_extra is set): the extra entries of every listed joint from the records of this
+// substep, summed per joint end into c.joint_extra, which the pair-solve kernels of the same substep add.
+hipError_t launch_joint_extras(double h, const ContactBuffers &c, hipStream_t stream);
 
 // Restitution, the velocity pass after derive (only when c.restitution is set): `post` holds the 13 dynamic fields after derive
 // (the dyn_out of launch_pair_solve_derive; NOT b.dyn), `start` velocity and angular velocity at the start of the substep

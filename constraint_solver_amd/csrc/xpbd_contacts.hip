@@ -999,7 +999,9 @@ __device__ __forceinline__ BodyDynamic pair_solve_derive_body(const ContactBuffe
             const Vec3 p_other = Frame{frame_origin(other.pos, other.rot, other.com), other.rot} * anchor_other;
             const Vec3 difference = self_is_a ? p_other - p_self : p_self - p_other; // p_b - p_a
             const double dist = length(difference);
-            if (dist != 0.0) { // (coincident points: the reference's direction() would be NaN (K6); nothing to correct)
+            // (coincident points: the reference's direction() would be NaN (K6); nothing to correct.  A slider has no
+            // positional term: its anchor is held to the axis by k_joint_extras)
+            if (dist != 0.0 && jt.kind != XPBD_JOINT_SLIDER) {
                 const Vec3 dir = difference * (1.0 / dist);
                 const double w = generalized_inverse_mass(self, p_self, dir) + generalized_inverse_mass(other, p_other, dir);
                 const double lambda = (dist - jt.distance) / (w + compliance);
@@ -1010,7 +1012,7 @@ __device__ __forceinline__ BodyDynamic pair_solve_derive_body(const ContactBuffe
                 drot = drot + (0.5 * spin) * self.rot;
                 ++count;
             }
-            if (jt.kind == XPBD_JOINT_HINGE) {
+            if (jt.kind != XPBD_JOINT_DISTANCE) { // XPBD_JOINT_HINGE, XPBD_JOINT_SLIDER
                 // the angular term (oracle: accumulate_hinge): the joint's axes, unit vectors in the object space of a and b,
                 // are kept aligned; evaluated per body, 3-vectors selected by role as above
                 const Vec3 axis_self = self_is_a ? Vec3{jt.axis_a[0], jt.axis_a[1], jt.axis_a[2]} : Vec3{jt.axis_b[0], jt.axis_b[1], jt.axis_b[2]};
@@ -1032,6 +1034,15 @@ __device__ __forceinline__ BodyDynamic pair_solve_derive_body(const ContactBuffe
             }
             if (c.limit_off)
                 joint_limit_terms(c, c.joint_list[k], jt, self_is_a, self, other, compliance, drot, count);
+            if (c.joint_extra) { // the joint's extra entries for this end, summed by k_joint_extras into the record of this
+                                 // slot of the body's joint list (zero count: none; adding zeros could flip the sign of a zero)
+                const double *e = c.joint_extra + (size_t)k * kJointExtraDoubles;
+                if (e[7] != 0.0) {
+                    dpos = dpos + Vec3{e[0], e[1], e[2]};
+                    drot = drot + Quat{e[3], e[4], e[5], e[6]};
+                    count += (uint32_t)e[7];
+                }
+            }
         }
     }
 
@@ -1156,6 +1167,138 @@ __global__ void __launch_bounds__(kBlock, XPBD_PAIR_SOLVE_MIN_WAVES) k_pair_solv
         }
     }
     block_add_stats(sub == 0 ? touching : 0u, sub == 0 ? points : 0u, c.stats);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Per substep, per joint with extras: sliders and joint drives (include/xpbd.h, "SLIDERS and joint DRIVES").
+// ---------------------------------------------------------------------------------------------------
+// The summed extra entries of one joint end.
+struct ExtraSum {
+    Vec3 dpos{0.0, 0.0, 0.0};
+    Quat drot{0.0, 0.0, 0.0, 0.0};
+    uint32_t count = 0;
+};
+
+// One linear entry: the impulse +lambda n on a at p_a, -lambda n on b at p_b, applied as the positional term applies its own.
+__device__ __forceinline__ void extra_linear_entry(const PairBody &a, const PairBody &b, Vec3 p_a, Vec3 p_b, Vec3 n, double lambda, ExtraSum &sum_a,
+                                                   ExtraSum &sum_b)
+{
+    const Vec3 impulse_a = lambda * n, impulse_b = (-lambda) * n;
+    sum_a.dpos = sum_a.dpos + impulse_a * a.inv_mass;
+    sum_b.dpos = sum_b.dpos + impulse_b * b.inv_mass;
+    const Vec3 arm_a = p_a - (a.pos + a.com), arm_b = p_b - (b.pos + b.com);
+    const Quat spin_a = quat_sv(0.0, cross(a.inv_inertia * arm_a, impulse_a)), spin_b = quat_sv(0.0, cross(b.inv_inertia * arm_b, impulse_b));
+    sum_a.drot = sum_a.drot + (0.5 * spin_a) * a.rot;
+    sum_b.drot = sum_b.drot + (0.5 * spin_b) * b.rot;
+    ++sum_a.count;
+    ++sum_b.count;
+}
+
+// One angular entry: a turns by +lambda n, b by -lambda n, as a limit's entry does.
+__device__ __forceinline__ void extra_angular_entry(const PairBody &a, const PairBody &b, Vec3 n, double lambda, ExtraSum &sum_a, ExtraSum &sum_b)
+{
+    const Quat spin_a = quat_sv(0.0, a.inv_inertia * (lambda * n)), spin_b = quat_sv(0.0, b.inv_inertia * ((-lambda) * n));
+    sum_a.drot = sum_a.drot + (0.5 * spin_a) * a.rot;
+    sum_b.drot = sum_b.drot + (0.5 * spin_b) * b.rot;
+    ++sum_a.count;
+    ++sum_b.count;
+}
+
+__device__ __forceinline__ double wrap_angle(double x)
+{
+    const double pi = 3.14159265358979323846;
+    return x > pi ? x - 2.0 * pi : (x < -pi ? x + 2.0 * pi : x);
+}
+
+__device__ __forceinline__ void store_extra_sum(double *__restrict__ out, const ExtraSum &s)
+{
+    double2 *o = reinterpret_cast<double2 *>(out);
+    o[0] = double2{s.dpos.x, s.dpos.y};
+    o[1] = double2{s.dpos.z, s.drot.s};
+    o[2] = double2{s.drot.x, s.drot.y};
+    o[3] = double2{s.drot.z, (double)s.count};
+}
+
+// One lane per joint with extras.  Both ends are loaded from the records of this substep and every term is evaluated ONCE,
+// so both ends get the same phi, n and lambda; the two sums go to the records of the joint's two slots in the bodies' joint
+// lists (c.extra_slots), where the pair solve of the same substep picks them up.  Nothing here is read by another lane of the launch.
+__global__ void __launch_bounds__(kBlock) k_joint_extras(double h, ContactBuffers c)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= c.n_extra_joints)
+        return;
+    const uint32_t joint = c.extra_joints[t];
+    const Joint &jt = c.joints[joint];
+    const PairBody a = load_pair_body(c, jt.body_a), b = load_pair_body(c, jt.body_b);
+    const double hh = h * h;
+    const double compliance = 1e-6 / hh;
+    const Vec3 anchor_a{jt.anchor_a[0], jt.anchor_a[1], jt.anchor_a[2]}, anchor_b{jt.anchor_b[0], jt.anchor_b[1], jt.anchor_b[2]};
+    const Vec3 axis_a{jt.axis_a[0], jt.axis_a[1], jt.axis_a[2]};
+    const Vec3 p_a = Frame{frame_origin(a.pos, a.rot, a.com), a.rot} * anchor_a;
+    const Vec3 p_b = Frame{frame_origin(b.pos, b.rot, b.com), b.rot} * anchor_b;
+    const Vec3 d = p_b - p_a;
+    const Vec3 a_w = a.rot * axis_a;
+    const double s = dot(d, a_w);
+    ExtraSum sum_a, sum_b;
+
+    if (jt.kind == XPBD_JOINT_SLIDER) { // 1. the anchor of b is held to the axis of a
+        const Vec3 r = d - a_w * s;
+        const double len = length(r);
+        if (len != 0.0) {
+            const Vec3 n = r * (1.0 / len);
+            const double w = generalized_inverse_mass(a, p_a, n) + generalized_inverse_mass(b, p_b, n);
+            extra_linear_entry(a, b, p_a, p_b, n, len / (w + compliance), sum_a, sum_b);
+        }
+    }
+    const uint32_t k_end = c.extra_off[t + 1];
+    for (uint32_t k = c.extra_off[t]; k < k_end; ++k) { // 2. the SLIDE limit, 3. the drives in the caller's order
+        const JointExtraItem &it = c.extra_items[k];
+        const bool angular = it.kind == XPBD_DRIVE_ANGLE || it.kind == XPBD_DRIVE_ANGULAR_VELOCITY;
+        double err, w;
+        if (angular) {
+            const Vec3 ref_a{it.ref_a[0], it.ref_a[1], it.ref_a[2]}, ref_b{it.ref_b[0], it.ref_b[1], it.ref_b[2]};
+            const Vec3 r_a = a.rot * ref_a, r_b = b.rot * ref_b;
+            const double phi = atan2(dot(cross(r_a, r_b), a_w), dot(r_a, r_b)); // as XPBD_LIMIT_HINGE
+            if (it.kind == XPBD_DRIVE_ANGLE) {
+                err = wrap_angle(phi - it.target);
+            } else { // the same angle at the start of the substep
+                const Vec3 a_w0 = a.past.rotation * axis_a;
+                const Vec3 r_a0 = a.past.rotation * ref_a, r_b0 = b.past.rotation * ref_b;
+                const double phi0 = atan2(dot(cross(r_a0, r_b0), a_w0), dot(r_a0, r_b0));
+                err = wrap_angle(phi - phi0) - it.target * h;
+            }
+            const Vec3 n_a = conjugate(a.rot) * a_w, n_b = conjugate(b.rot) * a_w;
+            w = dot(a.inv_inertia * n_a, n_a) + dot(b.inv_inertia * n_b, n_b);
+        } else {
+            if (it.kind == kExtraSlideLimit) {
+                const double clamped = s < it.target ? it.target : (s > it.compliance ? it.compliance : s); // lower, upper
+                err = s - clamped;
+            } else if (it.kind == XPBD_DRIVE_POSITION) {
+                err = s - it.target;
+            } else { // XPBD_DRIVE_VELOCITY: the same offset at the start of the substep
+                const Vec3 d0 = b.past * anchor_b - a.past * anchor_a;
+                const double s0 = dot(d0, a.past.rotation * axis_a);
+                err = (s - s0) - it.target * h;
+            }
+            w = generalized_inverse_mass(a, p_a, a_w) + generalized_inverse_mass(b, p_b, a_w);
+        }
+        if (err == 0.0)
+            continue;
+        double lambda;
+        if (it.kind == kExtraSlideLimit) {
+            lambda = err / (w + compliance);
+        } else {
+            lambda = err / (w + (1e-6 + it.compliance) / hh);
+            const double cap = it.max_force * hh;
+            lambda = lambda > cap ? cap : (lambda < -cap ? -cap : lambda);
+        }
+        if (angular)
+            extra_angular_entry(a, b, a_w, lambda, sum_a, sum_b);
+        else
+            extra_linear_entry(a, b, p_a, p_b, a_w, lambda, sum_a, sum_b);
+    }
+    store_extra_sum(c.joint_extra + (size_t)c.extra_slots[2 * t + 0] * kJointExtraDoubles, sum_a);
+    store_extra_sum(c.joint_extra + (size_t)c.extra_slots[2 * t + 1] * kJointExtraDoubles, sum_b);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1704,6 +1847,14 @@ hipError_t launch_pair_solve_derive(const BodyArrays &b, double *dyn_out, double
         launch(One{}, std::true_type{});
     else
         launch(One{}, std::false_type{});
+    return hipGetLastError();
+}
+
+hipError_t launch_joint_extras(double h, const ContactBuffers &c, hipStream_t stream)
+{
+    if (!c.joint_extra || c.n_extra_joints == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_joint_extras, dim3(blocks_for(c.n_extra_joints)), dim3(kBlock), 0, stream, h, c);
     return hipGetLastError();
 }
 

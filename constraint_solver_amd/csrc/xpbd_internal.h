@@ -106,6 +106,7 @@ struct HaloLists {
 struct xpbd_world;
 struct xpbd_joint;
 struct xpbd_joint_limit;
+struct xpbd_joint_drive;
 struct xpbd_material;
 struct xpbd_ray;
 struct xpbd_impulse;
@@ -189,6 +190,8 @@ int report_shard(xpbd_world *w, const uint8_t *dev_owned, const uint32_t *dev_gl
 // joint list (XPBD_E_INVALID with a message naming `who`).
 int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies);
 int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits);
+// ... of xpbd_world_set_joint_drives against a joint list.
+int check_joint_drives(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_drive *drives, uint32_t n_drives);
 // ... of a per-body array (`what`) handed to a world of n_bodies bodies: NULL only with n == 0 (the default), else n == n_bodies.
 // `count`: what the caller's interface calls n.
 int check_per_body(const char *who, const char *what, const void *values, uint32_t n, uint32_t n_bodies, const char *count = "n");

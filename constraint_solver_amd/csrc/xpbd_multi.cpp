@@ -185,6 +185,7 @@ struct xpbd_multi_world {
     uint32_t n_global = 0, first_global = 0, n_bodies = 0, capacity = 1;
     std::vector<xpbd_joint> joints;
     std::vector<xpbd_joint_limit> limits; // xpbd_multi_world_set_joint_limits: GLOBAL joint indices
+    std::vector<xpbd_joint_drive> drives; // xpbd_multi_world_set_joint_drives: GLOBAL joint indices
     std::vector<xpbd_collision_filter> filters; // xpbd_multi_world_set_collision_filters: [n_global] or empty (none)
     uint32_t filter_flags = 0;
     std::vector<xpbd_material> materials; // xpbd_multi_world_set_materials: [n_global] or empty (every body +inf)
@@ -577,6 +578,21 @@ int push_joint_limits(const xpbd_multi_world *mw, const Shard &s, const std::vec
     return xpbd_world_set_joint_limits(s.world, local.data(), (uint32_t)local.size());
 }
 
+// ... and the joint drives, the same way.
+int push_joint_drives(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &)
+{
+    std::vector<xpbd_joint_drive> local;
+    for (const xpbd_joint_drive &d : mw->drives) {
+        const auto at = std::lower_bound(s.joint_ids.begin(), s.joint_ids.end(), d.joint);
+        if (at != s.joint_ids.end() && *at == d.joint) {
+            xpbd_joint_drive m = d;
+            m.joint = (uint32_t)(at - s.joint_ids.begin());
+            local.push_back(m);
+        }
+    }
+    return xpbd_world_set_joint_drives(s.world, local.data(), (uint32_t)local.size());
+}
+
 int push_collision_filters(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &local_ids)
 {
     const std::vector<xpbd_collision_filter> local = local_rows(mw->filters, local_ids);
@@ -592,7 +608,7 @@ int push_materials(const xpbd_multi_world *mw, const Shard &s, const std::vector
 // Every body-indexed setting of the world on shard s (its joints are set: the limits name them).  A new setting is added here.
 int push_body_settings(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &local_ids)
 {
-    for (PushSetting push : {push_joint_limits, push_collision_filters, push_materials})
+    for (PushSetting push : {push_joint_limits, push_joint_drives, push_collision_filters, push_materials})
         XPBD_TRY(push(mw, s, local_ids));
     return XPBD_OK;
 }
@@ -1824,6 +1840,15 @@ try {
     return push_to_shards(mw, push_joint_limits, "joint limits");
 } XPBD_MULTI_ABI_CATCH
 
+int xpbd_multi_world_set_joint_drives(xpbd_multi_world *mw, const xpbd_joint_drive *drives, uint32_t n_drives)
+try {
+    XPBD_TRY(check_usable(mw, "xpbd_multi_world_set_joint_drives"));
+    if (int rc = xpbd::check_joint_drives("xpbd_multi_world_set_joint_drives", mw->joints.data(), (uint32_t)mw->joints.size(), drives, n_drives))
+        return rc;
+    mw->drives.assign(drives, drives + n_drives);
+    return push_to_shards(mw, push_joint_drives, "joint drives");
+} XPBD_MULTI_ABI_CATCH
+
 int xpbd_multi_world_set_collision_filters(xpbd_multi_world *mw, const xpbd_collision_filter *filters, uint32_t n_global, uint32_t flags)
 try {
     XPBD_TRY(check_usable(mw, "xpbd_multi_world_set_collision_filters"));
@@ -1939,7 +1964,8 @@ try {
     XPBD_TRY(xpbd::check_joints("xpbd_multi_world_upload", joints, n_joints, n_global));
     mw->n_global = n_global, mw->first_global = first_global, mw->n_bodies = n_bodies;
     mw->joints.assign(joints, joints + n_joints);
-    mw->limits.clear(); // limits name joints by index: a new upload invalidates them
+    mw->limits.clear(); // limits and drives name joints by index: a new upload invalidates them
+    mw->drives.clear();
     mw->filters.clear(); // filters name bodies by index
     mw->filter_flags = 0;
     mw->materials.clear(); // and so do materials

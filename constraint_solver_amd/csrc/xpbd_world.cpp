@@ -109,12 +109,17 @@ struct xpbd_world {
     bool frame_snapshot_valid = false, frame_snapshot_stepped = false;
     // Body-indexed settings: each names bodies (or the joints between them) by index, so a new set of bodies clears all four
     // (adopt_body_count).  Plain values whose clear() restores the defaults; their device tables stay allocated beside them.
-    struct Joints { // xpbd_world_set_joints, xpbd_world_set_joint_limits (limits name joints by index: new joints drop them)
-        uint32_t n = 0, n_limits = 0;
+    struct Joints { // xpbd_world_set_joints, xpbd_world_set_joint_limits, xpbd_world_set_joint_drives (limits and drives name
+                    // joints by index: new joints drop them)
+        uint32_t n = 0, n_limits = 0; // n_limits: the ANGULAR limits, the table the pair solve walks
+        uint32_t n_extra_joints = 0;  // joints with extra entries (sliders, SLIDE limits, drives): the lanes of k_joint_extras
         std::vector<xpbd_joint> host; // the joints of the last set_joints: what xpbd_world_set_joint_limits checks against
+        std::vector<xpbd_joint_limit> slide_limits; // the XPBD_LIMIT_SLIDE limits of the last set_joint_limits
+        std::vector<xpbd_joint_drive> drives;       // the drives of the last set_joint_drives, the caller's order
         void clear() { *this = Joints{}; }
     } joints;
     DeviceBuffer jt_joints, jt_off, jt_list, jt_limits, jt_limit_off;
+    DeviceBuffer jt_extra, jt_extra_joints, jt_extra_slots, jt_extra_off, jt_extra_items; // ContactBuffers::joint_extra, extra_*
     struct Filters { // xpbd_world_set_collision_filters: group, mask per body (on), XPBD_FILTER_* flags
         bool on = false;
         uint32_t flags = 0;
@@ -215,6 +220,12 @@ struct xpbd_world {
         c.restitution = restitution.on ? rs_restitution.as<double>() : nullptr;
         c.ground_restitution = restitution.ground;
         c.bounce_threshold = restitution.bounce_threshold;
+        c.joint_extra = joints.n_extra_joints ? jt_extra.as<double>() : nullptr;
+        c.extra_joints = joints.n_extra_joints ? jt_extra_joints.as<uint32_t>() : nullptr;
+        c.extra_slots = joints.n_extra_joints ? jt_extra_slots.as<uint32_t>() : nullptr;
+        c.extra_off = joints.n_extra_joints ? jt_extra_off.as<uint32_t>() : nullptr;
+        c.extra_items = joints.n_extra_joints ? jt_extra_items.as<xpbd::JointExtraItem>() : nullptr;
+        c.n_extra_joints = joints.n_extra_joints;
         return c;
     }
 
@@ -557,6 +568,7 @@ int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_ro
     XPBD_HIP_TRY(xpbd::launch_integrate_ground(b, w->shapes(), h, c, w->last_mask.as<uint32_t>(), trace, trace_row, w->stream));
     if (int rc = narrowphase_contacts(w, b, c))
         return rc;
+    XPBD_HIP_TRY(xpbd::launch_joint_extras(h, c, w->stream));
     if (!c.restitution) {
         XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream));
         return XPBD_OK;
@@ -593,6 +605,7 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         const xpbd::ContactBuffers c = w->contact_buffers(k & 1u);
         if (int rc = narrowphase_contacts(w, b, c))
             return rc;
+        XPBD_HIP_TRY(xpbd::launch_joint_extras(h, c, w->stream));
         if (k + 1 < substeps) {
             const xpbd::ContactBuffers next = w->contact_buffers((k + 1u) & 1u);
             XPBD_HIP_TRY(xpbd::launch_pair_solve_integrate_ground(b, w->shapes(), h, c, next.rec, w->last_mask.as<uint32_t>(), trace,
@@ -702,6 +715,7 @@ int halo_substep_boundary(xpbd_world *w, double h, uint32_t k, bool last, const 
         return rc;
     if (int rc = narrowphase_contacts(w, w->arrays(), w->contact_buffers(k & 1u)))
         return rc;
+    XPBD_HIP_TRY(launch_joint_extras(h, w->contact_buffers(k & 1u), w->stream)); // every record of substep k is complete, ghosts included
     BodySubset subset;
     subset.list = l.boundary;
     subset.count = l.n_boundary;
@@ -912,15 +926,17 @@ int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, u
             return set_error(XPBD_E_INVALID, "%s: joint %u links bodies %u and %u of %u", who, k, j.body_a, j.body_b, n_bodies);
         if (!(j.distance >= 0.0) || !(j.distance <= 1.0e300))
             return set_error(XPBD_E_INVALID, "%s: joint %u has distance %g", who, k, j.distance);
-        if (j.kind != XPBD_JOINT_DISTANCE && j.kind != XPBD_JOINT_HINGE)
+        if (j.kind != XPBD_JOINT_DISTANCE && j.kind != XPBD_JOINT_HINGE && j.kind != XPBD_JOINT_SLIDER)
             return set_error(XPBD_E_INVALID, "%s: joint %u has unknown kind %u", who, k, j.kind);
+        if (j.kind == XPBD_JOINT_SLIDER && j.distance != 0.0)
+            return set_error(XPBD_E_INVALID, "%s: slider %u needs distance 0 (got %g)", who, k, j.distance);
         if (j.reserved != 0)
             return set_error(XPBD_E_INVALID, "%s: joint %u: reserved must be 0", who, k);
-        if (j.kind == XPBD_JOINT_HINGE)
+        if (j.kind == XPBD_JOINT_HINGE || j.kind == XPBD_JOINT_SLIDER)
             for (const double *axis : {j.axis_a, j.axis_b}) {
                 const double len2 = axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2];
                 if (!(len2 > 0.999 && len2 < 1.001))
-                    return set_error(XPBD_E_INVALID, "%s: hinge %u needs unit axes (|axis|^2 = %g)", who, k, len2);
+                    return set_error(XPBD_E_INVALID, "%s: %s %u needs unit axes (|axis|^2 = %g)", who, j.kind == XPBD_JOINT_HINGE ? "hinge" : "slider", k, len2);
             }
     }
     return XPBD_OK;
@@ -966,8 +982,11 @@ int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joi
             return set_error(XPBD_E_INVALID, "%s: limit %u names joint %u of %u", who, k, l.joint, n_joints);
         const xpbd_joint &j = joints[l.joint];
         if (l.kind == XPBD_LIMIT_HINGE) {
-            if (j.kind != XPBD_JOINT_HINGE)
+            if (j.kind != XPBD_JOINT_HINGE && j.kind != XPBD_JOINT_SLIDER)
                 return set_error(XPBD_E_INVALID, "%s: limit %u is a HINGE limit on joint %u of kind %u", who, k, l.joint, j.kind);
+        } else if (l.kind == XPBD_LIMIT_SLIDE) {
+            if (j.kind != XPBD_JOINT_SLIDER)
+                return set_error(XPBD_E_INVALID, "%s: limit %u is a SLIDE limit on joint %u of kind %u", who, k, l.joint, j.kind);
         } else if (l.kind == XPBD_LIMIT_SWING || l.kind == XPBD_LIMIT_TWIST) {
             if (j.kind != XPBD_JOINT_DISTANCE)
                 return set_error(XPBD_E_INVALID, "%s: limit %u (kind %u) needs a DISTANCE joint, joint %u is of kind %u", who, k, l.kind, l.joint, j.kind);
@@ -979,6 +998,11 @@ int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joi
         if (kinds_seen[l.joint] & (1u << l.kind))
             return set_error(XPBD_E_INVALID, "%s: joint %u has two limits of kind %u", who, l.joint, l.kind);
         kinds_seen[l.joint] |= (uint8_t)(1u << l.kind);
+        if (l.kind == XPBD_LIMIT_SLIDE) { // metres: finite, lower <= upper; the references are not read
+            if (!(l.lower <= l.upper) || !std::isfinite(l.lower) || !std::isfinite(l.upper))
+                return set_error(XPBD_E_INVALID, "%s: slide limit %u has bounds [%g, %g] (need finite lower <= upper)", who, k, l.lower, l.upper);
+            continue;
+        }
         if (l.kind != XPBD_LIMIT_SWING) {
             if (!unit(l.ref_a) || !unit(l.ref_b))
                 return set_error(XPBD_E_INVALID, "%s: limit %u needs unit references", who, k);
@@ -989,6 +1013,52 @@ int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joi
             return set_error(XPBD_E_INVALID, "%s: limit %u has bounds [%g, %g] (need -pi <= lower <= upper <= pi)", who, k, l.lower, l.upper);
         if (l.kind == XPBD_LIMIT_SWING && l.lower != 0.0)
             return set_error(XPBD_E_INVALID, "%s: swing limit %u needs lower = 0 (got %g)", who, k, l.lower);
+    }
+    return XPBD_OK;
+}
+
+int check_joint_drives(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_drive *drives, uint32_t n_drives)
+{
+    static_assert(sizeof(xpbd_joint_drive) == 80 && sizeof(xpbd_joint_drive) == sizeof(JointExtraItem), "xpbd_joint_drive must mirror xpbd::JointExtraItem");
+    if (n_drives && !drives)
+        return set_error(XPBD_E_INVALID, "%s: NULL argument", who);
+    auto unit = [](const double *v) {
+        const double len2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+        return len2 > 0.999 && len2 < 1.001; // the limits' tolerances (check_joint_limits)
+    };
+    auto perpendicular = [](const double *v, const double *axis) {
+        const double d = v[0] * axis[0] + v[1] * axis[1] + v[2] * axis[2];
+        return d > -1e-3 && d < 1e-3;
+    };
+    std::vector<uint8_t> seen(n_joints, 0); // bit 0: an angular drive, bit 1: a linear one
+    for (uint32_t k = 0; k < n_drives; ++k) {
+        const xpbd_joint_drive &d = drives[k];
+        if (d.joint >= n_joints)
+            return set_error(XPBD_E_INVALID, "%s: drive %u names joint %u of %u", who, k, d.joint, n_joints);
+        const xpbd_joint &j = joints[d.joint];
+        const bool angular = d.kind == XPBD_DRIVE_ANGLE || d.kind == XPBD_DRIVE_ANGULAR_VELOCITY;
+        if (!angular && d.kind != XPBD_DRIVE_POSITION && d.kind != XPBD_DRIVE_VELOCITY)
+            return set_error(XPBD_E_INVALID, "%s: drive %u has unknown kind %u", who, k, d.kind);
+        if (angular ? (j.kind != XPBD_JOINT_HINGE && j.kind != XPBD_JOINT_SLIDER) : j.kind != XPBD_JOINT_SLIDER)
+            return set_error(XPBD_E_INVALID, "%s: drive %u (kind %u) does not fit joint %u of kind %u", who, k, d.kind, d.joint, j.kind);
+        const uint8_t bit = angular ? 1u : 2u;
+        if (seen[d.joint] & bit)
+            return set_error(XPBD_E_INVALID, "%s: joint %u has two %s drives", who, d.joint, angular ? "angular" : "linear");
+        seen[d.joint] |= bit;
+        if (angular) {
+            if (!unit(d.ref_a) || !unit(d.ref_b))
+                return set_error(XPBD_E_INVALID, "%s: drive %u needs unit references", who, k);
+            if (!perpendicular(d.ref_a, j.axis_a) || !perpendicular(d.ref_b, j.axis_b))
+                return set_error(XPBD_E_INVALID, "%s: drive %u: a reference is not perpendicular to its axis", who, k);
+        }
+        if (!std::isfinite(d.target))
+            return set_error(XPBD_E_INVALID, "%s: drive %u has target %g", who, k, d.target);
+        if (d.kind == XPBD_DRIVE_ANGLE && !(d.target >= -M_PI && d.target <= M_PI))
+            return set_error(XPBD_E_INVALID, "%s: angle drive %u has target %g (need -pi <= target <= pi)", who, k, d.target);
+        if (!(d.compliance >= 0.0) || !std::isfinite(d.compliance))
+            return set_error(XPBD_E_INVALID, "%s: drive %u has compliance %g (need finite, >= 0)", who, k, d.compliance);
+        if (!(d.max_force > 0.0)) // (NaN fails the comparison; +inf passes)
+            return set_error(XPBD_E_INVALID, "%s: drive %u has max_force %g (need > 0, +inf allowed)", who, k, d.max_force);
     }
     return XPBD_OK;
 }
@@ -1763,6 +1833,72 @@ try {
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
+namespace {
+// The table k_joint_extras walks, from the world's joints, SLIDE limits and drives: the joints that have extra entries
+// (ascending) and, per joint, its SLIDE limit followed by its drives in the caller's order.  The per-end sums start as zeros,
+// which is what the pair solve reads for a joint that is not listed.  The device is bound and the stream idle.
+int upload_joint_extras(xpbd_world *w)
+{
+    xpbd_world::Joints &J = w->joints;
+    J.n_extra_joints = 0; // (a failed copy below leaves none rather than a torn table)
+    std::vector<uint32_t> count(J.n, 0);
+    std::vector<uint8_t> listed(J.n, 0);
+    for (uint32_t j = 0; j < J.n; ++j)
+        listed[j] = J.host[j].kind == XPBD_JOINT_SLIDER;
+    for (const xpbd_joint_limit &l : J.slide_limits)
+        ++count[l.joint], listed[l.joint] = 1;
+    for (const xpbd_joint_drive &d : J.drives)
+        ++count[d.joint], listed[d.joint] = 1;
+    std::vector<uint32_t> list, off(1, 0), first(J.n, 0);
+    for (uint32_t j = 0; j < J.n; ++j)
+        if (listed[j]) {
+            list.push_back(j);
+            first[j] = off.back();
+            off.push_back(off.back() + count[j]);
+        }
+    if (list.empty())
+        return XPBD_OK;
+    // where the two ends of a listed joint sit in the bodies' joint lists (the CSR of xpbd_world_set_joints)
+    std::vector<uint32_t> slot_cursor((size_t)w->n + 1, 0), slots(2 * list.size());
+    for (const xpbd_joint &j : J.host) {
+        ++slot_cursor[j.body_a + 1];
+        ++slot_cursor[j.body_b + 1];
+    }
+    for (uint32_t i = 0; i < w->n; ++i)
+        slot_cursor[i + 1] += slot_cursor[i];
+    for (uint32_t j = 0, t = 0; j < J.n; ++j) {
+        const uint32_t slot_a = slot_cursor[J.host[j].body_a]++, slot_b = slot_cursor[J.host[j].body_b]++;
+        if (listed[j]) {
+            slots[2 * t] = slot_a, slots[2 * t + 1] = slot_b;
+            ++t;
+        }
+    }
+    std::vector<xpbd::JointExtraItem> items(std::max<size_t>(off.back(), 1));
+    std::vector<uint32_t> cursor = first;
+    for (const xpbd_joint_limit &l : J.slide_limits) {
+        xpbd::JointExtraItem it{};
+        it.joint = l.joint, it.kind = xpbd::kExtraSlideLimit, it.target = l.lower, it.compliance = l.upper;
+        items[cursor[l.joint]++] = it;
+    }
+    for (const xpbd_joint_drive &d : J.drives)
+        std::memcpy(&items[cursor[d.joint]++], &d, sizeof d);
+    const size_t sums = (size_t)2 * J.n * xpbd::kJointExtraDoubles * 8;
+    XPBD_HIP_TRY(w->jt_extra.reserve(sums));
+    XPBD_HIP_TRY(w->jt_extra_joints.reserve(list.size() * 4));
+    XPBD_HIP_TRY(w->jt_extra_slots.reserve(slots.size() * 4));
+    XPBD_HIP_TRY(w->jt_extra_off.reserve(off.size() * 4));
+    XPBD_HIP_TRY(w->jt_extra_items.reserve(items.size() * sizeof(xpbd::JointExtraItem)));
+    XPBD_HIP_TRY(hipMemsetAsync(w->jt_extra.ptr, 0, sums, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // (the world's stream may be another one by the time the table is read)
+    XPBD_HIP_TRY(hipMemcpy(w->jt_extra_joints.ptr, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+    XPBD_HIP_TRY(hipMemcpy(w->jt_extra_slots.ptr, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
+    XPBD_HIP_TRY(hipMemcpy(w->jt_extra_off.ptr, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    XPBD_HIP_TRY(hipMemcpy(w->jt_extra_items.ptr, items.data(), items.size() * sizeof(xpbd::JointExtraItem), hipMemcpyHostToDevice));
+    J.n_extra_joints = (uint32_t)list.size();
+    return XPBD_OK;
+}
+} // namespace
+
 int xpbd_world_set_joints(xpbd_world *w, const xpbd_joint *joints, uint32_t n_joints)
 try {
     static_assert(sizeof(xpbd_joint) == sizeof(xpbd::Joint), "xpbd_joint must mirror xpbd::Joint");
@@ -1797,7 +1933,7 @@ try {
     XPBD_HIP_TRY(hipMemcpy(w->jt_list.ptr, list.data(), (size_t)2 * n_joints * 4, hipMemcpyHostToDevice));
     w->joints.n = n_joints;
     w->joints.host.assign(joints, joints + n_joints);
-    return XPBD_OK;
+    return upload_joint_extras(w); // (a slider has an extra entry of its own)
 } XPBD_ABI_CATCH
 
 int xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, uint32_t n_limits)
@@ -1808,21 +1944,34 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_limits: limits need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
     if (int rc = xpbd::check_joint_limits("xpbd_world_set_joint_limits", w->joints.host.data(), w->joints.n, limits, n_limits))
         return rc;
-    // CSR joint -> limits, the caller's order inside a joint
-    std::vector<uint32_t> off((size_t)w->joints.n + 1, 0);
+    // the SLIDE limits are entries of k_joint_extras, not of the pair solve's table
+    std::vector<xpbd_joint_limit> slide;
     for (uint32_t k = 0; k < n_limits; ++k)
-        ++off[limits[k].joint + 1];
+        if (limits[k].kind == XPBD_LIMIT_SLIDE)
+            slide.push_back(limits[k]);
+    const uint32_t n_all = n_limits;
+    n_limits -= (uint32_t)slide.size();
+    // CSR joint -> angular limits, the caller's order inside a joint
+    std::vector<uint32_t> off((size_t)w->joints.n + 1, 0);
+    for (uint32_t k = 0; k < n_all; ++k)
+        if (limits[k].kind != XPBD_LIMIT_SLIDE)
+            ++off[limits[k].joint + 1];
     for (uint32_t j = 0; j < w->joints.n; ++j)
         off[j + 1] += off[j];
     std::vector<xpbd_joint_limit> sorted(n_limits);
     {
         std::vector<uint32_t> cursor(off.begin(), off.end() - 1);
-        for (uint32_t k = 0; k < n_limits; ++k)
-            sorted[cursor[limits[k].joint]++] = limits[k];
+        for (uint32_t k = 0; k < n_all; ++k)
+            if (limits[k].kind != XPBD_LIMIT_SLIDE)
+                sorted[cursor[limits[k].joint]++] = limits[k];
     }
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    if (!slide.empty() || !w->joints.slide_limits.empty()) {
+        w->joints.slide_limits = std::move(slide);
+        XPBD_TRY(upload_joint_extras(w));
+    }
     if (n_limits == 0) {
         w->joints.n_limits = 0;
         return XPBD_OK;
@@ -1834,6 +1983,23 @@ try {
     XPBD_HIP_TRY(hipMemcpy(w->jt_limit_off.ptr, off.data(), off.size() * 4, hipMemcpyHostToDevice));
     w->joints.n_limits = n_limits;
     return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_set_joint_drives(xpbd_world *w, const xpbd_joint_drive *drives, uint32_t n_drives)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_drives: NULL world");
+    if (n_drives && w->mode != XPBD_MODE_CONTACTS)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_drives: drives need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
+    if (int rc = xpbd::check_joint_drives("xpbd_world_set_joint_drives", w->joints.host.data(), w->joints.n, drives, n_drives))
+        return rc;
+    if (n_drives == 0 && w->joints.drives.empty())
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    w->joints.drives.assign(drives, drives + n_drives);
+    return upload_joint_extras(w);
 } XPBD_ABI_CATCH
 
 int xpbd_world_set_collision_filters(xpbd_world *w, const xpbd_collision_filter *filters, uint32_t n, uint32_t flags)

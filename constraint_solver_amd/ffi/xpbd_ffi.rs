@@ -90,13 +90,28 @@ pub struct XpbdJoint {
     pub anchor_a: [f64; 3],
     pub anchor_b: [f64; 3],
     pub distance: f64,
-    pub axis_a: [f64; 3], // XPBD_JOINT_HINGE: unit axes in the object space of a / b that the joint keeps aligned
+    pub axis_a: [f64; 3], // XPBD_JOINT_HINGE, XPBD_JOINT_SLIDER: unit axes in the object space of a / b that the joint keeps aligned
     pub axis_b: [f64; 3],
-    pub kind: u32,        // XPBD_JOINT_DISTANCE = 0, XPBD_JOINT_HINGE = 1
+    pub kind: u32,        // XPBD_JOINT_DISTANCE = 0, XPBD_JOINT_HINGE = 1, XPBD_JOINT_SLIDER = 2
     pub reserved: u32,
 }
 
-/// EXTENSION: angular limit of a joint (XPBD_LIMIT_HINGE = 0, XPBD_LIMIT_SWING = 1, XPBD_LIMIT_TWIST = 2; see xpbd.h).
+/// EXTENSION: drive of a joint (XPBD_DRIVE_ANGLE = 0, XPBD_DRIVE_ANGULAR_VELOCITY = 1, XPBD_DRIVE_POSITION = 2,
+/// XPBD_DRIVE_VELOCITY = 3; see xpbd.h, "SLIDERS and joint DRIVES").
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct XpbdJointDrive {
+    pub joint: u32,       // index into the joints of the last xpbd_world_set_joints
+    pub kind: u32,
+    pub ref_a: [f64; 3],  // angular kinds: unit vectors perpendicular to axis_a / axis_b, object space of a / b
+    pub ref_b: [f64; 3],
+    pub target: f64,      // rad, rad/s, m, m/s
+    pub compliance: f64,  // >= 0, finite
+    pub max_force: f64,   // > 0, +inf allowed
+}
+
+/// EXTENSION: limit of a joint (XPBD_LIMIT_HINGE = 0, XPBD_LIMIT_SWING = 1, XPBD_LIMIT_TWIST = 2: angular, radians;
+/// XPBD_LIMIT_SLIDE = 3: the travel of a slider, metres; see xpbd.h).
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct XpbdJointLimit {
@@ -366,6 +381,7 @@ extern "C" {
     pub fn xpbd_world_download_neighbours(w: *mut XpbdWorld, offsets: *mut u32, neighbours: *mut u32, cap: u32) -> c_int;
     pub fn xpbd_world_set_joints(w: *mut XpbdWorld, joints: *const XpbdJoint, n_joints: u32) -> c_int;
     pub fn xpbd_world_set_joint_limits(w: *mut XpbdWorld, limits: *const XpbdJointLimit, n_limits: u32) -> c_int;
+    pub fn xpbd_world_set_joint_drives(w: *mut XpbdWorld, drives: *const XpbdJointDrive, n_drives: u32) -> c_int;
     pub fn xpbd_world_set_max_depenetration_speed(w: *mut XpbdWorld, speed: f64) -> c_int;
     pub fn xpbd_multi_world_set_max_depenetration_speed(mw: *mut XpbdMultiWorld, speed: f64) -> c_int;
     pub fn xpbd_world_snapshot_positions(w: *mut XpbdWorld, dev_indices: *const u32, n: u32, dev_snapshot: *mut f64) -> c_int;
@@ -380,6 +396,7 @@ extern "C" {
     pub fn xpbd_multi_world_upload(mw: *mut XpbdMultiWorld, bodies: *const XpbdRigid, shape_id: *const u32, first_global: u32, n_bodies: u32,
                                    n_global: u32, joints: *const XpbdJoint, n_joints: u32) -> c_int;
     pub fn xpbd_multi_world_set_joint_limits(mw: *mut XpbdMultiWorld, limits: *const XpbdJointLimit, n_limits: u32) -> c_int;
+    pub fn xpbd_multi_world_set_joint_drives(mw: *mut XpbdMultiWorld, drives: *const XpbdJointDrive, n_drives: u32) -> c_int;
     pub fn xpbd_multi_world_step(mw: *mut XpbdMultiWorld, dt: f64, substeps: u32) -> c_int;
     pub fn xpbd_multi_world_replan(mw: *mut XpbdMultiWorld) -> c_int;
     pub fn xpbd_multi_world_synchronize(mw: *mut XpbdMultiWorld) -> c_int;

@@ -656,6 +656,11 @@ class ShardedWorld {
     {
         check(xpbd_multi_world_set_joint_limits(w_, limits.empty() ? nullptr : limits.data(), (uint32_t)limits.size()));
     }
+    // drives on the joints of the last upload (global joint indices; empty: none); upload clears them
+    void set_joint_drives(const std::vector<xpbd_joint_drive> &drives)
+    {
+        check(xpbd_multi_world_set_joint_drives(w_, drives.empty() ? nullptr : drives.data(), (uint32_t)drives.size()));
+    }
     void integrate(double dt, uint32_t substeps) { check(xpbd_multi_world_step(w_, dt, substeps)); }
     void replan() { check(xpbd_multi_world_replan(w_)); }
     // closest body along every ray, bodies by global index (collective: every rank passes the same rays)

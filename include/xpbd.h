@@ -279,6 +279,7 @@ int  xpbd_world_download_neighbours(xpbd_world *w, uint32_t *offsets, uint32_t *
  * Body indices refer to the bodies uploaded last; uploading bodies again clears the joints.
  * Only XPBD_MODE_CONTACTS projects joints: in the other modes a non-empty list is XPBD_E_INVALID. */
 #define XPBD_JOINT_DISTANCE 0u  /* positional term only (distance = 0: ball joint) */
+/* (XPBD_JOINT_SLIDER = 2: see "SLIDERS and joint DRIVES" below) */
 #define XPBD_JOINT_HINGE    1u  /* positional term + ANGULAR term: the unit axes axis_a / axis_b (object space of a / b) are kept
                                  * aligned.  With a_w = rot_a * axis_a, b_w = rot_b * axis_b: delta = a_w x b_w, n = delta / |delta|,
                                  * w = sum over both bodies of (I^-1 (q^-1 n)) . (q^-1 n) (the angular half of
@@ -291,7 +292,7 @@ typedef struct xpbd_joint {
     double   anchor_a[3];
     double   anchor_b[3];
     double   distance;
-    double   axis_a[3];   /* XPBD_JOINT_HINGE: unit vectors */
+    double   axis_a[3];   /* XPBD_JOINT_HINGE, XPBD_JOINT_SLIDER: unit vectors */
     double   axis_b[3];
     uint32_t kind;        /* XPBD_JOINT_* */
     uint32_t reserved;    /* must be 0 */
@@ -329,6 +330,58 @@ typedef struct xpbd_joint_limit {
     double   lower, upper;   /* radians */
 } xpbd_joint_limit;          /* 72 bytes */
 int  xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, uint32_t n_limits);
+
+/* SLIDERS and joint DRIVES (EXTENSION): a joint that lets a body translate along a line, and joints that do work.
+ *
+ * XPBD_JOINT_SLIDER (a kind of xpbd_joint) is a cylindrical joint: body b's anchor may move along body a's axis and the two
+ * axes stay aligned.  It needs unit axis_a / axis_b (the hinge's tolerance) and distance == 0.  It has the hinge's angular
+ * term but NOT the positional term; its anchor is held by the perpendicular term below.  Wherever a HINGE joint is accepted
+ * (XPBD_LIMIT_HINGE) a SLIDER is too: a prismatic joint is a slider with an XPBD_LIMIT_HINGE of lower = upper = 0.
+ * XPBD_LIMIT_SLIDE (a kind of xpbd_joint_limit, SLIDER joints only) bounds the travel: lower <= upper, both finite, in
+ * metres (the [-pi, pi] rule is for the angular kinds); ref_a / ref_b are ignored; at most one per joint.
+ * An xpbd_joint_drive moves the degree of freedom a joint leaves free.  compliance alpha >= 0 and finite (0: as stiff as
+ * a limit; rad/(N m) or m/N); max_force > 0, +inf allowed (N m or N).
+ *
+ * Every term is evaluated at the poses the joint pass sees, with c = 1e-6 / h^2, p_a, p_b the world anchors, d = p_b - p_a,
+ * a_w = q_a * axis_a, s = d . a_w, W(body, p, n) = Constraint::inverse_resitance (as the positional term), Wang(n) the
+ * angular w of the limits; a subscript 0 is the same expression at the poses of the START of the substep.  A joint's extra
+ * entries, in this order, are summed among themselves from 0 (position, rotation, count) and the sum is added to each
+ * body's accumulator after the joint's positional, hinge and angular-limit entries, only when its count is nonzero:
+ *   1. SLIDER, perpendicular term: r = d - a_w s, len = |r| (0: no entry), n = r / len, lambda = len / (W_a(p_a, n) +
+ *      W_b(p_b, n) + c); a gets the impulse +lambda n at p_a, b gets -lambda n at p_b, as the positional term applies its own.
+ *   2. XPBD_LIMIT_SLIDE: e = s - clamp(s, lower, upper) (0: no entry), n = a_w, lambda = e / (W_a + W_b + c), applied as 1.
+ *   3. the drives, in the caller's order.  n = a_w.  With phi the angle of XPBD_LIMIT_HINGE (from ref_a, ref_b) and
+ *      wrap(x) = x > pi ? x - 2 pi : (x < -pi ? x + 2 pi : x):
+ *        ANGLE             e = wrap(phi - target)                  ANGULAR_VELOCITY  e = wrap(phi - phi_0) - target h
+ *        POSITION          e = s - target                          VELOCITY          e = (s - s_0) - target h
+ *      e == 0: no entry.  w = Wang(n) (angular kinds: a turns by +lambda n, b by -lambda n, as a limit does) or W_a + W_b
+ *      (linear kinds: applied as 2);  lambda = e / (w + (1e-6 + alpha) / h^2), then clamped to +-max_force h^2.  The entry
+ *      counts even when lambda was clamped.
+ * The velocity drives keep no state: they ask for target * h of motion within every substep, so history restore reproduces
+ * a run bit for bit and a sharded world equals the single one.  A world without sliders, SLIDE limits and drives steps bit
+ * for bit as before.
+ * Drives name joints of the last xpbd_world_set_joints; setting joints or uploading bodies clears them; n_drives = 0 clears
+ * them; xpbd_world_set_joint_limits and xpbd_world_set_joint_drives do not clear each other.  XPBD_E_INVALID (the previous
+ * drives stay in place): a world not in XPBD_MODE_CONTACTS, a joint index out of range, an unknown kind, a kind that does
+ * not fit the joint, two angular or two linear drives on one joint, a non-unit ref_a / ref_b or one not perpendicular to its
+ * axis (angular kinds; the limits' 1e-3 tolerances), a non-finite target, an ANGLE target outside [-pi, pi], a negative or
+ * non-finite compliance, a max_force that is <= 0 or NaN. */
+#define XPBD_JOINT_SLIDER 2u              /* xpbd_joint.kind */
+#define XPBD_LIMIT_SLIDE 3u               /* xpbd_joint_limit.kind: joint kind SLIDER, s in [lower, upper] metres */
+#define XPBD_DRIVE_ANGLE 0u               /* joint kind HINGE or SLIDER: phi -> target (rad); refs as XPBD_LIMIT_HINGE */
+#define XPBD_DRIVE_ANGULAR_VELOCITY 1u    /* joint kind HINGE or SLIDER: phi moves by target (rad/s) * h per substep; refs as above */
+#define XPBD_DRIVE_POSITION 2u            /* joint kind SLIDER: s -> target (m) */
+#define XPBD_DRIVE_VELOCITY 3u            /* joint kind SLIDER: s moves by target (m/s) * h per substep */
+typedef struct xpbd_joint_drive {
+    uint32_t joint;          /* index into the list of the last xpbd_world_set_joints */
+    uint32_t kind;           /* XPBD_DRIVE_* */
+    double   ref_a[3];       /* angular kinds: unit vector perpendicular to axis_a, object space of body_a */
+    double   ref_b[3];       /* angular kinds: unit vector perpendicular to axis_b, object space of body_b */
+    double   target;         /* rad, rad/s, m, m/s */
+    double   compliance;     /* alpha */
+    double   max_force;      /* N m or N */
+} xpbd_joint_drive;          /* 80 bytes */
+int  xpbd_world_set_joint_drives(xpbd_world *w, const xpbd_joint_drive *drives, uint32_t n_drives);
 
 /* Collision FILTERS (EXTENSION): which body-body pairs may touch.
  * Pair rule: bodies i and j may touch iff (group_i & mask_j) != 0 && (group_j & mask_i) != 0; with XPBD_FILTER_JOINTED
@@ -566,6 +619,10 @@ int  xpbd_multi_world_upload(xpbd_multi_world *mw, const xpbd_rigid *bodies, con
  * clears them.  Checked against those joints before any device work; not collective.  A device failure while the limits are
  * handed to the local shards leaves the shards disagreeing: the world is unusable then (destroy it). */
 int  xpbd_multi_world_set_joint_limits(xpbd_multi_world *mw, const xpbd_joint_limit *limits, uint32_t n_limits);
+/* xpbd_world_set_joint_drives for the joints of the last upload (GLOBAL joint indices, the same list on every rank); upload
+ * clears them.  Checked against those joints before any device work; not collective.  Lifetime and errors as
+ * xpbd_multi_world_set_joint_limits. */
+int  xpbd_multi_world_set_joint_drives(xpbd_multi_world *mw, const xpbd_joint_drive *drives, uint32_t n_drives);
 /* xpbd_world_set_collision_filters for the whole world: n_global filters in GLOBAL body order, the same list on every rank;
  * upload clears them.  Every shard gets the filters of the bodies it owns and mirrors.  Not collective. */
 int  xpbd_multi_world_set_collision_filters(xpbd_multi_world *mw, const xpbd_collision_filter *filters, uint32_t n_global,
