@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "xpbd_multi_world_set_external_wrench", "xpbd_multi_world_apply_impulses",
     "xpbd_world_overlap", "xpbd_world_overlap_device", "xpbd_multi_world_overlap",
     "xpbd_world_sweep", "xpbd_world_sweep_device", "xpbd_multi_world_sweep",
+    "xpbd_world_remove_bodies", "xpbd_world_remove_bodies_device", "xpbd_world_add_bodies",
 ]
 
 
@@ -399,6 +400,12 @@ def hip_lib():
             L.xpbd_multi_world_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
+        try:
+            L.xpbd_world_remove_bodies.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, _u32p]
+            L.xpbd_world_remove_bodies_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u32p]
+            L.xpbd_world_add_bodies.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _u32p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
         _hip = L
     return _hip
 
@@ -450,6 +457,7 @@ class World:
         self._h = C.c_void_p()
         _check(L.xpbd_world_create(C.byref(self._h), C.byref(cfg)))
         self.n = 0
+        self.n_joints = 0
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -476,6 +484,7 @@ class World:
         sid = None if shape_id is None else np.ascontiguousarray(shape_id, dtype=np.uint32)
         _check(hip_lib().xpbd_world_upload_bodies(self._h, b.ctypes.data, None if sid is None else _u32(sid), b.shape[0]))
         self.n = b.shape[0]
+        self.n_joints = 0
 
     def step(self, dt, substeps):
         _check(hip_lib().xpbd_world_step(self._h, dt, substeps))
@@ -565,6 +574,7 @@ class World:
         """joints: JOINT_DTYPE records naming bodies of the last upload (extension; XPBD_MODE_CONTACTS)."""
         j = np.ascontiguousarray(joints, dtype=JOINT_DTYPE)
         _check(hip_lib().xpbd_world_set_joints(self._h, j.ctypes.data if j.size else None, j.size))
+        self.n_joints = j.size
 
     def set_joint_limits(self, limits):
         """limits: JOINT_LIMIT_DTYPE records naming joints of the last set_joints (extension; empty clears them)."""
@@ -705,6 +715,44 @@ class World:
         out = np.empty((n, DYNAMIC_DOUBLES), dtype=np.float64)
         _check(hip_lib().xpbd_world_get_dynamics(self._h, None if idx is None else idx.ctypes.data, n, out.ctypes.data if n else None))
         return out
+
+    # body population (include/xpbd.h, "Body POPULATION"): removing resident bodies and appending new ones
+    def remove_bodies(self, indices):
+        """Removes the listed bodies (an index may be listed twice); the survivors keep their order and their settings.
+        Returns (old_to_new, joint_old_to_new): uint32 arrays of the old body and joint counts, NO_HIT for what is gone.  Waits."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        old_to_new = np.empty(self.n, dtype=np.uint32)
+        joint_old_to_new = np.empty(self.n_joints, dtype=np.uint32)
+        n_out = C.c_uint32(self.n)
+        _check(hip_lib().xpbd_world_remove_bodies(self._h, idx.ctypes.data if idx.size else None, idx.size,
+                                                  old_to_new.ctypes.data if self.n else None,
+                                                  joint_old_to_new.ctypes.data if self.n_joints else None, C.byref(n_out)))
+        self.n = n_out.value
+        self.n_joints = int(np.count_nonzero(joint_old_to_new != NO_HIT))
+        return old_to_new, joint_old_to_new
+
+    def remove_bodies_device(self, dev_ptr, dev_map_ptr=None):
+        """dev_ptr: device array of one byte per body, nonzero = remove, produced on the world's stream or ordered before it;
+        dev_map_ptr: device uint32 array of the old body count that receives old_to_new, or None.  Returns joint_old_to_new.  Waits."""
+        joint_old_to_new = np.empty(self.n_joints, dtype=np.uint32)
+        n_out = C.c_uint32(self.n)
+        _check(hip_lib().xpbd_world_remove_bodies_device(self._h, C.c_void_p(dev_ptr or None), C.c_void_p(dev_map_ptr or None),
+                                                         joint_old_to_new.ctypes.data if self.n_joints else None, C.byref(n_out)))
+        self.n = n_out.value
+        self.n_joints = int(np.count_nonzero(joint_old_to_new != NO_HIT))
+        return joint_old_to_new
+
+    def add_bodies(self, bodies, shape_id):
+        """Appends bodies ((k, 38) rows with their shape ids) with the default settings; returns the index of the first.  Waits."""
+        b = np.ascontiguousarray(bodies, dtype=np.float64).reshape(-1, RIGID_DOUBLES)
+        sid = np.ascontiguousarray(shape_id, dtype=np.uint32).reshape(-1)
+        if sid.size != b.shape[0]:
+            raise ValueError("add_bodies: %d bodies but %d shape ids" % (b.shape[0], sid.size))
+        first = C.c_uint32(self.n)
+        _check(hip_lib().xpbd_world_add_bodies(self._h, b.ctypes.data if b.size else None, sid.ctypes.data if sid.size else None,
+                                               b.shape[0], C.byref(first)))
+        self.n += b.shape[0]
+        return first.value
 
     def get_stream(self):
         return hip_lib().xpbd_world_get_stream(self._h)

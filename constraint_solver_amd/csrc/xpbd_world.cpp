@@ -23,6 +23,8 @@
 #include "xpbd_contacts.h"
 #include "xpbd_gjk.h"
 #include "xpbd_pairs.h"
+#include "xpbd_population.h"
+#include "xpbd_population_remap.hpp"
 #include "xpbd_query.h"
 #include "xpbd_report.h"
 
@@ -114,7 +116,9 @@ struct xpbd_world {
         uint32_t n = 0, n_limits = 0; // n_limits: the ANGULAR limits, the table the pair solve walks
         uint32_t n_extra_joints = 0;  // joints with extra entries (sliders, SLIDE limits, drives): the lanes of k_joint_extras
         std::vector<xpbd_joint> host; // the joints of the last set_joints: what xpbd_world_set_joint_limits checks against
-        std::vector<xpbd_joint_limit> slide_limits; // the XPBD_LIMIT_SLIDE limits of the last set_joint_limits
+        std::vector<xpbd_joint_limit> limits;       // all limits of the last set_joint_limits, the caller's order (a population
+                                                    // change re-indexes them: xpbd_world_remove_bodies)
+        std::vector<xpbd_joint_limit> slide_limits; // the XPBD_LIMIT_SLIDE ones among them
         std::vector<xpbd_joint_drive> drives;       // the drives of the last set_joint_drives, the caller's order
         void clear() { *this = Joints{}; }
     } joints;
@@ -148,6 +152,9 @@ struct xpbd_world {
     // body edits (xpbd_world_set_external_wrench, _apply_impulses, _set_dynamics, _get_dynamics): the staging of the host
     // variants' indices, values (force + torque, or rows of 13 doubles) and impulse lists
     DeviceBuffer ed_indices, ed_values, ed_list;
+    // body population (xpbd_world_remove_bodies, _add_bodies): the removal flags and index list of the host variant, the scan,
+    // old_to_new and its inverse src[new] = old.  Scratch of one call; the new arrays are staged in buffers of their own.
+    DeviceBuffer pop_remove, pop_indices, pop_prefix, pop_scan, pop_map, pop_src;
     // state history (xpbd_world_history_*): `history_length` slots of history_slot_bytes() in one growing block
     DeviceBuffer history;
     uint32_t history_length = 0;
@@ -774,27 +781,17 @@ void absorb_stat_record(xpbd_world *w, const xpbd_rigid &body, uint32_t sid)
     }
 }
 
-// The world takes a new set of n_new bodies (xpbd_world_upload_bodies, xpbd::repack_bodies; device bound, stream idle): room for
-// them, and everything that named the old bodies by index or was derived from them is dropped -- the body-indexed settings,
-// neighbour lists, history, trace, frame snapshot and contact report.  The callers fill the arrays and see to the per-shape mass
-// properties (stat_shape_*), which one resets and the other keeps.
-int adopt_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id)
+uint32_t stride_for(uint32_t n_bodies) { return round_up(n_bodies ? n_bodies : 1, 256); }
+
+// The body arrays hold n_new bodies from now on (the caller made room: stride_for(n_new)): what was derived from the old
+// bodies is dropped -- neighbour lists, history, trace, contact masks, frame snapshot and the contact report's state.
+void take_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id)
 {
-    const uint32_t stride = round_up(n_new ? n_new : 1, 256);
-    XPBD_HIP_TRY(w->dyn.reserve((size_t)xpbd::kDynFields * stride * 8));
     w->have_neighbours = false;
-    w->joints.clear();
-    w->filters.clear();
-    w->materials.clear();
-    w->restitution.clear();
     w->history_length = 0;
     w->history_stepped.clear();
-    XPBD_HIP_TRY(w->stat.reserve((size_t)xpbd::kStatFields * stride * 8));
-    XPBD_HIP_TRY(w->shape_id.reserve((size_t)stride * 4));
-    XPBD_HIP_TRY(w->last_mask.reserve((size_t)stride * 4));
-    XPBD_HIP_TRY(w->aos_staging.reserve((size_t)(n_new ? n_new : 1) * sizeof(xpbd_rigid)));
     w->n = n_new;
-    w->stride = stride;
+    w->stride = stride_for(n_new);
     w->stat_rec_valid = false;
     w->max_shape_id = max_shape_id;
     w->stepped = false;
@@ -802,6 +799,32 @@ int adopt_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id)
     w->frame_snapshot_valid = false;
     w->bp_pending = false;
     report_reset(w);
+}
+
+// The settings that name bodies (or the joints between them) by index go back to their defaults.
+void drop_body_settings(xpbd_world *w)
+{
+    w->joints.clear();
+    w->filters.clear();
+    w->materials.clear();
+    w->restitution.clear();
+}
+
+// The world takes a new set of n_new bodies (xpbd_world_upload_bodies, xpbd::repack_bodies; device bound, stream idle): room for
+// them, and everything that named the old bodies by index or was derived from them is dropped -- the body-indexed settings
+// (drop_body_settings) and the derived state (take_body_count).  The callers fill the arrays and see to the per-shape mass
+// properties (stat_shape_*), which one resets and the other keeps.  (A population change keeps the settings: it stages its
+// arrays itself and calls take_body_count alone.)
+int adopt_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id)
+{
+    const uint32_t stride = stride_for(n_new);
+    XPBD_HIP_TRY(w->dyn.reserve((size_t)xpbd::kDynFields * stride * 8));
+    drop_body_settings(w);
+    XPBD_HIP_TRY(w->stat.reserve((size_t)xpbd::kStatFields * stride * 8));
+    XPBD_HIP_TRY(w->shape_id.reserve((size_t)stride * 4));
+    XPBD_HIP_TRY(w->last_mask.reserve((size_t)stride * 4));
+    XPBD_HIP_TRY(w->aos_staging.reserve((size_t)(n_new ? n_new : 1) * sizeof(xpbd_rigid)));
+    take_body_count(w, n_new, max_shape_id);
     return XPBD_OK;
 }
 
@@ -1839,49 +1862,15 @@ namespace {
 // which is what the pair solve reads for a joint that is not listed.  The device is bound and the stream idle.
 int upload_joint_extras(xpbd_world *w)
 {
+    static_assert(xpbd::kExtraItemSlideLimit == xpbd::kExtraSlideLimit && sizeof(xpbd::ExtraItem) == sizeof(xpbd::JointExtraItem),
+                  "xpbd::ExtraItem must mirror xpbd::JointExtraItem");
     xpbd_world::Joints &J = w->joints;
     J.n_extra_joints = 0; // (a failed copy below leaves none rather than a torn table)
-    std::vector<uint32_t> count(J.n, 0);
-    std::vector<uint8_t> listed(J.n, 0);
-    for (uint32_t j = 0; j < J.n; ++j)
-        listed[j] = J.host[j].kind == XPBD_JOINT_SLIDER;
-    for (const xpbd_joint_limit &l : J.slide_limits)
-        ++count[l.joint], listed[l.joint] = 1;
-    for (const xpbd_joint_drive &d : J.drives)
-        ++count[d.joint], listed[d.joint] = 1;
-    std::vector<uint32_t> list, off(1, 0), first(J.n, 0);
-    for (uint32_t j = 0; j < J.n; ++j)
-        if (listed[j]) {
-            list.push_back(j);
-            first[j] = off.back();
-            off.push_back(off.back() + count[j]);
-        }
+    const xpbd::ExtraTables t = xpbd::build_extra_tables(J.host, J.slide_limits, J.drives, w->n);
+    const std::vector<uint32_t> &list = t.list, &slots = t.slots, &off = t.off;
+    const std::vector<xpbd::ExtraItem> &items = t.items;
     if (list.empty())
         return XPBD_OK;
-    // where the two ends of a listed joint sit in the bodies' joint lists (the CSR of xpbd_world_set_joints)
-    std::vector<uint32_t> slot_cursor((size_t)w->n + 1, 0), slots(2 * list.size());
-    for (const xpbd_joint &j : J.host) {
-        ++slot_cursor[j.body_a + 1];
-        ++slot_cursor[j.body_b + 1];
-    }
-    for (uint32_t i = 0; i < w->n; ++i)
-        slot_cursor[i + 1] += slot_cursor[i];
-    for (uint32_t j = 0, t = 0; j < J.n; ++j) {
-        const uint32_t slot_a = slot_cursor[J.host[j].body_a]++, slot_b = slot_cursor[J.host[j].body_b]++;
-        if (listed[j]) {
-            slots[2 * t] = slot_a, slots[2 * t + 1] = slot_b;
-            ++t;
-        }
-    }
-    std::vector<xpbd::JointExtraItem> items(std::max<size_t>(off.back(), 1));
-    std::vector<uint32_t> cursor = first;
-    for (const xpbd_joint_limit &l : J.slide_limits) {
-        xpbd::JointExtraItem it{};
-        it.joint = l.joint, it.kind = xpbd::kExtraSlideLimit, it.target = l.lower, it.compliance = l.upper;
-        items[cursor[l.joint]++] = it;
-    }
-    for (const xpbd_joint_drive &d : J.drives)
-        std::memcpy(&items[cursor[d.joint]++], &d, sizeof d);
     const size_t sums = (size_t)2 * J.n * xpbd::kJointExtraDoubles * 8;
     XPBD_HIP_TRY(w->jt_extra.reserve(sums));
     XPBD_HIP_TRY(w->jt_extra_joints.reserve(list.size() * 4));
@@ -1907,18 +1896,8 @@ try {
     if (n_joints && w->mode != XPBD_MODE_CONTACTS) // only the contact pipeline projects joints: do not accept and ignore them
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joints: joints need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
     XPBD_TRY(xpbd::check_joints("xpbd_world_set_joints", joints, n_joints, w->n));
-    std::vector<uint32_t> off((size_t)w->n + 2, 0), list((size_t)2 * n_joints);
-    for (uint32_t k = 0; k < n_joints; ++k) {
-        ++off[joints[k].body_a + 1];
-        ++off[joints[k].body_b + 1];
-    }
-    for (uint32_t i = 0; i < w->n; ++i)
-        off[i + 1] += off[i];
-    std::vector<uint32_t> cursor(off.begin(), off.end() - 1);
-    for (uint32_t k = 0; k < n_joints; ++k) { // ascending joint index inside every body's list
-        list[cursor[joints[k].body_a]++] = k;
-        list[cursor[joints[k].body_b]++] = k;
-    }
+    const xpbd::JointCsr csr = xpbd::build_joint_csr(joints, n_joints, w->n);
+    const std::vector<uint32_t> &off = csr.off, &list = csr.list;
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
@@ -1944,30 +1923,17 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_limits: limits need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
     if (int rc = xpbd::check_joint_limits("xpbd_world_set_joint_limits", w->joints.host.data(), w->joints.n, limits, n_limits))
         return rc;
-    // the SLIDE limits are entries of k_joint_extras, not of the pair solve's table
-    std::vector<xpbd_joint_limit> slide;
-    for (uint32_t k = 0; k < n_limits; ++k)
-        if (limits[k].kind == XPBD_LIMIT_SLIDE)
-            slide.push_back(limits[k]);
+    // the SLIDE limits apart (entries of k_joint_extras), the angular ones behind a CSR joint -> limits
+    xpbd::LimitTables tables = xpbd::build_limit_tables(limits, n_limits, w->joints.n);
+    std::vector<xpbd_joint_limit> &slide = tables.slide;
+    const std::vector<xpbd_joint_limit> &sorted = tables.sorted;
+    const std::vector<uint32_t> &off = tables.off;
     const uint32_t n_all = n_limits;
     n_limits -= (uint32_t)slide.size();
-    // CSR joint -> angular limits, the caller's order inside a joint
-    std::vector<uint32_t> off((size_t)w->joints.n + 1, 0);
-    for (uint32_t k = 0; k < n_all; ++k)
-        if (limits[k].kind != XPBD_LIMIT_SLIDE)
-            ++off[limits[k].joint + 1];
-    for (uint32_t j = 0; j < w->joints.n; ++j)
-        off[j + 1] += off[j];
-    std::vector<xpbd_joint_limit> sorted(n_limits);
-    {
-        std::vector<uint32_t> cursor(off.begin(), off.end() - 1);
-        for (uint32_t k = 0; k < n_all; ++k)
-            if (limits[k].kind != XPBD_LIMIT_SLIDE)
-                sorted[cursor[limits[k].joint]++] = limits[k];
-    }
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    w->joints.limits.assign(limits, limits + n_all);
     if (!slide.empty() || !w->joints.slide_limits.empty()) {
         w->joints.slide_limits = std::move(slide);
         XPBD_TRY(upload_joint_extras(w));
@@ -2563,6 +2529,294 @@ try {
     XPBD_HIP_TRY(xpbd::launch_export_dynamic(w->arrays(), w->ed_indices.as<uint32_t>(), n, w->ed_values.as<double>(), w->stream));
     XPBD_HIP_TRY(hipMemcpyAsync(rows, w->ed_values.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+// ---- body population (include/xpbd.h, "Body POPULATION") -----------------------------------------------------------------------
+namespace {
+// Everything a population change replaces, built aside: the body arrays at the new stride, the per-body tables that are on, the
+// scratch sized by the stride, and the joint tables.  Only commit_population touches the world, after every allocation, copy
+// and launch has succeeded; a stage that is dropped frees its blocks and leaves the previous population in force.
+struct PopulationStage {
+    uint32_t n = 0, stride = 0;
+    DeviceBuffer dyn, stat, shape_id, last_mask, aos_staging, filters, friction, restitution, dyn_alt, rs_start;
+    xpbd_world::Joints joints;
+    DeviceBuffer jt_joints, jt_off, jt_list, jt_limits, jt_limit_off, jt_extra, jt_extra_joints, jt_extra_slots, jt_extra_off, jt_extra_items;
+};
+
+int stage_upload(DeviceBuffer &fresh, const void *values, size_t bytes)
+{
+    XPBD_HIP_TRY(fresh.reserve(bytes ? bytes : 8));
+    if (bytes)
+        XPBD_HIP_TRY(hipMemcpy(fresh.ptr, values, bytes, hipMemcpyHostToDevice));
+    return XPBD_OK;
+}
+
+// The tables xpbd_world_set_joints / _set_joint_limits / _set_joint_drives would build from `set` in a world of n_bodies bodies.
+int stage_joint_tables(const xpbd::JointSet &set, uint32_t n_bodies, PopulationStage &st)
+{
+    xpbd_world::Joints &J = st.joints;
+    J.clear();
+    const uint32_t n_joints = (uint32_t)set.joints.size();
+    if (n_joints == 0)
+        return XPBD_OK;
+    const xpbd::JointCsr csr = xpbd::build_joint_csr(set.joints.data(), n_joints, n_bodies);
+    XPBD_TRY(stage_upload(st.jt_joints, set.joints.data(), (size_t)n_joints * sizeof(xpbd::Joint)));
+    XPBD_TRY(stage_upload(st.jt_off, csr.off.data(), (size_t)(n_bodies + 1) * 4));
+    XPBD_TRY(stage_upload(st.jt_list, csr.list.data(), (size_t)2 * n_joints * 4));
+    xpbd::LimitTables lt = xpbd::build_limit_tables(set.limits.data(), (uint32_t)set.limits.size(), n_joints);
+    if (!lt.sorted.empty()) {
+        XPBD_TRY(stage_upload(st.jt_limits, lt.sorted.data(), lt.sorted.size() * sizeof(xpbd::JointLimit)));
+        XPBD_TRY(stage_upload(st.jt_limit_off, lt.off.data(), lt.off.size() * 4));
+    }
+    const xpbd::ExtraTables et = xpbd::build_extra_tables(set.joints, lt.slide, set.drives, n_bodies);
+    if (!et.list.empty()) {
+        const size_t sums = (size_t)2 * n_joints * xpbd::kJointExtraDoubles * 8;
+        XPBD_HIP_TRY(st.jt_extra.reserve(sums));
+        XPBD_HIP_TRY(hipMemset(st.jt_extra.ptr, 0, sums));
+        XPBD_TRY(stage_upload(st.jt_extra_joints, et.list.data(), et.list.size() * 4));
+        XPBD_TRY(stage_upload(st.jt_extra_slots, et.slots.data(), et.slots.size() * 4));
+        XPBD_TRY(stage_upload(st.jt_extra_off, et.off.data(), et.off.size() * 4));
+        XPBD_TRY(stage_upload(st.jt_extra_items, et.items.data(), et.items.size() * sizeof(xpbd::ExtraItem)));
+    }
+    J.n = n_joints;
+    J.n_limits = (uint32_t)lt.sorted.size();
+    J.n_extra_joints = (uint32_t)et.list.size();
+    J.host = set.joints;
+    J.limits = set.limits;
+    J.slide_limits = std::move(lt.slide);
+    J.drives = set.drives;
+    return XPBD_OK;
+}
+
+// The new body arrays and per-body tables: new body s < n_keep is the present body dev_src[s] (NULL: body s), the n_add bodies
+// of `aos` follow.  Device bound, stream idle; enqueues on the world's stream and does not wait.
+int stage_bodies(xpbd_world *w, const uint32_t *dev_src, uint32_t n_keep, const xpbd_rigid *aos, const uint32_t *shape_id, uint32_t n_add,
+                 PopulationStage &st)
+{
+    const uint32_t n_new = n_keep + n_add, stride = stride_for(n_new);
+    st.n = n_new;
+    st.stride = stride;
+    XPBD_HIP_TRY(st.dyn.reserve((size_t)xpbd::kDynFields * stride * 8));
+    XPBD_HIP_TRY(st.stat.reserve((size_t)xpbd::kStatFields * stride * 8));
+    XPBD_HIP_TRY(st.shape_id.reserve((size_t)stride * 4));
+    XPBD_HIP_TRY(st.last_mask.reserve((size_t)stride * 4));
+    const size_t aos_bytes = (size_t)(n_new ? n_new : 1) * sizeof(xpbd_rigid);
+    if (w->aos_staging.bytes < aos_bytes) // (xpbd_world_download_bodies stages n bodies there)
+        XPBD_HIP_TRY(st.aos_staging.reserve(aos_bytes));
+    XPBD_HIP_TRY(hipMemsetAsync(st.last_mask.ptr, 0, (size_t)stride * 4, w->stream));
+    const xpbd::BodyArrays fresh{st.dyn.as<double>(), st.stat.as<double>(), st.shape_id.as<uint32_t>(), stride, n_new};
+    XPBD_HIP_TRY(xpbd::launch_population_gather_bodies(w->arrays(), fresh, dev_src, n_keep, w->stream));
+    if (n_add) {
+        // the appended bodies take k_aos_to_soa's tile path into the same arrays, from slot n_keep on
+        double *incoming = (st.aos_staging.ptr ? st.aos_staging : w->aos_staging).as<double>();
+        XPBD_HIP_TRY(hipMemcpyAsync(incoming, aos, (size_t)n_add * sizeof(xpbd_rigid), hipMemcpyHostToDevice, w->stream));
+        XPBD_HIP_TRY(hipMemcpyAsync(fresh.shape_id + n_keep, shape_id, (size_t)n_add * 4, hipMemcpyHostToDevice, w->stream));
+        const xpbd::BodyArrays tail{fresh.dyn + n_keep, fresh.stat + n_keep, fresh.shape_id + n_keep, stride, n_add};
+        XPBD_HIP_TRY(xpbd::launch_aos_to_soa(incoming, tail, w->stream));
+    }
+    // the per-body tables: a table that is off stays off; an appended body gets the default
+    if (w->filters.on) {
+        XPBD_HIP_TRY(st.filters.reserve((size_t)(n_new ? n_new : 1) * sizeof(uint2)));
+        XPBD_HIP_TRY(xpbd::launch_population_gather_filters(w->ft_filters.as<uint2>(), st.filters.as<uint2>(), dev_src, n_keep, n_new,
+                                                            uint2{~0u, ~0u}, w->stream));
+    }
+    if (w->materials.on) {
+        XPBD_HIP_TRY(st.friction.reserve((size_t)(n_new ? n_new : 1) * 8));
+        XPBD_HIP_TRY(xpbd::launch_population_gather_doubles(w->mt_friction.as<double>(), st.friction.as<double>(), dev_src, n_keep, n_new,
+                                                            std::numeric_limits<double>::infinity(), w->stream));
+    }
+    if (w->restitution.on) {
+        XPBD_HIP_TRY(st.restitution.reserve((size_t)(n_new ? n_new : 1) * 8));
+        XPBD_HIP_TRY(xpbd::launch_population_gather_doubles(w->rs_restitution.as<double>(), st.restitution.as<double>(), dev_src, n_keep, n_new, 0.0,
+                                                            w->stream));
+        if (w->dyn_alt.bytes < (size_t)xpbd::kDynFields * stride * 8) // the velocity pass's scratch follows the stride
+            XPBD_HIP_TRY(st.dyn_alt.reserve((size_t)xpbd::kDynFields * stride * 8));
+        if (w->rs_start.bytes < (size_t)6 * stride * 8)
+            XPBD_HIP_TRY(st.rs_start.reserve((size_t)6 * stride * 8));
+    }
+    return XPBD_OK;
+}
+
+// Nothing here can fail.  The old blocks leave with the stage.
+void commit_population(xpbd_world *w, PopulationStage &st, uint32_t max_shape_id)
+{
+    auto take = [](DeviceBuffer &mine, DeviceBuffer &fresh) {
+        if (fresh.ptr)
+            mine = std::move(fresh);
+    };
+    take(w->dyn, st.dyn);
+    take(w->stat, st.stat);
+    take(w->shape_id, st.shape_id);
+    take(w->last_mask, st.last_mask);
+    take(w->aos_staging, st.aos_staging);
+    take(w->ft_filters, st.filters);
+    take(w->mt_friction, st.friction);
+    take(w->rs_restitution, st.restitution);
+    take(w->dyn_alt, st.dyn_alt);
+    take(w->rs_start, st.rs_start);
+    w->joints = std::move(st.joints);
+    take(w->jt_joints, st.jt_joints);
+    take(w->jt_off, st.jt_off);
+    take(w->jt_list, st.jt_list);
+    take(w->jt_limits, st.jt_limits);
+    take(w->jt_limit_off, st.jt_limit_off);
+    take(w->jt_extra, st.jt_extra);
+    take(w->jt_extra_joints, st.jt_extra_joints);
+    take(w->jt_extra_slots, st.jt_extra_slots);
+    take(w->jt_extra_off, st.jt_extra_off);
+    take(w->jt_extra_items, st.jt_extra_items);
+    take_body_count(w, st.n, max_shape_id);
+}
+
+// Both variants of xpbd_world_remove_bodies, after their checks: the removal flags are on the device (dev_remove), or
+// `indices` still has to be scattered into the world's own flag array (dev_remove == NULL).
+int remove_bodies(xpbd_world *w, const uint8_t *dev_remove, const uint32_t *indices, uint32_t n_indices, uint32_t *old_to_new,
+                  uint32_t *dev_old_to_new, uint32_t *joint_old_to_new, uint32_t *n_bodies_out)
+{
+    XPBD_TRY(bind_device(w));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the scratch below may move, and the old arrays are freed at the end
+    const uint32_t n = w->n;
+    XPBD_HIP_TRY(w->pop_prefix.reserve(((size_t)n + 1) * 4));
+    XPBD_HIP_TRY(w->pop_scan.reserve(((size_t)n / 1024 + 8) * 4));
+    XPBD_HIP_TRY(w->pop_map.reserve((size_t)n * 4));
+    XPBD_HIP_TRY(w->pop_src.reserve((size_t)n * 4));
+    if (!dev_remove) {
+        XPBD_HIP_TRY(w->pop_remove.reserve(n));
+        XPBD_HIP_TRY(w->pop_indices.reserve((size_t)n_indices * 4));
+        XPBD_HIP_TRY(hipMemsetAsync(w->pop_remove.ptr, 0, n, w->stream));
+        XPBD_HIP_TRY(hipMemcpyAsync(w->pop_indices.ptr, indices, (size_t)n_indices * 4, hipMemcpyHostToDevice, w->stream));
+        XPBD_HIP_TRY(xpbd::launch_population_mark(w->pop_indices.as<uint32_t>(), n_indices, w->pop_remove.as<uint8_t>(), n, w->stream));
+        dev_remove = w->pop_remove.as<uint8_t>();
+    }
+    XPBD_HIP_TRY(xpbd::launch_population_map(dev_remove, n, w->pop_prefix.as<uint32_t>(), w->pop_scan.as<uint32_t>(), w->pop_map.as<uint32_t>(),
+                                             w->pop_src.as<uint32_t>(), w->stream));
+    uint32_t n_keep = 0;
+    XPBD_HIP_TRY(hipMemcpyAsync(&n_keep, w->pop_prefix.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, w->stream));
+    std::vector<uint32_t> map; // on the host only for the caller or for the joint re-index
+    if (old_to_new || w->joints.n) {
+        map.resize(n);
+        XPBD_HIP_TRY(hipMemcpyAsync(map.data(), w->pop_map.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, w->stream));
+    }
+    if (dev_old_to_new)
+        XPBD_HIP_TRY(hipMemcpyAsync(dev_old_to_new, w->pop_map.ptr, (size_t)n * 4, hipMemcpyDeviceToDevice, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    if (n_keep > n)
+        return set_error(XPBD_E_HIP, "xpbd_world_remove_bodies: the scan left %u survivors of %u bodies", n_keep, n);
+    std::vector<uint32_t> joint_map(w->joints.n);
+    if (n_keep == n) { // (the device variant with no flag set) nobody leaves: nothing changes, history and the rest stay
+        for (uint32_t j = 0; j < w->joints.n; ++j)
+            joint_map[j] = j;
+    } else {
+        PopulationStage st;
+        if (w->joints.n) {
+            xpbd::JointSet present;
+            present.joints = w->joints.host;
+            present.limits = w->joints.limits;
+            present.drives = w->joints.drives;
+            XPBD_TRY(stage_joint_tables(xpbd::remap_joint_set(present, map.data(), n, joint_map), n_keep, st));
+        }
+        XPBD_TRY(stage_bodies(w, w->pop_src.as<uint32_t>(), n_keep, nullptr, nullptr, 0, st));
+        XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+        commit_population(w, st, w->max_shape_id); // (max_shape_id stays an upper bound)
+        if (n_keep == 0)
+            w->stat_shared = false; // as after an upload of no bodies
+    }
+    if (old_to_new)
+        std::memcpy(old_to_new, map.data(), (size_t)n * 4);
+    if (joint_old_to_new && !joint_map.empty())
+        std::memcpy(joint_old_to_new, joint_map.data(), joint_map.size() * 4);
+    if (n_bodies_out)
+        *n_bodies_out = n_keep;
+    return XPBD_OK;
+}
+} // namespace
+
+int xpbd_world_remove_bodies(xpbd_world *w, const uint32_t *indices, uint32_t n, uint32_t *old_to_new, uint32_t *joint_old_to_new,
+                             uint32_t *n_bodies_out)
+try {
+    const char *who = "xpbd_world_remove_bodies";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0) { // nothing at all: the maps are the identity
+        for (uint32_t i = 0; old_to_new && i < w->n; ++i)
+            old_to_new[i] = i;
+        for (uint32_t j = 0; joint_old_to_new && j < w->joints.n; ++j)
+            joint_old_to_new[j] = j;
+        if (n_bodies_out)
+            *n_bodies_out = w->n;
+        return XPBD_OK;
+    }
+    if (!indices)
+        return set_error(XPBD_E_INVALID, "%s: NULL indices with n = %u", who, n);
+    if (w->n == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    for (uint32_t k = 0; k < n; ++k)
+        if (indices[k] >= w->n)
+            return set_error(XPBD_E_INVALID, "%s: indices[%u] = %u but the world holds %u bodies", who, k, indices[k], w->n);
+    return remove_bodies(w, nullptr, indices, n, old_to_new, nullptr, joint_old_to_new, n_bodies_out);
+} XPBD_ABI_CATCH
+
+int xpbd_world_remove_bodies_device(xpbd_world *w, const uint8_t *dev_remove, uint32_t *dev_old_to_new, uint32_t *joint_old_to_new,
+                                    uint32_t *n_bodies_out)
+try {
+    const char *who = "xpbd_world_remove_bodies_device";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (!dev_remove)
+        return set_error(XPBD_E_INVALID, "%s: NULL dev_remove", who);
+    if (w->n == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    return remove_bodies(w, dev_remove, nullptr, 0, nullptr, dev_old_to_new, joint_old_to_new, n_bodies_out);
+} XPBD_ABI_CATCH
+
+int xpbd_world_add_bodies(xpbd_world *w, const xpbd_rigid *aos, const uint32_t *shape_id, uint32_t n_add, uint32_t *first_index_out)
+try {
+    const char *who = "xpbd_world_add_bodies";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n_add == 0) {
+        if (first_index_out)
+            *first_index_out = w->n;
+        return XPBD_OK;
+    }
+    if (!aos || !shape_id)
+        return set_error(XPBD_E_INVALID, "%s: NULL aos or shape_id with n_add = %u", who, n_add);
+    if (w->n_shapes == 0)
+        return set_error(XPBD_E_INVALID, "%s: call xpbd_world_set_shapes first", who);
+    if (n_add > std::numeric_limits<uint32_t>::max() - 256u - w->n) // (the stride rounds the count up to a multiple of 256)
+        return set_error(XPBD_E_INVALID, "%s: %u + %u bodies exceed what xpbd_world_upload_bodies accepts", who, w->n, n_add);
+    uint32_t max_shape_id = w->n ? w->max_shape_id : 0u;
+    for (uint32_t i = 0; i < n_add; ++i) {
+        if (shape_id[i] >= w->n_shapes)
+            return set_error(XPBD_E_INVALID, "%s: shape_id[%u] = %u >= n_shapes %u", who, i, shape_id[i], w->n_shapes);
+        max_shape_id = shape_id[i] > max_shape_id ? shape_id[i] : max_shape_id;
+    }
+    XPBD_TRY(bind_device(w));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the old arrays are freed at the end
+    const uint32_t first = w->n;
+    PopulationStage st;
+    if (w->joints.n) { // the same joints in a world of more bodies: the CSR body -> joints grows
+        xpbd::JointSet present;
+        present.joints = w->joints.host;
+        present.limits = w->joints.limits;
+        present.drives = w->joints.drives;
+        XPBD_TRY(stage_joint_tables(present, first + n_add, st));
+    }
+    XPBD_TRY(stage_bodies(w, nullptr, first, aos, shape_id, n_add, st));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the caller's arrays are only borrowed
+    commit_population(w, st, max_shape_id);
+    // mass properties shared per shape: the bodies that stay kept the property, the appended ones are checked (a world that
+    // was empty starts over, as an upload does)
+    if (first == 0 || w->stat_shape_seen.size() != w->n_shapes) {
+        w->stat_shape_host.assign((size_t)w->n_shapes * xpbd::kStatRecDoubles, 0.0);
+        w->stat_shape_seen.assign(w->n_shapes, 0);
+        w->stat_shared = first == 0;
+    }
+    for (uint32_t i = 0; i < n_add && w->stat_shared; ++i)
+        absorb_stat_record(w, aos[i], shape_id[i]);
+    if (first_index_out)
+        *first_index_out = first;
     return XPBD_OK;
 } XPBD_ABI_CATCH
 

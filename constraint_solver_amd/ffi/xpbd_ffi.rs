@@ -452,6 +452,13 @@ extern "C" {
     pub fn xpbd_multi_world_set_external_wrench(mw: *mut XpbdMultiWorld, indices: *const u32, n: u32, force_xyz: *const f64,
                                                 torque_xyz: *const f64) -> c_int;
     pub fn xpbd_multi_world_apply_impulses(mw: *mut XpbdMultiWorld, list: *const XpbdImpulse, n: u32) -> c_int;
+    // Body POPULATION: removing resident bodies and appending new ones (include/xpbd.h); the maps use XPBD_NO_HIT for what is gone
+    pub fn xpbd_world_remove_bodies(w: *mut XpbdWorld, indices: *const u32, n: u32, old_to_new: *mut u32, joint_old_to_new: *mut u32,
+                                    n_bodies_out: *mut u32) -> c_int;
+    pub fn xpbd_world_remove_bodies_device(w: *mut XpbdWorld, dev_remove: *const u8, dev_old_to_new: *mut u32, joint_old_to_new: *mut u32,
+                                           n_bodies_out: *mut u32) -> c_int;
+    pub fn xpbd_world_add_bodies(w: *mut XpbdWorld, aos: *const XpbdRigid, shape_id: *const u32, n_add: u32, first_index_out: *mut u32)
+        -> c_int;
     pub fn xpbd_world_raycast_masked(w: *mut XpbdWorld, rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32, hits: *mut XpbdRayHit)
         -> c_int;
     pub fn xpbd_world_raycast_masked_device(w: *mut XpbdWorld, dev_rays: *const XpbdRay, n_rays: u32, flags: u32, mask: u32,

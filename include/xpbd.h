@@ -784,6 +784,70 @@ int  xpbd_multi_world_set_external_wrench(xpbd_multi_world *mw, const uint32_t *
 int  xpbd_multi_world_apply_impulses(xpbd_multi_world *mw, const xpbd_impulse *list, uint32_t n); /* GLOBAL bodies */
 
 /* ---------------------------------------------------------------------------
+ * Body POPULATION (EXTENSION): removing RESIDENT bodies and appending new ones, without uploading the others again.  NOT in
+ * the reference, whose world is a fixed pair of `Rigid`s (src/world.rs).  xpbd_world_upload_bodies is the other way to change
+ * the population, and it drops every body-indexed setting; here everything that belongs to a surviving body survives with it,
+ * re-indexed, and the work stays on the device: a scan of the removal flags, one SoA -> SoA gather of the bodies and one
+ * gather per per-body table.
+ *
+ * Order.  The survivors keep their relative order and are packed to the front: old_to_new[i] is the number of survivors among
+ * the bodies 0..i-1; a removed body maps to XPBD_NO_HIT (0xFFFFFFFF).  Added bodies are appended in the caller's order;
+ * *first_index_out is the body count before the call.  There are no handles: the maps are the contract.
+ *
+ * What travels with a surviving body.  All 38 doubles of its xpbd_rigid (external and internal forces among them, so whatever
+ * xpbd_world_set_external_wrench wrote), its shape id, and its row of the collision-filter table, the friction table and the
+ * restitution table.  The world-level values stay: the XPBD_FILTER_* flags, ground_friction, ground restitution, bounce
+ * threshold, contact pad, depenetration limit, narrowphase, SAT schedule, the contact report's enable flag, and the mode.
+ *
+ * Joints.  A joint whose two ends both survive stays, body_a and body_b re-indexed (their orientation kept).  A joint with a
+ * removed end is dropped, with its limits (angular and SLIDE) and its drives.  The surviving joints keep their relative order:
+ * joint_old_to_new[j] is the new number of joint j, XPBD_NO_HIT for a dropped one.  Limits and drives are re-indexed to the
+ * new joint numbers and keep the caller's relative order.  The result is what xpbd_world_set_joints / _set_joint_limits /
+ * _set_joint_drives would build from the re-indexed arrays.
+ *
+ * Added bodies get the defaults -- filter {~0u, ~0u}, friction +inf, restitution 0, no joints -- in a table that is on; a table
+ * that is off stays off.  They are checked exactly as xpbd_world_upload_bodies checks its bodies (the shape id range; the
+ * values of an xpbd_rigid are taken as given), take part in the per-shape test for shared mass properties as uploaded bodies
+ * do, and are valid in every mode.  shape_id is required here (upload's NULL = "all shape 0" form does not exist).
+ *
+ * What is DROPPED, exactly as after an upload: the history (xpbd_world_history_length becomes 0) and the contact trace, the
+ * contact masks of the last substep (xpbd_world_download_contacts reports none until the next step), the frame snapshot of a
+ * shard, the neighbour lists and the per-pair axis caches, and the contact report's state: there are NO END events for removed
+ * bodies, and the previous frame's pair list is invalid, so every pair touching in the next frame is a BEGIN.
+ *
+ * Calling discipline.  Every variant waits for completion and leaves a consistent world (the new body count has to reach the
+ * host anyway).  xpbd_world_remove_bodies and xpbd_world_add_bodies take host arrays and check everything before any device
+ * work.  xpbd_world_remove_bodies_device takes DEVICE flags, one byte per body, nonzero = remove; it is ordered on the world's
+ * stream (xpbd_world_get_stream / _set_stream: the producer of dev_remove runs on that stream or is ordered before it).
+ * dev_old_to_new (device, [old body count], or NULL) receives the map without a host round trip; when the world has joints the
+ * map is also brought to the host for the joint re-index.  old_to_new is a host array of the OLD body count, joint_old_to_new
+ * a host array of the old joint count, n_bodies_out the new body count; each may be NULL.
+ *
+ * The same index twice in `indices` is allowed and removes the body once.  n == 0 / n_add == 0 is XPBD_OK and changes nothing
+ * at all (history and the rest stay; the maps are the identity), and so is a device call none of whose flags is set.  Removing
+ * every body leaves a world of 0 bodies, as xpbd_world_upload_bodies(.., 0) does.
+ *
+ * XPBD_E_INVALID, with the world exactly as it was: a NULL world; a NULL list with n > 0 (dev_remove == NULL); NULL aos or
+ * shape_id with n_add > 0; a world without resident bodies (remove); an index >= xpbd_world_body_count; a body count that
+ * would exceed what xpbd_world_upload_bodies accepts; a bad added body, with the code xpbd_world_upload_bodies returns for it.
+ * Failure.  Every new array is staged in a buffer of its own and moved over the old one only after every allocation, copy and
+ * launch has succeeded: a failed call (XPBD_E_OOM, XPBD_E_HIP) leaves the previous population and settings in force.
+ *
+ * Not here: the multi-GPU world (global numbering across ranks and a collective re-plan need a design of their own);
+ * per-call settings for added bodies (use the setters afterwards); stable handles; END events for removed bodies.
+ * ------------------------------------------------------------------------- */
+int  xpbd_world_remove_bodies(xpbd_world *w, const uint32_t *indices, uint32_t n,
+                              uint32_t *old_to_new,        /* host [old body count] or NULL */
+                              uint32_t *joint_old_to_new,  /* host [old joint count] or NULL */
+                              uint32_t *n_bodies_out);     /* or NULL */
+int  xpbd_world_remove_bodies_device(xpbd_world *w, const uint8_t *dev_remove, /* device [body count], nonzero = remove */
+                                     uint32_t *dev_old_to_new,    /* device [old body count] or NULL */
+                                     uint32_t *joint_old_to_new,  /* host, as above */
+                                     uint32_t *n_bodies_out);
+int  xpbd_world_add_bodies(xpbd_world *w, const xpbd_rigid *aos, const uint32_t *shape_id, uint32_t n_add,
+                           uint32_t *first_index_out);     /* or NULL */
+
+/* ---------------------------------------------------------------------------
  * Scene queries (EXTENSION): the closest body along each of a batch of rays, at the bodies' current poses.  NOT in the
  * reference; its app would use it for picking under the cursor (src/app.rs, src/camera.rs).
  *
