@@ -563,35 +563,24 @@ template <class T> std::vector<T> local_rows(const std::vector<T> &global, const
     return local;
 }
 
-// The joint limits on the joints of shard s, re-indexed to the shard's joint numbering (the caller's order kept).
-int push_joint_limits(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &)
+// The records (limits or drives: both name a joint in .joint) on the joints of shard s, re-indexed to the shard's joint numbering
+// (the caller's order kept), handed to the shard's setter.
+template <class Record> int push_joint_records(const std::vector<Record> &global, const Shard &s, int (*set)(xpbd_world *, const Record *, uint32_t))
 {
-    std::vector<xpbd_joint_limit> local;
-    for (const xpbd_joint_limit &l : mw->limits) {
-        const auto at = std::lower_bound(s.joint_ids.begin(), s.joint_ids.end(), l.joint);
-        if (at != s.joint_ids.end() && *at == l.joint) {
-            xpbd_joint_limit m = l;
-            m.joint = (uint32_t)(at - s.joint_ids.begin());
-            local.push_back(m);
+    std::vector<Record> local;
+    for (const Record &r : global) {
+        const auto at = std::lower_bound(s.joint_ids.begin(), s.joint_ids.end(), r.joint);
+        if (at != s.joint_ids.end() && *at == r.joint) {
+            local.push_back(r);
+            local.back().joint = (uint32_t)(at - s.joint_ids.begin());
         }
     }
-    return xpbd_world_set_joint_limits(s.world, local.data(), (uint32_t)local.size());
+    return set(s.world, local.data(), (uint32_t)local.size());
 }
 
-// ... and the joint drives, the same way.
-int push_joint_drives(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &)
-{
-    std::vector<xpbd_joint_drive> local;
-    for (const xpbd_joint_drive &d : mw->drives) {
-        const auto at = std::lower_bound(s.joint_ids.begin(), s.joint_ids.end(), d.joint);
-        if (at != s.joint_ids.end() && *at == d.joint) {
-            xpbd_joint_drive m = d;
-            m.joint = (uint32_t)(at - s.joint_ids.begin());
-            local.push_back(m);
-        }
-    }
-    return xpbd_world_set_joint_drives(s.world, local.data(), (uint32_t)local.size());
-}
+int push_joint_limits(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &) { return push_joint_records(mw->limits, s, xpbd_world_set_joint_limits); }
+
+int push_joint_drives(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &) { return push_joint_records(mw->drives, s, xpbd_world_set_joint_drives); }
 
 int push_collision_filters(const xpbd_multi_world *mw, const Shard &s, const std::vector<uint32_t> &local_ids)
 {

@@ -37,6 +37,45 @@ uint32_t round_up(uint32_t v, uint32_t to) { return (v + to - 1) / to * to; }
 using xpbd::DeviceBuffer;
 using xpbd::set_error;
 
+// The joints of a world: what the caller handed to xpbd_world_set_joints, _set_joint_limits and _set_joint_drives, and the
+// device tables built from it in three parts, one per setter.  A part is complete or empty (count 0, no buffers); only
+// stage_csr, stage_limits and stage_extras fill one, aside, and a setter or a population change moves it in.
+namespace {
+struct JointTables {
+    xpbd::JointSet set;                         // joints, limits of all kinds and drives, the caller's order (limits and drives name
+                                                // joints by index: new joints drop them; a population change re-indexes all three)
+    std::vector<xpbd_joint_limit> slide_limits; // the XPBD_LIMIT_SLIDE ones among set.limits
+    struct Csr { // the joints and the CSR body -> joints
+        uint32_t n = 0;
+        DeviceBuffer joints, off, list;
+    } csr;
+    struct Limits { // the ANGULAR limits behind a CSR joint -> limits, the table the pair solve walks
+        uint32_t n_limits = 0;
+        DeviceBuffer limits, limit_off;
+    } limits;
+    struct Extras { // the lanes of k_joint_extras: the joints with extra entries (sliders, SLIDE limits, drives), the per-end sums
+        uint32_t n_extra_joints = 0;
+        DeviceBuffer sums, joints, slots, off, items;
+    } extras;
+
+    void fill(xpbd::ContactBuffers &c) const // (an empty part holds no buffer: NULL)
+    {
+        c.joints = csr.joints.as<xpbd::Joint>();
+        c.joint_off = csr.off.as<uint32_t>();
+        c.joint_list = csr.list.as<uint32_t>();
+        c.limits = limits.limits.as<xpbd::JointLimit>();
+        c.limit_off = limits.limit_off.as<uint32_t>();
+        c.joint_extra = extras.sums.as<double>();
+        c.extra_joints = extras.joints.as<uint32_t>();
+        c.extra_slots = extras.slots.as<uint32_t>();
+        c.extra_off = extras.off.as<uint32_t>();
+        c.extra_items = extras.items.as<xpbd::JointExtraItem>();
+        c.n_extra_joints = extras.n_extra_joints;
+    }
+    void clear() { *this = JointTables{}; }
+};
+} // namespace
+
 struct xpbd_world {
     int device = 0;
     uint32_t mode = XPBD_MODE_FUSED;
@@ -110,20 +149,8 @@ struct xpbd_world {
     DeviceBuffer frame_snapshot;
     bool frame_snapshot_valid = false, frame_snapshot_stepped = false;
     // Body-indexed settings: each names bodies (or the joints between them) by index, so a new set of bodies clears all four
-    // (adopt_body_count).  Plain values whose clear() restores the defaults; their device tables stay allocated beside them.
-    struct Joints { // xpbd_world_set_joints, xpbd_world_set_joint_limits, xpbd_world_set_joint_drives (limits and drives name
-                    // joints by index: new joints drop them)
-        uint32_t n = 0, n_limits = 0; // n_limits: the ANGULAR limits, the table the pair solve walks
-        uint32_t n_extra_joints = 0;  // joints with extra entries (sliders, SLIDE limits, drives): the lanes of k_joint_extras
-        std::vector<xpbd_joint> host; // the joints of the last set_joints: what xpbd_world_set_joint_limits checks against
-        std::vector<xpbd_joint_limit> limits;       // all limits of the last set_joint_limits, the caller's order (a population
-                                                    // change re-indexes them: xpbd_world_remove_bodies)
-        std::vector<xpbd_joint_limit> slide_limits; // the XPBD_LIMIT_SLIDE ones among them
-        std::vector<xpbd_joint_drive> drives;       // the drives of the last set_joint_drives, the caller's order
-        void clear() { *this = Joints{}; }
-    } joints;
-    DeviceBuffer jt_joints, jt_off, jt_list, jt_limits, jt_limit_off;
-    DeviceBuffer jt_extra, jt_extra_joints, jt_extra_slots, jt_extra_off, jt_extra_items; // ContactBuffers::joint_extra, extra_*
+    // (adopt_body_count).  Values whose clear() restores the defaults; the per-body device tables stay allocated beside theirs.
+    JointTables joints;
     struct Filters { // xpbd_world_set_collision_filters: group, mask per body (on), XPBD_FILTER_* flags
         bool on = false;
         uint32_t flags = 0;
@@ -213,11 +240,7 @@ struct xpbd_world {
         c.pair_codes = cb_pair_codes.as<uint8_t>();
         c.stats = cb_stats.as<unsigned long long>();
         c.scan_scratch = cb_scan.as<uint32_t>();
-        c.joints = joints.n ? jt_joints.as<xpbd::Joint>() : nullptr;
-        c.joint_off = joints.n ? jt_off.as<uint32_t>() : nullptr;
-        c.joint_list = joints.n ? jt_list.as<uint32_t>() : nullptr;
-        c.limits = joints.n_limits ? jt_limits.as<xpbd::JointLimit>() : nullptr;
-        c.limit_off = joints.n_limits ? jt_limit_off.as<uint32_t>() : nullptr;
+        joints.fill(c);
         c.filter = filters.on ? ft_filters.as<uint2>() : nullptr;
         c.slot_filter = filters.on ? cb_slot_filter.as<uint32_t>() : nullptr;
         c.filter_jointed = (filters.flags & XPBD_FILTER_JOINTED) ? 1u : 0u;
@@ -227,12 +250,6 @@ struct xpbd_world {
         c.restitution = restitution.on ? rs_restitution.as<double>() : nullptr;
         c.ground_restitution = restitution.ground;
         c.bounce_threshold = restitution.bounce_threshold;
-        c.joint_extra = joints.n_extra_joints ? jt_extra.as<double>() : nullptr;
-        c.extra_joints = joints.n_extra_joints ? jt_extra_joints.as<uint32_t>() : nullptr;
-        c.extra_slots = joints.n_extra_joints ? jt_extra_slots.as<uint32_t>() : nullptr;
-        c.extra_off = joints.n_extra_joints ? jt_extra_off.as<uint32_t>() : nullptr;
-        c.extra_items = joints.n_extra_joints ? jt_extra_items.as<xpbd::JointExtraItem>() : nullptr;
-        c.n_extra_joints = joints.n_extra_joints;
         return c;
     }
 
@@ -781,6 +798,17 @@ void absorb_stat_record(xpbd_world *w, const xpbd_rigid &body, uint32_t sid)
     }
 }
 
+// Before n more bodies are absorbed.  start_over: the bodies before them are gone (an upload, the first bodies of an empty
+// world); a changed shape count starts over too, with the property lost.
+void reset_stat_records(xpbd_world *w, bool start_over, uint32_t n)
+{
+    if (start_over || w->stat_shape_seen.size() != w->n_shapes) {
+        w->stat_shape_host.assign((size_t)w->n_shapes * xpbd::kStatRecDoubles, 0.0);
+        w->stat_shape_seen.assign(w->n_shapes, 0);
+        w->stat_shared = start_over && n != 0;
+    }
+}
+
 uint32_t stride_for(uint32_t n_bodies) { return round_up(n_bodies ? n_bodies : 1, 256); }
 
 // The body arrays hold n_new bodies from now on (the caller made room: stride_for(n_new)): what was derived from the old
@@ -828,14 +856,82 @@ int adopt_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id)
     return XPBD_OK;
 }
 
+// `bytes` (> 0) of `values` in a block of its own.
+int stage_upload(DeviceBuffer &fresh, const void *values, size_t bytes)
+{
+    XPBD_HIP_TRY(fresh.reserve(bytes));
+    XPBD_HIP_TRY(hipMemcpy(fresh.ptr, values, bytes, hipMemcpyHostToDevice));
+    return XPBD_OK;
+}
+
 // A per-body table of a setter: staged in a buffer of its own and moved over `table`, so that a failed allocation or copy
 // leaves the previous table in force.  The stream is idle (queued work may still read the present table).
 int upload_table(DeviceBuffer &table, const void *values, size_t bytes)
 {
     DeviceBuffer fresh;
-    XPBD_HIP_TRY(fresh.reserve(bytes));
-    XPBD_HIP_TRY(hipMemcpy(fresh.ptr, values, bytes, hipMemcpyHostToDevice));
+    XPBD_TRY(stage_upload(fresh, values, bytes));
     table = std::move(fresh);
+    return XPBD_OK;
+}
+
+// ---- the joint tables (JointTables): nothing but these three allocates or copies one ----------------------------------------
+// Each fills a fresh part from the host tables of xpbd_population_remap.hpp; the caller moves it in once nothing can fail any
+// more, so a failed call leaves the previous tables in force.  An empty part is left without blocks, so every table that is
+// copied has at least one element.  The device is bound.
+int stage_csr(const xpbd_joint *joints, uint32_t n_joints, const xpbd::JointCsr &csr, uint32_t n_bodies, JointTables::Csr &out)
+{
+    static_assert(sizeof(xpbd_joint) == sizeof(xpbd::Joint), "xpbd_joint must mirror xpbd::Joint");
+    if (n_joints == 0)
+        return XPBD_OK;
+    XPBD_TRY(stage_upload(out.joints, joints, (size_t)n_joints * sizeof(xpbd::Joint)));
+    XPBD_TRY(stage_upload(out.off, csr.off.data(), (size_t)(n_bodies + 1) * 4));
+    XPBD_TRY(stage_upload(out.list, csr.list.data(), (size_t)2 * n_joints * 4));
+    out.n = n_joints;
+    return XPBD_OK;
+}
+
+int stage_limits(const xpbd::LimitTables &t, JointTables::Limits &out)
+{
+    if (t.sorted.empty())
+        return XPBD_OK;
+    XPBD_TRY(stage_upload(out.limits, t.sorted.data(), t.sorted.size() * sizeof(xpbd::JointLimit)));
+    XPBD_TRY(stage_upload(out.limit_off, t.off.data(), t.off.size() * 4));
+    out.n_limits = (uint32_t)t.sorted.size();
+    return XPBD_OK;
+}
+
+// The per-end sums start as zeros, which is what the pair solve reads for a joint that is not listed.
+int stage_extras(const xpbd::ExtraTables &t, uint32_t n_joints, hipStream_t stream, JointTables::Extras &out)
+{
+    static_assert(xpbd::kExtraItemSlideLimit == xpbd::kExtraSlideLimit && sizeof(xpbd::ExtraItem) == sizeof(xpbd::JointExtraItem),
+                  "xpbd::ExtraItem must mirror xpbd::JointExtraItem");
+    if (t.list.empty())
+        return XPBD_OK;
+    const size_t sums = (size_t)2 * n_joints * xpbd::kJointExtraDoubles * 8;
+    XPBD_HIP_TRY(out.sums.reserve(sums));
+    XPBD_HIP_TRY(hipMemsetAsync(out.sums.ptr, 0, sums, stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(stream)); // done before the call returns: a stream the world is given later reads zeros too
+    XPBD_TRY(stage_upload(out.joints, t.list.data(), t.list.size() * 4));
+    XPBD_TRY(stage_upload(out.slots, t.slots.data(), t.slots.size() * 4));
+    XPBD_TRY(stage_upload(out.off, t.off.data(), t.off.size() * 4));
+    XPBD_TRY(stage_upload(out.items, t.items.data(), t.items.size() * sizeof(xpbd::ExtraItem)));
+    out.n_extra_joints = (uint32_t)t.list.size();
+    return XPBD_OK;
+}
+
+// All three from `set` in a world of n_bodies bodies: what the three setters, called in turn, would build.
+int stage_joint_tables(xpbd::JointSet set, uint32_t n_bodies, hipStream_t stream, JointTables &out)
+{
+    out.clear();
+    const uint32_t n_joints = (uint32_t)set.joints.size();
+    if (n_joints == 0)
+        return XPBD_OK;
+    xpbd::LimitTables lt = xpbd::build_limit_tables(set.limits.data(), (uint32_t)set.limits.size(), n_joints);
+    XPBD_TRY(stage_csr(set.joints.data(), n_joints, xpbd::build_joint_csr(set.joints.data(), n_joints, n_bodies), n_bodies, out.csr));
+    XPBD_TRY(stage_limits(lt, out.limits));
+    XPBD_TRY(stage_extras(xpbd::build_extra_tables(set.joints, lt.slide, set.drives, n_bodies), n_joints, stream, out.extras));
+    out.set = std::move(set);
+    out.slide_limits = std::move(lt.slide);
     return XPBD_OK;
 }
 } // namespace
@@ -921,11 +1017,7 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     // 2. the world takes the new size
     XPBD_TRY(adopt_body_count(w, n_new, max_shape_id));
     // mass properties shared per shape: the bodies that stay kept the property, the incoming ones are checked
-    if (w->stat_shape_seen.size() != w->n_shapes) {
-        w->stat_shape_host.assign((size_t)w->n_shapes * kStatRecDoubles, 0.0);
-        w->stat_shape_seen.assign(w->n_shapes, 0);
-        w->stat_shared = false;
-    }
+    reset_stat_records(w, false, n_incoming);
     for (uint32_t k = 0; k < n_incoming && w->stat_shared; ++k) {
         xpbd_rigid body;
         std::memcpy(&body, incoming39 + (size_t)k * rec, sizeof body);
@@ -1619,9 +1711,7 @@ try {
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     XPBD_TRY(adopt_body_count(w, n, max_shape_id));
-    w->stat_shape_host.assign((size_t)w->n_shapes * xpbd::kStatRecDoubles, 0.0);
-    w->stat_shape_seen.assign(w->n_shapes, 0);
-    w->stat_shared = n != 0;
+    reset_stat_records(w, true, n);
     for (uint32_t i = 0; i < n && w->stat_shared; ++i)
         absorb_stat_record(w, aos[i], shape_id ? shape_id[i] : 0u);
     if (n == 0)
@@ -1856,63 +1946,23 @@ try {
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
-namespace {
-// The table k_joint_extras walks, from the world's joints, SLIDE limits and drives: the joints that have extra entries
-// (ascending) and, per joint, its SLIDE limit followed by its drives in the caller's order.  The per-end sums start as zeros,
-// which is what the pair solve reads for a joint that is not listed.  The device is bound and the stream idle.
-int upload_joint_extras(xpbd_world *w)
-{
-    static_assert(xpbd::kExtraItemSlideLimit == xpbd::kExtraSlideLimit && sizeof(xpbd::ExtraItem) == sizeof(xpbd::JointExtraItem),
-                  "xpbd::ExtraItem must mirror xpbd::JointExtraItem");
-    xpbd_world::Joints &J = w->joints;
-    J.n_extra_joints = 0; // (a failed copy below leaves none rather than a torn table)
-    const xpbd::ExtraTables t = xpbd::build_extra_tables(J.host, J.slide_limits, J.drives, w->n);
-    const std::vector<uint32_t> &list = t.list, &slots = t.slots, &off = t.off;
-    const std::vector<xpbd::ExtraItem> &items = t.items;
-    if (list.empty())
-        return XPBD_OK;
-    const size_t sums = (size_t)2 * J.n * xpbd::kJointExtraDoubles * 8;
-    XPBD_HIP_TRY(w->jt_extra.reserve(sums));
-    XPBD_HIP_TRY(w->jt_extra_joints.reserve(list.size() * 4));
-    XPBD_HIP_TRY(w->jt_extra_slots.reserve(slots.size() * 4));
-    XPBD_HIP_TRY(w->jt_extra_off.reserve(off.size() * 4));
-    XPBD_HIP_TRY(w->jt_extra_items.reserve(items.size() * sizeof(xpbd::JointExtraItem)));
-    XPBD_HIP_TRY(hipMemsetAsync(w->jt_extra.ptr, 0, sums, w->stream));
-    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // (the world's stream may be another one by the time the table is read)
-    XPBD_HIP_TRY(hipMemcpy(w->jt_extra_joints.ptr, list.data(), list.size() * 4, hipMemcpyHostToDevice));
-    XPBD_HIP_TRY(hipMemcpy(w->jt_extra_slots.ptr, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
-    XPBD_HIP_TRY(hipMemcpy(w->jt_extra_off.ptr, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    XPBD_HIP_TRY(hipMemcpy(w->jt_extra_items.ptr, items.data(), items.size() * sizeof(xpbd::JointExtraItem), hipMemcpyHostToDevice));
-    J.n_extra_joints = (uint32_t)list.size();
-    return XPBD_OK;
-}
-} // namespace
-
+// The three joint setters: validate, stage the affected parts aside (stage_csr / stage_limits / stage_extras), then commit by
+// moves that cannot fail.  Queued substeps may still read the present tables: the stream is waited for first.
 int xpbd_world_set_joints(xpbd_world *w, const xpbd_joint *joints, uint32_t n_joints)
 try {
-    static_assert(sizeof(xpbd_joint) == sizeof(xpbd::Joint), "xpbd_joint must mirror xpbd::Joint");
     if (!w || (n_joints && !joints))
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joints: NULL argument");
     if (n_joints && w->mode != XPBD_MODE_CONTACTS) // only the contact pipeline projects joints: do not accept and ignore them
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joints: joints need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
     XPBD_TRY(xpbd::check_joints("xpbd_world_set_joints", joints, n_joints, w->n));
-    const xpbd::JointCsr csr = xpbd::build_joint_csr(joints, n_joints, w->n);
-    const std::vector<uint32_t> &off = csr.off, &list = csr.list;
-    if (int rc = bind_device(w))
-        return rc;
+    xpbd::JointSet set; // (limits and drives name joints by index: new joints drop them)
+    set.joints.assign(joints, joints + n_joints);
+    XPBD_TRY(bind_device(w));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    w->joints.clear(); // (limits name joints by index: new joints invalidate them)
-    if (n_joints == 0)
-        return XPBD_OK;
-    XPBD_HIP_TRY(w->jt_joints.reserve((size_t)n_joints * sizeof(xpbd::Joint)));
-    XPBD_HIP_TRY(w->jt_off.reserve((size_t)(w->n + 1) * 4));
-    XPBD_HIP_TRY(w->jt_list.reserve((size_t)2 * n_joints * 4));
-    XPBD_HIP_TRY(hipMemcpy(w->jt_joints.ptr, joints, (size_t)n_joints * sizeof(xpbd::Joint), hipMemcpyHostToDevice));
-    XPBD_HIP_TRY(hipMemcpy(w->jt_off.ptr, off.data(), (size_t)(w->n + 1) * 4, hipMemcpyHostToDevice));
-    XPBD_HIP_TRY(hipMemcpy(w->jt_list.ptr, list.data(), (size_t)2 * n_joints * 4, hipMemcpyHostToDevice));
-    w->joints.n = n_joints;
-    w->joints.host.assign(joints, joints + n_joints);
-    return upload_joint_extras(w); // (a slider has an extra entry of its own)
+    JointTables fresh;
+    XPBD_TRY(stage_joint_tables(std::move(set), w->n, w->stream, fresh)); // (a slider has an extra entry of its own; no joints: all empty)
+    w->joints = std::move(fresh);
+    return XPBD_OK;
 } XPBD_ABI_CATCH
 
 int xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, uint32_t n_limits)
@@ -1921,33 +1971,24 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_limits: NULL world");
     if (n_limits && w->mode != XPBD_MODE_CONTACTS)
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_limits: limits need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
-    if (int rc = xpbd::check_joint_limits("xpbd_world_set_joint_limits", w->joints.host.data(), w->joints.n, limits, n_limits))
-        return rc;
+    JointTables &J = w->joints;
+    XPBD_TRY(xpbd::check_joint_limits("xpbd_world_set_joint_limits", J.set.joints.data(), J.csr.n, limits, n_limits));
     // the SLIDE limits apart (entries of k_joint_extras), the angular ones behind a CSR joint -> limits
-    xpbd::LimitTables tables = xpbd::build_limit_tables(limits, n_limits, w->joints.n);
-    std::vector<xpbd_joint_limit> &slide = tables.slide;
-    const std::vector<xpbd_joint_limit> &sorted = tables.sorted;
-    const std::vector<uint32_t> &off = tables.off;
-    const uint32_t n_all = n_limits;
-    n_limits -= (uint32_t)slide.size();
-    if (int rc = bind_device(w))
-        return rc;
+    std::vector<xpbd_joint_limit> all(limits, limits + n_limits);
+    xpbd::LimitTables lt = xpbd::build_limit_tables(limits, n_limits, J.csr.n);
+    XPBD_TRY(bind_device(w));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    w->joints.limits.assign(limits, limits + n_all);
-    if (!slide.empty() || !w->joints.slide_limits.empty()) {
-        w->joints.slide_limits = std::move(slide);
-        XPBD_TRY(upload_joint_extras(w));
-    }
-    if (n_limits == 0) {
-        w->joints.n_limits = 0;
-        return XPBD_OK;
-    }
-    XPBD_HIP_TRY(w->jt_limits.reserve((size_t)n_limits * sizeof(xpbd::JointLimit)));
-    XPBD_HIP_TRY(w->jt_limit_off.reserve(off.size() * 4));
-    w->joints.n_limits = 0; // (a failed copy below leaves none rather than a torn table)
-    XPBD_HIP_TRY(hipMemcpy(w->jt_limits.ptr, sorted.data(), (size_t)n_limits * sizeof(xpbd::JointLimit), hipMemcpyHostToDevice));
-    XPBD_HIP_TRY(hipMemcpy(w->jt_limit_off.ptr, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    w->joints.n_limits = n_limits;
+    JointTables::Limits fresh;
+    XPBD_TRY(stage_limits(lt, fresh));
+    const bool slide_changes = !lt.slide.empty() || !J.slide_limits.empty();
+    JointTables::Extras extras;
+    if (slide_changes)
+        XPBD_TRY(stage_extras(xpbd::build_extra_tables(J.set.joints, lt.slide, J.set.drives, w->n), J.csr.n, w->stream, extras));
+    J.set.limits = std::move(all);
+    J.slide_limits = std::move(lt.slide);
+    J.limits = std::move(fresh);
+    if (slide_changes)
+        J.extras = std::move(extras);
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -1957,15 +1998,18 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_drives: NULL world");
     if (n_drives && w->mode != XPBD_MODE_CONTACTS)
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_drives: drives need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
-    if (int rc = xpbd::check_joint_drives("xpbd_world_set_joint_drives", w->joints.host.data(), w->joints.n, drives, n_drives))
-        return rc;
-    if (n_drives == 0 && w->joints.drives.empty())
+    JointTables &J = w->joints;
+    XPBD_TRY(xpbd::check_joint_drives("xpbd_world_set_joint_drives", J.set.joints.data(), J.csr.n, drives, n_drives));
+    if (n_drives == 0 && J.set.drives.empty())
         return XPBD_OK;
-    if (int rc = bind_device(w))
-        return rc;
+    std::vector<xpbd_joint_drive> all(drives, drives + n_drives);
+    XPBD_TRY(bind_device(w));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    w->joints.drives.assign(drives, drives + n_drives);
-    return upload_joint_extras(w);
+    JointTables::Extras fresh;
+    XPBD_TRY(stage_extras(xpbd::build_extra_tables(J.set.joints, J.slide_limits, all, w->n), J.csr.n, w->stream, fresh));
+    J.set.drives = std::move(all);
+    J.extras = std::move(fresh);
+    return XPBD_OK;
 } XPBD_ABI_CATCH
 
 int xpbd_world_set_collision_filters(xpbd_world *w, const xpbd_collision_filter *filters, uint32_t n, uint32_t flags)
@@ -2540,54 +2584,8 @@ namespace {
 struct PopulationStage {
     uint32_t n = 0, stride = 0;
     DeviceBuffer dyn, stat, shape_id, last_mask, aos_staging, filters, friction, restitution, dyn_alt, rs_start;
-    xpbd_world::Joints joints;
-    DeviceBuffer jt_joints, jt_off, jt_list, jt_limits, jt_limit_off, jt_extra, jt_extra_joints, jt_extra_slots, jt_extra_off, jt_extra_items;
+    JointTables joints;
 };
-
-int stage_upload(DeviceBuffer &fresh, const void *values, size_t bytes)
-{
-    XPBD_HIP_TRY(fresh.reserve(bytes ? bytes : 8));
-    if (bytes)
-        XPBD_HIP_TRY(hipMemcpy(fresh.ptr, values, bytes, hipMemcpyHostToDevice));
-    return XPBD_OK;
-}
-
-// The tables xpbd_world_set_joints / _set_joint_limits / _set_joint_drives would build from `set` in a world of n_bodies bodies.
-int stage_joint_tables(const xpbd::JointSet &set, uint32_t n_bodies, PopulationStage &st)
-{
-    xpbd_world::Joints &J = st.joints;
-    J.clear();
-    const uint32_t n_joints = (uint32_t)set.joints.size();
-    if (n_joints == 0)
-        return XPBD_OK;
-    const xpbd::JointCsr csr = xpbd::build_joint_csr(set.joints.data(), n_joints, n_bodies);
-    XPBD_TRY(stage_upload(st.jt_joints, set.joints.data(), (size_t)n_joints * sizeof(xpbd::Joint)));
-    XPBD_TRY(stage_upload(st.jt_off, csr.off.data(), (size_t)(n_bodies + 1) * 4));
-    XPBD_TRY(stage_upload(st.jt_list, csr.list.data(), (size_t)2 * n_joints * 4));
-    xpbd::LimitTables lt = xpbd::build_limit_tables(set.limits.data(), (uint32_t)set.limits.size(), n_joints);
-    if (!lt.sorted.empty()) {
-        XPBD_TRY(stage_upload(st.jt_limits, lt.sorted.data(), lt.sorted.size() * sizeof(xpbd::JointLimit)));
-        XPBD_TRY(stage_upload(st.jt_limit_off, lt.off.data(), lt.off.size() * 4));
-    }
-    const xpbd::ExtraTables et = xpbd::build_extra_tables(set.joints, lt.slide, set.drives, n_bodies);
-    if (!et.list.empty()) {
-        const size_t sums = (size_t)2 * n_joints * xpbd::kJointExtraDoubles * 8;
-        XPBD_HIP_TRY(st.jt_extra.reserve(sums));
-        XPBD_HIP_TRY(hipMemset(st.jt_extra.ptr, 0, sums));
-        XPBD_TRY(stage_upload(st.jt_extra_joints, et.list.data(), et.list.size() * 4));
-        XPBD_TRY(stage_upload(st.jt_extra_slots, et.slots.data(), et.slots.size() * 4));
-        XPBD_TRY(stage_upload(st.jt_extra_off, et.off.data(), et.off.size() * 4));
-        XPBD_TRY(stage_upload(st.jt_extra_items, et.items.data(), et.items.size() * sizeof(xpbd::ExtraItem)));
-    }
-    J.n = n_joints;
-    J.n_limits = (uint32_t)lt.sorted.size();
-    J.n_extra_joints = (uint32_t)et.list.size();
-    J.host = set.joints;
-    J.limits = set.limits;
-    J.slide_limits = std::move(lt.slide);
-    J.drives = set.drives;
-    return XPBD_OK;
-}
 
 // The new body arrays and per-body tables: new body s < n_keep is the present body dev_src[s] (NULL: body s), the n_add bodies
 // of `aos` follow.  Device bound, stream idle; enqueues on the world's stream and does not wait.
@@ -2656,16 +2654,6 @@ void commit_population(xpbd_world *w, PopulationStage &st, uint32_t max_shape_id
     take(w->dyn_alt, st.dyn_alt);
     take(w->rs_start, st.rs_start);
     w->joints = std::move(st.joints);
-    take(w->jt_joints, st.jt_joints);
-    take(w->jt_off, st.jt_off);
-    take(w->jt_list, st.jt_list);
-    take(w->jt_limits, st.jt_limits);
-    take(w->jt_limit_off, st.jt_limit_off);
-    take(w->jt_extra, st.jt_extra);
-    take(w->jt_extra_joints, st.jt_extra_joints);
-    take(w->jt_extra_slots, st.jt_extra_slots);
-    take(w->jt_extra_off, st.jt_extra_off);
-    take(w->jt_extra_items, st.jt_extra_items);
     take_body_count(w, st.n, max_shape_id);
 }
 
@@ -2694,7 +2682,7 @@ int remove_bodies(xpbd_world *w, const uint8_t *dev_remove, const uint32_t *indi
     uint32_t n_keep = 0;
     XPBD_HIP_TRY(hipMemcpyAsync(&n_keep, w->pop_prefix.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, w->stream));
     std::vector<uint32_t> map; // on the host only for the caller or for the joint re-index
-    if (old_to_new || w->joints.n) {
+    if (old_to_new || w->joints.csr.n) {
         map.resize(n);
         XPBD_HIP_TRY(hipMemcpyAsync(map.data(), w->pop_map.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, w->stream));
     }
@@ -2703,19 +2691,14 @@ int remove_bodies(xpbd_world *w, const uint8_t *dev_remove, const uint32_t *indi
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     if (n_keep > n)
         return set_error(XPBD_E_HIP, "xpbd_world_remove_bodies: the scan left %u survivors of %u bodies", n_keep, n);
-    std::vector<uint32_t> joint_map(w->joints.n);
+    std::vector<uint32_t> joint_map(w->joints.csr.n);
     if (n_keep == n) { // (the device variant with no flag set) nobody leaves: nothing changes, history and the rest stay
-        for (uint32_t j = 0; j < w->joints.n; ++j)
+        for (uint32_t j = 0; j < w->joints.csr.n; ++j)
             joint_map[j] = j;
     } else {
         PopulationStage st;
-        if (w->joints.n) {
-            xpbd::JointSet present;
-            present.joints = w->joints.host;
-            present.limits = w->joints.limits;
-            present.drives = w->joints.drives;
-            XPBD_TRY(stage_joint_tables(xpbd::remap_joint_set(present, map.data(), n, joint_map), n_keep, st));
-        }
+        if (w->joints.csr.n)
+            XPBD_TRY(stage_joint_tables(xpbd::remap_joint_set(w->joints.set, map.data(), n, joint_map), n_keep, w->stream, st.joints));
         XPBD_TRY(stage_bodies(w, w->pop_src.as<uint32_t>(), n_keep, nullptr, nullptr, 0, st));
         XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
         commit_population(w, st, w->max_shape_id); // (max_shape_id stays an upper bound)
@@ -2741,7 +2724,7 @@ try {
     if (n == 0) { // nothing at all: the maps are the identity
         for (uint32_t i = 0; old_to_new && i < w->n; ++i)
             old_to_new[i] = i;
-        for (uint32_t j = 0; joint_old_to_new && j < w->joints.n; ++j)
+        for (uint32_t j = 0; joint_old_to_new && j < w->joints.csr.n; ++j)
             joint_old_to_new[j] = j;
         if (n_bodies_out)
             *n_bodies_out = w->n;
@@ -2796,23 +2779,14 @@ try {
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the old arrays are freed at the end
     const uint32_t first = w->n;
     PopulationStage st;
-    if (w->joints.n) { // the same joints in a world of more bodies: the CSR body -> joints grows
-        xpbd::JointSet present;
-        present.joints = w->joints.host;
-        present.limits = w->joints.limits;
-        present.drives = w->joints.drives;
-        XPBD_TRY(stage_joint_tables(present, first + n_add, st));
-    }
+    if (w->joints.csr.n) // the same joints in a world of more bodies: the CSR body -> joints grows
+        XPBD_TRY(stage_joint_tables(w->joints.set, first + n_add, w->stream, st.joints));
     XPBD_TRY(stage_bodies(w, nullptr, first, aos, shape_id, n_add, st));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the caller's arrays are only borrowed
     commit_population(w, st, max_shape_id);
     // mass properties shared per shape: the bodies that stay kept the property, the appended ones are checked (a world that
     // was empty starts over, as an upload does)
-    if (first == 0 || w->stat_shape_seen.size() != w->n_shapes) {
-        w->stat_shape_host.assign((size_t)w->n_shapes * xpbd::kStatRecDoubles, 0.0);
-        w->stat_shape_seen.assign(w->n_shapes, 0);
-        w->stat_shared = first == 0;
-    }
+    reset_stat_records(w, first == 0, n_add);
     for (uint32_t i = 0; i < n_add && w->stat_shared; ++i)
         absorb_stat_record(w, aos[i], shape_id[i]);
     if (first_index_out)

@@ -277,7 +277,8 @@ int  xpbd_world_download_neighbours(xpbd_world *w, uint32_t *offsets, uint32_t *
  * joint; XPBD_JOINT_HINGE adds an angular term (below).  Joints are projected in XPBD_MODE_CONTACTS together
  * with the body-body contacts (same Jacobi pass, after a body's contacts, ascending joint index).
  * Body indices refer to the bodies uploaded last; uploading bodies again clears the joints.
- * Only XPBD_MODE_CONTACTS projects joints: in the other modes a non-empty list is XPBD_E_INVALID. */
+ * Only XPBD_MODE_CONTACTS projects joints: in the other modes a non-empty list is XPBD_E_INVALID.
+ * After a failed call (XPBD_E_OOM, XPBD_E_HIP) the previous joints, limits and drives are all still in force. */
 #define XPBD_JOINT_DISTANCE 0u  /* positional term only (distance = 0: ball joint) */
 /* (XPBD_JOINT_SLIDER = 2: see "SLIDERS and joint DRIVES" below) */
 #define XPBD_JOINT_HINGE    1u  /* positional term + ANGULAR term: the unit axes axis_a / axis_b (object space of a / b) are kept
@@ -318,7 +319,8 @@ int  xpbd_world_set_joints(xpbd_world *w, const xpbd_joint *joints, uint32_t n_j
  * a kind that does not fit the joint (HINGE needs XPBD_JOINT_HINGE, SWING and TWIST need XPBD_JOINT_DISTANCE with unit
  * axis_a / axis_b), two limits of one kind on one joint, a non-unit ref_a / ref_b or one not perpendicular to its axis
  * (HINGE, TWIST; |ref|^2 and ref . axis within 1e-3 as the hinge's axes), NaN bounds, bounds outside
- * -pi <= lower <= upper <= pi, SWING with lower != 0. */
+ * -pi <= lower <= upper <= pi, SWING with lower != 0.  After a failed call (XPBD_E_OOM, XPBD_E_HIP) the previous limits
+ * are still in force, as are the joints and the drives. */
 #define XPBD_LIMIT_HINGE 0u  /* joint kind HINGE: signed angle about a_w from r_a to r_b in [lower, upper] */
 #define XPBD_LIMIT_SWING 1u  /* joint kind DISTANCE: angle between a_w and b_w <= upper (lower must be 0) */
 #define XPBD_LIMIT_TWIST 2u  /* joint kind DISTANCE: signed twist about the bisector of a_w, b_w in [lower, upper] */
@@ -365,7 +367,8 @@ int  xpbd_world_set_joint_limits(xpbd_world *w, const xpbd_joint_limit *limits, 
  * drives stay in place): a world not in XPBD_MODE_CONTACTS, a joint index out of range, an unknown kind, a kind that does
  * not fit the joint, two angular or two linear drives on one joint, a non-unit ref_a / ref_b or one not perpendicular to its
  * axis (angular kinds; the limits' 1e-3 tolerances), a non-finite target, an ANGLE target outside [-pi, pi], a negative or
- * non-finite compliance, a max_force that is <= 0 or NaN. */
+ * non-finite compliance, a max_force that is <= 0 or NaN.  After a failed call (XPBD_E_OOM, XPBD_E_HIP) the previous drives
+ * are still in force, as are the joints and the limits. */
 #define XPBD_JOINT_SLIDER 2u              /* xpbd_joint.kind */
 #define XPBD_LIMIT_SLIDE 3u               /* xpbd_joint_limit.kind: joint kind SLIDER, s in [lower, upper] metres */
 #define XPBD_DRIVE_ANGLE 0u               /* joint kind HINGE or SLIDER: phi -> target (rad); refs as XPBD_LIMIT_HINGE */
