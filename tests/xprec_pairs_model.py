@@ -28,8 +28,14 @@ MUTATIONS = ("reference_sign", "arm_without_com", "transposed_inertia", "average
 JOINT_MUTATIONS = ("joint_sign_a", "anchor_without_com", "joints_from_integrated", "joints_uncounted", "nonbinding_counted",
                    "binding_twice", "hinge_without_compliance", "twist_unprojected", "limit_same_sign",
                    "joint_depenetration_limited", "joint_transposed_inertia")
-JOINT_DISTANCE, JOINT_HINGE = 0, 1                                       # XPBD_JOINT_*
-LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST = 0, 1, 2                          # XPBD_LIMIT_*
+# wrong readings of a joint's extra entries (xpbd.h, "SLIDERS and joint DRIVES"): sliders, SLIDE limits, drives.  A list of
+# its own beside JOINT_MUTATIONS, whose table (test_xprec_joints_oracle.py) names a scene per member.
+DRIVE_MUTATIONS = ("slider_keeps_positional", "perpendicular_sign_a", "extras_uncounted", "nonbinding_slide_counted",
+                   "drive_without_base_compliance", "clamp_by_h", "clamped_uncounted", "velocity_from_integrated",
+                   "extras_from_integrated", "wrap_dropped", "angular_drive_same_sign", "linear_drive_w_without_angular")
+JOINT_DISTANCE, JOINT_HINGE, JOINT_SLIDER = 0, 1, 2                      # XPBD_JOINT_*
+LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST, LIMIT_SLIDE = 0, 1, 2, 3          # XPBD_LIMIT_*
+DRIVE_ANGLE, DRIVE_ANGULAR_VELOCITY, DRIVE_POSITION, DRIVE_VELOCITY = 0, 1, 2, 3   # XPBD_DRIVE_*
 
 
 def shape(poly):
@@ -238,7 +244,8 @@ def manifold_points(manifolds):
     return inc, ref, pair, p_inc, p_ref
 
 
-def joint_terms(num, s, pos, rot, joints, limits, compliance, depenetration=None, mutation=None):
+def joint_terms(num, s, pos, rot, joints, limits, compliance, depenetration=None, mutation=None, drives=(), past=None,
+                integrated=None, h=None):
     """The joint entries of stage S's Jacobi pass, all evaluated on the pose (pos, rot) (3, n), (4, n): the pose after
     step 3.  joints / limits: records with the fields of xpbd_joint / xpbd_joint_limit (a limit belongs to `joint`; a joint's
     limits act in the caller's order).  Per joint, each a Jacobi entry of its own on both bodies:
@@ -251,20 +258,40 @@ def joint_terms(num, s, pos, rot, joints, limits, compliance, depenetration=None
                   rotation += 0.5 Quat(0, I^-1 (lambda n)) * rotation.
       limits      SWING, HINGE, TWIST as xpbd.h states them; err = phi - clamp(phi, lower, upper); err == 0 adds nothing,
                   not even to the count; otherwise lambda = err / (w + compliance), turned like the hinge term.
+      extras      (xpbd.h, "SLIDERS and joint DRIVES") a SLIDER has the hinge entry and no positional one.  With d = p_b - p_a,
+                  a_w = q_a axis_a, s = d . a_w, W(body, p, n) the positional term's w of one body, Wang(n) the limits' w, and
+                  a subscript 0 the same expression on `past` = (position, rotation) (3, n), (4, n) at the start of the
+                  substep: the perpendicular term r = d - a_w s (|r| = 0: no entry), lambda = |r| / (W_a + W_b + c), +lambda n
+                  on a at p_a, -lambda n on b at p_b; the SLIDE limit e = s - clamp(s, lower, upper) (0: nothing), n = a_w,
+                  applied alike; then the joint's `drives` (records of xpbd_joint_drive) in the caller's order, e as the
+                  header's table, lambda = e / (w + (1e-6 + alpha) / h^2) clamped to +-max_force h^2, w = Wang(a_w) and
+                  turned like a limit (angular kinds) or W_a + W_b and pushed like the SLIDE limit (linear kinds).  A joint's
+                  extras are summed among themselves and added after its other entries.  `h` in model scalars.
     Returns (sum of position terms (3, n), sum of rotation terms (4, n), count (n,), info): info holds per body n_joint (its
-    entries), n_binding (its binding limits), limit_margin (smallest |phi - nearer bound| of its limits, radians),
-    wrap_margin (smallest pi - |phi|) and joint_cond (smallest non-zero s, |bisector|, |delta| or anchor distance: what a
-    direction is normalised by), and per limit the list `limits` of (joint, kind, phi, err) in f64."""
-    assert mutation is None or mutation in JOINT_MUTATIONS
+    entries, extras included), n_extra (its extra entries), n_clamped (those whose lambda was clamped), slide_margin
+    (smallest |s - bound| of its SLIDE limits, metres), drive_margin (smallest |e| of its drives), drive_wrap_margin
+    (smallest |pi - |x|| of the argument x of wrap, which jumps at +-pi), the lists `slides` of (joint, s, e), `perps` of
+    (joint, |r|) and `drives` of (index in the caller's list, kind, e, clamped, phi or s), n_binding (its binding limits),
+    limit_margin (smallest |phi - nearer bound| of its limits, radians), wrap_margin (smallest pi - |phi|) and joint_cond
+    (smallest non-zero s, |bisector|, |delta|, |r| or anchor distance: what a direction is normalised by), and per limit the
+    list `limits` of (joint, kind, phi, err) in f64."""
+    assert mutation is None or mutation in JOINT_MUTATIONS + DRIVE_MUTATIONS
     sqrt = num.sqrt
     im, M, com = s["inverse_mass"], s["inverse_inertia"], s["center_of_mass"]
     n = pos.shape[1]
     sum_p, sum_q, count = pos * 0, rot * 0, np.zeros(n, dtype=np.int64)
     info = {"n_joint": np.zeros(n, dtype=np.int64), "n_binding": np.zeros(n, dtype=np.int64), "limit_margin": np.full(n, np.inf),
-            "wrap_margin": np.full(n, np.inf), "joint_cond": np.full(n, np.inf), "limits": []}
+            "wrap_margin": np.full(n, np.inf), "joint_cond": np.full(n, np.inf), "limits": [],
+            "n_extra": np.zeros(n, dtype=np.int64), "n_clamped": np.zeros(n, dtype=np.int64), "slide_margin": np.full(n, np.inf),
+            "drive_margin": np.full(n, np.inf), "drive_wrap_margin": np.full(n, np.inf), "slides": [], "perps": [], "drives": []}
     by_joint = [[] for _ in range(len(joints))]
     for lim in limits:
         by_joint[int(lim["joint"])].append(lim)
+    drives_of = [[] for _ in range(len(joints))]
+    for index, drv in enumerate(drives):
+        drives_of[int(drv["joint"])].append((index, drv))
+    # the poses the extras are read at: those of every other joint entry
+    e_pos, e_rot = integrated if mutation == "extras_from_integrated" else (pos, rot)
 
     def vec(x):
         return num.conv(np.asarray(x, dtype=np.float64))
@@ -301,20 +328,33 @@ def joint_terms(num, s, pos, rot, joints, limits, compliance, depenetration=None
         entry(a, None, matvec(inertia(a), n_axis * lam), counts)
         entry(b, None, matvec(inertia(b), n_axis * (lam if same_sign else -lam)), counts)
 
+    def anchors(P, Q, jt):
+        """World anchors (p_a, p_b) and body origins of a joint on the poses (P, Q)."""
+        p, origin = [], []
+        for body, anchor in ((int(jt["body_a"]), jt["anchor_a"]), (int(jt["body_b"]), jt["anchor_b"])):
+            o = P[:, body] + com[:, body]                                   # the body's origin in the world: position + com
+            frame_p = o + qrot(Q[:, body], -com[:, body])                   # Rigid::frame, rigid.rs:75-80
+            if mutation == "anchor_without_com":
+                frame_p = P[:, body]
+            p.append(frame_apply(frame_p, Q[:, body], vec(anchor)))
+            origin.append(o)
+        return p, origin
+
+    def hinge_phi(Q, a, b, axis_a, ref_a, ref_b):
+        """The angle of XPBD_LIMIT_HINGE on the rotations Q."""
+        n_axis = qrot(Q[:, a], vec(axis_a))
+        r_a, r_b = qrot(Q[:, a], vec(ref_a)), qrot(Q[:, b], vec(ref_b))
+        return num.atan2(dot(cross(r_a, r_b), n_axis), dot(r_a, r_b))
+
     for k, jt in enumerate(joints):
         a, b = int(jt["body_a"]), int(jt["body_b"])
-        p, origin = [], []
-        for body, anchor in ((a, jt["anchor_a"]), (b, jt["anchor_b"])):
-            o = pos[:, body] + com[:, body]                                 # the body's origin in the world: position + com
-            frame_p = o + qrot(rot[:, body], -com[:, body])                 # Rigid::frame, rigid.rs:75-80
-            if mutation == "anchor_without_com":
-                frame_p = pos[:, body]
-            p.append(frame_apply(frame_p, rot[:, body], vec(anchor)))
-            origin.append(o)
+        slider = int(jt["kind"]) == JOINT_SLIDER
+        p, origin = anchors(pos, rot, jt)
         diff = p[1] - p[0]                                                  # constraint.rs:13-15, contacts = (p_a, p_b)
         dist = sqrt(dot(diff, diff))
-        conditioned((a, b), dist)
-        if dist != 0:
+        if not slider:
+            conditioned((a, b), dist)
+        if dist != 0 and (not slider or mutation == "slider_keeps_positional"):
             direction = diff / dist
             w = 0
             for body, point, o in ((a, p[0], origin[0]), (b, p[1], origin[1])):
@@ -328,7 +368,7 @@ def joint_terms(num, s, pos, rot, joints, limits, compliance, depenetration=None
                                             (b, p[1], origin[1], direction * -lam)):
                 entry(body, impulse * im[body], cross(matvec(inertia(body), point - o), impulse))
         a_w, b_w = qrot(rot[:, a], vec(jt["axis_a"])), qrot(rot[:, b], vec(jt["axis_b"]))
-        if int(jt["kind"]) == JOINT_HINGE:
+        if int(jt["kind"]) != JOINT_DISTANCE:                               # HINGE and SLIDER
             delta = cross(a_w, b_w)
             mag = sqrt(dot(delta, delta))
             conditioned((a, b), mag)
@@ -336,6 +376,8 @@ def joint_terms(num, s, pos, rot, joints, limits, compliance, depenetration=None
                 angular(a, b, delta / mag, mag, with_compliance=mutation != "hinge_without_compliance")
         for lim in by_joint[k]:
             kind = int(lim["kind"])
+            if kind == LIMIT_SLIDE:                                         # the slider rule, among the extras below
+                continue
             if kind == LIMIT_SWING:
                 c = cross(a_w, b_w)
                 sine = sqrt(dot(c, c))
@@ -373,11 +415,124 @@ def joint_terms(num, s, pos, rot, joints, limits, compliance, depenetration=None
                 continue
             info["n_binding"][[a, b]] += 1
             angular(a, b, n_axis, error, counts=2 if mutation == "binding_twice" else 1, same_sign=mutation == "limit_same_sign")
+        # ---- the joint's extra entries, summed among themselves from 0 -------------------------------------------------------
+        slides = [lim for lim in by_joint[k] if int(lim["kind"]) == LIMIT_SLIDE]
+        if not (slider or slides or drives_of[k]):
+            continue
+        ex_p = {a: pos[:, a] * 0, b: pos[:, b] * 0}
+        ex_q = {a: rot[:, a] * 0, b: rot[:, b] * 0}
+        ex_n, ex_entries = {a: 0, b: 0}, {a: 0, b: 0}
+        p, origin = anchors(e_pos, e_rot, jt)
+        n_axis = qrot(e_rot[:, a], vec(jt["axis_a"]))                       # a_w
+        d = p[1] - p[0]
+        travel = dot(d, n_axis)                                             # s
+
+        def extra(body, dp, turn, counted=True):
+            if dp is not None:
+                ex_p[body] = ex_p[body] + dp
+            ex_q[body] = ex_q[body] + qmul(pure(turn) * 0.5, e_rot[:, body])
+            ex_n[body] += 1 if counted else 0
+            ex_entries[body] += 1
+
+        def w_linear(direction, angular_half=True):
+            w = 0
+            for body, point, o in ((a, p[0], origin[0]), (b, p[1], origin[1])):
+                w = w + im[body]
+                if angular_half:
+                    local = qrot(conj(e_rot[:, body]), cross(point - o, direction))
+                    w = w + dot(matvec(inertia(body), local), local)
+            return w
+
+        def w_angular(direction):
+            w = 0
+            for body in (a, b):
+                local = qrot(conj(e_rot[:, body]), direction)
+                w = w + dot(matvec(inertia(body), local), local)
+            return w
+
+        def push(direction, lam, counted=True, sign_a=1):
+            """+lambda direction on a at p_a, -lambda direction on b at p_b (Rigid::apply_impulse)."""
+            for body, point, o, impulse in ((a, p[0], origin[0], direction * (lam * sign_a)), (b, p[1], origin[1], direction * -lam)):
+                extra(body, impulse * im[body], cross(matvec(inertia(body), point - o), impulse), counted)
+
+        if slider:                                                          # 1. the perpendicular term
+            r = d - n_axis * travel
+            length = sqrt(dot(r, r))
+            conditioned((a, b), length)
+            info["perps"].append((k, as_float(length)))
+            if length != 0:
+                direction = r / length
+                push(direction, length / (w_linear(direction) + compliance), sign_a=-1 if mutation == "perpendicular_sign_a" else 1)
+        for lim in slides:                                                  # 2. XPBD_LIMIT_SLIDE
+            lower, upper = vec([lim["lower"], lim["upper"]])
+            error = travel - min(max(travel, lower), upper)
+            info["slides"].append((k, as_float(travel), as_float(error)))
+            for body in (a, b):
+                info["slide_margin"][body] = min(info["slide_margin"][body], abs(as_float(travel - lower)), abs(as_float(travel - upper)))
+            if error == 0:
+                if mutation == "nonbinding_slide_counted":
+                    ex_n[a] += 1
+                    ex_n[b] += 1
+                continue
+            push(n_axis, error / (w_linear(n_axis) + compliance))
+        pi = num.atan2(vec([1.0])[0], vec([1.0])[0]) * 4
+        for index, drv in drives_of[k]:                                     # 3. the drives, in the caller's order
+            kind = int(drv["kind"])
+            target, alpha, max_force = vec([drv["target"], drv["compliance"], drv["max_force"]])
+            at_start = integrated if mutation == "velocity_from_integrated" else past
+            angular_kind = kind in (DRIVE_ANGLE, DRIVE_ANGULAR_VELOCITY)
+            if angular_kind:
+                measure = hinge_phi(e_rot, a, b, jt["axis_a"], drv["ref_a"], drv["ref_b"])
+                if kind == DRIVE_ANGLE:
+                    x = measure - target
+                else:
+                    x = measure - hinge_phi(at_start[1], a, b, jt["axis_a"], drv["ref_a"], drv["ref_b"])
+                wrapped = x if mutation == "wrap_dropped" else (x - pi * 2 if x > pi else (x + pi * 2 if x < -pi else x))
+                error = wrapped if kind == DRIVE_ANGLE else wrapped - target * h
+                margin = abs(np.pi - abs(as_float(x)))                   # x lies in (-2 pi, 2 pi): the jumps are at +-pi
+                for body in (a, b):
+                    info["drive_wrap_margin"][body] = min(info["drive_wrap_margin"][body], margin)
+                w = w_angular(n_axis)
+            else:
+                measure = travel
+                if kind == DRIVE_POSITION:
+                    error = travel - target
+                else:
+                    assert kind == DRIVE_VELOCITY
+                    p0, _ = anchors(at_start[0], at_start[1], jt)
+                    error = (travel - dot(p0[1] - p0[0], qrot(at_start[1][:, a], vec(jt["axis_a"])))) - target * h
+                w = w_linear(n_axis, angular_half=mutation != "linear_drive_w_without_angular")
+            for body in (a, b):
+                info["drive_margin"][body] = min(info["drive_margin"][body], abs(as_float(error)))
+            if error == 0:
+                info["drives"].append((index, kind, 0.0, False, as_float(measure)))
+                continue
+            base = alpha if mutation == "drive_without_base_compliance" else alpha + vec([1e-6])[0]
+            lam = error / (w + base / (h * h))
+            cap = max_force * (h if mutation == "clamp_by_h" else h * h)
+            clamped = bool(lam > cap or lam < -cap)
+            lam = min(max(lam, -cap), cap)
+            info["drives"].append((index, kind, as_float(error), clamped, as_float(measure)))
+            counted = not (clamped and mutation == "clamped_uncounted")
+            if clamped:
+                info["n_clamped"][[a, b]] += 1
+            if angular_kind:
+                extra(a, None, matvec(inertia(a), n_axis * lam), counted)
+                extra(b, None, matvec(inertia(b), n_axis * (lam if mutation == "angular_drive_same_sign" else -lam)), counted)
+            else:
+                push(n_axis, lam, counted)
+        for body in (a, b):                                                 # ... and added after the joint's other entries
+            if ex_n[body] or ex_entries[body]:
+                sum_p[:, body] = sum_p[:, body] + ex_p[body]
+                sum_q[:, body] = sum_q[:, body] + ex_q[body]
+                count[body] += 0 if mutation in ("extras_uncounted", "joints_uncounted") else ex_n[body]
+                info["n_extra"][body] += ex_entries[body]
+                info["n_joint"][body] += ex_entries[body]
     return sum_p, sum_q, count, info
 
 
 def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.inf, max_depenetration_speed=0.0, num=None,
-            mutation=None, tau=0.0, joints=(), limits=()):
+            mutation=None, tau=0.0, joints=(), limits=(), drives=()):
     """Stage S: one contacts substep (steps 1, 3, 4, 5 of xpbd_pairs_oracle.h) of n bodies ((n, 38) f64).  shapes: list of
     shape() dicts.  manifolds: {(i, j), i < j: {"feature", "p_ref": [(3,)], "p_inc": [(3,)]}} of the touching pairs at the
     post-integrate frames, or None: stage N on every pair (stage S o N, the fully independent substep).  mu: per-body
@@ -386,15 +541,18 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     records with the fields of xpbd_joint / xpbd_joint_limit: all their entries are evaluated on the poses after step 3, in
     the same Jacobi pass as the pair points, and a body applies the average of ALL its entries -- pair points, positional
     joint entries, hinge entries and binding limits each count 1 (joint_terms).  Friction and the depenetration limit never
-    touch a joint entry.
+    touch a joint entry.  drives: records of xpbd_joint_drive; a joint's extra entries (SLIDER, XPBD_LIMIT_SLIDE, drives) are
+    read at the same poses, the velocity drives' subscript-0 quantities at the poses the substep started from, and each
+    counts 1 in the same average (joint_terms).
 
     Returns a dict: state (n, 38) model scalars; frames: the post-integrate frames [(position, rotation)]; manifolds: the
     ones used; per body: mask, margin, cond, flip_margin, domain (as xprec_model.step), branch (smallest distance in
     metres of a friction or depenetration-limit comparison from its threshold) and pair_cond (smallest |c1 - c0| of a
     pair point); undecided: the pairs whose stage N manifold has a margin in (0, tau]; n_points (pair-contact points of the
-    body) and, from joint_terms, n_joint, n_binding, limit_margin, wrap_margin, joint_cond and `limits`."""
-    assert mutation is None or mutation in MUTATIONS + JOINT_MUTATIONS
-    joint_mutation = mutation if mutation in JOINT_MUTATIONS else None
+    body) and, from joint_terms, n_joint, n_binding, limit_margin, wrap_margin, joint_cond, `limits` and the extras' n_extra,
+    n_clamped, slide_margin, drive_margin, drive_wrap_margin, `slides`, `perps`, `drives`."""
+    assert mutation is None or mutation in MUTATIONS + JOINT_MUTATIONS + DRIVE_MUTATIONS
+    joint_mutation = mutation if mutation in JOINT_MUTATIONS + DRIVE_MUTATIONS else None
     num = num or xm.native()
     sqrt = num.sqrt
     b64 = np.ascontiguousarray(bodies, dtype=np.float64).reshape(-1, 38)
@@ -504,7 +662,9 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     n_points = count.copy()
     # ... and the joints' entries, from the same poses, in the same average
     at = (integrated_pos, integrated_rot) if joint_mutation == "joints_from_integrated" else (pos, rot)
-    joint_p, joint_q, joint_count, joint_info = joint_terms(num, s, at[0], at[1], joints, limits, compliance, limit, joint_mutation)
+    joint_p, joint_q, joint_count, joint_info = joint_terms(
+        num, s, at[0], at[1], joints, limits, compliance, limit, joint_mutation, drives=drives, past=(past_pos, past_rot),
+        integrated=(integrated_pos, integrated_rot), h=hx)
     if len(joints):
         sum_p, sum_q, count = sum_p + joint_p, sum_q + joint_q, count + joint_count
     hit = np.nonzero(count)[0]
