@@ -322,6 +322,52 @@ __device__ __forceinline__ int32_t clamp_axis(const QueryGrid &g, int a, double 
     return (int32_t)(q > hi ? hi : q);
 }
 
+// ---- the line walk shared by the rays and the sweeps' centre lines ------------------------------------------------------------
+// Clip the line o + t * d, t in [0, tmax], to the grid's box grown by `grow` on every side: [t_near, t_far]; false: the line
+// misses the box.  A ray passes grow = 0.0 and gets the plain box, bit for bit: x - 0.0 is x for every x, and hi + 0.0 differs
+// from hi only for hi = -0.0, which (double)(a sum of integers) * edge cannot produce (such a sum is never -0.0, edge > 0).
+__device__ __forceinline__ bool clip_to_grid(const QueryGrid &g, const double (&o)[3], const double (&d)[3], double tmax, double grow,
+                                             double &t_near, double &t_far)
+{
+    t_near = 0.0, t_far = tmax;
+    bool inside = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double lo = (double)g.lo[a] * g.edge - grow, hi = ((double)g.lo[a] + (double)g.dims[a]) * g.edge + grow;
+        if (d[a] == 0.0) {
+            inside = inside && o[a] >= lo && o[a] <= hi;
+        } else {
+            const double t1 = (lo - o[a]) / d[a], t2 = (hi - o[a]) / d[a];
+            const double tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1;
+            t_near = tn > t_near ? tn : t_near;
+            t_far = tf < t_far ? tf : t_far;
+        }
+    }
+    return inside && t_near <= t_far;
+}
+
+// The axis of the nearest cell face ahead of `cell` and its t (-1 and +inf: the line does not move).  Each face's t comes from
+// its own coordinate (no accumulated error); a line through an edge or a corner steps one axis at a time (first axis first),
+// with equal t.
+__device__ __forceinline__ int next_face(const QueryGrid &g, const int32_t (&cell)[3], const int32_t (&step)[3], const double (&o)[3],
+                                         const double (&d)[3], double &t_next)
+{
+    double nearest = INFINITY; // (a local, not t_next, on purpose: a measured constraint, see DESIGN, "One walk, measured")
+    int axis = -1;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        if (step[a] != 0) {
+            const double face = (double)(cell[a] + (step[a] > 0 ? 1 : 0)) * g.edge;
+            const double ta = (face - o[a]) / d[a];
+            if (ta < nearest) {
+                nearest = ta;
+                axis = a;
+            }
+        }
+    t_next = nearest;
+    return axis;
+}
+
 // Every body into every cell its padded sphere box overlaps: FILL = false counts the cells' populations, true lists the bodies.
 template <bool FILL>
 __global__ void __launch_bounds__(kBlock) k_query_bin(uint32_t n, const double *__restrict__ rec, const QueryGrid *__restrict__ grid,
@@ -374,22 +420,8 @@ __global__ void __launch_bounds__(kBlock) k_query_walk(const xpbd_ray *__restric
             test_body(ray, rec, shape_id, gid, t, i, best);
     } else if (ray.valid && g.mode == kGrid) {
         const double o[3] = {ray.o.x, ray.o.y, ray.o.z}, d[3] = {ray.d.x, ray.d.y, ray.d.z};
-        // clip to the grid's box: [t_near, t_far]
-        double t_near = 0.0, t_far = ray.tmax;
-        bool inside = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double lo = (double)g.lo[a] * g.edge, hi = ((double)g.lo[a] + (double)g.dims[a]) * g.edge;
-            if (d[a] == 0.0) {
-                inside = inside && o[a] >= lo && o[a] <= hi;
-            } else {
-                const double t1 = (lo - o[a]) / d[a], t2 = (hi - o[a]) / d[a];
-                const double tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1;
-                t_near = tn > t_near ? tn : t_near;
-                t_far = tf < t_far ? tf : t_far;
-            }
-        }
-        if (inside && t_near <= t_far) {
+        double t_near, t_far;
+        if (clip_to_grid(g, o, d, ray.tmax, 0.0, t_near, t_far)) {
             int32_t cell[3], step[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -408,20 +440,8 @@ __global__ void __launch_bounds__(kBlock) k_query_walk(const xpbd_ray *__restric
                 const uint32_t s1 = cell_start[key + 1];
                 for (uint32_t s = cell_start[key]; s < s1; ++s)
                     test_body(ray, rec, shape_id, gid, t, items[s], best);
-                // the next cell: the nearest face ahead, each face's t from its own coordinate (no accumulated error); a
-                // ray through an edge or a corner steps one axis at a time (first axis first), with equal t
-                double t_next = INFINITY;
-                int axis = -1;
-#pragma unroll
-                for (int a = 0; a < 3; ++a)
-                    if (step[a] != 0) {
-                        const double face = (double)(cell[a] + (step[a] > 0 ? 1 : 0)) * g.edge;
-                        const double ta = (face - o[a]) / d[a];
-                        if (ta < t_next) {
-                            t_next = ta;
-                            axis = a;
-                        }
-                    }
+                double t_next;
+                const int axis = next_face(g, cell, step, o, d, t_next);
                 if (axis < 0 || t_next > t_far)
                     break;
                 cell[axis] += step[axis];
@@ -700,19 +720,109 @@ __device__ __forceinline__ bool overlap_decide(Lds &s, const PolytopeTables &t, 
     return true;
 }
 
-struct OverlapArgs {
-    const xpbd_overlap_query *queries;
-    const double *qrec;         // k_overlap_queries
+// What the overlap pass and the sweep pass are both given (n: queries or sweeps).
+struct PassArgs {
+    const double *qrec;         // k_overlap_queries or k_sweep_queries
     const double *rec;          // k_query_bodies
     const uint32_t *gid;        // the index a body is known by (null: its slot); XPBD_NO_HIT bodies have radius < 0 in rec
     const uint2 *filter;        // collision filters (null: every body in group ~0u)
     const QueryGrid *grid;      // grid path only
     const uint32_t *cell_start;
     const uint32_t *items;
+    uint32_t n, masked, brute;
+};
+
+struct OverlapArgs : PassArgs {
+    const xpbd_overlap_query *queries;
     uint32_t *offsets;          // count pass: offsets[q] = hits of q; fill pass: the scanned array
     xpbd_overlap_hit *hits;
-    uint32_t n_queries, cap, masked, brute;
+    uint32_t cap;
 };
+
+// The part of a candidate's admission that reads its record alone (one lane): a body that can be hit at all, not the one to
+// ignore, in a group of the mask.  Its bounding sphere comes back for the caller's own last test.
+__device__ __forceinline__ bool admit_record(const PassArgs &a, uint32_t i, uint32_t ignore, uint32_t mask, Vec3 &centre, double &radius)
+{
+    const double2 *r = reinterpret_cast<const double2 *>(a.rec + (size_t)i * kQueryRecDoubles);
+    const double2 d = r[3], e = r[4], f = r[5];
+    centre = Vec3{d.y, e.x, e.y};
+    radius = f.x;
+    if (!(radius >= 0.0))
+        return false;
+    if ((a.gid ? a.gid[i] : i) == ignore)
+        return false;
+    return !(a.masked && ((a.filter ? a.filter[i].x : ~0u) & mask) == 0);
+}
+
+// each(i), by the whole group, for every body the lanes of the group hold in `mine` (kNoBody: none), in lane order.
+template <uint32_t L, class Each>
+__device__ __forceinline__ void for_each_held(uint32_t mine, Each &&each)
+{
+    uint64_t todo = group_bits<L>(__ballot(mine != kNoBody));
+    while (todo) {
+        const uint32_t src = (uint32_t)__ffsll((long long)todo) - 1u;
+        todo &= todo - 1;
+        each((uint32_t)__shfl((int)mine, (int)src, L));
+    }
+}
+
+// The bodies listed in the box of cells qlo .. qlo + qdim - 1, each once: lane `lane` of a group of L takes cells lane, lane + L,
+// ... of the box, admits the bodies listed there -- admit(i, centre, radius), one lane -- and whenever every lane holds a survivor
+// or has run out of cells the group calls decide(mine).  seen(axis, lo, hi) is asked about the body's cell range on every axis:
+// true on all three drops the body (the sweeps' "the previous stretch's box met it").
+template <uint32_t L, class Admit, class Seen, class Decide>
+__device__ __forceinline__ void walk_cell_box(const QueryGrid &g, const int32_t (&qlo)[3], const uint32_t (&qdim)[3], const uint32_t *cell_start,
+                                              const uint32_t *items, uint32_t lane, Admit &&admit, Seen &&seen, Decide &&decide)
+{
+    const uint32_t cells = qdim[0] * qdim[1] * qdim[2];
+    uint32_t next = lane, at = 0, end = 0, first = 0;
+    int32_t cell[3] = {0, 0, 0};
+    for (;;) {
+        uint32_t mine = kNoBody;
+        while (mine == kNoBody) {
+            if (at == end) { // this lane's next cell
+                if (next >= cells)
+                    break;
+                const uint32_t zy = next / qdim[0];
+                cell[0] = qlo[0] + (int32_t)(next - zy * qdim[0]);
+                cell[1] = qlo[1] + (int32_t)(zy % qdim[1]);
+                cell[2] = qlo[2] + (int32_t)(zy / qdim[1]);
+                next += L;
+                const uint32_t key = query_key(g, cell[0], cell[1], cell[2]);
+                first = at = cell_start[key];
+                end = cell_start[key + 1];
+                continue;
+            }
+            const uint32_t slot = at++, i = items[slot];
+            Vec3 cb;
+            double rb;
+            if (!admit(i, cb, rb))
+                continue;
+            // A body is listed in up to 8 cells and the box covers several: the pair counts in ONE cell, the component-wise
+            // maximum of the lower corners of the two cell ranges (k_query_bin's expressions).  A hashed key is shared by
+            // several cells: the body must really be listed in this one, and once.
+            const double c[3] = {cb.x, cb.y, cb.z};
+            bool here = true, before = true;
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                const int32_t lo = clamp_axis(g, ax, floor((c[ax] - rb - g.pad) / g.edge));
+                int32_t hi = clamp_axis(g, ax, floor((c[ax] + rb + g.pad) / g.edge));
+                hi = hi > lo + 1 ? lo + 1 : hi;
+                here = here && cell[ax] == (lo > qlo[ax] ? lo : qlo[ax]) && cell[ax] <= hi;
+                before = before && seen(ax, lo, hi);
+            }
+            here = here && !before;
+            if (here && !g.dense)
+                for (uint32_t e = first; e < slot; ++e)
+                    here = here && items[e] != i;
+            if (here)
+                mine = i;
+        }
+        if (!group_bits<L>(__ballot(mine != kNoBody)))
+            break; // every lane has run out of cells
+        decide(mine);
+    }
+}
 
 // Count (FILL = false) or list (true) the hits of every query: one group of L lanes per query, 64 / L queries per wave.  The
 // lanes of a group run steps 1 and 2 for one candidate each -- on the grid path each lane walks cells of its own out of the
@@ -724,7 +834,7 @@ __global__ void __launch_bounds__(64) k_overlap_pass(BodyArrays b, PolytopeTable
     __shared__ OverlapLds<V> s_all[PW];
     const uint32_t group = threadIdx.x / L, lane = threadIdx.x % L;
     const uint32_t q = blockIdx.x * PW + group;
-    if (q >= a.n_queries)
+    if (q >= a.n)
         return;
     OverlapLds<V> &s = s_all[group];
     const double2 *qr = reinterpret_cast<const double2 *>(a.qrec + (size_t)q * kOverlapRecDoubles);
@@ -758,27 +868,15 @@ __global__ void __launch_bounds__(64) k_overlap_pass(BodyArrays b, PolytopeTable
         }
         // steps 1 and 2 of body i (one lane)
         auto admit = [&](uint32_t i, Vec3 &centre, double &radius) -> bool {
-            const double2 *r = reinterpret_cast<const double2 *>(a.rec + (size_t)i * kQueryRecDoubles);
-            const double2 d = r[3], e = r[4], f = r[5];
-            centre = Vec3{d.y, e.x, e.y};
-            radius = f.x;
-            if (!(radius >= 0.0))
-                return false;
-            if ((a.gid ? a.gid[i] : i) == ignore)
-                return false;
-            if (a.masked && ((a.filter ? a.filter[i].x : ~0u) & mask) == 0)
+            if (!admit_record(a, i, ignore, mask, centre, radius))
                 return false;
             const Vec3 between = centre - cq;
             const double reach = rq + radius;
             return dot(between, between) < reach * reach;
         };
-        // step 3 of the bodies the lanes of the group hold in `mine` (kNoBody: none), in lane order
+        // step 3 of the bodies the lanes of the group hold in `mine`
         auto decide = [&](uint32_t mine) {
-            uint64_t todo = group_bits<L>(__ballot(mine != kNoBody));
-            while (todo) {
-                const uint32_t src = (uint32_t)__ffsll((long long)todo) - 1u;
-                todo &= todo - 1;
-                const uint32_t i = (uint32_t)__shfl((int)mine, (int)src, L);
+            for_each_held<L>(mine, [&](uint32_t i) {
                 uint32_t feature = 0;
                 double separation = 0.0;
                 if (overlap_decide<L>(s, t, fq, fq_inv, sq, body_frame(b, i), b.shape_id[i], lane, feature, separation)) {
@@ -791,7 +889,7 @@ __global__ void __launch_bounds__(64) k_overlap_pass(BodyArrays b, PolytopeTable
                     }
                     ++count;
                 }
-            }
+            });
         };
         // the cells of the query on the grid, and whether walking them beats looking at every body
         QueryGrid g{};
@@ -813,61 +911,16 @@ __global__ void __launch_bounds__(64) k_overlap_pass(BodyArrays b, PolytopeTable
                 walk = cells <= (double)g.mask + 1.0; // at most the cells a dense grid can have; beyond that, every body in turn
             }
         }
-        if (walk) {
-            const uint32_t cells = qdim[0] * qdim[1] * qdim[2];
-            uint32_t next = lane, at = 0, end = 0, first = 0;
-            int32_t cell[3] = {0, 0, 0};
-            for (;;) {
-                uint32_t mine = kNoBody;
-                while (mine == kNoBody) {
-                    if (at == end) { // this lane's next cell
-                        if (next >= cells)
-                            break;
-                        const uint32_t zy = next / qdim[0];
-                        cell[0] = qlo[0] + (int32_t)(next - zy * qdim[0]);
-                        cell[1] = qlo[1] + (int32_t)(zy % qdim[1]);
-                        cell[2] = qlo[2] + (int32_t)(zy / qdim[1]);
-                        next += L;
-                        const uint32_t key = query_key(g, cell[0], cell[1], cell[2]);
-                        first = at = a.cell_start[key];
-                        end = a.cell_start[key + 1];
-                        continue;
-                    }
-                    const uint32_t slot = at++, i = a.items[slot];
-                    Vec3 cb;
-                    double rb;
-                    if (!admit(i, cb, rb))
-                        continue;
-                    // A body is listed in up to 8 cells and the query covers a box of them: the pair counts in ONE cell, the
-                    // component-wise maximum of the lower corners of the two cell ranges (k_query_bin's expressions).  A
-                    // hashed key is shared by several cells: the body must really be listed in this one, and once.
-                    const double c[3] = {cb.x, cb.y, cb.z};
-                    bool here = true;
-#pragma unroll
-                    for (int ax = 0; ax < 3; ++ax) {
-                        const int32_t lo = clamp_axis(g, ax, floor((c[ax] - rb - g.pad) / g.edge));
-                        int32_t hi = clamp_axis(g, ax, floor((c[ax] + rb + g.pad) / g.edge));
-                        hi = hi > lo + 1 ? lo + 1 : hi;
-                        here = here && cell[ax] == (lo > qlo[ax] ? lo : qlo[ax]) && cell[ax] <= hi;
-                    }
-                    if (here && !g.dense)
-                        for (uint32_t e = first; e < slot; ++e)
-                            here = here && a.items[e] != i;
-                    if (here)
-                        mine = i;
-                }
-                if (!group_bits<L>(__ballot(mine != kNoBody)))
-                    break; // every lane has run out of cells
-                decide(mine);
-            }
-        } else if (ordered || g.mode != kEmpty) {
+        if (walk)
+            walk_cell_box<L>(g, qlo, qdim, a.cell_start, a.items, lane, admit, [](int, int32_t, int32_t) { return false; }, decide);
+        else if (ordered || g.mode != kEmpty)
+            // (its own loop, like the sweep pass's; see DESIGN, "One walk, measured")
             for (uint32_t i0 = 0; i0 < b.n && count < room; i0 += L) {
                 const uint32_t i = i0 + lane;
                 Vec3 cb;
                 double rb;
                 decide(i < b.n && admit(i, cb, rb) ? i : kNoBody);
             }
-        }
     }
     if (!FILL && lane == 0)
         a.offsets[q] = count;
@@ -1082,17 +1135,9 @@ __device__ __forceinline__ bool sweep_decide(Lds &s, const PolytopeTables &t, co
     return t_hit <= t_hi;
 }
 
-struct SweepArgs {
+struct SweepArgs : PassArgs {
     const xpbd_sweep *sweeps;
-    const double *qrec;         // k_sweep_queries
-    const double *rec;          // k_query_bodies
-    const uint32_t *gid;        // the index a body is known by (null: its slot); XPBD_NO_HIT bodies have radius < 0 in rec
-    const uint2 *filter;        // collision filters (null: every body in group ~0u)
-    const QueryGrid *grid;      // grid path only
-    const uint32_t *cell_start;
-    const uint32_t *items;
     xpbd_sweep_hit *hits;
-    uint32_t n_sweeps, masked, brute;
 };
 
 // The closest body of every sweep: one group of L lanes per sweep, 64 / L sweeps per wave.  The lanes of a group admit one
@@ -1106,7 +1151,7 @@ __global__ void __launch_bounds__(64) k_sweep_pass(BodyArrays b, PolytopeTables 
     __shared__ OverlapLds<V> s_all[PW];
     const uint32_t group = threadIdx.x / L, lane = threadIdx.x % L;
     const uint32_t q = blockIdx.x * PW + group;
-    if (q >= a.n_sweeps)
+    if (q >= a.n)
         return;
     OverlapLds<V> &s = s_all[group];
     const double2 *qr = reinterpret_cast<const double2 *>(a.qrec + (size_t)q * kOverlapRecDoubles);
@@ -1129,25 +1174,12 @@ __global__ void __launch_bounds__(64) k_sweep_pass(BodyArrays b, PolytopeTables 
         }
         // may body i win? (one lane)
         auto admit = [&](uint32_t i, Vec3 &centre, double &radius) -> bool {
-            const double2 *r = reinterpret_cast<const double2 *>(a.rec + (size_t)i * kQueryRecDoubles);
-            const double2 d = r[3], e = r[4], f = r[5];
-            centre = Vec3{d.y, e.x, e.y};
-            radius = f.x;
-            if (!(radius >= 0.0))
-                return false;
-            if ((a.gid ? a.gid[i] : i) == sw.ignore)
-                return false;
-            if (a.masked && ((a.filter ? a.filter[i].x : ~0u) & sw.mask) == 0)
-                return false;
-            return sweep_may_reach(cq, rq, sw.d, best.t < sw.tmax ? best.t : sw.tmax, centre, radius);
+            return admit_record(a, i, sw.ignore, sw.mask, centre, radius) &&
+                   sweep_may_reach(cq, rq, sw.d, best.t < sw.tmax ? best.t : sw.tmax, centre, radius);
         };
-        // the bodies the lanes of the group hold in `mine` (kNoBody: none), in lane order
+        // the bodies the lanes of the group hold in `mine`
         auto decide = [&](uint32_t mine) {
-            uint64_t todo = group_bits<L>(__ballot(mine != kNoBody));
-            while (todo) {
-                const uint32_t src = (uint32_t)__ffsll((long long)todo) - 1u;
-                todo &= todo - 1;
-                const uint32_t i = (uint32_t)__shfl((int)mine, (int)src, L);
+            for_each_held<L>(mine, [&](uint32_t i) {
                 double th = 0.0;
                 uint32_t entering = kNoBody;
                 if (sweep_decide<L>(s, t, sw.f, fq_inv, sw.shape, sw.d, d_q, body_frame(b, i), b.shape_id[i], lane,
@@ -1156,7 +1188,7 @@ __global__ void __launch_bounds__(64) k_sweep_pass(BodyArrays b, PolytopeTables 
                     if (better(th, id, best))
                         best = Best{th, id, entering, i, 0};
                 }
-            }
+            });
         };
         QueryGrid g{};
         if (!a.brute)
@@ -1172,22 +1204,8 @@ __global__ void __launch_bounds__(64) k_sweep_pass(BodyArrays b, PolytopeTables 
             const double o[3] = {cq.x, cq.y, cq.z}, d[3] = {sw.d.x, sw.d.y, sw.d.z};
             // clip the centre line to the grid's box grown by the volume's radius: [t_near, t_far].  Outside it the volume
             // reaches no body's sphere; the cells of the walk may lie outside the grid, the boxes below are clamped to it.
-            const double grow = rq + kSweepMargin * g.edge;
-            double t_near = 0.0, t_far = sw.tmax;
-            bool inside = true;
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                const double lo = (double)g.lo[ax] * g.edge - grow, hi = ((double)g.lo[ax] + (double)g.dims[ax]) * g.edge + grow;
-                if (d[ax] == 0.0) {
-                    inside = inside && o[ax] >= lo && o[ax] <= hi;
-                } else {
-                    const double t1 = (lo - o[ax]) / d[ax], t2 = (hi - o[ax]) / d[ax];
-                    const double tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1;
-                    t_near = tn > t_near ? tn : t_near;
-                    t_far = tf < t_far ? tf : t_far;
-                }
-            }
-            if (inside && t_near <= t_far) {
+            double t_near, t_far;
+            if (clip_to_grid(g, o, d, sw.tmax, rq + kSweepMargin * g.edge, t_near, t_far)) {
                 int32_t cell[3], step[3];
 #pragma unroll
                 for (int ax = 0; ax < 3; ++ax) {
@@ -1205,19 +1223,9 @@ __global__ void __launch_bounds__(64) k_sweep_pass(BodyArrays b, PolytopeTables 
                 for (;;) {
                     if (t_enter > best.t) // strict: a tie later on can still win on the smaller index
                         break;
-                    // when the centre leaves this cell: the nearest face ahead, each face's t from its own coordinate
-                    double t_next = INFINITY;
-                    int axis = -1;
-#pragma unroll
-                    for (int ax = 0; ax < 3; ++ax)
-                        if (step[ax] != 0) {
-                            const double face = (double)(cell[ax] + (step[ax] > 0 ? 1 : 0)) * g.edge;
-                            const double ta = (face - o[ax]) / d[ax];
-                            if (ta < t_next) {
-                                t_next = ta;
-                                axis = ax;
-                            }
-                        }
+                    // when the centre leaves this cell
+                    double t_next;
+                    const int axis = next_face(g, cell, step, o, d, t_next);
                     const double t_leave = t_next < t_far ? t_next : t_far;
                     // the box of cells the sphere covers while its centre runs over [t_enter, t_leave]
                     int32_t qlo[3];
@@ -1230,55 +1238,12 @@ __global__ void __launch_bounds__(64) k_sweep_pass(BodyArrays b, PolytopeTables 
                         const int32_t hi = clamp_axis(g, ax, floor((c_max + rq + g.pad) / g.edge));
                         qdim[ax] = (uint32_t)(hi - qlo[ax]) + 1u;
                     }
-                    const uint32_t cells = qdim[0] * qdim[1] * qdim[2];
-                    uint32_t next = lane, at = 0, end = 0, first = 0;
-                    int32_t cc[3] = {0, 0, 0};
-                    for (;;) {
-                        uint32_t mine = kNoBody;
-                        while (mine == kNoBody) {
-                            if (at == end) { // this lane's next cell
-                                if (next >= cells)
-                                    break;
-                                const uint32_t zy = next / qdim[0];
-                                cc[0] = qlo[0] + (int32_t)(next - zy * qdim[0]);
-                                cc[1] = qlo[1] + (int32_t)(zy % qdim[1]);
-                                cc[2] = qlo[2] + (int32_t)(zy / qdim[1]);
-                                next += L;
-                                const uint32_t key = query_key(g, cc[0], cc[1], cc[2]);
-                                first = at = a.cell_start[key];
-                                end = a.cell_start[key + 1];
-                                continue;
-                            }
-                            const uint32_t slot = at++, i = a.items[slot];
-                            Vec3 cb;
-                            double rb;
-                            if (!admit(i, cb, rb))
-                                continue;
-                            // A body is listed in up to 8 cells: within this box the pair counts in ONE of them, as in the
-                            // overlap pass, and not at all if the previous segment's box held one of its cells -- the boxes
-                            // that meet a body's cells are consecutive segments (the centre moves one way on every axis), so
-                            // it was looked at then, with a t_cap no smaller than now.  A test too many would change nothing.
-                            const double c[3] = {cb.x, cb.y, cb.z};
-                            bool here = true, before = true;
-#pragma unroll
-                            for (int ax = 0; ax < 3; ++ax) {
-                                const int32_t lo = clamp_axis(g, ax, floor((c[ax] - rb - g.pad) / g.edge));
-                                int32_t hi = clamp_axis(g, ax, floor((c[ax] + rb + g.pad) / g.edge));
-                                hi = hi > lo + 1 ? lo + 1 : hi;
-                                here = here && cc[ax] == (lo > qlo[ax] ? lo : qlo[ax]) && cc[ax] <= hi;
-                                before = before && lo <= phi[ax] && hi >= plo[ax];
-                            }
-                            here = here && !before;
-                            if (here && !g.dense)
-                                for (uint32_t e = first; e < slot; ++e)
-                                    here = here && a.items[e] != i;
-                            if (here)
-                                mine = i;
-                        }
-                        if (!group_bits<L>(__ballot(mine != kNoBody)))
-                            break; // every lane has run out of cells
-                        decide(mine);
-                    }
+                    // A body counts in one cell of this box (walk_cell_box), and not at all if the previous stretch's box held
+                    // one of its cells -- the boxes that meet a body's cells are consecutive stretches (the centre moves one
+                    // way on every axis), so it was looked at then, with a t_cap no smaller than now.  A test too many would
+                    // change nothing.
+                    walk_cell_box<L>(g, qlo, qdim, a.cell_start, a.items, lane, admit,
+                                     [&](int ax, int32_t lo, int32_t hi) { return lo <= phi[ax] && hi >= plo[ax]; }, decide);
                     if (axis < 0 || t_next > t_far)
                         break;
 #pragma unroll
@@ -1399,6 +1364,24 @@ hipError_t launch_query_grid(const BodyArrays &b, const QueryScratch &s, hipStre
                        s.items);
     return hipSuccess;
 }
+PassArgs pass_args(const QueryScratch &s, const uint32_t *global_id, const uint2 *filter, uint32_t n, bool masked, bool brute)
+{
+    return PassArgs{s.qrec, s.rec, global_id, filter, static_cast<QueryGrid *>(s.grid), s.cell_start, s.items, n, masked ? 1u : 0u, brute ? 1u : 0u};
+}
+
+// Lanes per query (L) and vertex capacity (V) of the group kernels by the largest shape, as the SAT launchers of the contact
+// pipeline choose theirs: launch(L, V, workgroups) with L and V as std::integral_constant, 64 / L queries per workgroup.
+template <class Launch>
+void with_group_shape(const PolytopeTables &t, uint32_t n_queries, Launch &&launch)
+{
+    using std::integral_constant;
+    if (t.max_verts <= 8 && t.max_faces <= 8)
+        launch(integral_constant<uint32_t, 16>{}, integral_constant<uint32_t, 8>{}, dim3((n_queries + 3) / 4));
+    else if (t.max_verts <= 16)
+        launch(integral_constant<uint32_t, 32>{}, integral_constant<uint32_t, 16>{}, dim3((n_queries + 1) / 2));
+    else
+        launch(integral_constant<uint32_t, 64>{}, integral_constant<uint32_t, XPBD_MAX_SHAPE_VERTS>{}, dim3(n_queries));
+}
 } // namespace
 
 hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const RayFilter &filter, const void *rays_v, uint32_t n_rays,
@@ -1448,17 +1431,12 @@ hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const ui
                        n_queries, t, s.qrec);
     if (!brute && (e = launch_query_grid(b, s, stream)) != hipSuccess) // the grid of a ray cast, by the same passes
         return e;
-    const OverlapArgs a{static_cast<const xpbd_overlap_query *>(queries_v), s.qrec, s.rec, global_id, filter, static_cast<QueryGrid *>(s.grid),
-                        s.cell_start, s.items, offsets, static_cast<xpbd_overlap_hit *>(hits_v), n_queries, cap, masked ? 1u : 0u, brute ? 1u : 0u};
-    // lanes per query and vertex capacity by the largest shape, as the SAT launchers of the contact pipeline choose theirs
+    const OverlapArgs a{pass_args(s, global_id, filter, n_queries, masked, brute), static_cast<const xpbd_overlap_query *>(queries_v), offsets,
+                        static_cast<xpbd_overlap_hit *>(hits_v), cap};
     auto pass = [&](auto fill) {
-        constexpr bool FILL = decltype(fill)::value;
-        if (t.max_verts <= 8 && t.max_faces <= 8)
-            hipLaunchKernelGGL((k_overlap_pass<16, 8, FILL>), dim3((n_queries + 3) / 4), dim3(64), 0, stream, b, t, a);
-        else if (t.max_verts <= 16)
-            hipLaunchKernelGGL((k_overlap_pass<32, 16, FILL>), dim3((n_queries + 1) / 2), dim3(64), 0, stream, b, t, a);
-        else
-            hipLaunchKernelGGL((k_overlap_pass<64, XPBD_MAX_SHAPE_VERTS, FILL>), dim3(n_queries), dim3(64), 0, stream, b, t, a);
+        with_group_shape(t, n_queries, [&](auto l, auto v, dim3 blocks) {
+            hipLaunchKernelGGL((k_overlap_pass<decltype(l)::value, decltype(v)::value, decltype(fill)::value>), blocks, dim3(64), 0, stream, b, t, a);
+        });
     };
     pass(std::false_type{});
     if ((e = launch_exclusive_scan(offsets, n_queries, s.scan_scratch, stream)) != hipSuccess)
@@ -1483,15 +1461,10 @@ hipError_t launch_sweep(const BodyArrays &b, const PolytopeTables &t, const uint
     if (!brute)
         if (hipError_t e = launch_query_grid(b, s, stream)) // the grid of a ray cast, by the same passes
             return e;
-    const SweepArgs a{sweeps, s.qrec, s.rec, global_id, filter, static_cast<QueryGrid *>(s.grid), s.cell_start, s.items,
-                      static_cast<xpbd_sweep_hit *>(hits_v), n_sweeps, masked ? 1u : 0u, brute ? 1u : 0u};
-    // lanes per sweep and vertex capacity by the largest shape, as the overlap pass chooses them
-    if (t.max_verts <= 8 && t.max_faces <= 8)
-        hipLaunchKernelGGL((k_sweep_pass<16, 8>), dim3((n_sweeps + 3) / 4), dim3(64), 0, stream, b, t, a);
-    else if (t.max_verts <= 16)
-        hipLaunchKernelGGL((k_sweep_pass<32, 16>), dim3((n_sweeps + 1) / 2), dim3(64), 0, stream, b, t, a);
-    else
-        hipLaunchKernelGGL((k_sweep_pass<64, XPBD_MAX_SHAPE_VERTS>), dim3(n_sweeps), dim3(64), 0, stream, b, t, a);
+    const SweepArgs a{pass_args(s, global_id, filter, n_sweeps, masked, brute), sweeps, static_cast<xpbd_sweep_hit *>(hits_v)};
+    with_group_shape(t, n_sweeps, [&](auto l, auto v, dim3 blocks) {
+        hipLaunchKernelGGL((k_sweep_pass<decltype(l)::value, decltype(v)::value>), blocks, dim3(64), 0, stream, b, t, a);
+    });
     return hipGetLastError();
 }
 

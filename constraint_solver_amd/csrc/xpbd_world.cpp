@@ -1241,6 +1241,29 @@ int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, u
     return XPBD_OK;
 }
 
+// The filter table a masked query reads (null: unmasked, or no filters set -- every body is then in group ~0u).
+const uint2 *masked_filter(const xpbd_world *w, bool masked) { return masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr; }
+
+// The host variant of a query with one result per record: n records in, enqueue(device records, device results), n results out,
+// and the stream synchronised.
+template <class In, class Out, class Enqueue>
+int query_host(xpbd_world *w, const In *in, uint32_t n, Out *out, Enqueue &&enqueue)
+{
+    if (n == 0)
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    SceneQueryScratch &s = w->query;
+    const size_t in_bytes = (size_t)n * sizeof(In), out_bytes = (size_t)n * sizeof(Out);
+    XPBD_HIP_TRY(s.reserve(QuerySizes{}, in_bytes, out_bytes, 0, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(s.in.ptr, in, in_bytes, hipMemcpyHostToDevice, w->stream));
+    if (int rc = enqueue(s.in.as<In>(), s.out.as<Out>()))
+        return rc;
+    XPBD_HIP_TRY(hipMemcpyAsync(out, s.out.ptr, out_bytes, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    return XPBD_OK;
+}
+
 int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits,
                     const uint32_t *dev_global_id, bool masked, uint32_t mask)
 {
@@ -1253,7 +1276,7 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
     const bool brute = (flags & XPBD_RAYCAST_BRUTE_FORCE) || n_rays <= XPBD_RAYCAST_BRUTE_FORCE_RAYS || w->n == 0;
     const QuerySizes q = query_scratch_bytes(w->n, n_rays, brute);
     XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
-    const RayFilter filter{masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr, mask, masked ? 1u : 0u};
+    const RayFilter filter{masked_filter(w, masked), mask, masked ? 1u : 0u};
     XPBD_HIP_TRY(launch_raycast(w->arrays(), w->tables(), dev_global_id, filter, dev_rays, n_rays, brute, w->query.view(q.table_size), dev_hits,
                                 w->stream));
     return XPBD_OK;
@@ -1262,19 +1285,9 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
 int raycast_host(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits, const uint32_t *dev_global_id,
                  bool masked, uint32_t mask)
 {
-    if (n_rays == 0)
-        return XPBD_OK;
-    if (int rc = bind_device(w))
-        return rc;
-    SceneQueryScratch &s = w->query;
-    const size_t bytes = (size_t)n_rays * sizeof(xpbd_ray);
-    XPBD_HIP_TRY(s.reserve(QuerySizes{}, bytes, bytes, 0, w->stream));
-    XPBD_HIP_TRY(hipMemcpyAsync(s.in.ptr, rays, bytes, hipMemcpyHostToDevice, w->stream));
-    if (int rc = raycast_enqueue(w, s.in.as<xpbd_ray>(), n_rays, flags, s.out.as<xpbd_ray_hit>(), dev_global_id, masked, mask))
-        return rc;
-    XPBD_HIP_TRY(hipMemcpyAsync(hits, s.out.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
-    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    return XPBD_OK;
+    return query_host(w, rays, n_rays, hits, [&](const xpbd_ray *dev_rays, xpbd_ray_hit *dev_hits) {
+        return raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, dev_global_id, masked, mask);
+    });
 }
 
 int check_overlap(const char *who, const QueryTarget &t, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
@@ -1314,8 +1327,8 @@ int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32
     const QuerySizes q = overlap_scratch_bytes(w->n, n_queries, brute);
     XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
     const bool masked = (flags & XPBD_OVERLAP_MASKED) != 0;
-    XPBD_HIP_TRY(launch_overlap(w->arrays(), w->tables(), dev_global_id, masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr, dev_queries,
-                                n_queries, masked, brute, w->query.view(q.table_size), dev_offsets, dev_hits, cap, w->stream));
+    XPBD_HIP_TRY(launch_overlap(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute,
+                                w->query.view(q.table_size), dev_offsets, dev_hits, cap, w->stream));
     return XPBD_OK;
 }
 
@@ -1376,26 +1389,16 @@ int sweep_enqueue(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps
     const QuerySizes q = overlap_scratch_bytes(w->n, n_sweeps, brute); // a sweep's records are an overlap query's
     XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
     const bool masked = (flags & XPBD_SWEEP_MASKED) != 0;
-    XPBD_HIP_TRY(launch_sweep(w->arrays(), w->tables(), dev_global_id, masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr, dev_sweeps,
-                              n_sweeps, masked, brute, w->query.view(q.table_size), dev_hits, w->stream));
+    XPBD_HIP_TRY(launch_sweep(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_sweeps, n_sweeps, masked, brute,
+                              w->query.view(q.table_size), dev_hits, w->stream));
     return XPBD_OK;
 }
 
 int sweep_host(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits, const uint32_t *dev_global_id)
 {
-    if (n_sweeps == 0)
-        return XPBD_OK;
-    if (int rc = bind_device(w))
-        return rc;
-    SceneQueryScratch &s = w->query;
-    const size_t in_bytes = (size_t)n_sweeps * sizeof(xpbd_sweep), out_bytes = (size_t)n_sweeps * sizeof(xpbd_sweep_hit);
-    XPBD_HIP_TRY(s.reserve(QuerySizes{}, in_bytes, out_bytes, 0, w->stream));
-    XPBD_HIP_TRY(hipMemcpyAsync(s.in.ptr, sweeps, in_bytes, hipMemcpyHostToDevice, w->stream));
-    if (int rc = sweep_enqueue(w, s.in.as<xpbd_sweep>(), n_sweeps, flags, s.out.as<xpbd_sweep_hit>(), dev_global_id))
-        return rc;
-    XPBD_HIP_TRY(hipMemcpyAsync(hits, s.out.ptr, out_bytes, hipMemcpyDeviceToHost, w->stream));
-    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    return XPBD_OK;
+    return query_host(w, sweeps, n_sweeps, hits, [&](const xpbd_sweep *dev_sweeps, xpbd_sweep_hit *dev_hits) {
+        return sweep_enqueue(w, dev_sweeps, n_sweeps, flags, dev_hits, dev_global_id);
+    });
 }
 
 } // namespace xpbd

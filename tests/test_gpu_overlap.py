@@ -200,6 +200,103 @@ def test_a_sparse_hashed_world():
     assert np.mean(counts[:384] > 0) > 0.2 and counts[384] > 50 and counts[385] > 50
 
 
+def unit(v):
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def centred_queries(rng, polys, at, shape):
+    """Queries of random rotation whose bounding-sphere centres (the shapes' centroids) lie at the points `at`."""
+    import raycast_model as rm
+    rot = unit_quaternions(rng, len(at))
+    shape = np.broadcast_to(shape, len(at))
+    off = np.array([rm.rotate(tuple(r), tuple(float(x) for x in polys[int(s)]["centroid"])) for r, s in zip(rot, shape)])
+    return capi.overlap_queries(at - off, rot, shape)
+
+
+def put_centres(bodies, sid, polys, rows, at):
+    """Move the bodies `rows` so that the centres of their bounding spheres lie at the points `at`."""
+    import raycast_model as rm
+    bodies[rows, 31:34] = at
+    bodies[rows, 31:34] -= np.array([capi.rigid_frame(row)[:3] - row[31:34] for row in bodies[rows]])   # (the frame's origin, not `position`)
+    bodies[rows, 31:34] -= np.array([rm.rotate(tuple(bodies[i, 34:38]), tuple(float(x) for x in polys[int(sid[i])]["centroid"])) for i in rows])
+
+
+def test_a_one_body_world_and_a_world_inside_one_cell():
+    polys = [capi.polytope(capi.SHAPE_CUBE)]                        # cubes only: the 16-lane groups
+    rng = np.random.default_rng(271)
+    one, sid1 = capi.scene_generate(capi.SCENE_BOXES, 2, 1)
+    one[0, 31:34] = [0.3, -0.2, 1.0]
+    edge = cell_edge(polys, sid1)
+    few, sid6 = capi.scene_generate(capi.SCENE_BOXES, 3, 6)
+    few[:, 34:38] = unit_quaternions(rng, 6)
+    # a sphere is narrower than a cell by 1e-6 of an edge: centres within 2e-7 of the middle of the cell (10, 10, 10) keep every
+    # sphere inside it, the pad of 1e-7 radii included -- a grid of one cell
+    put_centres(few, sid6, polys, range(6), 10.5 * edge + rng.uniform(-2e-7, 2e-7, (6, 3)) * edge)
+    for bodies, sid in ((one, sid1), (few, sid6)):
+        scene = om.Scene(bodies, sid, polys)
+        if len(bodies) > 1:
+            reach = scene.body_radius[:, None] * (1.0 + 1e-7)
+            assert (np.floor((scene.centres - reach) / edge) == 10).all() and (np.floor((scene.centres + reach) / edge) == 10).all()
+        # on the bodies and up to two cells away from them: the centres of a hit lie within 2 * radius, just over one edge
+        at = scene.centres[rng.integers(0, len(bodies), 40)] + unit(rng.normal(size=(40, 3))) * rng.uniform(0.0, 2.0, (40, 1)) * edge
+        q = centred_queries(rng, polys, at, 0)
+        with capi.World(mode=capi.MODE_CONTACTS) as w:
+            w.set_polytopes(polys)
+            w.upload(bodies, sid)
+            offsets, hits = check_three_ways(w, scene, q)
+        counts = np.diff(offsets.astype(np.int64))
+        assert np.sum(counts > 0) > 8 and np.sum(counts == 0) > 8
+        assert set(counts) <= set(range(len(bodies) + 1)) and counts.max() == len(bodies)
+
+
+def test_bodies_around_the_origin_and_in_the_negative_octant():
+    """Cell coordinates of either sign: bodies whose spheres contain the origin are binned in the cells -1 .. 0 on all three axes,
+    others lie wholly at negative coordinates.  Volumes of body size and volumes several cells wide, whose boxes of cells span
+    the change of sign, unmasked and masked."""
+    kinds = capi.scene_polytopes(KIND)
+    polys = kinds + [capi.polytope(capi.SHAPE_CUBE, 2.5)]           # the last: larger than a cell, no body uses it
+    big = len(kinds)
+    rng = np.random.default_rng(311)
+    n = 96
+    bodies, sid = capi.scene_generate(KIND, 4, n)
+    bodies[:, 34:38] = unit_quaternions(rng, n)
+    bodies[:, 31:34] = rng.uniform(-6.0, 2.0, (n, 3))
+    put_centres(bodies, sid, polys, range(8), rng.uniform(-0.2, 0.2, (8, 3)))   # around the origin
+    groups = np.where(np.arange(n) < 8, 1, 2).astype(np.uint32)
+    scene = om.Scene(bodies, sid, polys, groups)
+    edge = cell_edge(polys, sid)
+    cells_lo = np.floor((scene.centres - scene.body_radius[:, None]) / edge)
+    cells_hi = np.floor((scene.centres + scene.body_radius[:, None]) / edge)
+    straddle = ((cells_lo == -1) & (cells_hi == 0)).all(axis=1)
+    negative = (cells_hi < 0).all(axis=1)
+    assert straddle[:8].all() and negative.sum() > 10
+    assert 2.0 * om.shape_radius(polys[big]) > 2.0 * edge            # its sphere's box of cells is 3 to 4 cells wide
+    # body-sized volumes at the bodies around the origin; large ones whose boxes hold the origin's cells; the families over the
+    # whole cloud, with volumes of every shape
+    q = np.concatenate([centred_queries(rng, polys, scene.centres[rng.integers(0, 8, 48)] + rng.normal(size=(48, 3)) * 0.4, rng.integers(0, big, 48)),
+                        centred_queries(rng, polys, rng.uniform(-0.5, 0.5, (32, 3)), big),
+                        centred_queries(rng, polys, rng.uniform(-6.0, -1.0, (24, 3)), big),
+                        query_families(rng, bodies, sid, polys, 96)])
+    assert len(q) == 200
+    q["ignore_body"][1:48:3] = rng.integers(0, 8, 16)
+    q["mask"] = rng.integers(0, 4, len(q))
+    filters = np.zeros(n, dtype=capi.COLLISION_FILTER_DTYPE)
+    filters["group"], filters["mask"] = groups, 0xFFFFFFFF
+    with capi.World(mode=capi.MODE_CONTACTS) as w:
+        w.set_polytopes(polys)
+        w.upload(bodies, sid)
+        w.set_collision_filters(filters)
+        offsets, hits = check_three_ways(w, scene, q)
+        counts = np.diff(offsets.astype(np.int64))
+        assert np.sum(hits["body"] < 8) > 100 and np.sum(negative[hits["body"]]) > 100
+        # (the eight centres lie within 0.35 of the origin and a large volume's within 0.87, less than the 1.25 from its centre to a face)
+        assert (counts[48:80] >= 8).all()                            # around the origin a large volume holds all eight
+        assert np.sum(counts > 0) > 100 and np.sum(counts == 0) > 20
+        m_offsets, m_hits = check_three_ways(w, scene, q, MASKED)
+        assert 50 < len(m_hits) < len(hits) and np.all(groups[m_hits["body"]] & np.repeat(q["mask"], np.diff(m_offsets.astype(np.int64))))
+        assert np.sum(m_hits["body"] < 8) > 30 and np.sum(negative[m_hits["body"]]) > 30
+
+
 def test_masks():
     bodies, sid = pile(1024)
     polys = capi.scene_polytopes(KIND)
