@@ -1,5 +1,6 @@
-// xpbd_merge.hpp -- how the multi-GPU world (xpbd_multi.cpp) merges the scene queries' answers of its ranks.  Host-only: pure
-// functions of the gathered bytes, no device and no collective (tests/merge_standalone_main.cpp runs them on their own).
+// xpbd_merge.hpp -- how the multi-GPU world (xpbd_multi.cpp) merges what its ranks answer: the hits of the scene queries (ray
+// casts, sweeps, overlaps) and the contact report of a frame with its begin / end events.  Host-only: pure functions of the
+// gathered bytes, no device and no collective (tests/merge_standalone_main.cpp runs them on their own).
 #pragma once
 
 #include <algorithm>
@@ -84,6 +85,70 @@ inline uint32_t merge_overlap_lists(const void *offset_rows, const void *hit_row
     }
     offsets[n_queries] = at;
     return at;
+}
+
+// ---- contact reports ---------------------------------------------------------------------------------------------------------
+// pair_rows: n_ranks rows of `pair_width` xpbd_pair_contact, of which rank r filled pair_counts[r]; first_point indexes the
+// rank's row of point_rows (n_ranks rows of `point_width` xpbd_contact_point).  The ranks' lists are disjoint (a pair belongs
+// to the owner of its lower body).  pairs = all of them in key order (body_a << 32 | body_b) with first_point re-based into
+// `points`, the pairs' points in that order; keys = the keys, ascending.
+inline void merge_contact_reports(const void *pair_rows, uint32_t pair_width, const uint32_t *pair_counts, const void *point_rows, uint32_t point_width,
+                                  uint32_t n_ranks, std::vector<xpbd_pair_contact> &pairs, std::vector<xpbd_contact_point> &points,
+                                  std::vector<uint64_t> &keys)
+{
+    const uint8_t *pair_bytes = static_cast<const uint8_t *>(pair_rows), *point_bytes = static_cast<const uint8_t *>(point_rows);
+    auto pair_at = [&](uint32_t r, uint32_t i) {
+        xpbd_pair_contact c;
+        std::memcpy(&c, pair_bytes + ((size_t)r * pair_width + i) * sizeof c, sizeof c);
+        return c;
+    };
+    struct Item {
+        uint64_t key;
+        uint32_t rank, row;
+    };
+    std::vector<Item> items;
+    for (uint32_t r = 0; r < n_ranks; ++r)
+        for (uint32_t i = 0; i < pair_counts[r]; ++i) {
+            const xpbd_pair_contact c = pair_at(r, i);
+            items.push_back(Item{(uint64_t)c.body_a << 32 | c.body_b, r, i});
+        }
+    std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.key < b.key; });
+    pairs.resize(items.size());
+    keys.resize(items.size());
+    points.clear();
+    for (size_t i = 0; i < items.size(); ++i) {
+        xpbd_pair_contact c = pair_at(items[i].rank, items[i].row);
+        const size_t from = (size_t)items[i].rank * point_width + c.first_point, old = points.size();
+        c.first_point = (uint32_t)old;
+        points.resize(old + c.n_points);
+        if (c.n_points)
+            std::memcpy(points.data() + old, point_bytes + from * sizeof(xpbd_contact_point), (size_t)c.n_points * sizeof(xpbd_contact_point));
+        pairs[i] = c;
+        keys[i] = items[i].key;
+    }
+}
+
+// The events of a frame from the keys of its touching pairs and of the previous frame's (both ascending): the BEGINs (keys -
+// prev) in key order, then the ENDs (prev - keys) in key order.  Returns the number of BEGINs.
+inline uint32_t contact_events(const std::vector<uint64_t> &keys, const std::vector<uint64_t> &prev, std::vector<xpbd_contact_event> &events)
+{
+    std::vector<xpbd_contact_event> ends;
+    events.clear();
+    size_t a = 0, b = 0;
+    while (a < keys.size() || b < prev.size()) {
+        if (b == prev.size() || (a < keys.size() && keys[a] < prev[b])) {
+            events.push_back(xpbd_contact_event{(uint32_t)(keys[a] >> 32), (uint32_t)keys[a], XPBD_CONTACT_BEGIN});
+            ++a;
+        } else if (a == keys.size() || prev[b] < keys[a]) {
+            ends.push_back(xpbd_contact_event{(uint32_t)(prev[b] >> 32), (uint32_t)prev[b], XPBD_CONTACT_END});
+            ++b;
+        } else {
+            ++a, ++b;
+        }
+    }
+    const uint32_t begins = (uint32_t)events.size();
+    events.insert(events.end(), ends.begin(), ends.end());
+    return begins;
 }
 
 } // namespace xpbd

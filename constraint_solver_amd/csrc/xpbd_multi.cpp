@@ -20,7 +20,10 @@
 // One function enqueues a shard's frame (shard_frame), from one host thread per local shard.
 // This file holds what needs a device or a communicator: the shards, the transport, the plan-time collectives around the
 // planner (a handful of small all-gathers: cell keys or rims, boundary lists, the records of migrating and boundary bodies;
-// no rank holds the global scene), settings, edits, the frame, reports and the xpbd_multi_world_* ABI.
+// no rank holds the global scene), the device half of a plan (re-pack, uploads), settings, edits, the frame, the gathers of
+// reports and scene queries and the xpbd_multi_world_* ABI.  The index arithmetic lives in the host-only units: every rank's
+// plan, the layout of a shard (local slots, source map, ghost rows, its joints: layout_shard) and the re-indexing of joint
+// records in xpbd_plan.hpp; the merges of query hits and of the contact report with its events in xpbd_merge.hpp.
 // Every plan-time all-gather carries a status word per rank and so does the frame's last one, so a rank that fails locally
 // (out of memory, say) still takes part in the collectives and EVERY rank returns an error instead of the others hanging.
 //
@@ -64,6 +67,9 @@ using namespace xpbd::plan;
 constexpr uint32_t kDyn = 13;    // dynamic doubles per body: position, rotation, velocity, angular velocity
 constexpr uint32_t kRigid = 38;  // sizeof(xpbd_rigid) / 8
 constexpr uint32_t kRecord = 39; // a body's plan-time record: its xpbd_rigid + the shape id
+struct BodyRecord {
+    double v[kRecord];
+};
 struct Shard {
     int device = 0;
     uint32_t rank = 0;
@@ -83,8 +89,9 @@ struct Shard {
     std::vector<uint8_t> far; // per owned body: more than two cells away from every foreign body (larger travel allowance)
     std::vector<uint32_t> joint_ids; // global ids (ascending) of the joints the shard's world has: local joint q = joint_ids[q]
     DeviceBuffer boundary_slots, ghost_slots, ghost_rows, owned_slots, skip_flags, disp_scale, send, recv, snapshot, disp, disp_all, stage_send, stage_recv;
-    DeviceBuffer query_ids; // xpbd_multi_world_raycast: global id of every local slot, XPBD_NO_HIT for the ghosts
-    DeviceBuffer report_ids, report_owned; // contact reports: global id of every local slot; 1 for the owned slots, 0 for the ghosts
+    // per local slot, uploaded with the plan: the global id with XPBD_NO_HIT for the ghosts (scene queries: the OWNED bodies
+    // answer, under their global ids); the global id, and 1 for the owned slots, 0 for the ghosts (contact reports)
+    DeviceBuffer query_ids, report_ids, report_owned;
     double *disp_host = nullptr;   // pinned, n_ranks x {largest squared fraction of an allowance used, status}
     double *status_host = nullptr; // pinned, this process's status of the frame
     const xpbd::RcclApi *rccl = nullptr; // destroys `comm`
@@ -412,7 +419,8 @@ int all_gather_host(xpbd_multi_world *mw, const std::vector<const void *> &send,
 
 // Variable-length lists of T from every rank: `local` holds every local shard's list; gather_counts (one collective for the
 // lengths of all the lists it is given) yields `counts` and `widest`, gather_rows (one collective) pads every local list to
-// `widest` and yields `rows`.  Both carry `st` as all_gather_host does: a failed shard takes part with whatever it holds.
+// `widest` (value-initialised entries: no reader looks past counts[r]) and yields `rows`.  Both carry `st` as all_gather_host
+// does: a failed shard takes part with whatever it holds.
 template <class T> struct RankLists {
     std::vector<std::vector<T>> local;
     std::vector<uint32_t> counts; // per rank
@@ -563,18 +571,11 @@ template <class T> std::vector<T> local_rows(const std::vector<T> &global, const
     return local;
 }
 
-// The records (limits or drives: both name a joint in .joint) on the joints of shard s, re-indexed to the shard's joint numbering
-// (the caller's order kept), handed to the shard's setter.
+// The records (limits or drives) on the joints of shard s, in the shard's joint numbering (local_joint_records), handed to the
+// shard's setter.
 template <class Record> int push_joint_records(const std::vector<Record> &global, const Shard &s, int (*set)(xpbd_world *, const Record *, uint32_t))
 {
-    std::vector<Record> local;
-    for (const Record &r : global) {
-        const auto at = std::lower_bound(s.joint_ids.begin(), s.joint_ids.end(), r.joint);
-        if (at != s.joint_ids.end() && *at == r.joint) {
-            local.push_back(r);
-            local.back().joint = (uint32_t)(at - s.joint_ids.begin());
-        }
-    }
+    const std::vector<Record> local = local_joint_records(global, s.joint_ids);
     return set(s.world, local.data(), (uint32_t)local.size());
 }
 
@@ -620,14 +621,8 @@ int push_to_shards(xpbd_multi_world *mw, PushSetting push, const char *what)
     return XPBD_OK;
 }
 
-// Body edits (include/xpbd.h, "Body EDITS") reach every local shard that HOLDS the body, as owner or as ghost: the slot of
-// global body g in shard s (local_ids is ascending), or -1.
-int32_t slot_in_shard(const Shard &s, uint32_t g)
-{
-    const auto at = std::lower_bound(s.local_ids.begin(), s.local_ids.end(), g);
-    return at != s.local_ids.end() && *at == g ? (int32_t)(at - s.local_ids.begin()) : -1;
-}
-
+// Body edits (include/xpbd.h, "Body EDITS") reach every local shard that HOLDS the body, as owner or as ghost (slot_in_shard
+// over the shard's local_ids).
 // The tail of an edit: a shard that fails here has not done what the others did.
 int edit_failed(xpbd_multi_world *mw, int rc, const char *what)
 {
@@ -641,183 +636,70 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
 {
     const uint32_t n = mw->n_global, w = mw->n_ranks;
     const size_t n_local = mw->shards.size();
-    std::vector<uint8_t> gathered;
-    std::vector<const void *> send(n_local);
     // 4. the boundary lists of all ranks (ascending global ids) fix the rows of the per-substep all-gather; the export lists
     //    those of the plan-time record exchange
-    struct Counts {
-        uint32_t boundary, exports;
-    };
-    std::vector<Counts> mine(n_local), counts(w);
-    for (size_t k = 0; k < n_local; ++k) {
-        mine[k] = Counts{(uint32_t)plans[k].boundary.size(), (uint32_t)plans[k].exports.size()};
-        send[k] = &mine[k];
-    }
-    XPBD_TRY(all_gather_host(mw, send, sizeof(Counts), gathered, st));
-    std::memcpy(counts.data(), gathered.data(), (size_t)w * sizeof(Counts));
-    uint32_t cap = 1, cap_exp = 0;
-    for (uint32_t r = 0; r < w; ++r) {
-        cap = std::max(cap, counts[r].boundary);
-        cap_exp = std::max(cap_exp, counts[r].exports);
-    }
-    std::vector<uint32_t> lists((size_t)w * cap);
-    {
-        std::vector<std::vector<uint32_t>> pad_list(n_local);
-        for (size_t k = 0; k < n_local; ++k) {
-            pad_list[k].assign(cap, 0xFFFFFFFFu);
-            if (st.ok())
-                std::copy(plans[k].boundary.begin(), plans[k].boundary.end(), pad_list[k].begin());
-            send[k] = pad_list[k].data();
-        }
-        XPBD_TRY(all_gather_host(mw, send, (size_t)cap * 4, gathered, st));
-        std::memcpy(lists.data(), gathered.data(), lists.size() * 4);
-    }
-    // the records of the exported bodies: gathered on the device that holds them, 39 doubles each
-    std::vector<uint32_t> exp_lists;
-    std::vector<double> exp_records;
-    if (cap_exp > 0) {
-        std::vector<std::vector<uint32_t>> pad_list(n_local);
-        std::vector<std::vector<double>> pad_rec(n_local);
-        for (size_t k = 0; k < n_local; ++k) {
-            pad_list[k].assign(cap_exp, 0xFFFFFFFFu);
-            if (st.ok())
-                std::copy(plans[k].exports.begin(), plans[k].exports.end(), pad_list[k].begin());
-            send[k] = pad_list[k].data();
-        }
-        XPBD_TRY(all_gather_host(mw, send, (size_t)cap_exp * 4, gathered, st));
-        exp_lists.resize((size_t)w * cap_exp);
-        std::memcpy(exp_lists.data(), gathered.data(), exp_lists.size() * 4);
+    RankLists<uint32_t> boundary(n_local), exports(n_local);
+    RankLists<BodyRecord> records(n_local);
+    for (size_t k = 0; k < n_local && st.ok(); ++k)
+        boundary.local[k] = plans[k].boundary, exports.local[k] = plans[k].exports;
+    XPBD_TRY(gather_counts(mw, st, boundary, exports));
+    XPBD_TRY(gather_rows(mw, st, boundary));
+    // the records of the exported bodies: gathered on the device that holds them, 39 doubles each (nothing to exchange if
+    // nobody exports anything: every rank sees that in the gathered counts)
+    if (std::any_of(exports.counts.begin(), exports.counts.end(), [](uint32_t c) { return c > 0; })) {
+        XPBD_TRY(gather_rows(mw, st, exports));
+        records.counts = exports.counts, records.widest = exports.widest;
         std::vector<uint32_t> slots;
         for (size_t k = 0; k < n_local; ++k) {
             Shard &s = mw->shards[k];
-            pad_rec[k].assign((size_t)cap_exp * kRecord, 0.0);
+            records.local[k].resize(records.widest);
             slots.clear();
             if (st.ok())
                 for (uint32_t g : plans[k].exports)
                     slots.push_back(s.owned_slots_h[std::lower_bound(s.held_ids.begin(), s.held_ids.end(), g) - s.held_ids.begin()]);
             if (st.ok())
-                st.keep(xpbd::download_records(s.world, slots.data(), (uint32_t)slots.size(), pad_rec[k].data()));
-            send[k] = pad_rec[k].data();
+                st.keep(xpbd::download_records(s.world, slots.data(), (uint32_t)slots.size(), records.local[k][0].v));
         }
-        XPBD_TRY(all_gather_host(mw, send, (size_t)cap_exp * kRecord * 8, gathered, st));
-        exp_records.resize((size_t)w * cap_exp * kRecord);
-        std::memcpy(exp_records.data(), gathered.data(), exp_records.size() * 8);
+        XPBD_TRY(gather_rows(mw, st, records));
     }
     trace.lap("lists, exported records");
 
-    // 5. every shard's local world: owned + ghost bodies in ascending global id.  A body the shard owned before and still
-    //    owns moves on the device; a body that arrives (a new owner, a ghost) comes from its holder's exported record.
-    const uint32_t rows = cap; // (rows per rank of the per-substep all-gather from now on: mw->capacity, set when the plan has succeeded)
-    auto exported = [&](const Shard &me, uint32_t g, uint32_t h) -> const double * {
-        const uint32_t *lo = exp_lists.data() + (size_t)h * cap_exp, *hi = h < w ? lo + counts[h].exports : lo;
-        const uint32_t *at = h < w ? std::lower_bound(lo, hi, g) : hi;
-        if (at == hi || *at != g) {
-            (void)set_error(XPBD_E_HIP, "xpbd_multi_world: body %u is needed by rank %u but not exported by its holder %u (inconsistent plans)", g, me.rank, h);
-            return nullptr;
-        }
-        return &exp_records[((size_t)h * cap_exp + (size_t)(at - lo)) * kRecord];
-    };
+    // 5. every shard's local world: owned + ghost bodies in ascending global id (layout_shard), re-packed on its device
+    const uint32_t rows = boundary.widest; // (rows per rank of the per-substep all-gather from now on: mw->capacity, set when the plan has succeeded)
+    const RankIds boundary_ids{reinterpret_cast<const uint32_t *>(boundary.rows.data()), boundary.counts.data(), boundary.widest, w};
+    const RankIds export_ids{reinterpret_cast<const uint32_t *>(exports.rows.data()), exports.counts.data(), exports.widest, w};
+    const JointIndex ji = mw->joint_lists.view(mw->joints.data());
     if (mw->slot_of.size() != n)
         mw->slot_of.assign(n, -1);
     auto build_shard = [&](size_t k) -> int {
         Shard &s = mw->shards[k];
         ShardPlan &pl = plans[k];
         XPBD_TRY(bind(s));
-        const uint32_t n_own = (uint32_t)pl.own.size(), n_ghost = (uint32_t)pl.ghosts.size(), n_loc = n_own + n_ghost;
-        std::vector<int32_t> src(n_loc);
-        std::vector<double> incoming;
-        std::vector<uint32_t> ghost_slots(n_ghost), ghost_rows(n_ghost), boundary_slots(pl.boundary.size()), owned_slots(n_own);
-        std::vector<uint32_t> local_ids(n_loc);
-        uint32_t slot = 0, oi = 0, gi = 0, n_in = 0;
-        size_t old = 0; // walks the bodies owned so far (ascending, like pl.own)
-        while (oi < n_own || gi < n_ghost) {
-            const bool take_own = gi >= n_ghost || (oi < n_own && pl.own[oi] < pl.ghosts[gi]);
-            const uint32_t g = take_own ? pl.own[oi] : pl.ghosts[gi];
-            local_ids[slot] = g;
-            bool here = false;
-            if (take_own && pl.own_holder[oi] == s.rank) {
-                while (old < s.held_ids.size() && s.held_ids[old] < g)
-                    ++old;
-                if (old == s.held_ids.size() || s.held_ids[old] != g)
-                    return set_error(XPBD_E_HIP, "xpbd_multi_world: body %u is not among the bodies rank %u holds (inconsistent plans)", g, s.rank);
-                src[slot] = (int32_t)s.owned_slots_h[old];
-                here = true;
-            }
-            if (!here) {
-                const double *rec = exported(s, g, take_own ? pl.own_holder[oi] : pl.ghost_holder[gi]);
-                if (!rec)
-                    return XPBD_E_HIP;
-                incoming.insert(incoming.end(), rec, rec + kRecord);
-                src[slot] = -(int32_t)(++n_in);
-            }
-            if (take_own) {
-                owned_slots[oi++] = slot;
-            } else {
-                const uint32_t o = pl.ghost_owner[gi];
-                const uint32_t *lo = &lists[(size_t)(o < w ? o : 0) * cap], *hi = o < w ? lo + counts[o].boundary : lo;
-                const uint32_t *at = std::lower_bound(lo, hi, g);
-                if (at == hi || *at != g)
-                    return set_error(XPBD_E_HIP, "xpbd_multi_world: body %u is mirrored by rank %u but not exported by its owner %u (inconsistent plans)", g, s.rank, o);
-                ghost_slots[gi] = slot;
-                ghost_rows[gi] = o * rows + (uint32_t)(at - lo);
-                ++gi;
-            }
-            ++slot;
-        }
-        for (size_t q = 0; q < pl.boundary.size(); ++q)
-            boundary_slots[q] = owned_slots[std::lower_bound(pl.own.begin(), pl.own.end(), pl.boundary[q]) - pl.own.begin()];
+        ShardLayout lay;
+        XPBD_TRY(layout_shard(s.rank, pl, s.held_ids, s.owned_slots_h, boundary_ids, export_ids, rows, ji, mw->slot_of, mw->margin, edge, lay));
+        std::vector<BodyRecord> incoming(lay.incoming.size());
+        for (size_t i = 0; i < incoming.size(); ++i)
+            incoming[i] = records.at(lay.incoming[i].holder, lay.incoming[i].row);
+        const uint32_t n_own = (uint32_t)pl.own.size(), n_loc = (uint32_t)lay.local_ids.size();
         trace.lap("  source map of a shard");
-        if (int rc = xpbd::repack_bodies(s.world, src.data(), n_loc, incoming.data(), n_in))
+        if (int rc = xpbd::repack_bodies(s.world, lay.src.data(), n_loc, incoming.empty() ? nullptr : incoming[0].v, (uint32_t)incoming.size()))
             return rc;
         trace.lap("  re-pack on the device");
-        // joints whose two bodies are both present here, in global joint order, re-indexed to local slots: the joints of the
-        // local bodies through the per-body joint lists (a joint is taken at its lower-numbered end)
-        for (uint32_t q = 0; q < n_loc; ++q)
-            mw->slot_of[local_ids[q]] = (int32_t)q;
-        std::vector<uint32_t> joint_ids;
-        for (uint32_t q = 0; q < n_loc; ++q) {
-            const uint32_t g = local_ids[q];
-            for (uint32_t e = mw->joint_lists.off[g]; e < mw->joint_lists.off[g + 1]; ++e) {
-                const xpbd_joint &j = mw->joints[mw->joint_lists.adj[e]];
-                const uint32_t other = j.body_a == g ? j.body_b : j.body_a;
-                if (mw->slot_of[other] >= 0 && (g < other || (g == other && j.body_a == g)))
-                    joint_ids.push_back(mw->joint_lists.adj[e]);
-            }
-        }
-        std::sort(joint_ids.begin(), joint_ids.end());
-        joint_ids.erase(std::unique(joint_ids.begin(), joint_ids.end()), joint_ids.end());
-        std::vector<xpbd_joint> local_joints(joint_ids.size());
-        for (size_t q = 0; q < joint_ids.size(); ++q) {
-            xpbd_joint l = mw->joints[joint_ids[q]];
-            l.body_a = (uint32_t)mw->slot_of[l.body_a];
-            l.body_b = (uint32_t)mw->slot_of[l.body_b];
-            local_joints[q] = l;
-        }
-        for (uint32_t q = 0; q < n_loc; ++q)
-            mw->slot_of[local_ids[q]] = -1;
-        if (int rc = xpbd_world_set_joints(s.world, local_joints.data(), (uint32_t)local_joints.size()))
+        if (int rc = xpbd_world_set_joints(s.world, lay.joints.data(), (uint32_t)lay.joints.size()))
             return rc;
-        s.joint_ids = std::move(joint_ids);
-        XPBD_TRY(push_body_settings(mw, s, local_ids));
+        s.joint_ids.swap(lay.joint_ids);
+        XPBD_TRY(push_body_settings(mw, s, lay.local_ids));
         XPBD_HIP_TRY(hipStreamSynchronize(s.stream));
         trace.lap("  joints");
-        XPBD_TRY(upload_vector(s.boundary_slots, boundary_slots, s.stream));
-        XPBD_TRY(upload_vector(s.ghost_slots, ghost_slots, s.stream));
-        XPBD_TRY(upload_vector(s.ghost_rows, ghost_rows, s.stream));
-        XPBD_TRY(upload_vector(s.owned_slots, owned_slots, s.stream));
-        std::vector<uint8_t> skip(n_loc, 0); // what the interior launch leaves out: boundary bodies (done first) and ghosts (done last)
-        for (uint32_t q : boundary_slots)
-            skip[q] = 1;
-        for (uint32_t q : ghost_slots)
-            skip[q] = 1;
-        XPBD_TRY(upload_vector(s.skip_flags, skip, s.stream));
-        // 1 / allowance^2 per owned body: the displacement check then yields the largest FRACTION of its allowance any body has used
-        std::vector<double> scale(n_own);
-        const double near_allow = mw->margin, far_allow = mw->margin + 0.5 * edge;
-        const double near_scale = 1.0 / (near_allow * near_allow), far_scale = 1.0 / (far_allow * far_allow);
-        for (uint32_t i = 0; i < n_own; ++i)
-            scale[i] = pl.far[i] ? far_scale : near_scale;
-        XPBD_TRY(upload_vector(s.disp_scale, scale, s.stream));
+        XPBD_TRY(upload_vector(s.boundary_slots, lay.boundary_slots, s.stream));
+        XPBD_TRY(upload_vector(s.ghost_slots, lay.ghost_slots, s.stream));
+        XPBD_TRY(upload_vector(s.ghost_rows, lay.ghost_rows, s.stream));
+        XPBD_TRY(upload_vector(s.owned_slots, lay.owned_slots, s.stream));
+        XPBD_TRY(upload_vector(s.skip_flags, lay.skip, s.stream));
+        XPBD_TRY(upload_vector(s.disp_scale, lay.disp_scale, s.stream));
+        XPBD_TRY(upload_vector(s.query_ids, lay.query_ids, s.stream));
+        XPBD_TRY(upload_vector(s.report_ids, lay.local_ids, s.stream));
+        XPBD_TRY(upload_vector(s.report_owned, lay.owned, s.stream));
         XPBD_HIP_TRY(s.send.reserve((size_t)rows * kDyn * 8));
         XPBD_HIP_TRY(s.recv.reserve((size_t)w * rows * kDyn * 8));
         XPBD_HIP_TRY(hipMemsetAsync(s.send.ptr, 0, (size_t)rows * kDyn * 8, s.stream));
@@ -826,9 +708,9 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
         XPBD_HIP_TRY(s.disp_all.reserve((size_t)w * 16));
         if (int rc = xpbd_world_snapshot_positions(s.world, s.owned_slots.as<uint32_t>(), n_own, s.snapshot.as<double>()))
             return rc;
-        XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // the host vectors above go out of scope
-        s.owned_slots_h.swap(owned_slots);
-        s.local_ids.swap(local_ids);
+        XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // the layout's host vectors go out of scope
+        s.owned_slots_h.swap(lay.owned_slots);
+        s.local_ids.swap(lay.local_ids);
         s.held_ids.swap(pl.own); // from now on the shard holds what it owns
         s.ghosts.swap(pl.ghosts);
         s.boundary.swap(pl.boundary);
@@ -842,13 +724,12 @@ int finish_plan(xpbd_multi_world *mw, LocalStatus &st, std::vector<ShardPlan> &p
             mw->plan_torn = true; // some shards re-packed, this one half-way: there is no plan to go back to (see make_plan)
     }
     // all ranks leave the plan together: a last status-only exchange (a failed re-pack on one rank fails the plan everywhere)
-    for (size_t k = 0; k < n_local; ++k)
-        send[k] = nullptr;
-    if (int rc = all_gather_host(mw, send, 0, gathered, st)) {
+    std::vector<uint8_t> gathered;
+    if (int rc = all_gather_host(mw, std::vector<const void *>(n_local, nullptr), 0, gathered, st)) {
         mw->plan_torn = true; // (a shard of some rank failed while being re-packed)
         return rc;
     }
-    mw->capacity = cap;
+    mw->capacity = rows;
     mw->cell_edge = edge;
     mw->planned = true;
     mw->violated = false;
@@ -929,23 +810,9 @@ int make_plan_full(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace)
             migrated += owner[g] != holder[g];
         }
         trace.lap("cuts, owners");
-        std::vector<uint8_t> held_owner;
-        for (size_t k = 0; k < n_local; ++k) {
-            Shard &s = mw->shards[k];
-            ShardPlan &pl = plans[k];
-            HaloPlanner::plan_rank(keys.data(), owner.data(), n, s.rank, mw->joints.data(), (uint32_t)mw->joints.size(), pl.own, pl.ghosts, pl.boundary, &pl.far);
-            pl.own_holder.resize(pl.own.size());
-            for (size_t i = 0; i < pl.own.size(); ++i)
-                pl.own_holder[i] = holder[pl.own[i]];
-            pl.ghost_owner.resize(pl.ghosts.size());
-            pl.ghost_holder.resize(pl.ghosts.size());
-            for (size_t i = 0; i < pl.ghosts.size(); ++i)
-                pl.ghost_owner[i] = owner[pl.ghosts[i]], pl.ghost_holder[i] = holder[pl.ghosts[i]];
-            held_owner.resize(s.held_ids.size());
-            for (size_t i = 0; i < s.held_ids.size(); ++i)
-                held_owner[i] = owner[s.held_ids[i]];
-            exports_of(s.rank, s.held_ids, held_owner, pl.boundary, pl.exports);
-        }
+        for (size_t k = 0; k < n_local; ++k)
+            full_rank_plan(mw->shards[k].rank, mw->shards[k].held_ids, keys.data(), owner.data(), holder.data(), n, mw->joints.data(),
+                           (uint32_t)mw->joints.size(), plans[k]);
     }
     trace.lap("halo plans");
     XPBD_TRY(finish_plan(mw, st, plans, edge, trace));
@@ -1023,41 +890,28 @@ int make_plan_light(xpbd_multi_world *mw, LocalStatus &st, PlanTrace &trace, boo
     // the rims: (key, id, new owner) of the held bodies near a cut, changing owner, or at the end of a joint that leaves the shard
     const std::vector<int64_t> cut_layers = cut_layers_of(mw->cuts);
     const JointIndex ji = mw->joint_lists.view(mw->joints.data());
-    std::vector<std::vector<RimRow>> rim(n_local);
+    RankLists<RimRow> rim(n_local);
     if (mw->slot_of.size() != n)
         mw->slot_of.assign(n, -1);
     for (size_t k = 0; k < n_local && st.ok(); ++k)
-        rim_rows_of(mw->shards[k].rank, mw->shards[k].held_ids, held_keys[k], held_owner[k], held_slab[k], cut_layers, ji, mw->slot_of, rim[k]);
-    std::vector<uint32_t> rim_count(n_local), rim_counts(w);
-    for (size_t k = 0; k < n_local; ++k) {
-        rim_count[k] = (uint32_t)rim[k].size();
-        send[k] = &rim_count[k];
-    }
-    XPBD_TRY(all_gather_host(mw, send, 4, gathered, st));
-    std::memcpy(rim_counts.data(), gathered.data(), (size_t)w * 4);
-    uint32_t cap_rim = 1;
-    for (uint32_t c : rim_counts)
-        cap_rim = std::max(cap_rim, c);
-    for (size_t k = 0; k < n_local; ++k) {
-        rim[k].resize(cap_rim, RimRow{0, UINT32_MAX, 0xFF, {0, 0, 0}});
-        send[k] = rim[k].data();
-    }
-    XPBD_TRY(all_gather_host(mw, send, (size_t)cap_rim * sizeof(RimRow), gathered, st));
+        rim_rows_of(mw->shards[k].rank, mw->shards[k].held_ids, held_keys[k], held_owner[k], held_slab[k], cut_layers, ji, mw->slot_of, rim.local[k]);
+    XPBD_TRY(gather_counts(mw, st, rim));
+    XPBD_TRY(gather_rows(mw, st, rim));
     if (trace.on)
-        std::fprintf(stderr, "[xpbd plan %llu] rim rows per rank: up to %u\n", (unsigned long long)mw->plans, cap_rim);
+        std::fprintf(stderr, "[xpbd plan %llu] rim rows per rank: up to %u\n", (unsigned long long)mw->plans, rim.widest);
     trace.lap("rims of the world");
     // everybody's rim by body id: (key, owner, holder)
     KnownMap known;
     if (st.ok()) {
         size_t total = 0;
-        for (uint32_t c : rim_counts)
+        for (uint32_t c : rim.counts)
             total += c;
         known.reserve(total * 2 + 16);
         for (uint32_t h = 0; h < w && st.ok(); ++h) {
-            const RimRow *rows = reinterpret_cast<const RimRow *>(gathered.data() + (size_t)h * cap_rim * sizeof(RimRow));
-            for (uint32_t i = 0; i < rim_counts[h]; ++i) {
-                if (rows[i].id >= n || rows[i].owner >= w || !known.emplace(rows[i].id, Known{rows[i].key, rows[i].owner, (uint8_t)h}).second) {
-                    st.keep(set_error(XPBD_E_INVALID, "xpbd_multi_world: body %u is held twice or out of range (rank %u)", rows[i].id, h));
+            for (uint32_t i = 0; i < rim.counts[h]; ++i) {
+                const RimRow row = rim.at(h, i);
+                if (row.id >= n || row.owner >= w || !known.emplace(row.id, Known{row.key, row.owner, (uint8_t)h}).second) {
+                    st.keep(set_error(XPBD_E_INVALID, "xpbd_multi_world: body %u is held twice or out of range (rank %u)", row.id, h));
                     break;
                 }
             }
@@ -1384,46 +1238,11 @@ int restore_frame(xpbd_multi_world *mw)
     return XPBD_OK;
 }
 
-// 1 for the slots of a shard's owned bodies, 0 for its ghosts.
-std::vector<uint8_t> owned_mask(const Shard &s)
-{
-    std::vector<uint8_t> owned(s.local_ids.size(), 1);
-    size_t g = 0;
-    for (size_t q = 0; q < s.local_ids.size(); ++q) { // local_ids and ghosts are both ascending
-        while (g < s.ghosts.size() && s.ghosts[g] < s.local_ids[q])
-            ++g;
-        if (g < s.ghosts.size() && s.ghosts[g] == s.local_ids[q])
-            owned[q] = 0;
-    }
-    return owned;
-}
-
-// The global id of every local slot of a shard for its scene queries: its OWNED bodies answer, under their global ids (ghosts
-// are listed as XPBD_NO_HIT).
-int upload_query_ids(Shard &s)
-{
-    XPBD_TRY(bind(s));
-    const std::vector<uint8_t> owned = owned_mask(s);
-    std::vector<uint32_t> ids(s.local_ids);
-    for (size_t q = 0; q < ids.size(); ++q)
-        if (!owned[q])
-            ids[q] = XPBD_NO_HIT;
-    XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
-    return upload_vector(s.query_ids, ids, s.stream);
-}
-
-int shard_raycast(Shard &s, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, bool masked, uint32_t mask, xpbd_ray_hit *hits)
-{
-    XPBD_TRY(upload_query_ids(s));
-    return xpbd::raycast_host(s.world, rays, n_rays, flags, hits, s.query_ids.as<uint32_t>(), masked, mask);
-}
-
 // One shard's part of an overlap query: its OWNED bodies answer, under their global ids.  Counts first, then lists into a
 // buffer of exactly that size; local_ids ascend, so every query's list is ascending in global index.
 int shard_overlap(Shard &s, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, std::vector<uint32_t> &offsets,
                   std::vector<xpbd_overlap_hit> &hits)
 {
-    XPBD_TRY(upload_query_ids(s));
     offsets.assign((size_t)n_queries + 1, 0);
     uint32_t total = 0;
     const int rc = xpbd::overlap_host(s.world, queries, n_queries, flags, offsets.data(), nullptr, 0, &total, s.query_ids.as<uint32_t>());
@@ -1433,12 +1252,6 @@ int shard_overlap(Shard &s, const xpbd_overlap_query *queries, uint32_t n_querie
     if (total == 0)
         return XPBD_OK;
     return xpbd::overlap_host(s.world, queries, n_queries, flags, offsets.data(), hits.data(), total, &total, s.query_ids.as<uint32_t>());
-}
-
-int shard_sweep(Shard &s, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits)
-{
-    XPBD_TRY(upload_query_ids(s));
-    return xpbd::sweep_host(s.world, sweeps, n_sweeps, flags, hits, s.query_ids.as<uint32_t>());
 }
 
 int check_usable(const xpbd_multi_world *mw, const char *who)
@@ -1473,7 +1286,7 @@ int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, u
     std::vector<const void *> send;
     for (size_t k = 0; k < mw->shards.size(); ++k) {
         if (st.ok())
-            st.keep(shard_raycast(mw->shards[k], rays, n_rays, flags, masked, mask, mine[k].data()));
+            st.keep(xpbd::raycast_host(mw->shards[k].world, rays, n_rays, flags, mine[k].data(), mw->shards[k].query_ids.as<uint32_t>(), masked, mask));
         send.push_back(mine[k].data());
     }
     std::vector<uint8_t> all;
@@ -1534,7 +1347,7 @@ int multi_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint32_t n_sweep
     std::vector<const void *> send;
     for (size_t k = 0; k < mw->shards.size(); ++k) {
         if (st.ok())
-            st.keep(shard_sweep(mw->shards[k], sweeps, n_sweeps, flags, mine[k].data()));
+            st.keep(xpbd::sweep_host(mw->shards[k].world, sweeps, n_sweeps, flags, mine[k].data(), mw->shards[k].query_ids.as<uint32_t>()));
         send.push_back(mine[k].data());
     }
     std::vector<uint8_t> all;
@@ -1562,10 +1375,6 @@ int shard_report(Shard &s, std::vector<xpbd_pair_contact> &pairs, std::vector<xp
     if (xpbd_world_body_count(s.world) != s.local_ids.size())
         return set_error(XPBD_E_INVALID, "contact report: shard %u holds %u bodies, its plan %zu", s.rank, xpbd_world_body_count(s.world),
                          s.local_ids.size());
-    const std::vector<uint8_t> owned = owned_mask(s);
-    XPBD_HIP_TRY(hipStreamSynchronize(s.stream)); // reserve() may free the previous block
-    XPBD_TRY(upload_vector(s.report_ids, s.local_ids, s.stream));
-    XPBD_TRY(upload_vector(s.report_owned, owned, s.stream));
     return xpbd::report_shard(s.world, s.report_owned.as<uint8_t>(), s.report_ids.as<uint32_t>(), pairs, points);
 }
 
@@ -1584,47 +1393,12 @@ int capture_report(xpbd_multi_world *mw)
     XPBD_TRY(gather_counts(mw, st, pairs, points));
     XPBD_TRY(gather_rows(mw, st, pairs));
     XPBD_TRY(gather_rows(mw, st, points));
-    // merge: (key, rank, row) in key order
-    struct Item {
-        uint64_t key;
-        uint32_t rank, row;
-    };
-    std::vector<Item> items;
-    for (uint32_t r = 0; r < mw->n_ranks; ++r)
-        for (uint32_t i = 0; i < pairs.counts[r]; ++i) {
-            const xpbd_pair_contact c = pairs.at(r, i);
-            items.push_back(Item{(uint64_t)c.body_a << 32 | c.body_b, r, i});
-        }
-    std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.key < b.key; });
-    std::vector<xpbd_pair_contact> merged(items.size());
+    std::vector<xpbd_pair_contact> merged;
     std::vector<xpbd_contact_point> merged_points;
-    std::vector<uint64_t> keys(items.size());
-    for (size_t i = 0; i < items.size(); ++i) {
-        xpbd_pair_contact c = pairs.at(items[i].rank, items[i].row);
-        const uint32_t from = c.first_point;
-        c.first_point = (uint32_t)merged_points.size();
-        for (uint32_t q = 0; q < c.n_points; ++q)
-            merged_points.push_back(points.at(items[i].rank, from + q));
-        merged[i] = c;
-        keys[i] = items[i].key;
-    }
-    // events: BEGINs (keys - prev), then ENDs (prev - keys), each in key order
-    std::vector<xpbd_contact_event> events, ends;
-    size_t a = 0, b = 0;
-    const std::vector<uint64_t> &prev = mw->report_prev;
-    while (a < keys.size() || b < prev.size()) {
-        if (b == prev.size() || (a < keys.size() && keys[a] < prev[b])) {
-            events.push_back(xpbd_contact_event{(uint32_t)(keys[a] >> 32), (uint32_t)keys[a], XPBD_CONTACT_BEGIN});
-            ++a;
-        } else if (a == keys.size() || prev[b] < keys[a]) {
-            ends.push_back(xpbd_contact_event{(uint32_t)(prev[b] >> 32), (uint32_t)prev[b], XPBD_CONTACT_END});
-            ++b;
-        } else {
-            ++a, ++b;
-        }
-    }
-    mw->report_begins = (uint32_t)events.size();
-    events.insert(events.end(), ends.begin(), ends.end());
+    std::vector<uint64_t> keys;
+    std::vector<xpbd_contact_event> events;
+    xpbd::merge_contact_reports(pairs.rows.data(), pairs.widest, pairs.counts.data(), points.rows.data(), points.widest, mw->n_ranks, merged, merged_points, keys);
+    mw->report_begins = xpbd::contact_events(keys, mw->report_prev, events);
     mw->report_pairs.swap(merged);
     mw->report_points.swap(merged_points);
     mw->report_events.swap(events);
@@ -1887,7 +1661,7 @@ try {
     for (Shard &s : mw->shards) {
         slots.clear(), force.clear(), torque.clear();
         for (uint32_t k = 0; k < n; ++k) {
-            const int32_t slot = slot_in_shard(s, indices ? indices[k] : k);
+            const int32_t slot = slot_in_shard(s.local_ids, indices ? indices[k] : k);
             if (slot < 0)
                 continue;
             slots.push_back((uint32_t)slot);
@@ -1918,7 +1692,7 @@ try {
     for (Shard &s : mw->shards) {
         local.clear();
         for (uint32_t k = 0; k < n; ++k) { // list order kept: the shard's world sorts by slot (stable), which ascends with the global id
-            const int32_t slot = slot_in_shard(s, list[k].body);
+            const int32_t slot = slot_in_shard(s.local_ids, list[k].body);
             if (slot < 0)
                 continue;
             local.push_back(list[k]);

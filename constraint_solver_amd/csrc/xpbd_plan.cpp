@@ -561,6 +561,111 @@ int light_rank_plan(uint32_t rank, const std::vector<uint32_t> &held_ids, const 
     return XPBD_OK;
 }
 
+void full_rank_plan(uint32_t rank, const std::vector<uint32_t> &held_ids, const int64_t *keys, const uint8_t *owner, const uint8_t *holder, uint32_t n,
+                    const xpbd_joint *joints, uint32_t n_joints, ShardPlan &pl)
+{
+    HaloPlanner::plan_rank(keys, owner, n, rank, joints, n_joints, pl.own, pl.ghosts, pl.boundary, &pl.far);
+    pl.own_holder.resize(pl.own.size());
+    for (size_t i = 0; i < pl.own.size(); ++i)
+        pl.own_holder[i] = holder[pl.own[i]];
+    pl.ghost_owner.resize(pl.ghosts.size());
+    pl.ghost_holder.resize(pl.ghosts.size());
+    for (size_t i = 0; i < pl.ghosts.size(); ++i)
+        pl.ghost_owner[i] = owner[pl.ghosts[i]], pl.ghost_holder[i] = holder[pl.ghosts[i]];
+    std::vector<uint8_t> held_owner(held_ids.size());
+    for (size_t i = 0; i < held_ids.size(); ++i)
+        held_owner[i] = owner[held_ids[i]];
+    exports_of(rank, held_ids, held_owner, pl.boundary, pl.exports);
+}
+
+int layout_shard(uint32_t rank, const ShardPlan &pl, const std::vector<uint32_t> &held_ids, const std::vector<uint32_t> &held_slots, const RankIds &boundary,
+                 const RankIds &exports, uint32_t rows, const JointIndex &ji, std::vector<int32_t> &slot_of, double margin, double edge, ShardLayout &out)
+{
+    const uint32_t n_own = (uint32_t)pl.own.size(), n_ghost = (uint32_t)pl.ghosts.size(), n_loc = n_own + n_ghost;
+    out = ShardLayout();
+    out.local_ids.resize(n_loc);
+    out.src.resize(n_loc);
+    out.owned_slots.resize(n_own);
+    out.ghost_slots.resize(n_ghost);
+    out.ghost_rows.resize(n_ghost);
+    // owned + ghost bodies in ascending global id.  A body the shard owned before and still owns moves on the device; a body
+    // that arrives (a new owner, a ghost) comes from its holder's exported record.
+    uint32_t slot = 0, oi = 0, gi = 0;
+    size_t old = 0; // walks the bodies held so far (ascending, like pl.own)
+    while (oi < n_own || gi < n_ghost) {
+        const bool take_own = gi >= n_ghost || (oi < n_own && pl.own[oi] < pl.ghosts[gi]);
+        const uint32_t g = take_own ? pl.own[oi] : pl.ghosts[gi];
+        out.local_ids[slot] = g;
+        if (take_own && pl.own_holder[oi] == rank) {
+            while (old < held_ids.size() && held_ids[old] < g)
+                ++old;
+            if (old == held_ids.size() || held_ids[old] != g)
+                return set_error(XPBD_E_HIP, "xpbd_multi_world: body %u is not among the bodies rank %u holds (inconsistent plans)", g, rank);
+            out.src[slot] = (int32_t)held_slots[old];
+        } else {
+            const uint32_t h = take_own ? pl.own_holder[oi] : pl.ghost_holder[gi];
+            const int64_t at = exports.find(h, g);
+            if (at < 0)
+                return set_error(XPBD_E_HIP, "xpbd_multi_world: body %u is needed by rank %u but not exported by its holder %u (inconsistent plans)", g, rank, h);
+            out.incoming.push_back(ShardLayout::Incoming{h, (uint32_t)at});
+            out.src[slot] = -(int32_t)out.incoming.size();
+        }
+        if (take_own) {
+            out.owned_slots[oi++] = slot;
+        } else {
+            const uint32_t o = pl.ghost_owner[gi];
+            const int64_t at = boundary.find(o, g);
+            if (at < 0)
+                return set_error(XPBD_E_HIP, "xpbd_multi_world: body %u is mirrored by rank %u but not exported by its owner %u (inconsistent plans)", g, rank, o);
+            out.ghost_slots[gi] = slot;
+            out.ghost_rows[gi] = o * rows + (uint32_t)at;
+            ++gi;
+        }
+        ++slot;
+    }
+    out.boundary_slots.resize(pl.boundary.size());
+    for (size_t q = 0; q < pl.boundary.size(); ++q)
+        out.boundary_slots[q] = out.owned_slots[std::lower_bound(pl.own.begin(), pl.own.end(), pl.boundary[q]) - pl.own.begin()];
+    out.skip.assign(n_loc, 0);
+    out.owned.assign(n_loc, 1);
+    out.query_ids = out.local_ids;
+    for (uint32_t q : out.boundary_slots)
+        out.skip[q] = 1;
+    for (uint32_t q : out.ghost_slots)
+        out.skip[q] = 1, out.owned[q] = 0, out.query_ids[q] = XPBD_NO_HIT;
+    // joints whose two bodies are both present here, in global joint order, re-indexed to local slots: the joints of the
+    // local bodies through the per-body joint lists (a joint is taken at its lower-numbered end)
+    for (uint32_t q = 0; q < n_loc; ++q)
+        slot_of[out.local_ids[q]] = (int32_t)q;
+    for (uint32_t q = 0; q < n_loc && ji.any; ++q) {
+        const uint32_t g = out.local_ids[q];
+        for (uint32_t e = ji.off[g]; e < ji.off[g + 1]; ++e) {
+            const xpbd_joint &j = ji.joints[ji.adj[e]];
+            const uint32_t other = j.body_a == g ? j.body_b : j.body_a;
+            if (slot_of[other] >= 0 && (g < other || (g == other && j.body_a == g)))
+                out.joint_ids.push_back(ji.adj[e]);
+        }
+    }
+    std::sort(out.joint_ids.begin(), out.joint_ids.end());
+    out.joint_ids.erase(std::unique(out.joint_ids.begin(), out.joint_ids.end()), out.joint_ids.end());
+    out.joints.resize(out.joint_ids.size());
+    for (size_t q = 0; q < out.joint_ids.size(); ++q) {
+        xpbd_joint l = ji.joints[out.joint_ids[q]];
+        l.body_a = (uint32_t)slot_of[l.body_a];
+        l.body_b = (uint32_t)slot_of[l.body_b];
+        out.joints[q] = l;
+    }
+    for (uint32_t q = 0; q < n_loc; ++q)
+        slot_of[out.local_ids[q]] = -1;
+    // 1 / allowance^2 per owned body: the displacement check then yields the largest FRACTION of its allowance any body has used
+    const double near_allow = margin, far_allow = margin + 0.5 * edge;
+    const double near_scale = 1.0 / (near_allow * near_allow), far_scale = 1.0 / (far_allow * far_allow);
+    out.disp_scale.resize(n_own);
+    for (uint32_t i = 0; i < n_own; ++i)
+        out.disp_scale[i] = pl.far[i] ? far_scale : near_scale;
+    return XPBD_OK;
+}
+
 namespace {
 // Ownership by contiguous index ranges (what a caller that orders its bodies itself would get).
 void range_owners(uint32_t n_global, uint32_t n_ranks, std::vector<uint8_t> &owner)

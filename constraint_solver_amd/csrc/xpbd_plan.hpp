@@ -166,5 +166,70 @@ void rim_rows_of(uint32_t rank, const std::vector<uint32_t> &held_ids, const std
 int light_rank_plan(uint32_t rank, const std::vector<uint32_t> &held_ids, const std::vector<int64_t> &held_keys, const std::vector<uint8_t> &held_owner,
                     KnownMap &known, const JointIndex &ji, std::vector<int32_t> &slot_of, ShardPlan &pl);
 
+// ... and the same plan from the keys, owners and holders of ALL n bodies of the world (a full plan).
+void full_rank_plan(uint32_t rank, const std::vector<uint32_t> &held_ids, const int64_t *keys, const uint8_t *owner, const uint8_t *holder, uint32_t n,
+                    const xpbd_joint *joints, uint32_t n_joints, ShardPlan &pl);
+
+// ---- the layout of a shard: a plan turned into local slots -----------------------------------------------------------------------
+// The id lists of all ranks as gathered: rank r's counts[r] ids (ascending) start at ids[r * width].
+struct RankIds {
+    const uint32_t *ids, *counts;
+    uint32_t width, n_ranks;
+    int64_t find(uint32_t rank, uint32_t g) const // where g stands in the list of `rank`, or -1 (no such rank, not listed)
+    {
+        if (rank >= n_ranks || counts[rank] == 0)
+            return -1;
+        const uint32_t *lo = ids + (size_t)rank * width, *hi = lo + counts[rank], *at = std::lower_bound(lo, hi, g);
+        return at != hi && *at == g ? (int64_t)(at - lo) : -1;
+    }
+};
+
+// A shard's local world under a plan: its owned bodies and its ghosts in ascending global id, one slot each.
+struct ShardLayout {
+    struct Incoming { // where the record of a body that arrives lies: its holder, its place in the holder's export list
+        uint32_t holder, row;
+    };
+    std::vector<uint32_t> local_ids;                  // global id of every slot
+    std::vector<uint32_t> owned_slots, ghost_slots;   // slot of pl.own[i], of pl.ghosts[i]
+    std::vector<uint32_t> ghost_rows;                 // row of pl.ghosts[i] in the per-substep all-gather: owner * rows + place on its boundary list
+    std::vector<uint32_t> boundary_slots;             // slot of pl.boundary[i]
+    std::vector<uint8_t> skip;                        // per slot: 1 for boundary bodies and ghosts (what the interior launch leaves out)
+    std::vector<uint8_t> owned;                       // per slot: 1 for owned bodies, 0 for ghosts
+    std::vector<uint32_t> query_ids;                  // per slot: local_ids, XPBD_NO_HIT for the ghosts (the owned bodies answer scene queries)
+    std::vector<int32_t> src;                         // per slot: the slot the body has now (it stays on this shard), or -(k + 1) for the k-th arrival
+    std::vector<Incoming> incoming;                   // the arrivals, in slot order
+    std::vector<uint32_t> joint_ids;                  // global joints (ascending) with both ends here
+    std::vector<xpbd_joint> joints;                   // ... re-indexed to slots: local joint q = joint_ids[q]
+    std::vector<double> disp_scale;                   // per owned body: 1 / allowance^2 (allowance: margin, or margin + edge / 2 where pl.far)
+};
+
+// held_ids / held_slots: the bodies the shard holds now (ascending) and their slots; boundary / exports: those lists of every
+// rank's NEW plan; rows: rows per rank of the per-substep all-gather.  slot_of: [n_global] scratch, -1 everywhere on entry and
+// on return.  XPBD_E_HIP ("inconsistent plans") if the plans of the ranks do not fit together; `out` is unspecified then.
+int layout_shard(uint32_t rank, const ShardPlan &pl, const std::vector<uint32_t> &held_ids, const std::vector<uint32_t> &held_slots, const RankIds &boundary,
+                 const RankIds &exports, uint32_t rows, const JointIndex &ji, std::vector<int32_t> &slot_of, double margin, double edge, ShardLayout &out);
+
+// The slot of global body g among local_ids (ascending), or -1.
+inline int32_t slot_in_shard(const std::vector<uint32_t> &local_ids, uint32_t g)
+{
+    const auto at = std::lower_bound(local_ids.begin(), local_ids.end(), g);
+    return at != local_ids.end() && *at == g ? (int32_t)(at - local_ids.begin()) : -1;
+}
+
+// The records (joint limits or drives: both name a joint in .joint) on the joints of a shard (joint_ids, ascending), re-indexed
+// to the shard's joint numbering; the caller's order is kept.
+template <class Record> std::vector<Record> local_joint_records(const std::vector<Record> &global, const std::vector<uint32_t> &joint_ids)
+{
+    std::vector<Record> local;
+    for (const Record &r : global) {
+        const int32_t q = slot_in_shard(joint_ids, r.joint);
+        if (q >= 0) {
+            local.push_back(r);
+            local.back().joint = (uint32_t)q;
+        }
+    }
+    return local;
+}
+
 } // namespace plan
 } // namespace xpbd

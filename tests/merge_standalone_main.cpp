@@ -1,12 +1,13 @@
-// merge_standalone_main.cpp -- the merges of the multi-GPU world's scene queries (csrc/xpbd_merge.hpp) on their own, with no
-// device and no Python: built by tests/test_merge_standalone.py with plain g++, also under ASan/UBSan.  The expected answers
-// come from concatenating every rank's candidates and sorting them.  Exits non-zero with a one-line message on the first
-// difference.
+// merge_standalone_main.cpp -- the merges of the multi-GPU world's scene queries and contact reports (csrc/xpbd_merge.hpp) on
+// their own, with no device and no Python: built by tests/test_merge_standalone.py with plain g++, also under ASan/UBSan.  The
+// expected answers come from concatenating every rank's candidates and sorting them, the events from set differences.  Exits
+// non-zero with a one-line message on the first difference.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <set>
 #include <vector>
 
 #include "../constraint_solver_amd/csrc/xpbd_merge.hpp"
@@ -220,6 +221,123 @@ int run_overlaps()
     return check_overlaps("overlaps, no hits", nothing, concatenate_and_sort(nothing));
 }
 
+// ---- contact reports -------------------------------------------------------------------------------------------------------
+struct RankReport {
+    std::vector<xpbd_pair_contact> pairs; // in the rank's own key order
+    std::vector<xpbd_contact_point> points;
+};
+
+int check_report(const char *scene, const std::vector<RankReport> &ranks, const std::vector<uint64_t> &prev)
+{
+    const uint32_t n_ranks = (uint32_t)ranks.size();
+    uint32_t pair_width = 1, point_width = 1;
+    std::vector<uint32_t> counts;
+    for (const RankReport &r : ranks) {
+        pair_width = std::max(pair_width, (uint32_t)r.pairs.size());
+        point_width = std::max(point_width, (uint32_t)r.points.size());
+        counts.push_back((uint32_t)r.pairs.size());
+    }
+    // the gathered rows; the padding holds a pattern that is no record
+    std::vector<xpbd_pair_contact> pair_rows((size_t)n_ranks * pair_width);
+    std::vector<xpbd_contact_point> point_rows((size_t)n_ranks * point_width);
+    std::memset(pair_rows.data(), 0xEE, pair_rows.size() * sizeof(xpbd_pair_contact));
+    std::memset(point_rows.data(), 0xEE, point_rows.size() * sizeof(xpbd_contact_point));
+    struct Want {
+        uint64_t key;
+        xpbd_pair_contact pair;
+        std::vector<xpbd_contact_point> points;
+    };
+    std::vector<Want> want;
+    for (uint32_t r = 0; r < n_ranks; ++r) {
+        std::copy(ranks[r].pairs.begin(), ranks[r].pairs.end(), pair_rows.begin() + (size_t)r * pair_width);
+        std::copy(ranks[r].points.begin(), ranks[r].points.end(), point_rows.begin() + (size_t)r * point_width);
+        for (const xpbd_pair_contact &c : ranks[r].pairs)
+            want.push_back(Want{(uint64_t)c.body_a << 32 | c.body_b, c,
+                                std::vector<xpbd_contact_point>(ranks[r].points.begin() + c.first_point, ranks[r].points.begin() + c.first_point + c.n_points)});
+    }
+    std::sort(want.begin(), want.end(), [](const Want &a, const Want &b) { return a.key < b.key; });
+    std::vector<xpbd_pair_contact> pairs(3); // (whatever the vectors held is replaced)
+    std::vector<xpbd_contact_point> points(5);
+    std::vector<uint64_t> keys(7);
+    xpbd::merge_contact_reports(pair_rows.data(), pair_width, counts.data(), point_rows.data(), point_width, n_ranks, pairs, points, keys);
+    if (pairs.size() != want.size() || keys.size() != want.size())
+        return fail(scene, "the merged report has the wrong number of pairs", (uint32_t)pairs.size());
+    uint32_t at = 0;
+    for (size_t i = 0; i < want.size(); ++i) {
+        xpbd_pair_contact c = want[i].pair;
+        c.first_point = at;
+        if (keys[i] != want[i].key || std::memcmp(&pairs[i], &c, sizeof c) != 0)
+            return fail(scene, "a pair is out of key order or its first_point is not re-based", (uint32_t)i);
+        if (points.size() < at + c.n_points ||
+            (c.n_points && std::memcmp(&points[at], want[i].points.data(), c.n_points * sizeof(xpbd_contact_point)) != 0))
+            return fail(scene, "a pair's points did not follow it", (uint32_t)i);
+        at += c.n_points;
+    }
+    if (points.size() != at)
+        return fail(scene, "points nobody refers to", at);
+    // events: BEGINs = keys - prev, ENDs = prev - keys, each ascending
+    const std::set<uint64_t> now(keys.begin(), keys.end()), before(prev.begin(), prev.end());
+    std::vector<xpbd_contact_event> want_events, events(2);
+    for (uint64_t k : now)
+        if (!before.count(k))
+            want_events.push_back(xpbd_contact_event{(uint32_t)(k >> 32), (uint32_t)k, XPBD_CONTACT_BEGIN});
+    const uint32_t want_begins = (uint32_t)want_events.size();
+    for (uint64_t k : before)
+        if (!now.count(k))
+            want_events.push_back(xpbd_contact_event{(uint32_t)(k >> 32), (uint32_t)k, XPBD_CONTACT_END});
+    const uint32_t begins = xpbd::contact_events(keys, prev, events);
+    if (begins != want_begins || events.size() != want_events.size() ||
+        (!events.empty() && std::memcmp(events.data(), want_events.data(), events.size() * sizeof(xpbd_contact_event)) != 0))
+        return fail(scene, "the events are not the BEGINs then the ENDs of the set differences, in key order", begins);
+    return 0;
+}
+
+int run_reports()
+{
+    for (uint32_t n_ranks : {2u, 3u, 4u}) {
+        Lcg rng{0xA0761D6478BD642Full ^ n_ranks};
+        // disjoint lists: the pair (a, b) belongs to rank a % n_ranks; rank 1 has no pairs; 0 .. 8 points each
+        std::vector<RankReport> ranks(n_ranks);
+        std::vector<uint64_t> all_keys;
+        for (uint32_t r = 0; r < n_ranks; ++r) {
+            if (r == 1)
+                continue;
+            uint32_t a = r;
+            for (uint32_t k = 0; k < 37; ++k) {
+                a += n_ranks * (rng.next() % 3); // (the same a again: several pairs of one lower body)
+                xpbd_pair_contact c{};
+                c.body_a = a, c.body_b = a + 1 + 50 * k + rng.next() % 50, c.substeps = 1 + rng.next() % 20, c.n_points = rng.next() % 9;
+                c.feature = r, c.first_point = (uint32_t)ranks[r].points.size(), c.depth = -(double)k;
+                for (uint32_t q = 0; q < c.n_points; ++q) {
+                    xpbd_contact_point p{};
+                    p.p_ref[0] = (double)c.body_a, p.p_ref[1] = (double)c.body_b, p.p_inc[2] = (double)q;
+                    ranks[r].points.push_back(p);
+                }
+                ranks[r].pairs.push_back(c);
+                all_keys.push_back((uint64_t)c.body_a << 32 | c.body_b);
+            }
+        }
+        // the previous frame: half of this frame's pairs and as many that are gone
+        std::vector<uint64_t> prev;
+        for (uint64_t k : all_keys) {
+            if (rng.next() % 2)
+                prev.push_back(k);
+            if (rng.next() % 2)
+                prev.push_back(k ^ 0x80000000ull); // (body_b + 2^31: no pair of this frame)
+        }
+        std::sort(prev.begin(), prev.end());
+        if (int rc = check_report("reports, random", ranks, prev))
+            return rc;
+        if (int rc = check_report("reports, empty previous frame", ranks, {}))
+            return rc;
+        if (int rc = check_report("reports, empty frame", std::vector<RankReport>(n_ranks), prev))
+            return rc;
+        if (int rc = check_report("reports, nothing at all", std::vector<RankReport>(n_ranks), {}))
+            return rc;
+    }
+    return 0;
+}
+
 } // namespace
 
 int main()
@@ -227,6 +345,8 @@ int main()
     if (int rc = run_rays())
         return rc;
     if (int rc = run_overlaps())
+        return rc;
+    if (int rc = run_reports())
         return rc;
     std::puts("merge_standalone: ok");
     return 0;

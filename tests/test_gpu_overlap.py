@@ -458,13 +458,14 @@ def test_the_sharded_world_equals_the_single_world(n_ranks):
         mw.upload(bodies, sid, 0, n)
         for _ in range(frames):
             mw.step(DT, substeps)
-        mw.replan()
-        assert mw.plan_stats()["plans"] >= 2
         state = single.download()
-        assert same_bits(mw.download(), state)
         q = query_families(np.random.default_rng(20 + n_ranks), state, sid, polys, 192)
         want = single.overlap(q)
         assert want[0][-1] > 100 and np.any(q["ignore_body"] != capi.NO_HIT)
+        assert same_answer(mw.overlap(q), want)             # under the plans the steps made; then under one more
+        mw.replan()
+        assert mw.plan_stats()["plans"] >= 2
+        assert same_bits(mw.download(), state)
         assert same_answer(mw.overlap(q), want)
         assert same_answer(mw.overlap(q, BRUTE), want)
         assert same_answer(mw.overlap(q[:3]), single.overlap(q[:3]))

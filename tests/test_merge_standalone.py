@@ -1,8 +1,9 @@
-"""The merges of the multi-GPU world's scene queries are host-only: csrc/xpbd_merge.hpp builds with plain g++ (no hipcc, no
-ROCm include path) into a stand-alone program, tests/merge_standalone_main.cpp, which checks the ray merge (ties in distance
-broken by body, a rank without hits, one rank) and the overlap merge (a query one rank answers, a query three ranks answer,
-empty queries, every cap from 0 -- with NULL hits -- to past the total) against concatenate-and-sort and exits 0.  No GPU and
-no Python extension involved.
+"""The merges of the multi-GPU world's scene queries and contact reports are host-only: csrc/xpbd_merge.hpp builds with plain
+g++ (no hipcc, no ROCm include path) into a stand-alone program, tests/merge_standalone_main.cpp, which checks the ray merge
+(ties in distance broken by body, a rank without hits, one rank), the overlap merge (a query one rank answers, a query three
+ranks answer, empty queries, every cap from 0 -- with NULL hits -- to past the total) and the report merge (2 to 4 ranks, one
+without pairs, 0 to 8 points a pair; the events against a random, an empty previous frame and from an empty frame) against
+concatenate-and-sort and set differences and exits 0.  No GPU and no Python extension involved.
 
 With XPBD_HOST_SANITIZE=1 the same program is also built and run under ASan + UBSan; it must leave stderr empty.  Opt-in
 because a sanitizer-linked executable refuses to start where something else is preloaded into every process."""

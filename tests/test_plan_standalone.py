@@ -1,6 +1,9 @@
 """The shard planner is host-only: csrc/xpbd_plan.cpp and csrc/xpbd_error.cpp build with plain g++ (no hipcc, no ROCm include
 path) into a stand-alone program, tests/plan_standalone_main.cpp, which checks the planner's properties on a 997-body cloud
-and on a 70 001-body slab (the threaded passes) and exits 0.  No GPU and no Python extension involved.
+and on a 70 001-body slab (the threaded passes) and exits 0.  On the cloud it also re-plans after a motion of less than a cell
+for 2, 3 and 5 ranks: the full and the light plan of every rank agree field by field, the layout of every shard (layout_shard:
+local slots, source map, ghost rows, boundary slots, skip flags, joints) and the re-indexed joint records equal a brute-force
+reading of the plans, and plans that do not fit together are refused.  No GPU and no Python extension involved.
 
 With XPBD_HOST_SANITIZE=1 the same program is also built and run under ASan + UBSan and under TSan (the planner is the only
 multi-threaded host code of the library); they must leave stderr empty.  Opt-in because a sanitizer-linked executable
