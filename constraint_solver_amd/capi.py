@@ -65,6 +65,7 @@ ABI_SYMBOLS = [
     "xpbd_world_overlap", "xpbd_world_overlap_device", "xpbd_multi_world_overlap",
     "xpbd_world_sweep", "xpbd_world_sweep_device", "xpbd_multi_world_sweep",
     "xpbd_world_remove_bodies", "xpbd_world_remove_bodies_device", "xpbd_world_add_bodies",
+    "xpbd_world_set_terrain", "xpbd_world_sample_terrain",
 ]
 
 
@@ -90,6 +91,12 @@ class MultiConfig(C.Structure):
                 ("contact_pad", C.c_double), ("halo_margin", C.c_double), ("narrowphase", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class HEIGHTFIELD(C.Structure):
+    """xpbd_heightfield (48 bytes): terrain (EXTENSION)"""
+    _fields_ = [("nx", C.c_uint32), ("ny", C.c_uint32), ("origin", C.c_double * 2), ("cell", C.c_double * 2), ("heights", _f64p)]
+
+
+MAX_TERRAIN_SAMPLES = 1 << 22
 COMM_ID_BYTES = 128
 TRANSPORT_RCCL, TRANSPORT_LOCAL = 0, 1
 MULTI_AUTO_REPLAN = 1
@@ -406,6 +413,11 @@ def hip_lib():
             L.xpbd_world_add_bodies.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _u32p]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
+        try:
+            L.xpbd_world_set_terrain.argtypes = [C.c_void_p, C.POINTER(HEIGHTFIELD)]
+            L.xpbd_world_sample_terrain.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
         _hip = L
     return _hip
 
@@ -605,6 +617,28 @@ class World:
         e = None if restitution is None else np.ascontiguousarray(restitution, dtype=np.float64).reshape(-1)
         _check(hip_lib().xpbd_world_set_restitution(self._h, None if e is None else e.ctypes.data, 0 if e is None else e.size,
                                                     ground_restitution, bounce_threshold))
+
+    def set_terrain(self, heights=None, origin=(0.0, 0.0), cell=(1.0, 1.0)):
+        """heights: (ny, nx) array, heights[iy, ix] at world (origin[0] + ix * cell[0], origin[1] + iy * cell[1]), the ground
+        of XPBD_MODE_CONTACTS in place of the plane z = 0 (extension); None: back to the plane."""
+        if heights is None:
+            _check(hip_lib().xpbd_world_set_terrain(self._h, None))
+            return
+        h = np.ascontiguousarray(heights, dtype=np.float64)
+        if h.ndim != 2:
+            raise ValueError("heights must be a 2-d array (ny rows of nx)")
+        hf = HEIGHTFIELD(h.shape[1], h.shape[0], (C.c_double * 2)(*origin), (C.c_double * 2)(*cell), _f64(h))
+        _check(hip_lib().xpbd_world_set_terrain(self._h, C.byref(hf)))
+
+    def sample_terrain(self, xy, normals=True):
+        """(height[n], normal[n, 3]) of the terrain under the points xy (n, 2): NaN and (0, 0, 0) outside the field.
+        normals=False: the heights alone."""
+        p = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        height = np.empty(p.shape[0], dtype=np.float64)
+        normal = np.empty((p.shape[0], 3), dtype=np.float64) if normals else None
+        _check(hip_lib().xpbd_world_sample_terrain(self._h, p.ctypes.data, p.shape[0], height.ctypes.data,
+                                                   None if normal is None else normal.ctypes.data))
+        return (height, normal) if normals else height
 
     def contacts_begin(self, dt):
         _check(hip_lib().xpbd_world_contacts_begin(self._h, dt))

@@ -105,6 +105,10 @@ struct ContactBuffers {
     const uint32_t *extra_off;         // [n_extra_joints + 1] CSR into extra_items: the SLIDE limit first, then the drives in the caller's order
     const JointExtraItem *extra_items;
     uint32_t n_extra_joints;
+    // heightfield terrain (xpbd_world_set_terrain): planes == NULL = none, the ground is the plane z = 0 and no kernel reads this.
+    // (Last again.)  With one, the integrate + ground stage and the restitution pass run their TERRAIN forms; the fused
+    // pair-solve + integrate + ground kernel has none, so the step runs the unfused schedule.
+    Terrain terrain;
 };
 
 // Which bodies a per-body kernel of the pipeline works on.  Default: all of them.  The multi-GPU world (xpbd_multi.cpp) runs
@@ -160,6 +164,12 @@ hipError_t launch_joint_extras(double h, const ContactBuffers &c, hipStream_t st
 // Every body's end-of-substep state (pose copied, velocities updated) goes to b.dyn, which no lane of the launch reads.
 hipError_t launch_restitution(const BodyArrays &b, const double *post, const double *start, const ShapeTable &s, const ContactBuffers &c,
                               const uint32_t *ground_masks, hipStream_t stream);
+
+// Heightfield terrain.  The plane table of a field from its heights (device, ny rows of nx): both triangles of every cell into
+// planes[cell][8], `t` describing the field (t.planes is not read).  And the terrain at n points xy[2k..] (device arrays):
+// height[k] and, unless normal_xyz is NULL, the unit normal; NaN and (0, 0, 0) outside the field.
+hipError_t launch_terrain_planes(const double *heights, const Terrain &t, double *planes, hipStream_t stream);
+hipError_t launch_sample_terrain(const Terrain &t, const double *xy, uint32_t n, double *height, double *normal_xyz, hipStream_t stream);
 
 // Rigid::frame() of all bodies from the SoA state into the post-integrate frame of their records (all the diagnostic
 // narrowphase entry points need); and the StatRecords from the SoA static fields (after an upload).

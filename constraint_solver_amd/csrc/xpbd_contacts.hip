@@ -552,7 +552,8 @@ __device__ __forceinline__ BodyDynamic load_row(const double *__restrict__ rows,
 // Per substep, per body: integrate, remember the frames, ground contacts (reference path).
 // ---------------------------------------------------------------------------------------------------
 // MATERIALS: the form of a world with contact materials (c.friction set); the plain form never reads them.
-template <bool TRACE, bool MATERIALS>
+// TERRAIN: the form of a world with a heightfield terrain (c.terrain.planes set): the ground contacts of xpbd_step.hpp's terrain forms.
+template <bool TRACE, bool MATERIALS, bool TERRAIN = false>
 __global__ void __launch_bounds__(kBlock) k_integrate_ground(BodyArrays b, ShapeTable shapes, double h, ContactBuffers c, BodySubset subset,
                                                              uint32_t *__restrict__ last_mask,
                                                              uint32_t *__restrict__ trace_masks, uint32_t trace_row)
@@ -578,9 +579,15 @@ __global__ void __launch_bounds__(kBlock) k_integrate_ground(BodyArrays b, Shape
     const double compliance = 1e-6 / (h * h);
 
     const SubstepFrames f = integrate_body(d, s, h);
-    const uint32_t mask = solve_ground<MATERIALS>(d, s, f, compliance, lds + 3 * v0, lds_off[sid + 1] - v0,
-                                                  c.max_depenetration_speed > 0.0 ? c.max_depenetration_speed * h : 0.0,
-                                                  MATERIALS ? ground_mu(c, i) : 0.0);
+    uint32_t mask;
+    if (TERRAIN)
+        mask = solve_ground<MATERIALS, true>(d, s, f, compliance, lds + 3 * v0, lds_off[sid + 1] - v0,
+                                             c.max_depenetration_speed > 0.0 ? c.max_depenetration_speed * h : 0.0,
+                                             MATERIALS ? ground_mu(c, i) : 0.0, c.terrain);
+    else
+        mask = solve_ground<MATERIALS>(d, s, f, compliance, lds + 3 * v0, lds_off[sid + 1] - v0,
+                                       c.max_depenetration_speed > 0.0 ? c.max_depenetration_speed * h : 0.0,
+                                       MATERIALS ? ground_mu(c, i) : 0.0);
 
     // the pose after the ground contacts lives in the record only: the pair solve (the one reader) takes it from there and
     // rewrites the whole SoA state (velocities come from derive)
@@ -588,6 +595,53 @@ __global__ void __launch_bounds__(kBlock) k_integrate_ground(BodyArrays b, Shape
     last_mask[i] = mask;
     if (TRACE)
         trace_masks[(size_t)trace_row * st + i] = mask;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Heightfield terrain (include/xpbd.h, "TERRAIN"): the plane table, once per xpbd_world_set_terrain, and the sampling call.
+// ---------------------------------------------------------------------------------------------------
+// One lane per cell: the planes of its lower (h00, h10, h11) and upper (h00, h11, h01) triangle, each {n.x, n.y, n.z, d}, as one
+// 64-byte record.  The header's formulas, operation by operation; (double)i is the lookup's floor(u).
+__global__ void __launch_bounds__(kBlock) k_terrain_planes(const double *__restrict__ heights, Terrain t, double *__restrict__ planes)
+{
+    const uint32_t cells_x = t.nx - 1;
+    const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
+    if (cell >= cells_x * (t.ny - 1))
+        return;
+    const uint32_t i = cell % cells_x, j = cell / cells_x;
+    const double *row = heights + (size_t)j * t.nx + i;
+    const double h00 = row[0], h10 = row[1], h01 = row[t.nx], h11 = row[t.nx + 1];
+    const Vec3 corner{t.x0 + (double)i * t.dx, t.y0 + (double)j * t.dy, h00};
+    double *out = planes + (size_t)cell * 8;
+#pragma unroll
+    for (uint32_t upper = 0; upper < 2; ++upper) {
+        const double sx = upper ? (h11 - h01) / t.dx : (h10 - h00) / t.dx;
+        const double sy = upper ? (h01 - h00) / t.dy : (h11 - h10) / t.dy;
+        const Vec3 raw{-sx, -sy, 1.0};
+        const Vec3 n = raw * (1.0 / length(raw));
+        out[4 * upper + 0] = n.x, out[4 * upper + 1] = n.y, out[4 * upper + 2] = n.z;
+        out[4 * upper + 3] = dot(n, corner);
+    }
+}
+
+// One lane per point: the stepper's lookup at (x, y, 0), then the plane solved for z.
+__global__ void __launch_bounds__(kBlock) k_sample_terrain(Terrain t, const double *__restrict__ xy, uint32_t n, double *__restrict__ height,
+                                                           double *__restrict__ normal_xyz)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n)
+        return;
+    const double x = xy[2 * (size_t)k + 0], y = xy[2 * (size_t)k + 1];
+    Plane p;
+    double z = __builtin_nan("");
+    Vec3 normal{0.0, 0.0, 0.0};
+    if (terrain_plane(t, Vec3{x, y, 0.0}, p)) {
+        z = (p.displacement - (p.normal.x * x + p.normal.y * y)) / p.normal.z;
+        normal = p.normal;
+    }
+    height[k] = z;
+    if (normal_xyz)
+        normal_xyz[3 * (size_t)k + 0] = normal.x, normal_xyz[3 * (size_t)k + 1] = normal.y, normal_xyz[3 * (size_t)k + 2] = normal.z;
 }
 
 __global__ void k_body_frames(BodyArrays b, double *__restrict__ rec)
@@ -1337,6 +1391,9 @@ __device__ __forceinline__ double max_restitution(double a, double b) { return a
 
 // One lane per body.  Reads the post-derive state of every body from `post` and the start-of-substep velocities from `start`,
 // writes the body's whole end-of-substep state to b.dyn, which no lane of this launch reads.
+// TERRAIN: the ground part looks the terrain's plane up at every vertex of the mask again (the pose has moved since the
+// integrate + ground stage): outside the field the vertex makes no entry, inside the plane's normal stands for (0, 0, 1).
+template <bool TERRAIN>
 __global__ void __launch_bounds__(kBlock) k_restitution(BodyArrays b, const double *__restrict__ post, const double *__restrict__ start,
                                                         ShapeTable shapes, ContactBuffers c, const uint32_t *__restrict__ ground_masks)
 {
@@ -1453,11 +1510,17 @@ __global__ void __launch_bounds__(kBlock) k_restitution(BodyArrays b, const doub
         const uint32_t sid = b.shape_id[i];
         const double *verts = lds + 3 * lds_off[sid];
         const Frame frame{frame_origin(self.pos, self.rot, self.com), self.rot};
-        const Vec3 n{0.0, 0.0, 1.0};
+        Vec3 n{0.0, 0.0, 1.0};
         const double target_scale = -e_ground;
         for (uint32_t todo = mask; todo != 0; todo &= todo - 1) {
             const uint32_t v = __ffs(todo) - 1;
             const Vec3 p = frame * Vec3{verts[3 * v + 0], verts[3 * v + 1], verts[3 * v + 2]};
+            if (TERRAIN) {
+                Plane plane;
+                if (!terrain_plane(c.terrain, p, plane))
+                    continue;
+                n = plane.normal;
+            }
             const Vec3 arm = p - centre;
             const double vn = dot(n, self.vel + cross(self.ang, arm));
             const double vn0 = dot(n, self.vel0 + cross(self.ang0, arm));
@@ -1805,8 +1868,12 @@ hipError_t launch_integrate_ground(const BodyArrays &b, const ShapeTable &s, dou
         return hipSuccess;
     const size_t lds_bytes = (size_t)s.total_verts * 3 * sizeof(double) + (size_t)(s.n_shapes + 1) * sizeof(uint32_t);
     auto launch = [&](auto trace, auto materials) {
-        hipLaunchKernelGGL((k_integrate_ground<decltype(trace)::value, decltype(materials)::value>), dim3(blocks_for(items)), dim3(kBlock),
-                           lds_bytes, stream, b, s, h, c, subset, last_mask, trace_masks, trace_row);
+        if (c.terrain.planes)
+            hipLaunchKernelGGL((k_integrate_ground<decltype(trace)::value, decltype(materials)::value, true>), dim3(blocks_for(items)),
+                               dim3(kBlock), lds_bytes, stream, b, s, h, c, subset, last_mask, trace_masks, trace_row);
+        else
+            hipLaunchKernelGGL((k_integrate_ground<decltype(trace)::value, decltype(materials)::value>), dim3(blocks_for(items)), dim3(kBlock),
+                               lds_bytes, stream, b, s, h, c, subset, last_mask, trace_masks, trace_row);
     };
     if (trace_masks && c.friction)
         launch(std::true_type{}, std::true_type{});
@@ -1816,6 +1883,21 @@ hipError_t launch_integrate_ground(const BodyArrays &b, const ShapeTable &s, dou
         launch(std::false_type{}, std::true_type{});
     else
         launch(std::false_type{}, std::false_type{});
+    return hipGetLastError();
+}
+
+hipError_t launch_terrain_planes(const double *heights, const Terrain &t, double *planes, hipStream_t stream)
+{
+    const uint32_t cells = (t.nx - 1) * (t.ny - 1);
+    hipLaunchKernelGGL(k_terrain_planes, dim3(blocks_for(cells)), dim3(kBlock), 0, stream, heights, t, planes);
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_terrain(const Terrain &t, const double *xy, uint32_t n, double *height, double *normal_xyz, hipStream_t stream)
+{
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_sample_terrain, dim3(blocks_for(n)), dim3(kBlock), 0, stream, t, xy, n, height, normal_xyz);
     return hipGetLastError();
 }
 
@@ -1866,7 +1948,10 @@ hipError_t launch_restitution(const BodyArrays &b, const double *post, const dou
     if (!c.restitution || post == b.dyn || start == b.dyn)
         return hipErrorInvalidValue; // (the kernel writes b.dyn while other lanes read `post` and `start`)
     const size_t lds_bytes = (size_t)s.total_verts * 3 * sizeof(double) + (size_t)(s.n_shapes + 1) * sizeof(uint32_t);
-    hipLaunchKernelGGL(k_restitution, dim3(blocks_for(b.n)), dim3(kBlock), lds_bytes, stream, b, post, start, s, c, ground_masks);
+    if (c.terrain.planes)
+        hipLaunchKernelGGL(k_restitution<true>, dim3(blocks_for(b.n)), dim3(kBlock), lds_bytes, stream, b, post, start, s, c, ground_masks);
+    else
+        hipLaunchKernelGGL(k_restitution<false>, dim3(blocks_for(b.n)), dim3(kBlock), lds_bytes, stream, b, post, start, s, c, ground_masks);
     return hipGetLastError();
 }
 

@@ -47,6 +47,15 @@ struct ShapeTable {
     uint32_t total_verts;
 };
 
+// Heightfield terrain (include/xpbd.h, "TERRAIN"), device copy: the planes of both triangles of every cell, written once by
+// k_terrain_planes.  planes == NULL: no terrain, the ground is the reference's plane z = 0.
+struct Terrain {
+    const double *planes; // [(ny - 1) * (nx - 1)][8] cell (i, j) at j * (nx - 1) + i: lower triangle {n.x, n.y, n.z, d}, then upper
+    double x0, y0;        // world x, y of sample (0, 0)
+    double dx, dy;        // spacing
+    uint32_t nx, ny;      // samples
+};
+
 // Algorithmic HBM traffic of one unfused substep of one body:
 // read 13 dyn + 25 stat doubles + 4 B shape id, write 13 dyn doubles.
 constexpr uint32_t kBytesPerBodySubstep = (13 + 25) * 8 + 4 + 13 * 8; // 412

@@ -133,6 +133,47 @@ __device__ __forceinline__ uint32_t ground_mask_table(const Frame &cur, const do
     return mask;
 }
 
+// The terrain's plane under world point x (include/xpbd.h, "TERRAIN", Lookup): false when x is outside the field (a NaN is).
+// One division per axis, then one 32-byte load from the cell's 64-byte record: the planes themselves were evaluated once, by
+// k_terrain_planes, with the header's formulas.
+__device__ __forceinline__ bool terrain_plane(const Terrain &t, const Vec3 &x, Plane &plane)
+{
+    const double u = (x.x - t.x0) / t.dx, v = (x.y - t.y0) / t.dy;
+    if (!(u >= 0.0 && v >= 0.0))
+        return false;
+    const double fi = floor(u), fj = floor(v);
+    if (!(fi < (double)(t.nx - 1) && fj < (double)(t.ny - 1))) // half-open at the far edges; only now are fi, fj known to fit
+        return false;
+    const uint32_t i = (uint32_t)fi, j = (uint32_t)fj;
+    const double fu = u - fi, fv = v - fj;
+    const double *p = t.planes + ((size_t)j * (t.nx - 1) + i) * 8 + (fu >= fv ? 0 : 4);
+    plane = Plane{Vec3{p[0], p[1], p[2]}, p[3]};
+    return true;
+}
+
+// Pass 1 on a terrain: vertex v contacts iff it is inside the field and below the plane under it.  (A vertex outside has no
+// ground contact: beyond the terrain there is nothing.)
+__device__ __forceinline__ uint32_t ground_mask_terrain(const Frame &cur, const double *verts, uint32_t n_verts, const Terrain &terrain)
+{
+    uint32_t mask = 0;
+    for (uint32_t v = 0; v < n_verts; ++v) {
+        const Vec3 vertex{verts[3 * v + 0], verts[3 * v + 1], verts[3 * v + 2]};
+        const Vec3 x = cur * vertex;
+        Plane plane;
+        if (terrain_plane(terrain, x, plane) && !(distance(plane, x) >= 0.0))
+            mask |= 1u << v;
+    }
+    return mask;
+}
+
+// The point of the terrain's plane below x: the `target` of a terrain contact.  (x is a vertex of the mask, so it is inside.)
+__device__ __forceinline__ Vec3 terrain_target(const Terrain &terrain, const Vec3 &x)
+{
+    Plane plane{Vec3{0.0, 0.0, 1.0}, 0.0};
+    (void)terrain_plane(terrain, x, plane);
+    return x - distance(plane, x) * plane.normal;
+}
+
 // Pass 2 -- the lane walks the penetrating vertices of `mask` in ascending index order (the reference's push
 // order).  Lane-compacting the contact work this way makes a wave run the expensive body max-over-lanes(contact
 // count) times instead of once per shape vertex with most lanes masked off.  Recomputing x for the chosen vertex
@@ -143,10 +184,13 @@ __device__ __forceinline__ uint32_t ground_mask_table(const Frame &cur, const do
 // MATERIALS (XPBD_MODE_CONTACTS with xpbd_world_set_materials only; the pinned path compiles the plain form, where `mu` is
 // never read and the reference's literal 1.0 stays a literal): Coulomb friction, mu = min(body, ground) -- the constraint
 // takes back at most mu * |correction| of the tangential slip (include/xpbd.h, "Contact MATERIALS").
-template <bool MATERIALS = false>
+// TERRAIN (XPBD_MODE_CONTACTS with xpbd_world_set_terrain only; `mask` is then ground_mask_terrain's and every other form never
+// reads `terrain`): the target is the point of the terrain's plane below the vertex instead of {x.x, x.y, 0.0}; the lookup
+// repeats pass 1's on the same x, so the same plane.  Everything after `target` is the same arithmetic.
+template <bool MATERIALS = false, bool TERRAIN = false>
 __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_mass, const Mat3 &inv_inertia, const Vec3 &com,
                                              const Frame &cur, const Frame &past, double compliance, const double *verts,
-                                             uint32_t mask, double limit = 0.0, double mu = 0.0)
+                                             uint32_t mask, double limit = 0.0, double mu = 0.0, const Terrain &terrain = Terrain{})
 {
     const Frame cur_inv = inverse(cur); // src/frame.rs:30-37, shared by every penetrating vertex
     for (uint32_t todo = mask; todo != 0; todo &= todo - 1) {
@@ -155,7 +199,7 @@ __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_ma
         const Vec3 x = cur * vertex; // src/collision.rs:17
 
         // src/collision.rs:22-29
-        const Vec3 target{x.x, x.y, 0.0};
+        const Vec3 target = TERRAIN ? terrain_target(terrain, x) : Vec3{x.x, x.y, 0.0};
         const Vec3 correction = target - x;
         const Vec3 local = cur_inv * x;      // src/frame.rs:41
         const Vec3 delta = x - past * local; // src/frame.rs:42-43
@@ -199,13 +243,14 @@ __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_ma
 }
 
 // Both passes for the lane's own body.  Returns the contact mask.
-template <bool MATERIALS = false>
+template <bool MATERIALS = false, bool TERRAIN = false>
 __device__ __forceinline__ uint32_t solve_ground(BodyDynamic &d, const BodyStatic &s, const SubstepFrames &f,
                                                  double compliance, const double *verts, uint32_t n_verts, double limit = 0.0,
-                                                 double mu = 0.0)
+                                                 double mu = 0.0, const Terrain &terrain = Terrain{})
 {
-    const uint32_t mask = ground_mask(f.cur, verts, n_verts);
-    solve_masked<MATERIALS>(d.pos, d.rot, s.inv_mass, s.inv_inertia, s.com, f.cur, f.past, compliance, verts, mask, limit, mu);
+    const uint32_t mask = TERRAIN ? ground_mask_terrain(f.cur, verts, n_verts, terrain) : ground_mask(f.cur, verts, n_verts);
+    solve_masked<MATERIALS, TERRAIN>(d.pos, d.rot, s.inv_mass, s.inv_inertia, s.com, f.cur, f.past, compliance, verts, mask, limit, mu,
+                                     terrain);
     return mask;
 }
 

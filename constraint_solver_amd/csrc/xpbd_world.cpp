@@ -174,6 +174,11 @@ struct xpbd_world {
         void clear() { *this = Restitution{}; }
     } restitution;
     DeviceBuffer rs_restitution, rs_start;
+    // xpbd_world_set_terrain: the plane table of the heightfield and its description (planes == NULL: none).  World-level, as the
+    // contact pad: it names no body, so no upload, population change or restore touches it.  With one the step runs the unfused
+    // schedule (the fused pair-solve + integrate + ground kernel has no terrain form).  tr_xy, tr_out: staging of xpbd_world_sample_terrain.
+    xpbd::Terrain terrain{};
+    DeviceBuffer tr_planes, tr_xy, tr_out;
     // scene queries (xpbd_world_raycast*, xpbd_world_overlap*): scratch of one call, staging of the host variants' arrays
     xpbd::SceneQueryScratch query;
     // body edits (xpbd_world_set_external_wrench, _apply_impulses, _set_dynamics, _get_dynamics): the staging of the host
@@ -250,6 +255,7 @@ struct xpbd_world {
         c.restitution = restitution.on ? rs_restitution.as<double>() : nullptr;
         c.ground_restitution = restitution.ground;
         c.bounce_threshold = restitution.bounce_threshold;
+        c.terrain = terrain;
         return c;
     }
 
@@ -616,7 +622,8 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         return rc;
     if (substeps == 0)
         return XPBD_OK;
-    if (w->restitution.on) { // the velocity pass sits where the fused kernel below has the next substep's integrate
+    // the velocity pass sits where the fused kernel below has the next substep's integrate; and that kernel has no terrain form
+    if (w->restitution.on || w->terrain.planes) {
         for (uint32_t k = 0; k < substeps; ++k)
             if (int rc = substep_contacts(w, h, trace, k))
                 return rc;
@@ -2098,6 +2105,76 @@ try {
     w->restitution.on = true;
     w->restitution.ground = ground_restitution;
     w->restitution.bounce_threshold = bounce_threshold;
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_set_terrain(xpbd_world *w, const xpbd_heightfield *hf)
+try {
+    static_assert(sizeof(xpbd_heightfield) == 48, "xpbd_heightfield is {nx, ny, origin[2], cell[2], heights}");
+    const char *who = "xpbd_world_set_terrain";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    size_t samples = 0;
+    if (hf) {
+        if (hf->nx < 2 || hf->ny < 2)
+            return set_error(XPBD_E_INVALID, "%s: %u x %u samples (each must be >= 2)", who, hf->nx, hf->ny);
+        samples = (size_t)hf->nx * hf->ny;
+        if (samples > XPBD_MAX_TERRAIN_SAMPLES)
+            return set_error(XPBD_E_INVALID, "%s: %u x %u samples (at most %u)", who, hf->nx, hf->ny, XPBD_MAX_TERRAIN_SAMPLES);
+        if (!hf->heights)
+            return set_error(XPBD_E_INVALID, "%s: NULL heights", who);
+        for (int a = 0; a < 2; ++a) {
+            if (!std::isfinite(hf->origin[a]))
+                return set_error(XPBD_E_INVALID, "%s: origin[%d] = %g (must be finite)", who, a, hf->origin[a]);
+            if (!(std::isfinite(hf->cell[a]) && hf->cell[a] > 0.0))
+                return set_error(XPBD_E_INVALID, "%s: cell[%d] = %g (must be finite and > 0)", who, a, hf->cell[a]);
+        }
+        for (size_t k = 0; k < samples; ++k)
+            if (!std::isfinite(hf->heights[k]))
+                return set_error(XPBD_E_INVALID, "%s: heights[%zu] = %g (must be finite)", who, k, hf->heights[k]);
+    }
+    if (int rc = bind_device(w))
+        return rc;
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present table
+    if (!hf) {
+        w->terrain = xpbd::Terrain{};
+        w->tr_planes.release();
+        return XPBD_OK;
+    }
+    // heights and the new table in blocks of their own: the present table stays in force until nothing can fail any more
+    xpbd::Terrain t{nullptr, hf->origin[0], hf->origin[1], hf->cell[0], hf->cell[1], hf->nx, hf->ny};
+    DeviceBuffer heights, planes;
+    XPBD_TRY(stage_upload(heights, hf->heights, samples * sizeof(double)));
+    XPBD_HIP_TRY(planes.reserve((size_t)(hf->nx - 1) * (hf->ny - 1) * 8 * sizeof(double)));
+    XPBD_HIP_TRY(xpbd::launch_terrain_planes(heights.as<double>(), t, planes.as<double>(), w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    w->tr_planes = std::move(planes);
+    t.planes = w->tr_planes.as<double>();
+    w->terrain = t;
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_sample_terrain(xpbd_world *w, const double *xy, uint32_t n, double *height, double *normal_xyz)
+try {
+    const char *who = "xpbd_world_sample_terrain";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (!w->terrain.planes)
+        return set_error(XPBD_E_INVALID, "%s: the world has no terrain (xpbd_world_set_terrain)", who);
+    if (n == 0)
+        return XPBD_OK;
+    if (!xy || !height)
+        return set_error(XPBD_E_INVALID, "%s: NULL xy or height", who);
+    if (int rc = bind_device(w))
+        return rc;
+    XPBD_HIP_TRY(xpbd::reserve_after_sync(w->stream, {{w->tr_xy, (size_t)n * 2 * 8}, {w->tr_out, (size_t)n * 4 * 8}}));
+    double *dev_height = w->tr_out.as<double>(), *dev_normal = normal_xyz ? dev_height + n : nullptr;
+    XPBD_HIP_TRY(hipMemcpyAsync(w->tr_xy.ptr, xy, (size_t)n * 2 * 8, hipMemcpyHostToDevice, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_sample_terrain(w->terrain, w->tr_xy.as<double>(), n, dev_height, dev_normal, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(height, dev_height, (size_t)n * 8, hipMemcpyDeviceToHost, w->stream));
+    if (normal_xyz)
+        XPBD_HIP_TRY(hipMemcpyAsync(normal_xyz, dev_normal, (size_t)n * 3 * 8, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
 } XPBD_ABI_CATCH
 

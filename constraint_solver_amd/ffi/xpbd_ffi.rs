@@ -154,6 +154,18 @@ impl Default for XpbdMaterial {
     }
 }
 
+/// EXTENSION: heightfield terrain, the ground of XPBD_MODE_CONTACTS in place of the plane z = 0 (xpbd_world_set_terrain); 48 bytes.
+pub const XPBD_MAX_TERRAIN_SAMPLES: u32 = 1 << 22;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct XpbdHeightfield {
+    pub nx: u32,               // samples along x and y, each >= 2, nx * ny <= XPBD_MAX_TERRAIN_SAMPLES
+    pub ny: u32,
+    pub origin: [f64; 2],      // world x, y of sample (0, 0)
+    pub cell: [f64; 2],        // spacing along x and y: finite, > 0
+    pub heights: *const f64,   // ny rows of nx: heights[iy * nx + ix], all finite; copied
+}
+
 /// EXTENSION: body edits -- one impulse on a resident body (xpbd_world_apply_impulses); 80 bytes.
 pub const XPBD_IMPULSE_AT_POINT: u32 = 0; // the impulse acts at `point` (world space)
 pub const XPBD_IMPULSE_AT_CENTRE: u32 = 1; // ... at position + center_of_mass; `point` is ignored
@@ -440,6 +452,9 @@ extern "C" {
         -> c_int;
     pub fn xpbd_world_set_restitution(w: *mut XpbdWorld, restitution: *const f64, n: u32, ground_restitution: f64, bounce_threshold: f64)
         -> c_int;
+    // terrain: hf NULL = back to the plane z = 0; sample_terrain takes host arrays and waits (normal_xyz may be NULL)
+    pub fn xpbd_world_set_terrain(w: *mut XpbdWorld, hf: *const XpbdHeightfield) -> c_int;
+    pub fn xpbd_world_sample_terrain(w: *mut XpbdWorld, xy: *const f64, n: u32, height: *mut f64, normal_xyz: *mut f64) -> c_int;
     // body edits: forces, impulses and state of resident bodies (host arrays wait; `_device`: device arrays, stream-ordered)
     pub fn xpbd_world_set_external_wrench(w: *mut XpbdWorld, indices: *const u32, n: u32, force_xyz: *const f64, torque_xyz: *const f64)
         -> c_int;

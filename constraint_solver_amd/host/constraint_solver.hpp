@@ -557,6 +557,26 @@ class BatchWorld {
         check(xpbd_world_set_restitution(w_, restitution.empty() ? nullptr : restitution.data(), (uint32_t)restitution.size(), ground_restitution,
                                          bounce_threshold));
     }
+    // heightfield terrain (include/xpbd.h, "TERRAIN"): ny rows of nx heights, heights[iy * nx + ix] at (origin_x + ix * cell_x,
+    // origin_y + iy * cell_y), the ground of XPBD_MODE_CONTACTS in place of the plane z = 0.  World-level: upload keeps it.
+    void set_terrain(const std::vector<double> &heights, uint32_t nx, uint32_t ny, double origin_x, double origin_y, double cell_x, double cell_y)
+    {
+        if (heights.size() != (size_t)nx * ny)
+            throw Error(XPBD_E_INVALID, "set_terrain: heights must hold nx * ny samples");
+        const xpbd_heightfield hf{nx, ny, {origin_x, origin_y}, {cell_x, cell_y}, heights.data()};
+        check(xpbd_world_set_terrain(w_, &hf));
+    }
+    void clear_terrain() { check(xpbd_world_set_terrain(w_, nullptr)); }
+    // height of the terrain under the points xy[2k], xy[2k + 1] (NaN outside the field) and, with `normals`, its unit normals
+    std::vector<double> sample_terrain(const std::vector<double> &xy, std::vector<double> *normals = nullptr)
+    {
+        const uint32_t n = (uint32_t)(xy.size() / 2);
+        std::vector<double> height(n);
+        if (normals)
+            normals->resize((size_t)3 * n);
+        check(xpbd_world_sample_terrain(w_, xy.data(), n, height.data(), normals ? normals->data() : nullptr));
+        return height;
+    }
 
     // contact reports (include/xpbd.h, "Contact REPORTS"): the touching pairs of the current frame and the begin / end events
     void set_contact_report(bool enable) { check(xpbd_world_set_contact_report(w_, enable ? 1u : 0u)); }

@@ -4,7 +4,10 @@
 //
 //   xpbd_headless --bodies 262144 --substeps 20 --frames 10 [--scene boxes|mixed|boxes-drop|mixed-drop|stacks]
 //                 [--seed 1] [--mode fused|substep|contacts] [--device 0] [--dump poses.bin]
-//                 [--history] [--rewind K] [--shards N] [--friction MU] [--restitution E]
+//                 [--history] [--rewind K] [--shards N] [--friction MU] [--restitution E] [--terrain waves:AMPLITUDE:WAVELENGTH]
+// --terrain waves:A:L (with --mode contacts, not with --shards): a heightfield A sin(2 pi x / L) sin(2 pi y / L) under the scene
+// (eight samples per wavelength, a margin of two wavelengths around the bodies) in place of the plane z = 0; every body is
+// lifted by the terrain's height under its centre plus A before the upload.
 // --friction MU, --restitution E (with --mode contacts, not with --shards): one Coulomb friction coefficient (>= 0) / one
 // restitution coefficient (in [0, 1]) for every body and the ground.
 // --shards N (with --mode contacts): the world sharded over N GPUs driven by this one process (world::ShardedWorld over
@@ -12,7 +15,9 @@
 // exchange by peer copies -- the one-GPU rehearsal).  The dump then equals the unsharded run's, byte for byte.
 // --history keeps every frame on the device like the reference app's `states` vector (src/app.rs:48) and steps through
 // world::Timeline; --rewind K then scrubs back to state K (0 = the initial world) before the dump.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,6 +32,7 @@ int main(int argc, char **argv)
     uint32_t bodies = 4096, substeps = 20, frames = 10, warmup = 2, shards = 0;
     bool history = false;
     double friction = -1.0, restitution = -1.0; // < 0: not given
+    double wave_amplitude = 0.0, wave_length = 0.0; // --terrain waves:A:L (wave_length > 0: given)
     long rewind = -1;
     uint64_t seed = 1;
     int device = 0;
@@ -70,14 +76,23 @@ int main(int argc, char **argv)
                 return 2;
             }
         }
+        else if (const char *v = val("--terrain")) {
+            const std::string text(v);
+            const size_t colon = text.find(':', 6);
+            if (text.compare(0, 6, "waves:") != 0 || colon == std::string::npos || !number(text.substr(6, colon - 6).c_str(), wave_amplitude) ||
+                !number(text.c_str() + colon + 1, wave_length) || !std::isfinite(wave_amplitude) || !(wave_length > 0.0) || !std::isfinite(wave_length)) {
+                std::fprintf(stderr, "--terrain %s: must be waves:AMPLITUDE:WAVELENGTH with a finite amplitude and a wavelength > 0\n", v);
+                return 2;
+            }
+        }
         else if (std::strcmp(argv[i], "--history") == 0) history = true;
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
             return 2;
         }
     }
-    if ((friction >= 0.0 || restitution >= 0.0) && (mode != XPBD_MODE_CONTACTS || shards)) {
-        std::fprintf(stderr, "--friction and --restitution need --mode contacts and no --shards\n");
+    if ((friction >= 0.0 || restitution >= 0.0 || wave_length > 0.0) && (mode != XPBD_MODE_CONTACTS || shards)) {
+        std::fprintf(stderr, "--friction, --restitution and --terrain need --mode contacts and no --shards\n");
         return 2;
     }
     try {
@@ -130,6 +145,39 @@ int main(int argc, char **argv)
             w.set_polytopes(scene::shapes_of(kind)); // extension: body-body contacts
         else
             w.set_shapes(scene::shapes_of(kind));
+        if (wave_length > 0.0 && !state.empty()) {
+            // the field: the bodies' footprint and two wavelengths around it, eight samples per wavelength (coarser when that
+            // would exceed the cap)
+            double lo[2] = {state[0].position.x, state[0].position.y}, hi[2] = {lo[0], lo[1]};
+            for (const rigid::Rigid &r : state) {
+                lo[0] = std::min(lo[0], r.position.x), hi[0] = std::max(hi[0], r.position.x);
+                lo[1] = std::min(lo[1], r.position.y), hi[1] = std::max(hi[1], r.position.y);
+            }
+            const double margin = 2.0 * wave_length + 2.0;
+            double cell = wave_length / 8.0;
+            uint32_t samples[2];
+            for (;; cell *= 2.0) {
+                const double nx = std::ceil((hi[0] - lo[0] + 2.0 * margin) / cell) + 1.0, ny = std::ceil((hi[1] - lo[1] + 2.0 * margin) / cell) + 1.0;
+                if (nx * ny <= (double)XPBD_MAX_TERRAIN_SAMPLES) {
+                    samples[0] = (uint32_t)nx, samples[1] = (uint32_t)ny;
+                    break;
+                }
+            }
+            const double origin[2] = {lo[0] - margin, lo[1] - margin}, k = 2.0 * 3.14159265358979323846 / wave_length;
+            std::vector<double> heights((size_t)samples[0] * samples[1]);
+            for (uint32_t iy = 0; iy < samples[1]; ++iy)
+                for (uint32_t ix = 0; ix < samples[0]; ++ix)
+                    heights[(size_t)iy * samples[0] + ix] = wave_amplitude * std::sin(k * (origin[0] + ix * cell)) * std::sin(k * (origin[1] + iy * cell));
+            w.set_terrain(heights, samples[0], samples[1], origin[0], origin[1], cell, cell);
+            std::vector<double> centres(2 * state.size());
+            for (size_t b = 0; b < state.size(); ++b) {
+                centres[2 * b + 0] = state[b].position.x + state[b].center_of_mass.x;
+                centres[2 * b + 1] = state[b].position.y + state[b].center_of_mass.y;
+            }
+            const std::vector<double> ground = w.sample_terrain(centres);
+            for (size_t b = 0; b < state.size(); ++b)
+                state[b].position.z += ground[b] + std::fabs(wave_amplitude);
+        }
         w.upload(state, shape_id);
         if (friction >= 0.0)
             w.set_materials(std::vector<xpbd_material>(state.size(), xpbd_material{friction, 0.0}), friction);

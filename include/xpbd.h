@@ -510,6 +510,61 @@ int  xpbd_world_set_materials(xpbd_world *w, const xpbd_material *materials, uin
 int  xpbd_world_set_restitution(xpbd_world *w, const double *restitution, uint32_t n, double ground_restitution,
                                 double bounce_threshold);
 
+/* TERRAIN (EXTENSION): a heightfield as the ground of the contact pipeline, in place of the reference's plane z = 0.
+ * A grid of nx * ny heights over the world's x, y plane; every cell is split along its (0,0)-(1,1) diagonal into two triangles,
+ * and the ground under a point is the PLANE of the triangle above or below it.  Ground contacts stay vertex against plane, at
+ * most one per shape vertex, so the contact mask, xpbd_world_download_contacts, XPBD_FLAG_TRACE_CONTACTS, the history and the
+ * frame snapshot keep their shape; only the plane under each vertex changes.
+ * Lookup, the one definition every user of the terrain shares (dot, length and reciprocal-then-multiply as everywhere else,
+ * correctly rounded / and sqrt, nothing contracted).  For a world point x, with x0, y0 = origin and dx, dy = cell:
+ *   1. u = (x.x - x0) / dx, v = (x.y - y0) / dy.  Unless u >= 0 && v >= 0 the point is OUTSIDE (so a NaN is outside).
+ *   2. fi = floor(u), fj = floor(v), as doubles.  Unless fi < nx - 1 && fj < ny - 1 the point is outside: the field is
+ *      half-open at its far edges.  Only then i = fi, j = fj as integers.
+ *   3. fu = u - fi, fv = v - fj; h00 = H[j][i], h10 = H[j][i+1], h01 = H[j+1][i], h11 = H[j+1][i+1]  (H[j][i] = heights[j * nx + i]).
+ *   4. fu >= fv, the lower triangle h00, h10, h11:  sx = (h10 - h00) / dx, sy = (h11 - h10) / dy;
+ *      otherwise the upper triangle h00, h11, h01:  sx = (h11 - h01) / dx, sy = (h01 - h00) / dy.
+ *   5. raw = (-sx, -sy, 1.0), n = raw * (1.0 / length(raw)).
+ *   6. d = dot(n, (x0 + fi * dx, y0 + fj * dy, h00)).  The plane is {n, d}; s = dot(n, x) - d is the signed distance of x
+ *      (src/geometry.rs:39-41).
+ * (The device keeps n and d of both triangles of every cell, evaluated once by the setter with exactly these operations: 64
+ * bytes per cell, at most 256 MiB.  The heights themselves are not kept.)
+ * Ground contacts (XPBD_MODE_CONTACTS only), collision::ground with a terrain: vertex v with x = frame * vertex contacts iff
+ * x is inside the field and !(s >= 0.0); its target = x - s * n per component, where the reference has {x.x, x.y, 0.0}.
+ * Everything after `target` is unchanged, operation by operation: correction, delta, delta_tangential, the friction factor,
+ * c1, the depenetration limit, W, lagrange, the impulse.  A vertex outside the field has NO ground contact: the terrain
+ * replaces the plane, and beyond it there is nothing.  A field with every height 0 therefore steps bodies that stay over it
+ * bit for bit as the plane does.
+ * Vertex against plane misses a terrain ridge that pokes into a body's FACE between its vertices; the reference's ground
+ * misses nothing only because a plane is flat.  Choose cells no smaller than the bodies that are to lie on them.
+ * Restitution's ground part with a terrain: for every set bit of the mask in vertex order p is formed as before, the lookup
+ * is repeated at p (outside the field: the vertex makes no entry) and n is the plane's normal in place of (0, 0, 1); the rest
+ * is unchanged.
+ * xpbd_world_sample_terrain takes HOST arrays and waits; it is evaluated on the device from the table the stepper reads.
+ * For point k = (x, y) = xy[2k], xy[2k+1], the lookup at (x, y, 0): inside the field height[k] = (d - (n.x * x + n.y * y)) / n.z
+ * and normal_xyz[3k..3k+2] = n; outside (NaN included) height[k] = NaN and the normal is (0, 0, 0).  normal_xyz may be NULL.
+ * Hosts place bodies on the ground with it.  XPBD_E_INVALID without a terrain, or with NULL xy / height and n > 0.
+ * Lifetime: world-level, as the contact pad: the terrain survives xpbd_world_upload_bodies, population changes, history
+ * restore, the joint and material setters and mode changes.  XPBD_MODE_FUSED and XPBD_MODE_PER_SUBSTEP (the pinned reference
+ * path) accept the call and ignore the terrain, as they ignore materials.  hf == NULL: back to the plane z = 0.  The heights
+ * are copied.  The call waits for queued substeps.  With a terrain xpbd_world_step runs the substeps one kernel sequence each
+ * (as with restitution on) instead of fusing the end of one with the start of the next; a world without one runs the same
+ * kernels in the same order as before.
+ * XPBD_E_INVALID, the previous terrain staying in force: a NULL world, nx or ny below 2, more than XPBD_MAX_TERRAIN_SAMPLES
+ * samples, NULL heights, a non-finite height, origin or cell, a cell <= 0.  After XPBD_E_OOM / XPBD_E_HIP the previous
+ * terrain still holds too: the new table is built in a block of its own and moved in last.
+ * Not here: xpbd_multi_world_* has no such call (its frame runs the fused pair-solve + integrate + ground kernel at the halo
+ * seam, which has no terrain form); rays, overlaps and sweeps do not see the terrain (it is not a body, as the plane is
+ * not); the contact report lists body pairs only. */
+#define XPBD_MAX_TERRAIN_SAMPLES (1u << 22)
+typedef struct xpbd_heightfield {   /* 48 bytes */
+    uint32_t nx, ny;          /* samples along x and y, each >= 2, nx * ny <= XPBD_MAX_TERRAIN_SAMPLES */
+    double   origin[2];       /* world x, y of sample (0, 0) */
+    double   cell[2];         /* spacing along x and y: finite, > 0 */
+    const double *heights;    /* ny rows of nx: heights[iy * nx + ix], all finite; copied */
+} xpbd_heightfield;
+int  xpbd_world_set_terrain(xpbd_world *w, const xpbd_heightfield *hf);   /* NULL: back to the plane z = 0 */
+int  xpbd_world_sample_terrain(xpbd_world *w, const double *xy, uint32_t n, double *height, double *normal_xyz);
+
 /* Split form of xpbd_world_step(w, dt, n) in XPBD_MODE_CONTACTS, for hosts that exchange halo
  * bodies between substeps (multi-GPU):  begin(dt); n x { substep(dt / n); <exchange> }.
  * begin runs the broadphase for the coming frame; substep is one substep of the pipeline. */
