@@ -158,6 +158,9 @@ RAY_HIT_DTYPE = np.dtype([("body", "<u4"), ("face", "<u4"), ("distance", "<f8"),
 NO_HIT = RAY_INSIDE = 0xFFFFFFFF
 RAYCAST_BRUTE_FORCE = 1
 RAYCAST_BRUTE_FORCE_RAYS = 8      # calls with at most this many rays take the brute-force path anyway
+# Terrain in the scene queries (EXTENSION): a flag of raycast, overlap and sweep alike (World only; MultiWorld has no terrain)
+QUERY_TERRAIN = 0x100             # the heightfield of World.set_terrain answers too
+HIT_TERRAIN = 0xFFFFFFFE          # .body of a hit on the terrain; .face is then the triangle 2 * (j * (nx - 1) + i) + k
 
 
 def rays(origins, directions, max_distance=np.inf, ignore=None):
@@ -679,7 +682,9 @@ class World:
 
     def raycast(self, rays, flags=0, mask=None):
         """RAY_HIT_DTYPE records of the closest body along every ray (RAY_DTYPE records, see rays()) at the current poses.
-        mask: only bodies whose collision-filter group meets it can be hit (None: every body)."""
+        mask: only bodies whose collision-filter group meets it can be hit (None: every body).
+        flags | QUERY_TERRAIN: the terrain stops rays too (body = HIT_TERRAIN, face = the triangle, or RAY_INSIDE from in or
+        under the ground); it needs set_terrain, and neither mask nor ignore_body concerns it."""
         r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
         out = np.zeros(r.size, dtype=RAY_HIT_DTYPE)
         rp, hp = r.ctypes.data if r.size else None, out.ctypes.data if r.size else None
@@ -698,7 +703,9 @@ class World:
 
     def overlap(self, queries, flags=0):
         """(offsets, hits) of the bodies every convex volume touches (OVERLAP_QUERY_DTYPE records, see overlap_queries()) at the
-        current poses: the hits of query q are hits[offsets[q]:offsets[q + 1]] (OVERLAP_HIT_DTYPE), in ascending body index."""
+        current poses: the hits of query q are hits[offsets[q]:offsets[q + 1]] (OVERLAP_HIT_DTYPE), in ascending body index.
+        flags | QUERY_TERRAIN: a volume with a vertex under the ground (the stepper's ground contact) gets one more entry, the
+        last of its segment: {HIT_TERRAIN, FEATURE_FACE_B, the deepest vertex's signed distance}."""
         return _overlap(hip_lib().xpbd_world_overlap, self._h, queries, flags)
 
     def overlap_device(self, queries_ptr, n, offsets_ptr, hits_ptr, cap, flags=0):
@@ -709,7 +716,9 @@ class World:
 
     def sweep(self, sweeps, flags=0):
         """SWEEP_HIT_DTYPE records of the first body every convex volume hits when moved along its segment (SWEEP_DTYPE records,
-        see sweeps()) at the current poses."""
+        see sweeps()) at the current poses.
+        flags | QUERY_TERRAIN: the volume also stops where its first vertex goes under the ground (body = HIT_TERRAIN, feature =
+        FEATURE_FACE_B, face = the triangle; SWEEP_INITIAL when a vertex starts there), if that is strictly earlier."""
         return _sweep(hip_lib().xpbd_world_sweep, self._h, sweeps, flags)
 
     def sweep_device(self, sweeps_ptr, n, hits_ptr, flags=0):

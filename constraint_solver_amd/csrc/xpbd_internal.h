@@ -151,11 +151,14 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
 // The argument checks of the scene queries, shared by the single and the multi-GPU world (XPBD_E_INVALID with a message naming
 // `who`; the caller has dealt with a NULL world).  In order: NULL arrays, unknown flags, no polytopes (`setter`: the call that
 // sets them), with `host` the records' own fields (reserved, shape: the arrays are host memory) and, for an overlap, a target
-// without bodies.  A ray cast does not mind one: every ray misses.
+// without bodies.  A ray cast does not mind one: every ray misses.  XPBD_QUERY_TERRAIN is a known flag only where
+// `terrain_allowed` (the single world; the multi-GPU world has no terrain), and then needs `has_terrain`: without one the call
+// is refused right after the flags, naming xpbd_world_set_terrain, as xpbd_world_sample_terrain is.
 struct QueryTarget {
     bool has_topology;
     uint32_t n_bodies, n_shapes;
     const char *setter;
+    bool terrain_allowed = false, has_terrain = false;
 };
 int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host);
 // n_out: what a host variant reports its total through (NULL passes for a device variant, which has none).

@@ -67,8 +67,11 @@ struct RayFilter {
 // Casts n_rays rays (device xpbd_ray) against the bodies of `b` and writes n_rays xpbd_ray_hit.  global_id (device, n entries,
 // or null): the index a body is known by -- the tie-break and what ignore_body and hit.body mean -- and XPBD_NO_HIT for a
 // body that must not answer; null: the body's slot.  A body the filter drops answers no ray, as a ghost does.
+// terrain (null: no terrain pass): after the body pass, on the same stream, launch_terrain_rays puts the terrain's answer next to
+// the bodies' (XPBD_QUERY_TERRAIN); terrain_brute: every ray against every triangle instead of the walk.
 hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const RayFilter &filter, const void *rays,
-                          uint32_t n_rays, bool brute, const QueryScratch &s, void *hits, hipStream_t stream);
+                          uint32_t n_rays, bool brute, const QueryScratch &s, void *hits, hipStream_t stream, const Terrain *terrain = nullptr,
+                          bool terrain_brute = false);
 
 // ---- overlap queries: which bodies does each convex volume touch? (include/xpbd.h, "Overlap queries") ---------------------
 // Passes: the bounding spheres of the bodies (k_query_bodies) and of the queries (k_overlap_queries); on the grid path the grid
@@ -89,7 +92,7 @@ QuerySizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute);
 // queries' masks when `masked`.
 hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *queries,
                           uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, uint32_t *offsets, void *hits, uint32_t cap,
-                          hipStream_t stream);
+                          hipStream_t stream, const Terrain *terrain = nullptr);
 
 // ---- sweep queries: the first body a translating convex volume hits (include/xpbd.h, "Sweep queries") ----------------------
 // Passes: the bounding spheres of the bodies (k_query_bodies) and of the volumes at t = 0 (k_sweep_queries, the records of an
@@ -98,6 +101,25 @@ hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const ui
 // the minimum under (t, index).  The brute-force path visits every body instead.  A sweep's scratch is an overlap's
 // (overlap_scratch_bytes with the number of sweeps).
 hipError_t launch_sweep(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *sweeps,
-                        uint32_t n_sweeps, bool masked, bool brute, const QueryScratch &s, void *hits, hipStream_t stream);
+                        uint32_t n_sweeps, bool masked, bool brute, const QueryScratch &s, void *hits, hipStream_t stream,
+                        const Terrain *terrain = nullptr, bool terrain_brute = false);
+
+// ---- the terrain in the scene queries (include/xpbd.h, "Terrain in the scene queries"; xpbd_terrain_query.hip) ---------------
+// Each is one kernel on `stream`, called by the three launchers above when they are given a terrain, and reads the plane table of
+// k_terrain_planes alone.
+//  * rays: after the body pass.  One lane per ray reads hits[r], walks the cells under the ray's xy-projection (a 2D DDA whose
+//    border times come from the slab expression of each border; `brute`: every triangle instead) no further than that distance,
+//    and overwrites the record only if the terrain wins under (t, body).
+//  * sweeps: after k_sweep_pass.  32 lanes per sweep, one per vertex of the volume, each casting its vertex as a ray no further
+//    than hits[q].distance; the minimum under (t, triangle, vertex) replaces the record only if it is strictly earlier.
+//    qrec: k_sweep_queries' records (radius < 0: the sweep hits nothing).
+//  * overlaps: one lane per query looks every vertex up as the stepper does.  fill == false, between the count pass and the
+//    scan: offsets[q] += 1 for a volume with a vertex under the ground; fill == true, after the fill pass and before the sort:
+//    its entry at offsets[q + 1] - 1 when that slot is below cap.  qrec: k_overlap_queries' records.
+hipError_t launch_terrain_rays(const Terrain &terrain, const void *rays, uint32_t n_rays, bool brute, void *hits, hipStream_t stream);
+hipError_t launch_terrain_sweeps(const Terrain &terrain, const PolytopeTables &t, const void *sweeps, uint32_t n_sweeps, bool brute, const double *qrec,
+                                 void *hits, hipStream_t stream);
+hipError_t launch_terrain_overlap(const Terrain &terrain, const PolytopeTables &t, const void *queries, uint32_t n_queries, bool fill, const double *qrec,
+                                  uint32_t *offsets, void *hits, uint32_t cap, hipStream_t stream);
 
 } // namespace xpbd

@@ -1385,8 +1385,10 @@ void with_group_shape(const PolytopeTables &t, uint32_t n_queries, Launch &&laun
 } // namespace
 
 hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const RayFilter &filter, const void *rays_v, uint32_t n_rays,
-                          bool brute, const QueryScratch &s, void *hits_v, hipStream_t stream)
+                          bool brute, const QueryScratch &s, void *hits_v, hipStream_t stream, const Terrain *terrain, bool terrain_brute)
 {
+    // the terrain's pass, after the bodies' whichever path that took (null: none, and nothing but the launches below)
+    auto finish = [&](hipError_t e) { return e != hipSuccess || !terrain ? e : launch_terrain_rays(*terrain, rays_v, n_rays, terrain_brute, hits_v, stream); };
     if (n_rays == 0)
         return hipSuccess;
     const xpbd_ray *rays = static_cast<const xpbd_ray *>(rays_v);
@@ -1399,13 +1401,13 @@ hipError_t launch_raycast(const BodyArrays &b, const PolytopeTables &t, const ui
         hipLaunchKernelGGL(k_query_brute, dim3(tiles, chunks), dim3(kBlock), 0, stream, rays, n_rays, b.n, chunk_len, s.rec, b.shape_id,
                            global_id, t, partial);
         hipLaunchKernelGGL(k_query_brute_finish, dim3(n_rays), dim3(64), 0, stream, rays, chunks, partial, s.rec, b.shape_id, t, hits);
-        return hipGetLastError();
+        return finish(hipGetLastError());
     }
     if (hipError_t e = launch_query_grid(b, s, stream))
         return e;
     hipLaunchKernelGGL(k_query_walk, dim3(blocks_of(n_rays)), dim3(kBlock), 0, stream, rays, n_rays, b.n, s.rec, b.shape_id, global_id, t,
                        static_cast<QueryGrid *>(s.grid), s.cell_start, s.items, hits);
-    return hipGetLastError();
+    return finish(hipGetLastError());
 }
 
 QuerySizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute)
@@ -1420,7 +1422,7 @@ QuerySizes overlap_scratch_bytes(uint32_t n, uint32_t n_queries, bool brute)
 
 hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *queries_v,
                           uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, uint32_t *offsets, void *hits_v, uint32_t cap,
-                          hipStream_t stream)
+                          hipStream_t stream, const Terrain *terrain)
 {
     if (n_queries == 0)
         return hipMemsetAsync(offsets, 0, sizeof(uint32_t), stream);
@@ -1439,10 +1441,15 @@ hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const ui
         });
     };
     pass(std::false_type{});
+    if (terrain && (e = launch_terrain_overlap(*terrain, t, queries_v, n_queries, false, s.qrec, offsets, hits_v, cap, stream)) != hipSuccess)
+        return e;
     if ((e = launch_exclusive_scan(offsets, n_queries, s.scan_scratch, stream)) != hipSuccess)
         return e;
     if (cap) {
         pass(std::true_type{});
+        // (before the sort, which takes whole segments: the terrain's index is the largest, so its entry stays the last)
+        if (terrain && (e = launch_terrain_overlap(*terrain, t, queries_v, n_queries, true, s.qrec, offsets, hits_v, cap, stream)) != hipSuccess)
+            return e;
         if (!brute)
             hipLaunchKernelGGL(k_overlap_sort, dim3(n_queries), dim3(kBlock), 0, stream, offsets, static_cast<xpbd_overlap_hit *>(hits_v), cap);
     }
@@ -1450,7 +1457,8 @@ hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const ui
 }
 
 hipError_t launch_sweep(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *sweeps_v,
-                        uint32_t n_sweeps, bool masked, bool brute, const QueryScratch &s, void *hits_v, hipStream_t stream)
+                        uint32_t n_sweeps, bool masked, bool brute, const QueryScratch &s, void *hits_v, hipStream_t stream, const Terrain *terrain,
+                        bool terrain_brute)
 {
     if (n_sweeps == 0)
         return hipSuccess;
@@ -1465,7 +1473,8 @@ hipError_t launch_sweep(const BodyArrays &b, const PolytopeTables &t, const uint
     with_group_shape(t, n_sweeps, [&](auto l, auto v, dim3 blocks) {
         hipLaunchKernelGGL((k_sweep_pass<decltype(l)::value, decltype(v)::value>), blocks, dim3(64), 0, stream, b, t, a);
     });
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess || !terrain ? e : launch_terrain_sweeps(*terrain, t, sweeps_v, n_sweeps, terrain_brute, s.qrec, hits_v, stream);
 }
 
 } // namespace xpbd

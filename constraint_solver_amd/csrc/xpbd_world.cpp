@@ -816,6 +816,7 @@ void reset_stat_records(xpbd_world *w, bool start_over, uint32_t n)
     }
 }
 
+constexpr uint32_t kMaxBodies = 0xFFFFFF00u; // the largest count whose stride fits 32 bits
 uint32_t stride_for(uint32_t n_bodies) { return round_up(n_bodies ? n_bodies : 1, 256); }
 
 // The body arrays hold n_new bodies from now on (the caller made room: stride_for(n_new)): what was derived from the old
@@ -852,6 +853,10 @@ void drop_body_settings(xpbd_world *w)
 // arrays itself and calls take_body_count alone.)
 int adopt_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id)
 {
+    // (the stride rounds the count up to a multiple of 256; and no body index can then be XPBD_HIT_TERRAIN or XPBD_NO_HIT)
+    static_assert(kMaxBodies - 1u < XPBD_HIT_TERRAIN && XPBD_HIT_TERRAIN < XPBD_NO_HIT, "the scene queries' reserved body indices are no body's");
+    if (n_new > kMaxBodies)
+        return set_error(XPBD_E_INVALID, "a world holds at most %u bodies, not %u", kMaxBodies, n_new);
     const uint32_t stride = stride_for(n_new);
     XPBD_HIP_TRY(w->dyn.reserve((size_t)xpbd::kDynFields * stride * 8));
     drop_body_settings(w);
@@ -1234,12 +1239,22 @@ int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32
     return XPBD_OK;
 }
 
+// The flags' part of the three checks: `known` are the family's own bits.
+int check_query_flags(const char *who, const QueryTarget &t, uint32_t flags, uint32_t known)
+{
+    if (flags & ~(known | (t.terrain_allowed ? XPBD_QUERY_TERRAIN : 0u)))
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if ((flags & XPBD_QUERY_TERRAIN) && !t.has_terrain)
+        return set_error(XPBD_E_INVALID, "%s: XPBD_QUERY_TERRAIN but the world has no terrain (xpbd_world_set_terrain)", who);
+    return XPBD_OK;
+}
+
 int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host)
 {
     if (n_rays && (!rays || !hits))
         return set_error(XPBD_E_INVALID, "%s: NULL rays or hits", who);
-    if (flags & ~XPBD_RAYCAST_BRUTE_FORCE)
-        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (int rc = check_query_flags(who, t, flags, XPBD_RAYCAST_BRUTE_FORCE))
+        return rc;
     if (!t.has_topology)
         return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
     for (uint32_t r = 0; host && r < n_rays; ++r)
@@ -1247,6 +1262,9 @@ int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, u
             return set_error(XPBD_E_INVALID, "%s: ray %u has reserved = %u (must be 0)", who, r, rays[r].reserved);
     return XPBD_OK;
 }
+
+// The terrain a query with these flags asks about (null: none; the checks have refused the flag on a world without one).
+const Terrain *query_terrain(const xpbd_world *w, uint32_t flags) { return (flags & XPBD_QUERY_TERRAIN) && w->terrain.planes ? &w->terrain : nullptr; }
 
 // The filter table a masked query reads (null: unmasked, or no filters set -- every body is then in group ~0u).
 const uint2 *masked_filter(const xpbd_world *w, bool masked) { return masked && w->filters.on ? w->ft_filters.as<uint2>() : nullptr; }
@@ -1285,7 +1303,7 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
     XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
     const RayFilter filter{masked_filter(w, masked), mask, masked ? 1u : 0u};
     XPBD_HIP_TRY(launch_raycast(w->arrays(), w->tables(), dev_global_id, filter, dev_rays, n_rays, brute, w->query.view(q.table_size), dev_hits,
-                                w->stream));
+                                w->stream, query_terrain(w, flags), (flags & XPBD_RAYCAST_BRUTE_FORCE) != 0));
     return XPBD_OK;
 }
 
@@ -1304,8 +1322,8 @@ int check_overlap(const char *who, const QueryTarget &t, const xpbd_overlap_quer
         return set_error(XPBD_E_INVALID, "%s: NULL queries, offsets or n_out", who);
     if (cap && !hits)
         return set_error(XPBD_E_INVALID, "%s: NULL hits with cap = %u", who, cap);
-    if (flags & ~(XPBD_OVERLAP_BRUTE_FORCE | XPBD_OVERLAP_MASKED))
-        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (int rc = check_query_flags(who, t, flags, XPBD_OVERLAP_BRUTE_FORCE | XPBD_OVERLAP_MASKED))
+        return rc;
     if (!t.has_topology)
         return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
     for (uint32_t q = 0; host && q < n_queries; ++q) {
@@ -1335,7 +1353,7 @@ int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32
     XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
     const bool masked = (flags & XPBD_OVERLAP_MASKED) != 0;
     XPBD_HIP_TRY(launch_overlap(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute,
-                                w->query.view(q.table_size), dev_offsets, dev_hits, cap, w->stream));
+                                w->query.view(q.table_size), dev_offsets, dev_hits, cap, w->stream, query_terrain(w, flags)));
     return XPBD_OK;
 }
 
@@ -1371,8 +1389,8 @@ int check_sweep(const char *who, const QueryTarget &t, const xpbd_sweep *sweeps,
 {
     if (n_sweeps && (!sweeps || !hits))
         return set_error(XPBD_E_INVALID, "%s: NULL sweeps or hits", who);
-    if (flags & ~(XPBD_SWEEP_BRUTE_FORCE | XPBD_SWEEP_MASKED))
-        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (int rc = check_query_flags(who, t, flags, XPBD_SWEEP_BRUTE_FORCE | XPBD_SWEEP_MASKED))
+        return rc;
     if (!t.has_topology)
         return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
     for (uint32_t q = 0; host && q < n_sweeps; ++q)
@@ -1397,7 +1415,7 @@ int sweep_enqueue(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps
     XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
     const bool masked = (flags & XPBD_SWEEP_MASKED) != 0;
     XPBD_HIP_TRY(launch_sweep(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_sweeps, n_sweeps, masked, brute,
-                              w->query.view(q.table_size), dev_hits, w->stream));
+                              w->query.view(q.table_size), dev_hits, w->stream, query_terrain(w, flags), (flags & XPBD_SWEEP_BRUTE_FORCE) != 0));
     return XPBD_OK;
 }
 
@@ -2672,6 +2690,9 @@ struct PopulationStage {
 int stage_bodies(xpbd_world *w, const uint32_t *dev_src, uint32_t n_keep, const xpbd_rigid *aos, const uint32_t *shape_id, uint32_t n_add,
                  PopulationStage &st)
 {
+    // (adopt_body_count's bound, before the sum can wrap: this is the other way a world comes by its body count)
+    if (n_keep > kMaxBodies || n_add > kMaxBodies - n_keep)
+        return set_error(XPBD_E_INVALID, "a world holds at most %u bodies, not %u + %u", kMaxBodies, n_keep, n_add);
     const uint32_t n_new = n_keep + n_add, stride = stride_for(n_new);
     st.n = n_new;
     st.stride = stride;
@@ -2878,7 +2899,7 @@ namespace {
 // The scene queries' argument checks (xpbd::check_raycast, xpbd::check_overlap, xpbd::check_sweep) against one world.
 xpbd::QueryTarget query_target(const xpbd_world *w)
 {
-    return {w->has_topology, w->n, w->n_shapes, "xpbd_world_set_polytopes (set_shapes gives vertices only)"};
+    return {w->has_topology, w->n, w->n_shapes, "xpbd_world_set_polytopes (set_shapes gives vertices only)", true, w->terrain.planes != nullptr};
 }
 
 int check_world_raycast(const char *who, const xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host)

@@ -204,6 +204,11 @@ pub struct XpbdEdgeQuery {
 pub const XPBD_NO_HIT: u32 = 0xFFFF_FFFF;
 pub const XPBD_RAY_INSIDE: u32 = 0xFFFF_FFFF;
 pub const XPBD_RAYCAST_BRUTE_FORCE: u32 = 1;
+/// EXTENSION: a flag of the raycast, overlap and sweep calls of xpbd_world alike: the heightfield of xpbd_world_set_terrain answers
+/// too (XPBD_E_INVALID without one; an unknown flag for xpbd_multi_world_*).  A hit on it has body = XPBD_HIT_TERRAIN and face = the
+/// triangle 2 * (j * (nx - 1) + i) + k (XPBD_RAY_INSIDE from in or under the ground); an overlap's entry for it is the last of its segment.
+pub const XPBD_QUERY_TERRAIN: u32 = 0x100;
+pub const XPBD_HIT_TERRAIN: u32 = 0xFFFF_FFFE;
 
 /// xpbd_ray (64 bytes): distances are in units of |direction|; ignore_body = XPBD_NO_HIT for none; reserved = 0
 #[repr(C)]

@@ -502,7 +502,8 @@ class BatchWorld {
     void history_restore(uint32_t index) { check(xpbd_world_history_restore(w_, index)); }
     void history_truncate(uint32_t length) { check(xpbd_world_history_truncate(w_, length)); }
     uint32_t history_length() const { return xpbd_world_history_length(w_); }
-    // closest body along every ray at the current poses (include/xpbd.h, "Scene queries")
+    // closest body along every ray at the current poses (include/xpbd.h, "Scene queries").  For this call, overlap() and sweep():
+    // flags | XPBD_QUERY_TERRAIN makes the terrain of set_terrain answer too (body = XPBD_HIT_TERRAIN; "Terrain in the scene queries")
     std::vector<xpbd_ray_hit> raycast(const std::vector<xpbd_ray> &rays, uint32_t flags = 0)
     {
         std::vector<xpbd_ray_hit> hits(rays.size());

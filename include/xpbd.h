@@ -553,8 +553,8 @@ int  xpbd_world_set_restitution(xpbd_world *w, const double *restitution, uint32
  * samples, NULL heights, a non-finite height, origin or cell, a cell <= 0.  After XPBD_E_OOM / XPBD_E_HIP the previous
  * terrain still holds too: the new table is built in a block of its own and moved in last.
  * Not here: xpbd_multi_world_* has no such call (its frame runs the fused pair-solve + integrate + ground kernel at the halo
- * seam, which has no terrain form); rays, overlaps and sweeps do not see the terrain (it is not a body, as the plane is
- * not); the contact report lists body pairs only. */
+ * seam, which has no terrain form); the contact report lists body pairs only.  Rays, overlaps and sweeps see the terrain
+ * when asked to: "Terrain in the scene queries", XPBD_QUERY_TERRAIN. */
 #define XPBD_MAX_TERRAIN_SAMPLES (1u << 22)
 typedef struct xpbd_heightfield {   /* 48 bytes */
     uint32_t nx, ny;          /* samples along x and y, each >= 2, nx * ny <= XPBD_MAX_TERRAIN_SAMPLES */
@@ -1137,6 +1137,69 @@ int  xpbd_world_sweep_device(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32
  * ignore_body are global indices.  Same bits as one xpbd_world over the same bodies. */
 int  xpbd_multi_world_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags,
                             xpbd_sweep_hit *hits);
+
+/* ---------------------------------------------------------------------------
+ * Terrain in the scene queries (EXTENSION): with XPBD_QUERY_TERRAIN in `flags` the heightfield of xpbd_world_set_terrain
+ * answers a ray cast, an overlap query and a sweep next to the bodies.  One flag value serves the three families, above each
+ * family's own bits.  Accepted by xpbd_world_raycast, _raycast_masked, _raycast_device, _raycast_masked_device,
+ * xpbd_world_overlap(_device) and xpbd_world_sweep(_device).  xpbd_multi_world_* has no terrain: there the flag is an unknown
+ * flag.  With the flag and no terrain set the call is XPBD_E_INVALID and the outputs are untouched (what
+ * xpbd_world_sample_terrain does without a terrain); every other argument check is unchanged, "no polytopes" and "no bodies"
+ * included.  Without the flag a call enqueues exactly what it did before: a world with a terrain then answers as one
+ * without.  Masks and ignore_body do not concern the terrain: it has no group and no index.  No body has the index
+ * XPBD_HIT_TERRAIN: a world holds fewer bodies than that.
+ *
+ * The terrain as a solid.  With xi = x0 + i * dx and yj = y0 + j * dy (formed exactly so, no fused multiply-add) triangle
+ * T = (i, j, k) -- k = 0 the lower triangle of cell (i, j), k = 1 the upper, number 2 * (j * (nx - 1) + i) + k -- stands for
+ * the prism under it, unbounded below: the points with
+ *     xi <= x <= x(i+1),  yj <= y <= y(j+1),
+ *     g = (x - xi) * dy - (y - yj) * dx:  g >= 0 for the lower triangle, g <= 0 for the upper,
+ *     dot(n, p) - d <= 0   with {n, d} the plane of T (TERRAIN, steps 4 to 6).
+ * The terrain is the union of the prisms, so the ground has an inside.  A query's cell borders are x0 + i * dx; the
+ * stepper's lookup puts them where floor((x - x0) / dx) changes.  The two can differ in the last place.
+ *
+ * One ray (o, dir, max_distance) against T follows the ray-body rule above: t_lo = 0, entering = none, t_hi = max_distance,
+ * and the constraints are visited in the order top plane, x slab, y slab, diagonal.
+ *   The top plane is (s, v) = (dot(n, o) - d, dot(n, dir)); the diagonal is (g(o), dir.x * dy - dir.y * dx) for the upper
+ *   triangle and both negated for the lower (the two triangles of a cell compute the same t bit for bit).  For (s, v):
+ *     s or v is NaN: the ray misses;
+ *     v < 0: t_k = (-s) / v, and it replaces t_lo only if strictly greater;   v > 0: t_hi = min(t_hi, (-s) / v);
+ *     v = 0: the ray misses if s > 0.
+ *   A slab [lo, hi] along an axis with components o_a, dir_a:  dir_a = 0: the ray misses unless lo <= o_a <= hi; else
+ *     t1 = (lo - o_a) / dir_a, t2 = (hi - o_a) / dir_a; the smaller replaces t_lo if greater, the larger t_hi if smaller.
+ *   The ray hits T iff t_lo <= t_hi, at t = t_lo.
+ * Neighbouring prisms share the t of their wall and of their diagonal bit for bit, the test t_lo <= t_hi is inclusive and the
+ * prisms are solid below, so no ray slips through a seam: where it leaves one prism above that prism's plane it is in the
+ * next one from the same t on, and either hits it there (through the wall, if it is already under the next plane) or goes on.
+ * The terrain's answer is the minimum over ALL triangles under the order (t, triangle number).  Its fields:
+ *   body = XPBD_HIT_TERRAIN;  distance = t;  point = o + t * dir per component;
+ *   face = the triangle's number, normal = its n -- also when the ray entered through a wall or the diagonal (a seam of
+ *   rounding size, or the outer wall of the field met from outside below the surface);
+ *   face = XPBD_RAY_INSIDE and normal = (0,0,0) when nothing entered: the origin is in or under the ground, and t = 0.
+ * (A direction component so small that (lo - o_a) / dir_a overflows is still a valid direction: the rule holds as it stands with
+ * t = +inf, so such a ray's answer can lie AT t = +inf, distance +inf, as it can for a body.  Every call returns.)
+ * A terrain hit's fields do not depend on max_distance, only whether there is one.  A ray that is invalid for the bodies (a
+ * NaN or infinite component, a zero direction, a bad max_distance) hits nothing.  The ray's result is the smaller of the
+ * bodies' answer and the terrain's under the existing order (t, body): a body wins a tie against the terrain.
+ * With XPBD_RAYCAST_BRUTE_FORCE (and XPBD_SWEEP_BRUTE_FORCE) every triangle is tested, a diagnostic for small fields; else the
+ * cells under the ray's xy-projection are walked (2D-DDA, every border's t from its own slab expression).  Same bits.
+ *
+ * Sweeps: vertex against terrain, as the stepper's ground contact.  Every world vertex aw_v = fa * a_v of the volume is the
+ * ray (aw_v, direction, max_distance) against the terrain; the winner is the minimum under (t, triangle, vertex).  Fields:
+ * body = XPBD_HIT_TERRAIN, feature = XPBD_FEATURE_FACE_B, face = the triangle, normal = n, position = sweep.position +
+ * t * direction.  A vertex that starts in or under the ground gives XPBD_SWEEP_INITIAL with t = 0, face = XPBD_NO_HIT and
+ * normal = (0,0,0).  The terrain replaces the bodies' hit only if it is strictly earlier.  A sweep that hits no body by
+ * its own fields (shape, frame, direction, max_distance; see above) does not hit the terrain either.  As the stepper, this
+ * misses a terrain ridge that meets a FACE or an edge of the volume between its vertices.
+ *
+ * Overlaps: a volume touches the terrain iff the stepper would give it a ground contact there: some vertex x = fq * a_v has
+ * the stepper's lookup (TERRAIN, steps 1 to 3) inside the field and s = dot(n, x) - d < 0.  "Free" therefore means "no ground
+ * contact in the next step".  The entry is {XPBD_HIT_TERRAIN, XPBD_FEATURE_FACE_B, the smallest s (the first minimum)}: the
+ * last of the query's segment, because its index is the largest.  offsets, *n_out and XPBD_E_CAPACITY count it as any other
+ * entry.
+ * ------------------------------------------------------------------------- */
+#define XPBD_QUERY_TERRAIN 0x100u      /* raycast, overlap and sweep flags: the terrain answers too */
+#define XPBD_HIT_TERRAIN   0xFFFFFFFEu /* .body of a hit on the terrain */
 
 /* ---------------------------------------------------------------------------
  * Contact REPORTS (EXTENSION): which body pairs the contact pipeline of XPBD_MODE_CONTACTS found touching, with the
