@@ -1,0 +1,266 @@
+// xpbd_checks.cpp -- the argument checks of the C ABI that need no device, shared by the single and the multi-GPU world.
+// Host-only: no HIP header, builds with plain g++ (as xpbd_population_remap.cpp).
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "xpbd_checks.hpp"
+#include "xpbd_error.h"
+
+namespace xpbd {
+
+int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies)
+{
+    for (uint32_t k = 0; k < n_joints; ++k) {
+        const xpbd_joint &j = joints[k];
+        if (j.body_a >= n_bodies || j.body_b >= n_bodies || j.body_a == j.body_b)
+            return set_error(XPBD_E_INVALID, "%s: joint %u links bodies %u and %u of %u", who, k, j.body_a, j.body_b, n_bodies);
+        if (!(j.distance >= 0.0) || !(j.distance <= 1.0e300))
+            return set_error(XPBD_E_INVALID, "%s: joint %u has distance %g", who, k, j.distance);
+        if (j.kind != XPBD_JOINT_DISTANCE && j.kind != XPBD_JOINT_HINGE && j.kind != XPBD_JOINT_SLIDER)
+            return set_error(XPBD_E_INVALID, "%s: joint %u has unknown kind %u", who, k, j.kind);
+        if (j.kind == XPBD_JOINT_SLIDER && j.distance != 0.0)
+            return set_error(XPBD_E_INVALID, "%s: slider %u needs distance 0 (got %g)", who, k, j.distance);
+        if (j.reserved != 0)
+            return set_error(XPBD_E_INVALID, "%s: joint %u: reserved must be 0", who, k);
+        if (j.kind == XPBD_JOINT_HINGE || j.kind == XPBD_JOINT_SLIDER)
+            for (const double *axis : {j.axis_a, j.axis_b}) {
+                const double len2 = axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2];
+                if (!(len2 > 0.999 && len2 < 1.001))
+                    return set_error(XPBD_E_INVALID, "%s: %s %u needs unit axes (|axis|^2 = %g)", who, j.kind == XPBD_JOINT_HINGE ? "hinge" : "slider", k, len2);
+            }
+    }
+    return XPBD_OK;
+}
+
+int check_per_body(const char *who, const char *what, const void *values, uint32_t n, uint32_t n_bodies, const char *count)
+{
+    if (!values && n)
+        return set_error(XPBD_E_INVALID, "%s: NULL %s with %s = %u", who, what, count, n);
+    if (values && n != n_bodies)
+        return set_error(XPBD_E_INVALID, "%s: %s = %u but the world holds %u bodies", who, count, n, n_bodies);
+    return XPBD_OK;
+}
+
+int check_materials(const char *who, const xpbd_material *materials, uint32_t n)
+{
+    for (uint32_t i = 0; materials && i < n; ++i) {
+        if (!(materials[i].friction >= 0.0))
+            return set_error(XPBD_E_INVALID, "%s: materials[%u].friction = %g (must be >= 0, +inf allowed)", who, i, materials[i].friction);
+        if (!(materials[i].reserved == 0.0))
+            return set_error(XPBD_E_INVALID, "%s: materials[%u].reserved = %g (must be 0)", who, i, materials[i].reserved);
+    }
+    return XPBD_OK;
+}
+
+int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits)
+{
+    if (n_limits && !limits)
+        return set_error(XPBD_E_INVALID, "%s: NULL argument", who);
+    auto unit = [](const double *v) {
+        const double len2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+        return len2 > 0.999 && len2 < 1.001; // the hinge's tolerance (xpbd_world_set_joints)
+    };
+    auto perpendicular = [](const double *v, const double *axis) {
+        const double d = v[0] * axis[0] + v[1] * axis[1] + v[2] * axis[2];
+        return d > -1e-3 && d < 1e-3;
+    };
+    std::vector<uint8_t> kinds_seen(n_joints, 0);
+    for (uint32_t k = 0; k < n_limits; ++k) {
+        const xpbd_joint_limit &l = limits[k];
+        if (l.joint >= n_joints)
+            return set_error(XPBD_E_INVALID, "%s: limit %u names joint %u of %u", who, k, l.joint, n_joints);
+        const xpbd_joint &j = joints[l.joint];
+        if (l.kind == XPBD_LIMIT_HINGE) {
+            if (j.kind != XPBD_JOINT_HINGE && j.kind != XPBD_JOINT_SLIDER)
+                return set_error(XPBD_E_INVALID, "%s: limit %u is a HINGE limit on joint %u of kind %u", who, k, l.joint, j.kind);
+        } else if (l.kind == XPBD_LIMIT_SLIDE) {
+            if (j.kind != XPBD_JOINT_SLIDER)
+                return set_error(XPBD_E_INVALID, "%s: limit %u is a SLIDE limit on joint %u of kind %u", who, k, l.joint, j.kind);
+        } else if (l.kind == XPBD_LIMIT_SWING || l.kind == XPBD_LIMIT_TWIST) {
+            if (j.kind != XPBD_JOINT_DISTANCE)
+                return set_error(XPBD_E_INVALID, "%s: limit %u (kind %u) needs a DISTANCE joint, joint %u is of kind %u", who, k, l.kind, l.joint, j.kind);
+            if (!unit(j.axis_a) || !unit(j.axis_b))
+                return set_error(XPBD_E_INVALID, "%s: limit %u needs unit axes on joint %u", who, k, l.joint);
+        } else {
+            return set_error(XPBD_E_INVALID, "%s: limit %u has unknown kind %u", who, k, l.kind);
+        }
+        if (kinds_seen[l.joint] & (1u << l.kind))
+            return set_error(XPBD_E_INVALID, "%s: joint %u has two limits of kind %u", who, l.joint, l.kind);
+        kinds_seen[l.joint] |= (uint8_t)(1u << l.kind);
+        if (l.kind == XPBD_LIMIT_SLIDE) { // metres: finite, lower <= upper; the references are not read
+            if (!(l.lower <= l.upper) || !std::isfinite(l.lower) || !std::isfinite(l.upper))
+                return set_error(XPBD_E_INVALID, "%s: slide limit %u has bounds [%g, %g] (need finite lower <= upper)", who, k, l.lower, l.upper);
+            continue;
+        }
+        if (l.kind != XPBD_LIMIT_SWING) {
+            if (!unit(l.ref_a) || !unit(l.ref_b))
+                return set_error(XPBD_E_INVALID, "%s: limit %u needs unit references", who, k);
+            if (!perpendicular(l.ref_a, j.axis_a) || !perpendicular(l.ref_b, j.axis_b))
+                return set_error(XPBD_E_INVALID, "%s: limit %u: a reference is not perpendicular to its axis", who, k);
+        }
+        if (!(l.lower >= -M_PI && l.lower <= l.upper && l.upper <= M_PI)) // (NaN fails every comparison)
+            return set_error(XPBD_E_INVALID, "%s: limit %u has bounds [%g, %g] (need -pi <= lower <= upper <= pi)", who, k, l.lower, l.upper);
+        if (l.kind == XPBD_LIMIT_SWING && l.lower != 0.0)
+            return set_error(XPBD_E_INVALID, "%s: swing limit %u needs lower = 0 (got %g)", who, k, l.lower);
+    }
+    return XPBD_OK;
+}
+
+int check_joint_drives(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_drive *drives, uint32_t n_drives)
+{
+    if (n_drives && !drives)
+        return set_error(XPBD_E_INVALID, "%s: NULL argument", who);
+    auto unit = [](const double *v) {
+        const double len2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+        return len2 > 0.999 && len2 < 1.001; // the limits' tolerances (check_joint_limits)
+    };
+    auto perpendicular = [](const double *v, const double *axis) {
+        const double d = v[0] * axis[0] + v[1] * axis[1] + v[2] * axis[2];
+        return d > -1e-3 && d < 1e-3;
+    };
+    std::vector<uint8_t> seen(n_joints, 0); // bit 0: an angular drive, bit 1: a linear one
+    for (uint32_t k = 0; k < n_drives; ++k) {
+        const xpbd_joint_drive &d = drives[k];
+        if (d.joint >= n_joints)
+            return set_error(XPBD_E_INVALID, "%s: drive %u names joint %u of %u", who, k, d.joint, n_joints);
+        const xpbd_joint &j = joints[d.joint];
+        const bool angular = d.kind == XPBD_DRIVE_ANGLE || d.kind == XPBD_DRIVE_ANGULAR_VELOCITY;
+        if (!angular && d.kind != XPBD_DRIVE_POSITION && d.kind != XPBD_DRIVE_VELOCITY)
+            return set_error(XPBD_E_INVALID, "%s: drive %u has unknown kind %u", who, k, d.kind);
+        if (angular ? (j.kind != XPBD_JOINT_HINGE && j.kind != XPBD_JOINT_SLIDER) : j.kind != XPBD_JOINT_SLIDER)
+            return set_error(XPBD_E_INVALID, "%s: drive %u (kind %u) does not fit joint %u of kind %u", who, k, d.kind, d.joint, j.kind);
+        const uint8_t bit = angular ? 1u : 2u;
+        if (seen[d.joint] & bit)
+            return set_error(XPBD_E_INVALID, "%s: joint %u has two %s drives", who, d.joint, angular ? "angular" : "linear");
+        seen[d.joint] |= bit;
+        if (angular) {
+            if (!unit(d.ref_a) || !unit(d.ref_b))
+                return set_error(XPBD_E_INVALID, "%s: drive %u needs unit references", who, k);
+            if (!perpendicular(d.ref_a, j.axis_a) || !perpendicular(d.ref_b, j.axis_b))
+                return set_error(XPBD_E_INVALID, "%s: drive %u: a reference is not perpendicular to its axis", who, k);
+        }
+        if (!std::isfinite(d.target))
+            return set_error(XPBD_E_INVALID, "%s: drive %u has target %g", who, k, d.target);
+        if (d.kind == XPBD_DRIVE_ANGLE && !(d.target >= -M_PI && d.target <= M_PI))
+            return set_error(XPBD_E_INVALID, "%s: angle drive %u has target %g (need -pi <= target <= pi)", who, k, d.target);
+        if (!(d.compliance >= 0.0) || !std::isfinite(d.compliance))
+            return set_error(XPBD_E_INVALID, "%s: drive %u has compliance %g (need finite, >= 0)", who, k, d.compliance);
+        if (!(d.max_force > 0.0)) // (NaN fails the comparison; +inf passes)
+            return set_error(XPBD_E_INVALID, "%s: drive %u has max_force %g (need > 0, +inf allowed)", who, k, d.max_force);
+    }
+    return XPBD_OK;
+}
+
+int check_edit_indices(const char *who, const uint32_t *indices, uint32_t n, uint32_t n_bodies, bool unique)
+{
+    if (n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    if (!indices) {
+        if (n != n_bodies)
+            return set_error(XPBD_E_INVALID, "%s: indices == NULL names the bodies 0..n-1, but n = %u and the world holds %u bodies", who, n, n_bodies);
+        return XPBD_OK;
+    }
+    std::vector<uint8_t> seen(unique ? n_bodies : 0u, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        if (indices[k] >= n_bodies)
+            return set_error(XPBD_E_INVALID, "%s: indices[%u] = %u but the world holds %u bodies", who, k, indices[k], n_bodies);
+        if (unique && seen[indices[k]]++)
+            return set_error(XPBD_E_INVALID, "%s: indices[%u] = %u is listed twice", who, k, indices[k]);
+    }
+    return XPBD_OK;
+}
+
+int check_edit_finite(const char *who, const char *what, const double *values, size_t count)
+{
+    for (size_t k = 0; values && k < count; ++k)
+        if (!std::isfinite(values[k]))
+            return set_error(XPBD_E_INVALID, "%s: %s[%zu] = %g (must be finite)", who, what, k, values[k]);
+    return XPBD_OK;
+}
+
+int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32_t n_bodies)
+{
+    if (!list)
+        return set_error(XPBD_E_INVALID, "%s: NULL list", who);
+    if (n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    for (uint32_t k = 0; k < n; ++k) {
+        const xpbd_impulse &e = list[k];
+        if (e.body >= n_bodies)
+            return set_error(XPBD_E_INVALID, "%s: list[%u].body = %u but the world holds %u bodies", who, k, e.body, n_bodies);
+        if (e.flags & ~XPBD_IMPULSE_AT_CENTRE)
+            return set_error(XPBD_E_INVALID, "%s: list[%u] has unknown flags 0x%x", who, k, e.flags);
+        bool finite = true;
+        for (int a = 0; a < 3; ++a)
+            finite = finite && std::isfinite(e.impulse[a]) && std::isfinite(e.angular_impulse[a]) &&
+                     ((e.flags & XPBD_IMPULSE_AT_CENTRE) || std::isfinite(e.point[a]));
+        if (!finite)
+            return set_error(XPBD_E_INVALID, "%s: list[%u] has a component that is not finite", who, k);
+    }
+    return XPBD_OK;
+}
+
+// The flags' part of the three checks: `known` are the family's own bits.
+int check_query_flags(const char *who, const QueryTarget &t, uint32_t flags, uint32_t known)
+{
+    if (flags & ~(known | (t.terrain_allowed ? XPBD_QUERY_TERRAIN : 0u)))
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if ((flags & XPBD_QUERY_TERRAIN) && !t.has_terrain)
+        return set_error(XPBD_E_INVALID, "%s: XPBD_QUERY_TERRAIN but the world has no terrain (xpbd_world_set_terrain)", who);
+    return XPBD_OK;
+}
+
+int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host)
+{
+    if (n_rays && (!rays || !hits))
+        return set_error(XPBD_E_INVALID, "%s: NULL rays or hits", who);
+    if (int rc = check_query_flags(who, t, flags, XPBD_RAYCAST_BRUTE_FORCE))
+        return rc;
+    if (!t.has_topology)
+        return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
+    for (uint32_t r = 0; host && r < n_rays; ++r)
+        if (rays[r].reserved)
+            return set_error(XPBD_E_INVALID, "%s: ray %u has reserved = %u (must be 0)", who, r, rays[r].reserved);
+    return XPBD_OK;
+}
+
+int check_overlap(const char *who, const QueryTarget &t, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
+                  const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host)
+{
+    if (n_queries && (!queries || !offsets || (host && !n_out)))
+        return set_error(XPBD_E_INVALID, "%s: NULL queries, offsets or n_out", who);
+    if (cap && !hits)
+        return set_error(XPBD_E_INVALID, "%s: NULL hits with cap = %u", who, cap);
+    if (int rc = check_query_flags(who, t, flags, XPBD_OVERLAP_BRUTE_FORCE | XPBD_OVERLAP_MASKED))
+        return rc;
+    if (!t.has_topology)
+        return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
+    for (uint32_t q = 0; host && q < n_queries; ++q) {
+        if (queries[q].reserved)
+            return set_error(XPBD_E_INVALID, "%s: query %u has reserved = %u (must be 0)", who, q, queries[q].reserved);
+        if (queries[q].shape >= t.n_shapes)
+            return set_error(XPBD_E_INVALID, "%s: query %u has shape = %u but the table holds %u shapes", who, q, queries[q].shape, t.n_shapes);
+    }
+    if (t.n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    return XPBD_OK;
+}
+
+int check_sweep(const char *who, const QueryTarget &t, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, const void *hits, bool host)
+{
+    if (n_sweeps && (!sweeps || !hits))
+        return set_error(XPBD_E_INVALID, "%s: NULL sweeps or hits", who);
+    if (int rc = check_query_flags(who, t, flags, XPBD_SWEEP_BRUTE_FORCE | XPBD_SWEEP_MASKED))
+        return rc;
+    if (!t.has_topology)
+        return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
+    for (uint32_t q = 0; host && q < n_sweeps; ++q)
+        if (sweeps[q].reserved)
+            return set_error(XPBD_E_INVALID, "%s: sweep %u has reserved = %u (must be 0)", who, q, sweeps[q].reserved);
+    if (t.n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    return XPBD_OK;
+}
+
+} // namespace xpbd

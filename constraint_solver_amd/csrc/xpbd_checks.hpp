@@ -1,0 +1,52 @@
+// xpbd_checks.hpp -- the argument checks of the C ABI that need no device, shared by the single and the multi-GPU world (not
+// installed).  Each answers XPBD_OK or XPBD_E_INVALID with a message naming `who`.  Host-only: no HIP header, builds with
+// plain g++ (as xpbd_population_remap.hpp).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/xpbd.h"
+
+namespace xpbd {
+
+// The argument checks of the scene queries (the caller has dealt with a NULL world).  In order: NULL arrays, unknown flags, no
+// polytopes (`setter`: the call that sets them), with `host` the records' own fields (reserved, shape: the arrays are host
+// memory) and, for an overlap, a target without bodies.  A ray cast does not mind one: every ray misses.  XPBD_QUERY_TERRAIN
+// is a known flag only where `terrain_allowed` (the single world; the multi-GPU world has no terrain), and then needs
+// `has_terrain`: without one the call is refused right after the flags, naming xpbd_world_set_terrain, as
+// xpbd_world_sample_terrain is.
+struct QueryTarget {
+    bool has_topology;
+    uint32_t n_bodies, n_shapes;
+    const char *setter;
+    bool terrain_allowed = false, has_terrain = false;
+};
+// The flags' part of the three checks: `known` are the family's own bits.
+int check_query_flags(const char *who, const QueryTarget &t, uint32_t flags, uint32_t known);
+int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host);
+// n_out: what a host variant reports its total through (NULL passes for a device variant, which has none).
+int check_overlap(const char *who, const QueryTarget &t, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
+                  const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host);
+// As check_overlap; a sweep's shape is not an error, it hits nothing.
+int check_sweep(const char *who, const QueryTarget &t, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, const void *hits, bool host);
+// The argument checks of xpbd_world_set_joints against a world of n_bodies bodies / of xpbd_world_set_joint_limits against a
+// joint list.
+int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies);
+int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits);
+// ... of xpbd_world_set_joint_drives against a joint list.
+int check_joint_drives(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_drive *drives, uint32_t n_drives);
+// ... of a per-body array (`what`) handed to a world of n_bodies bodies: NULL only with n == 0 (the default), else n == n_bodies.
+// `count`: what the caller's interface calls n.
+int check_per_body(const char *who, const char *what, const void *values, uint32_t n, uint32_t n_bodies, const char *count = "n");
+// ... and of the records of xpbd_world_set_materials: friction >= 0 (+inf allowed, NaN not), reserved == 0.
+int check_materials(const char *who, const xpbd_material *materials, uint32_t n);
+// ... of the host variants of the body edits (include/xpbd.h, "Body EDITS") against a world of n_bodies bodies, after the
+// caller has dealt with a NULL world and n == 0: a world without bodies, an index list (NULL: bodies 0..n-1, then n ==
+// n_bodies; an index >= n_bodies; with `unique`, an index twice), `count` doubles that must all be finite (`what` names them;
+// NULL values pass), and an impulse list (NULL, a body >= n_bodies, unknown flags, non-finite components).
+int check_edit_indices(const char *who, const uint32_t *indices, uint32_t n, uint32_t n_bodies, bool unique);
+int check_edit_finite(const char *who, const char *what, const double *values, size_t count);
+int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32_t n_bodies);
+
+} // namespace xpbd

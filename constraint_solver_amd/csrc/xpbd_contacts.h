@@ -209,5 +209,7 @@ hipError_t launch_repack_bodies(const double *old_aos, const uint32_t *old_shape
 
 // Exclusive scan of data[0..n) in place; data[n] receives the total.  scratch: >= n/1024 + 2 uint32.
 hipError_t launch_exclusive_scan(uint32_t *data, uint32_t n, uint32_t *scratch, hipStream_t stream);
+// What the host callers reserve for `scratch` (bytes), with room to spare.
+inline size_t scan_scratch_bytes(size_t n) { return (n / 1024 + 8) * 4; }
 
 } // namespace xpbd

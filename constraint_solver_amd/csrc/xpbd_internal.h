@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "xpbd_checks.hpp" // the argument checks both worlds share
 #include "xpbd_error.h"
 
 namespace xpbd {
@@ -148,22 +149,6 @@ int download_records(xpbd_world *w, const uint32_t *host_slots, uint32_t n, doub
 // The world's bodies become: body s = the present body host_src[s] (>= 0) or incoming record -host_src[s] - 1 (39 doubles
 // each).  Only the incoming records cross the bus; otherwise as xpbd_world_upload_bodies (joints and neighbour lists dropped).
 int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const double *incoming39, uint32_t n_incoming);
-// The argument checks of the scene queries, shared by the single and the multi-GPU world (XPBD_E_INVALID with a message naming
-// `who`; the caller has dealt with a NULL world).  In order: NULL arrays, unknown flags, no polytopes (`setter`: the call that
-// sets them), with `host` the records' own fields (reserved, shape: the arrays are host memory) and, for an overlap, a target
-// without bodies.  A ray cast does not mind one: every ray misses.  XPBD_QUERY_TERRAIN is a known flag only where
-// `terrain_allowed` (the single world; the multi-GPU world has no terrain), and then needs `has_terrain`: without one the call
-// is refused right after the flags, naming xpbd_world_set_terrain, as xpbd_world_sample_terrain is.
-struct QueryTarget {
-    bool has_topology;
-    uint32_t n_bodies, n_shapes;
-    const char *setter;
-    bool terrain_allowed = false, has_terrain = false;
-};
-int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host);
-// n_out: what a host variant reports its total through (NULL passes for a device variant, which has none).
-int check_overlap(const char *who, const QueryTarget &t, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
-                  const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host);
 // Ray casts of the world's bodies, stream-ordered (device arrays) / from and to host arrays (waits).  dev_global_id: device
 // array of w's body count, the index each body is known by (XPBD_NO_HIT: the body does not answer); NULL: its slot.
 // masked: only bodies whose collision-filter group meets `mask` answer (xpbd_world_raycast_masked); else every body does.
@@ -178,9 +163,8 @@ int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32
                     xpbd_overlap_hit *dev_hits, uint32_t cap, const uint32_t *dev_global_id);
 int overlap_host(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets, xpbd_overlap_hit *hits,
                  uint32_t cap, uint32_t *n_out, const uint32_t *dev_global_id);
-// Sweep queries against the world's bodies (include/xpbd.h, "Sweep queries"): the check (as check_overlap; a sweep's shape is
-// not an error, it hits nothing), then stream-ordered / from and to host arrays, on the scratch and staging of the other queries.
-int check_sweep(const char *who, const QueryTarget &t, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, const void *hits, bool host);
+// Sweep queries against the world's bodies (include/xpbd.h, "Sweep queries"): stream-ordered / from and to host arrays, on the
+// scratch and staging of the other queries.
 int sweep_enqueue(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *dev_hits,
                   const uint32_t *dev_global_id);
 int sweep_host(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits, const uint32_t *dev_global_id);
@@ -189,22 +173,4 @@ int sweep_host(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint3
 // ascending with the slot).  Waits.  A world without bodies reports nothing.
 int report_shard(xpbd_world *w, const uint8_t *dev_owned, const uint32_t *dev_global_id, std::vector<xpbd_pair_contact> &pairs,
                  std::vector<xpbd_contact_point> &points) noexcept;
-// The argument checks of xpbd_world_set_joints against a world of n_bodies bodies / of xpbd_world_set_joint_limits against a
-// joint list (XPBD_E_INVALID with a message naming `who`).
-int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies);
-int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits);
-// ... of xpbd_world_set_joint_drives against a joint list.
-int check_joint_drives(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_drive *drives, uint32_t n_drives);
-// ... of a per-body array (`what`) handed to a world of n_bodies bodies: NULL only with n == 0 (the default), else n == n_bodies.
-// `count`: what the caller's interface calls n.
-int check_per_body(const char *who, const char *what, const void *values, uint32_t n, uint32_t n_bodies, const char *count = "n");
-// ... and of the records of xpbd_world_set_materials: friction >= 0 (+inf allowed, NaN not), reserved == 0.
-int check_materials(const char *who, const xpbd_material *materials, uint32_t n);
-// ... of the host variants of the body edits (include/xpbd.h, "Body EDITS") against a world of n_bodies bodies, after the
-// caller has dealt with a NULL world and n == 0: a world without bodies, an index list (NULL: bodies 0..n-1, then n ==
-// n_bodies; an index >= n_bodies; with `unique`, an index twice), `count` doubles that must all be finite (`what` names them;
-// NULL values pass), and an impulse list (NULL, a body >= n_bodies, unknown flags, non-finite components).
-int check_edit_indices(const char *who, const uint32_t *indices, uint32_t n, uint32_t n_bodies, bool unique);
-int check_edit_finite(const char *who, const char *what, const double *values, size_t count);
-int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32_t n_bodies);
 } // namespace xpbd

@@ -63,7 +63,7 @@ def test_sharded_equals_single_device_and_oracle(n_ranks, through_device):
 @pytest.mark.parametrize("which", ["every third body", "one shard's side only"])
 def test_sharded_bodies_of_one_shape_with_different_masses(which):
     """Bodies of ONE shape with different mass properties: a world keeps the mass properties per shape while all bodies of a
-    shape share them bit for bit (xpbd_world.cpp: stat_shared) and per body otherwise.  The re-plans re-pack the shards on the
+    shape share them bit for bit (xpbd_world.hpp: stat_shared) and per body otherwise.  The re-plans re-pack the shards on the
     device and must notice when an ARRIVING body (a ghost, a migrated body) breaks a shard's sharing: heavy bodies everywhere,
     and heavy bodies at one end of the line only (so that one shard starts with shared properties and learns better from
     its first ghosts)."""
