@@ -1,0 +1,184 @@
+"""The scenes of tests/xprec_bounce_cases.py through the C ABI (World.set_restitution, set_terrain, set_materials, set_joints,
+set_joint_limits, set_joint_drives; SAT): stage 6 and the terrain as ground within K_BOUNCE of the extended-precision model on
+every scene and under every SAT schedule, on the eight-lanes-per-body path and, behind a far field, on the one-lane-per-body
+path; the controls without set_restitution, without set_terrain and on a flattened field; the seam between a four-substep
+step, four single-substep steps and the split API; and xpbd_world_sample_terrain against the model's lookup."""
+import numpy as np
+import pytest
+
+import xprec_bounce_cases as bc
+import xprec_model as xm
+import xprec_pairs_cases as pc
+from constraint_solver_amd import capi
+from golden_util import bits_equal
+
+pytestmark = pytest.mark.gpu
+
+SMALL_WORLD = 16384          # xpbd_contacts.hip: up to this many bodies the pair solve runs eight lanes per body
+SCENE_NAMES = list(bc.SCENES)
+SCHEDULES = (capi.SAT_SCHEDULE_AUTO, capi.SAT_SCHEDULE_ONE_PASS, capi.SAT_SCHEDULE_TWO_PASS)
+SEAM_SCENES = ["bounce-h1200", "jointed-h1200", "lifts-h1200", "wheels-h1200", "terrain-h1200-on"]
+
+
+def far_field(far):
+    """That many boxes on a 4 m grid 200 m away (test_gpu_xprec_drives.far_field)."""
+    if not far:
+        return np.zeros((0, 38)), np.zeros(0, dtype=np.uint32)
+    extra, extra_sid = capi.scene_generate(capi.SCENE_BOXES, 9, far)
+    k = np.arange(far)
+    extra[:, 31], extra[:, 32] = 200.0 + 4.0 * (k % 128), 4.0 * (k // 128)
+    extra[:, 22:25] *= 0.3
+    return extra, extra_sid
+
+
+def prepare(w, s, start, extra, sid, without=()):
+    w.upload(np.concatenate([start, extra]), sid)
+    if len(s["joints"]):
+        w.set_joints(s["joints"])
+    if len(s["limits"]):
+        w.set_joint_limits(s["limits"])
+    if len(s["drives"]):
+        w.set_joint_drives(s["drives"])
+    if s["speed"]:
+        w.set_max_depenetration_speed(s["speed"])
+    if s["mu"] is not None:
+        w.set_materials(np.concatenate([s["mu"], np.full(len(extra), np.inf)]), s["ground_mu"])
+    if s["bouncing"] and "restitution" not in without:
+        w.set_restitution(np.concatenate([s["e"], np.zeros(len(extra))]), s["ground_e"], s["threshold"])
+    field = None if "terrain" in without else s["terrain"]
+    if field is None:
+        w.set_terrain(None)
+    else:
+        w.set_terrain(field["heights"] * 0.0 if "flat" in without else field["heights"], field["origin"], field["cell"])
+
+
+def run(name, schedule=capi.SAT_SCHEDULE_AUTO, far=0, without=(), frames=None):
+    """Every single-substep frame of the scene on the device, each from the scene's state at its start."""
+    t = bc.trajectory(name)
+    extra, extra_sid = far_field(far)
+    out = []
+    with capi.World(mode=capi.MODE_CONTACTS) as w:
+        w.set_polytopes(pc.capi_polytopes(capi))
+        w.set_narrowphase(capi.NARROWPHASE_SAT)
+        w.set_sat_schedule(schedule)
+        for start, _, _, s in t["frames"][:frames]:
+            sid = np.concatenate([s["sid"], extra_sid]).astype(np.uint32)
+            prepare(w, s, start, extra, sid, without)
+            w.step(s["h"], 1)
+            out.append(w.download()[:len(start)])
+    return t, out
+
+
+def verdict(name, got):
+    """The model's bound and the exclusion caps on this run."""
+    errs, excl, entry = bc.check_states(name, got)
+    bc.assert_caps(name, excl, entry)
+    print("%s: device against the model %.1f" % (name, bc.worst(errs, excl)))
+
+
+@pytest.mark.parametrize("schedule", SCHEDULES, ids=["auto", "one-pass", "two-pass"])
+@pytest.mark.parametrize("name", SCENE_NAMES)
+def test_bouncing_and_terrain_scenes(name, schedule):
+    _, got = run(name, schedule=schedule)
+    verdict(name, got)
+
+
+@pytest.mark.parametrize("name", ["bounce-h1200", "jointed-h240", "lifts-h240", "chain-h1200", "terrain-h240-on"])
+def test_behind_a_far_field_uses_one_lane_per_body(name):
+    """Scenes (a), (e) and (g) with more than SMALL_WORLD bodies in the world: the same verdict, and the small world's bits."""
+    _, got = run(name, far=SMALL_WORLD + 16)
+    verdict(name, got)
+    _, small = run(name)
+    for f in range(len(got)):
+        assert bits_equal(got[f], small[f]), f
+
+
+def leaves_the_bound(name, without):
+    t, got = run(name, without=(without,), frames=2)
+    worst = 0.0
+    for f in range(2):
+        _, _, res, s = t["frames"][f]
+        worst = max(worst, np.where(bc.excluded(res, s["exact"]), 0, bc.errors(name, f, got[f], res)).max())
+    return worst
+
+
+@pytest.mark.parametrize("name", ["bounce-h1200", "faces-h1200"])
+def test_without_set_restitution_the_device_leaves_the_bound(name):
+    assert leaves_the_bound(name, "restitution") > bc.K_BOUNCE
+
+
+@pytest.mark.parametrize("without", ["terrain", "flat"])
+def test_without_the_terrain_the_device_leaves_the_bound(without):
+    """Without set_terrain, and with scene (g)'s field replaced by an all-zero one of the same grid."""
+    assert leaves_the_bound("terrain-h1200-on", without) > bc.K_BOUNCE
+
+
+@pytest.mark.parametrize("name", SEAM_SCENES)
+def test_four_substeps_in_one_step_equal_four_steps_and_the_split_api(name):
+    """From frame 0: step(4 h, 4) equals four step(h, 1) and contacts_begin + 4 x contacts_substep bit for bit, so the schedule
+    that stage 6 and the terrain force (one kernel sequence per substep) hands stage 6 the v0, w0 and the masks of the
+    single-substep path that the model checks.  Printed beside it: the four-substep result against the model chained four times
+    (a figure, no bound: the device's rounding of one substep is the next one's input)."""
+    t = bc.trajectory(name)
+    start, _, _, s = t["frames"][0]
+    h = s["h"]
+    none = far_field(0)[0]
+    with capi.World(mode=capi.MODE_CONTACTS) as w:
+        w.set_polytopes(pc.capi_polytopes(capi))
+        w.set_narrowphase(capi.NARROWPHASE_SAT)
+        prepare(w, s, start, none, s["sid"])
+        w.step(4 * h, 4)
+        fused = w.download()
+        prepare(w, s, start, none, s["sid"])
+        for _ in range(4):
+            w.step(h, 1)
+        single = w.download()
+        prepare(w, s, start, none, s["sid"])
+        w.contacts_begin(4 * h)
+        for _ in range(4):
+            w.contacts_substep(h)
+        split = w.download()
+    state = start
+    for _ in range(4):
+        res = bc.model(name, 0, state=state)
+        state = xm.native().to_f64(res["state"])
+    e = pc.normalized_errors(fused, res["state"], start, s["ext"], h, bc.links(name, 0, res))
+    print("%s: four substeps against the model chained four times %.1f" % (name, e.max()))
+    assert np.abs(fused - start)[:, 31:38].max() > 1e-4
+    assert bits_equal(fused, single)
+    assert bits_equal(fused, split)
+
+
+def probe_points(field):
+    """Grid corners, points on the diagonals, on cell lines and inside both triangles of every cell, and points outside."""
+    ny, nx = field["heights"].shape
+    (x0, y0), (dx, dy) = field["origin"], field["cell"]
+    pts = []
+    for j in range(ny):
+        for i in range(nx):
+            for fu, fv in ((0.0, 0.0), (0.5, 0.5), (0.25, 0.25), (0.5, 0.0), (0.0, 0.5), (0.75, 0.25), (0.25, 0.75)):
+                pts.append((x0 + (i + fu) * dx, y0 + (j + fv) * dy))
+    pts += [(x0 - dx, y0), (x0, y0 - dy), (x0 + (nx - 1) * dx, y0), (x0, y0 + (ny - 1) * dy), (np.nan, y0)]
+    return np.array(pts)
+
+
+@pytest.mark.parametrize("which", ["cell", "grid", "zero", "bumpy"])
+def test_sample_terrain_equals_the_models_lookup(which):
+    """xpbd_world_sample_terrain against xprec_model.terrain_lookup evaluated in f64 with the header's operations: inside or
+    outside, n and the height (d - (n.x x + n.y y)) / n.z to the bit.  This holds k_terrain_planes to the second reading."""
+    field = {"cell": bc.ONE_CELL, "grid": bc.GRID, "zero": bc.ZERO, "bumpy": bc.bumpy_field()}[which]
+    pts = probe_points(field)
+    num = xm.f64()
+    x = np.stack([pts[:, 0], pts[:, 1], np.zeros(len(pts))])
+    inside, n, d, where = xm.terrain_lookup(num, field, x)
+    with np.errstate(invalid="ignore"):
+        height = np.where(inside, (d - (n[0] * x[0] + n[1] * x[1])) / n[2], np.nan)
+    normal = np.where(inside, n, 0.0).T
+    with capi.World(mode=capi.MODE_CONTACTS) as w:
+        w.set_terrain(field["heights"], field["origin"], field["cell"])
+        got_h, got_n = w.sample_terrain(pts)
+    assert inside.sum() >= 7 * (field["heights"].shape[0] - 1) * (field["heights"].shape[1] - 1) and (~inside).sum() >= 5
+    assert where["lower"][inside].any() and (~where["lower"][inside]).any()
+    assert np.array_equal(np.isnan(got_h), ~inside)
+    assert np.array_equal(got_h[inside].view(np.uint64), height[inside].view(np.uint64))
+    assert np.array_equal((got_n + 0.0).view(np.uint64), (np.ascontiguousarray(normal) + 0.0).view(np.uint64))

@@ -11,7 +11,8 @@ significand on x86-64, 2^11 times finer than f64: the fast path) or of mpmath.mp
 arrays (3, n), quaternions (4, n) as (s, x, y, z), matrices (3, 3, n) indexed [column, row] (cgmath Matrix3, the ABI's
 [3*col + row]).
 
-Reference lines below are jim-ec/constraint_solver src/*.rs.
+Reference lines below are jim-ec/constraint_solver src/*.rs.  The terrain (terrain_lookup, ground(terrain=)) is the one
+extension here: a second reading of include/xpbd.h, "TERRAIN", alone, generic over the scalar like the rest.
 """
 import numpy as np
 
@@ -182,10 +183,79 @@ def limited(num, dist, limit, delta, correction, cc):
     return np.where((dist > allowed).astype(bool), allowed, dist), np.abs(num.to_f64(dist - allowed))
 
 
-def ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain, mu=None, limit=None):
+TERRAIN_MUTATIONS = ("triangles_swapped", "target_vertical", "d_unnormalised", "plane_beyond_field")
+
+
+def heightfield(heights, origin, cell):
+    """The terrain of include/xpbd.h, "TERRAIN", as the model takes it: heights (ny, nx) f64, H[j][i] = heights[j, i]."""
+    return {"heights": np.ascontiguousarray(heights, dtype=np.float64), "origin": (float(origin[0]), float(origin[1])),
+            "cell": (float(cell[0]), float(cell[1]))}
+
+
+def _floor(num, u):
+    """floor(u) as an f64 array (whole numbers are exact in every scalar type), decided in the model's scalars."""
+    f = np.floor(num.to_f64(u))
+    f = np.where((num.conv(f) > u).astype(bool), f - 1, f)
+    return np.where((num.conv(f + 1) <= u).astype(bool), f + 1, f)
+
+
+def terrain_lookup(num, terrain, x, mutation=None):
+    """include/xpbd.h, "TERRAIN", "Lookup", steps 1 to 6, for the world points x (3, k); written from that prose alone, not
+    from tests/terrain_model.py or the kernels.  Returns (inside (k,) bool -- False is the header's OUTSIDE --, n (3, k),
+    d (k,), info): the plane {n, d} of the triangle above or below each point (a stand-in where it is outside), and in
+    `info` per point `lower` (bool, the triangle of step 4) and, in metres and f64, the distances at which the plane changes
+    discretely: `cell` from the nearest cell line, `diagonal` from the line fu == fv of its cell, `border` from the field's
+    border (for points outside too)."""
+    assert mutation is None or mutation in TERRAIN_MUTATIONS
+    H = terrain["heights"]
+    ny, nx = H.shape
+    x0, y0 = (num.conv(np.array([c]))[0] for c in terrain["origin"])
+    dx, dy = (num.conv(np.array([c]))[0] for c in terrain["cell"])
+    u, v = (x[0] - x0) / dx, (x[1] - y0) / dy                                          # 1.
+    inside = (u >= 0).astype(bool) & (v >= 0).astype(bool)
+    safe_u, safe_v = np.where(inside, u, u * 0), np.where(inside, v, v * 0)
+    fi, fj = _floor(num, safe_u), _floor(num, safe_v)                                  # 2. half-open at the far edges
+    inside = inside & (fi < nx - 1) & (fj < ny - 1)
+    fi, fj = np.where(inside, fi, 0.0), np.where(inside, fj, 0.0)
+    i, j = fi.astype(np.int64), fj.astype(np.int64)
+    fu, fv = safe_u - num.conv(fi), safe_v - num.conv(fj)                              # 3.
+    h00, h10, h01, h11 = (num.conv(H[j + a, i + b]) for a, b in ((0, 0), (0, 1), (1, 0), (1, 1)))
+    lower = (fu >= fv).astype(bool)                                                    # 4. the diagonal belongs to the lower one
+    if mutation == "triangles_swapped":
+        lower = ~lower
+    sx = np.where(lower, (h10 - h00) / dx, (h11 - h01) / dx)
+    sy = np.where(lower, (h11 - h10) / dy, (h01 - h00) / dy)
+    raw = np.stack([-sx, -sy, sx * 0 + 1])                                             # 5.
+    n = raw * ((sx * 0 + 1) / num.sqrt(dot(raw, raw)))                                 # raw * (1.0 / length(raw))
+    corner = np.stack([x0 + num.conv(fi) * dx, y0 + num.conv(fj) * dy, h00])           # 6.
+    d = dot(raw if mutation == "d_unnormalised" else n, corner)
+    # how far the point is from where the plane changes (f64, metres)
+    u64, v64, fu64, fv64 = (np.asarray(num.to_f64(a), dtype=np.float64) for a in (u, v, fu, fv))
+    cx, cy = terrain["cell"]
+    cell = np.minimum(np.minimum(fu64, 1 - fu64) * cx, np.minimum(fv64, 1 - fv64) * cy)
+    diagonal = np.abs(fu64 - fv64) * cx * cy / np.hypot(cx, cy)
+    px, py, lx, ly = u64 * cx, v64 * cy, (nx - 1) * cx, (ny - 1) * cy
+    within = (px >= 0) & (py >= 0) & (px <= lx) & (py <= ly)
+    out_x, out_y = np.maximum(np.maximum(-px, px - lx), 0), np.maximum(np.maximum(-py, py - ly), 0)
+    border = np.where(within, np.minimum(np.minimum(px, lx - px), np.minimum(py, ly - py)), np.hypot(out_x, out_y))
+    border = np.where(np.isnan(border), 0.0, border)
+    info = {"lower": lower, "cell": np.where(inside, cell, np.inf), "diagonal": np.where(inside, diagonal, np.inf), "border": border}
+    if mutation == "plane_beyond_field":                                               # the plane z = 0 wherever the field is not
+        n = np.where(inside, n, np.stack([sx * 0, sx * 0, sx * 0 + 1]))
+        d = np.where(inside, d, d * 0)
+        inside = np.ones_like(inside)
+    return inside, n, d, info
+
+
+def ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain, mu=None, limit=None, terrain=None, mutation=None):
     """collision::ground and solver::solve for every body, from the post-integrate pose (pos, rot).  mu (f64 per body) and
-    limit (speed h) are the extension's friction and depenetration limit; None is the reference.  Returns the pose after
-    the solve and the masks, margins and conditioning of step()."""
+    limit (speed h) are the extension's friction and depenetration limit; None is the reference.  terrain (heightfield()):
+    the plane under each vertex is the lookup's {n, d} in place of z = 0 (xpbd.h, "TERRAIN", "Ground contacts"): the vertex
+    contacts iff it is inside the field and !(s >= 0), s = dot(n, x) - d; target = x - s n; everything after `target` is the
+    code of the plane.  mutation: one of TERRAIN_MUTATIONS.  Returns the pose after the solve and the masks, margins and
+    conditioning of step(); `margin` is min |s| with a terrain (inside vertices), and cell_margin, diagonal_margin and
+    border_margin the smallest terrain_lookup distances of a tested vertex; lower_contacts / upper_contacts count the body's
+    contacts by triangle and n_outside its vertices outside the field."""
     sqrt = num.sqrt
     im, M, com = s["inverse_mass"], s["inverse_inertia"], s["center_of_mass"]
     n, vmax = pos.shape[1], len(vert)
@@ -194,12 +264,27 @@ def ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain,
     mask = np.zeros(n, dtype=np.uint32)
     margin = np.full(n, np.inf)
     branch = np.full(n, np.inf)
-    xs = []
+    lines = {k: np.full(n, np.inf) for k in ("cell_margin", "diagonal_margin", "border_margin")}
+    tally = {k: np.zeros(n, dtype=np.int64) for k in ("lower_contacts", "upper_contacts", "n_outside")}
+    xs, planes = [], []
     for v in range(vmax):
         x = frame_apply(cur_p, cur_q, vert[v])                              # collision.rs:17
         live = v < counts
-        z = num.to_f64(x[2])
-        below = live & (x[2] < 0).astype(bool)                              # collision.rs:18, skip when z >= 0
+        if terrain is None:
+            z = num.to_f64(x[2])
+            below = live & (x[2] < 0).astype(bool)                          # collision.rs:18, skip when z >= 0
+            planes.append(None)
+        else:
+            inside, pn, pd, where = terrain_lookup(num, terrain, x, mutation if mutation in TERRAIN_MUTATIONS else None)
+            dist = dot(pn, x) - pd
+            z = np.where(inside, num.to_f64(dist), np.inf)
+            below = live & inside & ~(dist >= 0).astype(bool)
+            planes.append((pn, dist))
+            for key, name in (("cell_margin", "cell"), ("diagonal_margin", "diagonal"), ("border_margin", "border")):
+                lines[key] = np.where(live, np.minimum(lines[key], where[name]), lines[key])
+            tally["lower_contacts"] += below & where["lower"]
+            tally["upper_contacts"] += below & ~where["lower"]
+            tally["n_outside"] += live & ~inside
         margin = np.where(live, np.minimum(margin, np.abs(z)), margin)
         mask |= below.astype(np.uint32) << np.uint32(v)
         xs.append(x)
@@ -213,7 +298,13 @@ def ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain,
             continue
         x = xs[v][:, idx]
         p_, q_, M_, c_, im_ = pos[:, idx], rot[:, idx], M[:, :, idx], com[:, idx], im[idx]
-        target = np.stack([x[0], x[1], x[2] * 0])                          # collision.rs:22
+        if terrain is None:
+            target = np.stack([x[0], x[1], x[2] * 0])                      # collision.rs:22
+        else:
+            pn, dist = planes[v][0][:, idx], planes[v][1][idx]
+            target = x - pn * dist                                          # xpbd.h: target = x - s * n per component
+            if mutation == "target_vertical":                               # the surface point straight below or above x
+                target = np.stack([x[0], x[1], x[2] - dist / pn[2]])
         correction = target - x                                             # collision.rs:23
         cc = dot(correction, correction)
         domain[idx] &= num.to_f64(cc) >= F64_MIN_NORMAL
@@ -242,7 +333,7 @@ def ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain,
         spin = cross(matvec(M_, c0 - (p_ + c_)), impulse)
         q_ = normalize_q(q_ + qmul(pure(spin) * 0.5, q_), sqrt)
         pos[:, idx], rot[:, idx] = p_, q_
-    return pos, rot, {"mask": mask, "margin": margin, "cond": cond, "branch": branch}
+    return pos, rot, {"mask": mask, "margin": margin, "cond": cond, "branch": branch, "xs": xs, **lines, **tally}
 
 
 def derive(num, pos, rot, past_pos, past_rot, h):

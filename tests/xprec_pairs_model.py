@@ -8,6 +8,9 @@ geometry: every query is a maximum over ALL faces or edge pairs of a minimum ove
 Stage S uses tests/xprec_model.py's scalar abstraction, cgmath helpers, integrate, ground and derive.  Its joint and limit
 entries (joint_terms) are read from include/xpbd.h (XPBD_JOINT_*, XPBD_LIMIT_*), the joint prose of xpbd_pairs_oracle.h and
 constraint.rs:6-37, rigid.rs:113-123; they follow neither tests/joint_limit_model.py, the oracle's C nor the kernel.
+Stage 6 (bounce) and the terrain (xprec_model.terrain_lookup, xprec_model.ground) are read from include/xpbd.h's sections
+"RESTITUTION" and "TERRAIN" alone; tests/restitution_model.py, tests/terrain_model.py, xpbd_step.hpp and xpbd_contacts.hip were
+not read for them.
 
 Vectors are arrays (3, k) of model scalars as in xprec_model.py.  Reference lines are jim-ec/constraint_solver src/*.rs.
 """
@@ -33,6 +36,14 @@ JOINT_MUTATIONS = ("joint_sign_a", "anchor_without_com", "joints_from_integrated
 DRIVE_MUTATIONS = ("slider_keeps_positional", "perpendicular_sign_a", "extras_uncounted", "nonbinding_slide_counted",
                    "drive_without_base_compliance", "clamp_by_h", "clamped_uncounted", "velocity_from_integrated",
                    "extras_from_integrated", "wrap_dropped", "angular_drive_same_sign", "linear_drive_w_without_angular")
+# wrong readings of stage 6 (xpbd.h, "RESTITUTION") and of the terrain as ground ("TERRAIN"); the table of
+# test_xprec_bounce_oracle.py names a scene per member
+BOUNCE_MUTATIONS = ("e_smaller_side", "vn0_post_derive", "threshold_on_vn", "arms_at_integrated", "points_averaged", "one_sweep",
+                    "no_give_back", "entries_summed", "idle_counted", "reference_pushed_same_way", "compliance_in_wsum",
+                    "ground_before_pairs", "ground_reads_pre_ground", "impulse_arm_in_rest_space", "triangles_swapped",
+                    "target_vertical", "d_unnormalised", "plane_beyond_field", "bounce_normal_vertical",
+                    "bounce_lookup_at_integrated")
+SWEEPS = 4                                                               # XPBD_RESTITUTION_SWEEPS
 JOINT_DISTANCE, JOINT_HINGE, JOINT_SLIDER = 0, 1, 2                      # XPBD_JOINT_*
 LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST, LIMIT_SLIDE = 0, 1, 2, 3          # XPBD_LIMIT_*
 DRIVE_ANGLE, DRIVE_ANGULAR_VELOCITY, DRIVE_POSITION, DRIVE_VELOCITY = 0, 1, 2, 3   # XPBD_DRIVE_*
@@ -220,7 +231,8 @@ def manifold(frame_a, frame_b, sh_a, sh_b, num=None):
             out["p_inc"].append(p)
             out["p_ref"].append(p - normal * depth)                      # Plane::project, geometry.rs:45-47
     margins["clip"] = clip
-    out.update(feature=feature, index_a=rf if feature == FACE_A else inc, index_b=inc if feature == FACE_A else rf)
+    out.update(feature=feature, index_a=rf if feature == FACE_A else inc, index_b=inc if feature == FACE_A else rf,
+               normal=normal)                                            # the reference plane's: out of the reference body
     return out
 
 
@@ -531,8 +543,244 @@ def joint_terms(num, s, pos, rot, joints, limits, compliance, depenetration=None
     return sum_p, sum_q, count, info
 
 
+def _scalars(num, x):
+    x = np.asarray(x)
+    return num.conv(x) if x.dtype == np.float64 else x
+
+
+def bounce(num, s, pose, velocities, start_velocities, manifolds, mask, vert, h, restitution, ground_restitution,
+           bounce_threshold, terrain=None, mutation=None, integrated=None, ground_xs=None, compliance=None):
+    """Stage 6: include/xpbd.h, "RESTITUTION", and the restitution paragraph of "TERRAIN", written from that prose alone; it
+    follows neither tests/restitution_model.py, tests/terrain_model.py, xpbd_step.hpp nor the kernels.  pose = (x, q) after
+    derive, velocities = (v, w) after derive, start_velocities = (v0, w0) before integrate, all (3 | 4, n) model scalars;
+    manifolds and mask: THIS substep's, formed at the post-integrate poses; restitution: f64 per body or None (all 0).
+      e        the header's compare-and-select, (e_inc < e_ref) ? e_ref : e_inc; ground: (e_b < e_ground) ? e_ground : e_b.
+      manifold XPBD_RESTITUTION_SWEEPS passes over its points in point order on copies of the two bodies' post-derive
+               velocities; a visit does nothing unless e > 0 && vn0 < -bounce_threshold && Wsum > 0; wanted = total_k +
+               ((-e) vn0 - vn) / Wsum, no compliance; if (!(wanted > 0)) wanted = 0; lambda = wanted - total_k, nothing
+               more when it is 0; +lambda n on the incident copy at p_inc, -lambda n on the reference copy at p_ref, at once.
+               n: stage N's reference plane normal of a face contact, d / |d| with d = p_ref - p_inc of the one-point
+               contact (no visit at |d| == 0).  A manifold in which no visit applied an impulse makes no entry.
+      Jacobi   every body adds the entries (v_copy - v, w_copy - w) of its manifolds in neighbour order from 0 and applies
+               sum / count.
+      ground   then, per body, the set bits of the mask in ascending vertex order, sequentially on the body's current v, w:
+               p = Rigid::frame() at (x, q) * vertex, n = (0, 0, 1) or -- with a terrain -- the plane's normal of the lookup
+               repeated at p (outside: no entry); entry iff e > 0 && vn0 < -bounce_threshold && Wsum > 0 && vn < (-e) vn0.
+    Arms and W are formed at (x, q): arm = p - (x + center_of_mass), W = inverse_mass + (I^-1 a) . a, a = q^-1 (arm x n); an
+    impulse P changes v by P inverse_mass and w by (I^-1 arm) x P, the arm NOT rotated into rest space (rigid.rs:113-123).
+    Poses are not touched.
+    Continuity.  The clamp !(wanted > 0) and the ground condition vn < (-e) vn0 are continuous: lambda is 0 at the boundary,
+    so which side a rounding takes changes nothing, and neither excludes a body.  The threshold vn0 < -bounce_threshold is
+    a jump (threshold_margin), and so is a manifold's entry: with no applied impulse its count of 1 vanishes (entry_margin).
+    Returns (v, w, info); info per body: bounce_pair_entries, bounce_one_point (those of them from a manifold of one point),
+    bounce_ground_entries, bounce_push / bounce_give_back /
+    bounce_clamped (visits with lambda > 0, lambda < 0, wanted clamped to 0), threshold_margin (smallest |vn0 + threshold| h of
+    a point with e > 0 and Wsum > 0: metres), entry_margin (metres: of a manifold that takes part and applies nothing the
+    smallest |(-e) vn0 - vn| h of its visits; of one that has an entry the largest |lambda| Wsum h), bounce_cell_margin,
+    bounce_diagonal_margin, bounce_border_margin (the repeated terrain lookup's), `bounce_seen`, a set of tags, and
+    `bounce_impulses`, every point's total impulse after the last pass and every ground entry's lambda (f64)."""
+    assert mutation is None or mutation in BOUNCE_MUTATIONS
+    sqrt = num.sqrt
+    im, M, com = s["inverse_mass"], s["inverse_inertia"], s["center_of_mass"]
+    pos, rot = pose
+    vel, ang = velocities
+    v0, w0 = (vel, ang) if mutation == "vn0_post_derive" else start_velocities
+    a_pos, a_rot = integrated if mutation == "arms_at_integrated" else (pos, rot)
+    n = pos.shape[1]
+    e_body = np.zeros(n) if restitution is None else np.asarray(restitution, dtype=np.float64)
+    threshold = num.conv(np.array([float(bounce_threshold)]))[0]
+    info = {k: np.zeros(n, dtype=np.int64) for k in ("bounce_pair_entries", "bounce_ground_entries", "bounce_push",
+                                                     "bounce_give_back", "bounce_clamped", "bounce_one_point")}
+    info.update({k: np.full(n, np.inf) for k in ("threshold_margin", "entry_margin", "bounce_cell_margin",
+                                                 "bounce_diagonal_margin", "bounce_border_margin")})
+    seen = set()
+    impulses = []                                                        # every point's final total and every ground lambda
+    lookup_mutation = mutation if mutation in xm.TERRAIN_MUTATIONS else None
+
+    def as_float(x):
+        return float(num.to_f64(np.array([x]))[0])
+
+    def lower(key, bodies, value):
+        for b in bodies:
+            info[key][b] = min(info[key][b], value)
+
+    def arm_of(b, p):
+        return p - (a_pos[:, b] + com[:, b])
+
+    def resistance(b, arm, normal):
+        a = qrot(conj(a_rot[:, b]), cross(arm, normal))
+        return im[b] + dot(matvec(M[:, :, b], a), a)
+
+    def push(b, v, w, arm, impulse):
+        lever = qrot(conj(a_rot[:, b]), arm) if mutation == "impulse_arm_in_rest_space" else arm
+        return v + impulse * im[b], w + cross(matvec(M[:, :, b], lever), impulse)
+
+    def pairs(vel, ang):
+        entries = [[] for _ in range(n)]
+        for (i, j), m in sorted(manifolds.items()):
+            if m["separated"] or not len(m["p_ref"]):
+                continue
+            ref, inc = (j, i) if m["feature"] == FACE_B else (i, j)
+            e_inc, e_ref = float(e_body[inc]), float(e_body[ref])
+            e64 = (e_ref if e_inc < e_ref else e_inc) if mutation != "e_smaller_side" else min(e_inc, e_ref)
+            if e_inc != e_ref and e64 > 0:
+                seen.add("larger e on the incident side" if e_inc > e_ref else "larger e on the reference side")
+            e = num.conv(np.array([e64]))[0]
+            points = []
+            for p_ref, p_inc in zip(m["p_ref"], m["p_inc"]):
+                p_ref, p_inc = _scalars(num, p_ref), _scalars(num, p_inc)
+                if m["feature"] == EDGES:
+                    d = p_ref - p_inc
+                    length = sqrt(dot(d, d))
+                    if length == 0:
+                        continue
+                    normal = d / length
+                else:
+                    normal = _scalars(num, m["normal"])
+                arm_i, arm_r = arm_of(inc, p_inc), arm_of(ref, p_ref)
+                w_sum = resistance(inc, arm_i, normal) + resistance(ref, arm_r, normal)
+                if mutation == "compliance_in_wsum":
+                    w_sum = w_sum + compliance
+                vn0 = dot(normal, (v0[:, inc] + cross(w0[:, inc], arm_i)) - (v0[:, ref] + cross(w0[:, ref], arm_r)))
+                points.append((normal, arm_i, arm_r, w_sum, vn0))
+                if e64 > 0 and w_sum > 0:
+                    lower("threshold_margin", (inc, ref), abs(as_float(vn0 + threshold) * h))
+                    seen.add("a point over the threshold" if vn0 < -threshold else "a point under the threshold")
+            copies = {inc: (vel[:, inc], ang[:, inc]), ref: (vel[:, ref], ang[:, ref])}
+            totals = [e * 0 for _ in points]
+            applied, idle_gap, largest = False, np.inf, 0.0
+
+            def closing(normal, arm_i, arm_r):
+                (vi, wi), (vr, wr) = copies[inc], copies[ref]
+                return dot(normal, (vi + cross(wi, arm_i)) - (vr + cross(wr, arm_r)))
+
+            def takes_part(w_sum, vn, vn0):
+                tested = vn if mutation == "threshold_on_vn" else vn0
+                return e64 > 0 and bool(tested < -threshold) and bool(w_sum > 0)
+
+            if mutation == "points_averaged":            # every point from the same copies, a share of 1 / points each
+                lams = []
+                for normal, arm_i, arm_r, w_sum, vn0 in points:
+                    vn = closing(normal, arm_i, arm_r)
+                    lam = ((-e) * vn0 - vn) / w_sum if takes_part(w_sum, vn, vn0) else e * 0
+                    lams.append(lam / len(points) if lam > 0 else e * 0)
+                for lam, (normal, arm_i, arm_r, _, _) in zip(lams, points):
+                    if lam != 0:
+                        applied = True
+                        copies[inc] = push(inc, *copies[inc], arm_i, normal * lam)
+                        copies[ref] = push(ref, *copies[ref], arm_r, normal * -lam)
+            else:
+                for _ in range(1 if mutation == "one_sweep" else SWEEPS):
+                    for k, (normal, arm_i, arm_r, w_sum, vn0) in enumerate(points):
+                        vn = closing(normal, arm_i, arm_r)
+                        if not takes_part(w_sum, vn, vn0):
+                            continue
+                        step = ((-e) * vn0 - vn) / w_sum
+                        wanted = totals[k] + step
+                        clamped = not bool(wanted > 0)
+                        if clamped:
+                            wanted = wanted * 0
+                        if mutation == "no_give_back":     # lambda clamped, not the total
+                            wanted = totals[k] + (step if step > 0 else step * 0)
+                        lam = wanted - totals[k]
+                        info["bounce_clamped"][[inc, ref]] += 1 if clamped else 0
+                        if lam == 0:
+                            idle_gap = min(idle_gap, abs(as_float((-e) * vn0 - vn)) * h)
+                            continue
+                        totals[k] = wanted
+                        applied = True
+                        largest = max(largest, abs(as_float(lam * w_sum)) * h)
+                        info["bounce_push" if lam > 0 else "bounce_give_back"][[inc, ref]] += 1
+                        copies[inc] = push(inc, *copies[inc], arm_i, normal * lam)
+                        copies[ref] = push(ref, *copies[ref], arm_r, normal * (lam if mutation == "reference_pushed_same_way" else -lam))
+            impulses.extend(as_float(x) for x in totals)
+            if applied:
+                lower("entry_margin", (inc, ref), largest if mutation != "points_averaged" else np.inf)
+            elif idle_gap < np.inf:
+                lower("entry_margin", (inc, ref), idle_gap)
+                seen.add("a manifold that takes part without an entry")
+            if applied or (mutation == "idle_counted" and points):
+                for b in (inc, ref):
+                    entries[b].append((copies[b][0] - vel[:, b], copies[b][1] - ang[:, b]))
+                    info["bounce_pair_entries"][b] += 1
+                    info["bounce_one_point"][b] += len(points) == 1
+        vel, ang = vel.copy(), ang.copy()
+        for b in range(n):
+            if entries[b]:
+                dv, dw = vel[:, b] * 0, ang[:, b] * 0
+                for x, y in entries[b]:
+                    dv, dw = dv + x, dw + y
+                count = 1 if mutation == "entries_summed" else len(entries[b])
+                vel[:, b], ang[:, b] = vel[:, b] + dv / count, ang[:, b] + dw / count
+        return vel, ang
+
+    def grounded(vel, ang):
+        vel, ang = vel.copy(), ang.copy()
+        up = num.conv(np.array([0.0, 0.0, 1.0]))
+        for b in np.nonzero(mask)[0]:
+            e_b = float(e_body[b])
+            e64 = (ground_restitution if e_b < ground_restitution else e_b) if mutation != "e_smaller_side" else min(e_b, ground_restitution)
+            e = num.conv(np.array([e64]))[0]
+            frame_p = a_pos[:, b] + com[:, b] + qrot(a_rot[:, b], -com[:, b])        # Rigid::frame, rigid.rs:75-80
+            v, w = vel[:, b], ang[:, b]
+            before = (v, w)
+            for k in range(len(vert)):
+                if not (int(mask[b]) >> k) & 1:
+                    continue
+                p = frame_apply(frame_p, a_rot[:, b], vert[k][:, b])
+                normal = up
+                if terrain is not None:
+                    at = ground_xs[k][:, b] if mutation == "bounce_lookup_at_integrated" else p
+                    inside, pn, _, where = xm.terrain_lookup(num, terrain, at[:, None], lookup_mutation)
+                    for key in ("cell", "diagonal", "border"):
+                        lower("bounce_%s_margin" % key, (b,), float(where[key][0]))
+                    if not inside[0]:
+                        seen.add("a bounce vertex outside the field")
+                        continue
+                    if mutation != "bounce_normal_vertical":
+                        normal = pn[:, 0]
+                arm = arm_of(b, p)
+                w_sum = resistance(b, arm, normal)
+                if mutation == "compliance_in_wsum":
+                    w_sum = w_sum + compliance
+                rv, rw = before if mutation == "ground_reads_pre_ground" else (v, w)
+                vn = dot(normal, rv + cross(rw, arm))
+                vn0 = dot(normal, v0[:, b] + cross(w0[:, b], arm))
+                if not (e64 > 0 and bool(w_sum > 0)):
+                    continue
+                lower("threshold_margin", (b,), abs(as_float(vn0 + threshold) * h))
+                tested = vn if mutation == "threshold_on_vn" else vn0
+                seen.add("a point over the threshold" if vn0 < -threshold else "a point under the threshold")
+                if not (bool(tested < -threshold) and bool(vn < (-e) * vn0)):
+                    continue
+                lam = ((-e) * vn0 - vn) / w_sum
+                v, w = push(b, v, w, arm, normal * lam)
+                impulses.append(as_float(lam))
+                info["bounce_ground_entries"][b] += 1
+                if terrain is not None:
+                    seen.add("a terrain bounce")
+            vel[:, b], ang[:, b] = v, w
+        return vel, ang
+
+    if mutation == "ground_before_pairs":
+        vel, ang = pairs(*grounded(vel, ang))
+    else:
+        vel, ang = grounded(*pairs(vel, ang))
+    if info["bounce_pair_entries"].any():
+        seen.add("a pair entry")
+    if info["bounce_ground_entries"].any():
+        seen.add("a ground entry")
+    for key, tag in (("bounce_push", "a pushing visit"), ("bounce_give_back", "a give-back visit"), ("bounce_clamped", "a clamped wanted")):
+        if info[key].any():
+            seen.add(tag)
+    info["bounce_seen"] = seen
+    info["bounce_impulses"] = np.array(impulses)
+    return vel, ang, info
+
+
 def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.inf, max_depenetration_speed=0.0, num=None,
-            mutation=None, tau=0.0, joints=(), limits=(), drives=()):
+            mutation=None, tau=0.0, joints=(), limits=(), drives=(), restitution=None, ground_restitution=0.0,
+            bounce_threshold=0.0, terrain=None):
     """Stage S: one contacts substep (steps 1, 3, 4, 5 of xpbd_pairs_oracle.h) of n bodies ((n, 38) f64).  shapes: list of
     shape() dicts.  manifolds: {(i, j), i < j: {"feature", "p_ref": [(3,)], "p_inc": [(3,)]}} of the touching pairs at the
     post-integrate frames, or None: stage N on every pair (stage S o N, the fully independent substep).  mu: per-body
@@ -543,15 +791,20 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     joint entries, hinge entries and binding limits each count 1 (joint_terms).  Friction and the depenetration limit never
     touch a joint entry.  drives: records of xpbd_joint_drive; a joint's extra entries (SLIDER, XPBD_LIMIT_SLIDE, drives) are
     read at the same poses, the velocity drives' subscript-0 quantities at the poses the substep started from, and each
-    counts 1 in the same average (joint_terms).
+    counts 1 in the same average (joint_terms).  restitution (f64 per body, or None), ground_restitution, bounce_threshold:
+    stage 6, the velocity pass of xpbd.h's "RESTITUTION", after derive (bounce); with restitution None and ground_restitution
+    0 the stage is not run.  terrain (xprec_model.heightfield): the ground of step 3 and of stage 6's ground part in place of
+    the plane z = 0 (xprec_model.ground, xprec_model.terrain_lookup).  Without the four the result is what it was.
 
     Returns a dict: state (n, 38) model scalars; frames: the post-integrate frames [(position, rotation)]; manifolds: the
     ones used; per body: mask, margin, cond, flip_margin, domain (as xprec_model.step), branch (smallest distance in
     metres of a friction or depenetration-limit comparison from its threshold) and pair_cond (smallest |c1 - c0| of a
     pair point); undecided: the pairs whose stage N manifold has a margin in (0, tau]; n_points (pair-contact points of the
     body) and, from joint_terms, n_joint, n_binding, limit_margin, wrap_margin, joint_cond, `limits` and the extras' n_extra,
-    n_clamped, slide_margin, drive_margin, drive_wrap_margin, `slides`, `perps`, `drives`."""
-    assert mutation is None or mutation in MUTATIONS + JOINT_MUTATIONS + DRIVE_MUTATIONS
+    n_clamped, slide_margin, drive_margin, drive_wrap_margin, `slides`, `perps`, `drives`; from xprec_model.ground cell_margin,
+    diagonal_margin, border_margin, lower_contacts, upper_contacts, n_outside (inf and 0 without a terrain; `margin` is then
+    min |s|); and, when stage 6 ran, bounce's info."""
+    assert mutation is None or mutation in MUTATIONS + JOINT_MUTATIONS + DRIVE_MUTATIONS + BOUNCE_MUTATIONS
     joint_mutation = mutation if mutation in JOINT_MUTATIONS + DRIVE_MUTATIONS else None
     num = num or xm.native()
     sqrt = num.sqrt
@@ -574,6 +827,7 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
 
     # 1. past = pose; integrate; P1 = Rigid::frame()                        solver.rs:7-10
     past_pos, past_rot = pos, rot
+    start_vel, start_ang = vel, ang                                      # v0, w0 of stage 6
     past_p = pos + com + qrot(rot, -com)
     pos, rot, vel, ang = xm.integrate(s, pos, rot, vel, ang, hx, sqrt)
     p1_p, p1_q = pos + com + qrot(rot, -com), rot
@@ -600,7 +854,8 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     if mu is not None or np.isfinite(ground_mu):
         body_mu = np.minimum(np.full(n, np.inf) if mu is None else np.asarray(mu, dtype=np.float64), ground_mu)
     integrated_pos, integrated_rot = pos, rot
-    pos, rot, g = xm.ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain, body_mu, limit)
+    pos, rot, g = xm.ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain, body_mu, limit, terrain,
+                            mutation if mutation in xm.TERRAIN_MUTATIONS else None)
 
     # 4. pair contacts, Jacobi: every point from the poses after step 3, a body applies the average of its points
     inc, ref, pair, p_inc, p_ref = manifold_points(manifolds)
@@ -676,7 +931,16 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
 
     # 5. Rigid::derive(past, h)                                             solver.rs:15
     vel, ang, _, flip_margin = xm.derive(num, pos, rot, past_pos, past_rot, hx)
+
+    # 6. restitution: a velocity pass on this substep's manifolds and ground mask          xpbd.h, "RESTITUTION"
+    bounce_info = {}
+    if restitution is not None or ground_restitution > 0:
+        vel, ang, bounce_info = bounce(num, s, (pos, rot), (vel, ang), (start_vel, start_ang), manifolds, g["mask"], vert, float(h),
+                                       restitution, float(ground_restitution), bounce_threshold, terrain,
+                                       mutation if mutation in BOUNCE_MUTATIONS else None, (integrated_pos, integrated_rot),
+                                       g["xs"], compliance)
     s.update(position=pos, rotation=rot, velocity=vel, angular_velocity=ang)
     return {"state": xm._pack(s), "frames": frames, "manifolds": manifolds, "undecided": undecided, "mask": g["mask"],
             "margin": g["margin"], "cond": g["cond"], "flip_margin": flip_margin, "domain": domain, "branch": branch,
-            "pair_cond": pair_cond, "n_points": n_points, **joint_info}
+            "pair_cond": pair_cond, "n_points": n_points, **joint_info, **bounce_info,
+            **{k: g[k] for k in ("cell_margin", "diagonal_margin", "border_margin", "lower_contacts", "upper_contacts", "n_outside")}}
