@@ -41,7 +41,7 @@ def test_rust_binding_text_declares_every_symbol():
 
 def test_no_entry_point_lets_an_exception_out():
     """Every function include/xpbd.h declares is defined noexcept, or as a function-try-block closed by the ABI's handler
-    (csrc/xpbd_internal.h: XPBD_ABI_CATCH; csrc/xpbd_multi.cpp: XPBD_MULTI_ABI_CATCH)."""
+    (csrc/xpbd_internal.h: XPBD_ABI_CATCH; csrc/xpbd_multi.hpp: XPBD_MULTI_ABI_CATCH)."""
     src = "".join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "constraint_solver_amd", "csrc", "*.cpp"))))
     for name in header_functions():
         m = re.search(r"^[A-Za-z_][\w *]*\b%s\(([^;{}]*?)\)( noexcept)?\s*(try )?\{" % name, src, re.M)
