@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "xpbd_multi_world_set_external_wrench", "xpbd_multi_world_apply_impulses",
     "xpbd_world_overlap", "xpbd_world_overlap_device", "xpbd_multi_world_overlap",
     "xpbd_world_sweep", "xpbd_world_sweep_device", "xpbd_multi_world_sweep",
+    "xpbd_world_distance", "xpbd_world_distance_device", "xpbd_multi_world_distance",
     "xpbd_world_remove_bodies", "xpbd_world_remove_bodies_device", "xpbd_world_add_bodies",
     "xpbd_world_set_terrain", "xpbd_world_sample_terrain",
 ]
@@ -243,6 +244,39 @@ def _sweep(fn, h, sweeps, flags):
     return out
 
 
+# xpbd_distance_query (80 bytes) / xpbd_distance_hit (96 bytes) as numpy records; distance queries (EXTENSION)
+DISTANCE_QUERY_DTYPE = np.dtype([("position", "<f8", (3,)), ("rotation", "<f8", (4,)), ("max_distance", "<f8"), ("shape", "<u4"),
+                                 ("ignore_body", "<u4"), ("mask", "<u4"), ("reserved", "<u4")])
+DISTANCE_HIT_DTYPE = np.dtype([("body", "<u4"), ("feature", "<u4"), ("index_a", "<u4"), ("index_b", "<u4"), ("distance", "<f8"),
+                               ("point_a", "<f8", (3,)), ("point_b", "<f8", (3,)), ("normal", "<f8", (3,))])
+DISTANCE_BRUTE_FORCE, DISTANCE_MASKED = 1, 2
+DISTANCE_OVERLAP = 3              # xpbd_distance_hit.feature: the volume and the body are not separated (distance 0)
+DISTANCE_POINT = 0xFFFFFFFF       # xpbd_distance_query.shape: the volume is the single point `position`
+DISTANCE_BRUTE_FORCE_QUERIES = 8  # calls with at most this many queries take the brute-force path anyway
+
+
+def distances(position, rotation=(1.0, 0.0, 0.0, 0.0), shape=DISTANCE_POINT, max_distance=np.inf, ignore=None, mask=None):
+    """DISTANCE_QUERY_DTYPE records from (n, 3) positions, (n, 4) rotations {s, x, y, z} and shape indices (all broadcast; the
+    default shape is DISTANCE_POINT, the point `position`), a max_distance per query or for all, the body each query ignores
+    (None: none) and its group mask (None: ~0; read with DISTANCE_MASKED only)."""
+    p, r = np.atleast_2d(np.asarray(position, dtype=np.float64)), np.atleast_2d(np.asarray(rotation, dtype=np.float64))
+    sh = np.atleast_1d(np.asarray(shape, dtype=np.uint32))
+    extra = [np.atleast_1d(np.asarray(x)) for x in (max_distance, ignore, mask) if x is not None]
+    n = max([p.shape[0], r.shape[0], sh.shape[0]] + [x.shape[0] for x in extra])
+    out = np.zeros(n, dtype=DISTANCE_QUERY_DTYPE)
+    out["position"], out["rotation"], out["shape"], out["max_distance"] = p, r, sh, max_distance
+    out["ignore_body"] = NO_HIT if ignore is None else ignore
+    out["mask"] = 0xFFFFFFFF if mask is None else mask
+    return out
+
+
+def _distance(fn, h, queries, flags):
+    q = np.ascontiguousarray(queries, dtype=DISTANCE_QUERY_DTYPE).reshape(-1)
+    out = np.zeros(q.size, dtype=DISTANCE_HIT_DTYPE)
+    _check(fn(h, q.ctypes.data if q.size else None, q.size, flags, out.ctypes.data if q.size else None))
+    return out
+
+
 # Contact reports (EXTENSION): xpbd_pair_contact (64 bytes), xpbd_contact_point (48), xpbd_contact_event (12)
 PAIR_CONTACT_DTYPE = np.dtype([("body_a", "<u4"), ("body_b", "<u4"), ("substeps", "<u4"), ("n_points", "<u4"), ("feature", "<u4"),
                                ("first_point", "<u4"), ("reserved", "<u4", (2,)), ("normal", "<f8", (3,)), ("depth", "<f8")])
@@ -408,6 +442,9 @@ def hip_lib():
             L.xpbd_world_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
             L.xpbd_world_sweep_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
             L.xpbd_multi_world_sweep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.xpbd_world_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.xpbd_world_distance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.xpbd_multi_world_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         try:
@@ -725,6 +762,16 @@ class World:
         """Device arrays of n xpbd_sweep and n xpbd_sweep_hit, stream-ordered on the world's stream."""
         _check(hip_lib().xpbd_world_sweep_device(self._h, C.c_void_p(sweeps_ptr), n, flags, C.c_void_p(hits_ptr)))
 
+    def distance(self, queries, flags=0):
+        """DISTANCE_HIT_DTYPE records of the body nearest to every convex volume or point (DISTANCE_QUERY_DTYPE records, see
+        distances()) at the current poses: the distance, the two closest points and the normal from the body to the volume;
+        DISTANCE_OVERLAP at distance 0 where the overlap query would list the body."""
+        return _distance(hip_lib().xpbd_world_distance, self._h, queries, flags)
+
+    def distance_device(self, queries_ptr, n, hits_ptr, flags=0):
+        """Device arrays of n xpbd_distance_query and n xpbd_distance_hit, stream-ordered on the world's stream."""
+        _check(hip_lib().xpbd_world_distance_device(self._h, C.c_void_p(queries_ptr), n, flags, C.c_void_p(hits_ptr)))
+
     # body edits (include/xpbd.h, "Body EDITS"): forces, impulses and state of resident bodies
     def set_external_wrench(self, indices=None, force=None, torque=None):
         """external_force / external_torque of the listed bodies (None: all bodies, in order) = rows of force / torque
@@ -1039,6 +1086,10 @@ class MultiWorld:
     def sweep(self, sweeps, flags=0):
         """World.sweep over the whole sharded world (collective); bodies and ignore_body are global indices."""
         return _sweep(hip_lib().xpbd_multi_world_sweep, self._h, sweeps, flags)
+
+    def distance(self, queries, flags=0):
+        """World.distance over the whole sharded world (collective); bodies and ignore_body are global indices."""
+        return _distance(hip_lib().xpbd_multi_world_distance, self._h, queries, flags)
 
     def synchronize(self):
         _check(hip_lib().xpbd_multi_world_synchronize(self._h))

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "xpbd_checks.hpp"
+#include "xpbd_checks_distance.hpp"
 #include "xpbd_error.h"
 
 namespace xpbd {
@@ -258,6 +259,23 @@ int check_sweep(const char *who, const QueryTarget &t, const xpbd_sweep *sweeps,
     for (uint32_t q = 0; host && q < n_sweeps; ++q)
         if (sweeps[q].reserved)
             return set_error(XPBD_E_INVALID, "%s: sweep %u has reserved = %u (must be 0)", who, q, sweeps[q].reserved);
+    if (t.n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    return XPBD_OK;
+}
+
+int check_distance(const char *who, const QueryTarget &t, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, const void *hits,
+                   bool host)
+{
+    if (n_queries && (!queries || !hits))
+        return set_error(XPBD_E_INVALID, "%s: NULL queries or hits", who);
+    if (flags & ~(XPBD_DISTANCE_BRUTE_FORCE | XPBD_DISTANCE_MASKED)) // (XPBD_QUERY_TERRAIN too: the terrain is no body)
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if (!t.has_topology)
+        return set_error(XPBD_E_INVALID, "%s: call %s first", who, t.setter);
+    for (uint32_t q = 0; host && q < n_queries; ++q)
+        if (queries[q].reserved)
+            return set_error(XPBD_E_INVALID, "%s: query %u has reserved = %u (must be 0)", who, q, queries[q].reserved);
     if (t.n_bodies == 0)
         return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
     return XPBD_OK;

@@ -30,6 +30,7 @@ int check_overlap(const char *who, const QueryTarget &t, const xpbd_overlap_quer
                   const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host);
 // As check_overlap; a sweep's shape is not an error, it hits nothing.
 int check_sweep(const char *who, const QueryTarget &t, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, const void *hits, bool host);
+// (The distance queries' check, also defined in xpbd_checks.cpp, is declared in xpbd_checks_distance.hpp.)
 // The argument checks of xpbd_world_set_joints against a world of n_bodies bodies / of xpbd_world_set_joint_limits against a
 // joint list.
 int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies);

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "xpbd_checks.hpp" // the argument checks both worlds share
+#include "xpbd_checks_distance.hpp"
 #include "xpbd_error.h"
 
 namespace xpbd {
@@ -116,6 +117,8 @@ struct xpbd_overlap_query;
 struct xpbd_overlap_hit;
 struct xpbd_sweep;
 struct xpbd_sweep_hit;
+struct xpbd_distance_query;
+struct xpbd_distance_hit;
 struct xpbd_pair_contact;
 struct xpbd_contact_point;
 
@@ -168,6 +171,12 @@ int overlap_host(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_qu
 int sweep_enqueue(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *dev_hits,
                   const uint32_t *dev_global_id);
 int sweep_host(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits, const uint32_t *dev_global_id);
+// Distance queries against the world's bodies (include/xpbd.h, "Distance queries"): stream-ordered / from and to host arrays, on
+// the scratch and staging of the other queries.
+int distance_enqueue(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *dev_hits,
+                     const uint32_t *dev_global_id);
+int distance_host(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits,
+                  const uint32_t *dev_global_id);
 // The current frame's contact report of a shard of the multi-GPU world (include/xpbd.h, "Contact REPORTS"): only the pairs whose
 // lower body has dev_owned[slot] != 0, bodies named by dev_global_id[slot] (device arrays of the world's body count; global ids
 // ascending with the slot).  Waits.  A world without bodies reports nothing.

@@ -47,6 +47,24 @@ inline void merge_sweep_hits(const void *rows, uint32_t n_ranks, uint32_t n_swee
     }
 }
 
+// The same for distance queries: rows of n_queries xpbd_distance_hit, the minimum on (distance, body).  An overlap's distance is 0
+// and a miss stands at +inf with body XPBD_NO_HIT, so neither needs a rule of its own.
+inline void merge_distance_hits(const void *rows, uint32_t n_ranks, uint32_t n_queries, xpbd_distance_hit *out)
+{
+    const uint8_t *bytes = static_cast<const uint8_t *>(rows);
+    for (uint32_t i = 0; i < n_queries; ++i) {
+        xpbd_distance_hit best;
+        std::memcpy(&best, bytes + (size_t)i * sizeof best, sizeof best);
+        for (uint32_t r = 1; r < n_ranks; ++r) {
+            xpbd_distance_hit h;
+            std::memcpy(&h, bytes + ((size_t)r * n_queries + i) * sizeof h, sizeof h);
+            if (h.distance < best.distance || (h.distance == best.distance && h.body < best.body))
+                best = h;
+        }
+        out[i] = best;
+    }
+}
+
 // offset_rows: n_ranks rows of n_queries + 1 CSR offsets into the rank's row of hit_rows (n_ranks rows of `widest`
 // xpbd_overlap_hit).  The ranks' lists of a query are disjoint and each ascends in body, so a query one rank answers keeps its
 // order and the others are sorted.  Writes offsets[0 .. n_queries] and hits[0 .. min(total, cap)) (hits may be NULL with cap ==

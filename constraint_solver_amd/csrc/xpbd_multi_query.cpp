@@ -117,6 +117,29 @@ int multi_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint32_t n_sweep
     return XPBD_OK;
 }
 
+// xpbd_multi_world_distance: every local shard answers for its owned bodies; one all-gather of the hit records, merged by the
+// (distance, global index) rule of a single world (xpbd::merge_distance_hits).
+int multi_distance(xpbd_multi_world *mw, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits)
+{
+    const char *who = "xpbd_multi_world_distance";
+    XPBD_TRY(check_usable(mw, who));
+    XPBD_TRY(xpbd::check_distance(who, query_target(mw), queries, n_queries, flags, hits, true));
+    if (n_queries == 0)
+        return XPBD_OK;
+    LocalStatus st;
+    std::vector<std::vector<xpbd_distance_hit>> mine(mw->shards.size(), std::vector<xpbd_distance_hit>(n_queries));
+    std::vector<const void *> send;
+    for (size_t k = 0; k < mw->shards.size(); ++k) {
+        if (st.ok())
+            st.keep(xpbd::distance_host(mw->shards[k].world, queries, n_queries, flags, mine[k].data(), mw->shards[k].query_ids.as<uint32_t>()));
+        send.push_back(mine[k].data());
+    }
+    std::vector<uint8_t> all;
+    XPBD_TRY(all_gather_host(mw, send, (size_t)n_queries * sizeof(xpbd_distance_hit), all, st));
+    xpbd::merge_distance_hits(all.data(), mw->n_ranks, n_queries, hits);
+    return XPBD_OK;
+}
+
 } // namespace
 } // namespace xpbd::multi
 
@@ -144,6 +167,11 @@ try {
 int xpbd_multi_world_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits)
 try {
     return multi_sweep(mw, sweeps, n_sweeps, flags, hits);
+} XPBD_MULTI_ABI_CATCH
+
+int xpbd_multi_world_distance(xpbd_multi_world *mw, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits)
+try {
+    return multi_distance(mw, queries, n_queries, flags, hits);
 } XPBD_MULTI_ABI_CATCH
 
 } // extern "C"

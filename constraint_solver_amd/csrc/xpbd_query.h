@@ -1,4 +1,5 @@
-// xpbd_query.h -- scene queries (EXTENSION): launchers for the batched ray casts, overlap queries and sweep queries in xpbd_query.hip.
+// xpbd_query.h -- scene queries (EXTENSION): launchers for the batched ray casts, overlap queries, sweep queries and distance queries in
+// xpbd_query.hip.
 //
 // Semantics: include/xpbd.h, "Scene queries".  Two paths give the same bits in every field of every hit:
 //  * grid: the bodies' bounding spheres (frame * centroid, PolytopeTables::radii) go into a uniform grid built for this call
@@ -44,8 +45,8 @@ struct QuerySizes {
 // What a ray cast over n bodies and n_rays rays needs (brute: whether it takes the brute-force path).
 QuerySizes query_scratch_bytes(uint32_t n, uint32_t n_rays, bool brute);
 
-// The scene queries' device memory of one world: the scratch of a call, shared by the ray casts, the overlap and the sweep queries, and
-// the staging of the host variants' arrays (rays or queries in, hits out, an overlap's offsets).  One call uses it at a time:
+// The scene queries' device memory of one world: the scratch of a call, shared by the ray casts, the overlap, the sweep and the
+// distance queries, and the staging of the host variants' arrays (rays or queries in, hits out, an overlap's offsets).  One call uses it at a time:
 // the calls of a world are ordered on its stream, and every host variant ends with a wait.
 struct SceneQueryScratch {
     DeviceBuffer rec, partials, grid, cell_start, cell_fill, items, scan, brute, qrec;
@@ -103,6 +104,16 @@ hipError_t launch_overlap(const BodyArrays &b, const PolytopeTables &t, const ui
 hipError_t launch_sweep(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *sweeps,
                         uint32_t n_sweeps, bool masked, bool brute, const QueryScratch &s, void *hits, hipStream_t stream,
                         const Terrain *terrain = nullptr, bool terrain_brute = false);
+
+// ---- distance queries: the body nearest to a convex volume or a point (include/xpbd.h, "Distance queries") ----------------
+// Passes: the bounding spheres of the bodies (k_query_bodies) and of the volumes (k_distance_queries, the records of an overlap
+// query); on the grid path the grid of a ray cast; then one group of 16 / 32 / 64 lanes per query walks the cells the volume's
+// sphere covers and then those the sphere grown by min(max_distance, best so far) covers, decides every candidate -- the overlap
+// query's decision, the vertex-face candidates, the edge pairs -- and keeps the minimum under (distance, index).  The brute-force
+// path, and a query that reaches further than kSweepReach cell edges, visits every body instead.  A distance query's scratch is
+// an overlap's (overlap_scratch_bytes with the number of queries).  No terrain.
+hipError_t launch_distance(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *queries,
+                           uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, void *hits, hipStream_t stream);
 
 // ---- the terrain in the scene queries (include/xpbd.h, "Terrain in the scene queries"; xpbd_terrain_query.hip) ---------------
 // Each is one kernel on `stream`, called by the three launchers above when they are given a terrain, and reads the plane table of

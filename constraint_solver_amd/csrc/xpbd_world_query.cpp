@@ -1,4 +1,4 @@
-// xpbd_world_query.cpp -- scene queries of the single-GPU world (ray casts, overlaps, sweeps): the host layer the multi-GPU
+// xpbd_world_query.cpp -- scene queries of the single-GPU world (ray casts, overlaps, sweeps, distances): the host layer the multi-GPU
 // world shares (xpbd_internal.h) and the entry points.  The argument checks: xpbd_checks.cpp.
 #include "xpbd_world.hpp"
 
@@ -129,6 +129,32 @@ int sweep_host(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint3
     });
 }
 
+int distance_enqueue(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *dev_hits,
+                     const uint32_t *dev_global_id)
+{
+    static_assert(sizeof(xpbd_distance_query) == 80 && sizeof(xpbd_distance_hit) == 96, "xpbd_distance_query is 80 bytes, xpbd_distance_hit 96");
+    if (n_queries == 0)
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    // (a shard without bodies takes the brute-force path too: every query finds nothing, no grid to build)
+    const bool brute = (flags & XPBD_DISTANCE_BRUTE_FORCE) || n_queries <= XPBD_DISTANCE_BRUTE_FORCE_QUERIES || w->n == 0;
+    const QuerySizes q = overlap_scratch_bytes(w->n, n_queries, brute); // a distance query's records are an overlap query's
+    XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
+    const bool masked = (flags & XPBD_DISTANCE_MASKED) != 0;
+    XPBD_HIP_TRY(launch_distance(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute,
+                                 w->query.view(q.table_size), dev_hits, w->stream));
+    return XPBD_OK;
+}
+
+int distance_host(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits,
+                  const uint32_t *dev_global_id)
+{
+    return query_host(w, queries, n_queries, hits, [&](const xpbd_distance_query *dev_queries, xpbd_distance_hit *dev_hits) {
+        return distance_enqueue(w, dev_queries, n_queries, flags, dev_hits, dev_global_id);
+    });
+}
+
 } // namespace xpbd
 
 extern "C" {
@@ -221,6 +247,24 @@ try {
     if (int rc = xpbd::check_sweep("xpbd_world_sweep_device", query_target(w), dev_sweeps, n_sweeps, flags, dev_hits, false))
         return rc;
     return xpbd::sweep_enqueue(w, dev_sweeps, n_sweeps, flags, dev_hits, nullptr);
+} XPBD_ABI_CATCH
+
+int xpbd_world_distance(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_distance: NULL world");
+    if (int rc = xpbd::check_distance("xpbd_world_distance", query_target(w), queries, n_queries, flags, hits, true))
+        return rc;
+    return xpbd::distance_host(w, queries, n_queries, flags, hits, nullptr);
+} XPBD_ABI_CATCH
+
+int xpbd_world_distance_device(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *dev_hits)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_distance_device: NULL world");
+    if (int rc = xpbd::check_distance("xpbd_world_distance_device", query_target(w), dev_queries, n_queries, flags, dev_hits, false))
+        return rc;
+    return xpbd::distance_enqueue(w, dev_queries, n_queries, flags, dev_hits, nullptr);
 } XPBD_ABI_CATCH
 
 } // extern "C"

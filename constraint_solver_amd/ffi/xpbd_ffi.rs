@@ -269,6 +269,43 @@ pub struct XpbdSweepHit {
     pub normal: [f64; 3],
 }
 
+pub const XPBD_DISTANCE_BRUTE_FORCE: u32 = 1;
+pub const XPBD_DISTANCE_MASKED: u32 = 2;
+pub const XPBD_DISTANCE_OVERLAP: u32 = 3;
+pub const XPBD_DISTANCE_POINT: u32 = 0xFFFF_FFFF;
+pub const XPBD_DISTANCE_BRUTE_FORCE_QUERIES: u32 = 8;
+
+/// xpbd_distance_query (80 bytes): the convex volume `shape` at the frame {position, rotation {s, x, y, z}}, or the point `position`
+/// with shape = XPBD_DISTANCE_POINT; bodies further than max_distance do not answer; ignore_body = XPBD_NO_HIT for none; mask is
+/// read with XPBD_DISTANCE_MASKED only; reserved = 0
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdDistanceQuery {
+    pub position: [f64; 3],
+    pub rotation: [f64; 4],
+    pub max_distance: f64,
+    pub shape: u32,
+    pub ignore_body: u32,
+    pub mask: u32,
+    pub reserved: u32,
+}
+
+/// xpbd_distance_hit (96 bytes): the nearest body (XPBD_NO_HIT: none within max_distance); feature = XPBD_FEATURE_* (A = the volume,
+/// B = the body) with the indices of the two closest features, or XPBD_DISTANCE_OVERLAP at distance 0; the closest points in
+/// world space; normal from the body to the volume
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdDistanceHit {
+    pub body: u32,
+    pub feature: u32,
+    pub index_a: u32,
+    pub index_b: u32,
+    pub distance: f64,
+    pub point_a: [f64; 3],
+    pub point_b: [f64; 3],
+    pub normal: [f64; 3],
+}
+
 /// xpbd_overlap_query (72 bytes): a convex volume, shape `shape` of the polytope table at the frame {position, rotation {s, x, y, z}};
 /// ignore_body = XPBD_NO_HIT for none; mask is read with XPBD_OVERLAP_MASKED only; reserved = 0
 #[repr(C)]
@@ -496,6 +533,12 @@ extern "C" {
                                    dev_hits: *mut XpbdSweepHit) -> c_int;
     pub fn xpbd_multi_world_sweep(mw: *mut XpbdMultiWorld, sweeps: *const XpbdSweep, n_sweeps: u32, flags: u32,
                                   hits: *mut XpbdSweepHit) -> c_int;
+    pub fn xpbd_world_distance(w: *mut XpbdWorld, queries: *const XpbdDistanceQuery, n_queries: u32, flags: u32,
+                               hits: *mut XpbdDistanceHit) -> c_int;
+    pub fn xpbd_world_distance_device(w: *mut XpbdWorld, dev_queries: *const XpbdDistanceQuery, n_queries: u32, flags: u32,
+                                      dev_hits: *mut XpbdDistanceHit) -> c_int;
+    pub fn xpbd_multi_world_distance(mw: *mut XpbdMultiWorld, queries: *const XpbdDistanceQuery, n_queries: u32, flags: u32,
+                                     hits: *mut XpbdDistanceHit) -> c_int;
     pub fn xpbd_world_set_contact_report(w: *mut XpbdWorld, enable: u32) -> c_int;
     pub fn xpbd_world_contact_report_counts(w: *mut XpbdWorld, out: *mut u32) -> c_int;
     pub fn xpbd_world_download_pair_contacts(w: *mut XpbdWorld, pairs: *mut XpbdPairContact, pair_cap: u32, points: *mut XpbdContactPoint,

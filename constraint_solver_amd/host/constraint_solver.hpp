@@ -540,6 +540,13 @@ class BatchWorld {
         check(xpbd_world_sweep(w_, sweeps.empty() ? nullptr : sweeps.data(), (uint32_t)sweeps.size(), flags, hits.empty() ? nullptr : hits.data()));
         return hits;
     }
+    // the body nearest to every convex volume or point, with the closest points, at the current poses (include/xpbd.h, "Distance queries")
+    std::vector<xpbd_distance_hit> distance(const std::vector<xpbd_distance_query> &queries, uint32_t flags = 0)
+    {
+        std::vector<xpbd_distance_hit> hits(queries.size());
+        check(xpbd_world_distance(w_, queries.empty() ? nullptr : queries.data(), (uint32_t)queries.size(), flags, hits.empty() ? nullptr : hits.data()));
+        return hits;
+    }
     // collision filters, one per body (empty: every body {~0u, ~0u}); flags: XPBD_FILTER_JOINTED or 0.  Upload clears them.
     void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)
     {
@@ -718,6 +725,13 @@ class ShardedWorld {
     {
         std::vector<xpbd_sweep_hit> hits(sweeps.size());
         check(xpbd_multi_world_sweep(w_, sweeps.empty() ? nullptr : sweeps.data(), (uint32_t)sweeps.size(), flags, hits.empty() ? nullptr : hits.data()));
+        return hits;
+    }
+    // the body nearest to every convex volume or point, bodies by global index; collective (include/xpbd.h, "Distance queries")
+    std::vector<xpbd_distance_hit> distance(const std::vector<xpbd_distance_query> &queries, uint32_t flags = 0)
+    {
+        std::vector<xpbd_distance_hit> hits(queries.size());
+        check(xpbd_multi_world_distance(w_, queries.empty() ? nullptr : queries.data(), (uint32_t)queries.size(), flags, hits.empty() ? nullptr : hits.data()));
         return hits;
     }
     // collision filters of the whole world, global body order (not collective); upload clears them

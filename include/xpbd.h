@@ -1139,6 +1139,120 @@ int  xpbd_multi_world_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint
                             xpbd_sweep_hit *hits);
 
 /* ---------------------------------------------------------------------------
+ * Distance queries (EXTENSION): the body nearest to each of a batch of convex volumes (or points), how far it is, and the two
+ * closest points, at the bodies' current poses.  NOT in the reference.  A host asks for proximity sensors, for clearance before
+ * a spawn ("5 cm of air around this place", not only "free"), for grasp and placement planning, steering, soft keep-out zones,
+ * and to pick the object nearest to a cursor point.
+ *
+ * The volume of query q is the convex polytope `shape` at the frame fa = {position, rotation}, exactly as for an overlap query.
+ * With shape == XPBD_DISTANCE_POINT it is the single point `position`: one vertex (number 0, aw_0 = position itself, no
+ * arithmetic), no faces, one edge (number 0, both ends vertex 0), radius 0 and centroid `position`; `rotation` is not used but
+ * must still be finite.  Bodies stand at the pose the other queries see.  The ground plane and the terrain are not bodies, and
+ * XPBD_QUERY_TERRAIN is an unknown flag for these calls.
+ *
+ * One volume A against one body B, with fb = Rigid::frame() of the body.  World vertices aw_v = fa * a_v, bw_v = fb * b_v; in the
+ * other's local space a_in_b_v = inverse(fb) * aw_v, b_in_a_v = inverse(fa) * bw_v (the sweep's).  In this order:
+ *
+ *   1. Overlap.  The pair is "not separated" by exactly rules 2 and 3 of the overlap query -- the tight bounding spheres, then
+ *      the decision part of the SAT.  For the point volume: the sphere test with radius_q = 0 and centre `position`, then
+ *      max over the faces f of B (face order; the first face's value, replaced by a later one that is larger) of
+ *      dot(n_f, a_in_b_0) - disp_f, which must be < 0 (a NaN is not: separated).  A pair that is not separated answers
+ *      feature = XPBD_DISTANCE_OVERLAP, distance = 0, index_a = index_b = XPBD_NO_HIT, point_a = point_b = normal = (0,0,0).
+ *
+ *   2. Otherwise the squared distance d2 is the minimum over the candidates below, visited in this order; the first minimum wins
+ *      (a candidate replaces the best so far only if its d2 is strictly smaller; a NaN d2 never is).
+ *      The test "x lies in face F of polytope P", for a point x of P's local space, F with the local outward plane (n, disp) and
+ *      the vertices w_0 .. w_(m-1) in the face's own winding (face_indices): for k = 0 .. m-1, with a = w_k, b = w_((k+1) % m),
+ *      c = w_((k+2) % m):
+ *          side = cross(b - a, n);  if dot(side, c - a) > 0 then side = -side;  the edge passes iff dot(side, x - a) <= 0.
+ *      x lies in F iff every edge passes (inclusive; a NaN fails).
+ *      (a) every vertex v of A (vertex order) against every face f of B (face order), position v * n_faces_b + f, in B's local
+ *          space: p = a_in_b_v, h = dot(n, p) - disp.  The candidate counts only if h >= 0 (a NaN: skipped) and foot =
+ *          p - h * n (per component: p.x - h * n.x, ...) lies in f.  d2 = h * h.  feature = XPBD_FEATURE_FACE_B, index_a = v,
+ *          index_b = f, point_a = aw_v, point_b = fb * foot.
+ *      (b) the same with the roles swapped: every vertex v of B against every face f of A, position v * n_faces_a + f, in A's
+ *          local space: p = b_in_a_v, h and foot from A's plane, foot in f.  d2 = h * h.  feature = XPBD_FEATURE_FACE_A,
+ *          index_a = f, index_b = v, point_a = fa * foot, point_b = bw_v.  The point volume has none of these.
+ *      (c) every edge i of A against every edge j of B (edge order), position i * n_edges_b + j, in world space: the clamped
+ *          closest points of the segments P0 = aw_(e_i.0), P1 = aw_(e_i.1) and Q0 = bw_(e_j.0), Q1 = bw_(e_j.1).  With
+ *          clamp(x) = (x < 0) ? 0 : ((x > 1) ? 1 : x)  (a NaN stays a NaN):
+ *              u = P1 - P0, w = Q1 - Q0, r = P0 - Q0, a = dot(u, u), e = dot(w, w), f = dot(w, r);
+ *              a == 0 and e == 0:  s = 0, t = 0
+ *              a == 0 (e != 0):    s = 0, t = clamp(f / e)
+ *              otherwise c = dot(u, r), and
+ *                e == 0:           t = 0, s = clamp((-c) / a)
+ *                else b = dot(u, w), den = a * e - b * b;  s = (den > 0) ? clamp((b * f - c * e) / den) : 0   (parallel
+ *                                  segments, or a denominator that rounding made zero or negative, start from s = 0);
+ *                                  t = (b * s + f) / e;
+ *                                  t < 0:  t = 0, s = clamp((-c) / a);   else t > 1:  t = 1, s = clamp((b - c) / a)
+ *              ca = P0 + u * s, cb = Q0 + w * t (per component), g = ca - cb, d2 = dot(g, g).
+ *          feature = XPBD_FEATURE_EDGES, index_a = i, index_b = j, point_a = ca, point_b = cb.  The clamps make this cover
+ *          vertex-edge and vertex-vertex, and a vertex whose foot rounding pushed just outside a face.
+ *      A pair without any candidate (every d2 a NaN) does not answer.  Then distance = sqrt(d2) and normal = (point_a - point_b)
+ *      * (1 / distance) per component, (0,0,0) when distance == 0: it points from the body to the volume.  The candidates are
+ *      complete for two disjoint convex polytopes: the closest pair is a vertex over the interior of a face, or two points on
+ *      two edges.
+ *
+ *   3. The pair answers iff distance <= max_distance.
+ *
+ * Per query the smallest distance wins and equal distances go to the smaller body index (in xpbd_multi_world_distance: the
+ * caller's global index).  ignore_body never answers; with XPBD_DISTANCE_MASKED body b answers only if (group_b & mask) != 0
+ * (bodies without filters are in group ~0u; without the flag no group is tested).  A body whose pose is not finite never
+ * answers.  A query whose `shape` is outside the table and not XPBD_DISTANCE_POINT, whose frame has a NaN or infinite component
+ * or whose max_distance is negative or NaN finds nothing (the call still succeeds); max_distance may be +inf.  A miss is
+ * {XPBD_NO_HIT, 0, XPBD_NO_HIT, XPBD_NO_HIT, +inf, zeros}.  Quotients and square roots are correctly rounded, there is no fused
+ * multiply-add; dot, cross and the frame products are as everywhere else.
+ *
+ * Errors (host variants, before any device work; the outputs are untouched): XPBD_E_INVALID for a NULL world, NULL queries /
+ * hits with n_queries > 0, unknown flags (XPBD_QUERY_TERRAIN included), a nonzero `reserved`, no polytopes set, no bodies
+ * resident.  n_queries == 0 is XPBD_OK.  A distance query changes no body, list, mask, report, history entry or plan: stepping
+ * after it gives the same bits as stepping without it.  Every mode accepts it.
+ *
+ * Method: the per-call grid of the ray casts; a group of lanes per query walks the cells its bounding sphere covers, then those
+ * the sphere grown by min(max_distance, best so far) covers.  A query that reaches further than a wide sweep's volume may
+ * (+inf included) looks at every body.  With XPBD_DISTANCE_BRUTE_FORCE, or for at most XPBD_DISTANCE_BRUTE_FORCE_QUERIES
+ * queries, every body is looked at and no grid is built.  Same bits either way.
+ * ------------------------------------------------------------------------- */
+#define XPBD_DISTANCE_BRUTE_FORCE 1u          /* diagnostics: every query against every body, no grid */
+#define XPBD_DISTANCE_MASKED      2u          /* test xpbd_distance_query.mask against the bodies' filter groups */
+#define XPBD_DISTANCE_OVERLAP     3u          /* xpbd_distance_hit.feature when the volume and the body are not separated */
+#define XPBD_DISTANCE_POINT       0xFFFFFFFFu /* xpbd_distance_query.shape: the volume is the single point `position` */
+#define XPBD_DISTANCE_BRUTE_FORCE_QUERIES 8u  /* calls with at most this many queries take the brute-force path anyway */
+
+typedef struct xpbd_distance_query {  /* 80 bytes */
+    double   position[3];             /* frame of the volume: x_world = position + rotation * x_shape */
+    double   rotation[4];             /* {s, x, y, z}, taken as given (the caller keeps it a unit quaternion) */
+    double   max_distance;            /* bodies further away do not answer; may be +inf */
+    uint32_t shape;                   /* index into the table of xpbd_world_set_polytopes, or XPBD_DISTANCE_POINT */
+    uint32_t ignore_body;             /* never answers (XPBD_NO_HIT: none) */
+    uint32_t mask;                    /* with XPBD_DISTANCE_MASKED: body b answers only if (group_b & mask) != 0 */
+    uint32_t reserved;                /* must be 0 */
+} xpbd_distance_query;
+
+typedef struct xpbd_distance_hit {    /* 96 bytes */
+    uint32_t body;                    /* XPBD_NO_HIT: nothing within max_distance */
+    uint32_t feature;                 /* XPBD_FEATURE_* (A = the volume, B = the body) or XPBD_DISTANCE_OVERLAP */
+    uint32_t index_a;                 /* FACE_B: vertex of the volume; FACE_A: face of the volume; EDGES: edge of the volume */
+    uint32_t index_b;                 /* FACE_B: face of the body; FACE_A: vertex of the body; EDGES: edge of the body */
+    double   distance;                /* 0 for XPBD_DISTANCE_OVERLAP */
+    double   point_a[3];              /* world space, on the volume */
+    double   point_b[3];              /* world space, on the body */
+    double   normal[3];               /* (point_a - point_b) / distance: from the body to the volume; (0,0,0) at distance 0 */
+} xpbd_distance_hit;
+
+/* Host arrays; checks everything before any device work and waits for the result. */
+int  xpbd_world_distance(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags,
+                         xpbd_distance_hit *hits);
+/* Device arrays; stream-ordered on the world's stream, returns before completion (it waits only when its scratch has to
+ * grow).  `reserved` is not checked. */
+int  xpbd_world_distance_device(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags,
+                                xpbd_distance_hit *dev_hits);
+/* Collective: every rank passes the same queries and gets all hits.  Every shard answers for the bodies it OWNS; body and
+ * ignore_body are global indices.  Same bits as one xpbd_world over the same bodies. */
+int  xpbd_multi_world_distance(xpbd_multi_world *mw, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags,
+                               xpbd_distance_hit *hits);
+
+/* ---------------------------------------------------------------------------
  * Terrain in the scene queries (EXTENSION): with XPBD_QUERY_TERRAIN in `flags` the heightfield of xpbd_world_set_terrain
  * answers a ray cast, an overlap query and a sweep next to the bodies.  One flag value serves the three families, above each
  * family's own bits.  Accepted by xpbd_world_raycast, _raycast_masked, _raycast_device, _raycast_masked_device,
