@@ -65,6 +65,7 @@ ABI_SYMBOLS = [
     "xpbd_world_overlap", "xpbd_world_overlap_device", "xpbd_multi_world_overlap",
     "xpbd_world_sweep", "xpbd_world_sweep_device", "xpbd_multi_world_sweep",
     "xpbd_world_distance", "xpbd_world_distance_device", "xpbd_multi_world_distance",
+    "xpbd_world_terrain_distance", "xpbd_world_terrain_distance_device",
     "xpbd_world_remove_bodies", "xpbd_world_remove_bodies_device", "xpbd_world_add_bodies",
     "xpbd_world_set_terrain", "xpbd_world_sample_terrain",
 ]
@@ -445,6 +446,8 @@ def hip_lib():
             L.xpbd_world_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
             L.xpbd_world_distance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
             L.xpbd_multi_world_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.xpbd_world_terrain_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.xpbd_world_terrain_distance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         try:
@@ -771,6 +774,18 @@ class World:
     def distance_device(self, queries_ptr, n, hits_ptr, flags=0):
         """Device arrays of n xpbd_distance_query and n xpbd_distance_hit, stream-ordered on the world's stream."""
         _check(hip_lib().xpbd_world_distance_device(self._h, C.c_void_p(queries_ptr), n, flags, C.c_void_p(hits_ptr)))
+
+    def terrain_distance(self, queries, flags=0):
+        """DISTANCE_HIT_DTYPE records of the feature of the TERRAIN's surface nearest to every convex volume or point
+        (DISTANCE_QUERY_DTYPE records, see distances(); ignore_body and mask are not read): body HIT_TERRAIN, the distance, the
+        two closest points and the normal from the ground to the volume; DISTANCE_OVERLAP at distance 0 where a vertex is under
+        the ground or a terrain edge enters the volume.  index_b numbers the triangle (FACE_B), sample (FACE_A) or terrain edge
+        (EDGES).  The world's nearest thing is the smaller distance of this and distance(); a body wins a tie."""
+        return _distance(hip_lib().xpbd_world_terrain_distance, self._h, queries, flags)
+
+    def terrain_distance_device(self, queries_ptr, n, hits_ptr, flags=0):
+        """Device arrays of n xpbd_distance_query and n xpbd_distance_hit, stream-ordered on the world's stream; never waits."""
+        _check(hip_lib().xpbd_world_terrain_distance_device(self._h, C.c_void_p(queries_ptr), n, flags, C.c_void_p(hits_ptr)))
 
     # body edits (include/xpbd.h, "Body EDITS"): forces, impulses and state of resident bodies
     def set_external_wrench(self, indices=None, force=None, torque=None):

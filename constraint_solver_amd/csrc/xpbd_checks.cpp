@@ -6,6 +6,7 @@
 
 #include "xpbd_checks.hpp"
 #include "xpbd_checks_distance.hpp"
+#include "xpbd_checks_terrain_distance.hpp"
 #include "xpbd_error.h"
 
 namespace xpbd {
@@ -278,6 +279,21 @@ int check_distance(const char *who, const QueryTarget &t, const xpbd_distance_qu
             return set_error(XPBD_E_INVALID, "%s: query %u has reserved = %u (must be 0)", who, q, queries[q].reserved);
     if (t.n_bodies == 0)
         return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
+    return XPBD_OK;
+}
+
+int check_terrain_distance(const char *who, const QueryTarget &t, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags,
+                           const void *hits, bool host)
+{
+    if (n_queries && (!queries || !hits))
+        return set_error(XPBD_E_INVALID, "%s: NULL queries or hits", who);
+    if (flags & ~(XPBD_DISTANCE_BRUTE_FORCE | XPBD_DISTANCE_MASKED)) // (XPBD_QUERY_TERRAIN too: the call is the terrain's already)
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    for (uint32_t q = 0; host && q < n_queries; ++q)
+        if (queries[q].reserved)
+            return set_error(XPBD_E_INVALID, "%s: query %u has reserved = %u (must be 0)", who, q, queries[q].reserved);
+    if (!t.has_terrain)
+        return set_error(XPBD_E_INVALID, "%s: the world has no terrain (xpbd_world_set_terrain)", who);
     return XPBD_OK;
 }
 

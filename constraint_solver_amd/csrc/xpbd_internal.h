@@ -11,6 +11,7 @@
 
 #include "xpbd_checks.hpp" // the argument checks both worlds share
 #include "xpbd_checks_distance.hpp"
+#include "xpbd_checks_terrain_distance.hpp"
 #include "xpbd_error.h"
 
 namespace xpbd {
@@ -177,6 +178,10 @@ int distance_enqueue(xpbd_world *w, const xpbd_distance_query *dev_queries, uint
                      const uint32_t *dev_global_id);
 int distance_host(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits,
                   const uint32_t *dev_global_id);
+// Distance queries against the world's terrain (include/xpbd.h, "Terrain in the distance queries"): one kernel that needs no
+// scratch, so the stream-ordered form never waits; the host form goes through the staging of the other queries.
+int terrain_distance_enqueue(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *dev_hits);
+int terrain_distance_host(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits);
 // The current frame's contact report of a shard of the multi-GPU world (include/xpbd.h, "Contact REPORTS"): only the pairs whose
 // lower body has dev_owned[slot] != 0, bodies named by dev_global_id[slot] (device arrays of the world's body count; global ids
 // ascending with the slot).  Waits.  A world without bodies reports nothing.

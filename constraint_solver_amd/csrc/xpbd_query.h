@@ -111,7 +111,7 @@ hipError_t launch_sweep(const BodyArrays &b, const PolytopeTables &t, const uint
 // sphere covers and then those the sphere grown by min(max_distance, best so far) covers, decides every candidate -- the overlap
 // query's decision, the vertex-face candidates, the edge pairs -- and keeps the minimum under (distance, index).  The brute-force
 // path, and a query that reaches further than kSweepReach cell edges, visits every body instead.  A distance query's scratch is
-// an overlap's (overlap_scratch_bytes with the number of queries).  No terrain.
+// an overlap's (overlap_scratch_bytes with the number of queries).  No terrain: launch_terrain_distance below is a call of its own.
 hipError_t launch_distance(const BodyArrays &b, const PolytopeTables &t, const uint32_t *global_id, const uint2 *filter, const void *queries,
                            uint32_t n_queries, bool masked, bool brute, const QueryScratch &s, void *hits, hipStream_t stream);
 
@@ -132,5 +132,20 @@ hipError_t launch_terrain_sweeps(const Terrain &terrain, const PolytopeTables &t
                                  void *hits, hipStream_t stream);
 hipError_t launch_terrain_overlap(const Terrain &terrain, const PolytopeTables &t, const void *queries, uint32_t n_queries, bool fill, const double *qrec,
                                   uint32_t *offsets, void *hits, uint32_t cap, hipStream_t stream);
+
+// ---- the terrain in the distance queries (include/xpbd.h, "Terrain in the distance queries"; xpbd_terrain_query.hip) -----------
+// A call of its own (xpbd_world_terrain_distance), not a pass after launch_distance.  What the kernel reads of the field: the
+// stepper's Terrain, unchanged (its kernels take it by value), and the heights the plane table was made from, ny rows of nx.
+struct TerrainHeights {
+    Terrain tr;
+    const double *heights;
+};
+// One kernel on `stream`: a group of 8 lanes per query walks rings of samples around the one under the volume's centre
+// (`brute`: every sample), each lane deciding what its sample owns -- two triangles, the sample, up to three edges -- and the
+// group keeps the minimum under (d2, class, terrain feature, volume index).  It writes hits[0 .. n_queries) and nothing else: no
+// atomics, no scratch of its own, so the device variant never waits.  `t` may be an empty table (n_shapes == 0): only point
+// queries then find anything.
+hipError_t launch_terrain_distance(const TerrainHeights &terrain, const PolytopeTables &t, const void *queries, uint32_t n_queries, bool brute, void *hits,
+                                   hipStream_t stream);
 
 } // namespace xpbd

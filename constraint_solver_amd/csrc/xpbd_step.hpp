@@ -135,8 +135,8 @@ __device__ __forceinline__ uint32_t ground_mask_table(const Frame &cur, const do
 
 // The terrain's plane under world point x (include/xpbd.h, "TERRAIN", Lookup): false when x is outside the field (a NaN is).
 // One division per axis, then one 32-byte load from the cell's 64-byte record: the planes themselves were evaluated once, by
-// k_terrain_planes, with the header's formulas.
-__device__ __forceinline__ bool terrain_plane(const Terrain &t, const Vec3 &x, Plane &plane)
+// k_terrain_planes, with the header's formulas.  (Host code too: the terrain distance walk's CPU check runs it.)
+XPBD_HD bool terrain_plane(const Terrain &t, const Vec3 &x, Plane &plane)
 {
     const double u = (x.x - t.x0) / t.dx, v = (x.y - t.y0) / t.dy;
     if (!(u >= 0.0 && v >= 0.0))

@@ -5,11 +5,13 @@
 // ray's answer is the minimum over all triangles under (t, triangle).  A triangle's t is a function of the ray and the triangle
 // alone, and neighbouring prisms compute the t of their shared wall and diagonal from the same expression, so the walk below
 // -- which only chooses which cells are looked at -- cannot change a bit of the answer.  Nothing here writes anything but the
-// callers' result arrays: no atomics, no LDS, no scratch memory of its own.
+// callers' result arrays: no atomics, no scratch memory of its own (the distance pass stages the volume's vertices in LDS).
+// The distance pass (xpbd_world_terrain_distance) is a call of its own, not a flag: see "distances" below.
 #include <cmath>
 #include <cstdint>
 
 #include "xpbd_query.h"
+#include "xpbd_query_shared.hpp"
 #include "xpbd_step.hpp"
 
 namespace xpbd {
@@ -35,7 +37,16 @@ struct TerrainBest {
     uint32_t tri;
 };
 
-XPBD_HD bool finite3(Vec3 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
+// (isfinite by the name each side of the compilation knows it under: the distance walk's CPU check calls these on the host)
+XPBD_HD bool finite1(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return isfinite(x);
+#else
+    return std::isfinite(x);
+#endif
+}
+XPBD_HD bool finite3(Vec3 v) { return finite1(v.x) && finite1(v.y) && finite1(v.z); }
 
 // The interval of one constraint list: the header's (s, v) rule and the slab rule of clip_to_grid (xpbd_query.hip).
 struct Interval {
@@ -343,6 +354,376 @@ __global__ void __launch_bounds__(kBlock) k_terrain_overlap(Terrain tr, Polytope
     }
 }
 
+// ---- distances: the terrain feature nearest to a convex volume or a point ---------------------------------------------------------
+// Semantics: include/xpbd.h, "Terrain in the distance queries".  The answer is the minimum over ALL features of the surface under
+// the total order (d2, class, terrain feature number, volume index); a candidate's d2 is a function of the query and the feature
+// alone, and every feature has one number and one owner -- sample (i, j) owns the two triangles of cell (i, j), itself, and the
+// three edges that start at it -- so the walk below, which only chooses the samples, cannot change a bit of the answer.
+// (The routines up to terrain_distance_walk and terrain_distance_record are host code too: a CPU build runs the walk against the
+// brute-force minimum.)
+#ifndef XPBD_TERRAIN_DISTANCE_LANES
+#define XPBD_TERRAIN_DISTANCE_LANES 8      // measured against 16, 32 and 64 ("Terrain in the distance queries"; a build flag for that A/B only)
+#endif
+constexpr uint32_t kDistanceLanes = XPBD_TERRAIN_DISTANCE_LANES; // lanes per query; the samples of a ring are shared out among them
+static_assert(kDistanceLanes == 8 || kDistanceLanes == 16 || kDistanceLanes == 32 || kDistanceLanes == 64, "a group is a power-of-two part of a wave");
+constexpr uint64_t kNoCandidate = ~0ull;   // DistanceBest::key before anything counted
+constexpr double kNotSeparated = -1.0;     // DistanceBest::d2 of rule 1: below every squared distance, so it wins every minimum
+
+// The minimum so far.  key = class << 56 | terrain feature number << 16 | the volume's index (vertex, face or edge): the number of
+// a feature is below 2^24 (XPBD_MAX_TERRAIN_SAMPLES * 3), the volume's index below 2^16.
+struct DistanceBest {
+    double d2;
+    uint64_t key;
+
+    XPBD_HD void offer(double x, uint32_t cls, uint32_t feature, uint32_t index)
+    {
+        const uint64_t k = (uint64_t)cls << 56 | (uint64_t)feature << 16 | index;
+        if (x < d2 || (x == d2 && key != kNoCandidate && k < key)) { // (a NaN never replaces; nor does +inf the empty minimum)
+            d2 = x;
+            key = k;
+        }
+    }
+};
+static_assert(3ull * XPBD_MAX_TERRAIN_SAMPLES <= (1ull << 24), "a terrain feature's number fits 24 bits of the key");
+
+// The minimum over the L lanes of a group, left in every lane.  (A host build is a group of one lane.)
+template <uint32_t L>
+XPBD_HD void group_min(DistanceBest &b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    for (uint32_t off = L >> 1; off; off >>= 1) {
+        const double od = __shfl_xor(b.d2, off, L);
+        const unsigned long long ok = __shfl_xor((unsigned long long)b.key, off, L);
+        if (od < b.d2 || (od == b.d2 && ok < b.key))
+            b = DistanceBest{od, ok};
+    }
+#else
+    (void)b; // (a CPU program calls the walk with L = 1)
+#endif
+}
+
+// The volume of one query as the candidates see it.
+struct DistanceVolume {
+    Frame fa, fa_inv;
+    ShapeDesc da;   // the point volume: one vertex, no faces, one edge from it to itself
+    uint32_t shape;
+    bool point;
+    Vec3 c;         // centre and radius of the bounding sphere, as k_distance_queries forms them
+    double rs;
+    double dmax;
+    bool valid;     // the query can find something: a shape of the table or the point, a finite frame, a max_distance >= 0
+};
+
+XPBD_HD DistanceVolume load_distance_volume(const PolytopeTables &t, const xpbd_distance_query &x)
+{
+    DistanceVolume vol{};
+    vol.fa = Frame{Vec3{x.position[0], x.position[1], x.position[2]}, Quat{x.rotation[0], x.rotation[1], x.rotation[2], x.rotation[3]}};
+    vol.shape = x.shape;
+    vol.point = x.shape == XPBD_DISTANCE_POINT;
+    vol.dmax = x.max_distance;
+    vol.c = Vec3{0.0, 0.0, 0.0};
+    vol.rs = -1.0;
+    vol.valid = false;
+    if (vol.point || x.shape < t.n_shapes) {
+        vol.da = vol.point ? ShapeDesc{0, 1, 0, 0, 0, 1, 0, 0} : t.desc[x.shape];
+        vol.c = vol.fa.position;
+        double rs = 0.0;
+        if (!vol.point) {
+            const double *cc = t.centroids + 3 * (size_t)x.shape;
+            vol.c = vol.fa * Vec3{cc[0], cc[1], cc[2]};
+            rs = t.radii[x.shape];
+        }
+        const bool finite = finite3(vol.fa.position) && finite1(vol.fa.rotation.s) && finite1(vol.fa.rotation.x) && finite1(vol.fa.rotation.y) &&
+                            finite1(vol.fa.rotation.z) && finite3(vol.c);
+        if (finite && vol.dmax >= 0.0 && rs >= 0.0 && vol.da.n_verts <= XPBD_MAX_SHAPE_VERTS) { // (a NaN max_distance fails; +inf passes)
+            vol.rs = rs;
+            vol.valid = true;
+            vol.fa_inv = inverse(vol.fa);
+        }
+    }
+    return vol;
+}
+
+// World vertex v of the volume: aw_v = fa * a_v; the point volume's is `position` itself.
+XPBD_HD Vec3 volume_vertex(const PolytopeTables &t, const DistanceVolume &vol, uint32_t v)
+{
+    if (vol.point)
+        return vol.fa.position;
+    const double *a = t.verts + 3 * (size_t)(vol.da.vert0 + v);
+    return vol.fa * Vec3{a[0], a[1], a[2]};
+}
+
+XPBD_HD void volume_edge(const PolytopeTables &t, const DistanceVolume &vol, uint32_t e, uint32_t &a0, uint32_t &a1)
+{
+    a0 = a1 = 0;
+    if (!vol.point) {
+        const uint32_t *ea = t.edges + 2 * (size_t)(vol.da.edge0 + e);
+        a0 = ea[0], a1 = ea[1];
+    }
+}
+
+XPBD_HD Vec3 terrain_sample(const TerrainHeights &tf, uint32_t i, uint32_t j)
+{
+    return Vec3{tf.tr.x0 + (double)i * tf.tr.dx, tf.tr.y0 + (double)j * tf.tr.dy, tf.heights[(size_t)j * tf.tr.nx + i]};
+}
+
+// The far end of terrain edge (i, j, e): 0 along x, 1 along y, 2 the diagonal.
+XPBD_HD Vec3 terrain_edge_end(const TerrainHeights &tf, uint32_t i, uint32_t j, uint32_t e)
+{
+    return terrain_sample(tf, e == 1 ? i : i + 1, e == 0 ? j : j + 1);
+}
+
+// Rule 2 (a) for one vertex and one triangle: whether the candidate counts, with h and the foot.
+XPBD_HD bool vertex_over_triangle(const Terrain &tr, uint32_t i, uint32_t j, uint32_t upper, const Plane &pl, Vec3 p, double &h, Vec3 &foot)
+{
+    h = dot(pl.normal, p) - pl.displacement;
+    if (!(h >= 0.0))
+        return false;
+    foot = p - h * pl.normal;
+    const double xi = tr.x0 + (double)i * tr.dx, xi1 = tr.x0 + (double)(i + 1) * tr.dx;
+    const double yj = tr.y0 + (double)j * tr.dy, yj1 = tr.y0 + (double)(j + 1) * tr.dy;
+    if (!(xi <= foot.x && foot.x <= xi1 && yj <= foot.y && foot.y <= yj1))
+        return false;
+    const double g = (foot.x - xi) * tr.dy - (foot.y - yj) * tr.dx;
+    return upper ? g <= 0.0 : g >= 0.0;
+}
+
+XPBD_HD Plane triangle_plane(const Terrain &tr, uint32_t tri)
+{
+    const double *pl = tr.planes + (size_t)tri * 4;
+    return Plane{Vec3{pl[0], pl[1], pl[2]}, pl[3]};
+}
+
+// Everything sample (i, j) owns against the volume: its two triangles (a), itself (b), its up to three edges (c) and rule 1 (ii).
+// aw: the volume's world vertices.
+XPBD_HD void distance_sample(const TerrainHeights &tf, const PolytopeTables &t, const DistanceVolume &vol, const Vec3 *aw, uint32_t i, uint32_t j,
+                             DistanceBest &best)
+{
+    const Terrain &tr = tf.tr;
+    const bool has_x = i + 1u < tr.nx, has_y = j + 1u < tr.ny;
+    const uint32_t sample = j * tr.nx + i;
+    if (has_x && has_y) { // (a)
+        const uint32_t cell = j * (tr.nx - 1u) + i;
+        for (uint32_t upper = 0; upper < 2; ++upper) {
+            const uint32_t tri = 2u * cell + upper;
+            const Plane pl = triangle_plane(tr, tri);
+            for (uint32_t v = 0; v < vol.da.n_verts; ++v) {
+                double h;
+                Vec3 foot;
+                if (vertex_over_triangle(tr, i, j, upper, pl, aw[v], h, foot))
+                    best.offer(h * h, 0u, tri, v);
+            }
+        }
+    }
+    const Vec3 P = terrain_sample(tf, i, j);
+    if (!vol.point) { // (b)
+        const Vec3 p = vol.fa_inv * P;
+        for (uint32_t f = 0; f < vol.da.n_faces; ++f) {
+            double h;
+            Vec3 foot;
+            if (vertex_over_face(t, vol.da.vert0, vol.da.face0 + f, p, INFINITY, h, foot))
+                best.offer(h * h, 1u, sample, f);
+        }
+    }
+    for (uint32_t e = 0; e < 3; ++e) { // (c), and rule 1 (ii)
+        if (!(e == 0 ? has_x : (e == 1 ? has_y : has_x && has_y)))
+            continue;
+        const Vec3 Q = terrain_edge_end(tf, i, j, e);
+        if (!vol.point) {
+            const Ray ray{P, Q - P, 1.0, XPBD_NO_HIT, true};
+            const BodyQ q{vol.fa_inv.position, vol.fa_inv.rotation, vol.c, vol.rs};
+            double t_hit;
+            uint32_t face;
+            if (ray_body(ray, q, t, vol.shape, t_hit, face))
+                best = DistanceBest{kNotSeparated, 0ull};
+        }
+        for (uint32_t k = 0; k < vol.da.n_edges; ++k) {
+            uint32_t a0, a1;
+            volume_edge(t, vol, k, a0, a1);
+            Vec3 ca, cb;
+            best.offer(segment_closest(aw[a0], aw[a1], P, Q, ca, cb), 2u, 3u * sample + e, k);
+        }
+    }
+}
+
+// floor((c - c0) / dc) clamped into the samples 0 .. n - 1 (a NaN: 0).
+XPBD_HD int32_t centre_sample(double c, double c0, double dc, uint32_t n)
+{
+    const double u = (c - c0) / dc, top = (double)(n - 1u);
+    return u >= 0.0 ? (u < top ? (int32_t)floor(u) : (int32_t)(n - 1u)) : 0;
+}
+
+// The minimum of one query by a group of L lanes (lane = this one's number in it); every lane returns it.  best.d2 ==
+// kNotSeparated: rule 1; best.key == kNoCandidate: nothing counted.  BRUTE: every sample.  Otherwise rings of samples around the
+// one under the volume's centre.  Ring r >= 1 and all beyond it lie outside the open rectangle between the borders x(ci - r + 1),
+// x(ci + r), y(cj - r + 1), y(cj + r) -- of those sides on which the field still has samples -- so once the bounding sphere is
+// further inside than min(max_distance, best so far) from every such side, no ring can hold the minimum or a tie with it.  The
+// test carries the conservative slack of the body pass; it is never part of the definition.  At most max(nx, ny) rings: a +inf
+// query, a NaN bound and a volume beside the field end with the field.
+template <bool BRUTE, uint32_t L>
+XPBD_HD DistanceBest terrain_distance_walk(const TerrainHeights &tf, const PolytopeTables &t, const DistanceVolume &vol, const Vec3 *aw, uint32_t lane,
+                                           uint32_t *looked_at = nullptr)
+{
+    const Terrain &tr = tf.tr;
+    DistanceBest best{INFINITY, kNoCandidate};
+    // rule 1 (i): a vertex under the plane of the stepper's lookup
+    for (uint32_t v = lane; v < vol.da.n_verts; v += L) {
+        Plane pl;
+        if (terrain_plane(tr, aw[v], pl) && distance(pl, aw[v]) < 0.0)
+            best = DistanceBest{kNotSeparated, 0ull};
+    }
+    group_min<L>(best);
+    if (best.d2 < 0.0)
+        return best;
+    if (BRUTE) {
+        const uint32_t samples = tr.nx * tr.ny;
+        for (uint32_t s = lane; s < samples; s += L)
+            distance_sample(tf, t, vol, aw, s % tr.nx, s / tr.nx, best);
+        group_min<L>(best);
+        return best;
+    }
+    const int32_t nx = (int32_t)tr.nx, ny = (int32_t)tr.ny;
+    const int32_t ci = centre_sample(vol.c.x, tr.x0, tr.dx, tr.nx), cj = centre_sample(vol.c.y, tr.y0, tr.dy, tr.ny);
+    const int32_t rings = nx > ny ? nx : ny;
+    if (lane == 0)
+        distance_sample(tf, t, vol, aw, (uint32_t)ci, (uint32_t)cj, best);
+    if (looked_at)
+        *looked_at += 1u;
+    group_min<L>(best);
+    for (int32_t r = 1; r < rings && !(best.d2 < 0.0); ++r) {
+        const bool left = ci >= r, right = ci + r <= nx - 1, low = cj >= r, high = cj + r <= ny - 1;
+        if (!(left || right || low || high))
+            break;
+        double g = INFINITY; // how far inside the nearest side the centre lies
+        if (left) {
+            const double s = vol.c.x - (tr.x0 + (double)(ci - r + 1) * tr.dx);
+            g = s < g ? s : g;
+        }
+        if (right) {
+            const double s = (tr.x0 + (double)(ci + r) * tr.dx) - vol.c.x;
+            g = s < g ? s : g;
+        }
+        if (low) {
+            const double s = vol.c.y - (tr.y0 + (double)(cj - r + 1) * tr.dy);
+            g = s < g ? s : g;
+        }
+        if (high) {
+            const double s = (tr.y0 + (double)(cj + r) * tr.dy) - vol.c.y;
+            g = s < g ? s : g;
+        }
+        const double so_far = sqrt(best.d2), reach = vol.rs + (so_far < vol.dmax ? so_far : vol.dmax);
+        if (g > 0.0 && g * g > reach * reach * kSphereSlack + 1e-12 * (g * g))
+            break;
+        // the ring inside the field: its two rows, then its two columns between them
+        const int32_t ilo = left ? ci - r : 0, ihi = right ? ci + r : nx - 1;
+        const int32_t jlo = low ? cj - r + 1 : 0, jhi = high ? cj + r - 1 : ny - 1;
+        const int32_t row = ihi - ilo + 1, col = jhi >= jlo ? jhi - jlo + 1 : 0;
+        const int32_t n0 = low ? row : 0, n1 = high ? row : 0, n2 = left ? col : 0, n3 = right ? col : 0;
+        const int32_t total = n0 + n1 + n2 + n3;
+        for (int32_t k = (int32_t)lane; k < total; k += (int32_t)L) {
+            int32_t i, j;
+            if (k < n0)
+                i = ilo + k, j = cj - r;
+            else if (k < n0 + n1)
+                i = ilo + (k - n0), j = cj + r;
+            else if (k < n0 + n1 + n2)
+                i = ci - r, j = jlo + (k - n0 - n1);
+            else
+                i = ci + r, j = jlo + (k - n0 - n1 - n2);
+            distance_sample(tf, t, vol, aw, (uint32_t)i, (uint32_t)j, best);
+        }
+        if (looked_at)
+            *looked_at += (uint32_t)total;
+        group_min<L>(best);
+    }
+    return best;
+}
+
+// The record of a query's minimum: the winning candidate once more, by the expressions that measured it.
+XPBD_HD xpbd_distance_hit terrain_distance_record(const TerrainHeights &tf, const PolytopeTables &t, const DistanceVolume &vol, const Vec3 *aw,
+                                                  const DistanceBest &best)
+{
+    xpbd_distance_hit h;
+    h.body = XPBD_NO_HIT;
+    h.feature = 0;
+    h.index_a = h.index_b = XPBD_NO_HIT;
+    h.distance = INFINITY;
+    h.point_a[0] = h.point_a[1] = h.point_a[2] = 0.0;
+    h.point_b[0] = h.point_b[1] = h.point_b[2] = 0.0;
+    h.normal[0] = h.normal[1] = h.normal[2] = 0.0;
+    if (!vol.valid || best.key == kNoCandidate)
+        return h;
+    if (best.d2 < 0.0) {
+        h.body = XPBD_HIT_TERRAIN;
+        h.feature = XPBD_DISTANCE_OVERLAP;
+        h.distance = 0.0;
+        return h;
+    }
+    const double dist = sqrt(best.d2);
+    if (!(dist <= vol.dmax))
+        return h;
+    const uint32_t cls = (uint32_t)(best.key >> 56), feature = (uint32_t)(best.key >> 16) & 0xFFFFFFu, index = (uint32_t)best.key & 0xFFFFu;
+    const Terrain &tr = tf.tr;
+    Vec3 pa{0.0, 0.0, 0.0}, pb{0.0, 0.0, 0.0};
+    double hh = 0.0;
+    if (cls == 0u) {
+        const uint32_t cell = feature >> 1, j = cell / (tr.nx - 1u), i = cell - j * (tr.nx - 1u);
+        pa = aw[index];
+        vertex_over_triangle(tr, i, j, feature & 1u, triangle_plane(tr, feature), pa, hh, pb);
+        h.feature = XPBD_FEATURE_FACE_B;
+    } else if (cls == 1u) {
+        const uint32_t j = feature / tr.nx, i = feature - j * tr.nx;
+        Vec3 foot{0.0, 0.0, 0.0};
+        pb = terrain_sample(tf, i, j);
+        vertex_over_face(t, vol.da.vert0, vol.da.face0 + index, vol.fa_inv * pb, INFINITY, hh, foot);
+        pa = vol.fa * foot;
+        h.feature = XPBD_FEATURE_FACE_A;
+    } else {
+        const uint32_t sample = feature / 3u, e = feature - 3u * sample, j = sample / tr.nx, i = sample - j * tr.nx;
+        uint32_t a0, a1;
+        volume_edge(t, vol, index, a0, a1);
+        segment_closest(aw[a0], aw[a1], terrain_sample(tf, i, j), terrain_edge_end(tf, i, j, e), pa, pb);
+        h.feature = XPBD_FEATURE_EDGES;
+    }
+    h.body = XPBD_HIT_TERRAIN;
+    h.index_a = index, h.index_b = feature;
+    h.distance = dist;
+    h.point_a[0] = pa.x, h.point_a[1] = pa.y, h.point_a[2] = pa.z;
+    h.point_b[0] = pb.x, h.point_b[1] = pb.y, h.point_b[2] = pb.z;
+    if (dist != 0.0) {
+        const Vec3 n = (pa - pb) * (1.0 / dist);
+        h.normal[0] = n.x, h.normal[1] = n.y, h.normal[2] = n.z;
+    }
+    return h;
+}
+
+// One group of L lanes per query; lane 0 writes the record.
+template <bool BRUTE, uint32_t L>
+__global__ void __launch_bounds__(kBlock) k_terrain_distance(TerrainHeights tf, PolytopeTables t, const xpbd_distance_query *__restrict__ queries,
+                                                             uint32_t n_queries, xpbd_distance_hit *__restrict__ hits)
+{
+    constexpr uint32_t PB = kBlock / L;
+    __shared__ Vec3 s_aw[PB][XPBD_MAX_SHAPE_VERTS];
+    const uint32_t group = threadIdx.x / L, lane = threadIdx.x % L;
+    const uint32_t q = blockIdx.x * PB + group;
+    const bool live = q < n_queries;
+    DistanceVolume vol{};
+    if (live) {
+        vol = load_distance_volume(t, queries[q]);
+        if (vol.valid)
+            for (uint32_t v = lane; v < vol.da.n_verts; v += L)
+                s_aw[group][v] = volume_vertex(t, vol, v);
+    }
+    __syncthreads();
+    if (!live)
+        return;
+    DistanceBest best{INFINITY, kNoCandidate};
+    if (vol.valid)
+        best = terrain_distance_walk<BRUTE, L>(tf, t, vol, s_aw[group], lane);
+    if (lane == 0)
+        hits[q] = terrain_distance_record(tf, t, vol, s_aw[group], best);
+}
+
 } // namespace
 
 hipError_t launch_terrain_rays(const Terrain &terrain, const void *rays, uint32_t n_rays, bool brute, void *hits, hipStream_t stream)
@@ -384,6 +765,21 @@ hipError_t launch_terrain_overlap(const Terrain &terrain, const PolytopeTables &
         hipLaunchKernelGGL(k_terrain_overlap<true>, dim3(blocks_of(n_queries)), dim3(kBlock), 0, stream, terrain, t, q, n_queries, qrec, offsets, h, cap);
     else
         hipLaunchKernelGGL(k_terrain_overlap<false>, dim3(blocks_of(n_queries)), dim3(kBlock), 0, stream, terrain, t, q, n_queries, qrec, offsets, h, cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_terrain_distance(const TerrainHeights &terrain, const PolytopeTables &t, const void *queries, uint32_t n_queries, bool brute, void *hits,
+                                   hipStream_t stream)
+{
+    if (n_queries == 0)
+        return hipSuccess;
+    const xpbd_distance_query *q = static_cast<const xpbd_distance_query *>(queries);
+    xpbd_distance_hit *h = static_cast<xpbd_distance_hit *>(hits);
+    const dim3 blocks(blocks_of(n_queries, kBlock / kDistanceLanes));
+    if (brute)
+        hipLaunchKernelGGL((k_terrain_distance<true, kDistanceLanes>), blocks, dim3(kBlock), 0, stream, terrain, t, q, n_queries, h);
+    else
+        hipLaunchKernelGGL((k_terrain_distance<false, kDistanceLanes>), blocks, dim3(kBlock), 0, stream, terrain, t, q, n_queries, h);
     return hipGetLastError();
 }
 

@@ -818,6 +818,7 @@ try {
     if (!hf) {
         w->terrain = xpbd::Terrain{};
         w->tr_planes.release();
+        w->tr_heights.release();
         return XPBD_OK;
     }
     // heights and the new table in blocks of their own: the present table stays in force until nothing can fail any more
@@ -828,6 +829,7 @@ try {
     XPBD_HIP_TRY(xpbd::launch_terrain_planes(heights.as<double>(), t, planes.as<double>(), w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     w->tr_planes = std::move(planes);
+    w->tr_heights = std::move(heights);
     t.planes = w->tr_planes.as<double>();
     w->terrain = t;
     return XPBD_OK;

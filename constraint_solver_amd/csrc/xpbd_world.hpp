@@ -342,6 +342,7 @@ struct xpbd_world {
     // schedule (the fused pair-solve + integrate + ground kernel has no terrain form).
     xpbd::Terrain terrain{};
     DeviceBuffer tr_planes;
+    DeviceBuffer tr_heights; // the heights the table was made from, ny rows of nx: the terrain distance queries read the samples
     TerrainStaging terrain_staging; // of xpbd_world_sample_terrain
     // scene queries (xpbd_world_raycast*, xpbd_world_overlap*): scratch of one call, staging of the host variants' arrays
     xpbd::SceneQueryScratch query;

@@ -155,6 +155,26 @@ int distance_host(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_
     });
 }
 
+int terrain_distance_enqueue(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *dev_hits)
+{
+    if (n_queries == 0)
+        return XPBD_OK;
+    if (int rc = bind_device(w))
+        return rc;
+    // (without polytopes the shape table is empty: every shape index is outside it, and only the point volume finds anything)
+    const PolytopeTables tables = w->has_topology ? w->tables() : PolytopeTables{};
+    XPBD_HIP_TRY(launch_terrain_distance(TerrainHeights{w->terrain, w->tr_heights.as<double>()}, tables, dev_queries, n_queries,
+                                         (flags & XPBD_DISTANCE_BRUTE_FORCE) != 0, dev_hits, w->stream));
+    return XPBD_OK;
+}
+
+int terrain_distance_host(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits)
+{
+    return query_host(w, queries, n_queries, hits, [&](const xpbd_distance_query *dev_queries, xpbd_distance_hit *dev_hits) {
+        return terrain_distance_enqueue(w, dev_queries, n_queries, flags, dev_hits);
+    });
+}
+
 } // namespace xpbd
 
 extern "C" {
@@ -265,6 +285,25 @@ try {
     if (int rc = xpbd::check_distance("xpbd_world_distance_device", query_target(w), dev_queries, n_queries, flags, dev_hits, false))
         return rc;
     return xpbd::distance_enqueue(w, dev_queries, n_queries, flags, dev_hits, nullptr);
+} XPBD_ABI_CATCH
+
+int xpbd_world_terrain_distance(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_terrain_distance: NULL world");
+    if (int rc = xpbd::check_terrain_distance("xpbd_world_terrain_distance", query_target(w), queries, n_queries, flags, hits, true))
+        return rc;
+    return xpbd::terrain_distance_host(w, queries, n_queries, flags, hits);
+} XPBD_ABI_CATCH
+
+int xpbd_world_terrain_distance_device(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags,
+                                       xpbd_distance_hit *dev_hits)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_terrain_distance_device: NULL world");
+    if (int rc = xpbd::check_terrain_distance("xpbd_world_terrain_distance_device", query_target(w), dev_queries, n_queries, flags, dev_hits, false))
+        return rc;
+    return xpbd::terrain_distance_enqueue(w, dev_queries, n_queries, flags, dev_hits);
 } XPBD_ABI_CATCH
 
 } // extern "C"

@@ -539,6 +539,11 @@ extern "C" {
                                       dev_hits: *mut XpbdDistanceHit) -> c_int;
     pub fn xpbd_multi_world_distance(mw: *mut XpbdMultiWorld, queries: *const XpbdDistanceQuery, n_queries: u32, flags: u32,
                                      hits: *mut XpbdDistanceHit) -> c_int;
+    // the nearest feature of the terrain's surface (body = XPBD_HIT_TERRAIN); a call of its own, XPBD_QUERY_TERRAIN stays unknown
+    pub fn xpbd_world_terrain_distance(w: *mut XpbdWorld, queries: *const XpbdDistanceQuery, n_queries: u32, flags: u32,
+                                       hits: *mut XpbdDistanceHit) -> c_int;
+    pub fn xpbd_world_terrain_distance_device(w: *mut XpbdWorld, dev_queries: *const XpbdDistanceQuery, n_queries: u32, flags: u32,
+                                              dev_hits: *mut XpbdDistanceHit) -> c_int;
     pub fn xpbd_world_set_contact_report(w: *mut XpbdWorld, enable: u32) -> c_int;
     pub fn xpbd_world_contact_report_counts(w: *mut XpbdWorld, out: *mut u32) -> c_int;
     pub fn xpbd_world_download_pair_contacts(w: *mut XpbdWorld, pairs: *mut XpbdPairContact, pair_cap: u32, points: *mut XpbdContactPoint,

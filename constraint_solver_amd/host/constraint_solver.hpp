@@ -547,6 +547,15 @@ class BatchWorld {
         check(xpbd_world_distance(w_, queries.empty() ? nullptr : queries.data(), (uint32_t)queries.size(), flags, hits.empty() ? nullptr : hits.data()));
         return hits;
     }
+    // the feature of the terrain's surface nearest to every convex volume or point (include/xpbd.h, "Terrain in the distance queries");
+    // the world's nearest thing is the smaller distance of this and distance(), a body winning a tie
+    std::vector<xpbd_distance_hit> terrain_distance(const std::vector<xpbd_distance_query> &queries, uint32_t flags = 0)
+    {
+        std::vector<xpbd_distance_hit> hits(queries.size());
+        check(xpbd_world_terrain_distance(w_, queries.empty() ? nullptr : queries.data(), (uint32_t)queries.size(), flags,
+                                          hits.empty() ? nullptr : hits.data()));
+        return hits;
+    }
     // collision filters, one per body (empty: every body {~0u, ~0u}); flags: XPBD_FILTER_JOINTED or 0.  Upload clears them.
     void set_collision_filters(const std::vector<xpbd_collision_filter> &filters, uint32_t flags = 0)
     {

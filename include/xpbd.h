@@ -527,7 +527,8 @@ int  xpbd_world_set_restitution(xpbd_world *w, const double *restitution, uint32
  *   6. d = dot(n, (x0 + fi * dx, y0 + fj * dy, h00)).  The plane is {n, d}; s = dot(n, x) - d is the signed distance of x
  *      (src/geometry.rs:39-41).
  * (The device keeps n and d of both triangles of every cell, evaluated once by the setter with exactly these operations: 64
- * bytes per cell, at most 256 MiB.  The heights themselves are not kept.)
+ * bytes per cell, at most 256 MiB.  The heights are kept beside it for the terrain distance queries, which measure against the
+ * samples themselves: 8 bytes per sample, at most 32 MiB.)
  * Ground contacts (XPBD_MODE_CONTACTS only), collision::ground with a terrain: vertex v with x = frame * vertex contacts iff
  * x is inside the field and !(s >= 0.0); its target = x - s * n per component, where the reference has {x.x, x.y, 0.0}.
  * Everything after `target` is unchanged, operation by operation: correction, delta, delta_tangential, the friction factor,
@@ -554,7 +555,7 @@ int  xpbd_world_set_restitution(xpbd_world *w, const double *restitution, uint32
  * terrain still holds too: the new table is built in a block of its own and moved in last.
  * Not here: xpbd_multi_world_* has no such call (its frame runs the fused pair-solve + integrate + ground kernel at the halo
  * seam, which has no terrain form); the contact report lists body pairs only.  Rays, overlaps and sweeps see the terrain
- * when asked to: "Terrain in the scene queries", XPBD_QUERY_TERRAIN. */
+ * when asked to: "Terrain in the scene queries", XPBD_QUERY_TERRAIN; distance queries through xpbd_world_terrain_distance. */
 #define XPBD_MAX_TERRAIN_SAMPLES (1u << 22)
 typedef struct xpbd_heightfield {   /* 48 bytes */
     uint32_t nx, ny;          /* samples along x and y, each >= 2, nx * ny <= XPBD_MAX_TERRAIN_SAMPLES */
@@ -1148,7 +1149,8 @@ int  xpbd_multi_world_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint
  * With shape == XPBD_DISTANCE_POINT it is the single point `position`: one vertex (number 0, aw_0 = position itself, no
  * arithmetic), no faces, one edge (number 0, both ends vertex 0), radius 0 and centroid `position`; `rotation` is not used but
  * must still be finite.  Bodies stand at the pose the other queries see.  The ground plane and the terrain are not bodies, and
- * XPBD_QUERY_TERRAIN is an unknown flag for these calls.
+ * XPBD_QUERY_TERRAIN is an unknown flag for these calls.  (The terrain has calls of its own with the same records:
+ * xpbd_world_terrain_distance, "Terrain in the distance queries" below.)
  *
  * One volume A against one body B, with fb = Rigid::frame() of the body.  World vertices aw_v = fa * a_v, bw_v = fb * b_v; in the
  * other's local space a_in_b_v = inverse(fb) * aw_v, b_in_a_v = inverse(fa) * bw_v (the sweep's).  In this order:
@@ -1314,6 +1316,82 @@ int  xpbd_multi_world_distance(xpbd_multi_world *mw, const xpbd_distance_query *
  * ------------------------------------------------------------------------- */
 #define XPBD_QUERY_TERRAIN 0x100u      /* raycast, overlap and sweep flags: the terrain answers too */
 #define XPBD_HIT_TERRAIN   0xFFFFFFFEu /* .body of a hit on the terrain */
+
+/* ---------------------------------------------------------------------------
+ * Terrain in the distance queries (EXTENSION): the feature of the heightfield's SURFACE nearest to each of a batch of convex
+ * volumes or points, how far it is, and the two closest points.  Calls of their own, xpbd_world_terrain_distance(_device),
+ * with the records of xpbd_world_distance; that call, its device form and xpbd_multi_world_distance keep refusing
+ * XPBD_QUERY_TERRAIN.  The world's nearest thing is the smaller `distance` of the two calls' answers, and a body wins a tie;
+ * merging is the caller's.  Hosts ask for hover and foot clearance, "5 cm of air around this spawn place" on a terrain,
+ * steering along slopes, the ground point nearest to a cursor or a gripper.  There is no multi-world form: the sharded world has
+ * no terrain.  Arithmetic as everywhere: no fused multiply-add, dot / cross / frame products as in the other queries,
+ * correctly rounded / and sqrt, and a NaN d2 never replaces anything.
+ *
+ * The surface.  Sample (i, j) is the point P(i,j) = (x0 + i * dx, y0 + j * dy, H[j][i]), the coordinates formed exactly so, as
+ * the ray rule forms its borders; its number is j * nx + i.  Triangle T = (i, j, k) has the number 2 * (j * (nx - 1) + i) + k and
+ * the plane {n, d} of the table k_terrain_planes wrote (TERRAIN, steps 4 to 6): every user reads the same bits.  Terrain edge
+ * (i, j, e) has the number 3 * (j * nx + i) + e:  e = 0 from P(i,j) to P(i+1,j), it exists iff i < nx - 1;  e = 1 to P(i,j+1),
+ * iff j < ny - 1;  e = 2 the diagonal to P(i+1,j+1), iff both.  Every feature of the surface has exactly one number, so shared
+ * edges and corners are looked at once.
+ *
+ * The volume is that of xpbd_world_distance: the polytope `shape` at fa = {position, rotation}, world vertices aw_v = fa * a_v, or
+ * the single point `position` for XPBD_DISTANCE_POINT (one vertex, no faces, one edge from vertex 0 to itself).  ignore_body and
+ * mask do not concern the terrain and are not read.
+ *
+ *   1. Not separated: feature = XPBD_DISTANCE_OVERLAP, distance = 0, index_a = index_b = XPBD_NO_HIT, point_a = point_b =
+ *      normal = (0,0,0).  The volume is not separated iff (i) or (ii):
+ *      (i)  some world vertex x = aw_v (the point volume: `position`) has the stepper's lookup (TERRAIN, steps 1 to 6) inside
+ *           the field and s = dot(n, x) - d < 0: exactly the rule by which xpbd_world_overlap with XPBD_QUERY_TERRAIN lists
+ *           the terrain;
+ *      (ii) polytopes only: some terrain edge hits the volume.  The edge Q0 Q1 is the ray (origin = Q0, direction = Q1 - Q0,
+ *           max_distance = 1), the volume a body with frame fa, the test the ray-body rule above: hit iff t_lo <= t_hi.  This
+ *           catches the ridge or peak that pokes into a face or an edge of the volume between its vertices; a terrain vertex
+ *           inside the volume is the start or the end of such an edge and needs no rule of its own.
+ *   2. Otherwise d2 is the minimum over the candidates below under the total order (d2, class, terrain feature number, the
+ *      volume's index), class (a) < (b) < (c): the first minimum of the literal loop "all of (a), then all of (b), then all of
+ *      (c), terrain feature ascending, the volume's index ascending within it" (a candidate replaces the best so far only if
+ *      its d2 is strictly smaller).  The order is total, so which features an implementation looks at cannot change a bit.
+ *      (a) every volume vertex p = aw_v against every triangle T, in world space: h = dot(n, p) - d, counted only if h >= 0;
+ *          foot = p - h * n per component, which must satisfy the xy constraints of T's prism, inclusive, a NaN failing:
+ *          xi <= foot.x <= x(i+1), yj <= foot.y <= y(j+1), g = (foot.x - xi) * dy - (foot.y - yj) * dx with g >= 0 for the
+ *          lower triangle and g <= 0 for the upper.  d2 = h * h, feature = XPBD_FEATURE_FACE_B, index_a = v, index_b = the
+ *          triangle's number, point_a = p, point_b = foot.
+ *      (b) polytopes only: every sample P against every face f of the volume, in the volume's local space: p = inverse(fa) * P
+ *          and rule 2 (b) of the distance queries as it stands (h >= 0, the foot in f by the face's own winding test).
+ *          d2 = h * h, XPBD_FEATURE_FACE_A, index_a = f, index_b = the sample's number, point_a = fa * foot, point_b = P.
+ *      (c) every edge of the volume (the point: its one edge) against every terrain edge, in world space: the clamped segment
+ *          rule 2 (c) of the distance queries, branch by branch, with P0 P1 the volume's edge and Q0 Q1 the terrain's.
+ *          XPBD_FEATURE_EDGES, index_a = the volume's edge, index_b = the terrain edge's number, point_a = ca, point_b = cb.
+ *      Then distance = sqrt(d2) and normal = (point_a - point_b) * (1 / distance) per component, (0,0,0) at distance 0: it
+ *      points from the ground to the volume.
+ *   3. The terrain answers iff distance <= max_distance, with body = XPBD_HIT_TERRAIN; else the distance queries' miss record.
+ *      A query whose shape is outside the table and not the point, whose frame is not finite or whose max_distance is negative
+ *      or NaN finds nothing, and the call still succeeds.
+ *
+ * What this is and is not.  Above the field the candidates are complete for a volume that rules (i) and (ii) call separated:
+ * the closest pair is a vertex over the interior of a triangle, a sample over the interior of a face, or two points on two
+ * edges, clamps included.  Beyond the field's border there is no ground, as for the stepper: a vertex outside the field cannot
+ * make rule (i) true, and the nearest feature may then be a border edge.  A volume wholly inside the solid is OVERLAP through
+ * (i).  Not caught: a volume that skewers a hill -- in through one triangle's interior, under the ridge edge, out through the
+ * next triangle's, both ends in the air -- has no vertex under the ground and meets no terrain edge; the rules call it separated.
+ *
+ * Flags: XPBD_DISTANCE_BRUTE_FORCE -- every sample is looked at, a diagnostic for small fields -- and XPBD_DISTANCE_MASKED,
+ * accepted and ignored so that a caller can pass the flags of its body call.  Everything else is unknown, XPBD_QUERY_TERRAIN
+ * included.  XPBD_E_INVALID, the outputs untouched: a NULL world, NULL queries / hits with n_queries > 0, unknown flags, a
+ * nonzero `reserved` (host variant only), a world without a terrain (xpbd_world_set_terrain).  n_queries == 0 is XPBD_OK.
+ * Neither bodies nor polytopes are required: without polytopes the shape table is empty and only point queries find anything.
+ * The call changes nothing: stepping after it gives the bits of stepping without it.
+ *
+ * Method: a group of lanes per query visits rings of samples around the one under the volume's centre and stops when the ring's
+ * inner border is further from the volume's bounding sphere than min(max_distance, best so far).  Same bits as brute force.
+ * ------------------------------------------------------------------------- */
+/* Host arrays; checks everything before any device work and waits for the result. */
+int  xpbd_world_terrain_distance(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags,
+                                 xpbd_distance_hit *hits);
+/* Device arrays; stream-ordered on the world's stream, returns at once: it has no scratch of its own and never waits.
+ * `reserved` is not checked. */
+int  xpbd_world_terrain_distance_device(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags,
+                                        xpbd_distance_hit *dev_hits);
 
 /* ---------------------------------------------------------------------------
  * Contact REPORTS (EXTENSION): which body pairs the contact pipeline of XPBD_MODE_CONTACTS found touching, with the

@@ -1,0 +1,70 @@
+"""The terrain distance queries' ABI without a device: the symbols, the argument error that needs no world, and the declarations in
+the header, the Rust text and the C++ host mirror."""
+import os
+import re
+
+import numpy as np
+
+from constraint_solver_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("xpbd_world_terrain_distance", "xpbd_world_terrain_distance_device")
+
+
+def read(*path):
+    with open(os.path.join(ROOT, *path)) as f:
+        return f.read()
+
+
+def test_the_symbols_are_listed_and_exported_and_the_abi_version_stays():
+    L = capi.hip_lib()
+    for name in NAMES:
+        assert name in capi.ABI_SYMBOLS and hasattr(L, name)
+        assert getattr(L, name).argtypes == L.xpbd_world_distance.argtypes
+    assert L.xpbd_abi_version() == 2
+    assert not hasattr(L, "xpbd_multi_world_terrain_distance")                # the sharded world has no terrain
+
+
+def test_a_null_world_is_invalid_and_leaves_the_outputs_untouched():
+    L = capi.hip_lib()
+    q = capi.distances([[0.0, 0.0, 0.0]])
+    hits = np.zeros(2, dtype=capi.DISTANCE_HIT_DTYPE)
+    hits["body"] = 0xCDCDCDCD
+    for name in NAMES:
+        fn = getattr(L, name)
+        assert fn(None, q.ctypes.data, 1, 0, hits.ctypes.data) == capi.E_INVALID
+        assert b"NULL" in L.xpbd_last_error() and name.encode() in L.xpbd_last_error()
+        assert fn(None, None, 0, 0, None) == capi.E_INVALID
+    # (the remaining checks need a handle, and a handle needs a device: tests/test_gpu_terrain_distance.py)
+    assert (hits["body"] == 0xCDCDCDCD).all() and not hits["distance"].any()
+
+
+def test_the_python_world_has_both_forms():
+    assert callable(capi.World.terrain_distance) and callable(capi.World.terrain_distance_device)
+    assert not hasattr(capi.MultiWorld, "terrain_distance")
+
+
+def test_the_declarations_are_in_the_header_the_rust_text_and_the_host_mirror():
+    header = read("include", "xpbd.h")
+    section = header.index("Terrain in the distance queries (EXTENSION)")
+    assert section > header.index("Terrain in the scene queries (EXTENSION)") and section > header.index("#define XPBD_HIT_TERRAIN")
+    for text in ("int  xpbd_world_terrain_distance(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags,",
+                 "int  xpbd_world_terrain_distance_device(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags,"):
+        assert text in header and header.index(text) > section, text
+    assert "XPBD_QUERY_TERRAIN is an unknown flag for these calls" in header   # the bodies' calls keep refusing the flag
+    assert "The heights themselves are not kept" not in header and "#define XPBD_ABI_VERSION 2" in re.sub(r" +", " ", header)
+    assert "a body wins a tie" in header[section:]
+    rust = read("constraint_solver_amd", "ffi", "xpbd_ffi.rs")
+    assert re.search(r"pub fn xpbd_world_terrain_distance\(w: \*mut XpbdWorld, queries: \*const XpbdDistanceQuery, n_queries: u32, flags: u32,\s*"
+                     r"hits: \*mut XpbdDistanceHit\) -> c_int;", rust)
+    assert re.search(r"pub fn xpbd_world_terrain_distance_device\(w: \*mut XpbdWorld, dev_queries: \*const XpbdDistanceQuery, n_queries: u32, flags: u32,\s*"
+                     r"dev_hits: \*mut XpbdDistanceHit\) -> c_int;", rust)
+    host = read("constraint_solver_amd", "host", "constraint_solver.hpp")
+    assert host.count("std::vector<xpbd_distance_hit> terrain_distance(const std::vector<xpbd_distance_query> &queries") == 1
+    assert "xpbd_world_terrain_distance(w_" in host
+
+
+def test_the_check_has_a_header_of_its_own_and_includes_no_hip_header():
+    text = read("constraint_solver_amd", "csrc", "xpbd_checks_terrain_distance.hpp")
+    assert re.findall(r"\bint (check_\w+)\(", text) == ["check_terrain_distance"]
+    assert "#include <hip" not in text and "xpbd_internal.h" not in text
