@@ -5,8 +5,6 @@
 #include <vector>
 
 #include "xpbd_checks.hpp"
-#include "xpbd_checks_distance.hpp"
-#include "xpbd_checks_terrain_distance.hpp"
 #include "xpbd_error.h"
 
 namespace xpbd {
@@ -203,7 +201,7 @@ int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32
     return XPBD_OK;
 }
 
-// The flags' part of the three checks: `known` are the family's own bits.
+// The flags' part of the scene queries' checks: `known` are the family's own bits.
 int check_query_flags(const char *who, const QueryTarget &t, uint32_t flags, uint32_t known)
 {
     if (flags & ~(known | (t.terrain_allowed ? XPBD_QUERY_TERRAIN : 0u)))

@@ -22,7 +22,7 @@ struct QueryTarget {
     const char *setter;
     bool terrain_allowed = false, has_terrain = false;
 };
-// The flags' part of the three checks: `known` are the family's own bits.
+// The flags' part of the scene queries' checks: `known` are the family's own bits.
 int check_query_flags(const char *who, const QueryTarget &t, uint32_t flags, uint32_t known);
 int check_raycast(const char *who, const QueryTarget &t, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host);
 // n_out: what a host variant reports its total through (NULL passes for a device variant, which has none).
@@ -30,7 +30,16 @@ int check_overlap(const char *who, const QueryTarget &t, const xpbd_overlap_quer
                   const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host);
 // As check_overlap; a sweep's shape is not an error, it hits nothing.
 int check_sweep(const char *who, const QueryTarget &t, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, const void *hits, bool host);
-// (The distance queries' check, also defined in xpbd_checks.cpp, is declared in xpbd_checks_distance.hpp.)
+// As check_sweep: NULL arrays, unknown flags, no polytopes, with `host` a nonzero `reserved`, a target without bodies.  A shape
+// outside the table (XPBD_DISTANCE_POINT aside) is no error, the query finds nothing; XPBD_QUERY_TERRAIN is an unknown flag whatever
+// the target (the terrain is no body).
+int check_distance(const char *who, const QueryTarget &t, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, const void *hits,
+                   bool host);
+// The terrain distance queries: NULL arrays, unknown flags (everything but XPBD_DISTANCE_BRUTE_FORCE and XPBD_DISTANCE_MASKED,
+// XPBD_QUERY_TERRAIN included), with `host` a nonzero `reserved`, a target without a terrain.  Neither polytopes nor bodies are
+// required: without polytopes only point queries find anything.
+int check_terrain_distance(const char *who, const QueryTarget &t, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags,
+                           const void *hits, bool host);
 // The argument checks of xpbd_world_set_joints against a world of n_bodies bodies / of xpbd_world_set_joint_limits against a
 // joint list.
 int check_joints(const char *who, const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies);

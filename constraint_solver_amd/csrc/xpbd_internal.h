@@ -10,8 +10,6 @@
 #include <hip/hip_runtime_api.h>
 
 #include "xpbd_checks.hpp" // the argument checks both worlds share
-#include "xpbd_checks_distance.hpp"
-#include "xpbd_checks_terrain_distance.hpp"
 #include "xpbd_error.h"
 
 namespace xpbd {

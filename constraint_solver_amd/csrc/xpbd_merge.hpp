@@ -1,5 +1,5 @@
 // xpbd_merge.hpp -- how the multi-GPU world (xpbd_multi.cpp) merges what its ranks answer: the hits of the scene queries (ray
-// casts, sweeps, overlaps) and the contact report of a frame with its begin / end events.  Host-only: pure functions of the
+// casts, sweeps, distances, overlaps) and the contact report of a frame with its begin / end events.  Host-only: pure functions of the
 // gathered bytes, no device and no collective (tests/merge_standalone_main.cpp runs them on their own).
 #pragma once
 
@@ -12,52 +12,19 @@
 
 namespace xpbd {
 
-// rows: n_ranks rows of n_rays xpbd_ray_hit, rank r's answer for its owned bodies (a miss: XPBD_NO_HIT at +inf).  out[i] = the
+// rows: n_ranks rows of n records of type Hit (xpbd_ray_hit, xpbd_sweep_hit, xpbd_distance_hit), rank r's answer for its owned
+// bodies (a miss: XPBD_NO_HIT at +inf; a distance query's overlap: distance 0, so neither needs a rule of its own).  out[i] = the
 // minimum over the ranks under the order of a single world: distance, then body.
-inline void merge_ray_hits(const void *rows, uint32_t n_ranks, uint32_t n_rays, xpbd_ray_hit *out)
+template <class Hit>
+void merge_first_hits(const void *rows, uint32_t n_ranks, uint32_t n, Hit *out)
 {
     const uint8_t *bytes = static_cast<const uint8_t *>(rows);
-    for (uint32_t i = 0; i < n_rays; ++i) {
-        xpbd_ray_hit best;
+    for (uint32_t i = 0; i < n; ++i) {
+        Hit best;
         std::memcpy(&best, bytes + (size_t)i * sizeof best, sizeof best);
         for (uint32_t r = 1; r < n_ranks; ++r) {
-            xpbd_ray_hit h;
-            std::memcpy(&h, bytes + ((size_t)r * n_rays + i) * sizeof h, sizeof h);
-            if (h.distance < best.distance || (h.distance == best.distance && h.body < best.body))
-                best = h;
-        }
-        out[i] = best;
-    }
-}
-
-// The same for sweeps: rows of n_sweeps xpbd_sweep_hit, the minimum on (distance, body).
-inline void merge_sweep_hits(const void *rows, uint32_t n_ranks, uint32_t n_sweeps, xpbd_sweep_hit *out)
-{
-    const uint8_t *bytes = static_cast<const uint8_t *>(rows);
-    for (uint32_t i = 0; i < n_sweeps; ++i) {
-        xpbd_sweep_hit best;
-        std::memcpy(&best, bytes + (size_t)i * sizeof best, sizeof best);
-        for (uint32_t r = 1; r < n_ranks; ++r) {
-            xpbd_sweep_hit h;
-            std::memcpy(&h, bytes + ((size_t)r * n_sweeps + i) * sizeof h, sizeof h);
-            if (h.distance < best.distance || (h.distance == best.distance && h.body < best.body))
-                best = h;
-        }
-        out[i] = best;
-    }
-}
-
-// The same for distance queries: rows of n_queries xpbd_distance_hit, the minimum on (distance, body).  An overlap's distance is 0
-// and a miss stands at +inf with body XPBD_NO_HIT, so neither needs a rule of its own.
-inline void merge_distance_hits(const void *rows, uint32_t n_ranks, uint32_t n_queries, xpbd_distance_hit *out)
-{
-    const uint8_t *bytes = static_cast<const uint8_t *>(rows);
-    for (uint32_t i = 0; i < n_queries; ++i) {
-        xpbd_distance_hit best;
-        std::memcpy(&best, bytes + (size_t)i * sizeof best, sizeof best);
-        for (uint32_t r = 1; r < n_ranks; ++r) {
-            xpbd_distance_hit h;
-            std::memcpy(&h, bytes + ((size_t)r * n_queries + i) * sizeof h, sizeof h);
+            Hit h;
+            std::memcpy(&h, bytes + ((size_t)r * n + i) * sizeof h, sizeof h);
             if (h.distance < best.distance || (h.distance == best.distance && h.body < best.body))
                 best = h;
         }

@@ -24,10 +24,30 @@ int shard_overlap(Shard &s, const xpbd_overlap_query *queries, uint32_t n_querie
     return xpbd::overlap_host(s.world, queries, n_queries, flags, offsets.data(), hits.data(), total, &total, s.query_ids.as<uint32_t>());
 }
 
-// What the scene queries' argument checks (xpbd::check_raycast, xpbd::check_overlap, xpbd::check_sweep) need to know of the world.
+// What the scene queries' argument checks (xpbd_checks.hpp) need to know of the world.
 xpbd::QueryTarget query_target(const xpbd_multi_world *mw)
 {
     return {mw->have_shapes, mw->plan.planned ? mw->n_global : 0u, (uint32_t)mw->shape_radius.size(), "xpbd_multi_world_set_polytopes"};
+}
+
+// The queries with one record per query (ray casts, sweeps, distances): every local shard answers for its owned bodies --
+// per_shard(shard, its n records) -- then one all-gather of the hit records (with every rank's status) over all ranks, and every
+// rank merges the n_ranks rows by the (distance, global index) rule of a single world (xpbd::merge_first_hits).
+template <class Hit, class PerShard>
+int gather_first_hits(xpbd_multi_world *mw, uint32_t n, Hit *hits, PerShard &&per_shard)
+{
+    LocalStatus st;
+    std::vector<std::vector<Hit>> mine(mw->shards.size(), std::vector<Hit>(n));
+    std::vector<const void *> send;
+    for (size_t k = 0; k < mw->shards.size(); ++k) {
+        if (st.ok())
+            st.keep(per_shard(mw->shards[k], mine[k].data()));
+        send.push_back(mine[k].data());
+    }
+    std::vector<uint8_t> all;
+    XPBD_TRY(all_gather_host(mw, send, (size_t)n * sizeof(Hit), all, st));
+    xpbd::merge_first_hits(all.data(), mw->n_ranks, n, hits);
+    return XPBD_OK;
 }
 
 // xpbd_multi_world_raycast(_masked), named `who` in its errors.
@@ -40,20 +60,9 @@ int multi_raycast(const char *who, xpbd_multi_world *mw, const xpbd_ray *rays, u
         return set_error(XPBD_E_INVALID, "%s: no bodies uploaded", who);
     if (n_rays == 0)
         return XPBD_OK;
-    // every local shard casts against its owned bodies; one all-gather of the hit records (with every rank's status) over
-    // all ranks, then every rank merges the n_ranks rows by the (t, global index) rule of a single world
-    LocalStatus st;
-    std::vector<std::vector<xpbd_ray_hit>> mine(mw->shards.size(), std::vector<xpbd_ray_hit>(n_rays));
-    std::vector<const void *> send;
-    for (size_t k = 0; k < mw->shards.size(); ++k) {
-        if (st.ok())
-            st.keep(xpbd::raycast_host(mw->shards[k].world, rays, n_rays, flags, mine[k].data(), mw->shards[k].query_ids.as<uint32_t>(), masked, mask));
-        send.push_back(mine[k].data());
-    }
-    std::vector<uint8_t> all;
-    XPBD_TRY(all_gather_host(mw, send, (size_t)n_rays * sizeof(xpbd_ray_hit), all, st));
-    xpbd::merge_ray_hits(all.data(), mw->n_ranks, n_rays, hits);
-    return XPBD_OK;
+    return gather_first_hits(mw, n_rays, hits, [&](Shard &s, xpbd_ray_hit *mine) {
+        return xpbd::raycast_host(s.world, rays, n_rays, flags, mine, s.query_ids.as<uint32_t>(), masked, mask);
+    });
 }
 
 // xpbd_multi_world_overlap: every local shard answers for its owned bodies; the counts, the offsets and the hits of every
@@ -94,8 +103,7 @@ int multi_overlap(xpbd_multi_world *mw, const xpbd_overlap_query *queries, uint3
     return XPBD_OK;
 }
 
-// xpbd_multi_world_sweep: every local shard sweeps against its owned bodies; one all-gather of the hit records, merged by the
-// (t, global index) rule of a single world (xpbd::merge_sweep_hits).
+// xpbd_multi_world_sweep.
 int multi_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits)
 {
     const char *who = "xpbd_multi_world_sweep";
@@ -103,22 +111,12 @@ int multi_sweep(xpbd_multi_world *mw, const xpbd_sweep *sweeps, uint32_t n_sweep
     XPBD_TRY(xpbd::check_sweep(who, query_target(mw), sweeps, n_sweeps, flags, hits, true));
     if (n_sweeps == 0)
         return XPBD_OK;
-    LocalStatus st;
-    std::vector<std::vector<xpbd_sweep_hit>> mine(mw->shards.size(), std::vector<xpbd_sweep_hit>(n_sweeps));
-    std::vector<const void *> send;
-    for (size_t k = 0; k < mw->shards.size(); ++k) {
-        if (st.ok())
-            st.keep(xpbd::sweep_host(mw->shards[k].world, sweeps, n_sweeps, flags, mine[k].data(), mw->shards[k].query_ids.as<uint32_t>()));
-        send.push_back(mine[k].data());
-    }
-    std::vector<uint8_t> all;
-    XPBD_TRY(all_gather_host(mw, send, (size_t)n_sweeps * sizeof(xpbd_sweep_hit), all, st));
-    xpbd::merge_sweep_hits(all.data(), mw->n_ranks, n_sweeps, hits);
-    return XPBD_OK;
+    return gather_first_hits(mw, n_sweeps, hits, [&](Shard &s, xpbd_sweep_hit *mine) {
+        return xpbd::sweep_host(s.world, sweeps, n_sweeps, flags, mine, s.query_ids.as<uint32_t>());
+    });
 }
 
-// xpbd_multi_world_distance: every local shard answers for its owned bodies; one all-gather of the hit records, merged by the
-// (distance, global index) rule of a single world (xpbd::merge_distance_hits).
+// xpbd_multi_world_distance.
 int multi_distance(xpbd_multi_world *mw, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits)
 {
     const char *who = "xpbd_multi_world_distance";
@@ -126,18 +124,9 @@ int multi_distance(xpbd_multi_world *mw, const xpbd_distance_query *queries, uin
     XPBD_TRY(xpbd::check_distance(who, query_target(mw), queries, n_queries, flags, hits, true));
     if (n_queries == 0)
         return XPBD_OK;
-    LocalStatus st;
-    std::vector<std::vector<xpbd_distance_hit>> mine(mw->shards.size(), std::vector<xpbd_distance_hit>(n_queries));
-    std::vector<const void *> send;
-    for (size_t k = 0; k < mw->shards.size(); ++k) {
-        if (st.ok())
-            st.keep(xpbd::distance_host(mw->shards[k].world, queries, n_queries, flags, mine[k].data(), mw->shards[k].query_ids.as<uint32_t>()));
-        send.push_back(mine[k].data());
-    }
-    std::vector<uint8_t> all;
-    XPBD_TRY(all_gather_host(mw, send, (size_t)n_queries * sizeof(xpbd_distance_hit), all, st));
-    xpbd::merge_distance_hits(all.data(), mw->n_ranks, n_queries, hits);
-    return XPBD_OK;
+    return gather_first_hits(mw, n_queries, hits, [&](Shard &s, xpbd_distance_hit *mine) {
+        return xpbd::distance_host(s.world, queries, n_queries, flags, mine, s.query_ids.as<uint32_t>());
+    });
 }
 
 } // namespace

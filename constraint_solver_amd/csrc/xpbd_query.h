@@ -1,5 +1,7 @@
-// xpbd_query.h -- scene queries (EXTENSION): launchers for the batched ray casts, overlap queries, sweep queries and distance queries in
-// xpbd_query.hip.
+// xpbd_query.h -- scene queries (EXTENSION): launchers for the batched ray casts, overlap queries, sweep queries and distance queries.
+// One unit per family -- xpbd_query_rays.hip, xpbd_query_overlap.hip, xpbd_query_sweep.hip, xpbd_query_distance.hip -- on top of
+// xpbd_query_grid.hip (the bodies' records, the grid, the scratch); the device routines more than one family uses are in
+// xpbd_query_device.hpp, which opens with the table of who uses what.  The terrain's passes: xpbd_terrain_query.hip.
 //
 // Semantics: include/xpbd.h, "Scene queries".  Two paths give the same bits in every field of every hit:
 //  * grid: the bodies' bounding spheres (frame * centroid, PolytopeTables::radii) go into a uniform grid built for this call
@@ -7,7 +9,7 @@
 //    box of all spheres fits the table, hashed keys otherwise), and every ray walks its cells in order (3D-DDA), testing the
 //    bodies listed there, until the next cell starts beyond the best hit;
 //  * brute force: every ray against every body, reduced on (t, index) across lanes, waves and workgroups.
-// Both use one routine for a (ray, body) pair (ray_body in xpbd_query.hip) and the same total order on candidates, so the
+// Both use one routine for a (ray, body) pair (ray_body in xpbd_query_shared.hpp) and the same total order on candidates, so the
 // winner -- the minimum -- does not depend on which bodies were tested how often or in which order.
 #pragma once
 
@@ -28,7 +30,7 @@ constexpr uint32_t kQueryRecDoubles = 12;
 struct QueryScratch {
     double *rec;          // [n][kQueryRecDoubles]
     double *partials;     // [blocks_for(n)][7]
-    void *grid;           // one QueryGrid (xpbd_query.hip)
+    void *grid;           // one QueryGrid (xpbd_query_device.hpp)
     uint32_t *cell_start; // [table_size + 1]: exclusive scan of the cell populations
     uint32_t *cell_fill;  // [table_size]
     uint32_t *items;      // [8 n]: body slots, grouped by cell

@@ -30,6 +30,18 @@ int query_host(xpbd_world *w, const In *in, uint32_t n, Out *out, Enqueue &&enqu
     return XPBD_OK;
 }
 
+// The prologue of the queries whose records are an overlap query's (overlaps, sweeps, distances): the device bound, room for the
+// scratch of n of them over the world's bodies, and the view of it.
+static int group_scratch(xpbd_world *w, uint32_t n, bool brute, QueryScratch &scratch)
+{
+    if (int rc = bind_device(w))
+        return rc;
+    const QuerySizes q = overlap_scratch_bytes(w->n, n, brute);
+    XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
+    scratch = w->query.view(q.table_size);
+    return XPBD_OK;
+}
+
 int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits,
                     const uint32_t *dev_global_id, bool masked, uint32_t mask)
 {
@@ -60,19 +72,19 @@ int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32
                     xpbd_overlap_hit *dev_hits, uint32_t cap, const uint32_t *dev_global_id)
 {
     static_assert(sizeof(xpbd_overlap_query) == 72 && sizeof(xpbd_overlap_hit) == 16, "xpbd_overlap_query is 72 bytes, xpbd_overlap_hit 16");
-    if (int rc = bind_device(w))
-        return rc;
     if (n_queries == 0) {
+        if (int rc = bind_device(w))
+            return rc;
         if (dev_offsets)
             XPBD_HIP_TRY(hipMemsetAsync(dev_offsets, 0, sizeof(uint32_t), w->stream));
         return XPBD_OK;
     }
     const bool brute = (flags & XPBD_OVERLAP_BRUTE_FORCE) || w->n == 0;
-    const QuerySizes q = overlap_scratch_bytes(w->n, n_queries, brute);
-    XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
+    QueryScratch scratch;
+    XPBD_TRY(group_scratch(w, n_queries, brute, scratch));
     const bool masked = (flags & XPBD_OVERLAP_MASKED) != 0;
-    XPBD_HIP_TRY(launch_overlap(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute,
-                                w->query.view(q.table_size), dev_offsets, dev_hits, cap, w->stream, query_terrain(w, flags)));
+    XPBD_HIP_TRY(launch_overlap(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute, scratch,
+                                dev_offsets, dev_hits, cap, w->stream, query_terrain(w, flags)));
     return XPBD_OK;
 }
 
@@ -110,15 +122,13 @@ int sweep_enqueue(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps
     static_assert(sizeof(xpbd_sweep) == 104 && sizeof(xpbd_sweep_hit) == 72, "xpbd_sweep is 104 bytes, xpbd_sweep_hit 72");
     if (n_sweeps == 0)
         return XPBD_OK;
-    if (int rc = bind_device(w))
-        return rc;
     // (a shard without bodies takes the brute-force path too: every sweep misses, no grid to build)
     const bool brute = (flags & XPBD_SWEEP_BRUTE_FORCE) || n_sweeps <= XPBD_SWEEP_BRUTE_FORCE_SWEEPS || w->n == 0;
-    const QuerySizes q = overlap_scratch_bytes(w->n, n_sweeps, brute); // a sweep's records are an overlap query's
-    XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
+    QueryScratch scratch;
+    XPBD_TRY(group_scratch(w, n_sweeps, brute, scratch));
     const bool masked = (flags & XPBD_SWEEP_MASKED) != 0;
-    XPBD_HIP_TRY(launch_sweep(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_sweeps, n_sweeps, masked, brute,
-                              w->query.view(q.table_size), dev_hits, w->stream, query_terrain(w, flags), (flags & XPBD_SWEEP_BRUTE_FORCE) != 0));
+    XPBD_HIP_TRY(launch_sweep(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_sweeps, n_sweeps, masked, brute, scratch,
+                              dev_hits, w->stream, query_terrain(w, flags), (flags & XPBD_SWEEP_BRUTE_FORCE) != 0));
     return XPBD_OK;
 }
 
@@ -135,15 +145,13 @@ int distance_enqueue(xpbd_world *w, const xpbd_distance_query *dev_queries, uint
     static_assert(sizeof(xpbd_distance_query) == 80 && sizeof(xpbd_distance_hit) == 96, "xpbd_distance_query is 80 bytes, xpbd_distance_hit 96");
     if (n_queries == 0)
         return XPBD_OK;
-    if (int rc = bind_device(w))
-        return rc;
     // (a shard without bodies takes the brute-force path too: every query finds nothing, no grid to build)
     const bool brute = (flags & XPBD_DISTANCE_BRUTE_FORCE) || n_queries <= XPBD_DISTANCE_BRUTE_FORCE_QUERIES || w->n == 0;
-    const QuerySizes q = overlap_scratch_bytes(w->n, n_queries, brute); // a distance query's records are an overlap query's
-    XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
+    QueryScratch scratch;
+    XPBD_TRY(group_scratch(w, n_queries, brute, scratch));
     const bool masked = (flags & XPBD_DISTANCE_MASKED) != 0;
-    XPBD_HIP_TRY(launch_distance(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute,
-                                 w->query.view(q.table_size), dev_hits, w->stream));
+    XPBD_HIP_TRY(launch_distance(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute, scratch,
+                                 dev_hits, w->stream));
     return XPBD_OK;
 }
 
@@ -179,63 +187,62 @@ int terrain_distance_host(xpbd_world *w, const xpbd_distance_query *queries, uin
 
 extern "C" {
 
-namespace { // (inside the extern "C" block, where these three have always been: they keep their unmangled names in the library)
-// The scene queries' argument checks (xpbd::check_raycast, xpbd::check_overlap, xpbd::check_sweep) against one world.
-xpbd::QueryTarget query_target(const xpbd_world *w)
-{
-    return {w->has_topology, w->n, w->n_shapes, "xpbd_world_set_polytopes (set_shapes gives vertices only)", true, w->terrain.planes != nullptr};
-}
-
-int check_world_raycast(const char *who, const xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, const void *hits, bool host)
+namespace { // (inside the extern "C" block, where it has always been: it keeps its unmangled name in the library)
+// What the scene queries' argument checks (xpbd_checks.hpp) need to know of world `w`, for the entry point `who`: XPBD_OK and
+// *target, or the error of a NULL world.
+int query_target(const char *who, const xpbd_world *w, xpbd::QueryTarget *target)
 {
     if (!w)
         return set_error(XPBD_E_INVALID, "%s: NULL world", who);
-    return xpbd::check_raycast(who, query_target(w), rays, n_rays, flags, hits, host);
-}
-
-int check_world_overlap(const char *who, const xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags,
-                        const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host)
-{
-    if (!w)
-        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
-    return xpbd::check_overlap(who, query_target(w), queries, n_queries, flags, offsets, hits, cap, n_out, host);
+    *target = {w->has_topology, w->n, w->n_shapes, "xpbd_world_set_polytopes (set_shapes gives vertices only)", true, w->terrain.planes != nullptr};
+    return XPBD_OK;
 }
 } // namespace
 
 int xpbd_world_raycast(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *hits)
 try {
-    if (int rc = check_world_raycast("xpbd_world_raycast", w, rays, n_rays, flags, hits, true))
-        return rc;
+    const char *who = "xpbd_world_raycast";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_raycast(who, target, rays, n_rays, flags, hits, true));
     return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr, false, 0u);
 } XPBD_ABI_CATCH
 
 int xpbd_world_raycast_masked(xpbd_world *w, const xpbd_ray *rays, uint32_t n_rays, uint32_t flags, uint32_t mask, xpbd_ray_hit *hits)
 try {
-    if (int rc = check_world_raycast("xpbd_world_raycast_masked", w, rays, n_rays, flags, hits, true))
-        return rc;
+    const char *who = "xpbd_world_raycast_masked";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_raycast(who, target, rays, n_rays, flags, hits, true));
     return xpbd::raycast_host(w, rays, n_rays, flags, hits, nullptr, true, mask);
 } XPBD_ABI_CATCH
 
 int xpbd_world_raycast_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, xpbd_ray_hit *dev_hits)
 try {
-    if (int rc = check_world_raycast("xpbd_world_raycast_device", w, dev_rays, n_rays, flags, dev_hits, false))
-        return rc;
+    const char *who = "xpbd_world_raycast_device";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_raycast(who, target, dev_rays, n_rays, flags, dev_hits, false));
     return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr, false, 0u);
 } XPBD_ABI_CATCH
 
 int xpbd_world_raycast_masked_device(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, uint32_t flags, uint32_t mask,
                                      xpbd_ray_hit *dev_hits)
 try {
-    if (int rc = check_world_raycast("xpbd_world_raycast_masked_device", w, dev_rays, n_rays, flags, dev_hits, false))
-        return rc;
+    const char *who = "xpbd_world_raycast_masked_device";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_raycast(who, target, dev_rays, n_rays, flags, dev_hits, false));
     return xpbd::raycast_enqueue(w, dev_rays, n_rays, flags, dev_hits, nullptr, true, mask);
 } XPBD_ABI_CATCH
 
 int xpbd_world_overlap(xpbd_world *w, const xpbd_overlap_query *queries, uint32_t n_queries, uint32_t flags, uint32_t *offsets,
                        xpbd_overlap_hit *hits, uint32_t cap, uint32_t *n_out)
 try {
-    if (int rc = check_world_overlap("xpbd_world_overlap", w, queries, n_queries, flags, offsets, hits, cap, n_out, true))
-        return rc;
+    const char *who = "xpbd_world_overlap";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_overlap(who, target, queries, n_queries, flags, offsets, hits, cap, n_out, true));
     uint32_t total = 0;
     const int rc = xpbd::overlap_host(w, queries, n_queries, flags, offsets, hits, cap, &total, nullptr);
     if (n_out && (rc == XPBD_OK || rc == XPBD_E_CAPACITY))
@@ -246,63 +253,65 @@ try {
 int xpbd_world_overlap_device(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32_t n_queries, uint32_t flags, uint32_t *dev_offsets,
                               xpbd_overlap_hit *dev_hits, uint32_t cap)
 try {
-    if (int rc = check_world_overlap("xpbd_world_overlap_device", w, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap, nullptr, false))
-        return rc;
+    const char *who = "xpbd_world_overlap_device";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_overlap(who, target, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap, nullptr, false));
     return xpbd::overlap_enqueue(w, dev_queries, n_queries, flags, dev_offsets, dev_hits, cap, nullptr);
 } XPBD_ABI_CATCH
 
 int xpbd_world_sweep(xpbd_world *w, const xpbd_sweep *sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *hits)
 try {
-    if (!w)
-        return set_error(XPBD_E_INVALID, "xpbd_world_sweep: NULL world");
-    if (int rc = xpbd::check_sweep("xpbd_world_sweep", query_target(w), sweeps, n_sweeps, flags, hits, true))
-        return rc;
+    const char *who = "xpbd_world_sweep";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_sweep(who, target, sweeps, n_sweeps, flags, hits, true));
     return xpbd::sweep_host(w, sweeps, n_sweeps, flags, hits, nullptr);
 } XPBD_ABI_CATCH
 
 int xpbd_world_sweep_device(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps, uint32_t flags, xpbd_sweep_hit *dev_hits)
 try {
-    if (!w)
-        return set_error(XPBD_E_INVALID, "xpbd_world_sweep_device: NULL world");
-    if (int rc = xpbd::check_sweep("xpbd_world_sweep_device", query_target(w), dev_sweeps, n_sweeps, flags, dev_hits, false))
-        return rc;
+    const char *who = "xpbd_world_sweep_device";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_sweep(who, target, dev_sweeps, n_sweeps, flags, dev_hits, false));
     return xpbd::sweep_enqueue(w, dev_sweeps, n_sweeps, flags, dev_hits, nullptr);
 } XPBD_ABI_CATCH
 
 int xpbd_world_distance(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits)
 try {
-    if (!w)
-        return set_error(XPBD_E_INVALID, "xpbd_world_distance: NULL world");
-    if (int rc = xpbd::check_distance("xpbd_world_distance", query_target(w), queries, n_queries, flags, hits, true))
-        return rc;
+    const char *who = "xpbd_world_distance";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_distance(who, target, queries, n_queries, flags, hits, true));
     return xpbd::distance_host(w, queries, n_queries, flags, hits, nullptr);
 } XPBD_ABI_CATCH
 
 int xpbd_world_distance_device(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *dev_hits)
 try {
-    if (!w)
-        return set_error(XPBD_E_INVALID, "xpbd_world_distance_device: NULL world");
-    if (int rc = xpbd::check_distance("xpbd_world_distance_device", query_target(w), dev_queries, n_queries, flags, dev_hits, false))
-        return rc;
+    const char *who = "xpbd_world_distance_device";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_distance(who, target, dev_queries, n_queries, flags, dev_hits, false));
     return xpbd::distance_enqueue(w, dev_queries, n_queries, flags, dev_hits, nullptr);
 } XPBD_ABI_CATCH
 
 int xpbd_world_terrain_distance(xpbd_world *w, const xpbd_distance_query *queries, uint32_t n_queries, uint32_t flags, xpbd_distance_hit *hits)
 try {
-    if (!w)
-        return set_error(XPBD_E_INVALID, "xpbd_world_terrain_distance: NULL world");
-    if (int rc = xpbd::check_terrain_distance("xpbd_world_terrain_distance", query_target(w), queries, n_queries, flags, hits, true))
-        return rc;
+    const char *who = "xpbd_world_terrain_distance";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_terrain_distance(who, target, queries, n_queries, flags, hits, true));
     return xpbd::terrain_distance_host(w, queries, n_queries, flags, hits);
 } XPBD_ABI_CATCH
 
 int xpbd_world_terrain_distance_device(xpbd_world *w, const xpbd_distance_query *dev_queries, uint32_t n_queries, uint32_t flags,
                                        xpbd_distance_hit *dev_hits)
 try {
-    if (!w)
-        return set_error(XPBD_E_INVALID, "xpbd_world_terrain_distance_device: NULL world");
-    if (int rc = xpbd::check_terrain_distance("xpbd_world_terrain_distance_device", query_target(w), dev_queries, n_queries, flags, dev_hits, false))
-        return rc;
+    const char *who = "xpbd_world_terrain_distance_device";
+    xpbd::QueryTarget target;
+    XPBD_TRY(query_target(who, w, &target));
+    XPBD_TRY(xpbd::check_terrain_distance(who, target, dev_queries, n_queries, flags, dev_hits, false));
     return xpbd::terrain_distance_enqueue(w, dev_queries, n_queries, flags, dev_hits);
 } XPBD_ABI_CATCH
 

@@ -71,6 +71,16 @@ int main()
     accepted(check_sweep("sweep_ok", world, &sweep, 1, XPBD_SWEEP_BRUTE_FORCE, &sweep_hit, true), "check_sweep");
     refused(check_sweep("sweep_bad", bare, &sweep, 1, 0, &sweep_hit, true), "sweep_bad"); // no polytopes
 
+    xpbd_distance_query distance{};
+    xpbd_distance_hit distance_hit{};
+    distance.shape = XPBD_DISTANCE_POINT;
+    accepted(check_distance("distance_ok", world, &distance, 1, XPBD_DISTANCE_MASKED, &distance_hit, true), "check_distance");
+    refused(check_distance("distance_bad", world, &distance, 1, XPBD_QUERY_TERRAIN, &distance_hit, true), "distance_bad"); // the terrain is no body
+
+    const QueryTarget flat{true, 4, 2, "the_setter", true, false}; // no terrain
+    accepted(check_terrain_distance("terrain_distance_ok", world, &distance, 1, XPBD_DISTANCE_BRUTE_FORCE, &distance_hit, true), "check_terrain_distance");
+    refused(check_terrain_distance("terrain_distance_bad", flat, &distance, 1, 0, &distance_hit, true), "terrain_distance_bad");
+
     xpbd_joint joints[2] = {hinge(0, 1), hinge(1, 2)};
     accepted(check_joints("joints_ok", joints, 2, 3), "check_joints");
     refused(check_joints("joints_bad", joints, 2, 2), "joints_bad"); // body 2 of 2

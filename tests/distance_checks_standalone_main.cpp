@@ -1,11 +1,11 @@
-// distance_checks_standalone_main.cpp -- check_distance (csrc/xpbd_checks.cpp, declared in csrc/xpbd_checks_distance.hpp) built with
+// distance_checks_standalone_main.cpp -- check_distance (csrc/xpbd_checks.cpp, declared in csrc/xpbd_checks.hpp) built with
 // plain g++ (no hipcc, no ROCm include path; see test_distance_checks_standalone.py): every way it refuses a call, each with
 // XPBD_E_INVALID and a message that names the `who` it was given, and the calls it accepts.  Exits 0.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 
-#include "../constraint_solver_amd/csrc/xpbd_checks_distance.hpp"
+#include "../constraint_solver_amd/csrc/xpbd_checks.hpp"
 
 namespace {
 

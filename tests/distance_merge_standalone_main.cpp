@@ -1,4 +1,4 @@
-// distance_merge_standalone_main.cpp -- the merge of the multi-GPU world's distance queries (merge_distance_hits,
+// distance_merge_standalone_main.cpp -- the merge of the multi-GPU world's distance queries (merge_first_hits<xpbd_distance_hit>,
 // csrc/xpbd_merge.hpp) on hand-made rows, with no device and no Python: built by tests/test_distance_merge_standalone.py with
 // plain g++, also under ASan/UBSan.  The expected winner of every query comes from sorting the ranks' records by (distance, body).
 // Exits non-zero with a one-line message on the first difference.
@@ -56,7 +56,7 @@ int check(const char *scene, const std::vector<std::vector<xpbd_distance_hit>> &
     for (const auto &row : rows)
         flat.insert(flat.end(), row.begin(), row.end());
     std::vector<xpbd_distance_hit> got(n);
-    xpbd::merge_distance_hits(flat.data(), n_ranks, n, got.data());
+    xpbd::merge_first_hits<xpbd_distance_hit>(flat.data(), n_ranks, n, got.data());
     for (uint32_t i = 0; i < n; ++i) {
         std::vector<xpbd_distance_hit> all;
         for (const auto &row : rows)
@@ -81,7 +81,7 @@ int run()
         std::vector<xpbd_distance_hit> flat(rows[0]);
         flat.insert(flat.end(), rows[1].begin(), rows[1].end());
         xpbd_distance_hit got[4];
-        xpbd::merge_distance_hits(flat.data(), 2, 4, got);
+        xpbd::merge_first_hits<xpbd_distance_hit>(flat.data(), 2, 4, got);
         if (got[0].body != 5 || got[0].index_a != 1 || got[0].distance != 1.5)
             return fail("by hand", "a tie on distance did not go to the smaller body", 0);
         if (got[1].body != 8 || got[1].feature != XPBD_DISTANCE_OVERLAP || got[1].distance != 0.0)
@@ -127,11 +127,11 @@ int run()
         return rc;
     // one rank: its row as it is
     std::vector<xpbd_distance_hit> got(257);
-    xpbd::merge_distance_hits(rows[1].data(), 1, 257, got.data());
+    xpbd::merge_first_hits<xpbd_distance_hit>(rows[1].data(), 1, 257, got.data());
     if (std::memcmp(got.data(), rows[1].data(), 257 * sizeof(xpbd_distance_hit)) != 0)
         return fail("one rank", "the row changed", 0);
     // no queries at all
-    xpbd::merge_distance_hits(rows[1].data(), 4, 0, got.data());
+    xpbd::merge_first_hits<xpbd_distance_hit>(rows[1].data(), 4, 0, got.data());
     return 0;
 }
 

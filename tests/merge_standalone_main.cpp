@@ -50,7 +50,7 @@ int check_rays(const char *scene, const std::vector<std::vector<xpbd_ray_hit>> &
     for (const auto &row : rows)
         flat.insert(flat.end(), row.begin(), row.end());
     std::vector<xpbd_ray_hit> got(n_rays);
-    xpbd::merge_ray_hits(flat.data(), n_ranks, n_rays, got.data());
+    xpbd::merge_first_hits<xpbd_ray_hit>(flat.data(), n_ranks, n_rays, got.data());
     for (uint32_t i = 0; i < n_rays; ++i) {
         std::vector<xpbd_ray_hit> all;
         for (const auto &row : rows)
@@ -102,7 +102,7 @@ int run_rays()
     if (int rc = check_rays("rays, one rank", one))
         return rc;
     std::vector<xpbd_ray_hit> got(257);
-    xpbd::merge_ray_hits(one[0].data(), 1, 257, got.data());
+    xpbd::merge_first_hits<xpbd_ray_hit>(one[0].data(), 1, 257, got.data());
     if (std::memcmp(got.data(), one[0].data(), 257 * sizeof(xpbd_ray_hit)) != 0)
         return fail("rays, one rank", "the row changed", 0);
     return 0;

@@ -1,5 +1,5 @@
-// sweep_merge_standalone_main.cpp -- the merge of the multi-GPU world's sweep queries (merge_sweep_hits, csrc/xpbd_merge.hpp) on
-// hand-made rows, with no device and no Python: built by tests/test_sweep_merge_standalone.py with plain g++, also under
+// sweep_merge_standalone_main.cpp -- the merge of the multi-GPU world's sweep queries (merge_first_hits<xpbd_sweep_hit>,
+// csrc/xpbd_merge.hpp) on hand-made rows, with no device and no Python: built by tests/test_sweep_merge_standalone.py with plain g++, also under
 // ASan/UBSan.  The expected winner of every sweep comes from sorting the ranks' records by (distance, body).  Exits non-zero with
 // a one-line message on the first difference.
 #include <algorithm>
@@ -48,7 +48,7 @@ int check(const char *scene, const std::vector<std::vector<xpbd_sweep_hit>> &row
     for (const auto &row : rows)
         flat.insert(flat.end(), row.begin(), row.end());
     std::vector<xpbd_sweep_hit> got(n);
-    xpbd::merge_sweep_hits(flat.data(), n_ranks, n, got.data());
+    xpbd::merge_first_hits<xpbd_sweep_hit>(flat.data(), n_ranks, n, got.data());
     for (uint32_t i = 0; i < n; ++i) {
         std::vector<xpbd_sweep_hit> all;
         for (const auto &row : rows)
@@ -71,7 +71,7 @@ int run()
         std::vector<xpbd_sweep_hit> flat(rows[0]);
         flat.insert(flat.end(), rows[1].begin(), rows[1].end());
         xpbd_sweep_hit got[3];
-        xpbd::merge_sweep_hits(flat.data(), 2, 3, got);
+        xpbd::merge_first_hits<xpbd_sweep_hit>(flat.data(), 2, 3, got);
         if (got[0].body != 5 || got[0].face != 1 || got[1].body != 3 || got[1].face != 0 || got[2].body != 2 || got[2].distance != 4.0)
             return fail("sweeps, by hand", "wrong winner", 0);
     }
@@ -108,11 +108,11 @@ int run()
         return rc;
     // one rank: its row as it is
     std::vector<xpbd_sweep_hit> got(257);
-    xpbd::merge_sweep_hits(rows[1].data(), 1, 257, got.data());
+    xpbd::merge_first_hits<xpbd_sweep_hit>(rows[1].data(), 1, 257, got.data());
     if (std::memcmp(got.data(), rows[1].data(), 257 * sizeof(xpbd_sweep_hit)) != 0)
         return fail("sweeps, one rank", "the row changed", 0);
     // no sweeps at all
-    xpbd::merge_sweep_hits(rows[1].data(), 4, 0, got.data());
+    xpbd::merge_first_hits<xpbd_sweep_hit>(rows[1].data(), 4, 0, got.data());
     return 0;
 }
 

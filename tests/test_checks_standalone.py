@@ -31,7 +31,7 @@ def test_checks_build_and_run_without_a_device(variant, tmp_path):
     assert build.returncode == 0, build.stdout
     run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
     assert run.returncode == 0, run.stdout + run.stderr
-    assert "24 calls ok" in run.stdout
+    assert "28 calls ok" in run.stdout
     if sanitized:
         assert run.stderr == ""
 
@@ -39,7 +39,7 @@ def test_checks_build_and_run_without_a_device(variant, tmp_path):
 def test_the_program_calls_every_check_twice():
     declared = set(re.findall(r"\bint (check_\w+)\(", open(os.path.join(CSRC, "xpbd_checks.hpp")).read()))
     main = open(os.path.join(ROOT, "tests", "checks_standalone_main.cpp")).read()
-    assert len(declared) == 12
+    assert len(declared) == 14
     for name in declared:
         assert len(re.findall(r"\b(?:accepted|refused)\(%s\(" % name, main)) == 2, name
 

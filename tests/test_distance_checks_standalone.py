@@ -2,8 +2,7 @@
 csrc/xpbd_error.cpp build with plain g++ (no hipcc, no ROCm include path) into a stand-alone program,
 tests/distance_checks_standalone_main.cpp, which makes the calls the check accepts and one call for every way it refuses,
 asserts the code returned and that each refusal's message names the `who` it was given, and exits 0.  It is declared in
-csrc/xpbd_checks_distance.hpp, a header of its own, so that the checks declared in xpbd_checks.hpp stay the set
-tests/test_checks_standalone.py holds them to.
+csrc/xpbd_checks.hpp with the other checks.
 
 The same program is also built and run under ASan + UBSan and must leave stderr empty.  A sanitizer-linked executable refuses
 to start where something else is preloaded into every process, so that variant is skipped there, and only there."""
@@ -44,6 +43,6 @@ def test_check_distance_builds_and_runs_without_a_device(variant, tmp_path):
 
 
 def test_the_header_declares_the_check_and_includes_no_hip_header():
-    text = open(os.path.join(CSRC, "xpbd_checks_distance.hpp")).read()
-    assert re.findall(r"\bint (check_\w+)\(", text) == ["check_distance"]
+    text = open(os.path.join(CSRC, "xpbd_checks.hpp")).read()
+    assert re.findall(r"\bint (check_\w+)\(", text).count("check_distance") == 1
     assert "#include <hip" not in text and "xpbd_internal.h" not in text

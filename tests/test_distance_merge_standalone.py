@@ -1,4 +1,4 @@
-"""merge_distance_hits (csrc/xpbd_merge.hpp) is host-only: it builds with plain g++ into a stand-alone program,
+"""merge_first_hits<xpbd_distance_hit> (csrc/xpbd_merge.hpp) is host-only: it builds with plain g++ into a stand-alone program,
 tests/distance_merge_standalone_main.cpp, which runs it on hand-made rows -- ties on distance broken by body, an overlap (0)
 against a positive distance, a rank without hits, all misses, one rank -- and exits 0.  No GPU and no Python extension involved.
 

@@ -31,7 +31,7 @@ def stepped(bodies, sid, kind, frames, substeps=20, mode=capi.MODE_CONTACTS):
 
 
 def cell_edge(kind, sid):
-    """The query grid's cell edge (xpbd_query.hip): 2 x the largest bounding radius of the shapes in use x (1 + 1e-6), the
+    """The query grid's cell edge (xpbd_query_grid.hip): 2 x the largest bounding radius of the shapes in use x (1 + 1e-6), the
     radius as xpbd_world_set_polytopes computes it."""
     rmax = 0.0
     for s in np.unique(sid):
