@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "xpbd_world_terrain_distance", "xpbd_world_terrain_distance_device",
     "xpbd_world_remove_bodies", "xpbd_world_remove_bodies_device", "xpbd_world_add_bodies",
     "xpbd_world_set_terrain", "xpbd_world_sample_terrain",
+    "xpbd_world_islands", "xpbd_world_islands_device",
 ]
 
 
@@ -285,6 +286,11 @@ CONTACT_POINT_DTYPE = np.dtype([("p_ref", "<f8", (3,)), ("p_inc", "<f8", (3,))])
 CONTACT_EVENT_DTYPE = np.dtype([("body_a", "<u4"), ("body_b", "<u4"), ("kind", "<u4")])
 CONTACT_BEGIN, CONTACT_END = 0, 1
 
+# Contact islands (EXTENSION): xpbd_island (40 bytes)
+ISLAND_DTYPE = np.dtype([("first_body", "<u4"), ("n_bodies", "<u4"), ("n_pairs", "<u4"), ("n_joints", "<u4"), ("n_anchors", "<u4"),
+                         ("n_grounded", "<u4"), ("max_speed2", "<f8"), ("max_angular_speed2", "<f8")])
+ISLAND_NONE = 0xFFFFFFFF          # island_of[] of a fixed body
+ISLANDS_NO_JOINTS, ISLANDS_NO_CONTACTS = 1, 2
 
 MANIFOLD_DTYPE = np.dtype([("n_points", "<u4"), ("feature", "<u4"), ("index_a", "<u4"), ("index_b", "<u4"),
                            ("separation", "<f8"), ("p_ref", "<f8", (8, 3)), ("p_inc", "<f8", (8, 3))])
@@ -459,6 +465,11 @@ def hip_lib():
         try:
             L.xpbd_world_set_terrain.argtypes = [C.c_void_p, C.POINTER(HEIGHTFIELD)]
             L.xpbd_world_sample_terrain.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            L.xpbd_world_islands.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, _u32p]
+            L.xpbd_world_islands_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -884,6 +895,24 @@ class World:
     def contact_events(self):
         """CONTACT_EVENT_DTYPE records: BEGINs then ENDs, each in (body_a, body_b) order."""
         return _contact_events(hip_lib().xpbd_world_contact_report_counts, hip_lib().xpbd_world_download_contact_events, self._h)
+
+    # contact islands (include/xpbd.h, "Contact ISLANDS"): connected groups of the non-fixed bodies and their rest state
+    def islands(self, flags=0, cap=None):
+        """(island_of, ISLAND_DTYPE records): island_of[i] = island of body i, ISLAND_NONE for a fixed body.  cap: room for
+        that many records (None: one per body, which always suffices; a smaller one raises E_CAPACITY when it is short).  Waits."""
+        island_of = np.empty(self.n, dtype=np.uint32)
+        room = self.n if cap is None else cap
+        out = np.zeros(room, dtype=ISLAND_DTYPE)
+        total = C.c_uint32(0)
+        _check(hip_lib().xpbd_world_islands(self._h, flags, island_of.ctypes.data if self.n else None, out.ctypes.data if room else None,
+                                            room, C.byref(total)))
+        return island_of, out[:total.value]
+
+    def islands_device(self, flags, dev_island_of_ptr, dev_islands_ptr, cap, dev_n_islands_ptr):
+        """Device arrays (island_of: uint32 per body or None; records: cap x 40 bytes, 8-byte aligned; the count: one uint32);
+        enqueues on the world's stream and returns at once."""
+        _check(hip_lib().xpbd_world_islands_device(self._h, flags, C.c_void_p(dev_island_of_ptr or None), C.c_void_p(dev_islands_ptr or None),
+                                                   cap, C.c_void_p(dev_n_islands_ptr or None)))
 
 
 def _report_counts(counts_fn, h):

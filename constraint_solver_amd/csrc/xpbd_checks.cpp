@@ -201,6 +201,28 @@ int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32
     return XPBD_OK;
 }
 
+int IslandsTarget::check(const char *who, uint32_t flags, const void *records, uint32_t cap, const void *count) const
+{
+    if (!count)
+        return set_error(XPBD_E_INVALID, "%s: NULL count", who);
+    if (!records && cap)
+        return set_error(XPBD_E_INVALID, "%s: NULL records with cap = %u", who, cap);
+    if (flags & ~(XPBD_ISLANDS_NO_JOINTS | XPBD_ISLANDS_NO_CONTACTS))
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, flags);
+    if ((flags & XPBD_ISLANDS_NO_JOINTS) && (flags & XPBD_ISLANDS_NO_CONTACTS))
+        return set_error(XPBD_E_INVALID, "%s: XPBD_ISLANDS_NO_JOINTS and XPBD_ISLANDS_NO_CONTACTS together leave no edges", who);
+    if (n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    if (flags & XPBD_ISLANDS_NO_CONTACTS)
+        return XPBD_OK;
+    if (!report_on)
+        return set_error(XPBD_E_INVALID, "%s: contact reports are off (xpbd_world_set_contact_report); XPBD_ISLANDS_NO_CONTACTS needs none", who);
+    if (!report_frame)
+        return set_error(XPBD_E_INVALID, "%s: no report: no substep of XPBD_MODE_CONTACTS has run since the last broadphase, upload, "
+                                         "history restore, enable, failed step or step in another mode", who);
+    return XPBD_OK;
+}
+
 // The flags' part of the scene queries' checks: `known` are the family's own bits.
 int check_query_flags(const char *who, const QueryTarget &t, uint32_t flags, uint32_t known)
 {

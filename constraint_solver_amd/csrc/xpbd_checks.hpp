@@ -58,5 +58,14 @@ int check_materials(const char *who, const xpbd_material *materials, uint32_t n)
 int check_edit_indices(const char *who, const uint32_t *indices, uint32_t n, uint32_t n_bodies, bool unique);
 int check_edit_finite(const char *who, const char *what, const double *values, size_t count);
 int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32_t n_bodies);
+// ... of xpbd_world_islands and _islands_device (include/xpbd.h, "Contact ISLANDS"), after the caller has dealt with a NULL
+// world: what the call is made on, and its check -- a NULL count, a NULL record buffer with a nonzero cap, unknown flags, both
+// flags, a world without bodies, and, without XPBD_ISLANDS_NO_CONTACTS, a report that xpbd_world_contact_report_counts would
+// refuse (reporting off; no frame).
+struct IslandsTarget {
+    uint32_t n_bodies;
+    bool report_on, report_frame;
+    int check(const char *who, uint32_t flags, const void *records, uint32_t cap, const void *count) const;
+};
 
 } // namespace xpbd

@@ -7,6 +7,7 @@
 //   xpbd_world_report.cpp    ContactReport and the report entry points
 //   xpbd_world_query.cpp     the scene-query host layer and entry points
 //   xpbd_world_edit.cpp      body edits, population changes, re-packing a shard
+//   xpbd_world_islands.cpp   Islands and the island entry points
 #pragma once
 
 #include <cstdint>
@@ -20,6 +21,7 @@
 #include "xpbd_kernels.h"
 #include "xpbd_contacts.h"
 #include "xpbd_gjk.h"
+#include "xpbd_islands.h"
 #include "xpbd_pairs.h"
 #include "xpbd_population_remap.hpp"
 #include "xpbd_query.h"
@@ -251,6 +253,17 @@ struct History {
     std::vector<uint8_t> stepped;
 };
 
+// Contact islands (xpbd_world_islands*; xpbd_islands.h; xpbd_world_islands.cpp): the scratch of one call, reserved like the
+// report's -- sized by the body count, grown only when it has grown.  result: the give-up word and the island count of the
+// last call, next to each other; records: what the host variant downloads from.  The operations read the bodies, the joints,
+// the report and the stream of the world `w` they belong to.
+struct Islands {
+    DeviceBuffer parent, fixed, flag, scan, result, island_of, records;
+
+    int reserve(const xpbd_world *w, bool host_island_of, uint32_t host_records);
+    int enqueue(xpbd_world *w, uint32_t flags, uint32_t *dev_island_of, xpbd_island *dev_records, uint32_t cap, uint32_t *dev_total);
+};
+
 #pragma GCC visibility pop
 
 struct xpbd_world {
@@ -354,6 +367,8 @@ struct xpbd_world {
     PopulationScratch pop;
     // state history (xpbd_world_history_*): `length` slots of history_slot_bytes() in one growing block
     History history;
+    // contact islands (xpbd_world_islands, _islands_device): scratch of one call; a world that never calls them holds none
+    Islands islands;
     size_t history_slot_bytes() const { return ((size_t)xpbd::kDynFields * stride * 8 + (size_t)stride * 4 + 255) / 256 * 256; }
 
     // frame_set: which of the two frame sets the substep reads (always 0 outside step_contacts)

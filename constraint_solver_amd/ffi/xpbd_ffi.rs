@@ -363,6 +363,24 @@ pub struct XpbdContactEvent {
     pub kind: u32,
 }
 
+pub const XPBD_ISLAND_NONE: u32 = 0xFFFF_FFFF;
+pub const XPBD_ISLANDS_NO_JOINTS: u32 = 1;
+pub const XPBD_ISLANDS_NO_CONTACTS: u32 = 2;
+
+/// xpbd_island (40 bytes): one connected group of non-fixed bodies (include/xpbd.h, "Contact ISLANDS")
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdIsland {
+    pub first_body: u32,
+    pub n_bodies: u32,
+    pub n_pairs: u32,
+    pub n_joints: u32,
+    pub n_anchors: u32,
+    pub n_grounded: u32,
+    pub max_speed2: f64,
+    pub max_angular_speed2: f64,
+}
+
 #[repr(C)]
 pub struct XpbdWorld {
     _private: [u8; 0],
@@ -549,6 +567,10 @@ extern "C" {
     pub fn xpbd_world_download_pair_contacts(w: *mut XpbdWorld, pairs: *mut XpbdPairContact, pair_cap: u32, points: *mut XpbdContactPoint,
                                              point_cap: u32, n_pairs: *mut u32, n_points: *mut u32) -> c_int;
     pub fn xpbd_world_download_contact_events(w: *mut XpbdWorld, out: *mut XpbdContactEvent, cap: u32, n_out: *mut u32) -> c_int;
+    pub fn xpbd_world_islands(w: *mut XpbdWorld, flags: u32, island_of: *mut u32, islands: *mut XpbdIsland, cap: u32,
+                              n_islands: *mut u32) -> c_int;
+    pub fn xpbd_world_islands_device(w: *mut XpbdWorld, flags: u32, dev_island_of: *mut u32, dev_islands: *mut XpbdIsland, cap: u32,
+                                     dev_n_islands: *mut u32) -> c_int;
     pub fn xpbd_multi_world_set_contact_report(mw: *mut XpbdMultiWorld, enable: u32) -> c_int;
     pub fn xpbd_multi_world_contact_report_counts(mw: *mut XpbdMultiWorld, out: *mut u32) -> c_int;
     pub fn xpbd_multi_world_download_pair_contacts(mw: *mut XpbdMultiWorld, pairs: *mut XpbdPairContact, pair_cap: u32,

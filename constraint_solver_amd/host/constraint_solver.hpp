@@ -620,6 +620,19 @@ class BatchWorld {
         check(xpbd_world_download_contact_events(w_, out.empty() ? nullptr : out.data(), (uint32_t)out.size(), &n_out));
         return out;
     }
+    // contact islands (include/xpbd.h, "Contact ISLANDS"): the connected groups of the non-fixed bodies over the frame's touching
+    // pairs and the joints (flags: XPBD_ISLANDS_*); island_of: per body, XPBD_ISLAND_NONE for a fixed one, or NULL
+    std::vector<xpbd_island> islands(uint32_t flags = 0, std::vector<uint32_t> *island_of = nullptr)
+    {
+        const uint32_t n = xpbd_world_body_count(w_);
+        if (island_of)
+            island_of->resize(n);
+        std::vector<xpbd_island> out(n); // (at most one island per body)
+        uint32_t total = 0;
+        check(xpbd_world_islands(w_, flags, island_of && n ? island_of->data() : nullptr, out.empty() ? nullptr : out.data(), n, &total));
+        out.resize(total);
+        return out;
+    }
 
     std::vector<xpbd_contact> contacts()
     {

@@ -1479,6 +1479,80 @@ int  xpbd_multi_world_download_pair_contacts(xpbd_multi_world *mw, xpbd_pair_con
                                              xpbd_contact_point *points, uint32_t point_cap, uint32_t *n_pairs, uint32_t *n_points);
 int  xpbd_multi_world_download_contact_events(xpbd_multi_world *mw, xpbd_contact_event *out, uint32_t cap, uint32_t *n_out);
 
+/* ---------------------------------------------------------------------------
+ * Contact ISLANDS (EXTENSION): which bodies belong together -- a pile, a jointed mechanism, a stack on a slab -- what holds
+ * each group up, and whether it has stopped moving.  NOT in the reference, whose world is a fixed pair of `Rigid`s
+ * (src/world.rs).  One connected-components pass on the device over what is already resident there: the contact report's
+ * touching pairs, the joints, the mass properties, the velocities and the last substep's ground contacts.
+ *
+ * Fixed body.  A body is fixed when inverse_mass == 0 and all nine inverse_inertia entries are == 0.  A body with zero
+ * inverse mass but a nonzero inverse inertia can still turn: it is not fixed.
+ *
+ * Graph.  The nodes are the non-fixed bodies.  The edges are (a) every pair of the current report frame's touching set S
+ * ("Contact REPORTS" above: the pairs the BEGIN / END events use, those that touched in at least one substep of the frame)
+ * and (b) every joint of the world, of any kind.  An edge with ONE fixed end connects nothing; it is counted as an anchor
+ * of its other end's island (otherwise everything resting on one slab would be a single island).  An edge between two fixed
+ * bodies is ignored.
+ *
+ * Island.  One connected component; a non-fixed body without edges is an island of one.  Islands are numbered 0..K-1 in
+ * ascending order of their smallest member.  The numbering, like everything else the calls return, does not depend on
+ * scheduling: the grouping keeps the smallest member as the root of every component, the numbers come from a scan, and the
+ * records are integer sums and integer maxima.
+ *
+ * Records.  island_of[i] is the island of body i, XPBD_ISLAND_NONE for a fixed body.  Per island:
+ *   first_body          its smallest member;
+ *   n_bodies            its members;
+ *   n_pairs, n_joints   touching pairs / joints with both ends in the island (the same two bodies joined twice count twice);
+ *   n_anchors           touching pairs and joints between a member and a fixed body;
+ *   n_grounded          members whose LAST substep had a ground contact (plane or terrain): the contact mask as it stands,
+ *                       so zero after an upload or a population change, and what the history restored after a restore;
+ *   max_speed2          the largest v.x * v.x + v.y * v.y + v.z * v.z (evaluated left to right) over the members' velocity,
+ *   max_angular_speed2  the same of angular_velocity.  Both maxima are taken over the BIT PATTERNS of the values with the
+ *                       sign bit cleared, compared as unsigned 64-bit integers: order-free, exact, and a NaN shows as a NaN.
+ * With XPBD_ISLANDS_NO_JOINTS the edges (b), with XPBD_ISLANDS_NO_CONTACTS the edges (a) count NOWHERE: they add neither
+ * connectivity nor n_pairs / n_joints / n_anchors.  XPBD_ISLANDS_NO_CONTACTS needs no contact report.
+ *
+ * Calls.  xpbd_world_islands takes host arrays and waits for the device.  It always writes the island count to *n_islands
+ * and fills min(count, cap) records; a count above cap is XPBD_E_CAPACITY, as xpbd_world_download_contacts.  islands == NULL
+ * with cap == 0 and island_of == NULL are allowed.  xpbd_world_islands_device takes DEVICE arrays (8-byte aligned records)
+ * and only enqueues on the world's stream (xpbd_world_get_stream / _set_stream): no wait, no host read, the number of
+ * touching pairs is read on the device; it writes the count to *dev_n_islands and only the first `cap` records.  (The
+ * unit's scratch grows on the first call and when the body or pair count has grown: only then does the call wait for the
+ * stream, as every stream-ordered call of the library.)  Its flags compose with xpbd_world_remove_bodies_device.
+ *
+ * The grouping is lock-free and every loop of it is bounded by construction; the bound is carried anyway.  Should a lane
+ * reach it, xpbd_world_islands returns XPBD_E_HIP and xpbd_world_islands_device leaves XPBD_ISLAND_NONE in *dev_n_islands.
+ *
+ * XPBD_E_INVALID, nothing written: a NULL world or count; a NULL record buffer with a nonzero cap; unknown flag bits; both
+ * flags together; a world without resident bodies; and, without XPBD_ISLANDS_NO_CONTACTS, exactly when
+ * xpbd_world_contact_report_counts is XPBD_E_INVALID (reporting off, no report frame: "Contact REPORTS").
+ *
+ * The calls only read: bodies, report downloads, events, history and every later step are the same bits whether or not they
+ * were made, and a world that never makes them enqueues nothing new.
+ *
+ * Not here: the multi-GPU world (xpbd_multi_world_*).  Its report lives merged on the host and its bodies on several
+ * devices; islands there are a different design.  These calls cover the single world only.
+ * ------------------------------------------------------------------------- */
+#define XPBD_ISLAND_NONE         0xFFFFFFFFu /* island_of[] of a fixed body */
+#define XPBD_ISLANDS_NO_JOINTS   1u          /* edges (a) only */
+#define XPBD_ISLANDS_NO_CONTACTS 2u          /* edges (b) only; needs no contact report */
+
+typedef struct xpbd_island {     /* 40 bytes */
+    uint32_t first_body;         /* smallest member */
+    uint32_t n_bodies;
+    uint32_t n_pairs;            /* touching pairs with both bodies in the island */
+    uint32_t n_joints;           /* joints with both ends in the island */
+    uint32_t n_anchors;          /* touching pairs and joints between a member and a fixed body */
+    uint32_t n_grounded;         /* members whose last substep had a ground (plane or terrain) contact */
+    double   max_speed2;         /* max over members of v.x*v.x + v.y*v.y + v.z*v.z, left to right */
+    double   max_angular_speed2; /* the same of angular_velocity */
+} xpbd_island;
+
+int  xpbd_world_islands(xpbd_world *w, uint32_t flags, uint32_t *island_of /* [body count] or NULL */,
+                        xpbd_island *islands, uint32_t cap, uint32_t *n_islands);
+int  xpbd_world_islands_device(xpbd_world *w, uint32_t flags, uint32_t *dev_island_of /* or NULL */,
+                               xpbd_island *dev_islands, uint32_t cap, uint32_t *dev_n_islands);
+
 /* Diagnostics: quotient[i] = a[i] / b[i], root[i] = sqrt(a[i]) computed on the
  * device with the stepper's own code generation.  Bit-exact contact lists need
  * both to be correctly rounded; the parity tests check this against the host. */
