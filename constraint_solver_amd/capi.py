@@ -69,6 +69,8 @@ ABI_SYMBOLS = [
     "xpbd_world_remove_bodies", "xpbd_world_remove_bodies_device", "xpbd_world_add_bodies",
     "xpbd_world_set_terrain", "xpbd_world_sample_terrain",
     "xpbd_world_islands", "xpbd_world_islands_device",
+    "xpbd_world_set_sleeping", "xpbd_world_sleep_state", "xpbd_world_sleep_state_device", "xpbd_world_wake_bodies",
+    "xpbd_world_wake_bodies_device",
 ]
 
 
@@ -292,6 +294,14 @@ ISLAND_DTYPE = np.dtype([("first_body", "<u4"), ("n_bodies", "<u4"), ("n_pairs",
 ISLAND_NONE = 0xFFFFFFFF          # island_of[] of a fixed body
 ISLANDS_NO_JOINTS, ISLANDS_NO_CONTACTS = 1, 2
 
+
+class SLEEP_CONFIG(C.Structure):
+    """xpbd_sleep_config (24 bytes): island sleeping (EXTENSION)"""
+    _fields_ = [("linear_speed", C.c_double), ("angular_speed", C.c_double), ("frames_to_sleep", C.c_uint32), ("flags", C.c_uint32)]
+
+
+SLEEP_GROUP_NONE = 0xFFFFFFFF     # group[] of a body that is awake
+
 MANIFOLD_DTYPE = np.dtype([("n_points", "<u4"), ("feature", "<u4"), ("index_a", "<u4"), ("index_b", "<u4"),
                            ("separation", "<f8"), ("p_ref", "<f8", (8, 3)), ("p_inc", "<f8", (8, 3))])
 
@@ -470,6 +480,14 @@ def hip_lib():
         try:
             L.xpbd_world_islands.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, _u32p]
             L.xpbd_world_islands_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            L.xpbd_world_set_sleeping.argtypes = [C.c_void_p, C.POINTER(SLEEP_CONFIG)]
+            L.xpbd_world_sleep_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _u32p]
+            L.xpbd_world_sleep_state_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.xpbd_world_wake_bodies.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_wake_bodies_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -913,6 +931,42 @@ class World:
         enqueues on the world's stream and returns at once."""
         _check(hip_lib().xpbd_world_islands_device(self._h, flags, C.c_void_p(dev_island_of_ptr or None), C.c_void_p(dev_islands_ptr or None),
                                                    cap, C.c_void_p(dev_n_islands_ptr or None)))
+
+    # island sleeping (include/xpbd.h, "SLEEPING"): resting islands leave the step until something disturbs them
+    def set_sleeping(self, linear_speed=None, angular_speed=None, frames_to_sleep=None, flags=0):
+        """Turns sleeping on with these thresholds, or off when called without arguments."""
+        if linear_speed is None and angular_speed is None and frames_to_sleep is None:
+            _check(hip_lib().xpbd_world_set_sleeping(self._h, None))
+            return
+        cfg = SLEEP_CONFIG(linear_speed, angular_speed, frames_to_sleep, flags)
+        _check(hip_lib().xpbd_world_set_sleeping(self._h, C.byref(cfg)))
+
+    def sleep_state(self):
+        """(asleep uint8[n], rest_frames uint32[n], group uint32[n], (asleep bodies, sleeping groups, woken, put to sleep by the
+        last pass)).  Waits."""
+        asleep = np.zeros(self.n, dtype=np.uint8)
+        rest = np.zeros(self.n, dtype=np.uint32)
+        group = np.zeros(self.n, dtype=np.uint32)
+        counts = (C.c_uint32 * 4)()
+        _check(hip_lib().xpbd_world_sleep_state(self._h, asleep.ctypes.data if self.n else None, rest.ctypes.data if self.n else None,
+                                                group.ctypes.data if self.n else None, counts))
+        return asleep, rest, group, tuple(int(v) for v in counts)
+
+    def sleep_state_device(self, dev_asleep_ptr, dev_rest_frames_ptr, dev_group_ptr, dev_counts_ptr):
+        """Device arrays (any may be None); enqueues on the world's stream and returns at once."""
+        _check(hip_lib().xpbd_world_sleep_state_device(self._h, C.c_void_p(dev_asleep_ptr or None), C.c_void_p(dev_rest_frames_ptr or None),
+                                                       C.c_void_p(dev_group_ptr or None), C.c_void_p(dev_counts_ptr or None)))
+
+    def wake_bodies(self, indices=None):
+        """The groups of the listed bodies wake at the start of the next step; None: everybody."""
+        if indices is None:
+            _check(hip_lib().xpbd_world_wake_bodies(self._h, None, 0))
+            return
+        idx = np.ascontiguousarray(indices, dtype=np.uint32)
+        _check(hip_lib().xpbd_world_wake_bodies(self._h, idx.ctypes.data if idx.size else None, idx.size))
+
+    def wake_bodies_device(self, dev_indices_ptr, n):
+        _check(hip_lib().xpbd_world_wake_bodies_device(self._h, C.c_void_p(dev_indices_ptr or None), n))
 
 
 def _report_counts(counts_fn, h):

@@ -223,6 +223,42 @@ int IslandsTarget::check(const char *who, uint32_t flags, const void *records, u
     return XPBD_OK;
 }
 
+int SleepTarget::check(const char *who, const xpbd_sleep_config &cfg) const
+{
+    if (!(cfg.linear_speed >= 0.0) || !std::isfinite(cfg.linear_speed))
+        return set_error(XPBD_E_INVALID, "%s: linear_speed = %g (must be finite and >= 0)", who, cfg.linear_speed);
+    if (!(cfg.angular_speed >= 0.0) || !std::isfinite(cfg.angular_speed))
+        return set_error(XPBD_E_INVALID, "%s: angular_speed = %g (must be finite and >= 0)", who, cfg.angular_speed);
+    if (cfg.frames_to_sleep == 0)
+        return set_error(XPBD_E_INVALID, "%s: frames_to_sleep must be >= 1", who);
+    if (cfg.flags)
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x", who, cfg.flags);
+    if (mode != XPBD_MODE_CONTACTS)
+        return set_error(XPBD_E_INVALID, "%s: sleeping needs XPBD_MODE_CONTACTS (world is in mode %u)", who, mode);
+    if (!report_on)
+        return set_error(XPBD_E_INVALID, "%s: sleeping needs the contact report (xpbd_world_set_contact_report)", who);
+    return XPBD_OK;
+}
+
+int SleepTarget::state_check(const char *who) const
+{
+    if (!sleeping_on)
+        return set_error(XPBD_E_INVALID, "%s: sleeping is off (xpbd_world_set_sleeping)", who);
+    return XPBD_OK;
+}
+
+int SleepTarget::wake_check(const char *who, const uint32_t *indices, uint32_t n) const
+{
+    if (int rc = state_check(who))
+        return rc;
+    if (!indices && n)
+        return set_error(XPBD_E_INVALID, "%s: NULL indices with n = %u (NULL with n == 0 wakes everybody)", who, n);
+    for (uint32_t k = 0; k < n; ++k)
+        if (indices[k] >= n_bodies)
+            return set_error(XPBD_E_INVALID, "%s: indices[%u] = %u but the world holds %u bodies", who, k, indices[k], n_bodies);
+    return XPBD_OK;
+}
+
 // The flags' part of the scene queries' checks: `known` are the family's own bits.
 int check_query_flags(const char *who, const QueryTarget &t, uint32_t flags, uint32_t known)
 {

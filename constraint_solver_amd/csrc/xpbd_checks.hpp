@@ -67,5 +67,16 @@ struct IslandsTarget {
     bool report_on, report_frame;
     int check(const char *who, uint32_t flags, const void *records, uint32_t cap, const void *count) const;
 };
+// ... of the sleeping calls (include/xpbd.h, "SLEEPING"), after the caller has dealt with a NULL world: what the call is made
+// on.  check: xpbd_world_set_sleeping with a configuration (a negative or non-finite speed, frames_to_sleep == 0, flags, a
+// mode other than XPBD_MODE_CONTACTS, the contact report off).  state_check: the state and wake calls (sleeping off).
+// wake_check: the host variant's index list on top of it (NULL with n != 0, an index >= n_bodies).
+struct SleepTarget {
+    uint32_t mode, n_bodies;
+    bool report_on, sleeping_on;
+    int check(const char *who, const xpbd_sleep_config &cfg) const;
+    int state_check(const char *who) const;
+    int wake_check(const char *who, const uint32_t *indices, uint32_t n) const;
+};
 
 } // namespace xpbd

@@ -111,6 +111,14 @@ struct ContactBuffers {
     Terrain terrain;
 };
 
+// Sleeping (xpbd_world_set_sleeping): which bodies are inert -- asleep or fixed -- as the frame started.  A pair whose two ends
+// are both inert is no neighbour pair.  Default: none, the broadphase launches the kernels it launched before; with a table it
+// launches the forms that take this as one more argument (ContactBuffers and the kernels that take it stay as they are).
+struct InertBodies {
+    const uint8_t *inert = nullptr; // [n]
+    uint8_t *slot_inert = nullptr;  // [stride] inert[items[s]] (bucket order, written by launch_build_buckets)
+};
+
 // Which bodies a per-body kernel of the pipeline works on.  Default: all of them.  The multi-GPU world (xpbd_multi.cpp) runs
 // the BOUNDARY bodies first, with their end-of-substep state exported straight into the halo send buffer, starts the
 // exchange, runs the interior bodies meanwhile (`skip` marks boundary and ghost bodies), and finally gives the ghosts their
@@ -127,10 +135,10 @@ struct BodySubset {
 // ---- broadphase (once per step call) -------------------------------------------------------------
 hipError_t launch_bounds_and_cells(const BodyArrays &b, const PolytopeTables &t, const double *shape_radius,
                                    double dt, double pad, const ContactBuffers &c, hipStream_t stream);
-hipError_t launch_build_buckets(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream);
+hipError_t launch_build_buckets(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream, const InertBodies &inert = InertBodies());
 // counts into nbr_off / pair_first (then scanned in place; totals at [n])
-hipError_t launch_neighbour_count(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream);
-hipError_t launch_neighbour_fill(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream);
+hipError_t launch_neighbour_count(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream, const InertBodies &inert = InertBodies());
+hipError_t launch_neighbour_fill(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream, const InertBodies &inert = InertBodies());
 
 // ---- per substep -----------------------------------------------------------------------------------
 // integrate + ground contacts (sequential per body): reads b.dyn, writes the body's record (frames, pose') into c.rec
@@ -162,8 +170,10 @@ hipError_t launch_joint_extras(double h, const ContactBuffers &c, hipStream_t st
 // (the dyn_out of launch_pair_solve_derive; NOT b.dyn), `start` velocity and angular velocity at the start of the substep
 // ([6][stride]: fields D_VEL.. of b.dyn before launch_integrate_ground), ground_masks the masks of launch_integrate_ground.
 // Every body's end-of-substep state (pose copied, velocities updated) goes to b.dyn, which no lane of the launch reads.
+// With subset.skip (the sleepers of a world with sleeping on) the bodies it marks end as `post` holds them: the caller has put
+// their state there, the pass runs over everybody and they are put back from it.  (No list form.)
 hipError_t launch_restitution(const BodyArrays &b, const double *post, const double *start, const ShapeTable &s, const ContactBuffers &c,
-                              const uint32_t *ground_masks, hipStream_t stream);
+                              const uint32_t *ground_masks, hipStream_t stream, const BodySubset &subset = BodySubset());
 
 // Heightfield terrain.  The plane table of a field from its heights (device, ny rows of nx): both triangles of every cell into
 // planes[cell][8], `t` describing the field (t.planes is not read).  And the terrain at n points xy[2k..] (device arrays):

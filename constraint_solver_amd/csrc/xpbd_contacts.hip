@@ -304,6 +304,14 @@ __global__ void k_gather_slots(BodyArrays b, ContactBuffers c)
     }
 }
 
+// ... and, in a world with sleeping on, who of them is inert.
+__global__ void k_gather_slot_inert(BodyArrays b, ContactBuffers c, InertBodies inert)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < b.n)
+        inert.slot_inert[s] = inert.inert[c.items[s]];
+}
+
 constexpr uint32_t kCellLanes = 8;    // lanes per body in the neighbour kernels
 constexpr uint32_t kNbrStage = 128;   // neighbours of one body staged in LDS for the rank sort
 constexpr uint32_t kBodiesPerBlock = kBlock / kCellLanes;
@@ -325,6 +333,12 @@ __device__ __forceinline__ bool joined(const ContactBuffers &c, uint32_t i, uint
     return false;
 }
 
+// Is body i / the body in slot s inert?  (Without a table: nobody is.)
+__device__ __forceinline__ bool inert_body(uint32_t) { return false; }
+__device__ __forceinline__ bool inert_body(uint32_t i, const InertBodies &t) { return t.inert[i] != 0; }
+__device__ __forceinline__ bool inert_slot(uint32_t) { return false; }
+__device__ __forceinline__ bool inert_slot(uint32_t s, const InertBodies &t) { return t.slot_inert[s] != 0; }
+
 // Neighbour search of body i by its group of kCellLanes lanes (`cl` = lane inside the group, `g` = the group's row in
 // the LDS tables).  First the 27 bucket ranges are fetched side by side; then the lanes stride over the CONCATENATION
 // of the 27 ranges, so every lane has independent loads in flight whatever the occupancy of the single cells.
@@ -334,9 +348,12 @@ __device__ __forceinline__ bool joined(const ContactBuffers &c, uint32_t i, uint
 // FILTER: a pair whose collision filters exclude each other is no neighbour (the candidate's filter is read in slot order,
 // next to its sphere); JOINTED: nor is a pair joined by a joint.  Both tests are symmetric in i and j -- count, fill and
 // the pair index of both ends rely on every pair being seen from both of them or from neither.
-template <bool FILTER, bool JOINTED, class Visit>
+// inert... (nothing, or the InertBodies of a world with sleeping on): nor is a pair whose two ends are both inert, asleep or
+// fixed; one byte per slot, read as the slot's filter is.  Without the argument the two tests are constants and the function
+// is what it was before there was one.
+template <bool FILTER, bool JOINTED, class Visit, class... Inert>
 __device__ __forceinline__ void for_each_neighbour(const BodyArrays &b, const ContactBuffers &c, CellRanges &r, uint32_t i, bool live,
-                                                   uint32_t g, uint32_t cl, Visit visit)
+                                                   uint32_t g, uint32_t cl, Visit visit, const Inert &...inert)
 {
     const size_t st = b.stride;
     int32_t cx = 0, cy = 0, cz = 0;
@@ -359,6 +376,7 @@ __device__ __forceinline__ void for_each_neighbour(const BodyArrays &b, const Co
     uint2 fi = {0u, 0u};
     if (FILTER)
         fi = c.filter[i];
+    const bool inert_i = inert_body(i, inert...);
     uint32_t k = 0, base = 0; // cell being walked and the position of its first candidate in the concatenation
     for (uint32_t q = cl;; q += kCellLanes) {
         while (k < 27 && q >= base + r.len[g][k])
@@ -380,6 +398,8 @@ __device__ __forceinline__ void for_each_neighbour(const BodyArrays &b, const Co
             continue;
         if (JOINTED && joined(c, i, j))
             continue;
+        if (inert_i && inert_slot(s, inert...))
+            continue;
         visit(j);
     }
 }
@@ -392,8 +412,9 @@ __device__ __forceinline__ uint32_t cell_group_sum(uint32_t v)
 }
 
 // Counts of all neighbours of every body and of those with a larger id.
-template <bool FILTER, bool JOINTED>
-__global__ void __launch_bounds__(kBlock) k_neighbour_count(BodyArrays b, ContactBuffers c)
+// (inert...: see for_each_neighbour; the kernels of a world with sleeping on take the table as a third argument)
+template <bool FILTER, bool JOINTED, class... Inert>
+__global__ void __launch_bounds__(kBlock) k_neighbour_count(BodyArrays b, ContactBuffers c, Inert... inert)
 {
     __shared__ CellRanges ranges;
     const uint32_t g = threadIdx.x / kCellLanes, cl = threadIdx.x % kCellLanes;
@@ -406,7 +427,7 @@ __global__ void __launch_bounds__(kBlock) k_neighbour_count(BodyArrays b, Contac
     for_each_neighbour<FILTER, JOINTED>(b, c, ranges, i, live, g, cl, [&](uint32_t j) {
         ++all;
         upper += j > i;
-    });
+    }, inert...);
     if (!live)
         return;
     all = cell_group_sum(all);
@@ -420,8 +441,8 @@ __global__ void __launch_bounds__(kBlock) k_neighbour_count(BodyArrays b, Contac
 // Neighbour list of every body, ASCENDING, the pair list i < j in (i, j) order, and upper_start.  The lanes append
 // their finds to an LDS list in arrival order; a rank sort (ids are distinct) then gives every entry its final
 // place, so the result does not depend on that order.  Lists longer than kNbrStage take a one-lane path.
-template <bool FILTER, bool JOINTED>
-__global__ void __launch_bounds__(kBlock) k_neighbour_fill(BodyArrays b, ContactBuffers c)
+template <bool FILTER, bool JOINTED, class... Inert>
+__global__ void __launch_bounds__(kBlock) k_neighbour_fill(BodyArrays b, ContactBuffers c, Inert... inert)
 {
     __shared__ CellRanges ranges;
     __shared__ uint32_t stage[kBodiesPerBlock][kNbrStage];
@@ -444,7 +465,7 @@ __global__ void __launch_bounds__(kBlock) k_neighbour_fill(BodyArrays b, Contact
             stage[g][pos] = j;
         else
             c.nbr[lo + pos] = j;
-    });
+    }, inert...);
     __syncthreads();
     if (!live)
         return;
@@ -1540,6 +1561,17 @@ __global__ void __launch_bounds__(kBlock) k_restitution(BodyArrays b, const doub
     store_dynamic(b.dyn, st, i, d);
 }
 
+// The pass has no subset form.  The bodies a BodySubset skips (the sleepers of a world with sleeping on) are put back
+// afterwards from `post`, which holds their state as it was: one lane per body, 13 stores for a skipped one.
+__global__ void __launch_bounds__(kBlock) k_restitution_put_back(BodyArrays b, const double *__restrict__ post, const uint8_t *__restrict__ skip)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b.n || !skip[i])
+        return;
+    for (uint32_t f = 0; f < kDynFields; ++f)
+        b.dyn[(size_t)f * b.stride + i] = post[(size_t)f * b.stride + i];
+}
+
 // Halo exchange: one lane per (body, field); the buffer side is contiguous, the SoA side is a gather.
 __global__ void k_export_dynamic(BodyArrays b, const uint32_t *__restrict__ indices, uint32_t n, double *__restrict__ buf)
 {
@@ -1807,7 +1839,7 @@ hipError_t launch_bounds_and_cells(const BodyArrays &b, const PolytopeTables &t,
     return hipGetLastError();
 }
 
-hipError_t launch_build_buckets(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream)
+hipError_t launch_build_buckets(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream, const InertBodies &inert)
 {
     hipError_t e = launch_exclusive_scan(c.bucket_start, c.table_size, c.scan_scratch, stream);
     if (e != hipSuccess || b.n == 0)
@@ -1815,25 +1847,32 @@ hipError_t launch_build_buckets(const BodyArrays &b, const ContactBuffers &c, hi
     hipLaunchKernelGGL(k_scatter, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
     hipLaunchKernelGGL(k_rank_items, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
     hipLaunchKernelGGL(k_gather_slots, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
+    if (inert.inert)
+        hipLaunchKernelGGL(k_gather_slot_inert, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c, inert);
     return hipGetLastError();
 }
 
 // Which form of the neighbour kernels a broadphase runs: bit 0 = group / mask test, bit 1 = jointed-pair test (only when
 // there are joints).  A world without filters runs the plain form, the loads of which are those of a world before filters.
-static uint32_t filter_variant(const ContactBuffers &c)
+// Bit 2 = both-ends-inert test (only with sleeping on): the kernels that take the table.
+static uint32_t filter_variant(const ContactBuffers &c, const InertBodies &inert)
 {
-    return (c.filter ? 1u : 0u) | (c.filter_jointed && c.joint_off ? 2u : 0u);
+    return (c.filter ? 1u : 0u) | (c.filter_jointed && c.joint_off ? 2u : 0u) | (inert.inert ? 4u : 0u);
 }
 
-hipError_t launch_neighbour_count(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream)
+hipError_t launch_neighbour_count(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream, const InertBodies &inert)
 {
     if (b.n) {
         const dim3 grid((b.n + kBodiesPerBlock - 1) / kBodiesPerBlock);
-        switch (filter_variant(c)) {
+        switch (filter_variant(c, inert)) {
         case 0: hipLaunchKernelGGL((k_neighbour_count<false, false>), grid, dim3(kBlock), 0, stream, b, c); break;
         case 1: hipLaunchKernelGGL((k_neighbour_count<true, false>), grid, dim3(kBlock), 0, stream, b, c); break;
         case 2: hipLaunchKernelGGL((k_neighbour_count<false, true>), grid, dim3(kBlock), 0, stream, b, c); break;
-        default: hipLaunchKernelGGL((k_neighbour_count<true, true>), grid, dim3(kBlock), 0, stream, b, c); break;
+        case 3: hipLaunchKernelGGL((k_neighbour_count<true, true>), grid, dim3(kBlock), 0, stream, b, c); break;
+        case 4: hipLaunchKernelGGL((k_neighbour_count<false, false>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
+        case 5: hipLaunchKernelGGL((k_neighbour_count<true, false>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
+        case 6: hipLaunchKernelGGL((k_neighbour_count<false, true>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
+        default: hipLaunchKernelGGL((k_neighbour_count<true, true>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
         }
     }
     hipError_t e = hipGetLastError();
@@ -1844,16 +1883,20 @@ hipError_t launch_neighbour_count(const BodyArrays &b, const ContactBuffers &c, 
     return e;
 }
 
-hipError_t launch_neighbour_fill(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream)
+hipError_t launch_neighbour_fill(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream, const InertBodies &inert)
 {
     if (b.n == 0)
         return hipSuccess;
     const dim3 grid((b.n + kBodiesPerBlock - 1) / kBodiesPerBlock);
-    switch (filter_variant(c)) {
+    switch (filter_variant(c, inert)) {
     case 0: hipLaunchKernelGGL((k_neighbour_fill<false, false>), grid, dim3(kBlock), 0, stream, b, c); break;
     case 1: hipLaunchKernelGGL((k_neighbour_fill<true, false>), grid, dim3(kBlock), 0, stream, b, c); break;
     case 2: hipLaunchKernelGGL((k_neighbour_fill<false, true>), grid, dim3(kBlock), 0, stream, b, c); break;
-    default: hipLaunchKernelGGL((k_neighbour_fill<true, true>), grid, dim3(kBlock), 0, stream, b, c); break;
+    case 3: hipLaunchKernelGGL((k_neighbour_fill<true, true>), grid, dim3(kBlock), 0, stream, b, c); break;
+    case 4: hipLaunchKernelGGL((k_neighbour_fill<false, false>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
+    case 5: hipLaunchKernelGGL((k_neighbour_fill<true, false>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
+    case 6: hipLaunchKernelGGL((k_neighbour_fill<false, true>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
+    default: hipLaunchKernelGGL((k_neighbour_fill<true, true>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
     }
     hipLaunchKernelGGL(k_neighbour_pair_index, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
     return hipGetLastError();
@@ -1941,17 +1984,19 @@ hipError_t launch_joint_extras(double h, const ContactBuffers &c, hipStream_t st
 }
 
 hipError_t launch_restitution(const BodyArrays &b, const double *post, const double *start, const ShapeTable &s, const ContactBuffers &c,
-                              const uint32_t *ground_masks, hipStream_t stream)
+                              const uint32_t *ground_masks, hipStream_t stream, const BodySubset &subset)
 {
     if (b.n == 0)
         return hipSuccess;
-    if (!c.restitution || post == b.dyn || start == b.dyn)
-        return hipErrorInvalidValue; // (the kernel writes b.dyn while other lanes read `post` and `start`)
+    if (!c.restitution || post == b.dyn || start == b.dyn || subset.list)
+        return hipErrorInvalidValue; // (the kernel writes b.dyn while other lanes read `post` and `start`; it has no list form)
     const size_t lds_bytes = (size_t)s.total_verts * 3 * sizeof(double) + (size_t)(s.n_shapes + 1) * sizeof(uint32_t);
     if (c.terrain.planes)
         hipLaunchKernelGGL(k_restitution<true>, dim3(blocks_for(b.n)), dim3(kBlock), lds_bytes, stream, b, post, start, s, c, ground_masks);
     else
         hipLaunchKernelGGL(k_restitution<false>, dim3(blocks_for(b.n)), dim3(kBlock), lds_bytes, stream, b, post, start, s, c, ground_masks);
+    if (subset.skip)
+        hipLaunchKernelGGL(k_restitution_put_back, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, post, subset.skip);
     return hipGetLastError();
 }
 

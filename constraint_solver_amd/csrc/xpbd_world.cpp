@@ -60,6 +60,9 @@ void take_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id)
     w->snapshot.valid = false;
     w->bp.pending = false;
     w->report.reset();
+    w->history.sleep_requests.clear();
+    w->sleep.fresh = true; // sleeping stays on; every body of the new set is awake with zero counters
+    w->sleep.requests = 0;
 }
 
 // The settings that name bodies (or the joints between them) by index go back to their defaults.
@@ -390,6 +393,7 @@ try {
     XPBD_HIP_TRY(upload(w->edge_dirs, dirs.data(), dirs.size() * 8));
     XPBD_HIP_TRY(upload(w->edge_dir_id, dir_id.data(), dir_id.size() * 4));
     w->has_topology = true;
+    w->sleep.wake_all(true);
     uint32_t max_verts = 0, max_faces = 0, max_face_verts = 0, small_max_face_verts = 0, n_small = 0;
     std::vector<uint8_t> shape_class(n_shapes, 0);
     for (uint32_t k = 0; k < n_shapes; ++k) {
@@ -604,6 +608,8 @@ int xpbd_world_set_mode(xpbd_world *w, uint32_t mode)
 try {
     if (!w || (mode != XPBD_MODE_FUSED && mode != XPBD_MODE_PER_SUBSTEP && mode != XPBD_MODE_CONTACTS))
         return set_error(XPBD_E_INVALID, "xpbd_world_set_mode: bad argument");
+    if (w->sleep.on && mode != XPBD_MODE_CONTACTS)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_mode: sleeping is on and needs XPBD_MODE_CONTACTS (xpbd_world_set_sleeping(w, NULL) first)");
     w->mode = mode;
     return XPBD_OK;
 } XPBD_ABI_CATCH
@@ -651,6 +657,7 @@ try {
     JointTables fresh;
     XPBD_TRY(stage_joint_tables(std::move(set), w->n, w->stream, fresh)); // (a slider has an extra entry of its own; no joints: all empty)
     w->joints = std::move(fresh);
+    w->sleep.wake_all(true);
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -678,6 +685,7 @@ try {
     J.limits = std::move(fresh);
     if (slide_changes)
         J.extras = std::move(extras);
+    w->sleep.wake_all(true);
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -689,6 +697,7 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_drives: drives need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
     JointTables &J = w->joints;
     XPBD_TRY(xpbd::check_joint_drives("xpbd_world_set_joint_drives", J.set.joints.data(), J.csr.n, drives, n_drives));
+    w->sleep.wake_all(true);
     if (n_drives == 0 && J.set.drives.empty())
         return XPBD_OK;
     std::vector<xpbd_joint_drive> all(drives, drives + n_drives);
@@ -712,6 +721,7 @@ try {
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued broadphases may still read the present filters
+    w->sleep.wake_all(true);
     if (!filters || n == 0) {
         w->filters.clear();
         w->filters.flags = flags;
@@ -736,6 +746,7 @@ try {
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present coefficients
+    w->sleep.wake_all(true);
     const double inf = std::numeric_limits<double>::infinity();
     if ((!materials || n == 0) && ground_friction == inf) { // the default: the contact kernels' plain forms
         w->materials.clear();
@@ -769,6 +780,7 @@ try {
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present coefficients
+    w->sleep.wake_all(true);
     if (!any) { // nothing can bounce: the step runs what it ran before the call
         w->restitution.clear();
         w->restitution.bounce_threshold = bounce_threshold;
@@ -815,6 +827,7 @@ try {
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present table
+    w->sleep.wake_all(true);
     if (!hf) {
         w->terrain = xpbd::Terrain{};
         w->tr_planes.release();
@@ -888,6 +901,12 @@ try {
     const size_t dyn_bytes = (size_t)xpbd::kDynFields * w->stride * 8;
     XPBD_HIP_TRY(hipMemcpyAsync(dst, w->dyn.ptr, dyn_bytes, hipMemcpyDeviceToDevice, w->stream));
     XPBD_HIP_TRY(hipMemcpyAsync(dst + dyn_bytes, w->last_mask.ptr, (size_t)w->stride * 4, hipMemcpyDeviceToDevice, w->stream));
+    if (w->sleep.on) { // the sleep state behind the masks
+        XPBD_TRY(w->sleep.ensure(w));
+        XPBD_HIP_TRY(hipMemcpyAsync(dst + dyn_bytes + (size_t)w->stride * 4, w->sleep.state.ptr, Sleep::state_bytes(w->stride), hipMemcpyDeviceToDevice,
+                                    w->stream));
+    }
+    w->history.sleep_requests.push_back((uint8_t)w->sleep.requests);
     w->history.stepped.push_back(w->stepped ? 1 : 0);
     if (index_out)
         *index_out = w->history.length;
@@ -908,6 +927,12 @@ try {
     const size_t dyn_bytes = (size_t)xpbd::kDynFields * w->stride * 8;
     XPBD_HIP_TRY(hipMemcpyAsync(w->dyn.ptr, src, dyn_bytes, hipMemcpyDeviceToDevice, w->stream));
     XPBD_HIP_TRY(hipMemcpyAsync(w->last_mask.ptr, src + dyn_bytes, (size_t)w->stride * 4, hipMemcpyDeviceToDevice, w->stream));
+    if (w->sleep.on) {
+        XPBD_TRY(w->sleep.ensure(w));
+        XPBD_HIP_TRY(hipMemcpyAsync(w->sleep.state.ptr, src + dyn_bytes + (size_t)w->stride * 4, Sleep::state_bytes(w->stride), hipMemcpyDeviceToDevice,
+                                    w->stream));
+        w->sleep.requests = w->history.sleep_requests[index];
+    }
     w->stepped = w->history.stepped[index] != 0;
     w->bp.have_neighbours = false;
     w->report.reset();
@@ -923,6 +948,7 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_history_truncate: length %u > %u", length, w->history.length);
     w->history.length = length;
     w->history.stepped.resize(length);
+    w->history.sleep_requests.resize(length);
     return XPBD_OK;
 } XPBD_ABI_CATCH
 

@@ -8,6 +8,7 @@
 //   xpbd_world_query.cpp     the scene-query host layer and entry points
 //   xpbd_world_edit.cpp      body edits, population changes, re-packing a shard
 //   xpbd_world_islands.cpp   Islands and the island entry points
+//   xpbd_world_sleep.cpp     Sleep and the sleeping entry points
 #pragma once
 
 #include <cstdint>
@@ -26,6 +27,7 @@
 #include "xpbd_population_remap.hpp"
 #include "xpbd_query.h"
 #include "xpbd_report.h"
+#include "xpbd_sleep.h"
 
 struct xpbd_world;
 
@@ -88,7 +90,7 @@ struct JointTables {
 // list of the current frame with its per-pair results.  have_neighbours: the lists describe the bodies as they are.
 struct Broadphase {
     DeviceBuffer centers, radius, cell, key, maxr, grid_partials, bucket_start, bucket_cursor, items, items_unsorted, slot_sphere,
-        slot_cell, slot_filter, nbr_off, pair_first, upper_start, nbr, nbr_pair, pairs, manifolds, pair_codes, scan;
+        slot_cell, slot_filter, slot_inert, nbr_off, pair_first, upper_start, nbr, nbr_pair, pairs, manifolds, pair_codes, scan;
     uint32_t table_size = 0, n_entries = 0, n_pairs = 0;
     bool have_neighbours = false;
     // The broadphase in two halves (build_neighbours_enqueue / _collect): the counting kernels leave the totals the host
@@ -251,6 +253,7 @@ struct History {
     DeviceBuffer states;
     uint32_t length = 0;
     std::vector<uint8_t> stepped;
+    std::vector<uint8_t> sleep_requests; // Sleep::requests as they stood at the push (all 0 with sleeping off)
 };
 
 // Contact islands (xpbd_world_islands*; xpbd_islands.h; xpbd_world_islands.cpp): the scratch of one call, reserved like the
@@ -262,6 +265,34 @@ struct Islands {
 
     int reserve(const xpbd_world *w, bool host_island_of, uint32_t host_records);
     int enqueue(xpbd_world *w, uint32_t flags, uint32_t *dev_island_of, xpbd_island *dev_records, uint32_t cap, uint32_t *dev_total);
+};
+
+// Island sleeping (xpbd_world_set_sleeping; xpbd_sleep.h; xpbd_world_sleep.cpp).  `state` is what a history entry carries
+// beside the bodies: rest_frames, group, the wake marks, the control words and the asleep bytes, in one block so that a push or
+// a restore is one copy.  `scratch` holds what a frame derives from it.  Both follow the stride; `fresh` (after an enable, an
+// upload or a population change) has ensure() start every body awake with zero counters.  requests: the wake requests made on
+// the host since the last frame began that name no group (kSleepWakeAll, kSleepZeroCounters).  The operations read the bodies,
+// the report, the joints and the stream of the world `w` they belong to; a world with sleeping off calls none of them.
+struct Sleep {
+    bool on = false, fresh = true;
+    xpbd_sleep_config cfg{};
+    uint32_t requests = 0;
+    DeviceBuffer state, scratch;
+
+    static size_t state_bytes(uint32_t stride) { return (size_t)stride * 13 + xpbd::kSleepCtrlWords * 4; }
+    xpbd::SleepState view(const xpbd_world *w) const;
+    const uint8_t *asleep(const xpbd_world *w) const { return view(w).asleep; }
+    void wake_all(bool zero_counters)
+    {
+        if (on)
+            requests |= xpbd::kSleepWakeAll | (zero_counters ? xpbd::kSleepZeroCounters : 0u);
+    }
+    int ensure(const xpbd_world *w);
+    int frame_begin(xpbd_world *w);                                        // before the broadphase: the wake requests
+    int frame_records(xpbd_world *w, uint32_t *trace, uint32_t trace_rows); // after it: the sleepers' records
+    int frame_end(xpbd_world *w);                                          // after the last substep: the sleep pass
+    // wake requests of an edit: entry k names body dev_indices[k * every] (NULL: body k)
+    int request(xpbd_world *w, const uint32_t *dev_indices, uint32_t every, uint32_t n);
 };
 
 #pragma GCC visibility pop
@@ -369,7 +400,12 @@ struct xpbd_world {
     History history;
     // contact islands (xpbd_world_islands, _islands_device): scratch of one call; a world that never calls them holds none
     Islands islands;
-    size_t history_slot_bytes() const { return ((size_t)xpbd::kDynFields * stride * 8 + (size_t)stride * 4 + 255) / 256 * 256; }
+    // island sleeping (xpbd_world_set_sleeping): off, a world holds and enqueues nothing of it
+    Sleep sleep;
+    size_t history_slot_bytes() const
+    {
+        return ((size_t)xpbd::kDynFields * stride * 8 + (size_t)stride * 4 + (sleep.on ? Sleep::state_bytes(stride) : 0) + 255) / 256 * 256;
+    }
 
     // frame_set: which of the two frame sets the substep reads (always 0 outside step_contacts)
     xpbd::ContactBuffers contact_buffers(uint32_t frame_set = 0) const
@@ -392,6 +428,12 @@ struct xpbd_world {
         c.bounce_threshold = restitution.bounce_threshold;
         c.terrain = terrain;
         return c;
+    }
+
+    // who is inert in the coming frame, for the broadphase (sleeping off: nobody, the kernels of a world without sleeping)
+    xpbd::InertBodies inert_bodies() const
+    {
+        return sleep.on ? xpbd::InertBodies{sleep.view(this).inert, bp.slot_inert.as<uint8_t>()} : xpbd::InertBodies{};
     }
 
     xpbd::BodyArrays arrays() const
@@ -420,6 +462,24 @@ struct xpbd_world {
 
 #pragma GCC visibility push(hidden)
 
+// The sections of Sleep::state and ::scratch for a world of w->stride (valid once ensure() has run).
+inline xpbd::SleepState Sleep::view(const xpbd_world *w) const
+{
+    const size_t st = w->stride;
+    xpbd::SleepState s{};
+    s.rest_frames = state.as<uint32_t>();
+    s.group = s.rest_frames + st;
+    s.mark = s.group + st;
+    s.ctrl = s.mark + st;
+    s.asleep = reinterpret_cast<uint8_t *>(s.ctrl + xpbd::kSleepCtrlWords);
+    s.island_min = scratch.as<uint32_t>();
+    s.fixed = reinterpret_cast<uint8_t *>(s.island_min + st);
+    s.inert = s.fixed + st;
+    s.n = w->n;
+    s.stride = w->stride;
+    return s;
+}
+
 inline int bind_device(const xpbd_world *w)
 {
     XPBD_HIP_TRY(hipSetDevice(w->device));
@@ -444,7 +504,7 @@ int build_neighbours_enqueue(xpbd_world *w, double dt);
 int build_neighbours_collect(xpbd_world *w);
 int build_neighbours(xpbd_world *w, double dt);
 int narrowphase_contacts(xpbd_world *w, const xpbd::BodyArrays &b, const xpbd::ContactBuffers &c);
-int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_row);
+int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_row, const xpbd::BodySubset &awake = xpbd::BodySubset());
 int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_t *trace);
 
 #pragma GCC visibility pop

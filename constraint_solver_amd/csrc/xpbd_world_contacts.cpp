@@ -50,6 +50,8 @@ int build_neighbours_enqueue(xpbd_world *w, double dt)
 {
     if (int rc = w->report.frame_end(w))
         return rc;
+    if (w->sleep.on) // the wake requests made since the last frame, and who is inert in this one
+        XPBD_TRY(w->sleep.frame_begin(w));
     if (!w->bp.totals) {
         XPBD_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->bp.totals), sizeof *w->bp.totals, hipHostMallocDefault));
         XPBD_HIP_TRY(hipEventCreateWithFlags(&w->bp.event, hipEventDisableTiming));
@@ -70,6 +72,8 @@ int build_neighbours_enqueue(xpbd_world *w, double dt)
     XPBD_HIP_TRY(w->bp.slot_cell.reserve((size_t)3 * st * 4));
     if (w->filters.on)
         XPBD_HIP_TRY(w->bp.slot_filter.reserve((size_t)2 * st * 4));
+    if (w->sleep.on)
+        XPBD_HIP_TRY(w->bp.slot_inert.reserve((size_t)st));
     XPBD_HIP_TRY(w->bp.nbr_off.reserve((size_t)(st + 1) * 4));
     XPBD_HIP_TRY(w->bp.pair_first.reserve((size_t)(st + 1) * 4));
     XPBD_HIP_TRY(w->bp.upper_start.reserve((size_t)st * 4));
@@ -103,8 +107,8 @@ int build_neighbours_enqueue(xpbd_world *w, double dt)
     xpbd::ContactBuffers c = w->contact_buffers();
     XPBD_HIP_TRY(xpbd::launch_bounds_and_cells(b, w->tables(), w->shape_radii.as<double>(), dt, w->contact_pad, c,
                                                w->stream));
-    XPBD_HIP_TRY(xpbd::launch_build_buckets(b, c, w->stream));
-    XPBD_HIP_TRY(xpbd::launch_neighbour_count(b, c, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_build_buckets(b, c, w->stream, w->inert_bodies()));
+    XPBD_HIP_TRY(xpbd::launch_neighbour_count(b, c, w->stream, w->inert_bodies()));
     XPBD_HIP_TRY(hipMemcpyAsync(&w->bp.totals->entries, c.nbr_off + n, 4, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipMemcpyAsync(&w->bp.totals->pairs, c.pair_first + n, 4, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipMemcpyAsync(w->bp.totals->stats, c.stats, 16, hipMemcpyDeviceToHost, w->stream));
@@ -149,7 +153,7 @@ int build_neighbours_collect(xpbd_world *w)
     XPBD_HIP_TRY(w->bp.manifolds.reserve((size_t)at_least_one(w->bp.n_pairs) * sizeof(xpbd::ContactManifold)));
     XPBD_HIP_TRY(w->bp.pair_codes.reserve((size_t)at_least_one(w->bp.n_pairs)));
     c = w->contact_buffers();
-    XPBD_HIP_TRY(xpbd::launch_neighbour_fill(b, c, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_neighbour_fill(b, c, w->stream, w->inert_bodies()));
     w->bp.have_neighbours = true;
     return w->report.frame_begin(w);
 }
@@ -183,7 +187,8 @@ int narrowphase_contacts(xpbd_world *w, const xpbd::BodyArrays &b, const xpbd::C
 
 // One substep of the contact pipeline (neighbour lists must be current): the form the split API
 // (xpbd_world_contacts_substep) exposes, with a seam for the halo exchange after it.
-int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_row)
+// awake: all bodies, or (sleeping on, from step_contacts) all but the sleepers.
+int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_row, const xpbd::BodySubset &awake)
 {
     const xpbd::BodyArrays b = w->arrays();
     const xpbd::ContactBuffers c = w->contact_buffers();
@@ -194,17 +199,17 @@ int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_ro
         XPBD_HIP_TRY(hipMemcpyAsync(w->rs_start.ptr, b.dyn + (size_t)xpbd::D_VEL * b.stride, (size_t)6 * b.stride * 8, hipMemcpyDeviceToDevice,
                                     w->stream));
     }
-    XPBD_HIP_TRY(xpbd::launch_integrate_ground(b, w->shapes(), h, c, w->last_mask.as<uint32_t>(), trace, trace_row, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_integrate_ground(b, w->shapes(), h, c, w->last_mask.as<uint32_t>(), trace, trace_row, w->stream, awake));
     if (int rc = narrowphase_contacts(w, b, c))
         return rc;
     XPBD_HIP_TRY(xpbd::launch_joint_extras(h, c, w->stream));
     if (!c.restitution) {
-        XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream));
+        XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream, awake));
         return XPBD_OK;
     }
-    XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, w->dyn_alt.as<double>(), h, c, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, w->dyn_alt.as<double>(), h, c, w->stream, awake));
     XPBD_HIP_TRY(xpbd::launch_restitution(b, w->dyn_alt.as<double>(), w->rs_start.as<double>(), w->shapes(), c, w->last_mask.as<uint32_t>(),
-                                          w->stream));
+                                          w->stream, awake));
     return XPBD_OK;
 }
 
@@ -221,15 +226,22 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         return rc;
     if (substeps == 0)
         return XPBD_OK;
+    // Sleeping (include/xpbd.h, "SLEEPING"): the sleepers' records once, every per-body stage without them, the sleep pass last.
+    // Off: `awake` is the default subset and nothing else happens, the launches are the ones of a world without sleeping.
+    xpbd::BodySubset awake;
+    if (w->sleep.on) {
+        XPBD_TRY(w->sleep.frame_records(w, trace, substeps));
+        awake.skip = w->sleep.asleep(w);
+    }
     // the velocity pass sits where the fused kernel below has the next substep's integrate; and that kernel has no terrain form
     if (w->restitution.on || w->terrain.planes) {
         for (uint32_t k = 0; k < substeps; ++k)
-            if (int rc = substep_contacts(w, h, trace, k))
+            if (int rc = substep_contacts(w, h, trace, k, awake))
                 return rc;
-        return XPBD_OK;
+        return w->sleep.on ? w->sleep.frame_end(w) : XPBD_OK;
     }
     XPBD_HIP_TRY(xpbd::launch_integrate_ground(w->arrays(), w->shapes(), h, w->contact_buffers(0), w->last_mask.as<uint32_t>(), trace, 0,
-                                               w->stream));
+                                               w->stream, awake));
     for (uint32_t k = 0; k < substeps; ++k) {
         const xpbd::BodyArrays b = w->arrays();
         const xpbd::ContactBuffers c = w->contact_buffers(k & 1u);
@@ -239,12 +251,12 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         if (k + 1 < substeps) {
             const xpbd::ContactBuffers next = w->contact_buffers((k + 1u) & 1u);
             XPBD_HIP_TRY(xpbd::launch_pair_solve_integrate_ground(b, w->shapes(), h, c, next.rec, w->last_mask.as<uint32_t>(), trace,
-                                                                  k + 1, w->stream));
+                                                                  k + 1, w->stream, awake));
         } else {
-            XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream));
+            XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream, awake));
         }
     }
-    return XPBD_OK;
+    return w->sleep.on ? w->sleep.frame_end(w) : XPBD_OK;
 }
 
 // ---- the frame of a multi-GPU shard, split at the halo exchange (xpbd_internal.h) -------------------------------------------
@@ -483,6 +495,8 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: NULL world");
     if (w->mode != XPBD_MODE_CONTACTS || !w->has_topology)
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
+    if (w->sleep.on)
+        return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: the split API has no frame end, sleeping is on (xpbd_world_set_sleeping)");
     if (int rc = bind_device(w))
         return rc;
     w->stepped = true;
@@ -500,6 +514,8 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_substep: NULL world");
     if (w->mode != XPBD_MODE_CONTACTS || (w->n && !w->bp.have_neighbours))
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_substep: call xpbd_world_contacts_begin first");
+    if (w->sleep.on)
+        return set_error(XPBD_E_INVALID, "xpbd_world_contacts_substep: the split API has no frame end, sleeping is on (xpbd_world_set_sleeping)");
     if (w->n == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))
@@ -584,6 +600,7 @@ int xpbd_world_set_contact_pad(xpbd_world *w, double pad)
 try {
     if (!w || !(pad >= 0.0) || pad > 1.0e6)
         return set_error(XPBD_E_INVALID, "xpbd_world_set_contact_pad: bad argument");
+    w->sleep.wake_all(true);
     w->contact_pad = pad;
     return XPBD_OK;
 } XPBD_ABI_CATCH
@@ -623,6 +640,8 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_build_neighbours: NULL argument");
     if (!w->has_topology)
         return set_error(XPBD_E_INVALID, "xpbd_world_build_neighbours: call xpbd_world_set_polytopes first");
+    if (w->sleep.on) // (a broadphase applies the pending wake requests, which belongs to the start of a step)
+        return set_error(XPBD_E_INVALID, "xpbd_world_build_neighbours: a broadphase outside a step, sleeping is on (xpbd_world_set_sleeping)");
     if (int rc = bind_device(w))
         return rc;
     if (int rc = build_neighbours(w, dt))

@@ -157,6 +157,8 @@ try {
         XPBD_HIP_TRY(hipMemcpyAsync(dev_torque, torque_xyz, half, hipMemcpyHostToDevice, w->stream));
     XPBD_HIP_TRY(xpbd::launch_set_wrench(w->arrays(), indices ? w->edit.indices.as<uint32_t>() : nullptr, n, force_xyz ? dev_force : nullptr,
                                          torque_xyz ? dev_torque : nullptr, w->stream));
+    if (w->sleep.on) // an edited sleeper wakes with its group at the start of the next step ("SLEEPING")
+        XPBD_TRY(w->sleep.request(w, indices ? w->edit.indices.as<uint32_t>() : nullptr, 1, n));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the caller's arrays are only borrowed
     return XPBD_OK;
 } XPBD_ABI_CATCH
@@ -179,6 +181,8 @@ try {
         return set_error(XPBD_E_INVALID, "%s: n = %u (at most %u entries per call)", who, n, xpbd::kMaxEditEntries);
     XPBD_TRY(bind_device(w));
     XPBD_HIP_TRY(xpbd::launch_set_wrench(w->arrays(), dev_indices, n, dev_force_xyz, dev_torque_xyz, w->stream));
+    if (w->sleep.on)
+        XPBD_TRY(w->sleep.request(w, dev_indices, 1, n));
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -198,6 +202,8 @@ try {
     XPBD_TRY(reserve_edit_staging(w, 0, 0, bytes));
     XPBD_HIP_TRY(hipMemcpyAsync(w->edit.list.ptr, sorted.data(), bytes, hipMemcpyHostToDevice, w->stream));
     XPBD_HIP_TRY(xpbd::launch_apply_impulses(w->arrays(), w->edit.list.as<xpbd_impulse>(), n, w->stream));
+    if (w->sleep.on) // (an entry's first word is its body)
+        XPBD_TRY(w->sleep.request(w, w->edit.list.as<uint32_t>(), sizeof(xpbd_impulse) / 4, n));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // `sorted` is read by the copy
     return XPBD_OK;
 } XPBD_ABI_CATCH
@@ -219,6 +225,8 @@ try {
         return set_error(XPBD_E_INVALID, "%s: n = %u (at most %u entries per call)", who, n, xpbd::kMaxEditEntries);
     XPBD_TRY(bind_device(w));
     XPBD_HIP_TRY(xpbd::launch_apply_impulses(w->arrays(), dev_list, n, w->stream));
+    if (w->sleep.on)
+        XPBD_TRY(w->sleep.request(w, reinterpret_cast<const uint32_t *>(dev_list), sizeof(xpbd_impulse) / 4, n));
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -240,6 +248,8 @@ try {
     XPBD_TRY(stage_edit_indices(w, indices, n, iota));
     XPBD_HIP_TRY(hipMemcpyAsync(w->edit.values.ptr, rows, bytes, hipMemcpyHostToDevice, w->stream));
     XPBD_HIP_TRY(xpbd::launch_import_dynamic(w->arrays(), w->edit.indices.as<uint32_t>(), nullptr, n, w->edit.values.as<double>(), w->stream));
+    if (w->sleep.on)
+        XPBD_TRY(w->sleep.request(w, w->edit.indices.as<uint32_t>(), 1, n));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
 } XPBD_ABI_CATCH

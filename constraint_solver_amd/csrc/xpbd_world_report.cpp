@@ -105,6 +105,9 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_set_contact_report: NULL world");
     if (enable > 1u)
         return set_error(XPBD_E_INVALID, "xpbd_world_set_contact_report: enable must be 0 or 1, not %u", enable);
+    if (!enable && w->sleep.on)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_contact_report: sleeping is on and takes its touching pairs from the report "
+                                         "(xpbd_world_set_sleeping(w, NULL) first)");
     if (int rc = bind_device(w))
         return rc;
     if (enable && !w->report.host)

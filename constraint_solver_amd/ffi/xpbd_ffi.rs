@@ -381,6 +381,18 @@ pub struct XpbdIsland {
     pub max_angular_speed2: f64,
 }
 
+pub const XPBD_SLEEP_GROUP_NONE: u32 = 0xFFFF_FFFF;
+
+/// xpbd_sleep_config (24 bytes): the thresholds of island sleeping (include/xpbd.h, "SLEEPING")
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct XpbdSleepConfig {
+    pub linear_speed: f64,
+    pub angular_speed: f64,
+    pub frames_to_sleep: u32,
+    pub flags: u32,
+}
+
 #[repr(C)]
 pub struct XpbdWorld {
     _private: [u8; 0],
@@ -571,6 +583,13 @@ extern "C" {
                               n_islands: *mut u32) -> c_int;
     pub fn xpbd_world_islands_device(w: *mut XpbdWorld, flags: u32, dev_island_of: *mut u32, dev_islands: *mut XpbdIsland, cap: u32,
                                      dev_n_islands: *mut u32) -> c_int;
+    // island sleeping (include/xpbd.h, "SLEEPING"); cfg NULL: off; any array of the state calls may be NULL, counts: [u32; 4]
+    pub fn xpbd_world_set_sleeping(w: *mut XpbdWorld, cfg: *const XpbdSleepConfig) -> c_int;
+    pub fn xpbd_world_sleep_state(w: *mut XpbdWorld, asleep: *mut u8, rest_frames: *mut u32, group: *mut u32, counts: *mut u32) -> c_int;
+    pub fn xpbd_world_sleep_state_device(w: *mut XpbdWorld, dev_asleep: *mut u8, dev_rest_frames: *mut u32, dev_group: *mut u32,
+                                         dev_counts: *mut u32) -> c_int;
+    pub fn xpbd_world_wake_bodies(w: *mut XpbdWorld, indices: *const u32, n: u32) -> c_int;
+    pub fn xpbd_world_wake_bodies_device(w: *mut XpbdWorld, dev_indices: *const u32, n: u32) -> c_int;
     pub fn xpbd_multi_world_set_contact_report(mw: *mut XpbdMultiWorld, enable: u32) -> c_int;
     pub fn xpbd_multi_world_contact_report_counts(mw: *mut XpbdMultiWorld, out: *mut u32) -> c_int;
     pub fn xpbd_multi_world_download_pair_contacts(mw: *mut XpbdMultiWorld, pairs: *mut XpbdPairContact, pair_cap: u32,

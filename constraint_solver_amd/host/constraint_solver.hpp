@@ -633,6 +633,35 @@ class BatchWorld {
         out.resize(total);
         return out;
     }
+    // island sleeping (include/xpbd.h, "SLEEPING"): resting islands leave the step until something disturbs them
+    void set_sleeping(double linear_speed, double angular_speed, uint32_t frames_to_sleep)
+    {
+        const xpbd_sleep_config cfg{linear_speed, angular_speed, frames_to_sleep, 0u};
+        check(xpbd_world_set_sleeping(w_, &cfg));
+    }
+    void set_sleeping_off() { check(xpbd_world_set_sleeping(w_, nullptr)); }
+    // counts: asleep bodies, sleeping groups, bodies woken / put to sleep by the last pass; any vector may be NULL
+    std::array<uint32_t, 4> sleep_state(std::vector<uint8_t> *asleep = nullptr, std::vector<uint32_t> *rest_frames = nullptr,
+                                        std::vector<uint32_t> *group = nullptr)
+    {
+        const uint32_t n = xpbd_world_body_count(w_);
+        if (asleep)
+            asleep->resize(n);
+        if (rest_frames)
+            rest_frames->resize(n);
+        if (group)
+            group->resize(n);
+        std::array<uint32_t, 4> counts{};
+        check(xpbd_world_sleep_state(w_, asleep && n ? asleep->data() : nullptr, rest_frames && n ? rest_frames->data() : nullptr,
+                                     group && n ? group->data() : nullptr, counts.data()));
+        return counts;
+    }
+    void wake_bodies(const std::vector<uint32_t> &indices)
+    {
+        if (!indices.empty()) // (NULL with n == 0 would wake everybody)
+            check(xpbd_world_wake_bodies(w_, indices.data(), (uint32_t)indices.size()));
+    }
+    void wake_all() { check(xpbd_world_wake_bodies(w_, nullptr, 0)); }
 
     std::vector<xpbd_contact> contacts()
     {

@@ -1553,6 +1553,91 @@ int  xpbd_world_islands(xpbd_world *w, uint32_t flags, uint32_t *island_of /* [b
 int  xpbd_world_islands_device(xpbd_world *w, uint32_t flags, uint32_t *dev_island_of /* or NULL */,
                                xpbd_island *dev_islands, uint32_t cap, uint32_t *dev_n_islands);
 
+/* ---------------------------------------------------------------------------
+ * SLEEPING (EXTENSION): resting groups of bodies leave the step until something disturbs them.  NOT in the reference.  Opt-in:
+ * a world that never calls xpbd_world_set_sleeping runs exactly what it ran before.  Single world, XPBD_MODE_CONTACTS, contact
+ * report on (the touching set is the report's S, "Contact REPORTS").
+ *
+ * Per body the world keeps  asleep (0 / 1),  rest_frames (consecutive frames at rest)  and  group (the smallest member of the
+ * island the body fell asleep with; XPBD_SLEEP_GROUP_NONE while awake).  Enabling starts every body awake with rest_frames 0.
+ *
+ * Fixed body and island: exactly as in "Contact ISLANDS" above.  INERT: asleep or fixed.
+ *
+ * At rest.  A body is at rest when  v.x*v.x + v.y*v.y + v.z*v.z <= linear_speed*linear_speed  for its velocity and the same
+ * expression of its angular_velocity is <= angular_speed*angular_speed; every expression evaluated left to right without
+ * contraction, as max_speed2 of the islands is.  A NaN compares false: not at rest.
+ *
+ * During a frame (one xpbd_world_step) the asleep set does not change, and
+ *  (a) the broadphase forms no pair whose two ends are both inert.  The pair list, xpbd_world_contact_stats and the report
+ *      change with it: the report holds only pairs with at least one awake, non-fixed body; the pairs inside a group that falls
+ *      asleep produce END events in the next frame, those of a group that wakes BEGIN events;
+ *  (b) no per-body stage advances an asleep body -- integrate + ground, pair solve, derive, restitution: its 13 dynamic
+ *      doubles, its contact mask (xpbd_world_download_contacts; the trace rows of a step repeat it) stay the same bits;
+ *  (c) awake neighbours see an asleep body through a body record made from its resting pose: frame before integrate = frame
+ *      after integrate = Rigid::frame(), pose after the ground contacts = its pose, with its own mass properties.  (A
+ *      neighbour's correction is therefore shared as with an awake body, but the sleeper's share is not applied in that frame.)
+ *
+ * The sleep pass runs at the end of every xpbd_world_step, on the state the last substep left, in this order:
+ *  1. Wake.  Every asleep body s is MARKED when the frame's touching set holds a pair (s, a) with a awake and not fixed.  Every
+ *     asleep body whose group equals the group of a marked body wakes: asleep = 0, rest_frames = 0, group = NONE.
+ *  2. Count.  For every body that is now awake and not fixed:  rest_frames = at rest ? min(rest_frames + 1, UINT32_MAX) : 0.
+ *  3. Sleep.  Take the islands of the frame as xpbd_world_islands(flags 0) returns them.  An island none of whose members is
+ *     asleep and all of whose members have rest_frames >= frames_to_sleep goes to sleep: asleep = 1, group = the island's
+ *     first_body, velocity and angular_velocity = +0.0 for every member.  rest_frames keeps its value.  (The grouping is the
+ *     islands call's, loop bound included: should a lane ever reach the bound -- the case in which xpbd_world_islands returns
+ *     XPBD_E_HIP -- the pass puts nobody to sleep in that frame, counts[3] is 0, and steps 1 and 2 stand.  The step itself does
+ *     not fail: nothing waits for the device.)
+ * counts[2] / counts[3] of xpbd_world_sleep_state are the bodies step 1 woke / step 3 put to sleep in the last pass.
+ *
+ * Wake requests between frames are applied by the same group-wide wake at the START of the next xpbd_world_step, before its
+ * broadphase (until then xpbd_world_sleep_state shows the state the last pass left):
+ *   xpbd_world_wake_bodies(_device): the groups of the listed sleepers; indices == NULL with n == 0: everybody.
+ *   xpbd_world_set_external_wrench(_device), xpbd_world_apply_impulses(_device), xpbd_world_set_dynamics: the groups of the
+ *     sleepers they name.  A call that names a FIXED body wakes everybody (an anchor may have moved).  An awake body keeps
+ *     its rest_frames.  (The edit itself is applied at once, to a sleeper too.)
+ *   xpbd_world_set_joints, _set_joint_limits, _set_joint_drives, _set_collision_filters, _set_materials, _set_restitution,
+ *     _set_terrain, _set_polytopes, _set_contact_pad: everybody wakes and every rest_frames becomes 0.
+ *   xpbd_world_upload_bodies and a population change (xpbd_world_add_bodies, _remove_bodies that removes a body): the state
+ *     starts over at once, every body awake with rest_frames 0; sleeping stays on.
+ * The device variants scatter their requests on the device and wait for nothing; an index outside the world is skipped.
+ *
+ * History.  While sleeping is on an entry carries asleep, rest_frames, group and the pending requests, and a restore brings
+ * them back: a run repeated from a restored entry is the same bits, sleep state included.  Turning sleeping on or off changes
+ * the size of an entry, so both drop the history (xpbd_world_history_length becomes 0).
+ *
+ * xpbd_world_set_sleeping(w, cfg) turns sleeping on or, when already on, replaces the configuration and keeps the state;
+ * cfg == NULL turns it off: everything is awake, and the world steps as a world that never slept given its bodies.
+ * XPBD_E_INVALID, nothing changed: a NULL world; a negative or non-finite speed; frames_to_sleep == 0; flags != 0; a mode other
+ * than XPBD_MODE_CONTACTS; the contact report off.  While sleeping is on, xpbd_world_set_contact_report(w, 0),
+ * xpbd_world_set_mode to another mode, the split API (xpbd_world_contacts_begin / _substep: it has no frame end) and the
+ * diagnostic xpbd_world_build_neighbours (a broadphase outside a step: it would have to apply the wake requests early) are
+ * XPBD_E_INVALID.
+ *
+ * xpbd_world_sleep_state takes host arrays of the body count (any may be NULL) and waits; counts = {asleep bodies, sleeping
+ * groups, bodies woken by the last pass, bodies put to sleep by it}.  xpbd_world_sleep_state_device takes device arrays and
+ * only enqueues on the world's stream.  Both, and the wake calls, are XPBD_E_INVALID when sleeping is off; the host variant
+ * of the wake call also for NULL indices with n != 0 and for an index >= the body count (nothing is requested then).
+ *
+ * Not here: the multi-GPU world; putting bodies to sleep by request; keeping sleepers asleep across a population change.
+ * And by decision no wake from xpbd_world_set_shapes, xpbd_world_set_narrowphase, xpbd_world_set_sat_schedule and
+ * xpbd_world_set_max_depenetration_speed: they change how a step computes, not what a resting group rests on.  Sleepers stay
+ * asleep across them; a caller who wants otherwise calls xpbd_world_wake_bodies(w, NULL, 0).
+ * ------------------------------------------------------------------------- */
+typedef struct xpbd_sleep_config {   /* 24 bytes */
+    double   linear_speed;           /* m/s, finite, >= 0 */
+    double   angular_speed;          /* rad/s, finite, >= 0 */
+    uint32_t frames_to_sleep;        /* >= 1: consecutive frames at rest before an island may sleep */
+    uint32_t flags;                  /* 0 */
+} xpbd_sleep_config;
+#define XPBD_SLEEP_GROUP_NONE 0xFFFFFFFFu /* group[] of a body that is awake */
+
+int  xpbd_world_set_sleeping(xpbd_world *w, const xpbd_sleep_config *cfg /* NULL: off */);
+int  xpbd_world_sleep_state(xpbd_world *w, uint8_t *asleep, uint32_t *rest_frames, uint32_t *group, uint32_t counts[4]);
+int  xpbd_world_sleep_state_device(xpbd_world *w, uint8_t *dev_asleep, uint32_t *dev_rest_frames, uint32_t *dev_group,
+                                   uint32_t *dev_counts /* [4] */);
+int  xpbd_world_wake_bodies(xpbd_world *w, const uint32_t *indices, uint32_t n /* NULL, 0: all */);
+int  xpbd_world_wake_bodies_device(xpbd_world *w, const uint32_t *dev_indices, uint32_t n /* NULL, 0: all */);
+
 /* Diagnostics: quotient[i] = a[i] / b[i], root[i] = sqrt(a[i]) computed on the
  * device with the stepper's own code generation.  Bit-exact contact lists need
  * both to be correctly rounded; the parity tests check this against the host. */
