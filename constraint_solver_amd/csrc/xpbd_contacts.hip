@@ -1,24 +1,18 @@
-// xpbd_contacts.hip -- body-body contact EXTENSION for gfx950: sphere broadphase on a hashed
-// uniform grid and the per-substep contact pipeline
+// xpbd_contacts.hip -- body-body contact EXTENSION for gfx950: the per-substep contact pipeline
 //     integrate + ground contacts  ->  wave-per-pair SAT  ->  Jacobi pair solve + derive.
 // Semantics are defined by oracle/xpbd_pairs_oracle.h (op_contacts_step); the reference has no
 // body-body contacts, so parity is UNPINNED.  The ground-contact part reuses the reference path
-// (xpbd_step.hpp) unchanged.
+// (xpbd_step.hpp) unchanged.  The broadphase before it: xpbd_broadphase.hip; the velocity pass after it:
+// xpbd_restitution.hip; what the units of the pipeline share: xpbd_contacts_device.hpp.
 //
 // Determinism: every floating-point sum is formed by ONE lane in a fixed order (neighbour index,
-// then manifold point index); atomics are used on integers only (bucket counts, cursors, stats)
-// and every order they leave open is removed by a sort.  Results do not depend on launch order,
-// on the hash-table size or on how the world is sharded.
-#include <cfloat>
-#include <type_traits>
-
-#include "xpbd_contacts.h"
-#include "xpbd_step.hpp"
+// then manifold point index); atomics are used on integers only (the statistics) and what they sum does not depend
+// on the order.  Results do not depend on launch order or on how the world is sharded.
+#include "xpbd_contacts_device.hpp"
 
 namespace xpbd {
 namespace {
 
-constexpr uint32_t kBlock = 256;
 // Worlds up to this many bodies run the pair solve with one lane per manifold POINT (eight lanes per body): below it
 // the GPU is not full and a substep costs the dependent chain of one wave, which this shortens.
 #ifndef XPBD_SMALL_WORLD
@@ -28,512 +22,6 @@ constexpr uint32_t kSmallWorld = XPBD_SMALL_WORLD;
 #ifndef XPBD_PAIR_SOLVE_MIN_WAVES
 #define XPBD_PAIR_SOLVE_MIN_WAVES 2
 #endif
-
-// Bucket key of a grid cell.  (Tried: a Morton interleave of the coordinates, so that neighbouring cells share cache
-// lines.  With equal bits per axis a flat scene -- 144 x 144 x 9 cells -- folds six cells onto one bucket and the
-// search slowed down, 178 -> 196 us at 262 144 stacked boxes; the multiplicative hash spreads any extent evenly.)
-__device__ __forceinline__ uint32_t cell_hash(int32_t x, int32_t y, int32_t z)
-{
-    return ((uint32_t)x * 73856093u) ^ ((uint32_t)y * 19349663u) ^ ((uint32_t)z * 83492791u);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Exclusive scan of uint32 (three small kernels; 1024 elements per block).
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t block_scan_exclusive(uint32_t v, uint32_t *total)
-{
-    __shared__ uint32_t wave_sum[kBlock / 64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t up = __shfl_up(inc, d, 64);
-        if (lane >= d)
-            inc += up;
-    }
-    if (lane == 63)
-        wave_sum[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kBlock / 64; ++k) {
-        const uint32_t ws = wave_sum[k];
-        if (k < wave)
-            before += ws;
-        all += ws;
-    }
-    __syncthreads();
-    *total = all;
-    return before + inc - v;
-}
-
-__global__ void k_scan_blocks(uint32_t *__restrict__ data, uint32_t n, uint32_t *__restrict__ block_totals)
-{
-    const uint32_t base = blockIdx.x * (kBlock * 4) + threadIdx.x * 4;
-    uint32_t v[4], sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-        v[k] = base + k < n ? data[base + k] : 0u;
-        sum += v[k];
-    }
-    uint32_t total;
-    uint32_t run = block_scan_exclusive(sum, &total);
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-        if (base + k < n)
-            data[base + k] = run;
-        run += v[k];
-    }
-    if (threadIdx.x == 0)
-        block_totals[blockIdx.x] = total;
-}
-
-__global__ void k_scan_totals(uint32_t *__restrict__ block_totals, uint32_t nb)
-{
-    __shared__ uint32_t carry_s;
-    if (threadIdx.x == 0)
-        carry_s = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < nb; base += kBlock) {
-        const uint32_t k = base + threadIdx.x;
-        const uint32_t v = k < nb ? block_totals[k] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_scan_exclusive(v, &total);
-        const uint32_t carry = carry_s;
-        if (k < nb)
-            block_totals[k] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            carry_s = carry + total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-        block_totals[nb] = carry_s;
-}
-
-__global__ void k_scan_add(uint32_t *__restrict__ data, uint32_t n, const uint32_t *__restrict__ block_totals, uint32_t nb)
-{
-    const uint32_t base = blockIdx.x * (kBlock * 4) + threadIdx.x * 4;
-    const uint32_t add = block_totals[blockIdx.x];
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k)
-        if (base + k < n)
-            data[base + k] += add;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        data[n] = block_totals[nb];
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Broadphase
-// ---------------------------------------------------------------------------------------------------
-// Bounding sphere of every body: centre = frame * centroid, radius = r_shape + min(|v| dt, r_shape) + pad.
-// The clamp keeps one runaway body from inflating the grid cell of everybody (cell edge = 2 * max radius).
-// Every workgroup also leaves the largest radius and the bounding box of its centres in c.grid_partials (7 doubles
-// per workgroup: no atomics); k_grid reduces them.
-__global__ void __launch_bounds__(kBlock) k_bounds(BodyArrays b, PolytopeTables t, const double *__restrict__ shape_radius, double dt,
-                                                   double pad, ContactBuffers c)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    double v[7] = {0.0, DBL_MAX, DBL_MAX, DBL_MAX, -DBL_MAX, -DBL_MAX, -DBL_MAX}; // rmax, min xyz, max xyz
-    if (i < b.n) {
-        const uint32_t sid = b.shape_id[i];
-        const double *cc = t.centroids + 3 * (size_t)sid;
-        const Vec3 centre = body_frame(b, i) * Vec3{cc[0], cc[1], cc[2]};
-        const Vec3 vel = load3(b.dyn, D_VEL, b.stride, i);
-        const double rs = shape_radius[sid], travel = length(vel) * dt;
-        const double r = rs + (travel < rs ? travel : rs) + pad;
-        store3(c.centers, 0, b.stride, i, centre);
-        c.radius[i] = r;
-        v[0] = (r > 0.0 && r <= DBL_MAX) ? r : 0.0;
-        const double xyz[3] = {centre.x, centre.y, centre.z};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { // a NaN coordinate opens the box completely: the grid then falls back to hashing
-            v[1 + a] = xyz[a] == xyz[a] ? xyz[a] : -DBL_MAX;
-            v[4 + a] = xyz[a] == xyz[a] ? xyz[a] : DBL_MAX;
-        }
-    }
-    __shared__ double part[kBlock / 64][7];
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-        double x = v[q];
-        for (uint32_t off = 32; off; off >>= 1) {
-            const double o = __shfl_xor(x, off, 64);
-            x = (q >= 1 && q <= 3) ? (o < x ? o : x) : (o > x ? o : x);
-        }
-        if ((threadIdx.x & 63u) == 0)
-            part[threadIdx.x >> 6][q] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const uint32_t q = threadIdx.x;
-        double x = part[0][q];
-        for (uint32_t w = 1; w < kBlock / 64; ++w) {
-            const double o = part[w][q];
-            x = (q >= 1 && q <= 3) ? (o < x ? o : x) : (o > x ? o : x);
-        }
-        c.grid_partials[(size_t)blockIdx.x * 7 + q] = x;
-    }
-}
-
-__device__ __forceinline__ double clamp_cell(double q)
-{
-    if (!(q >= -1.0e9)) // NaN or far negative
-        q = -1.0e9;
-    return q > 1.0e9 ? 1.0e9 : q;
-}
-
-// One workgroup: reduces the partials of k_bounds to the grid of this broadphase.  Cell edge = 2 * largest radius, so
-// overlapping spheres sit in adjacent cells.  When the box of all centres (plus one cell of margin on every side)
-// has no more cells than the table has buckets, the bucket key is the LINEAR cell index (`dense`): neighbouring
-// cells are neighbouring buckets, the 27 lookups of a body become 9 runs of 3 consecutive entries and bodies next to
-// each other share them.  Otherwise the key is a hash of the cell and buckets may hold several cells.
-__global__ void __launch_bounds__(kBlock) k_grid(ContactBuffers c, uint32_t n_partials)
-{
-    __shared__ double part[kBlock / 64][7];
-    double v[7] = {0.0, DBL_MAX, DBL_MAX, DBL_MAX, -DBL_MAX, -DBL_MAX, -DBL_MAX};
-    for (uint32_t k = threadIdx.x; k < n_partials; k += kBlock)
-#pragma unroll
-        for (int q = 0; q < 7; ++q) {
-            const double o = c.grid_partials[(size_t)k * 7 + q];
-            v[q] = (q >= 1 && q <= 3) ? (o < v[q] ? o : v[q]) : (o > v[q] ? o : v[q]);
-        }
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-        double x = v[q];
-        for (uint32_t off = 32; off; off >>= 1) {
-            const double o = __shfl_xor(x, off, 64);
-            x = (q >= 1 && q <= 3) ? (o < x ? o : x) : (o > x ? o : x);
-        }
-        if ((threadIdx.x & 63u) == 0)
-            part[threadIdx.x >> 6][q] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0)
-        return;
-    for (int q = 0; q < 7; ++q)
-        for (uint32_t w = 1; w < kBlock / 64; ++w) {
-            const double o = part[w][q];
-            part[0][q] = (q >= 1 && q <= 3) ? (o < part[0][q] ? o : part[0][q]) : (o > part[0][q] ? o : part[0][q]);
-        }
-    GridInfo g;
-    g.edge = 2.0 * part[0][0];
-    double cells = 1.0;
-    for (int a = 0; a < 3; ++a) {
-        const double lo = g.edge > 0.0 ? clamp_cell(floor(part[0][1 + a] / g.edge)) : 0.0;
-        const double hi = g.edge > 0.0 ? clamp_cell(floor(part[0][4 + a] / g.edge)) : 0.0;
-        const double dim = hi >= lo ? hi - lo + 3.0 : 3.0; // one cell of margin on either side
-        g.origin[a] = (int32_t)lo - 1;
-        g.dims[a] = dim <= 2147483647.0 ? (uint32_t)dim : 0x7FFFFFFFu;
-        cells *= dim;
-    }
-    g.dense = (g.edge > 0.0 && cells <= (double)c.table_size) ? 1u : 0u;
-    *c.grid = g;
-}
-
-__device__ __forceinline__ uint32_t cell_key(const GridInfo &g, uint32_t table_size, int32_t x, int32_t y, int32_t z)
-{
-    if (g.dense)
-        return (uint32_t)(x - g.origin[0]) + g.dims[0] * ((uint32_t)(y - g.origin[1]) + g.dims[1] * (uint32_t)(z - g.origin[2]));
-    return cell_hash(x, y, z) & (table_size - 1);
-}
-
-// Grid cell of every body and the population count of its bucket.
-__global__ void k_cells(BodyArrays b, ContactBuffers c)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= b.n)
-        return;
-    const GridInfo g = *c.grid;
-    const Vec3 centre = load3(c.centers, 0, b.stride, i);
-    int32_t cell[3];
-    const double coord[3] = {centre.x, centre.y, centre.z};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        cell[a] = (int32_t)(g.edge > 0.0 ? clamp_cell(floor(coord[a] / g.edge)) : 0.0);
-        c.cell[(size_t)a * b.stride + i] = cell[a];
-    }
-    const uint32_t key = cell_key(g, c.table_size, cell[0], cell[1], cell[2]);
-    c.key[i] = key;
-    atomicAdd(&c.bucket_start[key], 1u);
-}
-
-// The scatter order inside a bucket depends on timing; the bucket's place of body i is instead its RANK among the
-// bodies of the bucket (ids are distinct), which every body works out for itself: one lane per body, O(bucket) reads
-// each.  (The first version sorted every bucket with one lane and an insertion sort: 55 us per broadphase on the
-// mixed scene, whose dense-grid buckets hold ~19 bodies.)
-__global__ void k_scatter(BodyArrays b, ContactBuffers c)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= b.n)
-        return;
-    const uint32_t key = c.key[i];
-    c.items_unsorted[c.bucket_start[key] + atomicAdd(&c.bucket_cursor[key], 1u)] = i;
-}
-
-__global__ void k_rank_items(BodyArrays b, ContactBuffers c)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= b.n)
-        return;
-    const uint32_t key = c.key[i];
-    const uint32_t lo = c.bucket_start[key], hi = c.bucket_start[key + 1];
-    uint32_t rank = 0;
-    for (uint32_t s = lo; s < hi; ++s)
-        rank += c.items_unsorted[s] < i;
-    c.items[lo + rank] = i;
-}
-
-// Bounding spheres and cells once more, in bucket (slot) order: a bucket scan then reads contiguous memory.
-__global__ void k_gather_slots(BodyArrays b, ContactBuffers c)
-{
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= b.n)
-        return;
-    const uint32_t j = c.items[s];
-    const size_t st = b.stride;
-#pragma unroll
-    for (uint32_t a = 0; a < 3; ++a) {
-        c.slot_sphere[a * st + s] = c.centers[a * st + j];
-        c.slot_cell[a * st + s] = c.cell[a * st + j];
-    }
-    c.slot_sphere[3 * st + s] = c.radius[j];
-    if (c.filter) { // (a kernel argument: uniform)
-        const uint2 f = c.filter[j];
-        c.slot_filter[s] = f.x;
-        c.slot_filter[st + s] = f.y;
-    }
-}
-
-// ... and, in a world with sleeping on, who of them is inert.
-__global__ void k_gather_slot_inert(BodyArrays b, ContactBuffers c, InertBodies inert)
-{
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < b.n)
-        inert.slot_inert[s] = inert.inert[c.items[s]];
-}
-
-constexpr uint32_t kCellLanes = 8;    // lanes per body in the neighbour kernels
-constexpr uint32_t kNbrStage = 128;   // neighbours of one body staged in LDS for the rank sort
-constexpr uint32_t kBodiesPerBlock = kBlock / kCellLanes;
-
-// Bucket ranges of the 27 cells around one body, in LDS (one row per body of the block).
-struct CellRanges {
-    uint32_t start[kBodiesPerBlock][27];
-    uint32_t len[kBodiesPerBlock][27];
-};
-
-// A joint of the world links i and j.  joint_list holds every joint at both of its ends, so joined(i, j) == joined(j, i).
-__device__ __forceinline__ bool joined(const ContactBuffers &c, uint32_t i, uint32_t j)
-{
-    for (uint32_t k = c.joint_off[i]; k < c.joint_off[i + 1]; ++k) {
-        const Joint &jt = c.joints[c.joint_list[k]];
-        if ((jt.body_a == i ? jt.body_b : jt.body_a) == j)
-            return true;
-    }
-    return false;
-}
-
-// Is body i / the body in slot s inert?  (Without a table: nobody is.)
-__device__ __forceinline__ bool inert_body(uint32_t) { return false; }
-__device__ __forceinline__ bool inert_body(uint32_t i, const InertBodies &t) { return t.inert[i] != 0; }
-__device__ __forceinline__ bool inert_slot(uint32_t) { return false; }
-__device__ __forceinline__ bool inert_slot(uint32_t s, const InertBodies &t) { return t.slot_inert[s] != 0; }
-
-// Neighbour search of body i by its group of kCellLanes lanes (`cl` = lane inside the group, `g` = the group's row in
-// the LDS tables).  First the 27 bucket ranges are fetched side by side; then the lanes stride over the CONCATENATION
-// of the 27 ranges, so every lane has independent loads in flight whatever the occupancy of the single cells.
-// Several cells can share a bucket, so a candidate counts only when it sits in the cell being visited: every
-// overlapping j != i is visited exactly once, by exactly one lane.  Must be called by all lanes of the block
-// (`live` = false for the groups past the last body): it contains a barrier.
-// FILTER: a pair whose collision filters exclude each other is no neighbour (the candidate's filter is read in slot order,
-// next to its sphere); JOINTED: nor is a pair joined by a joint.  Both tests are symmetric in i and j -- count, fill and
-// the pair index of both ends rely on every pair being seen from both of them or from neither.
-// inert... (nothing, or the InertBodies of a world with sleeping on): nor is a pair whose two ends are both inert, asleep or
-// fixed; one byte per slot, read as the slot's filter is.  Without the argument the two tests are constants and the function
-// is what it was before there was one.
-template <bool FILTER, bool JOINTED, class Visit, class... Inert>
-__device__ __forceinline__ void for_each_neighbour(const BodyArrays &b, const ContactBuffers &c, CellRanges &r, uint32_t i, bool live,
-                                                   uint32_t g, uint32_t cl, Visit visit, const Inert &...inert)
-{
-    const size_t st = b.stride;
-    int32_t cx = 0, cy = 0, cz = 0;
-    if (live) {
-        cx = c.cell[i], cy = c.cell[st + i], cz = c.cell[2 * st + i];
-        const GridInfo grid = *c.grid;
-        for (uint32_t k = cl; k < 27; k += kCellLanes) {
-            const int32_t nx = cx + (int32_t)(k % 3) - 1, ny = cy + (int32_t)((k / 3) % 3) - 1, nz = cz + (int32_t)(k / 9) - 1;
-            const uint32_t key = cell_key(grid, c.table_size, nx, ny, nz);
-            const uint32_t lo = c.bucket_start[key];
-            r.start[g][k] = lo;
-            r.len[g][k] = c.bucket_start[key + 1] - lo;
-        }
-    }
-    __syncthreads();
-    if (!live)
-        return;
-    const Vec3 ci = load3(c.centers, 0, b.stride, i);
-    const double ri = c.radius[i];
-    uint2 fi = {0u, 0u};
-    if (FILTER)
-        fi = c.filter[i];
-    const bool inert_i = inert_body(i, inert...);
-    uint32_t k = 0, base = 0; // cell being walked and the position of its first candidate in the concatenation
-    for (uint32_t q = cl;; q += kCellLanes) {
-        while (k < 27 && q >= base + r.len[g][k])
-            base += r.len[g][k++];
-        if (k == 27)
-            break;
-        const uint32_t s = r.start[g][k] + (q - base);
-        const int32_t nx = cx + (int32_t)(k % 3) - 1, ny = cy + (int32_t)((k / 3) % 3) - 1, nz = cz + (int32_t)(k / 9) - 1;
-        if (c.slot_cell[s] != nx || c.slot_cell[st + s] != ny || c.slot_cell[2 * st + s] != nz)
-            continue;
-        const uint32_t j = c.items[s];
-        if (j == i)
-            continue;
-        const Vec3 d = ci - load3(c.slot_sphere, 0, b.stride, s);
-        const double reach = ri + c.slot_sphere[3 * st + s];
-        if (!(dot(d, d) < reach * reach))
-            continue;
-        if (FILTER && !((fi.x & c.slot_filter[st + s]) && (c.slot_filter[s] & fi.y)))
-            continue;
-        if (JOINTED && joined(c, i, j))
-            continue;
-        if (inert_i && inert_slot(s, inert...))
-            continue;
-        visit(j);
-    }
-}
-
-__device__ __forceinline__ uint32_t cell_group_sum(uint32_t v)
-{
-    for (uint32_t off = kCellLanes / 2; off; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// Counts of all neighbours of every body and of those with a larger id.
-// (inert...: see for_each_neighbour; the kernels of a world with sleeping on take the table as a third argument)
-template <bool FILTER, bool JOINTED, class... Inert>
-__global__ void __launch_bounds__(kBlock) k_neighbour_count(BodyArrays b, ContactBuffers c, Inert... inert)
-{
-    __shared__ CellRanges ranges;
-    const uint32_t g = threadIdx.x / kCellLanes, cl = threadIdx.x % kCellLanes;
-    // bodies in BUCKET order when the grid is dense (= cell order: the groups of a workgroup then search the same few
-    // cells), in index order under the scattering hash (bucket order is a random order there: 178 -> 335 us on `stacks`)
-    const uint32_t slot = blockIdx.x * kBodiesPerBlock + g;
-    const bool live = slot < b.n;
-    const uint32_t i = (live && c.grid->dense) ? c.items[slot] : slot;
-    uint32_t all = 0, upper = 0;
-    for_each_neighbour<FILTER, JOINTED>(b, c, ranges, i, live, g, cl, [&](uint32_t j) {
-        ++all;
-        upper += j > i;
-    }, inert...);
-    if (!live)
-        return;
-    all = cell_group_sum(all);
-    upper = cell_group_sum(upper);
-    if (cl == 0) {
-        c.nbr_off[i] = all;
-        c.pair_first[i] = upper;
-    }
-}
-
-// Neighbour list of every body, ASCENDING, the pair list i < j in (i, j) order, and upper_start.  The lanes append
-// their finds to an LDS list in arrival order; a rank sort (ids are distinct) then gives every entry its final
-// place, so the result does not depend on that order.  Lists longer than kNbrStage take a one-lane path.
-template <bool FILTER, bool JOINTED, class... Inert>
-__global__ void __launch_bounds__(kBlock) k_neighbour_fill(BodyArrays b, ContactBuffers c, Inert... inert)
-{
-    __shared__ CellRanges ranges;
-    __shared__ uint32_t stage[kBodiesPerBlock][kNbrStage];
-    __shared__ uint32_t cursor[kBodiesPerBlock];
-    const uint32_t g = threadIdx.x / kCellLanes, cl = threadIdx.x % kCellLanes;
-    const uint32_t slot = blockIdx.x * kBodiesPerBlock + g;
-    const bool live = slot < b.n;
-    const uint32_t i = (live && c.grid->dense) ? c.items[slot] : slot;
-    uint32_t lo = 0, total = 0;
-    if (live) {
-        lo = c.nbr_off[i];
-        total = c.nbr_off[i + 1] - lo;
-    }
-    const bool staged = total <= kNbrStage;
-    if (cl == 0)
-        cursor[g] = 0; // for_each_neighbour's barrier comes before the first visit
-    for_each_neighbour<FILTER, JOINTED>(b, c, ranges, i, live, g, cl, [&](uint32_t j) {
-        const uint32_t pos = atomicAdd(&cursor[g], 1u);
-        if (staged)
-            stage[g][pos] = j;
-        else
-            c.nbr[lo + pos] = j;
-    }, inert...);
-    __syncthreads();
-    if (!live)
-        return;
-    const uint32_t first = c.pair_first[i];
-    if (staged) {
-        // entry e of the arrival list goes to place rank(e); lane cl takes e = cl, cl + kCellLanes, ...
-        uint32_t below = 0;
-        for (uint32_t e = cl; e < total; e += kCellLanes)
-            below += stage[g][e] < i;
-        below = cell_group_sum(below);
-        if (cl == 0)
-            c.upper_start[i] = lo + below;
-        for (uint32_t e = cl; e < total; e += kCellLanes) {
-            const uint32_t v = stage[g][e];
-            uint32_t rank = 0;
-            for (uint32_t k = 0; k < total; ++k)
-                rank += stage[g][k] < v;
-            c.nbr[lo + rank] = v;
-            if (v > i) {
-                const size_t pair = (size_t)first + (rank - below);
-                c.pairs[2 * pair] = i;
-                c.pairs[2 * pair + 1] = v;
-            }
-        }
-    } else if (cl == 0) {
-        for (uint32_t a = lo + 1; a < lo + total; ++a) {
-            const uint32_t v = c.nbr[a];
-            uint32_t q = a;
-            while (q > lo && c.nbr[q - 1] > v) {
-                c.nbr[q] = c.nbr[q - 1];
-                --q;
-            }
-            c.nbr[q] = v;
-        }
-        uint32_t below = 0;
-        while (below < total && c.nbr[lo + below] < i)
-            ++below;
-        c.upper_start[i] = lo + below;
-        for (uint32_t k = below; k < total; ++k) {
-            c.pairs[2 * (size_t)(first + k - below)] = i;
-            c.pairs[2 * (size_t)(first + k - below) + 1] = c.nbr[lo + k];
-        }
-    }
-}
-
-__global__ void k_neighbour_pair_index(BodyArrays b, ContactBuffers c)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= b.n)
-        return;
-    for (uint32_t k = c.nbr_off[i]; k < c.nbr_off[i + 1]; ++k) {
-        const uint32_t j = c.nbr[k];
-        if (j > i) {
-            c.nbr_pair[k] = c.pair_first[i] + (k - c.upper_start[i]);
-        } else {
-            // i sits in the upper part of j's ascending list: binary search
-            uint32_t lo = c.upper_start[j], hi = c.nbr_off[j + 1];
-            while (lo + 1 < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (c.nbr[mid] <= i)
-                    lo = mid;
-                else
-                    hi = mid;
-            }
-            c.nbr_pair[k] = c.pair_first[j] + (lo - c.upper_start[j]);
-        }
-    }
-}
 
 // Contact materials (include/xpbd.h, "Contact MATERIALS"): the coefficient of a contact is the smaller of its two sides'.
 // (The coefficients are validated on the host: never NaN, so the comparison is an exact minimum.)
@@ -580,12 +68,7 @@ __global__ void __launch_bounds__(kBlock) k_integrate_ground(BodyArrays b, Shape
                                                              uint32_t *__restrict__ trace_masks, uint32_t trace_row)
 {
     extern __shared__ double lds[]; // shape vertex tables, as in k_step
-    uint32_t *lds_off = reinterpret_cast<uint32_t *>(lds + 3 * shapes.total_verts);
-    for (uint32_t k = threadIdx.x; k < 3 * shapes.total_verts; k += blockDim.x)
-        lds[k] = shapes.verts[k];
-    for (uint32_t k = threadIdx.x; k <= shapes.n_shapes; k += blockDim.x)
-        lds_off[k] = shapes.offsets[k];
-    __syncthreads();
+    uint32_t *lds_off = stage_shape_tables(lds, shapes);
 
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t i;
@@ -616,53 +99,6 @@ __global__ void __launch_bounds__(kBlock) k_integrate_ground(BodyArrays b, Shape
     last_mask[i] = mask;
     if (TRACE)
         trace_masks[(size_t)trace_row * st + i] = mask;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Heightfield terrain (include/xpbd.h, "TERRAIN"): the plane table, once per xpbd_world_set_terrain, and the sampling call.
-// ---------------------------------------------------------------------------------------------------
-// One lane per cell: the planes of its lower (h00, h10, h11) and upper (h00, h11, h01) triangle, each {n.x, n.y, n.z, d}, as one
-// 64-byte record.  The header's formulas, operation by operation; (double)i is the lookup's floor(u).
-__global__ void __launch_bounds__(kBlock) k_terrain_planes(const double *__restrict__ heights, Terrain t, double *__restrict__ planes)
-{
-    const uint32_t cells_x = t.nx - 1;
-    const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
-    if (cell >= cells_x * (t.ny - 1))
-        return;
-    const uint32_t i = cell % cells_x, j = cell / cells_x;
-    const double *row = heights + (size_t)j * t.nx + i;
-    const double h00 = row[0], h10 = row[1], h01 = row[t.nx], h11 = row[t.nx + 1];
-    const Vec3 corner{t.x0 + (double)i * t.dx, t.y0 + (double)j * t.dy, h00};
-    double *out = planes + (size_t)cell * 8;
-#pragma unroll
-    for (uint32_t upper = 0; upper < 2; ++upper) {
-        const double sx = upper ? (h11 - h01) / t.dx : (h10 - h00) / t.dx;
-        const double sy = upper ? (h01 - h00) / t.dy : (h11 - h10) / t.dy;
-        const Vec3 raw{-sx, -sy, 1.0};
-        const Vec3 n = raw * (1.0 / length(raw));
-        out[4 * upper + 0] = n.x, out[4 * upper + 1] = n.y, out[4 * upper + 2] = n.z;
-        out[4 * upper + 3] = dot(n, corner);
-    }
-}
-
-// One lane per point: the stepper's lookup at (x, y, 0), then the plane solved for z.
-__global__ void __launch_bounds__(kBlock) k_sample_terrain(Terrain t, const double *__restrict__ xy, uint32_t n, double *__restrict__ height,
-                                                           double *__restrict__ normal_xyz)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n)
-        return;
-    const double x = xy[2 * (size_t)k + 0], y = xy[2 * (size_t)k + 1];
-    Plane p;
-    double z = __builtin_nan("");
-    Vec3 normal{0.0, 0.0, 0.0};
-    if (terrain_plane(t, Vec3{x, y, 0.0}, p)) {
-        z = (p.displacement - (p.normal.x * x + p.normal.y * y)) / p.normal.z;
-        normal = p.normal;
-    }
-    height[k] = z;
-    if (normal_xyz)
-        normal_xyz[3 * (size_t)k + 0] = normal.x, normal_xyz[3 * (size_t)k + 1] = normal.y, normal_xyz[3 * (size_t)k + 2] = normal.z;
 }
 
 __global__ void k_body_frames(BodyArrays b, double *__restrict__ rec)
@@ -817,15 +253,6 @@ __device__ __forceinline__ Vec3 frame_delta(const Frame &cur, const Frame &past,
 {
     const Vec3 local = inverse(cur) * global;
     return global - past * local;
-}
-
-// Constraint::inverse_resitance for one body, src/constraint.rs:25-32
-// (Body: PairBody -- the pose after the ground contacts -- or the velocity pass's VelBody, the pose after derive)
-template <class Body>
-__device__ __forceinline__ double generalized_inverse_mass(const Body &p, Vec3 point, Vec3 dir)
-{
-    const Vec3 angular_impulse = conjugate(p.rot) * cross(point - (p.pos + p.com), dir);
-    return p.inv_mass + dot(p.inv_inertia * angular_impulse, angular_impulse);
 }
 
 // The angular limits of joint `joint` for body `self` (xpbd.h, XPBD_LIMIT_*): every limit that binds is a Jacobi entry of its
@@ -1199,12 +626,7 @@ __global__ void __launch_bounds__(kBlock, XPBD_PAIR_SOLVE_MIN_WAVES) k_pair_solv
     uint32_t *__restrict__ last_mask, uint32_t *__restrict__ trace_masks, uint32_t trace_row)
 {
     extern __shared__ double lds[]; // shape vertex tables, as in k_integrate_ground
-    uint32_t *lds_off = reinterpret_cast<uint32_t *>(lds + 3 * shapes.total_verts);
-    for (uint32_t k = threadIdx.x; k < 3 * shapes.total_verts; k += blockDim.x)
-        lds[k] = shapes.verts[k];
-    for (uint32_t k = threadIdx.x; k <= shapes.n_shapes; k += blockDim.x)
-        lds_off[k] = shapes.offsets[k];
-    __syncthreads();
+    uint32_t *lds_off = stage_shape_tables(lds, shapes);
 
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x, slot = gid / G, sub = gid % G;
     constexpr bool kStage = G == 1 && XPBD_PAIR_SOLVE_STAGE_RECORDS; // see k_pair_solve_derive
@@ -1376,532 +798,25 @@ __global__ void __launch_bounds__(kBlock) k_joint_extras(double h, ContactBuffer
     store_extra_sum(c.joint_extra + (size_t)c.extra_slots[2 * t + 1] * kJointExtraDoubles, sum_b);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Per substep, per body: restitution, the velocity pass after derive (include/xpbd.h, "RESTITUTION").
-// ---------------------------------------------------------------------------------------------------
-// What the pass needs of a body: pose and velocities after derive, velocities at the start of the substep, mass properties.
-struct VelBody {
-    Vec3 pos;
-    Quat rot;
-    Vec3 vel, ang, vel0, ang0;
-    double inv_mass;
-    Mat3 inv_inertia;
-    Vec3 com;
-};
-
-// post: the 13 dynamic fields after derive (SoA, as b.dyn); start: velocity and angular velocity at the start of the substep,
-// [6][stride]
-__device__ __forceinline__ VelBody load_vel_body(const double *__restrict__ post, const double *__restrict__ start, uint32_t st,
-                                                 const ContactBuffers &c, uint32_t i)
+// The one choice of the pair-solve kernels' form: launch(G, MATERIALS) with G = lanes per body as std::integral_constant --
+// kMaxManifoldPoints up to kSmallWorld bodies, else 1 -- and MATERIALS as std::bool_constant (contact materials: uniform
+// over the launch, see pair_solve_derive_body).
+template <class Launch>
+void with_pair_solve_form(const BodyArrays &b, const ContactBuffers &c, Launch &&launch)
 {
-    const BodyDynamic d = load_dynamic(post, st, i);
-    const StatRecord s = load_stat_record(c.stat_rec, c.stat_index ? c.stat_index[i] : i);
-    VelBody v;
-    v.pos = d.pos, v.rot = d.rot, v.vel = d.vel, v.ang = d.ang;
-    v.vel0 = load3(start, 0, st, i);
-    v.ang0 = load3(start, 3, st, i);
-    v.inv_mass = s.inv_mass;
-    v.inv_inertia = s.inv_inertia;
-    v.com = s.com;
-    return v;
+    with_flag(c.friction != nullptr, [&](auto materials) {
+        if (b.n <= kSmallWorld)
+            launch(std::integral_constant<uint32_t, kMaxManifoldPoints>{}, materials);
+        else
+            launch(std::integral_constant<uint32_t, 1>{}, materials);
+    });
 }
-
-constexpr uint32_t kRestitutionSweeps = XPBD_RESTITUTION_SWEEPS; // passes over the points of one manifold
-
-__device__ __forceinline__ double max_restitution(double a, double b) { return a < b ? b : a; }
-
-// One lane per body.  Reads the post-derive state of every body from `post` and the start-of-substep velocities from `start`,
-// writes the body's whole end-of-substep state to b.dyn, which no lane of this launch reads.
-// TERRAIN: the ground part looks the terrain's plane up at every vertex of the mask again (the pose has moved since the
-// integrate + ground stage): outside the field the vertex makes no entry, inside the plane's normal stands for (0, 0, 1).
-template <bool TERRAIN>
-__global__ void __launch_bounds__(kBlock) k_restitution(BodyArrays b, const double *__restrict__ post, const double *__restrict__ start,
-                                                        ShapeTable shapes, ContactBuffers c, const uint32_t *__restrict__ ground_masks)
-{
-    extern __shared__ double lds[]; // shape vertex tables, as in k_integrate_ground
-    uint32_t *lds_off = reinterpret_cast<uint32_t *>(lds + 3 * shapes.total_verts);
-    for (uint32_t k = threadIdx.x; k < 3 * shapes.total_verts; k += blockDim.x)
-        lds[k] = shapes.verts[k];
-    for (uint32_t k = threadIdx.x; k <= shapes.n_shapes; k += blockDim.x)
-        lds_off[k] = shapes.offsets[k];
-    __syncthreads();
-
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= b.n)
-        return;
-    const uint32_t st = b.stride;
-    VelBody self = load_vel_body(post, start, st, c, i);
-    const double e_self = c.restitution[i], threshold = c.bounce_threshold;
-    const Vec3 centre = self.pos + self.com;
-
-    // pair contacts: Jacobi over the manifolds on the post-derive velocities, neighbour order
-    Vec3 dv{0.0, 0.0, 0.0}, dw{0.0, 0.0, 0.0};
-    uint32_t count = 0;
-    const uint32_t k_end = c.nbr_off[i + 1];
-    for (uint32_t k = c.nbr_off[i]; k < k_end; ++k) {
-        const uint32_t pair = c.nbr_pair[k];
-        const uint32_t code = c.pair_codes[pair];
-        const uint32_t n_points = code & ((1u << kPairCodeFeatureShift) - 1u);
-        if (!n_points)
-            continue;
-        const uint32_t j = c.nbr[k];
-        const double e = max_restitution(e_self, c.restitution[j]); // (the larger of two values: the same from both sides)
-        if (!(e > 0.0))
-            continue;
-        const VelBody other = load_vel_body(post, start, st, c, j);
-        const Vec3 centre_other = other.pos + other.com;
-        const ContactManifold *m = c.manifolds + pair;
-        const uint32_t feature = code >> kPairCodeFeatureShift;
-        // roles and points exactly as pair_solve_derive_body forms them
-        const bool self_is_a = i < j;
-        const bool ref_is_a = feature != 1u;
-        const bool self_is_inc = self_is_a != ref_is_a;
-        const bool face = feature != 2u;
-        const Plane ref_plane{Vec3{m->plane[0], m->plane[1], m->plane[2]}, m->plane[3]};
-        // Sequential impulses inside the manifold, on copies of the two bodies' post-derive velocities: every point keeps the
-        // impulse it has applied so far (never negative), kRestitutionSweeps passes in point order.  Both bodies of the pair
-        // run the same sequence on the same values (3-vectors selected by role, w_inc + w_ref commutes): the same bits.
-        Vec3 v_s = self.vel, w_s = self.ang, v_o = other.vel, w_o = other.ang;
-        double total[kMaxManifoldPoints];
-#pragma unroll
-        for (uint32_t pt = 0; pt < kMaxManifoldPoints; ++pt)
-            total[pt] = 0.0;
-        uint32_t applied = 0;
-        for (uint32_t sweep = 0; sweep < kRestitutionSweeps; ++sweep) {
-#pragma unroll
-            for (uint32_t pt = 0; pt < kMaxManifoldPoints; ++pt) { // (unrolled: total[] stays in registers)
-                if (pt >= n_points)
-                    break;
-                const Vec3 p_inc{m->point[pt][0], m->point[pt][1], m->point[pt][2]};
-                Vec3 p_ref, n;
-                if (face) {
-                    const double depth = distance(ref_plane, p_inc);
-                    p_ref = p_inc - depth * ref_plane.normal;
-                    n = ref_plane.normal;
-                } else {
-                    p_ref = Vec3{m->point[1][0], m->point[1][1], m->point[1][2]};
-                    const Vec3 d = p_ref - p_inc;
-                    const double len = length(d);
-                    if (len == 0.0)
-                        continue;
-                    n = d * (1.0 / len);
-                }
-                const Vec3 p_self = self_is_inc ? p_inc : p_ref, p_other = self_is_inc ? p_ref : p_inc;
-                const Vec3 arm = p_self - centre, arm_other = p_other - centre_other;
-                const Vec3 u_self = v_s + cross(w_s, arm), u_other = v_o + cross(w_o, arm_other);
-                const Vec3 u0_self = self.vel0 + cross(self.ang0, arm), u0_other = other.vel0 + cross(other.ang0, arm_other);
-                const double vn = dot(n, self_is_inc ? u_self - u_other : u_other - u_self);      // incident - reference
-                const double vn0 = dot(n, self_is_inc ? u0_self - u0_other : u0_other - u0_self);
-                // w = w_incident + w_reference; IEEE addition commutes
-                const double w = generalized_inverse_mass(self, p_self, n) + generalized_inverse_mass(other, p_other, n);
-                if (!(vn0 < -threshold && w > 0.0))
-                    continue;
-                double wanted = total[pt] + ((-e) * vn0 - vn) / w;
-                if (!(wanted > 0.0))
-                    wanted = 0.0;
-                const double lambda = wanted - total[pt];
-                if (lambda == 0.0)
-                    continue;
-                total[pt] = wanted;
-                const Vec3 plus = lambda * n, minus = (-lambda) * n; // on the incident, on the reference body
-                const Vec3 impulse = self_is_inc ? plus : minus, impulse_other = self_is_inc ? minus : plus;
-                v_s = v_s + impulse * self.inv_mass;
-                w_s = w_s + cross(self.inv_inertia * arm, impulse);
-                v_o = v_o + impulse_other * other.inv_mass;
-                w_o = w_o + cross(other.inv_inertia * arm_other, impulse_other);
-                ++applied;
-            }
-        }
-        if (applied) { // one Jacobi entry per manifold that bounced
-            dv = dv + (v_s - self.vel);
-            dw = dw + (w_s - self.ang);
-            ++count;
-        }
-    }
-    if (count) {
-        const double cnt = (double)count;
-        self.vel = self.vel + dv / cnt;
-        self.ang = self.ang + dw / cnt;
-    }
-
-    // ground: the vertices of this substep's contact mask in vertex order, each applied at once
-    const double e_ground = max_restitution(e_self, c.ground_restitution);
-    const uint32_t mask = ground_masks[i];
-    if (e_ground > 0.0 && mask) {
-        const uint32_t sid = b.shape_id[i];
-        const double *verts = lds + 3 * lds_off[sid];
-        const Frame frame{frame_origin(self.pos, self.rot, self.com), self.rot};
-        Vec3 n{0.0, 0.0, 1.0};
-        const double target_scale = -e_ground;
-        for (uint32_t todo = mask; todo != 0; todo &= todo - 1) {
-            const uint32_t v = __ffs(todo) - 1;
-            const Vec3 p = frame * Vec3{verts[3 * v + 0], verts[3 * v + 1], verts[3 * v + 2]};
-            if (TERRAIN) {
-                Plane plane;
-                if (!terrain_plane(c.terrain, p, plane))
-                    continue;
-                n = plane.normal;
-            }
-            const Vec3 arm = p - centre;
-            const double vn = dot(n, self.vel + cross(self.ang, arm));
-            const double vn0 = dot(n, self.vel0 + cross(self.ang0, arm));
-            const double w = generalized_inverse_mass(self, p, n);
-            const double target = target_scale * vn0;
-            if (!(vn0 < -threshold && vn < target && w > 0.0))
-                continue;
-            const double lambda = (target - vn) / w;
-            const Vec3 impulse = lambda * n;
-            self.vel = self.vel + impulse * self.inv_mass;
-            self.ang = self.ang + cross(self.inv_inertia * arm, impulse);
-        }
-    }
-
-    BodyDynamic d;
-    d.pos = self.pos, d.rot = self.rot, d.vel = self.vel, d.ang = self.ang;
-    store_dynamic(b.dyn, st, i, d);
-}
-
-// The pass has no subset form.  The bodies a BodySubset skips (the sleepers of a world with sleeping on) are put back
-// afterwards from `post`, which holds their state as it was: one lane per body, 13 stores for a skipped one.
-__global__ void __launch_bounds__(kBlock) k_restitution_put_back(BodyArrays b, const double *__restrict__ post, const uint8_t *__restrict__ skip)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= b.n || !skip[i])
-        return;
-    for (uint32_t f = 0; f < kDynFields; ++f)
-        b.dyn[(size_t)f * b.stride + i] = post[(size_t)f * b.stride + i];
-}
-
-// Halo exchange: one lane per (body, field); the buffer side is contiguous, the SoA side is a gather.
-__global__ void k_export_dynamic(BodyArrays b, const uint32_t *__restrict__ indices, uint32_t n, double *__restrict__ buf)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * kDynFields)
-        return;
-    const uint32_t k = t / kDynFields, f = t - k * kDynFields;
-    buf[t] = b.dyn[(size_t)f * b.stride + indices[k]];
-}
-
-// (rows: optional; entry k of the list then comes from row rows[k] of buf instead of row k -- the gathered halo
-// buffer of an all-gather can be imported as it is)
-__global__ void k_import_dynamic(BodyArrays b, const uint32_t *__restrict__ indices, const uint32_t *__restrict__ rows, uint32_t n,
-                                 const double *__restrict__ buf)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * kDynFields)
-        return;
-    const uint32_t k = t / kDynFields, f = t - k * kDynFields;
-    b.dyn[(size_t)f * b.stride + indices[k]] = buf[(size_t)(rows ? rows[k] : k) * kDynFields + f];
-}
-
-// ---- body edits (include/xpbd.h, "Body EDITS") ----------------------------------------------------------------------------
-// external_force / external_torque of the listed bodies: one lane per (entry, component), three force components and then
-// three torque components; force / torque may be NULL (that field is left alone), indices NULL means body k.  An index
-// outside the world is skipped.
-__global__ void k_set_wrench(BodyArrays b, const uint32_t *__restrict__ indices, uint32_t n, const double *__restrict__ force,
-                             const double *__restrict__ torque)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * 6u)
-        return;
-    const uint32_t k = t / 6u, f = t - k * 6u;
-    const uint32_t i = indices ? indices[k] : k;
-    if (i >= b.n)
-        return;
-    if (f < 3u) {
-        if (force)
-            b.stat[(size_t)(S_EXT_FORCE + f) * b.stride + i] = force[3 * (size_t)k + f];
-    } else if (torque) {
-        b.stat[(size_t)(S_EXT_TORQUE + (f - 3u)) * b.stride + i] = torque[3 * (size_t)k + (f - 3u)];
-    }
-}
-
-// One xpbd_impulse (80 bytes = five 16-byte loads): {body | flags << 32, P.x} {P.y, P.z} {point.x, point.y}
-// {point.z, L.x} {L.y, L.z}.
-struct ImpulseEntry {
-    uint32_t body, flags;
-    Vec3 impulse, point, angular;
-};
-
-__device__ __forceinline__ ImpulseEntry load_impulse(const ulonglong2 *__restrict__ list, uint32_t k)
-{
-    const ulonglong2 *e = list + (size_t)k * 5;
-    const ulonglong2 q0 = e[0], q1 = e[1], q2 = e[2], q3 = e[3], q4 = e[4];
-    ImpulseEntry r;
-    r.body = (uint32_t)q0.x;
-    r.flags = (uint32_t)(q0.x >> 32);
-    r.impulse = Vec3{__longlong_as_double((long long)q0.y), __longlong_as_double((long long)q1.x), __longlong_as_double((long long)q1.y)};
-    r.point = Vec3{__longlong_as_double((long long)q2.x), __longlong_as_double((long long)q2.y), __longlong_as_double((long long)q3.x)};
-    r.angular = Vec3{__longlong_as_double((long long)q3.y), __longlong_as_double((long long)q4.x), __longlong_as_double((long long)q4.y)};
-    return r;
-}
-
-__device__ __forceinline__ uint32_t impulse_body(const ulonglong2 *__restrict__ list, uint32_t k)
-{
-    return reinterpret_cast<const uint32_t *>(list + (size_t)k * 5)[0];
-}
-
-// Impulses on the listed bodies, the entries of one body adjacent (a run) and applied in list order.  One lane per entry; the
-// lane of a run's first entry does the whole run -- the body's mass properties, centre and velocities are loaded once, every
-// entry is applied to the result of the one before with the restitution pass's impulse arithmetic, the velocities are stored
-// once -- and the other lanes leave at once.  No two lanes write one body, so there are no atomics and the result does not
-// depend on the launch shape.  A long run is serial in its lane by design (the order is the semantics); the lanes of a wave
-// that have shorter runs wait for it.  A body outside the world is skipped.
-__global__ void __launch_bounds__(kBlock) k_apply_impulses(BodyArrays b, const ulonglong2 *__restrict__ list, uint32_t n)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n)
-        return;
-    const uint32_t i = impulse_body(list, k);
-    if (k != 0 && impulse_body(list, k - 1) == i)
-        return;
-    if (i >= b.n)
-        return;
-    const uint32_t st = b.stride;
-    const double inv_mass = b.stat[(size_t)S_INV_MASS * st + i];
-    Mat3 inv_inertia;
-    inv_inertia.cx = load3(b.stat, S_INV_INERTIA + 0, st, i);
-    inv_inertia.cy = load3(b.stat, S_INV_INERTIA + 3, st, i);
-    inv_inertia.cz = load3(b.stat, S_INV_INERTIA + 6, st, i);
-    const Vec3 centre = load3(b.dyn, D_POS, st, i) + load3(b.stat, S_COM, st, i);
-    Vec3 vel = load3(b.dyn, D_VEL, st, i), ang = load3(b.dyn, D_ANG, st, i);
-    for (uint32_t j = k; j < n; ++j) {
-        const ImpulseEntry e = load_impulse(list, j);
-        if (e.body != i)
-            break;
-        vel = vel + e.impulse * inv_mass;
-        if (!(e.flags & XPBD_IMPULSE_AT_CENTRE)) {
-            const Vec3 arm = e.point - centre;
-            ang = ang + cross(inv_inertia * arm, e.impulse);
-        }
-        ang = ang + inv_inertia * e.angular;
-    }
-    store3(b.dyn, D_VEL, st, i, vel);
-    store3(b.dyn, D_ANG, st, i, ang);
-}
-
-// Halo validity (multi-GPU): positions of the listed bodies when the halos were chosen ...
-__global__ void k_snapshot_positions(BodyArrays b, const uint32_t *__restrict__ indices, uint32_t n, double *__restrict__ snapshot)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n)
-        return;
-    const Vec3 p = load3(b.dyn, D_POS, b.stride, indices[k]);
-    snapshot[3 * (size_t)k + 0] = p.x, snapshot[3 * (size_t)k + 1] = p.y, snapshot[3 * (size_t)k + 2] = p.z;
-}
-
-// ... and the largest squared distance any of them has travelled since: *out = max(*out, max_k |pos_k - snapshot_k|^2).
-// Non-negative doubles order like their bit patterns, so the maximum is an integer atomicMax (one per workgroup); a NaN
-// position counts as +inf.
-// (scale: optional per-entry factor on the squared distance, e.g. 1 / allowance^2: the result is then a ratio)
-__global__ void __launch_bounds__(kBlock) k_max_displacement2(BodyArrays b, const uint32_t *__restrict__ indices, uint32_t n,
-                                                              const double *__restrict__ snapshot, const double *__restrict__ scale,
-                                                              double *__restrict__ out)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    double d2 = 0.0;
-    if (k < n) {
-        const Vec3 p = load3(b.dyn, D_POS, b.stride, indices[k]);
-        const Vec3 d = p - Vec3{snapshot[3 * (size_t)k + 0], snapshot[3 * (size_t)k + 1], snapshot[3 * (size_t)k + 2]};
-        d2 = dot(d, d);
-        if (scale)
-            d2 *= scale[k];
-        if (!(d2 <= DBL_MAX))
-            d2 = __longlong_as_double(0x7FF0000000000000ll);
-    }
-    for (uint32_t off = 32; off; off >>= 1) {
-        const double o = __shfl_xor(d2, off, 64);
-        d2 = o > d2 ? o : d2;
-    }
-    __shared__ double part[kBlock / 64];
-    if ((threadIdx.x & 63u) == 0)
-        part[threadIdx.x >> 6] = d2;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (uint32_t w = 1; w < kBlock / 64; ++w)
-            d2 = part[w] > d2 ? part[w] : d2;
-        if (d2 > 0.0)
-            atomicMax(reinterpret_cast<unsigned long long *>(out), (unsigned long long)__double_as_longlong(d2));
-    }
-}
-
-// ---- re-planning the multi-GPU world without a host round trip of the bodies (xpbd_multi.cpp) --------------------------------
-// The grid cell of the bounding-sphere centre (position + center_of_mass, as the host planner adds them) of the listed
-// bodies: the same floor(c / edge), clamp and packing as xpbd_halo_cell_key, so the same bits.  *bad = the smallest list
-// index with a non-finite centre (UINT32_MAX: none).
-constexpr long long kHaloCellBias = 1ll << 20, kHaloCellLimit = kHaloCellBias - 4;
-
-__device__ __forceinline__ long long halo_clamp_cell(double q)
-{
-    const double lim = (double)kHaloCellLimit;
-    if (!(q >= -lim)) // NaN or far negative
-        return -kHaloCellLimit;
-    return q > lim ? kHaloCellLimit : (long long)q;
-}
-
-__global__ void k_cell_keys(BodyArrays b, const uint32_t *__restrict__ indices, uint32_t n, double edge, long long *__restrict__ keys,
-                            uint32_t *__restrict__ bad)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n)
-        return;
-    const uint32_t i = indices ? indices[k] : k;
-    const Vec3 p = load3(b.dyn, D_POS, b.stride, i), com = load3(b.stat, S_COM, b.stride, i);
-    const double c[3] = {p.x + com.x, p.y + com.y, p.z + com.z};
-    long long cell[3];
-    bool finite = true;
-    for (int a = 0; a < 3; ++a) {
-        finite = finite && fabs(c[a]) <= DBL_MAX;
-        cell[a] = halo_clamp_cell(floor(c[a] / edge));
-    }
-    if (!finite)
-        atomicMin(bad, k);
-    keys[k] = ((cell[0] + kHaloCellBias) << 42) | ((cell[1] + kHaloCellBias) << 21) | (cell[2] + kHaloCellBias);
-}
-
-__device__ __forceinline__ uint32_t aos_slot_of_field(uint32_t f) // xpbd_rigid double index of SoA field f (dyn first, then stat)
-{
-    if (f < kDynFields) // pos 31-33, rot 34-37, vel 22-24, ang 25-27
-        return f < 7 ? 31 + f : (f < 10 ? 22 + (f - 7) : 25 + (f - 10));
-    const uint32_t g = f - kDynFields; // 0..21 identical; com 28-30
-    return g < 22 ? g : 28 + (g - 22);
-}
-
-// out[k] = {xpbd_rigid of body indices[k] (38 doubles), its shape id as a double}: the plan-time record of a body
-__global__ void k_gather_records(BodyArrays b, const uint32_t *__restrict__ indices, uint32_t n, double *__restrict__ out)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    constexpr uint32_t kFields = kDynFields + kStatFields;
-    if (t >= n * (kFields + 1))
-        return;
-    const uint32_t k = t / (kFields + 1), f = t - k * (kFields + 1), i = indices[k];
-    double *rec = out + (size_t)k * (kFields + 1);
-    if (f == kFields)
-        rec[kFields] = (double)b.shape_id[i];
-    else
-        rec[aos_slot_of_field(f)] = f < kDynFields ? b.dyn[(size_t)f * b.stride + i] : b.stat[(size_t)(f - kDynFields) * b.stride + i];
-}
-
-// The bodies of a new local world in AoS: body s comes from slot src[s] of the old world's AoS copy (src[s] >= 0) or is
-// incoming record -src[s] - 1 (39 doubles each: xpbd_rigid + shape id).
-__global__ void k_repack_bodies(const double *__restrict__ old_aos, const uint32_t *__restrict__ old_shape, const int32_t *__restrict__ src,
-                                uint32_t n_new, const double *__restrict__ incoming, double *__restrict__ new_aos,
-                                uint32_t *__restrict__ new_shape)
-{
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    constexpr uint32_t kFields = kDynFields + kStatFields;
-    if (t >= (size_t)n_new * kFields)
-        return;
-    const uint32_t s = (uint32_t)(t / kFields), f = (uint32_t)(t - (size_t)s * kFields);
-    const int32_t from = src[s];
-    if (from >= 0) {
-        new_aos[t] = old_aos[(size_t)from * kFields + f];
-        if (f == 0)
-            new_shape[s] = old_shape[from];
-    } else {
-        const double *rec = incoming + (size_t)(-(from + 1)) * (kFields + 1);
-        new_aos[t] = rec[f];
-        if (f == 0)
-            new_shape[s] = (uint32_t)rec[kFields];
-    }
-}
-
-uint32_t blocks_for(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 } // namespace
 
 // ---------------------------------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------------------------------
-hipError_t launch_exclusive_scan(uint32_t *data, uint32_t n, uint32_t *scratch, hipStream_t stream)
-{
-    const uint32_t nb = (n + kBlock * 4 - 1) / (kBlock * 4);
-    if (nb == 0) {
-        return hipMemsetAsync(data, 0, sizeof(uint32_t), stream);
-    }
-    hipLaunchKernelGGL(k_scan_blocks, dim3(nb), dim3(kBlock), 0, stream, data, n, scratch);
-    hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(kBlock), 0, stream, scratch, nb);
-    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(kBlock), 0, stream, data, n, scratch, nb);
-    return hipGetLastError();
-}
-
-hipError_t launch_bounds_and_cells(const BodyArrays &b, const PolytopeTables &t, const double *shape_radius,
-                                   double dt, double pad, const ContactBuffers &c, hipStream_t stream)
-{
-    hipError_t e = hipMemsetAsync(c.bucket_start, 0, (size_t)(c.table_size + 1) * 4, stream);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(c.bucket_cursor, 0, (size_t)c.table_size * 4, stream);
-    if (e != hipSuccess || b.n == 0)
-        return e;
-    hipLaunchKernelGGL(k_bounds, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, t, shape_radius, dt, pad, c);
-    hipLaunchKernelGGL(k_grid, dim3(1), dim3(kBlock), 0, stream, c, blocks_for(b.n));
-    hipLaunchKernelGGL(k_cells, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_buckets(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream, const InertBodies &inert)
-{
-    hipError_t e = launch_exclusive_scan(c.bucket_start, c.table_size, c.scan_scratch, stream);
-    if (e != hipSuccess || b.n == 0)
-        return e;
-    hipLaunchKernelGGL(k_scatter, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
-    hipLaunchKernelGGL(k_rank_items, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
-    hipLaunchKernelGGL(k_gather_slots, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
-    if (inert.inert)
-        hipLaunchKernelGGL(k_gather_slot_inert, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c, inert);
-    return hipGetLastError();
-}
-
-// Which form of the neighbour kernels a broadphase runs: bit 0 = group / mask test, bit 1 = jointed-pair test (only when
-// there are joints).  A world without filters runs the plain form, the loads of which are those of a world before filters.
-// Bit 2 = both-ends-inert test (only with sleeping on): the kernels that take the table.
-static uint32_t filter_variant(const ContactBuffers &c, const InertBodies &inert)
-{
-    return (c.filter ? 1u : 0u) | (c.filter_jointed && c.joint_off ? 2u : 0u) | (inert.inert ? 4u : 0u);
-}
-
-hipError_t launch_neighbour_count(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream, const InertBodies &inert)
-{
-    if (b.n) {
-        const dim3 grid((b.n + kBodiesPerBlock - 1) / kBodiesPerBlock);
-        switch (filter_variant(c, inert)) {
-        case 0: hipLaunchKernelGGL((k_neighbour_count<false, false>), grid, dim3(kBlock), 0, stream, b, c); break;
-        case 1: hipLaunchKernelGGL((k_neighbour_count<true, false>), grid, dim3(kBlock), 0, stream, b, c); break;
-        case 2: hipLaunchKernelGGL((k_neighbour_count<false, true>), grid, dim3(kBlock), 0, stream, b, c); break;
-        case 3: hipLaunchKernelGGL((k_neighbour_count<true, true>), grid, dim3(kBlock), 0, stream, b, c); break;
-        case 4: hipLaunchKernelGGL((k_neighbour_count<false, false>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
-        case 5: hipLaunchKernelGGL((k_neighbour_count<true, false>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
-        case 6: hipLaunchKernelGGL((k_neighbour_count<false, true>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
-        default: hipLaunchKernelGGL((k_neighbour_count<true, true>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
-        }
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = launch_exclusive_scan(c.nbr_off, b.n, c.scan_scratch, stream);
-    if (e == hipSuccess)
-        e = launch_exclusive_scan(c.pair_first, b.n, c.scan_scratch, stream);
-    return e;
-}
-
-hipError_t launch_neighbour_fill(const BodyArrays &b, const ContactBuffers &c, hipStream_t stream, const InertBodies &inert)
-{
-    if (b.n == 0)
-        return hipSuccess;
-    const dim3 grid((b.n + kBodiesPerBlock - 1) / kBodiesPerBlock);
-    switch (filter_variant(c, inert)) {
-    case 0: hipLaunchKernelGGL((k_neighbour_fill<false, false>), grid, dim3(kBlock), 0, stream, b, c); break;
-    case 1: hipLaunchKernelGGL((k_neighbour_fill<true, false>), grid, dim3(kBlock), 0, stream, b, c); break;
-    case 2: hipLaunchKernelGGL((k_neighbour_fill<false, true>), grid, dim3(kBlock), 0, stream, b, c); break;
-    case 3: hipLaunchKernelGGL((k_neighbour_fill<true, true>), grid, dim3(kBlock), 0, stream, b, c); break;
-    case 4: hipLaunchKernelGGL((k_neighbour_fill<false, false>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
-    case 5: hipLaunchKernelGGL((k_neighbour_fill<true, false>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
-    case 6: hipLaunchKernelGGL((k_neighbour_fill<false, true>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
-    default: hipLaunchKernelGGL((k_neighbour_fill<true, true>), grid, dim3(kBlock), 0, stream, b, c, inert); break;
-    }
-    hipLaunchKernelGGL(k_neighbour_pair_index, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, c);
-    return hipGetLastError();
-}
-
 hipError_t launch_integrate_ground(const BodyArrays &b, const ShapeTable &s, double h, const ContactBuffers &c,
                                    uint32_t *last_mask, uint32_t *trace_masks, uint32_t trace_row, hipStream_t stream,
                                    const BodySubset &subset)
@@ -1909,38 +824,15 @@ hipError_t launch_integrate_ground(const BodyArrays &b, const ShapeTable &s, dou
     const uint32_t items = subset.list ? subset.count : b.n;
     if (items == 0)
         return hipSuccess;
-    const size_t lds_bytes = (size_t)s.total_verts * 3 * sizeof(double) + (size_t)(s.n_shapes + 1) * sizeof(uint32_t);
-    auto launch = [&](auto trace, auto materials) {
-        if (c.terrain.planes)
-            hipLaunchKernelGGL((k_integrate_ground<decltype(trace)::value, decltype(materials)::value, true>), dim3(blocks_for(items)),
-                               dim3(kBlock), lds_bytes, stream, b, s, h, c, subset, last_mask, trace_masks, trace_row);
-        else
-            hipLaunchKernelGGL((k_integrate_ground<decltype(trace)::value, decltype(materials)::value>), dim3(blocks_for(items)), dim3(kBlock),
-                               lds_bytes, stream, b, s, h, c, subset, last_mask, trace_masks, trace_row);
-    };
-    if (trace_masks && c.friction)
-        launch(std::true_type{}, std::true_type{});
-    else if (trace_masks)
-        launch(std::true_type{}, std::false_type{});
-    else if (c.friction)
-        launch(std::false_type{}, std::true_type{});
-    else
-        launch(std::false_type{}, std::false_type{});
-    return hipGetLastError();
-}
-
-hipError_t launch_terrain_planes(const double *heights, const Terrain &t, double *planes, hipStream_t stream)
-{
-    const uint32_t cells = (t.nx - 1) * (t.ny - 1);
-    hipLaunchKernelGGL(k_terrain_planes, dim3(blocks_for(cells)), dim3(kBlock), 0, stream, heights, t, planes);
-    return hipGetLastError();
-}
-
-hipError_t launch_sample_terrain(const Terrain &t, const double *xy, uint32_t n, double *height, double *normal_xyz, hipStream_t stream)
-{
-    if (n == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(k_sample_terrain, dim3(blocks_for(n)), dim3(kBlock), 0, stream, t, xy, n, height, normal_xyz);
+    const size_t lds_bytes = shape_lds_bytes(s);
+    with_flag(trace_masks != nullptr, [&](auto trace) {
+        with_flag(c.friction != nullptr, [&](auto materials) {
+            with_flag(c.terrain.planes != nullptr, [&](auto terrain) {
+                hipLaunchKernelGGL((k_integrate_ground<decltype(trace)::value, decltype(materials)::value, decltype(terrain)::value>),
+                                   dim3(blocks_for(items)), dim3(kBlock), lds_bytes, stream, b, s, h, c, subset, last_mask, trace_masks, trace_row);
+            });
+        });
+    });
     return hipGetLastError();
 }
 
@@ -1956,22 +848,11 @@ hipError_t launch_pair_solve_derive(const BodyArrays &b, double *dyn_out, double
     const uint32_t items = subset.list ? subset.count : b.n;
     if (items == 0)
         return hipSuccess;
-    auto launch = [&](auto lanes, auto materials) {
+    with_pair_solve_form(b, c, [&](auto lanes, auto materials) {
         constexpr uint32_t G = decltype(lanes)::value;
         hipLaunchKernelGGL((k_pair_solve_derive<G, decltype(materials)::value>), dim3(blocks_for(items * G)), dim3(kBlock), 0, stream, b,
                            dyn_out, h, c, subset);
-    };
-    using Wide = std::integral_constant<uint32_t, kMaxManifoldPoints>;
-    using One = std::integral_constant<uint32_t, 1>;
-    const bool small = b.n <= kSmallWorld;
-    if (small && c.friction)
-        launch(Wide{}, std::true_type{});
-    else if (small)
-        launch(Wide{}, std::false_type{});
-    else if (c.friction)
-        launch(One{}, std::true_type{});
-    else
-        launch(One{}, std::false_type{});
+    });
     return hipGetLastError();
 }
 
@@ -1983,23 +864,6 @@ hipError_t launch_joint_extras(double h, const ContactBuffers &c, hipStream_t st
     return hipGetLastError();
 }
 
-hipError_t launch_restitution(const BodyArrays &b, const double *post, const double *start, const ShapeTable &s, const ContactBuffers &c,
-                              const uint32_t *ground_masks, hipStream_t stream, const BodySubset &subset)
-{
-    if (b.n == 0)
-        return hipSuccess;
-    if (!c.restitution || post == b.dyn || start == b.dyn || subset.list)
-        return hipErrorInvalidValue; // (the kernel writes b.dyn while other lanes read `post` and `start`; it has no list form)
-    const size_t lds_bytes = (size_t)s.total_verts * 3 * sizeof(double) + (size_t)(s.n_shapes + 1) * sizeof(uint32_t);
-    if (c.terrain.planes)
-        hipLaunchKernelGGL(k_restitution<true>, dim3(blocks_for(b.n)), dim3(kBlock), lds_bytes, stream, b, post, start, s, c, ground_masks);
-    else
-        hipLaunchKernelGGL(k_restitution<false>, dim3(blocks_for(b.n)), dim3(kBlock), lds_bytes, stream, b, post, start, s, c, ground_masks);
-    if (subset.skip)
-        hipLaunchKernelGGL(k_restitution_put_back, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, post, subset.skip);
-    return hipGetLastError();
-}
-
 hipError_t launch_pair_solve_integrate_ground(const BodyArrays &b, const ShapeTable &s, double h, const ContactBuffers &c,
                                               double *next_rec, uint32_t *last_mask, uint32_t *trace_masks, uint32_t trace_row,
                                               hipStream_t stream, const BodySubset &subset)
@@ -2007,29 +871,14 @@ hipError_t launch_pair_solve_integrate_ground(const BodyArrays &b, const ShapeTa
     const uint32_t items = subset.list ? subset.count : b.n;
     if (items == 0)
         return hipSuccess;
-    const size_t lds_bytes = (size_t)s.total_verts * 3 * sizeof(double) + (size_t)(s.n_shapes + 1) * sizeof(uint32_t);
-    auto launch_form = [&](auto trace, auto lanes, auto materials) {
-        constexpr uint32_t G = decltype(lanes)::value;
-        hipLaunchKernelGGL((k_pair_solve_integrate_ground<decltype(trace)::value, G, decltype(materials)::value>), dim3(blocks_for(items * G)),
-                           dim3(kBlock), lds_bytes, stream, b, s, h, c, subset, next_rec, last_mask, trace_masks, trace_row);
-    };
-    auto launch = [&](auto trace, auto lanes) { // contact materials: uniform over the launch, see pair_solve_derive_body
-        if (c.friction)
-            launch_form(trace, lanes, std::true_type{});
-        else
-            launch_form(trace, lanes, std::false_type{});
-    };
-    using Wide = std::integral_constant<uint32_t, kMaxManifoldPoints>;
-    using One = std::integral_constant<uint32_t, 1>;
-    const bool small = b.n <= kSmallWorld;
-    if (trace_masks && small)
-        launch(std::true_type{}, Wide{});
-    else if (trace_masks)
-        launch(std::true_type{}, One{});
-    else if (small)
-        launch(std::false_type{}, Wide{});
-    else
-        launch(std::false_type{}, One{});
+    const size_t lds_bytes = shape_lds_bytes(s);
+    with_pair_solve_form(b, c, [&](auto lanes, auto materials) {
+        with_flag(trace_masks != nullptr, [&](auto trace) {
+            constexpr uint32_t G = decltype(lanes)::value;
+            hipLaunchKernelGGL((k_pair_solve_integrate_ground<decltype(trace)::value, G, decltype(materials)::value>), dim3(blocks_for(items * G)),
+                               dim3(kBlock), lds_bytes, stream, b, s, h, c, subset, next_rec, last_mask, trace_masks, trace_row);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -2037,81 +886,6 @@ hipError_t launch_body_frames_aos(const BodyArrays &b, double *frames, hipStream
 {
     if (b.n)
         hipLaunchKernelGGL(k_body_frames_aos, dim3(blocks_for(b.n)), dim3(kBlock), 0, stream, b, frames);
-    return hipGetLastError();
-}
-
-hipError_t launch_export_dynamic(const BodyArrays &b, const uint32_t *indices, uint32_t n, double *buf, hipStream_t stream)
-{
-    if (n)
-        hipLaunchKernelGGL(k_export_dynamic, dim3(blocks_for(n * kDynFields)), dim3(kBlock), 0, stream, b, indices, n, buf);
-    return hipGetLastError();
-}
-
-hipError_t launch_import_dynamic(const BodyArrays &b, const uint32_t *indices, const uint32_t *rows, uint32_t n, const double *buf,
-                                 hipStream_t stream)
-{
-    if (n)
-        hipLaunchKernelGGL(k_import_dynamic, dim3(blocks_for(n * kDynFields)), dim3(kBlock), 0, stream, b, indices, rows, n, buf);
-    return hipGetLastError();
-}
-
-hipError_t launch_set_wrench(const BodyArrays &b, const uint32_t *indices, uint32_t n, const double *force, const double *torque,
-                             hipStream_t stream)
-{
-    if (n > kMaxEditEntries)
-        return hipErrorInvalidValue;
-    if (n && (force || torque))
-        hipLaunchKernelGGL(k_set_wrench, dim3(blocks_for(n * 6u)), dim3(kBlock), 0, stream, b, indices, n, force, torque);
-    return hipGetLastError();
-}
-
-hipError_t launch_apply_impulses(const BodyArrays &b, const xpbd_impulse *list, uint32_t n, hipStream_t stream)
-{
-    static_assert(sizeof(xpbd_impulse) == 80 && sizeof(ulonglong2) == 16, "an xpbd_impulse is five 16-byte loads");
-    if (n > kMaxEditEntries || (reinterpret_cast<uintptr_t>(list) & 15u))
-        return hipErrorInvalidValue;
-    if (n)
-        hipLaunchKernelGGL(k_apply_impulses, dim3(blocks_for(n)), dim3(kBlock), 0, stream, b, reinterpret_cast<const ulonglong2 *>(list), n);
-    return hipGetLastError();
-}
-
-hipError_t launch_snapshot_positions(const BodyArrays &b, const uint32_t *indices, uint32_t n, double *snapshot, hipStream_t stream)
-{
-    if (n)
-        hipLaunchKernelGGL(k_snapshot_positions, dim3(blocks_for(n)), dim3(kBlock), 0, stream, b, indices, n, snapshot);
-    return hipGetLastError();
-}
-
-hipError_t launch_max_displacement2(const BodyArrays &b, const uint32_t *indices, uint32_t n, const double *snapshot, const double *scale,
-                                    double *out, hipStream_t stream)
-{
-    if (n)
-        hipLaunchKernelGGL(k_max_displacement2, dim3(blocks_for(n)), dim3(kBlock), 0, stream, b, indices, n, snapshot, scale, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_cell_keys(const BodyArrays &b, const uint32_t *indices, uint32_t n, double edge, int64_t *keys, uint32_t *bad, hipStream_t stream)
-{
-    if (n)
-        hipLaunchKernelGGL(k_cell_keys, dim3(blocks_for(n)), dim3(kBlock), 0, stream, b, indices, n, edge, reinterpret_cast<long long *>(keys), bad);
-    return hipGetLastError();
-}
-
-hipError_t launch_gather_records(const BodyArrays &b, const uint32_t *indices, uint32_t n, double *out, hipStream_t stream)
-{
-    if (n)
-        hipLaunchKernelGGL(k_gather_records, dim3(blocks_for(n * (kDynFields + kStatFields + 1))), dim3(kBlock), 0, stream, b, indices, n, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_repack_bodies(const double *old_aos, const uint32_t *old_shape, const int32_t *src, uint32_t n_new, const double *incoming,
-                                double *new_aos, uint32_t *new_shape, hipStream_t stream)
-{
-    if (n_new) {
-        const size_t threads = (size_t)n_new * (kDynFields + kStatFields);
-        hipLaunchKernelGGL(k_repack_bodies, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, old_aos, old_shape, src, n_new,
-                           incoming, new_aos, new_shape);
-    }
     return hipGetLastError();
 }
 

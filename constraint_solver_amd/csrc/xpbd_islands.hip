@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "xpbd_islands.h"
+#include "xpbd_scan.h"
 
 namespace xpbd {
 namespace {

@@ -87,7 +87,7 @@ struct EdgeQuery {
 hipError_t launch_edge_axes_reference(const BodyArrays &b, const PolytopeTables &t, const double *frames, const uint32_t *pairs,
                                       uint32_t n_pairs, EdgeQuery *out, hipStream_t stream);
 
-// (The pipeline's statistics -- touching pairs, contact points -- are summed by the pair solve, xpbd_contacts.hip.)
+// (The pipeline's statistics -- touching pairs, contact points -- are summed by the pair solve, xpbd_contacts.hip: block_add_stats.)
 
 // Device scratch of the two-pass form (pre-test pass + SAT over the survivors).  `counters`: two SETS of
 // kSurvivorCounters uint32 (one counter per pair class), zero when idle; launch k appends through set k & 1 and its

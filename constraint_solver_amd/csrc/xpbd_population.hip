@@ -1,14 +1,14 @@
 // xpbd_population.hip -- gfx950 kernels behind xpbd_world_remove_bodies / _add_bodies (include/xpbd.h, "Body POPULATION").
 //
-// Removal is a stream compaction: flags -> exclusive scan (the contact pipeline's launch_exclusive_scan) -> old_to_new and its
+// Removal is a stream compaction: flags -> exclusive scan (launch_exclusive_scan, xpbd_scan.h) -> old_to_new and its
 // inverse src[new] = old.  The scan makes every write position unique, so there are no atomics and the result does not
 // depend on the schedule.  The gathers then read through src, which is ascending: lane l of a wave writes new body s0 + l of
 // one field -- one 512-byte store per wave and field -- and reads old bodies that are at most as far apart as bodies were
 // removed between them, so the loads of a wave fall into a few adjacent cache lines.  No arithmetic: the kernels move bits.
 #include <hip/hip_runtime.h>
 
-#include "xpbd_contacts.h"
 #include "xpbd_population.h"
+#include "xpbd_scan.h"
 
 namespace xpbd {
 namespace {

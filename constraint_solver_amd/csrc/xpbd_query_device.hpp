@@ -33,7 +33,8 @@
 #include "xpbd_clip.hpp"
 #include "xpbd_query.h"
 #include "xpbd_query_shared.hpp"
-#include "xpbd_contacts.h"
+#include "xpbd_pairs.h"
+#include "xpbd_scan.h"
 #include "xpbd_device.hpp"
 
 namespace xpbd {

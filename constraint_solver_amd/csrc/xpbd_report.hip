@@ -4,7 +4,7 @@
 // Determinism: every order is made by a scan (launch_exclusive_scan) over an order the pair list already has; no atomic
 // decides a position.  The kernels only read what the pipeline wrote, so a report changes no bit of the simulation.
 #include "xpbd_report.h"
-#include "xpbd_contacts.h"
+#include "xpbd_scan.h"
 #include "xpbd_device.hpp"
 
 namespace xpbd {

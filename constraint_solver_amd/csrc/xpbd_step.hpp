@@ -1,6 +1,7 @@
 // xpbd_step.hpp -- the per-body substep of solver::step (reference src/solver.rs:6-16) as device
 // functions, shared by the fused stepper (xpbd_kernels.hip) and the contact pipeline
-// (xpbd_contacts.hip).  All arithmetic keeps the reference's operation order.
+// (xpbd_contacts.hip; the terrain lookup also xpbd_restitution.hip and xpbd_terrain.hip).  All arithmetic keeps the
+// reference's operation order.
 #pragma once
 
 #include "xpbd_device.hpp"

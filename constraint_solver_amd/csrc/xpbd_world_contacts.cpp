@@ -2,6 +2,8 @@
 // the narrowphase schedule, the fused and the unfused substeps, the pieces of a shard's frame split at the halo exchange, and
 // the entry points of the split API.
 #include "xpbd_world.hpp"
+#include "xpbd_body_ops.h"
+#include "xpbd_scan.h"
 
 void NarrowphaseSchedule::choose(unsigned long long touching_now, uint32_t two_classes)
 {

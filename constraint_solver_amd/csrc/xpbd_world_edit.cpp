@@ -7,7 +7,9 @@
 #include <vector>
 
 #include "xpbd_world.hpp"
+#include "xpbd_body_ops.h"
 #include "xpbd_population.h"
+#include "xpbd_scan.h"
 
 // ---- re-planning a shard of the multi-GPU world on the device (xpbd_multi.cpp) ---------------------------------------------
 namespace xpbd {

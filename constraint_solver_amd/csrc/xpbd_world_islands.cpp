@@ -1,6 +1,7 @@
 // xpbd_world_islands.cpp -- contact islands of the single-GPU world: Islands (xpbd_world.hpp) and the island entry points.
 // Semantics: include/xpbd.h, "Contact ISLANDS"; the kernels: xpbd_islands.hip.
 #include "xpbd_world.hpp"
+#include "xpbd_scan.h"
 
 namespace {
 

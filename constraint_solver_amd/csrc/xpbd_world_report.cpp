@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "xpbd_world.hpp"
+#include "xpbd_scan.h"
 
 // This frame's touching pairs -> keys[cur]; their count travels to host[cur].  Enqueued only.
 int ContactReport::compact_keys(const xpbd_world *w)

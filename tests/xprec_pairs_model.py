@@ -9,8 +9,8 @@ Stage S uses tests/xprec_model.py's scalar abstraction, cgmath helpers, integrat
 entries (joint_terms) are read from include/xpbd.h (XPBD_JOINT_*, XPBD_LIMIT_*), the joint prose of xpbd_pairs_oracle.h and
 constraint.rs:6-37, rigid.rs:113-123; they follow neither tests/joint_limit_model.py, the oracle's C nor the kernel.
 Stage 6 (bounce) and the terrain (xprec_model.terrain_lookup, xprec_model.ground) are read from include/xpbd.h's sections
-"RESTITUTION" and "TERRAIN" alone; tests/restitution_model.py, tests/terrain_model.py, xpbd_step.hpp and xpbd_contacts.hip were
-not read for them.
+"RESTITUTION" and "TERRAIN" alone; tests/restitution_model.py, tests/terrain_model.py, xpbd_step.hpp, xpbd_contacts.hip and
+xpbd_restitution.hip were not read for them.
 
 Vectors are arrays (3, k) of model scalars as in xprec_model.py.  Reference lines are jim-ec/constraint_solver src/*.rs.
 """
