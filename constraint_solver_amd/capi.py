@@ -71,6 +71,7 @@ ABI_SYMBOLS = [
     "xpbd_world_islands", "xpbd_world_islands_device",
     "xpbd_world_set_sleeping", "xpbd_world_sleep_state", "xpbd_world_sleep_state_device", "xpbd_world_wake_bodies",
     "xpbd_world_wake_bodies_device",
+    "xpbd_world_joint_states", "xpbd_world_joint_states_device", "xpbd_world_set_drive_targets", "xpbd_world_set_drive_targets_device",
 ]
 
 
@@ -128,6 +129,15 @@ LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST, LIMIT_SLIDE = 0, 1, 2, 3
 JOINT_DRIVE_DTYPE = np.dtype([("joint", "<u4"), ("kind", "<u4"), ("ref_a", "<f8", (3,)), ("ref_b", "<f8", (3,)),
                               ("target", "<f8"), ("compliance", "<f8"), ("max_force", "<f8")])
 DRIVE_ANGLE, DRIVE_ANGULAR_VELOCITY, DRIVE_POSITION, DRIVE_VELOCITY = 0, 1, 2, 3
+# xpbd_joint_state as a numpy record (80 bytes): what World.joint_states reports of one joint; XPBD_JOINT_STATE_* flags
+JOINT_STATE_DTYPE = np.dtype([("separation", "<f8"), ("misalignment", "<f8"), ("angle", "<f8"), ("angle_rate", "<f8"), ("travel", "<f8"),
+                              ("travel_rate", "<f8"), ("swing", "<f8"), ("twist", "<f8"), ("joint", "<u4"), ("kind", "<u4"), ("flags", "<u4"),
+                              ("reserved", "<u4")])
+JOINT_STATE_HAS_ANGLE, JOINT_STATE_HAS_TRAVEL, JOINT_STATE_HAS_SWING, JOINT_STATE_HAS_TWIST = 0x001, 0x002, 0x004, 0x008
+JOINT_STATE_ANGLE_OF_DRIVE = 0x010   # angle, angle_rate use the angular drive's references (else the hinge limit's)
+JOINT_STATE_ANGLE_BELOW, JOINT_STATE_ANGLE_ABOVE, JOINT_STATE_TRAVEL_BELOW, JOINT_STATE_TRAVEL_ABOVE = 0x100, 0x200, 0x400, 0x800
+JOINT_STATE_SWING_ABOVE, JOINT_STATE_TWIST_BELOW, JOINT_STATE_TWIST_ABOVE = 0x1000, 0x2000, 0x4000
+JOINT_STATE_NO_JOINT = 0xFFFFFFFF    # .kind of an index out of range (device variant)
 # xpbd_collision_filter as a numpy record (8 bytes): bodies i, j may touch iff group_i & mask_j and group_j & mask_i
 COLLISION_FILTER_DTYPE = np.dtype([("group", "<u4"), ("mask", "<u4")])
 FILTER_JOINTED = 1                # bodies joined by a joint never collide
@@ -488,6 +498,13 @@ def hip_lib():
             L.xpbd_world_sleep_state_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.xpbd_world_wake_bodies.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
             L.xpbd_world_wake_bodies_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            L.xpbd_world_joint_states.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.xpbd_world_joint_states_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.xpbd_world_set_drive_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_set_drive_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -967,6 +984,41 @@ class World:
 
     def wake_bodies_device(self, dev_indices_ptr, n):
         _check(hip_lib().xpbd_world_wake_bodies_device(self._h, C.c_void_p(dev_indices_ptr or None), n))
+
+    # joint states and drive targets (include/xpbd.h, "Joint STATES and drive TARGETS")
+    def joint_states(self, joints=None):
+        """JOINT_STATE_DTYPE records of the listed joints; None: all of them.  Reads only; waits."""
+        if joints is None:
+            n = self.n_joints
+            out = np.zeros(n, dtype=JOINT_STATE_DTYPE)
+            _check(hip_lib().xpbd_world_joint_states(self._h, None, n, out.ctypes.data if n else None))
+            return out
+        idx = np.ascontiguousarray(joints, dtype=np.uint32)
+        out = np.zeros(idx.size, dtype=JOINT_STATE_DTYPE)
+        if idx.size:
+            _check(hip_lib().xpbd_world_joint_states(self._h, idx.ctypes.data, idx.size, out.ctypes.data))
+        return out
+
+    def joint_states_device(self, dev_joints_ptr, n, dev_out_ptr):
+        """Device arrays (joints: uint32 or None for joints 0..n-1; out: n x 80 bytes, 16-byte aligned); enqueues on the world's
+        stream and returns at once.  An index out of range gives a record with kind = JOINT_STATE_NO_JOINT."""
+        _check(hip_lib().xpbd_world_joint_states_device(self._h, C.c_void_p(dev_joints_ptr or None), n, C.c_void_p(dev_out_ptr or None)))
+
+    def set_drive_targets(self, drives, targets):
+        """Replaces the targets of the listed drives of the last set_joint_drives (strictly ascending indices; None: all of
+        them, one target each) and nothing else of them.  Waits."""
+        tgt = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1)
+        idx = None if drives is None else np.ascontiguousarray(drives, dtype=np.uint32)
+        if idx is not None and idx.size != tgt.size:
+            raise ValueError("set_drive_targets: %d drives but %d targets" % (idx.size, tgt.size))
+        if idx is not None and idx.size == 0:
+            return
+        _check(hip_lib().xpbd_world_set_drive_targets(self._h, None if idx is None else idx.ctypes.data, tgt.ctypes.data if tgt.size else None, tgt.size))
+
+    def set_drive_targets_device(self, dev_drives_ptr, dev_targets_ptr, n):
+        """Device arrays (drives: uint32, strictly ascending, or None for drives 0..n-1; targets: float64); enqueues only.  An
+        entry the host variant would refuse is skipped."""
+        _check(hip_lib().xpbd_world_set_drive_targets_device(self._h, C.c_void_p(dev_drives_ptr or None), C.c_void_p(dev_targets_ptr or None), n))
 
 
 def _report_counts(counts_fn, h):

@@ -259,6 +259,38 @@ int SleepTarget::wake_check(const char *who, const uint32_t *indices, uint32_t n
     return XPBD_OK;
 }
 
+int JointStateTarget::check(const char *who, const uint32_t *joints, uint32_t n, const void *out, bool host) const
+{
+    if (n && !out)
+        return set_error(XPBD_E_INVALID, "%s: NULL out with n = %u", who, n);
+    if (!joints && n != n_joints)
+        return set_error(XPBD_E_INVALID, "%s: joints == NULL names the joints 0..n-1, but n = %u and the world holds %u joints", who, n, n_joints);
+    for (uint32_t k = 0; host && joints && k < n; ++k)
+        if (joints[k] >= n_joints)
+            return set_error(XPBD_E_INVALID, "%s: joints[%u] = %u but the world holds %u joints", who, k, joints[k], n_joints);
+    return XPBD_OK;
+}
+
+int DriveTargets::check(const char *who, const uint32_t *drives, const double *targets, uint32_t n, bool host) const
+{
+    if (n && !targets)
+        return set_error(XPBD_E_INVALID, "%s: NULL targets with n = %u", who, n);
+    if (!drives && n != n_drives)
+        return set_error(XPBD_E_INVALID, "%s: drives == NULL names the drives 0..n-1, but n = %u and the world holds %u drives", who, n, n_drives);
+    for (uint32_t k = 0; host && k < n; ++k) {
+        const uint32_t d = drives ? drives[k] : k;
+        if (d >= n_drives)
+            return set_error(XPBD_E_INVALID, "%s: drives[%u] = %u but the world holds %u drives", who, k, d, n_drives);
+        if (drives && k && drives[k - 1] >= d)
+            return set_error(XPBD_E_INVALID, "%s: drives[%u] = %u does not ascend from drives[%u] = %u", who, k, d, k - 1, drives[k - 1]);
+        if (!std::isfinite(targets[k])) // (xpbd_world_set_joint_drives' target rules)
+            return set_error(XPBD_E_INVALID, "%s: targets[%u] = %g (must be finite)", who, k, targets[k]);
+        if (resident[d].kind == XPBD_DRIVE_ANGLE && !(targets[k] >= -M_PI && targets[k] <= M_PI))
+            return set_error(XPBD_E_INVALID, "%s: targets[%u] = %g for angle drive %u (need -pi <= target <= pi)", who, k, targets[k], d);
+    }
+    return XPBD_OK;
+}
+
 // The flags' part of the scene queries' checks: `known` are the family's own bits.
 int check_query_flags(const char *who, const QueryTarget &t, uint32_t flags, uint32_t known)
 {

@@ -79,4 +79,20 @@ struct SleepTarget {
     int wake_check(const char *who, const uint32_t *indices, uint32_t n) const;
 };
 
+// ... of the joint states and drive targets (include/xpbd.h, "Joint STATES and drive TARGETS"), after the caller has dealt with a
+// NULL world: what the call is made on.  JointStateTarget::check, of xpbd_world_joint_states(_device): a NULL out with n > 0,
+// joints == NULL with n != n_joints, and with `host` (the list is host memory) an index out of range.  DriveTargets::check, of
+// xpbd_world_set_drive_targets(_device) against the resident drives (`resident` is read only with `host`): NULL targets with
+// n > 0, drives == NULL with n != n_drives, and with `host` an index out of range or not above its predecessor, a non-finite
+// target, an ANGLE target outside [-pi, pi].
+struct JointStateTarget {
+    uint32_t n_joints;
+    int check(const char *who, const uint32_t *joints, uint32_t n, const void *out, bool host) const;
+};
+struct DriveTargets {
+    const xpbd_joint_drive *resident;
+    uint32_t n_drives;
+    int check(const char *who, const uint32_t *drives, const double *targets, uint32_t n, bool host) const;
+};
+
 } // namespace xpbd

@@ -123,8 +123,11 @@ ExtraTables build_extra_tables(const std::vector<xpbd_joint> &joints, const std:
         it.joint = l.joint, it.kind = kExtraItemSlideLimit, it.target = l.lower, it.compliance = l.upper;
         t.items[cursor[l.joint]++] = it;
     }
-    for (const xpbd_joint_drive &d : drives)
+    t.drive_item.reserve(drives.size());
+    for (const xpbd_joint_drive &d : drives) {
+        t.drive_item.push_back(cursor[d.joint]);
         std::memcpy(&t.items[cursor[d.joint]++], &d, sizeof d);
+    }
     return t;
 }
 

@@ -50,10 +50,12 @@ static_assert(sizeof(ExtraItem) == 80 && sizeof(ExtraItem) == sizeof(xpbd_joint_
 
 // The table k_joint_extras walks: the joints that have extra entries (sliders, SLIDE limits, drives; ascending), where their
 // two ends sit in the bodies' joint lists (the CSR above), and per joint its SLIDE limit followed by its drives in the
-// caller's order.  list.empty(): no extras.
+// caller's order.  list.empty(): no extras.  drive_item: per drive, in the caller's order, its index in `items` (what
+// xpbd_world_set_drive_targets edits in place).
 struct ExtraTables {
     std::vector<uint32_t> list, slots, off;
     std::vector<ExtraItem> items; // at least one element when !list.empty()
+    std::vector<uint32_t> drive_item; // [drives.size()]
 };
 ExtraTables build_extra_tables(const std::vector<xpbd_joint> &joints, const std::vector<xpbd_joint_limit> &slide_limits,
                                const std::vector<xpbd_joint_drive> &drives, uint32_t n_bodies);

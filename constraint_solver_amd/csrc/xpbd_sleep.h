@@ -8,6 +8,7 @@
 #pragma once
 
 #include "xpbd_contacts.h"
+#include "xpbd_joint_state.h"
 
 namespace xpbd {
 
@@ -50,6 +51,10 @@ hipError_t launch_sleep_islands(const SleepState &s, double *dyn, const uint32_t
 // Wake requests from an index list: entry k names body indices[k * every] (indices == NULL: body k).  A sleeper's group is
 // marked, a fixed body (from `stat`) sets kSleepWakeAll, an index outside the world is skipped.
 hipError_t launch_sleep_request(const SleepState &s, const double *stat, const uint32_t *indices, uint32_t every, uint32_t n, hipStream_t stream);
+// Wake requests of a retarget list (xpbd_world_set_drive_targets; DriveTable and the entry rules: xpbd_joint_state.h): for every
+// entry the call accepts, the groups of the asleep ends of its drive's joint are marked.
+hipError_t launch_sleep_request_drives(const SleepState &s, const DriveTable &t, const Joint *joints, uint32_t n_joints, const uint32_t *drives,
+                                       const double *targets, uint32_t n, hipStream_t stream);
 // ctrl[SC_ASLEEP], ctrl[SC_GROUPS] from the state as it stands.
 hipError_t launch_sleep_tally(const SleepState &s, hipStream_t stream);
 

@@ -208,6 +208,32 @@ __global__ void __launch_bounds__(kBlock) k_sleep_request(SleepState s, const do
         atomicOr(&s.mark[g], 1u);
 }
 
+// One lane per entry of a retarget list (xpbd_world_set_drive_targets): the asleep ends of a valid entry's joint have their
+// groups marked.  A fixed end is never asleep and its anchor did not move: it requests nothing.
+__global__ void __launch_bounds__(kBlock) k_sleep_request_drives(SleepState s, DriveTable t, const Joint *__restrict__ joints, uint32_t n_joints,
+                                                                 const uint32_t *__restrict__ drives, const double *__restrict__ targets, uint32_t n)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n)
+        return;
+    uint32_t drive;
+    if (!drive_entry_valid(t, drives, targets, k, drive))
+        return;
+    const uint32_t joint = t.items[t.drive_item[drive]].joint;
+    if (joint >= n_joints)
+        return; // (never: the items come from the world's own tables)
+    const uint32_t ends[2] = {joints[joint].body_a, joints[joint].body_b};
+#pragma unroll
+    for (uint32_t e = 0; e < 2; ++e) {
+        const uint32_t i = ends[e];
+        if (i >= s.n || !s.asleep[i])
+            continue;
+        const uint32_t g = s.group[i];
+        if (g < s.n)
+            atomicOr(&s.mark[g], 1u);
+    }
+}
+
 __global__ void __launch_bounds__(kBlock) k_sleep_tally(SleepState s)
 {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -275,6 +301,15 @@ hipError_t launch_sleep_request(const SleepState &s, const double *stat, const u
     if (s.n == 0 || n == 0)
         return hipSuccess;
     hipLaunchKernelGGL(k_sleep_request, dim3(blocks_of(n)), dim3(kBlock), 0, stream, s, stat, indices, every, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_sleep_request_drives(const SleepState &s, const DriveTable &t, const Joint *joints, uint32_t n_joints, const uint32_t *drives,
+                                       const double *targets, uint32_t n, hipStream_t stream)
+{
+    if (s.n == 0 || n == 0 || t.n_drives == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_sleep_request_drives, dim3(blocks_of(n)), dim3(kBlock), 0, stream, s, t, joints, n_joints, drives, targets, n);
     return hipGetLastError();
 }
 

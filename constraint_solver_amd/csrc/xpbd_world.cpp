@@ -158,6 +158,14 @@ int stage_extras(const xpbd::ExtraTables &t, uint32_t n_joints, hipStream_t stre
     XPBD_TRY(stage_upload(out.slots, t.slots.data(), t.slots.size() * 4));
     XPBD_TRY(stage_upload(out.off, t.off.data(), t.off.size() * 4));
     XPBD_TRY(stage_upload(out.items, t.items.data(), t.items.size() * sizeof(xpbd::ExtraItem)));
+    // what the joint states and the drive targets look a joint's / a drive's items up by
+    std::vector<uint32_t> joint_slot(n_joints, xpbd::kNoExtraSlot);
+    for (size_t k = 0; k < t.list.size(); ++k)
+        joint_slot[t.list[k]] = (uint32_t)k;
+    XPBD_TRY(stage_upload(out.joint_slot, joint_slot.data(), joint_slot.size() * 4));
+    if (!t.drive_item.empty())
+        XPBD_TRY(stage_upload(out.drive_item, t.drive_item.data(), t.drive_item.size() * 4));
+    out.drive_item_host = t.drive_item;
     out.n_extra_joints = (uint32_t)t.list.size();
     return XPBD_OK;
 }
@@ -678,8 +686,10 @@ try {
     XPBD_TRY(stage_limits(lt, fresh));
     const bool slide_changes = !lt.slide.empty() || !J.slide_limits.empty();
     JointTables::Extras extras;
-    if (slide_changes)
+    if (slide_changes) { // the extras are re-staged from the host copy: targets set on the device come back first
+        XPBD_TRY(sync_drive_targets(w));
         XPBD_TRY(stage_extras(xpbd::build_extra_tables(J.set.joints, lt.slide, J.set.drives, w->n), J.csr.n, w->stream, extras));
+    }
     J.set.limits = std::move(all);
     J.slide_limits = std::move(lt.slide);
     J.limits = std::move(fresh);
@@ -706,7 +716,7 @@ try {
     JointTables::Extras fresh;
     XPBD_TRY(stage_extras(xpbd::build_extra_tables(J.set.joints, J.slide_limits, all, w->n), J.csr.n, w->stream, fresh));
     J.set.drives = std::move(all);
-    J.extras = std::move(fresh);
+    J.extras = std::move(fresh); // (with targets_on_device clear: the drives are replaced)
     return XPBD_OK;
 } XPBD_ABI_CATCH
 

@@ -9,6 +9,7 @@
 //   xpbd_world_edit.cpp      body edits, population changes, re-packing a shard
 //   xpbd_world_islands.cpp   Islands and the island entry points
 //   xpbd_world_sleep.cpp     Sleep and the sleeping entry points
+//   xpbd_world_joint_state.cpp  joint states and drive targets: the entry points, and the way back of device-set targets
 #pragma once
 
 #include <cstdint>
@@ -23,6 +24,7 @@
 #include "xpbd_contacts.h"
 #include "xpbd_gjk.h"
 #include "xpbd_islands.h"
+#include "xpbd_joint_state.h"
 #include "xpbd_pairs.h"
 #include "xpbd_population_remap.hpp"
 #include "xpbd_query.h"
@@ -67,6 +69,13 @@ struct JointTables {
     struct Extras { // the lanes of k_joint_extras: the joints with extra entries (sliders, SLIDE limits, drives), the per-end sums
         uint32_t n_extra_joints = 0;
         DeviceBuffer sums, joints, slots, off, items;
+        // for the joint states and drive targets: joint -> its lane here (xpbd::kNoExtraSlot: none), drive -> its item, and that
+        // map on the host.  targets_on_device: xpbd_world_set_drive_targets_device has written targets that set.drives does
+        // not hold yet (sync_drive_targets brings them back before anything re-stages this part from the host copy; a fresh
+        // part starts clean, which is how the setters that replace the drives clear it)
+        DeviceBuffer joint_slot, drive_item;
+        std::vector<uint32_t> drive_item_host;
+        bool targets_on_device = false;
     } extras;
 
     void fill(xpbd::ContactBuffers &c) const // (an empty part holds no buffer: NULL)
@@ -82,6 +91,15 @@ struct JointTables {
         c.extra_off = extras.off.as<uint32_t>();
         c.extra_items = extras.items.as<xpbd::JointExtraItem>();
         c.n_extra_joints = extras.n_extra_joints;
+    }
+    xpbd::JointStateTables state_tables() const
+    {
+        return xpbd::JointStateTables{csr.joints.as<xpbd::Joint>(), csr.n, limits.limits.as<xpbd::JointLimit>(), limits.limit_off.as<uint32_t>(),
+                                      extras.joint_slot.as<uint32_t>(), extras.off.as<uint32_t>(), extras.items.as<xpbd::JointExtraItem>()};
+    }
+    xpbd::DriveTable drive_table() const
+    {
+        return xpbd::DriveTable{extras.items.as<xpbd::JointExtraItem>(), extras.drive_item.as<uint32_t>(), (uint32_t)extras.drive_item_host.size()};
     }
     void clear() { *this = JointTables{}; }
 };
@@ -293,6 +311,8 @@ struct Sleep {
     int frame_end(xpbd_world *w);                                          // after the last substep: the sleep pass
     // wake requests of an edit: entry k names body dev_indices[k * every] (NULL: body k)
     int request(xpbd_world *w, const uint32_t *dev_indices, uint32_t every, uint32_t n);
+    // wake requests of a retarget list (xpbd_world_set_drive_targets): the asleep ends of the joints of its valid entries
+    int request_drives(xpbd_world *w, const uint32_t *dev_drives, const double *dev_targets, uint32_t n);
 };
 
 #pragma GCC visibility pop
@@ -498,6 +518,10 @@ int adopt_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id);
 int stage_upload(DeviceBuffer &fresh, const void *values, size_t bytes);
 int upload_table(DeviceBuffer &table, const void *values, size_t bytes);
 int stage_joint_tables(xpbd::JointSet set, uint32_t n_bodies, hipStream_t stream, JointTables &out);
+
+// ---- xpbd_world_joint_state.cpp ---------------------------------------------------------------------------------------------
+// Targets set on the device go back into joints.set.drives (no-op unless extras.targets_on_device).  Device bound, stream idle.
+int sync_drive_targets(xpbd_world *w);
 
 // ---- xpbd_world_contacts.cpp ------------------------------------------------------------------------------------------------
 int build_neighbours_enqueue(xpbd_world *w, double dt);

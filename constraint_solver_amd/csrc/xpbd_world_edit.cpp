@@ -401,6 +401,7 @@ int remove_bodies(xpbd_world *w, const uint8_t *dev_remove, const uint32_t *indi
             joint_map[j] = j;
     } else {
         PopulationStage st;
+        XPBD_TRY(sync_drive_targets(w)); // the joint tables are re-staged from the host copy
         if (w->joints.csr.n)
             XPBD_TRY(stage_joint_tables(xpbd::remap_joint_set(w->joints.set, map.data(), n, joint_map), n_keep, w->stream, st.joints));
         XPBD_TRY(stage_bodies(w, w->pop.src.as<uint32_t>(), n_keep, nullptr, nullptr, 0, st));
@@ -483,6 +484,7 @@ try {
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the old arrays are freed at the end
     const uint32_t first = w->n;
     PopulationStage st;
+    XPBD_TRY(sync_drive_targets(w)); // the joint tables are re-staged from the host copy
     if (w->joints.csr.n) // the same joints in a world of more bodies: the CSR body -> joints grows
         XPBD_TRY(stage_joint_tables(w->joints.set, first + n_add, w->stream, st.joints));
     XPBD_TRY(stage_bodies(w, nullptr, first, aos, shape_id, n_add, st));

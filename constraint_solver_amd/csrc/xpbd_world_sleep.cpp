@@ -74,6 +74,14 @@ int Sleep::request(xpbd_world *w, const uint32_t *dev_indices, uint32_t every, u
     return XPBD_OK;
 }
 
+int Sleep::request_drives(xpbd_world *w, const uint32_t *dev_drives, const double *dev_targets, uint32_t n)
+{
+    XPBD_TRY(ensure(w));
+    XPBD_HIP_TRY(xpbd::launch_sleep_request_drives(view(w), w->joints.drive_table(), w->joints.csr.joints.as<xpbd::Joint>(), w->joints.csr.n, dev_drives,
+                                                   dev_targets, n, w->stream));
+    return XPBD_OK;
+}
+
 extern "C" {
 
 int xpbd_world_set_sleeping(xpbd_world *w, const xpbd_sleep_config *cfg)

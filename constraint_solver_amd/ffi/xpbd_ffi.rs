@@ -110,6 +110,38 @@ pub struct XpbdJointDrive {
     pub max_force: f64,   // > 0, +inf allowed
 }
 
+/// EXTENSION: xpbd_joint_state (80 bytes): what xpbd_world_joint_states reports of one joint (see xpbd.h, "Joint STATES and
+/// drive TARGETS"); a field whose XPBD_JOINT_STATE_HAS_* flag is clear is +0.0.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct XpbdJointState {
+    pub separation: f64,   // DISTANCE, HINGE: |d| - distance; SLIDER: |d - a_w s|
+    pub misalignment: f64, // HINGE, SLIDER: |a_w x b_w|
+    pub angle: f64,        // rad, in [-pi, pi]
+    pub angle_rate: f64,   // rad/s
+    pub travel: f64,       // SLIDER: m
+    pub travel_rate: f64,  // m/s
+    pub swing: f64,        // DISTANCE with a SWING or TWIST limit: rad
+    pub twist: f64,        // DISTANCE with a TWIST limit: rad
+    pub joint: u32,
+    pub kind: u32,         // XPBD_JOINT_*; XPBD_JOINT_STATE_NO_JOINT: the index was out of range (device variant)
+    pub flags: u32,        // XPBD_JOINT_STATE_*
+    pub reserved: u32,
+}
+pub const XPBD_JOINT_STATE_HAS_ANGLE: u32 = 0x001;
+pub const XPBD_JOINT_STATE_HAS_TRAVEL: u32 = 0x002;
+pub const XPBD_JOINT_STATE_HAS_SWING: u32 = 0x004;
+pub const XPBD_JOINT_STATE_HAS_TWIST: u32 = 0x008;
+pub const XPBD_JOINT_STATE_ANGLE_OF_DRIVE: u32 = 0x010;
+pub const XPBD_JOINT_STATE_ANGLE_BELOW: u32 = 0x100;
+pub const XPBD_JOINT_STATE_ANGLE_ABOVE: u32 = 0x200;
+pub const XPBD_JOINT_STATE_TRAVEL_BELOW: u32 = 0x400;
+pub const XPBD_JOINT_STATE_TRAVEL_ABOVE: u32 = 0x800;
+pub const XPBD_JOINT_STATE_SWING_ABOVE: u32 = 0x1000;
+pub const XPBD_JOINT_STATE_TWIST_BELOW: u32 = 0x2000;
+pub const XPBD_JOINT_STATE_TWIST_ABOVE: u32 = 0x4000;
+pub const XPBD_JOINT_STATE_NO_JOINT: u32 = 0xFFFF_FFFF;
+
 /// EXTENSION: limit of a joint (XPBD_LIMIT_HINGE = 0, XPBD_LIMIT_SWING = 1, XPBD_LIMIT_TWIST = 2: angular, radians;
 /// XPBD_LIMIT_SLIDE = 3: the travel of a slider, metres; see xpbd.h).
 #[repr(C)]
@@ -590,6 +622,11 @@ extern "C" {
                                          dev_counts: *mut u32) -> c_int;
     pub fn xpbd_world_wake_bodies(w: *mut XpbdWorld, indices: *const u32, n: u32) -> c_int;
     pub fn xpbd_world_wake_bodies_device(w: *mut XpbdWorld, dev_indices: *const u32, n: u32) -> c_int;
+    // joint states and drive targets (include/xpbd.h, "Joint STATES and drive TARGETS"); a NULL list names all joints / drives
+    pub fn xpbd_world_joint_states(w: *mut XpbdWorld, joints: *const u32, n: u32, out: *mut XpbdJointState) -> c_int;
+    pub fn xpbd_world_joint_states_device(w: *mut XpbdWorld, dev_joints: *const u32, n: u32, dev_out: *mut XpbdJointState) -> c_int;
+    pub fn xpbd_world_set_drive_targets(w: *mut XpbdWorld, drives: *const u32, targets: *const f64, n: u32) -> c_int;
+    pub fn xpbd_world_set_drive_targets_device(w: *mut XpbdWorld, dev_drives: *const u32, dev_targets: *const f64, n: u32) -> c_int;
     pub fn xpbd_multi_world_set_contact_report(mw: *mut XpbdMultiWorld, enable: u32) -> c_int;
     pub fn xpbd_multi_world_contact_report_counts(mw: *mut XpbdMultiWorld, out: *mut u32) -> c_int;
     pub fn xpbd_multi_world_download_pair_contacts(mw: *mut XpbdMultiWorld, pairs: *mut XpbdPairContact, pair_cap: u32,

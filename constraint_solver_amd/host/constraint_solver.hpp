@@ -662,6 +662,36 @@ class BatchWorld {
             check(xpbd_world_wake_bodies(w_, indices.data(), (uint32_t)indices.size()));
     }
     void wake_all() { check(xpbd_world_wake_bodies(w_, nullptr, 0)); }
+    // joint states and drive targets (include/xpbd.h, "Joint STATES and drive TARGETS"): an encoder on every joint, and the
+    // targets of resident drives replaced in place (`drives` ascending; empty: all of them, one target each)
+    std::vector<xpbd_joint_state> joint_states(uint32_t n_joints)
+    {
+        std::vector<xpbd_joint_state> out(n_joints);
+        check(xpbd_world_joint_states(w_, nullptr, n_joints, out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    std::vector<xpbd_joint_state> joint_states(const std::vector<uint32_t> &joints)
+    {
+        std::vector<xpbd_joint_state> out(joints.size());
+        if (!joints.empty()) // (NULL with n == 0 is "all joints" of a world without any)
+            check(xpbd_world_joint_states(w_, joints.data(), (uint32_t)joints.size(), out.data()));
+        return out;
+    }
+    void joint_states_device(const uint32_t *dev_joints, uint32_t n, xpbd_joint_state *dev_out)
+    {
+        check(xpbd_world_joint_states_device(w_, dev_joints, n, dev_out));
+    }
+    void set_drive_targets(const std::vector<uint32_t> &drives, const std::vector<double> &targets)
+    {
+        if (!drives.empty() && drives.size() != targets.size())
+            throw std::invalid_argument("set_drive_targets: one target per listed drive");
+        if (!targets.empty())
+            check(xpbd_world_set_drive_targets(w_, drives.empty() ? nullptr : drives.data(), targets.data(), (uint32_t)targets.size()));
+    }
+    void set_drive_targets_device(const uint32_t *dev_drives, const double *dev_targets, uint32_t n)
+    {
+        check(xpbd_world_set_drive_targets_device(w_, dev_drives, dev_targets, n));
+    }
 
     std::vector<xpbd_contact> contacts()
     {

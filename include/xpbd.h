@@ -386,6 +386,70 @@ typedef struct xpbd_joint_drive {
 } xpbd_joint_drive;          /* 80 bytes */
 int  xpbd_world_set_joint_drives(xpbd_world *w, const xpbd_joint_drive *drives, uint32_t n_drives);
 
+/* Joint STATES and drive TARGETS (EXTENSION): an encoder on every joint, and a control input that stays on the device.
+ *
+ * xpbd_world_joint_states evaluates, for the listed joints (joints == NULL: all of them, n = the joint count), the quantities
+ * the joint pass works with, at the poses xpbd_world_download_bodies would return at that point of the world's stream.  The
+ * symbols are those of the sections above: p_a, p_b the world anchors, d = p_b - p_a, a_w = q_a * axis_a, b_w = q_b * axis_b,
+ * s = d . a_w; the velocity of a point p of a body is v_p = velocity + angular_velocity x (p - (position + center_of_mass)),
+ * angular_velocity (omega) in world space, as derive leaves it.  Every expression is the solver's own, in its order, so a bound
+ * that the report calls violated is one the next substep would act on at these poses.
+ *   angle, angle_rate  HINGE and SLIDER joints that have references: those of the joint's angular drive if it has one
+ *                      (XPBD_JOINT_STATE_ANGLE_OF_DRIVE), otherwise those of its XPBD_LIMIT_HINGE; with neither the angle is
+ *                      not available.  The idiom for a free hinge: an XPBD_LIMIT_HINGE of [-pi, pi] never binds, leaves the
+ *                      step bit for bit unchanged, and gives the hinge an encoder.  The angle is in [-pi, pi]; turns are not counted.
+ *   flags              which fields are available (a field that is not is +0.0 with its flag clear), and the status of the
+ *                      joint's limits by the very comparisons the solver uses (phi < lower, phi > upper; s likewise),
+ *                      always with the limit's own references, even where `angle` is reported with the drive's.
+ * The call reads only and wakes nobody; it is accepted in every mode, and a world without joints accepts n == 0.
+ * The host variant waits.  XPBD_E_INVALID, with nothing written: a NULL world, a NULL out with n > 0, joints == NULL with n
+ * other than the joint count, an index out of range.  The device variant enqueues on the world's stream and waits for nothing
+ * (dev_out: 16-byte aligned); for an index out of range it writes a record with kind = 0xFFFFFFFF and everything else zero.
+ *
+ * xpbd_world_set_drive_targets replaces the `target` of resident drives and nothing else: kind, references, compliance and
+ * max_force stay, and the next substep that runs sees the new target exactly as if xpbd_world_set_joint_drives had been given
+ * the whole table with it.  drives[k] indexes the list of the last xpbd_world_set_joint_drives (NULL: all of them, n = the
+ * drive count); the indices must be strictly ascending.  The host variant applies that call's target rules and waits:
+ * XPBD_E_INVALID, with nothing changed, for a NULL world, NULL targets with n > 0, drives == NULL with n other than the drive
+ * count, an index out of range or not above its predecessor, a non-finite target, an ANGLE target outside [-pi, pi].  The
+ * device variant only enqueues; an entry that breaks one of those rules is skipped (entry k is compared with dev_drives[k - 1]
+ * whether or not that one was valid, so which entries count does not depend on the schedule; a list that names a drive again
+ * after a descent can leave two valid entries for it, and which of their targets it keeps is then unspecified).
+ * With sleeping on, both variants request a wake for the groups of the asleep ends of the named drives' joints, as an edit of
+ * those bodies would; a fixed end requests nothing (the anchor did not move) and nobody else wakes --
+ * xpbd_world_set_joint_drives wakes every body.  xpbd_world_set_joint_limits and the population changes keep the targets set
+ * here.  History push and restore do not carry targets, as they do not carry drives.
+ * Not here: the multi-GPU world; editing compliance or max_force in place; multi-turn angle counting; joint reactions (the
+ * impulse a joint applies differs at its two ends under the Jacobi averaging, and is not reported). */
+#define XPBD_JOINT_STATE_HAS_ANGLE       0x001u
+#define XPBD_JOINT_STATE_HAS_TRAVEL      0x002u
+#define XPBD_JOINT_STATE_HAS_SWING       0x004u
+#define XPBD_JOINT_STATE_HAS_TWIST       0x008u
+#define XPBD_JOINT_STATE_ANGLE_OF_DRIVE  0x010u  /* angle, angle_rate use the angular drive's references */
+#define XPBD_JOINT_STATE_ANGLE_BELOW     0x100u  /* XPBD_LIMIT_HINGE: phi < lower */
+#define XPBD_JOINT_STATE_ANGLE_ABOVE     0x200u  /*                   phi > upper */
+#define XPBD_JOINT_STATE_TRAVEL_BELOW    0x400u  /* XPBD_LIMIT_SLIDE: s < lower */
+#define XPBD_JOINT_STATE_TRAVEL_ABOVE    0x800u  /*                   s > upper */
+#define XPBD_JOINT_STATE_SWING_ABOVE     0x1000u /* XPBD_LIMIT_SWING: phi > upper */
+#define XPBD_JOINT_STATE_TWIST_BELOW     0x2000u /* XPBD_LIMIT_TWIST: phi < lower */
+#define XPBD_JOINT_STATE_TWIST_ABOVE     0x4000u /*                   phi > upper */
+#define XPBD_JOINT_STATE_NO_JOINT        0xFFFFFFFFu /* xpbd_joint_state.kind of an index out of range (device variant) */
+typedef struct xpbd_joint_state {   /* 80 bytes */
+    double   separation;    /* DISTANCE, HINGE: |d| - distance, the positional term's error.  SLIDER: |d - a_w s|, the perpendicular term's len */
+    double   misalignment;  /* HINGE, SLIDER: |a_w x b_w|, the angular term's mag.  DISTANCE: +0.0 */
+    double   angle;         /* HINGE, SLIDER with references (above): phi of XPBD_LIMIT_HINGE, in [-pi, pi] */
+    double   angle_rate;    /* same joints: (omega_b - omega_a) . a_w, rad/s */
+    double   travel;        /* SLIDER: s = d . a_w, metres */
+    double   travel_rate;   /* SLIDER: (v_pb - v_pa) . a_w + d . (omega_a x a_w), m/s */
+    double   swing;         /* DISTANCE with a SWING or TWIST limit: phi of XPBD_LIMIT_SWING */
+    double   twist;         /* DISTANCE with a TWIST limit: phi of XPBD_LIMIT_TWIST (|a_w + b_w| = 0: not available) */
+    uint32_t joint, kind, flags, reserved;
+} xpbd_joint_state;
+int  xpbd_world_joint_states(xpbd_world *w, const uint32_t *joints /* NULL: all, n = joint count */, uint32_t n, xpbd_joint_state *out);
+int  xpbd_world_joint_states_device(xpbd_world *w, const uint32_t *dev_joints /* NULL: all */, uint32_t n, xpbd_joint_state *dev_out);
+int  xpbd_world_set_drive_targets(xpbd_world *w, const uint32_t *drives /* NULL: all, n = drive count */, const double *targets, uint32_t n);
+int  xpbd_world_set_drive_targets_device(xpbd_world *w, const uint32_t *dev_drives /* NULL: all */, const double *dev_targets, uint32_t n);
+
 /* Collision FILTERS (EXTENSION): which body-body pairs may touch.
  * Pair rule: bodies i and j may touch iff (group_i & mask_j) != 0 && (group_j & mask_i) != 0; with XPBD_FILTER_JOINTED
  * they also may not touch when any joint of the world's current joint list connects them.  The rule is symmetric.
