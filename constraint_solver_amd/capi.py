@@ -72,7 +72,26 @@ ABI_SYMBOLS = [
     "xpbd_world_set_sleeping", "xpbd_world_sleep_state", "xpbd_world_sleep_state_device", "xpbd_world_wake_bodies",
     "xpbd_world_wake_bodies_device",
     "xpbd_world_joint_states", "xpbd_world_joint_states_device", "xpbd_world_set_drive_targets", "xpbd_world_set_drive_targets_device",
+    "xpbd_world_set_kinematics", "xpbd_world_set_kinematic_targets", "xpbd_world_set_kinematic_targets_device", "xpbd_world_kinematic_count",
 ]
+
+# kinematic bodies (include/xpbd.h, "KINEMATIC bodies"): xpbd_kinematic, 64 bytes
+KINEMATIC_POSE, KINEMATIC_VELOCITY = 0, 1
+KINEMATIC_DTYPE = np.dtype([("body", np.uint32), ("mode", np.uint32), ("linear", np.float64, 3), ("angular", np.float64, 4)])
+
+
+def kinematics(body, mode, linear, angular):
+    """KINEMATIC_DTYPE records: POSE entries take a target position and rotation (s, x, y, z), VELOCITY entries a velocity and
+    an angular velocity (three components; a fourth is ignored)."""
+    body = np.atleast_1d(np.asarray(body, dtype=np.uint32))
+    out = np.zeros(body.size, dtype=KINEMATIC_DTYPE)
+    out["body"] = body
+    out["mode"] = mode
+    out["linear"] = np.asarray(linear, dtype=np.float64).reshape(-1, 3)
+    ang = np.asarray(angular, dtype=np.float64)
+    ang = ang.reshape(-1, ang.shape[-1])
+    out["angular"][:, :ang.shape[1]] = ang
+    return out
 
 
 class XpbdError(RuntimeError):
@@ -505,6 +524,14 @@ def hip_lib():
             L.xpbd_world_joint_states_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
             L.xpbd_world_set_drive_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
             L.xpbd_world_set_drive_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            L.xpbd_world_set_kinematics.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_set_kinematic_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_set_kinematic_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_kinematic_count.argtypes = [C.c_void_p]
+            L.xpbd_world_kinematic_count.restype = C.c_uint32
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -1019,6 +1046,45 @@ class World:
         """Device arrays (drives: uint32, strictly ascending, or None for drives 0..n-1; targets: float64); enqueues only.  An
         entry the host variant would refuse is skipped."""
         _check(hip_lib().xpbd_world_set_drive_targets_device(self._h, C.c_void_p(dev_drives_ptr or None), C.c_void_p(dev_targets_ptr or None), n))
+
+    # kinematic bodies (include/xpbd.h, "KINEMATIC bodies")
+    def set_kinematics(self, table):
+        """Replaces the kinematic table: KINEMATIC_DTYPE records (see kinematics()), bodies strictly ascending and fixed; None or
+        an empty table clears it.  May wait."""
+        t = np.zeros(0, dtype=KINEMATIC_DTYPE) if table is None else np.ascontiguousarray(table, dtype=KINEMATIC_DTYPE)
+        _check(hip_lib().xpbd_world_set_kinematics(self._h, t.ctypes.data if t.size else None, t.size))
+
+    def set_kinematic_targets(self, entries, rows):
+        """Replaces linear and angular (rows of seven doubles) of the listed entries of the last set_kinematics (strictly
+        ascending indices; None: all of them) and leaves body and mode.  Waits; wakes nobody."""
+        r = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 7)
+        idx = None if entries is None else np.ascontiguousarray(entries, dtype=np.uint32)
+        if idx is not None and idx.size != r.shape[0]:
+            raise ValueError("set_kinematic_targets: %d entries but %d rows" % (idx.size, r.shape[0]))
+        if idx is not None and idx.size == 0:
+            return
+        _check(hip_lib().xpbd_world_set_kinematic_targets(self._h, None if idx is None else idx.ctypes.data, r.ctypes.data if r.size else None, r.shape[0]))
+
+    def set_kinematic_targets_device(self, dev_entries_ptr, dev_rows_ptr, n):
+        """Device arrays (entries: uint32, strictly ascending, or None for entries 0..n-1; rows: n x 7 float64); enqueues only.
+        An entry the host variant would refuse is skipped."""
+        _check(hip_lib().xpbd_world_set_kinematic_targets_device(self._h, C.c_void_p(dev_entries_ptr or None), C.c_void_p(dev_rows_ptr or None), n))
+
+    def frame_neighbours(self):
+        """(offsets[n+1], neighbours) CSR of the neighbour lists the last step's broadphase built: the frame's pair list, seen
+        from both ends.  Downloads only (neighbours() runs a broadphase of its own)."""
+        off = np.zeros(self.n + 1, dtype=np.uint32)
+        cap = max(64, 16 * self.n)
+        while True:
+            nb = np.zeros(cap, dtype=np.uint32)
+            rc = hip_lib().xpbd_world_download_neighbours(self._h, _u32(off), _u32(nb), cap)
+            if rc != E_CAPACITY:
+                _check(rc)
+                return off, nb[:off[-1]]
+            cap *= 4
+
+    def kinematic_count(self):
+        return int(hip_lib().xpbd_world_kinematic_count(self._h))
 
 
 def _report_counts(counts_fn, h):

@@ -1,6 +1,7 @@
 // xpbd_checks.cpp -- the argument checks of the C ABI that need no device, shared by the single and the multi-GPU world.
 // Host-only: no HIP header, builds with plain g++ (as xpbd_population_remap.cpp).
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -287,6 +288,74 @@ int DriveTargets::check(const char *who, const uint32_t *drives, const double *t
             return set_error(XPBD_E_INVALID, "%s: targets[%u] = %g (must be finite)", who, k, targets[k]);
         if (resident[d].kind == XPBD_DRIVE_ANGLE && !(targets[k] >= -M_PI && targets[k] <= M_PI))
             return set_error(XPBD_E_INVALID, "%s: targets[%u] = %g for angle drive %u (need -pi <= target <= pi)", who, k, targets[k], d);
+    }
+    return XPBD_OK;
+}
+
+namespace {
+// The value rules of a kinematic entry: `row` is linear[3] followed by angular[4].
+int check_kinematic_row(const char *who, const char *what, uint32_t k, uint32_t mode, const double *row)
+{
+    for (uint32_t c = 0; c < 7; ++c)
+        if (!std::isfinite(row[c]))
+            return set_error(XPBD_E_INVALID, "%s: %s[%u] has %s[%u] = %g (must be finite)", who, what, k, c < 3 ? "linear" : "angular", c < 3 ? c : c - 3,
+                             row[c]);
+    if (mode == XPBD_KINEMATIC_POSE && row[3] == 0.0 && row[4] == 0.0 && row[5] == 0.0 && row[6] == 0.0)
+        return set_error(XPBD_E_INVALID, "%s: %s[%u] has an all-zero target rotation", who, what, k);
+    return XPBD_OK;
+}
+} // namespace
+
+int KinematicTarget::check(const char *who, const xpbd_kinematic *list, uint32_t n) const
+{
+    static_assert(sizeof(xpbd_kinematic) == 64 && offsetof(xpbd_kinematic, linear) == 8 && offsetof(xpbd_kinematic, angular) == 32,
+                  "xpbd_kinematic is {body, mode, linear[3], angular[4]}: seven consecutive doubles");
+    if (n && !list)
+        return set_error(XPBD_E_INVALID, "%s: NULL list with n = %u", who, n);
+    if (n && n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    for (uint32_t k = 0; k < n; ++k) {
+        const xpbd_kinematic &e = list[k];
+        if (e.body >= n_bodies)
+            return set_error(XPBD_E_INVALID, "%s: list[%u].body = %u but the world holds %u bodies", who, k, e.body, n_bodies);
+        if (k && list[k - 1].body >= e.body)
+            return set_error(XPBD_E_INVALID, "%s: list[%u].body = %u does not ascend from list[%u].body = %u", who, k, e.body, k - 1, list[k - 1].body);
+        if (e.mode != XPBD_KINEMATIC_POSE && e.mode != XPBD_KINEMATIC_VELOCITY)
+            return set_error(XPBD_E_INVALID, "%s: list[%u] has unknown mode %u", who, k, e.mode);
+        if (int rc = check_kinematic_row(who, "list", k, e.mode, e.linear))
+            return rc;
+    }
+    return XPBD_OK;
+}
+
+int KinematicTarget::fixed_check(const char *who, const xpbd_kinematic *list, uint32_t n, const double *mass) const
+{
+    for (uint32_t k = 0; k < n; ++k)
+        for (uint32_t f = 0; f < 10; ++f)
+            if (!(mass[(size_t)k * 10 + f] == 0.0))
+                return set_error(XPBD_E_INVALID, "%s: list[%u].body = %u is not fixed (%s = %g; a kinematic body has zero inverse mass and inertia)", who, k,
+                                 list[k].body, f ? "an inverse_inertia entry" : "inverse_mass", mass[(size_t)k * 10 + f]);
+    return XPBD_OK;
+}
+
+int KinematicTargets::check(const char *who, const uint32_t *entries, const double *rows, uint32_t n, bool host) const
+{
+    if (n && !rows)
+        return set_error(XPBD_E_INVALID, "%s: NULL rows with n = %u", who, n);
+    if (!entries && n != n_entries)
+        return set_error(XPBD_E_INVALID, "%s: entries == NULL names the entries 0..n-1, but n = %u and the table holds %u entries", who, n, n_entries);
+    if (!host && n > (1u << 29))
+        return set_error(XPBD_E_INVALID, "%s: n = %u (at most 2^29 entries)", who, n);
+    if (!host && (reinterpret_cast<uintptr_t>(rows) & 7u))
+        return set_error(XPBD_E_INVALID, "%s: dev_rows is not 8-byte aligned", who);
+    for (uint32_t k = 0; host && k < n; ++k) {
+        const uint32_t e = entries ? entries[k] : k;
+        if (e >= n_entries)
+            return set_error(XPBD_E_INVALID, "%s: entries[%u] = %u but the table holds %u entries", who, k, e, n_entries);
+        if (entries && k && entries[k - 1] >= e)
+            return set_error(XPBD_E_INVALID, "%s: entries[%u] = %u does not ascend from entries[%u] = %u", who, k, e, k - 1, entries[k - 1]);
+        if (int rc = check_kinematic_row(who, "rows", k, resident[e].mode, rows + (size_t)k * 7))
+            return rc;
     }
     return XPBD_OK;
 }

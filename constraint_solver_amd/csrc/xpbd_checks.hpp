@@ -95,4 +95,23 @@ struct DriveTargets {
     int check(const char *who, const uint32_t *drives, const double *targets, uint32_t n, bool host) const;
 };
 
+// ... of the kinematic table and its targets (include/xpbd.h, "KINEMATIC bodies"), after the caller has dealt with a NULL world:
+// what the call is made on.  KinematicTarget::check, of xpbd_world_set_kinematics (its check_kinematics): a NULL list with n > 0,
+// no resident bodies, a body out of range or not above its predecessor, an unknown mode, a non-finite value, an all-zero POSE
+// rotation; fixed_check, once the ten mass doubles of the named bodies are on the host (mass: [n][10]): a body that is not fixed.
+// KinematicTargets::check, of xpbd_world_set_kinematic_targets(_device) against the resident table (its check_kinematic_targets;
+// `resident` is read only with `host`): NULL rows with n > 0, entries == NULL with n != n_entries, a device list of more than
+// 2^29 entries or rows that are not 8-byte aligned, and with `host` an index out of range or not above its predecessor, a
+// non-finite value, an all-zero POSE rotation.
+struct KinematicTarget {
+    uint32_t n_bodies;
+    int check(const char *who, const xpbd_kinematic *list, uint32_t n) const;
+    int fixed_check(const char *who, const xpbd_kinematic *list, uint32_t n, const double *mass) const;
+};
+struct KinematicTargets {
+    const xpbd_kinematic *resident;
+    uint32_t n_entries;
+    int check(const char *who, const uint32_t *entries, const double *rows, uint32_t n, bool host) const;
+};
+
 } // namespace xpbd

@@ -36,6 +36,18 @@ JointSet remap_joint_set(const JointSet &in, const uint32_t *old_to_new, uint32_
     return out;
 }
 
+std::vector<xpbd_kinematic> remap_kinematics(const std::vector<xpbd_kinematic> &in, const uint32_t *old_to_new, uint32_t n_bodies)
+{
+    std::vector<xpbd_kinematic> out;
+    for (const xpbd_kinematic &e : in) {
+        if (e.body >= n_bodies || old_to_new[e.body] == kRemoved)
+            continue;
+        out.push_back(e);
+        out.back().body = old_to_new[e.body];
+    }
+    return out;
+}
+
 JointCsr build_joint_csr(const xpbd_joint *joints, uint32_t n_joints, uint32_t n_bodies)
 {
     JointCsr c;

@@ -24,6 +24,10 @@ struct JointSet {
 // relative order; limits and drives name the new joint numbers.  joint_old_to_new: [joints.size()], kRemoved for a dropped one.
 JointSet remap_joint_set(const JointSet &in, const uint32_t *old_to_new, uint32_t n_bodies, std::vector<uint32_t> &joint_old_to_new);
 
+// The kinematic table (include/xpbd.h, "KINEMATIC bodies") after the same re-index: the entries of surviving bodies with their
+// new body numbers, in order (the map is monotone, so the table stays ascending); those of removed bodies are dropped.
+std::vector<xpbd_kinematic> remap_kinematics(const std::vector<xpbd_kinematic> &in, const uint32_t *old_to_new, uint32_t n_bodies);
+
 // CSR body -> joints of xpbd_world_set_joints: off[n_bodies + 1] (allocated n_bodies + 2), list[2 * n_joints] with ascending
 // joint index inside every body's list.
 struct JointCsr {

@@ -9,6 +9,7 @@
 
 #include "xpbd_contacts.h"
 #include "xpbd_joint_state.h"
+#include "xpbd_kinematic.h"
 
 namespace xpbd {
 
@@ -28,6 +29,7 @@ struct SleepState {
     // scratch of a frame
     uint8_t *fixed;        // [stride] as the islands unit defines it, from the mass properties at the start of the frame
     uint8_t *inert;        // [stride] asleep or fixed: what the broadphase reads
+    uint8_t *moving;       // [stride] a MOVING kinematic body of the frame (k_kinematic_velocities; only read where a world has a table)
     uint32_t *island_min;  // [stride] by an island's first body: the smallest rest_frames of its members, 0 with a sleeper
     uint32_t n, stride;
 };
@@ -41,10 +43,24 @@ hipError_t launch_sleep_frame_begin(const SleepState &s, const double *stat, uin
 // neighbours' state after derive from it); with `trace` its contact mask into the `trace_rows` rows of the step's trace.
 hipError_t launch_sleep_records(const SleepState &s, const BodyArrays &b, double *rec_a, double *rec_b, double *post, const uint32_t *last_mask,
                                 uint32_t *trace, uint32_t trace_rows, hipStream_t stream);
+// A MOVING kinematic body is not inert in its frame: inert[body] = 0 for every entry of `t` whose body has moving[] set (a
+// fixed body is never asleep).  Behind launch_sleep_frame_begin, only in a world with a kinematic table.
+hipError_t launch_sleep_moving_inert(const SleepState &s, const KinematicTable &t, hipStream_t stream);
+// What the end-of-frame wake reads of the frame's MOVING bodies (default: none, the launches of a world without a table):
+// moving[], the frame's pair list (not the touching set: a platform that moves away stops touching in the first substep) and the
+// joints.
+struct MovingBodies {
+    const uint8_t *moving = nullptr; // [n]
+    const uint32_t *pairs = nullptr; // [n_pairs][2]
+    uint32_t n_pairs = 0;
+    const Joint *joints = nullptr;
+    uint32_t n_joints = 0;
+};
 // End of a frame: wake (marks from the `key_lanes` >= *key_count touching pairs `keys`, a << 32 | b; NULL: none), count
 // (speed limits squared on the host), and, after the islands unit has grouped the frame (launch_sleep_islands below), sleep.
 hipError_t launch_sleep_wake_count(const SleepState &s, const double *dyn, const unsigned long long *keys, const uint32_t *key_count,
-                                   uint32_t key_lanes, double linear2, double angular2, hipStream_t stream);
+                                   uint32_t key_lanes, double linear2, double angular2, hipStream_t stream,
+                                   const MovingBodies &moving = MovingBodies());
 // parent: the islands unit's flattened parents (parent[i] = first body of i's island); status: its give-up word (nonzero: nobody sleeps).
 hipError_t launch_sleep_islands(const SleepState &s, double *dyn, const uint32_t *parent, const uint32_t *status, uint32_t frames_to_sleep,
                                 hipStream_t stream);

@@ -95,6 +95,45 @@ __global__ void __launch_bounds__(kBlock) k_sleep_touch_mark(SleepState s, const
         atomicOr(&s.mark[g], 1u);
 }
 
+// One lane per kinematic entry: a MOVING body is not inert (fixed, so never asleep).
+__global__ void __launch_bounds__(kBlock) k_sleep_moving_inert(SleepState s, KinematicTable t)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= t.n)
+        return;
+    const uint32_t i = t.entries[k].body;
+    if (i < s.n && s.moving[i])
+        s.inert[i] = 0;
+}
+
+// One lane per pair of the frame's pair list, then one per joint: a sleeper that shares one with a MOVING body has its group
+// marked (whether or not they touch: the rule is conservative).
+__global__ void __launch_bounds__(kBlock) k_sleep_moving_mark(SleepState s, MovingBodies m)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t a, b;
+    if (t < m.n_pairs) {
+        a = m.pairs[2 * (size_t)t];
+        b = m.pairs[2 * (size_t)t + 1];
+    } else if (t - m.n_pairs < m.n_joints) {
+        a = m.joints[t - m.n_pairs].body_a;
+        b = m.joints[t - m.n_pairs].body_b;
+    } else {
+        return;
+    }
+    if (a >= s.n || b >= s.n)
+        return; // (never: both come from the world's own tables)
+    const bool ma = m.moving[a] != 0, mb = m.moving[b] != 0;
+    if (ma == mb)
+        return; // (two MOVING bodies are both fixed: neither sleeps)
+    const uint32_t sleeper = ma ? b : a;
+    if (!s.asleep[sleeper])
+        return;
+    const uint32_t g = s.group[sleeper];
+    if (g < s.n)
+        s.mark[g] = 1u; // (a plain store: every lane that writes the word writes this value)
+}
+
 // v.x * v.x + v.y * v.y + v.z * v.z, left to right (the unit is built without contraction)
 __device__ __forceinline__ double speed2(const double *__restrict__ dyn, uint32_t field, uint32_t stride, uint32_t i)
 {
@@ -267,15 +306,27 @@ hipError_t launch_sleep_records(const SleepState &s, const BodyArrays &b, double
     return hipGetLastError();
 }
 
+hipError_t launch_sleep_moving_inert(const SleepState &s, const KinematicTable &t, hipStream_t stream)
+{
+    if (s.n == 0 || t.n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(k_sleep_moving_inert, dim3(blocks_of(t.n)), dim3(kBlock), 0, stream, s, t);
+    return hipGetLastError();
+}
+
 hipError_t launch_sleep_wake_count(const SleepState &s, const double *dyn, const unsigned long long *keys, const uint32_t *key_count,
-                                   uint32_t key_lanes, double linear2, double angular2, hipStream_t stream)
+                                   uint32_t key_lanes, double linear2, double angular2, hipStream_t stream, const MovingBodies &moving)
 {
     if (s.n == 0)
         return hipSuccess;
     if (hipError_t e = hipMemsetAsync(s.ctrl + SC_WOKEN, 0, 2 * 4, stream)) // SC_WOKEN, SC_SLEPT
         return e;
-    if (keys && key_lanes) {
-        hipLaunchKernelGGL(k_sleep_touch_mark, dim3(blocks_of(key_lanes)), dim3(kBlock), 0, stream, s, keys, key_count, key_lanes);
+    const uint64_t moving_lanes = moving.moving ? (uint64_t)moving.n_pairs + moving.n_joints : 0u;
+    if (moving_lanes)
+        hipLaunchKernelGGL(k_sleep_moving_mark, dim3(blocks_of(moving_lanes)), dim3(kBlock), 0, stream, s, moving);
+    if ((keys && key_lanes) || moving_lanes) {
+        if (keys && key_lanes)
+            hipLaunchKernelGGL(k_sleep_touch_mark, dim3(blocks_of(key_lanes)), dim3(kBlock), 0, stream, s, keys, key_count, key_lanes);
         hipLaunchKernelGGL(k_sleep_wake, dim3(blocks_of(s.n)), dim3(kBlock), 0, stream, s, (const double *)nullptr, 0u, true);
         if (hipError_t e = hipGetLastError())
             return e;

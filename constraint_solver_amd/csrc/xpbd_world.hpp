@@ -10,6 +10,7 @@
 //   xpbd_world_islands.cpp   Islands and the island entry points
 //   xpbd_world_sleep.cpp     Sleep and the sleeping entry points
 //   xpbd_world_joint_state.cpp  joint states and drive targets: the entry points, and the way back of device-set targets
+//   xpbd_world_kinematic.cpp    KinematicBodies and the kinematic entry points
 #pragma once
 
 #include <cstdint>
@@ -25,6 +26,7 @@
 #include "xpbd_gjk.h"
 #include "xpbd_islands.h"
 #include "xpbd_joint_state.h"
+#include "xpbd_kinematic.h"
 #include "xpbd_pairs.h"
 #include "xpbd_population_remap.hpp"
 #include "xpbd_query.h"
@@ -102,6 +104,21 @@ struct JointTables {
         return xpbd::DriveTable{extras.items.as<xpbd::JointExtraItem>(), extras.drive_item.as<uint32_t>(), (uint32_t)extras.drive_item_host.size()};
     }
     void clear() { *this = JointTables{}; }
+};
+
+// The kinematic table of a world (xpbd_world_set_kinematics; xpbd_kinematic.h; xpbd_world_kinematic.cpp): what the caller handed
+// over, and its copy on the device, complete or absent (an empty table holds no block).  Only the setter and a population
+// change replace the block, each staged aside and moved in once nothing can fail.  targets_on_device:
+// xpbd_world_set_kinematic_targets_device has written rows that `list` does not hold yet (sync_kinematic_targets brings them
+// back before a population change re-stages the table from the host copy; a fresh table starts clean).
+struct KinematicBodies {
+    std::vector<xpbd_kinematic> list;
+    DeviceBuffer table;
+    bool targets_on_device = false;
+
+    bool any() const { return !list.empty(); }
+    xpbd::KinematicTable view() const { return xpbd::KinematicTable{table.as<xpbd_kinematic>(), (uint32_t)list.size()}; }
+    void clear() { *this = KinematicBodies{}; }
 };
 
 // The sphere broadphase of the contact pipeline (xpbd_world_contacts.cpp): grid, buckets, the neighbour lists and the pair
@@ -293,6 +310,7 @@ struct Islands {
 // the report, the joints and the stream of the world `w` they belong to; a world with sleeping off calls none of them.
 struct Sleep {
     bool on = false, fresh = true;
+    bool moving = false; // the scratch's moving[] describes the frame under way: step_contacts filled it from a non-empty kinematic table
     xpbd_sleep_config cfg{};
     uint32_t requests = 0;
     DeviceBuffer state, scratch;
@@ -375,7 +393,7 @@ struct xpbd_world {
     ReplanStaging replan;
     // state at the start of a frame (xpbd::frame_snapshot_save / _restore): the 13 dynamic fields and the contact masks
     FrameSnapshot snapshot;
-    // Body-indexed settings: each names bodies (or the joints between them) by index, so a new set of bodies clears all four
+    // Body-indexed settings: each names bodies (or the joints between them) by index, so a new set of bodies clears all five
     // (adopt_body_count).  Values whose clear() restores the defaults; the per-body device tables stay allocated beside theirs.
     JointTables joints;
     struct Filters { // xpbd_world_set_collision_filters: group, mask per body (on), XPBD_FILTER_* flags
@@ -401,6 +419,9 @@ struct xpbd_world {
         void clear() { *this = Restitution{}; }
     } restitution;
     DeviceBuffer rs_restitution, rs_start;
+    // xpbd_world_set_kinematics: the fixed bodies that move on a script.  Non-empty, the step runs the unfused schedule with the
+    // velocity overwrite before every integrate stage; empty, a world holds and enqueues nothing of it
+    KinematicBodies kinematics;
     // xpbd_world_set_terrain: the plane table of the heightfield and its description (planes == NULL: none).  World-level, as the
     // contact pad: it names no body, so no upload, population change or restore touches it.  With one the step runs the unfused
     // schedule (the fused pair-solve + integrate + ground kernel has no terrain form).
@@ -495,6 +516,7 @@ inline xpbd::SleepState Sleep::view(const xpbd_world *w) const
     s.island_min = scratch.as<uint32_t>();
     s.fixed = reinterpret_cast<uint8_t *>(s.island_min + st);
     s.inert = s.fixed + st;
+    s.moving = s.inert + st;
     s.n = w->n;
     s.stride = w->stride;
     return s;
@@ -523,12 +545,19 @@ int stage_joint_tables(xpbd::JointSet set, uint32_t n_bodies, hipStream_t stream
 // Targets set on the device go back into joints.set.drives (no-op unless extras.targets_on_device).  Device bound, stream idle.
 int sync_drive_targets(xpbd_world *w);
 
+// ---- xpbd_world_kinematic.cpp -----------------------------------------------------------------------------------------------
+// Rows set on the device go back into kinematics.list (no-op unless targets_on_device).  Device bound, stream idle.
+int sync_kinematic_targets(xpbd_world *w);
+
 // ---- xpbd_world_contacts.cpp ------------------------------------------------------------------------------------------------
 int build_neighbours_enqueue(xpbd_world *w, double dt);
 int build_neighbours_collect(xpbd_world *w);
 int build_neighbours(xpbd_world *w, double dt);
 int narrowphase_contacts(xpbd_world *w, const xpbd::BodyArrays &b, const xpbd::ContactBuffers &c);
-int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_row, const xpbd::BodySubset &awake = xpbd::BodySubset());
+// kinematic_left: the substeps of the frame still to run, this one included, when the kinematic overwrite belongs before this
+// substep's integrate stage (0: not -- no table, or the frame's first substep, whose overwrite precedes the broadphase)
+int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_row, const xpbd::BodySubset &awake = xpbd::BodySubset(),
+                     uint32_t kinematic_left = 0);
 int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_t *trace);
 
 #pragma GCC visibility pop

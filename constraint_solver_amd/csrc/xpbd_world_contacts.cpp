@@ -190,10 +190,12 @@ int narrowphase_contacts(xpbd_world *w, const xpbd::BodyArrays &b, const xpbd::C
 // One substep of the contact pipeline (neighbour lists must be current): the form the split API
 // (xpbd_world_contacts_substep) exposes, with a seam for the halo exchange after it.
 // awake: all bodies, or (sleeping on, from step_contacts) all but the sleepers.
-int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_row, const xpbd::BodySubset &awake)
+int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_row, const xpbd::BodySubset &awake, uint32_t kinematic_left)
 {
     const xpbd::BodyArrays b = w->arrays();
     const xpbd::ContactBuffers c = w->contact_buffers();
+    if (kinematic_left) // before the copy below: the restitution pass sees the scripted start velocities
+        XPBD_HIP_TRY(xpbd::launch_kinematic_velocities(b, w->kinematics.view(), h, kinematic_left, nullptr, w->stream));
     if (c.restitution) {
         // The velocity pass reads, of every body, the velocities the substep started from and the state after derive while it
         // writes its own body's result: the former are copied aside first (fields D_VEL.. of the SoA state are one block), the
@@ -224,6 +226,20 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
 {
     if (!w->has_topology)
         return set_error(XPBD_E_INVALID, "XPBD_MODE_CONTACTS needs xpbd_world_set_polytopes");
+    // Kinematic bodies (include/xpbd.h, "KINEMATIC bodies"): the overwrite of substep 0 comes before the broadphase, whose bounding
+    // spheres then include the scripted travel; with sleeping on it also tells who is MOVING in this frame.  No table: nothing.
+    const bool kinematic = w->kinematics.any() && substeps != 0 && w->n != 0;
+    w->sleep.moving = false;
+    if (kinematic) {
+        uint8_t *moving = nullptr;
+        if (w->sleep.on) {
+            XPBD_TRY(w->sleep.ensure(w));
+            moving = w->sleep.view(w).moving;
+            XPBD_HIP_TRY(hipMemsetAsync(moving, 0, w->stride, w->stream));
+            w->sleep.moving = true;
+        }
+        XPBD_HIP_TRY(xpbd::launch_kinematic_velocities(w->arrays(), w->kinematics.view(), h, substeps, moving, w->stream));
+    }
     if (int rc = build_neighbours(w, dt))
         return rc;
     if (substeps == 0)
@@ -236,9 +252,10 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         awake.skip = w->sleep.asleep(w);
     }
     // the velocity pass sits where the fused kernel below has the next substep's integrate; and that kernel has no terrain form
-    if (w->restitution.on || w->terrain.planes) {
+    // ... and the kinematic overwrite goes between the substeps, on the SoA state the fused kernel does not write
+    if (w->restitution.on || w->terrain.planes || kinematic) {
         for (uint32_t k = 0; k < substeps; ++k)
-            if (int rc = substep_contacts(w, h, trace, k, awake))
+            if (int rc = substep_contacts(w, h, trace, k, awake, kinematic && k ? substeps - k : 0u))
                 return rc;
         return w->sleep.on ? w->sleep.frame_end(w) : XPBD_OK;
     }
@@ -499,6 +516,9 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
     if (w->sleep.on)
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: the split API has no frame end, sleeping is on (xpbd_world_set_sleeping)");
+    if (w->kinematics.any())
+        return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: the split API does not know the frame's substep count, the kinematic table is not empty "
+                                         "(xpbd_world_set_kinematics)");
     if (int rc = bind_device(w))
         return rc;
     w->stepped = true;
@@ -518,6 +538,9 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_substep: call xpbd_world_contacts_begin first");
     if (w->sleep.on)
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_substep: the split API has no frame end, sleeping is on (xpbd_world_set_sleeping)");
+    if (w->kinematics.any())
+        return set_error(XPBD_E_INVALID, "xpbd_world_contacts_substep: the split API does not know the frame's substep count, the kinematic table is not empty "
+                                         "(xpbd_world_set_kinematics)");
     if (w->n == 0)
         return XPBD_OK;
     if (int rc = bind_device(w))

@@ -286,6 +286,8 @@ struct PopulationStage {
     uint32_t n = 0, stride = 0;
     DeviceBuffer dyn, stat, shape_id, last_mask, aos_staging, filters, friction, restitution, dyn_alt, rs_start;
     JointTables joints;
+    KinematicBodies kinematics; // (a removal only: the table as it stands stays where nobody leaves)
+    bool kinematics_staged = false;
 };
 
 // The new body arrays and per-body tables: new body s < n_keep is the present body dev_src[s] (NULL: body s), the n_add bodies
@@ -358,6 +360,8 @@ void commit_population(xpbd_world *w, PopulationStage &st, uint32_t max_shape_id
     take(w->dyn_alt, st.dyn_alt);
     take(w->rs_start, st.rs_start);
     w->joints = std::move(st.joints);
+    if (st.kinematics_staged)
+        w->kinematics = std::move(st.kinematics);
     take_body_count(w, st.n, max_shape_id);
 }
 
@@ -386,7 +390,7 @@ int remove_bodies(xpbd_world *w, const uint8_t *dev_remove, const uint32_t *indi
     uint32_t n_keep = 0;
     XPBD_HIP_TRY(hipMemcpyAsync(&n_keep, w->pop.prefix.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, w->stream));
     std::vector<uint32_t> map; // on the host only for the caller or for the joint re-index
-    if (old_to_new || w->joints.csr.n) {
+    if (old_to_new || w->joints.csr.n || w->kinematics.any()) {
         map.resize(n);
         XPBD_HIP_TRY(hipMemcpyAsync(map.data(), w->pop.map.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, w->stream));
     }
@@ -404,6 +408,13 @@ int remove_bodies(xpbd_world *w, const uint8_t *dev_remove, const uint32_t *indi
         XPBD_TRY(sync_drive_targets(w)); // the joint tables are re-staged from the host copy
         if (w->joints.csr.n)
             XPBD_TRY(stage_joint_tables(xpbd::remap_joint_set(w->joints.set, map.data(), n, joint_map), n_keep, w->stream, st.joints));
+        if (w->kinematics.any()) { // the kinematic table, re-indexed on its host copy next to the joints
+            XPBD_TRY(sync_kinematic_targets(w));
+            st.kinematics.list = xpbd::remap_kinematics(w->kinematics.list, map.data(), n);
+            if (!st.kinematics.list.empty())
+                XPBD_TRY(stage_upload(st.kinematics.table, st.kinematics.list.data(), st.kinematics.list.size() * sizeof(xpbd_kinematic)));
+            st.kinematics_staged = true;
+        }
         XPBD_TRY(stage_bodies(w, w->pop.src.as<uint32_t>(), n_keep, nullptr, nullptr, 0, st));
         XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
         commit_population(w, st, w->max_shape_id); // (max_shape_id stays an upper bound)

@@ -18,7 +18,7 @@ xpbd::SleepTarget sleep_target(const xpbd_world *w)
 int Sleep::ensure(const xpbd_world *w)
 {
     const size_t st = w->stride ? w->stride : 256u;
-    XPBD_HIP_TRY(xpbd::reserve_after_sync(w->stream, {{state, state_bytes((uint32_t)st)}, {scratch, st * 6}}));
+    XPBD_HIP_TRY(xpbd::reserve_after_sync(w->stream, {{state, state_bytes((uint32_t)st)}, {scratch, st * 7}}));
     if (fresh) {
         XPBD_HIP_TRY(hipMemsetAsync(state.ptr, 0, state_bytes((uint32_t)st), w->stream));
         XPBD_HIP_TRY(hipMemsetAsync(state.as<uint32_t>() + st, 0xFF, st * 4, w->stream)); // group = XPBD_SLEEP_GROUP_NONE
@@ -31,6 +31,8 @@ int Sleep::frame_begin(xpbd_world *w)
 {
     XPBD_TRY(ensure(w));
     XPBD_HIP_TRY(xpbd::launch_sleep_frame_begin(view(w), w->stat.as<double>(), requests, w->stream));
+    if (moving) // a MOVING kinematic body is not inert in this frame ("KINEMATIC bodies"; no table: the launches of before)
+        XPBD_HIP_TRY(xpbd::launch_sleep_moving_inert(view(w), w->kinematics.view(), w->stream));
     requests = 0;
     return XPBD_OK;
 }
@@ -57,8 +59,11 @@ int Sleep::frame_end(xpbd_world *w)
         keys = r.keys[r.cur].as<unsigned long long>();
         key_count = r.flag.as<uint32_t>() + w->bp.n_pairs;
     }
+    xpbd::MovingBodies mv; // the frame's MOVING kinematic bodies mark what shares a pair of the pair list or a joint with them
+    if (moving)
+        mv = xpbd::MovingBodies{s.moving, w->bp.pairs.as<uint32_t>(), w->bp.n_pairs, w->joints.csr.joints.as<xpbd::Joint>(), w->joints.csr.n};
     XPBD_HIP_TRY(xpbd::launch_sleep_wake_count(s, w->dyn.as<double>(), keys, key_count, w->bp.n_pairs, cfg.linear_speed * cfg.linear_speed,
-                                               cfg.angular_speed * cfg.angular_speed, w->stream));
+                                               cfg.angular_speed * cfg.angular_speed, w->stream, mv));
     Islands &isl = w->islands;
     XPBD_TRY(isl.reserve(w, false, 0));
     uint32_t *result = isl.result.as<uint32_t>();

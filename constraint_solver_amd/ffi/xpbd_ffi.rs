@@ -96,6 +96,19 @@ pub struct XpbdJoint {
     pub reserved: u32,
 }
 
+/// EXTENSION: one entry of the kinematic table (xpbd_kinematic, 64 bytes; see xpbd.h, "KINEMATIC bodies"): a fixed body that
+/// moves on a script.
+pub const XPBD_KINEMATIC_POSE: u32 = 0;     // linear = target position, angular = target rotation {s, x, y, z}
+pub const XPBD_KINEMATIC_VELOCITY: u32 = 1; // linear = velocity, angular = {wx, wy, wz, ignored}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct XpbdKinematic {
+    pub body: u32,
+    pub mode: u32,
+    pub linear: [f64; 3],
+    pub angular: [f64; 4],
+}
+
 /// EXTENSION: drive of a joint (XPBD_DRIVE_ANGLE = 0, XPBD_DRIVE_ANGULAR_VELOCITY = 1, XPBD_DRIVE_POSITION = 2,
 /// XPBD_DRIVE_VELOCITY = 3; see xpbd.h, "SLIDERS and joint DRIVES").
 #[repr(C)]
@@ -627,6 +640,11 @@ extern "C" {
     pub fn xpbd_world_joint_states_device(w: *mut XpbdWorld, dev_joints: *const u32, n: u32, dev_out: *mut XpbdJointState) -> c_int;
     pub fn xpbd_world_set_drive_targets(w: *mut XpbdWorld, drives: *const u32, targets: *const f64, n: u32) -> c_int;
     pub fn xpbd_world_set_drive_targets_device(w: *mut XpbdWorld, dev_drives: *const u32, dev_targets: *const f64, n: u32) -> c_int;
+    // kinematic bodies (include/xpbd.h, "KINEMATIC bodies"); a NULL entry list names all entries; rows are [n][7] doubles
+    pub fn xpbd_world_set_kinematics(w: *mut XpbdWorld, list: *const XpbdKinematic, n: u32) -> c_int;
+    pub fn xpbd_world_set_kinematic_targets(w: *mut XpbdWorld, entries: *const u32, rows: *const f64, n: u32) -> c_int;
+    pub fn xpbd_world_set_kinematic_targets_device(w: *mut XpbdWorld, dev_entries: *const u32, dev_rows: *const f64, n: u32) -> c_int;
+    pub fn xpbd_world_kinematic_count(w: *const XpbdWorld) -> u32;
     pub fn xpbd_multi_world_set_contact_report(mw: *mut XpbdMultiWorld, enable: u32) -> c_int;
     pub fn xpbd_multi_world_contact_report_counts(mw: *mut XpbdMultiWorld, out: *mut u32) -> c_int;
     pub fn xpbd_multi_world_download_pair_contacts(mw: *mut XpbdMultiWorld, pairs: *mut XpbdPairContact, pair_cap: u32,

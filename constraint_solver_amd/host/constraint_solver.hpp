@@ -692,6 +692,23 @@ class BatchWorld {
     {
         check(xpbd_world_set_drive_targets_device(w_, dev_drives, dev_targets, n));
     }
+    // kinematic bodies (include/xpbd.h, "KINEMATIC bodies"): the whole table; rows of seven doubles for resident entries
+    void set_kinematics(const std::vector<xpbd_kinematic> &table)
+    {
+        check(xpbd_world_set_kinematics(w_, table.empty() ? nullptr : table.data(), (uint32_t)table.size()));
+    }
+    void set_kinematic_targets(const std::vector<uint32_t> &entries, const std::vector<double> &rows)
+    {
+        if (rows.size() % 7 != 0 || (!entries.empty() && entries.size() * 7 != rows.size()))
+            throw std::invalid_argument("set_kinematic_targets: seven doubles per listed entry");
+        if (!rows.empty())
+            check(xpbd_world_set_kinematic_targets(w_, entries.empty() ? nullptr : entries.data(), rows.data(), (uint32_t)(rows.size() / 7)));
+    }
+    void set_kinematic_targets_device(const uint32_t *dev_entries, const double *dev_rows, uint32_t n)
+    {
+        check(xpbd_world_set_kinematic_targets_device(w_, dev_entries, dev_rows, n));
+    }
+    uint32_t kinematic_count() const { return xpbd_world_kinematic_count(w_); }
 
     std::vector<xpbd_contact> contacts()
     {

@@ -450,6 +450,68 @@ int  xpbd_world_joint_states_device(xpbd_world *w, const uint32_t *dev_joints /*
 int  xpbd_world_set_drive_targets(xpbd_world *w, const uint32_t *drives /* NULL: all, n = drive count */, const double *targets, uint32_t n);
 int  xpbd_world_set_drive_targets_device(xpbd_world *w, const uint32_t *dev_drives /* NULL: all */, const double *dev_targets, uint32_t n);
 
+/* KINEMATIC bodies (EXTENSION): fixed bodies that move on a script and push and carry what they meet -- elevators, doors,
+ * platforms, conveyors, spinners.
+ *
+ * A kinematic body is a FIXED body (inverse_mass and all nine inverse_inertia entries == 0, the islands' definition) that has
+ * an entry in the world's kinematic table.  Take a frame xpbd_world_step(dt, S), h = dt / S, and substep k = 0..S-1 with
+ * r = S - k substeps left.  Before the integrate stage of substep k the two velocities of every entry's body are overwritten
+ * from its current position p and rotation q (what xpbd_world_download_bodies would show at that point); all arithmetic per
+ * component, no fused multiply-add, correctly rounded divisions:
+ *   XPBD_KINEMATIC_POSE      linear = target position p_t, angular = target rotation q_t {s, x, y, z}
+ *     velocity = (p_t - p) / ((double)r * h)
+ *     dq = q_t * conjugate(q); if dq.s < 0 then dq = -dq;  m = length(vec(dq))
+ *     m == 0: angular_velocity = 0;  else half = atan2(m, dq.s), angular_velocity = vec(dq) * ((2 / h) * tan(half / r) / m)
+ *     This is the exact inverse of the integrate stage's rotation update, which turns a body by the half angle atan(h |w| / 2)
+ *     about w: the body turns half / r per substep and arrives at q_t in the last one.  q_t need not be unit, only the ratio
+ *     m : s enters.  The target persists: in later frames p == p_t, the velocities are zero and the body holds.
+ *   XPBD_KINEMATIC_VELOCITY  linear = velocity, angular = {wx, wy, wz, ignored}
+ *     velocity = linear, angular_velocity = angular[0..2], re-asserted before every substep (a fixed body that was merely given
+ *     a velocity through xpbd_world_set_dynamics loses angular speed in every substep: derive recomputes it from the rotation
+ *     the body made).  The pose follows the integrate stage: a substep turns the body by 2 atan(h |w| / 2), not by h |w|.
+ * After the overwrite everything is what a fixed body with those velocities does: integrate moves it, no constraint moves it
+ * (its inverse mass is zero), and derive leaves the velocities its neighbours' restitution pass reads.  The compliance term
+ * 1e-6 / h^2 keeps a contact's lagrange finite where both inverse masses are zero, so a kinematic body may cross the ground,
+ * the terrain or another fixed body without effect.  The k = 0 overwrite happens before the broadphase, so the bounding spheres
+ * of the frame include the scripted travel.
+ *
+ * xpbd_world_set_kinematics replaces the whole table (n == 0 clears it); `body` strictly ascending.  It reads the ten mass
+ * doubles of the named bodies from the device and may wait for that.  XPBD_E_INVALID, with the table as it was: a NULL world,
+ * a NULL list with n > 0, no resident bodies, an index out of range or not above its predecessor, an unknown mode, a body that
+ * is not fixed, any non-finite value (angular[3] of a VELOCITY entry included), an all-zero POSE rotation.
+ * xpbd_world_set_kinematic_targets replaces the seven doubles (linear, angular) of resident entries and nothing else: the mode
+ * and the body stay, and the next substep that runs sees the new row exactly as if xpbd_world_set_kinematics had been given the
+ * whole table with it.  entries[k] indexes the table of the last xpbd_world_set_kinematics (NULL: all of them, n = the entry
+ * count); the indices must be strictly ascending.  The host variant applies that call's value rules and waits: XPBD_E_INVALID,
+ * with nothing changed, for a NULL world, NULL rows with n > 0, entries == NULL with n other than the entry count, an index out
+ * of range or not above its predecessor, a non-finite value, an all-zero POSE rotation.  The device variant only enqueues
+ * (dev_rows 8-byte aligned, n <= 2^29); an entry that breaks one of those rules is skipped (entry k is compared with
+ * dev_entries[k - 1] whether or not that one was valid, so which entries count does not depend on the schedule; a list that
+ * names an entry again after a descent can leave two valid rows for it, and which of them it keeps is then unspecified).
+ * Neither variant wakes anybody by itself (see SLEEPING: a body that MOVES wakes what it meets).
+ * xpbd_world_upload_bodies clears the table, as it clears joints and filters.  A population change keeps the entries of the
+ * surviving bodies, re-indexed, in order, and drops those of removed bodies; added bodies are not kinematic.  History push and
+ * restore do not carry the table, as they do not carry drives; the definition uses no stored start pose, so a run repeated from
+ * a restored entry with the same targets gives the same bits.
+ * The table is accepted in every mode; only xpbd_world_step in XPBD_MODE_CONTACTS applies it, and a frame with a non-empty
+ * table runs the unfused schedule (as restitution and terrain do).  While it is non-empty the split API
+ * (xpbd_world_contacts_begin / _substep) is XPBD_E_INVALID.  A world that never calls these, or whose table is empty, launches
+ * what it launched before.
+ * Not here: the multi-GPU world; making a body with mass kinematic (the mass properties of resident bodies cannot change
+ * yet); a form of the fused schedule that applies the table. */
+#define XPBD_KINEMATIC_POSE     0u  /* linear = target position, angular = target rotation {s,x,y,z} */
+#define XPBD_KINEMATIC_VELOCITY 1u  /* linear = velocity, angular = {wx, wy, wz, ignored} */
+typedef struct xpbd_kinematic {     /* 64 bytes */
+    uint32_t body, mode;
+    double   linear[3];
+    double   angular[4];
+} xpbd_kinematic;
+int  xpbd_world_set_kinematics(xpbd_world *w, const xpbd_kinematic *list, uint32_t n);   /* whole table; n == 0 clears */
+int  xpbd_world_set_kinematic_targets(xpbd_world *w, const uint32_t *entries /* NULL: all, n = entry count */,
+                                      const double *rows /* [n][7] */, uint32_t n);
+int  xpbd_world_set_kinematic_targets_device(xpbd_world *w, const uint32_t *dev_entries /* NULL: all */, const double *dev_rows, uint32_t n);
+uint32_t xpbd_world_kinematic_count(const xpbd_world *w) XPBD_NOEXCEPT;
+
 /* Collision FILTERS (EXTENSION): which body-body pairs may touch.
  * Pair rule: bodies i and j may touch iff (group_i & mask_j) != 0 && (group_j & mask_i) != 0; with XPBD_FILTER_JOINTED
  * they also may not touch when any joint of the world's current joint list connects them.  The rule is symmetric.
@@ -882,8 +944,8 @@ uint32_t xpbd_world_history_length(const xpbd_world *w) XPBD_NOEXCEPT;
  * Before the first xpbd_multi_world_upload: XPBD_E_INVALID.  A device failure inside leaves the shards disagreeing: the world is
  * unusable then (destroy it).
  * Not here: xpbd_multi_world_set_dynamics (a teleported body interacts with the halo plan's travel allowance and needs a
- * design of its own: upload again, or move the body with impulses), device variants of the multi-world calls, kinematic
- * bodies, changing the mass properties of resident bodies.
+ * design of its own: upload again, or move the body with impulses), device variants of the multi-world calls, changing
+ * the mass properties of resident bodies.  (Scripted bodies that push and carry: "KINEMATIC bodies".)
  * ------------------------------------------------------------------------- */
 #define XPBD_IMPULSE_AT_POINT  0u   /* impulse acts at `point` (world space) */
 #define XPBD_IMPULSE_AT_CENTRE 1u   /* impulse acts at position + center_of_mass; `point` is ignored */
@@ -1664,6 +1726,21 @@ int  xpbd_world_islands_device(xpbd_world *w, uint32_t flags, uint32_t *dev_isla
  *   xpbd_world_upload_bodies and a population change (xpbd_world_add_bodies, _remove_bodies that removes a body): the state
  *     starts over at once, every body awake with rest_frames 0; sleeping stays on.
  * The device variants scatter their requests on the device and wait for nothing; an index outside the world is skipped.
+ *
+ * Kinematic bodies ("KINEMATIC bodies").  An entry's body is MOVING in a frame when, at the frame's start, its mode is POSE and
+ * the overwrite before the first substep produced any nonzero velocity or angular-velocity component, or its mode is VELOCITY
+ * and any of its six components is nonzero.  With sleeping on,
+ *   - a MOVING body is not inert in that frame: inert = asleep || (fixed && !moving), so the broadphase forms its pairs with
+ *     sleepers (rule (a) reads "inert" so);
+ *   - wake step 1 additionally MARKS every asleep body that shares a pair of the frame's PAIR LIST (the broadphase's, not the
+ *     touching set: a platform that moves away from a resting stack stops touching it in the first substep, and a floater must
+ *     never be left behind) or a joint with a MOVING body.  The rule is conservative: a sleeper whose bounding sphere the
+ *     moving body's swept sphere merely passes wakes too, and sleeps again once it has rested;
+ *   - for the islands a kinematic body remains a fixed body: an anchor, never a member; it never sleeps and has no counter.
+ * The sleepers stay asleep DURING the frame in which the body first moves (the asleep set does not change within a frame): they
+ * follow from the next frame on.  xpbd_world_set_kinematic_targets(_device) and xpbd_world_set_kinematics request no wake by
+ * themselves -- only motion does, and only near the body that moves; xpbd_world_set_dynamics on a fixed body still wakes
+ * everybody.  A world with sleeping on and an empty kinematic table launches the sleeping kernels it launched before.
  *
  * History.  While sleeping is on an entry carries asleep, rest_frames, group and the pending requests, and a restore brings
  * them back: a run repeated from a restored entry is the same bits, sleep state included.  Turning sleeping on or off changes
