@@ -73,7 +73,12 @@ ABI_SYMBOLS = [
     "xpbd_world_wake_bodies_device",
     "xpbd_world_joint_states", "xpbd_world_joint_states_device", "xpbd_world_set_drive_targets", "xpbd_world_set_drive_targets_device",
     "xpbd_world_set_kinematics", "xpbd_world_set_kinematic_targets", "xpbd_world_set_kinematic_targets_device", "xpbd_world_kinematic_count",
+    "xpbd_world_set_mass_properties", "xpbd_world_set_mass_properties_device", "xpbd_world_get_mass_properties",
 ]
+
+# mass edits (include/xpbd.h, "MASS properties of resident bodies"): the flags, and the doubles of a row
+MASS_INVERSE, MASS_DIRECT, MASS_KEEP_FRAME = 0, 1, 0x100
+MASS_DOUBLES = 13                 # inverse_mass | mass, inverse_inertia[9] | inertia[9] (column-major), center_of_mass[3]
 
 # kinematic bodies (include/xpbd.h, "KINEMATIC bodies"): xpbd_kinematic, 64 bytes
 KINEMATIC_POSE, KINEMATIC_VELOCITY = 0, 1
@@ -534,6 +539,12 @@ def hip_lib():
             L.xpbd_world_kinematic_count.restype = C.c_uint32
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
+        try:
+            L.xpbd_world_set_mass_properties.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+            L.xpbd_world_set_mass_properties_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+            L.xpbd_world_get_mass_properties.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
         _hip = L
     return _hip
 
@@ -892,6 +903,28 @@ class World:
         n = self.n if idx is None else idx.size
         out = np.empty((n, DYNAMIC_DOUBLES), dtype=np.float64)
         _check(hip_lib().xpbd_world_get_dynamics(self._h, None if idx is None else idx.ctypes.data, n, out.ctypes.data if n else None))
+        return out
+
+    # mass edits (include/xpbd.h, "MASS properties of resident bodies"): freeze, release, re-weigh
+    def set_mass_properties(self, indices, rows, flags=MASS_INVERSE):
+        """rows: (n, 13) of the listed bodies (None: all) in the layout flags names -- MASS_INVERSE: inverse_mass,
+        inverse_inertia[9], center_of_mass[3]; MASS_DIRECT: mass, inertia[9], center_of_mass[3], inverted on the device; with
+        MASS_KEEP_FRAME the geometry stays where it is when the centre of mass changes.  Waits."""
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        r = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, MASS_DOUBLES)
+        _check(hip_lib().xpbd_world_set_mass_properties(self._h, None if idx is None else idx.ctypes.data, r.shape[0],
+                                                        r.ctypes.data if r.size else None, flags))
+
+    def set_mass_properties_device(self, dev_indices_ptr, n, dev_rows_ptr, flags=MASS_INVERSE):
+        """Device pointers (0 / None: no index list), stream-ordered on the world's stream; an invalid entry is skipped."""
+        _check(hip_lib().xpbd_world_set_mass_properties_device(self._h, C.c_void_p(dev_indices_ptr or None), n, C.c_void_p(dev_rows_ptr or None), flags))
+
+    def get_mass_properties(self, indices=None):
+        """(n, 13) rows of the listed bodies (None: all bodies, in order), always in the MASS_INVERSE layout."""
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        n = self.n if idx is None else idx.size
+        out = np.empty((n, MASS_DOUBLES), dtype=np.float64)
+        _check(hip_lib().xpbd_world_get_mass_properties(self._h, None if idx is None else idx.ctypes.data, n, out.ctypes.data if n else None))
         return out
 
     # body population (include/xpbd.h, "Body POPULATION"): removing resident bodies and appending new ones

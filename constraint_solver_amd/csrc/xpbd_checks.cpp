@@ -1,5 +1,6 @@
 // xpbd_checks.cpp -- the argument checks of the C ABI that need no device, shared by the single and the multi-GPU world.
 // Host-only: no HIP header, builds with plain g++ (as xpbd_population_remap.cpp).
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -7,6 +8,7 @@
 
 #include "xpbd_checks.hpp"
 #include "xpbd_error.h"
+#include "xpbd_mass_row.hpp"
 
 namespace xpbd {
 
@@ -358,6 +360,60 @@ int KinematicTargets::check(const char *who, const uint32_t *entries, const doub
             return rc;
     }
     return XPBD_OK;
+}
+
+int MassEditTarget::check(const char *who, const uint32_t *indices, uint32_t n, const double *rows, uint32_t flags, bool host) const
+{
+    if (!rows)
+        return set_error(XPBD_E_INVALID, "%s: NULL rows with n = %u", who, n);
+    if (n_bodies == 0)
+        return set_error(XPBD_E_INVALID, "%s: the world holds no bodies", who);
+    if (!mass_flags_known(flags))
+        return set_error(XPBD_E_INVALID, "%s: unknown flags 0x%x (a layout, XPBD_MASS_INVERSE or XPBD_MASS_DIRECT, and XPBD_MASS_KEEP_FRAME)", who, flags);
+    if (!host) {
+        if (!indices && n != n_bodies)
+            return set_error(XPBD_E_INVALID, "%s: dev_indices == NULL names the bodies 0..n-1, but n = %u and the world holds %u bodies", who, n, n_bodies);
+        if (n > (1u << 29))
+            return set_error(XPBD_E_INVALID, "%s: n = %u (at most 2^29 entries per call)", who, n);
+        if (reinterpret_cast<uintptr_t>(rows) & 7u)
+            return set_error(XPBD_E_INVALID, "%s: dev_rows is not 8-byte aligned", who);
+        return XPBD_OK;
+    }
+    if (int rc = check_edit_indices(who, indices, n, n_bodies, true))
+        return rc;
+    const uint32_t layout = flags & kMassLayoutBits;
+    for (uint32_t k = 0; k < n; ++k) {
+        const double *row = rows + (size_t)k * kMassRowDoubles;
+        double out[kMassRowDoubles];
+        switch (resolve_mass_row(row, layout, out)) {
+        case kMassRowOk:
+            break;
+        case kMassRowNotFinite:
+            return set_error(XPBD_E_INVALID, "%s: rows[%u] has a value that is not finite", who, k);
+        case kMassRowNegativeInverseMass:
+            return set_error(XPBD_E_INVALID, "%s: rows[%u] has inverse_mass = %g (must be >= 0)", who, k, row[0]);
+        case kMassRowMassNotPositive:
+            return set_error(XPBD_E_INVALID, "%s: rows[%u] has mass = %g (XPBD_MASS_DIRECT needs mass > 0)", who, k, row[0]);
+        case kMassRowSingular:
+            return set_error(XPBD_E_SINGULAR_INERTIA, "%s: rows[%u]: the inertia tensor is not invertible (its determinant is 0)", who, k);
+        }
+        if (mass_row_fixed(out))
+            continue;
+        const uint32_t body = indices ? indices[k] : k;
+        const xpbd_kinematic *end = kinematic + n_kinematic;
+        const xpbd_kinematic *at = std::lower_bound(kinematic, end, body, [](const xpbd_kinematic &e, uint32_t b) { return e.body < b; });
+        if (at != end && at->body == body)
+            return set_error(XPBD_E_INVALID, "%s: rows[%u] gives mass to body %u, which has an entry in the kinematic table (clear it with "
+                                             "xpbd_world_set_kinematics first)", who, k, body);
+    }
+    return XPBD_OK;
+}
+
+int MassEditTarget::get_check(const char *who, const uint32_t *indices, uint32_t n, const void *rows) const
+{
+    if (!rows)
+        return set_error(XPBD_E_INVALID, "%s: NULL rows with n = %u", who, n);
+    return check_edit_indices(who, indices, n, n_bodies, false);
 }
 
 // The flags' part of the scene queries' checks: `known` are the family's own bits.

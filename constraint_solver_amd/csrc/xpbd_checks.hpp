@@ -114,4 +114,20 @@ struct KinematicTargets {
     int check(const char *who, const uint32_t *entries, const double *rows, uint32_t n, bool host) const;
 };
 
+// ... of the mass edits (include/xpbd.h, "MASS properties of resident bodies"), after the caller has dealt with a NULL world and
+// n == 0: what the call is made on -- the body count and the host copy of the kinematic table (ascending by body; read only
+// with `host`).  check, of xpbd_world_set_mass_properties(_device): NULL rows, no resident bodies, unknown flag bits or a layout
+// other than XPBD_MASS_INVERSE / _DIRECT; for the device variant indices == NULL with n != n_bodies, more than 2^29 entries,
+// rows that are not 8-byte aligned; with `host` the index list (out of range, twice) and every row by the rules of
+// resolve_mass_row (xpbd_mass_row.hpp: a non-finite value, inverse_mass < 0, DIRECT with mass <= 0; a singular DIRECT tensor is
+// XPBD_E_SINGULAR_INERTIA) and the kinematic rule: a body with an entry in the table takes only a row that leaves it fixed.
+// get_check, of xpbd_world_get_mass_properties: NULL rows, no resident bodies, the index list (an index may repeat).
+struct MassEditTarget {
+    uint32_t n_bodies;
+    const xpbd_kinematic *kinematic;
+    uint32_t n_kinematic;
+    int check(const char *who, const uint32_t *indices, uint32_t n, const double *rows, uint32_t flags, bool host) const;
+    int get_check(const char *who, const uint32_t *indices, uint32_t n, const void *rows) const;
+};
+
 } // namespace xpbd

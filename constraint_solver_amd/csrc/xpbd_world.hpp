@@ -6,7 +6,7 @@
 //                            the halo pieces, the frame snapshot
 //   xpbd_world_report.cpp    ContactReport and the report entry points
 //   xpbd_world_query.cpp     the scene-query host layer and entry points
-//   xpbd_world_edit.cpp      body edits, population changes, re-packing a shard
+//   xpbd_world_edit.cpp      body edits, mass edits, population changes, re-packing a shard
 //   xpbd_world_islands.cpp   Islands and the island entry points
 //   xpbd_world_sleep.cpp     Sleep and the sleeping entry points
 //   xpbd_world_joint_state.cpp  joint states and drive targets: the entry points, and the way back of device-set targets
@@ -280,6 +280,7 @@ struct TerrainStaging {
 };
 struct EditStaging {
     DeviceBuffer indices, values, list;
+    DeviceBuffer owner; // xpbd_world_set_mass_properties_device: one claim word per body (xpbd_mass_edit.h)
 };
 struct PopulationScratch {
     DeviceBuffer remove, indices, prefix, scan, map, src;
@@ -431,8 +432,8 @@ struct xpbd_world {
     TerrainStaging terrain_staging; // of xpbd_world_sample_terrain
     // scene queries (xpbd_world_raycast*, xpbd_world_overlap*): scratch of one call, staging of the host variants' arrays
     xpbd::SceneQueryScratch query;
-    // body edits (xpbd_world_set_external_wrench, _apply_impulses, _set_dynamics, _get_dynamics): the staging of the host
-    // variants' indices, values (force + torque, or rows of 13 doubles) and impulse lists
+    // body edits (xpbd_world_set_external_wrench, _apply_impulses, _set_dynamics, _get_dynamics, _set / _get_mass_properties): the
+    // staging of the host variants' indices, values (force + torque, or rows of 13 doubles) and impulse lists
     EditStaging edit;
     // body population (xpbd_world_remove_bodies, _add_bodies): the removal flags and index list of the host variant, the scan,
     // old_to_new and its inverse src[new] = old.  Scratch of one call; the new arrays are staged in buffers of their own.

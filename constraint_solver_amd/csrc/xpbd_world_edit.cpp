@@ -8,6 +8,7 @@
 
 #include "xpbd_world.hpp"
 #include "xpbd_body_ops.h"
+#include "xpbd_mass_edit.h"
 #include "xpbd_population.h"
 #include "xpbd_scan.h"
 
@@ -272,6 +273,85 @@ try {
     std::vector<uint32_t> iota;
     XPBD_TRY(stage_edit_indices(w, indices, n, iota));
     XPBD_HIP_TRY(xpbd::launch_export_dynamic(w->arrays(), w->edit.indices.as<uint32_t>(), n, w->edit.values.as<double>(), w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(rows, w->edit.values.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+// ---- mass edits (include/xpbd.h, "MASS properties of resident bodies") ----------------------------------------------------------
+namespace {
+xpbd::MassEditTarget mass_edit_target(const xpbd_world *w)
+{
+    return xpbd::MassEditTarget{w->n, w->kinematics.list.data(), (uint32_t)w->kinematics.list.size()};
+}
+
+// Both variants of xpbd_world_set_mass_properties, after their checks, with the list on the device.  The wake requests come
+// first, so that they see the mass properties the bodies rested under (a named fixed body wakes everybody, a named sleeper its
+// group).  The contact pipeline's copies of the mass properties are dropped: the per-shape table no longer describes every body of
+// a shape, and the per-body records are rebuilt by the next broadphase -- which the split API has to run again too.
+int enqueue_mass_edit(xpbd_world *w, const xpbd::MassEditList &list)
+{
+    if (w->sleep.on)
+        XPBD_TRY(w->sleep.request(w, list.indices, 1, list.n));
+    XPBD_HIP_TRY(xpbd::launch_set_mass(w->arrays(), w->kinematics.view(), list, w->stream));
+    w->stat_shared = false;
+    w->stat_rec_valid = false;
+    w->bp.have_neighbours = false;
+    return XPBD_OK;
+}
+} // namespace
+
+int xpbd_world_set_mass_properties(xpbd_world *w, const uint32_t *indices, uint32_t n, const double *rows, uint32_t flags)
+try {
+    const char *who = "xpbd_world_set_mass_properties";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0)
+        return XPBD_OK;
+    XPBD_TRY(mass_edit_target(w).check(who, indices, n, rows, flags, true));
+    XPBD_TRY(bind_device(w));
+    const size_t bytes = (size_t)n * xpbd::kMassRowDoubles * 8;
+    XPBD_TRY(reserve_edit_staging(w, (size_t)n * 4, bytes, 0));
+    if (indices)
+        XPBD_HIP_TRY(hipMemcpyAsync(w->edit.indices.ptr, indices, (size_t)n * 4, hipMemcpyHostToDevice, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(w->edit.values.ptr, rows, bytes, hipMemcpyHostToDevice, w->stream));
+    // (the indices are distinct: no claim pass)
+    XPBD_TRY(enqueue_mass_edit(w, xpbd::MassEditList{indices ? w->edit.indices.as<uint32_t>() : nullptr, w->edit.values.as<double>(), n, flags, nullptr}));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // the caller's arrays are only borrowed
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_set_mass_properties_device(xpbd_world *w, const uint32_t *dev_indices, uint32_t n, const double *dev_rows, uint32_t flags)
+try {
+    const char *who = "xpbd_world_set_mass_properties_device";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0)
+        return XPBD_OK;
+    XPBD_TRY(mass_edit_target(w).check(who, dev_indices, n, dev_rows, flags, false));
+    XPBD_TRY(bind_device(w));
+    uint32_t *owner = nullptr;
+    if (dev_indices) { // a list may name a body twice: the claim words, one per body
+        XPBD_HIP_TRY(xpbd::reserve_after_sync(w->stream, {{w->edit.owner, (size_t)w->stride * 4}}));
+        owner = w->edit.owner.as<uint32_t>();
+    }
+    return enqueue_mass_edit(w, xpbd::MassEditList{dev_indices, dev_rows, n, flags, owner});
+} XPBD_ABI_CATCH
+
+int xpbd_world_get_mass_properties(xpbd_world *w, const uint32_t *indices, uint32_t n, double *rows)
+try {
+    const char *who = "xpbd_world_get_mass_properties";
+    if (!w)
+        return set_error(XPBD_E_INVALID, "%s: NULL world", who);
+    if (n == 0)
+        return XPBD_OK;
+    XPBD_TRY(mass_edit_target(w).get_check(who, indices, n, rows));
+    XPBD_TRY(bind_device(w));
+    const size_t bytes = (size_t)n * xpbd::kMassRowDoubles * 8;
+    XPBD_TRY(reserve_edit_staging(w, (size_t)n * 4, bytes, 0));
+    if (indices)
+        XPBD_HIP_TRY(hipMemcpyAsync(w->edit.indices.ptr, indices, (size_t)n * 4, hipMemcpyHostToDevice, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_get_mass(w->arrays(), indices ? w->edit.indices.as<uint32_t>() : nullptr, n, w->edit.values.as<double>(), w->stream));
     XPBD_HIP_TRY(hipMemcpyAsync(rows, w->edit.values.ptr, bytes, hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;

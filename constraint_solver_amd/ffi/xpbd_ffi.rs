@@ -100,6 +100,9 @@ pub struct XpbdJoint {
 /// moves on a script.
 pub const XPBD_KINEMATIC_POSE: u32 = 0;     // linear = target position, angular = target rotation {s, x, y, z}
 pub const XPBD_KINEMATIC_VELOCITY: u32 = 1; // linear = velocity, angular = {wx, wy, wz, ignored}
+pub const XPBD_MASS_INVERSE: u32 = 0; // row = inverse_mass, inverse_inertia[9], center_of_mass[3]
+pub const XPBD_MASS_DIRECT: u32 = 1; // row = mass, inertia[9], center_of_mass[3]: inverted on the device
+pub const XPBD_MASS_KEEP_FRAME: u32 = 0x100; // the geometry stays where it is when center_of_mass changes
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct XpbdKinematic {
@@ -645,6 +648,10 @@ extern "C" {
     pub fn xpbd_world_set_kinematic_targets(w: *mut XpbdWorld, entries: *const u32, rows: *const f64, n: u32) -> c_int;
     pub fn xpbd_world_set_kinematic_targets_device(w: *mut XpbdWorld, dev_entries: *const u32, dev_rows: *const f64, n: u32) -> c_int;
     pub fn xpbd_world_kinematic_count(w: *const XpbdWorld) -> u32;
+    // mass edits (include/xpbd.h, "MASS properties of resident bodies"); a NULL index list names all bodies; rows are [n][13] doubles
+    pub fn xpbd_world_set_mass_properties(w: *mut XpbdWorld, indices: *const u32, n: u32, rows: *const f64, flags: u32) -> c_int;
+    pub fn xpbd_world_set_mass_properties_device(w: *mut XpbdWorld, dev_indices: *const u32, n: u32, dev_rows: *const f64, flags: u32) -> c_int;
+    pub fn xpbd_world_get_mass_properties(w: *mut XpbdWorld, indices: *const u32, n: u32, rows: *mut f64) -> c_int;
     pub fn xpbd_multi_world_set_contact_report(mw: *mut XpbdMultiWorld, enable: u32) -> c_int;
     pub fn xpbd_multi_world_contact_report_counts(mw: *mut XpbdMultiWorld, out: *mut u32) -> c_int;
     pub fn xpbd_multi_world_download_pair_contacts(mw: *mut XpbdMultiWorld, pairs: *mut XpbdPairContact, pair_cap: u32,

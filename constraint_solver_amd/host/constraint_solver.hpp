@@ -709,6 +709,25 @@ class BatchWorld {
         check(xpbd_world_set_kinematic_targets_device(w_, dev_entries, dev_rows, n));
     }
     uint32_t kinematic_count() const { return xpbd_world_kinematic_count(w_); }
+    // mass edits (include/xpbd.h, "MASS properties of resident bodies"): rows of 13 doubles; an empty index list names all bodies
+    void set_mass_properties(const std::vector<uint32_t> &indices, const std::vector<double> &rows, uint32_t flags = XPBD_MASS_INVERSE)
+    {
+        if (rows.size() % 13 != 0 || (!indices.empty() && indices.size() * 13 != rows.size()))
+            throw std::invalid_argument("set_mass_properties: 13 doubles per listed body");
+        if (!rows.empty())
+            check(xpbd_world_set_mass_properties(w_, indices.empty() ? nullptr : indices.data(), (uint32_t)(rows.size() / 13), rows.data(), flags));
+    }
+    void set_mass_properties_device(const uint32_t *dev_indices, uint32_t n, const double *dev_rows, uint32_t flags = XPBD_MASS_INVERSE)
+    {
+        check(xpbd_world_set_mass_properties_device(w_, dev_indices, n, dev_rows, flags));
+    }
+    std::vector<double> get_mass_properties(const std::vector<uint32_t> &indices)
+    {
+        std::vector<double> rows(indices.size() * 13);
+        if (!indices.empty())
+            check(xpbd_world_get_mass_properties(w_, indices.data(), (uint32_t)indices.size(), rows.data()));
+        return rows;
+    }
 
     std::vector<xpbd_contact> contacts()
     {

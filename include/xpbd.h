@@ -497,8 +497,8 @@ int  xpbd_world_set_drive_targets_device(xpbd_world *w, const uint32_t *dev_driv
  * table runs the unfused schedule (as restitution and terrain do).  While it is non-empty the split API
  * (xpbd_world_contacts_begin / _substep) is XPBD_E_INVALID.  A world that never calls these, or whose table is empty, launches
  * what it launched before.
- * Not here: the multi-GPU world; making a body with mass kinematic (the mass properties of resident bodies cannot change
- * yet); a form of the fused schedule that applies the table. */
+ * Not here: the multi-GPU world; a form of the fused schedule that applies the table.  (Making a body with mass kinematic:
+ * freeze it first, "MASS properties of resident bodies".) */
 #define XPBD_KINEMATIC_POSE     0u  /* linear = target position, angular = target rotation {s,x,y,z} */
 #define XPBD_KINEMATIC_VELOCITY 1u  /* linear = velocity, angular = {wx, wy, wz, ignored} */
 typedef struct xpbd_kinematic {     /* 64 bytes */
@@ -944,8 +944,8 @@ uint32_t xpbd_world_history_length(const xpbd_world *w) XPBD_NOEXCEPT;
  * Before the first xpbd_multi_world_upload: XPBD_E_INVALID.  A device failure inside leaves the shards disagreeing: the world is
  * unusable then (destroy it).
  * Not here: xpbd_multi_world_set_dynamics (a teleported body interacts with the halo plan's travel allowance and needs a
- * design of its own: upload again, or move the body with impulses), device variants of the multi-world calls, changing
- * the mass properties of resident bodies.  (Scripted bodies that push and carry: "KINEMATIC bodies".)
+ * design of its own: upload again, or move the body with impulses), device variants of the multi-world calls.  (Scripted
+ * bodies that push and carry: "KINEMATIC bodies".  Changing the mass properties: "MASS properties of resident bodies".)
  * ------------------------------------------------------------------------- */
 #define XPBD_IMPULSE_AT_POINT  0u   /* impulse acts at `point` (world space) */
 #define XPBD_IMPULSE_AT_CENTRE 1u   /* impulse acts at position + center_of_mass; `point` is ignored */
@@ -967,6 +967,75 @@ int  xpbd_world_get_dynamics(xpbd_world *w, const uint32_t *indices, uint32_t n,
 int  xpbd_multi_world_set_external_wrench(xpbd_multi_world *mw, const uint32_t *indices, uint32_t n,
                                           const double *force_xyz, const double *torque_xyz);   /* GLOBAL indices */
 int  xpbd_multi_world_apply_impulses(xpbd_multi_world *mw, const xpbd_impulse *list, uint32_t n); /* GLOBAL bodies */
+
+/* ---------------------------------------------------------------------------
+ * MASS properties of resident bodies (EXTENSION): freeze, release, re-weigh -- the 13 mass doubles of RESIDENT bodies
+ * (inverse_mass, inverse_inertia[9], center_of_mass[3]) changed in place.  NOT in the reference, whose `Rigid`s get theirs once,
+ * from Rigid::new (src/rigid.rs:53-71).  The single world only.
+ *
+ * The property everything rests on is the one of "Body EDITS": a world after the call steps bit for bit like a fresh world into
+ * which xpbd_world_download_bodies taken after the call was uploaded, with the same settings set again -- in every mode and for
+ * every flag below.  Index lists, the NULL form, n == 0, the host / device split and the ordering on the world's stream are those
+ * of xpbd_world_set_dynamics and xpbd_world_set_external_wrench(_device).  All arithmetic is per component, with no fused
+ * multiply-add and correctly rounded divisions.
+ *
+ * flags = a layout (the low eight bits) | XPBD_MASS_KEEP_FRAME or not.  Row k is 13 doubles for body indices[k]:
+ *   XPBD_MASS_INVERSE  inverse_mass, inverse_inertia[9] (column-major), center_of_mass[3]: the xpbd_rigid fields, taken as given;
+ *                      the 13 doubles of the body become rows[13k..13k+12].
+ *   XPBD_MASS_DIRECT   mass, inertia[9] (column-major, about the centre of mass), center_of_mass[3], inverted on the device as
+ *                      Rigid::new does: inverse_mass = 1.0 / mass;  inverse_inertia = cgmath's Matrix3::invert of the tensor m
+ *                      (columns x, y, z):  det = m.x.x * (m.y.y * m.z.z - m.z.y * m.y.z) - m.y.x * (m.x.y * m.z.z - m.z.y * m.x.z)
+ *                      + m.z.x * (m.x.y * m.y.z - m.y.y * m.x.z) first, det == 0.0 is singular;  then the columns
+ *                      cross(m.y, m.z) / det, cross(m.z, m.x) / det, cross(m.x, m.y) / det, transposed.  center_of_mass as given.
+ *   XPBD_MASS_KEEP_FRAME (either layout): the body's geometry stays where it is when center_of_mass changes.  With com, com' the
+ *                      old and the new centre of mass, d = com' - com, q the body's rotation and r = q * d (the rotation operator
+ *                      of Rigid::frame):  position' = position + (r - d);  velocity' = velocity + cross(angular_velocity, r), the
+ *                      velocity of the material point that becomes the centre of mass.  Rotation and angular velocity stay.
+ *                      Rigid::frame() of the body is then what it was, up to the roundings of these two formulas.
+ *   Without XPBD_MASS_KEEP_FRAME no dynamic double is touched: the world is what an upload of the downloaded bodies with the new
+ *   13 doubles would be, and the geometry shifts if center_of_mass changed.
+ * xpbd_world_get_mass_properties returns rows in the INVERSE layout, whatever layout they were set in.
+ *
+ * The kinematic rule.  A body with an entry in the kinematic table ("KINEMATIC bodies") stays FIXED: only a row whose inverse_mass
+ * and nine inverse_inertia entries are all == 0 is taken (its center_of_mass may change).  To give it mass, clear its entry first.
+ * Grab, carry, release: get the 13 doubles, set zeros (freeze), xpbd_world_set_kinematics with a target, step, clear the table,
+ * set the saved doubles.  Nothing here remembers the mass from before a freeze: the caller keeps what get returned.  A frozen
+ * body keeps the velocities it had, and a fixed body moves at its velocity: stop it with xpbd_world_set_dynamics if it shall stay.
+ *
+ * Host variants check EVERYTHING before any device work and wait for completion.  XPBD_E_INVALID, with nothing changed: a NULL
+ * world; NULL rows with n > 0; no resident bodies; indices == NULL with n other than the body count; an index out of range; in
+ * set, the same index twice; unknown flag bits or a layout other than 0 or 1; any non-finite row value; inverse_mass < 0; DIRECT
+ * with mass <= 0; a row that breaks the kinematic rule.  DIRECT with a singular tensor is XPBD_E_SINGULAR_INERTIA, with nothing
+ * changed: the code that mirrors the reference's panic.
+ * The device variant takes DEVICE arrays, only enqueues and cannot see the values.  XPBD_E_INVALID: NULL arguments, no bodies,
+ * dev_indices == NULL with n != body count, n > 2^29, dev_rows not 8-byte aligned, unknown flag or layout bits.  The kernel SKIPS
+ * an entry -- that entry changes no body -- whose index is out of range, that has a non-finite value, a negative inverse mass or a
+ * mass that is not positive, whose DIRECT determinant is == 0, or that breaks the kinematic rule.  The same index twice is
+ * unspecified, but one entry wins whole: the 13 doubles (and with KEEP_FRAME the position and velocity) are never a mix of two.
+ *
+ * What else changes: nothing.  Joints, limits, drives, filters, materials, restitution, the kinematic table, the contact report
+ * and its S_prev, contact masks and the history entries stay.  A history entry carries only dynamic doubles, so the edited mass
+ * STAYS after xpbd_world_history_restore, as an external wrench does (a KEEP_FRAME shift of position and velocity is dynamic state
+ * and is restored away with the rest).  A population change carries the edited doubles with the body.  xpbd_world_islands reads the
+ * mass properties per call: a body made fixed is an anchor from the next call on.  A host on the split API calls
+ * xpbd_world_contacts_begin again after a mass edit (xpbd_world_contacts_substep refuses until then), and
+ * xpbd_world_download_neighbours waits for the next broadphase too.  The contact pipeline reads the mass properties through a
+ * per-shape table while all bodies of a shape share theirs bit for bit; an edited world reads per-body records instead, same
+ * values and same bits, until the next xpbd_world_upload_bodies.
+ * SLEEPING: as every edit, naming a sleeper wakes its group at the start of the next step and naming a FIXED body wakes everybody
+ * (an anchor changed) -- judged by the mass properties from BEFORE the edit, so releasing a frozen body wakes everybody, and
+ * freezing a sleeper wakes its group: the new fixed body is inert from then on and never asleep again, and what rested on it may
+ * go back to sleep anchored to it.  An entry the device variant skips may still wake its body's group (a wake is always safe).
+ * Not here: the multi-GPU world; a shadow copy of the mass from before a freeze (the caller keeps the 13 doubles get returned);
+ * sharing the per-shape table again after an edit; deriving mass from a shape and a density on the device (the host mirror's
+ * rigid_metrics does that, and its result is a DIRECT row).
+ * ------------------------------------------------------------------------- */
+#define XPBD_MASS_INVERSE    0u     /* row = inverse_mass, inverse_inertia[9] (column-major), center_of_mass[3]: taken as given */
+#define XPBD_MASS_DIRECT     1u     /* row = mass, inertia[9] (column-major, about the centre of mass), center_of_mass[3]: inverted on the device */
+#define XPBD_MASS_KEEP_FRAME 0x100u /* the body's geometry stays where it is when center_of_mass changes */
+int  xpbd_world_set_mass_properties(xpbd_world *w, const uint32_t *indices, uint32_t n, const double *rows /* [n][13] */, uint32_t flags);
+int  xpbd_world_set_mass_properties_device(xpbd_world *w, const uint32_t *dev_indices, uint32_t n, const double *dev_rows, uint32_t flags);
+int  xpbd_world_get_mass_properties(xpbd_world *w, const uint32_t *indices, uint32_t n, double *rows /* [n][13], always the INVERSE layout */);
 
 /* ---------------------------------------------------------------------------
  * Body POPULATION (EXTENSION): removing RESIDENT bodies and appending new ones, without uploading the others again.  NOT in
