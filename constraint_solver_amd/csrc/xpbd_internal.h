@@ -11,6 +11,7 @@
 
 #include "xpbd_checks.hpp" // the argument checks both worlds share
 #include "xpbd_error.h"
+#include "xpbd_shape_tables.hpp" // the compiler of the shape tables, for both worlds too
 
 namespace xpbd {
 
@@ -151,6 +152,9 @@ int download_records(xpbd_world *w, const uint32_t *host_slots, uint32_t n, doub
 // The world's bodies become: body s = the present body host_src[s] (>= 0) or incoming record -host_src[s] - 1 (39 doubles
 // each).  Only the incoming records cross the bus; otherwise as xpbd_world_upload_bodies (joints and neighbour lists dropped).
 int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const double *incoming39, uint32_t n_incoming);
+// Compiled shape tables (xpbd_shape_tables.hpp) become the world's: what both shape setters end in, and how every shard takes
+// tables compiled once.  A refusal (fewer shapes than the resident bodies use) or a failure leaves the previous tables in force.
+int install_shape_tables(xpbd_world *w, const ShapeTablesHost &tables);
 // Ray casts of the world's bodies, stream-ordered (device arrays) / from and to host arrays (waits).  dev_global_id: device
 // array of w's body count, the index each body is known by (XPBD_NO_HIT: the body does not answer); NULL: its slot.
 // masked: only bodies whose collision-filter group meets `mask` answer (xpbd_world_raycast_masked); else every body does.

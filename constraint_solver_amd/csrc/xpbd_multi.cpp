@@ -40,6 +40,7 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "xpbd_multi.hpp"
@@ -273,27 +274,15 @@ int xpbd_multi_world_set_polytopes(xpbd_multi_world *mw, const xpbd_polytope *sh
 try {
     if (!mw || !shapes || n_shapes == 0)
         return set_error(XPBD_E_INVALID, "xpbd_multi_world_set_polytopes: NULL argument or no shapes");
-    // validated by the first shard before any shard changes; a later failure leaves the world without shapes (and says so)
+    // compiled once and validated before any shard changes; a later failure leaves the world without shapes (and says so)
     mw->have_shapes = false;
     mw->plan.drop();
+    xpbd::ShapeTablesHost t;
+    XPBD_TRY(xpbd::compile_polytopes("xpbd_world_set_polytopes", shapes, n_shapes, t));
     for (Shard &s : mw->shards)
-        if (int rc = xpbd_world_set_polytopes(s.world, shapes, n_shapes))
-            return rc;
-    mw->shape_radius.assign(n_shapes, 0.0);
-    mw->shape_centroid.assign((size_t)3 * n_shapes, 0.0);
-    for (uint32_t k = 0; k < n_shapes; ++k) {
-        const xpbd_polytope &p = shapes[k];
-        for (int a = 0; a < 3; ++a)
-            mw->shape_centroid[3 * (size_t)k + a] = p.centroid[a];
-        for (uint32_t v = 0; v < p.n_vertices; ++v) {
-            double d2 = 0.0;
-            for (int a = 0; a < 3; ++a) {
-                const double d = p.vertices_xyz[3 * (size_t)v + a] - p.centroid[a];
-                d2 += d * d;
-            }
-            mw->shape_radius[k] = std::max(mw->shape_radius[k], std::sqrt(d2));
-        }
-    }
+        XPBD_TRY(xpbd::install_shape_tables(s.world, t));
+    mw->shape_radius = std::move(t.radii); // for the shard planner: max |vertex - centroid| and the centroid per shape
+    mw->shape_centroid = std::move(t.centroids);
     mw->have_shapes = true;
     return XPBD_OK;
 } XPBD_MULTI_ABI_CATCH

@@ -10,16 +10,9 @@
 #include <hip/hip_runtime_api.h>
 
 #include "xpbd_kernels.h"
+#include "xpbd_shape_tables.hpp" // ShapeDesc, kMaxFaceVerts
 
 namespace xpbd {
-
-// Per-shape topology tables in device memory (all shapes back to back).
-struct ShapeDesc {
-    uint32_t vert0, n_verts;   // into verts (shared with ShapeTable::verts)
-    uint32_t face0, n_faces;   // into planes / face_start
-    uint32_t edge0, n_edges;   // into edges / edge_dir_id
-    uint32_t dir0, n_dirs;     // into edge_dirs: unique edge directions (up to sign)
-};
 
 struct PolytopeTables {
     const double *verts;         // [total_verts][3]
@@ -44,7 +37,6 @@ struct PolytopeTables {
 };
 
 constexpr uint32_t kMaxManifoldPoints = 8;
-constexpr uint32_t kMaxFaceVerts = 8;      // vertices per face accepted by the clipper
 constexpr double kEdgeBias = 1e-6;         // an edge axis must beat both face axes by this much (metres)
 
 // Result of one pair, 16-byte header + 8 x 2 points (xpbd_manifold in include/xpbd.h has this layout).

@@ -1,6 +1,6 @@
-// xpbd_world.cpp -- the single-GPU world of the C ABI in include/xpbd.h: its life, shapes and polytopes, the bodies' way in and
-// out, the body-indexed settings with the staging of the joint tables, the history and the step.  The state: xpbd_world.hpp;
-// the contact pipeline, reports, scene queries and body edits have units of their own (listed there).
+// xpbd_world.cpp -- the single-GPU world of the C ABI in include/xpbd.h: its life, the bodies' way in and out, the body-indexed
+// settings with the staging of the joint tables, the history and the step.  The state: xpbd_world.hpp; the shape tables, the
+// contact pipeline, reports, scene queries and body edits have units of their own (listed there).
 //
 // Every ABI call turns into kernel launches.  There is no CPU fallback: without a usable HIP device every compute entry point
 // fails with XPBD_E_NO_DEVICE / XPBD_E_HIP.
@@ -13,7 +13,6 @@
 #include <vector>
 
 #include "xpbd_world.hpp"
-#include "xpbd_math.hpp"
 
 constexpr uint32_t kDefaultBlock = 64;
 
@@ -37,9 +36,9 @@ void absorb_stat_record(xpbd_world *w, const xpbd_rigid &body, uint32_t sid)
 // world); a changed shape count starts over too, with the property lost.
 void reset_stat_records(xpbd_world *w, bool start_over, uint32_t n)
 {
-    if (start_over || w->stat_shape_seen.size() != w->n_shapes) {
-        w->stat_shape_host.assign((size_t)w->n_shapes * xpbd::kStatRecDoubles, 0.0);
-        w->stat_shape_seen.assign(w->n_shapes, 0);
+    if (start_over || w->stat_shape_seen.size() != w->geom.n_shapes) {
+        w->stat_shape_host.assign((size_t)w->geom.n_shapes * xpbd::kStatRecDoubles, 0.0);
+        w->stat_shape_seen.assign(w->geom.n_shapes, 0);
         w->stat_shared = start_over && n != 0;
     }
 }
@@ -97,11 +96,12 @@ int adopt_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id)
     return XPBD_OK;
 }
 
-// `bytes` (> 0) of `values` in a block of its own.
+// `bytes` of `values` in a block of its own (no bytes: a block all the same, so that no table of a world with shapes is NULL).
 int stage_upload(DeviceBuffer &fresh, const void *values, size_t bytes)
 {
-    XPBD_HIP_TRY(fresh.reserve(bytes));
-    XPBD_HIP_TRY(hipMemcpy(fresh.ptr, values, bytes, hipMemcpyHostToDevice));
+    XPBD_HIP_TRY(fresh.reserve(bytes ? bytes : 8));
+    if (bytes)
+        XPBD_HIP_TRY(hipMemcpy(fresh.ptr, values, bytes, hipMemcpyHostToDevice));
     return XPBD_OK;
 }
 
@@ -261,184 +261,18 @@ try {
 
 void xpbd_world_destroy(xpbd_world *w) noexcept { delete w; }
 
-int xpbd_world_set_shapes(xpbd_world *w, const double *verts_xyz, const uint32_t *vert_offsets,
-                          uint32_t n_shapes)
-try {
-    if (!w || !verts_xyz || !vert_offsets || n_shapes == 0)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: NULL argument or no shapes");
-    if (vert_offsets[0] != 0)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: vert_offsets[0] must be 0");
-    for (uint32_t s = 0; s < n_shapes; ++s) {
-        if (vert_offsets[s + 1] < vert_offsets[s])
-            return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: vert_offsets not monotone at %u", s);
-        if (vert_offsets[s + 1] - vert_offsets[s] > XPBD_MAX_SHAPE_VERTS)
-            return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: shape %u has %u vertices (max %u)", s,
-                             vert_offsets[s + 1] - vert_offsets[s], XPBD_MAX_SHAPE_VERTS);
-    }
-    const uint32_t total = vert_offsets[n_shapes];
-    // The tables are staged into LDS by every block; keep them far below the 160 KiB/CU.
-    if ((size_t)total * 24 + (size_t)(n_shapes + 1) * 4 > 48 * 1024)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: shape tables exceed 48 KiB");
-    // the resident bodies keep their shape ids: the kernels index the staged table with them unchecked
-    if (w->n && n_shapes <= w->max_shape_id)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_shapes: %u shapes, but the uploaded bodies use shape id %u (upload bodies "
-                                         "again after shrinking the table)", n_shapes, w->max_shape_id);
-    if (int rc = bind_device(w))
-        return rc;
-    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    XPBD_HIP_TRY(w->shape_verts.reserve(total ? (size_t)total * 24 : 8));
-    XPBD_HIP_TRY(w->shape_offsets.reserve((size_t)(n_shapes + 1) * 4));
-    if (total)
-        XPBD_HIP_TRY(hipMemcpy(w->shape_verts.ptr, verts_xyz, (size_t)total * 24, hipMemcpyHostToDevice));
-    XPBD_HIP_TRY(hipMemcpy(w->shape_offsets.ptr, vert_offsets, (size_t)(n_shapes + 1) * 4, hipMemcpyHostToDevice));
-    w->n_shapes = n_shapes;
-    w->total_verts = total;
-    w->has_topology = false;
-    return XPBD_OK;
-} XPBD_ABI_CATCH
-
-int xpbd_world_set_polytopes(xpbd_world *w, const xpbd_polytope *shapes, uint32_t n_shapes)
-try {
-    if (!w || !shapes || n_shapes == 0)
-        return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: NULL argument or no shapes");
-    std::vector<double> verts, planes, centroids, radii, dirs;
-    std::vector<uint32_t> vert_offsets{0}, face_start{0}, face_verts, edges, dir_id;
-    std::vector<xpbd::ShapeDesc> desc;
-    for (uint32_t s = 0; s < n_shapes; ++s) {
-        const xpbd_polytope &p = shapes[s];
-        if ((p.n_vertices && !p.vertices_xyz) || (p.n_edges && !p.edges) ||
-            (p.n_faces && (!p.face_offsets || !p.face_indices)))
-            return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u has a NULL table", s);
-        if (p.n_vertices > XPBD_MAX_SHAPE_VERTS || p.n_faces > 64 || p.n_edges > 4096)
-            return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u too large (%u vertices, %u faces, %u edges)",
-                             s, p.n_vertices, p.n_faces, p.n_edges);
-        xpbd::ShapeDesc d{};
-        d.vert0 = (uint32_t)(verts.size() / 3);
-        d.n_verts = p.n_vertices;
-        d.face0 = (uint32_t)(planes.size() / 4);
-        d.n_faces = p.n_faces;
-        d.edge0 = (uint32_t)(edges.size() / 2);
-        d.n_edges = p.n_edges;
-        verts.insert(verts.end(), p.vertices_xyz, p.vertices_xyz + 3 * (size_t)p.n_vertices);
-        vert_offsets.push_back((uint32_t)(verts.size() / 3));
-        auto vertex = [&](uint32_t i) {
-            return xpbd::Vec3{p.vertices_xyz[3 * i], p.vertices_xyz[3 * i + 1], p.vertices_xyz[3 * i + 2]};
-        };
-        for (uint32_t e = 0; e < 2 * p.n_edges; ++e) {
-            if (p.edges[e] >= p.n_vertices)
-                return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u edge vertex out of range", s);
-            edges.push_back(p.edges[e]);
-        }
-        // unique edge directions (up to sign), first edge with a direction represents it
-        d.dir0 = (uint32_t)(dirs.size() / 3);
-        for (uint32_t e = 0; e < p.n_edges; ++e) {
-            const xpbd::Vec3 dv = vertex(p.edges[2 * e + 1]) - vertex(p.edges[2 * e]);
-            const uint32_t nd = (uint32_t)(dirs.size() / 3) - d.dir0;
-            uint32_t found = nd;
-            for (uint32_t k = 0; k < nd; ++k) {
-                const double *u = &dirs[3 * (size_t)(d.dir0 + k)];
-                const xpbd::Vec3 uv{u[0], u[1], u[2]};
-                const xpbd::Vec3 c = xpbd::cross(dv, uv);
-                if (xpbd::dot(c, c) <= 1e-12 * (xpbd::dot(dv, dv) * xpbd::dot(uv, uv))) {
-                    found = k;
-                    break;
-                }
-            }
-            if (found == nd)
-                dirs.insert(dirs.end(), {dv.x, dv.y, dv.z});
-            dir_id.push_back(found);
-        }
-        d.n_dirs = (uint32_t)(dirs.size() / 3) - d.dir0;
-        const xpbd::Vec3 centroid{p.centroid[0], p.centroid[1], p.centroid[2]};
-        for (uint32_t f = 0; f < p.n_faces; ++f) {
-            const uint32_t f0 = p.face_offsets[f], f1 = p.face_offsets[f + 1];
-            if (f1 < f0 || f1 - f0 < 3 || f1 - f0 > xpbd::kMaxFaceVerts)
-                return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u face %u needs 3..%u vertices", s, f,
-                                 xpbd::kMaxFaceVerts);
-            for (uint32_t q = f0; q < f1; ++q) {
-                if (p.face_indices[q] >= p.n_vertices)
-                    return set_error(XPBD_E_INVALID, "xpbd_world_set_polytopes: shape %u face vertex out of range", s);
-                face_verts.push_back(p.face_indices[q]);
-            }
-            face_start.push_back((uint32_t)face_verts.size());
-            // Polytope::plane (src/geometry.rs:262-271) over Plane::from_points / facing / flip (:16-24, :55-68)
-            const xpbd::Vec3 p0 = vertex(p.face_indices[f0]), p1 = vertex(p.face_indices[f0 + 1]),
-                             p2 = vertex(p.face_indices[f0 + 2]);
-            xpbd::Vec3 n = xpbd::normalized(xpbd::cross(p1 - p0, p2 - p0));
-            double disp = xpbd::dot(n, p0);
-            const bool facing = xpbd::dot(n, centroid - disp * n) >= 0.0;
-            if (facing) {
-                n = -n;
-                disp = -disp;
-            }
-            planes.insert(planes.end(), {n.x, n.y, n.z, disp});
-        }
-        centroids.insert(centroids.end(), {centroid.x, centroid.y, centroid.z});
-        double radius = 0.0; // bounding sphere about the centroid
-        for (uint32_t k = 0; k < p.n_vertices; ++k) {
-            const double dist = xpbd::length(vertex(k) - centroid);
-            if (dist > radius)
-                radius = dist;
-        }
-        radii.push_back(radius);
-        desc.push_back(d);
-    }
-    static const double zero3[3] = {0, 0, 0};
-    if (int rc = xpbd_world_set_shapes(w, verts.empty() ? zero3 : verts.data(), vert_offsets.data(), n_shapes))
-        return rc;
-    auto upload = [&](DeviceBuffer &buf, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = buf.reserve(bytes ? bytes : 8);
-        if (e == hipSuccess && bytes)
-            e = hipMemcpy(buf.ptr, src, bytes, hipMemcpyHostToDevice);
-        return e;
-    };
-    XPBD_HIP_TRY(upload(w->planes, planes.data(), planes.size() * 8));
-    XPBD_HIP_TRY(upload(w->centroids, centroids.data(), centroids.size() * 8));
-    XPBD_HIP_TRY(upload(w->shape_desc, desc.data(), desc.size() * sizeof(xpbd::ShapeDesc)));
-    XPBD_HIP_TRY(upload(w->face_start, face_start.data(), face_start.size() * 4));
-    XPBD_HIP_TRY(upload(w->face_verts, face_verts.data(), face_verts.size() * 4));
-    XPBD_HIP_TRY(upload(w->edges, edges.data(), edges.size() * 4));
-    XPBD_HIP_TRY(upload(w->shape_radii, radii.data(), radii.size() * 8));
-    XPBD_HIP_TRY(upload(w->edge_dirs, dirs.data(), dirs.size() * 8));
-    XPBD_HIP_TRY(upload(w->edge_dir_id, dir_id.data(), dir_id.size() * 4));
-    w->has_topology = true;
-    w->sleep.wake_all(true);
-    uint32_t max_verts = 0, max_faces = 0, max_face_verts = 0, small_max_face_verts = 0, n_small = 0;
-    std::vector<uint8_t> shape_class(n_shapes, 0);
-    for (uint32_t k = 0; k < n_shapes; ++k) {
-        max_verts = shapes[k].n_vertices > max_verts ? shapes[k].n_vertices : max_verts;
-        max_faces = shapes[k].n_faces > max_faces ? shapes[k].n_faces : max_faces;
-        const bool small = shapes[k].n_vertices <= 8 && shapes[k].n_faces <= 8;
-        shape_class[k] = small ? 0 : 1;
-        n_small += small;
-        for (uint32_t f = 0; f < shapes[k].n_faces; ++f) {
-            const uint32_t nfv = shapes[k].face_offsets[f + 1] - shapes[k].face_offsets[f];
-            max_face_verts = nfv > max_face_verts ? nfv : max_face_verts;
-            if (small)
-                small_max_face_verts = nfv > small_max_face_verts ? nfv : small_max_face_verts;
-        }
-    }
-    XPBD_HIP_TRY(upload(w->shape_class, shape_class.data(), shape_class.size()));
-    w->two_classes = (n_small != 0 && n_small != n_shapes) ? 1u : 0u;
-    w->small_max_face_verts = small_max_face_verts;
-    w->max_verts = max_verts;
-    w->max_faces = max_faces;
-    w->max_face_verts = max_face_verts;
-    return XPBD_OK;
-} XPBD_ABI_CATCH
-
 int xpbd_world_upload_bodies(xpbd_world *w, const xpbd_rigid *aos, const uint32_t *shape_id, uint32_t n)
 try {
     if (!w || (!aos && n))
         return set_error(XPBD_E_INVALID, "xpbd_world_upload_bodies: NULL argument");
-    if (w->n_shapes == 0)
+    if (w->geom.n_shapes == 0)
         return set_error(XPBD_E_INVALID, "xpbd_world_upload_bodies: call xpbd_world_set_shapes first");
     uint32_t max_shape_id = 0;
     if (shape_id)
         for (uint32_t i = 0; i < n; ++i) {
-            if (shape_id[i] >= w->n_shapes)
+            if (shape_id[i] >= w->geom.n_shapes)
                 return set_error(XPBD_E_INVALID, "xpbd_world_upload_bodies: shape_id[%u] = %u >= n_shapes %u", i,
-                                 shape_id[i], w->n_shapes);
+                                 shape_id[i], w->geom.n_shapes);
             max_shape_id = shape_id[i] > max_shape_id ? shape_id[i] : max_shape_id;
         }
     if (int rc = bind_device(w))
@@ -505,7 +339,7 @@ try {
         return set_error(XPBD_E_INVALID, "xpbd_world_step: NULL world");
     if (substeps == 0) // the reference divides by zero and runs no substep; treat as an argument error
         return set_error(XPBD_E_INVALID, "xpbd_world_step: substeps must be > 0");
-    if (w->n_shapes == 0)
+    if (w->geom.n_shapes == 0)
         return set_error(XPBD_E_INVALID, "xpbd_world_step: no shapes set");
     if (w->n == 0)
         return XPBD_OK;
@@ -526,12 +360,12 @@ try {
         }
     } else if (w->mode == XPBD_MODE_FUSED) {
         w->report.reset();
-        XPBD_HIP_TRY(xpbd::launch_step(w->arrays(), w->shapes(), h, substeps, w->last_mask.as<uint32_t>(), trace, 0,
+        XPBD_HIP_TRY(xpbd::launch_step(w->arrays(), w->geom.shapes(), h, substeps, w->last_mask.as<uint32_t>(), trace, 0,
                                        w->block_size, w->stream));
     } else {
         w->report.reset();
         for (uint32_t k = 0; k < substeps; ++k)
-            XPBD_HIP_TRY(xpbd::launch_step(w->arrays(), w->shapes(), h, 1, w->last_mask.as<uint32_t>(), trace, k,
+            XPBD_HIP_TRY(xpbd::launch_step(w->arrays(), w->geom.shapes(), h, 1, w->last_mask.as<uint32_t>(), trace, k,
                                            w->block_size, w->stream));
     }
     w->stepped = true;

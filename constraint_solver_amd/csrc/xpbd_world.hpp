@@ -1,7 +1,8 @@
 // xpbd_world.hpp -- the single-GPU world behind the C ABI: its state, the owners of the parts that have an invariant, and
 // what the units that implement it share (not installed; no .hip file includes it).
 //
-//   xpbd_world.cpp           create/destroy, shapes, upload/download, the body-indexed setters, joint staging, history, step
+//   xpbd_world.cpp           create/destroy, upload/download, the body-indexed setters, joint staging, history, step
+//   xpbd_world_shapes.cpp    ShapeTables: the two shape setters and their one staged install
 //   xpbd_world_contacts.cpp  Broadphase, NarrowphaseSchedule, the contact schedules and their settings, the one-shot narrowphases,
 //                            the halo pieces, the frame snapshot
 //   xpbd_world_report.cpp    ContactReport and the report entry points
@@ -104,6 +105,27 @@ struct JointTables {
         return xpbd::DriveTable{extras.items.as<xpbd::JointExtraItem>(), extras.drive_item.as<uint32_t>(), (uint32_t)extras.drive_item_host.size()};
     }
     void clear() { *this = JointTables{}; }
+};
+
+// The shape tables of a world (xpbd_world_set_shapes, _set_polytopes; xpbd_shape_tables.hpp; xpbd_world_shapes.cpp), which every
+// kernel reads.  The vertex part (verts, vert_offsets) and the topology part (the ten other tables, the maxima, has_topology) are
+// each complete or absent, and they always describe the same n_shapes shapes.  Only stage_shape_tables fills one, aside, and only
+// install_shape_tables (the two setters; the multi-GPU world for its shards) moves one in, once nothing can fail any more: a
+// vertex-only set leaves no topology behind.  (Vertices alone that fit the present blocks are filled into those, with both parts
+// marked absent meanwhile.)
+struct ShapeTables : xpbd::ShapeCounts {
+    DeviceBuffer verts, vert_offsets;
+    DeviceBuffer planes, centroids, desc, face_start, face_verts, edges, radii, edge_dirs, edge_dir_id, shape_class;
+
+    xpbd::ShapeTable shapes() const { return xpbd::ShapeTable{verts.as<double>(), vert_offsets.as<uint32_t>(), n_shapes, total_verts}; }
+    xpbd::PolytopeTables tables() const
+    {
+        return xpbd::PolytopeTables{verts.as<double>(), planes.as<double>(), centroids.as<double>(), desc.as<xpbd::ShapeDesc>(),
+                                    face_start.as<uint32_t>(), face_verts.as<uint32_t>(), edges.as<uint32_t>(), radii.as<double>(),
+                                    edge_dirs.as<double>(), edge_dir_id.as<uint32_t>(), n_shapes, total_verts, max_verts, max_faces, max_face_verts,
+                                    shape_class.as<uint8_t>(), two_classes, small_max_face_verts};
+    }
+    void clear() { *this = ShapeTables{}; }
 };
 
 // The kinematic table of a world (xpbd_world_set_kinematics; xpbd_kinematic.h; xpbd_world_kinematic.cpp): what the caller handed
@@ -278,6 +300,9 @@ struct FrameSnapshot {
 struct TerrainStaging {
     DeviceBuffer xy, out;
 };
+struct NarrowphaseStaging {
+    DeviceBuffer pairs, results;
+};
 struct EditStaging {
     DeviceBuffer indices, values, list;
     DeviceBuffer owner; // xpbd_world_set_mass_properties_device: one claim word per body (xpbd_mass_edit.h)
@@ -348,29 +373,13 @@ struct xpbd_world {
     // bodies
     uint32_t n = 0;
     uint32_t stride = 0;
-    uint32_t max_shape_id = 0; // largest shape id among the uploaded bodies (xpbd_world_set_shapes re-validates against it)
+    uint32_t max_shape_id = 0; // largest shape id among the uploaded bodies (install_shape_tables re-validates against it)
     DeviceBuffer dyn, stat, shape_id, aos_staging, last_mask, trace, block_counts, contacts;
     uint32_t trace_rows = 0; // substeps recorded by the last step()
     bool stepped = false;
 
-    // shapes
-    DeviceBuffer shape_verts, shape_offsets;
-    uint32_t n_shapes = 0, total_verts = 0;
-
-    // extension: polytope topology for the body-body narrowphase
-    DeviceBuffer planes, centroids, shape_desc, face_start, face_verts, edges, pair_buf, manifold_buf;
-    DeviceBuffer shape_radii, edge_dirs, edge_dir_id, shape_class;
-    uint32_t two_classes = 0, small_max_face_verts = 0;
-    bool has_topology = false;
-    uint32_t max_verts = 0, max_faces = 0, max_face_verts = 0;
-    xpbd::PolytopeTables tables() const
-    {
-        return xpbd::PolytopeTables{shape_verts.as<double>(), planes.as<double>(), centroids.as<double>(),
-                                    shape_desc.as<xpbd::ShapeDesc>(), face_start.as<uint32_t>(),
-                                    face_verts.as<uint32_t>(), edges.as<uint32_t>(), shape_radii.as<double>(),
-                                    edge_dirs.as<double>(), edge_dir_id.as<uint32_t>(), n_shapes, total_verts, max_verts, max_faces, max_face_verts,
-                                    shape_class.as<uint8_t>(), two_classes, small_max_face_verts};
-    }
+    // shapes: vertices, and the polytope topology for the body-body narrowphase (extension)
+    ShapeTables geom;
 
     // extension: contact pipeline (XPBD_MODE_CONTACTS)
     double contact_pad = 0.02;
@@ -388,6 +397,8 @@ struct xpbd_world {
     std::vector<uint8_t> stat_shape_seen; // [n_shapes] a body of the shape has been uploaded: its row of stat_shape_host is set
     Broadphase bp;
     NarrowphaseSchedule np;
+    // the one-shot narrowphases (xpbd_world_narrowphase, _edge_axes_separation, _narrowphase_gjk): the caller's pairs and their results
+    NarrowphaseStaging np_staging;
     ContactReport report;
     // re-planning a shard on the device (xpbd::repack_bodies, download_records, halo_cell_keys): the new world in AoS, its
     // shape ids, the source map, incoming records; the cell keys and the gathered records
@@ -481,10 +492,6 @@ struct xpbd_world {
     xpbd::BodyArrays arrays() const
     {
         return xpbd::BodyArrays{dyn.as<double>(), stat.as<double>(), shape_id.as<uint32_t>(), stride, n};
-    }
-    xpbd::ShapeTable shapes() const
-    {
-        return xpbd::ShapeTable{shape_verts.as<double>(), shape_offsets.as<uint32_t>(), n_shapes, total_verts};
     }
 
     // Nothing queued may outlive the members: the stream is waited for first.  Then, in this order, the pinned blocks and the

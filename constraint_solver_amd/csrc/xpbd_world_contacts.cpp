@@ -107,7 +107,7 @@ int build_neighbours_enqueue(xpbd_world *w, double dt)
     }
     const xpbd::BodyArrays b = w->arrays();
     xpbd::ContactBuffers c = w->contact_buffers();
-    XPBD_HIP_TRY(xpbd::launch_bounds_and_cells(b, w->tables(), w->shape_radii.as<double>(), dt, w->contact_pad, c,
+    XPBD_HIP_TRY(xpbd::launch_bounds_and_cells(b, w->geom.tables(), w->geom.radii.as<double>(), dt, w->contact_pad, c,
                                                w->stream));
     XPBD_HIP_TRY(xpbd::launch_build_buckets(b, c, w->stream, w->inert_bodies()));
     XPBD_HIP_TRY(xpbd::launch_neighbour_count(b, c, w->stream, w->inert_bodies()));
@@ -132,7 +132,7 @@ int build_neighbours_collect(xpbd_world *w)
     xpbd::ContactBuffers c = w->contact_buffers();
     w->bp.n_entries = w->bp.totals->entries;
     w->bp.n_pairs = w->bp.totals->pairs;
-    w->np.choose(w->bp.totals->stats[0], w->two_classes);
+    w->np.choose(w->bp.totals->stats[0], w->geom.two_classes);
     if (!w->np.sat_counters.ptr) {
         XPBD_HIP_TRY(w->np.sat_counters.reserve(2 * xpbd::kSurvivorCounters * 4));
         XPBD_HIP_TRY(hipMemsetAsync(w->np.sat_counters.ptr, 0, 2 * xpbd::kSurvivorCounters * 4, w->stream));
@@ -177,10 +177,10 @@ int narrowphase_contacts(xpbd_world *w, const xpbd::BodyArrays &b, const xpbd::C
         // part of the narrowphase's semantics (og_gjk_epa_cached of the oracle), not a schedule
         w->np.gjk_scratch.axis_cache = w->np.gjk_axis_cache.as<double>();
         w->np.gjk_scratch.codes = c.pair_codes;
-        XPBD_HIP_TRY(xpbd::launch_gjk_epa_pairs(b, w->tables(), c.rec, c.pairs, w->bp.n_pairs, nullptr, c.manifolds,
+        XPBD_HIP_TRY(xpbd::launch_gjk_epa_pairs(b, w->geom.tables(), c.rec, c.pairs, w->bp.n_pairs, nullptr, c.manifolds,
                                                 w->np.gjk_scratch, true, &w->np.sat_scratch, w->stream));
     } else {
-        XPBD_HIP_TRY(xpbd::launch_sat_contact_pairs(b, w->tables(), c, w->bp.n_pairs, w->np.sat_two_pass ? &w->np.sat_scratch : nullptr,
+        XPBD_HIP_TRY(xpbd::launch_sat_contact_pairs(b, w->geom.tables(), c, w->bp.n_pairs, w->np.sat_two_pass ? &w->np.sat_scratch : nullptr,
                                                     w->stream, w->np.sat_scratch.cache_edge_axes /* = a dense scene, see below */));
     }
     w->np.stats_pair_substeps += w->bp.n_pairs;
@@ -203,7 +203,7 @@ int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_ro
         XPBD_HIP_TRY(hipMemcpyAsync(w->rs_start.ptr, b.dyn + (size_t)xpbd::D_VEL * b.stride, (size_t)6 * b.stride * 8, hipMemcpyDeviceToDevice,
                                     w->stream));
     }
-    XPBD_HIP_TRY(xpbd::launch_integrate_ground(b, w->shapes(), h, c, w->last_mask.as<uint32_t>(), trace, trace_row, w->stream, awake));
+    XPBD_HIP_TRY(xpbd::launch_integrate_ground(b, w->geom.shapes(), h, c, w->last_mask.as<uint32_t>(), trace, trace_row, w->stream, awake));
     if (int rc = narrowphase_contacts(w, b, c))
         return rc;
     XPBD_HIP_TRY(xpbd::launch_joint_extras(h, c, w->stream));
@@ -212,7 +212,7 @@ int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_ro
         return XPBD_OK;
     }
     XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, w->dyn_alt.as<double>(), h, c, w->stream, awake));
-    XPBD_HIP_TRY(xpbd::launch_restitution(b, w->dyn_alt.as<double>(), w->rs_start.as<double>(), w->shapes(), c, w->last_mask.as<uint32_t>(),
+    XPBD_HIP_TRY(xpbd::launch_restitution(b, w->dyn_alt.as<double>(), w->rs_start.as<double>(), w->geom.shapes(), c, w->last_mask.as<uint32_t>(),
                                           w->stream, awake));
     return XPBD_OK;
 }
@@ -224,7 +224,7 @@ int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_ro
 // the last.
 int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_t *trace)
 {
-    if (!w->has_topology)
+    if (!w->geom.has_topology)
         return set_error(XPBD_E_INVALID, "XPBD_MODE_CONTACTS needs xpbd_world_set_polytopes");
     // Kinematic bodies (include/xpbd.h, "KINEMATIC bodies"): the overwrite of substep 0 comes before the broadphase, whose bounding
     // spheres then include the scripted travel; with sleeping on it also tells who is MOVING in this frame.  No table: nothing.
@@ -259,7 +259,7 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
                 return rc;
         return w->sleep.on ? w->sleep.frame_end(w) : XPBD_OK;
     }
-    XPBD_HIP_TRY(xpbd::launch_integrate_ground(w->arrays(), w->shapes(), h, w->contact_buffers(0), w->last_mask.as<uint32_t>(), trace, 0,
+    XPBD_HIP_TRY(xpbd::launch_integrate_ground(w->arrays(), w->geom.shapes(), h, w->contact_buffers(0), w->last_mask.as<uint32_t>(), trace, 0,
                                                w->stream, awake));
     for (uint32_t k = 0; k < substeps; ++k) {
         const xpbd::BodyArrays b = w->arrays();
@@ -269,7 +269,7 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         XPBD_HIP_TRY(xpbd::launch_joint_extras(h, c, w->stream));
         if (k + 1 < substeps) {
             const xpbd::ContactBuffers next = w->contact_buffers((k + 1u) & 1u);
-            XPBD_HIP_TRY(xpbd::launch_pair_solve_integrate_ground(b, w->shapes(), h, c, next.rec, w->last_mask.as<uint32_t>(), trace,
+            XPBD_HIP_TRY(xpbd::launch_pair_solve_integrate_ground(b, w->geom.shapes(), h, c, next.rec, w->last_mask.as<uint32_t>(), trace,
                                                                   k + 1, w->stream, awake));
         } else {
             XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream, awake));
@@ -283,7 +283,7 @@ namespace xpbd {
 
 int halo_frame_begin_enqueue(xpbd_world *w, double dt) noexcept
 {
-    if (!w || w->mode != XPBD_MODE_CONTACTS || !w->has_topology)
+    if (!w || w->mode != XPBD_MODE_CONTACTS || !w->geom.has_topology)
         return set_error(XPBD_E_INVALID, "halo_frame_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
     if (w->n == 0)
         return XPBD_OK;
@@ -294,7 +294,7 @@ int halo_frame_begin_enqueue(xpbd_world *w, double dt) noexcept
 
 int halo_frame_begin_collect(xpbd_world *w, double h) noexcept
 {
-    if (!w || w->mode != XPBD_MODE_CONTACTS || !w->has_topology)
+    if (!w || w->mode != XPBD_MODE_CONTACTS || !w->geom.has_topology)
         return set_error(XPBD_E_INVALID, "halo_frame_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
     if (w->n == 0)
         return XPBD_OK;
@@ -302,7 +302,7 @@ int halo_frame_begin_collect(xpbd_world *w, double h) noexcept
         return rc;
     if (int rc = build_neighbours_collect(w))
         return rc;
-    XPBD_HIP_TRY(launch_integrate_ground(w->arrays(), w->shapes(), h, w->contact_buffers(0), w->last_mask.as<uint32_t>(), nullptr, 0, w->stream));
+    XPBD_HIP_TRY(launch_integrate_ground(w->arrays(), w->geom.shapes(), h, w->contact_buffers(0), w->last_mask.as<uint32_t>(), nullptr, 0, w->stream));
     w->stepped = true;
     return XPBD_OK;
 }
@@ -360,7 +360,7 @@ int halo_pair_solve(xpbd_world *w, double h, uint32_t k, bool last, const BodySu
     if (last)
         XPBD_HIP_TRY(launch_pair_solve_derive(b, b.dyn, h, c, w->stream, subset));
     else
-        XPBD_HIP_TRY(launch_pair_solve_integrate_ground(b, w->shapes(), h, c, w->contact_buffers((k + 1u) & 1u).rec, w->last_mask.as<uint32_t>(),
+        XPBD_HIP_TRY(launch_pair_solve_integrate_ground(b, w->geom.shapes(), h, c, w->contact_buffers((k + 1u) & 1u).rec, w->last_mask.as<uint32_t>(),
                                                         nullptr, k + 1, w->stream, subset));
     return XPBD_OK;
 }
@@ -409,7 +409,7 @@ int halo_substep_ghosts(xpbd_world *w, double h, uint32_t k, bool last, const Ha
     subset.count = l.n_ghosts;
     subset.import_buf = l.recv;
     subset.import_rows = l.ghost_rows;
-    XPBD_HIP_TRY(launch_integrate_ground(b, w->shapes(), h, w->contact_buffers((k + 1u) & 1u), w->last_mask.as<uint32_t>(), nullptr, k + 1, w->stream,
+    XPBD_HIP_TRY(launch_integrate_ground(b, w->geom.shapes(), h, w->contact_buffers((k + 1u) & 1u), w->last_mask.as<uint32_t>(), nullptr, k + 1, w->stream,
                                          subset));
     return XPBD_OK;
 }
@@ -424,7 +424,7 @@ try {
     static_assert(sizeof(xpbd_manifold) == sizeof(xpbd::Manifold), "xpbd_manifold must mirror xpbd::Manifold");
     if (!w || (n_pairs && (!pairs || !out)))
         return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase: NULL argument");
-    if (!w->has_topology)
+    if (!w->geom.has_topology)
         return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase: call xpbd_world_set_polytopes first");
     for (uint32_t k = 0; k < 2 * n_pairs; ++k)
         if (pairs[k] >= w->n)
@@ -434,15 +434,15 @@ try {
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    XPBD_HIP_TRY(w->pair_buf.reserve((size_t)n_pairs * 8));
-    XPBD_HIP_TRY(w->manifold_buf.reserve((size_t)n_pairs * sizeof(xpbd::Manifold)));
-    XPBD_HIP_TRY(hipMemcpyAsync(w->pair_buf.ptr, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, w->stream));
-    XPBD_HIP_TRY(hipMemsetAsync(w->manifold_buf.ptr, 0, (size_t)n_pairs * sizeof(xpbd::Manifold), w->stream));
+    XPBD_HIP_TRY(w->np_staging.pairs.reserve((size_t)n_pairs * 8));
+    XPBD_HIP_TRY(w->np_staging.results.reserve((size_t)n_pairs * sizeof(xpbd::Manifold)));
+    XPBD_HIP_TRY(hipMemcpyAsync(w->np_staging.pairs.ptr, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, w->stream));
+    XPBD_HIP_TRY(hipMemsetAsync(w->np_staging.results.ptr, 0, (size_t)n_pairs * sizeof(xpbd::Manifold), w->stream));
     XPBD_HIP_TRY(w->cb_rec.reserve((size_t)xpbd::kRecDoubles * w->stride * 8));
     XPBD_HIP_TRY(xpbd::launch_body_frames(w->arrays(), w->cb_rec.as<double>(), w->stream));
-    XPBD_HIP_TRY(xpbd::launch_sat_pairs(w->arrays(), w->tables(), w->cb_rec.as<double>(), w->pair_buf.as<uint32_t>(),
-                                        n_pairs, w->manifold_buf.as<xpbd::Manifold>(), w->stream));
-    XPBD_HIP_TRY(hipMemcpyAsync(out, w->manifold_buf.ptr, (size_t)n_pairs * sizeof(xpbd::Manifold),
+    XPBD_HIP_TRY(xpbd::launch_sat_pairs(w->arrays(), w->geom.tables(), w->cb_rec.as<double>(), w->np_staging.pairs.as<uint32_t>(),
+                                        n_pairs, w->np_staging.results.as<xpbd::Manifold>(), w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(out, w->np_staging.results.ptr, (size_t)n_pairs * sizeof(xpbd::Manifold),
                                 hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
@@ -453,7 +453,7 @@ try {
     static_assert(sizeof(xpbd_edge_query) == sizeof(xpbd::EdgeQuery), "xpbd_edge_query must mirror xpbd::EdgeQuery");
     if (!w || (n_pairs && (!pairs || !out)))
         return set_error(XPBD_E_INVALID, "xpbd_world_edge_axes_separation: NULL argument");
-    if (!w->has_topology)
+    if (!w->geom.has_topology)
         return set_error(XPBD_E_INVALID, "xpbd_world_edge_axes_separation: call xpbd_world_set_polytopes first");
     for (uint32_t k = 0; k < 2 * n_pairs; ++k)
         if (pairs[k] >= w->n)
@@ -463,14 +463,14 @@ try {
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    XPBD_HIP_TRY(w->pair_buf.reserve((size_t)n_pairs * 8));
-    XPBD_HIP_TRY(w->manifold_buf.reserve((size_t)n_pairs * sizeof(xpbd::EdgeQuery)));
+    XPBD_HIP_TRY(w->np_staging.pairs.reserve((size_t)n_pairs * 8));
+    XPBD_HIP_TRY(w->np_staging.results.reserve((size_t)n_pairs * sizeof(xpbd::EdgeQuery)));
     XPBD_HIP_TRY(w->cb_rec.reserve((size_t)xpbd::kRecDoubles * w->stride * 8));
-    XPBD_HIP_TRY(hipMemcpyAsync(w->pair_buf.ptr, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(w->np_staging.pairs.ptr, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, w->stream));
     XPBD_HIP_TRY(xpbd::launch_body_frames(w->arrays(), w->cb_rec.as<double>(), w->stream));
-    XPBD_HIP_TRY(xpbd::launch_edge_axes_reference(w->arrays(), w->tables(), w->cb_rec.as<double>(), w->pair_buf.as<uint32_t>(), n_pairs,
-                                                  w->manifold_buf.as<xpbd::EdgeQuery>(), w->stream));
-    XPBD_HIP_TRY(hipMemcpyAsync(out, w->manifold_buf.ptr, (size_t)n_pairs * sizeof(xpbd::EdgeQuery), hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(xpbd::launch_edge_axes_reference(w->arrays(), w->geom.tables(), w->cb_rec.as<double>(), w->np_staging.pairs.as<uint32_t>(), n_pairs,
+                                                  w->np_staging.results.as<xpbd::EdgeQuery>(), w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(out, w->np_staging.results.ptr, (size_t)n_pairs * sizeof(xpbd::EdgeQuery), hipMemcpyDeviceToHost, w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
 } XPBD_ABI_CATCH
@@ -480,7 +480,7 @@ try {
     static_assert(sizeof(xpbd_gjk_result) == sizeof(xpbd::GjkResult), "xpbd_gjk_result must mirror xpbd::GjkResult");
     if (!w || (n_pairs && (!pairs || !out)))
         return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase_gjk: NULL argument");
-    if (!w->has_topology)
+    if (!w->geom.has_topology)
         return set_error(XPBD_E_INVALID, "xpbd_world_narrowphase_gjk: call xpbd_world_set_polytopes first");
     for (uint32_t k = 0; k < 2 * n_pairs; ++k)
         if (pairs[k] >= w->n)
@@ -490,18 +490,18 @@ try {
     if (int rc = bind_device(w))
         return rc;
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
-    XPBD_HIP_TRY(w->pair_buf.reserve((size_t)n_pairs * 8));
-    XPBD_HIP_TRY(w->manifold_buf.reserve((size_t)n_pairs * sizeof(xpbd::GjkResult)));
+    XPBD_HIP_TRY(w->np_staging.pairs.reserve((size_t)n_pairs * 8));
+    XPBD_HIP_TRY(w->np_staging.results.reserve((size_t)n_pairs * sizeof(xpbd::GjkResult)));
     XPBD_HIP_TRY(w->cb_rec.reserve((size_t)xpbd::kRecDoubles * w->stride * 8));
-    XPBD_HIP_TRY(hipMemcpyAsync(w->pair_buf.ptr, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, w->stream));
-    XPBD_HIP_TRY(hipMemsetAsync(w->manifold_buf.ptr, 0, (size_t)n_pairs * sizeof(xpbd::GjkResult), w->stream));
+    XPBD_HIP_TRY(hipMemcpyAsync(w->np_staging.pairs.ptr, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, w->stream));
+    XPBD_HIP_TRY(hipMemsetAsync(w->np_staging.results.ptr, 0, (size_t)n_pairs * sizeof(xpbd::GjkResult), w->stream));
     XPBD_HIP_TRY(xpbd::launch_body_frames(w->arrays(), w->cb_rec.as<double>(), w->stream));
     if (int rc = w->np.ensure_gjk_scratch(n_pairs, w->stream))
         return rc;
-    XPBD_HIP_TRY(xpbd::launch_gjk_epa_pairs(w->arrays(), w->tables(), w->cb_rec.as<double>(),
-                                            w->pair_buf.as<uint32_t>(), n_pairs, w->manifold_buf.as<xpbd::GjkResult>(),
+    XPBD_HIP_TRY(xpbd::launch_gjk_epa_pairs(w->arrays(), w->geom.tables(), w->cb_rec.as<double>(),
+                                            w->np_staging.pairs.as<uint32_t>(), n_pairs, w->np_staging.results.as<xpbd::GjkResult>(),
                                             nullptr, w->np.gjk_scratch, false, nullptr, w->stream));
-    XPBD_HIP_TRY(hipMemcpyAsync(out, w->manifold_buf.ptr, (size_t)n_pairs * sizeof(xpbd::GjkResult), hipMemcpyDeviceToHost,
+    XPBD_HIP_TRY(hipMemcpyAsync(out, w->np_staging.results.ptr, (size_t)n_pairs * sizeof(xpbd::GjkResult), hipMemcpyDeviceToHost,
                                 w->stream));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
     return XPBD_OK;
@@ -512,7 +512,7 @@ int xpbd_world_contacts_begin(xpbd_world *w, double dt)
 try {
     if (!w)
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: NULL world");
-    if (w->mode != XPBD_MODE_CONTACTS || !w->has_topology)
+    if (w->mode != XPBD_MODE_CONTACTS || !w->geom.has_topology)
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: needs XPBD_MODE_CONTACTS and xpbd_world_set_polytopes");
     if (w->sleep.on)
         return set_error(XPBD_E_INVALID, "xpbd_world_contacts_begin: the split API has no frame end, sleeping is on (xpbd_world_set_sleeping)");
@@ -663,7 +663,7 @@ int xpbd_world_build_neighbours(xpbd_world *w, double dt, uint32_t *n_entries_ou
 try {
     if (!w || !n_entries_out)
         return set_error(XPBD_E_INVALID, "xpbd_world_build_neighbours: NULL argument");
-    if (!w->has_topology)
+    if (!w->geom.has_topology)
         return set_error(XPBD_E_INVALID, "xpbd_world_build_neighbours: call xpbd_world_set_polytopes first");
     if (w->sleep.on) // (a broadphase applies the pending wake requests, which belongs to the start of a step)
         return set_error(XPBD_E_INVALID, "xpbd_world_build_neighbours: a broadphase outside a step, sleeping is on (xpbd_world_set_sleeping)");

@@ -69,8 +69,8 @@ int repack_bodies(xpbd_world *w, const int32_t *host_src, uint32_t n_new, const 
     }
     for (uint32_t k = 0; k < n_incoming; ++k) {
         const double sid = incoming39[(size_t)k * rec + kRigidDoubles];
-        if (!(sid >= 0.0) || sid >= (double)w->n_shapes)
-            return set_error(XPBD_E_INVALID, "xpbd::repack_bodies: incoming record %u has shape id %g of %u", k, sid, w->n_shapes);
+        if (!(sid >= 0.0) || sid >= (double)w->geom.n_shapes)
+            return set_error(XPBD_E_INVALID, "xpbd::repack_bodies: incoming record %u has shape id %g of %u", k, sid, w->geom.n_shapes);
         max_shape_id = std::max(max_shape_id, (uint32_t)sid);
     }
     if (int rc = bind_device(w))
@@ -561,14 +561,14 @@ try {
     }
     if (!aos || !shape_id)
         return set_error(XPBD_E_INVALID, "%s: NULL aos or shape_id with n_add = %u", who, n_add);
-    if (w->n_shapes == 0)
+    if (w->geom.n_shapes == 0)
         return set_error(XPBD_E_INVALID, "%s: call xpbd_world_set_shapes first", who);
     if (n_add > std::numeric_limits<uint32_t>::max() - 256u - w->n) // (the stride rounds the count up to a multiple of 256)
         return set_error(XPBD_E_INVALID, "%s: %u + %u bodies exceed what xpbd_world_upload_bodies accepts", who, w->n, n_add);
     uint32_t max_shape_id = w->n ? w->max_shape_id : 0u;
     for (uint32_t i = 0; i < n_add; ++i) {
-        if (shape_id[i] >= w->n_shapes)
-            return set_error(XPBD_E_INVALID, "%s: shape_id[%u] = %u >= n_shapes %u", who, i, shape_id[i], w->n_shapes);
+        if (shape_id[i] >= w->geom.n_shapes)
+            return set_error(XPBD_E_INVALID, "%s: shape_id[%u] = %u >= n_shapes %u", who, i, shape_id[i], w->geom.n_shapes);
         max_shape_id = shape_id[i] > max_shape_id ? shape_id[i] : max_shape_id;
     }
     XPBD_TRY(bind_device(w));

@@ -55,7 +55,7 @@ int raycast_enqueue(xpbd_world *w, const xpbd_ray *dev_rays, uint32_t n_rays, ui
     const QuerySizes q = query_scratch_bytes(w->n, n_rays, brute);
     XPBD_HIP_TRY(w->query.reserve(q, 0, 0, 0, w->stream));
     const RayFilter filter{masked_filter(w, masked), mask, masked ? 1u : 0u};
-    XPBD_HIP_TRY(launch_raycast(w->arrays(), w->tables(), dev_global_id, filter, dev_rays, n_rays, brute, w->query.view(q.table_size), dev_hits,
+    XPBD_HIP_TRY(launch_raycast(w->arrays(), w->geom.tables(), dev_global_id, filter, dev_rays, n_rays, brute, w->query.view(q.table_size), dev_hits,
                                 w->stream, query_terrain(w, flags), (flags & XPBD_RAYCAST_BRUTE_FORCE) != 0));
     return XPBD_OK;
 }
@@ -83,7 +83,7 @@ int overlap_enqueue(xpbd_world *w, const xpbd_overlap_query *dev_queries, uint32
     QueryScratch scratch;
     XPBD_TRY(group_scratch(w, n_queries, brute, scratch));
     const bool masked = (flags & XPBD_OVERLAP_MASKED) != 0;
-    XPBD_HIP_TRY(launch_overlap(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute, scratch,
+    XPBD_HIP_TRY(launch_overlap(w->arrays(), w->geom.tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute, scratch,
                                 dev_offsets, dev_hits, cap, w->stream, query_terrain(w, flags)));
     return XPBD_OK;
 }
@@ -127,7 +127,7 @@ int sweep_enqueue(xpbd_world *w, const xpbd_sweep *dev_sweeps, uint32_t n_sweeps
     QueryScratch scratch;
     XPBD_TRY(group_scratch(w, n_sweeps, brute, scratch));
     const bool masked = (flags & XPBD_SWEEP_MASKED) != 0;
-    XPBD_HIP_TRY(launch_sweep(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_sweeps, n_sweeps, masked, brute, scratch,
+    XPBD_HIP_TRY(launch_sweep(w->arrays(), w->geom.tables(), dev_global_id, masked_filter(w, masked), dev_sweeps, n_sweeps, masked, brute, scratch,
                               dev_hits, w->stream, query_terrain(w, flags), (flags & XPBD_SWEEP_BRUTE_FORCE) != 0));
     return XPBD_OK;
 }
@@ -150,7 +150,7 @@ int distance_enqueue(xpbd_world *w, const xpbd_distance_query *dev_queries, uint
     QueryScratch scratch;
     XPBD_TRY(group_scratch(w, n_queries, brute, scratch));
     const bool masked = (flags & XPBD_DISTANCE_MASKED) != 0;
-    XPBD_HIP_TRY(launch_distance(w->arrays(), w->tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute, scratch,
+    XPBD_HIP_TRY(launch_distance(w->arrays(), w->geom.tables(), dev_global_id, masked_filter(w, masked), dev_queries, n_queries, masked, brute, scratch,
                                  dev_hits, w->stream));
     return XPBD_OK;
 }
@@ -170,7 +170,7 @@ int terrain_distance_enqueue(xpbd_world *w, const xpbd_distance_query *dev_queri
     if (int rc = bind_device(w))
         return rc;
     // (without polytopes the shape table is empty: every shape index is outside it, and only the point volume finds anything)
-    const PolytopeTables tables = w->has_topology ? w->tables() : PolytopeTables{};
+    const PolytopeTables tables = w->geom.has_topology ? w->geom.tables() : PolytopeTables{};
     XPBD_HIP_TRY(launch_terrain_distance(TerrainHeights{w->terrain, w->tr_heights.as<double>()}, tables, dev_queries, n_queries,
                                          (flags & XPBD_DISTANCE_BRUTE_FORCE) != 0, dev_hits, w->stream));
     return XPBD_OK;
@@ -194,7 +194,7 @@ int query_target(const char *who, const xpbd_world *w, xpbd::QueryTarget *target
 {
     if (!w)
         return set_error(XPBD_E_INVALID, "%s: NULL world", who);
-    *target = {w->has_topology, w->n, w->n_shapes, "xpbd_world_set_polytopes (set_shapes gives vertices only)", true, w->terrain.planes != nullptr};
+    *target = {w->geom.has_topology, w->n, w->geom.n_shapes, "xpbd_world_set_polytopes (set_shapes gives vertices only)", true, w->terrain.planes != nullptr};
     return XPBD_OK;
 }
 } // namespace
