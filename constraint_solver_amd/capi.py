@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "xpbd_world_destroy", "xpbd_world_set_shapes", "xpbd_world_upload_bodies", "xpbd_world_download_bodies",
     "xpbd_world_body_count", "xpbd_world_download_frames", "xpbd_world_step", "xpbd_world_synchronize", "xpbd_world_download_contacts",
     "xpbd_world_download_contact_masks", "xpbd_world_set_stream", "xpbd_world_get_stream", "xpbd_world_set_mode",
-    "xpbd_step_one", "xpbd_selftest_div_sqrt", "xpbd_world_set_polytopes", "xpbd_world_narrowphase",
+    "xpbd_step_one", "xpbd_selftest_div_sqrt", "xpbd_selftest_exact_math", "xpbd_world_set_polytopes", "xpbd_world_narrowphase",
     "xpbd_world_set_contact_pad", "xpbd_world_set_max_depenetration_speed", "xpbd_multi_world_set_max_depenetration_speed",
     "xpbd_world_contact_stats", "xpbd_world_build_neighbours",
     "xpbd_world_download_neighbours", "xpbd_world_contacts_begin", "xpbd_world_contacts_substep",
@@ -382,6 +382,10 @@ def hip_lib():
         L.xpbd_world_set_mode.argtypes = [C.c_void_p, C.c_uint32]
         L.xpbd_step_one.argtypes = [C.c_void_p, _f64p, C.c_uint32, C.c_double, C.c_uint32]
         L.xpbd_selftest_div_sqrt.argtypes = [C.c_int32, _f64p, _f64p, _f64p, _f64p, C.c_uint32]
+        try:
+            L.xpbd_selftest_exact_math.argtypes = [C.c_int32, _f64p, _f64p, C.c_double, C.c_uint32, _f64p, _f64p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB for an A/B measurement (scripts/)
+            pass
         L.xpbd_selftest_hbm_copy.argtypes = [C.c_int32, C.c_uint64, C.c_uint32, _f64p]
         L.xpbd_selftest_field_streams.argtypes = [C.c_int32, C.c_uint64, C.c_uint32, C.c_uint32, _f64p]
         L.xpbd_world_snapshot_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -1489,6 +1493,18 @@ def selftest_div_sqrt(a, b, device=0):
     q, s = np.empty_like(a), np.empty_like(a)
     _check(hip_lib().xpbd_selftest_div_sqrt(device, _f64(a), _f64(b), _f64(q), _f64(s), a.size))
     return q, s
+
+
+def selftest_exact_math(x, a, h, device=0):
+    """(fast, plain), each [3, n]: div_by(x, h), then s and k of sqrt_and_reciprocal(a) -- and x / h, sqrt(a), 1 / sqrt(a),
+    all computed on the GPU."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if x.shape != a.shape or x.ndim != 1:
+        raise ValueError("x and a must be one-dimensional and of one length")
+    fast, plain = np.empty((3, x.size)), np.empty((3, x.size))
+    _check(hip_lib().xpbd_selftest_exact_math(device, _f64(x), _f64(a), float(h), x.size, _f64(fast), _f64(plain)))
+    return fast, plain
 
 
 def selftest_gather(records, record_bytes, read_bytes, repeats=5, device=0):

@@ -100,4 +100,9 @@ hipError_t launch_gather_records(const void *in, double *out, uint32_t records, 
 hipError_t launch_selftest_div_sqrt(const double *a, const double *b, double *q, double *r, uint32_t n,
                                     hipStream_t stream);
 
+// Diagnostics: xpbd_exact.hpp's sequences and the plain expressions on x[i] / h and a[i]: fast and plain are [3n] each
+// (quotient, root, reciprocal of the root), all device pointers.
+hipError_t launch_selftest_exact_math(const double *x, const double *a, double h, uint32_t n, double *fast, double *plain,
+                                      hipStream_t stream);
+
 } // namespace xpbd

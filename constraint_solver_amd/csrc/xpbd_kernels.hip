@@ -269,6 +269,23 @@ __global__ void k_selftest_div_sqrt(const double *__restrict__ a, const double *
     }
 }
 
+__global__ void k_selftest_exact_math(const double *__restrict__ x, const double *__restrict__ a, exact::Divisor h, uint32_t n,
+                                      double *__restrict__ fast, double *__restrict__ plain)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        double s, k;
+        exact::sqrt_and_reciprocal(a[i], s, k);
+        fast[i] = exact::div_by(x[i], h.h, h.inv_h, h.ok != 0u);
+        fast[(size_t)n + i] = s;
+        fast[2 * (size_t)n + i] = k;
+        const double root = sqrt(a[i]);
+        plain[i] = x[i] / h.h;
+        plain[(size_t)n + i] = root;
+        plain[2 * (size_t)n + i] = 1.0 / root;
+    }
+}
+
 // Device-to-device copy kernels: the measured HBM roof the stepper's achieved bandwidth is priced against
 // (xpbd_selftest_hbm_copy reports the fastest variant).  16 bytes per lane and access; ONE element per lane with a
 // grid as large as the buffer, or grid-stride with four independent loads in flight per lane; plain or non-temporal
@@ -466,6 +483,14 @@ hipError_t launch_selftest_div_sqrt(const double *a, const double *b, double *q,
 {
     if (n)
         hipLaunchKernelGGL(k_selftest_div_sqrt, dim3((n + 255) / 256), dim3(256), 0, stream, a, b, q, r, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_selftest_exact_math(const double *x, const double *a, double h, uint32_t n, double *fast, double *plain,
+                                      hipStream_t stream)
+{
+    if (n)
+        hipLaunchKernelGGL(k_selftest_exact_math, dim3((n + 255) / 256), dim3(256), 0, stream, x, a, exact::divisor(h), n, fast, plain);
     return hipGetLastError();
 }
 

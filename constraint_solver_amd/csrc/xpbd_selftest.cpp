@@ -1,4 +1,4 @@
-// xpbd_selftest.cpp -- the device self-tests of the C ABI (division and square root, and three bandwidth probes).  They
+// xpbd_selftest.cpp -- the device self-tests of the C ABI (division and square root, the stepper's short sequences for them, and three bandwidth probes).  They
 // touch no world.
 #include <cstdint>
 
@@ -33,6 +33,30 @@ try {
     if (e == hipSuccess) e = hipMemcpy(root, d + 3 * (size_t)n, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess)
         return set_error(XPBD_E_HIP, "xpbd_selftest_div_sqrt: %s", hipGetErrorString(e));
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_selftest_exact_math(int32_t device, const double *x, const double *a, double h, uint32_t n, double *fast, double *plain)
+try {
+    if (n && (!x || !a || !fast || !plain))
+        return set_error(XPBD_E_INVALID, "xpbd_selftest_exact_math: NULL argument");
+    if (n == 0)
+        return XPBD_OK;
+    XPBD_HIP_TRY(hipSetDevice(device));
+    DeviceBuffer buf;
+    const size_t bytes = (size_t)n * 8;
+    hipError_t e = buf.reserve(8 * bytes); // x, a, fast[3n], plain[3n]
+    if (e != hipSuccess)
+        return set_error(XPBD_E_OOM, "xpbd_selftest_exact_math: %s", hipGetErrorString(e));
+    double *d = buf.as<double>();
+    double *d_fast = d + 2 * (size_t)n, *d_plain = d + 5 * (size_t)n;
+    e = hipMemcpy(d, x, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + n, a, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = xpbd::launch_selftest_exact_math(d, d + n, h, n, d_fast, d_plain, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(fast, d_fast, 3 * bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(plain, d_plain, 3 * bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return set_error(XPBD_E_HIP, "xpbd_selftest_exact_math: %s", hipGetErrorString(e));
     return XPBD_OK;
 } XPBD_ABI_CATCH
 

@@ -1,12 +1,24 @@
 // xpbd_step.hpp -- the per-body substep of solver::step (reference src/solver.rs:6-16) as device
 // functions, shared by the fused stepper (xpbd_kernels.hip) and the contact pipeline
 // (xpbd_contacts.hip; the terrain lookup also xpbd_restitution.hip and xpbd_terrain.hip).  All arithmetic keeps the
-// reference's operation order.
+// reference's operation order.  Where a square root is followed by the reciprocal of its own result (the three places
+// of a substep that normalize), both correctly rounded values come from one sequence of xpbd_exact.hpp: the same bits as
+// `sqrt` and `1.0 / s` in fewer f64 issue slots.  (The quotients by h of derive_body stay plain: DESIGN section 4.)
 #pragma once
 
 #include "xpbd_device.hpp"
+#include "xpbd_exact.hpp"
 
 namespace xpbd {
+
+// normalized(Quat) of xpbd_math.hpp, |q| and 1 / |q| from one sequence.
+__device__ __forceinline__ Quat normalized_exact(Quat q)
+{
+    const double m2 = q.s * q.s + (q.x * q.x + q.y * q.y + q.z * q.z);
+    double m, k;
+    exact::sqrt_and_reciprocal(m2, m, k);
+    return Quat{q.s * k, q.x * k, q.y * k, q.z * k};
+}
 
 // Per-body state held in registers.
 struct BodyStatic {
@@ -88,7 +100,7 @@ __device__ __forceinline__ SubstepFrames integrate_body(BodyDynamic &d, const Bo
     const Vec3 torque = s.ext_torque + d.rot * s.int_torque;
     d.ang = d.ang + (h * s.inv_inertia) * torque;
     const Quat dq = ((h * 0.5) * Quat{0.0, d.ang.x, d.ang.y, d.ang.z}) * d.rot;
-    d.rot = normalized(d.rot + dq);
+    d.rot = normalized_exact(d.rot + dq);
 
     f.cur = Frame{frame_origin(d.pos, d.rot, s.com), d.rot};
     return f;
@@ -217,8 +229,9 @@ __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_ma
 
         // solver::solve body, src/solver.rs:23-25 (distance == 0.0, src/collision.rs:30)
         const Vec3 difference = c1 - c0;                              // src/constraint.rs:13-15
-        const double current_distance = length(difference);           // src/constraint.rs:21-23
-        const Vec3 direction = difference * (1.0 / current_distance); // src/constraint.rs:17-19
+        double current_distance, inv_distance; // length(difference), src/constraint.rs:21-23, and 1.0 / it
+        exact::sqrt_and_reciprocal(length2(difference), current_distance, inv_distance);
+        const Vec3 direction = difference * inv_distance; // src/constraint.rs:17-19
         // inverse_resitance, src/constraint.rs:25-32 (reads the LIVE pose)
         const Vec3 angular_impulse = conjugate(rot) * cross(c0 - (pos + com), direction);
         const double w = inv_mass + dot(inv_inertia * angular_impulse, angular_impulse);
@@ -239,7 +252,7 @@ __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_ma
         const Vec3 arm = c0 - (pos + com);
         const Quat spin = quat_sv(0.0, cross(inv_inertia * arm, impulse));
         rot = rot + (0.5 * spin) * rot;
-        rot = normalized(rot);
+        rot = normalized_exact(rot);
     }
 }
 

@@ -496,6 +496,7 @@ extern "C" {
     pub fn xpbd_world_set_mode(w: *mut XpbdWorld, mode: u32) -> c_int;
     pub fn xpbd_step_one(rigid: *mut XpbdRigid, verts_xyz: *const f64, nverts: u32, dt: f64, substeps: u32) -> c_int;
     pub fn xpbd_selftest_div_sqrt(device: i32, a: *const f64, b: *const f64, q: *mut f64, r: *mut f64, n: u32) -> c_int;
+    pub fn xpbd_selftest_exact_math(device: i32, x: *const f64, a: *const f64, h: f64, n: u32, fast: *mut f64, plain: *mut f64) -> c_int;
     pub fn xpbd_selftest_hbm_copy(device: i32, bytes: u64, repeats: u32, gbytes_per_s: *mut f64) -> c_int;
     pub fn xpbd_selftest_field_streams(device: i32, bodies: u64, tile_major: u32, repeats: u32, gbytes_per_s: *mut f64) -> c_int;
     pub fn xpbd_selftest_gather(device: i32, records: u32, record_bytes: u32, read_bytes: u32, repeats: u32, gbytes_per_s: *mut f64) -> c_int;

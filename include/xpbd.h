@@ -1853,6 +1853,11 @@ int  xpbd_world_wake_bodies_device(xpbd_world *w, const uint32_t *dev_indices, u
  * both to be correctly rounded; the parity tests check this against the host. */
 int  xpbd_selftest_div_sqrt(int32_t device, const double *a, const double *b,
                             double *quotient, double *root, uint32_t n);
+/* Diagnostics: the stepper's two short sequences (xpbd_exact.hpp) next to the plain expressions, all evaluated on the device.
+ * fast[0..n) = div_by(x[i], h), fast[n..2n) = s and fast[2n..3n) = k of sqrt_and_reciprocal(a[i]);
+ * plain[0..n) = x[i] / h, plain[n..2n) = sqrt(a[i]), plain[2n..3n) = 1.0 / sqrt(a[i]).  The two must agree bit for bit. */
+int  xpbd_selftest_exact_math(int32_t device, const double *x, const double *a, double h, uint32_t n,
+                              double *fast /* [3n] */, double *plain /* [3n] */);
 
 /* Diagnostics: the HBM roof as this library can reach it -- a device-to-device copy of `bytes` (use far more than the
  * 256 MiB Infinity Cache) by the library's own streaming kernel, `repeats` launches timed with HIP events.
