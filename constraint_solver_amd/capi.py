@@ -74,7 +74,27 @@ ABI_SYMBOLS = [
     "xpbd_world_joint_states", "xpbd_world_joint_states_device", "xpbd_world_set_drive_targets", "xpbd_world_set_drive_targets_device",
     "xpbd_world_set_kinematics", "xpbd_world_set_kinematic_targets", "xpbd_world_set_kinematic_targets_device", "xpbd_world_kinematic_count",
     "xpbd_world_set_mass_properties", "xpbd_world_set_mass_properties_device", "xpbd_world_get_mass_properties",
+    "xpbd_world_set_damping", "xpbd_world_get_damping", "xpbd_world_set_joint_damping",
 ]
+
+# damping (include/xpbd.h, "DAMPING"): xpbd_body_damping, 32 bytes, and xpbd_joint_damping, 24 bytes
+BODY_DAMPING_DTYPE = np.dtype([("linear", np.float64), ("angular", np.float64), ("max_linear_speed", np.float64), ("max_angular_speed", np.float64)])
+JOINT_DAMPING_DTYPE = np.dtype([("joint", np.uint32), ("reserved", np.uint32), ("linear", np.float64), ("angular", np.float64)])
+
+
+def body_damping(n, linear=0.0, angular=0.0, max_linear_speed=np.inf, max_angular_speed=np.inf):
+    """n BODY_DAMPING_DTYPE rows; every argument a scalar or an array of n.  The defaults are the default row."""
+    rows = np.zeros(n, dtype=BODY_DAMPING_DTYPE)
+    rows["linear"], rows["angular"], rows["max_linear_speed"], rows["max_angular_speed"] = linear, angular, max_linear_speed, max_angular_speed
+    return rows
+
+
+def joint_damping(joint, linear=0.0, angular=0.0):
+    """JOINT_DAMPING_DTYPE records for the joints `joint` (an array); linear, angular: scalars or arrays of the same length."""
+    joint = np.asarray(joint, dtype=np.uint32).reshape(-1)
+    out = np.zeros(joint.size, dtype=JOINT_DAMPING_DTYPE)
+    out["joint"], out["linear"], out["angular"] = joint, linear, angular
+    return out
 
 # mass edits (include/xpbd.h, "MASS properties of resident bodies"): the flags, and the doubles of a row
 MASS_INVERSE, MASS_DIRECT, MASS_KEEP_FRAME = 0, 1, 0x100
@@ -536,6 +556,12 @@ def hip_lib():
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         try:
+            L.xpbd_world_set_damping.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_get_damping.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_set_joint_damping.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
             L.xpbd_world_set_kinematics.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
             L.xpbd_world_set_kinematic_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
             L.xpbd_world_set_kinematic_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
@@ -748,6 +774,24 @@ class World:
         e = None if restitution is None else np.ascontiguousarray(restitution, dtype=np.float64).reshape(-1)
         _check(hip_lib().xpbd_world_set_restitution(self._h, None if e is None else e.ctypes.data, 0 if e is None else e.size,
                                                     ground_restitution, bounce_threshold))
+
+    def set_damping(self, rows=None):
+        """rows: BODY_DAMPING_DTYPE records (see body_damping()), one per body, or None for the default row everywhere (extension;
+        XPBD_MODE_CONTACTS; include/xpbd.h, "DAMPING")."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=BODY_DAMPING_DTYPE).reshape(-1)
+        _check(hip_lib().xpbd_world_set_damping(self._h, None if r is None else r.ctypes.data, 0 if r is None else r.size))
+
+    def get_damping(self):
+        """The rows in force, one BODY_DAMPING_DTYPE record per body."""
+        rows = np.zeros(self.n, dtype=BODY_DAMPING_DTYPE)
+        _check(hip_lib().xpbd_world_get_damping(self._h, rows.ctypes.data if rows.size else None, rows.size))
+        return rows
+
+    def set_joint_damping(self, dampers=None):
+        """Replaces the joint dampers: JOINT_DAMPING_DTYPE records (see joint_damping()), at most one per joint of the last
+        set_joints; None or an empty list clears them."""
+        d = np.zeros(0, dtype=JOINT_DAMPING_DTYPE) if dampers is None else np.ascontiguousarray(dampers, dtype=JOINT_DAMPING_DTYPE).reshape(-1)
+        _check(hip_lib().xpbd_world_set_joint_damping(self._h, d.ctypes.data if d.size else None, d.size))
 
     def set_terrain(self, heights=None, origin=(0.0, 0.0), cell=(1.0, 1.0)):
         """heights: (ny, nx) array, heights[iy, ix] at world (origin[0] + ix * cell[0], origin[1] + iy * cell[1]), the ground

@@ -56,6 +56,52 @@ int check_materials(const char *who, const xpbd_material *materials, uint32_t n)
     return XPBD_OK;
 }
 
+int DampingTarget::rows(const char *who, const xpbd_body_damping *rows, uint32_t n, bool *any_set) const
+{
+    static_assert(sizeof(xpbd_body_damping) == 32, "xpbd_body_damping is {linear, angular, max_linear_speed, max_angular_speed}");
+    if (int rc = check_per_body(who, "rows", rows, n, n_bodies))
+        return rc;
+    bool any = false;
+    for (uint32_t i = 0; rows && i < n; ++i) {
+        const xpbd_body_damping &r = rows[i];
+        if (!(r.linear >= 0.0 && std::isfinite(r.linear)))
+            return set_error(XPBD_E_INVALID, "%s: rows[%u].linear = %g (must be >= 0 and finite)", who, i, r.linear);
+        if (!(r.angular >= 0.0 && std::isfinite(r.angular)))
+            return set_error(XPBD_E_INVALID, "%s: rows[%u].angular = %g (must be >= 0 and finite)", who, i, r.angular);
+        if (!(r.max_linear_speed > 0.0))
+            return set_error(XPBD_E_INVALID, "%s: rows[%u].max_linear_speed = %g (must be > 0, +inf allowed)", who, i, r.max_linear_speed);
+        if (!(r.max_angular_speed > 0.0))
+            return set_error(XPBD_E_INVALID, "%s: rows[%u].max_angular_speed = %g (must be > 0, +inf allowed)", who, i, r.max_angular_speed);
+        any = any || r.linear > 0.0 || r.angular > 0.0 || std::isfinite(r.max_linear_speed) || std::isfinite(r.max_angular_speed);
+    }
+    if (any_set)
+        *any_set = any;
+    return XPBD_OK;
+}
+
+int DampingTarget::dampers(const char *who, const xpbd_joint_damping *list, uint32_t n) const
+{
+    static_assert(sizeof(xpbd_joint_damping) == 24, "xpbd_joint_damping is {joint, reserved, linear, angular}");
+    if (n && !list)
+        return set_error(XPBD_E_INVALID, "%s: NULL list with n = %u", who, n);
+    std::vector<uint8_t> seen(n_joints, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        const xpbd_joint_damping &d = list[k];
+        if (d.joint >= n_joints)
+            return set_error(XPBD_E_INVALID, "%s: list[%u] names joint %u of %u", who, k, d.joint, n_joints);
+        if (d.reserved != 0)
+            return set_error(XPBD_E_INVALID, "%s: list[%u]: reserved must be 0", who, k);
+        if (seen[d.joint])
+            return set_error(XPBD_E_INVALID, "%s: list[%u] is a second entry for joint %u", who, k, d.joint);
+        seen[d.joint] = 1;
+        if (!(d.linear >= 0.0 && std::isfinite(d.linear)))
+            return set_error(XPBD_E_INVALID, "%s: list[%u].linear = %g (must be >= 0 and finite)", who, k, d.linear);
+        if (!(d.angular >= 0.0 && std::isfinite(d.angular)))
+            return set_error(XPBD_E_INVALID, "%s: list[%u].angular = %g (must be >= 0 and finite)", who, k, d.angular);
+    }
+    return XPBD_OK;
+}
+
 int check_joint_limits(const char *who, const xpbd_joint *joints, uint32_t n_joints, const xpbd_joint_limit *limits, uint32_t n_limits)
 {
     if (n_limits && !limits)

@@ -62,6 +62,16 @@ int check_impulses(const char *who, const xpbd_impulse *list, uint32_t n, uint32
 // world: what the call is made on, and its check -- a NULL count, a NULL record buffer with a nonzero cap, unknown flags, both
 // flags, a world without bodies, and, without XPBD_ISLANDS_NO_CONTACTS, a report that xpbd_world_contact_report_counts would
 // refuse (reporting off; no frame).
+// ... of the damping calls (include/xpbd.h, "DAMPING"), after the caller has dealt with a NULL world and the world's mode: what
+// the call is made on, and its checks.  rows, of xpbd_world_set_damping: check_per_body's rules, then a drag coefficient that is
+// negative, NaN or infinite, a cap that is <= 0 or NaN (+inf allowed); any_set (NULL: not wanted): does a row differ from the
+// default {0, 0, +inf, +inf}?  dampers, of xpbd_world_set_joint_damping: a NULL list with n > 0, a joint index out of range, two
+// entries for one joint, a nonzero `reserved`, a coefficient that is negative, NaN or infinite.
+struct DampingTarget {
+    uint32_t n_bodies, n_joints;
+    int rows(const char *who, const xpbd_body_damping *rows, uint32_t n, bool *any_set = nullptr) const;
+    int dampers(const char *who, const xpbd_joint_damping *list, uint32_t n) const;
+};
 struct IslandsTarget {
     uint32_t n_bodies;
     bool report_on, report_frame;

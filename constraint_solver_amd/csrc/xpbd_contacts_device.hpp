@@ -10,6 +10,7 @@
 //   generalized_inverse_mass                                  x          x
 //   shape_lds_bytes, stage_shape_tables                       x          x
 //
+// xpbd_damping.hip (stage 7, not split from xpbd_contacts.hip) uses kBlock, blocks_for and generalized_inverse_mass.
 // xpbd_scan.hip includes nothing of this: it serves units that are no part of the pipeline and keeps a kBlock of its own.
 // What a single unit uses is in that unit: cell_hash ... for_each_neighbour (broadphase); min_mu, ground_mu, subset_body,
 // store_row, load_row, PairBody ... block_add_stats, the joint helpers (contacts); VelBody, load_vel_body, max_restitution

@@ -33,6 +33,11 @@ JointSet remap_joint_set(const JointSet &in, const uint32_t *old_to_new, uint32_
             out.drives.push_back(d);
             out.drives.back().joint = joint_old_to_new[d.joint];
         }
+    for (const xpbd_joint_damping &d : in.damping)
+        if (d.joint < joint_old_to_new.size() && joint_old_to_new[d.joint] != kRemoved) {
+            out.damping.push_back(d);
+            out.damping.back().joint = joint_old_to_new[d.joint];
+        }
     return out;
 }
 
@@ -141,6 +146,23 @@ ExtraTables build_extra_tables(const std::vector<xpbd_joint> &joints, const std:
         std::memcpy(&t.items[cursor[d.joint]++], &d, sizeof d);
     }
     return t;
+}
+
+std::vector<double> build_joint_damping_table(const std::vector<xpbd_joint_damping> &list, uint32_t n_joints)
+{
+    bool any = false;
+    for (const xpbd_joint_damping &d : list)
+        any = any || (d.joint < n_joints && (d.linear != 0.0 || d.angular != 0.0));
+    std::vector<double> table;
+    if (!any)
+        return table;
+    table.assign((size_t)2 * n_joints, 0.0);
+    for (const xpbd_joint_damping &d : list)
+        if (d.joint < n_joints) {
+            table[(size_t)2 * d.joint] = d.linear;
+            table[(size_t)2 * d.joint + 1] = d.angular;
+        }
+    return table;
 }
 
 } // namespace xpbd

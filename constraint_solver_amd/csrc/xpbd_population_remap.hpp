@@ -11,17 +11,18 @@ namespace xpbd {
 
 constexpr uint32_t kRemoved = 0xFFFFFFFFu; // XPBD_NO_HIT: what a removed body or a dropped joint maps to
 
-// The joints, limits (all kinds) and drives of a world, as the caller handed them to the three setters.
+// The joints, limits (all kinds), drives and dampers of a world, as the caller handed them to the four setters.
 struct JointSet {
     std::vector<xpbd_joint> joints;
     std::vector<xpbd_joint_limit> limits;
     std::vector<xpbd_joint_drive> drives;
+    std::vector<xpbd_joint_damping> damping; // (last: the aggregate initialisers of three vectors stay valid)
 };
 
 // The joint set after the bodies were re-indexed by old_to_new ([n_bodies]; kRemoved: the body is gone).  A joint whose two ends
 // both survive stays with body_a / body_b re-indexed (a joint given with body_a > body_b keeps that orientation: the map is
-// monotone); a joint with a removed end is dropped with its limits and drives.  Surviving joints, limits and drives keep their
-// relative order; limits and drives name the new joint numbers.  joint_old_to_new: [joints.size()], kRemoved for a dropped one.
+// monotone); a joint with a removed end is dropped with its limits, drives and damper.  Surviving joints, limits, drives and
+// dampers keep their relative order and name the new joint numbers.  joint_old_to_new: [joints.size()], kRemoved for a dropped one.
 JointSet remap_joint_set(const JointSet &in, const uint32_t *old_to_new, uint32_t n_bodies, std::vector<uint32_t> &joint_old_to_new);
 
 // The kinematic table (include/xpbd.h, "KINEMATIC bodies") after the same re-index: the entries of surviving bodies with their
@@ -63,5 +64,9 @@ struct ExtraTables {
 };
 ExtraTables build_extra_tables(const std::vector<xpbd_joint> &joints, const std::vector<xpbd_joint_limit> &slide_limits,
                                const std::vector<xpbd_joint_drive> &drives, uint32_t n_bodies);
+
+// The table of xpbd_world_set_joint_damping as stage 7 reads it: (mu_l, mu_a) of every joint, zeros for a joint that is not
+// listed.  Empty when no entry has a nonzero coefficient: the pass is then off.
+std::vector<double> build_joint_damping_table(const std::vector<xpbd_joint_damping> &list, uint32_t n_joints);
 
 } // namespace xpbd

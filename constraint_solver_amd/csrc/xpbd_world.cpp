@@ -72,6 +72,7 @@ void drop_body_settings(xpbd_world *w)
     w->materials.clear();
     w->restitution.clear();
     w->kinematics.clear();
+    w->damping.clear();
 }
 
 // The world takes a new set of n_new bodies (xpbd_world_upload_bodies, xpbd::repack_bodies; device bound, stream idle): room for
@@ -116,7 +117,7 @@ int upload_table(DeviceBuffer &table, const void *values, size_t bytes)
 }
 
 namespace {
-// ---- the joint tables (JointTables): nothing but these three allocates or copies one ----------------------------------------
+// ---- the joint tables (JointTables): nothing but these four allocates or copies one -----------------------------------------
 // Each fills a fresh part from the host tables of xpbd_population_remap.hpp; the caller moves it in once nothing can fail any
 // more, so a failed call leaves the previous tables in force.  An empty part is left without blocks, so every table that is
 // copied has at least one element.  The device is bound.
@@ -171,9 +172,20 @@ int stage_extras(const xpbd::ExtraTables &t, uint32_t n_joints, hipStream_t stre
     return XPBD_OK;
 }
 
+// Stage 7's (mu_l, mu_a) per joint; a list without a nonzero coefficient leaves the part empty, which is what turns the pass off.
+int stage_joint_damping(const std::vector<xpbd_joint_damping> &list, uint32_t n_joints, JointTables::Damping &out)
+{
+    const std::vector<double> table = xpbd::build_joint_damping_table(list, n_joints);
+    if (table.empty())
+        return XPBD_OK;
+    XPBD_TRY(stage_upload(out.table, table.data(), table.size() * sizeof(double)));
+    out.n = n_joints;
+    return XPBD_OK;
+}
+
 } // namespace
 
-// All three from `set` in a world of n_bodies bodies: what the three setters, called in turn, would build.
+// All four from `set` in a world of n_bodies bodies: what the four setters, called in turn, would build.
 int stage_joint_tables(xpbd::JointSet set, uint32_t n_bodies, hipStream_t stream, JointTables &out)
 {
     out.clear();
@@ -184,6 +196,7 @@ int stage_joint_tables(xpbd::JointSet set, uint32_t n_bodies, hipStream_t stream
     XPBD_TRY(stage_csr(set.joints.data(), n_joints, xpbd::build_joint_csr(set.joints.data(), n_joints, n_bodies), n_bodies, out.csr));
     XPBD_TRY(stage_limits(lt, out.limits));
     XPBD_TRY(stage_extras(xpbd::build_extra_tables(set.joints, lt.slide, set.drives, n_bodies), n_joints, stream, out.extras));
+    XPBD_TRY(stage_joint_damping(set.damping, n_joints, out.damping));
     out.set = std::move(set);
     out.slide_limits = std::move(lt.slide);
     return XPBD_OK;
@@ -484,8 +497,8 @@ try {
     return xpbd_world_download_bodies(cache.w, rigid, 1);
 } XPBD_ABI_CATCH
 
-// The three joint setters: validate, stage the affected parts aside (stage_csr / stage_limits / stage_extras), then commit by
-// moves that cannot fail.  Queued substeps may still read the present tables: the stream is waited for first.
+// The four joint setters: validate, stage the affected parts aside (stage_csr / stage_limits / stage_extras /
+// stage_joint_damping), then commit by moves that cannot fail.  Queued substeps may still read the present tables: the stream is waited for first.
 int xpbd_world_set_joints(xpbd_world *w, const xpbd_joint *joints, uint32_t n_joints)
 try {
     if (!w || (n_joints && !joints))
@@ -493,7 +506,7 @@ try {
     if (n_joints && w->mode != XPBD_MODE_CONTACTS) // only the contact pipeline projects joints: do not accept and ignore them
         return set_error(XPBD_E_INVALID, "xpbd_world_set_joints: joints need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
     XPBD_TRY(xpbd::check_joints("xpbd_world_set_joints", joints, n_joints, w->n));
-    xpbd::JointSet set; // (limits and drives name joints by index: new joints drop them)
+    xpbd::JointSet set; // (limits, drives and dampers name joints by index: new joints drop them)
     set.joints.assign(joints, joints + n_joints);
     XPBD_TRY(bind_device(w));
     XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
@@ -552,6 +565,29 @@ try {
     XPBD_TRY(stage_extras(xpbd::build_extra_tables(J.set.joints, J.slide_limits, all, w->n), J.csr.n, w->stream, fresh));
     J.set.drives = std::move(all);
     J.extras = std::move(fresh); // (with targets_on_device clear: the drives are replaced)
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_set_joint_damping(xpbd_world *w, const xpbd_joint_damping *list, uint32_t n)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_damping: NULL world");
+    if (n && w->mode != XPBD_MODE_CONTACTS)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_joint_damping: joint dampers need XPBD_MODE_CONTACTS (world is in mode %u)", w->mode);
+    JointTables &J = w->joints;
+    XPBD_TRY((xpbd::DampingTarget{w->n, J.csr.n}.dampers("xpbd_world_set_joint_damping", list, n)));
+    w->sleep.wake_all(true);
+    if (n == 0 && J.set.damping.empty())
+        return XPBD_OK;
+    std::vector<xpbd_joint_damping> all(list, list + n);
+    XPBD_TRY(bind_device(w));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present table
+    JointTables::Damping fresh;
+    XPBD_TRY(stage_joint_damping(all, J.csr.n, fresh));
+    if (fresh.n) // the joint part's results: follows the stride (a population change grows it)
+        XPBD_HIP_TRY(w->dp_scratch.reserve((size_t)6 * (w->stride ? w->stride : 256u) * 8));
+    J.set.damping = std::move(all);
+    J.damping = std::move(fresh);
     return XPBD_OK;
 } XPBD_ABI_CATCH
 
@@ -641,6 +677,59 @@ try {
     w->restitution.on = true;
     w->restitution.ground = ground_restitution;
     w->restitution.bounce_threshold = bounce_threshold;
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_set_damping(xpbd_world *w, const xpbd_body_damping *rows, uint32_t n)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_set_damping: NULL world");
+    bool any = false;
+    XPBD_TRY((xpbd::DampingTarget{w->n, w->joints.csr.n}.rows("xpbd_world_set_damping", rows, n, &any)));
+    if (int rc = bind_device(w))
+        return rc;
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream)); // queued substeps may still read the present rows
+    w->sleep.wake_all(true);
+    if (!any) { // every row the default: the step runs what it ran before the call
+        w->damping.clear();
+        return XPBD_OK;
+    }
+    // SoA, field by field (xpbd_damping.h)
+    const size_t rs = at_least_one(w->n);
+    std::vector<double> values(xpbd::kDampingRowFields * rs);
+    for (uint32_t i = 0; i < n; ++i) {
+        values[0 * rs + i] = rows[i].linear;
+        values[1 * rs + i] = rows[i].angular;
+        values[2 * rs + i] = rows[i].max_linear_speed;
+        values[3 * rs + i] = rows[i].max_angular_speed;
+    }
+    XPBD_TRY(upload_table(w->dp_rows, values.data(), values.size() * sizeof(double)));
+    w->damping.on = true;
+    return XPBD_OK;
+} XPBD_ABI_CATCH
+
+int xpbd_world_get_damping(xpbd_world *w, xpbd_body_damping *rows, uint32_t n)
+try {
+    if (!w)
+        return set_error(XPBD_E_INVALID, "xpbd_world_get_damping: NULL world");
+    if (n && !rows)
+        return set_error(XPBD_E_INVALID, "xpbd_world_get_damping: NULL rows with n = %u", n);
+    if (n != w->n)
+        return set_error(XPBD_E_INVALID, "xpbd_world_get_damping: n = %u but the world holds %u bodies", n, w->n);
+    const double inf = std::numeric_limits<double>::infinity();
+    if (!w->damping.on) {
+        for (uint32_t i = 0; i < n; ++i)
+            rows[i] = xpbd_body_damping{0.0, 0.0, inf, inf};
+        return XPBD_OK;
+    }
+    if (int rc = bind_device(w))
+        return rc;
+    const size_t rs = at_least_one(w->n);
+    std::vector<double> values(xpbd::kDampingRowFields * rs);
+    XPBD_HIP_TRY(hipMemcpyAsync(values.data(), w->dp_rows.ptr, values.size() * sizeof(double), hipMemcpyDeviceToHost, w->stream));
+    XPBD_HIP_TRY(hipStreamSynchronize(w->stream));
+    for (uint32_t i = 0; i < n; ++i)
+        rows[i] = xpbd_body_damping{values[0 * rs + i], values[1 * rs + i], values[2 * rs + i], values[3 * rs + i]};
     return XPBD_OK;
 } XPBD_ABI_CATCH
 

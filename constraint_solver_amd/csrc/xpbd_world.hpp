@@ -24,6 +24,7 @@
 #include "xpbd_internal.h"
 #include "xpbd_kernels.h"
 #include "xpbd_contacts.h"
+#include "xpbd_damping.h"
 #include "xpbd_gjk.h"
 #include "xpbd_islands.h"
 #include "xpbd_joint_state.h"
@@ -54,12 +55,13 @@ inline uint32_t next_pow2(uint32_t v)
     return p;
 }
 
-// The joints of a world: what the caller handed to xpbd_world_set_joints, _set_joint_limits and _set_joint_drives, and the
-// device tables built from it in three parts, one per setter.  A part is complete or empty (count 0, no buffers); only
-// stage_csr, stage_limits and stage_extras fill one, aside, and a setter or a population change moves it in.
+// The joints of a world: what the caller handed to xpbd_world_set_joints, _set_joint_limits, _set_joint_drives and
+// _set_joint_damping, and the device tables built from it in four parts, one per setter.  A part is complete or empty (count 0,
+// no buffers); only stage_csr, stage_limits, stage_extras and stage_joint_damping fill one, aside, and a setter or a population
+// change moves it in.
 struct JointTables {
-    xpbd::JointSet set;                         // joints, limits of all kinds and drives, the caller's order (limits and drives name
-                                                // joints by index: new joints drop them; a population change re-indexes all three)
+    xpbd::JointSet set;                         // joints, limits of all kinds, drives and dampers, the caller's order (the last three
+                                                // name joints by index: new joints drop them; a population change re-indexes all four)
     std::vector<xpbd_joint_limit> slide_limits; // the XPBD_LIMIT_SLIDE ones among set.limits
     struct Csr { // the joints and the CSR body -> joints
         uint32_t n = 0;
@@ -80,6 +82,10 @@ struct JointTables {
         std::vector<uint32_t> drive_item_host;
         bool targets_on_device = false;
     } extras;
+    struct Damping { // (mu_l, mu_a) of every joint for stage 7 (xpbd_damping.h); empty unless a listed coefficient is nonzero
+        uint32_t n = 0;
+        DeviceBuffer table;
+    } damping;
 
     void fill(xpbd::ContactBuffers &c) const // (an empty part holds no buffer: NULL)
     {
@@ -405,7 +411,7 @@ struct xpbd_world {
     ReplanStaging replan;
     // state at the start of a frame (xpbd::frame_snapshot_save / _restore): the 13 dynamic fields and the contact masks
     FrameSnapshot snapshot;
-    // Body-indexed settings: each names bodies (or the joints between them) by index, so a new set of bodies clears all five
+    // Body-indexed settings: each names bodies (or the joints between them) by index, so a new set of bodies clears all six
     // (adopt_body_count).  Values whose clear() restores the defaults; the per-body device tables stay allocated beside theirs.
     JointTables joints;
     struct Filters { // xpbd_world_set_collision_filters: group, mask per body (on), XPBD_FILTER_* flags
@@ -431,6 +437,20 @@ struct xpbd_world {
         void clear() { *this = Restitution{}; }
     } restitution;
     DeviceBuffer rs_restitution, rs_start;
+    // xpbd_world_set_damping: the rows of every body, SoA ([4][at_least_one(n)]: xpbd_damping.h).  on: a row differs from the
+    // default -- the step then runs the unfused schedule with stage 7 behind every substep, as it does while a joint has a damper
+    // (joints.damping); with neither a world enqueues what it enqueued before.  dp_scratch: the joint part's results, [6][stride]
+    struct BodyDamping {
+        bool on = false;
+        void clear() { *this = BodyDamping{}; }
+    } damping;
+    DeviceBuffer dp_rows, dp_scratch;
+    bool damping_on() const { return damping.on || joints.damping.n != 0; }
+    xpbd::DampingTables damping_tables() const
+    {
+        return xpbd::DampingTables{damping.on ? dp_rows.as<double>() : nullptr, at_least_one(n), joints.damping.n ? joints.damping.table.as<double2>() : nullptr,
+                                   dp_scratch.as<double>()};
+    }
     // xpbd_world_set_kinematics: the fixed bodies that move on a script.  Non-empty, the step runs the unfused schedule with the
     // velocity overwrite before every integrate stage; empty, a world holds and enqueues nothing of it
     KinematicBodies kinematics;
@@ -544,7 +564,7 @@ void reset_stat_records(xpbd_world *w, bool start_over, uint32_t n);
 void take_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id);
 void drop_body_settings(xpbd_world *w);
 int adopt_body_count(xpbd_world *w, uint32_t n_new, uint32_t max_shape_id);
-// Staged uploads: a block of its own / moved over `table` once nothing can fail; all three joint tables from a JointSet.
+// Staged uploads: a block of its own / moved over `table` once nothing can fail; all four joint tables from a JointSet.
 int stage_upload(DeviceBuffer &fresh, const void *values, size_t bytes);
 int upload_table(DeviceBuffer &table, const void *values, size_t bytes);
 int stage_joint_tables(xpbd::JointSet set, uint32_t n_bodies, hipStream_t stream, JointTables &out);

@@ -209,11 +209,14 @@ int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_ro
     XPBD_HIP_TRY(xpbd::launch_joint_extras(h, c, w->stream));
     if (!c.restitution) {
         XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream, awake));
-        return XPBD_OK;
+    } else {
+        XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, w->dyn_alt.as<double>(), h, c, w->stream, awake));
+        XPBD_HIP_TRY(xpbd::launch_restitution(b, w->dyn_alt.as<double>(), w->rs_start.as<double>(), w->geom.shapes(), c, w->last_mask.as<uint32_t>(),
+                                              w->stream, awake));
     }
-    XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, w->dyn_alt.as<double>(), h, c, w->stream, awake));
-    XPBD_HIP_TRY(xpbd::launch_restitution(b, w->dyn_alt.as<double>(), w->rs_start.as<double>(), w->geom.shapes(), c, w->last_mask.as<uint32_t>(),
-                                          w->stream, awake));
+    // stage 7 (include/xpbd.h, "DAMPING") on the end-of-substep state, which is in the SoA arrays either way
+    if (w->damping_on())
+        XPBD_HIP_TRY(xpbd::launch_damping(b, w->damping_tables(), h, c, w->stream, awake));
     return XPBD_OK;
 }
 
@@ -252,8 +255,8 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         awake.skip = w->sleep.asleep(w);
     }
     // the velocity pass sits where the fused kernel below has the next substep's integrate; and that kernel has no terrain form
-    // ... and the kinematic overwrite goes between the substeps, on the SoA state the fused kernel does not write
-    if (w->restitution.on || w->terrain.planes || kinematic) {
+    // ... and the kinematic overwrite goes between the substeps, on the SoA state the fused kernel does not write, as does stage 7
+    if (w->restitution.on || w->terrain.planes || kinematic || w->damping_on()) {
         for (uint32_t k = 0; k < substeps; ++k)
             if (int rc = substep_contacts(w, h, trace, k, awake, kinematic && k ? substeps - k : 0u))
                 return rc;

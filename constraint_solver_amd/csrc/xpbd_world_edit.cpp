@@ -364,7 +364,7 @@ namespace {
 // and launch has succeeded; a stage that is dropped frees its blocks and leaves the previous population in force.
 struct PopulationStage {
     uint32_t n = 0, stride = 0;
-    DeviceBuffer dyn, stat, shape_id, last_mask, aos_staging, filters, friction, restitution, dyn_alt, rs_start;
+    DeviceBuffer dyn, stat, shape_id, last_mask, aos_staging, filters, friction, restitution, dyn_alt, rs_start, damping, dp_scratch;
     JointTables joints;
     KinematicBodies kinematics; // (a removal only: the table as it stands stays where nobody leaves)
     bool kinematics_staged = false;
@@ -419,6 +419,16 @@ int stage_bodies(xpbd_world *w, const uint32_t *dev_src, uint32_t n_keep, const 
         if (w->rs_start.bytes < (size_t)6 * stride * 8)
             XPBD_HIP_TRY(st.rs_start.reserve((size_t)6 * stride * 8));
     }
+    if (w->damping.on) { // the four fields of the rows, each a table of doubles with its own default
+        const size_t rs_old = at_least_one(w->n), rs_new = at_least_one(n_new);
+        const double defaults[xpbd::kDampingRowFields] = {0.0, 0.0, std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()};
+        XPBD_HIP_TRY(st.damping.reserve(xpbd::kDampingRowFields * rs_new * 8));
+        for (uint32_t f = 0; f < xpbd::kDampingRowFields; ++f)
+            XPBD_HIP_TRY(xpbd::launch_population_gather_doubles(w->dp_rows.as<double>() + f * rs_old, st.damping.as<double>() + f * rs_new, dev_src, n_keep,
+                                                                n_new, defaults[f], w->stream));
+    }
+    if (w->joints.damping.n && w->dp_scratch.bytes < (size_t)6 * stride * 8) // the joint part's scratch follows the stride
+        XPBD_HIP_TRY(st.dp_scratch.reserve((size_t)6 * stride * 8));
     return XPBD_OK;
 }
 
@@ -439,6 +449,8 @@ void commit_population(xpbd_world *w, PopulationStage &st, uint32_t max_shape_id
     take(w->rs_restitution, st.restitution);
     take(w->dyn_alt, st.dyn_alt);
     take(w->rs_start, st.rs_start);
+    take(w->dp_rows, st.damping);
+    take(w->dp_scratch, st.dp_scratch);
     w->joints = std::move(st.joints);
     if (st.kinematics_staged)
         w->kinematics = std::move(st.kinematics);

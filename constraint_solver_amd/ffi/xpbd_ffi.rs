@@ -112,6 +112,25 @@ pub struct XpbdKinematic {
     pub angular: [f64; 4],
 }
 
+/// EXTENSION: damping row of a body and damper of a joint (see xpbd.h, "DAMPING").  The default row is
+/// {0.0, 0.0, f64::INFINITY, f64::INFINITY}.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct XpbdBodyDamping {
+    pub linear: f64,
+    pub angular: f64,
+    pub max_linear_speed: f64,
+    pub max_angular_speed: f64,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct XpbdJointDamping {
+    pub joint: u32,
+    pub reserved: u32, // must be 0
+    pub linear: f64,
+    pub angular: f64,
+}
+
 /// EXTENSION: drive of a joint (XPBD_DRIVE_ANGLE = 0, XPBD_DRIVE_ANGULAR_VELOCITY = 1, XPBD_DRIVE_POSITION = 2,
 /// XPBD_DRIVE_VELOCITY = 3; see xpbd.h, "SLIDERS and joint DRIVES").
 #[repr(C)]
@@ -573,6 +592,10 @@ extern "C" {
         -> c_int;
     pub fn xpbd_world_set_restitution(w: *mut XpbdWorld, restitution: *const f64, n: u32, ground_restitution: f64, bounce_threshold: f64)
         -> c_int;
+    // damping: rows NULL with n = 0 = the default row for every body; the joint list replaces the previous one (n = 0 clears)
+    pub fn xpbd_world_set_damping(w: *mut XpbdWorld, rows: *const XpbdBodyDamping, n: u32) -> c_int;
+    pub fn xpbd_world_get_damping(w: *mut XpbdWorld, rows: *mut XpbdBodyDamping, n: u32) -> c_int;
+    pub fn xpbd_world_set_joint_damping(w: *mut XpbdWorld, list: *const XpbdJointDamping, n: u32) -> c_int;
     // terrain: hf NULL = back to the plane z = 0; sample_terrain takes host arrays and waits (normal_xyz may be NULL)
     pub fn xpbd_world_set_terrain(w: *mut XpbdWorld, hf: *const XpbdHeightfield) -> c_int;
     pub fn xpbd_world_sample_terrain(w: *mut XpbdWorld, xy: *const f64, n: u32, height: *mut f64, normal_xyz: *mut f64) -> c_int;

@@ -574,6 +574,22 @@ class BatchWorld {
         check(xpbd_world_set_restitution(w_, restitution.empty() ? nullptr : restitution.data(), (uint32_t)restitution.size(), ground_restitution,
                                          bounce_threshold));
     }
+    // damping (include/xpbd.h, "DAMPING"): one row per body (empty: the default row everywhere), read back with get_damping; and
+    // the dampers of the joints set last (empty: none).  Upload resets both, set_joints clears the dampers.
+    void set_damping(const std::vector<xpbd_body_damping> &rows)
+    {
+        check(xpbd_world_set_damping(w_, rows.empty() ? nullptr : rows.data(), (uint32_t)rows.size()));
+    }
+    std::vector<xpbd_body_damping> get_damping()
+    {
+        std::vector<xpbd_body_damping> rows(xpbd_world_body_count(w_));
+        check(xpbd_world_get_damping(w_, rows.empty() ? nullptr : rows.data(), (uint32_t)rows.size()));
+        return rows;
+    }
+    void set_joint_damping(const std::vector<xpbd_joint_damping> &dampers)
+    {
+        check(xpbd_world_set_joint_damping(w_, dampers.empty() ? nullptr : dampers.data(), (uint32_t)dampers.size()));
+    }
     // heightfield terrain (include/xpbd.h, "TERRAIN"): ny rows of nx heights, heights[iy * nx + ix] at (origin_x + ix * cell_x,
     // origin_y + iy * cell_y), the ground of XPBD_MODE_CONTACTS in place of the plane z = 0.  World-level: upload keeps it.
     void set_terrain(const std::vector<double> &heights, uint32_t nx, uint32_t ny, double origin_x, double origin_y, double cell_x, double cell_y)

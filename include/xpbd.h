@@ -636,6 +636,79 @@ int  xpbd_world_set_materials(xpbd_world *w, const xpbd_material *materials, uin
 int  xpbd_world_set_restitution(xpbd_world *w, const double *restitution, uint32_t n, double ground_restitution,
                                 double bounce_threshold);
 
+/* DAMPING (EXTENSION): body drag, speed caps and joint dampers, a velocity pass after derive.
+ * Every body has a row {linear c_l, angular c_a, max_linear_speed, max_angular_speed}: drag coefficients >= 0 (1/s, finite,
+ * default 0) and caps > 0 (m/s, rad/s; +inf allowed and the default: no cap).  A joint of the last xpbd_world_set_joints may
+ * have a damper {linear mu_l, angular mu_a}, both >= 0 (1/s, finite; a joint that is not listed has 0, 0): with a compliant
+ * ANGLE / POSITION drive as the spring this is the D-term of a PD controller (Mueller et al. 2020, 3.5).
+ * Where: XPBD_MODE_CONTACTS only, as stage 7 of every substep, after stage 6 (RESTITUTION) or, with restitution off, after
+ * Rigid::derive, under both narrowphases; xpbd_world_step and xpbd_world_contacts_substep run it alike.  It changes the two
+ * velocities of every body that is awake (SLEEPING) and not FIXED (inverse_mass and all nine inverse_inertia entries == 0, the
+ * islands' definition) and nothing else: a fixed body -- a kinematic one included -- keeps its velocities to the bit, a
+ * sleeper stays frozen, and no position or rotation is touched.
+ * Notation.  h: the substep; x, q, v, w: a body's position, rotation, velocity and angular velocity as stage 6 left them;
+ * c = x + center_of_mass.  u(p), W(p, n), dot, length and "an impulse P at p" are those of RESTITUTION, at these values:
+ *   u(p) = v + cross(w, p - c)      W(p, n) = inverse_mass + dot(inverse_inertia * a, a),  a = conjugate(q) * cross(p - c, n)
+ *   P at p changes the body's velocities by   dv = P * inverse_mass,   dw = cross(inverse_inertia * (p - c), P)
+ * Every / is a correctly rounded division and every length a correctly rounded sqrt, nothing is contracted, and a reciprocal
+ * is formed first and then multiplied where the text writes x * (1.0 / y).
+ * 1. Joint dampers, Jacobi over the joints in the convention of the position pass: every body reads x, q, v, w of ALL bodies
+ *    as stage 6 left them (nobody sees a neighbour's stage-7 result) and walks its joints in ascending joint index.  For joint
+ *    j with mu_l, mu_a not both 0 and ends a, b: p_a, p_b are the world anchors as the joint pass forms them (Rigid::frame() of
+ *    the end at x, q, times the anchor), and for each of the two coefficients  k = (mu * h < 1.0) ? mu * h : 1.0.
+ *      linear (mu_l > 0):   d = u_b(p_b) - u_a(p_a), len = length(d); no term if len == 0.  n = d * (1.0 / len),
+ *        Wsum = W_a(p_a, n) + W_b(p_b, n); no term unless Wsum > 0.  lambda = (k_l * len) / Wsum.  The term changes a by the
+ *        impulse P = lambda * n at p_a and b by the impulse (-lambda) * n at p_b (dv and dw as above).
+ *      angular (mu_a > 0), on the SAME stage-6 velocities (not on the linear term's result):  d = w_b - w_a, len = length(d);
+ *        no term if len == 0.  n = d * (1.0 / len), Wang = dot(inverse_inertia_a * n_a, n_a) + dot(inverse_inertia_b * n_b, n_b)
+ *        with n_a = conjugate(q_a) * n, n_b = conjugate(q_b) * n (the angular w of the limits); no term unless Wang > 0.
+ *        lambda = (k_a * len) / Wang.  The term changes a by  dw = q_a * (inverse_inertia_a * (conjugate(q_a) * (lambda * n)))
+ *        and b by  dw = q_b * (inverse_inertia_b * (conjugate(q_b) * ((-lambda) * n))).
+ *    The joint's ENTRY for a body is (dv, dw), each the sum, started from 0, of the changes its terms make to that body, the
+ *    linear term's first; a joint with no term makes no entry.  A body adds the entries of its joints, each sum started from 0,
+ *    and with count = the number of entries as a double, nonzero:  v = v + dv / count,  w = w + dw / count.
+ *    Both ends of a joint evaluate the same expressions on the same values, so a term's two impulses are opposite and of one
+ *    size; the division by count is per body, so where the two ends' counts differ the impulses they APPLY differ, as in the
+ *    position pass (the damper then removes less relative velocity than k asks for, never more).
+ * 2. Drag, implicit and unconditionally stable:  s_l = 1.0 / (1.0 + h * c_l),  v = v * s_l  per component; likewise w with
+ *    s_a = 1.0 / (1.0 + h * c_a).  c == 0 gives s == 1.0, which leaves every bit.  After S substeps a free body's velocity is
+ *    v0 multiplied S times by s; while (S + 1) h c <= 4 / 3 it exceeds v0 * exp(-c S h) by at most S (h c)^2 / 2, relative
+ *    (tests/test_damping_model.py derives it).
+ * 3. Caps:  m = length(v);  if (m > max_linear_speed) v = v * (max_linear_speed / m);  likewise w with max_angular_speed.
+ *    +inf never fires; afterwards length(v) <= cap up to the two roundings per component.
+ * Off means off: the pass is on -- and the step then runs the unfused schedule, as with restitution -- only while some body
+ * row differs from the default or the joint list holds a nonzero coefficient.  Otherwise the step launches exactly what it
+ * launched before; a call of either setter with all defaults turns the pass off again.
+ * xpbd_world_set_damping: rows == NULL with n == 0 gives every body the default row; otherwise n must equal
+ * xpbd_world_body_count, the caller's order.  xpbd_world_get_damping returns the rows in force (n = the body count).
+ * xpbd_world_set_joint_damping replaces the whole list (n == 0 clears it); at most one entry per joint.
+ * Lifetime.  The rows are a body-indexed setting like materials and restitution: xpbd_world_upload_bodies resets them,
+ * xpbd_world_remove_bodies(_device) keeps the survivors' rows, xpbd_world_add_bodies gives the new bodies the default row; mass
+ * edits, history push / restore and the joint setters leave them alone.  The joint list names joints by index like limits and
+ * drives: xpbd_world_set_joints and xpbd_world_upload_bodies clear it, xpbd_world_set_joint_limits, _set_joint_drives and
+ * _set_drive_targets leave it alone, a population change re-indexes it with the joints.  With sleeping on both setters wake
+ * every body.  XPBD_MODE_FUSED / _PER_SUBSTEP accept xpbd_world_set_damping and ignore the values.
+ * XPBD_E_INVALID (the previous values stay in force): a NULL world; NULL rows / list with n > 0; n not equal to the body count
+ * (set_damping with rows, get_damping); a negative, NaN or infinite coefficient; a cap that is <= 0 or NaN;
+ * xpbd_world_set_joint_damping with n > 0 on a world not in XPBD_MODE_CONTACTS; a joint index out of range; two entries for
+ * one joint; reserved != 0.  After a failed call (XPBD_E_OOM, XPBD_E_HIP) the previous values are still in force.
+ * Not here: the multi-GPU world (a ghost's post-derive velocity is not its owner's: restitution's reason); editing rows in
+ * place or on the device; the pinned reference modes; drives on ball joints; joint reactions; sleeping of part of a group. */
+typedef struct xpbd_body_damping {   /* 32 bytes */
+    double linear;             /* c_l >= 0, 1/s, default 0 */
+    double angular;            /* c_a >= 0, 1/s, default 0 */
+    double max_linear_speed;   /* > 0, +inf allowed = default: no cap (m/s) */
+    double max_angular_speed;  /* > 0, +inf allowed = default: no cap (rad/s) */
+} xpbd_body_damping;
+int  xpbd_world_set_damping(xpbd_world *w, const xpbd_body_damping *rows, uint32_t n);   /* NULL, 0: all defaults */
+int  xpbd_world_get_damping(xpbd_world *w, xpbd_body_damping *rows, uint32_t n);
+typedef struct xpbd_joint_damping {  /* 24 bytes */
+    uint32_t joint, reserved;  /* index into the list of the last xpbd_world_set_joints; reserved must be 0 */
+    double   linear;           /* mu_l >= 0, 1/s */
+    double   angular;          /* mu_a >= 0, 1/s */
+} xpbd_joint_damping;
+int  xpbd_world_set_joint_damping(xpbd_world *w, const xpbd_joint_damping *list, uint32_t n);   /* whole list; n == 0 clears */
+
 /* TERRAIN (EXTENSION): a heightfield as the ground of the contact pipeline, in place of the reference's plane z = 0.
  * A grid of nx * ny heights over the world's x, y plane; every cell is split along its (0,0)-(1,1) diagonal into two triangles,
  * and the ground under a point is the PLANE of the triangle above or below it.  Ground contacts stay vertex against plane, at
