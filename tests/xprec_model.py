@@ -22,10 +22,10 @@ F64_MIN_NORMAL = 2.0 ** -1022
 
 class Num:
     """The scalar type: `conv` turns an f64 array into model scalars exactly, `sqrt` is the type's square root, `atan2` its
-    two-argument arc tangent (the angular joint limits)."""
+    two-argument arc tangent (the angular joint limits), `tan` its tangent (the kinematic overwrite)."""
 
-    def __init__(self, name, conv, sqrt, to_f64, const, atan2=np.arctan2):
-        self.name, self.conv, self.sqrt, self.to_f64, self.const, self.atan2 = name, conv, sqrt, to_f64, const, atan2
+    def __init__(self, name, conv, sqrt, to_f64, const, atan2=np.arctan2, tan=np.tan):
+        self.name, self.conv, self.sqrt, self.to_f64, self.const, self.atan2, self.tan = name, conv, sqrt, to_f64, const, atan2, tan
 
 
 def longdouble():
@@ -48,7 +48,7 @@ def mp(digits=40):
     back = np.frompyfunc(float, 1, 1)
     return Num("mpmath%d" % digits, lambda a: conv(np.asarray(a, dtype=np.float64)).astype(object),
                np.frompyfunc(ctx.sqrt, 1, 1), lambda a: back(np.asarray(a, dtype=object)).astype(np.float64), mpf,
-               np.frompyfunc(ctx.atan2, 2, 1))
+               np.frompyfunc(ctx.atan2, 2, 1), np.frompyfunc(ctx.tan, 1, 1))
 
 
 def native():

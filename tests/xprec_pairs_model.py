@@ -11,6 +11,9 @@ constraint.rs:6-37, rigid.rs:113-123; they follow neither tests/joint_limit_mode
 Stage 6 (bounce) and the terrain (xprec_model.terrain_lookup, xprec_model.ground) are read from include/xpbd.h's sections
 "RESTITUTION" and "TERRAIN" alone; tests/restitution_model.py, tests/terrain_model.py, xpbd_step.hpp, xpbd_contacts.hip and
 xpbd_restitution.hip were not read for them.
+Stage 0 (kinematic_velocities, the overwrite before integrate) and stage 7 (damp) are read from include/xpbd.h's sections
+"KINEMATIC bodies" and "DAMPING" alone; tests/damping_model.py, tests/kinematic_model.py, xpbd_damping.hip, xpbd_kinematic.hip
+and xpbd_world_contacts.cpp were not read for them.
 
 Vectors are arrays (3, k) of model scalars as in xprec_model.py.  Reference lines are jim-ec/constraint_solver src/*.rs.
 """
@@ -43,6 +46,13 @@ BOUNCE_MUTATIONS = ("e_smaller_side", "vn0_post_derive", "threshold_on_vn", "arm
                     "ground_before_pairs", "ground_reads_pre_ground", "impulse_arm_in_rest_space", "triangles_swapped",
                     "target_vertical", "d_unnormalised", "plane_beyond_field", "bounce_normal_vertical",
                     "bounce_lookup_at_integrated")
+# wrong readings of stage 7 (xpbd.h, "DAMPING") and of the kinematic overwrite ("KINEMATIC bodies"); the table of
+# test_xprec_damping_oracle.py names a scene per member
+DAMPING_MUTATIONS = ("drag_explicit", "caps_before_drag", "drag_before_dampers", "stage7_before_stage6", "angular_on_linear_result",
+                     "neighbour_stage7_velocities", "count_is_terms", "damper_entries_summed", "k_unclamped", "damper_arm_without_com",
+                     "wang_unrotated", "anchors_at_integrated", "fixed_body_damped", "cap_per_component", "second_end_same_sign")
+KINEMATIC_MUTATIONS = ("dq_conjugate_first", "dq_not_negated", "full_angle", "r_counted_up", "overwrite_after_integrate",
+                       "p_frame_origin", "v0_before_overwrite", "velocity_once_per_frame")
 SWEEPS = 4                                                               # XPBD_RESTITUTION_SWEEPS
 JOINT_DISTANCE, JOINT_HINGE, JOINT_SLIDER = 0, 1, 2                      # XPBD_JOINT_*
 LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST, LIMIT_SLIDE = 0, 1, 2, 3          # XPBD_LIMIT_*
@@ -778,9 +788,271 @@ def bounce(num, s, pose, velocities, start_velocities, manifolds, mask, vert, h,
     return vel, ang, info
 
 
+def is_fixed(s):
+    """FIXED (xpbd.h, the islands' definition): inverse_mass and all nine inverse_inertia entries == 0.  (n,) bool."""
+    zero = np.array([bool(x == 0) for x in s["inverse_mass"]])
+    M = s["inverse_inertia"]
+    for c in range(3):
+        for r in range(3):
+            zero &= np.array([bool(x == 0) for x in M[c, r]])
+    return zero
+
+
+def kinematic_velocities(num, s, pos, rot, entries, h, r, mutation=None, substep_index=0):
+    """Stage 0: include/xpbd.h, "KINEMATIC bodies", the overwrite before the integrate stage of a substep with `r` substeps
+    left, written from that prose alone.  pos, rot: (3, n), (4, n) model scalars, the bodies' position and rotation FIELDS (what
+    a download shows, not Rigid::frame()); entries: records with the fields of xpbd_kinematic; h in model scalars.
+      POSE      velocity = (p_t - p) / (r h);  dq = q_t * conjugate(q), negated if dq.s < 0;  m = |vec(dq)|;  m == 0: angular
+                velocity 0;  else half = atan2(m, dq.s), angular velocity = vec(dq) * ((2 / h) * tan(half / r) / m).
+      VELOCITY  velocity = linear, angular velocity = angular[0..2], before every substep.
+    Returns ({body: (velocity (3,), angular velocity (3,))}, info); info per body (inf / False without an entry):
+    kin_flip_margin |dq.s| (the negation jumps at 0), kin_tan_margin |pi / 2 - half / r| (tan's pole; half / r <= pi / 2 always,
+    with equality only at r = 1 and dq.s == 0) and kin_zero (m == 0), and kin_mode (-1 without an entry).
+    substep_index: k, read by two of the wrong readings only (`r` counted as k + 1; VELOCITY asserted at k == 0 only)."""
+    assert mutation is None or mutation in KINEMATIC_MUTATIONS
+    n = pos.shape[1]
+    com = s["center_of_mass"]
+    info = {"kin_flip_margin": np.full(n, np.inf), "kin_tan_margin": np.full(n, np.inf), "kin_zero": np.zeros(n, dtype=bool),
+            "kin_mode": np.full(n, -1, dtype=np.int64), "kin_negated": np.zeros(n, dtype=bool)}
+    out = {}
+    one = h * 0 + 1
+    left = substep_index + 1 if mutation == "r_counted_up" else r
+    pi = num.atan2(one, one) * 4
+    for e in entries:
+        b, mode = int(e["body"]), int(e["mode"])
+        info["kin_mode"][b] = mode
+        linear = num.conv(np.asarray(e["linear"], dtype=np.float64))
+        angular = num.conv(np.asarray(e["angular"], dtype=np.float64))
+        if mode == 1:                                                        # XPBD_KINEMATIC_VELOCITY
+            if mutation == "velocity_once_per_frame" and substep_index > 0:
+                continue
+            out[b] = (linear, angular[:3])
+            continue
+        assert mode == 0                                                     # XPBD_KINEMATIC_POSE
+        p, q = pos[:, b], rot[:, b]
+        if mutation == "p_frame_origin":
+            p = p + com[:, b] + qrot(q, -com[:, b])
+        v = (linear - p) / (h * left)
+        dq = qmul(conj(q), angular) if mutation == "dq_conjugate_first" else qmul(angular, conj(q))
+        info["kin_flip_margin"][b] = abs(float(num.to_f64(np.array([dq[0]]))[0]))
+        if dq[0] < 0 and mutation != "dq_not_negated":
+            dq = -dq
+            info["kin_negated"][b] = True
+        m = num.sqrt(dot(dq[1:], dq[1:]))
+        if m == 0:
+            info["kin_zero"][b] = True
+            out[b] = (v, dq[1:] * 0)
+            continue
+        half = num.atan2(m, dq[0])
+        if mutation == "full_angle":
+            half = half * 2
+        info["kin_tan_margin"][b] = abs(float(num.to_f64(np.array([pi / 2 - half / left]))[0]))
+        out[b] = (v, dq[1:] * ((one * 2 / h) * num.tan(half / left) / m))
+    return out, info
+
+
+def damp(num, s, pose, velocities, joints, rows, joint_damping, h, mutation=None, integrated=None):
+    """Stage 7: include/xpbd.h, "DAMPING", steps 1 to 3, written from that prose alone.  pose = (x, q), velocities = (v, w):
+    (3 | 4, n) model scalars as stage 6 left them (derive's with stage 6 off); joints: records of xpbd_joint; rows: records of
+    xpbd_body_damping, one per body, or None (every row the default); joint_damping: records of xpbd_joint_damping or None; h in
+    model scalars.  A FIXED body keeps its velocities; nothing else is touched.
+      1. dampers  Jacobi: every term of every joint is evaluated on (x, q, v, w) of ALL bodies as given; joints in ascending
+                  index.  c = x + center_of_mass, p_a, p_b = Rigid::frame() at (x, q) times the anchor, k = mu h < 1 ? mu h : 1.
+                  linear (mu_l > 0): d = u_b(p_b) - u_a(p_a), u(p) = v + w x (p - c); len = |d|, no term at 0; n = d (1 / len);
+                  Wsum = W_a(p_a, n) + W_b(p_b, n), W = inverse_mass + (I^-1 a) . a, a = q^-1 ((p - c) x n); no term unless
+                  Wsum > 0; lambda = k len / Wsum; +lambda n at p_a on a, -lambda n at p_b on b: dv = P inverse_mass,
+                  dw = (I^-1 (p - c)) x P.  angular (mu_a > 0), on the SAME velocities: d = w_b - w_a, n = d (1 / len),
+                  Wang = (I_a^-1 n_a) . n_a + (I_b^-1 n_b) . n_b, n_a = q_a^-1 n; lambda = k len / Wang; a turns by
+                  q_a (I_a^-1 (q_a^-1 (lambda n))), b by the same with -lambda.  A joint's entry for a body is the sum of its
+                  terms' changes, the linear one first; no term, no entry.  v += sum of entries / number of entries.
+      2. drag     v = v * (1 / (1 + h c_l)), w likewise with c_a.
+      3. caps     m = |v|; if m > cap: v = v * (cap / m); likewise w.
+    Continuity.  The clamp of k and drag are continuous, and Wsum > 0 fails only where both ends are fixed, exactly: none changes
+    anything discretely.  A cap that fires scales by cap / m, which is 1 at the boundary: continuous, but the cases file takes
+    cap_margin in (0, TAU] out all the same; a term's direction d / len is not continuous at len == 0 (damper_cond).
+    Returns (v, w, info); info per body: n_damper_entries, n_damper_terms, damper_cond (smallest len h of a term of one of its
+    joints, metres or radians; inf without), cap_margin (smallest |m - cap| h over its two caps; inf for +inf), cap_fired_linear,
+    cap_fired_angular, n_damper_fixed_end (its entries from a joint whose other end is fixed), the set `damping_seen` and the
+    list `damper_terms` of (joint, "linear" | "angular", k, len) in f64."""
+    assert mutation is None or mutation in DAMPING_MUTATIONS
+    sqrt = num.sqrt
+    im, M, com = s["inverse_mass"], s["inverse_inertia"], s["center_of_mass"]
+    pos, rot = pose
+    vel, ang = velocities
+    a_pos, a_rot = integrated if mutation == "anchors_at_integrated" else (pos, rot)
+    n = pos.shape[1]
+    fixed = is_fixed(s)
+    one = h * 0 + 1
+    info = {"n_damper_entries": np.zeros(n, dtype=np.int64), "n_damper_terms": np.zeros(n, dtype=np.int64),
+            "damper_cond": np.full(n, np.inf), "cap_margin": np.full(n, np.inf), "cap_fired_linear": np.zeros(n, dtype=bool),
+            "cap_fired_angular": np.zeros(n, dtype=bool), "n_damper_fixed_end": np.zeros(n, dtype=np.int64)}
+    seen = set()
+    terms_of = {}
+
+    def as_float(x):
+        return float(num.to_f64(np.array([x]))[0])
+
+    def const(x):
+        return num.conv(np.array([float(x)]))[0]
+
+    coefficient = {}
+    for d in ([] if joint_damping is None else joint_damping):
+        coefficient[int(d["joint"])] = (float(d["linear"]), float(d["angular"]))
+
+    def share(mu):
+        k = const(mu) * h
+        if mutation == "k_unclamped":
+            return k
+        return k if k < 1 else one
+
+    def centre(b):
+        return a_pos[:, b] if mutation == "damper_arm_without_com" else a_pos[:, b] + com[:, b]
+
+    def anchor(b, local):
+        frame_p = a_pos[:, b] + com[:, b] + qrot(a_rot[:, b], -com[:, b])            # Rigid::frame()
+        return frame_apply(frame_p, a_rot[:, b], num.conv(np.asarray(local, dtype=np.float64)))
+
+    def joint_entries(j, jt, v, w):
+        """The two ends' entries ((dv, dw) or None, terms) of joint j on the velocities (v, w)."""
+        mu_l, mu_a = coefficient.get(j, (0.0, 0.0))
+        a, b = int(jt["body_a"]), int(jt["body_b"])
+        dv = {a: vel[:, 0] * 0, b: vel[:, 0] * 0}
+        dw = {a: vel[:, 0] * 0, b: vel[:, 0] * 0}
+        terms, kinds = 0, []
+        if mu_l == 0 and mu_a == 0:
+            return a, b, None, 0, kinds
+        wa, wb = w[:, a], w[:, b]
+        if mu_l > 0:
+            p_a, p_b = anchor(a, jt["anchor_a"]), anchor(b, jt["anchor_b"])
+            arm_a, arm_b = p_a - centre(a), p_b - centre(b)
+            d = (v[:, b] + cross(wb, arm_b)) - (v[:, a] + cross(wa, arm_a))
+            length = sqrt(dot(d, d))
+            if length != 0:
+                for body in (a, b):
+                    info["damper_cond"][body] = min(info["damper_cond"][body], as_float(length * h))
+                nrm = d * (one / length)
+                w_sum = 0
+                for body, arm in ((a, arm_a), (b, arm_b)):
+                    local = qrot(conj(a_rot[:, body]), cross(arm, nrm))
+                    w_sum = w_sum + (im[body] + dot(matvec(M[:, :, body], local), local))
+                if w_sum > 0:
+                    seen.add("mu_l h below 1" if const(mu_l) * h < 1 else "mu_l h at or above 1")
+                    lam = (share(mu_l) * length) / w_sum
+                    terms_of[(j, "linear")] = (as_float(share(mu_l)), as_float(length))
+                    for body, arm, P in ((a, arm_a, nrm * lam), (b, arm_b, nrm * (lam if mutation == "second_end_same_sign" else -lam))):
+                        dv[body] = dv[body] + P * im[body]
+                        dw[body] = dw[body] + cross(matvec(M[:, :, body], arm), P)
+                    terms += 1
+                    kinds.append("linear")
+                    if mutation == "angular_on_linear_result":
+                        wa, wb = wa + dw[a], wb + dw[b]
+        if mu_a > 0:
+            d = wb - wa
+            length = sqrt(dot(d, d))
+            if length != 0:
+                for body in (a, b):
+                    info["damper_cond"][body] = min(info["damper_cond"][body], as_float(length * h))
+                nrm = d * (one / length)
+                local = {body: (nrm if mutation == "wang_unrotated" else qrot(conj(a_rot[:, body]), nrm)) for body in (a, b)}
+                w_ang = dot(matvec(M[:, :, a], local[a]), local[a]) + dot(matvec(M[:, :, b], local[b]), local[b])
+                if w_ang > 0:
+                    seen.add("mu_a h below 1" if const(mu_a) * h < 1 else "mu_a h at or above 1")
+                    lam = (share(mu_a) * length) / w_ang
+                    terms_of[(j, "angular")] = (as_float(share(mu_a)), as_float(length))
+                    for body, signed in ((a, lam), (b, -lam)):
+                        turn = qrot(conj(a_rot[:, body]), nrm * signed)
+                        dw[body] = dw[body] + qrot(a_rot[:, body], matvec(M[:, :, body], turn))
+                    terms += 1
+                    kinds.append("angular")
+        if not terms:
+            return a, b, None, 0, kinds
+        return a, b, {a: (dv[a], dw[a]), b: (dv[b], dw[b])}, terms, kinds
+
+    def dampers(vel, ang):
+        sequential = mutation == "neighbour_stage7_velocities"
+        out_v, out_w = vel.copy(), ang.copy()
+        read_v, read_w = (out_v, out_w) if sequential else (vel, ang)
+        for body in range(n):
+            sum_v, sum_w, entries, terms = vel[:, body] * 0, vel[:, body] * 0, 0, 0
+            for j, jt in enumerate(joints):
+                if body not in (int(jt["body_a"]), int(jt["body_b"])):
+                    continue
+                a, b, entry, t, kinds = joint_entries(j, jt, read_v, read_w)
+                if entry is None:
+                    continue
+                sum_v, sum_w = sum_v + entry[body][0], sum_w + entry[body][1]
+                entries, terms = entries + 1, terms + t
+                other = b if body == a else a
+                if not fixed[body]:
+                    seen.add({("linear",): "a linear-only entry", ("angular",): "an angular-only entry",
+                              ("linear", "angular"): "a two-term entry"}[tuple(kinds)])
+                    if fixed[other]:
+                        info["n_damper_fixed_end"][body] += 1
+                        seen.add("a damper with one end fixed")
+            info["n_damper_entries"][body], info["n_damper_terms"][body] = entries, terms
+            if entries and (not fixed[body] or mutation == "fixed_body_damped"):
+                count = {"count_is_terms": terms, "damper_entries_summed": 1}.get(mutation, entries)
+                out_v[:, body] = read_v[:, body] + sum_v / count
+                out_w[:, body] = read_w[:, body] + sum_w / count
+        for jt in joints:
+            a, b = int(jt["body_a"]), int(jt["body_b"])
+            ea, eb = info["n_damper_entries"][a], info["n_damper_entries"][b]
+            if ea and eb and ea != eb and not fixed[a] and not fixed[b]:
+                seen.add("ends with unequal counts")
+        return out_v, out_w
+
+    def row(b):
+        if rows is None:
+            return 0.0, 0.0, np.inf, np.inf
+        r = rows[b]
+        return float(r["linear"]), float(r["angular"]), float(r["max_linear_speed"]), float(r["max_angular_speed"])
+
+    def moved(b):
+        return not fixed[b] or mutation == "fixed_body_damped"
+
+    def drag(vel, ang):
+        vel, ang = vel.copy(), ang.copy()
+        for b in range(n):
+            if not moved(b):
+                continue
+            c_l, c_a = row(b)[:2]
+            for arr, c in ((vel, c_l), (ang, c_a)):
+                scale = one - h * const(c) if mutation == "drag_explicit" else one / (one + h * const(c))
+                arr[:, b] = arr[:, b] * scale
+        return vel, ang
+
+    def caps(vel, ang):
+        vel, ang = vel.copy(), ang.copy()
+        for b in range(n):
+            if not moved(b):
+                continue
+            for arr, cap, key in ((vel, row(b)[2], "cap_fired_linear"), (ang, row(b)[3], "cap_fired_angular")):
+                if not np.isfinite(cap):
+                    continue
+                c = const(cap)
+                if mutation == "cap_per_component":
+                    arr[:, b] = np.array([min(max(x, -c), c) for x in arr[:, b]], dtype=arr.dtype)
+                    continue
+                m = sqrt(dot(arr[:, b], arr[:, b]))
+                info["cap_margin"][b] = min(info["cap_margin"][b], abs(as_float(m - c)) * as_float(h))
+                if m > c:
+                    arr[:, b] = arr[:, b] * (c / m)
+                    info[key][b] = True
+                seen.add(("%s cap that fires" if m > c else "%s cap that does not fire") % ("a linear" if arr is vel else "an angular"))
+        return vel, ang
+
+    order = {"caps_before_drag": (dampers, caps, drag), "drag_before_dampers": (drag, dampers, caps)}.get(mutation, (dampers, drag, caps))
+    for stage in order:
+        vel, ang = stage(vel, ang)
+    info["damping_seen"] = seen
+    info["damper_terms"] = [(j, kind, k, length) for (j, kind), (k, length) in sorted(terms_of.items())]
+    return vel, ang, info
+
+
 def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.inf, max_depenetration_speed=0.0, num=None,
             mutation=None, tau=0.0, joints=(), limits=(), drives=(), restitution=None, ground_restitution=0.0,
-            bounce_threshold=0.0, terrain=None):
+            bounce_threshold=0.0, terrain=None, kinematics=None, substeps_left=1, damping=None, joint_damping=None,
+            substep_index=0):
     """Stage S: one contacts substep (steps 1, 3, 4, 5 of xpbd_pairs_oracle.h) of n bodies ((n, 38) f64).  shapes: list of
     shape() dicts.  manifolds: {(i, j), i < j: {"feature", "p_ref": [(3,)], "p_inc": [(3,)]}} of the touching pairs at the
     post-integrate frames, or None: stage N on every pair (stage S o N, the fully independent substep).  mu: per-body
@@ -803,8 +1075,13 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     body) and, from joint_terms, n_joint, n_binding, limit_margin, wrap_margin, joint_cond, `limits` and the extras' n_extra,
     n_clamped, slide_margin, drive_margin, drive_wrap_margin, `slides`, `perps`, `drives`; from xprec_model.ground cell_margin,
     diagonal_margin, border_margin, lower_contacts, upper_contacts, n_outside (inf and 0 without a terrain; `margin` is then
-    min |s|); and, when stage 6 ran, bounce's info."""
-    assert mutation is None or mutation in MUTATIONS + JOINT_MUTATIONS + DRIVE_MUTATIONS + BOUNCE_MUTATIONS
+    min |s|); and, when stage 6 ran, bounce's info.
+    kinematics (records of xpbd_kinematic) and substeps_left (r): stage 0, kinematic_velocities, overwrites the entries' two
+    velocities before integrate; stage 6 reads them as v0, w0.  damping (records of xpbd_body_damping, one per body) and
+    joint_damping (records of xpbd_joint_damping): stage 7, damp, after stage 6 -- after derive with stage 6 off.  Without the
+    four the result is what it was; with them the stages' info is in the dict too.  substep_index: see kinematic_velocities."""
+    assert mutation is None or mutation in (MUTATIONS + JOINT_MUTATIONS + DRIVE_MUTATIONS + BOUNCE_MUTATIONS + DAMPING_MUTATIONS
+                                            + KINEMATIC_MUTATIONS)
     joint_mutation = mutation if mutation in JOINT_MUTATIONS + DRIVE_MUTATIONS else None
     num = num or xm.native()
     sqrt = num.sqrt
@@ -825,11 +1102,28 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
         slots[b, :counts[b]] = shapes[sid[b]]["verts"]
     vert = [num.conv(slots[:, v].T) for v in range(vmax)]
 
+    # 0. the kinematic overwrite, before integrate                          xpbd.h, "KINEMATIC bodies"
+    kin_mutation = mutation if mutation in KINEMATIC_MUTATIONS else None
+    kin_info = {}
+
+    def overwritten(vel, ang, at_pos, at_rot):
+        scripted, info = kinematic_velocities(num, s, at_pos, at_rot, kinematics, hx, substeps_left, kin_mutation, substep_index)
+        vel, ang = vel.copy(), ang.copy()
+        for b, (v, w) in scripted.items():
+            vel[:, b], ang[:, b] = v, w
+        return vel, ang, info
+
+    before_vel, before_ang = vel, ang
+    if kinematics is not None and len(kinematics) and kin_mutation != "overwrite_after_integrate":
+        vel, ang, kin_info = overwritten(vel, ang, pos, rot)
+
     # 1. past = pose; integrate; P1 = Rigid::frame()                        solver.rs:7-10
     past_pos, past_rot = pos, rot
-    start_vel, start_ang = vel, ang                                      # v0, w0 of stage 6
+    start_vel, start_ang = (before_vel, before_ang) if kin_mutation == "v0_before_overwrite" else (vel, ang)   # v0, w0 of stage 6
     past_p = pos + com + qrot(rot, -com)
     pos, rot, vel, ang = xm.integrate(s, pos, rot, vel, ang, hx, sqrt)
+    if kinematics is not None and len(kinematics) and kin_mutation == "overwrite_after_integrate":
+        vel, ang, kin_info = overwritten(vel, ang, pos, rot)
     p1_p, p1_q = pos + com + qrot(rot, -com), rot
     frames = [(p1_p[:, b], p1_q[:, b]) for b in range(n)]
 
@@ -933,14 +1227,27 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     vel, ang, _, flip_margin = xm.derive(num, pos, rot, past_pos, past_rot, hx)
 
     # 6. restitution: a velocity pass on this substep's manifolds and ground mask          xpbd.h, "RESTITUTION"
+    # 7. damping: joint dampers, drag, caps on what stage 6 left                            xpbd.h, "DAMPING"
     bounce_info = {}
+    damp_mutation = mutation if mutation in DAMPING_MUTATIONS else None
+    damped = damping is not None or (joint_damping is not None and len(joint_damping))
+
+    def stage7(vel, ang):
+        return damp(num, s, (pos, rot), (vel, ang), joints, damping, joint_damping, hx, damp_mutation,
+                    (integrated_pos, integrated_rot))
+
+    damp_info = {}
+    if damped and damp_mutation == "stage7_before_stage6":
+        vel, ang, damp_info = stage7(vel, ang)
     if restitution is not None or ground_restitution > 0:
         vel, ang, bounce_info = bounce(num, s, (pos, rot), (vel, ang), (start_vel, start_ang), manifolds, g["mask"], vert, float(h),
                                        restitution, float(ground_restitution), bounce_threshold, terrain,
                                        mutation if mutation in BOUNCE_MUTATIONS else None, (integrated_pos, integrated_rot),
                                        g["xs"], compliance)
+    if damped and damp_mutation != "stage7_before_stage6":
+        vel, ang, damp_info = stage7(vel, ang)
     s.update(position=pos, rotation=rot, velocity=vel, angular_velocity=ang)
     return {"state": xm._pack(s), "frames": frames, "manifolds": manifolds, "undecided": undecided, "mask": g["mask"],
             "margin": g["margin"], "cond": g["cond"], "flip_margin": flip_margin, "domain": domain, "branch": branch,
-            "pair_cond": pair_cond, "n_points": n_points, **joint_info, **bounce_info,
+            "pair_cond": pair_cond, "n_points": n_points, **joint_info, **bounce_info, **kin_info, **damp_info,
             **{k: g[k] for k in ("cell_margin", "diagonal_margin", "border_margin", "lower_contacts", "upper_contacts", "n_outside")}}
