@@ -28,9 +28,10 @@ namespace {
 #define XPBD_STEP_MIN_WAVES_PER_SIMD 1
 #endif
 
-// The substep loop of one lane.  `pass1(cur)` returns the lane's contact mask (the three table paths of k_step differ
-// in it alone); pass 2 reads the lane's penetrating vertices from the LDS table `verts`.
-template <bool TRACE, class Pass1>
+// The substep loop of one lane.  `pass1(cur)` returns the lane's contact mask (the table paths of k_step differ in it, and
+// the grid path below also in BOUNDED_VERTS, solve_masked's flag); pass 2 reads the lane's penetrating vertices from the LDS
+// table `verts`.
+template <bool TRACE, bool BOUNDED_VERTS = false, class Pass1>
 __device__ __forceinline__ uint32_t run_substeps(BodyDynamic &d, const BodyStatic &s, double h, uint32_t substeps, const double *verts,
                                                  Pass1 pass1, uint32_t *__restrict__ trace_lane, uint32_t trace_stride)
 {
@@ -39,7 +40,7 @@ __device__ __forceinline__ uint32_t run_substeps(BodyDynamic &d, const BodyStati
     for (uint32_t k = 0; k < substeps; ++k) {
         const SubstepFrames f = integrate_body(d, s, h);
         mask = pass1(f.cur);
-        solve_masked(d.pos, d.rot, s.inv_mass, s.inv_inertia, s.com, f.cur, f.past, compliance, verts, mask);
+        solve_masked<false, false, BOUNDED_VERTS>(d.pos, d.rot, s.inv_mass, s.inv_inertia, s.com, f.cur, f.past, compliance, verts, mask);
         derive_body(d, f.past_pos, f.past_rot, h);
         if (TRACE)
             trace_lane[(size_t)k * trace_stride] = mask;
@@ -47,7 +48,35 @@ __device__ __forceinline__ uint32_t run_substeps(BodyDynamic &d, const BodyStati
     return mask;
 }
 
-// A wave of one shape with exactly NV vertices: the table is read once, through a wave-uniform address.
+// A grid table: vertex v is (X[v & 1], Y[(v >> 1) & 1], Z[(v >> 2) & 1]) for all eight v -- an axis-aligned box in binary
+// vertex order, six distinct numbers in 24 entries.  Decided on 64-bit patterns (+0.0 and -0.0 are different entries, a NaN
+// equals only its own bits), so a table that passes IS the table rebuilt from its six values.  The six must also be below
+// 2^970 in magnitude (inf and NaN fail that): the licence for rotate_bounded.  Wave-uniform work, once per kernel.
+__device__ __forceinline__ bool is_bounded_grid_table(const double (&table)[24])
+{
+    const auto bits = [&](uint32_t k) { return __builtin_bit_cast(uint64_t, table[k]); };
+    // The or of all xors is zero iff all 24 patterns are the grid's.  The empty asm pins the running value to a scalar register
+    // pair: without it the compiler turns the sum back into 18 compares and gathers their outcomes in vector registers.
+    uint64_t differ = 0;
+#pragma unroll
+    for (uint32_t v = 1; v < 8; ++v) {
+        differ |= (bits(3 * v + 0) ^ bits(3 * (v & 1) + 0)) | (bits(3 * v + 1) ^ bits(3 * (v & 2) + 1)) |
+                  (bits(3 * v + 2) ^ bits(3 * (v & 4) + 2));
+        asm("" : "+s"(differ));
+    }
+    // |x| < 2^970 on the high dword without its sign: doubles of one sign order as their patterns do, and 2^970's low dword is 0.
+    uint32_t biggest = 0;
+#pragma unroll
+    for (uint32_t k : {0u, 3u, 1u, 7u, 2u, 14u})
+        biggest = max(biggest, (uint32_t)(bits(k) >> 32) & 0x7fffffffu);
+    return differ == 0 && biggest < ((1023u + 970u) << 20);
+}
+
+// A wave of one shape with exactly NV vertices: the table is read once, through a wave-uniform address.  Eight vertices that
+// form a bounded grid table take a copy of the loop whose pass 1 sees the table rebuilt from its six values (the products the
+// eight unrolled vertices share are then visibly the same operations on the same operands, and one of each is left; every
+// one that remains has the operands and the order it had) and whose frame * vertex, in both passes, is rotate_bounded's.
+// Any other 8-vertex table -- a permuted cube, a sheared box, one coordinate off by an ulp -- keeps the general copy.
 template <bool TRACE, uint32_t NV>
 __device__ __forceinline__ uint32_t run_substeps_table(BodyDynamic &d, const BodyStatic &s, double h, uint32_t substeps,
                                                        const double *verts, const double *__restrict__ uniform_verts,
@@ -57,6 +86,20 @@ __device__ __forceinline__ uint32_t run_substeps_table(BodyDynamic &d, const Bod
 #pragma unroll
     for (uint32_t k = 0; k < 3 * NV; ++k)
         table[k] = uniform_verts[k];
+    if constexpr (NV == 8) {
+        if (is_bounded_grid_table(table)) {
+            double grid[24];
+#pragma unroll
+            for (uint32_t v = 0; v < 8; ++v) {
+                grid[3 * v + 0] = table[3 * (v & 1) + 0];
+                grid[3 * v + 1] = table[3 * (v & 2) + 1];
+                grid[3 * v + 2] = table[3 * (v & 4) + 2];
+            }
+            return run_substeps<TRACE, true>(d, s, h, substeps, verts,
+                                             [&](const Frame &cur) { return ground_mask_table<8, true>(cur, grid); }, trace_lane,
+                                             trace_stride);
+        }
+    }
     return run_substeps<TRACE>(d, s, h, substeps, verts, [&](const Frame &cur) { return ground_mask_table<NV>(cur, table); },
                                trace_lane, trace_stride);
 }

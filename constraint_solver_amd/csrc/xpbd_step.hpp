@@ -128,18 +128,40 @@ __device__ __forceinline__ uint32_t ground_mask(const Frame &cur, const double *
     return mask;
 }
 
+// Quat * Vec3 of xpbd_math.hpp for a v whose components are all below 2^970 in magnitude: the closing `c * 2.0 + v` in one
+// fma per component.  Doubling is exact, so both forms round the same real number 2c + v -- unless 2c overflows
+// (|c| >= 2^1023), where the plain form gives +-inf; then |2c + v| > 2^1024 - 2^970, the threshold from which rounding to
+// nearest gives +-inf too.  NaN and inf in c behave alike in both forms.  So: the same bits for every c, with no guard, but
+// only under the bound on v -- which the caller owes (k_step tests it once per kernel on a wave-uniform table; DESIGN
+// section 2).  Every other rotation keeps the plain form.
+__device__ __forceinline__ Vec3 rotate_bounded(Quat q, Vec3 v)
+{
+    const Vec3 qv = vec_of(q);
+    const Vec3 t = cross(qv, v) + v * q.s;
+    const Vec3 c = cross(qv, t);
+    return Vec3{__builtin_fma(c.x, 2.0, v.x), __builtin_fma(c.y, 2.0, v.y), __builtin_fma(c.z, 2.0, v.z)};
+}
+
+// frame * vertex (src/frame.rs:47-53); BOUNDED: the vertex is an entry of a table that passed the 2^970 bound.
+template <bool BOUNDED>
+__device__ __forceinline__ Vec3 frame_times_vertex(const Frame &f, Vec3 vertex)
+{
+    return (BOUNDED ? rotate_bounded(f.rotation, vertex) : f.rotation * vertex) + f.position;
+}
+
 // Pass 1 for a wave whose lanes all have the same shape of exactly NV vertices: `table` holds that shape's vertices in
 // wave-uniform values (k_step loads them once per kernel through a uniform address, so they live in scalar registers
 // and feed the f64 instructions as scalar operands).  Fully unrolled: no LDS read and no per-lane loop in the substep.
-// The expression per vertex is ground_mask's.
-template <uint32_t NV>
+// The expression per vertex is ground_mask's.  (k_step's grid path hands in a table rebuilt from a box's six distinct
+// coordinates: the unrolled copies then repeat products on the same operands and the compiler keeps one of each.)
+template <uint32_t NV, bool BOUNDED = false>
 __device__ __forceinline__ uint32_t ground_mask_table(const Frame &cur, const double (&table)[3 * NV])
 {
     uint32_t mask = 0;
 #pragma unroll
     for (uint32_t v = 0; v < NV; ++v) {
         const Vec3 vertex{table[3 * v + 0], table[3 * v + 1], table[3 * v + 2]};
-        const Vec3 x = cur * vertex;
+        const Vec3 x = frame_times_vertex<BOUNDED>(cur, vertex);
         if (!(x.z >= 0.0))
             mask |= 1u << v;
     }
@@ -200,7 +222,9 @@ __device__ __forceinline__ Vec3 terrain_target(const Terrain &terrain, const Vec
 // TERRAIN (XPBD_MODE_CONTACTS with xpbd_world_set_terrain only; `mask` is then ground_mask_terrain's and every other form never
 // reads `terrain`): the target is the point of the terrain's plane below the vertex instead of {x.x, x.y, 0.0}; the lookup
 // repeats pass 1's on the same x, so the same plane.  Everything after `target` is the same arithmetic.
-template <bool MATERIALS = false, bool TERRAIN = false>
+// BOUNDED_VERTS (k_step's grid path only): every entry of `verts` is below 2^970 in magnitude, so x takes rotate_bounded's
+// single fma per component -- the same bits as the plain form.
+template <bool MATERIALS = false, bool TERRAIN = false, bool BOUNDED_VERTS = false>
 __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_mass, const Mat3 &inv_inertia, const Vec3 &com,
                                              const Frame &cur, const Frame &past, double compliance, const double *verts,
                                              uint32_t mask, double limit = 0.0, double mu = 0.0, const Terrain &terrain = Terrain{})
@@ -209,7 +233,7 @@ __device__ __forceinline__ void solve_masked(Vec3 &pos, Quat &rot, double inv_ma
     for (uint32_t todo = mask; todo != 0; todo &= todo - 1) {
         const uint32_t v = __ffs(todo) - 1;
         const Vec3 vertex{verts[3 * v + 0], verts[3 * v + 1], verts[3 * v + 2]};
-        const Vec3 x = cur * vertex; // src/collision.rs:17
+        const Vec3 x = frame_times_vertex<BOUNDED_VERTS>(cur, vertex); // src/collision.rs:17
 
         // src/collision.rs:22-29
         const Vec3 target = TERRAIN ? terrain_target(terrain, x) : Vec3{x.x, x.y, 0.0};
