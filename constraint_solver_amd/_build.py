@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG, "csrc")
 HOST = os.path.join(PKG, "host")
 ORACLE = os.path.join(ROOT, "oracle")
 
-HIP_SOURCES = ["xpbd_kernels.hip", "xpbd_pairs.hip", "xpbd_scan.hip", "xpbd_broadphase.hip", "xpbd_contacts.hip", "xpbd_restitution.hip", "xpbd_damping.hip", "xpbd_terrain.hip", "xpbd_body_ops.hip", "xpbd_gjk.hip", "xpbd_query_grid.hip", "xpbd_query_rays.hip", "xpbd_query_overlap.hip", "xpbd_query_sweep.hip", "xpbd_query_distance.hip", "xpbd_terrain_query.hip", "xpbd_report.hip", "xpbd_population.hip", "xpbd_islands.hip", "xpbd_sleep.hip", "xpbd_joint_state.hip", "xpbd_kinematic.hip", "xpbd_mass_edit.hip", "xpbd_population_remap.cpp", "xpbd_shape_tables.cpp", "xpbd_world.cpp", "xpbd_world_shapes.cpp", "xpbd_world_contacts.cpp", "xpbd_world_report.cpp", "xpbd_world_query.cpp", "xpbd_world_edit.cpp", "xpbd_world_islands.cpp", "xpbd_world_sleep.cpp", "xpbd_world_joint_state.cpp", "xpbd_world_kinematic.cpp", "xpbd_selftest.cpp", "xpbd_checks.cpp", "xpbd_multi.cpp", "xpbd_multi_transport.cpp", "xpbd_multi_plan.cpp", "xpbd_multi_frame.cpp", "xpbd_multi_query.cpp", "xpbd_multi_report.cpp", "xpbd_multi_edit.cpp", "xpbd_rccl.cpp", "xpbd_error.cpp", "xpbd_plan.cpp"]
+HIP_SOURCES = ["xpbd_kernels.hip", "xpbd_pairs.hip", "xpbd_scan.hip", "xpbd_broadphase.hip", "xpbd_contacts.hip", "xpbd_restitution.hip", "xpbd_damping.hip", "xpbd_terrain.hip", "xpbd_body_ops.hip", "xpbd_gjk.hip", "xpbd_query_grid.hip", "xpbd_query_rays.hip", "xpbd_query_overlap.hip", "xpbd_query_sweep.hip", "xpbd_query_distance.hip", "xpbd_terrain_query.hip", "xpbd_report.hip", "xpbd_population.hip", "xpbd_islands.hip", "xpbd_sleep.hip", "xpbd_joint_state.hip", "xpbd_kinematic.hip", "xpbd_mass_edit.hip", "xpbd_sensors.hip", "xpbd_population_remap.cpp", "xpbd_shape_tables.cpp", "xpbd_world.cpp", "xpbd_world_shapes.cpp", "xpbd_world_contacts.cpp", "xpbd_world_report.cpp", "xpbd_world_query.cpp", "xpbd_world_edit.cpp", "xpbd_world_islands.cpp", "xpbd_world_sleep.cpp", "xpbd_world_joint_state.cpp", "xpbd_world_kinematic.cpp", "xpbd_world_sensors.cpp", "xpbd_selftest.cpp", "xpbd_checks.cpp", "xpbd_multi.cpp", "xpbd_multi_transport.cpp", "xpbd_multi_plan.cpp", "xpbd_multi_frame.cpp", "xpbd_multi_query.cpp", "xpbd_multi_report.cpp", "xpbd_multi_edit.cpp", "xpbd_rccl.cpp", "xpbd_error.cpp", "xpbd_plan.cpp"]
 # -ffp-contract=off is a correctness flag: the reference (Rust) never fuses a*b+c.
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall"]
 CXX_FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra"]

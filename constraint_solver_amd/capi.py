@@ -75,7 +75,11 @@ ABI_SYMBOLS = [
     "xpbd_world_set_kinematics", "xpbd_world_set_kinematic_targets", "xpbd_world_set_kinematic_targets_device", "xpbd_world_kinematic_count",
     "xpbd_world_set_mass_properties", "xpbd_world_set_mass_properties_device", "xpbd_world_get_mass_properties",
     "xpbd_world_set_damping", "xpbd_world_get_damping", "xpbd_world_set_joint_damping",
+    "xpbd_world_set_sensors", "xpbd_world_get_sensors", "xpbd_world_sensor_count", "xpbd_world_sensor_overlaps", "xpbd_world_sensor_overlaps_device",
 ]
+
+# sensor bodies (include/xpbd.h, "SENSOR bodies"): xpbd_sensor_hit, 8 bytes
+SENSOR_HIT_DTYPE = np.dtype([("body", "<u4"), ("pair", "<u4")])
 
 # damping (include/xpbd.h, "DAMPING"): xpbd_body_damping, 32 bytes, and xpbd_joint_damping, 24 bytes
 BODY_DAMPING_DTYPE = np.dtype([("linear", np.float64), ("angular", np.float64), ("max_linear_speed", np.float64), ("max_angular_speed", np.float64)])
@@ -573,6 +577,15 @@ def hip_lib():
             L.xpbd_world_set_mass_properties.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
             L.xpbd_world_set_mass_properties_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
             L.xpbd_world_get_mass_properties.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        except AttributeError:          # an older build loaded through XPBD_HIP_LIB
+            pass
+        try:
+            L.xpbd_world_set_sensors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_get_sensors.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            L.xpbd_world_sensor_count.argtypes = [C.c_void_p]
+            L.xpbd_world_sensor_count.restype = C.c_uint32
+            L.xpbd_world_sensor_overlaps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.xpbd_world_sensor_overlaps_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         except AttributeError:          # an older build loaded through XPBD_HIP_LIB
             pass
         _hip = L
@@ -1166,6 +1179,47 @@ class World:
 
     def kinematic_count(self):
         return int(hip_lib().xpbd_world_kinematic_count(self._h))
+
+    # sensor bodies (include/xpbd.h, "SENSOR bodies")
+    def set_sensors(self, is_sensor):
+        """Replaces the sensor table: one byte (0 / 1) per body; None or an empty array clears it.  May wait."""
+        t = np.zeros(0, dtype=np.uint8) if is_sensor is None else np.ascontiguousarray(is_sensor, dtype=np.uint8).reshape(-1)
+        _check(hip_lib().xpbd_world_set_sensors(self._h, t.ctypes.data if t.size else None, t.size))
+
+    def get_sensors(self):
+        out = np.zeros(self.n, dtype=np.uint8)
+        _check(hip_lib().xpbd_world_get_sensors(self._h, out.ctypes.data if out.size else None, out.size))
+        return out
+
+    def sensor_count(self):
+        return int(hip_lib().xpbd_world_sensor_count(self._h))
+
+    def sensor_overlaps(self, cap=None):
+        """(sensors, offsets, hits) of the current report frame: hits[offsets[k]:offsets[k + 1]] (SENSOR_HIT_DTYPE) are the bodies
+        that touched sensors[k] in the frame, ascending, each with the index of its record in pair_contacts().  cap=None sizes
+        the hits to fit; with a cap below the total the call raises XpbdError(E_CAPACITY) -- sensor_overlaps_raw shows the prefix."""
+        if cap is None:
+            cap = self.sensor_overlaps_raw(0)[4]
+        rc, sensors, offsets, hits, total = self.sensor_overlaps_raw(cap)
+        _check(rc)
+        return sensors, offsets, hits[:total]
+
+    def sensor_overlaps_raw(self, cap):
+        """(rc, sensors, offsets, hits[cap], total): the call as it is; rc other than OK or E_CAPACITY raises."""
+        k = self.sensor_count()
+        sensors, offsets = np.zeros(k, dtype=np.uint32), np.zeros(k + 1, dtype=np.uint32)
+        hits = np.zeros(cap, dtype=SENSOR_HIT_DTYPE)
+        total = C.c_uint32(0)
+        rc = hip_lib().xpbd_world_sensor_overlaps(self._h, sensors.ctypes.data, offsets.ctypes.data, hits.ctypes.data if cap else None, cap,
+                                                  C.byref(total))
+        if rc != E_CAPACITY:
+            _check(rc)
+        return rc, sensors, offsets, hits, int(total.value)
+
+    def sensor_overlaps_device(self, dev_sensors_ptr, dev_offsets_ptr, dev_hits_ptr, cap):
+        """Device arrays (sensors: sensor_count() uint32, offsets: one more, hits: cap SENSOR_HIT_DTYPE records); enqueues only."""
+        _check(hip_lib().xpbd_world_sensor_overlaps_device(self._h, C.c_void_p(dev_sensors_ptr or None), C.c_void_p(dev_offsets_ptr or None),
+                                                           C.c_void_p(dev_hits_ptr or None), cap))
 
 
 def _report_counts(counts_fn, h):

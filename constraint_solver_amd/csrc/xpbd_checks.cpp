@@ -272,6 +272,42 @@ int IslandsTarget::check(const char *who, uint32_t flags, const void *records, u
     return XPBD_OK;
 }
 
+int SensorTarget::table_check(const char *who, const uint8_t *is_sensor, uint32_t n, bool get, uint32_t *count) const
+{
+    if (n && !is_sensor)
+        return set_error(XPBD_E_INVALID, "%s: NULL is_sensor with n = %u", who, n);
+    if (n != n_bodies && (get || n || is_sensor))
+        return set_error(XPBD_E_INVALID, "%s: n = %u but the world holds %u bodies", who, n, n_bodies);
+    uint32_t flagged = 0;
+    for (uint32_t i = 0; !get && i < n; ++i) {
+        if (is_sensor[i] > 1u)
+            return set_error(XPBD_E_INVALID, "%s: is_sensor[%u] = %u (0 or 1: the other bits are reserved)", who, i, (unsigned)is_sensor[i]);
+        flagged += is_sensor[i];
+    }
+    if (count)
+        *count = flagged;
+    return XPBD_OK;
+}
+
+int SensorTarget::overlaps_check(const char *who, const void *sensors, const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out,
+                                 bool host) const
+{
+    if (!sensors || !offsets)
+        return set_error(XPBD_E_INVALID, "%s: NULL sensors or offsets", who);
+    if (!hits && cap)
+        return set_error(XPBD_E_INVALID, "%s: NULL hits with cap = %u", who, cap);
+    if (host && !n_out)
+        return set_error(XPBD_E_INVALID, "%s: NULL n_out", who);
+    if (n_sensors == 0)
+        return set_error(XPBD_E_INVALID, "%s: no sensor is set (xpbd_world_set_sensors)", who);
+    if (!report_on)
+        return set_error(XPBD_E_INVALID, "%s: contact reports are off (xpbd_world_set_contact_report)", who);
+    if (!report_frame)
+        return set_error(XPBD_E_INVALID, "%s: no report: no substep of XPBD_MODE_CONTACTS has run since the last broadphase, upload, "
+                                         "history restore, enable, failed step or step in another mode", who);
+    return XPBD_OK;
+}
+
 int SleepTarget::check(const char *who, const xpbd_sleep_config &cfg) const
 {
     if (!(cfg.linear_speed >= 0.0) || !std::isfinite(cfg.linear_speed))

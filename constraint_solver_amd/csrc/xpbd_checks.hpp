@@ -124,6 +124,19 @@ struct KinematicTargets {
     int check(const char *who, const uint32_t *entries, const double *rows, uint32_t n, bool host) const;
 };
 
+// ... of the sensor calls (include/xpbd.h, "SENSOR bodies"), after the caller has dealt with a NULL world: what the call is made
+// on.  table_check, of xpbd_world_set_sensors and (get == true) _get_sensors: NULL with n > 0, n different from the body count
+// (only NULL with n == 0, which clears, passes a setter without it; a getter takes no such exception), and for the setter a byte
+// other than 0 or 1; count (NULL: not wanted): the bytes that are 1.  overlaps_check, of xpbd_world_sensor_overlaps(_device): a
+// NULL sensors or offsets array, a NULL hits array with a nonzero cap, with `host` a NULL n_out, no sensor set, and a report that
+// xpbd_world_contact_report_counts would refuse (reporting off; no frame).
+struct SensorTarget {
+    uint32_t n_bodies, n_sensors;
+    bool report_on, report_frame;
+    int table_check(const char *who, const uint8_t *is_sensor, uint32_t n, bool get, uint32_t *count = nullptr) const;
+    int overlaps_check(const char *who, const void *sensors, const void *offsets, const void *hits, uint32_t cap, const uint32_t *n_out, bool host) const;
+};
+
 // ... of the mass edits (include/xpbd.h, "MASS properties of resident bodies"), after the caller has dealt with a NULL world and
 // n == 0: what the call is made on -- the body count and the host copy of the kinematic table (ascending by body; read only
 // with `host`).  check, of xpbd_world_set_mass_properties(_device): NULL rows, no resident bodies, unknown flag bits or a layout

@@ -73,6 +73,7 @@ void drop_body_settings(xpbd_world *w)
     w->restitution.clear();
     w->kinematics.clear();
     w->damping.clear();
+    w->sensors.clear();
 }
 
 // The world takes a new set of n_new bodies (xpbd_world_upload_bodies, xpbd::repack_bodies; device bound, stream idle): room for

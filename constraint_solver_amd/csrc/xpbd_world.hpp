@@ -12,6 +12,7 @@
 //   xpbd_world_sleep.cpp     Sleep and the sleeping entry points
 //   xpbd_world_joint_state.cpp  joint states and drive targets: the entry points, and the way back of device-set targets
 //   xpbd_world_kinematic.cpp    KinematicBodies and the kinematic entry points
+//   xpbd_world_sensors.cpp      Sensors, the sensor entry points and what the frame, the islands and the sleep pass ask of them
 #pragma once
 
 #include <cstdint>
@@ -33,6 +34,7 @@
 #include "xpbd_population_remap.hpp"
 #include "xpbd_query.h"
 #include "xpbd_report.h"
+#include "xpbd_sensors.h"
 #include "xpbd_sleep.h"
 
 struct xpbd_world;
@@ -147,6 +149,25 @@ struct KinematicBodies {
     bool any() const { return !list.empty(); }
     xpbd::KinematicTable view() const { return xpbd::KinematicTable{table.as<xpbd_kinematic>(), (uint32_t)list.size()}; }
     void clear() { *this = KinematicBodies{}; }
+};
+
+// The sensor table of a world (xpbd_world_set_sensors; xpbd_sensors.h; xpbd_world_sensors.cpp): one byte per body, what the caller
+// handed over (`host`) and its copy on the device, complete or absent; `count`: the bodies flagged.  Only the setter and a
+// population change replace the table, each staged aside and moved in once nothing can fail.  Everything a frame does for sensors
+// hangs on any(): an empty or all-zero table enqueues nothing.  The other blocks are scratch: the masked pair codes of the
+// substep under way, the report's keys without the sensor pairs, the ascending sensor list (list_ready: it describes `flags`)
+// and the staging of the host variant of the occupancy.
+struct Sensors {
+    std::vector<uint8_t> host;
+    uint32_t count = 0;
+    bool list_ready = false;
+    DeviceBuffer flags;
+    DeviceBuffer solve_codes;
+    DeviceBuffer key_flag, key_scan, solid_keys;
+    DeviceBuffer list, list_flag, occ_scan, occ_sensors, occ_offsets, occ_hits;
+
+    bool any() const { return count != 0; }
+    void clear() { *this = Sensors{}; }
 };
 
 // The sphere broadphase of the contact pipeline (xpbd_world_contacts.cpp): grid, buckets, the neighbour lists and the pair
@@ -411,7 +432,7 @@ struct xpbd_world {
     ReplanStaging replan;
     // state at the start of a frame (xpbd::frame_snapshot_save / _restore): the 13 dynamic fields and the contact masks
     FrameSnapshot snapshot;
-    // Body-indexed settings: each names bodies (or the joints between them) by index, so a new set of bodies clears all six
+    // Body-indexed settings: each names bodies (or the joints between them) by index, so a new set of bodies clears all seven
     // (adopt_body_count).  Values whose clear() restores the defaults; the per-body device tables stay allocated beside theirs.
     JointTables joints;
     struct Filters { // xpbd_world_set_collision_filters: group, mask per body (on), XPBD_FILTER_* flags
@@ -454,6 +475,8 @@ struct xpbd_world {
     // xpbd_world_set_kinematics: the fixed bodies that move on a script.  Non-empty, the step runs the unfused schedule with the
     // velocity overwrite before every integrate stage; empty, a world holds and enqueues nothing of it
     KinematicBodies kinematics;
+    // xpbd_world_set_sensors: the bodies that report their pairs and solve none.  None flagged, a world enqueues nothing of it
+    Sensors sensors;
     // xpbd_world_set_terrain: the plane table of the heightfield and its description (planes == NULL: none).  World-level, as the
     // contact pad: it names no body, so no upload, population change or restore touches it.  With one the step runs the unfused
     // schedule (the fused pair-solve + integrate + ground kernel has no terrain form).
@@ -500,6 +523,15 @@ struct xpbd_world {
         c.ground_restitution = restitution.ground;
         c.bounce_threshold = restitution.bounce_threshold;
         c.terrain = terrain;
+        return c;
+    }
+
+    // What the launches that solve or bounce are handed (both forms of the pair solve, restitution): `c` with the pair codes
+    // masked for the sensor pairs (narrowphase_contacts fills the copy behind every narrowphase); no sensor: `c` itself.
+    xpbd::ContactBuffers solve_buffers(xpbd::ContactBuffers c) const
+    {
+        if (sensors.any())
+            c.pair_codes = sensors.solve_codes.as<uint8_t>();
         return c;
     }
 
@@ -576,6 +608,16 @@ int sync_drive_targets(xpbd_world *w);
 // ---- xpbd_world_kinematic.cpp -----------------------------------------------------------------------------------------------
 // Rows set on the device go back into kinematics.list (no-op unless targets_on_device).  Device bound, stream idle.
 int sync_kinematic_targets(xpbd_world *w);
+
+// ---- xpbd_world_sensors.cpp -------------------------------------------------------------------------------------------------
+// The contact edges of the current report frame for the islands and the sleep pass: the report's keys, compacted now if they are
+// not, or -- with sensors -- those of them without a sensor end; their count stays on the device.  Enqueues only (it waits only
+// when the scratch of the second form has to grow).  The frame has pairs (w->bp.n_pairs != 0).
+int contact_edge_keys(xpbd_world *w, const unsigned long long **keys, const uint32_t **key_count);
+// Behind a substep's narrowphase: the masked pair codes for the launches that solve (no sensor: nothing).
+int sensor_mask_codes(xpbd_world *w, const xpbd::ContactBuffers &c);
+// Behind launch_sleep_frame_begin: a sensor is not inert (no sensor: nothing).
+int sensor_not_inert(xpbd_world *w);
 
 // ---- xpbd_world_contacts.cpp ------------------------------------------------------------------------------------------------
 int build_neighbours_enqueue(xpbd_world *w, double dt);

@@ -184,7 +184,9 @@ int narrowphase_contacts(xpbd_world *w, const xpbd::BodyArrays &b, const xpbd::C
                                                     w->stream, w->np.sat_scratch.cache_edge_axes /* = a dense scene, see below */));
     }
     w->np.stats_pair_substeps += w->bp.n_pairs;
-    return w->report.note_substep(w, c.pair_codes);
+    if (int rc = w->report.note_substep(w, c.pair_codes))
+        return rc;
+    return sensor_mask_codes(w, c); // what solve_buffers() hands the launches that solve ("SENSOR bodies"; no sensor: nothing)
 }
 
 // One substep of the contact pipeline (neighbour lists must be current): the form the split API
@@ -207,11 +209,12 @@ int substep_contacts(xpbd_world *w, double h, uint32_t *trace, uint32_t trace_ro
     if (int rc = narrowphase_contacts(w, b, c))
         return rc;
     XPBD_HIP_TRY(xpbd::launch_joint_extras(h, c, w->stream));
+    const xpbd::ContactBuffers solve = w->solve_buffers(c);
     if (!c.restitution) {
-        XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream, awake));
+        XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, solve, w->stream, awake));
     } else {
-        XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, w->dyn_alt.as<double>(), h, c, w->stream, awake));
-        XPBD_HIP_TRY(xpbd::launch_restitution(b, w->dyn_alt.as<double>(), w->rs_start.as<double>(), w->geom.shapes(), c, w->last_mask.as<uint32_t>(),
+        XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, w->dyn_alt.as<double>(), h, solve, w->stream, awake));
+        XPBD_HIP_TRY(xpbd::launch_restitution(b, w->dyn_alt.as<double>(), w->rs_start.as<double>(), w->geom.shapes(), solve, w->last_mask.as<uint32_t>(),
                                               w->stream, awake));
     }
     // stage 7 (include/xpbd.h, "DAMPING") on the end-of-substep state, which is in the SoA arrays either way
@@ -270,12 +273,13 @@ int step_contacts(xpbd_world *w, double dt, double h, uint32_t substeps, uint32_
         if (int rc = narrowphase_contacts(w, b, c))
             return rc;
         XPBD_HIP_TRY(xpbd::launch_joint_extras(h, c, w->stream));
+        const xpbd::ContactBuffers solve = w->solve_buffers(c);
         if (k + 1 < substeps) {
             const xpbd::ContactBuffers next = w->contact_buffers((k + 1u) & 1u);
-            XPBD_HIP_TRY(xpbd::launch_pair_solve_integrate_ground(b, w->geom.shapes(), h, c, next.rec, w->last_mask.as<uint32_t>(), trace,
+            XPBD_HIP_TRY(xpbd::launch_pair_solve_integrate_ground(b, w->geom.shapes(), h, solve, next.rec, w->last_mask.as<uint32_t>(), trace,
                                                                   k + 1, w->stream, awake));
         } else {
-            XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, c, w->stream, awake));
+            XPBD_HIP_TRY(xpbd::launch_pair_solve_derive(b, b.dyn, h, solve, w->stream, awake));
         }
     }
     return w->sleep.on ? w->sleep.frame_end(w) : XPBD_OK;

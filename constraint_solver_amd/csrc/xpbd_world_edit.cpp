@@ -368,6 +368,8 @@ struct PopulationStage {
     JointTables joints;
     KinematicBodies kinematics; // (a removal only: the table as it stands stays where nobody leaves)
     bool kinematics_staged = false;
+    Sensors sensors; // (only where the world has a table: the flags gathered, the rest of the unit's blocks start over)
+    bool sensors_staged = false;
 };
 
 // The new body arrays and per-body tables: new body s < n_keep is the present body dev_src[s] (NULL: body s), the n_add bodies
@@ -429,6 +431,14 @@ int stage_bodies(xpbd_world *w, const uint32_t *dev_src, uint32_t n_keep, const 
     }
     if (w->joints.damping.n && w->dp_scratch.bytes < (size_t)6 * stride * 8) // the joint part's scratch follows the stride
         XPBD_HIP_TRY(st.dp_scratch.reserve((size_t)6 * stride * 8));
+    if (!w->sensors.host.empty()) { // the sensor flags ("SENSOR bodies"): a survivor keeps its byte, an appended body is no sensor
+        XPBD_HIP_TRY(st.sensors.flags.reserve(at_least_one(n_new)));
+        XPBD_HIP_TRY(xpbd::launch_sensor_gather(w->sensors.flags.as<uint8_t>(), st.sensors.flags.as<uint8_t>(), dev_src, n_keep, n_new, w->stream));
+        st.sensors.host.resize(n_new); // (pageable: the copy returns once the bytes are here)
+        if (n_new)
+            XPBD_HIP_TRY(hipMemcpyAsync(st.sensors.host.data(), st.sensors.flags.ptr, n_new, hipMemcpyDeviceToHost, w->stream));
+        st.sensors_staged = true;
+    }
     return XPBD_OK;
 }
 
@@ -454,6 +464,11 @@ void commit_population(xpbd_world *w, PopulationStage &st, uint32_t max_shape_id
     w->joints = std::move(st.joints);
     if (st.kinematics_staged)
         w->kinematics = std::move(st.kinematics);
+    if (st.sensors_staged) { // (the callers have waited for the stream: the host copy is complete)
+        for (uint8_t flag : st.sensors.host)
+            st.sensors.count += flag;
+        w->sensors = std::move(st.sensors);
+    }
     take_body_count(w, st.n, max_shape_id);
 }
 

@@ -38,11 +38,7 @@ int Islands::enqueue(xpbd_world *w, uint32_t flags, uint32_t *dev_island_of, xpb
     k.n = w->n;
     k.last_mask = w->last_mask.as<uint32_t>();
     if (!(flags & XPBD_ISLANDS_NO_CONTACTS) && w->bp.n_pairs) {
-        ContactReport &r = w->report;
-        if (!r.keys_ready)
-            XPBD_TRY(r.compact_keys(w));
-        k.keys = r.keys[r.cur].as<unsigned long long>();
-        k.key_count = r.flag.as<uint32_t>() + w->bp.n_pairs;
+        XPBD_TRY(contact_edge_keys(w, &k.keys, &k.key_count)); // (without the sensor pairs: "SENSOR bodies")
         k.key_lanes = w->bp.n_pairs;
     }
     if (!(flags & XPBD_ISLANDS_NO_JOINTS) && w->joints.csr.n) {

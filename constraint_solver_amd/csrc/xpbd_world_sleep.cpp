@@ -33,6 +33,7 @@ int Sleep::frame_begin(xpbd_world *w)
     XPBD_HIP_TRY(xpbd::launch_sleep_frame_begin(view(w), w->stat.as<double>(), requests, w->stream));
     if (moving) // a MOVING kinematic body is not inert in this frame ("KINEMATIC bodies"; no table: the launches of before)
         XPBD_HIP_TRY(xpbd::launch_sleep_moving_inert(view(w), w->kinematics.view(), w->stream));
+    XPBD_TRY(sensor_not_inert(w)); // a sensor is never inert ("SENSOR bodies"; no sensor: nothing)
     requests = 0;
     return XPBD_OK;
 }
@@ -52,13 +53,8 @@ int Sleep::frame_end(xpbd_world *w)
     const xpbd::SleepState s = view(w);
     const unsigned long long *keys = nullptr;
     const uint32_t *key_count = nullptr;
-    if (w->bp.n_pairs) {
-        ContactReport &r = w->report;
-        if (!r.keys_ready)
-            XPBD_TRY(r.compact_keys(w));
-        keys = r.keys[r.cur].as<unsigned long long>();
-        key_count = r.flag.as<uint32_t>() + w->bp.n_pairs;
-    }
+    if (w->bp.n_pairs)
+        XPBD_TRY(contact_edge_keys(w, &keys, &key_count)); // (without the sensor pairs: "SENSOR bodies")
     xpbd::MovingBodies mv; // the frame's MOVING kinematic bodies mark what shares a pair of the pair list or a joint with them
     if (moving)
         mv = xpbd::MovingBodies{s.moving, w->bp.pairs.as<uint32_t>(), w->bp.n_pairs, w->joints.csr.joints.as<xpbd::Joint>(), w->joints.csr.n};

@@ -386,6 +386,15 @@ pub struct XpbdOverlapQuery {
     pub reserved: u32,
 }
 
+/// EXTENSION: xpbd_sensor_hit (8 bytes; see xpbd.h, "SENSOR bodies"): a body that touched a sensor in the report frame, and the
+/// index of the pair's record in xpbd_world_download_pair_contacts.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct XpbdSensorHit {
+    pub body: u32,
+    pub pair: u32,
+}
+
 /// xpbd_overlap_hit (16 bytes): a body the volume touches; feature = XPBD_FEATURE_* (A = the volume, B = the body), separation < 0
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -672,6 +681,14 @@ extern "C" {
     pub fn xpbd_world_set_kinematic_targets(w: *mut XpbdWorld, entries: *const u32, rows: *const f64, n: u32) -> c_int;
     pub fn xpbd_world_set_kinematic_targets_device(w: *mut XpbdWorld, dev_entries: *const u32, dev_rows: *const f64, n: u32) -> c_int;
     pub fn xpbd_world_kinematic_count(w: *const XpbdWorld) -> u32;
+    // sensor bodies (include/xpbd.h, "SENSOR bodies"): one byte per body (NULL with n = 0 clears); the occupancy of the report frame
+    pub fn xpbd_world_set_sensors(w: *mut XpbdWorld, is_sensor: *const u8, n: u32) -> c_int;
+    pub fn xpbd_world_get_sensors(w: *mut XpbdWorld, is_sensor: *mut u8, n: u32) -> c_int;
+    pub fn xpbd_world_sensor_count(w: *const XpbdWorld) -> u32;
+    pub fn xpbd_world_sensor_overlaps(w: *mut XpbdWorld, sensors: *mut u32, offsets: *mut u32, hits: *mut XpbdSensorHit, cap: u32,
+                                      n_out: *mut u32) -> c_int;
+    pub fn xpbd_world_sensor_overlaps_device(w: *mut XpbdWorld, dev_sensors: *mut u32, dev_offsets: *mut u32, dev_hits: *mut XpbdSensorHit,
+                                             cap: u32) -> c_int;
     // mass edits (include/xpbd.h, "MASS properties of resident bodies"); a NULL index list names all bodies; rows are [n][13] doubles
     pub fn xpbd_world_set_mass_properties(w: *mut XpbdWorld, indices: *const u32, n: u32, rows: *const f64, flags: u32) -> c_int;
     pub fn xpbd_world_set_mass_properties_device(w: *mut XpbdWorld, dev_indices: *const u32, n: u32, dev_rows: *const f64, flags: u32) -> c_int;

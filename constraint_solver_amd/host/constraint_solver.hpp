@@ -725,6 +725,35 @@ class BatchWorld {
         check(xpbd_world_set_kinematic_targets_device(w_, dev_entries, dev_rows, n));
     }
     uint32_t kinematic_count() const { return xpbd_world_kinematic_count(w_); }
+    // sensor bodies (include/xpbd.h, "SENSOR bodies"): one byte per body (an empty table clears); the occupancy of the report frame
+    void set_sensors(const std::vector<uint8_t> &is_sensor)
+    {
+        check(xpbd_world_set_sensors(w_, is_sensor.empty() ? nullptr : is_sensor.data(), (uint32_t)is_sensor.size()));
+    }
+    std::vector<uint8_t> get_sensors()
+    {
+        std::vector<uint8_t> out(xpbd_world_body_count(w_));
+        check(xpbd_world_get_sensors(w_, out.empty() ? nullptr : out.data(), (uint32_t)out.size()));
+        return out;
+    }
+    uint32_t sensor_count() const { return xpbd_world_sensor_count(w_); }
+    // sensors[k], and hits[offsets[k] .. offsets[k + 1]) = who touched it; sized by a first call without room for hits
+    void sensor_overlaps(std::vector<uint32_t> &sensors, std::vector<uint32_t> &offsets, std::vector<xpbd_sensor_hit> &hits)
+    {
+        sensors.assign(sensor_count(), 0u);
+        offsets.assign(sensors.size() + 1, 0u);
+        hits.clear();
+        uint32_t total = 0;
+        const int rc = xpbd_world_sensor_overlaps(w_, sensors.data(), offsets.data(), nullptr, 0, &total);
+        if (rc != XPBD_E_CAPACITY)
+            return check(rc);
+        hits.resize(total);
+        check(xpbd_world_sensor_overlaps(w_, sensors.data(), offsets.data(), hits.data(), total, &total));
+    }
+    void sensor_overlaps_device(uint32_t *dev_sensors, uint32_t *dev_offsets, xpbd_sensor_hit *dev_hits, uint32_t cap)
+    {
+        check(xpbd_world_sensor_overlaps_device(w_, dev_sensors, dev_offsets, dev_hits, cap));
+    }
     // mass edits (include/xpbd.h, "MASS properties of resident bodies"): rows of 13 doubles; an empty index list names all bodies
     void set_mass_properties(const std::vector<uint32_t> &indices, const std::vector<double> &rows, uint32_t flags = XPBD_MASS_INVERSE)
     {

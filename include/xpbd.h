@@ -1921,6 +1921,74 @@ int  xpbd_world_sleep_state_device(xpbd_world *w, uint8_t *dev_asleep, uint32_t 
 int  xpbd_world_wake_bodies(xpbd_world *w, const uint32_t *indices, uint32_t n /* NULL, 0: all */);
 int  xpbd_world_wake_bodies_device(xpbd_world *w, const uint32_t *dev_indices, uint32_t n /* NULL, 0: all */);
 
+/* ---------------------------------------------------------------------------
+ * SENSOR bodies (EXTENSION): triggers -- bodies that see what enters them and push nothing: goal zones, pressure plates,
+ * pick-up volumes, a proximity zone carried by a kinematic gripper.  NOT in the reference.  Opt-in: a world whose sensor table is
+ * empty or all zero enqueues exactly what it enqueued before.  Single world, XPBD_MODE_CONTACTS.
+ *
+ * Definition.  A SENSOR is a body whose byte in the per-body table of xpbd_world_set_sensors is 1.  A SENSOR PAIR is a pair of
+ * the frame's pair list with at least one sensor end.  Only body-body pairs are affected: a dynamic sensor still integrates, hits
+ * the ground or the terrain, obeys joints, drives, damping and kinematic scripts, and is hit by the scene queries.  A fixed or
+ * kinematic sensor is the usual trigger.
+ *
+ * Never solved.  A sensor pair is still formed by the broadphase, subject to the collision filters as they are: group and mask
+ * bits are how a caller makes a sensor selective.  Its narrowphase runs every substep and its manifold and code are written as
+ * for any pair.  But the pair solve (both of its forms), the restitution pass and the depenetration limit see a code of 0 for
+ * it: no contact.  Every body of a world with sensors therefore steps BIT FOR BIT like the same world in which the sensor bodies
+ * carry the filter {group 0, mask 0} and no sensor flag.  The touching-pair and point counts of xpbd_world_contact_stats, which
+ * are counted inside the pair solve (and from which the SAT schedule is chosen), exclude sensor pairs; its pair count includes
+ * them.
+ *
+ * Reported.  The contact report ("Contact REPORTS") treats a sensor pair like any pair, with no special case: its touching
+ * substeps, the last substep's feature, normal, depth and points at the post-integrate poses, and BEGIN / END against the
+ * previous frame.  Sensor-sensor pairs are reported too.
+ *
+ * Islands and sleeping.  Sensor pairs are not contact edges ("Contact ISLANDS"): they add no connectivity, n_pairs or
+ * n_anchors, and wake step 1 of the sleep pass ("SLEEPING") does not read them: they wake nobody.  With sleeping on a sensor is
+ * never inert for the broadphase (inert = 0 for it, whatever it is), so a body that falls asleep inside a fixed sensor keeps its
+ * pair: no END event at sleep, and it is still listed by the occupancy below.  The wake rule of a MOVING kinematic body is
+ * unchanged -- it reads the frame's pair list, not the touching set -- so a MOVING kinematic sensor wakes what it shares a pair
+ * with.
+ *
+ * Lifetime.  xpbd_world_upload_bodies clears the table.  xpbd_world_remove_bodies / _add_bodies carry each survivor's flag; new
+ * bodies are not sensors.  History push and restore do not carry the table.  Setting or clearing the table while sleeping is on
+ * wakes everybody and zeroes every rest_frames, as the other table setters do.
+ *
+ * xpbd_world_set_sensors(w, is_sensor, n) replaces the table: n == the body count, one byte per body; NULL with n == 0 clears
+ * it.  XPBD_E_INVALID, the previous table left in force: a NULL world; NULL with n > 0; n different from the body count; a byte
+ * other than 0 or 1 (the other bits stay reserved).  xpbd_world_get_sensors writes the table as it stands (all 0 without one);
+ * XPBD_E_INVALID for a NULL world, NULL with n > 0, n different from the body count.  xpbd_world_sensor_count: the bodies
+ * flagged (0 for a NULL world).
+ *
+ * Occupancy.  xpbd_world_sensor_overlaps answers, for the current report frame: sensors[k] = the k-th sensor in ascending body
+ * index (k < xpbd_world_sensor_count), and hits[offsets[k] .. offsets[k + 1]) = the bodies that touched it in at least one
+ * substep of the frame, ascending by body, each with the index of the pair's record in xpbd_world_download_pair_contacts.  A
+ * pair of two sensors is listed under both.  The host variant takes host arrays (sensors: sensor count entries, offsets: one
+ * more) and waits for the device; the capacity rule is that of xpbd_world_overlap: offsets are always complete, *n_out is the
+ * total, and with more than `cap` hits XPBD_E_CAPACITY is returned with the first `cap` filled.  xpbd_world_sensor_overlaps_device
+ * takes DEVICE arrays, only enqueues on the world's stream (it waits only when its scratch has to grow) and writes only the
+ * first `cap` hits, the total being dev_offsets[sensor count]; it composes with xpbd_world_joint_states_device,
+ * xpbd_world_set_drive_targets_device and xpbd_world_set_kinematic_targets_device, so a loop "who is in the zone -> retarget"
+ * never leaves the device.  No atomic and no sort decide an order: the lists do not depend on the schedule.  XPBD_E_INVALID,
+ * nothing written: a NULL world; a NULL sensors or offsets array, a NULL hits array with a nonzero cap, for the host variant a
+ * NULL n_out; no sensor set; and exactly when xpbd_world_contact_report_counts is XPBD_E_INVALID (reporting off, no report
+ * frame).  The calls only read.
+ *
+ * Not here: the multi-GPU world (xpbd_multi_world_*); a per-sensor filter beyond group / mask.
+ * ------------------------------------------------------------------------- */
+typedef struct xpbd_sensor_hit {   /* 8 bytes */
+    uint32_t body;                 /* the other body of a touching sensor pair */
+    uint32_t pair;                 /* index of the pair's record in xpbd_world_download_pair_contacts */
+} xpbd_sensor_hit;
+
+int      xpbd_world_set_sensors(xpbd_world *w, const uint8_t *is_sensor, uint32_t n /* == body count; NULL, 0: clear */);
+int      xpbd_world_get_sensors(xpbd_world *w, uint8_t *is_sensor, uint32_t n);
+uint32_t xpbd_world_sensor_count(const xpbd_world *w) XPBD_NOEXCEPT;
+int      xpbd_world_sensor_overlaps(xpbd_world *w, uint32_t *sensors, uint32_t *offsets, xpbd_sensor_hit *hits, uint32_t cap,
+                                    uint32_t *n_out);
+int      xpbd_world_sensor_overlaps_device(xpbd_world *w, uint32_t *dev_sensors, uint32_t *dev_offsets, xpbd_sensor_hit *dev_hits,
+                                           uint32_t cap);
+
 /* Diagnostics: quotient[i] = a[i] / b[i], root[i] = sqrt(a[i]) computed on the
  * device with the stepper's own code generation.  Bit-exact contact lists need
  * both to be correctly rounded; the parity tests check this against the host. */
