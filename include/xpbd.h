@@ -1844,6 +1844,11 @@ int  xpbd_world_islands_device(xpbd_world *w, uint32_t flags, uint32_t *dev_isla
  *  (c) awake neighbours see an asleep body through a body record made from its resting pose: frame before integrate = frame
  *      after integrate = Rigid::frame(), pose after the ground contacts = its pose, with its own mass properties.  (A
  *      neighbour's correction is therefore shared as with an awake body, but the sleeper's share is not applied in that frame.)
+ *      Friction's past frame of a sleeper is that same Rigid::frame(), so its contact points have no travel of their own.  Stage 6
+ *      (RESTITUTION) reads a sleeper's v0, w0 and its v, w after derive as the +0.0 that step 3 below stored -- every edit of
+ *      a sleeper wakes it before the next step, so no sleeper carries another value -- shares the impulse with the sleeper's own
+ *      W, and drops the sleeper's entry as the position pass drops its share.  The ground contact mask a sleeper keeps is its
+ *      own: it enters no neighbour's count.
  *
  * The sleep pass runs at the end of every xpbd_world_step, on the state the last substep left, in this order:
  *  1. Wake.  Every asleep body s is MARKED when the frame's touching set holds a pair (s, a) with a awake and not fixed.  Every

@@ -427,8 +427,15 @@ def gjk_model_manifolds(state, sid, h):
     face clip where its largest query is a face axis (EPA's normal is then that face's), or EPA's point pair after its depth
     and normal have been checked against stage N's largest query where that is an edge axis no face is aligned with.
     Returns ({(i, j): manifold}, the bodies with a pair the model cannot reproduce, the bodies that touch a pair)."""
-    polys, shapes, _ = table()
     frames, oman, _ = oracle_manifolds(state, sid, h)
+    return gjk_manifolds_of(frames, oman, sid)
+
+
+def gjk_manifolds_of(frames, pairs, sid):
+    """gjk_model_manifolds on given f64 frames [(position, rotation)] and pairs (i, j), i < j: for a caller whose frames are not
+    every body's integrated pose."""
+    polys, shapes, _ = table()
+    oman = pairs
     num = xm.native()
     out, unknown, touching = {}, set(), set()
     for i, j in oman:

@@ -53,6 +53,10 @@ DAMPING_MUTATIONS = ("drag_explicit", "caps_before_drag", "drag_before_dampers",
                      "wang_unrotated", "anchors_at_integrated", "fixed_body_damped", "cap_per_component", "second_end_same_sign")
 KINEMATIC_MUTATIONS = ("dq_conjugate_first", "dq_not_negated", "full_angle", "r_counted_up", "overwrite_after_integrate",
                        "p_frame_origin", "v0_before_overwrite", "velocity_once_per_frame")
+# wrong readings of a substep with sleepers (xpbd.h, "SLEEPING", rules (a)-(c)); the table of test_xprec_sleep_oracle.py names a
+# scene per member
+SLEEP_MUTATIONS = ("sleeper_share_applied", "sleeper_fixed", "record_from_integrated", "record_after_ground", "record_without_com",
+                   "stage6_reads_stored_velocity", "sleeper_point_twice", "sleeper_point_uncounted", "sleeper_drag_applied")
 SWEEPS = 4                                                               # XPBD_RESTITUTION_SWEEPS
 JOINT_DISTANCE, JOINT_HINGE, JOINT_SLIDER = 0, 1, 2                      # XPBD_JOINT_*
 LIMIT_HINGE, LIMIT_SWING, LIMIT_TWIST, LIMIT_SLIDE = 0, 1, 2, 3          # XPBD_LIMIT_*
@@ -1052,7 +1056,7 @@ def damp(num, s, pose, velocities, joints, rows, joint_damping, h, mutation=None
 def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.inf, max_depenetration_speed=0.0, num=None,
             mutation=None, tau=0.0, joints=(), limits=(), drives=(), restitution=None, ground_restitution=0.0,
             bounce_threshold=0.0, terrain=None, kinematics=None, substeps_left=1, damping=None, joint_damping=None,
-            substep_index=0):
+            substep_index=0, asleep=None, contact_mask=None):
     """Stage S: one contacts substep (steps 1, 3, 4, 5 of xpbd_pairs_oracle.h) of n bodies ((n, 38) f64).  shapes: list of
     shape() dicts.  manifolds: {(i, j), i < j: {"feature", "p_ref": [(3,)], "p_inc": [(3,)]}} of the touching pairs at the
     post-integrate frames, or None: stage N on every pair (stage S o N, the fully independent substep).  mu: per-body
@@ -1079,9 +1083,19 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     kinematics (records of xpbd_kinematic) and substeps_left (r): stage 0, kinematic_velocities, overwrites the entries' two
     velocities before integrate; stage 6 reads them as v0, w0.  damping (records of xpbd_body_damping, one per body) and
     joint_damping (records of xpbd_joint_damping): stage 7, damp, after stage 6 -- after derive with stage 6 off.  Without the
-    four the result is what it was; with them the stages' info is in the dict too.  substep_index: see kinematic_velocities."""
+    four the result is what it was; with them the stages' info is in the dict too.  substep_index: see kinematic_velocities.
+    asleep ((n,) bool, or None: nobody, and the result is what it was): xpbd.h, "SLEEPING", rules (a)-(c), written from that
+    section alone; xpbd_sleep.hip, xpbd_contacts.hip, xpbd_restitution.hip, xpbd_world_sleep.cpp and sleep_model.py were not read
+    for it.  An asleep body has no stage: no overwrite, integrate, ground contacts, derive, stage 6 or 7; its 13 dynamic values
+    are returned as the input's bits and its contact mask as contact_mask's entry (0 without one).  Everybody else sees it through
+    a record of its stored pose: P0 = P1 = Rigid::frame() of that pose (stage N, every pair point, friction's past frame), the pose
+    after the ground contacts = that pose, its own inverse mass and inverse inertia in the shared denominator; its part of the
+    correction is dropped and counted nowhere, stage 6 reads its start and post-derive velocities as zero and drops its entry, and a
+    pair of two inert (asleep or FIXED) bodies does not exist.  Info: n_sleeper_points, per body the pair points whose other end
+    is asleep, and `asleep`."""
     assert mutation is None or mutation in (MUTATIONS + JOINT_MUTATIONS + DRIVE_MUTATIONS + BOUNCE_MUTATIONS + DAMPING_MUTATIONS
-                                            + KINEMATIC_MUTATIONS)
+                                            + KINEMATIC_MUTATIONS + SLEEP_MUTATIONS)
+    sleep_mutation = mutation if mutation in SLEEP_MUTATIONS else None
     joint_mutation = mutation if mutation in JOINT_MUTATIONS + DRIVE_MUTATIONS else None
     num = num or xm.native()
     sqrt = num.sqrt
@@ -1113,6 +1127,17 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
             vel[:, b], ang[:, b] = v, w
         return vel, ang, info
 
+    sleeping = asleep is not None
+    zz = np.asarray(asleep, dtype=bool) if sleeping else np.zeros(n, dtype=bool)
+    assert zz.shape == (n,)
+    stored = (pos, rot, vel, ang)
+
+    def keep(new, old):
+        """`new` with the sleepers' columns taken from `old`."""
+        out = new.copy()
+        out[..., zz] = old[..., zz]
+        return out
+
     before_vel, before_ang = vel, ang
     if kinematics is not None and len(kinematics) and kin_mutation != "overwrite_after_integrate":
         vel, ang, kin_info = overwritten(vel, ang, pos, rot)
@@ -1124,7 +1149,19 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     pos, rot, vel, ang = xm.integrate(s, pos, rot, vel, ang, hx, sqrt)
     if kinematics is not None and len(kinematics) and kin_mutation == "overwrite_after_integrate":
         vel, ang, kin_info = overwritten(vel, ang, pos, rot)
+    if sleeping:                                                          # rules (b), (c): no stage, and the record of the stored pose
+        if sleep_mutation != "record_from_integrated":
+            pos, rot = keep(pos, stored[0]), keep(rot, stored[1])
+        vel, ang = keep(vel, stored[2]), keep(ang, stored[3])
+        start_vel, start_ang = keep(start_vel, start_vel * 0), keep(start_ang, start_ang * 0)
+        if sleep_mutation == "stage6_reads_stored_velocity":
+            start_vel, start_ang = keep(start_vel, stored[2]), keep(start_ang, stored[3])
     p1_p, p1_q = pos + com + qrot(rot, -com), rot
+    if sleeping:
+        if sleep_mutation == "record_without_com":
+            p1_p = keep(p1_p, pos)
+        past_pos, past_rot, past_p = keep(past_pos, pos), keep(past_rot, rot), keep(past_p, p1_p)   # P0 = P1
+    inert = zz | is_fixed(s) if sleeping else zz
     frames = [(p1_p[:, b], p1_q[:, b]) for b in range(n)]
 
     # 2. manifolds of all pairs by brute force (stage N), unless given
@@ -1134,6 +1171,8 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
         centre = np.array([num.to_f64(frame_apply(p1_p[:, b], p1_q[:, b], num.conv(shapes[sid[b]]["centroid"]))) for b in range(n)])
         for i in range(n):
             for j in range(i + 1, n):
+                if inert[i] and inert[j]:                                  # rule (a)
+                    continue
                 reach = shapes[sid[i]]["radius"] + shapes[sid[j]]["radius"]
                 if np.linalg.norm(centre[i] - centre[j]) > reach + 1e-3:   # the bounding spheres are a millimetre apart
                     continue
@@ -1143,6 +1182,9 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
                 if not m["separated"]:
                     manifolds[(i, j)] = m
 
+    elif sleeping:
+        manifolds = {k: m for k, m in manifolds.items() if not (inert[k[0]] and inert[k[1]])}
+
     # 3. ground contacts from P1, sequentially per body                     solver.rs:12-13
     body_mu = None
     if mu is not None or np.isfinite(ground_mu):
@@ -1150,6 +1192,19 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     integrated_pos, integrated_rot = pos, rot
     pos, rot, g = xm.ground(num, s, pos, rot, past_p, past_rot, vert, counts, compliance, domain, body_mu, limit, terrain,
                             mutation if mutation in xm.TERRAIN_MUTATIONS else None)
+    if sleeping:
+        if sleep_mutation != "record_after_ground":
+            pos, rot = keep(pos, integrated_pos), keep(rot, integrated_rot)
+        domain[zz] = True
+        g["mask"][zz] = 0
+        for key in ("margin", "cond", "branch", "cell_margin", "diagonal_margin", "border_margin"):
+            g[key][zz] = np.inf
+        for key in ("lower_contacts", "upper_contacts", "n_outside"):
+            g[key][zz] = 0
+    s_shared = s
+    if sleep_mutation == "sleeper_fixed":                                # the sleeper as a fixed body in every shared denominator
+        s_shared = dict(s, inverse_mass=keep(im, im * 0), inverse_inertia=keep(M, M * 0))
+    n_sleeper_points = np.zeros(n, dtype=np.int64)
 
     # 4. pair contacts, Jacobi: every point from the poses after step 3, a body applies the average of its points
     inc, ref, pair, p_inc, p_ref = manifold_points(manifolds)
@@ -1188,7 +1243,9 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
         arm_i, arm_r = c0 - origin_i, surface - origin_r
         ai = qrot(conj(rot[:, inc]), cross(arm_i, direction))                           # constraint.rs:25-32
         ar = qrot(conj(rot[:, ref]), cross(arm_r, direction))
-        w = im[inc] + dot(matvec(Mi, ai), ai) + im[ref] + dot(matvec(Mr, ar), ar)
+        im_w, M_w = s_shared["inverse_mass"], s_shared["inverse_inertia"]
+        Mi_w, Mr_w = (Mi, Mr) if s_shared is s else (M_w[:, :, inc], M_w[:, :, ref])
+        w = im_w[inc] + dot(matvec(Mi_w, ai), ai) + im_w[ref] + dot(matvec(Mr_w, ar), ar)
         error, clamp = xm.limited(num, dist, limit, delta, correction, cc)
         lam = error / (w + compliance)
         impulse_i = direction * lam                                                      # +lambda dir on the incident body at c0
@@ -1200,14 +1257,19 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
         d64 = num.to_f64(dist)
         both = np.minimum(gap, clamp)
         for t in range(len(inc)):
-            for body, dp, dq in ((inc[t], dpos_i[:, t], drot_i[:, t]), (ref[t], dpos_r[:, t], drot_r[:, t])):
+            for body, other, dp, dq in ((inc[t], ref[t], dpos_i[:, t], drot_i[:, t]), (ref[t], inc[t], dpos_r[:, t], drot_r[:, t])):
                 sum_p[:, body] = sum_p[:, body] + dp
                 sum_q[:, body] = sum_q[:, body] + dq
                 if mutation != "average_by_pairs" or (body, pair[t]) not in seen:
                     count[body] += 1
+                if zz[other]:
+                    n_sleeper_points[body] += 1
+                    count[body] += {"sleeper_point_twice": 1, "sleeper_point_uncounted": -1}.get(sleep_mutation, 0)
                 seen.add((body, pair[t]))
                 pair_cond[body] = min(pair_cond[body], d64[t])
                 branch[body] = min(branch[body], both[t])
+    if sleeping and sleep_mutation != "sleeper_share_applied":          # the sleeper's share: dropped, counted nowhere
+        count[zz] = 0
     n_points = count.copy()
     # ... and the joints' entries, from the same poses, in the same average
     at = (integrated_pos, integrated_rot) if joint_mutation == "joints_from_integrated" else (pos, rot)
@@ -1216,6 +1278,8 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
         integrated=(integrated_pos, integrated_rot), h=hx)
     if len(joints):
         sum_p, sum_q, count = sum_p + joint_p, sum_q + joint_q, count + joint_count
+        if sleeping and sleep_mutation != "sleeper_share_applied":
+            count[zz] = 0
     hit = np.nonzero(count)[0]
     if len(hit):
         cnt = num.conv(count[hit].astype(np.float64))
@@ -1225,6 +1289,10 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
 
     # 5. Rigid::derive(past, h)                                             solver.rs:15
     vel, ang, _, flip_margin = xm.derive(num, pos, rot, past_pos, past_rot, hx)
+    if sleeping and sleep_mutation != "sleeper_share_applied":          # no derive: what stage 6 reads of a sleeper is zero
+        vel, ang = keep(vel, vel * 0), keep(ang, ang * 0)
+        if sleep_mutation == "stage6_reads_stored_velocity":
+            vel, ang = keep(vel, stored[2]), keep(ang, stored[3])
 
     # 6. restitution: a velocity pass on this substep's manifolds and ground mask          xpbd.h, "RESTITUTION"
     # 7. damping: joint dampers, drag, caps on what stage 6 left                            xpbd.h, "DAMPING"
@@ -1240,14 +1308,28 @@ def substep(bodies, shapes, shape_id, h, manifolds=None, mu=None, ground_mu=np.i
     if damped and damp_mutation == "stage7_before_stage6":
         vel, ang, damp_info = stage7(vel, ang)
     if restitution is not None or ground_restitution > 0:
-        vel, ang, bounce_info = bounce(num, s, (pos, rot), (vel, ang), (start_vel, start_ang), manifolds, g["mask"], vert, float(h),
+        vel, ang, bounce_info = bounce(num, s_shared, (pos, rot), (vel, ang), (start_vel, start_ang), manifolds, g["mask"], vert, float(h),
                                        restitution, float(ground_restitution), bounce_threshold, terrain,
                                        mutation if mutation in BOUNCE_MUTATIONS else None, (integrated_pos, integrated_rot),
                                        g["xs"], compliance)
+    if sleep_mutation == "sleeper_drag_applied":
+        vel, ang = keep(vel, stored[2]), keep(ang, stored[3])
     if damped and damp_mutation != "stage7_before_stage6":
         vel, ang, damp_info = stage7(vel, ang)
+    sleep_info = {}
+    if sleeping:                                                          # rule (b): the input's bits
+        if sleep_mutation != "sleeper_share_applied":
+            pos, rot = keep(pos, stored[0]), keep(rot, stored[1])
+            if sleep_mutation != "sleeper_drag_applied":
+                vel, ang = keep(vel, stored[2]), keep(ang, stored[3])
+        if contact_mask is not None:
+            g["mask"][zz] = np.asarray(contact_mask, dtype=np.uint32)[zz]
+        sleep_info = {"n_sleeper_points": n_sleeper_points, "asleep": zz}
+        for key in ("bounce_pair_entries", "bounce_one_point", "bounce_ground_entries", "bounce_push", "bounce_give_back", "bounce_clamped"):
+            if key in bounce_info:                                        # a sleeper's entry is dropped: it has none
+                bounce_info[key][zz] = 0
     s.update(position=pos, rotation=rot, velocity=vel, angular_velocity=ang)
     return {"state": xm._pack(s), "frames": frames, "manifolds": manifolds, "undecided": undecided, "mask": g["mask"],
             "margin": g["margin"], "cond": g["cond"], "flip_margin": flip_margin, "domain": domain, "branch": branch,
-            "pair_cond": pair_cond, "n_points": n_points, **joint_info, **bounce_info, **kin_info, **damp_info,
+            "pair_cond": pair_cond, "n_points": n_points, **joint_info, **bounce_info, **kin_info, **damp_info, **sleep_info,
             **{k: g[k] for k in ("cell_margin", "diagonal_margin", "border_margin", "lower_contacts", "upper_contacts", "n_outside")}}
