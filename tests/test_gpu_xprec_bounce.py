@@ -7,87 +7,36 @@ import numpy as np
 import pytest
 
 import xprec_bounce_cases as bc
+import xprec_check as xk
+import xprec_device as xd
 import xprec_model as xm
-import xprec_pairs_cases as pc
 from constraint_solver_amd import capi
 from golden_util import bits_equal
 
 pytestmark = pytest.mark.gpu
 
-SMALL_WORLD = 16384          # xpbd_contacts.hip: up to this many bodies the pair solve runs eight lanes per body
 SCENE_NAMES = list(bc.SCENES)
-SCHEDULES = (capi.SAT_SCHEDULE_AUTO, capi.SAT_SCHEDULE_ONE_PASS, capi.SAT_SCHEDULE_TWO_PASS)
 SEAM_SCENES = ["bounce-h1200", "jointed-h1200", "lifts-h1200", "wheels-h1200", "terrain-h1200-on"]
 
 
-def far_field(far):
-    """That many boxes on a 4 m grid 200 m away (test_gpu_xprec_drives.far_field)."""
-    if not far:
-        return np.zeros((0, 38)), np.zeros(0, dtype=np.uint32)
-    extra, extra_sid = capi.scene_generate(capi.SCENE_BOXES, 9, far)
-    k = np.arange(far)
-    extra[:, 31], extra[:, 32] = 200.0 + 4.0 * (k % 128), 4.0 * (k // 128)
-    extra[:, 22:25] *= 0.3
-    return extra, extra_sid
-
-
-def prepare(w, s, start, extra, sid, without=()):
-    w.upload(np.concatenate([start, extra]), sid)
-    if len(s["joints"]):
-        w.set_joints(s["joints"])
-    if len(s["limits"]):
-        w.set_joint_limits(s["limits"])
-    if len(s["drives"]):
-        w.set_joint_drives(s["drives"])
-    if s["speed"]:
-        w.set_max_depenetration_speed(s["speed"])
-    if s["mu"] is not None:
-        w.set_materials(np.concatenate([s["mu"], np.full(len(extra), np.inf)]), s["ground_mu"])
-    if s["bouncing"] and "restitution" not in without:
-        w.set_restitution(np.concatenate([s["e"], np.zeros(len(extra))]), s["ground_e"], s["threshold"])
-    field = None if "terrain" in without else s["terrain"]
-    if field is None:
-        w.set_terrain(None)
-    else:
-        w.set_terrain(field["heights"] * 0.0 if "flat" in without else field["heights"], field["origin"], field["cell"])
-
-
-def run(name, schedule=capi.SAT_SCHEDULE_AUTO, far=0, without=(), frames=None):
+def run(name, **kw):
     """Every single-substep frame of the scene on the device, each from the scene's state at its start."""
     t = bc.trajectory(name)
-    extra, extra_sid = far_field(far)
-    out = []
-    with capi.World(mode=capi.MODE_CONTACTS) as w:
-        w.set_polytopes(pc.capi_polytopes(capi))
-        w.set_narrowphase(capi.NARROWPHASE_SAT)
-        w.set_sat_schedule(schedule)
-        for start, _, _, s in t["frames"][:frames]:
-            sid = np.concatenate([s["sid"], extra_sid]).astype(np.uint32)
-            prepare(w, s, start, extra, sid, without)
-            w.step(s["h"], 1)
-            out.append(w.download()[:len(start)])
-    return t, out
+    return t, xd.run_frames([(fr[0], fr[3]) for fr in t["frames"]], **kw)
 
 
-def verdict(name, got):
-    """The model's bound and the exclusion caps on this run."""
-    errs, excl, entry = bc.check_states(name, got)
-    bc.assert_caps(name, excl, entry)
-    print("%s: device against the model %.1f" % (name, bc.worst(errs, excl)))
-
-
-@pytest.mark.parametrize("schedule", SCHEDULES, ids=["auto", "one-pass", "two-pass"])
+@pytest.mark.parametrize("schedule", xd.SAT_SCHEDULES, ids=xd.SCHEDULE_IDS)
 @pytest.mark.parametrize("name", SCENE_NAMES)
 def test_bouncing_and_terrain_scenes(name, schedule):
     _, got = run(name, schedule=schedule)
-    verdict(name, got)
+    xd.verdict(bc, name, got)
 
 
 @pytest.mark.parametrize("name", ["bounce-h1200", "jointed-h240", "lifts-h240", "chain-h1200", "terrain-h240-on"])
 def test_behind_a_far_field_uses_one_lane_per_body(name):
     """Scenes (a), (e) and (g) with more than SMALL_WORLD bodies in the world: the same verdict, and the small world's bits."""
-    _, got = run(name, far=SMALL_WORLD + 16)
-    verdict(name, got)
+    _, got = run(name, far=xd.SMALL_WORLD + 16)
+    xd.verdict(bc, name, got)
     _, small = run(name)
     for f in range(len(got)):
         assert bits_equal(got[f], small[f]), f
@@ -122,27 +71,13 @@ def test_four_substeps_in_one_step_equal_four_steps_and_the_split_api(name):
     t = bc.trajectory(name)
     start, _, _, s = t["frames"][0]
     h = s["h"]
-    none = far_field(0)[0]
-    with capi.World(mode=capi.MODE_CONTACTS) as w:
-        w.set_polytopes(pc.capi_polytopes(capi))
-        w.set_narrowphase(capi.NARROWPHASE_SAT)
-        prepare(w, s, start, none, s["sid"])
-        w.step(4 * h, 4)
-        fused = w.download()
-        prepare(w, s, start, none, s["sid"])
-        for _ in range(4):
-            w.step(h, 1)
-        single = w.download()
-        prepare(w, s, start, none, s["sid"])
-        w.contacts_begin(4 * h)
-        for _ in range(4):
-            w.contacts_substep(h)
-        split = w.download()
+    with xd.new_world() as w:
+        fused, single, split = xd.seam_runs(w, lambda: xd.prepare(w, s, start), h)
     state = start
     for _ in range(4):
         res = bc.model(name, 0, state=state)
         state = xm.native().to_f64(res["state"])
-    e = pc.normalized_errors(fused, res["state"], start, s["ext"], h, bc.links(name, 0, res))
+    e = xk.scene_errors(s, fused, res, start)
     print("%s: four substeps against the model chained four times %.1f" % (name, e.max()))
     assert np.abs(fused - start)[:, 31:38].max() > 1e-4
     assert bits_equal(fused, single)

@@ -7,84 +7,37 @@ in a world whose mass rows were edited in place."""
 import numpy as np
 import pytest
 
+import xprec_check as xk
 import xprec_damping_cases as dcs
+import xprec_device as xd
 import xprec_model as xm
 import xprec_pairs_cases as pc
 from constraint_solver_amd import capi
 from golden_util import bits_equal
-from test_gpu_xprec_bounce import SMALL_WORLD, far_field
 
 pytestmark = pytest.mark.gpu
 
 SCENE_NAMES = list(dcs.SCENES)
-SCHEDULES = (capi.SAT_SCHEDULE_AUTO, capi.SAT_SCHEDULE_ONE_PASS, capi.SAT_SCHEDULE_TWO_PASS)
 
 
-def settings(w, s, n_extra=0, without=(), kinematics=None):
-    """Everything but the bodies, in the order the setters allow: set_joints clears the dampers, upload everything."""
-    if len(s["joints"]):
-        w.set_joints(s["joints"])
-    if len(s["limits"]):
-        w.set_joint_limits(s["limits"])
-    if len(s["drives"]):
-        w.set_joint_drives(s["drives"])
-    if s["mu"] is not None:
-        w.set_materials(np.concatenate([s["mu"], np.full(n_extra, np.inf)]), s["ground_mu"])
-    w.set_restitution(np.concatenate([s["e"], np.zeros(n_extra)]), s["ground_e"], s["threshold"])
-    if s["rows"] is not None and "damping" not in without:
-        w.set_damping(np.concatenate([s["rows"], capi.body_damping(n_extra)]))
-    if s["dampers"] is not None and "joint_damping" not in without:
-        w.set_joint_damping(s["dampers"])
-    if s["kinematics"] is not None and "kinematics" not in without:
-        w.set_kinematics(s["kinematics"] if kinematics is None else kinematics)
-
-
-def prepare(w, s, start, extra, sid, without=(), kinematics=None):
-    w.upload(np.concatenate([start, extra]), sid)
-    settings(w, s, len(extra), without, kinematics)
-
-
-def new_world(schedule=capi.SAT_SCHEDULE_AUTO):
-    w = capi.World(mode=capi.MODE_CONTACTS)
-    w.set_polytopes(pc.capi_polytopes(capi))
-    w.set_narrowphase(capi.NARROWPHASE_SAT)
-    w.set_sat_schedule(schedule)
-    return w
-
-
-def run(name, schedule=capi.SAT_SCHEDULE_AUTO, far=0, without=(), frames=None):
+def run(name, **kw):
     """Every single-substep frame of the scene on the device, each from the scene's state at its start."""
     t = dcs.trajectory(name)
-    extra, extra_sid = far_field(far)
-    out = []
-    with new_world(schedule) as w:
-        for start, _, _, s in t["frames"][:frames]:
-            sid = np.concatenate([s["sid"], extra_sid]).astype(np.uint32)
-            prepare(w, s, start, extra, sid, without)
-            w.step(s["h"], 1)
-            out.append(w.download()[:len(start)])
-    return t, out
+    return t, xd.run_frames([(fr[0], fr[3]) for fr in t["frames"]], **kw)
 
 
-def verdict(name, got):
-    """The model's bound and the exclusion caps on this run."""
-    errs, excl, entry = dcs.check_states(name, got)
-    dcs.assert_caps(name, excl, entry)
-    print("%s: device against the model %.1f" % (name, dcs.worst(errs, excl)))
-
-
-@pytest.mark.parametrize("schedule", SCHEDULES, ids=["auto", "one-pass", "two-pass"])
+@pytest.mark.parametrize("schedule", xd.SAT_SCHEDULES, ids=xd.SCHEDULE_IDS)
 @pytest.mark.parametrize("name", SCENE_NAMES)
 def test_damped_and_kinematic_scenes(name, schedule):
     _, got = run(name, schedule=schedule)
-    verdict(name, got)
+    xd.verdict(dcs, name, got)
 
 
 @pytest.mark.parametrize("name", ["drag-h1200", "jointed-h240", "chain-h1200", "platforms-h240"])
 def test_behind_a_far_field_uses_one_lane_per_body(name):
     """Scenes (a), (c) and (e) with more than SMALL_WORLD bodies in the world: the same verdict, and the small world's bits."""
-    _, got = run(name, far=SMALL_WORLD + 16)
-    verdict(name, got)
+    _, got = run(name, far=xd.SMALL_WORLD + 16)
+    xd.verdict(dcs, name, got)
     _, small = run(name)
     for f in range(len(got)):
         assert bits_equal(got[f], small[f]), f
@@ -115,25 +68,13 @@ def test_four_substeps_in_one_step_equal_four_steps_and_the_split_api(name):
     contract, not stage 7's, and the figure printed for `chain` is accordingly large."""
     start, _, _, s = dcs.trajectory(name)["frames"][0]
     h = s["h"]
-    none = far_field(0)[0]
-    with new_world() as w:
-        prepare(w, s, start, none, s["sid"])
-        w.step(4 * h, 4)
-        fused = w.download()
-        prepare(w, s, start, none, s["sid"])
-        for _ in range(4):
-            w.step(h, 1)
-        single = w.download()
-        prepare(w, s, start, none, s["sid"])
-        w.contacts_begin(4 * h)
-        for _ in range(4):
-            w.contacts_substep(h)
-        split = w.download()
+    with xd.new_world() as w:
+        fused, single, split = xd.seam_runs(w, lambda: xd.prepare(w, s, start), h)
     state = start
     for _ in range(4):
         res = dcs.model(name, 0, state=state)
         state = xm.native().to_f64(res["state"])
-    e = pc.normalized_errors(fused, res["state"], start, s["ext"], h, dcs.links(s, res))
+    e = xk.scene_errors(s, fused, res, start)
     print("%s: four substeps against the model chained four times %.1f" % (name, e.max()))
     assert np.abs(fused - start)[:, 31:38].max() > 1e-4
     assert bits_equal(fused, split)
@@ -148,16 +89,9 @@ def test_velocity_entries_are_reasserted_at_every_substep_and_the_split_api_is_r
     h = s["h"]
     only = s["kinematics"][s["kinematics"]["mode"] == capi.KINEMATIC_VELOCITY]
     assert len(only) == 2
-    none = far_field(0)[0]
-    with new_world() as w:
-        prepare(w, s, start, none, s["sid"], kinematics=only)
-        w.step(4 * h, 4)
-        fused = w.download()
-        prepare(w, s, start, none, s["sid"], kinematics=only)
-        for _ in range(4):
-            w.step(h, 1)
-        single = w.download()
-        prepare(w, s, start, none, s["sid"], kinematics=only)
+    with xd.new_world() as w:
+        fused, single, _ = xd.seam_runs(w, lambda: xd.prepare(w, s, start, kinematics=only), h, split=False)
+        xd.prepare(w, s, start, kinematics=only)
         with pytest.raises(capi.XpbdError) as err:
             w.contacts_begin(4 * h)
         assert err.value.code == capi.E_INVALID
@@ -186,7 +120,7 @@ def test_lone_pose_entries_arrive_within_the_models_bound(substeps):
     substeps_left = S - k, within K_LONE[S] -- 8x the f64 evaluation's error against that chain, measured on the CPU."""
     bodies, sid, kin = dcs.lone_scene()
     ref, bad = dcs.lone_chain(substeps)
-    with new_world() as w:
+    with xd.new_world() as w:
         w.upload(bodies, sid)
         w.set_kinematics(kin)
         w.step(dcs.LONE_DT, substeps)
@@ -203,15 +137,15 @@ def test_a_platform_scene_stepped_with_four_substeps_is_printed_against_the_chai
     name = "platforms-h1200"
     start, _, _, s = dcs.trajectory(name)["frames"][0]
     h = s["h"]
-    with new_world() as w:
-        prepare(w, s, start, far_field(0)[0], s["sid"])
+    with xd.new_world() as w:
+        xd.prepare(w, s, start)
         w.step(4 * h, 4)
         got = w.download()
     state = start
     for k in range(4):
         res = dcs.model(name, 0, state=state, substeps_left=4 - k, substep_index=k)
         state = xm.native().to_f64(res["state"])
-    e = pc.normalized_errors(got, res["state"], start, s["ext"], h, dcs.links(s, res))
+    e = xk.scene_errors(s, got, res, start)
     print("%s: four substeps against the model chained four times: largest %.3g, median %.3g" % (name, e.max(), np.median(e)))
     assert np.isfinite(got).all()
 
@@ -223,9 +157,8 @@ def test_scene_f_in_a_world_whose_mass_rows_were_edited_in_place():
     name = "all-h240"
     t = dcs.trajectory(name)
     unit = pc.new_body(pc.CUBE, (0.0, 0.0, 0.0))
-    none = far_field(0)[0]
     edited, uploaded = [], []
-    with new_world() as w:
+    with xd.new_world() as w:
         for start, _, _, s in t["frames"]:
             kin = s["kinematics"]["body"].astype(np.int64)
             rows = np.concatenate([start[:, 0:10], start[:, 28:31]], axis=1)
@@ -233,7 +166,7 @@ def test_scene_f_in_a_world_whose_mass_rows_were_edited_in_place():
             plain = start.copy()
             plain[:, 0:10], plain[:, 28:31] = unit[0:10], unit[28:31]
             w.upload(plain, s["sid"])
-            settings(w, s, without=("kinematics",))
+            xd.apply_settings(w, s, without=("kinematics",))
             first = rows.copy()
             first[kin, 0:10] = unit[0:10]
             w.set_mass_properties(None, first, capi.MASS_INVERSE)
@@ -244,9 +177,9 @@ def test_scene_f_in_a_world_whose_mass_rows_were_edited_in_place():
             assert np.array_equal(w.get_mass_properties(), rows)
             w.step(s["h"], 1)
             edited.append(w.download())
-            prepare(w, s, start, none, s["sid"])
+            xd.prepare(w, s, start)
             w.step(s["h"], 1)
             uploaded.append(w.download())
-    verdict(name, edited)
+    xd.verdict(dcs, name, edited)
     for f in range(len(edited)):
         assert bits_equal(edited[f], uploaded[f]), f

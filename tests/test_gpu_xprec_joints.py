@@ -5,6 +5,7 @@ the one-lane-per-body path."""
 import numpy as np
 import pytest
 
+import xprec_device as xd
 import xprec_joints_cases as jc
 import xprec_pairs_cases as pc
 from constraint_solver_amd import capi
@@ -12,39 +13,13 @@ from golden_util import bits_equal
 
 pytestmark = pytest.mark.gpu
 
-SMALL_WORLD = 16384          # xpbd_contacts.hip: up to this many bodies the pair solve runs eight lanes per body
 SCENE_NAMES = list(jc.SCENES)
-SCHEDULES = (capi.SAT_SCHEDULE_AUTO, capi.SAT_SCHEDULE_ONE_PASS, capi.SAT_SCHEDULE_TWO_PASS)
 
 
-def run(name, schedule=capi.SAT_SCHEDULE_AUTO, far=0):
-    """Every single-substep frame of the scene on the device, each from the trajectory's state at its start.  far: that many
-    boxes on a 4 m grid 200 m away, behind the scene's bodies (test_gpu_xprec_pairs.run)."""
+def run(name, **kw):
+    """Every single-substep frame of the scene on the device, each from the trajectory's state at its start."""
     t = jc.trajectory(name)
-    n = len(t["sid"])
-    extra, extra_sid = capi.scene_generate(capi.SCENE_BOXES, 9, far) if far else (np.zeros((0, 38)), np.zeros(0, dtype=np.uint32))
-    if far:
-        k = np.arange(far)
-        extra[:, 31], extra[:, 32] = 200.0 + 4.0 * (k % 128), 4.0 * (k // 128)
-        extra[:, 22:25] *= 0.3
-    sid = np.concatenate([t["sid"], extra_sid]).astype(np.uint32)
-    out = []
-    with capi.World(mode=capi.MODE_CONTACTS) as w:
-        w.set_polytopes(pc.capi_polytopes(capi))
-        w.set_narrowphase(capi.NARROWPHASE_SAT)
-        w.set_sat_schedule(schedule)
-        for start, *_ in t["frames"]:
-            w.upload(np.concatenate([start, extra]), sid)
-            w.set_joints(t["joints"])
-            if len(t["limits"]):
-                w.set_joint_limits(t["limits"])
-            if t["speed"]:
-                w.set_max_depenetration_speed(t["speed"])
-            if t["mu"] is not None:
-                w.set_materials(np.concatenate([t["mu"], np.full(far, np.inf)]), t["ground_mu"])
-            w.step(t["h"], 1)
-            out.append(w.download()[:n])
-    return t, out
+    return t, xd.run_frames([(fr[0], t) for fr in t["frames"]], **kw)
 
 
 def verdict(name, t, got):
@@ -52,13 +27,10 @@ def verdict(name, t, got):
     if name in jc.ORACLE_SCENES:
         for f, fr in enumerate(t["frames"]):
             assert bits_equal(got[f], fr[1]), "state differs from the oracle in substep %d" % f
-    errs, excl, mixed = jc.check_states(name, got)
-    jc.assert_caps(name, excl, mixed)
-    print("%s: device against the model %.1f" % (name, np.where(excl, 0, errs).max()))
-    return errs, excl
+    xd.verdict(jc, name, got)
 
 
-@pytest.mark.parametrize("schedule", SCHEDULES, ids=["auto", "one-pass", "two-pass"])
+@pytest.mark.parametrize("schedule", xd.SAT_SCHEDULES, ids=xd.SCHEDULE_IDS)
 @pytest.mark.parametrize("name", SCENE_NAMES)
 def test_jointed_scenes(name, schedule):
     t, got = run(name, schedule=schedule)
@@ -69,7 +41,7 @@ def test_jointed_scenes(name, schedule):
 def test_behind_a_far_field_uses_one_lane_per_body(name):
     """The same verdicts with more than SMALL_WORLD bodies in the world, and the same bits as the small world's run: the
     one-lane path adds the same terms in the same order."""
-    t, got = run(name, far=SMALL_WORLD + 16)
+    t, got = run(name, far=xd.SMALL_WORLD + 16)
     verdict(name, t, got)
     _, small = run(name)
     for f in range(len(got)):
@@ -80,9 +52,9 @@ def test_behind_a_far_field_uses_one_lane_per_body(name):
 def test_limits_change_the_device_result(name):
     """Without set_joint_limits the device leaves the bound of the model with limits: the check sees the limits."""
     t = jc.trajectory(name)
+    start, _, res, _ = t["frames"][0]
     with capi.World(mode=capi.MODE_CONTACTS) as w:
         w.set_polytopes(pc.capi_polytopes(capi))
-        start, _, res, _ = t["frames"][0]
         w.upload(start, t["sid"])
         w.set_joints(t["joints"])
         w.step(t["h"], 1)

@@ -5,42 +5,21 @@ centre of mass, inverse mass 0 and 1e+-6, |x| = 1e4 m, fast spin) meet the pair 
 import numpy as np
 import pytest
 
+import xprec_device as xd
 import xprec_pairs_cases as pc
 from constraint_solver_amd import capi
 from golden_util import bits_equal
 
 pytestmark = pytest.mark.gpu
 
-SMALL_WORLD = 16384          # xpbd_contacts.hip: up to this many bodies the pair solve runs eight lanes per body
 SCENE_NAMES = list(pc.SCENES)
-SCHEDULES = (capi.SAT_SCHEDULE_AUTO, capi.SAT_SCHEDULE_ONE_PASS, capi.SAT_SCHEDULE_TWO_PASS)
 
 
-def run(name, narrowphase=capi.NARROWPHASE_SAT, schedule=capi.SAT_SCHEDULE_AUTO, far=0):
+def run(name, **kw):
     """Every single-substep frame of the scene on the device, each from the oracle's state at its start (for (b): from its
-    fresh exact configuration).  far: that many boxes on a 4 m grid 200 m away, behind the scene's bodies."""
+    fresh exact configuration)."""
     t = pc.trajectory(name)
-    n = len(t["sid"])
-    extra, extra_sid = capi.scene_generate(capi.SCENE_BOXES, 9, far) if far else (np.zeros((0, 38)), np.zeros(0, dtype=np.uint32))
-    if far:
-        k = np.arange(far)
-        extra[:, 31], extra[:, 32] = 200.0 + 4.0 * (k % 128), 4.0 * (k // 128)
-        extra[:, 22:25] *= 0.3
-    sid = np.concatenate([t["sid"], extra_sid]).astype(np.uint32)
-    out = []
-    with capi.World(mode=capi.MODE_CONTACTS) as w:
-        w.set_polytopes(pc.capi_polytopes(capi))
-        w.set_narrowphase(narrowphase)
-        w.set_sat_schedule(schedule)
-        for start, *_ in t["frames"]:
-            w.upload(np.concatenate([start, extra]), sid)
-            if t["speed"]:
-                w.set_max_depenetration_speed(t["speed"])
-            if t["mu"] is not None:
-                w.set_materials(np.concatenate([t["mu"], np.full(far, np.inf)]), t["ground_mu"])
-            w.step(t["h"], 1)
-            out.append(w.download()[:n])
-    return t, out
+    return t, xd.run_frames([(fr[0], t) for fr in t["frames"]], **kw)
 
 
 def assert_oracle(t, got):
@@ -89,7 +68,7 @@ def test_narrowphase_on_the_scenes_frames(name):
     assert checked >= 6 and tiled
 
 
-@pytest.mark.parametrize("schedule", SCHEDULES, ids=["auto", "one-pass", "two-pass"])
+@pytest.mark.parametrize("schedule", xd.SAT_SCHEDULES, ids=xd.SCHEDULE_IDS)
 @pytest.mark.parametrize("name", SCENE_NAMES)
 def test_sat_trajectories(name, schedule):
     """MODE_CONTACTS, SAT, every schedule; the pile scenes with set_materials and set_max_depenetration_speed."""
@@ -121,7 +100,7 @@ def test_gjk_epa_trajectories(name):
 
 @pytest.mark.parametrize("name", [s for s in SCENE_NAMES if s.startswith("pile")])
 def test_pile_behind_a_far_field_uses_one_lane_per_body(name):
-    t, got = run(name, far=SMALL_WORLD + 16)
+    t, got = run(name, far=xd.SMALL_WORLD + 16)
     assert_oracle(t, got)
     pc.check_states(name, got)
 

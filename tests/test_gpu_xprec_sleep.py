@@ -13,13 +13,14 @@ import numpy as np
 import pytest
 
 import islands_model as im
+import xprec_check as xk
+import xprec_device as xd
 import xprec_model as xm
 import xprec_pairs_cases as pc
 import xprec_sleep_cases as sc
 from constraint_solver_amd import capi
 from golden_util import bits_equal
 from sleep_common import DYN
-from test_gpu_xprec_bounce import SMALL_WORLD, far_field
 
 pytestmark = pytest.mark.gpu
 
@@ -41,13 +42,6 @@ CHAIN_FRAMES = 4
 _MODEL = {}
 
 
-def new_world(narrowphase=capi.NARROWPHASE_SAT):
-    w = capi.World(mode=capi.MODE_CONTACTS)
-    w.set_polytopes(pc.capi_polytopes(capi))
-    w.set_narrowphase(narrowphase)
-    return w
-
-
 def reach(w, s, schedule="natural", far=0, sleeping=True):
     """Uploads, sleeps, downloads and moves the probes into place.  Returns the state at the start of the frame under test (the
     scene's bodies), the sleepers' contact masks and the sleep state (asleep, group) before that frame."""
@@ -57,7 +51,7 @@ def reach(w, s, schedule="natural", far=0, sleeping=True):
     parked[probes, 31], parked[probes, 32], parked[probes, 33] = -500.0 - 50.0 * np.arange(len(probes)), -500.0, 300.0
     parked[probes, 22:25], parked[probes, 25:28] = (PARK_SPEED, 0.0, 0.0), 0.0
     post = pc.new_body(pc.CUBE, (-1000.0, 500.0, 50.0), static=True)
-    extra, extra_sid = far_field(far)
+    extra, extra_sid = xd.far_field(far)
     m = 1 + len(extra)
     w.upload(np.concatenate([parked, post[None], extra]), np.concatenate([s["sid"], [pc.CUBE], extra_sid]).astype(np.uint32))
     w.set_contact_report(True)
@@ -106,7 +100,7 @@ def run(name, schedule="natural", substeps=1, far=0, frames=sc.FRAMES):
     """Every frame of the scene on the device: (start, state after the frame, model result, excluded, carries) per frame, with the
     sleepers' frozen bits, the asleep set before the frame and the wake after it asserted on the way."""
     out = []
-    with new_world() as w:
+    with xd.new_world() as w:
         for f in range(frames):
             s = sc.build(name, f)
             n = len(s["sid"])
@@ -138,14 +132,12 @@ def run(name, schedule="natural", substeps=1, far=0, frames=sc.FRAMES):
 
 def verdict(name, frames, substeps=1):
     """The model's bound and the caps on this run; returns the largest normalised error of a checked body."""
-    errs, excl, entry = [], [], []
-    for f, (start, got, res, x, c, links, s) in enumerate(frames):
-        e = sc.errors(s, got, res, start) if substeps == 1 else sc.chain_errors(s, got, res, start, links, substeps)
-        bound = sc.bounds(res) if substeps == 1 else np.full(len(e), sc.K_SLEEP_CHAIN[substeps])
-        bad = np.nonzero(~x & ~(e <= bound))[0]
-        assert not len(bad), "%s frame %d: bodies %s (%s) beyond K = %s: %s" % (name, f, bad[:8], s["labels"][bad[:8]], bound[bad[:8]], e[bad[:8]])
-        errs.append(e), excl.append(x), entry.append(c)
-    worst = sc.worst(errs, excl)
+    errs, excl, entry = xk.check_frames(
+        name, [(start, res, dict(s, excluded=x, carries=c, links=links)) for start, _, res, x, c, links, s in frames],
+        [fr[1] for fr in frames], excluded=lambda res, s: s["excluded"], carries=lambda res, s: s["carries"],
+        errors=xk.scene_errors if substeps == 1 else lambda s, got, res, start: sc.chain_errors(s, got, res, start, s["links"], substeps),
+        bound=sc.bounds if substeps == 1 else lambda res: sc.K_SLEEP_CHAIN[substeps])
+    worst = xk.worst(errs, excl)
     print("%s, S = %d: device against the model %.1f" % (name, substeps, worst))
     return worst, excl, entry
 
@@ -155,7 +147,7 @@ def verdict(name, frames, substeps=1):
 def test_awake_bodies_against_sleepers(name, schedule):
     frames = run(name, schedule)
     _, excl, entry = verdict(name, frames)
-    sc.assert_caps(name, excl, entry)
+    xk.assert_caps(name, excl, entry, floor=sc.caps_floor(name))
     if schedule != "natural":                                                # the three schedules give one another's bits
         for a, b in zip(frames, run(name)):
             assert bits_equal(a[0], b[0]) and bits_equal(a[1], b[1])
@@ -183,8 +175,7 @@ def test_frames_of_several_substeps_against_the_chained_model(name, substeps):
     longdouble chain); and the three schedules' bits."""
     frames = run(name, substeps=substeps, frames=CHAIN_FRAMES)
     _, excl, entry = verdict(name, frames, substeps)
-    x, c = np.concatenate(excl), np.concatenate(entry)
-    assert x.mean() <= 0.10 and (x & c).sum() <= 0.10 * c.sum() and (c & ~x).sum() >= 20
+    xk.assert_caps(name, excl, entry)
     for schedule in SCHEDULES[1:]:
         for a, b in zip(frames, run(name, schedule, substeps=substeps, frames=CHAIN_FRAMES)):
             assert bits_equal(a[0], b[0]) and bits_equal(a[1], b[1]), schedule
@@ -202,7 +193,7 @@ def test_twenty_substeps_on_the_stack_give_the_same_bits_under_every_schedule():
 @pytest.mark.parametrize("name", ["general-h1200", "stack-h240", "bouncing-h240"])
 def test_behind_a_far_field_uses_one_lane_per_body(name):
     """Scenes (a), (c) and (e) with more than SMALL_WORLD bodies in the world: the same verdict, and the small world's bits."""
-    frames = run(name, far=SMALL_WORLD + 16, frames=CHAIN_FRAMES)
+    frames = run(name, far=xd.SMALL_WORLD + 16, frames=CHAIN_FRAMES)
     _, excl, entry = verdict(name, frames)
     for a, b in zip(frames, run(name, frames=CHAIN_FRAMES)):
         assert bits_equal(a[0], b[0]) and bits_equal(a[1], b[1])
@@ -215,7 +206,7 @@ def test_gjk_epa_on_the_manifolds_the_model_can_reproduce(name):
     depth and normal are stage N's), on at least half of the touching body-substeps; every sleeper bit-frozen."""
     checked = total = 0
     worst = 0.0
-    with new_world(capi.NARROWPHASE_GJK_EPA) as w:
+    with xd.new_world(narrowphase=capi.NARROWPHASE_GJK_EPA) as w:
         for f in range(sc.FRAMES):
             s = sc.build(name, f)
             n, z = len(s["sid"]), s["asleep"]
@@ -240,7 +231,7 @@ def test_without_set_sleeping_the_same_frames_leave_the_bound():
     name = "general-h1200"
     frames = run(name, frames=2)
     worst = 0.0
-    with new_world() as w:
+    with xd.new_world() as w:
         for f, (start, _, res, x, c, links, s) in enumerate(frames):
             reach(w, dict(s, bodies=start), sleeping=False)
             w.step(s["h"], 1)

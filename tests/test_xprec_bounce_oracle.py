@@ -10,13 +10,13 @@ import oracle_binding as ob
 import restitution_model as rm
 import terrain_model as tm
 import xprec_bounce_cases as bc
+import xprec_check as xk
 import xprec_model as xm
 import xprec_pairs_cases as pc
 import xprec_pairs_model as pm
 from constraint_solver_amd import capi
 from golden_util import bits_equal
 from halo_common import POLY_NAMES, pile
-from test_xprec_joints_oracle import lifted
 
 SCENE_NAMES = list(bc.SCENES)
 
@@ -34,8 +34,8 @@ def test_f64_reading_against_the_model_frame_by_frame(name):
     errs, excl, entry = bc.check_states(name, f64_states(name))
     x, c = np.concatenate(excl), np.concatenate(entry)
     print("%s: f64 evaluation %.1f; excluded %d of %d body-substeps, %d of %d with a stage-6 entry%s" % (
-        name, bc.worst(errs, excl), x.sum(), x.size, (x & c).sum(), c.sum(), " (terrain contact)" if name.startswith("terrain") else ""))
-    bc.assert_caps(name, excl, entry)
+        name, xk.worst(errs, excl), x.sum(), x.size, (x & c).sum(), c.sum(), " (terrain contact)" if name.startswith("terrain") else ""))
+    xk.assert_caps(name, excl, entry)
     for f, (start, want, res, s) in enumerate(t["frames"]):
         assert len(start) <= bc.MAX_BODIES and not np.isnan(want).any()
         if name.startswith("exact"):
@@ -138,16 +138,16 @@ def test_longdouble_model_equals_mpmath_model(name):
     f = int(np.argmax(per_frame))
     start, _, res, s = t["frames"][f]
     given = {key: m for key, m in res["manifolds"].items() if m["p_ref"]}
-    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [lifted(ref, p) for p in m["p_ref"]],
-                   "p_inc": [lifted(ref, p) for p in m["p_inc"]], **({"normal": lifted(ref, m["normal"])} if "normal" in m else {})}
+    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [xm.lifted(ref, p) for p in m["p_ref"]],
+                   "p_inc": [xm.lifted(ref, p) for p in m["p_inc"]], **({"normal": xm.lifted(ref, m["normal"])} if "normal" in m else {})}
              for key, m in given.items()}
     a = bc.model(name, f, num=fast, manifolds=given)
     b = bc.model(name, f, num=ref, manifolds=exact)
     for key in ("mask", "bounce_pair_entries", "bounce_ground_entries"):      # (a converged point's later visits are +-rounding)
         if key in a:
             assert np.array_equal(a[key], b[key]), key
-    d = np.abs(ref.to_f64(lifted(ref, a["state"]) - b["state"]))
-    scale = pc.scales(start, fast.to_f64(a["state"]), s["ext"], bc.links(name, f, res))
+    d = np.abs(ref.to_f64(xm.lifted(ref, a["state"]) - b["state"]))
+    scale = pc.scales(start, fast.to_f64(a["state"]), s["ext"], xk.joint_links(s, res))
     turn = scale / s["ext"]
     h = s["h"]
     e = np.max(np.stack([d[:, 31:34].max(axis=1) / (pc.EPS * scale), d[:, 34:38].max(axis=1) / (pc.EPS * turn),

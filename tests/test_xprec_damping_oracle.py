@@ -12,13 +12,13 @@ import kinematic_common as kc
 import kinematic_model as km
 import restitution_model as rm
 import xprec_bounce_cases as bc
+import xprec_check as xk
 import xprec_damping_cases as dcs
 import xprec_model as xm
 import xprec_pairs_cases as pc
 import xprec_pairs_model as pm
 from constraint_solver_amd import capi
 from golden_util import bits_equal
-from test_xprec_joints_oracle import lifted
 
 SCENE_NAMES = list(dcs.SCENES)
 
@@ -36,8 +36,8 @@ def test_f64_reading_against_the_model_frame_by_frame(name):
     errs, excl, entry = dcs.check_states(name, f64_states(name))
     x, c = np.concatenate(excl), np.concatenate(entry)
     print("%s: f64 evaluation %.1f; excluded %d of %d body-substeps, %d of %d that carry a damper entry or a fired cap" % (
-        name, dcs.worst(errs, excl), x.sum(), x.size, (x & c).sum(), c.sum()))
-    dcs.assert_caps(name, excl, entry)
+        name, xk.worst(errs, excl), x.sum(), x.size, (x & c).sum(), c.sum()))
+    xk.assert_caps(name, excl, entry)
     for f, (start, want, res, s) in enumerate(t["frames"]):
         assert len(start) <= dcs.MAX_BODIES and not np.isnan(want).any()
         if name.startswith("drag"):
@@ -114,8 +114,8 @@ def test_longdouble_model_equals_mpmath_model(name):
     f = int(np.argmax(per_frame))
     start, _, res, s = t["frames"][f]
     given = {key: m for key, m in res["manifolds"].items() if m["p_ref"]}
-    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [lifted(ref, p) for p in m["p_ref"]],
-                   "p_inc": [lifted(ref, p) for p in m["p_inc"]], **({"normal": lifted(ref, m["normal"])} if "normal" in m else {})}
+    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [xm.lifted(ref, p) for p in m["p_ref"]],
+                   "p_inc": [xm.lifted(ref, p) for p in m["p_inc"]], **({"normal": xm.lifted(ref, m["normal"])} if "normal" in m else {})}
              for key, m in given.items()}
     a = dcs.model(name, f, num=fast, manifolds=given)
     b = dcs.model(name, f, num=ref, manifolds=exact)
@@ -123,8 +123,8 @@ def test_longdouble_model_equals_mpmath_model(name):
                 "cap_fired_angular", "kin_zero", "kin_negated"):
         if key in a:
             assert np.array_equal(a[key], b[key]), key
-    d = np.abs(ref.to_f64(lifted(ref, a["state"]) - b["state"]))
-    scale = pc.scales(start, fast.to_f64(a["state"]), s["ext"], dcs.links(s, res))
+    d = np.abs(ref.to_f64(xm.lifted(ref, a["state"]) - b["state"]))
+    scale = pc.scales(start, fast.to_f64(a["state"]), s["ext"], xk.joint_links(s, res))
     turn = scale / s["ext"]
     h = s["h"]
     e = np.max(np.stack([d[:, 31:34].max(axis=1) / (pc.EPS * scale), d[:, 34:38].max(axis=1) / (pc.EPS * turn),
@@ -309,7 +309,7 @@ def against(step, state, shapes, sid, h, substeps, **settings):
         ext = r + 2 * np.linalg.norm(start[:, 28:31], axis=1)
         state = step(start, k)
         res = pm.substep(start, shapes, sid, h, None, tau=pc.TAU, **{key: value(k) if callable(value) else value for key, value in settings.items()})
-        e = pc.normalized_errors(state, res["state"], start, ext, h, dcs.links(scene, res))
+        e = pc.normalized_errors(state, res["state"], start, ext, h, xk.joint_links(scene, res))
         x = dcs.excluded(res, scene)
         worst = max(worst, float(np.where(x, 0, e / dcs.bounds(res)).max()))
         if "cap_fired_linear" in res:

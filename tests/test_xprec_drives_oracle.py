@@ -7,13 +7,13 @@ import numpy as np
 import pytest
 
 import joint_drive_model as jd
+import xprec_check as xk
 import xprec_drives_cases as dc
 import xprec_joints_cases as jc
 import xprec_model as xm
 import xprec_pairs_cases as pc
 import xprec_pairs_model as pm
 from constraint_solver_amd import capi
-from test_xprec_joints_oracle import lifted, momenta
 
 SCENE_NAMES = list(dc.SCENES)
 INF = float("inf")
@@ -25,9 +25,10 @@ def test_f64_reading_against_the_model_substep_by_substep(name):
     exclusion caps hold over all body-substeps and over those that carry both an extra entry and a pair or ground point."""
     t = dc.trajectory(name)
     errs, excl, mixed = dc.check_states(name, [fr[1] for fr in t["frames"]])
+    x, c = np.concatenate(excl), np.concatenate(mixed)
     print("%s: f64 evaluation %.1f; excluded %d of %d body-substeps, %d of %d with extra entry and contact point" % (
-        name, np.where(excl, 0, errs).max(), excl.sum(), excl.size, (excl & mixed).sum(), mixed.sum()))
-    dc.assert_caps(name, excl, mixed)
+        name, xk.worst(errs, excl), x.sum(), x.size, (x & c).sum(), c.sum()))
+    xk.assert_caps(name, excl, mixed)
     assert len(t["sid"]) <= dc.MAX_BODIES
     dynamic = t["bodies"][:, 0] > 0
     driven = np.zeros(len(t["sid"]), dtype=bool)
@@ -186,11 +187,11 @@ def test_longdouble_model_equals_mpmath_model(name):
     fast, ref = xm.native(), xm.mp(40)
     t = dc.trajectory(name)
     errs, excl, _ = dc.check_states(name, [fr[1] for fr in t["frames"]])
-    worst = int(np.where(excl, 0, errs).max(axis=1).argmax())
+    worst = int(np.argmax([np.where(x, 0, e).max() for e, x in zip(errs, excl)]))
     start, _, res, _ = t["frames"][worst]
     given = {key: m for key, m in res["manifolds"].items() if m["p_ref"]}
-    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [lifted(ref, p) for p in m["p_ref"]],
-                   "p_inc": [lifted(ref, p) for p in m["p_inc"]]} for key, m in given.items()}
+    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [xm.lifted(ref, p) for p in m["p_ref"]],
+                   "p_inc": [xm.lifted(ref, p) for p in m["p_inc"]]} for key, m in given.items()}
     a = dc.model(name, start, num=fast, manifolds=given)
     b = dc.model(name, start, num=ref, manifolds=exact)
     assert [(k, kind, err == 0) for k, kind, _, err in a["limits"]] == [(k, kind, err == 0) for k, kind, _, err in b["limits"]]
@@ -198,13 +199,13 @@ def test_longdouble_model_equals_mpmath_model(name):
     assert [(i, e == 0, c) for i, _, e, c, _ in a["drives"]] == [(i, e == 0, c) for i, _, e, c, _ in b["drives"]]
     for key in ("n_joint", "n_extra", "n_clamped", "mask"):
         assert np.array_equal(a[key], b[key]), key
-    d = np.abs(ref.to_f64(lifted(ref, a["state"]) - b["state"]))
-    scale = pc.scales(start, fast.to_f64(a["state"]), t["ext"], dc.links(name, res))
+    d = np.abs(ref.to_f64(xm.lifted(ref, a["state"]) - b["state"]))
+    scale = pc.scales(start, fast.to_f64(a["state"]), t["ext"], xk.joint_links(t, res))
     turn = scale / t["ext"]
     h = t["h"]
     e = np.max(np.stack([d[:, 31:34].max(axis=1) / (pc.EPS * scale), d[:, 34:38].max(axis=1) / (pc.EPS * turn),
                          d[:, 22:25].max(axis=1) * h / (pc.EPS * scale), d[:, 25:28].max(axis=1) * h / (pc.EPS * turn)]), axis=0)
-    top = np.where(excl, 0, errs).max()
+    top = xk.worst(errs, excl)
     print("%s substep %d: longdouble against mpmath %.4f = %.2g of the bound; the scene's maximum %.1f" % (
         name, worst, e.max(), e.max() / dc.K_DRIVES, top))
     assert e.max() <= dc.K_DRIVES / 2 ** 11 and e.max() <= 0.1 * top
@@ -281,14 +282,14 @@ def test_model_conserves_momentum_on_a_free_driven_pair(which):
     res = pm.substep(bodies, pc.table()[1], sid, pc.HS[1], {}, joints=joints, limits=lims, drives=drvs)
     assert res["n_extra"].min() >= (3 if which == "prismatic" else 1) and not res["n_points"].any() and not res["n_clamped"].any()
     before = num.conv(bodies)
-    lin, ang = momenta(num, before, res["state"], bodies)
+    lin, ang = xk.momenta(num, before, res["state"], bodies)
     moved = np.abs(num.to_f64(res["state"][:, 31:38] - before[:, 31:38])).max() / bodies[:, 0].min()
     assert moved > 1e-4
     assert np.abs(lin).max() <= max(1e-15 * moved, 8 * 9.0 * 2.0 ** -63), (lin, moved)      # or a few ulps of the model at 9 m
     assert np.abs(ang).max() <= 2e-2 * moved, (ang, moved)
     wrong = "angular_drive_same_sign" if which in ("angle", "angular-velocity") else "perpendicular_sign_a"
     bad = pm.substep(bodies, pc.table()[1], sid, pc.HS[1], {}, joints=joints, limits=lims, drives=drvs, mutation=wrong)
-    lin, ang = momenta(num, before, bad["state"], bodies)
+    lin, ang = xk.momenta(num, before, bad["state"], bodies)
     assert max(np.abs(lin).max(), np.abs(ang).max()) > 0.1 * moved
 
 

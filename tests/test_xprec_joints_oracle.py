@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import joint_limit_model as jm
+import xprec_check as xk
 import xprec_joints_cases as jc
 import xprec_model as xm
 import xprec_pairs_cases as pc
@@ -26,13 +27,14 @@ def test_f64_readings_against_the_model_substep_by_substep(name):
     have a binding limit and a pair-contact point."""
     t = jc.trajectory(name)
     errs, excl, mixed = jc.check_states(name, [fr[3] for fr in t["frames"]])
-    line = "%s: f64 evaluation %.1f" % (name, np.where(excl, 0, errs).max())
+    x, c = np.concatenate(excl), np.concatenate(mixed)
+    line = "%s: f64 evaluation %.1f" % (name, xk.worst(errs, excl))
     if name in jc.ORACLE_SCENES:
         errs_o, _, _ = jc.check_states(name, [fr[1] for fr in t["frames"]])
-        line += ", oracle %.1f" % np.where(excl, 0, errs_o).max()
+        line += ", oracle %.1f" % xk.worst(errs_o, excl)
     print("%s; excluded %d of %d body-substeps, %d of %d with joint entry and pair point" % (
-        line, excl.sum(), excl.size, (excl & mixed).sum(), mixed.sum()))
-    jc.assert_caps(name, excl, mixed)
+        line, x.sum(), x.size, (x & c).sum(), c.sum()))
+    xk.assert_caps(name, excl, mixed)
     kinds = set(t["joints"]["kind"].tolist())
     entries = sum(int(fr[2]["n_joint"].sum()) for fr in t["frames"])
     assert entries >= 2 * len(t["joints"])                               # the joints act
@@ -129,13 +131,6 @@ def test_the_contact_free_limit_model_lies_within_the_bound():
     assert worst <= jc.K_JOINTS and binding > 500 and left_out <= 0.10 * total
 
 
-def lifted(ref, a):
-    """A longdouble array in another scalar type, exactly: two doubles."""
-    hi = np.asarray(a).astype(np.float64)
-    lo = (a - hi.astype(a.dtype)).astype(np.float64)
-    return ref.conv(hi) + ref.conv(lo)
-
-
 @pytest.mark.parametrize("name", SCENE_NAMES)
 def test_longdouble_model_equals_mpmath_model(name):
     """The substep that holds the scene's largest error, stage S on the longdouble model's manifolds, in longdouble and in
@@ -145,23 +140,23 @@ def test_longdouble_model_equals_mpmath_model(name):
     t = jc.trajectory(name)
     errs, excl, _ = jc.check_states(name, [fr[3] for fr in t["frames"]])
     if name in jc.ORACLE_SCENES:
-        errs = np.maximum(errs, jc.check_states(name, [fr[1] for fr in t["frames"]])[0])
-    worst = int(np.where(excl, 0, errs).max(axis=1).argmax())
+        errs = [np.maximum(e, o) for e, o in zip(errs, jc.check_states(name, [fr[1] for fr in t["frames"]])[0])]
+    worst = int(np.argmax([np.where(x, 0, e).max() for e, x in zip(errs, excl)]))
     start, _, res, _ = t["frames"][worst]
     given = {key: m for key, m in res["manifolds"].items() if m["p_ref"]}
-    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [lifted(ref, p) for p in m["p_ref"]],
-                   "p_inc": [lifted(ref, p) for p in m["p_inc"]]} for key, m in given.items()}
+    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [xm.lifted(ref, p) for p in m["p_ref"]],
+                   "p_inc": [xm.lifted(ref, p) for p in m["p_inc"]]} for key, m in given.items()}
     a = jc.model(name, start, num=fast, manifolds=given)
     b = jc.model(name, start, num=ref, manifolds=exact)
     assert [(k, kind, err == 0) for k, kind, _, err in a["limits"]] == [(k, kind, err == 0) for k, kind, _, err in b["limits"]]
     assert np.array_equal(a["n_joint"], b["n_joint"]) and np.array_equal(a["mask"], b["mask"])
-    d = np.abs(ref.to_f64(lifted(ref, a["state"]) - b["state"]))
-    scale = pc.scales(start, fast.to_f64(a["state"]), t["ext"], jc.links(name, res))
+    d = np.abs(ref.to_f64(xm.lifted(ref, a["state"]) - b["state"]))
+    scale = pc.scales(start, fast.to_f64(a["state"]), t["ext"], xk.joint_links(t, res))
     turn = scale / t["ext"]
     h = t["h"]
     e = np.max(np.stack([d[:, 31:34].max(axis=1) / (pc.EPS * scale), d[:, 34:38].max(axis=1) / (pc.EPS * turn),
                          d[:, 22:25].max(axis=1) * h / (pc.EPS * scale), d[:, 25:28].max(axis=1) * h / (pc.EPS * turn)]), axis=0)
-    top = np.where(excl, 0, errs).max()
+    top = xk.worst(errs, excl)
     print("%s substep %d: longdouble against mpmath %.4f = %.2g of the bound; the scene's maximum %.1f" % (
         name, worst, e.max(), e.max() / jc.K_JOINTS, top))
     assert e.max() <= jc.K_JOINTS / 2 ** 11 and e.max() <= 0.1 * top
@@ -213,21 +208,6 @@ def free_pair(seed, kind):
     return bodies, jc.joints_of(rows), jc.limits_of(lims)
 
 
-def momenta(num, before, after, state0):
-    """Sum of m dx and of m x cross dx + I dtheta over the bodies, from the pose change of the Jacobi pass alone; dtheta is
-    twice the vector part of dq q^-1."""
-    lin, ang = 0, 0
-    for k in range(len(state0)):
-        m = 1.0 / state0[k, 0]
-        inv = state0[k, 1:10].reshape(3, 3).T
-        x0 = before[k, 31:34] + before[k, 28:31]
-        dx = after[k, 31:34] - before[k, 31:34]
-        dq = xm.qmul(after[k, 34:38][:, None], xm.conj(before[k, 34:38][:, None]))[:, 0]
-        lin = lin + dx * m
-        ang = ang + np.cross(x0, dx) * m + np.linalg.solve(inv, num.to_f64(dq[1:] * 2))
-    return num.to_f64(lin), num.to_f64(ang)
-
-
 @pytest.mark.parametrize("kind", ["rod", "ball", "hinge", "limits"])
 def test_model_conserves_momentum_on_a_free_jointed_pair(kind):
     """No gravity, no contact, bodies at rest: a joint's entries are +-lambda dir at two points of one line and +-lambda n
@@ -240,7 +220,7 @@ def test_model_conserves_momentum_on_a_free_jointed_pair(kind):
     res = pm.substep(bodies, pc.table()[1], np.zeros(2, dtype=np.uint32), pc.HS[1], {}, joints=joints, limits=lims)
     assert res["n_joint"].min() >= (3 if kind == "limits" else 2 if kind == "hinge" else 1) and not res["n_points"].any()
     before = num.conv(bodies)
-    lin, ang = momenta(num, before, res["state"], bodies)
+    lin, ang = xk.momenta(num, before, res["state"], bodies)
     moved = np.abs(num.to_f64(res["state"][:, 31:38] - before[:, 31:38])).max() / bodies[:, 0].min()
     assert moved > 1e-4
     assert np.abs(lin).max() <= 1e-15 * moved, (lin, moved)

@@ -7,12 +7,12 @@ import numpy as np
 import pytest
 
 import xprec_bounce_cases as bc
+import xprec_check as xk
 import xprec_model as xm
 import xprec_pairs_cases as pc
 import xprec_pairs_model as pm
 import xprec_sleep_cases as sc
 from golden_util import bits_equal
-from test_xprec_joints_oracle import lifted
 
 SCENE_NAMES = list(sc.SCENES)
 CHAIN_FRAMES = 4
@@ -32,8 +32,8 @@ def test_f64_reading_against_the_model_frame_by_frame(name):
     errs, excl, entry = sc.check_states(name, f64_states(name))
     x, c = np.concatenate(excl), np.concatenate(entry)
     print("%s: f64 evaluation %.1f; excluded %d of %d body-substeps, %d of %d with a sleeper's point" % (
-        name, sc.worst(errs, excl), x.sum(), x.size, (x & c).sum(), c.sum()))
-    sc.assert_caps(name, excl, entry)
+        name, xk.worst(errs, excl), x.sum(), x.size, (x & c).sum(), c.sum()))
+    xk.assert_caps(name, excl, entry, floor=sc.caps_floor(name))
     native = xm.native()
     for f, (start, want, res, s) in enumerate(t["frames"]):
         z = s["asleep"]
@@ -129,8 +129,8 @@ def test_longdouble_model_equals_mpmath_model(name):
     f = int(np.argmax(per_frame))
     start, _, res, s = t["frames"][f]
     given = {key: m for key, m in res["manifolds"].items() if m["p_ref"]}
-    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [lifted(ref, p) for p in m["p_ref"]],
-                   "p_inc": [lifted(ref, p) for p in m["p_inc"]], **({"normal": lifted(ref, m["normal"])} if "normal" in m else {})}
+    exact = {key: {"separated": False, "feature": m["feature"], "p_ref": [xm.lifted(ref, p) for p in m["p_ref"]],
+                   "p_inc": [xm.lifted(ref, p) for p in m["p_inc"]], **({"normal": xm.lifted(ref, m["normal"])} if "normal" in m else {})}
              for key, m in given.items()}
     a = sc.evaluate(s, num=fast, manifolds=given)
     b = sc.evaluate(s, num=ref, manifolds=exact)
@@ -138,7 +138,7 @@ def test_longdouble_model_equals_mpmath_model(name):
                 "cap_fired_angular"):
         if key in a:
             assert np.array_equal(a[key], b[key]), key
-    d = np.abs(ref.to_f64(lifted(ref, a["state"]) - b["state"]))
+    d = np.abs(ref.to_f64(xm.lifted(ref, a["state"]) - b["state"]))
     scale = pc.scales(start, fast.to_f64(a["state"]), s["ext"], list(res["manifolds"]))
     turn = scale / s["ext"]
     h = s["h"]
@@ -238,14 +238,15 @@ def test_gjk_manifolds_from_the_models_frames_cover_half_of_the_touching_bodies(
 
 # ---- frames of S substeps -------------------------------------------------------------------------------------------------------
 def chain_figures(name, substeps, mutation_at=None):
-    out = []
+    """(normalised errors, excluded, carries) of the f64 chain against the longdouble chain, lists over frames."""
+    errs, excl, entry = [], [], []
     for f in range(CHAIN_FRAMES):
         s = sc.build(name, f)
         res, x, c, links = sc.chain(s, s["bodies"], substeps)
         got, _, _, _ = sc.chain(s, s["bodies"], substeps, num=xm.f64(), mutation_at=mutation_at)
         e = sc.chain_errors(s, xm.f64().to_f64(got["state"]), res, s["bodies"], links, substeps)
-        out.append((e, x, c))
-    return out
+        errs.append(e), excl.append(x), entry.append(c)
+    return errs, excl, entry
 
 
 @pytest.mark.parametrize("substeps", sc.CHAIN_SUBSTEPS)
@@ -255,12 +256,12 @@ def test_the_f64_chain_stays_within_the_recorded_chain_bound(substeps):
     chained scenes; it is measured against the model only."""
     largest = 0.0
     for name in sc.CHAINED:
-        fig = chain_figures(name, substeps)
-        e = max(float(np.where(x, 0, e).max()) for e, x, _ in fig)
-        x, c = np.concatenate([x for _, x, _ in fig]), np.concatenate([c for _, _, c in fig])
+        errs, excl, entry = chain_figures(name, substeps)
+        e = xk.worst(errs, excl)
+        x, c = np.concatenate(excl), np.concatenate(entry)
         print("%s, S = %d: f64 chain against the longdouble chain %.1f; excluded %d of %d, %d of %d with a sleeper's point" % (
             name, substeps, e, x.sum(), x.size, (x & c).sum(), c.sum()))
-        assert x.mean() <= 0.10 and (x & c).sum() <= 0.10 * c.sum() and (c & ~x).sum() >= 20
+        xk.assert_caps(name, excl, entry)
         largest = max(largest, e)
     print("S = %d: largest %.2f, 8x = %.1f, K_SLEEP_CHAIN = %g" % (substeps, largest, 8 * largest, sc.K_SLEEP_CHAIN[substeps]))
     assert 8 * largest <= sc.K_SLEEP_CHAIN[substeps] <= 8.5 * largest
@@ -270,8 +271,8 @@ def test_a_stale_second_record_set_leaves_the_chain_bound():
     """S = 2: the second substep reads the sleeper's record from a pose integrated once -- what a second record set that was
     never rewritten looks like.  Invisible at S = 1 by construction."""
     name, recorded = STALE_SECOND_RECORD
-    fig = chain_figures(name, 2, mutation_at={1: "record_from_integrated"})
-    worst = max(float(np.where(x, 0, e).max()) for e, x, _ in fig) / sc.K_SLEEP_CHAIN[2]
+    errs, excl, _ = chain_figures(name, 2, mutation_at={1: "record_from_integrated"})
+    worst = xk.worst(errs, excl) / sc.K_SLEEP_CHAIN[2]
     print("a stale second record set on %s, S = 2: %.3g x K_SLEEP_CHAIN (recorded: %.2g)" % (name, worst, recorded))
     assert worst > 1.0
 

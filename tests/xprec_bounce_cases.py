@@ -47,13 +47,13 @@ import functools
 import numpy as np
 
 import edge_rigids as er
+import xprec_check as xk
 import xprec_drives_cases as dc
 import xprec_joints_cases as jc
 import xprec_model as xm
 import xprec_pairs_cases as pc
 import xprec_pairs_model as pm
 from constraint_solver_amd import capi
-from xprec_cases import TAU
 from xprec_pairs_cases import CUBE, GROUND_MU, HS, HULL16, HULL18, ICOSA, K_PAIRS, MUS, SLAB, TETRA
 
 # MEASURED, largest normalised error of a checked body-substep, f64 evaluation against the longdouble model, h = 1/1200 and 1/240:
@@ -544,18 +544,9 @@ def model(name, frame, state=None, num=None, mutation=None, tau=0.0, manifolds=N
                       bounce_threshold=s["threshold"] if bouncing else 0.0, terrain=terrain)
 
 
-def links(name, frame, res):
-    s = build(name, frame)
-    return list(res["manifolds"]) + [(int(j["body_a"]), int(j["body_b"])) for j in s["joints"]]
-
-
 def errors(name, frame, got, res):
     s = build(name, frame)
-    return pc.normalized_errors(got, res["state"], s["bodies"], s["ext"], s["h"], links(name, frame, res))
-
-
-def in_band(margin):
-    return (margin > 0) & (margin <= TAU)
+    return xk.scene_errors(s, got, res, s["bodies"])
 
 
 def excluded(res, exact=()):
@@ -575,7 +566,7 @@ def excluded(res, exact=()):
     for key in ("cell_margin", "diagonal_margin", "border_margin", "threshold_margin", "entry_margin", "bounce_cell_margin",
                 "bounce_diagonal_margin", "bounce_border_margin"):
         if key in res:
-            x = x | in_band(res[key])
+            x = x | xk.in_band(res[key])
     return x
 
 
@@ -625,46 +616,17 @@ def trajectory(name):
     chain = name.startswith("chain")        # the 40-body pile: 8 frames as in xprec_joints_cases.py, and the nudged evaluation on
     for f in range(jc.CHAIN_SUBSTEPS if chain else SUBSTEPS):    # the model's own manifolds, to keep its brute-force stage N to two
         s = build(name, f)
-        exact = list(s["exact"])
-        res = model(name, f, tau=TAU)
-        want = xm.f64().to_f64(model(name, f, num=xm.f64())["state"])
-        moved = model(name, f, state=jc.nudged(s["bodies"], f, exact), manifolds=res["manifolds"] if chain else None)
-        res["sensitivity"] = errors(name, f, xm.native().to_f64(moved["state"]), res)
-        if exact:                       # on an exact tie the stated rule decides; one ulp beside it the decision is another one
-            res["sensitivity"][exact] = 0.0
+        res, want = xk.model_frame(s, functools.partial(model, name, f), s["bodies"], f, s["exact"], nudge_on_res_manifolds=chain)
         out.append((s["bodies"], want, res, s))
     return {"h": SCENES[name][1], "frames": out}
 
 
-def check_states(name, got_states, k=None, model_results=None):
-    """got_states[f]: the state after frame f of an implementation under test.  Asserts the bound (bounds(), or k) on every
-    body-substep that is not excluded; returns (normalised errors, excluded, carries a stage-6 entry), each a list over frames of (n,) arrays."""
-    t = trajectory(name)
-    errs, excl, entry = [], [], []
-    for f, (start, _, res, s) in enumerate(t["frames"]):
-        m = res if model_results is None else model_results[f]
-        e = pc.normalized_errors(got_states[f], m["state"], start, s["ext"], s["h"], links(name, f, res))
-        x = excluded(res, s["exact"])
-        bound = bounds(res) if k is None else np.full(len(e), float(k))
-        bad = np.nonzero(~x & ~(e <= bound))[0]
-        assert not len(bad), "%s frame %d: bodies %s (%s) beyond K = %s: %s" % (name, f, bad[:8], s["labels"][bad[:8]], bound[bad[:8]], e[bad[:8]])
-        errs.append(e)
-        excl.append(x)
-        entry.append(carries(name, res))
-    return errs, excl, entry
-
-
-def worst(errs, excl):
-    return max(float(np.where(x, 0, e).max()) for e, x in zip(errs, excl))
-
-
-def assert_caps(name, excl, entry):
-    """At most 10 % of all body-substeps, and of those that carry a stage-6 entry (scene (g): a terrain contact), are excluded,
-    and at least 20 of the latter are checked."""
-    x, c = np.concatenate(excl), np.concatenate(entry)
-    assert x.mean() <= 0.10, (name, x.mean())
-    assert (x & c).sum() <= 0.10 * c.sum(), (name, (x & c).sum(), c.sum())
-    assert (c & ~x).sum() >= 20, (name, (c & ~x).sum())
+def check_states(name, got_states):
+    """got_states[f]: the state after frame f of an implementation under test.  Asserts bounds() on every body-substep that is
+    not excluded; returns (normalised errors, excluded, carries a stage-6 entry), each a list over frames of (n,) arrays."""
+    frames = [(start, res, s) for start, _, res, s in trajectory(name)["frames"]]
+    return xk.check_frames(name, frames, got_states, errors=xk.scene_errors, excluded=lambda res, s: excluded(res, s["exact"]),
+                           bound=bounds, carries=lambda res, s: carries(name, res))
 
 
 SEEN_BOTH_WAYS = {"a pair entry", "a ground entry", "a pushing visit", "a give-back visit", "a clamped wanted",

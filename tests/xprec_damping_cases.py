@@ -31,6 +31,7 @@ import functools
 import numpy as np
 
 import xprec_bounce_cases as bc
+import xprec_check as xk
 import xprec_drives_cases as dc
 import xprec_joints_cases as jc
 import xprec_model as xm
@@ -119,7 +120,7 @@ def with_caps(s, tag, bodies=None, seed=301):
         cap = np.where(np.isfinite(factors) & (speed > 0), factors * np.where(speed > 0, speed, 1.0), np.inf)
         rows["max_linear_speed"][chosen], rows["max_angular_speed"][chosen] = cap[chosen, 0], cap[chosen, 1]
         margin = evaluate(dict(s, rows=rows), num=xm.f64())["cap_margin"]
-        close = np.nonzero(bc.in_band(margin))[0]
+        close = np.nonzero(xk.in_band(margin))[0]
         if not len(close):
             break
         redrawn += len(close)
@@ -350,13 +351,9 @@ def model(name, frame, **kw):
     return evaluate(build(name, frame), **kw)
 
 
-def links(s, res):
-    return list(res["manifolds"]) + [(int(j["body_a"]), int(j["body_b"])) for j in s["joints"]]
-
-
 def errors(name, frame, got, res):
     s = build(name, frame)
-    return pc.normalized_errors(got, res["state"], s["bodies"], s["ext"], s["h"], links(s, res))
+    return xk.scene_errors(s, got, res, s["bodies"])
 
 
 def excluded(res, s):
@@ -366,10 +363,10 @@ def excluded(res, s):
     exclude nothing."""
     x = bc.excluded(res, s["exact"])
     if "cap_margin" in res:
-        x = x | bc.in_band(res["cap_margin"]) | ((res["damper_cond"] > 0) & (res["damper_cond"] < COND_MIN))
+        x = x | xk.in_band(res["cap_margin"]) | ((res["damper_cond"] > 0) & (res["damper_cond"] < COND_MIN))
     if "kin_flip_margin" in res:
         bad = (res["kin_flip_margin"] < FLIP_MIN) | (res["kin_tan_margin"] < TAU)
-        for i, j in links(s, res):
+        for i, j in xk.joint_links(s, res):
             if bad[i] or bad[j]:
                 x[i] = x[j] = True
         x = x | bad
@@ -407,35 +404,17 @@ def trajectory(name):
     chain = name.startswith("chain")
     for f in range(frames_of(name)):
         s = build(name, f)
-        exact = list(s["exact"])
-        res = model(name, f, tau=TAU)
-        want = xm.f64().to_f64(model(name, f, num=xm.f64())["state"])
-        moved = model(name, f, state=jc.nudged(s["bodies"], f, exact), manifolds=res["manifolds"] if chain else None)
-        res["sensitivity"] = errors(name, f, xm.native().to_f64(moved["state"]), res)
-        if exact:
-            res["sensitivity"][exact] = 0.0
+        res, want = xk.model_frame(s, functools.partial(evaluate, s), s["bodies"], f, s["exact"], nudge_on_res_manifolds=chain)
         out.append((s["bodies"], want, res, s))
     return {"h": SCENES[name][1], "frames": out}
 
 
-def check_states(name, got_states, k=None):
-    """got_states[f]: the state after frame f of an implementation under test.  Asserts the bound (bounds(), or k) on every
-    body-substep that is not excluded; returns (normalised errors, excluded, carries), each a list over frames of (n,) arrays."""
-    errs, excl, entry = [], [], []
-    for f, (start, _, res, s) in enumerate(trajectory(name)["frames"]):
-        e = errors(name, f, got_states[f], res)
-        x = excluded(res, s)
-        bound = bounds(res) if k is None else np.full(len(e), float(k))
-        bad = np.nonzero(~x & ~(e <= bound))[0]
-        assert not len(bad), "%s frame %d: bodies %s (%s) beyond K = %s: %s" % (name, f, bad[:8], s["labels"][bad[:8]], bound[bad[:8]], e[bad[:8]])
-        errs.append(e)
-        excl.append(x)
-        entry.append(carries(name, res, s))
-    return errs, excl, entry
-
-
-worst = bc.worst
-assert_caps = bc.assert_caps
+def check_states(name, got_states):
+    """got_states[f]: the state after frame f of an implementation under test.  Asserts bounds() on every body-substep that is
+    not excluded; returns (normalised errors, excluded, carries), each a list over frames of (n,) arrays."""
+    frames = [(start, res, s) for start, _, res, s in trajectory(name)["frames"]]
+    return xk.check_frames(name, frames, got_states, errors=xk.scene_errors, excluded=excluded, bound=bounds,
+                           carries=lambda res, s: carries(name, res, s))
 
 SEEN_BOTH_WAYS = {"a linear cap that fires", "a linear cap that does not fire", "an angular cap that fires",
                   "an angular cap that does not fire", "mu_l h below 1", "mu_l h at or above 1", "mu_a h below 1",

@@ -38,8 +38,8 @@ import functools
 
 import numpy as np
 
+import xprec_check as xk
 import xprec_joints_cases as jc
-import xprec_model as xm
 import xprec_pairs_cases as pc
 import xprec_pairs_model as pm
 from constraint_solver_amd import capi
@@ -375,14 +375,8 @@ def model(name, state, num=None, mutation=None, tau=0.0, manifolds=None, without
                       drives=NO_DRIVES if "drives" in without else s["drives"])
 
 
-def links(name, res):
-    s = build(name)
-    return list(res["manifolds"]) + [(int(j["body_a"]), int(j["body_b"])) for j in s["joints"]]
-
-
 def errors(name, got, res, start):
-    s = build(name)
-    return pc.normalized_errors(got, res["state"], start, s["ext"], s["h"], links(name, res))
+    return xk.scene_errors(build(name), got, res, start)
 
 
 def excluded(res):
@@ -391,7 +385,7 @@ def excluded(res):
     +-pi.  |r| of the perpendicular term is in joint_cond.  The clamp is continuous and excludes nothing."""
     x = jc.excluded(res)
     for key in ("slide_margin", "drive_margin"):
-        x = x | ((res[key] > 0) & (res[key] <= TAU))
+        x = x | xk.in_band(res[key])
     return x | (res["drive_wrap_margin"] <= TAU)
 
 
@@ -408,12 +402,7 @@ def trajectory(name):
         if exact and f and exact_now:
             state = state.copy()
             state[exact] = s["bodies"][exact]
-        res = model(name, state, tau=TAU)
-        want = xm.f64().to_f64(model(name, state, num=xm.f64())["state"])
-        moved = model(name, jc.nudged(state, f, exact if exact_now else ()))
-        res["sensitivity"] = errors(name, xm.native().to_f64(moved["state"]), res, state)
-        if exact_now:                   # on an exact tie the stated rule decides; one ulp beside it the decision is another one
-            res["sensitivity"][exact] = 0.0
+        res, want = xk.model_frame(s, functools.partial(model, name), state, f, exact if exact_now else ())
         out.append((state, want, res, want))
         state = want
     return dict(s, frames=out)
@@ -424,25 +413,13 @@ def both(res):
     return (res["n_extra"] > 0) & ((res["n_points"] > 0) | (res["mask"] != 0))
 
 
-def check_states(name, got_states, k=None, model_results=None):
+def check_states(name, got_states):
     """got_states[f]: the state after substep f of an implementation under test.  Asserts the bound on every body-substep
-    that is not excluded; returns (normalised errors, excluded, carries extra entry and contact point), each (frames, n)."""
+    that is not excluded; returns (normalised errors, excluded, carries extra entry and contact point), lists over frames."""
     t = trajectory(name)
-    k = K_DRIVES if k is None else k
-    errs, excl, mixed = [], [], []
-    for f, (start, _, res, _) in enumerate(t["frames"]):
-        m = res if model_results is None else model_results[f]
-        e = pc.normalized_errors(got_states[f], m["state"], start, t["ext"], t["h"], links(name, res))
-        x = excluded(res)
-        bad = np.nonzero(~x & ~(e <= k))[0]
-        assert not len(bad), "%s substep %d: bodies %s (%s) beyond K = %g: %s" % (name, f, bad[:8], t["labels"][bad[:8]], k, e[bad[:8]])
-        errs.append(e)
-        excl.append(x)
-        mixed.append(both(res))
-    return np.array(errs), np.array(excl), np.array(mixed)
-
-
-assert_caps = jc.assert_caps           # at most 10 % excluded, of all body-substeps and of >= 20 with extra entry and contact point
+    return xk.check_frames(name, [(start, res, t) for start, _, res, _ in t["frames"]], got_states, errors=xk.scene_errors,
+                           excluded=lambda res, scene: excluded(res), bound=lambda res: K_DRIVES,
+                           carries=lambda res, scene: both(res))
 
 
 def crossing(name):

@@ -34,7 +34,7 @@ import functools
 import numpy as np
 
 import oracle_binding as ob
-import xprec_cases as xc
+import xprec_check as xk
 import xprec_model as xm
 import xprec_pairs_cases as pc
 import xprec_pairs_model as pm
@@ -309,15 +309,8 @@ def oracle(name, state):
     return ob.contacts_step_joints(state, s["sid"], pc.table()[0], s["joints"], s["h"], 1, pc.PAD, max_depenetration_speed=s["speed"])
 
 
-def links(name, res):
-    """The body pairs that act on each other in the substep: touching pairs and joints."""
-    s = build(name)
-    return list(res["manifolds"]) + [(int(j["body_a"]), int(j["body_b"])) for j in s["joints"]]
-
-
 def errors(name, got, res, start):
-    s = build(name)
-    return pc.normalized_errors(got, res["state"], start, s["ext"], s["h"], links(name, res))
+    return xk.scene_errors(build(name), got, res, start)
 
 
 def excluded(res):
@@ -325,14 +318,7 @@ def excluded(res):
     stated rule decides: no entry) or within TAU of the wrap at +-pi, or a direction normalised by less than COND_MIN (s,
     |bisector|, |delta|, anchor distance; exactly 0 is the stated skip)."""
     x = pc.excluded(res)
-    margin = res["limit_margin"]
-    return x | ((margin > 0) & (margin <= TAU)) | (res["wrap_margin"] <= TAU) | (res["joint_cond"] < COND_MIN)
-
-
-def nudged(state, seed, exact):
-    out = xc.nudged(state, seed)
-    out[list(exact)] = state[list(exact)]
-    return out
+    return x | xk.in_band(res["limit_margin"]) | (res["wrap_margin"] <= TAU) | (res["joint_cond"] < COND_MIN)
 
 
 @functools.lru_cache(maxsize=None)
@@ -348,13 +334,8 @@ def trajectory(name):
         if exact and f and exact_now:
             state = state.copy()
             state[exact] = s["bodies"][exact]
-        res = model(name, state, tau=TAU)
-        plain = xm.f64().to_f64(model(name, state, num=xm.f64())["state"])
+        res, plain = xk.model_frame(s, functools.partial(model, name), state, f, exact if exact_now else ())
         want = oracle(name, state) if name in ORACLE_SCENES else plain
-        moved = model(name, nudged(state, f, exact if exact_now else ()))
-        res["sensitivity"] = errors(name, xm.native().to_f64(moved["state"]), res, state)
-        if exact_now:                   # on an exact tie the stated rule decides; one ulp beside it the decision is another one
-            res["sensitivity"][exact] = 0.0
         out.append((state, want, res, plain))
         state = want
     return dict(s, frames=out)
@@ -365,26 +346,10 @@ def both(res):
     return (res["n_joint"] > 0) & (res["n_points"] > 0)
 
 
-def check_states(name, got_states, k=None, model_results=None):
+def check_states(name, got_states):
     """got_states[f]: the state after substep f of an implementation under test.  Asserts the bound on every body-substep
-    that is not excluded; returns (normalised errors, excluded, carries joint entry and pair point), each (frames, n)."""
+    that is not excluded; returns (normalised errors, excluded, carries joint entry and pair point), lists over frames."""
     t = trajectory(name)
-    k = K_JOINTS if k is None else k
-    errs, excl, mixed = [], [], []
-    for f, (start, _, res, _) in enumerate(t["frames"]):
-        m = res if model_results is None else model_results[f]
-        e = pc.normalized_errors(got_states[f], m["state"], start, t["ext"], t["h"], links(name, res))
-        x = excluded(res)
-        bad = np.nonzero(~x & ~(e <= k))[0]
-        assert not len(bad), "%s substep %d: bodies %s (%s) beyond K = %g: %s" % (name, f, bad[:8], t["labels"][bad[:8]], k, e[bad[:8]])
-        errs.append(e)
-        excl.append(x)
-        mixed.append(both(res))
-    return np.array(errs), np.array(excl), np.array(mixed)
-
-
-def assert_caps(name, excl, mixed):
-    """At most 10 % of all body-substeps, and of those that carry both a joint entry and a pair point, are excluded."""
-    assert mixed.sum() >= 20, (name, mixed.sum())
-    assert excl.mean() <= 0.10, (name, excl.mean())
-    assert (excl & mixed).sum() <= 0.10 * mixed.sum(), (name, (excl & mixed).sum(), mixed.sum())
+    return xk.check_frames(name, [(start, res, t) for start, _, res, _ in t["frames"]], got_states, errors=xk.scene_errors,
+                           excluded=lambda res, scene: excluded(res), bound=lambda res: K_JOINTS,
+                           carries=lambda res, scene: both(res))

@@ -56,6 +56,13 @@ def native():
     return longdouble() if np.finfo(np.longdouble).nmant >= 63 else mp(40)
 
 
+def lifted(ref, a):
+    """A longdouble array in another scalar type, exactly: two doubles."""
+    hi = np.asarray(a).astype(np.float64)
+    lo = (a - hi.astype(a.dtype)).astype(np.float64)
+    return ref.conv(hi) + ref.conv(lo)
+
+
 # ---- cgmath semantics (cgmath 0.18: Vector3, Quaternion, Matrix3) ---------------------------------------------------
 def dot(a, b):
     return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]

@@ -26,6 +26,7 @@ import functools
 import numpy as np
 
 import xprec_bounce_cases as bc
+import xprec_check as xk
 import xprec_damping_cases as dcs
 import xprec_joints_cases as jc
 import xprec_model as xm
@@ -264,7 +265,7 @@ def evaluate(s, state=None, num=None, mutation=None, tau=0.0, manifolds=None, as
 
 
 def errors(s, got, res, start=None):
-    return pc.normalized_errors(got, res["state"], s["bodies"] if start is None else start, s["ext"], s["h"], list(res["manifolds"]))
+    return xk.scene_errors(s, got, res, s["bodies"] if start is None else start)          # no joints: the links are the manifolds
 
 
 def excluded(res, s):
@@ -274,7 +275,6 @@ def excluded(res, s):
 
 
 bounds = bc.bounds
-worst = bc.worst
 
 
 def carries(res):
@@ -282,15 +282,14 @@ def carries(res):
     return (res["n_sleeper_points"] > 0) & ~res["asleep"]
 
 
+def caps_floor(name):
+    """xprec_check.assert_caps' floor: the exact scene, asserted by name, has none."""
+    return 0 if name.startswith("exact") else 20
+
+
 def frame_result(s, start, seed):
     """The longdouble model's result of the scene's substep from `start`, with its one-ulp sensitivity."""
-    exact = list(s["exact"])
-    res = evaluate(s, state=start, tau=TAU)
-    moved = evaluate(s, state=jc.nudged(start, seed, exact))
-    res["sensitivity"] = errors(s, xm.native().to_f64(moved["state"]), res, start)
-    if exact:
-        res["sensitivity"][exact] = 0.0
-    return res
+    return xk.model_frame(s, functools.partial(evaluate, s), start, seed, s["exact"], want=False)[0]
 
 
 @functools.lru_cache(maxsize=None)
@@ -300,40 +299,18 @@ def trajectory(name):
     out = []
     for f in range(FRAMES):
         s = build(name, f)
-        res = frame_result(s, s["bodies"], f)
-        want = xm.f64().to_f64(evaluate(s, num=xm.f64())["state"])
+        res, want = xk.model_frame(s, functools.partial(evaluate, s), s["bodies"], f, s["exact"])
         out.append((s["bodies"], want, res, s))
     return {"h": SCENES[name][1], "frames": out}
 
 
-def check_frames(name, frames, got_states, k=None):
-    """frames: [(start, _, res, scene)]; got_states[f]: the state after frame f of an implementation under test.  Asserts the
-    bound (bounds(), or k) on every body-substep that is not excluded -- a sleeper's model state is its input, so a sleeper
-    is held to it as well; returns (normalised errors, excluded, carries), each a list over frames of (n,) arrays."""
-    errs, excl, entry = [], [], []
-    for f, (start, _, res, s) in enumerate(frames):
-        e = errors(s, got_states[f], res, start)
-        x = excluded(res, s)
-        bound = bounds(res) if k is None else np.full(len(e), float(k))
-        bad = np.nonzero(~x & ~(e <= bound))[0]
-        assert not len(bad), "%s frame %d: bodies %s (%s) beyond K = %s: %s" % (name, f, bad[:8], s["labels"][bad[:8]], bound[bad[:8]], e[bad[:8]])
-        errs.append(e)
-        excl.append(x)
-        entry.append(carries(res))
-    return errs, excl, entry
-
-
-def check_states(name, got_states, k=None):
-    return check_frames(name, trajectory(name)["frames"], got_states, k)
-
-
-def assert_caps(name, excl, entry):
-    """At most 10 % of all body-substeps, and of those with a sleeper's point, are excluded, and at least 20 of the latter are
-    checked (the exact scene, asserted by name, has no floor)."""
-    x, c = np.concatenate(excl), np.concatenate(entry)
-    assert x.mean() <= 0.10, (name, x.mean())
-    assert (x & c).sum() <= 0.10 * c.sum(), (name, (x & c).sum(), c.sum())
-    assert name.startswith("exact") or (c & ~x).sum() >= 20, (name, (c & ~x).sum())
+def check_states(name, got_states):
+    """got_states[f]: the state after frame f of an implementation under test.  Asserts bounds() on every body-substep that is
+    not excluded -- a sleeper's model state is its input, so a sleeper is held to it as well; returns (normalised errors,
+    excluded, carries), each a list over frames of (n,) arrays."""
+    frames = [(start, res, s) for start, _, res, s in trajectory(name)["frames"]]
+    return xk.check_frames(name, frames, got_states, errors=xk.scene_errors, excluded=excluded, bound=bounds,
+                           carries=lambda res, s: carries(res))
 
 
 # ---- GJK + EPA ------------------------------------------------------------------------------------------------------------------
